@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — CG mat-vecs/s on the L=16, Ntau=160 Holstein square lattice (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--nrhs R] [--precond]
+    python bench.py --gpus N --steps K --warmup W [--nrhs R] [--precond] [--dump-outputs DIR] [--full]
 
 A *step* is one conjugate-gradient iteration (1 MtM apply = 2 mat-vecs, + the vector updates and the reductions; + 1 KPM apply with
 --precond) advanced for a batch of `nrhs` right-hand sides resident in HBM.  Default batch: 144 independent Markov chains per GPU
@@ -9,16 +9,23 @@ A *step* is one conjugate-gradient iteration (1 MtM apply = 2 mat-vecs, + the ve
 x the 2 pseudofermion solves of one HMC force evaluation each (HMC.jl:851-886) = 288 right-hand sides.  Un-preconditioned solves
 run as the workgroup-resident kernel (csrc/cg_wg.hip: the whole solve in one launch), so the K timed steps are ONE launch of it.
 W untimed warm-up steps, then exactly K steps bracketed by barrier + device synchronise on both sides; the time is the MAX over
-ranks and value = (2 * nrhs * K * n_gpus) / time.  One JSON line on rank 0.
+ranks and value = (2 * nrhs * K * n_gpus) / time; ms_per_step = time / K.  One JSON line on rank 0.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  --full adds everything else the line used to carry
+(the roofline legs, the preconditioned and other-batch measurements, the other lattices, HMC updates, the CPU baselines and, with N > 1,
+the `spatial` sub-record); --no-cpu / --no-sweep / --no-spatial switch parts of --full off.
+--dump-outputs DIR writes what the timed path computed: DIR/x.npy (float64), the solution block x after the K timed iterations of a fixed,
+seeded sample of the right-hand sides (rank 0; the rows as listed in DIR/x_rows.npy, at most 32 MiB in all).  With the same arguments
+the inputs are the same from run to run, so two builds can be compared output for output.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): every GPU carries its own chains — no data-path collective, "weak"
-scaling (SURVEY.md §8e replica mode) — that is `value`.  The same run then records the north_star's OTHER curve as the sub-record
+scaling (SURVEY.md §8e replica mode) — that is `value`.  With --full the same run then records the north_star's OTHER curve as the sub-record
 `spatial`: ONE solve of configs C, D and E sharded over the N ranks (row slabs + ghost rows, device-initiated mailbox stores, the
 in-library path of csrc/shard.hip) with its device time per iteration, mat-vecs/s, fraction of the f64 roof of the N GPUs, the rank
 count RCCL sees and the peer-access matrix.  `--mode spatial` makes that solve (of --config) the headline line instead: strong
-scaling, latency-bound at these sizes; its line carries `roofline` and, on one rank, `cpu_baseline` too.
+scaling, latency-bound at these sizes; its line carries `roofline` and, with --full on one rank, `cpu_baseline` too.
 
-The JSON line (the driver's record keeps SCALARS of `roofline` and `cpu_baseline` only, so everything that matters is a flat key):
+The JSON line of --full (the driver's record keeps SCALARS of `roofline` and `cpu_baseline` only, so everything that matters is a flat key):
   roofline      the dominant kernel of the timed region.  Resident kernel: bound = "f64_vector+sync" — achieved = flops of the launch
                 (2 mat-vecs x (2 Ndim + 6 Ltau Nbonds) + 10 Ndim per right-hand side and iteration) / launch duration
                 against the 78.6 TFLOP/s f64 vector peak; its HBM fraction (small by design: the Krylov vectors stay on chip) is
@@ -85,9 +92,14 @@ def parse():
     ap.add_argument("--config", default="C", help="BASELINE config tag (C = Holstein square L=16 Ltau=160)")
     ap.add_argument("--precond", action="store_true", help="KPM (tau-FFT) preconditioned CG iteration")
     ap.add_argument("--streaming", action="store_true", help="time the two-kernel (HBM-streaming) iteration instead of the workgroup-resident kernel")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the secondary nrhs sweep")
-    ap.add_argument("--no-spatial", action="store_true", help="skip the `spatial` sub-record (sharded solves of C, D, E over the ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every secondary measurement: roofline legs, other batches / lattices / forms, HMC updates, "
+                         "CPU baselines, the `spatial` sub-record (a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (chains mode, rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip the secondary nrhs sweep")
+    ap.add_argument("--no-spatial", action="store_true", help="--full: skip the `spatial` sub-record (sharded solves of C, D, E over the ranks)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
     ap.add_argument("--hmc-seconds", type=float, default=6.0, help="wall time of the back-to-back HMC updates of the 64-chain leg")
     return ap.parse_args()
@@ -134,6 +146,8 @@ def dry_line(args, comm):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.mode == "spatial":
+        raise SystemExit("--dump-outputs: the chains mode only (the sharded solve of --mode spatial keeps its x on the ranks)")
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) <= 1:
         self_launch(args)              # does not return
     rpp = max(1, args.ranks_per_proc) if args.mode == "spatial" else 1
@@ -231,6 +245,8 @@ def main():
     check(lib.elph_synchronize(m._h))
     elapsed, matvecs = edist.timed_steps(comm, run_steps, K)
     ms_events = ev["ms"]
+    if args.dump_outputs and rank == 0:       # before anything else re-prepares the handle (that zeroes x)
+        dump_outputs(args.dump_outputs, lib, m, nrhs)
     fz_timed = C.c_int(0)                    # which form of the preconditioned iteration the timed region ran (0 unfused, 1 / 2 p/x-fused: lane program / registers)
     if args.precond:
         check(lib.elph_bench_px_info(m._h, C.byref(fz_timed)))
@@ -270,6 +286,7 @@ def main():
             "build_info": lib.elph_build_info().decode(),
         }
 
+    if rank == 0 and args.full:
         # ---- roofline ------------------------------------------------------------------------------------------------------------
         # (1) the two-kernel STREAMING iteration at the same batch: k_cg_ap and k_cg_xr timed alone with HIP events on their stream,
         #     priced on the compulsory bytes of each kernel as built against the HBM peak
@@ -739,7 +756,7 @@ def main():
     # ---- the north_star's other curve: ONE solve of configs C, D, E sharded over the N ranks (all ranks take part; N = 1 included as
     # the first point of the 1 / 2 / 4 / 8 series unless the secondary measurements are off)
     spatial = None
-    if not args.no_spatial and (world > 1 or not args.no_sweep):
+    if args.full and not args.no_spatial and (world > 1 or not args.no_sweep):
         spatial = spatial_records(comm, args.spatial_steps, cpu=False)
     if rank == 0:
         if spatial is not None:
@@ -755,9 +772,29 @@ def main():
                     flat.setdefault("spatial_devices", len(rec.get("devices") or []))
             out.update(flat)
             out["roofline"].update(flat)
-        out["roofline"] = order_roofline(out["roofline"])
+        if "roofline" in out:
+            out["roofline"] = order_roofline(out["roofline"])
         print(json.dumps(out))
     comm.close()
+
+
+DUMP_MAX_BYTES = 32 << 20       # --dump-outputs: at most this much of x (whole right-hand sides, a seeded sample beyond it)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, lib, m, nrhs):
+    """--dump-outputs: the solution block x the timed steps left on the device (elph_bench_get_x: what a solve of the batch hands its caller),
+    reference layout, as DIR/x.npy (float64, rows x Ndim); beyond DUMP_MAX_BYTES a fixed, seeded sample of the right-hand sides, whose
+    indices go to DIR/x_rows.npy."""
+    import numpy as np
+    from elphdynamics_amd import _lib
+    X = np.empty((nrhs, m.Ndim))
+    _lib.check(lib.elph_bench_get_x(m._h, nrhs, _lib.dptr(X)))
+    keep = max(1, min(nrhs, DUMP_MAX_BYTES // (8 * m.Ndim)))
+    rows = np.arange(nrhs) if keep == nrhs else np.sort(np.random.default_rng(DUMP_SEED).choice(nrhs, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), np.ascontiguousarray(X[rows]))
+    np.save(os.path.join(out_dir, "x_rows.npy"), rows.astype(np.float64))
 
 
 # The driver's record keeps the FIRST two dozen scalars of `roofline` (and drops every non-standard top-level key): what must survive
@@ -949,7 +986,7 @@ def main_sharded(args, comm):
                "roofline": {k: rec[k] for k in ("bound", "achieved", "peak", "unit", "frac", "hbm_streaming_equivalent_frac")} |
                            {"kernel": "k_cg_wg<SHARD>", "traffic": None, "ranks": rec["ranks"], "rccl_ranks": rec["rccl_ranks"]},
                "spatial": {args.config: rec}}
-        if not args.no_cpu and comm.world >= 1:
+        if args.full and not args.no_cpu and comm.world >= 1:
             out["cpu_baseline"] = cpu_baseline_leg(args.config, args.cpu_seconds)
         print(json.dumps(out))
     comm.close()

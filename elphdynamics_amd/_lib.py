@@ -122,6 +122,7 @@ BENCH_SIGNATURES = {
     "elph_shard_iterate": (c_int, [Handle, P_dbl, c_i64, P_dbl]),
     "elph_bench_prepare": (c_int, [Handle, c_int, c_int, P_dbl]),
     "elph_bench_run": (c_int, [Handle, c_int, c_int, c_int, c_int, P_dbl]),
+    "elph_bench_get_x": (c_int, [Handle, c_int, P_dbl]),
     "elph_bench_info": (c_int, [Handle, c_int, P_int]),
     "elph_bench_wg_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_px_info": (c_int, [Handle, P_int]),

@@ -2097,6 +2097,15 @@ extern "C" int elph_bench_prepare(elph_handle h, int what, int nrhs, const doubl
     return ELPH_OK;
 }
 
+extern "C" int elph_bench_get_x(elph_handle h, int nrhs, double *X) {
+    CHECK_H(h);
+    if (nrhs < 1 || nrhs > h->cap_rhs || !X) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    RC(elph_launch_s2r(h, h->d_stage_out, h->d_x, nrhs));
+    HIPCHK(hipMemcpyAsync(X, h->d_stage_out, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ELPH_OK;
+}
+
 extern "C" int elph_bench_info(elph_handle h, int nrhs, int *slices_per_wave) {
     CHECK_H(h);
     if (nrhs < 1 || !slices_per_wave) { elph_set_error("bad argument"); return ELPH_E_ARG; }

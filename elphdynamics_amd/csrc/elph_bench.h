@@ -27,6 +27,9 @@ extern "C" {
  *   stream, synchronises, and returns the event time in ms (total, not per rep). */
 int elph_bench_prepare(elph_handle h, int what, int nrhs, const double *B);
 int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int use_graph, double *ms_total);
+/* The solution block x the last elph_bench_run left on the device (nrhs right-hand sides, reference layout, nrhs*ndim doubles) copied to X:
+ * what a solve of the batch hands its caller.  The two-kernel forms apply x += alpha p one iteration late (in the next k_cg_ap). */
+int elph_bench_get_x(elph_handle h, int nrhs, double *X);
 /* Which k_cg_ap variant a batch of nrhs uses: *slices_per_wave = 1 (k_cg_ap_fast / generic) or T (k_cg_ap_chunk<T>). */
 int elph_bench_info(elph_handle h, int nrhs, int *slices_per_wave);
 /* Whether un-preconditioned solves of a batch of nrhs right-hand sides run as the workgroup-resident kernel (*usable = 1) and

@@ -8,11 +8,14 @@ own model values (registry of device handles, no wrapper type), so each of those
     reference's method through `invoke` when the model is not attached.
 Also checked: no subtype of AbstractModel is declared, no reference method is overwritten (no added signature equals a reference
 signature), every `ccall` matches the prototype in include/elph_gpu.h (symbol, arity, argument types, return type), block keywords
-balance, every name imported from a reference module is defined there.  When /root/reference is present (the build container) the
-committed signature list is re-derived from the sources and must be identical.
+balance, every name imported from a reference module is defined there.  What these checks need to know about the reference's sources
+(function headers, struct fields, defined names, include order) is stored in tests/golden/julia_reference_facts.json, derived from the
+sources by reference_facts() below: `python tests/test_julia_dispatch.py <reference src dir>` writes it again.
 """
+import json
 import os
 import re
+import sys
 
 import pytest
 
@@ -20,7 +23,7 @@ from conftest import ROOT
 
 JL = os.path.join(ROOT, "julia", "ElPhGPU.jl")
 HDR = os.path.join(ROOT, "include", "elph_gpu.h")
-REF = "/root/reference/src"
+FACTS = os.path.join(ROOT, "tests", "golden", "julia_reference_facts.json")
 
 # every `function NAME(... ::HolsteinModel / ::SSHModel ...)` of the reference: (name, file, line)
 CONCRETE_SIGNATURES = [
@@ -144,18 +147,16 @@ def _functions(code):
     return out
 
 
-def test_signature_list_is_the_reference(jl):
-    """The committed list equals what the reference's sources say (checked where the reference is present)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources not on this machine")
-    found = []
-    for f in sorted(os.listdir(REF)):
-        if not f.endswith(".jl"):
-            continue
-        for ln, line in enumerate(open(os.path.join(REF, f), encoding="utf-8"), 1):
-            m = re.match(r"^ *function ([^\s(]+)\(.*::(HolsteinModel|SSHModel)", line)
-            if m:
-                found.append((m.group(1), f, ln))
+@pytest.fixture(scope="module")
+def ref():
+    """The facts of the reference's sources (tests/golden/julia_reference_facts.json, written by reference_facts())."""
+    with open(FACTS, encoding="utf-8") as f:
+        return json.load(f)
+
+
+def test_signature_list_is_the_reference(jl, ref):
+    """The committed list equals what the reference's sources say."""
+    found = [tuple(s) for s in ref["concrete_signatures"]]
     assert sorted(found) == sorted(CONCRETE_SIGNATURES)
     outside = [s for s in CONCRETE_SIGNATURES if s[1] not in ("HolsteinModels.jl", "SSHModels.jl")]
     assert len(outside) == 33            # the callers the round-4 wrapper type lost
@@ -193,23 +194,23 @@ def test_added_methods_are_more_specific_and_fall_back(code):
     assert "const GPUModel = Union{HolsteinModel{Float64,Float64},SSHModel{Float64,Float64}}" in code
 
 
-def test_imported_names_exist_in_the_reference(code):
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources not on this machine")
+def test_imported_names_exist_in_the_reference(code, ref):
     files = {"Utilities": "Utilities.jl", "IterativeSolvers": "IterativeSolvers.jl", "Models": ("Models.jl", "HolsteinModels.jl", "SSHModels.jl"),
              "KPMPreconditioners": "KPMPreconditioners.jl", "FourierAcceleration": "FourierAcceleration.jl", "HMC": "HMC.jl"}
+    seen = 0
     for m in re.finditer(r"^(?:using|import)\s+\.\.(\w+):\s*(.+)$", code, re.M):
         mod, names = m.group(1), [x.strip() for x in m.group(2).split(",")]
         fs = files[mod] if isinstance(files[mod], tuple) else (files[mod],)
-        text = "".join(open(os.path.join(REF, f), encoding="utf-8").read() for f in fs)
+        defined = set().union(*(ref["defined_names"][f] for f in fs))
         for nm in names:
-            assert re.search(r"(function|struct|abstract type)\s+" + re.escape(nm) + r"(?![\w!])", text) or re.search(r"^" + re.escape(nm) + r"\s*=", text, re.M), (mod, nm)
+            assert nm in defined, (mod, nm)
+            seen += 1
+    assert seen >= 10
     # the include order the header comment prescribes puts this file after every module it names
-    order = re.findall(r'include\("(\w+)\.jl"\)', open(os.path.join(REF, "ElPhDynamics.jl"), encoding="utf-8").read())
+    order = ref["include_order"]
     assert order.index("HMC") < order.index("ProcessInputFile") and order[-1] == "ProcessInputFile"
     for name, (f, ln) in ABSTRACT_SPECIALISED.items():
-        lines = open(os.path.join(REF, f), encoding="utf-8").read().split("\n")
-        assert re.match(r"\s*function\s+" + re.escape(name) + r"\(", lines[ln - 1]), (name, f, ln, lines[ln - 1])
+        assert ref["function_lines"][f].get(str(ln)) == name, (name, f, ln, ref["function_lines"][f].get(str(ln)))
 
 
 C2JL = {"elph_handle": {"Ptr{Cvoid}"}, "elph_handle*": {"Ref{Ptr{Cvoid}}"}, "int": {"Cint"}, "int64_t": {"Int64"}, "double": {"Float64"},
@@ -333,21 +334,19 @@ def _struct_fields(path, name):
     return set(fields)
 
 
-def test_every_field_the_binding_touches_exists_in_the_reference(code):
+def test_every_field_the_binding_touches_exists_in_the_reference(code, ref):
     """The binding has never been executed: a mistyped field name would only show in Julia.  Here every `var.field` on a variable that holds
     a reference object (by the naming convention of the file: m / model, hmc, op, P, fa, cg, and `.solver`) is looked up in the struct
     definitions of the reference's sources."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources not on this machine")
-    j = lambda f: os.path.join(REF, f)      # noqa: E731
-    model = _struct_fields(j("HolsteinModels.jl"), "HolsteinModel") | _struct_fields(j("SSHModels.jl"), "SSHModel")
+    j = lambda f, name: set(ref["struct_fields"][f][name])      # noqa: E731
+    model = j("HolsteinModels.jl", "HolsteinModel") | j("SSHModels.jl", "SSHModel")
     fields = {
         "m": model, "model": model,
-        "hmc": _struct_fields(j("HMC.jl"), "HybridMonteCarlo"),
-        "op": _struct_fields(j("KPMPreconditioners.jl"), "KPMExpansion"),
-        "P": _struct_fields(j("KPMPreconditioners.jl"), "SymmetricKPMPreconditioner"),
-        "fa": _struct_fields(j("FourierAcceleration.jl"), "FourierAccelerator"),
-        "cg": _struct_fields(j("IterativeSolvers.jl"), "ConjugateGradient"),
+        "hmc": j("HMC.jl", "HybridMonteCarlo"),
+        "op": j("KPMPreconditioners.jl", "KPMExpansion"),
+        "P": j("KPMPreconditioners.jl", "SymmetricKPMPreconditioner"),
+        "fa": j("FourierAcceleration.jl", "FourierAccelerator"),
+        "cg": j("IterativeSolvers.jl", "ConjugateGradient"),
     }
     assert {"x", "expnΔτV", "cosht", "neighbor_table", "solver", "rng", "v′", "primary_field", "inv_checkerboard_perm", "bond_to_phonon"} <= model
     assert {"Λϕ₊", "O⁻¹Λϕ₋", "ϕ₊", "iters"} <= fields["hmc"] and {"λ_lo", "order", "model", "n", "buf", "c1", "c2", "active"} <= fields["op"]
@@ -378,7 +377,7 @@ def test_every_field_the_binding_touches_exists_in_the_reference(code):
 import julia_types as JT  # noqa: E402
 
 # the reference's methods of every function the binding invokes: (name, file, line, header).  Interface declarations only (no bodies);
-# re-derived from /root/reference/src when it is present (test_reference_method_table_is_current).
+# checked against the stored facts of the reference's sources (test_reference_method_table_is_current).
 INVOKED = ["update_model!", "mulM!", "mulMᵀ!", "mulMᵀM!", "mulMMᵀ!", "muldMdx!", "ldiv!", "solve!", "setup!", "calc_O⁻¹Λϕ!", "update!",
            "fourier_accelerate!"]
 # a name can belong to different generic functions in different modules: the files whose methods extend the function the binding imports
@@ -432,30 +431,25 @@ def _headers_of(src):
     return out
 
 
-def test_reference_method_table_is_current():
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources not on this machine")
+def test_reference_method_table_is_current(ref):
     found = []
-    for f in sorted(os.listdir(REF)):
-        if not f.endswith(".jl"):
-            continue
-        for name, ln, hdr in _headers_of(open(os.path.join(REF, f), encoding="utf-8").read()):
-            if name in INVOKED and f in OWNER_FILES.get(name, {f}) and not any(k in hdr for k in SKIPPED_HEADERS):
-                found.append((name, f, ln, hdr))
+    for name, f, ln, hdr in ref["invoked_headers"]:
+        if f in OWNER_FILES.get(name, {f}) and not any(k in hdr for k in SKIPPED_HEADERS):
+            found.append((name, f, ln, hdr))
     assert sorted(found) == sorted(REF_METHODS)
 
 
-def test_declarations_are_the_reference():
+DECLARED = ("IterativeSolver", "ConjugateGradient", "AbstractModel", "HolsteinModel", "SSHModel", "KPMPreconditioner",
+            "SymmetricKPMPreconditioner", "KPMExpansion", "HybridMonteCarlo", "FourierAccelerator")
+
+
+def test_declarations_are_the_reference(ref):
     """The struct / abstract-type headers tests/julia_types.py works from are the reference's (parameters, bounds, supertype)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources not on this machine")
-    text = "".join(open(os.path.join(REF, f), encoding="utf-8").read() for f in sorted(os.listdir(REF)) if f.endswith(".jl"))
-    for name in ("IterativeSolver", "ConjugateGradient", "AbstractModel", "HolsteinModel", "SSHModel", "KPMPreconditioner",
-                 "SymmetricKPMPreconditioner", "KPMExpansion", "HybridMonteCarlo", "FourierAccelerator"):
-        m = re.search(r"^(?:mutable\s+)?(?:struct|abstract type)\s+" + name + r"\{([^}]*)\}(?:\s*<:\s*(\S+))?", text, re.M)
-        assert m, name
+    for name in DECLARED:
+        assert name in ref["declarations"], name
+        m_params, m_super = ref["declarations"][name]
         params = []
-        for p in JT.split_top(m.group(1)):
+        for p in JT.split_top(m_params):
             nm, _, b = p.partition("<:")
             params.append((nm.strip(), b.strip() or None))
         decl, sup = JT.DECLS[name]
@@ -464,8 +458,49 @@ def test_declarations_are_the_reference():
             if name == "FourierAccelerator" and pn != "T":
                 continue                 # FFT plan types: never constrained by a signature on the path
             assert db == pb, (name, dn, db, pb)
-        assert (sup or "Any") == (m.group(2) or "Any"), (name, sup, m.group(2))
-    assert re.search(r"^Continuous = Union\{AbstractFloat,Complex\{<:AbstractFloat\}\}", text, re.M)
+        assert (sup or "Any") == (m_super or "Any"), (name, sup, m_super)
+    assert ref["continuous_union"]
+
+
+# ---- the facts of the reference's sources the checks above read ----------------------------------------------------------------------------
+
+def reference_facts(src):
+    """What the checks of this file need to know about the reference's Julia sources in directory `src`, as JSON-ready data."""
+    files = sorted(f for f in os.listdir(src) if f.endswith(".jl"))
+    read = lambda f: open(os.path.join(src, f), encoding="utf-8").read()      # noqa: E731
+    facts = {"concrete_signatures": [], "defined_names": {}, "function_lines": {}, "struct_fields": {}, "invoked_headers": [],
+             "declarations": {}}
+    for f in files:
+        text = read(f)
+        for ln, line in enumerate(text.split("\n"), 1):
+            m = re.match(r"^ *function ([^\s(]+)\(.*::(HolsteinModel|SSHModel)", line)
+            if m:
+                facts["concrete_signatures"].append([m.group(1), f, ln])
+        names = set(re.findall(r"(?:function|struct|abstract type)\s+([^\s(){}\[\]<:;,=]+)", text))
+        names |= set(re.findall(r"^([^\s=]+)\s*=", text, re.M))
+        facts["defined_names"][f] = sorted(names)
+        facts["function_lines"][f] = {str(ln): m.group(1) for ln, line in enumerate(text.split("\n"), 1)
+                                      for m in [re.match(r"\s*function\s+([^\s(]+)\(", line)] if m}
+        structs = re.findall(r"^(?:mutable\s+)?struct\s+(\w+)\b", text, re.M)
+        if structs:
+            facts["struct_fields"][f] = {s: sorted(_struct_fields(os.path.join(src, f), s)) for s in structs}
+        for name, ln, hdr in _headers_of(text):
+            if name in INVOKED:
+                facts["invoked_headers"].append([name, f, ln, hdr])
+    text = "".join(read(f) for f in files)
+    for name in DECLARED:
+        m = re.search(r"^(?:mutable\s+)?(?:struct|abstract type)\s+" + name + r"\{([^}]*)\}(?:\s*<:\s*(\S+))?", text, re.M)
+        if m:
+            facts["declarations"][name] = [m.group(1), m.group(2)]
+    facts["continuous_union"] = bool(re.search(r"^Continuous = Union\{AbstractFloat,Complex\{<:AbstractFloat\}\}", text, re.M))
+    facts["include_order"] = re.findall(r'include\("(\w+)\.jl"\)', read("ElPhDynamics.jl"))
+    return facts
+
+
+if __name__ == "__main__":      # python tests/test_julia_dispatch.py <reference src dir>: rewrite the stored facts
+    with open(FACTS, "w", encoding="utf-8") as g:
+        json.dump(reference_facts(sys.argv[1]), g, ensure_ascii=False, indent=1, sort_keys=True)
+        g.write("\n")
 
 
 def _binding_methods(code):

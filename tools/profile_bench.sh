@@ -15,10 +15,10 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B=$GRAFT_REPO_ROOT/bench.py
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $B --steps 1600 --warmup 0 --no-cpu --no-sweep $EXTRA > $OUT/bench_trace.json 2> $OUT/bench_trace.err
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $B --steps 160 --warmup 0 --no-cpu --no-sweep $EXTRA > $OUT/bench_pmc.json 2> $OUT/pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $B --steps 160 --warmup 0 --no-cpu --no-sweep $EXTRA > /dev/null 2> $OUT/pmc_write.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_kpm -- python3 $B --precond --steps 320 --warmup 32 --no-cpu --no-sweep $EXTRA > $OUT/bench_trace_kpm.json 2> $OUT/bench_trace_kpm.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $B --steps 1600 --warmup 0 --full --no-cpu --no-sweep $EXTRA > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $B --steps 160 --warmup 0 --full --no-cpu --no-sweep $EXTRA > $OUT/bench_pmc.json 2> $OUT/pmc_fetch.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $B --steps 160 --warmup 0 --full --no-cpu --no-sweep $EXTRA > /dev/null 2> $OUT/pmc_write.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_kpm -- python3 $B --precond --steps 320 --warmup 32 --full --no-cpu --no-sweep $EXTRA > $OUT/bench_trace_kpm.json 2> $OUT/bench_trace_kpm.err
 for d in trace pmc_fetch pmc_write trace_kpm; do
     n=$(find $OUT/$d -name '*.csv' | wc -l)
     if [ "$n" -lt 1 ]; then echo "profile_bench: rocprofv3 pass '$d' produced no csv (see $OUT/*.err)" >&2; exit 1; fi
