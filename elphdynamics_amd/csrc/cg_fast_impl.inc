@@ -855,115 +855,6 @@ __global__ void __launch_bounds__(WAVE) k_cg_xr_fast(CgBufs B, int N, int L, int
 }
 
 // ------------------------------------------------------------------------------------------
-// KPM per-omega Chebyshev recursion with register-resident bonds (KPMPreconditioners.jl:606-693,758-778)
-// ------------------------------------------------------------------------------------------
-
-template <int NPL, bool REVERSE>
-__device__ __forceinline__ void lp_sweep_z(double2 *buf, const unsigned (&ij)[ELPH_LP_MC * ((NPL + 1) / 2)],
-                                           const double (&c)[ELPH_LP_MC * ((NPL + 1) / 2)], const double (&s)[ELPH_LP_MC * ((NPL + 1) / 2)],
-                                           int ncol) {
-    constexpr int PP = (NPL + 1) / 2;
-#pragma unroll
-    for (int cc = 0; cc < ELPH_LP_MC; ++cc) {
-        const int col = REVERSE ? ELPH_LP_MC - 1 - cc : cc;
-        if (col < ncol) {
-            double2 a0[PP], a1[PP];
-#pragma unroll
-            for (int pp = 0; pp < PP; ++pp) {
-                const unsigned w = ij[col * PP + pp];
-                a0[pp] = buf[w & 0xFFFF]; a1[pp] = buf[w >> 16];
-            }
-#pragma unroll
-            for (int pp = 0; pp < PP; ++pp) {
-                const int e = col * PP + pp;
-                const unsigned w = ij[e];
-                buf[w & 0xFFFF] = make_double2(c[e] * a0[pp].x + s[e] * a1[pp].x, c[e] * a0[pp].y + s[e] * a1[pp].y);
-                buf[w >> 16] = make_double2(c[e] * a1[pp].x + s[e] * a0[pp].x, c[e] * a1[pp].y + s[e] * a0[pp].y);
-            }
-            WAVE_LDS_ORDER();
-        }
-    }
-}
-
-template <int NPL, bool TRANSPOSED, bool CONJ>
-__device__ __forceinline__ void kpm_series_fast(double2 (&acc)[NPL], const double2 (&vin)[NPL], double2 *buf,
-                                                const double (&eb)[NPL], const double2 *c, int order, double a, double b,
-                                                const unsigned (&ij)[ELPH_LP_MC * ((NPL + 1) / 2)], const double (&cb)[ELPH_LP_MC * ((NPL + 1) / 2)],
-                                                const double (&sb)[ELPH_LP_MC * ((NPL + 1) / 2)], int ncol, int N) {
-    double2 um1[NPL], un[NPL], up1[NPL];
-    double2 c0 = c[0];
-    if (CONJ) c0.y = -c0.y;
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) {
-        acc[q] = make_double2(c0.x * vin[q].x - c0.y * vin[q].y, c0.x * vin[q].y + c0.y * vin[q].x);
-        un[q] = vin[q];
-        um1[q] = make_double2(0.0, 0.0);
-    }
-    for (int n = 2; n <= order; ++n) {
-        // up1 = A' un   (mulA'!, :685-693; A = CBbar diag(Ebar), A^T = diag(Ebar) CBbar^T, :758-778)
-#pragma unroll
-        for (int q = 0; q < NPL; ++q)
-            buf[threadIdx.x + q * WAVE] = TRANSPOSED ? un[q] : make_double2(eb[q] * un[q].x, eb[q] * un[q].y);
-        WAVE_LDS_ORDER();
-        lp_sweep_z<NPL, TRANSPOSED>(buf, ij, cb, sb, ncol);
-        const double2 cn0 = c[n - 1];
-        const double2 cn = make_double2(cn0.x, CONJ ? -cn0.y : cn0.y);
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) {
-            double2 av = buf[threadIdx.x + q * WAVE];
-            if (TRANSPOSED) { av.x *= eb[q]; av.y *= eb[q]; }
-            up1[q] = make_double2(a * av.x - b * un[q].x, a * av.y - b * un[q].y);
-            if (n > 2) {     // u_{n+1} = 2 A' u_n - u_{n-1}; the first step is u_2 = A' u_1
-                up1[q].x = 2.0 * up1[q].x - um1[q].x;
-                up1[q].y = 2.0 * up1[q].y - um1[q].y;
-            }
-            um1[q] = un[q];
-            un[q] = up1[q];
-            acc[q].x += cn.x * un[q].x - cn.y * un[q].y;
-            acc[q].y += cn.x * un[q].y + cn.y * un[q].x;
-        }
-        WAVE_LDS_ORDER();
-    }
-}
-
-template <int NPL>
-__global__ void __launch_bounds__(WAVE) k_kpm_cheb_fast(double2 *__restrict__ nu, KpmDev K, ModelDev m, int Lo2,
-                                                        const CgState *state) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    constexpr int NE = ELPH_LP_MC * ((NPL + 1) / 2);
-    double2 *buf = reinterpret_cast<double2 *>(lds);
-    const int rhs = blockIdx.x;   // x = right-hand side, y = frequency in longest-first order: ALL long recursions are dispatched first
-    if (state && ld_state(state + 2 * rhs).done) return;   // `state` points at the current copy (host adds the parity)
-    const KpmChainView V = kpm_chain_view(K, rhs, m.N);
-    const int w = V.wsched[blockIdx.y];
-    const int N = m.N;
-    const int order = V.order[w];
-    const double2 *c = K.coeff + V.coff[w];
-    double2 *u = nu + ((size_t)rhs * Lo2 + w) * N;
-    unsigned ij[NE];
-    double cb[NE], sb[NE];
-    lp_load_ij<NPL>(ij, m);
-    lp_load_cs<NPL>(cb, sb, V.lp_cbar, V.lp_sbar);
-    double2 vin[NPL], mid[NPL], res[NPL];
-    double eb[NPL];
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) {
-        const int s = threadIdx.x + q * WAVE;
-        const int sc = (s < N) ? s : N - 1;
-        vin[q] = u[sc];
-        eb[q] = V.Ebar[sc];
-    }
-    const double a = V.a, b = V.b;
-    kpm_series_fast<NPL, true, true>(mid, vin, buf, eb, c, order, a, b, ij, cb, sb, m.ncol, N);
-    kpm_series_fast<NPL, false, false>(res, mid, buf, eb, c, order, a, b, ij, cb, sb, m.ncol, N);
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) {
-        const int s = threadIdx.x + q * WAVE;
-        if (s < N) u[s] = res[q];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // KPM Chebyshev recursion, re/im-split variant.
 // A' is real, so the real and the imaginary part of u_n obey the SAME real three-term recursion and never
 // mix; only the coefficient sums do.  One 128-thread workgroup per frequency block: wave 0 carries Re u,
@@ -1177,9 +1068,8 @@ int LPFN(elph_fast_cg_ap)(elph_handle_s *h, const CgBufs &B, int nrhs, int parit
             });
             return check_launch_f("k_cg_ap_chunk_rt");
         }
-        // (ELPH_CHUNK_ORDER=0: blocks in rhs-major order, the A/B of chunk_block_map; solo_chain: the model shows ONE chain to the kernels)
-        static const int xcd_order = []() { const char *e = getenv("ELPH_CHUNK_ORDER"); return (e && e[0] == '0') ? 0 : 1; }();
-        const int po = parity | ((xcd_order && h->solo_chain < 0) ? 2 : 0);
+        // (blocks in the XCD-aware order of chunk_block_map; solo_chain: the model shows ONE chain to the kernels)
+        const int po = parity | ((h->solo_chain < 0) ? 2 : 0);
 #if ELPH_LP_MC == 4      // (the p/x-fused form is planned for four-colour lane programs only: no six-colour instantiations)
 #define CHUNK_PX_BRANCH(TT) else if (px) { if constexpr (NPL >= 5) hipLaunchKernelGGL((k_cg_ap_chunk_px2<NPL, TT>), grid, dim3(WAVE), shm, h->stream, B, m, po); \
                                           else hipLaunchKernelGGL((k_cg_ap_chunk_px<NPL, TT>), grid, dim3(WAVE), shm, h->stream, B, m, po); }
@@ -1226,20 +1116,12 @@ int LPFN(elph_fast_cg_xr)(elph_handle_s *h, const CgBufs &B, int nrhs, int parit
 }
 
 
-// the Chebyshev recursion through the LDS slab (complex one-wave form / Re-Im two-wave form): what elph_fast_kpm_cheb falls to when no
+// the Chebyshev recursion through the LDS slab (the Re / Im two-wave form): what elph_fast_kpm_cheb falls to when no
 // register-exchange layout serves the lattice
-int LPFN(elph_fast_kpm_cheb_lds)(elph_handle_s *h, int nrhs, const CgState *st, bool complex_variant, double *rz_part, int nrz, const double *rr_part) {
+int LPFN(elph_fast_kpm_cheb_lds)(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, const double *rr_part) {
     KpmDev K = elph_kpm_dev(h);
     ModelDev m = elph_model_dev(h);
     const int Lo2 = (int)((h->L + 1) / 2);
-    if (complex_variant) {
-        const size_t shm = (size_t)(h->npl * WAVE + 2 * WAVE) * sizeof(double2);
-        DISPATCH_NPL_F(h->npl, {
-            hipLaunchKernelGGL((k_kpm_cheb_fast<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3(WAVE), shm, h->stream, h->d_nu, K,
-                               m, Lo2, st);
-        });
-        return check_launch_f("k_kpm_cheb_fast");
-    }
     const size_t shm = (size_t)(2 * (h->npl * WAVE + 2 * WAVE) + 2 * h->npl * WAVE) * sizeof(double);
     DISPATCH_NPL_F(h->npl, {
         hipLaunchKernelGGL((k_kpm_cheb_ri<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3(2 * WAVE), shm, h->stream, h->d_nu, K, m,

@@ -29,14 +29,13 @@ template <int P, bool UNI, bool ROWS, bool HC, bool GRID = false, int HGN = 0>
 __device__ __forceinline__ void kpm_cheb_sq_body(double2 *__restrict__ nu, KpmDev K, const double *__restrict__ sqc,
                                                  const double *__restrict__ sqs, int N, int Lo2,
                                                  const CgState *state, double *__restrict__ rz_part, int nrz, int Ltau,
-                                                 const double *__restrict__ rr_part, int dbg_ymax, int fold_nct) {
+                                                 const double *__restrict__ rr_part, int fold_nct) {
     constexpr int NS = (HGN > 0) ? HGN : (HC ? 6 : P * P), LS = 8 * P;
     static_assert(HGN == 0 || (UNI && !ROWS && !HC && !GRID), "honeycomb grid recursion: uniform hopping");
     static_assert(!HC || (UNI && !ROWS), "honeycomb recursion: uniform hopping");
     static_assert(!GRID || (P == 2 && UNI && !ROWS && !HC), "grid recursion: 2 x 2 patches, uniform hopping");
     int GG = 1;
     if (GRID) { while (4 * GG * GG < N) ++GG; }         // G = L / 2
-    if ((int)blockIdx.y >= dbg_ymax) return;            // (ELPH_CHEB_DBG_YMAX: timing experiment — only the dbg_ymax longest recursions run; wrong results)
     __shared__ double xch[2][NS * WAVE];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & (WAVE - 1);
     // x = right-hand side, y = frequency in longest-first order: ALL long recursions are dispatched first; a block takes the
@@ -207,7 +206,7 @@ static int check_launch_f(const char *what) {
     int elph_fast_mul_n##K(elph_handle_s *h, int which, double *yS, const double *vS, int nvec);               \
     int elph_fast_cg_ap_n##K(elph_handle_s *h, const CgBufs &B, int nrhs, int parity, bool px);                \
     int elph_fast_cg_xr_n##K(elph_handle_s *h, const CgBufs &B, int nrhs, int parity);                         \
-    int elph_fast_kpm_cheb_lds_n##K(elph_handle_s *h, int nrhs, const CgState *st, bool complex_variant, double *rz_part, int nrz, const double *rr_part);
+    int elph_fast_kpm_cheb_lds_n##K(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, const double *rr_part);
 LP_DECL(1) LP_DECL(2) LP_DECL(3) LP_DECL(4) LP_DECL(5) LP_DECL(6) LP_DECL(7) LP_DECL(8)
 #undef LP_DECL
 #define LP_SWITCH(fn, ...)                                  \
@@ -225,13 +224,12 @@ LP_DECL(1) LP_DECL(2) LP_DECL(3) LP_DECL(4) LP_DECL(5) LP_DECL(6) LP_DECL(7) LP_
 int elph_fast_mul(elph_handle_s *h, int which, double *yS, const double *vS, int nvec) { LP_SWITCH(elph_fast_mul, h, which, yS, vS, nvec) }
 int elph_fast_cg_ap(elph_handle_s *h, const CgBufs &B, int nrhs, int parity, bool px) { LP_SWITCH(elph_fast_cg_ap, h, B, nrhs, parity, px) }
 int elph_fast_cg_xr(elph_handle_s *h, const CgBufs &B, int nrhs, int parity) { LP_SWITCH(elph_fast_cg_xr, h, B, nrhs, parity) }
-static int kpm_cheb_lds_npl(elph_handle_s *h, int nrhs, const CgState *st, bool complex_variant, double *rz_part, int nrz, const double *rr_part) { LP_SWITCH(elph_fast_kpm_cheb_lds, h, nrhs, st, complex_variant, rz_part, nrz, rr_part) }
+static int kpm_cheb_lds_npl(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, const double *rr_part) { LP_SWITCH(elph_fast_kpm_cheb_lds, h, nrhs, st, rz_part, nrz, rr_part) }
 #undef LP_SWITCH
 
-// slices per wave for the batched kernel: the largest T in {20,16,10,8,5,4,2} dividing L that still leaves >= 1024 waves — or, when
-// that choice needs more waves than the chip has slots (2 per SIMD: 2048), a RAGGED cut of the time axis into floor(slots / nrhs)
-// chunks per right-hand side so that the batch runs in one round (k_cg_ap_chunk_rt; the partial sums are then ceil(L / T) per
-// right-hand side, the last chunk shorter).  ELPH_CHUNK_RAGGED=1 enables it (see the measurement below).
+// slices per wave for the batched kernel: the largest T in {20,16,10,8,5,4,2} dividing L that still leaves >= 1024 waves.  (A RAGGED cut
+// of the time axis that runs a batch in one round of the chip measured slower — the rolled kernel k_cg_ap_chunk_rt is ~15 % slower per
+// slice than the unrolled one, profiles/r03/time_kpm_ragged_chunks.log — and was removed; the run-time kernel serves ELPH_CHUNK_T.)
 static int choose_T_template(const elph_handle_s *h, int nrhs) {
     if (!h->fast || h->force_T == 1) return 1;
     // slices per wave must divide Ltau; 10 and 5 serve the time axes that are multiples of 10 but not of 8 (Ltau = 30, 50, 70, 90 …),
@@ -305,27 +303,7 @@ int elph_choose_T(const elph_handle_s *h, int nrhs) {
             return (int)T;
         }
     }
-    const int Tt = choose_T_template(h, nrhs);
-    if (Tt <= 1 || h->force_T > 0) return Tt;
-    // Measured (config C, profiles/r03/time_kpm_ragged_chunks.log): the rolled kernel is ~15 % slower per slice than the unrolled one
-    // (no scheduling across stages), which eats what the single round gains — CG iteration of 288 right-hand sides 167.7 us ragged
-    // (7 chunks of 23) against 165.8 us with 8 chunks of 20 in two rounds; 300: 183.4 against 168.9.  So the ragged cut is OFF unless
-    // ELPH_CHUNK_RAGGED=1; the run-time kernel stays for forced lengths (ELPH_CHUNK_T) and as the tested base of a better-scheduled one.
-    static const bool ragged = []() { const char *e = getenv("ELPH_CHUNK_RAGGED"); return e && e[0] == '1'; }();
-    const int64_t slots = 2048, L = h->L;
-    if (!ragged || (int64_t)nrhs * (L / Tt) <= slots) return Tt;
-    // more waves than slots: r rounds of the chip, floor(r slots / nrhs) chunks per right-hand side, r the smallest number of rounds
-    // that keeps a chunk at <= 48 slices
-    for (int64_t r = 1; r <= 64; ++r) {
-        const int64_t nch = (r * slots) / nrhs;
-        if (nch < 1) continue;
-        int64_t T = (L + nch - 1) / nch;
-        if (T > 48) continue;
-        if (T < 2) T = 2;
-        while (T < L && L - ((L + T - 1) / T - 1) * T < 2) ++T;      // the last chunk keeps >= 2 slices
-        return (int)T;
-    }
-    return Tt;
+    return choose_T_template(h, nrhs);
 }
 
 
@@ -334,17 +312,16 @@ template <int P, bool UNI, bool ROWS = false, bool HC = false, bool GRID = false
 __global__ void __launch_bounds__(2 * WAVE) k_kpm_cheb_sq(double2 *__restrict__ nu, KpmDev K, const double *__restrict__ sqc,
                                                           const double *__restrict__ sqs, int N, int Lo2,
                                                           const CgState *state, double *__restrict__ rz_part, int nrz, int Ltau,
-                                                          const double *__restrict__ rr_part, int dbg_ymax, int fold_nct) {
-    kpm_cheb_sq_body<P, UNI, ROWS, HC, GRID, HGN>(nu, K, sqc, sqs, N, Lo2, state, rz_part, nrz, Ltau, rr_part, dbg_ymax, fold_nct);
+                                                          const double *__restrict__ rr_part, int fold_nct) {
+    kpm_cheb_sq_body<P, UNI, ROWS, HC, GRID, HGN>(nu, K, sqc, sqs, N, Lo2, state, rz_part, nrz, Ltau, rr_part, fold_nct);
 }
 // the same for FOUR waves per SIMD (128 registers): the uniform-hopping recursion of the 16 x 16 lattice needs 132 as the compiler
 // allots them — one wave per SIMD less for four registers; a batch is thousands of latency-bound chains, every wave in flight counts
 template <int P, bool UNI, bool ROWS = false, bool HC = false>
 __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_kpm_cheb_sq_w4(double2 *__restrict__ nu, KpmDev K, const double *__restrict__ sqc, const double *__restrict__ sqs, int N, int Lo2,
-                 const CgState *state, double *__restrict__ rz_part, int nrz, int Ltau, const double *__restrict__ rr_part, int dbg_ymax,
-                 int fold_nct) {
-    kpm_cheb_sq_body<P, UNI, ROWS, HC>(nu, K, sqc, sqs, N, Lo2, state, rz_part, nrz, Ltau, rr_part, dbg_ymax, fold_nct);
+                 const CgState *state, double *__restrict__ rz_part, int nrz, int Ltau, const double *__restrict__ rr_part, int fold_nct) {
+    kpm_cheb_sq_body<P, UNI, ROWS, HC>(nu, K, sqc, sqs, N, Lo2, state, rz_part, nrz, Ltau, rr_part, fold_nct);
 }
 
 #endif
@@ -355,10 +332,8 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
     if (did_rz) *did_rz = false;
     KpmDev K = elph_kpm_dev(h);
     const int Lo2 = (int)((h->L + 1) / 2);
-    static const bool complex_variant = []() { const char *e = getenv("ELPH_CHEB_COMPLEX"); return e && e[0] == '1'; }();
-    if (complex_variant) return kpm_cheb_lds_npl(h, nrhs, st, true, nullptr, 0, nullptr);
 #if ELPH_LP_MC == 4
-    const bool no_sq = []() { const char *e = getenv("ELPH_NO_SQ"); return e && e[0] == '1'; }();       // (read per call: the tests switch both ways inside one process)
+    const bool no_sq = elph_no_sq();
     // with the fold only the frequencies that some chain still recurses on get a block (the schedule is longest first)
     unsigned gy = (unsigned)Lo2;
     if (fold_nct > 0) {
@@ -371,18 +346,14 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
         gy = (unsigned)std::min(Lo2, nl);
     }
     if (h->sq_P > 0 && !no_sq) {
-        static const bool patch16 = []() { const char *e = getenv("ELPH_CHEB_PATCH"); return e && e[0] == '1'; }();   // (A/B: the patch layout on 16 x 16)
         // one frequency per block (the kernel loops over y, y + gridDim.y, ...: 2, 4 or 8 frequencies per block were measured — no
         // faster at 1 right-hand side or at 128: block dispatch is not what the kernel waits for)
-        static const int dbg_ymax = []() { const char *e = getenv("ELPH_CHEB_DBG_YMAX"); return e ? atoi(e) : (1 << 30); }();
 #define SQ_LAUNCH(PV, UV, ...) hipLaunchKernelGGL((k_kpm_cheb_sq<PV, UV, ##__VA_ARGS__>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
-                                             h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, dbg_ymax, fold_nct)
-        static const bool w4 = []() { const char *e = getenv("ELPH_CHEB_W4"); return !(e && e[0] == '0'); }();        // (A/B: 0 = three waves per SIMD)
-        if (h->sq_P == 2 && !patch16 && h->sq_uniform && w4 && nrhs >= 16) {
+                                             h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
+        if (h->sq_P == 2 && h->sq_uniform && nrhs >= 16) {
             hipLaunchKernelGGL((k_kpm_cheb_sq_w4<2, true, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                               h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, dbg_ymax, fold_nct);
-        } else if (h->sq_P == 2 && !patch16) { if (h->sq_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
-        else if (h->sq_P == 2) { if (h->sq_uniform) SQ_LAUNCH(2, true); else SQ_LAUNCH(2, false); }
+                               h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+        } else if (h->sq_P == 2) { if (h->sq_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
         else              { if (h->sq_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
 #undef SQ_LAUNCH
         if (did_rz) *did_rz = (rz_part != nullptr);
@@ -390,9 +361,8 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
     }
     if (h->sq_L > 0 && h->sq_P == 0 && h->sq_uniform && h->kind == ELPH_MODEL_HOLSTEIN && !no_sq) {
         // any other even-L square lattice (L = 4, 6, 10, 12, 14) with one (cosh, sinh) for every bond: the recursion in the GRID layout
-        static const int dbg_ymax = []() { const char *e = getenv("ELPH_CHEB_DBG_YMAX"); return e ? atoi(e) : (1 << 30); }();
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                           h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, dbg_ymax, fold_nct);
+                           h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         if (did_rz) *did_rz = (rz_part != nullptr);
         return check_launch_f("k_kpm_cheb_sq(grid)");
     }
@@ -401,9 +371,8 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
         const int L = h->hc_L;
         const int hgn = (L * L <= 64) ? 2 : ((L % 2 == 0 && (L / 2) * L <= 64) ? 4 : ((L % 2 == 0 && (L / 2) * (L / 2) <= 64) ? 8 : 0));
         if (hgn) {
-            static const int dbg_ymax = []() { const char *e = getenv("ELPH_CHEB_DBG_YMAX"); return e ? atoi(e) : (1 << 30); }();
 #define HG_LAUNCH(NV) hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, false, NV>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
-                                         h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, dbg_ymax, fold_nct)
+                                         h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
             if (hgn == 2) HG_LAUNCH(2); else if (hgn == 4) HG_LAUNCH(4); else HG_LAUNCH(8);
 #undef HG_LAUNCH
             if (did_rz) *did_rz = (rz_part != nullptr);
@@ -413,9 +382,8 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
     const bool no_hc = no_sq;
     if (h->hc12 && h->hc_uniform && h->kind == ELPH_MODEL_HOLSTEIN && !no_hc) {
         // the honeycomb lattice of 12 x 12 cells with one (cosh, sinh) for every bond: the register-exchange recursion in the quad layout
-        static const int dbg_ymax = []() { const char *e = getenv("ELPH_CHEB_DBG_YMAX"); return e ? atoi(e) : (1 << 30); }();
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                           h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, dbg_ymax, fold_nct);
+                           h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         if (did_rz) *did_rz = (rz_part != nullptr);
         return check_launch_f("k_kpm_cheb_sq(honeycomb)");
     }
@@ -423,7 +391,7 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
     // the Re / Im recursion through the LDS slab delivers r.z too (round 6), where the caller's slots hold the 2 Lo2 partials of a launch
     const bool lds_rz = rz_part != nullptr && 2 * Lo2 <= nrz;
     if (did_rz) *did_rz = lds_rz;
-    return kpm_cheb_lds_npl(h, nrhs, st, false, lds_rz ? rz_part : nullptr, nrz, rr_part);
+    return kpm_cheb_lds_npl(h, nrhs, st, lds_rz ? rz_part : nullptr, nrz, rr_part);
 }
 
 }  // namespace LPNS

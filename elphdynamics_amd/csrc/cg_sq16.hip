@@ -301,20 +301,12 @@ int elph_sq16_cg_ap_px(elph_handle_s *h, const CgBufs &B, int nrhs, int parity) 
     ModelDev m = elph_model_dev(h);
     const int T = (int)(h->L / B.npap);
     if (!elph_sq16_ap_usable(h, T) || (int)h->L != T * B.npap) { elph_set_error("k_cg_ap_sq16_px: not planned for this handle"); return ELPH_E_STATE; }
-    static const int xcd_order = []() { const char *e = getenv("ELPH_CHUNK_ORDER"); return (e && e[0] == '0') ? 0 : 1; }();
-    const int po = parity | ((xcd_order && h->solo_chain < 0) ? 2 : 0);
+    const int po = parity | ((h->solo_chain < 0) ? 2 : 0);      // (the XCD-aware block order; solo_chain: the model shows ONE chain)
     const dim3 grid((unsigned)(nrhs * B.npap));
-    // (ring depth / waves per SIMD: ELPH_SQ16_SHAPE=<depth><waves>, e.g. 24 — measurement only)
-    const int shape = []() { const char *e = getenv("ELPH_SQ16_SHAPE"); return e ? atoi(e) : 0; }();      // (read per call: in-process A/B)
 #define SQ16_LAUNCH(TT)                                                                                                            \
     do {                                                                                                                            \
-        if (h->hc12 && shape == 32) hipLaunchKernelGGL((sq16::k_cg_ap_hc12_px<TT, 3, 2>), grid, dim3(WAVE), 0, h->stream, B, m, po);   \
-        else if (h->hc12 && shape == 22) hipLaunchKernelGGL((sq16::k_cg_ap_hc12_px<TT, 2, 2>), grid, dim3(WAVE), 0, h->stream, B, m, po); \
-        else if (h->hc12) hipLaunchKernelGGL((sq16::k_cg_ap_hc12_px<TT, 2, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po);           \
-        else if (!m.uniform) hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, false, 2, 2>), grid, dim3(WAVE), 0, h->stream, B, m, po);     \
-        else if (shape == 24) hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, true, 2, 4>), grid, dim3(WAVE), 0, h->stream, B, m, po); \
-        else if (shape == 33) hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, true, 3, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po); \
-        else if (shape == 42) hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, true, 4, 2>), grid, dim3(WAVE), 0, h->stream, B, m, po); \
+        if (h->hc12) hipLaunchKernelGGL((sq16::k_cg_ap_hc12_px<TT, 2, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po);                \
+        else if (!m.uniform) hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, false, 2, 2>), grid, dim3(WAVE), 0, h->stream, B, m, po);  \
         else hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, true, 4, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po);                 \
     } while (0)
     switch (T) {

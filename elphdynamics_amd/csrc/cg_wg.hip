@@ -16,7 +16,7 @@
 // (cdna_hip_programming.md, Guideline 16, form R2: the data is the flag; no fence).  The boundary slices of z travel as granules
 // of the same kind.  Every wave of a team reduces the same records in the same order, so alpha, beta and the stop decision are
 // bit-identical across the team and from run to run.  (A sharded solve, SHARD, meets on two levels: the workgroups of a rank, then
-// the ranks through their mailboxes.  -DELPH_SHARD_TWO_MEETINGS keeps round 2's two-meeting iteration for A/B.)
+// the ranks through their mailboxes.)
 //
 // Placement: team members are blocks with equal blockIdx % 8 (they share an XCD and its L2 under the observed round-robin
 // placement — speed only, never correctness).  The grid may hold more teams than the chip can keep resident: blocks are
@@ -107,38 +107,16 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
     // consumes them (24 registers that would otherwise sit through both sweeps)
     constexpr bool PH_LDS = HC && T >= 3;
     constexpr int NSREG = (SQ && SSH) ? (S_LDS ? T : T + 1) : 1;
-    // ONE: the single-meeting iteration (see the loop) — for a shard too: its meeting is two-level (workgroups of the rank, then ranks)
-    // and carries the ghost rows of z
-#ifdef ELPH_SHARD_TWO_MEETINGS
-    constexpr bool ONE = !SHARD;                       // (A/B build: a shard keeps round 2's two-meeting iteration)
-#else
-    constexpr bool ONE = true;
-#endif
     const int W = R.W, G = R.G;
     // (a shard: ONE right-hand side, its G workgroups are the whole grid, spread over the XCDs — several ranks on one GPU, the test
     //  box, would otherwise pile their teams onto the XCD where every dispatch starts: 2 x 20 workgroups do not fit its 32 CUs)
     const int xcd = SHARD ? 0 : (blockIdx.x & 7), idx = SHARD ? (RANKS ? bid : blockIdx.x) : (blockIdx.x >> 3);
     const int tq = idx / G, g = idx - tq * G;
-    // PERSISTENT TEAMS (-DELPH_WG_PERSISTENT; not the default): the grid holds at most as many teams as the chip keeps resident
-    // (R.teams_per_xcd per XCD, one workgroup per CU) and a team takes the right-hand sides tq, tq + teams, ... of its XCD's residue class
-    // one after the other, so that no workgroup ever waits for one that has not been dispatched yet.  The default keeps ONE solve per
-    // workgroup and an oversubscribed grid (teams at the dispatch frontier wait for members that start when another team ends —
-    // blocks are dispatched in index order; the wall-clock bound, the fallback and the cool-down of elph_wg_cg are the guard):
-    // measured, the loop around the solve costs 4 % (30.7 against 29.5 us per iteration of 288 right-hand sides, 5.51 against 5.22 at
-    // 48 — what stays live across the loop spills 126 scalar registers), profiles/r03/wg_persistent_teams.log.
-#ifdef ELPH_WG_PERSISTENT
-    for (int tqi = tq;; tqi += R.teams_per_xcd) {
-    // (the thread number is laundered per right-hand side: everything derived from it — sites, LDS offsets, DPP partners, addresses —
-    //  is made afresh for each solve; hoisted out of this loop it would sit in registers for all of them)
-    int tid = (int)threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & (WAVE - 1);
-#else
+    // ONE solve per workgroup and an oversubscribed grid (teams at the dispatch frontier wait for members that start when another team
+    // ends — blocks are dispatched in index order; the wall-clock bound, the fallback and the cool-down of elph_wg_cg are the guard).
+    // Persistent teams that loop over right-hand sides measured 4 % slower (profiles/r03/wg_persistent_teams.log) and were removed.
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & (WAVE - 1);
-    const int tqi = tq;
-    {
-#endif
-    const int rhs = tqi * 8 + xcd;
+    const int rhs = tq * 8 + xcd;
 #ifdef ELPH_WG_ARRIVE
     // diagnostic build (tools/diag_wg_arrive.py): where and when every workgroup of the grid started — XCC_ID and the hardware id of its
     // CU, the wall clock — to see which members a team that timed out was waiting for
@@ -176,11 +154,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
     const CgParams P = B.params;
     CgState *st2 = B.state + 2 * rhs;
     const CgState S = ld_state(st2);
-#ifdef ELPH_WG_PERSISTENT
-    if (!SHARD && (S.done || S.seq != 0)) continue;    // fresh solves only (the host guarantees it); a shard seeds its state below
-#else
     if (!SHARD && (S.done || S.seq != 0)) return;      // fresh solves only (the host guarantees it); a shard seeds its state below
-#endif
 
     // site of register q of this lane: lane + 64 q (layout S order), or the column segments of the DPP form
     int sc[NPL], ss[NPL];
@@ -317,33 +291,29 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
     // records and boundary granules exist TWICE, by the parity of the iteration: a workgroup that has met for iteration k goes on and
     // publishes its record of k + 1 one mat-vec later — into the OTHER set, so that a member that is late reading the records of k
     // (its polling wave held up: two workgroups sharing a CU, a time-sliced GPU) still finds them; nobody can reach k + 2 before that
-    // member has published k + 1, i.e. finished reading k.  (With ONE set such a member waited for tags that had already moved on —
+    // member has published k + 1, i.e. finished reading k.  (With a single set such a member waited for tags that had already moved on —
     // the time-out of the experimental 4-wave shape, tools/diag_wg_arrive.py.)
-    constexpr size_t SLOTS_RHS = ONE ? SLOTS_PER_RHS : 2 * 64;
+    constexpr size_t SLOTS_RHS = SLOTS_PER_RHS;
     u64 *const slots0 = R.slots + (size_t)rhs * 2 * SLOTS_RHS;
     u64 *const bnd0 = R.bnd + (size_t)rhs * 2 * G * 2 * HS * 2;     // [parity][G][first | last slice][HS][2 granules]
     const int gm = (g == 0) ? G - 1 : g - 1, gp = (g == G - 1) ? 0 : g + 1;
     double rho = S.rho, kmin = S.kmin, eps = S.eps;
     double eps0 = S.eps0, normb = S.normb;
 
-    // (ordered before their first readers by the barriers that follow.  bc — the seed meeting of a shard, the two-meeting form — shares
-    //  its three words with part[16..18], the z.z partials of waves 0..2: in the single-meeting form of an un-sharded solve it must NOT
-    //  be touched here — nothing orders this store of wave 0 before the first iteration's part[] stores of a wave that finished its
+    // (ordered before their first readers by the barriers that follow.  bc — the seed meeting of a shard — shares its three words with
+    //  part[16..18], the z.z partials of waves 0..2: in an un-sharded solve it must NOT be touched here — nothing orders this store of wave 0 before the first iteration's part[] stores of a wave that finished its
     //  set-up sooner, and a late 1.0 in place of wave 2's z.z partial costs that solve its first beta: one iteration more, about one
     //  first solve in three of a fresh handle with the slow set-up of the bond-phonon DPP form)
-    if (threadIdx.x == 0) { tot[5] = 1.0; if (SHARD || !ONE) bc[2] = 1.0; }
-    // single-meeting form: the boundary waves of a workgroup keep the neighbouring workgroup's boundary slice of r (p0 = r0: it sits in
-    // the halo of p)
-    if constexpr (ONE) {
-        if (G > 1) {
-            if (wv == 0) {
+    if (threadIdx.x == 0) { tot[5] = 1.0; if (SHARD) bc[2] = 1.0; }
+    // the boundary waves of a workgroup keep the neighbouring workgroup's boundary slice of r (p0 = r0: it sits in the halo of p)
+    if (G > 1) {
+        if (wv == 0) {
 #pragma unroll
-                for (int q = 0; q < NPL; ++q) if (lwok) rhalo[lr + q * LSL] = p[0][q];
-            }
-            if (wv == W - 1) {
+            for (int q = 0; q < NPL; ++q) if (lwok) rhalo[lr + q * LSL] = p[0][q];
+        }
+        if (wv == W - 1) {
 #pragma unroll
-                for (int q = 0; q < NPL; ++q) if (lwok) rhalo[HSL + lr + q * LSL] = p[T + 1][q];
-            }
+            for (int q = 0; q < NPL; ++q) if (lwok) rhalo[HSL + lr + q * LSL] = p[T + 1][q];
         }
     }
     // ghost sites of this lane: where their values arrive in the own mailbox (nullptr: not a ghost site), slice t0
@@ -386,7 +356,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
     for (long long seq = 0;; ++seq) {
         const unsigned epoch = R.epoch0 + (unsigned)seq + (SHARD ? 2u : 1u);
         const unsigned par = epoch & 1u;
-        u64 *const slotsA = slots0 + (size_t)par * SLOTS_RHS, *const slotsB = slotsA + (ONE ? SLOTS_A : 64);
+        u64 *const slotsA = slots0 + (size_t)par * SLOTS_RHS, *const slotsB = slotsA + SLOTS_A;
         u64 *const bnd = bnd0 + (size_t)par * G * 2 * HS * 2;
         const size_t ghp = SHARD ? (size_t)par * 2 * L * Sh.cap_ghost * 2 : 0;      // (a shard: the ghost rows of z in the mailboxes, by parity too)
         STAMP(9);
@@ -560,9 +530,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         //  number — kept across the loop they are 2 registers each, 24 of them, in a kernel that has none to spare)
         int lane_b = lane;
         if constexpr (HC && T >= 3) asm volatile("" : "+v"(lane_b));
-        double rr, hx[NPL];                                   // rr: r.r of the NEW residual; hx: the halo slice that comes from another workgroup (waves 0 and W-1)
-        if constexpr (ONE) {
-        // ================= single-meeting iteration ==========================================================================
+        double rr;                                            // r.r of the NEW residual
+        {   // ================= the single-meeting iteration ==================================================================
         // The two meetings of the textbook iteration (p.z -> alpha; then r.r of the new residual and its boundary slices -> beta, halo
         // of p) fold into ONE: every workgroup publishes FOUR sums — p.z, r.z, z.z and the r.r of the current residual — and the
         // boundary slices of z.  With them every wave has  alpha = r.r / p.z  and, by the algebraic identity of r' = r - alpha z,
@@ -724,16 +693,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             const int rw = (W > NSEG) ? NSEG : ((W >= 3) ? 1 : 0);        // (a wave without a segment if there is one)
             bool ok = true;
             double t4 = 0.0;
-#ifdef ELPH_WG_NOMEET
-            // diagnostic bound (tools/time_wg_nomeet.py, never the product): an iteration WITHOUT its meeting — no record, no poll, the
-            // workgroup's own sums taken for the team's, the boundary slices of z left as they are.  What any rearrangement of the
-            // meeting (a pipelined recurrence, XCD-local records) could reach at most; the numbers it computes mean nothing.
-            if (wv == rw) t4 = __shfl(sum_part4(part, W, lane), 8 * ((lane & 7) >> 1), WAVE);
-            for (int s0 = wv; false;) {
-#else
             if (wv == rw) publish_rec4(slotsA, g, sum_part4(part, W, lane), epoch, lane);
             for (int s0 = wv; s0 < NSEG || (s0 == wv && wv == rw); s0 += 2 * W) {
-#endif
                 const int s1 = s0 + W;
                 const u64 *b0 = nullptr, *b1 = nullptr;
                 if (s0 < NSEG) b0 = bnd + ((((s0 < NPL) ? (size_t)gm * 2 + 1 : (size_t)gp * 2 + 0) * HS) + lane_b + (size_t)(s0 % NPL) * WAVE) * 2;
@@ -764,13 +725,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         }
         STAMP(1);
         rho = rr0;                                            // r.r of the residual this iteration started from, summed from the vector
-#ifdef ELPH_WG_NOMEET
-        const double alpha = 1e-6 * (rr0 / pap);              // (the workgroup's own sums are no CG: keep the vectors bounded — r almost constant, beta = 1/2 —
-        rr = 0.5 * rr0 + 1e-30 * fabs(rr0 + alpha * (alpha * zz - 2.0 * rz));      //  so that no NaN sends a workgroup into the direct-sum meeting)
-#else
         const double alpha = rr0 / pap;                                                            // :278-279 (rho = r.r)
         rr = rr0 + alpha * (alpha * zz - 2.0 * rz);
-#endif
         // ---- x += alpha p, r -= alpha z (own slices) ----------------------------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < T; ++j)
@@ -837,170 +793,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         }
         wg_barrier();                                         // the new residual of every wave is in LDS: the neighbours' halo slices
         STAMP(4);
-        } else {
-        // ================= two-meeting iteration (sharded solves) ===============================================================
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < T; ++j)
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) if (own[q]) acc += p[j + 1][q] * z[j][q];
-        acc = wave_sum_dpp(acc);
-        // (x of the own slices lives in LDS)
-        STAMP(0);
-        // ---- meeting 1: p.z ---------------------------------------------------------------------------------------
-        // wave partials -> LDS -> barrier; with a team of several workgroups ONE wave per workgroup publishes the workgroup's
-        // record and polls the team's (80 waves polling one line serialise at the memory side: 1.5 -> ~0.7 us per meeting),
-        // then hands the total to its workgroup through LDS
-        if (lane == 0) partA[wv] = acc;
-        wg_barrier();
-        STAMP(2);
-        double pap;
-        if constexpr (SHARD) {
-            if (wv == 0) {
-                const double mine = wg_sum(partA, W, lane);
-                sh_publish<RANKS>(Sh, 0, g, G, mine, epoch, lane);
-                const u64 *none[NPL];
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) none[q] = nullptr;
-                double tot = 0.0, dummy[NPL];
-                const bool ok = sh_poll<NPL, RANKS>(Sh, true, 0, G, none, epoch, lane, R, tot, dummy);
-                if (lane == 0) { bc[0] = tot; if (!ok) bc[2] = 0.0; }
-            }
-            wg_barrier();
-            if (bc[2] == 0.0) return;
-            pap = bc[0];
-        } else if (G == 1) {
-            pap = wg_sum(partA, W, lane);
-        } else {
-            if (wv == 0) {
-                const double mine = wg_sum(partA, W, lane);
-                if (lane < 2) {
-                    const u64 bits = (u64)__double_as_longlong(mine);
-                    st_gran(slotsA + 2 * g + lane, ((u64)epoch << 32) | (lane ? (bits >> 32) : (bits & 0xFFFFFFFFull)));
-                }
-                u64 v = 0;
-                const bool ok = poll_records(slotsA, G, epoch, lane, R, v);
-                const int half = (int)(unsigned)v;
-                double tot = 0.0;
-                for (int k = 0; k < G; ++k)
-                    tot += __hiloint2double(__builtin_amdgcn_readlane(half, 2 * k + 1), __builtin_amdgcn_readlane(half, 2 * k));
-                if (lane == 0) { bc[0] = tot; if (!ok) bc[2] = 0.0; }
-            }
-            wg_barrier();
-            if (bc[2] == 0.0) return;
-            pap = bc[0];
         }
-        STAMP(1);
-        const double alpha = rho / pap;
-        // ---- x += alpha p (to memory), r -= alpha z, r.r; show the boundary slices of the new r ---------------------------
-        double a = 0.0, rn[T][NPL];
-#pragma unroll
-        for (int j = 0; j < T; ++j)
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) {
-                rn[j][q] = rl[j * HSL + lr + q * LSL] - alpha * z[j][q];                           // :285
-                rl[j * HSL + lr + q * LSL] = rn[j][q];
-                if (own[q]) a += rn[j][q] * rn[j][q];
-                if (X_REG) xr[X_REG ? j : 0][q] += alpha * p[j + 1][q];                            // :282
-                else xl[j * HSL + lr + q * LSL] += alpha * p[j + 1][q];
-            }
-        a = wave_sum_dpp(a);
-        if constexpr (SHARD) {
-            // the rows my neighbours hold as ghosts: straight into their mailboxes (device-initiated stores over xGMI)
-            const int prev = (Sh.rank + Sh.P - 1) % Sh.P, next = (Sh.rank + 1) % Sh.P;
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) {
-                const int s = lane + q * WAVE;
-                const u64 bits = (u64)__double_as_longlong(rn[0][q]), tag = (u64)epoch << 32;
-                if (s >= Sh.own_lo && s < Sh.own_lo + Sh.n_to_prev) {              // bottom rows -> previous rank's ghosts above its own rows
-                    u64 *d = sh_ghost(Sh.mail[prev], 1, L, Sh.cap_ghost, t0, s - Sh.own_lo);
-                    st_mail<RANKS>(d, tag | (bits & 0xFFFFFFFFull)); st_mail<RANKS>(d + 1, tag | (bits >> 32));
-                }
-                if (s >= Sh.own_hi - Sh.n_to_next && s < Sh.own_hi) {              // top rows -> next rank's ghosts below its own rows
-                    u64 *d = sh_ghost(Sh.mail[next], 0, L, Sh.cap_ghost, t0, s - (Sh.own_hi - Sh.n_to_next));
-                    st_mail<RANKS>(d, tag | (bits & 0xFFFFFFFFull)); st_mail<RANKS>(d + 1, tag | (bits >> 32));
-                }
-            }
-        }
-        // slices that cross a workgroup boundary travel as granules too ({iteration, half of the f64}: the data is its own flag —
-        // no drain here, no flag there; the neighbour polls them together with the r.r records)
-        if (G > 1) {
-            if (wv == 0) {
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) st_f64_gran(bnd + (((size_t)g * 2 + 0) * HS + lane + q * WAVE) * 2, rn[0][q], epoch);
-            }
-            if (wv == W - 1) {
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) st_f64_gran(bnd + (((size_t)g * 2 + 1) * HS + lane + q * WAVE) * 2, rn[T - 1][q], epoch);
-            }
-        }
-        if (lane == 0) partB[wv] = a;
-        STAMP(3);
-        wg_barrier();
-        STAMP(4);
-        // ---- meeting 2: r.r and the halo slices of the new r ------------------------------------------------------------------
-        if constexpr (SHARD) {
-            // every wave takes the ghost rows of its slice from the mailbox; wave 0 also trades the r.r records of all ranks
-            double tot = 0.0, gv[NPL];
-            if (wv == 0) sh_publish<RANKS>(Sh, 1, g, G, wg_sum(partB, W, lane), epoch, lane);
-            bool ok = sh_poll<NPL, RANKS>(Sh, wv == 0, 1, G, gaddr, epoch, lane, R, tot, gv);
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) if (gaddr[q]) rl[lane + q * WAVE] = gv[q];
-            if (G > 1 && (wv == 0 || wv == W - 1)) {          // the tau-neighbour workgroup of this rank: its boundary slice (own rows; ghosts follow below)
-                u64 v = 0, gh[NPL][2];
-                const u64 *bh = (wv == 0) ? bnd + (((size_t)gm * 2 + 1) * HS) * 2 : bnd + (((size_t)gp * 2 + 0) * HS) * 2;
-                ok = poll_granules<NPL>(nullptr, G, bh, epoch, lane, R, v, gh) && ok;
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) hx[q] = __hiloint2double((int)(unsigned)gh[q][1], (int)(unsigned)gh[q][0]);
-                // ... whose ghost rows are as stale as mine were: the neighbour slice's ghost values come from the mailbox too
-                const int th = (wv == 0) ? wrap(t0 - 1) : wrap(t0 + T);
-                const u64 *ga2[NPL];
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) {
-                    const int s = lane + q * WAVE;
-                    ga2[q] = (s < Sh.own_lo) ? sh_ghost(Sh.mail[Sh.rank], 0, L, Sh.cap_ghost, th, s)
-                           : (s >= Sh.own_hi && s < N) ? sh_ghost(Sh.mail[Sh.rank], 1, L, Sh.cap_ghost, th, s - Sh.own_hi) : nullptr;
-                }
-                double t2 = 0.0, gv2[NPL];
-                ok = sh_poll<NPL, RANKS>(Sh, false, 1, G, ga2, epoch, lane, R, t2, gv2) && ok;
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) if (ga2[q]) hx[q] = gv2[q];
-            }
-            if (lane == 0) { if (wv == 0) bc[1] = tot; if (!ok) bc[2] = 0.0; }
-            wg_barrier();
-            if (bc[2] == 0.0) return;
-            rr = bc[1];
-        } else if (G == 1) {
-            rr = wg_sum(partB, W, lane);
-        } else {
-            if (wv == 0 || wv == W - 1) {
-                u64 v = 0, gh[NPL][2];
-                const u64 *bh = (wv == 0) ? bnd + (((size_t)gm * 2 + 1) * HS) * 2                  // left halo: last slice of workgroup g - 1
-                                          : bnd + (((size_t)gp * 2 + 0) * HS) * 2;                 // right halo: first slice of workgroup g + 1
-                if (wv == 0) {
-                    const double mine = wg_sum(partB, W, lane);
-                    if (lane < 2) {
-                        const u64 bits = (u64)__double_as_longlong(mine);
-                        st_gran(slotsB + 2 * g + lane, ((u64)epoch << 32) | (lane ? (bits >> 32) : (bits & 0xFFFFFFFFull)));
-                    }
-                }
-                const bool ok = poll_granules<NPL>(wv == 0 ? slotsB : nullptr, G, bh, epoch, lane, R, v, gh);
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) hx[q] = __hiloint2double((int)(unsigned)gh[q][1], (int)(unsigned)gh[q][0]);
-                if (wv == 0) {
-                    const int half = (int)(unsigned)v;
-                    double tot = 0.0;
-                    for (int k = 0; k < G; ++k)
-                        tot += __hiloint2double(__builtin_amdgcn_readlane(half, 2 * k + 1), __builtin_amdgcn_readlane(half, 2 * k));
-                    if (lane == 0) bc[1] = tot;
-                }
-                if (!ok && lane == 0) bc[2] = 0.0;
-            }
-            wg_barrier();
-            if (bc[2] == 0.0) return;
-            rr = bc[1];
-        }
-        }   // two-meeting iteration
         STAMP(5);
         STAMP(6);
         // ---- stop test of iteration it = seq + 1 (IterativeSolvers.jl:286-295) ---------------------------------------------
@@ -1015,12 +808,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         const long long it = seq + 1;
         const bool fixed = R.fixed_iters > 0;
         int done = 0;
-#ifdef ELPH_WG_NOMEET
-        const bool screened = it < R.fixed_iters;             // (the sums mean nothing: no stop arithmetic before the last iteration)
-#else
         const bool screened = !P.record_hist && it < (fixed ? R.fixed_iters : P.maxiter) && (fixed || rr > rr_far) &&
                               (rr + rr <= y_num || rr >= y_num + y_num) && (double)it < it_kappa;
-#endif
         if (!screened) {
             eps = sqrt(rr) / normb;
             const double qq = 2.0 * (double)it / log(2.0 * eps0 / eps);
@@ -1059,11 +848,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                 st2[1] = o;
             }
             TL(3);
-#ifdef ELPH_WG_PERSISTENT
-            break;
-#else
             return;
-#endif
         }
         const double beta = rr / rho;
         rho = rr;
@@ -1074,8 +859,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             const double *sr = rall + ((size_t)((wv < W - 1) ? wv + 1 : 0) * T + 0) * HSL;         // first slice of the wave above
 #pragma unroll
             for (int q = 0; q < NPL; ++q) {
-                const double hl = lx ? (ONE ? rhalo[lr + q * LSL] : hx[q]) : sl[lr + q * LSL];
-                const double hr = rx ? (ONE ? rhalo[HSL + lr + q * LSL] : hx[q]) : sr[lr + q * LSL];
+                const double hl = lx ? rhalo[lr + q * LSL] : sl[lr + q * LSL];
+                const double hr = rx ? rhalo[HSL + lr + q * LSL] : sr[lr + q * LSL];
                 if constexpr (PH_LDS) {
                     const double n0 = hl + beta * PHALO(0, q), n1 = hr + beta * PHALO(1, q);
                     if (lwok) { PHALO(0, q) = n0; PHALO(1, q) = n1; }
@@ -1091,316 +876,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             for (int q = 0; q < NPL; ++q) p[j + 1][q] = rl[j * HSL + lr + q * LSL] + beta * p[j + 1][q];
         STAMP(8);
     }
-#ifdef ELPH_WG_PERSISTENT
-    if (SHARD) return;
-    wg_barrier();                                      // (the LDS of this right-hand side is rewritten by the next one)
-#endif
-    }
 #undef EXPV
 #undef PHALO
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// THE ROW FORM (round 5): Holstein with uniform hopping on the 16 x 16 square lattice (config C), batches that take the 4-slices-per-wave
-// shape.  Same team protocol as k_cg_wg's single-meeting iteration (one 64-byte record per workgroup, boundary slices of z as granules,
-// r'.r' by the one-step identity, the same stop test) around ANOTHER layout of the vectors: a 16-lane DPP ROW holds ONE time slice —
-// lane (X, Y) = (l & 3, (l >> 2) & 3) a 4 x 4 patch of its sites, register q = cx + 4 cy — and the four rows of a wave four consecutive
-// slices, 32 slices per workgroup.  Per colour the even bonds and the inner odd bonds pair registers of a lane; only the patch edges
-// cross: x-odd by quad permutations, y-odd by row rotations — 16 DPP moves of an f64 per sweep of a slice, all inside the row (the 2 x 2
-// patches of k_cg_wg: 12 moves + 4 ds_bpermute per SLAB sweep, nine slab sweeps per mat-vec pair of four slices).  The tau shift, which
-// there is a renaming of registers (at the price of one halo sweep per wave), goes through LDS here: p of the slice below, then
-// t = sg k4 E o CB^T(M p) of the slice above, 16 ds_write_b64 + 16 ds_read_b64 each and a barrier.  Only the workgroup's TOP boundary needs
-// a redundant slice (m and t of the slice above its last one): one extra sweep pair, by the last wave.
-// Measured before it was built (tools/probes/matvec_row_layout_probe.cpp): 2.4 us per mat-vec pair + sums + updates of a round of the
-// chip against ~3.9 us of the 2 x 2 layout.
-namespace rowf {
-constexpr int SV = 256;                       // values of a slice
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) { return dpp_f64<CTRL>(v); }
-// one colour of the checkerboard on the 4 x 4 patch v[cx + 4 cy]: v <- (I + th P_colour) v.  COL 0: x-even, 1: x-odd, 2: y-even, 3: y-odd
-template <int COL>
-__device__ __forceinline__ void colour(double (&v)[16], double th) {
-    if constexpr (COL == 0) {
-#pragma unroll
-        for (int cy = 0; cy < 4; ++cy)
-#pragma unroll
-            for (int cx = 0; cx < 4; cx += 2) { const int i = cx + 4 * cy, j = i + 1; const double a = v[i] + th * v[j], b = v[j] + th * v[i]; v[i] = a; v[j] = b; }
-    } else if constexpr (COL == 2) {
-#pragma unroll
-        for (int cx = 0; cx < 4; ++cx)
-#pragma unroll
-            for (int cy = 0; cy < 4; cy += 2) { const int i = cx + 4 * cy, j = i + 4; const double a = v[i] + th * v[j], b = v[j] + th * v[i]; v[i] = a; v[j] = b; }
-    } else if constexpr (COL == 1) {
-        double fu[4], fd[4];
-#pragma unroll
-        for (int cy = 0; cy < 4; ++cy) { fu[cy] = dpp<0x39>(v[0 + 4 * cy]); fd[cy] = dpp<0x93>(v[3 + 4 * cy]); }      // quad_perm [1,2,3,0]: from the patch X + 1; [3,0,1,2]: from X - 1
-#pragma unroll
-        for (int cy = 0; cy < 4; ++cy) { const int i = 1 + 4 * cy, j = i + 1; const double a = v[i] + th * v[j], b = v[j] + th * v[i]; v[i] = a; v[j] = b; }
-#pragma unroll
-        for (int cy = 0; cy < 4; ++cy) { v[3 + 4 * cy] += th * fu[cy]; v[0 + 4 * cy] += th * fd[cy]; }
-    } else {
-        double fu[4], fd[4];
-#pragma unroll
-        for (int cx = 0; cx < 4; ++cx) { fu[cx] = dpp<0x12C>(v[cx + 0]); fd[cx] = dpp<0x124>(v[cx + 12]); }            // row_ror:12: from lane + 4 (the patch Y + 1); row_ror:4: from lane - 4
-#pragma unroll
-        for (int cx = 0; cx < 4; ++cx) { const int i = cx + 4, j = i + 4; const double a = v[i] + th * v[j], b = v[j] + th * v[i]; v[i] = a; v[j] = b; }
-#pragma unroll
-        for (int cx = 0; cx < 4; ++cx) { v[cx + 12] += th * fu[cx]; v[cx + 0] += th * fd[cx]; }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <bool REVERSE>
-__device__ __forceinline__ void sweep(double (&v)[16], double th) {
-    if constexpr (!REVERSE) { colour<0>(v, th); colour<1>(v, th); colour<2>(v, th); colour<3>(v, th); }
-    else { colour<3>(v, th); colour<2>(v, th); colour<1>(v, th); colour<0>(v, th); }
-}
-}  // namespace rowf
-
-template <bool X0Z>
-__global__ void __launch_bounds__(512) k_cg_row(CgBufs B, ModelDev m, WgCtl R) {
-    using rowf::SV;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    constexpr int W = 8, NPLM = 4, HS = 256, LSL = WAVE;      // (the meeting sees a slice as four segments of 64 values, as k_cg_wg's 2 x 2 layout does)
-    const int G = R.G;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int tq = idx / G, g = idx - tq * G;
-    const int rhs = tq * 8 + xcd;
-    if (rhs >= B.nrhs) return;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & (WAVE - 1), row = lane >> 4, l16 = lane & 15;
-    const int N = m.N, L = m.L;
-    const int vr = 4 * wv + row;                       // this lane's row of the workgroup: 0 .. 31
-    const int t = g * 32 + vr;                         // ... and its time slice
-    const size_t ndim = (size_t)N * L;
-    // LDS: XB[34][256] exchange rows (row 0: p of the slice below the workgroup, kept; 1..32: the rows' p, then t; 33: t of the slice above) |
-    //      RL[34][256] r (0 and 33: the neighbouring workgroups' boundary slices) | PH1[256] p of the slice above | EH[256] its exp(-dtau V) |
-    //      zhalo[2][256] | part[32] tot[8] partF[8]
-    double *XB = lds, *RL = XB + 34 * SV, *PH1 = RL + 34 * SV, *EH = PH1 + SV, *zhalo = EH + SV, *part = zhalo + 2 * SV, *tot = part + 32, *partF = tot + 8;
-    auto wrap = [L](int tt) { return (tt < 0) ? tt + L : ((tt >= L) ? tt - L : tt); };
-    auto sgn = [](int tt) { return (tt == 0) ? -1.0 : 1.0; };
-    const CgParams P = B.params;
-    CgState *st2 = B.state + 2 * rhs;
-    const CgState S = ld_state(st2);
-    if (S.done || S.seq != 0) return;                  // fresh solves only (the host guarantees it)
-    // site of register q of a lane: (4 X + cx) + 16 (4 Y + cy) — made where it is used (set-up, final store), not kept across the loop
-    auto site_of = [](int l16v, int q) { return (4 * (l16v & 3) + (q & 3)) + 16 * (4 * (l16v >> 2) + (q >> 2)); };
-    double *xg = B.x + (size_t)rhs * ndim;
-    const double *rg = B.r + (size_t)rhs * ndim;
-    const double *Ech = m.E + (size_t)(rhs % m.nchains) * m.E_chain_stride;
-    const double th = m.s_uni / m.c_uni, k4 = (m.c_uni * m.c_uni) * (m.c_uni * m.c_uni);
-    double p[16], x[16], e[16], z[16];      // (x in memory instead — loaded behind the sums, stored by the update — was measured slower: 9.3 against 8.0 us)
-    const int own = (1 + vr) * SV + l16;               // this lane's words of its row: own + 16 q
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const double rv = rg[(size_t)t * N + site_of(l16, q)];
-        RL[own + 16 * q] = rv;
-        p[q] = rv;                                     // p0 = r0 (IterativeSolvers.jl:272)
-        x[q] = X0Z ? 0.0 : xg[(size_t)t * N + site_of(l16, q)];
-        e[q] = Ech[(size_t)t * m.E_tau_stride + site_of(l16, q)];
-    }
-    if (vr == 0) {                                     // the slice below the workgroup: p0 = r0 of it
-        const int tb = wrap(g * 32 - 1);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const double rv = rg[(size_t)tb * N + site_of(l16, q)]; XB[l16 + 16 * q] = rv; RL[l16 + 16 * q] = rv; }
-    }
-    if (vr == 31) {                                    // the slice above
-        const int ta = wrap(g * 32 + 32);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const double rv = rg[(size_t)ta * N + site_of(l16, q)];
-            PH1[l16 + 16 * q] = rv; RL[33 * SV + l16 + 16 * q] = rv;
-            EH[l16 + 16 * q] = Ech[(size_t)ta * m.E_tau_stride + site_of(l16, q)];
-        }
-    }
-    if (threadIdx.x == 0) tot[5] = 1.0;
-    u64 *const slots0 = R.slots + (size_t)rhs * 2 * SLOTS_PER_RHS;
-    u64 *const bnd0 = R.bnd + (size_t)rhs * 2 * G * 2 * HS * 2;     // [parity][G][first | last slice][HS][2 granules]
-    const int gm = (g == 0) ? G - 1 : g - 1, gp = (g == G - 1) ? 0 : g + 1;
-    double rho = S.rho, kmin = S.kmin, eps = S.eps;
-    const double eps0 = S.eps0, normb = S.normb;
-    const double rr_far = (P.tol * normb) * (P.tol * normb) * 1.000001, y_num = 4.0 * (eps0 * normb) * (eps0 * normb);
-    const double it_kappa = 0.17 * sqrt(P.kmax);
-    const double sg_own = sgn(t) * k4, sg_top = sgn(wrap(g * 32 + 32)) * k4;
-    wg_barrier();
-    STAMP_DECL;
-    for (long long seq = 0;; ++seq) {
-        const unsigned epoch = R.epoch0 + (unsigned)seq + 1u;
-        const unsigned par = epoch & 1u;
-        u64 *const slotsA = slots0 + (size_t)par * SLOTS_PER_RHS, *const slotsB = slotsA + SLOTS_A;
-        u64 *const bnd = bnd0 + (size_t)par * G * 2 * HS * 2;
-        STAMP(9);
-        // ---- z = M^T M p:  m(t) = p(t) - sg(t) k4 CB [E(t) o p(t-1)];  tv(t) = sg(t) k4 E(t) o CB^T m(t);  z(t) = m(t) - tv(t+1)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) XB[own + 16 * q] = p[q];
-        wg_barrier();
-        double u[16];
-#ifndef ELPH_ROW_NOHALO      // (timing experiment, wrong results: without the redundant slice of the last wave)
-        if (wv == W - 1) {
-            // the slice ABOVE the workgroup first (every row of this wave computes it, identically; in the registers the own slice uses next): its
-            // m from the kept p of that slice and the p of the workgroup's last slice (in its exchange row), then its tv into exchange row 33
-#pragma unroll
-            for (int q = 0; q < 16; ++q) u[q] = EH[l16 + 16 * q] * XB[32 * SV + l16 + 16 * q];
-            rowf::sweep<false>(u, th);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) u[q] = PH1[l16 + 16 * q] - sg_top * u[q];       // m of the slice above
-            rowf::sweep<true>(u, th);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) XB[33 * SV + l16 + 16 * q] = sg_top * (EH[l16 + 16 * q] * u[q]);
-        }
-#endif
-#pragma unroll
-        for (int q = 0; q < 16; ++q) u[q] = e[q] * XB[own - SV + 16 * q];            // p of the slice below (row 0: the kept halo)
-        rowf::sweep<false>(u, th);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { z[q] = p[q] - sg_own * u[q]; u[q] = z[q]; }   // z holds m for now
-        rowf::sweep<true>(u, th);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) u[q] = sg_own * (e[q] * u[q]);                  // tv of the own slice
-        wg_barrier();                                  // everybody has read the p of the row below: the rows take the tv's now
-#pragma unroll
-        for (int q = 0; q < 16; ++q) XB[own + 16 * q] = u[q];
-        wg_barrier();
-        double s_pz = 0.0, s_rz = 0.0, s_zz = 0.0, s_rr = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            z[q] = z[q] - XB[own + SV + 16 * q];       // z(t) = m(t) - tv(t+1)
-            const double rv = RL[own + 16 * q];
-            s_pz += p[q] * z[q]; s_rz += rv * z[q]; s_zz += z[q] * z[q]; s_rr += rv * rv;
-        }
-        {
-            const double k4s = wave_sum4(s_pz, s_rz, s_zz, s_rr, lane);
-            if (lane < 4) part[lane * 8 + wv] = k4s;
-        }
-        STAMP(0);
-        // boundary slices of z for the neighbouring workgroups (self-tagged granules; word i of a slice = 16 q + l16, as both sides see it)
-        if (vr == 0) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) st_f64_gran(bnd + (((size_t)g * 2 + 0) * HS + l16 + 16 * q) * 2, z[q], epoch);
-        }
-        if (vr == 31) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) st_f64_gran(bnd + (((size_t)g * 2 + 1) * HS + l16 + 16 * q) * 2, z[q], epoch);
-        }
-        wg_barrier();
-        STAMP(2);
-        double pap, rz, zz, rr0;
-        {
-            // the meeting, as k_cg_wg's: wave s takes segment s of the two boundary slices (8 segments of 64 values), wave 1 the records too
-            constexpr int NSEG = 2 * NPLM, rw = 1;
-            if (wv == rw) publish_rec4(slotsA, g, sum_part4(part, W, lane), epoch, lane);
-            bool ok = true;
-            double t4 = 0.0;
-            {
-                const int s0 = wv;
-                const u64 *b0 = bnd + ((((s0 < NPLM) ? (size_t)gm * 2 + 1 : (size_t)gp * 2 + 0) * HS) + lane + (size_t)(s0 % NPLM) * WAVE) * 2;
-                const bool recs = (wv == rw);
-                double z0 = 0.0, z1 = 0.0;
-                if (G <= 8) {
-                    u64 v[1] = {0};
-                    ok = poll_rec4<1>(recs ? slotsA : nullptr, G, b0, nullptr, epoch, lane, R, v, z0, z1) && ok;
-                    if (recs) t4 = sum_rec4<1>(v, G, lane);
-                } else {
-                    u64 v[4] = {0, 0, 0, 0};
-                    ok = poll_rec4<4>(recs ? slotsA : nullptr, G, b0, nullptr, epoch, lane, R, v, z0, z1) && ok;
-                    if (recs) t4 = sum_rec4<4>(v, G, lane);
-                }
-                zhalo[(size_t)s0 * LSL + lane] = z0;   // (segment s = side * 4 + k lives at [side][64 k + lane])
-                static_assert(NSEG == W, "one segment per wave");
-            }
-            if (wv == rw && lane < 8 && !(lane & 1)) tot[lane >> 1] = t4;
-            if (!ok && lane == 0) tot[5] = 0.0;
-            wg_barrier();
-            if (tot[5] == 0.0) return;
-            pap = tot[0]; rz = tot[1]; zz = tot[2]; rr0 = tot[3];
-        }
-        STAMP(1);
-        rho = rr0;
-        const double alpha = rr0 / pap;
-        double rr = rr0 + alpha * (alpha * zz - 2.0 * rz);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            RL[own + 16 * q] = RL[own + 16 * q] - alpha * z[q];
-            x[q] += alpha * p[q];
-        }
-        if (wv == 0 || wv == W - 1) {                  // the neighbouring workgroups' boundary slices of the new residual
-            double *rh = RL + ((wv == 0) ? 0 : 33 * SV);
-            const double *zh = zhalo + ((wv == 0) ? 0 : SV);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rh[lane + 64 * k] = rh[lane + 64 * k] - alpha * zh[lane + 64 * k];
-        }
-        if (!(rr > 1e-3 * rr0)) {
-            // the identity cancels: r'.r' from the vector itself (second meeting of this iteration; every wave of the team is here)
-            double a = 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) { const double rn = RL[own + 16 * q]; a += rn * rn; }
-            a = wave_sum_dpp(a);
-            if (lane == 0) partF[wv] = a;
-            wg_barrier();
-            if (wv == 0) {
-                const double mine = wg_sum(partF, W, lane);
-                if (lane < 2) {
-                    const u64 bits = (u64)__double_as_longlong(mine);
-                    st_gran(slotsB + 2 * g + lane, ((u64)epoch << 32) | (lane ? (bits >> 32) : (bits & 0xFFFFFFFFull)));
-                }
-                u64 v = 0;
-                const bool ok = poll_records(slotsB, G, epoch, lane, R, v);
-                const int half = (int)(unsigned)v;
-                double tt = 0.0;
-                for (int k = 0; k < G; ++k)
-                    tt += __hiloint2double(__builtin_amdgcn_readlane(half, 2 * k + 1), __builtin_amdgcn_readlane(half, 2 * k));
-                if (lane == 0) { tot[4] = tt; if (!ok) tot[5] = 0.0; }
-            }
-            wg_barrier();
-            if (tot[5] == 0.0) return;
-            rr = tot[4];
-        }
-        STAMP(3);
-        // ---- stop test of iteration it = seq + 1 (IterativeSolvers.jl:286-295), screened as in k_cg_wg
-        const long long it = seq + 1;
-        const bool fixed = R.fixed_iters > 0;
-        int done = 0;
-        const bool screened = !P.record_hist && it < (fixed ? R.fixed_iters : P.maxiter) && (fixed || rr > rr_far) &&
-                              (rr + rr <= y_num || rr >= y_num + y_num) && (double)it < it_kappa;
-        if (!screened) {
-            eps = sqrt(rr) / normb;
-            const double qq = 2.0 * (double)it / log(2.0 * eps0 / eps);
-            const double val = qq * qq;
-            kmin = (val > kmin) ? val : kmin;
-            if (eps < P.tol) done = 1;
-            else if (kmin > P.kmax) done = 2;
-            else if (it >= P.maxiter) done = 3;
-            if (fixed) done = (it >= R.fixed_iters) ? 3 : 0;
-            if (g == 0 && wv == 0 && lane == 0 && P.record_hist) B.hist[(size_t)rhs * P.hist_stride + it] = eps;
-        }
-        STAMP(7);
-        if (done) {
-            STAMP_OUT(it);
-            int l16b = l16;
-            asm volatile("" : "+v"(l16b));             // (addresses made here, from a laundered lane number: not 32 registers across the loop)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) xg[(size_t)t * N + site_of(l16b, q)] = x[q];
-            if (g == 0 && wv == 0 && lane == 0) {
-                CgState o = S;
-                o.rho = rho; o.kmin = kmin; o.eps = eps; o.seq = it + 1; o.iters = it; o.done = done;
-                st2[0] = o;
-                st2[1] = o;
-            }
-            return;
-        }
-        const double beta = rr / rho;
-        rho = rr;
-        // ---- next direction: own slice, and the two kept slices of the neighbouring workgroups (p = r + beta p is pointwise)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) p[q] = RL[own + 16 * q] + beta * p[q];
-        if (wv == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) XB[lane + 64 * k] = RL[lane + 64 * k] + beta * XB[lane + 64 * k];
-        }
-        if (wv == W - 1) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) PH1[lane + 64 * k] = RL[33 * SV + lane + 64 * k] + beta * PH1[lane + 64 * k];
-        }
-        STAMP(8);
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1409,10 +886,15 @@ __global__ void __launch_bounds__(512) k_cg_row(CgBufs B, ModelDev m, WgCtl R) {
 
 struct Shape { int T, W, G; size_t shm; bool sq, hc, s8, gr, hg; int npl; bool tg = false; };   // npl: sites per lane of the kernel (honeycomb DPP form: 6; grid form: 4)
 
+// ELPH_WG_NO_DPP=1: none of the register-exchange forms below, the lane-program form instead (read per call: the tests switch it)
+static bool wg_no_dpp() {
+    const char *e = getenv("ELPH_WG_NO_DPP");
+    return e && e[0] == '1';
+}
+
 // DPP form: Holstein on the 16 x 16 square lattice in the reference's colouring (detect_square)
 static bool sq_form(const elph_handle_s *h, const ModelDev &m) {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    return h->sq_P == 2 && h->N == 256 && m.sq_bond && !(e && e[0] == '1');
+    return h->sq_P == 2 && h->N == 256 && m.sq_bond && !wg_no_dpp();
 }
 
 // T slices per wave: what the register file takes at two waves per SIMD — lane-program form 2 for site phonons with <= 4 sites
@@ -1422,38 +904,33 @@ static bool sq_form(const elph_handle_s *h, const ModelDev &m) {
 // a meeting are polled by one wave instruction)
 // honeycomb DPP form: Holstein with uniform hopping on 12 x 12 cells in the reference's colouring (detect_honeycomb12)
 static bool hc_form(const elph_handle_s *h, const ModelDev &m) {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->hc12 && m.uniform && !(e && e[0] == '1');
+    return h->kind == ELPH_MODEL_HOLSTEIN && h->hc12 && m.uniform && !wg_no_dpp();
 }
 
 // 8 x 8 DPP form: Holstein with uniform hopping on the 8 x 8 square lattice in the reference's colouring (detect_square: sq_P = 1)
 static bool s8_form(const elph_handle_s *h, const ModelDev &m) {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->sq_P == 1 && h->N == 64 && m.uniform && !(e && e[0] == '1');
+    return h->kind == ELPH_MODEL_HOLSTEIN && h->sq_P == 1 && h->N == 64 && m.uniform && !wg_no_dpp();
 }
 
 // grid form: Holstein with uniform hopping on a periodic LX x LY square lattice in the reference's colouring whose 2 x 2 patches fit the
 // lanes of a wave (detect_square: sq_LX, sq_LY).  An ordinary solve takes it for the sizes WITHOUT a DPP form of their own (not 16 x 16,
 // not 8 x 8); a sharded solve (for_shard) for every size — the slab closed into a ring is such a lattice, and the DPP forms know no shards.
 static bool gr_form(const elph_handle_s *h, const ModelDev &m, bool for_shard = false) {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    if (h->kind != ELPH_MODEL_HOLSTEIN || h->sq_LX < 4 || h->sq_LY < 4 || !m.uniform || m.grid_GX * m.grid_GY < 1 || m.grid_GX * m.grid_GY > 64 || (e && e[0] == '1')) return false;
+    if (h->kind != ELPH_MODEL_HOLSTEIN || h->sq_LX < 4 || h->sq_LY < 4 || !m.uniform || m.grid_GX * m.grid_GY < 1 || m.grid_GX * m.grid_GY > 64 || wg_no_dpp()) return false;
     return for_shard || h->sq_P == 0;
 }
 
 // triangular grid form: Holstein with uniform hopping on an even-L triangular lattice of at most 16 x 16 sites in the reference's colouring
 // (detect_triangular: pg_kind 3): the GRID layout with the two diagonal colours (pgrid::Tri<2, 2>)
 static bool tg_form(const elph_handle_s *h, const ModelDev &m) {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->pg_kind == 3 && h->pg_L >= 4 && h->pg_L <= 16 && m.uniform && m.grid_GX == h->pg_L / 2 && m.grid_GY == h->pg_L / 2 && !(e && e[0] == '1');
+    return h->kind == ELPH_MODEL_HOLSTEIN && h->pg_kind == 3 && h->pg_L >= 4 && h->pg_L <= 16 && m.uniform && m.grid_GX == h->pg_L / 2 && m.grid_GY == h->pg_L / 2 && !wg_no_dpp();
 }
 
 // honeycomb grid form: Holstein with uniform hopping on a periodic honeycomb lattice of LX x LY cells in the reference's colouring whose cells
 // fit a grid of lanes (detect_honeycomb: hc_LX, hc_LY; 12 x 12 has a DPP form of its own — which knows no shards).  Returns the registers per
 // lane (2, 4 or 8: 1, 2 x 1 or 2 x 2 cells), 0: no.
 static int hg_form(const elph_handle_s *h, const ModelDev &m, bool for_shard = false) {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    if (h->kind != ELPH_MODEL_HOLSTEIN || h->hc_LX < 2 || h->hc_LY < 2 || (h->hc12 && !for_shard) || !m.uniform || m.hc_LX != h->hc_LX || (e && e[0] == '1')) return 0;
+    if (h->kind != ELPH_MODEL_HOLSTEIN || h->hc_LX < 2 || h->hc_LY < 2 || (h->hc12 && !for_shard) || !m.uniform || m.hc_LX != h->hc_LX || wg_no_dpp()) return 0;
     const int LX = h->hc_LX, LY = h->hc_LY;
     if (LX * LY <= 64) return 2;
     if (LX % 2 == 0 && (LX / 2) * LY <= 64) return 4;
@@ -1620,32 +1097,12 @@ static hipError_t launch_shard_grid(elph_handle_s *h, const Shape &sh, dim3 grid
     }
 }
 
-// the row form (k_cg_row) of the 4-slices-per-wave shape of the 16 x 16 DPP form: 32 slices per workgroup
-static bool row_form(const elph_handle_s *h, const Shape &sh) {
-    const char *e = getenv("ELPH_WG_ROW");
-    if (!(e && e[0] == '1')) return false;
-    return sh.sq && sh.T == 4 && sh.W == 8 && h->N == 256 && h->L % 32 == 0 && sh.G == (int)(h->L / 32) && sh.G >= 2 && sh.G <= 32;
-}
-
 template <int NPL>
 static hipError_t launch_npl(elph_handle_s *h, const Shape &sh, dim3 grid, const CgBufs &B, const ModelDev &m, const WgCtl &R) {
     if constexpr (NPL == 4) {
         if (sh.sq) {
             if (h->kind == ELPH_MODEL_SSH) return (sh.T == 2) ? launch_k<4, 2, true, false, 1>(h, sh, grid, B, m, R) : launch_k<4, 1, true, false, 1>(h, sh, grid, B, m, R);
             if (!m.uniform) return (sh.T == 2) ? launch_k<4, 2, false, false, 1>(h, sh, grid, B, m, R) : launch_k<4, 1, false, false, 1>(h, sh, grid, B, m, R);
-            if (sh.T == 4 && row_form(h, sh)) {      // the row form of the same shape (k_cg_row: a time slice per 16-lane row, 4 x 4 patches)
-                const size_t shm = ((size_t)(34 + 34) * rowf::SV + 2 * rowf::SV + 2 * rowf::SV + 48) * sizeof(double);
-                if (R.x0_zero) {
-                    hipError_t e = hipFuncSetAttribute((const void *)k_cg_row<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                    if (e != hipSuccess) return e;
-                    hipLaunchKernelGGL((k_cg_row<true>), grid, dim3(8 * WAVE), shm, h->stream, B, m, R);
-                } else {
-                    hipError_t e = hipFuncSetAttribute((const void *)k_cg_row<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                    if (e != hipSuccess) return e;
-                    hipLaunchKernelGGL((k_cg_row<false>), grid, dim3(8 * WAVE), shm, h->stream, B, m, R);
-                }
-                return hipGetLastError();
-            }
             if (sh.T == 4) return R.x0_zero ? launch_k<4, 4, false, true, 1, false, true>(h, sh, grid, B, m, R) : launch_k<4, 4, false, true, 1>(h, sh, grid, B, m, R);
             if (sh.T == 2) return launch_k<4, 2, false, true, 1>(h, sh, grid, B, m, R);
             return launch_k<4, 1, false, true, 1>(h, sh, grid, B, m, R);
@@ -1695,19 +1152,41 @@ int elph_i_resident_wg_limit(const elph_handle_s *h) {
     return cache[d];
 }
 
+// ELPH_WG_T: force the slices per wave of the resident kernel (0: the rule of pick_shape)
+static int wg_t() {
+    const char *et = getenv("ELPH_WG_T");
+    return et ? atoi(et) : 0;
+}
+
 bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs) {
     const char *eo = getenv("ELPH_NO_WG");                 // read per call: the tests switch between the two forms
     const bool off = eo && eo[0] == '1';
     // (h->npl > 5: the lane-program form's limit — 320 sites; the honeycomb grid form carries up to 512 in one wave)
     const bool tri_grid = h->kind == ELPH_MODEL_HOLSTEIN && h->pg_kind == 3 && h->pg_L <= 16;      // (a six-colour lattice, but its resident form needs no lane program)
     if (off || !h->fast || (h->lp_mc != 4 && !tri_grid) || (h->npl > 5 && !(h->hc_LX > 0 && !h->hc12 && h->kind == ELPH_MODEL_HOLSTEIN)) || h->dot_hi != 0 || h->solo_chain >= 0) return false;
-    const char *et = getenv("ELPH_WG_T");
     wg::Shape sh;
-    if (!wg::pick_shape(h, elph_model_dev(h), et ? atoi(et) : 0, nrhs, &sh)) return false;
+    if (!wg::pick_shape(h, elph_model_dev(h), wg_t(), nrhs, &sh)) return false;
     if (T) *T = sh.T;
     if (W) *W = sh.W;
     if (G) *G = sh.G;
     return true;
+}
+
+// The operational knobs of every resident kernel (cg_wg.hip, pcg_wg.hip, slabs.hip, shard.hip), read per call:
+// ELPH_WG_TIMEOUT_MS, the wait bound of a team (dflt: the caller's default when it is not set) ...
+long long elph_wg_timeout_ms(long long dflt) {
+    const char *e = getenv("ELPH_WG_TIMEOUT_MS");
+    return e ? atoll(e) : dflt;
+}
+// ... ELPH_WG_COOLDOWN, the solves that run streaming after a time-out (default 16) ...
+int elph_wg_cooldown() {
+    const char *e = getenv("ELPH_WG_COOLDOWN");
+    return e ? std::max(1, atoi(e)) : 16;
+}
+// ... and the tests' ELPH_SLABS_TEST_TIMEOUT: its first character, 0 when it is not set
+char elph_slabs_test_timeout() {
+    const char *e = getenv("ELPH_SLABS_TEST_TIMEOUT");
+    return e ? e[0] : 0;
 }
 
 // A team timed out on an earlier solve (the GPU was shared with something that held its CUs): the handle runs the streaming iteration
@@ -1730,10 +1209,9 @@ int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iter
     if (B.params.use_prec) return ELPH_OK;
     if (h->wg_broken) return ELPH_OK;                   // (cooling down after a time-out: elph_wg_cooldown_step, run_cg)
     if (!elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs)) return ELPH_OK;
-    const char *et = getenv("ELPH_WG_T");
     wg::Shape sh;
     ModelDev m = elph_model_dev(h);
-    if (!wg::pick_shape(h, m, et ? atoi(et) : 0, nrhs, &sh)) return ELPH_OK;
+    if (!wg::pick_shape(h, m, wg_t(), nrhs, &sh)) return ELPH_OK;
     // Which form is faster for THIS batch: a deterministic rule (never a timing at run time — which form runs decides the last bits of a
     // solution) from ONE table of measured constants, wg_cost_table above.  fixed_iters > 0 (measurement of this kernel) and
     // ELPH_WG_ALWAYS=1 skip it.
@@ -1770,22 +1248,15 @@ int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iter
     R.epoch0 = h->wg_epoch;
     h->wg_epoch += (unsigned)span;
     R.G = sh.G; R.W = sh.W;
-    const char *eto = getenv("ELPH_WG_TIMEOUT_MS");
     // (2 s: a team at the dispatch frontier of an oversubscribed grid waits for whole solves of the resident ones — tens of ms for a
     //  batch of hundreds of right-hand sides; a measurement launch of thousands of fixed iterations gets its own duration on top)
-    R.timeout_ticks = ((long long)(eto ? atoll(eto) : 2000) + (fixed_iters > 0 ? fixed_iters / 10 : 0)) * 100000LL;     // wall_clock64 runs at 100 MHz
+    R.timeout_ticks = (elph_wg_timeout_ms(2000) + (fixed_iters > 0 ? fixed_iters / 10 : 0)) * 100000LL;     // wall_clock64 runs at 100 MHz
     R.fixed_iters = fixed_iters;
-    { const char *ez = getenv("ELPH_WG_X0Z"); R.x0_zero = (h->wg_x0_zero && !(ez && ez[0] == '0')) ? 1 : 0; }     // (x0 = 0 known: the 4-slice DPP shape has an instantiation that does not read it)
+    R.x0_zero = h->wg_x0_zero ? 1 : 0;     // (x0 = 0 known: the 4-slice DPP shape has an instantiation that does not read it)
     h->wg_x0_zero = false;
     if (fixed_iters <= 0)       // the caller's initial guess survives in d_zp (unused by an un-preconditioned solve) for the fallback
         HIPCHK(hipMemcpyAsync(h->d_zp, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-#ifdef ELPH_WG_PERSISTENT
-    // persistent teams: per XCD (32 CUs, one workgroup each) floor(32 / G) teams at most
-    R.teams_per_xcd = std::max(1, std::min((nrhs + 7) / 8, 32 / sh.G));
-#else
-    R.teams_per_xcd = (nrhs + 7) / 8;                      // one solve per workgroup: every right-hand side has its team in the grid
-#endif
-    const dim3 grid((unsigned)(8 * R.teams_per_xcd * sh.G));
+    const dim3 grid((unsigned)(8 * ((nrhs + 7) / 8) * sh.G));      // one solve per workgroup: every right-hand side has its team in the grid
     hipError_t e = hipSuccess;
     if (sh.hg) {
         switch (sh.npl) {
@@ -1824,8 +1295,7 @@ int elph_wg_aborted(elph_handle_s *h, bool *aborted) {
     HIPCHK(hipMemcpy(&ab, static_cast<char *>(h->d_res) + h->wg_abort_off, sizeof(int), hipMemcpyDeviceToHost));
     if (ab) {
         h->wg_broken = true;
-        const char *ec = getenv("ELPH_WG_COOLDOWN");
-        h->wg_cooldown = ec ? std::max(1, atoi(ec)) : 16;
+        h->wg_cooldown = elph_wg_cooldown();
         ++h->wg_fallbacks;
         *aborted = true;
         elph_set_error("workgroup-resident CG timed out waiting for its team (T=%d W=%d G=%d); falling back to the two-kernel iteration",
@@ -1909,7 +1379,6 @@ static int shard_rank_setup(elph_handle_s *h, const CgBufs &B, long long fixed_i
     R.x0_zero = 0;
     HIPCHK(hipMemsetAsync(base, 0, h->res_cap, h->stream));   // boundary granules of this rank's workgroups: tags restart at 2
     h->wg_epoch = 0;
-    R.teams_per_xcd = 1;
     return ELPH_OK;
 }
 
@@ -1965,8 +1434,7 @@ int elph_wg_cg_ranks(elph_handle_s *const *hs, int P, const CgBufs *Bs, long lon
     wg::WgCtl R0 = A[0].R;
     R0.ranks = d_args;
     // (tests, ELPH_SLABS_TEST_TIMEOUT=2: the last rank's workgroups are NOT launched — the others wait for them until their bound and give up)
-    const char *edrop = getenv("ELPH_SLABS_TEST_TIMEOUT");
-    const int drop = (edrop && edrop[0] == '2') ? 1 : 0;
+    const int drop = (elph_slabs_test_timeout() == '2') ? 1 : 0;
     const dim3 grid((unsigned)((P - drop) * sh0.G)), block((unsigned)(sh0.W * WAVE));
     hipError_t e = hipSuccess;
 #define RANKS_LAUNCH(NPLV, UNIV) do {                                                                                                  \

@@ -23,7 +23,6 @@ struct WgCtl {
     long long timeout_ticks;   // wall_clock64 ticks (100 MHz)
     long long fixed_iters;     // > 0: measurement mode, exactly this many iterations, no stop test
     int x0_zero;               // the initial guess is zero (the library zeroed it): x0 is not read
-    int teams_per_xcd;         // persistent teams: team tq of an XCD takes right-hand sides tq, tq + teams_per_xcd, ... (times 8, plus the XCD)
     const void *ranks = nullptr;   // k_cg_wg<..., RANKS>: WgRankArgs[P] in device memory — the launch arguments of every rank of the grid (nullptr otherwise)
 };
 
@@ -419,26 +418,6 @@ __device__ __forceinline__ bool poll_records(const u64 *rec, int G, unsigned epo
         if (__all(!mine || (unsigned)(c >> 32) == epoch)) { v = c; return true; }
         if (mine) c = ld_gran(rec + lane);
         if (poll_bail<1>(spin, t_start, lane, R)) return false;
-    }
-}
-
-// records (optional) + the 2 NPL boundary granules of every lane; one poll at a time (a second poll set in flight costs 4 NPL + 2
-// registers next to the Krylov vectors: measured as spills)
-template <int NPL>
-__device__ __forceinline__ bool poll_granules(const u64 *rec, int G, const u64 *bh, unsigned epoch, int lane, const WgCtl &R, u64 &v,
-                                              u64 (&gh)[NPL][2]) {
-    long long t_start = 0;
-    for (int spin = 0;; ++spin) {
-        bool ok = true;
-        if (rec && lane < 2 * G) v = ld_gran(rec + lane);
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) { gh[q][0] = ld_gran(bh + 2 * (lane + q * WAVE)); gh[q][1] = ld_gran(bh + 2 * (lane + q * WAVE) + 1); }
-        if (rec && lane < 2 * G) ok = ((unsigned)(v >> 32) == epoch);
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) ok = ok && (unsigned)(gh[q][0] >> 32) == epoch && (unsigned)(gh[q][1] >> 32) == epoch;
-        if (__all(ok)) return true;
-        if (poll_bail<NPL>(spin, t_start, lane, R)) return false;
-        __builtin_amdgcn_s_sleep(1);
     }
 }
 

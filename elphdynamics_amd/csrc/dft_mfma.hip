@@ -730,8 +730,7 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
     // (L = 256 ... 400: 80 ... 128 KB of the CU's 160 KB) ask for it explicitly, once per kernel instantiation
     const size_t panel = (size_t)MG * T.nt * WAVE * sizeof(double);
     const size_t shm_s = panel + (X.fold ? (size_t)(L / 2) * 2 * sizeof(double) : 0);      // + the fold table of the chain (forward, XrFuse)
-    const char *es = getenv("ELPH_DFT_STREAM");
-    if (panel <= 144 * 1024 && !(es && atoi(es) == 0)) {
+    if (panel <= 144 * 1024) {
         hipError_t attr_rc = hipSuccess;
 #define R2S_LAUNCH(NTV, RZV, PXV) do {                                                                                         \
             auto kfn = k_dft_mfma_r2s<NTV, INV, XR, RZV, PXV>;                                                                  \
@@ -755,7 +754,7 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
 #define R2_CASE(NTV) case NTV: hipLaunchKernelGGL((k_dft_mfma_r2<NTV, INV, XR>), grid, block, 0, h->stream, out, in, T.W, tw, N, L, st, rvec, rz_part, nrz, X); break;
     switch (T.nt) {
         R2_CASE(5) R2_CASE(10) R2_CASE(15) R2_CASE(20) R2_CASE(25) R2_CASE(32)
-        default: elph_set_error("dft_mfma_r2: no register-resident kernel for %d reduction tiles (ELPH_DFT_STREAM=0 needs L <= 256)", T.nt); return ELPH_E_UNSUPPORTED;
+        default: elph_set_error("dft_mfma_r2: no register-resident kernel for %d reduction tiles (panels beyond 144 KB need L <= 256)", T.nt); return ELPH_E_UNSUPPORTED;
     }
 #undef R2_CASE
     return mf_check(INV ? "k_dft_mfma_r2(inverse)" : "k_dft_mfma_r2(forward)");
@@ -780,10 +779,8 @@ bool elph_dft_mfma_usable(const elph_handle_s *h, int which, bool inverse, int N
     return (long long)((N + 15) / 16) * T.groups * nrhs >= 512;
 }
 
-// one output tile per wave: the twisted pair for batches below the crossover of the forms above (ELPH_DFT_MFMA1=0: scalar kernels)
+// one output tile per wave: the twisted pair for batches below the crossover of the forms above
 bool elph_dft_mfma1_usable(const elph_handle_s *h, bool inverse, int N, int nrz_slots) {
-    const char *e = getenv("ELPH_DFT_MFMA1");
-    if (e && atoi(e) == 0) return false;
     const elph_handle_s::MfmaTab &T = h->mf[0][inverse ? 1 : 0];
     if (!T.W) return false;
     return !inverse || nrz_slots <= 0 || ((N + 15) / 16) * T.groups * MG <= nrz_slots;
@@ -808,13 +805,10 @@ int elph_dft_mfma_fwd(elph_handle_s *h, int which, double2 *nu, const double *vS
 
 // whether launch_r2<false> takes the streaming form (the one that knows the order-1 fold)
 bool elph_dft_mfma_fold_usable(const elph_handle_s *h) {
-    const char *ef = getenv("ELPH_KPM_FOLD");
-    if (ef && atoi(ef) == 0) return false;
     const elph_handle_s::MfmaTab &T = h->mf_r2[0];
     if (!T.W || !r2_enabled() || T.groups != 1 || (h->L & 1)) return false;
     const size_t panel = (size_t)MG * T.nt * WAVE * sizeof(double);
-    const char *es = getenv("ELPH_DFT_STREAM");
-    return panel <= 144 * 1024 && !(es && atoi(es) == 0);
+    return panel <= 144 * 1024;
 }
 
 // forward twisted transform of r - alpha z with the residual update of k_cg_xr folded in (see XrFuse); usable: see below
@@ -825,8 +819,7 @@ bool elph_dft_mfma_xr_usable(const elph_handle_s *h, int N, int nrhs) {
     // one per workgroup of CW tiles (round 6: large lattices on short time axes)
     const int nct = (N + 15) / 16;
     const size_t panel = (size_t)MG * h->mf_r2[0].nt * WAVE * sizeof(double);
-    const char *es = getenv("ELPH_DFT_STREAM");
-    const bool streaming = panel <= 144 * 1024 && !(es && atoi(es) == 0);
+    const bool streaming = panel <= 144 * 1024;
     const bool slots_ok = nct <= (int)h->L || (streaming && (nct + CW - 1) / CW <= (int)h->L);
     return h->mf_r2[0].W && r2_enabled() && elph_dft_mfma_usable(h, 0, false, N, nrhs) && slots_ok &&
            h->mf_r2[0].groups == 1;           // one row group: every element of r belongs to exactly one wave
@@ -859,8 +852,7 @@ bool elph_dft_mfma_px_usable(const elph_handle_s *h, int N, int nrhs) {
     const elph_handle_s::MfmaTab &T = h->mf_r2[1];
     if (!T.W || !r2_enabled() || T.groups != 1 || (h->L & 1)) return false;       // one row group: every element of p, x belongs to one lane
     const size_t panel = (size_t)MG * T.nt * WAVE * sizeof(double);
-    const char *es = getenv("ELPH_DFT_STREAM");
-    return panel <= 144 * 1024 && !(es && atoi(es) == 0) && elph_dft_mfma_usable(h, 0, true, N, nrhs);
+    return panel <= 144 * 1024 && elph_dft_mfma_usable(h, 0, true, N, nrhs);
 }
 
 int elph_dft_mfma_inv_px(elph_handle_s *h, const double2 *nu, int N, int nrhs, const CgState *st, double *pS, double *xS,

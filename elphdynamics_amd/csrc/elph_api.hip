@@ -63,11 +63,6 @@ static int dev_alloc(T **p, size_t n) {
     return ELPH_OK;
 }
 
-static void drop_graphs(elph_handle_s *h) {
-    for (auto &g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-    h->graphs.clear();
-}
-
 // ------------------------------------------------------------------------------------------
 // lane program (cg_fast.hip): bonds re-packed [colour][pass][lane]
 // ------------------------------------------------------------------------------------------
@@ -92,11 +87,6 @@ static int build_lane_program(elph_handle_s *h) {
     h->lp_mc = (h->ncol <= 4) ? 4 : 6;      // kernels exist for 4-colour (square, honeycomb, chain) and 6-colour (triangular) programs
     const int PP = (h->npl + 1) / 2, NE = h->lp_mc * PP;
     h->lp_ne = NE;
-    const char *ci = getenv("ELPH_CHUNK_ITERS");
-    h->chunk = ci ? atoi(ci) : ELPH_CG_CHUNK;
-    if (h->chunk < 2 || (h->chunk & 1)) h->chunk = ELPH_CG_CHUNK;   // must be even (ping-pong parity)
-    const char *co = getenv("ELPH_DBG_COPY_OUTSIDE");
-    h->dbg_copy_outside = (co && co[0] == '1');
     const char *ct = getenv("ELPH_CHUNK_T");
     h->force_T = ct ? atoi(ct) : 0;
     const char *nf = getenv("ELPH_NO_FAST");
@@ -233,17 +223,15 @@ static void detect_square(elph_handle_s *h) {
         if ((int64_t)l * l != h->N) continue;
         if (!pgrid::pick_patch(l, &px, &py)) {
             // no patch that fits one wavefront: several wavefronts per slice, the patch edges through LDS (ELPH_PG_MW=0: the generic kernels, A/B)
-            const char *em = getenv("ELPH_PG_MW");
-            if ((em && em[0] == '0') || !pgrid::pick_patch_mw(l, &px, &py, &nw)) continue;
+            if (!elph_pg_mw() || !pgrid::pick_patch_mw(l, &px, &py, &nw)) continue;
         }
         {   // hopping disorder on 28 x 28 / 32 x 32: 2 x 2 patches on four wavefronts instead of 4 x 4 on one — 12 table entries per thread instead of 40
             // (measured, profiles/r06/hopping_disorder_patch_kernels_with_tables.log); ELPH_PG_MW=0 keeps the one-wavefront shape
-            const char *em = getenv("ELPH_PG_MW");
             bool uni = true;
             if (h->kind == ELPH_MODEL_HOLSTEIN)
                 for (int64_t n = 1; n < h->nb && uni; ++n) uni = (h->h_c[(size_t)n] == h->h_c[0] && h->h_s[(size_t)n] == h->h_s[0]);
             // (... and 30 x 30, whose 2 x 10 patches have no table variant: 15 x 15 threads on four wavefronts)
-            if (!uni && nw == 1 && ((px == 4 && py == 4) || (px == 2 && py == 10)) && !(em && em[0] == '0')) { px = 2; py = 2; nw = ((l / 2) * (l / 2) + 63) / 64; }
+            if (!uni && nw == 1 && ((px == 4 && py == 4) || (px == 2 && py == 10)) && elph_pg_mw()) { px = 2; py = 2; nw = ((l / 2) * (l / 2) + 63) / 64; }
             h->pg_uniform_c = uni && h->kind == ELPH_MODEL_HOLSTEIN;
         }
         if (match_square(h, l, l)) { h->pg_L = l; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 1; h->pg_NW = nw; h->pg_bond = h->sq_bond; }
@@ -291,9 +279,8 @@ static void detect_honeycomb12(elph_handle_s *h) {
         if (c.first == c.second) {
             h->hc_L = c.first; h->hc12 = (c.first == 12);
             int px = 0, py = 0, nw = 1;
-            const char *em = getenv("ELPH_PG_MW");
             if (c.first > 16 && pgrid::pick_hpatch(c.first, &px, &py)) { h->pg_L = c.first; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 2; h->pg_NW = 1; }     // (pgrid.hip: PX x PY cells per lane)
-            else if (c.first > 16 && !(em && em[0] == '0') && pgrid::pick_hpatch_mw(c.first, &px, &py, &nw)) { h->pg_L = c.first; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 2; h->pg_NW = nw; }     // (several wavefronts per slice)
+            else if (c.first > 16 && elph_pg_mw() && pgrid::pick_hpatch_mw(c.first, &px, &py, &nw)) { h->pg_L = c.first; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 2; h->pg_NW = nw; }     // (several wavefronts per slice)
         }
         return;
     }
@@ -322,7 +309,6 @@ static int upload_lp_cs(elph_handle_s *h) {
 static int ensure_capacity(elph_handle_s *h, int nrhs) {
     if (nrhs <= h->cap_rhs) return ELPH_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    drop_graphs(h);
     const size_t nd = (size_t)h->ndim, c = (size_t)nrhs;
     RC(dev_alloc(&h->d_stage_in, c * nd));
     RC(dev_alloc(&h->d_stage_out, c * nd));
@@ -388,11 +374,6 @@ extern "C" int elph_create(elph_handle *out, int kind, int64_t nsites, int64_t l
     h->N = nsites; h->L = ltau; h->nb = nbonds; h->ndim = nsites * ltau;
     h->npl = (int)((nsites + ELPH_WAVE - 1) / ELPH_WAVE);
     h->maxiter = h->ndim;   // ConjugateGradient ctor default (IterativeSolvers.jl:49-51)
-    // hipGraph replay of CG chunks is opt-in (ELPH_USE_GRAPH=1).  Eager launches are within ~3 % of the replay
-    // speed here (the stream stays queued ahead of the GPU: kernels take 3-6 us, a launch ~2 us), rocprofv3
-    // --kernel-trace cannot trace graph replays on this image, and eager keeps bench == profile.
-    const char *ug = getenv("ELPH_USE_GRAPH");
-    h->use_graph = (ug && ug[0] == '1');
 
     // bond tables, 0-based; colours = maximal runs of site-disjoint bonds (reproduces the groups of
     // checkerboard_groups!, Checkerboard.jl:471-515, for any table in checkerboard order, and stays
@@ -480,7 +461,6 @@ extern "C" int elph_destroy(elph_handle h) {
     if (!h) return ELPH_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    drop_graphs(h);
     elph_i_slabs_free(h);                             // (the slab handles of a large lattice: each is destroyed through here again)
     elph_shard_free(h);
     elph_hmc_free(h);
@@ -496,7 +476,7 @@ extern "C" int elph_destroy(elph_handle h) {
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_scal) (void)hipHostFree(h->h_scal);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    for (int k = 1; k < ELPH_SPLIT_MAX; ++k)
+    for (int k = 1; k < ELPH_SPLIT_PARTS; ++k)
         if (h->split_stream[k]) (void)hipStreamDestroy(h->split_stream[k]);
     if (h->split_ev) (void)hipEventDestroy(h->split_ev);
     delete h;
@@ -506,7 +486,6 @@ extern "C" int elph_destroy(elph_handle h) {
 extern "C" int elph_set_stream(elph_handle h, void *hip_stream) {
     CHECK_H(h);
     HIPCHK(hipStreamSynchronize(h->stream));
-    drop_graphs(h);
     if (hip_stream) {
         if (h->own_stream) { HIPCHK(hipStreamDestroy(h->stream)); h->own_stream = false; }
         h->stream = (hipStream_t)hip_stream;
@@ -537,7 +516,7 @@ extern "C" int elph_update_model_holstein(elph_handle h, const double *x, const 
     HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_stage_in, x, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }   // expansions were per chain
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }   // expansions were per chain
     RC(elph_launch_expV(h, h->d_stage_in, dtau));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
@@ -557,7 +536,6 @@ extern "C" int elph_update_model_holstein_chains(elph_handle h, int nchains, con
         RC(dev_alloc(&h->d_E, (size_t)nchains * nd));
         h->E_cap = (int64_t)nchains * (int64_t)nd;
     }
-    drop_graphs(h);
     h->nchains = nchains;
     HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -577,7 +555,7 @@ extern "C" int elph_set_expV(elph_handle h, const double *expnDtauV) {
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!expnDtauV) { elph_set_error("null argument"); return ELPH_E_ARG; }
     HIPCHK(hipMemcpyAsync(h->d_stage_in, expnDtauV, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }   // expansions were per chain
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }   // expansions were per chain
     RC(elph_launch_r2s(h, h->d_E, h->d_stage_in, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
@@ -603,7 +581,7 @@ extern "C" int elph_update_model_ssh(elph_handle h, const double *cosht, const d
     HIPCHK(hipMemcpy(h->d_E, expDtauMu, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice));
     RC(upload_lp_cs(h));
     h->mu_per_chain = false;
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }      // host tables describe ONE configuration
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }      // host tables describe ONE configuration
     h->cs_host_stale = false;
     h->have_E = true;
     return ELPH_OK;
@@ -677,7 +655,7 @@ extern "C" int elph_update_model_ssh_fields(elph_handle h, const double *x, int6
     if (nph > 0 && !x) { elph_set_error("null argument"); return ELPH_E_ARG; }
     RC(elph_i_ssh_upload_params(h, nph, cb_index, t_ph, alpha, alpha2, t_bare_cb, mu));
     h->mu_per_chain = false;
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }
     const size_t np = (size_t)nph;
     if (np > 0) HIPCHK(hipMemcpyAsync(h->d_ssh_x, x, np * (size_t)h->L * sizeof(double), hipMemcpyHostToDevice, h->stream));
     RC(elph_launch_ssh_update(h, h->d_ssh_x, (int)np, h->d_ssh_cb, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_slot, dtau));
@@ -780,30 +758,6 @@ extern "C" int elph_solver_set(elph_handle h, double tol, int64_t maxiter, doubl
     return ELPH_OK;
 }
 
-static int get_chunk_graph(elph_handle_s *h, int nrhs, int use_prec, hipGraphExec_t *out) {
-    for (auto &g : h->graphs)
-        if (g.nrhs == nrhs && g.use_prec == use_prec) { *out = g.exec; return ELPH_OK; }
-    hipGraph_t graph = nullptr;
-    HIPCHK(hipStreamSynchronize(h->stream));   // drain the eager init kernels before the stream goes into capture mode
-    HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = ELPH_OK;
-    for (int it = 0; it < h->chunk && rc == ELPH_OK; ++it) rc = elph_launch_cg_iteration(h, nrhs, use_prec);
-    if (rc == ELPH_OK && !h->dbg_copy_outside) {
-        hipError_t e = hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) { elph_set_error("capture memcpy: %s", hipGetErrorString(e)); rc = ELPH_E_HIP; }
-    }
-    hipError_t e = hipStreamEndCapture(h->stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) { elph_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) { elph_set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    h->graphs.push_back({nrhs, use_prec, exec});
-    *out = exec;
-    return ELPH_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // A large KPM-preconditioned batch as TWO half-batches on two streams.  One iteration is four dependent kernels (k_cg_ap, forward
 // transform + residual update, Chebyshev recursion, inverse transform + p/x-update), each ending in a drain of the whole chip before the
@@ -851,7 +805,6 @@ static int streams_overlap(hipStream_t a, hipStream_t b, bool *yes) {
 }
 
 static int make_overlapping_stream(elph_handle_s *h, hipStream_t *out) {
-    const char *ep = getenv("ELPH_SPLIT_PROBE");      // (0: take the first stream HIP hands out — the A/B)
     std::vector<hipStream_t> aside;
     hipStream_t chosen = nullptr;
     int rc = ELPH_OK;
@@ -859,7 +812,7 @@ static int make_overlapping_stream(elph_handle_s *h, hipStream_t *out) {
         hipStream_t s = nullptr;
         if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { elph_set_error("hipStreamCreate failed"); rc = ELPH_E_HIP; break; }
         bool ok = true;
-        if (!(ep && ep[0] == '0')) rc = streams_overlap(h->stream, s, &ok);
+        rc = streams_overlap(h->stream, s, &ok);
         if (rc == ELPH_OK && (ok || attempt == 7)) chosen = s;      // (eight in a row on the main stream's queue: take it, the form still works)
         else aside.push_back(s);
     }
@@ -872,7 +825,7 @@ static int make_overlapping_stream(elph_handle_s *h, hipStream_t *out) {
 struct SplitRun {
     bool on = false, ok = false, px_before = false;
     int ways = 0, n1 = 0;                                 // `ways` parts of n1 right-hand sides each; part 0 is the handle itself on its own stream
-    elph_handle_s *main = nullptr, *view[ELPH_SPLIT_MAX] = {};
+    elph_handle_s *main = nullptr, *view[ELPH_SPLIT_PARTS] = {};
     // A solve that leaves through an error return must not leave kernels of the other streams in flight behind it (they write d_x, d_p, d_r,
     // d_state of their parts while the caller's next step — ldiv's zero-fill, a retry, a new solve — runs on the main stream), nor the handle
     // believing in a p/x-fused solve that never happened.
@@ -887,16 +840,9 @@ struct SplitRun {
     }
 };
 
-// parts of the split form: ELPH_SPLIT_WAYS (2 … 8) [2]
-static int split_ways() {
-    const char *e = getenv("ELPH_SPLIT_WAYS");
-    const int w = e ? atoi(e) : 2;
-    return w < 2 ? 2 : (w > ELPH_SPLIT_MAX ? ELPH_SPLIT_MAX : w);
-}
-
 static bool split_legal(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
-    const int ways = split_ways();
-    if (!use_prec || hist || h->use_graph || nrhs < 2 * ways || (nrhs % ways) || h->solo_chain >= 0 || h->dot_hi > 0) return false;
+    const int ways = ELPH_SPLIT_PARTS;
+    if (!use_prec || hist || nrhs < 2 * ways || (nrhs % ways) || h->solo_chain >= 0 || h->dot_hi > 0) return false;
     const int n1 = nrhs / ways;
     if (n1 % std::max(1, h->nchains) || n1 % std::max(1, h->kpm_nch)) return false;
     const int keep = h->T_rhs_hint;
@@ -921,7 +867,7 @@ static bool split_wanted(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
 
 // after elph_launch_cg_init(h, nrhs, 1, …) on the main stream
 static int split_begin(elph_handle_s *h, int nrhs, SplitRun &S) {
-    S.ways = split_ways();
+    S.ways = ELPH_SPLIT_PARTS;
     S.n1 = nrhs / S.ways;
     S.main = h;
     S.view[0] = h;
@@ -948,7 +894,6 @@ static int split_begin(elph_handle_s *h, int nrhs, SplitRun &S) {
         v->d_state += 2 * r0; v->h_state += 2 * r0; v->d_alpha += r0;
         v->d_part += r0 * nrz;    // the three partial-sum arrays lie cap_rhs * nrz apart and are indexed [rhs][<= nrz]: one offset serves all
         v->stream = h->split_stream[k];
-        v->graphs.clear();
         HIPCHK(hipStreamWaitEvent(v->stream, h->split_ev, 0));
     }
     S.on = true;
@@ -985,12 +930,10 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
         const int64_t need = (int64_t)nrhs * (maxiter + 1);
         if (need > h->hist_cap) {
             HIPCHK(hipStreamSynchronize(h->stream));
-            drop_graphs(h);
             RC(dev_alloc(&h->d_hist, (size_t)need));
             h->hist_cap = need;
         }
     }
-    if (memcmp(&P, &h->cur_params, sizeof(P)) != 0) drop_graphs(h);   // parameters are baked into captured launches
     h->cur_params = P;
     // one solve of the cool-down after a resident kernel timed out — counted only for solves that WOULD have taken a resident kernel (either
     // kernel, either kind of solve): a stream of large streaming batches in between does not bring the retry forward, and a solve that
@@ -1081,13 +1024,13 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
         }
     }
 
-    const int64_t max_chunks = (maxiter + 1 + h->chunk - 1) / h->chunk + 1;
+    const int64_t max_chunks = (maxiter + 1 + ELPH_CG_CHUNK - 1) / ELPH_CG_CHUNK + 1;
     bool all_done = false;
     if (split_wanted(h, nrhs, use_prec, eps_hist != nullptr)) {
         SplitRun S;
         RC(split_begin(h, nrhs, S));
         for (int64_t c = 0; c < max_chunks && !all_done; ++c) {
-            for (int it = 0; it < h->chunk; ++it) RC(split_iteration(S, use_prec));
+            for (int it = 0; it < ELPH_CG_CHUNK; ++it) RC(split_iteration(S, use_prec));
             for (int k = 0; k < S.ways; ++k)
                 HIPCHK(hipMemcpyAsync(S.view[k]->h_state, S.view[k]->d_state, sizeof(CgState) * 2 * (size_t)S.n1, hipMemcpyDeviceToHost, S.view[k]->stream));
             for (int k = 0; k < S.ways; ++k) HIPCHK(hipStreamSynchronize(S.view[k]->stream));
@@ -1105,17 +1048,8 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
         return ELPH_OK;
     }
     for (int64_t c = 0; c < max_chunks && !all_done; ++c) {
-        if (h->use_graph) {
-            hipGraphExec_t exec;
-            RC(get_chunk_graph(h, nrhs, use_prec, &exec));
-            HIPCHK(hipGraphLaunch(exec, h->stream));
-            h->ap_count += h->chunk;   // even: the captured launch parities stay aligned with seq
-            if (h->dbg_copy_outside)
-                HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
-        } else {
-            for (int it = 0; it < h->chunk; ++it) RC(elph_launch_cg_iteration(h, nrhs, use_prec));
-            HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
-        }
+        for (int it = 0; it < ELPH_CG_CHUNK; ++it) RC(elph_launch_cg_iteration(h, nrhs, use_prec));
+        HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         all_done = true;
         for (int r = 0; r < nrhs; ++r) {
@@ -1175,10 +1109,10 @@ static int ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, 
             HIPCHK(hipMemcpyAsync(h->d_stage_in, h->d_z, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         }
         int64_t it1 = 0; double rs1 = 0; int fl1 = 0;
-        if (h->nchains > 1) { h->solo_chain = r % h->nchains; drop_graphs(h); }   // slot 0 must keep rhs r's fermion matrix
+        if (h->nchains > 1) h->solo_chain = r % h->nchains;   // slot 0 must keep rhs r's fermion matrix
         int rc1 = run_cg(h, 1, 0, h->tol, 10 * maxiter, h->kmax, &it1, nullptr);
         if (rc1 == ELPH_OK) rc1 = residual_and_flags(h, 1, &it1, h->maxiter, &rs1, &fl1);
-        if (h->solo_chain >= 0) { h->solo_chain = -1; drop_graphs(h); }
+        if (h->solo_chain >= 0) h->solo_chain = -1;
         RC(rc1);
         iters[r] = it1; resid[r] = rs1; flag[r] = fl1;
         if (r != 0) {
@@ -1198,7 +1132,6 @@ int elph_i_ensure_capacity(elph_handle_s *h, int nrhs) { return ensure_capacity(
 static int ssh_reserve_chains(elph_handle_s *h, int nchains) {
     if (nchains <= h->ssh_chain_cap) return ELPH_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    drop_graphs(h);
     const size_t L = (size_t)h->L, nb = (size_t)h->nb, per = (size_t)h->lp_ne * ELPH_WAVE, nc = (size_t)nchains;
     RC(dev_alloc(&h->d_c, nc * L * nb));
     RC(dev_alloc(&h->d_s, nc * L * nb));
@@ -1224,7 +1157,7 @@ int elph_i_reserve_chains(elph_handle_s *h, int nchains) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->kind == ELPH_MODEL_SSH) {
         RC(ssh_reserve_chains(h, nchains));
-        if (h->nchains != nchains) { h->nchains = nchains; drop_graphs(h); h->kpm_ready = false; }
+        if (h->nchains != nchains) { h->nchains = nchains; h->kpm_ready = false; }
         return ELPH_OK;
     }
     const int64_t need = (int64_t)nchains * h->ndim;
@@ -1233,10 +1166,9 @@ int elph_i_reserve_chains(elph_handle_s *h, int nchains) {
         h->E_cap = need;
         h->have_E = false;
     }
-    if (h->nchains != nchains) { h->nchains = nchains; drop_graphs(h); h->kpm_ready = false; }
+    if (h->nchains != nchains) { h->nchains = nchains; h->kpm_ready = false; }
     return ELPH_OK;
 }
-void elph_i_drop_graphs(elph_handle_s *h) { drop_graphs(h); }
 
 static int stage_in_dev(elph_handle_s *h, int nrhs, const double *X_dev, const double *B_dev) {
     RC(ensure_capacity(h, nrhs));
@@ -1337,7 +1269,6 @@ extern "C" int elph_cg_solve(elph_handle h, double *x, const double *b, double t
 int elph_i_set_dot_range(elph_handle_s *h, int64_t site_lo, int64_t site_hi) {
     if (site_lo < 0 || site_hi > h->N || site_lo >= site_hi) { elph_set_error("bad site range [%lld, %lld)", (long long)site_lo, (long long)site_hi); return ELPH_E_ARG; }
     HIPCHK(hipStreamSynchronize(h->stream));
-    drop_graphs(h);
     const bool all = (site_lo == 0 && site_hi == h->N);
     h->dot_lo = all ? 0 : (int)site_lo;
     h->dot_hi = all ? 0 : (int)site_hi;
@@ -1357,7 +1288,7 @@ extern "C" int elph_fermion_force_holstein(elph_handle h, const double *x, const
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!x || !lambda || !lambda2 || !mu || !phi_plus || !phi_minus || !dSfdx || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
     RC(ensure_capacity(h, 2));
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }   // expansions were per chain
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }   // expansions were per chain
     const size_t nd = (size_t)h->ndim, N = (size_t)h->N, bytes = nd * sizeof(double);
     // update_model! (HolsteinModels.jl:526-549) and x in layout S
     HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1783,7 +1714,6 @@ static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b
             for (size_t k = 0; k < per; ++k) { q0[k] = h->h_cbar[(size_t)c * h->nb + h->sq_bond[k]]; q1[k] = h->h_sbar[(size_t)c * h->nb + h->sq_bond[k]]; }
             for (size_t k = 1; k < per; ++k) uni = uni && q0[k] == q0[0] && q1[k] == q1[0];       // uniform within the chain
         }
-        if (uni != h->sq_uniform) drop_graphs(h);
         h->sq_uniform = uni;
         HIPCHK(hipMemcpy(h->d_sq_cbar, qc.data(), sizeof(double) * qc.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_sq_sbar, qs.data(), sizeof(double) * qs.size(), hipMemcpyHostToDevice));
@@ -1791,13 +1721,11 @@ static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b
     if (hop_fresh && h->hc_LX > 0) {
         bool uni = h->nb > 0 && !h->kpm_hop_per_chain;
         for (size_t k = 1; k < (size_t)h->nb && uni; ++k) uni = h->h_cbar[k] == h->h_cbar[0] && h->h_sbar[k] == h->h_sbar[0];
-        if (uni != h->hc_uniform) drop_graphs(h);
         h->hc_uniform = uni;
     }
     if (hop_fresh && h->pg_L > 0) {
         bool uni = h->nb > 0 && !h->kpm_hop_per_chain;
         for (size_t k = 1; k < (size_t)h->nb && uni; ++k) uni = h->h_cbar[k] == h->h_cbar[0] && h->h_sbar[k] == h->h_sbar[0];
-        if (uni != h->pg_uniform) drop_graphs(h);       // (a captured chunk holds the Chebyshev kernel chosen under the old flag)
         h->pg_uniform = uni;
     }
     h->kpm_hop_uploaded = true;
@@ -1893,7 +1821,6 @@ static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b
     h->kpm_active = any_active;
     if (changed || was_active != h->kpm_active) {
         RC(kpm_upload(h));
-        drop_graphs(h);   // KpmDev (lam_avg, lam_mag, active) is baked into captured kernel arguments
     }
     h->kpm_ready = true;
     return ELPH_OK;
@@ -1903,7 +1830,7 @@ static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b
 // field of its own — every rank contributes the Ē of its own rows and the sum is injected here (hmc.hip).  One chain.
 int elph_i_kpm_setup_ebar(elph_handle_s *h, const double *Ebar_host, const double *b_max, const double *b_min) {
     if (h->kind != ELPH_MODEL_HOLSTEIN || !h->kpm_created) { elph_set_error("Ē injection: a Holstein handle with elph_kpm_create done"); return ELPH_E_STATE; }
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }
     RC(kpm_reserve(h, 1));
     HIPCHK(hipMemcpy(h->d_Ebar, Ebar_host, sizeof(double) * (size_t)h->N, hipMemcpyHostToDevice));
     const bool had_E = h->have_E;
@@ -1923,7 +1850,7 @@ int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const doub
         elph_set_error("c̄ / s̄ injection: a bond-phonon handle with elph_kpm_create and one elph_update_model_ssh done");
         return ELPH_E_STATE;
     }
-    if (h->nchains != 1) { h->nchains = 1; drop_graphs(h); h->kpm_ready = false; }
+    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }
     h->h_cbar.assign(cbar_host, cbar_host + h->nb);
     h->h_sbar.assign(sbar_host, sbar_host + h->nb);
     h->csbar_external = true;
@@ -2156,6 +2083,7 @@ extern "C" int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, in
 extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int use_graph, double *ms_total) {
     CHECK_H(h);
     if (nrhs < 1 || nrhs > h->cap_rhs || reps < 1 || !ms_total || what < 0 || what > 12) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    if (use_graph) { elph_set_error("elph_bench_run: captured-graph replay is not supported (use_graph must be 0)"); return ELPH_E_UNSUPPORTED; }
     if (what == 12) {        // `reps` un-preconditioned iterations of every right-hand side in the slab form of a large lattice (slabs.hip): sum of the launches' event times
         const int prev_broken = h->wg_broken;
         h->wg_broken = false;
@@ -2219,35 +2147,11 @@ extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int u
         *ms_total = (double)ms;
         return ELPH_OK;
     }
-    hipGraphExec_t exec = nullptr;
-    const int chunk = ELPH_CG_CHUNK;
-    if (use_graph && h->use_graph && reps % chunk == 0) {
-        // capture `chunk` units once (not cached: the bench owns it)
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            elph_set_error("elph_bench_run: stream capture did not start");
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            return ELPH_E_HIP;
-        }
-        for (int i = 0; i < chunk && rc == ELPH_OK; ++i) rc = bench_launch_unit(h, what, nrhs);
-        hipError_t e = hipStreamEndCapture(h->stream, &graph);
-        if (rc == ELPH_OK && e != hipSuccess) { elph_set_error("capture: %s", hipGetErrorString(e)); rc = ELPH_E_HIP; }
-        if (rc == ELPH_OK) {
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            if (e != hipSuccess) { elph_set_error("instantiate: %s", hipGetErrorString(e)); rc = ELPH_E_HIP; }
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-    }
     if (rc == ELPH_OK) {
         hipError_t er = hipStreamSynchronize(h->stream);
         if (er == hipSuccess) er = hipEventRecord(e0, h->stream);
         if (er == hipSuccess) {
-            if (exec) {
-                for (int r = 0; r < reps / chunk && er == hipSuccess; ++r) er = hipGraphLaunch(exec, h->stream);
-            } else {
-                for (int r = 0; r < reps && rc == ELPH_OK; ++r) rc = bench_launch_unit(h, what, nrhs);
-            }
+            for (int r = 0; r < reps && rc == ELPH_OK; ++r) rc = bench_launch_unit(h, what, nrhs);
         }
         if (er == hipSuccess) er = hipEventRecord(e1, h->stream);
         if (er == hipSuccess) er = hipEventSynchronize(e1);
@@ -2256,7 +2160,6 @@ extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int u
         if (er != hipSuccess) { elph_set_error("elph_bench_run: %s", hipGetErrorString(er)); rc = ELPH_E_HIP; }
         else *ms_total = (double)ms;
     }
-    if (exec) (void)hipGraphExecDestroy(exec);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return rc;

@@ -22,9 +22,9 @@ extern "C" {
  *       kernel on slabs of rows, all on this device, one launch per right-hand side; prepare with what = 1; *ms_total = sum of the launches).
  * elph_bench_prepare: loads nrhs right-hand sides (B: host, reference layout, nrhs*ndim; NULL keeps what the
  *   last solve left on the device), zeroes x, seeds the CG state with tol = 0 (never converges).
- * elph_bench_run: launches `reps` units back-to-back on the handle's stream (captured graph chunks when
- *   use_graph != 0 and reps is a multiple of the chunk), brackets them with HIP events recorded on that
- *   stream, synchronises, and returns the event time in ms (total, not per rep). */
+ * elph_bench_run: launches `reps` units back-to-back on the handle's stream, brackets them with HIP events recorded on that
+ *   stream, synchronises, and returns the event time in ms (total, not per rep).  use_graph must be 0: the replay of
+ *   captured graphs was removed, and any other value returns ELPH_E_UNSUPPORTED (the parameter stays for the ABI). */
 int elph_bench_prepare(elph_handle h, int what, int nrhs, const double *B);
 int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int use_graph, double *ms_total);
 /* The solution block x the last elph_bench_run left on the device (nrhs right-hand sides, reference layout, nrhs*ndim doubles) copied to X:

@@ -25,7 +25,7 @@
 #define ELPH_WAVE 64
 #define ELPH_MAX_NPL 8          // sites per thread
 #define ELPH_MAX_SITES 8192      // generic kernels: workgroups of up to 1024 threads x 8 sites
-#define ELPH_CG_CHUNK 16        // CG iterations per captured graph launch
+#define ELPH_CG_CHUNK 16        // CG iterations between two reads of the CG states by the host (even: ping-pong parity)
 
 void elph_set_error(const char *fmt, ...);
 
@@ -87,7 +87,7 @@ __device__ __forceinline__ void ssh_chain_select(ModelDev &m, int rhs) {
 int elph_i_resident_wg_limit(const elph_handle_s *h);      // cg_wg.hip: workgroups of a resident kernel that can be co-resident on the handle's device
 
 // Solver parameters travel BY VALUE in the kernel arguments (never through a small H2D copy + scalar load).
-#define ELPH_SPLIT_MAX 8      // parts of a preconditioned batch on streams of their own (elph_api.hip: SplitRun)
+#define ELPH_SPLIT_PARTS 2    // parts of a preconditioned batch on streams of their own (elph_api.hip: SplitRun)
 
 struct CgParams {
     double tol, kmax;
@@ -207,7 +207,7 @@ struct elph_handle_s {
     bool fast_capable = false;             // lane-program kernels possible for this bond table (fast may be switched off)
     int solo_chain = -1;                   // >= 0: kernels see only this chain (single re-solve of one RHS of a chains batch)
     double *d_lam = nullptr;               // [3N] lambda, lambda2, mu staging
-    hipStream_t split_stream[8] = {};      // streams 1 … ways-1 + event of the split form of a preconditioned batch (elph_api.hip: SplitRun; [0] unused: the handle's own stream)
+    hipStream_t split_stream[ELPH_SPLIT_PARTS] = {};      // streams 1 … ways-1 + event of the split form of a preconditioned batch (elph_api.hip: SplitRun; [0] unused: the handle's own stream)
     hipEvent_t split_ev = nullptr;
     int T_rhs_hint = 0;                    // > 0: right-hand sides in flight when the slices per wave are chosen (two-stream batches: both halves)
     bool csbar_external = false;           // kpm_setup_core: h_cbar / h_sbar were filled by the caller (elph_i_kpm_setup_csbar)
@@ -296,13 +296,6 @@ struct elph_handle_s {
     double *d_alpha = nullptr;             // cap_rhs: CG step length handed from k_cg_xr to the next k_cg_ap
     double *h_scal = nullptr;              // pinned
 
-    // captured CG chunk graphs, keyed by (nrhs, use_prec)
-    struct GraphEntry { int nrhs, use_prec; hipGraphExec_t exec; };
-    std::vector<GraphEntry> graphs;
-    bool use_graph = false;                // hipGraph replay of CG chunks: opt-in (ELPH_USE_GRAPH=1), see DESIGN.md §3
-    int chunk = ELPH_CG_CHUNK;             // CG iterations per graph launch (even)
-    bool dbg_copy_outside = false;
-
     // KPM
     bool kpm_created = false, kpm_ready = false;
     int kpm_n = 20;
@@ -362,7 +355,6 @@ int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, 
 int elph_i_ensure_capacity(elph_handle_s *h, int nrhs);
 int elph_i_set_dot_range(elph_handle_s *h, int64_t site_lo, int64_t site_hi);   // inner products over [lo, hi) only (a shard's own sites)
 int elph_i_reserve_chains(elph_handle_s *h, int nchains);   // d_E for nchains configurations, h->nchains = nchains
-void elph_i_drop_graphs(elph_handle_s *h);
 void elph_hmc_free(elph_handle_s *h);
 void elph_shard_free(elph_handle_s *h);
 // sharded callers (shard.hip): hooks for hmc.hip
@@ -453,11 +445,16 @@ bool elph_pg_cheb_usable(const elph_handle_s *h);
 bool elph_pg_disorder_ok(const elph_handle_s *h);      // hopping disorder on this handle's patch shape (pgrid.hip)                       // pgrid.hip
 int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part = nullptr, int nrz = 0, const double *rr_part = nullptr);
 bool elph_pg_ap_usable(const elph_handle_s *h);
+bool elph_pg_mw();                                          // ELPH_PG_MW: patch shapes of several wavefronts per slice allowed (pgrid.hip)
+bool elph_no_sq();                                          // ELPH_NO_SQ=1: no register-exchange Chebyshev kernel (kernels.hip)
 bool elph_pg_mul_usable(const elph_handle_s *h);
 int elph_pg_mul(elph_handle_s *h, const ModelDev &m, int which, double *yS, const double *vS, int nvec);
 int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs, int parity, bool fused = false);      // fused: the p/x-fused iteration (reads the ready p)
 int elph_wg_cooldown_step(elph_handle_s *h);                // one solve of the cool-down after a time-out (both resident kernels call it)
 long long elph_shard_timeout_ms();                          // wait bound of the sharded solves (shard.hip)
+long long elph_wg_timeout_ms(long long dflt);               // ELPH_WG_TIMEOUT_MS, dflt when unset (cg_wg.hip)
+int elph_wg_cooldown();                                     // ELPH_WG_COOLDOWN (cg_wg.hip)
+char elph_slabs_test_timeout();                             // first character of ELPH_SLABS_TEST_TIMEOUT, 0 when unset (cg_wg.hip)
 // ---- workgroup-resident KPM-preconditioned CG (pcg_wg.hip): the whole preconditioned solve of 1..8 right-hand sides in one launch
 bool elph_pcg_wg_usable(const elph_handle_s *h, int nrhs);
 int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran);

@@ -979,7 +979,6 @@ __global__ void __launch_bounds__(1024) k_force_ssh(double *__restrict__ q, cons
 ModelDev elph_model_dev(const elph_handle_s *h) {
     ModelDev m;
     m.N = (int)h->N; m.L = (int)h->L; m.nb = (int)h->nb; m.ncol = h->ncol;
-    { static const bool nosweep = []() { const char *e = getenv("ELPH_DBG_NOSWEEP"); return e && e[0] == '1'; }(); if (nosweep) m.ncol = 0; }   // timing experiments only
     m.cs_tau_stride = (h->kind == ELPH_MODEL_SSH) ? (int)h->nb : 0;
     m.E_tau_stride = (h->kind == ELPH_MODEL_SSH) ? 0 : (int)h->N;
     m.nchains = h->nchains;
@@ -1182,9 +1181,15 @@ int elph_launch_ebar(elph_handle_s *h, int nch) {
 // that k_cg_ap_chunk<PX> and the inverse transform agree: the batched Holstein iteration on a four-colour lane program whose
 // Chebyshev kernel leaves r.z in frequency space (so that beta is known BEFORE the inverse transform), residual update folded into the
 // forward transform, streaming MFMA inverse with one row group, the templated chunk lengths.  ELPH_FUSE_PX=0: off (A/B, parity tests).
-static bool reg_cheb_form(const elph_handle_s *h) {      // a register-exchange Chebyshev kernel (the forms that deliver r.z in frequency space)
+// ELPH_NO_SQ=1: the Chebyshev recursion through the LDS slab where a register-exchange form exists (the A/B; read per call: the tests
+// switch both ways inside one process)
+bool elph_no_sq() {
     const char *e = getenv("ELPH_NO_SQ");
-    if (e && e[0] == '1') return false;
+    return e && e[0] == '1';
+}
+
+static bool reg_cheb_form(const elph_handle_s *h) {      // a register-exchange Chebyshev kernel (the forms that deliver r.z in frequency space)
+    if (elph_no_sq()) return false;
     return h->sq_P > 0 || (h->sq_L > 0 && h->sq_uniform && h->kind == ELPH_MODEL_HOLSTEIN) ||
            (h->hc_L > 0 && h->hc_uniform && h->kind == ELPH_MODEL_HOLSTEIN && (h->hc12 || h->hc_L * h->hc_L <= 64 || (h->hc_L % 2 == 0 && h->hc_L <= 16)));
 }
@@ -1206,8 +1211,6 @@ static bool px_plan(elph_handle_s *h, int nrhs) {
         const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
         CgBufs B = make_bufs(h, nrhs);
         if (!(B.dot_lo == 0 && B.dot_hi == N) || B.npap != L || 2 * Lo2 > B.nrz) return false;
-        const char *ef = getenv("ELPH_FREQ_RZ");
-        if (ef && ef[0] == '0') return false;
         return elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs);
     }
     if (!h->fast) {
@@ -1218,8 +1221,6 @@ static bool px_plan(elph_handle_s *h, int nrhs) {
         const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
         CgBufs B = make_bufs(h, nrhs);
         if (!(B.dot_lo == 0 && B.dot_hi == N) || B.npap != L || Lo2 > B.nrz || elph_pg_cheb_usable(h)) return false;
-        const char *ef = getenv("ELPH_FREQ_RZ");
-        if (ef && ef[0] == '0') return false;
         return elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs);
     }
     if (h->lp_mc != 4) {
@@ -1233,23 +1234,19 @@ static bool px_plan(elph_handle_s *h, int nrhs) {
         CgBufs B = make_bufs(h, nrhs);
         h->cur_params = kp; h->px_via_pg = keep; h->px_solve = keeps;
         if (!(B.dot_lo == 0 && B.dot_hi == N) || B.npap != L || 2 * Lo2 > B.nrz) return false;
-        const char *ef = getenv("ELPH_FREQ_RZ");
-        if (ef && ef[0] == '0') return false;
         return elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs);
     }
     const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
     CgBufs B = make_bufs(h, nrhs);
     if (!(B.dot_lo == 0 && B.dot_hi == N) || !elph_dft_mfma_xr_usable(h, N, nrhs)) return false;      // the iteration takes cg_mode 2
-    const char *ef = getenv("ELPH_FREQ_RZ");
-    if ((ef && ef[0] == '0') || 2 * Lo2 > B.nrz) return false;
+    if (2 * Lo2 > B.nrz) return false;
     // (r.z in frequency space comes from a register-exchange Chebyshev kernel — or, round 6, from the patch-form one: square L = 18, 20 of this family)
     // or from the Re / Im recursion through the LDS slab (k_kpm_cheb_ri: square L = 22, disordered honeycomb lattices, ...; ELPH_LDS_CHEB_PX=0 and
     // ELPH_NO_SQ=1 — the A/B that forces that recursion on a lattice with a register form — keep the unfused iteration)
     if (!reg_cheb_form(h) && !(elph_pg_cheb_usable(h) && pg_px_allowed())) {
-        const char *el = getenv("ELPH_LDS_CHEB_PX"), *ens = getenv("ELPH_NO_SQ");
-        if ((el && el[0] == '0') || (ens && ens[0] == '1') || elph_pg_cheb_usable(h)) return false;
+        const char *el = getenv("ELPH_LDS_CHEB_PX");
+        if ((el && el[0] == '0') || elph_no_sq() || elph_pg_cheb_usable(h)) return false;
     }
-    { const char *ec = getenv("ELPH_CHEB_COMPLEX"); if (ec && ec[0] == '1') return false; }
     const int T = elph_choose_T_px(h, h->T_rhs_hint > 0 ? h->T_rhs_hint : nrhs);
     if (!(T > 1 && L % T == 0 && (T == 20 || T == 16 || T == 10 || T == 8 || T == 5 || T == 4 || T == 2))) return false;
     return elph_dft_mfma_px_usable(h, N, nrhs);
@@ -1281,11 +1278,9 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
     // FOLD (dft_mfma.hip: XrFuse): in the batched CG iteration (forward transform with the residual update folded in, register-exchange
     // Chebyshev kernel with the r.z partials in frequency space) the frequencies of order 1 — z_w = |c0|^2 r_w — are finished by the
     // forward transform; the Chebyshev kernel keeps their slot bookkeeping only
-    static const bool freq_rz_on = []() { const char *e = getenv("ELPH_FREQ_RZ"); return !(e && e[0] == '0'); }();
     const int nct = (N + 15) / 16;
-    const bool no_sq = []() { const char *e = getenv("ELPH_NO_SQ"); return e && e[0] == '1'; }();                    // (A/B: the LDS recursion, which knows no fold)
-    const bool reg_cheb = !no_sq && (h->sq_P > 0 || (h->sq_L > 0 && h->sq_uniform && h->kind == ELPH_MODEL_HOLSTEIN) || (h->hc_L > 0 && h->hc_uniform && h->kind == ELPH_MODEL_HOLSTEIN && (h->hc12 || h->hc_L * h->hc_L <= 64 || (h->hc_L % 2 == 0 && h->hc_L <= 16))));     // (a register-exchange Chebyshev kernel: the one that knows the fold)
-    const bool fold = cg_mode == 2 && h->fast && reg_cheb && h->lp_mc == 4 && freq_rz_on && h->d_kfold &&
+    const bool reg_cheb = reg_cheb_form(h);      // (a register-exchange Chebyshev kernel: the one that knows the fold; ELPH_NO_SQ=1 forces the LDS recursion, which does not)
+    const bool fold = cg_mode == 2 && h->fast && reg_cheb && h->lp_mc == 4 && h->d_kfold &&
                       2 * Lo2 + nct <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && elph_dft_mfma_fold_usable(h);
     if (!(parts & 1)) {
     } else if (cg_mode == 2) {
@@ -1304,19 +1299,16 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
     } else if (elph_pg_cheb_usable(h)) {
         // an even-L square lattice beyond 16 x 16 (L = 18 ... 32), uniform hopping: the recursion in registers, a patch of sites per lane
         // (whether the lattice still fits the lane-program family — 18 x 18, 20 x 20 — or only the generic kernels)
-        static const bool freq_rz = []() { const char *e = getenv("ELPH_FREQ_RZ"); return !(e && e[0] == '0'); }();
-        const bool want = cg_mode && freq_rz && 2 * Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && h->px_solve;      // (r.z in frequency space: the p/x-fused iteration's)
+        const bool want = cg_mode && 2 * Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && h->px_solve;      // (r.z in frequency space: the p/x-fused iteration's)
         int rcp = elph_pg_kpm_cheb(h, nrhs, st, want ? B.rz : nullptr, B.nrz, B.rr);
         if (rcp) return rcp;
         rz_done = want;
     } else if (h->fast) {
-        static const bool freq_rz = []() { const char *e = getenv("ELPH_FREQ_RZ"); return !(e && e[0] == '0'); }();
-        const bool want = cg_mode && freq_rz && 2 * Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N;
+        const bool want = cg_mode && 2 * Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N;
         int rcf = elph_fast_kpm_cheb(h, nrhs, st, want ? B.rz : nullptr, B.nrz, &rz_done, B.rr, (fold && want) ? nct : 0);
         if (rcf) return rcf;
     } else {
-        static const bool gfreq_rz = []() { const char *e = getenv("ELPH_FREQ_RZ"); return !(e && e[0] == '0'); }();
-        const bool gwant = cg_mode && gfreq_rz && Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && h->px_solve;      // (the p/x-fused iteration of the generic family)
+        const bool gwant = cg_mode && Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && h->px_solve;      // (the p/x-fused iteration of the generic family)
         // one thread per bond of the largest colour (up to 1024): a colour is then one LDS round trip per thread; the bond
         // program rides in LDS when it fits next to the slab
         int maxcol = 1;
@@ -1353,9 +1345,8 @@ int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero) {
     h->ap_count = 0;
     const int N = (int)h->N, L = (int)h->L;
     int rc = ELPH_OK;
-    {   // the form of this solve's preconditioned iteration; a captured graph of the other form is dropped
+    {   // the form of this solve's preconditioned iteration
         const bool px = use_prec && h->kpm_ready && px_plan(h, nrhs);
-        if (px != h->px_solve) elph_i_drop_graphs(h);
         h->px_solve = px;
         h->px_via_pg = px && h->fast && h->lp_mc != 4;
     }

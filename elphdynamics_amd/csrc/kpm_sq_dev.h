@@ -15,42 +15,17 @@ struct SqLane {
 
 #define SQC(col, i) (UNI ? T.cu : T.c[col][i])
 #define SQS(col, i) (UNI ? T.su : T.s[col][i])
+// the 8 x 8 lattice, one site per lane (P = 1): every colour is a lane permutation.  (The 2 x 2 patch layout of the 16 x 16 lattice that
+// this apply also served was replaced by the row layout, sq16_cb_apply, and removed.)
 template <int P, bool REVERSE, bool UNI>
 __device__ __forceinline__ void sq_cb_apply(double (&v)[P * P], const SqLane<P> &T) {
-    // slot index: dx + P*dy
+    static_assert(P == 1, "sq_cb_apply: one site per lane");
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
         const int col = REVERSE ? 3 - cc : cc;
-        if (P == 2) {
-            if (col == 0 || col == 2) {          // in-lane pairs: (0,d)-(1,d) along x, (d,0)-(d,1) along y
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    const int i = (col == 0) ? (0 + 2 * d) : (d + 0), j = (col == 0) ? (1 + 2 * d) : (d + 2);
-                    const double t0 = v[i], t1 = v[j];
-                    v[i] = SQC(col, i) * t0 + SQS(col, i) * t1;
-                    v[j] = SQC(col, j) * t1 + SQS(col, j) * t0;
-                }
-            } else {                             // cross-lane: my high-side sites pair with the +neighbour's low-side sites
-                const int up = (col == 1) ? T.xp : T.yp, dn = (col == 1) ? T.xm : T.ym;
-                double fromUp[2], fromDn[2];
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    const int lo = (col == 1) ? (0 + 2 * d) : (d + 0), hi = (col == 1) ? (1 + 2 * d) : (d + 2);
-                    fromUp[d] = __shfl(v[lo], up, WAVE);      // neighbour's low-side value -> partner of my high-side site
-                    fromDn[d] = __shfl(v[hi], dn, WAVE);      // neighbour's high-side value -> partner of my low-side site
-                }
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    const int lo = (col == 1) ? (0 + 2 * d) : (d + 0), hi = (col == 1) ? (1 + 2 * d) : (d + 2);
-                    v[hi] = SQC(col, hi) * v[hi] + SQS(col, hi) * fromUp[d];
-                    v[lo] = SQC(col, lo) * v[lo] + SQS(col, lo) * fromDn[d];
-                }
-            }
-        } else {                                 // P == 1: one site per lane, every colour is a lane permutation
-            const int partner = (col == 0) ? T.xe : (col == 2) ? T.ye : (col == 1) ? T.xp : T.yp;   // xp/yp hold the odd-colour partner
-            const double t = __shfl(v[0], partner, WAVE);
-            v[0] = SQC(col, 0) * v[0] + SQS(col, 0) * t;
-        }
+        const int partner = (col == 0) ? T.xe : (col == 2) ? T.ye : (col == 1) ? T.xp : T.yp;   // xp/yp hold the odd-colour partner
+        const double t = __shfl(v[0], partner, WAVE);
+        v[0] = SQC(col, 0) * v[0] + SQS(col, 0) * t;
     }
 }
 

@@ -493,12 +493,17 @@ int pg_check(const char *what) {
 // p/x-fused k_cg_ap_pg 70 -> 61, 100 -> 92, 157 -> 139; the iteration 250 -> 233, 318 -> 291, 477 -> 443, 589 -> 546; 28 x 28 at 64: 281 -> 261.  The
 // UNFUSED k_cg_ap_pg and k_mul_pg keep the handle's shape (72 right-hand sides: 184 -> 203 us the wrong way, 96: 273 -> 252).
 // `big`: a launch that may switch (the recursion, the fused k_cg_ap).  ELPH_PG_2X2_FROM=n: from n right-hand sides [48] (A/B; 0: never).
+// ELPH_PG_MW=0: one wavefront per slice, here and in the patch shape a handle chooses (elph_api.hip) — read per call
+bool elph_pg_mw() {
+    const char *e = getenv("ELPH_PG_MW");
+    return !(e && e[0] == '0');
+}
 static void pg_launch_shape(const elph_handle_s *h, int nrhs, bool big, int *px, int *py, int *nw) {
     *px = h->pg_PX; *py = h->pg_PY; *nw = h->pg_NW > 1 ? h->pg_NW : 1;
     if (!big || *nw != 1) return;
-    const char *e = getenv("ELPH_PG_2X2_FROM"), *em = getenv("ELPH_PG_MW");
+    const char *e = getenv("ELPH_PG_2X2_FROM");
     const int from = e ? atoi(e) : 48;
-    if (from <= 0 || nrhs < from || (em && em[0] == '0')) return;
+    if (from <= 0 || nrhs < from || !elph_pg_mw()) return;
     if (h->pg_kind == 1 && *px * *py >= 16 && ((h->pg_L / 2) * (h->pg_L / 2) + 63) / 64 <= 6 && h->pg_uniform_c) {      // 4 x 4 (28, 32), 2 x 10 (30: 96 right-hand sides on two streams 477 -> 415 us), 4 x 6 (36: 472 -> 459 at 64)
         *px = 2; *py = 2; *nw = ((h->pg_L / 2) * (h->pg_L / 2) + 63) / 64;      // 28: 196 threads, 32: 256 — four wavefronts; 30: 225 — four; 36: 324 — six
     } else if (h->pg_kind == 2 && *px == 4 && *py == 2) {
@@ -509,10 +514,15 @@ static void pg_launch_shape(const elph_handle_s *h, int nrhs, bool big, int *px,
     }
 }
 
-// Can the per-frequency recursion of this handle run in the patch layout?  (ELPH_NO_PG=1: the generic kernel, the A/B — read per call)
-bool elph_pg_cheb_usable(const elph_handle_s *h) {
+// ELPH_NO_PG=1: the generic kernels instead of the patch layout, the A/B — read per call
+static bool no_pg() {
     const char *e = getenv("ELPH_NO_PG");
-    return h->pg_L > 0 && (h->pg_uniform || elph_pg_disorder_ok(h)) && h->kind == ELPH_MODEL_HOLSTEIN && !(e && e[0] == '1');
+    return e && e[0] == '1';
+}
+
+// Can the per-frequency recursion of this handle run in the patch layout?
+bool elph_pg_cheb_usable(const elph_handle_s *h) {
+    return h->pg_L > 0 && (h->pg_uniform || elph_pg_disorder_ok(h)) && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
 }
 
 // hopping disorder on this handle's patch shape (square lattices whose (cosh, sinh) table fits the LDS: pgrid::patch_takes_disorder; ELPH_PG_DIS=0:
@@ -583,8 +593,7 @@ int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_p
 
 // the mat-vec kernel of the CG iteration in the patch layout (generic family only: the lane-program family has its own chunked kernel)
 bool elph_pg_ap_usable(const elph_handle_s *h) {
-    const char *e = getenv("ELPH_NO_PG");
-    return h->pg_L > 0 && !h->fast && h->kind == ELPH_MODEL_HOLSTEIN && !(e && e[0] == '1');
+    return h->pg_L > 0 && !h->fast && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
 }
 
 int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs, int parity, bool fused) {
@@ -595,13 +604,11 @@ int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs
     // filled round costs more than the two halo slices per chunk (measured at L = 32, 72 right-hand sides: 16 slices per wave = 720
     // waves 98 us, 10 = 1152 waves 140 us; profiles/r04/pgrid_large_lattices.log); beyond one round of 40-slice chunks: 20
     const int L = (int)h->L;
-    static const int forceT = []() { const char *e = getenv("ELPH_PG_T"); return e ? atoi(e) : 0; }();
     int px, py, nw;
     pg_launch_shape(h, nrhs, fused, &px, &py, &nw);
     const long long slots = 1024LL * ((h->pg_kind != 2 && px * py <= 8) ? 2 : 1) / nw;      // (a slice of several wavefronts holds as many slots)
     int T = 20;
     for (int c : {1, 2, 4, 5, 8, 10, 16, 20, 32, 40}) { if ((long long)nrhs * ((L + c - 1) / c) <= slots) { T = c; break; } }
-    if (forceT > 0) T = forceT;
     T = std::max(1, std::min(T, L));
     const int nch = (L + T - 1) / T;
     const dim3 grid((unsigned)(nrhs * nch));

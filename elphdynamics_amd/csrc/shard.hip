@@ -543,8 +543,8 @@ static int launch_ok(const char *what) {
 // behind it (a time-out is ELPH_E_HIP), so it keeps the long bound; the 2 s default of ELPH_WG_TIMEOUT_MS belongs to the un-sharded
 // resident kernels, which fall back to the streaming iteration.
 long long elph_shard_timeout_ms() {
-    const char *es = getenv("ELPH_SHARD_TIMEOUT_MS"), *ew = getenv("ELPH_WG_TIMEOUT_MS");
-    const long long ms = es ? atoll(es) : (ew ? atoll(ew) : 20000);
+    const char *es = getenv("ELPH_SHARD_TIMEOUT_MS");
+    const long long ms = es ? atoll(es) : elph_wg_timeout_ms(20000);
     return ms > 0 ? ms : 20000;
 }
 static long long shard_timeout_ticks() { return elph_shard_timeout_ms() * 100000LL; }      // wall_clock64 runs at 100 MHz

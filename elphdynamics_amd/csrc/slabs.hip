@@ -32,7 +32,6 @@ struct SlabSet {
     int P = 0, Nloc = 0, own_lo = 0, own_n = 0, hi = 0;
     int nsets = 0;                          // sets of P slab handles: set k solves right-hand side k of a pair in the same launch (own mailboxes)
     int G = 0;                              // workgroups per slab
-    int ring_row = 0;                       // > 0: sites per row of the recognised square lattice — the slabs are closed into rings (add_set)
     std::vector<elph_handle_s *> hs;        // [nsets][P]
     std::vector<int *> d_g;                 // [P][Nloc] site of the parent lattice of every slab site
     void *h_args = nullptr, *d_args = nullptr;
@@ -62,11 +61,6 @@ void closure(const elph_handle_s *h, int start, int n, std::vector<char> &S, std
     };
     for (int b = 0; b < nb; ++b) visit(b);             // M^T backwards (bond 0 was applied last) ...
     for (int b = nb - 1; b >= 0; --b) visit(b);        // ... then M backwards
-}
-
-bool uniform_hop(const elph_handle_s *h) {
-    for (int64_t n = 1; n < h->nb; ++n) if (h->h_c[(size_t)n] != h->h_c[0] || h->h_s[(size_t)n] != h->h_s[0]) return false;
-    return h->nb > 0;
 }
 
 void free_set(SlabSet *S) {
@@ -116,47 +110,14 @@ int add_set(elph_handle_s *h, SlabSet *S) {
         closure(h, q * n, n, Cs, need);
         std::vector<int64_t> tab;
         std::vector<double> c, s;
-        // THE RING (as sharded.py: SpatialSlabs(ring=True)): on a square lattice the library recognised (row = L sites) the bonds that leave
-        // the slab through its last row re-enter at its first row — the own sites do not see the difference (the ring bond lies beyond the
-        // closure that fixed the ghost rows; it only stirs the outermost ghost rows, whose values nothing reads), but the slab becomes a
-        // periodic rectangle in the reference's colouring, which the GRID form of the resident kernel takes (2 x 2 patches in registers
-        // instead of the lane program's LDS slabs).  Kept only if it leaves the colouring alone.
-        for (int pass = (S->ring_row > 0 ? 0 : 1); pass < 2; ++pass) {
-            const bool ring = pass == 0;
-            tab.clear(); c.clear(); s.clear();
-            const int row = S->ring_row, top = g[(size_t)Nloc - 1];          // (the slab's last site)
-            for (int b = 0; b < nb; ++b) {
-                int i = loc[(size_t)h->h_bi[(size_t)b]], j = loc[(size_t)h->h_bj[(size_t)b]];
-                if (ring && (i < 0) != (j < 0)) {
-                    const int in = (i < 0) ? j : i, out = (i < 0) ? h->h_bi[(size_t)b] : h->h_bj[(size_t)b];
-                    const int k = ((out - top - 1) % N + N) % N;              // the outer end is site k of the row above the slab
-                    if (in >= Nloc - row && k < row) { if (i < 0) i = k; else j = k; }
-                }
-                if (i < 0 || j < 0) {
-                    if (need[(size_t)b]) { elph_set_error("slabs: a bond the own sites depend on leaves the slab"); rc = ELPH_E_UNSUPPORTED; break; }
-                    continue;
-                }
-                tab.push_back(i + 1); tab.push_back(j + 1);
-                c.push_back(h->h_c[(size_t)b]); s.push_back(h->h_s[(size_t)b]);
+        for (int b = 0; b < nb; ++b) {
+            const int i = loc[(size_t)h->h_bi[(size_t)b]], j = loc[(size_t)h->h_bj[(size_t)b]];
+            if (i < 0 || j < 0) {
+                if (need[(size_t)b]) { elph_set_error("slabs: a bond the own sites depend on leaves the slab"); rc = ELPH_E_UNSUPPORTED; break; }
+                continue;
             }
-            if (rc || !ring) break;
-            // colours = maximal runs of site-disjoint bonds (elph_create): the ring must not add one
-            auto ncolours = [&](const std::vector<int64_t> &t) {
-                std::vector<char> used((size_t)Nloc, 0);
-                int nc = t.empty() ? 0 : 1;
-                for (size_t b2 = 0; b2 + 1 < t.size(); b2 += 2) {
-                    const size_t a = (size_t)t[b2] - 1, d = (size_t)t[b2 + 1] - 1;
-                    if (used[a] || used[d]) { ++nc; std::fill(used.begin(), used.end(), 0); }
-                    used[a] = used[d] = 1;
-                }
-                return nc;
-            };
-            std::vector<int64_t> open_tab;
-            for (int b = 0; b < nb; ++b) {
-                const int i = loc[(size_t)h->h_bi[(size_t)b]], j = loc[(size_t)h->h_bj[(size_t)b]];
-                if (i >= 0 && j >= 0) { open_tab.push_back(i + 1); open_tab.push_back(j + 1); }
-            }
-            if (ncolours(tab) == ncolours(open_tab)) break;      // the ring stands
+            tab.push_back(i + 1); tab.push_back(j + 1);
+            c.push_back(h->h_c[(size_t)b]); s.push_back(h->h_s[(size_t)b]);
         }
         if (rc) break;
         elph_handle sh = nullptr;
@@ -187,16 +148,8 @@ int add_set(elph_handle_s *h, SlabSet *S) {
 int build(elph_handle_s *h, int P, int lo, int hi, int G, SlabSet **out) {
     SlabSet *S = new SlabSet();
     S->P = P; S->Nloc = lo + (int)h->N / P + hi; S->own_lo = lo; S->own_n = (int)h->N / P; S->hi = hi; S->G = G;
-    {   // rings on a recognised square lattice whose slabs are whole rows: an even number of them, at least four, at most 64 lanes of 2 x 2 patches.
-        // OPT-IN (ELPH_SLABS_RING=1): measured slower — the GRID form of the sharded kernel sits at 256 registers with scratch: 15.5 us per
-        // iteration against 11.0 (24 x 24) / 12.5 (32 x 32) in the lane program (profiles/r05/slabs_resident_large_lattices.log)
-        const char *er = getenv("ELPH_SLABS_RING");
-        const int row = (h->pg_kind == 1) ? h->pg_L : 0;
-        if ((er && er[0] == '1') && row > 0 && (int64_t)row * row == h->N && S->Nloc % row == 0 && lo % row == 0 && S->own_n % row == 0 && (row & 1) == 0) {
-            const int rows = S->Nloc / row;
-            if (rows >= 4 && (rows & 1) == 0 && (row / 2) * (rows / 2) <= 64 && uniform_hop(h)) S->ring_row = row;
-        }
-    }
+    // (slabs closed into rings, which the GRID form of the sharded kernel takes, measured slower than the lane program — 15.5 us per
+    //  iteration against 11.0 / 12.5 — and were removed: profiles/r05/slabs_resident_large_lattices.log)
     int rc = add_set(h, S);
     if (rc == ELPH_OK) {
         const size_t bytes = 2 * (size_t)P * elph_wg_rank_args_bytes();
@@ -229,6 +182,9 @@ void elph_i_slabs_free(elph_handle_s *h) {
     free_set(static_cast<SlabSet *>(h->slabs));
     h->slabs = nullptr;
 }
+
+// ELPH_SLABS_DEBUG: print the decomposition of a handle, or why there is none
+static bool slabs_debug() { return getenv("ELPH_SLABS_DEBUG") != nullptr; }
 
 // Does the resident slab form serve an un-preconditioned solve of nrhs right-hand sides on this handle?  Decided by rule from measurements
 // (profiles/r05/slabs_resident_large_lattices.log; Ltau = 160, one right-hand side, us per iteration, slab form / streaming pair):
@@ -279,11 +235,11 @@ bool elph_i_slabs_usable(elph_handle_s *h, int nrhs) {
             if (build(h, c.P, c.lo, c.hi, G, &S) != ELPH_OK) { why = "a slab handle could not be made"; continue; }
             // (that every slab takes the lane-program form of the sharded kernel is checked by the launch set-up of the first solve)
             h->slabs = S;
-            if (getenv("ELPH_SLABS_DEBUG")) fprintf(stderr, "[slabs] N = %lld: %d slabs of %d own + %d / %d ghost sites, %d workgroups each\n", (long long)h->N, c.P, S->own_n, c.lo, c.hi, G);
+            if (slabs_debug()) fprintf(stderr, "[slabs] N = %lld: %d slabs of %d own + %d / %d ghost sites, %d workgroups each\n", (long long)h->N, c.P, S->own_n, c.lo, c.hi, G);
             return nrhs == 1 || force == 1 || 2LL * S->P * S->G <= elph_i_resident_wg_limit(h);
         }
     }
-    if (getenv("ELPH_SLABS_DEBUG")) fprintf(stderr, "[slabs] N = %lld: not decomposed (%s)\n", (long long)h->N, why);
+    if (slabs_debug()) fprintf(stderr, "[slabs] N = %lld: not decomposed (%s)\n", (long long)h->N, why);
     return false;
 }
 
@@ -312,10 +268,8 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
         hipLaunchKernelGGL(k_slab_gather, gg, dim3(256), 0, h->stream, ptrs_of(S, k, 1), (const double *)h->d_E, N, Nloc);
         for (int q = 0; q < Pq; ++q) S->hs[(size_t)k * Pq + q]->have_E = true;
     }
-    const char *et = getenv("ELPH_WG_TIMEOUT_MS");
-    const long long timeout_ms = et ? std::max(1, atoi(et)) : 2000;
-    const char *etest = getenv("ELPH_SLABS_TEST_TIMEOUT");
-    const bool test_give_up = etest && etest[0] == '1';      // (tests: 1 = the launch is taken to have given up — the host side of a time-out; 2 = a real one, cg_wg.hip)
+    const long long timeout_ms = std::max(1LL, elph_wg_timeout_ms(2000));
+    const bool test_give_up = elph_slabs_test_timeout() == '1';      // (tests: 1 = the launch is taken to have given up — the host side of a time-out; 2 = a real one, cg_wg.hip)
     double ms_sum = 0.0;
     for (int r = 0; r < nrhs;) {
         const int ns = (pairs && r + 1 < nrhs) ? 2 : 1;        // right-hand sides of this launch
@@ -338,8 +292,7 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
             // a time-out inside the launch (the abort word was raised — and nothing else: an event, copy or launch failure comes back as
             // ELPH_E_HIP and is returned below): cool down like the other resident kernels, streaming takes over
             h->wg_broken = true;
-            const char *ec = getenv("ELPH_WG_COOLDOWN");
-            h->wg_cooldown = ec ? std::max(1, atoi(ec)) : 16;
+            h->wg_cooldown = elph_wg_cooldown();
             ++h->wg_fallbacks;
             HIPCHK(hipMemsetAsync(h->d_x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
             return ELPH_OK;

@@ -119,6 +119,26 @@ def test_every_environment_switch_is_in_the_design_table():
     table = design[design.index("## 9. Environment switches"):]
     missing = sorted(n for n in names if n not in table)
     assert len(names) > 30 and not missing, missing
+    # ... and the other way: every switch named in the first column of the table is still read somewhere (a retired switch leaves no row)
+    listed = set()
+    for line in table.splitlines():
+        cells = line.split("|")
+        if line.startswith("| `ELPH_") and len(cells) > 2:
+            listed |= set(re.findall(r"ELPH_[A-Z0-9_]+", cells[1]))
+    csrc, py = [], []
+    for f in glob.glob(os.path.join(ROOT, "elphdynamics_amd", "csrc", "*")):
+        if os.path.isfile(f):
+            csrc.append(open(f, errors="replace").read())
+    for pattern in ("elphdynamics_amd/*.py", "bench.py", "tests/**/*.py", "tools/**/*.py"):
+        for f in glob.glob(os.path.join(ROOT, pattern), recursive=True):
+            py.append(open(f, errors="replace").read())
+    csrc, py = "\n".join(csrc), "\n".join(py)
+
+    def read(n):   # getenv or a preprocessor condition in csrc; os.environ[...] / os.environ.get(...) in Python
+        return (re.search(r'getenv\("' + n + r'"\)', csrc) or re.search(r'^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b[^\n]*\b' + n + r'\b', csrc, re.M)
+                or re.search(r'environ(?:\.get|\.pop|\.setdefault)?[\(\[]\s*["\']' + n + r'["\']', py))
+    stale = sorted(n for n in listed if not read(n))
+    assert len(listed) > 30 and not stale, stale
 
 
 def test_tools_compile_and_are_indexed():
