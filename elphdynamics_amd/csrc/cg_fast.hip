@@ -32,25 +32,43 @@ namespace lp6 {
 int elph_fast_mul(elph_handle_s *h, int which, double *yS, const double *vS, int nvec);
 int elph_fast_cg_ap(elph_handle_s *h, const CgBufs &B, int nrhs, int parity, bool px);
 int elph_fast_cg_xr(elph_handle_s *h, const CgBufs &B, int nrhs, int parity);
-int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, bool *did_rz, const double *rr_part, int fold_nct);
+int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, double *rz_part, int nrz, const double *rr_part, int fold_nct);
 }  // namespace lp6
 // ---- dispatch on the handle's lane-program width ------------------------------------------------------------
 int elph_fast_mul(elph_handle_s *h, int which, double *yS, const double *vS, int nvec) {
     return h->lp_mc == 4 ? lp4::elph_fast_mul(h, which, yS, vS, nvec) : lp6::elph_fast_mul(h, which, yS, vS, nvec);
 }
 int elph_choose_T(const elph_handle_s *h, int nrhs) { return lp4::elph_choose_T(h, nrhs); }
-int elph_choose_T_px(const elph_handle_s *h, int nrhs) { return lp4::elph_choose_T_px(h, nrhs); }
+int elph_choose_T_px(const elph_handle_s *h, int nrhs, bool two_streams) { return lp4::elph_choose_T_px(h, nrhs, two_streams); }
 int elph_fast_cg_ap(elph_handle_s *h, const CgBufs &B, int nrhs, int parity, bool px) {
-    // the p/x-fused step of a preconditioned batch on the 16 x 16 square lattice: the checkerboard in registers (cg_sq16.hip)
-    h->sq16_ap_ran = px && B.npap > 0 && B.npap < (int)h->L && (int)h->L % B.npap == 0 && elph_sq16_ap_usable(h, (int)h->L / B.npap);
-    if (h->sq16_ap_ran) return elph_sq16_cg_ap_px(h, B, nrhs, parity);
     return h->lp_mc == 4 ? lp4::elph_fast_cg_ap(h, B, nrhs, parity, px) : lp6::elph_fast_cg_ap(h, B, nrhs, parity, px);
 }
 int elph_fast_cg_xr(elph_handle_s *h, const CgBufs &B, int nrhs, int parity) {
     return h->lp_mc == 4 ? lp4::elph_fast_cg_xr(h, B, nrhs, parity) : lp6::elph_fast_cg_xr(h, B, nrhs, parity);
 }
-int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, bool *did_rz, const double *rr_part, int fold_nct) {
-    return h->lp_mc == 4 ? lp4::elph_fast_kpm_cheb(h, nrhs, st, rz_part, nrz, did_rz, rr_part, fold_nct)
-                         : lp6::elph_fast_kpm_cheb(h, nrhs, st, rz_part, nrz, did_rz, rr_part, fold_nct);
+int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, double *rz_part, int nrz, const double *rr_part, int fold_nct) {
+    return h->lp_mc == 4 ? lp4::elph_fast_kpm_cheb(h, nrhs, st, reg, rz_part, nrz, rr_part, fold_nct)
+                         : lp6::elph_fast_kpm_cheb(h, nrhs, st, reg, rz_part, nrz, rr_part, fold_nct);
+}
+
+// The register-exchange Chebyshev recursion of the lane family for this lattice (the four-colour kernels of elph_fast_kpm_cheb; the forms
+// that can deliver r.z in frequency space), in the order the dispatch tries them; *hgn: cells per lane of the honeycomb grid form
+int elph_reg_cheb_form(const elph_handle_s *h, int *hgn) {
+    const bool hol = h->kind == ELPH_MODEL_HOLSTEIN;
+    if (h->sq_P > 0) return REG_SQ;
+    // any other even-L square lattice (L = 4, 6, 10, 12, 14) with one (cosh, sinh) for every bond: the GRID layout
+    if (h->sq_L > 0 && h->sq_uniform && hol) return REG_SQ_GRID;
+    if (h->hc_L > 0 && !h->hc12 && h->hc_uniform && hol) {
+        // any other honeycomb lattice whose cells fit a grid of lanes, one (cosh, sinh) for every bond: the HGRID layout
+        const int L = h->hc_L;
+        const int n = (L * L <= 64) ? 2 : ((L % 2 == 0 && (L / 2) * L <= 64) ? 4 : ((L % 2 == 0 && (L / 2) * (L / 2) <= 64) ? 8 : 0));
+        if (n) {
+            if (hgn) *hgn = n;
+            return REG_HC_GRID;
+        }
+    }
+    // the honeycomb lattice of 12 x 12 cells with one (cosh, sinh) for every bond: the quad layout
+    if (h->hc12 && h->hc_uniform && hol) return REG_HC12;
+    return REG_NONE;
 }
 

@@ -261,7 +261,7 @@ int elph_choose_T(const elph_handle_s *h, int nrhs);
 // whose grid still fills most of one round (>= 2560 waves) — measured at config C (tools/time_px_chunk_T.py, profiles/r05/
 // px_chunk_T.log): 288 right-hand sides 16 slices per wave (2880 waves: iteration 289 us; 20: 293, 8: 297), 128 right-hand sides 8 (2560
 // waves: 131 us; 20 = 1024 waves: 142).  nrhs = the right-hand sides IN FLIGHT (both halves of a two-stream batch).
-int elph_choose_T_px(const elph_handle_s *h, int nrhs) {
+int elph_choose_T_px(const elph_handle_s *h, int nrhs, bool two_streams) {
     if (!h->fast || h->force_T == 1) return 1;
     const int cand[7] = {20, 16, 10, 8, 5, 4, 2};
     // (forced lengths; bond phonons: the fused kernel keeps two sets of hopping tables in registers and stays at two waves per SIMD — the
@@ -277,10 +277,10 @@ int elph_choose_T_px(const elph_handle_s *h, int nrhs) {
         for (int T : capped) if (h->L % T == 0) return T;
         return T0;
     }
-    // two half-batches on two streams (T_rhs_hint: both halves counted): the other half's kernels fill what a shorter grid leaves idle, so
+    // two half-batches on two streams (nrhs: both halves counted): the other half's kernels fill what a shorter grid leaves idle, so
     // the longest chunks whose grid is 1536 ... 2048 waves win — 256 right-hand sides 20 slices per wave 230 us against 243 with 16, 192:
     // 182 against 185 with 10; 288 (2304 waves at 20) stays with the one-stream rule: 16 slices per wave 259 us against 262
-    if (h->T_rhs_hint > 0)
+    if (two_streams)
         for (int T : cand) {
             if (h->L % T) continue;
             const int64_t w = (int64_t)nrhs * (h->L / T);
@@ -326,14 +326,13 @@ k_kpm_cheb_sq_w4(double2 *__restrict__ nu, KpmDev K, const double *__restrict__ 
 
 #endif
 
-// rz_part != nullptr: the caller wants the r.z partial sums of the CG from this kernel (frequency space); *did_rz tells whether
-// the kernel that ran provides them (only the register-exchange kernel does)
-int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, bool *did_rz, const double *rr_part, int fold_nct) {
-    if (did_rz) *did_rz = false;
+// rz_part != nullptr: the caller wants the r.z partial sums of the CG from this kernel (frequency space; every form below delivers them,
+// the LDS recursion where the caller's slots hold the 2 Lo2 partials of a launch: elph_plan_cg plans rz_freq by that rule).  reg: the
+// register-exchange recursion where this lattice has one (elph_reg_cheb_form), else the Re / Im recursion through the LDS slab
+int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, double *rz_part, int nrz, const double *rr_part, int fold_nct) {
     KpmDev K = elph_kpm_dev(h);
     const int Lo2 = (int)((h->L + 1) / 2);
 #if ELPH_LP_MC == 4
-    const bool no_sq = elph_no_sq();
     // with the fold only the frequencies that some chain still recurses on get a block (the schedule is longest first)
     unsigned gy = (unsigned)Lo2;
     if (fold_nct > 0) {
@@ -345,7 +344,9 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
         }
         gy = (unsigned)std::min(Lo2, nl);
     }
-    if (h->sq_P > 0 && !no_sq) {
+    int hgn = 0;
+    const int form = reg ? elph_reg_cheb_form(h, &hgn) : REG_NONE;
+    if (form == REG_SQ) {
         // one frequency per block (the kernel loops over y, y + gridDim.y, ...: 2, 4 or 8 frequencies per block were measured — no
         // faster at 1 right-hand side or at 128: block dispatch is not what the kernel waits for)
 #define SQ_LAUNCH(PV, UV, ...) hipLaunchKernelGGL((k_kpm_cheb_sq<PV, UV, ##__VA_ARGS__>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
@@ -356,41 +357,30 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz
         } else if (h->sq_P == 2) { if (h->sq_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
         else              { if (h->sq_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
 #undef SQ_LAUNCH
-        if (did_rz) *did_rz = (rz_part != nullptr);
         return check_launch_f("k_kpm_cheb_sq");
     }
-    if (h->sq_L > 0 && h->sq_P == 0 && h->sq_uniform && h->kind == ELPH_MODEL_HOLSTEIN && !no_sq) {
-        // any other even-L square lattice (L = 4, 6, 10, 12, 14) with one (cosh, sinh) for every bond: the recursion in the GRID layout
+    if (form == REG_SQ_GRID) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
                            h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
-        if (did_rz) *did_rz = (rz_part != nullptr);
         return check_launch_f("k_kpm_cheb_sq(grid)");
     }
-    if (h->hc_L > 0 && !h->hc12 && h->hc_uniform && h->kind == ELPH_MODEL_HOLSTEIN && !no_sq) {
-        // any other honeycomb lattice whose cells fit a grid of lanes, one (cosh, sinh) for every bond: the recursion in the HGRID layout
-        const int L = h->hc_L;
-        const int hgn = (L * L <= 64) ? 2 : ((L % 2 == 0 && (L / 2) * L <= 64) ? 4 : ((L % 2 == 0 && (L / 2) * (L / 2) <= 64) ? 8 : 0));
-        if (hgn) {
+    if (form == REG_HC_GRID) {
 #define HG_LAUNCH(NV) hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, false, NV>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
                                          h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
-            if (hgn == 2) HG_LAUNCH(2); else if (hgn == 4) HG_LAUNCH(4); else HG_LAUNCH(8);
+        if (hgn == 2) HG_LAUNCH(2); else if (hgn == 4) HG_LAUNCH(4); else HG_LAUNCH(8);
 #undef HG_LAUNCH
-            if (did_rz) *did_rz = (rz_part != nullptr);
-            return check_launch_f("k_kpm_cheb_sq(honeycomb grid)");
-        }
+        return check_launch_f("k_kpm_cheb_sq(honeycomb grid)");
     }
-    const bool no_hc = no_sq;
-    if (h->hc12 && h->hc_uniform && h->kind == ELPH_MODEL_HOLSTEIN && !no_hc) {
-        // the honeycomb lattice of 12 x 12 cells with one (cosh, sinh) for every bond: the register-exchange recursion in the quad layout
+    if (form == REG_HC12) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
                            h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
-        if (did_rz) *did_rz = (rz_part != nullptr);
         return check_launch_f("k_kpm_cheb_sq(honeycomb)");
     }
+#else
+    (void)reg;
 #endif
     // the Re / Im recursion through the LDS slab delivers r.z too (round 6), where the caller's slots hold the 2 Lo2 partials of a launch
     const bool lds_rz = rz_part != nullptr && 2 * Lo2 <= nrz;
-    if (did_rz) *did_rz = lds_rz;
     return kpm_cheb_lds_npl(h, nrhs, st, lds_rz ? rz_part : nullptr, nrz, rr_part);
 }
 

@@ -286,11 +286,9 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, 
 
 }  // namespace sq16
 
-// Does the p/x-fused k_cg_ap of this handle run in the register-exchange form?  Holstein on the 16 x 16 square lattice in the reference's
-// colouring (detect_square: sq_P = 2), a template chunk length.  ELPH_SQ16_AP=0: the lane-program kernel (A/B; read per call).
+// Can the p/x-fused k_cg_ap of this handle run in the register-exchange form?  Holstein on the 16 x 16 square lattice in the reference's
+// colouring (detect_square: sq_P = 2), a template chunk length.  (ELPH_SQ16_AP=0, the lane-program kernel instead, is elph_plan_cg's.)
 bool elph_sq16_ap_usable(const elph_handle_s *h, int T) {
-    const char *e = getenv("ELPH_SQ16_AP");
-    if (e && e[0] == '0') return false;
     if (h->kind != ELPH_MODEL_HOLSTEIN) return false;
     const bool sq = h->sq_P == 2 && h->N == 256 && h->d_sq_bond, hc = h->hc12 && h->hc_uniform && h->N == 288;      // (config C; config D, uniform hopping)
     if (!sq && !hc) return false;

@@ -822,21 +822,24 @@ static int make_overlapping_stream(elph_handle_s *h, hipStream_t *out) {
     return ELPH_OK;
 }
 
+// The parts of a solve's chunk loop: `ways` parts of n1 right-hand sides each, part 0 the handle itself on its own stream — one part (the
+// default: a one-stream solve) or ELPH_SPLIT_PARTS of a preconditioned batch on streams of their own (split_begin)
 struct SplitRun {
-    bool on = false, ok = false, px_before = false;
-    int ways = 0, n1 = 0;                                 // `ways` parts of n1 right-hand sides each; part 0 is the handle itself on its own stream
+    bool on = false, ok = false;
+    int ways = 1, n1 = 0;
     elph_handle_s *main = nullptr, *view[ELPH_SPLIT_PARTS] = {};
+    CgPlan before;                                        // the whole batch's plan (split_begin replaces it with the parts')
+    SplitRun(elph_handle_s *h, int nrhs) : n1(nrhs), main(h) { view[0] = h; }
     // A solve that leaves through an error return must not leave kernels of the other streams in flight behind it (they write d_x, d_p, d_r,
     // d_state of their parts while the caller's next step — ldiv's zero-fill, a retry, a new solve — runs on the main stream), nor the handle
-    // believing in a p/x-fused solve that never happened.
+    // believing in a plan that never ran to its end.
     ~SplitRun() {
-        if (main) main->T_rhs_hint = 0;
         for (int k = 1; k < ways; ++k)
             if (view[k]) {
                 if (on) (void)hipStreamSynchronize(view[k]->stream);
                 delete view[k];
             }
-        if (main && on && !ok) main->px_solve = px_before;
+        if (ways > 1 && !ok) main->plan = before;      // (split_begin changed it; also when it failed before its streams ran)
     }
 };
 
@@ -845,11 +848,7 @@ static bool split_legal(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
     if (!use_prec || hist || nrhs < 2 * ways || (nrhs % ways) || h->solo_chain >= 0 || h->dot_hi > 0) return false;
     const int n1 = nrhs / ways;
     if (n1 % std::max(1, h->nchains) || n1 % std::max(1, h->kpm_nch)) return false;
-    const int keep = h->T_rhs_hint;
-    h->T_rhs_hint = nrhs;                 // the parts choose their slices per wave for the whole batch in flight
-    const bool ok = elph_px_plan(h, n1);
-    h->T_rhs_hint = keep;
-    return ok;
+    return elph_plan_cg(h, n1, true, nrhs).px;      // (the parts choose their slices per wave for the whole batch in flight)
 }
 
 static bool split_wanted(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
@@ -869,9 +868,7 @@ static bool split_wanted(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
 static int split_begin(elph_handle_s *h, int nrhs, SplitRun &S) {
     S.ways = ELPH_SPLIT_PARTS;
     S.n1 = nrhs / S.ways;
-    S.main = h;
-    S.view[0] = h;
-    S.px_before = h->px_solve;
+    S.before = h->plan;
     // The parts must run on DIFFERENT hardware queues.  HIP maps its streams onto a few hardware queues per process (four by default,
     // GPU_MAX_HW_QUEUES) by a rule of its own: in a process that holds several handles a part's stream can share the queue of the handle's main
     // stream — the parts then run one after the other, slower than one stream (round 6: the second handle of a process, 32 x 32 at 72 right-hand
@@ -881,9 +878,7 @@ static int split_begin(elph_handle_s *h, int nrhs, SplitRun &S) {
     for (int k = 1; k < S.ways; ++k)
         if (!h->split_stream[k]) RC(make_overlapping_stream(h, &h->split_stream[k]));
     if (!h->split_ev) HIPCHK(hipEventCreateWithFlags(&h->split_ev, hipEventDisableTiming));
-    h->px_solve = true;                                   // (split_legal: the parts run p/x-fused whatever the whole batch would have run)
-    h->px_via_pg = h->fast && h->lp_mc != 4;              // (six-colour lane programs: the patch-form pair, kernels.hip: px_plan)
-    h->T_rhs_hint = nrhs;                                 // slices per wave for the right-hand sides in flight = all parts
+    h->plan = elph_plan_cg(h, S.n1, true, nrhs);          // (split_legal: the parts run p/x-fused whatever the whole batch would have run)
     HIPCHK(hipEventRecord(h->split_ev, h->stream));       // the start state (x0, r0, p0, rho0 of every right-hand side) is on the main stream
     const size_t nd = (size_t)h->ndim, Lo2 = (size_t)(h->L + 1) / 2, nrz = (size_t)h->L * (size_t)h->npl;
     for (int k = 1; k < S.ways; ++k) {
@@ -916,6 +911,30 @@ static int split_join(SplitRun &S) {
     return ELPH_OK;
 }
 
+// The CG states of every part come back to the host (each on its stream, then all drained): iters[r] = the iteration count of every
+// right-hand side whose newer state copy is terminal; *all_done: every one is
+static int read_states(const SplitRun &S, int64_t *iters, bool *all_done) {
+    for (int k = 0; k < S.ways; ++k)
+        HIPCHK(hipMemcpyAsync(S.view[k]->h_state, S.view[k]->d_state, sizeof(CgState) * 2 * (size_t)S.n1, hipMemcpyDeviceToHost, S.view[k]->stream));
+    for (int k = 0; k < S.ways; ++k) HIPCHK(hipStreamSynchronize(S.view[k]->stream));
+    *all_done = true;
+    for (int r = 0; r < S.ways * S.n1; ++r) {
+        const CgState &a = S.main->h_state[2 * r], &b = S.main->h_state[2 * r + 1];
+        const CgState &s = (b.seq > a.seq) ? b : a;
+        if (!s.done) *all_done = false;
+        else iters[r] = s.iters;
+    }
+    return ELPH_OK;
+}
+
+// the eps histories of a finished solve (host, nrhs x (maxiter + 1); nullptr: none recorded)
+static int read_hist(elph_handle_s *h, int nrhs, int64_t maxiter, double *eps_hist) {
+    if (!eps_hist) return ELPH_OK;
+    HIPCHK(hipMemcpyAsync(eps_hist, h->d_hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ELPH_OK;
+}
+
 // Runs CG on d_b / d_x (layout S) for nrhs right-hand sides.  Returns per-rhs iteration counts.
 static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t maxiter, double kmax, int64_t *iters,
                   double *eps_hist /* host, optional, nrhs*(maxiter+1) */) {
@@ -939,16 +958,14 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
     // kernel, either kind of solve): a stream of large streaming batches in between does not bring the retry forward, and a solve that
     // never launches a resident kernel does not clear the abort word
     if (h->wg_broken) {
-        bool eligible = false;
-        if (!use_prec) eligible = h->fast && maxiter >= 1 && elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs);
-        else { h->wg_broken = false; eligible = maxiter >= 1 && elph_pcg_wg_usable(h, nrhs); h->wg_broken = true; }      // (its shape test reads the flag itself)
-        if (!use_prec && !eligible && h->slabs && x0_zero && maxiter >= 1) {      // (the slab form of a large lattice, slabs.hip)
-            h->wg_broken = false; eligible = elph_i_slabs_usable(h, nrhs); h->wg_broken = true;
-        }
+        bool eligible = maxiter >= 1 && (use_prec ? elph_pcg_wg_usable(h, nrhs) : h->fast && elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs));
+        if (!use_prec && !eligible && h->slabs && x0_zero && maxiter >= 1) eligible = elph_i_slabs_usable(h, nrhs);      // (the slab form of a large lattice, slabs.hip)
         if (eligible) RC(elph_wg_cooldown_step(h));
     }
     RC(elph_launch_cg_init(h, nrhs, use_prec, x0_zero));      // (x0 = 0: A x0 = 0 without the mat-vec)
     h->wg_x0_zero = h->x_zero_seen;
+    SplitRun S(h, nrhs);
+    bool all_done = false;
 
     // whole solve in one launch with the Krylov vectors in registers (cg_wg.hip: k_cg_wg) when it applies
     if (h->fast && !use_prec && maxiter >= 1 && elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs)) {
@@ -958,20 +975,12 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
         // (elph_wg_cg saves the caller's initial guess in d_zp — unused by an un-preconditioned solve — once it has decided to launch)
         RC(elph_wg_cg(h, B, nrhs, 0, &ran));
         if (ran) {
-            HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            RC(read_states(S, iters, &all_done));
             bool aborted = false;
             RC(elph_wg_aborted(h, &aborted));
             if (!aborted) {
-                for (int r = 0; r < nrhs; ++r) {
-                    if (!h->h_state[2 * r].done) { elph_set_error("workgroup-resident CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-                    iters[r] = h->h_state[2 * r].iters;
-                }
-                if (eps_hist) {
-                    HIPCHK(hipMemcpyAsync(eps_hist, h->d_hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
-                    HIPCHK(hipStreamSynchronize(h->stream));
-                }
-                return ELPH_OK;
+                if (!all_done) { elph_set_error("workgroup-resident CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
+                return read_hist(h, nrhs, maxiter, eps_hist);
             }
             // a team gave up (x, r of the right-hand sides that had finished were overwritten): start every right-hand side again
             // from the caller's initial guess; the two-kernel iteration below does the work
@@ -982,21 +991,15 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
 
     // a lattice beyond one wave's slice: the resident kernel on slabs of rows of the lattice, all on this device, one launch per right-hand
     // side (slabs.hip).  x0 = 0 only (the slab kernel starts from it): ldiv!'s zero-fill.
-    if (!use_prec && maxiter >= 1 && x0_zero && elph_i_slabs_usable(h, nrhs)) {
+    if (!use_prec && maxiter >= 1 && x0_zero && !h->wg_broken && elph_i_slabs_usable(h, nrhs)) {
         bool ran = false;
         RC(elph_i_slabs_solve(h, nrhs, P, 0, iters, &ran, nullptr));
-        if (ran) {
-            if (eps_hist) {
-                HIPCHK(hipMemcpyAsync(eps_hist, h->d_hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-            }
-            return ELPH_OK;
-        }
+        if (ran) return read_hist(h, nrhs, maxiter, eps_hist);
         RC(elph_launch_cg_init(h, nrhs, use_prec, true));      // (x is zero again: elph_i_slabs_solve)
     }
 
     // the whole PRECONDITIONED solve in one launch (pcg_wg.hip: k_pcg_wg) for one to eight right-hand sides on the 16 x 16 square lattice
-    if (use_prec && maxiter >= 1 && elph_pcg_wg_usable(h, nrhs)) {
+    if (use_prec && maxiter >= 1 && !h->wg_broken && elph_pcg_wg_usable(h, nrhs)) {
         bool ran = false;
         CgBufs B = elph_make_bufs(h, nrhs);
         B.params = P;
@@ -1004,67 +1007,33 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
         HIPCHK(hipMemcpyAsync(h->d_tmp, h->d_x, xbytes, hipMemcpyDeviceToDevice, h->stream));     // the initial guess, for the fallback (A x0 in d_tmp has been consumed)
         RC(elph_pcg_wg(h, B, nrhs, 0, &ran));
         if (ran) {
-            HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            RC(read_states(S, iters, &all_done));
             bool aborted = false;
             RC(elph_wg_aborted(h, &aborted));
             if (!aborted) {
-                for (int r = 0; r < nrhs; ++r) {
-                    if (!h->h_state[2 * r].done) { elph_set_error("resident preconditioned CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-                    iters[r] = h->h_state[2 * r].iters;
-                }
-                if (eps_hist) {
-                    HIPCHK(hipMemcpyAsync(eps_hist, h->d_hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
-                    HIPCHK(hipStreamSynchronize(h->stream));
-                }
-                return ELPH_OK;
+                if (!all_done) { elph_set_error("resident preconditioned CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
+                return read_hist(h, nrhs, maxiter, eps_hist);
             }
             HIPCHK(hipMemcpyAsync(h->d_x, h->d_tmp, xbytes, hipMemcpyDeviceToDevice, h->stream));
             RC(elph_launch_cg_init(h, nrhs, use_prec));
         }
     }
 
+    // the streaming iteration, ELPH_CG_CHUNK iterations of every part between two reads of the states
+    if (split_wanted(h, nrhs, use_prec, eps_hist != nullptr)) RC(split_begin(h, nrhs, S));
     const int64_t max_chunks = (maxiter + 1 + ELPH_CG_CHUNK - 1) / ELPH_CG_CHUNK + 1;
-    bool all_done = false;
-    if (split_wanted(h, nrhs, use_prec, eps_hist != nullptr)) {
-        SplitRun S;
-        RC(split_begin(h, nrhs, S));
-        for (int64_t c = 0; c < max_chunks && !all_done; ++c) {
-            for (int it = 0; it < ELPH_CG_CHUNK; ++it) RC(split_iteration(S, use_prec));
-            for (int k = 0; k < S.ways; ++k)
-                HIPCHK(hipMemcpyAsync(S.view[k]->h_state, S.view[k]->d_state, sizeof(CgState) * 2 * (size_t)S.n1, hipMemcpyDeviceToHost, S.view[k]->stream));
-            for (int k = 0; k < S.ways; ++k) HIPCHK(hipStreamSynchronize(S.view[k]->stream));
-            all_done = true;
-            for (int r = 0; r < nrhs; ++r) {
-                const CgState &a = h->h_state[2 * r], &b = h->h_state[2 * r + 1];
-                const CgState &s = (b.seq > a.seq) ? b : a;
-                if (!s.done) all_done = false;
-                else iters[r] = s.iters;
-            }
-        }
-        h->ap_count = S.view[S.ways - 1]->ap_count;
-        S.ok = all_done;
-        if (!all_done) { elph_set_error("CG chunk loop (two streams) ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-        return ELPH_OK;
-    }
+    all_done = false;
     for (int64_t c = 0; c < max_chunks && !all_done; ++c) {
-        for (int it = 0; it < ELPH_CG_CHUNK; ++it) RC(elph_launch_cg_iteration(h, nrhs, use_prec));
-        HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        all_done = true;
-        for (int r = 0; r < nrhs; ++r) {
-            const CgState &a = h->h_state[2 * r], &b = h->h_state[2 * r + 1];
-            const CgState &s = (b.seq > a.seq) ? b : a;
-            if (!s.done) all_done = false;
-            else iters[r] = s.iters;
-        }
+        for (int it = 0; it < ELPH_CG_CHUNK; ++it) RC(split_iteration(S, use_prec));
+        RC(read_states(S, iters, &all_done));
     }
-    if (!all_done) { elph_set_error("CG chunk loop ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-    if (eps_hist) {
-        HIPCHK(hipMemcpyAsync(eps_hist, h->d_hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+    h->ap_count = S.view[S.ways - 1]->ap_count;
+    S.ok = all_done;
+    if (!all_done) {
+        elph_set_error(S.ways > 1 ? "CG chunk loop (two streams) ended without a terminal state (internal error)" : "CG chunk loop ended without a terminal state (internal error)");
+        return ELPH_E_STATE;
     }
-    return ELPH_OK;
+    return read_hist(h, nrhs, maxiter, eps_hist);
 }
 
 // residual + flag logic of ldiv! for rhs already solved into d_x; zeroes x where flag > 0
@@ -1183,11 +1152,7 @@ static int stage_in_dev(elph_handle_s *h, int nrhs, const double *X_dev, const d
 // non-zero; a zero guess costs one pass over the vector on the host (1.3 MB at 32 x 32 sites, 160 slices) — against a solve of milliseconds.
 static bool x0_is_zero(elph_handle_s *h, int nrhs, int use_prec, const double *X) {
     if (use_prec || h->have_E == false) return false;
-    const bool prev = h->wg_broken;
-    h->wg_broken = false;                            // (cooling down: the hint still lets run_cg count the solve)
-    const bool cand = elph_i_slabs_usable(h, nrhs);
-    h->wg_broken = prev;
-    if (!cand) return false;
+    if (!elph_i_slabs_usable(h, nrhs)) return false;      // (also while cooling down: the hint still lets run_cg count the solve)
     const size_t n = (size_t)nrhs * (size_t)h->ndim;
     for (size_t i = 0; i < n; ++i) if (X[i] != 0.0) return false;
     return true;
@@ -1995,8 +1960,7 @@ static int bench_launch_unit(elph_handle_s *h, int what, int nrhs) {
         case 5: return elph_launch_cg_kernel(h, nrhs, 1);
         default: {
             // 6, 7, 8: the three kernels of the KPM apply as the preconditioned iteration (case 3) launches them, one at a time
-            const bool xr_fused = h->fast && h->kpm_active && h->dot_hi == 0 && elph_dft_mfma_xr_usable(h, (int)h->N, nrhs);
-            return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, xr_fused ? 2 : 1, 1 << (what - 6));
+            return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, h->plan.xr_in_fwd ? 2 : 1, 1 << (what - 6));
         }
     }
 }
@@ -2036,7 +2000,7 @@ extern "C" int elph_bench_get_x(elph_handle h, int nrhs, double *X) {
 extern "C" int elph_bench_info(elph_handle h, int nrhs, int *slices_per_wave) {
     CHECK_H(h);
     if (nrhs < 1 || !slices_per_wave) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    *slices_per_wave = (h->px_solve && h->cur_params.use_prec) ? elph_choose_T_px(h, nrhs) : elph_choose_T(h, nrhs);
+    *slices_per_wave = h->plan.T;      // (of the batch elph_bench_prepare planned)
     return ELPH_OK;
 }
 
@@ -2063,7 +2027,7 @@ extern "C" int elph_bench_wg_info(elph_handle h, int nrhs, int *usable, int *T, 
 extern "C" int elph_bench_px_info(elph_handle h, int *fused) {
     CHECK_H(h);
     if (!fused) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    *fused = h->px_solve ? (h->sq16_ap_ran ? 2 : 1) : 0;      // 2: with the register-exchange k_cg_ap of the 16 x 16 lattice (cg_sq16.hip)
+    *fused = h->plan.px ? (h->plan.ap == CgPlan::AP_SQ16 ? 2 : 1) : 0;      // 2: with the register-exchange k_cg_ap of the 16 x 16 lattice (cg_sq16.hip)
     return ELPH_OK;
 }
 
@@ -2085,11 +2049,7 @@ extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int u
     if (nrhs < 1 || nrhs > h->cap_rhs || reps < 1 || !ms_total || what < 0 || what > 12) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     if (use_graph) { elph_set_error("elph_bench_run: captured-graph replay is not supported (use_graph must be 0)"); return ELPH_E_UNSUPPORTED; }
     if (what == 12) {        // `reps` un-preconditioned iterations of every right-hand side in the slab form of a large lattice (slabs.hip): sum of the launches' event times
-        const int prev_broken = h->wg_broken;
-        h->wg_broken = false;
-        const bool ok = elph_i_slabs_usable(h, nrhs);
-        h->wg_broken = prev_broken;
-        if (!ok) { elph_set_error("the slab form does not apply to this handle / batch"); return ELPH_E_UNSUPPORTED; }
+        if (!elph_i_slabs_usable(h, nrhs)) { elph_set_error("the slab form does not apply to this handle / batch"); return ELPH_E_UNSUPPORTED; }
         bool ran = false;
         std::vector<int64_t> its((size_t)nrhs);
         RC(elph_i_slabs_solve(h, nrhs, h->cur_params, reps, its.data(), &ran, ms_total));
@@ -2128,7 +2088,7 @@ extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int u
     }
     if (what == 11) {        // `reps` preconditioned iterations of the batch as two half-batches on two streams (run_cg's form from 192 right-hand sides)
         if (!split_legal(h, nrhs, 1, false)) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); elph_set_error("the two-stream form does not apply to this batch"); return ELPH_E_UNSUPPORTED; }
-        SplitRun S;
+        SplitRun S(h, nrhs);
         hipError_t er = hipStreamSynchronize(h->stream);
         if (er == hipSuccess) er = hipEventRecord(e0, h->stream);
         if (er == hipSuccess) rc = split_begin(h, nrhs, S);

@@ -127,6 +127,22 @@ struct CgState {
 };
 
 
+// The kernels one CG iteration launches, chosen once per solve by elph_plan_cg (kernels.hip) and only read by the launchers (host only).
+struct CgPlan {
+    enum Ap { AP_LANE, AP_SQ16, AP_PG, AP_GEN };      // k_cg_ap: lane program, its register form (cg_sq16.hip), patch form (pgrid.hip), generic
+    enum Cheb { CH_LANE, CH_PG, CH_GEN };             // Chebyshev recursion: lane family (elph_fast_kpm_cheb), patch form, generic k_kpm_cheb
+    int nrhs = 0, in_flight = 0;   // right-hand sides of this stream / on all streams (the parts of a split batch: every part)
+    bool px = false;               // preconditioned and p/x-fused (x += alpha p, p = P^-1 r + beta p in the inverse transform's epilogue)
+    bool xr_in_fwd = false;        // a preconditioned iteration folds its residual update into the forward transform (kpm apply cg_mode 2)
+    bool reg_cheb = false;         // the lane family's register-exchange Chebyshev recursion runs (elph_reg_cheb_form; not under ELPH_NO_SQ=1)
+    bool rz_freq = false;          // inside CG the Chebyshev kernel delivers the r.z partials in frequency space
+    bool fold = false;             // cg_mode 2: the order-1 frequencies are finished by the forward transform (dft_mfma.hip: XrFuse)
+    Ap ap = AP_LANE;
+    Cheb cheb = CH_LANE;
+    int T = 1;                     // slices per wave of k_cg_ap: npap = ceil(L / T) p.Ap partials per right-hand side
+};
+
+
 // one frequency block of a chain's schedule, packed so that a Chebyshev block learns what it has to do from ONE 32-byte load
 // (frequency, order, offset of its coefficients, leading coefficient) instead of a chain of four dependent ones
 struct KpmDesc { int w, order, coff, pad; double c0x, c0y; };
@@ -209,12 +225,9 @@ struct elph_handle_s {
     double *d_lam = nullptr;               // [3N] lambda, lambda2, mu staging
     hipStream_t split_stream[ELPH_SPLIT_PARTS] = {};      // streams 1 … ways-1 + event of the split form of a preconditioned batch (elph_api.hip: SplitRun; [0] unused: the handle's own stream)
     hipEvent_t split_ev = nullptr;
-    int T_rhs_hint = 0;                    // > 0: right-hand sides in flight when the slices per wave are chosen (two-stream batches: both halves)
     bool csbar_external = false;           // kpm_setup_core: h_cbar / h_sbar were filled by the caller (elph_i_kpm_setup_csbar)
     bool ebar_external = false;            // kpm_setup_core: d_Ebar was filled by the caller (elph_i_kpm_setup_ebar)
-    bool px_solve = false;                 // the current solve's preconditioned iteration is p/x-fused (kernels.hip: px_plan)
-    bool px_via_pg = false;                // this solve's p/x-fused iteration takes the patch-form k_cg_ap_pg although the handle is of the lane-program family (six-colour lane programs: triangular lattices up to 16 x 16)
-    bool sq16_ap_ran = false;              // the latest p/x-fused k_cg_ap ran in the register-exchange form (cg_sq16.hip)
+    CgPlan plan;                           // the kernels of the current solve's CG iteration (kernels.hip: elph_plan_cg)
     // SSH update_model! on the device (elph_update_model_ssh_fields): staging of x, per-phonon tables, slot map
     double *d_ssh_x = nullptr, *d_ssh_par = nullptr, *d_ssh_tbare = nullptr, *d_ssh_bar = nullptr;
     int *d_ssh_cb = nullptr, *d_ssh_slot = nullptr;
@@ -409,7 +422,7 @@ int elph_fast_mul(elph_handle_s *h, int which, double *yS, const double *vS, int
 int elph_fast_cg_ap(elph_handle_s *h, const CgBufs &B, int nrhs, int parity, bool fused = false);      // fused: the p/x-fused iteration (reads the ready p)
 int elph_fast_cg_xr(elph_handle_s *h, const CgBufs &B, int nrhs, int parity);
 // cg_sq16.hip: the p/x-fused k_cg_ap of the 16 x 16 square lattice with the checkerboard in registers (no LDS slabs)
-bool elph_sq16_ap_usable(const elph_handle_s *h, int T);
+bool elph_sq16_ap_usable(const elph_handle_s *h, int T);      // the shape; ELPH_SQ16_AP is elph_plan_cg's
 int elph_sq16_cg_ap_px(elph_handle_s *h, const CgBufs &B, int nrhs, int parity);
 // ---- one solve over several GPUs (cg_wg.hip, shard.hip): by-value description of this rank's shard for the resident kernel
 #define ELPH_SHARD_MAXREC 256      // records of a meeting: ranks x workgroups per rank (8 x 20 at Ltau = 160; polled as 8 x 64 granules)
@@ -446,7 +459,6 @@ bool elph_pg_disorder_ok(const elph_handle_s *h);      // hopping disorder on th
 int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part = nullptr, int nrz = 0, const double *rr_part = nullptr);
 bool elph_pg_ap_usable(const elph_handle_s *h);
 bool elph_pg_mw();                                          // ELPH_PG_MW: patch shapes of several wavefronts per slice allowed (pgrid.hip)
-bool elph_no_sq();                                          // ELPH_NO_SQ=1: no register-exchange Chebyshev kernel (kernels.hip)
 bool elph_pg_mul_usable(const elph_handle_s *h);
 int elph_pg_mul(elph_handle_s *h, const ModelDev &m, int which, double *yS, const double *vS, int nvec);
 int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs, int parity, bool fused = false);      // fused: the p/x-fused iteration (reads the ready p)
@@ -459,10 +471,14 @@ char elph_slabs_test_timeout();                             // first character o
 bool elph_pcg_wg_usable(const elph_handle_s *h, int nrhs);
 int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran);
 CgBufs elph_make_bufs(elph_handle_s *h, int nrhs);
-int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part = nullptr, int nrz = 0, bool *did_rz = nullptr,
+// reg: the plan's reg_cheb (the register-exchange recursion where elph_reg_cheb_form has one); rz_part: the r.z partials in frequency space
+int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, double *rz_part = nullptr, int nrz = 0,
                        const double *rr_part = nullptr, int fold_nct = 0);
+enum RegCheb { REG_NONE, REG_SQ, REG_SQ_GRID, REG_HC_GRID, REG_HC12 };
+int elph_reg_cheb_form(const elph_handle_s *h, int *hgn = nullptr);      // cg_fast.hip: the lane family's register-exchange recursion of this lattice
 int elph_choose_T(const elph_handle_s *h, int nrhs);
-int elph_choose_T_px(const elph_handle_s *h, int nrhs);      // the p/x-fused kernel's own rule (three waves per SIMD)
+int elph_choose_T_px(const elph_handle_s *h, int nrhs, bool two_streams);      // the p/x-fused kernel's own rule (three waves per SIMD); nrhs in flight
+CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight);      // kernels.hip: mutates nothing
 // packs per-bond values (order of h_bi/h_bj) into the lane-program layout [NE][64] (idle slots = fill)
 void elph_lp_pack(const elph_handle_s *h, const double *per_bond, double *out, double fill);
 
@@ -480,7 +496,6 @@ int elph_dft_accel(elph_handle_s *h, double *outS, const double *inS, const doub
 int elph_dft_mfma_build_tables(elph_handle_s *h);
 bool elph_dft_mfma_xr_usable(const elph_handle_s *h, int N, int nrhs);
 bool elph_dft_mfma_px_usable(const elph_handle_s *h, int N, int nrhs);
-bool elph_px_plan(elph_handle_s *h, int nrhs);      // kernels.hip: would a preconditioned batch of nrhs run p/x-fused?
 int elph_dft_mfma_inv_px(elph_handle_s *h, const double2 *nu, int N, int nrhs, const CgState *st, double *pS, double *xS,
                          const double *alpha, const double *rz, int nrz);
 bool elph_dft_mfma_fold_usable(const elph_handle_s *h);

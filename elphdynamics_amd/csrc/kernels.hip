@@ -1123,11 +1123,7 @@ static CgBufs make_bufs(elph_handle_s *h, int nrhs) {
     B.dot_lo = h->dot_hi > 0 ? h->dot_lo : 0;
     B.dot_hi = h->dot_hi > 0 ? h->dot_hi : (int)h->N;
     B.nrz = (int)(h->L * h->npl);
-    {   // slices per wave of k_cg_ap: the p/x-fused kernel of a preconditioned batch has its own rule
-        const int Tc = (h->px_solve && h->cur_params.use_prec && h->px_via_pg) ? 1      // (k_cg_ap_pg: one p.z slot per time slice)
-                       : (h->px_solve && h->cur_params.use_prec) ? elph_choose_T_px(h, h->T_rhs_hint > 0 ? h->T_rhs_hint : nrhs) : elph_choose_T(h, nrhs);
-        B.npap = (int)((h->L + Tc - 1) / Tc);      // (a ragged cut: ceil)
-    }
+    B.npap = (int)((h->L + h->plan.T - 1) / h->plan.T);      // slices per wave of the planned k_cg_ap (a ragged cut: ceil)
     B.nrhs = nrhs;
     return B;
 }
@@ -1177,82 +1173,67 @@ int elph_launch_ebar(elph_handle_s *h, int nch) {
     return check_launch("k_ebar");
 }
 
-// Does the preconditioned iteration of THIS solve run p/x-fused (PxFuse, dft_mfma.hip)?  Decided once per solve (elph_launch_cg_init) so
-// that k_cg_ap_chunk<PX> and the inverse transform agree: the batched Holstein iteration on a four-colour lane program whose
-// Chebyshev kernel leaves r.z in frequency space (so that beta is known BEFORE the inverse transform), residual update folded into the
-// forward transform, streaming MFMA inverse with one row group, the templated chunk lengths.  ELPH_FUSE_PX=0: off (A/B, parity tests).
-// ELPH_NO_SQ=1: the Chebyshev recursion through the LDS slab where a register-exchange form exists (the A/B; read per call: the tests
-// switch both ways inside one process)
-bool elph_no_sq() {
-    const char *e = getenv("ELPH_NO_SQ");
-    return e && e[0] == '1';
-}
-
-static bool reg_cheb_form(const elph_handle_s *h) {      // a register-exchange Chebyshev kernel (the forms that deliver r.z in frequency space)
-    if (elph_no_sq()) return false;
-    return h->sq_P > 0 || (h->sq_L > 0 && h->sq_uniform && h->kind == ELPH_MODEL_HOLSTEIN) ||
-           (h->hc_L > 0 && h->hc_uniform && h->kind == ELPH_MODEL_HOLSTEIN && (h->hc12 || h->hc_L * h->hc_L <= 64 || (h->hc_L % 2 == 0 && h->hc_L <= 16)));
-}
-
-// the patch-form lattices of the generic family (round 6): Holstein, uniform hopping, k_cg_ap_pg + k_kpm_cheb_pg (pgrid.hip) — their p/x-fused
-// iteration is the lane-program family's with those two kernels in its place (ELPH_PG_PX=0: the unfused form, A/B; read per call)
-static bool pg_px_allowed() {
-    const char *e = getenv("ELPH_PG_PX");
-    return !(e && e[0] == '0');
-}
-static bool pg_px_form(const elph_handle_s *h) {
-    if (!pg_px_allowed()) return false;
-    return !h->fast && h->kind == ELPH_MODEL_HOLSTEIN && (h->pg_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && elph_pg_cheb_usable(h);
-}
-
-static bool px_plan(elph_handle_s *h, int nrhs) {
-    if (!h->kpm_active) return false;
-    if (pg_px_form(h)) {
-        const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
-        CgBufs B = make_bufs(h, nrhs);
-        if (!(B.dot_lo == 0 && B.dot_hi == N) || B.npap != L || 2 * Lo2 > B.nrz) return false;
-        return elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs);
+// The kernels of one CG iteration for nrhs right-hand sides on one stream (in_flight: on all streams — the parts of a split batch), decided
+// once per solve: elph_launch_cg_init plans the whole batch, split_begin each part; every launcher reads h->plan and decides nothing.
+// This is the only reader, on the iteration path, of the switches that choose the iteration's form (A/B; read when a solve is planned):
+// ELPH_NO_SQ=1 (the LDS Chebyshev recursion where a register-exchange form exists), ELPH_PG_PX=0 / ELPH_GEN_PX=0 / ELPH_LDS_CHEB_PX=0 (the
+// unfused iteration of the patch-form lattices / the rest of the generic family / the lane programs whose recursion runs through the LDS
+// slab), ELPH_SQ16_AP=0 (the lane-program k_cg_ap instead of the register form of cg_sq16.hip).  ELPH_FUSE_XR, ELPH_FUSE_PX and
+// ELPH_DFT_MFMA are read by the elph_dft_mfma_*_usable predicates it calls.
+CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) {
+    const char *e_nosq = getenv("ELPH_NO_SQ"), *e_pg = getenv("ELPH_PG_PX"), *e_gen = getenv("ELPH_GEN_PX");
+    const char *e_lds = getenv("ELPH_LDS_CHEB_PX"), *e_sq16 = getenv("ELPH_SQ16_AP");
+    const bool no_sq = e_nosq && e_nosq[0] == '1', pg_px_ok = !(e_pg && e_pg[0] == '0');
+    const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2, nrz = (int)(h->L * h->npl), nct = (N + 15) / 16;
+    const bool dot_all = h->dot_hi <= 0 || (h->dot_lo == 0 && h->dot_hi == N);      // every site enters the inner products (make_bufs)
+    const bool hol = h->kind == ELPH_MODEL_HOLSTEIN, pg_cheb = elph_pg_cheb_usable(h), rz2 = 2 * Lo2 <= nrz;
+    CgPlan c;
+    c.nrhs = nrhs;
+    c.in_flight = in_flight;
+    c.cheb = pg_cheb ? CgPlan::CH_PG : h->fast ? CgPlan::CH_LANE : CgPlan::CH_GEN;
+    c.reg_cheb = !no_sq && elph_reg_cheb_form(h) != REG_NONE;
+    // p/x-fused (PxFuse, dft_mfma.hip): residual update folded into the forward transform, r.z from the Chebyshev kernel in frequency space
+    // (so that beta is known BEFORE the inverse transform), streaming MFMA inverse with the p/x-update in its epilogue
+    if (prec && h->kpm_ready && h->kpm_active && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs)) {
+        if (!h->fast && hol && (h->pg_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && pg_cheb) {
+            // (round 6) the patch-form lattices of the generic family: k_cg_ap_pg + k_kpm_cheb_pg (pgrid.hip)
+            c.px = pg_px_ok && rz2;
+        } else if (!h->fast) {
+            // (round 6) every other lattice of the generic family — ragged colours, more than six colours, hopping disorder, no patch form, bond
+            // phonons beyond the lane-program sizes: k_cg_ap<PX> + k_kpm_cheb with r.z in frequency space
+            c.px = !(e_gen && e_gen[0] == '0') && Lo2 <= nrz && !pg_cheb;
+        } else if (h->lp_mc != 4) {
+            // six-colour lane programs (triangular lattices up to 16 x 16: the geometry of holstein_hmc_triangular.toml) have no fused chunk kernel of
+            // their own: their p/x-fused iteration takes the patch-form pair k_cg_ap_pg<PX> + k_kpm_cheb_pg (pgrid::Tri<2, 2>) — round 6
+            c.px = pg_px_ok && hol && h->pg_L > 0 && h->pg_uniform && pg_cheb && rz2;
+        } else {
+            // the four-colour lane programs: r.z in frequency space comes from a register-exchange Chebyshev kernel — or, round 6, from the
+            // patch-form one (square L = 18, 20 of this family) or from the Re / Im recursion through the LDS slab (k_kpm_cheb_ri: square L = 22,
+            // disordered honeycomb lattices, ...; ELPH_LDS_CHEB_PX=0 and ELPH_NO_SQ=1 — the A/B that forces that recursion on a lattice with a
+            // register form — keep the unfused iteration); the fused chunk kernel takes the template lengths
+            const bool lds_ok = !((e_lds && e_lds[0] == '0') || no_sq || pg_cheb);
+            const int T = elph_choose_T_px(h, in_flight, in_flight > nrhs);
+            c.px = rz2 && (c.reg_cheb || (pg_cheb && pg_px_ok) || lds_ok) && T > 1 && L % T == 0 &&
+                   (T == 20 || T == 16 || T == 10 || T == 8 || T == 5 || T == 4 || T == 2);
+        }
     }
-    if (!h->fast) {
-        // (round 6) every other lattice of the generic family — ragged colours, more than six colours, hopping disorder, no patch form, bond
-        // phonons beyond the lane-program sizes: k_cg_ap<PX> + k_kpm_cheb with r.z in frequency space (ELPH_GEN_PX=0: the unfused form, A/B)
-        const char *eg = getenv("ELPH_GEN_PX");
-        if (eg && eg[0] == '0') return false;
-        const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
-        CgBufs B = make_bufs(h, nrhs);
-        if (!(B.dot_lo == 0 && B.dot_hi == N) || B.npap != L || Lo2 > B.nrz || elph_pg_cheb_usable(h)) return false;
-        return elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs);
+    // (k_cg_ap_pg: one p.z slot per time slice)
+    c.T = !c.px ? elph_choose_T(h, nrhs) : (h->fast && h->lp_mc != 4) ? 1 : elph_choose_T_px(h, in_flight, in_flight > nrhs);
+    if (h->fast) {
+        const bool sq16 = !(e_sq16 && e_sq16[0] == '0') && elph_sq16_ap_usable(h, c.T);      // (the 16 x 16 lattice: the checkerboard in registers)
+        c.ap = !c.px ? CgPlan::AP_LANE : h->lp_mc != 4 ? CgPlan::AP_PG : sq16 ? CgPlan::AP_SQ16 : CgPlan::AP_LANE;
+    } else {
+        // a large even-L square lattice: the patch-layout kernel (pgrid.hip)
+        c.ap = (elph_pg_ap_usable(h) && (elph_model_dev(h).uniform || elph_pg_disorder_ok(h))) ? CgPlan::AP_PG : CgPlan::AP_GEN;
     }
-    if (h->lp_mc != 4) {
-        // six-colour lane programs (triangular lattices up to 16 x 16: the geometry of holstein_hmc_triangular.toml) have no fused chunk kernel of
-        // their own: their p/x-fused iteration takes the patch-form pair k_cg_ap_pg<PX> + k_kpm_cheb_pg (pgrid::Tri<2, 2>) — round 6
-        if (!(pg_px_allowed() && h->kind == ELPH_MODEL_HOLSTEIN && h->pg_L > 0 && h->pg_uniform && elph_pg_cheb_usable(h))) return false;
-        const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
-        const bool keep = h->px_via_pg, keeps = h->px_solve;
-        h->px_via_pg = true; h->px_solve = true;            // (make_bufs prices the partial-sum layout of the form being planned)
-        CgParams kp = h->cur_params; h->cur_params.use_prec = 1;
-        CgBufs B = make_bufs(h, nrhs);
-        h->cur_params = kp; h->px_via_pg = keep; h->px_solve = keeps;
-        if (!(B.dot_lo == 0 && B.dot_hi == N) || B.npap != L || 2 * Lo2 > B.nrz) return false;
-        return elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs);
-    }
-    const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
-    CgBufs B = make_bufs(h, nrhs);
-    if (!(B.dot_lo == 0 && B.dot_hi == N) || !elph_dft_mfma_xr_usable(h, N, nrhs)) return false;      // the iteration takes cg_mode 2
-    if (2 * Lo2 > B.nrz) return false;
-    // (r.z in frequency space comes from a register-exchange Chebyshev kernel — or, round 6, from the patch-form one: square L = 18, 20 of this family)
-    // or from the Re / Im recursion through the LDS slab (k_kpm_cheb_ri: square L = 22, disordered honeycomb lattices, ...; ELPH_LDS_CHEB_PX=0 and
-    // ELPH_NO_SQ=1 — the A/B that forces that recursion on a lattice with a register form — keep the unfused iteration)
-    if (!reg_cheb_form(h) && !(elph_pg_cheb_usable(h) && pg_px_allowed())) {
-        const char *el = getenv("ELPH_LDS_CHEB_PX");
-        if ((el && el[0] == '0') || elph_no_sq() || elph_pg_cheb_usable(h)) return false;
-    }
-    const int T = elph_choose_T_px(h, h->T_rhs_hint > 0 ? h->T_rhs_hint : nrhs);
-    if (!(T > 1 && L % T == 0 && (T == 20 || T == 16 || T == 10 || T == 8 || T == 5 || T == 4 || T == 2))) return false;
-    return elph_dft_mfma_px_usable(h, N, nrhs);
+    c.xr_in_fwd = c.px || (h->fast && h->kpm_active && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs));
+    c.rz_freq = dot_all && (c.cheb == CgPlan::CH_LANE ? rz2 : c.cheb == CgPlan::CH_PG ? c.px && rz2 : c.px && Lo2 <= nrz);
+    // FOLD (dft_mfma.hip: XrFuse): with the residual update in the forward transform and a register-exchange Chebyshev kernel (the one that
+    // knows the fold) the frequencies of order 1 — z_w = |c0|^2 r_w — are finished by the forward transform; the Chebyshev kernel keeps
+    // their slot bookkeeping only
+    c.fold = h->fast && c.reg_cheb && h->lp_mc == 4 && h->d_kfold && 2 * Lo2 + nct <= nrz && dot_all && elph_dft_mfma_fold_usable(h);
+    return c;
 }
-
-bool elph_px_plan(elph_handle_s *h, int nrhs) { return px_plan(h, nrhs); }
 
 // z = P^-1 r on layout-S vectors.  cg_mode: 0 standalone; 1 inside CG (skip when done, fuse r.z partials); 2 as 1 with the
 // residual update r -= alpha A p (k_cg_xr) folded into the forward transform (rS is then written)
@@ -1272,16 +1253,12 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         }
         return check_launch("kpm identity");
     }
+    // inside CG the solve's plan; a standalone apply takes its Chebyshev form from the same rule
+    const CgPlan pl = cg_mode ? h->plan : elph_plan_cg(h, nrhs, true, nrhs);
     KpmDev K = elph_kpm_dev(h);
     ModelDev m = elph_model_dev(h);
-
-    // FOLD (dft_mfma.hip: XrFuse): in the batched CG iteration (forward transform with the residual update folded in, register-exchange
-    // Chebyshev kernel with the r.z partials in frequency space) the frequencies of order 1 — z_w = |c0|^2 r_w — are finished by the
-    // forward transform; the Chebyshev kernel keeps their slot bookkeeping only
     const int nct = (N + 15) / 16;
-    const bool reg_cheb = reg_cheb_form(h);      // (a register-exchange Chebyshev kernel: the one that knows the fold; ELPH_NO_SQ=1 forces the LDS recursion, which does not)
-    const bool fold = cg_mode == 2 && h->fast && reg_cheb && h->lp_mc == 4 && h->d_kfold &&
-                      2 * Lo2 + nct <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && elph_dft_mfma_fold_usable(h);
+    const bool fold = cg_mode == 2 && pl.fold;
     if (!(parts & 1)) {
     } else if (cg_mode == 2) {
         int rcd = elph_dft_mfma_fwd_xr(h, h->d_nu, const_cast<double *>(rS), B.z, B.pap, B.npap, B.rr, B.alpha, N, nrhs, st,
@@ -1293,22 +1270,18 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         if (rcd) return rcd;
     }
     const size_t shm = (size_t)N * sizeof(double2);
-    bool rz_done = false;     // r.z partials already produced in frequency space by the Chebyshev kernel
+    bool rz_done = cg_mode && pl.rz_freq;     // r.z partials produced in frequency space by the Chebyshev kernel
     if (!(parts & 2)) {
-        rz_done = h->fast && reg_cheb && cg_mode;      // (timing the inverse transform alone: the form that follows the register-exchange kernel)
-    } else if (elph_pg_cheb_usable(h)) {
+        rz_done = h->fast && pl.reg_cheb && cg_mode;      // (timing the inverse transform alone: the form that follows the register-exchange kernel)
+    } else if (pl.cheb == CgPlan::CH_PG) {
         // an even-L square lattice beyond 16 x 16 (L = 18 ... 32), uniform hopping: the recursion in registers, a patch of sites per lane
         // (whether the lattice still fits the lane-program family — 18 x 18, 20 x 20 — or only the generic kernels)
-        const bool want = cg_mode && 2 * Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && h->px_solve;      // (r.z in frequency space: the p/x-fused iteration's)
-        int rcp = elph_pg_kpm_cheb(h, nrhs, st, want ? B.rz : nullptr, B.nrz, B.rr);
+        int rcp = elph_pg_kpm_cheb(h, nrhs, st, rz_done ? B.rz : nullptr, B.nrz, B.rr);
         if (rcp) return rcp;
-        rz_done = want;
-    } else if (h->fast) {
-        const bool want = cg_mode && 2 * Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N;
-        int rcf = elph_fast_kpm_cheb(h, nrhs, st, want ? B.rz : nullptr, B.nrz, &rz_done, B.rr, (fold && want) ? nct : 0);
+    } else if (pl.cheb == CgPlan::CH_LANE) {
+        int rcf = elph_fast_kpm_cheb(h, nrhs, st, pl.reg_cheb, rz_done ? B.rz : nullptr, B.nrz, B.rr, (fold && rz_done) ? nct : 0);
         if (rcf) return rcf;
     } else {
-        const bool gwant = cg_mode && Lo2 <= B.nrz && B.dot_lo == 0 && B.dot_hi == N && h->px_solve;      // (the p/x-fused iteration of the generic family)
         // one thread per bond of the largest colour (up to 1024): a colour is then one LDS round trip per thread; the bond
         // program rides in LDS when it fits next to the slab
         int maxcol = 1;
@@ -1319,12 +1292,11 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         const int lds_tables = (N <= 65535 && shm + tab <= 64 * 1024) ? 1 : 0;
         DISPATCH_NPL(cnpl, {
             hipLaunchKernelGGL((k_kpm_cheb<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs), shm + (lds_tables ? tab : 0),
-                               h->stream, h->d_nu, K, m, Lo2, st, lds_tables, gwant ? B.rz : nullptr, B.nrz, B.rr);
+                               h->stream, h->d_nu, K, m, Lo2, st, lds_tables, rz_done ? B.rz : nullptr, B.nrz, B.rr);
         });
-        rz_done = gwant;
     }
     // r.z partial slots: (blockIdx.y * gridDim.x + blockIdx.x) < ceil(L/TPT)*nst <= L*npl = nrz; the kernel clears the rest
-    if ((parts & 4) && cg_mode == 2 && h->px_solve) {
+    if ((parts & 4) && cg_mode == 2 && pl.px) {
         // p/x-fused tail: x += alpha p, p = P^-1 r + beta p in the epilogue of the inverse transform; P^-1 r itself is not written
         if (!rz_done) { elph_set_error("p/x-fused iteration planned, but the Chebyshev kernel did not deliver r.z (internal error)"); return ELPH_E_STATE; }
         int rcd = elph_dft_mfma_inv_px(h, h->d_nu, N, nrhs, st, h->d_p, h->d_x, B.alpha, B.rz, B.nrz);
@@ -1341,15 +1313,11 @@ int elph_launch_rz_partials(elph_handle_s *h, int nrhs);
 
 int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero) {
     // expects d_b (layout S), d_x = initial guess; computes r0, p0 and seeds the state
+    h->plan = elph_plan_cg(h, nrhs, use_prec, nrhs);      // the kernels of this solve's iteration
     CgBufs B = make_bufs(h, nrhs);
     h->ap_count = 0;
     const int N = (int)h->N, L = (int)h->L;
     int rc = ELPH_OK;
-    {   // the form of this solve's preconditioned iteration
-        const bool px = use_prec && h->kpm_ready && px_plan(h, nrhs);
-        h->px_solve = px;
-        h->px_via_pg = px && h->fast && h->lp_mc != 4;
-    }
     h->x_zero_seen = x_zero;
     if (h->x_zero_seen) {       // x0 = 0 (the library zeroed it for this solve): A x0 = 0 without the mat-vec
         if (hipMemsetAsync(h->d_tmp, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream) != hipSuccess) { elph_set_error("memset failed"); return ELPH_E_HIP; }
@@ -1399,85 +1367,59 @@ int elph_launch_rz_partials(elph_handle_s *h, int nrhs) {
     return check_launch("k_rz_part");
 }
 
-// one CG iteration's kernels (graph-capturable: no syncs, no allocations, launch-invariant arguments)
-int elph_launch_cg_iteration(elph_handle_s *h, int nrhs, int use_prec) {
-    CgBufs B = make_bufs(h, nrhs);
-    int rc;
-    if (h->fast) {
-        const bool px = use_prec && h->px_solve;
-        if (px && h->px_via_pg) { ModelDev mp = elph_model_dev(h); rc = elph_pg_cg_ap(h, B, mp, nrhs, (int)(h->ap_count & 1), true); }
-        else rc = elph_fast_cg_ap(h, B, nrhs, (int)(h->ap_count & 1), px);
-        h->ap_count++;
-        if (rc) return rc;
-        if (use_prec && h->kpm_active && B.dot_lo == 0 && B.dot_hi == (int)h->N && elph_dft_mfma_xr_usable(h, (int)h->N, nrhs))
-            return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 2);      // k_cg_xr rides on the forward transform
-        if (px) { elph_set_error("p/x-fused iteration planned, but the residual update is not folded into the forward transform (internal error)"); return ELPH_E_STATE; }
-        rc = elph_fast_cg_xr(h, B, nrhs, (int)(h->ap_count & 1));
-        if (rc) return rc;
-    } else {
-        ModelDev m = elph_model_dev(h);
-        const int N = (int)h->N, L = (int)h->L;
-        dim3 grid((unsigned)L, (unsigned)nrhs, 1);
-        const size_t shm = (2 * (size_t)N + 16) * sizeof(double);
-        const bool pg = elph_pg_ap_usable(h) && (m.uniform || elph_pg_disorder_ok(h)) && B.npap == L;      // a large even-L square lattice: the patch-layout kernel (pgrid.hip)
-        if (use_prec && h->px_solve) {
-            // the p/x-fused iteration of the generic family (px_plan): k_cg_ap_pg (patch-form lattices) or k_cg_ap<PX> reads the ready p; the
-            // residual update rides on the forward transform, r.z comes from the Chebyshev kernel in frequency space, the p/x-update is the
-            // inverse transform's epilogue
-            if (pg) rc = elph_pg_cg_ap(h, B, m, nrhs, (int)(h->ap_count & 1), true);
-            else {
-                DISPATCH_NPL(gen_npl(h), {
-                    hipLaunchKernelGGL((k_cg_ap<NPL, true>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, (int)(h->ap_count & 1));
-                });
-                rc = check_launch("k_cg_ap<PX>");
-            }
-            h->ap_count++;
-            if (rc) return rc;
-            return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 2);
-        }
-        if (pg) { rc = elph_pg_cg_ap(h, B, m, nrhs, (int)(h->ap_count & 1)); if (rc) return rc; }
-        DISPATCH_NPL(gen_npl(h), {
-            if (!pg) hipLaunchKernelGGL((k_cg_ap<NPL>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, (int)(h->ap_count & 1));
-            hipLaunchKernelGGL((k_cg_xr<NPL>), grid, dim3((unsigned)gen_bs(h)), 0, h->stream, B, N, L, (int)((h->ap_count + 1) & 1));
-        });
-        h->ap_count++;
-        rc = check_launch("cg iteration");
-        if (rc) return rc;
-    }
-    if (use_prec) rc = elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 1);
-    return rc;
-}
-
-// one kernel of the iteration alone (measurement only: bench.py times the dominant kernel by itself)
-int elph_launch_cg_kernel(elph_handle_s *h, int nrhs, int which) {
-    CgBufs B = make_bufs(h, nrhs);
-    if (h->fast) {
-        if (which == 0) {
-            int rc;
-            if (B.params.use_prec && h->px_solve && h->px_via_pg) { ModelDev mp = elph_model_dev(h); rc = elph_pg_cg_ap(h, B, mp, nrhs, (int)(h->ap_count & 1), true); }
-            else rc = elph_fast_cg_ap(h, B, nrhs, (int)(h->ap_count & 1), B.params.use_prec && h->px_solve);
-            h->ap_count++;
-            return rc;
-        }
-        return elph_fast_cg_xr(h, B, nrhs, (int)(h->ap_count & 1));
-    }
+// the generic family's k_cg_ap (which = 0; px: its p/x-fused form, which reads the ready p) or k_cg_xr (which = 1)
+static int launch_gen(elph_handle_s *h, const CgBufs &B, int nrhs, int which, bool px, int parity) {
     ModelDev m = elph_model_dev(h);
     const int N = (int)h->N, L = (int)h->L;
-    dim3 grid((unsigned)L, (unsigned)nrhs, 1);
+    const dim3 grid((unsigned)L, (unsigned)nrhs, 1);
     const size_t shm = (2 * (size_t)N + 16) * sizeof(double);
-    if (which == 0 && elph_pg_ap_usable(h) && (m.uniform || elph_pg_disorder_ok(h)) && B.npap == L) {
-        int rc = elph_pg_cg_ap(h, B, m, nrhs, (int)(h->ap_count & 1), B.params.use_prec && h->px_solve);
-        h->ap_count++;
-        return rc;
+    if (which == 0 && px) {
+        DISPATCH_NPL(gen_npl(h), {
+            hipLaunchKernelGGL((k_cg_ap<NPL, true>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, parity);
+        });
+        return check_launch("k_cg_ap<PX>");
     }
-    const bool gpx = B.params.use_prec && h->px_solve;
     DISPATCH_NPL(gen_npl(h), {
-        if (which == 0 && gpx) hipLaunchKernelGGL((k_cg_ap<NPL, true>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, (int)(h->ap_count & 1));
-        else if (which == 0) hipLaunchKernelGGL((k_cg_ap<NPL>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, (int)(h->ap_count & 1));
-        else hipLaunchKernelGGL((k_cg_xr<NPL>), grid, dim3((unsigned)gen_bs(h)), 0, h->stream, B, N, L, (int)(h->ap_count & 1));
+        if (which == 0) hipLaunchKernelGGL((k_cg_ap<NPL>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, parity);
+        else hipLaunchKernelGGL((k_cg_xr<NPL>), grid, dim3((unsigned)gen_bs(h)), 0, h->stream, B, N, L, parity);
     });
-    if (which == 0) h->ap_count++;
-    return check_launch("cg kernel");
+    return check_launch(which == 0 ? "k_cg_ap" : "k_cg_xr");
+}
+
+// the planned k_cg_ap (px: its p/x-fused form); advances the ping-pong parity
+static int launch_cg_ap(elph_handle_s *h, const CgBufs &B, int nrhs, bool px) {
+    const int parity = (int)(h->ap_count++ & 1);
+    const CgPlan::Ap ap = h->plan.ap;
+    if (h->fast) {
+        if (px && ap == CgPlan::AP_PG) return elph_pg_cg_ap(h, B, elph_model_dev(h), nrhs, parity, true);
+        if (px && ap == CgPlan::AP_SQ16) return elph_sq16_cg_ap_px(h, B, nrhs, parity);
+        return elph_fast_cg_ap(h, B, nrhs, parity, px);
+    }
+    if (ap == CgPlan::AP_PG) return elph_pg_cg_ap(h, B, elph_model_dev(h), nrhs, parity, px);
+    return launch_gen(h, B, nrhs, 0, px, parity);
+}
+
+// k_cg_xr after the latest k_cg_ap
+static int launch_cg_xr(elph_handle_s *h, const CgBufs &B, int nrhs) {
+    const int parity = (int)(h->ap_count & 1);
+    return h->fast ? elph_fast_cg_xr(h, B, nrhs, parity) : launch_gen(h, B, nrhs, 1, false, parity);
+}
+
+// one CG iteration's kernels (graph-capturable: no syncs, no allocations, launch-invariant arguments), as h->plan says
+int elph_launch_cg_iteration(elph_handle_s *h, int nrhs, int use_prec) {
+    CgBufs B = make_bufs(h, nrhs);
+    int rc = launch_cg_ap(h, B, nrhs, use_prec && h->plan.px);
+    if (rc) return rc;
+    if (use_prec && h->plan.xr_in_fwd) return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 2);      // k_cg_xr rides on the forward transform
+    rc = launch_cg_xr(h, B, nrhs);
+    if (rc) return rc;
+    return use_prec ? elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 1) : ELPH_OK;
+}
+
+// one kernel of the iteration alone (measurement; the sharded iteration): 0 = k_cg_ap, 1 = k_cg_xr
+int elph_launch_cg_kernel(elph_handle_s *h, int nrhs, int which) {
+    CgBufs B = make_bufs(h, nrhs);
+    return which == 0 ? launch_cg_ap(h, B, nrhs, h->plan.px) : launch_cg_xr(h, B, nrhs);
 }
 
 CgBufs elph_make_bufs(elph_handle_s *h, int nrhs) { return make_bufs(h, nrhs); }

@@ -526,7 +526,8 @@ extern "C" int elph_debug_pcg_stamps(unsigned long long *out32) {
 }
 #endif
 
-// Whether the resident preconditioned kernel takes this solve, and its team shape.
+// Whether the resident preconditioned kernel takes this solve, and its team shape (the shape only: a handle cooling down after a time-out
+// — h->wg_broken — is its callers' test).
 static bool pcg_shape(const elph_handle_s *h, int nrhs, int *Wo, int *Go, int *nto) {
     // Measured on MI355X (profiles/r03/pcg_wg_phase_stamps.log) this form takes 38.9 us per iteration for one
     // right-hand side of config C against 35.2 us of the five-kernel streaming form — the two tau-transforms cost 6 us each on the
@@ -539,7 +540,7 @@ static bool pcg_shape(const elph_handle_s *h, int nrhs, int *Wo, int *Go, int *n
     const char *eo = getenv("ELPH_PCG_WG");
     if (eo && eo[0] == '0') return false;
     if (!(eo && eo[0] == '1') && nrhs < 6) return false;
-    if (!h->fast || h->wg_broken || h->kind != ELPH_MODEL_HOLSTEIN || h->sq_P != 2 || h->N != 256 || !h->sq_uniform || h->lp_mc != 4) return false;
+    if (!h->fast || h->kind != ELPH_MODEL_HOLSTEIN || h->sq_P != 2 || h->N != 256 || !h->sq_uniform || h->lp_mc != 4) return false;
     if (!h->kpm_ready || !h->kpm_active || h->dot_hi != 0 || h->solo_chain >= 0) return false;
     // (h->kpm_active says that SOME chain's expansion is active; the kernel runs the series of every right-hand side's chain without
     //  looking at KpmChainView::active, so a chain whose expansion is the identity — lam_mag uploaded as -1, tables unset — keeps the
@@ -569,7 +570,7 @@ bool elph_pcg_wg_usable(const elph_handle_s *h, int nrhs) { return pcg_shape(h, 
 int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran) {
     *ran = false;
     int W = 0, G = 0, nt = 0;
-    if (!B.params.use_prec || !pcg_shape(h, nrhs, &W, &G, &nt)) return ELPH_OK;
+    if (!B.params.use_prec || h->wg_broken || !pcg_shape(h, nrhs, &W, &G, &nt)) return ELPH_OK;      // (cooling down: elph_wg_cooldown_step, run_cg)
     ModelDev m = elph_model_dev(h);
     if (!m.uniform || !m.sq_bond) return ELPH_OK;
     const size_t n_slots = 2 * (size_t)nrhs * wg::SLOTS_PER_RHS, n_flags = (size_t)nrhs * wg::PCG_FLAGS;

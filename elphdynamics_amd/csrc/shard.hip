@@ -275,6 +275,7 @@ static int shard_run(elph_handle_s *h, const double *b_slab, double tol, int64_t
     CgParams P;
     P.tol = tol; P.kmax = (kappa_max > 0.0) ? kappa_max : h->kmax; P.maxiter = maxiter; P.use_prec = 0; P.record_hist = 0; P.hist_stride = 0;
     h->cur_params = P;
+    h->plan = elph_plan_cg(h, 1, false, 1);
     const size_t bytes = (size_t)h->ndim * sizeof(double);
     if (b_slab) {
         HIPCHK(hipMemcpyAsync(h->d_stage_in, b_slab, bytes, hipMemcpyHostToDevice, h->stream));
@@ -334,6 +335,7 @@ int elph_i_shard_run_ranks(elph_handle_s *const *hs, int P, int nsets, void *h_a
         int rc = elph_i_ensure_capacity(h, 1);
         if (rc) return rc;
         h->cur_params = Pm;
+        h->plan = elph_plan_cg(h, 1, false, 1);
         const size_t bytes = (size_t)h->ndim * sizeof(double);
         HIPCHK(hipMemsetAsync(S->mail, 0, S->mail_bytes, st));
         HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, st));
@@ -702,6 +704,7 @@ static int shard_kpm_core(elph_handle_s *h, elph_handle_s *hfull, ShardState *S,
     CgParams P;
     P.tol = tol; P.kmax = (kappa_max > 0.0) ? kappa_max : h->kmax; P.maxiter = maxiter; P.use_prec = 1; P.record_hist = 0; P.hist_stride = 0;
     h->cur_params = P;
+    h->plan = elph_plan_cg(h, 1, false, 1);      // (unfused: the iteration's own kernels around the KPM apply of the full lattice)
     const size_t bytes = (size_t)h->ndim * sizeof(double);
     auto body = [&]() -> int {
         int r;

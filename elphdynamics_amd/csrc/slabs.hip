@@ -194,12 +194,12 @@ static bool slabs_debug() { return getenv("ELPH_SLABS_DEBUG") != nullptr; }
 // right-hand side, or two where two SETS of slabs fit the chip together (2 P G <= 240 workgroups: both solves in one launch — one launch
 // after the other two right-hand sides cost 22-25 us against 15-18 streaming).
 // ELPH_SLABS=0: never; =1: wherever the decomposition exists (any count, slabs up to 320 sites, up to 8 right-hand sides: the tests);
-// ELPH_SLABS_P forces the slab count.
+// ELPH_SLABS_P forces the slab count.  The shape only: a handle cooling down after a time-out (h->wg_broken) is its callers' test.
 bool elph_i_slabs_usable(elph_handle_s *h, int nrhs) {
     const char *e = getenv("ELPH_SLABS");
     const int force = e ? atoi(e) : -1;
     if (force == 0 || nrhs < 1 || nrhs > (force == 1 ? 8 : 2)) return false;
-    if (h->kind != ELPH_MODEL_HOLSTEIN || h->is_slab || h->shard || h->nchains != 1 || h->solo_chain >= 0 || h->dot_hi != 0 || h->wg_broken) return false;
+    if (h->kind != ELPH_MODEL_HOLSTEIN || h->is_slab || h->shard || h->nchains != 1 || h->solo_chain >= 0 || h->dot_hi != 0) return false;
     if (h->N <= 5 * ELPH_WAVE || !h->have_E) return false;
     if (h->slabs) {
         // two right-hand sides (the pseudofermion pair): only as ONE launch of two sets of slabs — all 2 P G workgroups resident at once;
@@ -321,7 +321,7 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
 extern "C" int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int *sites_per_slab, int *own_sites) {
     if (!h || !usable) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     HIPCHK(hipSetDevice(h->device));
-    *usable = elph_i_slabs_usable(h, nrhs) ? 1 : 0;
+    *usable = (!h->wg_broken && elph_i_slabs_usable(h, nrhs)) ? 1 : 0;      // (0 while the handle cools down after a time-out)
     const SlabSet *S = static_cast<const SlabSet *>(h->slabs);
     if (slabs) *slabs = (*usable && S) ? S->P : 0;
     if (sites_per_slab) *sites_per_slab = (*usable && S) ? S->Nloc : 0;
