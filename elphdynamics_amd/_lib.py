@@ -128,7 +128,24 @@ BENCH_SIGNATURES = {
     "elph_bench_px_info": (c_int, [Handle, P_int]),
     "elph_bench_pg_info": (c_int, [Handle, P_int, P_int, P_int, P_int, P_int]),
     "elph_bench_slabs_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
+    "elph_bench_lattice_shape": (c_int, [c_int, c_i64, c_i64, P_i64, P_dbl, P_dbl, P_int]),
 }
+
+# the slots of elph_bench_lattice_shape's vector, in order (elph_bench.h)
+LATTICE_SHAPE_SLOTS = ("sq_LX", "sq_LY", "sq_dpp", "hc_LX", "hc_LY", "hc12", "patch_kind", "patch_L", "patch_PX", "patch_PY", "patch_NW",
+                       "grid_GX", "grid_GY", "hgrid_regs", "hop_uniform", "bond_map")
+
+
+def lattice_shape(kind, nsites, table, cosht=None, sinht=None):
+    """What the library recognises in a checkerboard-ordered bond table (1-based, (nbonds, 2)), as {slot: value}.  Needs no device."""
+    lib = load()
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 2)
+    c = None if cosht is None else np.ascontiguousarray(cosht, dtype=np.float64)
+    s = None if sinht is None else np.ascontiguousarray(sinht, dtype=np.float64)
+    out = (c_int * len(LATTICE_SHAPE_SLOTS))()
+    check(lib.elph_bench_lattice_shape(int(kind), int(nsites), table.shape[0], iptr(table) if table.size else None,
+                                       None if c is None else dptr(c), None if s is None else dptr(s), out))
+    return dict(zip(LATTICE_SHAPE_SLOTS, list(out)))
 
 
 class ElphError(RuntimeError):

@@ -55,20 +55,17 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, 
 // that can deliver r.z in frequency space), in the order the dispatch tries them; *hgn: cells per lane of the honeycomb grid form
 int elph_reg_cheb_form(const elph_handle_s *h, int *hgn) {
     const bool hol = h->kind == ELPH_MODEL_HOLSTEIN;
-    if (h->sq_P > 0) return REG_SQ;
+    const LatticeShape &s = h->shape;
+    if (s.dpp() > 0) return REG_SQ;
     // any other even-L square lattice (L = 4, 6, 10, 12, 14) with one (cosh, sinh) for every bond: the GRID layout
-    if (h->sq_L > 0 && h->sq_uniform && hol) return REG_SQ_GRID;
-    if (h->hc_L > 0 && !h->hc12 && h->hc_uniform && hol) {
-        // any other honeycomb lattice whose cells fit a grid of lanes, one (cosh, sinh) for every bond: the HGRID layout
-        const int L = h->hc_L;
-        const int n = (L * L <= 64) ? 2 : ((L % 2 == 0 && (L / 2) * L <= 64) ? 4 : ((L % 2 == 0 && (L / 2) * (L / 2) <= 64) ? 8 : 0));
-        if (n) {
-            if (hgn) *hgn = n;
-            return REG_HC_GRID;
-        }
+    if (s.sq_L() > 0 && h->sq_chain_uniform && hol) return REG_SQ_GRID;
+    if (s.hc_L() > 0 && !s.hc12() && h->kpm_hop_uniform && hol && s.hgrid_regs()) {
+        // any other square honeycomb lattice whose cells fit a grid of lanes, one (cosh, sinh) for every bond: the HGRID layout
+        if (hgn) *hgn = s.hgrid_regs();
+        return REG_HC_GRID;
     }
     // the honeycomb lattice of 12 x 12 cells with one (cosh, sinh) for every bond: the quad layout
-    if (h->hc12 && h->hc_uniform && hol) return REG_HC12;
+    if (s.hc12() && h->kpm_hop_uniform && hol) return REG_HC12;
     return REG_NONE;
 }
 

@@ -96,7 +96,7 @@ __device__ __forceinline__ void dpp_pair_odd_up4(double (&t)[4], const double (&
 }
 
 // ---- GRID layout: ANY even-L square lattice, 4 <= L <= 16, in the reference's colouring [x-even | x-odd | y-even | y-odd] ----------------
-// (detect_square; cg_wg.hip FORM 5, cg_fast_impl.inc: the Chebyshev recursion).  The 2 x 2 patches of the lattice sit on a G x G grid
+// (elph_recognise_lattice; cg_wg.hip FORM 5, cg_fast_impl.inc: the Chebyshev recursion).  The 2 x 2 patches of the lattice sit on a G x G grid
 // of lanes, G = L / 2 <= 8: lane l < G*G holds the patch X = l % G, Y = l / G; register q is the site x = 2 X + (q & 1),
 // y = 2 Y + (q >> 1); site = x + L y.  x-even and y-even bonds pair two registers of a lane; x-odd and y-odd bonds cross to the
 // patches X +- 1 / Y +- 1 (cyclically) — by ds_bpermute, whatever G is: the 16 x 16 and 8 x 8 lattices have DPP forms of their own
@@ -170,7 +170,7 @@ __device__ __forceinline__ void grid_sweepN(double (&v)[NS][4], const GridCtx &X
 }
 
 // ---- HGRID layout: ANY honeycomb lattice of L x L two-site cells (site = 2 (x + L y) + orbital) in the reference's colouring
-// [A-B of a cell | B(x,y)-A(x+1,y) | B(x,y)-A(x,y+1)] (detect_honeycomb) whose cells fit a grid of lanes: PX x PY cells per lane
+// [A-B of a cell | B(x,y)-A(x+1,y) | B(x,y)-A(x,y+1)] (elph_recognise_lattice) whose cells fit a grid of lanes: PX x PY cells per lane
 // (NPL = 2 PX PY registers: 1 x 1 -> 2, 2 x 1 -> 4, 2 x 2 -> 8), lanes on a GX x GY grid, GX = L / PX, GY = L / PY, GX GY <= 64 —
 // L <= 8 with one cell per lane, L = 10 with two, L = 14 and 16 with four (512 sites in ONE wave).  Register 2 (cx + PX cy) + orbital
 // is the site of cell (PX X + cx, PY Y + cy) of lane (X, Y) = (l % GX, l / GX).  A-B pairs registers of the lane; the other two colours

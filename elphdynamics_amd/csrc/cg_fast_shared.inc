@@ -351,11 +351,12 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, 
         // faster at 1 right-hand side or at 128: block dispatch is not what the kernel waits for)
 #define SQ_LAUNCH(PV, UV, ...) hipLaunchKernelGGL((k_kpm_cheb_sq<PV, UV, ##__VA_ARGS__>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
                                              h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
-        if (h->sq_P == 2 && h->sq_uniform && nrhs >= 16) {
+        const int P = h->shape.dpp();
+        if (P == 2 && h->sq_chain_uniform && nrhs >= 16) {
             hipLaunchKernelGGL((k_kpm_cheb_sq_w4<2, true, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
                                h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
-        } else if (h->sq_P == 2) { if (h->sq_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
-        else              { if (h->sq_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
+        } else if (P == 2) { if (h->sq_chain_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
+        else        { if (h->sq_chain_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
 #undef SQ_LAUNCH
         return check_launch_f("k_kpm_cheb_sq");
     }

@@ -287,10 +287,10 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, 
 }  // namespace sq16
 
 // Can the p/x-fused k_cg_ap of this handle run in the register-exchange form?  Holstein on the 16 x 16 square lattice in the reference's
-// colouring (detect_square: sq_P = 2), a template chunk length.  (ELPH_SQ16_AP=0, the lane-program kernel instead, is elph_plan_cg's.)
+// colouring (elph_recognise_lattice: the 16 x 16 DPP size), a template chunk length.  (ELPH_SQ16_AP=0, the lane-program kernel instead, is elph_plan_cg's.)
 bool elph_sq16_ap_usable(const elph_handle_s *h, int T) {
     if (h->kind != ELPH_MODEL_HOLSTEIN) return false;
-    const bool sq = h->sq_P == 2 && h->N == 256 && h->d_sq_bond, hc = h->hc12 && h->hc_uniform && h->N == 288;      // (config C; config D, uniform hopping)
+    const bool sq = h->shape.dpp() == 2 && h->d_sq_bond, hc = h->shape.hc12() && h->kpm_hop_uniform;      // (config C; config D, uniform hopping)
     if (!sq && !hc) return false;
     return h->L % T == 0 && (T == 20 || T == 16 || T == 10 || T == 8 || T == 5 || T == 4 || T == 2);
 }
@@ -303,7 +303,7 @@ int elph_sq16_cg_ap_px(elph_handle_s *h, const CgBufs &B, int nrhs, int parity) 
     const dim3 grid((unsigned)(nrhs * B.npap));
 #define SQ16_LAUNCH(TT)                                                                                                            \
     do {                                                                                                                            \
-        if (h->hc12) hipLaunchKernelGGL((sq16::k_cg_ap_hc12_px<TT, 2, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po);                \
+        if (h->shape.hc12()) hipLaunchKernelGGL((sq16::k_cg_ap_hc12_px<TT, 2, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po);                \
         else if (!m.uniform) hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, false, 2, 2>), grid, dim3(WAVE), 0, h->stream, B, m, po);  \
         else hipLaunchKernelGGL((sq16::k_cg_ap_sq16_px<TT, true, 4, 3>), grid, dim3(WAVE), 0, h->stream, B, m, po);                 \
     } while (0)

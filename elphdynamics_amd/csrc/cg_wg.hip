@@ -892,9 +892,9 @@ static bool wg_no_dpp() {
     return e && e[0] == '1';
 }
 
-// DPP form: Holstein on the 16 x 16 square lattice in the reference's colouring (detect_square)
+// DPP form: Holstein on the 16 x 16 square lattice in the reference's colouring (elph_recognise_lattice)
 static bool sq_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->sq_P == 2 && h->N == 256 && m.sq_bond && !wg_no_dpp();
+    return h->shape.dpp() == 2 && m.sq_bond && !wg_no_dpp();
 }
 
 // T slices per wave: what the register file takes at two waves per SIMD — lane-program form 2 for site phonons with <= 4 sites
@@ -902,40 +902,36 @@ static bool sq_form(const elph_handle_s *h, const ModelDev &m) {
 // 2-slice shape cannot hold in one round (6.8 us per iteration, but 48 right-hand sides per round: 14 vs 7.3 M mat-vecs/s);
 // W = the largest divisor of Ltau / T that is <= 8 waves; G = workgroups per right-hand side (<= 32: the 2G record granules of
 // a meeting are polled by one wave instruction)
-// honeycomb DPP form: Holstein with uniform hopping on 12 x 12 cells in the reference's colouring (detect_honeycomb12)
+// honeycomb DPP form: Holstein with uniform hopping on 12 x 12 cells in the reference's colouring
 static bool hc_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->hc12 && m.uniform && !wg_no_dpp();
+    return h->kind == ELPH_MODEL_HOLSTEIN && h->shape.hc12() && m.uniform && !wg_no_dpp();
 }
 
-// 8 x 8 DPP form: Holstein with uniform hopping on the 8 x 8 square lattice in the reference's colouring (detect_square: sq_P = 1)
+// 8 x 8 DPP form: Holstein with uniform hopping on the 8 x 8 square lattice in the reference's colouring
 static bool s8_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->sq_P == 1 && h->N == 64 && m.uniform && !wg_no_dpp();
+    return h->kind == ELPH_MODEL_HOLSTEIN && h->shape.dpp() == 1 && m.uniform && !wg_no_dpp();
 }
 
 // grid form: Holstein with uniform hopping on a periodic LX x LY square lattice in the reference's colouring whose 2 x 2 patches fit the
-// lanes of a wave (detect_square: sq_LX, sq_LY).  An ordinary solve takes it for the sizes WITHOUT a DPP form of their own (not 16 x 16,
+// lanes of a wave (LatticeShape::small_square).  An ordinary solve takes it for the sizes WITHOUT a DPP form of their own (not 16 x 16,
 // not 8 x 8); a sharded solve (for_shard) for every size — the slab closed into a ring is such a lattice, and the DPP forms know no shards.
 static bool gr_form(const elph_handle_s *h, const ModelDev &m, bool for_shard = false) {
-    if (h->kind != ELPH_MODEL_HOLSTEIN || h->sq_LX < 4 || h->sq_LY < 4 || !m.uniform || m.grid_GX * m.grid_GY < 1 || m.grid_GX * m.grid_GY > 64 || wg_no_dpp()) return false;
-    return for_shard || h->sq_P == 0;
+    if (h->kind != ELPH_MODEL_HOLSTEIN || !h->shape.small_square() || !m.uniform || m.grid_GX * m.grid_GY < 1 || m.grid_GX * m.grid_GY > 64 || wg_no_dpp()) return false;
+    return for_shard || h->shape.dpp() == 0;
 }
 
 // triangular grid form: Holstein with uniform hopping on an even-L triangular lattice of at most 16 x 16 sites in the reference's colouring
-// (detect_triangular: pg_kind 3): the GRID layout with the two diagonal colours (pgrid::Tri<2, 2>)
+// (the recognised shape has a grid of lanes): the GRID layout with the two diagonal colours (pgrid::Tri<2, 2>)
 static bool tg_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->pg_kind == 3 && h->pg_L >= 4 && h->pg_L <= 16 && m.uniform && m.grid_GX == h->pg_L / 2 && m.grid_GY == h->pg_L / 2 && !wg_no_dpp();
+    return h->kind == ELPH_MODEL_HOLSTEIN && h->shape.kind == LatticeShape::TRIANGULAR && h->shape.GX > 0 && m.uniform && !wg_no_dpp();
 }
 
 // honeycomb grid form: Holstein with uniform hopping on a periodic honeycomb lattice of LX x LY cells in the reference's colouring whose cells
-// fit a grid of lanes (detect_honeycomb: hc_LX, hc_LY; 12 x 12 has a DPP form of its own — which knows no shards).  Returns the registers per
+// fit a grid of lanes (LatticeShape::hgrid_regs; 12 x 12 has a DPP form of its own — which knows no shards).  Returns the registers per
 // lane (2, 4 or 8: 1, 2 x 1 or 2 x 2 cells), 0: no.
 static int hg_form(const elph_handle_s *h, const ModelDev &m, bool for_shard = false) {
-    if (h->kind != ELPH_MODEL_HOLSTEIN || h->hc_LX < 2 || h->hc_LY < 2 || (h->hc12 && !for_shard) || !m.uniform || m.hc_LX != h->hc_LX || wg_no_dpp()) return 0;
-    const int LX = h->hc_LX, LY = h->hc_LY;
-    if (LX * LY <= 64) return 2;
-    if (LX % 2 == 0 && (LX / 2) * LY <= 64) return 4;
-    if (LX % 2 == 0 && LY % 2 == 0 && (LX / 2) * (LY / 2) <= 64) return 8;
-    return 0;
+    if (h->kind != ELPH_MODEL_HOLSTEIN || (h->shape.hc12() && !for_shard) || !m.uniform || wg_no_dpp()) return 0;
+    return h->shape.hgrid_regs();
 }
 
 static int largest_divisor_le8(int n, int cap = 8) { for (int w = std::min(cap, n); w >= 1; --w) if (n % w == 0) return w; return 1; }
@@ -1162,8 +1158,9 @@ bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs) {
     const char *eo = getenv("ELPH_NO_WG");                 // read per call: the tests switch between the two forms
     const bool off = eo && eo[0] == '1';
     // (h->npl > 5: the lane-program form's limit — 320 sites; the honeycomb grid form carries up to 512 in one wave)
-    const bool tri_grid = h->kind == ELPH_MODEL_HOLSTEIN && h->pg_kind == 3 && h->pg_L <= 16;      // (a six-colour lattice, but its resident form needs no lane program)
-    if (off || !h->fast || (h->lp_mc != 4 && !tri_grid) || (h->npl > 5 && !(h->hc_LX > 0 && !h->hc12 && h->kind == ELPH_MODEL_HOLSTEIN)) || h->dot_hi != 0 || h->solo_chain >= 0) return false;
+    const bool hol = h->kind == ELPH_MODEL_HOLSTEIN;
+    const bool tri_grid = hol && h->shape.kind == LatticeShape::TRIANGULAR && h->shape.GX > 0;      // (a six-colour lattice, but its resident form needs no lane program)
+    if (off || !h->fast || (h->lp_mc != 4 && !tri_grid) || (h->npl > 5 && !(h->shape.honeycomb() && !h->shape.hc12() && hol)) || h->dot_hi != 0 || h->solo_chain >= 0) return false;
     wg::Shape sh;
     if (!wg::pick_shape(h, elph_model_dev(h), wg_t(), nrhs, &sh)) return false;
     if (T) *T = sh.T;

@@ -85,7 +85,7 @@ __device__ __forceinline__ void sweepN(double *buf, const unsigned (&ij)[MC * ((
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The 16 x 16 square lattice with the reference's colouring [x-even | x-odd | y-even | y-odd] (verified on the host:
-// detect_square): the checkerboard WITHOUT LDS slabs.  Lane l holds a 2 x 2 PATCH of sites:
+// elph_recognise_lattice): the checkerboard WITHOUT LDS slabs.  Lane l holds a 2 x 2 PATCH of sites:
 //     X = (l >> 1) & 7,  Y = 2 (l >> 4) + (l & 1):  x = 2 X + (q & 1),  y = 2 Y + (q >> 1)   (registers q = 0..3)
 // with the two rows of the patch stored in REVERSE order in the lanes of odd Y (q >> 1 = 0 is the row y = 2 Y + 1 there).  Then
 //   x-even, y-even  pair two registers of one lane                                   — no data movement at all;
@@ -234,7 +234,7 @@ __device__ __forceinline__ void sq_sweepS(double (&v)[NS][4], const SqSsh<NREG, 
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The honeycomb lattice of 12 x 12 cells (config D: 288 sites) in the reference's colouring [A-B of a cell | B(x,y)-A(x+1,y) |
-// B(x,y)-A(x,y+1)] (verified on the host: detect_honeycomb12): the checkerboard WITHOUT LDS slabs.  A 16-lane DPP row holds the
+// B(x,y)-A(x,y+1)] (verified on the host: elph_recognise_lattice): the checkerboard WITHOUT LDS slabs.  A 16-lane DPP row holds the
 // twelve cells x = 0..11 of three lattice rows in its lanes 2..13, one lane per x, plus TWO MIRROR LANES on either side — lanes 0, 1
 // carry copies of x = 10, 11 and lanes 14, 15 copies of x = 0, 1 — so that the x-neighbour is always the next lane of the row
 // (row_ror:1 / row_ror:15) although 12 is no period of any DPP pattern.  Row g of the wave (lanes 16 g ..) holds the lattice rows
@@ -319,7 +319,7 @@ __device__ __forceinline__ void hc_sweepN(double (&v)[NS][HC_NPL], const HcCtx &
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The 8 x 8 square lattice (config B: 64 sites, ONE per lane) in the reference's colouring [x-even | x-odd | y-even | y-odd] (verified
-// on the host: detect_square, sq_P = 1): the checkerboard without LDS slabs.  Lane l holds the site x = (l >> 1) & 7,
+// on the host: elph_recognise_lattice, the 8 x 8 DPP size): the checkerboard without LDS slabs.  Lane l holds the site x = (l >> 1) & 7,
 // y = 2 (l >> 4) + (l & 1): two lattice rows are interleaved in a 16-lane DPP row, so that x +- 1 is the lane 2 up / 2 down of the
 // row, cyclically (the period of row_ror, as on the 16 x 16 lattice):
 //   x-even  partner = lane ^ 2: quad_perm [2,3,0,1];            x-odd   the lane 2 up (x odd) or 2 down (x even): two row

@@ -79,9 +79,7 @@ void elph_lp_pack(const elph_handle_s *h, const double *per_bond, double *out, d
     }
 }
 
-static void detect_square(elph_handle_s *h);
-static void detect_honeycomb12(elph_handle_s *h);
-static void detect_triangular(elph_handle_s *h);
+static LatticeShape elph_recognise_lattice(const elph_handle_s *h);
 
 static int build_lane_program(elph_handle_s *h) {
     h->lp_mc = (h->ncol <= 4) ? 4 : 6;      // kernels exist for 4-colour (square, honeycomb, chain) and 6-colour (triangular) programs
@@ -118,28 +116,26 @@ static int build_lane_program(elph_handle_s *h) {
     RC(dev_alloc(&h->d_lp_s, ntau * NE * ELPH_WAVE));
     RC(dev_alloc(&h->d_lp_cbar, (size_t)NE * ELPH_WAVE));
     RC(dev_alloc(&h->d_lp_sbar, (size_t)NE * ELPH_WAVE));
-    detect_honeycomb12(h);
-    detect_square(h);
-    detect_triangular(h);
-    if (h->sq_L > 0) {
+    h->shape = elph_recognise_lattice(h);
+    if (h->shape.sq_L() > 0) {
         RC(dev_alloc(&h->d_sq_cbar, (size_t)4 * h->N));
         RC(dev_alloc(&h->d_sq_sbar, (size_t)4 * h->N));
         RC(dev_alloc(&h->d_sq_bond, (size_t)4 * h->N));
-        HIPCHK(hipMemcpy(h->d_sq_bond, h->sq_bond.data(), sizeof(int) * 4 * h->N, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_sq_bond, h->shape.bond.data(), sizeof(int) * 4 * h->N, hipMemcpyHostToDevice));
     }
-    if (h->pg_kind == 1 && h->pg_bond.size() == (size_t)4 * h->N) {      // the site -> bond map of the colouring: hopping disorder in the patch layout (pgrid.hip)
+    if (h->shape.kind == LatticeShape::SQUARE && h->shape.patch()) {      // the site -> bond map of the colouring: hopping disorder in the patch layout (pgrid.hip)
         RC(dev_alloc(&h->d_pg_bond, (size_t)4 * h->N));
-        HIPCHK(hipMemcpy(h->d_pg_bond, h->pg_bond.data(), sizeof(int) * 4 * h->N, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_pg_bond, h->shape.bond.data(), sizeof(int) * 4 * h->N, hipMemcpyHostToDevice));
     }
     return ELPH_OK;
 }
 
-// Recognise the even-L square lattice with the reference's colouring [x-even | x-odd | y-even | y-odd]
-// (even L from 4 to 16, site = x + L*y).  Only then may the register-exchange forms run (sq_L; sq_P = L / 8 for L = 8, 16, the sizes with
-// DPP layouts of their own; the GRID layout of cg_fast_common.h serves the others); any deviation (other lattice, other bond order,
-// disordered table) leaves sq_L = sq_P = 0 and the LDS kernels are used.
-static bool match_square(elph_handle_s *h, int LX, int LY) {
-    h->sq_bond.assign((size_t)4 * h->N, -1);
+// Lattice recognition: the colouring elph_create found is matched against the reference's colourings of periodic square, honeycomb and triangular
+// lattices.  Any deviation (other lattice, other bond order) leaves the shape NONE, and the LDS kernels are used.
+
+// square LX x LY (site = x + LX y), colours [x-even | x-odd | y-even | y-odd]; fills bond ([4][N] the bond covering site i in colour col)
+static bool match_square(const elph_handle_s *h, int LX, int LY, std::vector<int> &bond) {
+    bond.assign((size_t)4 * h->N, -1);
     for (int col = 0; col < 4; ++col) {
         const int b0 = h->h_coloff[col], b1 = h->h_coloff[col + 1];
         if (b1 - b0 != h->N / 2) return false;
@@ -152,97 +148,17 @@ static bool match_square(elph_handle_s *h, int LX, int LY) {
             if (col < 2) ok = (yi == yj) && (partner(xi, col, LX) == xj) && (partner(xj, col, LX) == xi);
             else ok = (xi == xj) && (partner(yi, col - 2, LY) == yj) && (partner(yj, col - 2, LY) == yi);
             if (!ok) return false;
-            h->sq_bond[(size_t)col * h->N + i] = n;
-            h->sq_bond[(size_t)col * h->N + j] = n;
+            bond[(size_t)col * h->N + i] = n;
+            bond[(size_t)col * h->N + j] = n;
         }
     }
-    for (int v : h->sq_bond) if (v < 0) return false;
+    for (int v : bond) if (v < 0) return false;
     return true;
 }
 
-// Recognise an even-L triangular lattice (site = x + L y; bonds (1,0), (0,1), (1,-1): examples/holstein_hmc_triangular.toml) in the colouring
-// the checkerboard gives them: [x-even | x-odd | y-even | diagonal from even y | y-odd | diagonal from odd y], the diagonal of (x, y)
-// ending at (x - 1, y + 1).  Only then may the patch-layout kernels run on it (pgrid.hip, pgrid::Tri).
-static void detect_triangular(elph_handle_s *h) {
-    if (h->ncol != 6 || h->nb != 3 * h->N || h->N < 16) return;
-    int L = 0;
-    for (int l = 4; l <= 64; l += 2) if ((int64_t)l * l == h->N) L = l;
-    int px = 0, py = 0;
-    if (!L || !pgrid::pick_tpatch(L, &px, &py)) return;
-    auto partner = [L](int col, int x, int y, int *px_, int *py_) {
-        const int xp = (x + 1) % L, xm = (x + L - 1) % L, yp = (y + 1) % L, ym = (y + L - 1) % L;
-        switch (col) {
-            case 0: *px_ = x ^ 1; *py_ = y; break;
-            case 1: *px_ = (x & 1) ? xp : xm; *py_ = y; break;
-            case 2: *px_ = x; *py_ = y ^ 1; break;
-            case 3: if (!(y & 1)) { *px_ = xm; *py_ = yp; } else { *px_ = xp; *py_ = ym; } break;
-            case 4: *px_ = x; *py_ = (y & 1) ? yp : ym; break;
-            default: if (y & 1) { *px_ = xm; *py_ = yp; } else { *px_ = xp; *py_ = ym; } break;
-        }
-    };
-    std::vector<char> seen((size_t)6 * h->N, 0);
-    for (int col = 0; col < 6; ++col) {
-        const int b0 = h->h_coloff[col], b1 = h->h_coloff[col + 1];
-        if (b1 - b0 != h->N / 2) return;
-        for (int n = b0; n < b1; ++n) {
-            const int i = h->h_bi[n], j = h->h_bj[n];
-            int qx, qy;
-            partner(col, i % L, i / L, &qx, &qy);
-            if (qx + L * qy != j) return;
-            partner(col, j % L, j / L, &qx, &qy);
-            if (qx + L * qy != i) return;
-            if (seen[(size_t)col * h->N + i] || seen[(size_t)col * h->N + j]) return;
-            seen[(size_t)col * h->N + i] = seen[(size_t)col * h->N + j] = 1;
-        }
-    }
-    h->pg_L = L; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 3;
-}
-
-static void detect_square(elph_handle_s *h) {
-    h->sq_P = 0;
-    h->sq_L = 0;
-    h->sq_LX = h->sq_LY = 0;
-    if (h->ncol != 4 || h->nb != 2 * h->N || h->N < 16) return;
-    // candidates: the square first, then every even LX x LY with LX LY = N whose 2 x 2 patches fit the 64 lanes of a wave (the slab of a
-    // sharded solve: its rows closed into a ring)
-    std::vector<std::pair<int, int>> cand;
-    for (int l = 4; l <= 16; l += 2) if ((int64_t)l * l == h->N) cand.push_back({l, l});
-    for (int lx = 4; lx <= 32; lx += 2)
-        if (h->N % lx == 0) { const int ly = (int)(h->N / lx); if (ly >= 4 && ly % 2 == 0 && lx != ly && (lx / 2) * (ly / 2) <= 64) cand.push_back({lx, ly}); }
-    for (auto &c : cand) {
-        if (!match_square(h, c.first, c.second)) continue;
-        h->sq_LX = c.first; h->sq_LY = c.second;
-        if (c.first == c.second) { h->sq_L = c.first; h->sq_P = (c.first == 8 || c.first == 16) ? c.first / 8 : 0; }
-        return;
-    }
-    // a larger square lattice: PX x PY patches per lane (pgrid_dev.h) — the Chebyshev recursion of the preconditioner in registers
-    h->pg_L = h->pg_PX = h->pg_PY = h->pg_kind = 0;
-    h->pg_NW = 0;
-    for (int l = 18; l <= 64; l += 2) {
-        int px = 0, py = 0, nw = 1;
-        if ((int64_t)l * l != h->N) continue;
-        if (!pgrid::pick_patch(l, &px, &py)) {
-            // no patch that fits one wavefront: several wavefronts per slice, the patch edges through LDS (ELPH_PG_MW=0: the generic kernels, A/B)
-            if (!elph_pg_mw() || !pgrid::pick_patch_mw(l, &px, &py, &nw)) continue;
-        }
-        {   // hopping disorder on 28 x 28 / 32 x 32: 2 x 2 patches on four wavefronts instead of 4 x 4 on one — 12 table entries per thread instead of 40
-            // (measured, profiles/r06/hopping_disorder_patch_kernels_with_tables.log); ELPH_PG_MW=0 keeps the one-wavefront shape
-            bool uni = true;
-            if (h->kind == ELPH_MODEL_HOLSTEIN)
-                for (int64_t n = 1; n < h->nb && uni; ++n) uni = (h->h_c[(size_t)n] == h->h_c[0] && h->h_s[(size_t)n] == h->h_s[0]);
-            // (... and 30 x 30, whose 2 x 10 patches have no table variant: 15 x 15 threads on four wavefronts)
-            if (!uni && nw == 1 && ((px == 4 && py == 4) || (px == 2 && py == 10)) && elph_pg_mw()) { px = 2; py = 2; nw = ((l / 2) * (l / 2) + 63) / 64; }
-            h->pg_uniform_c = uni && h->kind == ELPH_MODEL_HOLSTEIN;
-        }
-        if (match_square(h, l, l)) { h->pg_L = l; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 1; h->pg_NW = nw; h->pg_bond = h->sq_bond; }
-    }
-    h->sq_bond.clear();
-}
-
-// Recognise a honeycomb lattice of L x L two-site cells (site = 2 (x + L y) + orbital; hc_L, and hc12 for L = 12) with the reference's colouring
-// [A-B of a cell | B(x,y)-A(x+1,y) | B(x,y)-A(x,y+1)] (the bond definitions of examples/holstein_hmc_honeycomb.toml through
-// Checkerboard.jl:471-515).  Only then may the register-exchange form of the resident CG run (cg_wg_dev.h, HcCtx).
-static bool match_honeycomb(elph_handle_s *h, int LX, int LY) {
+// honeycomb of LX x LY two-site cells (site = 2 (x + LX y) + orbital), colours [A-B of a cell | B(x,y)-A(x+1,y) | B(x,y)-A(x,y+1)] (the bond
+// definitions of examples/holstein_hmc_honeycomb.toml through Checkerboard.jl:471-515)
+static bool match_honeycomb(const elph_handle_s *h, int LX, int LY) {
     std::vector<char> seen((size_t)3 * h->N, 0);
     for (int col = 0; col < 3; ++col) {
         const int b0 = h->h_coloff[col], b1 = h->h_coloff[col + 1];
@@ -263,27 +179,105 @@ static bool match_honeycomb(elph_handle_s *h, int LX, int LY) {
     return true;
 }
 
-static void detect_honeycomb12(elph_handle_s *h) {
-    h->hc12 = false;
-    h->hc_L = 0;
-    h->hc_LX = h->hc_LY = 0;
-    if (h->ncol != 3 || (h->N & 1) || h->nb != 3 * (h->N / 2) || h->N < 8) return;
-    const int cells = (int)(h->N / 2);
-    std::vector<std::pair<int, int>> cand;
-    for (int l = 2; l <= 64; ++l) if (l * l == cells) cand.push_back({l, l});
-    for (int lx = 2; lx <= 32; ++lx)
-        if (cells % lx == 0) { const int ly = cells / lx; if (ly >= 2 && lx != ly) cand.push_back({lx, ly}); }
-    for (auto &c : cand) {
-        if (!match_honeycomb(h, c.first, c.second)) continue;
-        h->hc_LX = c.first; h->hc_LY = c.second;
-        if (c.first == c.second) {
-            h->hc_L = c.first; h->hc12 = (c.first == 12);
-            int px = 0, py = 0, nw = 1;
-            if (c.first > 16 && pgrid::pick_hpatch(c.first, &px, &py)) { h->pg_L = c.first; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 2; h->pg_NW = 1; }     // (pgrid.hip: PX x PY cells per lane)
-            else if (c.first > 16 && elph_pg_mw() && pgrid::pick_hpatch_mw(c.first, &px, &py, &nw)) { h->pg_L = c.first; h->pg_PX = px; h->pg_PY = py; h->pg_kind = 2; h->pg_NW = nw; }     // (several wavefronts per slice)
+// even-L triangular (site = x + L y; bonds (1,0), (0,1), (1,-1): examples/holstein_hmc_triangular.toml), colours [x-even | x-odd | y-even |
+// diagonal from even y | y-odd | diagonal from odd y], the diagonal of (x, y) ending at (x - 1, y + 1)
+static bool match_triangular(const elph_handle_s *h, int L) {
+    auto partner = [L](int col, int x, int y, int *px_, int *py_) {
+        const int xp = (x + 1) % L, xm = (x + L - 1) % L, yp = (y + 1) % L, ym = (y + L - 1) % L;
+        switch (col) {
+            case 0: *px_ = x ^ 1; *py_ = y; break;
+            case 1: *px_ = (x & 1) ? xp : xm; *py_ = y; break;
+            case 2: *px_ = x; *py_ = y ^ 1; break;
+            case 3: if (!(y & 1)) { *px_ = xm; *py_ = yp; } else { *px_ = xp; *py_ = ym; } break;
+            case 4: *px_ = x; *py_ = (y & 1) ? yp : ym; break;
+            default: if (y & 1) { *px_ = xm; *py_ = yp; } else { *px_ = xp; *py_ = ym; } break;
         }
-        return;
+    };
+    std::vector<char> seen((size_t)6 * h->N, 0);
+    for (int col = 0; col < 6; ++col) {
+        const int b0 = h->h_coloff[col], b1 = h->h_coloff[col + 1];
+        if (b1 - b0 != h->N / 2) return false;
+        for (int n = b0; n < b1; ++n) {
+            const int i = h->h_bi[n], j = h->h_bj[n];
+            int qx, qy;
+            partner(col, i % L, i / L, &qx, &qy);
+            if (qx + L * qy != j) return false;
+            partner(col, j % L, j / L, &qx, &qy);
+            if (qx + L * qy != i) return false;
+            if (seen[(size_t)col * h->N + i] || seen[(size_t)col * h->N + j]) return false;
+            seen[(size_t)col * h->N + i] = seen[(size_t)col * h->N + j] = 1;
+        }
     }
+    return true;
+}
+
+// The shape of a handle's lattice from its coloured bond table, its model kind and its hopping table (h_bi, h_bj, h_coloff, kind, h_c, h_s);
+// reads nothing else of the handle and changes nothing.  ELPH_PG_MW=0 (pgrid.hip: elph_pg_mw) keeps the patch shapes to one wavefront per slice.
+static LatticeShape elph_recognise_lattice(const elph_handle_s *h) {
+    LatticeShape s;
+    const bool hol = h->kind == ELPH_MODEL_HOLSTEIN;
+    if (hol && h->nb > 0) {      // the model's own hopping table: Holstein tables never change after elph_create
+        bool uni = true;
+        for (int64_t n = 1; n < h->nb && uni; ++n) uni = (h->h_c[(size_t)n] == h->h_c[0] && h->h_s[(size_t)n] == h->h_s[0]);
+        if (uni) { s.hop_uniform = true; s.hop_c = h->h_c[0]; s.hop_s = h->h_s[0]; }
+    }
+    const int64_t N = h->N;
+    if (h->ncol == 4 && h->nb == 2 * N && N >= 16) {
+        // the square up to 16 x 16 first, then every even LX x LY with LX LY = N whose 2 x 2 patches fit the 64 lanes of a wave (the slab of a
+        // sharded solve: its rows closed into a ring): the register-exchange forms (GRID layout; DPP layouts of their own for 8 x 8, 16 x 16)
+        std::vector<std::pair<int, int>> cand;
+        for (int l = 4; l <= 16; l += 2) if ((int64_t)l * l == N) cand.push_back({l, l});
+        for (int lx = 4; lx <= 32; lx += 2)
+            if (N % lx == 0) { const int ly = (int)(N / lx); if (ly >= 4 && ly % 2 == 0 && lx != ly && (lx / 2) * (ly / 2) <= 64) cand.push_back({lx, ly}); }
+        for (auto &c : cand)
+            if (match_square(h, c.first, c.second, s.bond)) {
+                s.kind = LatticeShape::SQUARE; s.LX = c.first; s.LY = c.second; s.GX = c.first / 2; s.GY = c.second / 2;
+                return s;
+            }
+        // a larger square lattice: PX x PY patches per lane (pgrid_dev.h) — the Chebyshev recursion of the preconditioner in registers
+        int l = 18;
+        while (l <= 64 && (int64_t)l * l != N) l += 2;
+        int px = 0, py = 0, nw = 1;
+        // no patch that fits one wavefront: several wavefronts per slice, the patch edges through LDS (ELPH_PG_MW=0: the generic kernels, A/B)
+        if (l <= 64 && (pgrid::pick_patch(l, &px, &py) || (elph_pg_mw() && pgrid::pick_patch_mw(l, &px, &py, &nw)))) {
+            // hopping disorder on 28 x 28 / 32 x 32: 2 x 2 patches on four wavefronts instead of 4 x 4 on one — 12 table entries per thread instead of 40
+            // (measured, profiles/r06/hopping_disorder_patch_kernels_with_tables.log); ELPH_PG_MW=0 keeps the one-wavefront shape
+            // (... and 30 x 30, whose 2 x 10 patches have no table variant: 15 x 15 threads on four wavefronts)
+            if (hol && !s.hop_uniform && nw == 1 && ((px == 4 && py == 4) || (px == 2 && py == 10)) && elph_pg_mw()) { px = 2; py = 2; nw = ((l / 2) * (l / 2) + 63) / 64; }
+            if (match_square(h, l, l, s.bond)) {
+                s.kind = LatticeShape::SQUARE; s.LX = s.LY = l; s.PX = px; s.PY = py; s.NW = nw;
+                return s;
+            }
+        }
+        s.bond.clear();
+    } else if (h->ncol == 3 && !(N & 1) && h->nb == 3 * (N / 2) && N >= 8) {
+        // honeycomb: square first, then rectangles (12 x 12 has the DPP / quad forms; beyond 16 x 16 cells, PX x PY cells per lane)
+        const int cells = (int)(N / 2);
+        std::vector<std::pair<int, int>> cand;
+        for (int l = 2; l <= 64; ++l) if (l * l == cells) cand.push_back({l, l});
+        for (int lx = 2; lx <= 32; ++lx)
+            if (cells % lx == 0) { const int ly = cells / lx; if (ly >= 2 && lx != ly) cand.push_back({lx, ly}); }
+        for (auto &c : cand) {
+            if (!match_honeycomb(h, c.first, c.second)) continue;
+            s.kind = LatticeShape::HONEYCOMB; s.LX = c.first; s.LY = c.second;
+            int px = 0, py = 0, nw = 1;
+            if (c.first == c.second && c.first > 16 &&
+                (pgrid::pick_hpatch(c.first, &px, &py) || (elph_pg_mw() && pgrid::pick_hpatch_mw(c.first, &px, &py, &nw)))) {
+                s.PX = px; s.PY = py; s.NW = nw;
+            }
+            return s;
+        }
+    } else if (h->ncol == 6 && h->nb == 3 * N && N >= 16) {
+        // triangular: the patch-layout kernels (pgrid::Tri); up to 16 x 16 also the GRID layout of the resident CG (cg_wg.hip: FORM 7)
+        int L = 0;
+        for (int l = 4; l <= 64; l += 2) if ((int64_t)l * l == N) L = l;
+        int px = 0, py = 0;
+        if (L && pgrid::pick_tpatch(L, &px, &py) && match_triangular(h, L)) {
+            s.kind = LatticeShape::TRIANGULAR; s.LX = s.LY = L; s.PX = px; s.PY = py; s.NW = 1;
+            if (L <= 16) s.GX = s.GY = L / 2;
+        }
+    }
+    return s;
 }
 
 // uploads the lane-program copy of the per-bond cosh/sinh tables (h_c/h_s)
@@ -336,6 +330,40 @@ static int ensure_capacity(elph_handle_s *h, int nrhs) {
     return ELPH_OK;
 }
 
+// the bond-table arguments of elph_create (and of the recognition probe)
+static int check_bond_table(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht, const double *sinht) {
+    if (nbonds > 0 && !neighbor_table) { elph_set_error("neighbor_table is null"); return ELPH_E_ARG; }
+    if (kind == ELPH_MODEL_HOLSTEIN && nbonds > 0 && (!cosht || !sinht)) { elph_set_error("cosht/sinht null"); return ELPH_E_ARG; }
+    for (int64_t n = 0; n < nbonds; ++n) {
+        const int64_t i = neighbor_table[2 * n], j = neighbor_table[2 * n + 1];
+        if (i < 1 || i > nsites || j < 1 || j > nsites || i == j) {
+            elph_set_error("neighbor_table[:,%lld] = (%lld,%lld) out of range 1..%lld", (long long)n + 1, (long long)i, (long long)j, (long long)nsites);
+            return ELPH_E_ARG;
+        }
+    }
+    return ELPH_OK;
+}
+
+// bond tables, 0-based; colours = maximal runs of site-disjoint bonds (reproduces the groups of checkerboard_groups!,
+// Checkerboard.jl:471-515, for any table in checkerboard order, and stays correct — only slower — for an arbitrary bond order).
+// Host only: h->N and h->nb are set, the table has been range-checked.
+static void colour_bonds(elph_handle_s *h, const int64_t *neighbor_table) {
+    h->h_bi.resize(h->nb); h->h_bj.resize(h->nb);
+    h->h_coloff.assign(1, 0);
+    std::vector<char> used(h->N, 0);
+    for (int64_t n = 0; n < h->nb; ++n) {
+        const int i = (int)(neighbor_table[2 * n] - 1), j = (int)(neighbor_table[2 * n + 1] - 1);
+        if (used[i] || used[j]) {
+            h->h_coloff.push_back((int)n);
+            std::fill(used.begin(), used.end(), 0);
+        }
+        used[i] = used[j] = 1;
+        h->h_bi[n] = i; h->h_bj[n] = j;
+    }
+    if (h->nb > 0) h->h_coloff.push_back((int)h->nb);
+    h->ncol = (int)h->h_coloff.size() - 1;
+}
+
 extern "C" int elph_create(elph_handle *out, int kind, int64_t nsites, int64_t ltau, int64_t nbonds,
                            const int64_t *neighbor_table, const double *cosht, const double *sinht, int device) {
     if (!out) { elph_set_error("out is null"); return ELPH_E_ARG; }
@@ -349,15 +377,7 @@ extern "C" int elph_create(elph_handle *out, int kind, int64_t nsites, int64_t l
     if (nsites * ltau > (int64_t)1 << 30) { elph_set_error("ndim too large"); return ELPH_E_UNSUPPORTED; }
     // (beyond 1024 slices the tau-transforms run as dft_big.hip's two-step form, whose launches carry the slice index in gridDim.y)
     if (ltau > 65535) { elph_set_error("ltau=%lld: the time axis is limited to 65535 slices (launch geometry of the long-axis transform)", (long long)ltau); return ELPH_E_UNSUPPORTED; }
-    if (nbonds > 0 && !neighbor_table) { elph_set_error("neighbor_table is null"); return ELPH_E_ARG; }
-    if (kind == ELPH_MODEL_HOLSTEIN && nbonds > 0 && (!cosht || !sinht)) { elph_set_error("cosht/sinht null"); return ELPH_E_ARG; }
-    for (int64_t n = 0; n < nbonds; ++n) {
-        const int64_t i = neighbor_table[2 * n], j = neighbor_table[2 * n + 1];
-        if (i < 1 || i > nsites || j < 1 || j > nsites || i == j) {
-            elph_set_error("neighbor_table[:,%lld] = (%lld,%lld) out of range 1..%lld", (long long)n + 1, (long long)i, (long long)j, (long long)nsites);
-            return ELPH_E_ARG;
-        }
-    }
+    RC(check_bond_table(kind, nsites, nbonds, neighbor_table, cosht, sinht));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { elph_set_error("no HIP device visible"); return ELPH_E_NOGPU; }
     if (device < 0 || device >= ndev) { elph_set_error("device %d not in 0..%d", device, ndev - 1); return ELPH_E_ARG; }
@@ -375,25 +395,7 @@ extern "C" int elph_create(elph_handle *out, int kind, int64_t nsites, int64_t l
     h->npl = (int)((nsites + ELPH_WAVE - 1) / ELPH_WAVE);
     h->maxiter = h->ndim;   // ConjugateGradient ctor default (IterativeSolvers.jl:49-51)
 
-    // bond tables, 0-based; colours = maximal runs of site-disjoint bonds (reproduces the groups of
-    // checkerboard_groups!, Checkerboard.jl:471-515, for any table in checkerboard order, and stays
-    // correct — only slower — for an arbitrary bond order)
-    h->h_bi.resize(nbonds); h->h_bj.resize(nbonds);
-    h->h_coloff.clear(); h->h_coloff.push_back(0);
-    {
-        std::vector<char> used(nsites, 0);
-        for (int64_t n = 0; n < nbonds; ++n) {
-            const int i = (int)(neighbor_table[2 * n] - 1), j = (int)(neighbor_table[2 * n + 1] - 1);
-            if (used[i] || used[j]) {
-                h->h_coloff.push_back((int)n);
-                std::fill(used.begin(), used.end(), 0);
-            }
-            used[i] = used[j] = 1;
-            h->h_bi[n] = i; h->h_bj[n] = j;
-        }
-        if (nbonds > 0) h->h_coloff.push_back((int)nbonds);
-    }
-    h->ncol = (int)h->h_coloff.size() - 1;
+    colour_bonds(h, neighbor_table);
 
     int rc = ELPH_OK;
     auto fail = [&](int code) { elph_destroy(h); return code; };
@@ -860,7 +862,7 @@ static bool split_wanted(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
     //  honeycomb 16 x 16 cells, eight sites per lane: 64 right-hand sides 64 -> 55 us, 256: 159 -> 145; D at 64: 89 -> 87)
     // (hopping disorder on 4 x 4 patches: the table variants of the patch kernels hold 40 KB of LDS per wavefront — two half-batches side by side lose to one
     //  stream: 32 x 32 at 96 right-hand sides 763 against 732 us, 28 x 28 695 against 663; profiles/r06/hopping_disorder_patch_kernels_with_tables.log)
-    if (!(e && e[0] == '1') && h->pg_L > 0 && h->pg_PX * h->pg_PY >= 16 && !h->pg_uniform && elph_pg_disorder_ok(h)) return false;
+    if (!(e && e[0] == '1') && h->shape.PX * h->shape.PY >= 16 && !h->kpm_hop_uniform && elph_pg_disorder_ok(h)) return false;
     return (e && e[0] == '1') || nrhs >= (h->npl >= 5 ? 64 : 192);
 }
 
@@ -1634,7 +1636,7 @@ static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b
                 RC(dev_alloc(&h->d_lp_cbar, (size_t)nch * h->lp_ne * ELPH_WAVE));
                 RC(dev_alloc(&h->d_lp_sbar, (size_t)nch * h->lp_ne * ELPH_WAVE));
             }
-            if (h->sq_L > 0) {
+            if (h->shape.sq_L() > 0) {
                 RC(dev_alloc(&h->d_sq_cbar, (size_t)nch * 4 * h->N));
                 RC(dev_alloc(&h->d_sq_sbar, (size_t)nch * 4 * h->N));
             }
@@ -1670,28 +1672,23 @@ static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b
         HIPCHK(hipMemcpy(h->d_lp_cbar, lc.data(), sizeof(double) * lc.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_lp_sbar, ls.data(), sizeof(double) * ls.size(), hipMemcpyHostToDevice));
     }
-    if (hop_fresh && h->sq_L > 0) {
+    if (hop_fresh && h->shape.sq_L() > 0) {
         const size_t per = (size_t)4 * h->N;
         std::vector<double> qc((size_t)hch * per), qs((size_t)hch * per);
         bool uni = true;
         for (int c = 0; c < hch; ++c) {
             double *q0 = qc.data() + (size_t)c * per, *q1 = qs.data() + (size_t)c * per;
-            for (size_t k = 0; k < per; ++k) { q0[k] = h->h_cbar[(size_t)c * h->nb + h->sq_bond[k]]; q1[k] = h->h_sbar[(size_t)c * h->nb + h->sq_bond[k]]; }
+            for (size_t k = 0; k < per; ++k) { q0[k] = h->h_cbar[(size_t)c * h->nb + h->shape.bond[k]]; q1[k] = h->h_sbar[(size_t)c * h->nb + h->shape.bond[k]]; }
             for (size_t k = 1; k < per; ++k) uni = uni && q0[k] == q0[0] && q1[k] == q1[0];       // uniform within the chain
         }
-        h->sq_uniform = uni;
+        h->sq_chain_uniform = uni;
         HIPCHK(hipMemcpy(h->d_sq_cbar, qc.data(), sizeof(double) * qc.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_sq_sbar, qs.data(), sizeof(double) * qs.size(), hipMemcpyHostToDevice));
     }
-    if (hop_fresh && h->hc_LX > 0) {
+    if (hop_fresh) {      // (read by the honeycomb and patch-layout forms only)
         bool uni = h->nb > 0 && !h->kpm_hop_per_chain;
         for (size_t k = 1; k < (size_t)h->nb && uni; ++k) uni = h->h_cbar[k] == h->h_cbar[0] && h->h_sbar[k] == h->h_sbar[0];
-        h->hc_uniform = uni;
-    }
-    if (hop_fresh && h->pg_L > 0) {
-        bool uni = h->nb > 0 && !h->kpm_hop_per_chain;
-        for (size_t k = 1; k < (size_t)h->nb && uni; ++k) uni = h->h_cbar[k] == h->h_cbar[0] && h->h_sbar[k] == h->h_sbar[0];
-        h->pg_uniform = uni;
+        h->kpm_hop_uniform = uni;
     }
     h->kpm_hop_uploaded = true;
     const int was_active = h->kpm_active;
@@ -2033,14 +2030,30 @@ extern "C" int elph_bench_px_info(elph_handle h, int *fused) {
 
 extern "C" int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, int *nw, int *tables) {
     CHECK_H(h);
-    if (kind) *kind = h->pg_L > 0 ? h->pg_kind : 0;
-    if (px) *px = h->pg_PX;
-    if (py) *py = h->pg_PY;
-    if (nw) *nw = h->pg_NW > 1 ? h->pg_NW : 1;
-    if (tables) {
-        ModelDev m = elph_model_dev(h);
-        *tables = (h->pg_L > 0 && h->kind == ELPH_MODEL_HOLSTEIN && !m.uniform && elph_pg_disorder_ok(h)) ? 1 : 0;
+    if (kind) *kind = h->shape.patch_kind();
+    if (px) *px = h->shape.PX;
+    if (py) *py = h->shape.PY;
+    if (nw) *nw = std::max(h->shape.NW, 1);
+    if (tables) *tables = (h->shape.patch() && h->kind == ELPH_MODEL_HOLSTEIN && !h->shape.hop_uniform && elph_pg_disorder_ok(h)) ? 1 : 0;
+    return ELPH_OK;
+}
+
+// what elph_create recognises in a bond table, on a host-only handle (no device): the slots of _lib.LATTICE_SHAPE_SLOTS
+extern "C" int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht,
+                                        const double *sinht, int *out) {
+    if (!out || (kind != ELPH_MODEL_HOLSTEIN && kind != ELPH_MODEL_SSH) || nsites < 1 || nsites > ELPH_MAX_SITES || nbonds < 0) {
+        elph_set_error("bad argument"); return ELPH_E_ARG;
     }
+    RC(check_bond_table(kind, nsites, nbonds, neighbor_table, cosht, sinht));
+    elph_handle_s h;
+    h.kind = kind; h.N = nsites; h.nb = nbonds;
+    colour_bonds(&h, neighbor_table);
+    if (kind == ELPH_MODEL_HOLSTEIN) { h.h_c.assign(cosht, cosht + nbonds); h.h_s.assign(sinht, sinht + nbonds); }
+    const LatticeShape sh = elph_recognise_lattice(&h);
+    const bool sq = sh.small_square(), hc = sh.honeycomb();
+    const int v[] = {sq ? sh.LX : 0, sq ? sh.LY : 0, sh.dpp(), hc ? sh.LX : 0, hc ? sh.LY : 0, sh.hc12(), sh.patch_kind(), sh.patch() ? sh.LX : 0, sh.PX, sh.PY,
+                     std::max(sh.NW, 1), sh.GX, sh.GY, sh.hgrid_regs(), sh.hop_uniform, sh.sq_L() > 0 ? 1 : sh.patch_kind() == LatticeShape::SQUARE ? 2 : 0};
+    std::copy(std::begin(v), std::end(v), out);
     return ELPH_OK;
 }
 

@@ -44,6 +44,14 @@ int elph_bench_px_info(elph_handle h, int *fused);
  * slice; *tables = 1 when the hopping is disordered and the mat-vec / Chebyshev kernels take the patch layout with a (cosh, sinh) table in LDS. */
 int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, int *nw, int *tables);
 
+/* What elph_create would recognise in this bond table (same table arguments; needs no device): out[16] = the small square lattice's LX, LY and its
+ * DPP size (1: 8 x 8, 2: 16 x 16, else 0); the honeycomb lattice's LX, LY (cells) and whether it is 12 x 12; the patch layout's kind (0 none,
+ * 1 square, 2 honeycomb, 3 triangular), side, PX, PY and wavefronts per slice (1 without one); the GRID layout's lanes GX, GY; the honeycomb grid
+ * form's registers per lane (2, 4, 8; 0); whether the model's hopping is one (cosh, sinh); the site -> bond map uploaded (0 none, 1 small square,
+ * 2 patch).  Reads ELPH_PG_MW as elph_create does. */
+int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht, const double *sinht,
+                             int *out);
+
 /* Whether an un-preconditioned solve of nrhs right-hand sides FROM x = 0 on this handle runs in the slab form (slabs.hip: lattices beyond
  * 320 sites as slabs of rows on the same device, the resident kernel per slab, one launch) and its shape. */
 int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int *sites_per_slab, int *own_sites);

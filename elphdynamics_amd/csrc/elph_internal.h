@@ -67,7 +67,7 @@ struct ModelDev {
     // a periodic square lattice of (2 grid_GX) x (2 grid_GY) sites in that colouring (square: GX = GY = L / 2; the slab of a sharded solve:
     // 16 x rows): the lane grid of the GRID layout (cg_fast_common.h); 0 otherwise
     int grid_GX, grid_GY;
-    // a periodic honeycomb lattice of hc_LX x hc_LY two-site cells in the reference's colouring (detect_honeycomb); 0 otherwise
+    // a periodic honeycomb lattice of hc_LX x hc_LY two-site cells in the reference's colouring (LatticeShape); 0 otherwise
     int hc_LX, hc_LY;
 };
 #ifdef __HIPCC__
@@ -203,6 +203,37 @@ __device__ __forceinline__ KpmChainView kpm_chain_view(const KpmDev &K, int rhs,
 }
 #endif
 
+// The lattice a handle's bond table holds, recognised once at elph_create by elph_recognise_lattice (elph_api.hip) in the reference's colouring
+// (host only).  Derived facts are accessors, not fields.
+struct LatticeShape {
+    enum Kind { NONE, SQUARE, HONEYCOMB, TRIANGULAR };     // (the values are the patch kinds of pgrid.hip)
+    Kind kind = NONE;
+    int LX = 0, LY = 0;            // periodic LX x LY sites (square, triangular) or two-site cells (honeycomb)
+    int PX = 0, PY = 0, NW = 0;    // patch layout (pgrid_dev.h): PX x PY sites / cells per lane on NW wavefronts per slice; 0: none
+    int GX = 0, GY = 0;            // GRID layout (cg_fast_common.h): a GX x GY grid of lanes holding 2 x 2 patches; 0: none
+    std::vector<int> bond;         // square lattices: [4][N] the bond that covers site i in colour col
+    bool hop_uniform = false;      // Holstein, and every bond of the model's table carries (hop_c, hop_s)
+    double hop_c = 1.0, hop_s = 0.0;
+
+    bool patch() const { return PX > 0; }
+    int patch_kind() const { return patch() ? (int)kind : 0; }
+    // a square lattice without patches: up to 16 x 16 sites, or a rectangle of at most 64 patches (a sharded solve's ring-closed slab)
+    bool small_square() const { return kind == SQUARE && !patch(); }
+    int sq_L() const { return small_square() && LX == LY ? LX : 0; }                        // ... when it is square
+    int dpp() const { return sq_L() == 8 ? 1 : sq_L() == 16 ? 2 : 0; }                      // 1: the 8 x 8, 2: the 16 x 16 DPP forms
+    bool honeycomb() const { return kind == HONEYCOMB; }
+    int hc_L() const { return honeycomb() && LX == LY ? LX : 0; }
+    bool hc12() const { return hc_L() == 12; }                                                // the honeycomb DPP / quad forms
+    // the honeycomb grid form: registers per lane (2, 4 or 8: 1, 2 x 1 or 2 x 2 cells) when the cells fit 64 lanes, else 0
+    int hgrid_regs() const {
+        if (!honeycomb()) return 0;
+        if (LX * LY <= 64) return 2;
+        if (LX % 2 == 0 && (LX / 2) * LY <= 64) return 4;
+        if (LX % 2 == 0 && LY % 2 == 0 && (LX / 2) * (LY / 2) <= 64) return 8;
+        return 0;
+    }
+};
+
 struct elph_handle_s {
     int kind = 0, device = 0;
     int64_t N = 0, L = 0, nb = 0, ndim = 0;
@@ -246,26 +277,13 @@ struct elph_handle_s {
     std::vector<unsigned> h_lp_ij;
     unsigned *d_lp_ij = nullptr;
     double *d_lp_c = nullptr, *d_lp_s = nullptr, *d_lp_cbar = nullptr, *d_lp_sbar = nullptr;
-    // even-L square lattice (L = 8 or 16) recognised in the bond table: P = L/8, per-site per-colour coefficients
-    int sq_P = 0;
-    int sq_L = 0;                          // even-L square lattice (4 <= L <= 16) recognised in the bond table: L (sq_P = L / 8 for L = 8, 16, the sizes with DPP forms)
-    int sq_LX = 0, sq_LY = 0;              // periodic LX x LY square lattice (both even, LX LY / 4 <= 64 lanes) recognised: sq_L = LX when LX == LY
-    bool sq_uniform = false;               // every bond has the same (cbar, sbar): the Chebyshev kernel keeps them in scalars
-    std::vector<int> sq_bond;              // [4][N] bond index touching site s in colour c
-    std::vector<int> pg_bond;              // ... of a square lattice in the patch layout (pg_kind 1)
-    bool hc_uniform = false;               // ... and its tau-averaged hopping tables are one (cosh, sinh) for every bond (the register-exchange Chebyshev recursion)
-    int pg_NW = 0;                         // wavefronts per time slice of the patch kernels (0 / 1: one; round 6: L = 22, 26, 34, 38 and 40 ... 64 take several)
-    int pg_L = 0, pg_PX = 0, pg_PY = 0;    // even-L square lattice beyond 16 x 16 in the reference's colouring (detect_square): PX x PY sites per lane (pgrid_dev.h)
-    int pg_kind = 0;                       // 1: that square lattice; 2: a honeycomb lattice beyond 16 x 16 cells, PX x PY CELLS per lane (detect_honeycomb);
-                                           // 3: an even-L triangular lattice of any size (detect_triangular)
-    bool pg_uniform_c = false;             // the model's own hopping table is uniform (known at elph_create; pg_uniform: the averaged one of the KPM set-up)
-    bool pg_uniform = false;               // ... and one (cbar, sbar) for every bond
-    int hc_L = 0;                          // honeycomb lattice of hc_L x hc_L cells in the reference's colouring (detect_honeycomb); hc12: hc_L == 12
-    int hc_LX = 0, hc_LY = 0;              // periodic honeycomb lattice of LX x LY cells recognised: hc_L = LX when LX == LY
-    bool hc12 = false;                     // honeycomb lattice of 12 x 12 cells in the reference's colouring (detect_honeycomb12): the DPP form of k_cg_wg
+    LatticeShape shape;                    // the lattice of the bond table (elph_create: elph_recognise_lattice)
+    bool sq_chain_uniform = false;         // kpm_setup_core, small square lattices: the tau-averaged hopping is one (cbar, sbar) WITHIN each chain
+                                           // (SSH chains may differ from one another): the register Chebyshev kernels keep them in scalars
+    bool kpm_hop_uniform = false;          // kpm_setup_core: the tau-averaged hopping tables are one (cbar, sbar) for every bond, shared by all chains
     double *d_sq_cbar = nullptr, *d_sq_sbar = nullptr;   // [4][N]
-    int *d_pg_bond = nullptr;                            // [4][N] the same for a square lattice in the patch layout (pg_kind 1): hopping disorder there
-    int *d_sq_bond = nullptr;                            // [4][N] device copy of sq_bond (sq_P > 0)
+    int *d_pg_bond = nullptr;                            // [4][N] shape.bond of a square lattice in the patch layout: hopping disorder there
+    int *d_sq_bond = nullptr;                            // [4][N] shape.bond of a small square lattice (shape.sq_L() > 0)
     void *shard = nullptr;                 // ShardState (shard.hip), owned
     void *slabs = nullptr;                 // SlabSet (slabs.hip), owned: slab handles of this lattice on the same device
     bool slabs_tried = false;              // the slab decomposition was attempted (slabs == nullptr: it does not apply)

@@ -993,15 +993,11 @@ ModelDev elph_model_dev(const elph_handle_s *h) {
     m.lp_tau_stride = (h->kind == ELPH_MODEL_SSH) ? h->lp_ne * ELPH_WAVE : 0;
     m.cs_chain_stride = m.lp_chain_stride = 0;
     m.uniform = 0; m.c_uni = 1.0; m.s_uni = 0.0;
-    m.sq_bond = (h->sq_L > 0) ? h->d_sq_bond : nullptr;
-    m.grid_GX = h->sq_LX / 2; m.grid_GY = h->sq_LY / 2;
-    if (h->pg_kind == 3 && h->pg_L <= 16) m.grid_GX = m.grid_GY = h->pg_L / 2;      // an even-L triangular lattice: the same grid of 2 x 2 patches (cg_wg.hip: FORM 7)
-    m.hc_LX = h->hc_LX; m.hc_LY = h->hc_LY;
-    if (h->kind == ELPH_MODEL_HOLSTEIN && h->nb > 0) {
-        bool uni = true;
-        for (int64_t n = 1; n < h->nb && uni; ++n) uni = (h->h_c[(size_t)n] == h->h_c[0] && h->h_s[(size_t)n] == h->h_s[0]);
-        if (uni) { m.uniform = 1; m.c_uni = h->h_c[0]; m.s_uni = h->h_s[0]; }
-    }
+    const LatticeShape &sh = h->shape;
+    m.sq_bond = (sh.sq_L() > 0) ? h->d_sq_bond : nullptr;
+    m.grid_GX = sh.GX; m.grid_GY = sh.GY;
+    m.hc_LX = sh.honeycomb() ? sh.LX : 0; m.hc_LY = sh.honeycomb() ? sh.LY : 0;
+    if (sh.hop_uniform) { m.uniform = 1; m.c_uni = sh.hop_c; m.s_uni = sh.hop_s; }
     if (h->kind == ELPH_MODEL_SSH && h->nchains > 1) {
         const long long cs = (long long)h->L * h->nb, lp = (long long)h->L * h->lp_ne * ELPH_WAVE;
         if (h->solo_chain >= 0) {
@@ -1195,7 +1191,7 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
     // p/x-fused (PxFuse, dft_mfma.hip): residual update folded into the forward transform, r.z from the Chebyshev kernel in frequency space
     // (so that beta is known BEFORE the inverse transform), streaming MFMA inverse with the p/x-update in its epilogue
     if (prec && h->kpm_ready && h->kpm_active && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs)) {
-        if (!h->fast && hol && (h->pg_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && pg_cheb) {
+        if (!h->fast && hol && (h->kpm_hop_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && pg_cheb) {
             // (round 6) the patch-form lattices of the generic family: k_cg_ap_pg + k_kpm_cheb_pg (pgrid.hip)
             c.px = pg_px_ok && rz2;
         } else if (!h->fast) {
@@ -1205,7 +1201,7 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
         } else if (h->lp_mc != 4) {
             // six-colour lane programs (triangular lattices up to 16 x 16: the geometry of holstein_hmc_triangular.toml) have no fused chunk kernel of
             // their own: their p/x-fused iteration takes the patch-form pair k_cg_ap_pg<PX> + k_kpm_cheb_pg (pgrid::Tri<2, 2>) — round 6
-            c.px = pg_px_ok && hol && h->pg_L > 0 && h->pg_uniform && pg_cheb && rz2;
+            c.px = pg_px_ok && hol && h->shape.patch() && h->kpm_hop_uniform && pg_cheb && rz2;
         } else {
             // the four-colour lane programs: r.z in frequency space comes from a register-exchange Chebyshev kernel — or, round 6, from the
             // patch-form one (square L = 18, 20 of this family) or from the Re / Im recursion through the LDS slab (k_kpm_cheb_ri: square L = 22,
@@ -1224,7 +1220,7 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
         c.ap = !c.px ? CgPlan::AP_LANE : h->lp_mc != 4 ? CgPlan::AP_PG : sq16 ? CgPlan::AP_SQ16 : CgPlan::AP_LANE;
     } else {
         // a large even-L square lattice: the patch-layout kernel (pgrid.hip)
-        c.ap = (elph_pg_ap_usable(h) && (elph_model_dev(h).uniform || elph_pg_disorder_ok(h))) ? CgPlan::AP_PG : CgPlan::AP_GEN;
+        c.ap = (elph_pg_ap_usable(h) && (h->shape.hop_uniform || elph_pg_disorder_ok(h))) ? CgPlan::AP_PG : CgPlan::AP_GEN;
     }
     c.xr_in_fwd = c.px || (h->fast && h->kpm_active && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs));
     c.rz_freq = dot_all && (c.cheb == CgPlan::CH_LANE ? rz2 : c.cheb == CgPlan::CH_PG ? c.px && rz2 : c.px && Lo2 <= nrz);

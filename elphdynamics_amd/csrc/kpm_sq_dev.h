@@ -68,7 +68,7 @@ __device__ __forceinline__ void sq16_cb_apply(double (&v)[4], const SqLane<2> &T
 #undef SQS
 
 // The honeycomb lattice of 12 x 12 cells (config D) in the reference's colouring [A-B of a cell | B(x,y)-A(x+1,y) | B(x,y)-A(x,y+1)]
-// (detect_honeycomb12), QUAD layout of the Chebyshev recursion: lane 4 y + i (48 of the 64 lanes) holds the three cells x = 3 i + b of
+// (elph_recognise_lattice), QUAD layout of the Chebyshev recursion: lane 4 y + i (48 of the 64 lanes) holds the three cells x = 3 i + b of
 // lattice row y — six sites, register 2 b + orbital.  12 = 3 cells in a lane x 4 lanes of a DPP quad, so the x-direction wraps where
 // quad_perm wraps: A-B pairs registers (0,1), (2,3), (4,5); B(x,y)-A(x+1,y) pairs (1,2), (3,4) of the lane and sends register 5 to
 // register 0 of the next lane of the quad (two DPP moves of an f64); B(x,y)-A(x,y+1) crosses to the lane 4 up / 4 down, cyclically

@@ -540,7 +540,7 @@ static bool pcg_shape(const elph_handle_s *h, int nrhs, int *Wo, int *Go, int *n
     const char *eo = getenv("ELPH_PCG_WG");
     if (eo && eo[0] == '0') return false;
     if (!(eo && eo[0] == '1') && nrhs < 6) return false;
-    if (!h->fast || h->kind != ELPH_MODEL_HOLSTEIN || h->sq_P != 2 || h->N != 256 || !h->sq_uniform || h->lp_mc != 4) return false;
+    if (!h->fast || h->kind != ELPH_MODEL_HOLSTEIN || h->shape.dpp() != 2 || !h->sq_chain_uniform || h->lp_mc != 4) return false;
     if (!h->kpm_ready || !h->kpm_active || h->dot_hi != 0 || h->solo_chain >= 0) return false;
     // (h->kpm_active says that SOME chain's expansion is active; the kernel runs the series of every right-hand side's chain without
     //  looking at KpmChainView::active, so a chain whose expansion is the identity — lam_mag uploaded as -1, tables unset — keeps the

@@ -485,6 +485,51 @@ int pg_check(const char *what) {
 
 }   // namespace
 
+// The patch-kernel instantiation of (kind, px, py, nw): calls launch(Tag<LAT>{}) for the matching alias.  tables: hopping disorder — the table
+// variants, chosen by nw / px / py alone (elph_pg_disorder_ok has checked the shape).  The three launchers below share this one ladder.
+template <class LAT> struct Tag { using type = LAT; };
+template <class F>
+static int pg_dispatch(int kind, int px, int py, int nw, bool tables, F &&launch) {
+    if (tables) {
+        if (nw == 2) launch(Tag<M22_2D>{});
+        else if (nw == 3) launch(Tag<M22_3D>{});
+        else if (nw == 4) launch(Tag<M22_4D>{});
+        else if (nw == 5) launch(Tag<M22_5D>{});
+        else if (px == 4) launch(Tag<SQ44D>{});
+        else if (py == 6) launch(Tag<SQ26D>{});
+        else launch(Tag<SQ24D>{});
+    }
+    else if (kind == 1 && px == 2 && py == 2 && nw == 2) launch(Tag<M22_2>{});
+    else if (kind == 1 && px == 2 && py == 2 && nw == 3) launch(Tag<M22_3>{});
+    else if (kind == 1 && px == 2 && py == 2 && nw == 4) launch(Tag<M22_4>{});
+    else if (kind == 1 && px == 2 && py == 2 && nw == 5) launch(Tag<M22_5>{});
+    else if (kind == 1 && px == 2 && py == 2 && nw == 6) launch(Tag<M22_6>{});
+    else if (kind == 1 && px == 4 && py == 4 && nw == 2) launch(Tag<M44_2>{});
+    else if (kind == 1 && px == 4 && py == 4 && nw == 3) launch(Tag<M44_3>{});
+    else if (kind == 1 && px == 4 && py == 4 && nw == 4) launch(Tag<M44_4>{});
+    else if (kind == 2 && px == 3 && nw == 2) launch(Tag<H33_2>{});
+    else if (kind == 2 && px == 3 && nw == 3) launch(Tag<H33_3>{});
+    else if (kind == 2 && px == 3 && nw == 4) launch(Tag<H33_4>{});
+    else if (kind == 2 && px == 2 && nw == 2) launch(Tag<H22_2>{});
+    else if (kind == 2 && px == 2 && nw == 3) launch(Tag<H22_3>{});
+    else if (kind == 2 && px == 2 && nw == 4) launch(Tag<H22_4>{});
+    else if (kind != 3 && nw > 1) { elph_set_error("patch kernels: no instantiation for kind %d, %d x %d patches on %d wavefronts", kind, px, py, nw); return ELPH_E_UNSUPPORTED; }
+    else if (kind == 1 && px == 4 && py == 4) launch(Tag<SQ44>{});
+    else if (kind == 1 && px == 2 && py == 6) launch(Tag<SQ26>{});
+    else if (kind == 1 && px == 2 && py == 4) launch(Tag<SQ24>{});
+    else if (kind == 1 && px == 2 && py == 10) launch(Tag<SQ2A>{});
+    else if (kind == 1 && px == 4 && py == 6) launch(Tag<SQ46>{});
+    else if (kind == 2 && px == 3 && py == 2) launch(Tag<HC32>{});
+    else if (kind == 2 && px == 4 && py == 2) launch(Tag<HC42>{});
+    else if (kind == 2 && px == 3 && py == 3) launch(Tag<HC33>{});
+    else if (kind == 3 && px == 2 && py == 2) launch(Tag<TR22>{});
+    else if (kind == 3 && px == 2 && py == 4) launch(Tag<TR24>{});
+    else if (kind == 3 && px == 2 && py == 6) launch(Tag<TR26>{});
+    else if (kind == 3 && px == 4 && py == 4) launch(Tag<TR44>{});
+    else { elph_set_error("patch kernels: no instantiation for kind %d, %d x %d patches", kind, px, py); return ELPH_E_UNSUPPORTED; }
+    return ELPH_OK;
+}
+
 // The patch shape of ONE launch.  The memory layout of a vector does not depend on it (a shape only says which thread holds which sites), so a launch may
 // take another shape than the handle's: 4 x 4 patches on one wavefront (28 x 28, 32 x 32) have the fewest instructions per site and the shortest
 // dependent chain — one right-hand side: 89 us per preconditioned iteration against 96 as 2 x 2 patches on four wavefronts — but hold ONE wave per
@@ -499,18 +544,20 @@ bool elph_pg_mw() {
     return !(e && e[0] == '0');
 }
 static void pg_launch_shape(const elph_handle_s *h, int nrhs, bool big, int *px, int *py, int *nw) {
-    *px = h->pg_PX; *py = h->pg_PY; *nw = h->pg_NW > 1 ? h->pg_NW : 1;
+    const LatticeShape &s = h->shape;
+    *px = s.PX; *py = s.PY; *nw = std::max(s.NW, 1);
     if (!big || *nw != 1) return;
     const char *e = getenv("ELPH_PG_2X2_FROM");
     const int from = e ? atoi(e) : 48;
     if (from <= 0 || nrhs < from || !elph_pg_mw()) return;
-    if (h->pg_kind == 1 && *px * *py >= 16 && ((h->pg_L / 2) * (h->pg_L / 2) + 63) / 64 <= 6 && h->pg_uniform_c) {      // 4 x 4 (28, 32), 2 x 10 (30: 96 right-hand sides on two streams 477 -> 415 us), 4 x 6 (36: 472 -> 459 at 64)
-        *px = 2; *py = 2; *nw = ((h->pg_L / 2) * (h->pg_L / 2) + 63) / 64;      // 28: 196 threads, 32: 256 — four wavefronts; 30: 225 — four; 36: 324 — six
-    } else if (h->pg_kind == 2 && *px == 4 && *py == 2) {
+    const int nw2 = ((s.LX / 2) * (s.LX / 2) + 63) / 64;      // wavefronts of 2 x 2 patches
+    if (s.patch_kind() == LatticeShape::SQUARE && *px * *py >= 16 && nw2 <= 6 && s.hop_uniform) {      // 4 x 4 (28, 32), 2 x 10 (30: 96 right-hand sides on two streams 477 -> 415 us), 4 x 6 (36: 472 -> 459 at 64)
+        *px = 2; *py = 2; *nw = nw2;      // 28: 196 threads, 32: 256 — four wavefronts; 30: 225 — four; 36: 324 — six
+    } else if (s.patch_kind() == LatticeShape::HONEYCOMB && *px == 4 && *py == 2) {
         // honeycomb 20 x 20 cells (4 x 2 cells per lane: the other 16-register shape) as 2 x 2 cells on two wavefronts: 96 right-hand sides 315 -> 292 us per
         // iteration, on two streams 295 -> 247; 18 x 18 (3 x 2 cells) is indifferent, 24 x 24 (3 x 3) LOSES as 2 x 2 cells on three (538 -> 590 at 128) and
         // keeps its shape (profiles/r06/patch_shape_by_batch_size.log)
-        *px = 2; *py = 2; *nw = ((h->pg_L / 2) * (h->pg_L / 2) + 63) / 64;
+        *px = 2; *py = 2; *nw = nw2;
     }
 }
 
@@ -522,7 +569,7 @@ static bool no_pg() {
 
 // Can the per-frequency recursion of this handle run in the patch layout?
 bool elph_pg_cheb_usable(const elph_handle_s *h) {
-    return h->pg_L > 0 && (h->pg_uniform || elph_pg_disorder_ok(h)) && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
+    return h->shape.patch() && (h->kpm_hop_uniform || elph_pg_disorder_ok(h)) && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
 }
 
 // hopping disorder on this handle's patch shape (square lattices whose (cosh, sinh) table fits the LDS: pgrid::patch_takes_disorder; ELPH_PG_DIS=0:
@@ -531,69 +578,33 @@ bool elph_pg_disorder_ok(const elph_handle_s *h) {
     const char *e = getenv("ELPH_PG_DIS");
     // (measured, profiles/r06/hopping_disorder_patch_kernels_with_tables.log: 18 x 18 — lane-program mat-vec, only the recursion would move — loses to
     //  the Re / Im recursion through the LDS slab, 214 -> 252 us at 96 right-hand sides; 20 x 20 and 22 x 22, the same family, gain: 241 -> 195, 313 -> 266)
-    if (h->fast && h->pg_L == 18) return false;
-    return h->pg_L > 0 && h->pg_kind == 1 && h->d_pg_bond && pgrid::patch_takes_disorder(h->pg_PX, h->pg_PY, h->pg_NW > 1 ? h->pg_NW : 1) && !(e && e[0] == '0');
+    const LatticeShape &s = h->shape;
+    if (h->fast && s.patch() && s.LX == 18) return false;
+    return s.patch_kind() == LatticeShape::SQUARE && h->d_pg_bond && pgrid::patch_takes_disorder(s.PX, s.PY, s.NW) && !(e && e[0] == '0');
 }
 
 // nu (d_nu: [nrhs][Lo2][N] complex) <- P^-1 in frequency space, every (right-hand side, frequency) a block of two wavefronts
 int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, const double *rr_part) {
     KpmDev K = elph_kpm_dev(h);
-    const int Lo2 = (int)((h->L + 1) / 2), N = (int)h->N, Ls = h->pg_L;
+    const int Lo2 = (int)((h->L + 1) / 2), N = (int)h->N, Ls = h->shape.LX;
     if (rz_part && 2 * Lo2 > nrz) { elph_set_error("k_kpm_cheb_pg: %d r.z slots needed, %d available", 2 * Lo2, nrz); return ELPH_E_STATE; }
     const dim3 grid((unsigned)nrhs, (unsigned)Lo2);
-#define PG_CHEB(LAT) hipLaunchKernelGGL((k_kpm_cheb_pg<LAT>), grid, dim3(2 * LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, h->d_nu, K, N, Ls, Lo2, st, rz_part, nrz, (int)h->L, rr_part, h->d_pg_bond)
     int px, py, nw;
     pg_launch_shape(h, nrhs, true, &px, &py, &nw);
-    if (!h->pg_uniform) {        // hopping disorder: the table variants (elph_pg_cheb_usable has checked the shape)
-        if (!elph_pg_disorder_ok(h)) { elph_set_error("k_kpm_cheb_pg: hopping disorder on a patch shape without a table variant"); return ELPH_E_UNSUPPORTED; }
-        if (nw == 2) PG_CHEB(M22_2D);
-        else if (nw == 3) PG_CHEB(M22_3D);
-        else if (nw == 4) PG_CHEB(M22_4D);
-        else if (nw == 5) PG_CHEB(M22_5D);
-        else if (px == 4) PG_CHEB(SQ44D);
-        else if (py == 6) PG_CHEB(SQ26D);
-        else PG_CHEB(SQ24D);
-    }
-    else if (h->pg_kind == 1 && nw > 1) {
-        if (px == 2 && py == 2 && nw == 2) PG_CHEB(M22_2);
-        else if (px == 2 && py == 2 && nw == 3) PG_CHEB(M22_3);
-        else if (px == 2 && py == 2 && nw == 4) PG_CHEB(M22_4);
-        else if (px == 2 && py == 2 && nw == 5) PG_CHEB(M22_5);
-        else if (px == 2 && py == 2 && nw == 6) PG_CHEB(M22_6);
-        else if (px == 4 && py == 4 && nw == 2) PG_CHEB(M44_2);
-        else if (px == 4 && py == 4 && nw == 3) PG_CHEB(M44_3);
-        else if (px == 4 && py == 4 && nw == 4) PG_CHEB(M44_4);
-        else { elph_set_error("patch kernels: no instantiation for %d x %d patches on %d wavefronts", px, py, nw); return ELPH_E_UNSUPPORTED; }
-    }
-    else if (h->pg_kind == 2 && nw > 1) {
-        if (px == 3 && nw == 2) PG_CHEB(H33_2);
-        else if (px == 3 && nw == 3) PG_CHEB(H33_3);
-        else if (px == 3 && nw == 4) PG_CHEB(H33_4);
-        else if (px == 2 && nw == 2) PG_CHEB(H22_2);
-        else if (px == 2 && nw == 3) PG_CHEB(H22_3);
-        else if (px == 2 && nw == 4) PG_CHEB(H22_4);
-        else { elph_set_error("patch kernels: no honeycomb instantiation for %d x %d cells on %d wavefronts", px, py, nw); return ELPH_E_UNSUPPORTED; }
-    }
-    else if (h->pg_kind == 1 && px == 4 && py == 4) PG_CHEB(SQ44);
-    else if (h->pg_kind == 1 && px == 2 && py == 6) PG_CHEB(SQ26);
-    else if (h->pg_kind == 1 && px == 2 && py == 4) PG_CHEB(SQ24);
-    else if (h->pg_kind == 1 && px == 2 && py == 10) PG_CHEB(SQ2A);
-    else if (h->pg_kind == 1 && px == 4 && py == 6) PG_CHEB(SQ46);
-    else if (h->pg_kind == 2 && px == 3 && py == 2) PG_CHEB(HC32);
-    else if (h->pg_kind == 2 && px == 4 && py == 2) PG_CHEB(HC42);
-    else if (h->pg_kind == 2 && px == 3 && py == 3) PG_CHEB(HC33);
-    else if (h->pg_kind == 3 && px == 2 && py == 2) PG_CHEB(TR22);
-    else if (h->pg_kind == 3 && px == 2 && py == 4) PG_CHEB(TR24);
-    else if (h->pg_kind == 3 && px == 2 && py == 6) PG_CHEB(TR26);
-    else if (h->pg_kind == 3 && px == 4 && py == 4) PG_CHEB(TR44);
-    else { elph_set_error("k_kpm_cheb_pg: no instantiation for kind %d, %d x %d patches", h->pg_kind, px, py); return ELPH_E_UNSUPPORTED; }
-#undef PG_CHEB
+    // hopping disorder: the table variants (elph_pg_cheb_usable has checked the shape)
+    if (!h->kpm_hop_uniform && !elph_pg_disorder_ok(h)) { elph_set_error("k_kpm_cheb_pg: hopping disorder on a patch shape without a table variant"); return ELPH_E_UNSUPPORTED; }
+    const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !h->kpm_hop_uniform, [&](auto tag) {
+        using LAT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((k_kpm_cheb_pg<LAT>), grid, dim3(2 * LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, h->d_nu, K, N, Ls, Lo2, st, rz_part, nrz,
+                           (int)h->L, rr_part, h->d_pg_bond);
+    });
+    if (rc) return rc;
     return pg_check("k_kpm_cheb_pg");
 }
 
 // the mat-vec kernel of the CG iteration in the patch layout (generic family only: the lane-program family has its own chunked kernel)
 bool elph_pg_ap_usable(const elph_handle_s *h) {
-    return h->pg_L > 0 && !h->fast && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
+    return h->shape.patch() && !h->fast && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
 }
 
 int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs, int parity, bool fused) {
@@ -606,61 +617,19 @@ int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs
     const int L = (int)h->L;
     int px, py, nw;
     pg_launch_shape(h, nrhs, fused, &px, &py, &nw);
-    const long long slots = 1024LL * ((h->pg_kind != 2 && px * py <= 8) ? 2 : 1) / nw;      // (a slice of several wavefronts holds as many slots)
+    const long long slots = 1024LL * ((!h->shape.honeycomb() && px * py <= 8) ? 2 : 1) / nw;      // (a slice of several wavefronts holds as many slots)
     int T = 20;
     for (int c : {1, 2, 4, 5, 8, 10, 16, 20, 32, 40}) { if ((long long)nrhs * ((L + c - 1) / c) <= slots) { T = c; break; } }
     T = std::max(1, std::min(T, L));
     const int nch = (L + T - 1) / T;
     const dim3 grid((unsigned)(nrhs * nch));
-    const int Ls = h->pg_L;
-#define PG_AP(LAT)                                                                                                        \
-    do {                                                                                                                  \
-        if (fused) hipLaunchKernelGGL((k_cg_ap_pg<LAT, true>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, B, m, parity, Ls, T, h->d_pg_bond);              \
-        else hipLaunchKernelGGL((k_cg_ap_pg<LAT, false>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, B, m, parity, Ls, T, h->d_pg_bond);                \
-    } while (0)
-    if (!m.uniform) {
-        if (nw == 2) PG_AP(M22_2D);
-        else if (nw == 3) PG_AP(M22_3D);
-        else if (nw == 4) PG_AP(M22_4D);
-        else if (nw == 5) PG_AP(M22_5D);
-        else if (px == 4) PG_AP(SQ44D);
-        else if (py == 6) PG_AP(SQ26D);
-        else PG_AP(SQ24D);
-    }
-    else if (h->pg_kind == 1 && nw > 1) {
-        if (px == 2 && py == 2 && nw == 2) PG_AP(M22_2);
-        else if (px == 2 && py == 2 && nw == 3) PG_AP(M22_3);
-        else if (px == 2 && py == 2 && nw == 4) PG_AP(M22_4);
-        else if (px == 2 && py == 2 && nw == 5) PG_AP(M22_5);
-        else if (px == 2 && py == 2 && nw == 6) PG_AP(M22_6);
-        else if (px == 4 && py == 4 && nw == 2) PG_AP(M44_2);
-        else if (px == 4 && py == 4 && nw == 3) PG_AP(M44_3);
-        else if (px == 4 && py == 4 && nw == 4) PG_AP(M44_4);
-        else { elph_set_error("patch kernels: no instantiation for %d x %d patches on %d wavefronts", px, py, nw); return ELPH_E_UNSUPPORTED; }
-    }
-    else if (h->pg_kind == 2 && nw > 1) {
-        if (px == 3 && nw == 2) PG_AP(H33_2);
-        else if (px == 3 && nw == 3) PG_AP(H33_3);
-        else if (px == 3 && nw == 4) PG_AP(H33_4);
-        else if (px == 2 && nw == 2) PG_AP(H22_2);
-        else if (px == 2 && nw == 3) PG_AP(H22_3);
-        else if (px == 2 && nw == 4) PG_AP(H22_4);
-        else { elph_set_error("patch kernels: no honeycomb instantiation for %d x %d cells on %d wavefronts", px, py, nw); return ELPH_E_UNSUPPORTED; }
-    }
-    else if (h->pg_kind == 1 && px == 4 && py == 4) PG_AP(SQ44);
-    else if (h->pg_kind == 1 && px == 2 && py == 6) PG_AP(SQ26);
-    else if (h->pg_kind == 1 && px == 2 && py == 4) PG_AP(SQ24);
-    else if (h->pg_kind == 1 && px == 2 && py == 10) PG_AP(SQ2A);
-    else if (h->pg_kind == 1 && px == 4 && py == 6) PG_AP(SQ46);
-    else if (h->pg_kind == 2 && px == 3 && py == 2) PG_AP(HC32);
-    else if (h->pg_kind == 2 && px == 4 && py == 2) PG_AP(HC42);
-    else if (h->pg_kind == 2 && px == 3 && py == 3) PG_AP(HC33);
-    else if (h->pg_kind == 3 && px == 2 && py == 2) PG_AP(TR22);
-    else if (h->pg_kind == 3 && px == 2 && py == 4) PG_AP(TR24);
-    else if (h->pg_kind == 3 && px == 2 && py == 6) PG_AP(TR26);
-    else if (h->pg_kind == 3 && px == 4 && py == 4) PG_AP(TR44);
-    else { elph_set_error("k_cg_ap_pg: no instantiation for kind %d, %d x %d patches", h->pg_kind, px, py); return ELPH_E_UNSUPPORTED; }
-#undef PG_AP
+    const int Ls = h->shape.LX;
+    const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !m.uniform, [&](auto tag) {
+        using LAT = typename decltype(tag)::type;
+        if (fused) hipLaunchKernelGGL((k_cg_ap_pg<LAT, true>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, B, m, parity, Ls, T, h->d_pg_bond);
+        else hipLaunchKernelGGL((k_cg_ap_pg<LAT, false>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, B, m, parity, Ls, T, h->d_pg_bond);
+    });
+    if (rc) return rc;
     return pg_check("k_cg_ap_pg");
 }
 
@@ -669,61 +638,19 @@ bool elph_pg_mul_usable(const elph_handle_s *h) { return elph_pg_ap_usable(h); }
 
 int elph_pg_mul(elph_handle_s *h, const ModelDev &m, int which, double *yS, const double *vS, int nvec) {
     if (!m.uniform && !elph_pg_disorder_ok(h)) return ELPH_E_UNSUPPORTED;
-    const int L = (int)h->L, Ls = h->pg_L;
+    const int L = (int)h->L, Ls = h->shape.LX;
     int T = 20;
     for (int c : {1, 2, 4, 5, 8, 10, 16, 20}) { if ((long long)nvec * ((L + c - 1) / c) <= 2048) { T = c; break; } }
     T = std::max(1, std::min(T, L));
     const dim3 grid((unsigned)(nvec * ((L + T - 1) / T)));
-#define PG_MUL(LAT)                                                                                                       \
-    do {                                                                                                                  \
-        if (which == 0) hipLaunchKernelGGL((k_mul_pg<LAT, 0>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);              \
-        else if (which == 1) hipLaunchKernelGGL((k_mul_pg<LAT, 1>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);         \
-        else hipLaunchKernelGGL((k_mul_pg<LAT, 2>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);                         \
-    } while (0)
     int px, py, nw;
     pg_launch_shape(h, nvec, false, &px, &py, &nw);
-    if (!m.uniform) {
-        if (nw == 2) PG_MUL(M22_2D);
-        else if (nw == 3) PG_MUL(M22_3D);
-        else if (nw == 4) PG_MUL(M22_4D);
-        else if (nw == 5) PG_MUL(M22_5D);
-        else if (px == 4) PG_MUL(SQ44D);
-        else if (py == 6) PG_MUL(SQ26D);
-        else PG_MUL(SQ24D);
-    }
-    else if (h->pg_kind == 1 && nw > 1) {
-        if (px == 2 && py == 2 && nw == 2) PG_MUL(M22_2);
-        else if (px == 2 && py == 2 && nw == 3) PG_MUL(M22_3);
-        else if (px == 2 && py == 2 && nw == 4) PG_MUL(M22_4);
-        else if (px == 2 && py == 2 && nw == 5) PG_MUL(M22_5);
-        else if (px == 2 && py == 2 && nw == 6) PG_MUL(M22_6);
-        else if (px == 4 && py == 4 && nw == 2) PG_MUL(M44_2);
-        else if (px == 4 && py == 4 && nw == 3) PG_MUL(M44_3);
-        else if (px == 4 && py == 4 && nw == 4) PG_MUL(M44_4);
-        else { elph_set_error("patch kernels: no instantiation for %d x %d patches on %d wavefronts", px, py, nw); return ELPH_E_UNSUPPORTED; }
-    }
-    else if (h->pg_kind == 2 && nw > 1) {
-        if (px == 3 && nw == 2) PG_MUL(H33_2);
-        else if (px == 3 && nw == 3) PG_MUL(H33_3);
-        else if (px == 3 && nw == 4) PG_MUL(H33_4);
-        else if (px == 2 && nw == 2) PG_MUL(H22_2);
-        else if (px == 2 && nw == 3) PG_MUL(H22_3);
-        else if (px == 2 && nw == 4) PG_MUL(H22_4);
-        else { elph_set_error("patch kernels: no honeycomb instantiation for %d x %d cells on %d wavefronts", px, py, nw); return ELPH_E_UNSUPPORTED; }
-    }
-    else if (h->pg_kind == 1 && px == 4 && py == 4) PG_MUL(SQ44);
-    else if (h->pg_kind == 1 && px == 2 && py == 6) PG_MUL(SQ26);
-    else if (h->pg_kind == 1 && px == 2 && py == 4) PG_MUL(SQ24);
-    else if (h->pg_kind == 1 && px == 2 && py == 10) PG_MUL(SQ2A);
-    else if (h->pg_kind == 1 && px == 4 && py == 6) PG_MUL(SQ46);
-    else if (h->pg_kind == 2 && px == 3 && py == 2) PG_MUL(HC32);
-    else if (h->pg_kind == 2 && px == 4 && py == 2) PG_MUL(HC42);
-    else if (h->pg_kind == 2 && px == 3 && py == 3) PG_MUL(HC33);
-    else if (h->pg_kind == 3 && px == 2 && py == 2) PG_MUL(TR22);
-    else if (h->pg_kind == 3 && px == 2 && py == 4) PG_MUL(TR24);
-    else if (h->pg_kind == 3 && px == 2 && py == 6) PG_MUL(TR26);
-    else if (h->pg_kind == 3 && px == 4 && py == 4) PG_MUL(TR44);
-    else { elph_set_error("k_mul_pg: no instantiation for kind %d, %d x %d patches", h->pg_kind, px, py); return ELPH_E_UNSUPPORTED; }
-#undef PG_MUL
+    const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !m.uniform, [&](auto tag) {
+        using LAT = typename decltype(tag)::type;
+        if (which == 0) hipLaunchKernelGGL((k_mul_pg<LAT, 0>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);
+        else if (which == 1) hipLaunchKernelGGL((k_mul_pg<LAT, 1>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);
+        else hipLaunchKernelGGL((k_mul_pg<LAT, 2>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);
+    });
+    if (rc) return rc;
     return pg_check("k_mul_pg");
 }
