@@ -129,6 +129,8 @@ BENCH_SIGNATURES = {
     "elph_bench_pg_info": (c_int, [Handle, P_int, P_int, P_int, P_int, P_int]),
     "elph_bench_slabs_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_lattice_shape": (c_int, [c_int, c_i64, c_i64, P_i64, P_dbl, P_dbl, P_int]),
+    "elph_bench_kpm_plan": (c_int, [c_i64, c_dbl, c_dbl, c_dbl, c_int, c_int, P_dbl, P_int, P_int, P_dbl, P_int, P_int, P_int, P_dbl,
+                                    P_dbl, P_dbl, c_i64, P_i64]),
 }
 
 # the slots of elph_bench_lattice_shape's vector, in order (elph_bench.h)
@@ -146,6 +148,29 @@ def lattice_shape(kind, nsites, table, cosht=None, sinht=None):
     check(lib.elph_bench_lattice_shape(int(kind), int(nsites), table.shape[0], iptr(table) if table.size else None,
                                        None if c is None else dptr(c), None if s is None else dptr(s), out))
     return dict(zip(LATTICE_SHAPE_SLOTS, list(out)))
+
+
+def kpm_plan(ltau, bounds, buf=0.05, c1=1.0, c2=1.0):
+    """What setup!(P) plans at Ltau = ltau for successive steps of per-chain eigenvalue bounds, bounds[step][chain] = (e_min, e_max).  Needs no
+    device.  Returns {"uploaded": [steps], and after the last step "active": [nch], "lam_lo", "lam_hi", "lam_avg", "lam_mag": [nch], "order",
+    "wsched": [nch, Lo2], "coff": [nch, Lo2 + 1], "c0": [nch, Lo2] complex (schedule order), "fold": [nch, Lo2, 2], "coeff": complex}."""
+    lib = load()
+    eb = np.ascontiguousarray(bounds, dtype=np.float64)
+    nsteps, nch = eb.shape[0], eb.shape[1]
+    Lo2 = (int(ltau) + 1) // 2
+    up, act = np.zeros(nsteps, dtype=np.int32), np.zeros(nch, dtype=np.int32)
+    lam, order, wsched = np.zeros((nch, 4)), np.zeros((nch, Lo2), dtype=np.int32), np.zeros((nch, Lo2), dtype=np.int32)
+    coff, c0, fold = np.zeros((nch, Lo2 + 1), dtype=np.int32), np.zeros((nch, Lo2, 2)), np.zeros((nch, Lo2, 2))
+    n = C.c_int64()
+    ip32 = lambda a: a.ctypes.data_as(P_int)  # noqa: E731
+    args = [int(ltau), float(buf), float(c1), float(c2), nch, nsteps, dptr(eb), ip32(up), ip32(act), dptr(lam), ip32(order), ip32(coff),
+            ip32(wsched), dptr(c0), dptr(fold)]
+    check(lib.elph_bench_kpm_plan(*args, None, 0, C.byref(n)))
+    coeff = np.zeros(n.value)
+    check(lib.elph_bench_kpm_plan(*args, dptr(coeff), n.value, C.byref(n)))
+    return dict(uploaded=up.astype(bool).tolist(), active=act.astype(bool).tolist(), lam_lo=lam[:, 0], lam_hi=lam[:, 1], lam_avg=lam[:, 2],
+                lam_mag=lam[:, 3], order=order, wsched=wsched, coff=coff, c0=c0[..., 0] + 1j * c0[..., 1], fold=fold,
+                coeff=coeff[0::2] + 1j * coeff[1::2])
 
 
 class ElphError(RuntimeError):

@@ -58,14 +58,14 @@ int elph_reg_cheb_form(const elph_handle_s *h, int *hgn) {
     const LatticeShape &s = h->shape;
     if (s.dpp() > 0) return REG_SQ;
     // any other even-L square lattice (L = 4, 6, 10, 12, 14) with one (cosh, sinh) for every bond: the GRID layout
-    if (s.sq_L() > 0 && h->sq_chain_uniform && hol) return REG_SQ_GRID;
-    if (s.hc_L() > 0 && !s.hc12() && h->kpm_hop_uniform && hol && s.hgrid_regs()) {
+    if (s.sq_L() > 0 && h->kpm.sq_chain_uniform && hol) return REG_SQ_GRID;
+    if (s.hc_L() > 0 && !s.hc12() && h->kpm.hop_uniform && hol && s.hgrid_regs()) {
         // any other square honeycomb lattice whose cells fit a grid of lanes, one (cosh, sinh) for every bond: the HGRID layout
         if (hgn) *hgn = s.hgrid_regs();
         return REG_HC_GRID;
     }
     // the honeycomb lattice of 12 x 12 cells with one (cosh, sinh) for every bond: the quad layout
-    if (s.hc12() && h->kpm_hop_uniform && hol) return REG_HC12;
+    if (s.hc12() && h->kpm.hop_uniform && hol) return REG_HC12;
     return REG_NONE;
 }
 

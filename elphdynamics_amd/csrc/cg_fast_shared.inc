@@ -334,47 +334,38 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, 
     const int Lo2 = (int)((h->L + 1) / 2);
 #if ELPH_LP_MC == 4
     // with the fold only the frequencies that some chain still recurses on get a block (the schedule is longest first)
-    unsigned gy = (unsigned)Lo2;
-    if (fold_nct > 0) {
-        int nl = 1;
-        for (int c = 0; c < h->kpm_nch; ++c) {
-            int n = 0;
-            for (int w = 0; w < Lo2; ++w) n += (h->h_order[(size_t)c * Lo2 + w] >= 2 || h->h_lam[2 * (size_t)c + 1] < 0.0) ? 1 : 0;
-            nl = std::max(nl, n);
-        }
-        gy = (unsigned)std::min(Lo2, nl);
-    }
+    const unsigned gy = (unsigned)(fold_nct > 0 ? h->kpm.tab.recurse : Lo2);
     int hgn = 0;
     const int form = reg ? elph_reg_cheb_form(h, &hgn) : REG_NONE;
     if (form == REG_SQ) {
         // one frequency per block (the kernel loops over y, y + gridDim.y, ...: 2, 4 or 8 frequencies per block were measured — no
         // faster at 1 right-hand side or at 128: block dispatch is not what the kernel waits for)
 #define SQ_LAUNCH(PV, UV, ...) hipLaunchKernelGGL((k_kpm_cheb_sq<PV, UV, ##__VA_ARGS__>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
-                                             h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
+                                             h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
         const int P = h->shape.dpp();
-        if (P == 2 && h->sq_chain_uniform && nrhs >= 16) {
+        if (P == 2 && h->kpm.sq_chain_uniform && nrhs >= 16) {
             hipLaunchKernelGGL((k_kpm_cheb_sq_w4<2, true, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                               h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
-        } else if (P == 2) { if (h->sq_chain_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
-        else        { if (h->sq_chain_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
+                               h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+        } else if (P == 2) { if (h->kpm.sq_chain_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
+        else        { if (h->kpm.sq_chain_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
 #undef SQ_LAUNCH
         return check_launch_f("k_kpm_cheb_sq");
     }
     if (form == REG_SQ_GRID) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                           h->d_nu, K, h->d_sq_cbar, h->d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+                           h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         return check_launch_f("k_kpm_cheb_sq(grid)");
     }
     if (form == REG_HC_GRID) {
 #define HG_LAUNCH(NV) hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, false, NV>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
-                                         h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
+                                         h->d_nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
         if (hgn == 2) HG_LAUNCH(2); else if (hgn == 4) HG_LAUNCH(4); else HG_LAUNCH(8);
 #undef HG_LAUNCH
         return check_launch_f("k_kpm_cheb_sq(honeycomb grid)");
     }
     if (form == REG_HC12) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                           h->d_nu, K, h->d_cbar, h->d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+                           h->d_nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         return check_launch_f("k_kpm_cheb_sq(honeycomb)");
     }
 #else

@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, 
 // colouring (elph_recognise_lattice: the 16 x 16 DPP size), a template chunk length.  (ELPH_SQ16_AP=0, the lane-program kernel instead, is elph_plan_cg's.)
 bool elph_sq16_ap_usable(const elph_handle_s *h, int T) {
     if (h->kind != ELPH_MODEL_HOLSTEIN) return false;
-    const bool sq = h->shape.dpp() == 2 && h->d_sq_bond, hc = h->shape.hc12() && h->kpm_hop_uniform;      // (config C; config D, uniform hopping)
+    const bool sq = h->shape.dpp() == 2 && h->d_sq_bond, hc = h->shape.hc12() && h->kpm.hop_uniform;      // (config C; config D, uniform hopping)
     if (!sq && !hc) return false;
     return h->L % T == 0 && (T == 20 || T == 16 || T == 10 || T == 8 || T == 5 || T == 4 || T == 2);
 }

@@ -63,6 +63,11 @@ static int dev_alloc(T **p, size_t n) {
     return ELPH_OK;
 }
 
+// the number of phonon configurations resident in the handle; the KPM expansion is per chain, so a change invalidates it
+static void set_nchains(elph_handle_s *h, int n) {
+    if (h->nchains != n) { h->nchains = n; h->kpm.ready = false; }
+}
+
 // ------------------------------------------------------------------------------------------
 // lane program (cg_fast.hip): bonds re-packed [colour][pass][lane]
 // ------------------------------------------------------------------------------------------
@@ -114,12 +119,8 @@ static int build_lane_program(elph_handle_s *h) {
     const size_t ntau = (h->kind == ELPH_MODEL_SSH) ? (size_t)h->L : 1;
     RC(dev_alloc(&h->d_lp_c, ntau * NE * ELPH_WAVE));
     RC(dev_alloc(&h->d_lp_s, ntau * NE * ELPH_WAVE));
-    RC(dev_alloc(&h->d_lp_cbar, (size_t)NE * ELPH_WAVE));
-    RC(dev_alloc(&h->d_lp_sbar, (size_t)NE * ELPH_WAVE));
     h->shape = elph_recognise_lattice(h);
     if (h->shape.sq_L() > 0) {
-        RC(dev_alloc(&h->d_sq_cbar, (size_t)4 * h->N));
-        RC(dev_alloc(&h->d_sq_sbar, (size_t)4 * h->N));
         RC(dev_alloc(&h->d_sq_bond, (size_t)4 * h->N));
         HIPCHK(hipMemcpy(h->d_sq_bond, h->shape.bond.data(), sizeof(int) * 4 * h->N, hipMemcpyHostToDevice));
     }
@@ -469,11 +470,11 @@ extern "C" int elph_destroy(elph_handle h) {
     elph_greens_free(h);
     elph_dft_mfma_free(h);
     elph_dft_big_free(h);
+    elph_kpm_free(h);
     void *ptrs[] = {h->d_bi, h->d_bj, h->d_coloff, h->d_c, h->d_s, h->d_E, h->d_lam, h->d_stage_in, h->d_stage_out,
                     h->d_b, h->d_x, h->d_r, h->d_z, h->d_zp, h->d_p, h->d_tmp, h->d_part, h->d_state, h->d_phi, h->d_xfield,
-                    h->d_hist, h->d_scal, h->d_alpha, h->d_Ebar, h->d_cbar, h->d_sbar, h->d_order, h->d_coff, h->d_wsched, h->d_kdesc, h->d_kfold,
-                    h->d_coeff, h->d_klam, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar, h->d_ssh_cb, h->d_ssh_slot, h->d_nu, h->d_tw, h->d_theta, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s, h->d_lp_cbar,
-                    h->d_lp_sbar, h->d_Tk, h->d_Tt, h->d_Pk, h->d_Pt, h->d_sq_cbar, h->d_sq_sbar, h->d_sq_bond, h->d_pg_bond, h->d_res, h->d_mu_ch, h->d_kpm_start};
+                    h->d_hist, h->d_scal, h->d_alpha, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar, h->d_ssh_cb, h->d_ssh_slot, h->d_nu, h->d_tw, h->d_theta, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s,
+                    h->d_Tk, h->d_Tt, h->d_Pk, h->d_Pt, h->d_sq_bond, h->d_pg_bond, h->d_res, h->d_mu_ch};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_scal) (void)hipHostFree(h->h_scal);
@@ -518,7 +519,7 @@ extern "C" int elph_update_model_holstein(elph_handle h, const double *x, const 
     HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_stage_in, x, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }   // expansions were per chain
+    set_nchains(h, 1);   // expansions were per chain
     RC(elph_launch_expV(h, h->d_stage_in, dtau));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
@@ -548,7 +549,7 @@ extern "C" int elph_update_model_holstein_chains(elph_handle h, int nchains, con
     for (int c = 0; c < nchains; ++c) RC(elph_launch_expV(h, h->d_stage_in + (size_t)c * nd, dtau, c));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
-    h->kpm_ready = false;   // the preconditioner belongs to ONE configuration
+    h->kpm.ready = false;   // the preconditioner belongs to ONE configuration
     return ELPH_OK;
 }
 
@@ -557,7 +558,7 @@ extern "C" int elph_set_expV(elph_handle h, const double *expnDtauV) {
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!expnDtauV) { elph_set_error("null argument"); return ELPH_E_ARG; }
     HIPCHK(hipMemcpyAsync(h->d_stage_in, expnDtauV, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }   // expansions were per chain
+    set_nchains(h, 1);   // expansions were per chain
     RC(elph_launch_r2s(h, h->d_E, h->d_stage_in, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
@@ -583,7 +584,7 @@ extern "C" int elph_update_model_ssh(elph_handle h, const double *cosht, const d
     HIPCHK(hipMemcpy(h->d_E, expDtauMu, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice));
     RC(upload_lp_cs(h));
     h->mu_per_chain = false;
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }      // host tables describe ONE configuration
+    set_nchains(h, 1);      // host tables describe ONE configuration
     h->cs_host_stale = false;
     h->have_E = true;
     return ELPH_OK;
@@ -657,7 +658,7 @@ extern "C" int elph_update_model_ssh_fields(elph_handle h, const double *x, int6
     if (nph > 0 && !x) { elph_set_error("null argument"); return ELPH_E_ARG; }
     RC(elph_i_ssh_upload_params(h, nph, cb_index, t_ph, alpha, alpha2, t_bare_cb, mu));
     h->mu_per_chain = false;
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }
+    set_nchains(h, 1);
     const size_t np = (size_t)nph;
     if (np > 0) HIPCHK(hipMemcpyAsync(h->d_ssh_x, x, np * (size_t)h->L * sizeof(double), hipMemcpyHostToDevice, h->stream));
     RC(elph_launch_ssh_update(h, h->d_ssh_x, (int)np, h->d_ssh_cb, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_slot, dtau));
@@ -685,7 +686,7 @@ extern "C" int elph_update_model_ssh_fields_chains(elph_handle h, int nchains, c
     h->ssh_dtau = dtau;
     h->cs_host_stale = true;
     h->have_E = true;
-    h->kpm_ready = false;
+    h->kpm.ready = false;
     return ELPH_OK;
 }
 
@@ -849,7 +850,7 @@ static bool split_legal(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
     const int ways = ELPH_SPLIT_PARTS;
     if (!use_prec || hist || nrhs < 2 * ways || (nrhs % ways) || h->solo_chain >= 0 || h->dot_hi > 0) return false;
     const int n1 = nrhs / ways;
-    if (n1 % std::max(1, h->nchains) || n1 % std::max(1, h->kpm_nch)) return false;
+    if (n1 % std::max(1, h->nchains) || n1 % std::max(1, h->kpm.nch())) return false;
     return elph_plan_cg(h, n1, true, nrhs).px;      // (the parts choose their slices per wave for the whole batch in flight)
 }
 
@@ -862,7 +863,7 @@ static bool split_wanted(elph_handle_s *h, int nrhs, int use_prec, bool hist) {
     //  honeycomb 16 x 16 cells, eight sites per lane: 64 right-hand sides 64 -> 55 us, 256: 159 -> 145; D at 64: 89 -> 87)
     // (hopping disorder on 4 x 4 patches: the table variants of the patch kernels hold 40 KB of LDS per wavefront — two half-batches side by side lose to one
     //  stream: 32 x 32 at 96 right-hand sides 763 against 732 us, 28 x 28 695 against 663; profiles/r06/hopping_disorder_patch_kernels_with_tables.log)
-    if (!(e && e[0] == '1') && h->shape.PX * h->shape.PY >= 16 && !h->kpm_hop_uniform && elph_pg_disorder_ok(h)) return false;
+    if (!(e && e[0] == '1') && h->shape.PX * h->shape.PY >= 16 && !h->kpm.hop_uniform && elph_pg_disorder_ok(h)) return false;
     return (e && e[0] == '1') || nrhs >= (h->npl >= 5 ? 64 : 192);
 }
 
@@ -942,7 +943,7 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
                   double *eps_hist /* host, optional, nrhs*(maxiter+1) */) {
     const bool x0_zero = h->x_zero;        // the hint belongs to THIS solve: consumed before anything can return
     h->x_zero = false;
-    if (use_prec && !h->kpm_ready) { elph_set_error("preconditioned solve requested before elph_kpm_setup"); return ELPH_E_STATE; }
+    if (use_prec && !h->kpm.ready) { elph_set_error("preconditioned solve requested before elph_kpm_setup"); return ELPH_E_STATE; }
     CgParams P;
     P.tol = tol; P.kmax = kmax; P.maxiter = maxiter; P.use_prec = use_prec;
     P.record_hist = eps_hist ? 1 : 0;
@@ -1128,7 +1129,7 @@ int elph_i_reserve_chains(elph_handle_s *h, int nchains) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->kind == ELPH_MODEL_SSH) {
         RC(ssh_reserve_chains(h, nchains));
-        if (h->nchains != nchains) { h->nchains = nchains; h->kpm_ready = false; }
+        set_nchains(h, nchains);
         return ELPH_OK;
     }
     const int64_t need = (int64_t)nchains * h->ndim;
@@ -1137,7 +1138,7 @@ int elph_i_reserve_chains(elph_handle_s *h, int nchains) {
         h->E_cap = need;
         h->have_E = false;
     }
-    if (h->nchains != nchains) { h->nchains = nchains; h->kpm_ready = false; }
+    set_nchains(h, nchains);
     return ELPH_OK;
 }
 
@@ -1255,7 +1256,7 @@ extern "C" int elph_fermion_force_holstein(elph_handle h, const double *x, const
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!x || !lambda || !lambda2 || !mu || !phi_plus || !phi_minus || !dSfdx || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
     RC(ensure_capacity(h, 2));
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }   // expansions were per chain
+    set_nchains(h, 1);   // expansions were per chain
     const size_t nd = (size_t)h->ndim, N = (size_t)h->N, bytes = nd * sizeof(double);
     // update_model! (HolsteinModels.jl:526-549) and x in layout S
     HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1495,352 +1496,244 @@ extern "C" int elph_muldMdx_ssh_fields_dev(elph_handle h, double *dMdx_dev, cons
 // KPM preconditioner
 // ------------------------------------------------------------------------------------------
 
+void elph_kpm_free(elph_handle_s *h) {
+    KpmState &K = h->kpm;
+    void *ptrs[] = {K.d_Ebar, K.d_cbar, K.d_sbar, K.d_lp_cbar, K.d_lp_sbar, K.d_sq_cbar, K.d_sq_sbar, K.d_order, K.d_coff, K.d_wsched,
+                    K.d_desc, K.d_fold, K.d_lam, K.d_coeff, K.d_start};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    K = KpmState();
+}
+
 extern "C" int elph_kpm_create(elph_handle h, int n, double buf, double c1, double c2) {
     CHECK_H(h);
     if (n < 1 || !(buf >= 0.0)) { elph_set_error("bad KPM parameters"); return ELPH_E_ARG; }
-    h->kpm_n = n; h->kpm_buf = buf; h->kpm_c1 = c1; h->kpm_c2 = c2;
     // KPMExpansion ctor, KPMPreconditioners.jl:101-146: λ_lo = 0, λ_hi = 2, order 1 everywhere (one per chain, made on demand)
-    h->lam_lo = 0.0; h->lam_hi = 2.0; h->lam_avg = 1.0; h->lam_mag = 1.0;
-    h->kpm_chain.clear();
-    h->kpm_nch = 1;
-    h->kpm_hop_uploaded = false;
-    h->h_cbar.assign((size_t)h->nb, 0.0);
-    h->h_sbar.assign((size_t)h->nb, 0.0);
-    RC(dev_alloc(&h->d_cbar, (size_t)h->nb));
-    RC(dev_alloc(&h->d_sbar, (size_t)h->nb));
-    h->kpm_tab_cap = 0;
-    h->kpm_created = true;
-    h->kpm_ready = false;
-    h->kpm_active = 1;
+    elph_kpm_free(h);
+    h->kpm.par = {n, buf, c1, c2};
+    h->kpm.ssh = h->kind == ELPH_MODEL_SSH; h->kpm.created = true;
     return ELPH_OK;
 }
 
-// (re)size the per-chain host state and the device tables for nch chains
+// (re)size the per-chain host state and the device buffers for nch chains
 static int kpm_reserve(elph_handle_s *h, int nch) {
+    KpmState &K = h->kpm;
     const int Lo2 = (int)((h->L + 1) / 2);
-    if ((int)h->kpm_chain.size() != nch) {
-        // a different number of configurations: every expansion starts from the constructor state again
-        h->kpm_chain.assign((size_t)nch, elph_handle_s::KpmChainHost());
-        for (auto &c : h->kpm_chain) { c.order.assign(Lo2, 1); c.coeff.assign(2 * (size_t)Lo2, 0.0); for (int w = 0; w < Lo2; ++w) c.coeff[2 * w] = 1.0; }
+    // a different number of configurations: every expansion starts from the constructor state again
+    if (K.nch() != nch) K.chains.assign((size_t)nch, KpmChain(Lo2));
+    K.h_Ebar.resize((size_t)nch * h->N);
+    if (nch > K.tab_cap) {
+        RC(dev_alloc(&K.d_Ebar, (size_t)nch * h->N));
+        RC(dev_alloc(&K.d_order, (size_t)nch * Lo2));
+        RC(dev_alloc(&K.d_coff, (size_t)nch * (Lo2 + 1)));
+        RC(dev_alloc(&K.d_wsched, (size_t)nch * Lo2));
+        RC(dev_alloc(&K.d_desc, (size_t)nch * Lo2));
+        RC(dev_alloc(&K.d_fold, (size_t)nch * Lo2 * 2));
+        RC(dev_alloc(&K.d_lam, (size_t)nch * 2));
+        if (K.d_start) { HIPCHK(hipFree(K.d_start)); K.d_start = nullptr; }      // (made again for nch chains on its next use)
+        K.tab_cap = nch;
     }
-    h->kpm_nch = nch;
-    h->h_Ebar.resize((size_t)nch * h->N);
-    if (nch > h->kpm_tab_cap) {
-        RC(dev_alloc(&h->d_Ebar, (size_t)nch * h->N));
-        RC(dev_alloc(&h->d_order, (size_t)nch * Lo2));
-        RC(dev_alloc(&h->d_coff, (size_t)nch * (Lo2 + 1)));
-        RC(dev_alloc(&h->d_wsched, (size_t)nch * Lo2));
-        RC(dev_alloc(&h->d_kdesc, (size_t)nch * Lo2));
-        RC(dev_alloc(&h->d_kfold, (size_t)nch * Lo2 * 2));
-        RC(dev_alloc(&h->d_klam, (size_t)nch * 2));
-        h->kpm_tab_cap = nch;
+    const int hch = K.hop_per_chain() ? nch : 1;      // averaged hopping: one set per chain (SSH chains) or shared
+    if (hch > K.hop_cap) {
+        RC(dev_alloc(&K.d_cbar, (size_t)hch * h->nb));
+        RC(dev_alloc(&K.d_sbar, (size_t)hch * h->nb));
+        if (h->fast_capable) {
+            RC(dev_alloc(&K.d_lp_cbar, (size_t)hch * h->lp_ne * ELPH_WAVE));
+            RC(dev_alloc(&K.d_lp_sbar, (size_t)hch * h->lp_ne * ELPH_WAVE));
+        }
+        if (h->shape.sq_L() > 0) {
+            RC(dev_alloc(&K.d_sq_cbar, (size_t)hch * 4 * h->N));
+            RC(dev_alloc(&K.d_sq_sbar, (size_t)hch * 4 * h->N));
+        }
+        K.hop_cap = hch;
     }
     return ELPH_OK;
 }
 
-// flatten the per-chain expansions into the device tables.  A chain whose expansion is inactive (while others are
-// active) gets the identity expansion: order 1, c₀ = 1 — ldiv! copies for it (KPMPreconditioners.jl:475-478).
-static int kpm_upload(elph_handle_s *h) {
-    const int Lo2 = (int)((h->L + 1) / 2), nch = h->kpm_nch;
-    h->h_order.assign((size_t)nch * Lo2, 1);
-    h->h_coff.assign((size_t)nch * (Lo2 + 1), 0);
-    h->h_wsched.assign((size_t)nch * Lo2, 0);
-    h->h_lam.assign((size_t)nch * 2, 1.0);
-    h->h_coeff.clear();
-    h->h_kdesc.assign((size_t)nch * Lo2, KpmDesc());
-    h->h_kfold.assign((size_t)nch * Lo2 * 2, 0.0);
-    int off = 0;
-    for (int c = 0; c < nch; ++c) {
-        const auto &C = h->kpm_chain[(size_t)c];
-        int *ord = h->h_order.data() + (size_t)c * Lo2, *cof = h->h_coff.data() + (size_t)c * (Lo2 + 1);
-        int *ws = h->h_wsched.data() + (size_t)c * Lo2;
-        int loc = 0;
-        for (int w = 0; w < Lo2; ++w) {
-            const int o = C.active ? C.order[w] : 1;
-            ord[w] = o;
-            cof[w] = off;
-            if (C.active) {
-                h->h_coeff.insert(h->h_coeff.end(), C.coeff.begin() + 2 * (size_t)loc, C.coeff.begin() + 2 * (size_t)(loc + o));
-                loc += o;
-            } else {
-                h->h_coeff.push_back(1.0); h->h_coeff.push_back(0.0);
-                loc += C.order[w];
-            }
-            off += o;
-        }
-        cof[Lo2] = off;
-        // schedule: frequency blocks by decreasing order (the low frequencies carry the long recursions)
-        std::iota(ws, ws + Lo2, 0);
-        std::stable_sort(ws, ws + Lo2, [&](int a, int b) { return ord[a] > ord[b]; });
-        for (int y = 0; y < Lo2; ++y) {
-            const int w = ws[y];
-            KpmDesc d;
-            d.w = w; d.order = ord[w]; d.coff = cof[w]; d.pad = 0;
-            d.c0x = h->h_coeff[2 * (size_t)cof[w]]; d.c0y = h->h_coeff[2 * (size_t)cof[w] + 1];
-            h->h_kdesc[(size_t)c * Lo2 + y] = d;
-            // order-1 fold (active chains only: an identity expansion hands over the r.r partial sums instead, bit for bit)
-            const bool fold = C.active && d.order == 1;
-            const double s1 = fold ? d.c0x * d.c0x + d.c0y * d.c0y : 1.0;
-            const double wgt = ((h->L & 1) && w == Lo2 - 1) ? 1.0 : 2.0;
-            h->h_kfold[2 * ((size_t)c * Lo2 + w)] = s1;
-            h->h_kfold[2 * ((size_t)c * Lo2 + w) + 1] = fold ? wgt * s1 / (double)h->L : 0.0;
-        }
-        h->h_lam[2 * c] = (C.lam_hi + C.lam_lo) / 2;
-        h->h_lam[2 * c + 1] = C.active ? (C.lam_hi - C.lam_lo) / 2 : -1.0;      // < 0 marks the identity (KpmChainView::active)
-    }
-    const size_t ntot = (size_t)off;
-    if ((int64_t)ntot > h->coeff_cap) {
-        RC(dev_alloc(&h->d_coeff, ntot));
-        h->coeff_cap = (int64_t)ntot;
-    }
-    HIPCHK(hipMemcpy(h->d_coeff, h->h_coeff.data(), ntot * sizeof(double2), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_order, h->h_order.data(), sizeof(int) * h->h_order.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_coff, h->h_coff.data(), sizeof(int) * h->h_coff.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_wsched, h->h_wsched.data(), sizeof(int) * h->h_wsched.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_kdesc, h->h_kdesc.data(), sizeof(KpmDesc) * h->h_kdesc.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_kfold, h->h_kfold.data(), sizeof(double) * h->h_kfold.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_klam, h->h_lam.data(), sizeof(double) * h->h_lam.size(), hipMemcpyHostToDevice));
-    h->lam_lo = h->kpm_chain[0].lam_lo; h->lam_hi = h->kpm_chain[0].lam_hi;
-    h->lam_avg = h->h_lam[0]; h->lam_mag = h->h_lam[1];
-    return ELPH_OK;
-}
+// Where update_A! takes its averaged inputs: the handle's own model, or the caller's — the full-lattice handle of a sharded HMC update holds
+// no field of its own, so every rank contributes its own rows and the sum is injected (hmc.hip): Ē (Holstein) or c̄ / s̄ (bond phonons).
+struct KpmSource { const double *Ebar = nullptr, *cbar = nullptr, *sbar = nullptr; };
 
-static bool jl_isapprox(double x, double y, double rtol) {
-    return x == y || (std::isfinite(x) && std::isfinite(y) && fabs(x - y) <= rtol * std::max(fabs(x), fabs(y)));
-}
-
-// setup!(P) for every chain resident in the handle (h->nchains of them).  All arrays are per chain.
-static int kpm_setup_core(elph_handle_s *h, const double *b_max, const double *b_min, const double *e_min_in,
-                          const double *e_max_in, int *active, double *lam_lo, double *lam_hi) {
-    if (!h->kpm_created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
-    RC(need_model(h));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2, nch = h->nchains;
-    const bool resized = ((int)h->kpm_chain.size() != nch);
-    RC(kpm_reserve(h, nch));
-    // update_A!  (KPMPreconditioners.jl:332-349 Holstein; :355-381 SSH)
+// update_A! (KPMPreconditioners.jl:332-349 Holstein; :355-381 SSH) and the device images of the averaged hopping
+static int kpm_update_A(elph_handle_s *h, const KpmSource &src) {
+    KpmState &K = h->kpm;
+    const int nch = K.nch();
+    const size_t N = (size_t)h->N, nb = (size_t)h->nb;
     if (h->kind == ELPH_MODEL_HOLSTEIN) {
-        if (!h->ebar_external) RC(elph_launch_ebar(h, nch));      // (Ē stays on the device: the Arnoldi kernel and the apply read it there;
-                                                                  //  ebar_external: d_Ebar was filled by the caller — elph_i_kpm_setup_ebar)
-        h->h_cbar = h->h_c;
-        h->h_sbar = h->h_s;
-        h->kpm_hop_per_chain = false;
+        // (Ē stays on the device: the Arnoldi kernel and the apply read it there)
+        if (src.Ebar) HIPCHK(hipMemcpy(K.d_Ebar, src.Ebar, sizeof(double) * N, hipMemcpyHostToDevice));
+        else RC(elph_launch_ebar(h, nch));
+        K.h_cbar = h->h_c; K.h_sbar = h->h_s;
     } else {
         // Ebar = exp(dtau mu), held per chain (equal unless the chemical potential is tuned per chain)
-        HIPCHK(hipMemcpyAsync(h->d_Ebar, h->d_E, sizeof(double) * (size_t)nch * N, hipMemcpyDeviceToDevice, h->stream));
-        h->kpm_hop_per_chain = nch > 1;
-        if (nch > h->kpm_hop_cap) {          // averaged hopping tables per chain (and their lane-program / register-exchange images)
-            RC(dev_alloc(&h->d_cbar, (size_t)nch * h->nb));
-            RC(dev_alloc(&h->d_sbar, (size_t)nch * h->nb));
-            if (h->fast_capable) {
-                RC(dev_alloc(&h->d_lp_cbar, (size_t)nch * h->lp_ne * ELPH_WAVE));
-                RC(dev_alloc(&h->d_lp_sbar, (size_t)nch * h->lp_ne * ELPH_WAVE));
-            }
-            if (h->shape.sq_L() > 0) {
-                RC(dev_alloc(&h->d_sq_cbar, (size_t)nch * 4 * h->N));
-                RC(dev_alloc(&h->d_sq_sbar, (size_t)nch * 4 * h->N));
-            }
-            h->kpm_hop_cap = nch;
-        }
-        h->h_cbar.resize((size_t)nch * h->nb);
-        h->h_sbar.resize((size_t)nch * h->nb);
-        if (h->nb > 0 && h->csbar_external) {      // (the caller's: the full-lattice handle of a sharded update — elph_i_kpm_setup_csbar filled h_cbar / h_sbar)
-            HIPCHK(hipMemcpyAsync(h->d_cbar, h->h_cbar.data(), sizeof(double) * (size_t)nch * h->nb, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_sbar, h->h_sbar.data(), sizeof(double) * (size_t)nch * h->nb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(K.d_Ebar, h->d_E, sizeof(double) * nch * N, hipMemcpyDeviceToDevice, h->stream));
+        if (src.cbar) { K.h_cbar.assign(src.cbar, src.cbar + nb); K.h_sbar.assign(src.sbar, src.sbar + nb); }
+        K.h_cbar.resize(nch * nb); K.h_sbar.resize(nch * nb);
+        if (nb > 0 && src.cbar) {
+            HIPCHK(hipMemcpyAsync(K.d_cbar, K.h_cbar.data(), sizeof(double) * nch * nb, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(K.d_sbar, K.h_sbar.data(), sizeof(double) * nch * nb, hipMemcpyHostToDevice, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
-        } else if (h->nb > 0) {   // tau-means of cosht, sinht from the device tables (they may have been produced there)
-            RC(elph_launch_cs_bar(h, h->d_cbar, h->d_sbar, nch));
-            HIPCHK(hipMemcpyAsync(h->h_cbar.data(), h->d_cbar, sizeof(double) * (size_t)nch * h->nb, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(h->h_sbar.data(), h->d_sbar, sizeof(double) * (size_t)nch * h->nb, hipMemcpyDeviceToHost, h->stream));
+        } else if (nb > 0) {   // tau-means of cosht, sinht from the device tables (they may have been produced there)
+            RC(elph_launch_cs_bar(h, K.d_cbar, K.d_sbar, nch));
+            HIPCHK(hipMemcpyAsync(K.h_cbar.data(), K.d_cbar, sizeof(double) * nch * nb, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(K.h_sbar.data(), K.d_sbar, sizeof(double) * nch * nb, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
         }
     }
     // Holstein: c̄ = cosh(Δτ t), s̄ = sinh(Δτ t) never change after elph_create — upload their three device images once
-    const bool hop_fresh = !(h->kind == ELPH_MODEL_HOLSTEIN && h->kpm_hop_uploaded);
-    const int hch = h->kpm_hop_per_chain ? nch : 1;                       // hopping tables: one per chain (SSH chains) or shared
-    if (hop_fresh && h->nb > 0 && h->kind == ELPH_MODEL_HOLSTEIN) {
-        HIPCHK(hipMemcpy(h->d_cbar, h->h_cbar.data(), sizeof(double) * h->nb, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sbar, h->h_sbar.data(), sizeof(double) * h->nb, hipMemcpyHostToDevice));
+    if (h->kind == ELPH_MODEL_HOLSTEIN && K.hop_uploaded) return ELPH_OK;
+    const int hch = K.hop_per_chain() ? nch : 1;
+    if (nb > 0 && h->kind == ELPH_MODEL_HOLSTEIN) {
+        HIPCHK(hipMemcpy(K.d_cbar, K.h_cbar.data(), sizeof(double) * nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(K.d_sbar, K.h_sbar.data(), sizeof(double) * nb, hipMemcpyHostToDevice));
     }
-    if (hop_fresh && h->fast_capable) {
+    if (h->fast_capable) {
         const size_t per = (size_t)h->lp_ne * ELPH_WAVE;
         std::vector<double> lc((size_t)hch * per), ls((size_t)hch * per);
         for (int c = 0; c < hch; ++c) {
-            elph_lp_pack(h, h->h_cbar.data() + (size_t)c * h->nb, lc.data() + (size_t)c * per, 1.0);
-            elph_lp_pack(h, h->h_sbar.data() + (size_t)c * h->nb, ls.data() + (size_t)c * per, 0.0);
+            elph_lp_pack(h, K.h_cbar.data() + c * nb, lc.data() + c * per, 1.0);
+            elph_lp_pack(h, K.h_sbar.data() + c * nb, ls.data() + c * per, 0.0);
         }
-        HIPCHK(hipMemcpy(h->d_lp_cbar, lc.data(), sizeof(double) * lc.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_lp_sbar, ls.data(), sizeof(double) * ls.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(K.d_lp_cbar, lc.data(), sizeof(double) * lc.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(K.d_lp_sbar, ls.data(), sizeof(double) * ls.size(), hipMemcpyHostToDevice));
     }
-    if (hop_fresh && h->shape.sq_L() > 0) {
-        const size_t per = (size_t)4 * h->N;
+    if (h->shape.sq_L() > 0) {
+        const size_t per = 4 * N;
         std::vector<double> qc((size_t)hch * per), qs((size_t)hch * per);
         bool uni = true;
         for (int c = 0; c < hch; ++c) {
-            double *q0 = qc.data() + (size_t)c * per, *q1 = qs.data() + (size_t)c * per;
-            for (size_t k = 0; k < per; ++k) { q0[k] = h->h_cbar[(size_t)c * h->nb + h->shape.bond[k]]; q1[k] = h->h_sbar[(size_t)c * h->nb + h->shape.bond[k]]; }
+            double *q0 = qc.data() + c * per, *q1 = qs.data() + c * per;
+            for (size_t k = 0; k < per; ++k) { q0[k] = K.h_cbar[c * nb + h->shape.bond[k]]; q1[k] = K.h_sbar[c * nb + h->shape.bond[k]]; }
             for (size_t k = 1; k < per; ++k) uni = uni && q0[k] == q0[0] && q1[k] == q1[0];       // uniform within the chain
         }
-        h->sq_chain_uniform = uni;
-        HIPCHK(hipMemcpy(h->d_sq_cbar, qc.data(), sizeof(double) * qc.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sq_sbar, qs.data(), sizeof(double) * qs.size(), hipMemcpyHostToDevice));
+        K.sq_chain_uniform = uni;
+        HIPCHK(hipMemcpy(K.d_sq_cbar, qc.data(), sizeof(double) * qc.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(K.d_sq_sbar, qs.data(), sizeof(double) * qs.size(), hipMemcpyHostToDevice));
     }
-    if (hop_fresh) {      // (read by the honeycomb and patch-layout forms only)
-        bool uni = h->nb > 0 && !h->kpm_hop_per_chain;
-        for (size_t k = 1; k < (size_t)h->nb && uni; ++k) uni = h->h_cbar[k] == h->h_cbar[0] && h->h_sbar[k] == h->h_sbar[0];
-        h->kpm_hop_uniform = uni;
-    }
-    h->kpm_hop_uploaded = true;
-    const int was_active = h->kpm_active;
-    bool changed = !h->kpm_ready || resized;
-    if (!(b_max && b_min))
-        for (int c = 0; c < nch; ++c)
-            if (!(e_min_in && e_max_in && std::isfinite(e_min_in[c]) && std::isfinite(e_max_in[c]))) {
-                elph_set_error("Arnoldi start vectors required when bounds are not injected");
-                return ELPH_E_ARG;
-            }
-    // eigenvalue bounds (:272-273): injected, or the Arnoldi process with the caller's start vectors — on the device for all chains at
-    // once (kpm_dev.hip: one wavefront per chain and per operator, Ritz values by a wave-parallel Hessenberg QR), on the host for
-    // lattices beyond one wave
-    std::vector<double> eb((size_t)2 * nch, NAN);
-    bool need_arnoldi = false;
-    for (int c = 0; c < nch; ++c)
-        if (!(e_min_in && e_max_in && std::isfinite(e_min_in[c]) && std::isfinite(e_max_in[c]))) need_arnoldi = true;
-    bool on_device = false;
-    if (need_arnoldi) {
-        const char *eh = getenv("ELPH_KPM_HOST"), *ed = getenv("ELPH_KPM_DEVICE");     // read per call: tests pin one path
-        const bool host_only = eh && eh[0] == '1', dev_always = ed && ed[0] == '1';
-        const size_t nst = (size_t)2 * nch * N;
-        // (one or two chains: the host's scalar Arnoldi + LAPACK-style QR, 0.1 ms per chain, beats a kernel whose one wave spends
-        //  ~0.25 ms on the same sequential work; from three chains on all of them run side by side on the device)
-        if (!host_only && N <= 512 && (nch >= 3 || dev_always)) {
-            if ((int64_t)(nst + 2 * nch) > h->kpm_start_cap) {
-                RC(dev_alloc(&h->d_kpm_start, nst + 2 * (size_t)nch));
-                h->kpm_start_cap = (int64_t)(nst + 2 * nch);
-            }
-            HIPCHK(hipMemcpyAsync(h->d_kpm_start, b_max, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_kpm_start + (size_t)nch * N, b_min, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
-            const int rcd = elph_kpm_bounds_dev(h, nch, h->d_kpm_start, h->d_kpm_start + nst);
-            if (rcd == ELPH_OK) {
-                HIPCHK(hipMemcpyAsync(eb.data(), h->d_kpm_start + nst, sizeof(double) * 2 * (size_t)nch, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                on_device = true;
-            } else if (rcd != ELPH_E_UNSUPPORTED) {
-                return rcd;
-            }
-        }
-        if (!on_device) {
-            // host path needs Ē (and the averaged hoppings) on the host
-            HIPCHK(hipMemcpy(h->h_Ebar.data(), h->d_Ebar, sizeof(double) * (size_t)nch * N, hipMemcpyDeviceToHost));
-        }
-    }
-    // per chain: acceptance window, and new orders + coefficients when the bounds moved by more than buf (host, ~0.1 ms per chain,
-    // only when they moved)
-    std::vector<char> moved((size_t)nch, 0);
-    std::vector<int> was((size_t)nch, 0);
-    auto one_chain = [&](int c) {
-        auto &C = h->kpm_chain[(size_t)c];
-        was[(size_t)c] = C.active;
-        double e_min = e_min_in ? e_min_in[c] : NAN, e_max = e_max_in ? e_max_in[c] : NAN;
-        if (!(std::isfinite(e_min) && std::isfinite(e_max))) {
-            if (on_device) { e_min = eb[2 * (size_t)c]; e_max = eb[2 * (size_t)c + 1]; }
-            else (void)elph_kpm_arnoldi(h, c, b_max + (size_t)c * N, b_min + (size_t)c * N, &e_min, &e_max);
-        }
-        if ((0.0 < e_min && e_min < 1.0) && (1.0 < e_max) && (e_max - e_min) < 2.0) {       // :280
-            const double lo = std::max(0.0, (1 - 2 * h->kpm_buf) * e_min), hi = (1 + 2 * h->kpm_buf) * e_max;
-            if (!jl_isapprox(lo, C.lam_lo, h->kpm_buf) || !jl_isapprox(hi, C.lam_hi, h->kpm_buf)) {   // :288
-                C.lam_lo = lo; C.lam_hi = hi;
-                int off = 0;
-                std::vector<double> coeff;
-                for (int w = 0; w < Lo2; ++w) {
-                    const double phi = 2.0 * M_PI / (double)L * (w + 0.5);                   // ctor :117
-                    int order = (int)floor((hi - lo) * (h->kpm_c1 / phi + h->kpm_c2));       // :300
-                    order = std::max(1, order);
-                    C.order[w] = order;
-                    coeff.resize(2 * (size_t)(off + order));
-                    elph_kpm_coefficients(coeff.data() + 2 * (size_t)off, order, lo, hi, phi);
-                    off += order;
-                }
-                C.coeff.swap(coeff);
-                moved[(size_t)c] = 1;
-            }
-            C.active = 1;
-        } else {
-            C.active = 0;                                                                    // :312-318
-        }
-    };
-    for (int c = 0; c < nch; ++c) one_chain(c);
-    int any_active = 0;
-    for (int c = 0; c < nch; ++c) {
-        auto &C = h->kpm_chain[(size_t)c];
-        if (moved[(size_t)c] || was[(size_t)c] != C.active || C.fresh) changed = true;
-        C.fresh = false;
-        any_active |= C.active;
-        if (active) active[c] = C.active;
-        if (lam_lo) lam_lo[c] = C.lam_lo;
-        if (lam_hi) lam_hi[c] = C.lam_hi;
-    }
-    h->kpm_active = any_active;
-    if (changed || was_active != h->kpm_active) {
-        RC(kpm_upload(h));
-    }
-    h->kpm_ready = true;
+    K.hop_uniform = nb > 0 && !K.hop_per_chain();      // (read by the honeycomb and patch-layout forms only)
+    for (size_t k = 1; k < nb && K.hop_uniform; ++k) K.hop_uniform = K.h_cbar[k] == K.h_cbar[0] && K.h_sbar[k] == K.h_sbar[0];
+    K.hop_uploaded = true;
     return ELPH_OK;
 }
 
-// setup!(P) of a Holstein handle whose τ-averaged exp(−ΔτV) comes from OUTSIDE: the full-lattice handle of a sharded HMC update holds no
-// field of its own — every rank contributes the Ē of its own rows and the sum is injected here (hmc.hip).  One chain.
-int elph_i_kpm_setup_ebar(elph_handle_s *h, const double *Ebar_host, const double *b_max, const double *b_min) {
-    if (h->kind != ELPH_MODEL_HOLSTEIN || !h->kpm_created) { elph_set_error("Ē injection: a Holstein handle with elph_kpm_create done"); return ELPH_E_STATE; }
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }
-    RC(kpm_reserve(h, 1));
-    HIPCHK(hipMemcpy(h->d_Ebar, Ebar_host, sizeof(double) * (size_t)h->N, hipMemcpyHostToDevice));
-    const bool had_E = h->have_E;
-    h->have_E = true;                  // (the expansion needs Ē and the hopping only; this handle never multiplies by M)
-    h->ebar_external = true;
-    const int rc = kpm_setup_core(h, b_max, b_min, nullptr, nullptr, nullptr, nullptr, nullptr);
-    h->ebar_external = false;
-    h->have_E = had_E;
-    return rc;
+// The eigenvalue bounds of every chain (:272-273), eb[2c] = e_min and eb[2c+1] = e_max: injected, or the Arnoldi process with the caller's
+// start vectors — on the device for all chains at once (kpm_dev.hip: one wavefront per chain and per operator, Ritz values by a
+// wave-parallel Hessenberg QR), on the host for lattices beyond one wave
+static int kpm_bounds(elph_handle_s *h, const double *b_max, const double *b_min, const double *e_min, const double *e_max,
+                      std::vector<double> &eb) {
+    KpmState &K = h->kpm;
+    const int N = (int)h->N, nch = K.nch();
+    auto injected = [&](int c) { return e_min && e_max && std::isfinite(e_min[c]) && std::isfinite(e_max[c]); };
+    eb.assign((size_t)2 * nch, NAN);
+    bool need_arnoldi = false;
+    for (int c = 0; c < nch; ++c)
+        if (injected(c)) { eb[2 * (size_t)c] = e_min[c]; eb[2 * (size_t)c + 1] = e_max[c]; } else need_arnoldi = true;
+    if (!need_arnoldi) return ELPH_OK;
+    if (!(b_max && b_min)) { elph_set_error("Arnoldi start vectors required when bounds are not injected"); return ELPH_E_ARG; }
+    const char *eh = getenv("ELPH_KPM_HOST"), *ed = getenv("ELPH_KPM_DEVICE");     // read per call: tests pin one path
+    const bool host_only = eh && eh[0] == '1', dev_always = ed && ed[0] == '1';
+    // (one or two chains: the host's scalar Arnoldi + LAPACK-style QR, 0.1 ms per chain, beats a kernel whose one wave spends
+    //  ~0.25 ms on the same sequential work; from three chains on all of them run side by side on the device)
+    if (!host_only && N <= 512 && (nch >= 3 || dev_always)) {
+        const size_t nst = (size_t)2 * nch * N;
+        if (!K.d_start) RC(dev_alloc(&K.d_start, (size_t)K.tab_cap * (2 * N + 2)));
+        HIPCHK(hipMemcpyAsync(K.d_start, b_max, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(K.d_start + (size_t)nch * N, b_min, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
+        const int rcd = elph_kpm_bounds_dev(h, nch, K.d_start, K.d_start + nst);
+        if (rcd == ELPH_OK) {
+            std::vector<double> dev((size_t)2 * nch);
+            HIPCHK(hipMemcpyAsync(dev.data(), K.d_start + nst, sizeof(double) * 2 * (size_t)nch, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            for (int c = 0; c < nch; ++c)
+                if (!injected(c)) { eb[2 * (size_t)c] = dev[2 * (size_t)c]; eb[2 * (size_t)c + 1] = dev[2 * (size_t)c + 1]; }
+            return ELPH_OK;
+        }
+        if (rcd != ELPH_E_UNSUPPORTED) return rcd;
+    }
+    // the host path needs Ē (and the averaged hoppings) on the host
+    HIPCHK(hipMemcpy(K.h_Ebar.data(), K.d_Ebar, sizeof(double) * (size_t)nch * N, hipMemcpyDeviceToHost));
+    for (int c = 0; c < nch; ++c)
+        if (!injected(c)) (void)elph_kpm_arnoldi(h, c, b_max + (size_t)c * N, b_min + (size_t)c * N, &eb[2 * (size_t)c], &eb[2 * (size_t)c + 1]);
+    return ELPH_OK;
 }
 
-// setup!(P) of a bond-phonon handle whose τ-averaged hopping tables come from OUTSIDE (update_A!, KPMPreconditioners.jl:355-381): the
-// full-lattice handle of a sharded HMC update — the hoppings move on the ranks' slabs, every rank contributes the τ-means of the bonds it
-// owns and the sum is injected here (hmc.hip).  exp(Δτμ) is the handle's own (elph_update_model_ssh once; μ does not move).  One chain.
+// the device copies of the tables
+static int kpm_upload(elph_handle_s *h) {
+    KpmState &K = h->kpm;
+    const KpmTables &T = K.tab;
+    const size_t ncoeff = T.coeff.size() / 2;
+    if (ncoeff > K.coeff_cap) {
+        RC(dev_alloc(&K.d_coeff, ncoeff));
+        K.coeff_cap = ncoeff;
+    }
+    HIPCHK(hipMemcpy(K.d_coeff, T.coeff.data(), ncoeff * sizeof(double2), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(K.d_order, T.order.data(), sizeof(int) * T.order.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(K.d_coff, T.coff.data(), sizeof(int) * T.coff.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(K.d_wsched, T.wsched.data(), sizeof(int) * T.wsched.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(K.d_desc, T.desc.data(), sizeof(KpmDesc) * T.desc.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(K.d_fold, T.fold.data(), sizeof(double) * T.fold.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(K.d_lam, T.lam.data(), sizeof(double) * T.lam.size(), hipMemcpyHostToDevice));
+    return ELPH_OK;
+}
+
+// setup!(P) for every chain resident in the handle (h->nchains of them).  All arrays are per chain.
+static int kpm_setup_core(elph_handle_s *h, const KpmSource &src, const double *b_max, const double *b_min, const double *e_min,
+                          const double *e_max, int *active, double *lam_lo, double *lam_hi) {
+    KpmState &K = h->kpm;
+    if (!K.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
+    if (!src.Ebar) RC(need_model(h));      // (an injected Ē is all the expansion needs: that handle never multiplies by M)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    RC(kpm_reserve(h, h->nchains));
+    RC(kpm_update_A(h, src));
+    std::vector<double> eb;
+    RC(kpm_bounds(h, b_max, b_min, e_min, e_max, eb));
+    if (elph_kpm_plan(K, (int)h->L, eb.data())) RC(kpm_upload(h));
+    K.ready = true;
+    for (int c = 0; c < K.nch(); ++c) {
+        if (active) active[c] = K.chains[(size_t)c].active;
+        if (lam_lo) lam_lo[c] = K.chains[(size_t)c].lam_lo;
+        if (lam_hi) lam_hi[c] = K.chains[(size_t)c].lam_hi;
+    }
+    return ELPH_OK;
+}
+
+// setup!(P) of a Holstein handle whose τ-averaged exp(−ΔτV) comes from OUTSIDE (KpmSource).  One chain.
+int elph_i_kpm_setup_ebar(elph_handle_s *h, const double *Ebar_host, const double *b_max, const double *b_min) {
+    if (h->kind != ELPH_MODEL_HOLSTEIN || !h->kpm.created) { elph_set_error("Ē injection: a Holstein handle with elph_kpm_create done"); return ELPH_E_STATE; }
+    set_nchains(h, 1);
+    return kpm_setup_core(h, KpmSource{Ebar_host, nullptr, nullptr}, b_max, b_min, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// setup!(P) of a bond-phonon handle whose τ-averaged hopping tables come from OUTSIDE (KpmSource); exp(Δτμ) is the handle's own
+// (elph_update_model_ssh once; μ does not move).  One chain.
 int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const double *sbar_host, const double *b_max, const double *b_min) {
-    if (h->kind != ELPH_MODEL_SSH || !h->kpm_created || !h->have_E) {
+    if (h->kind != ELPH_MODEL_SSH || !h->kpm.created || !h->have_E) {
         elph_set_error("c̄ / s̄ injection: a bond-phonon handle with elph_kpm_create and one elph_update_model_ssh done");
         return ELPH_E_STATE;
     }
-    if (h->nchains != 1) { h->nchains = 1; h->kpm_ready = false; }
-    h->h_cbar.assign(cbar_host, cbar_host + h->nb);
-    h->h_sbar.assign(sbar_host, sbar_host + h->nb);
-    h->csbar_external = true;
-    const int rc = kpm_setup_core(h, b_max, b_min, nullptr, nullptr, nullptr, nullptr, nullptr);
-    h->csbar_external = false;
-    return rc;
+    set_nchains(h, 1);
+    return kpm_setup_core(h, KpmSource{nullptr, cbar_host, sbar_host}, b_max, b_min, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" int elph_kpm_setup(elph_handle h, const double *b_max, const double *b_min, double e_min, double e_max,
                               int *active, double *lam_lo, double *lam_hi) {
     CHECK_H(h);
     if (h->nchains != 1) { elph_set_error("%d phonon configurations are resident: use elph_kpm_setup_chains", h->nchains); return ELPH_E_STATE; }
-    return kpm_setup_core(h, b_max, b_min, &e_min, &e_max, active, lam_lo, lam_hi);
+    return kpm_setup_core(h, KpmSource(), b_max, b_min, &e_min, &e_max, active, lam_lo, lam_hi);
 }
 
 extern "C" int elph_kpm_setup_chains(elph_handle h, const double *b_max, const double *b_min, const double *e_min,
                                      const double *e_max, int *active, double *lam_lo, double *lam_hi) {
     CHECK_H(h);
-    return kpm_setup_core(h, b_max, b_min, e_min, e_max, active, lam_lo, lam_hi);
+    return kpm_setup_core(h, KpmSource(), b_max, b_min, e_min, e_max, active, lam_lo, lam_hi);
 }
 
 extern "C" int elph_kpm_orders(elph_handle h, int64_t *orders, int64_t *total) {
     CHECK_H(h);
-    if (!h->kpm_created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
+    if (!h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
     const int Lo2 = (int)((h->L + 1) / 2);
     int64_t tot = 0;
     for (int w = 0; w < Lo2; ++w) {
-        const int o = h->kpm_chain.empty() ? 1 : h->kpm_chain[0].order[w];
+        const int o = h->kpm.chains.empty() ? 1 : h->kpm.chains[0].order[w];
         if (orders) orders[w] = o;
         tot += o;
     }
@@ -1850,7 +1743,7 @@ extern "C" int elph_kpm_orders(elph_handle h, int64_t *orders, int64_t *total) {
 
 extern "C" int elph_kpm_apply_dev(elph_handle h, double *z_dev, const double *r_dev) {
     CHECK_H(h);
-    if (!h->kpm_ready) { elph_set_error("elph_kpm_setup has not been called"); return ELPH_E_STATE; }
+    if (!h->kpm.ready) { elph_set_error("elph_kpm_setup has not been called"); return ELPH_E_STATE; }
     if (!z_dev || !r_dev) { elph_set_error("null argument"); return ELPH_E_ARG; }
     RC(elph_launch_r2s(h, h->d_r, r_dev, 1));
     RC(elph_launch_kpm_apply(h, h->d_zp, h->d_r, 1, 0));
@@ -1966,7 +1859,7 @@ extern "C" int elph_bench_prepare(elph_handle h, int what, int nrhs, const doubl
     CHECK_H(h);
     RC(need_model(h));
     if (nrhs < 1 || what < 0 || what > 12) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    if ((what == 2 || what == 3 || what == 10 || what == 11 || (what >= 6 && what <= 8)) && !h->kpm_ready) { elph_set_error("KPM not set up"); return ELPH_E_STATE; }
+    if ((what == 2 || what == 3 || what == 10 || what == 11 || (what >= 6 && what <= 8)) && !h->kpm.ready) { elph_set_error("KPM not set up"); return ELPH_E_STATE; }
     RC(ensure_capacity(h, nrhs));
     if (B) {
         const size_t bytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);

@@ -52,6 +52,15 @@ int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, int *nw, int 
 int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht, const double *sinht,
                              int *out);
 
+/* What setup!(P) plans for nch chains at Ltau = ltau over nsteps successive steps of bounds (kpm_host.cpp: elph_kpm_plan; needs no device).
+ * e_bounds: [nsteps][nch][2] (e_min, e_max); uploaded[s] = 1 when step s uploads the tables.  After the last step: active[nch]; lam[nch][4] =
+ * lam_lo, lam_hi and the uploaded (lam_avg, lam_mag); the tables order, wsched [nch][Lo2] and coff [nch][Lo2+1]; c0 [nch][Lo2][2] the leading
+ * coefficient of each schedule entry; fold [nch][Lo2][2]; the coefficients (complex interleaved) into coeff, which holds coeff_cap doubles.
+ * *ncoeff = the doubles they take (ELPH_E_ARG when coeff is given and too small).  Any output may be NULL. */
+int elph_bench_kpm_plan(int64_t ltau, double buf, double c1, double c2, int nch, int nsteps, const double *e_bounds, int *uploaded,
+                        int *active, double *lam, int *order, int *coff, int *wsched, double *c0, double *fold, double *coeff,
+                        int64_t coeff_cap, int64_t *ncoeff);
+
 /* Whether an un-preconditioned solve of nrhs right-hand sides FROM x = 0 on this handle runs in the slab form (slabs.hip: lattices beyond
  * 320 sites as slabs of rows on the same device, the resident kernel per slab, one launch) and its shape. */
 int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int *sites_per_slab, int *own_sites);

@@ -234,6 +234,61 @@ struct LatticeShape {
     }
 };
 
+// The KPM preconditioner of a handle (host only): elph_kpm_create's parameters, one expansion per chain, the averaged inputs and the
+// flattened tables, each with its device images.  kpm_setup_core (elph_api.hip) fills it; the planning is pure (kpm_host.cpp).
+struct KpmParams { int n = 20; double buf = 0.05, c1 = 1.0, c2 = 1.0; };
+
+// one chain's expansion (KPMExpansion, KPMPreconditioners.jl:101-146); the constructor state is order 1 and c₀ = 1 everywhere
+struct KpmChain {
+    double lam_lo = 0.0, lam_hi = 2.0;
+    int active = 1;
+    bool fresh = true;                     // never uploaded
+    std::vector<int> order;                // [Lo2]; coeff: complex interleaved, sum of order
+    std::vector<double> coeff;
+    explicit KpmChain(int Lo2 = 0) : order((size_t)Lo2, 1), coeff(2 * (size_t)Lo2, 0.0) { for (int w = 0; w < Lo2; ++w) coeff[2 * (size_t)w] = 1.0; }
+};
+
+// the device tables of every chain's expansion, flattened (elph_kpm_tables)
+struct KpmTables {
+    std::vector<int> order, coff, wsched;  // [nch][Lo2], [nch][Lo2+1] (absolute offsets into coeff), [nch][Lo2] frequencies longest first
+    std::vector<KpmDesc> desc;             // [nch][Lo2] the same schedule, packed
+    std::vector<double> fold;              // [nch][Lo2][2] order-1 fold of the forward transform: {scale, r.z weight} (dft_mfma.hip: XrFuse)
+    std::vector<double> lam;               // [nch][2] lam_avg, lam_mag (< 0: the identity expansion)
+    std::vector<double> coeff;             // complex interleaved, all chains
+    int recurse = 1;                       // frequency blocks that some chain still recurses on (order >= 2, or an identity expansion)
+};
+
+struct KpmState {
+    KpmParams par;
+    bool created = false, ready = false, ssh = false;      // ssh: bond phonons, every chain has its own averaged hopping
+    std::vector<KpmChain> chains;          // one per resident configuration
+    // averaged inputs (update_A!) and their device images
+    std::vector<double> h_Ebar, h_cbar, h_sbar;     // h_Ebar: [nch][N]; h_cbar, h_sbar: [nb], or [nch][nb] when hop_per_chain()
+    double *d_Ebar = nullptr, *d_cbar = nullptr, *d_sbar = nullptr;    // [nch][N]; [hop chains][nb]
+    double *d_lp_cbar = nullptr, *d_lp_sbar = nullptr;    // lane-program copies [hop chains][NE][64] (fast_capable)
+    double *d_sq_cbar = nullptr, *d_sq_sbar = nullptr;    // [hop chains][4][N] through shape.bond (shape.sq_L() > 0)
+    int hop_cap = 0;                       // chains the hopping images are allocated for
+    bool hop_uploaded = false;             // Holstein: c̄, s̄ (= cosh, sinh of the fixed hoppings) are on the device already
+    bool sq_chain_uniform = false;         // small square lattices: the averaged hopping is one (cbar, sbar) WITHIN each chain (SSH chains may
+                                           // differ from one another): the register Chebyshev kernels keep them in scalars
+    bool hop_uniform = false;              // the averaged hopping is one (cbar, sbar) for every bond, shared by all chains
+    // the flattened tables and their device copies
+    KpmTables tab;
+    int *d_order = nullptr, *d_coff = nullptr, *d_wsched = nullptr;
+    KpmDesc *d_desc = nullptr;
+    double *d_fold = nullptr, *d_lam = nullptr;
+    double2 *d_coeff = nullptr;
+    int tab_cap = 0;                       // chains d_Ebar, the tables and d_start are allocated for
+    size_t coeff_cap = 0;                  // coefficients d_coeff holds
+    double *d_start = nullptr;             // Arnoldi start vectors [2][nch][N] + the bounds [nch][2] coming back (kpm_dev.hip); made on first use
+    int nch() const { return (int)chains.size(); }
+    bool hop_per_chain() const { return ssh && nch() > 1; }
+    bool any_active() const { for (const auto &C : chains) if (C.active) return true; return chains.empty(); }
+    bool all_active() const { for (const auto &C : chains) if (!C.active) return false; return true; }
+    double lam_avg(int c) const { return tab.lam.empty() ? 1.0 : tab.lam[2 * (size_t)c]; }
+    double lam_mag(int c) const { return tab.lam.empty() ? 1.0 : tab.lam[2 * (size_t)c + 1]; }
+};
+
 struct elph_handle_s {
     int kind = 0, device = 0;
     int64_t N = 0, L = 0, nb = 0, ndim = 0;
@@ -256,8 +311,6 @@ struct elph_handle_s {
     double *d_lam = nullptr;               // [3N] lambda, lambda2, mu staging
     hipStream_t split_stream[ELPH_SPLIT_PARTS] = {};      // streams 1 … ways-1 + event of the split form of a preconditioned batch (elph_api.hip: SplitRun; [0] unused: the handle's own stream)
     hipEvent_t split_ev = nullptr;
-    bool csbar_external = false;           // kpm_setup_core: h_cbar / h_sbar were filled by the caller (elph_i_kpm_setup_csbar)
-    bool ebar_external = false;            // kpm_setup_core: d_Ebar was filled by the caller (elph_i_kpm_setup_ebar)
     CgPlan plan;                           // the kernels of the current solve's CG iteration (kernels.hip: elph_plan_cg)
     // SSH update_model! on the device (elph_update_model_ssh_fields): staging of x, per-phonon tables, slot map
     double *d_ssh_x = nullptr, *d_ssh_par = nullptr, *d_ssh_tbare = nullptr, *d_ssh_bar = nullptr;
@@ -276,12 +329,8 @@ struct elph_handle_s {
     int lp_ne = 0;
     std::vector<unsigned> h_lp_ij;
     unsigned *d_lp_ij = nullptr;
-    double *d_lp_c = nullptr, *d_lp_s = nullptr, *d_lp_cbar = nullptr, *d_lp_sbar = nullptr;
+    double *d_lp_c = nullptr, *d_lp_s = nullptr;
     LatticeShape shape;                    // the lattice of the bond table (elph_create: elph_recognise_lattice)
-    bool sq_chain_uniform = false;         // kpm_setup_core, small square lattices: the tau-averaged hopping is one (cbar, sbar) WITHIN each chain
-                                           // (SSH chains may differ from one another): the register Chebyshev kernels keep them in scalars
-    bool kpm_hop_uniform = false;          // kpm_setup_core: the tau-averaged hopping tables are one (cbar, sbar) for every bond, shared by all chains
-    double *d_sq_cbar = nullptr, *d_sq_sbar = nullptr;   // [4][N]
     int *d_pg_bond = nullptr;                            // [4][N] shape.bond of a square lattice in the patch layout: hopping disorder there
     int *d_sq_bond = nullptr;                            // [4][N] shape.bond of a small square lattice (shape.sq_L() > 0)
     void *shard = nullptr;                 // ShardState (shard.hip), owned
@@ -327,35 +376,7 @@ struct elph_handle_s {
     double *d_alpha = nullptr;             // cap_rhs: CG step length handed from k_cg_xr to the next k_cg_ap
     double *h_scal = nullptr;              // pinned
 
-    // KPM
-    bool kpm_created = false, kpm_ready = false;
-    int kpm_n = 20;
-    double kpm_buf = 0.05, kpm_c1 = 1.0, kpm_c2 = 1.0;
-    double lam_lo = 0.0, lam_hi = 2.0, lam_avg = 1.0, lam_mag = 1.0;
-    int kpm_active = 1;                    // 0: every chain's expansion is inactive (identity copy path)
-    int kpm_nch = 1;                       // chains the expansion tables are built for
-    bool kpm_hop_uploaded = false;         // Holstein: c̄, s̄ (= cosh, sinh of the fixed hoppings) are on the device already
-    struct KpmChainHost { double lam_lo = 0.0, lam_hi = 2.0; int active = 1; bool fresh = true;
-                          std::vector<int> order; std::vector<double> coeff; };
-    std::vector<KpmChainHost> kpm_chain;   // per chain: bounds, orders, coefficients (complex interleaved)
-    double *d_kpm_start = nullptr;         // Arnoldi start vectors [2][nch][N] + the bounds [nch][2] coming back (kpm_dev.hip)
-    int64_t kpm_start_cap = 0;
-    std::vector<double> h_Ebar, h_cbar, h_sbar;   // h_Ebar: [kpm_nch][N]; h_cbar, h_sbar: [nb], or [kpm_nch][nb] for SSH chains
-    bool kpm_hop_per_chain = false;        // SSH with several chains: averaged hopping tables per chain
-    int kpm_hop_cap = 1;                   // chains the device copies of the averaged hopping tables are allocated for
-    std::vector<int> h_order, h_coff, h_wsched;   // flattened [kpm_nch][...] images of the device tables
-    std::vector<double> h_coeff;           // complex interleaved, all chains
-    std::vector<double> h_lam;             // [kpm_nch][2]
-    double *d_klam = nullptr;
-    int64_t kpm_tab_cap = 0;               // chains the device tables are allocated for
-    double *d_Ebar = nullptr, *d_cbar = nullptr, *d_sbar = nullptr;
-    int *d_order = nullptr, *d_coff = nullptr, *d_wsched = nullptr;
-    KpmDesc *d_kdesc = nullptr;
-    std::vector<KpmDesc> h_kdesc;
-    double *d_kfold = nullptr;             // [kpm_nch][Lo2][2] order-1 fold of the forward transform: {scale, r.z weight} (dft_mfma.hip: XrFuse)
-    std::vector<double> h_kfold;
-    double2 *d_coeff = nullptr;
-    int64_t coeff_cap = 0;
+    KpmState kpm;                          // the KPM preconditioner (elph_kpm_create, kpm_setup_core)
     double2 *d_nu = nullptr;               // cap_rhs * Lo2 * N complex (half spectrum, omega-major)
 
     // FFT twiddles
@@ -538,6 +559,14 @@ int elph_dft_mfma_inv(elph_handle_s *h, int which, double *outS, const double2 *
 
 // ---- host-side KPM setup (kpm_host.cpp) ---------------------------------------------------
 void elph_kpm_coefficients(double *c_z, int order, double lam_lo, double lam_hi, double phi);
+// one chain for its bounds: acceptance window, hysteresis, orders and coefficients; true when the chain's tables change (moved, turned on
+// or off, or never uploaded)
+bool elph_kpm_plan_chain(const KpmParams &p, int L, double e_min, double e_max, KpmChain &C);
+KpmTables elph_kpm_tables(int L, const std::vector<KpmChain> &chains);
+// every chain of K for its bounds eb[nch][2] (e_min, e_max); rebuilds K.tab when a chain changed or K is not ready, and says so (the
+// caller then uploads the tables)
+bool elph_kpm_plan(KpmState &K, int L, const double *eb);
+void elph_kpm_free(elph_handle_s *h);      // elph_api.hip: the device buffers of h->kpm; h->kpm back to its initial state
 int elph_kpm_arnoldi(const elph_handle_s *h, int chain, const double *b_max, const double *b_min, double *e_min,
                      double *e_max);
 int elph_hess_eigvals(std::vector<double> &a, int n, std::vector<double> &wr, std::vector<double> &wi);

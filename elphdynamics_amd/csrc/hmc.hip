@@ -774,12 +774,12 @@ extern "C" int elph_hmc_update_chains(elph_handle h, double dt, int64_t nt, int 
         elph_set_error("R, Rp, Rm, u_accept (and kpm_randn with a preconditioner) are required unless elph_hmc_set_rng was called");
         return ELPH_E_ARG;
     }
-    if (use_precond && !h->kpm_created && !sharded(h)) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
+    if (use_precond && !h->kpm.created && !sharded(h)) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
     const int nch = st->nch;
     if (sharded(h)) {
         // one lattice over several ranks: the trajectory runs on the slab (own + ghost rows); the random vectors must be the slab's part
         // of the GLOBAL vectors (ghost entries included) and the uniform of the Metropolis test the same number on every rank
-        const bool prec_ok = !use_precond || (elph_i_shard_full(h) && elph_i_shard_full(h)->kpm_created && kpm_randn && (!st->ssh || elph_i_shard_has_bonds(h)));
+        const bool prec_ok = !use_precond || (elph_i_shard_full(h) && elph_i_shard_full(h)->kpm.created && kpm_randn && (!st->ssh || elph_i_shard_has_bonds(h)));
         if ((st->ssh && (!st->wown || st->shared)) || nch != 1 || !prec_ok || st->rng_on || !R || !Rp || !Rm || !u_accept) {
             elph_set_error("HMC on a sharded lattice: one chain, with R, Rp, Rm and u_accept given (the slab's part of the global vectors); bond "
                            "phonons after elph_shard_hmc_set_columns, without shared fields; a preconditioner needs elph_shard_set_full_lattice with "
@@ -1007,7 +1007,7 @@ extern "C" int elph_langevin_evolve(elph_handle h, int scheme, double dt, int us
         elph_set_error("eta, g1 (g2 beyond Euler, kpm_randn with a preconditioner) are required unless elph_hmc_set_rng was called");
         return ELPH_E_ARG;
     }
-    if (use_precond && !h->kpm_created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
+    if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
     const int nch = st->nch;
     RC(elph_i_ensure_capacity(h, std::max(2, 2 * nch)));
     RC(elph_i_reserve_chains(h, nch));
@@ -1115,7 +1115,7 @@ extern "C" int elph_hmc_special_move_chains(elph_handle h, int kind, const int64
         elph_set_error("Rp, Rm, u_accept (kpm_randn with a preconditioner) are required unless elph_hmc_set_rng was called");
         return ELPH_E_ARG;
     }
-    if (use_precond && !h->kpm_created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
+    if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
     RC(elph_i_ensure_capacity(h, 2 * nch));
     RC(elph_i_reserve_chains(h, nch));
     const size_t nd = (size_t)h->ndim, nfd = (size_t)st->nf * (size_t)h->L;

@@ -1013,23 +1013,22 @@ ModelDev elph_model_dev(const elph_handle_s *h) {
 
 KpmDev elph_kpm_dev(const elph_handle_s *h) {
     KpmDev K;
-    K.active = h->kpm_active;
+    const KpmState &P = h->kpm;
+    const int c = (h->solo_chain >= 0 && P.nch() > 1) ? h->solo_chain : -1;      // (a single re-solve of one chain of several)
+    K.active = P.any_active();
     K.Lo2 = (int)((h->L + 1) / 2);
-    K.lam_avg = h->lam_avg; K.lam_mag = h->lam_mag;
-    K.nchains = h->kpm_nch; K.lam = h->d_klam;
-    K.Ebar = h->d_Ebar; K.cbar = h->d_cbar; K.sbar = h->d_sbar;
-    K.order = h->d_order; K.coff = h->d_coff; K.coeff = h->d_coeff; K.wsched = h->d_wsched; K.desc = h->d_kdesc;
-    K.lp_cbar = h->d_lp_cbar; K.lp_sbar = h->d_lp_sbar;
-    const bool hop_per_chain = (h->kind == ELPH_MODEL_SSH && h->kpm_nch > 1);
-    K.hop_stride = hop_per_chain ? (long long)h->nb : 0;
-    K.lp_hop_stride = hop_per_chain ? (long long)h->lp_ne * ELPH_WAVE : 0;
-    K.sq_stride = hop_per_chain ? 4LL * h->N : 0;
-    if (h->solo_chain >= 0 && h->kpm_nch > 1) {
-        const int c = h->solo_chain;
+    K.lam_avg = P.lam_avg(std::max(c, 0)); K.lam_mag = P.lam_mag(std::max(c, 0));
+    K.nchains = std::max(1, P.nch()); K.lam = P.d_lam;
+    K.Ebar = P.d_Ebar; K.cbar = P.d_cbar; K.sbar = P.d_sbar;
+    K.order = P.d_order; K.coff = P.d_coff; K.coeff = P.d_coeff; K.wsched = P.d_wsched; K.desc = P.d_desc;
+    K.lp_cbar = P.d_lp_cbar; K.lp_sbar = P.d_lp_sbar;
+    K.hop_stride = P.hop_per_chain() ? (long long)h->nb : 0;
+    K.lp_hop_stride = P.hop_per_chain() ? (long long)h->lp_ne * ELPH_WAVE : 0;
+    K.sq_stride = P.hop_per_chain() ? 4LL * h->N : 0;
+    if (c >= 0) {
         K.cbar += (size_t)c * K.hop_stride; K.sbar += (size_t)c * K.hop_stride;
         K.lp_cbar += (size_t)c * K.lp_hop_stride; K.lp_sbar += (size_t)c * K.lp_hop_stride;
         K.nchains = 1;
-        K.lam_avg = h->h_lam[2 * c]; K.lam_mag = h->h_lam[2 * c + 1];
         K.Ebar += (size_t)c * h->N;
         K.order += (size_t)c * K.Lo2; K.coff += (size_t)c * (K.Lo2 + 1); K.wsched += (size_t)c * K.Lo2; K.desc += (size_t)c * K.Lo2;
     }
@@ -1164,7 +1163,7 @@ int elph_launch_cs_bar(elph_handle_s *h, double *cbar_dev, double *sbar_dev, int
 
 // Ē of the first `nch` resident chains in one launch
 int elph_launch_ebar(elph_handle_s *h, int nch) {
-    hipLaunchKernelGGL(k_ebar, dim3((unsigned)((h->N + 63) / 64), (unsigned)nch), dim3(256), 0, h->stream, h->d_Ebar, h->d_E,
+    hipLaunchKernelGGL(k_ebar, dim3((unsigned)((h->N + 63) / 64), (unsigned)nch), dim3(256), 0, h->stream, h->kpm.d_Ebar, h->d_E,
                        (int)h->N, (int)h->L);
     return check_launch("k_ebar");
 }
@@ -1190,8 +1189,8 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
     c.reg_cheb = !no_sq && elph_reg_cheb_form(h) != REG_NONE;
     // p/x-fused (PxFuse, dft_mfma.hip): residual update folded into the forward transform, r.z from the Chebyshev kernel in frequency space
     // (so that beta is known BEFORE the inverse transform), streaming MFMA inverse with the p/x-update in its epilogue
-    if (prec && h->kpm_ready && h->kpm_active && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs)) {
-        if (!h->fast && hol && (h->kpm_hop_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && pg_cheb) {
+    if (prec && h->kpm.ready && h->kpm.any_active() && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs)) {
+        if (!h->fast && hol && (h->kpm.hop_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && pg_cheb) {
             // (round 6) the patch-form lattices of the generic family: k_cg_ap_pg + k_kpm_cheb_pg (pgrid.hip)
             c.px = pg_px_ok && rz2;
         } else if (!h->fast) {
@@ -1201,7 +1200,7 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
         } else if (h->lp_mc != 4) {
             // six-colour lane programs (triangular lattices up to 16 x 16: the geometry of holstein_hmc_triangular.toml) have no fused chunk kernel of
             // their own: their p/x-fused iteration takes the patch-form pair k_cg_ap_pg<PX> + k_kpm_cheb_pg (pgrid::Tri<2, 2>) — round 6
-            c.px = pg_px_ok && hol && h->shape.patch() && h->kpm_hop_uniform && pg_cheb && rz2;
+            c.px = pg_px_ok && hol && h->shape.patch() && h->kpm.hop_uniform && pg_cheb && rz2;
         } else {
             // the four-colour lane programs: r.z in frequency space comes from a register-exchange Chebyshev kernel — or, round 6, from the
             // patch-form one (square L = 18, 20 of this family) or from the Re / Im recursion through the LDS slab (k_kpm_cheb_ri: square L = 22,
@@ -1222,12 +1221,12 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
         // a large even-L square lattice: the patch-layout kernel (pgrid.hip)
         c.ap = (elph_pg_ap_usable(h) && (h->shape.hop_uniform || elph_pg_disorder_ok(h))) ? CgPlan::AP_PG : CgPlan::AP_GEN;
     }
-    c.xr_in_fwd = c.px || (h->fast && h->kpm_active && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs));
+    c.xr_in_fwd = c.px || (h->fast && h->kpm.any_active() && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs));
     c.rz_freq = dot_all && (c.cheb == CgPlan::CH_LANE ? rz2 : c.cheb == CgPlan::CH_PG ? c.px && rz2 : c.px && Lo2 <= nrz);
     // FOLD (dft_mfma.hip: XrFuse): with the residual update in the forward transform and a register-exchange Chebyshev kernel (the one that
     // knows the fold) the frequencies of order 1 — z_w = |c0|^2 r_w — are finished by the forward transform; the Chebyshev kernel keeps
     // their slot bookkeeping only
-    c.fold = h->fast && c.reg_cheb && h->lp_mc == 4 && h->d_kfold && 2 * Lo2 + nct <= nrz && dot_all && elph_dft_mfma_fold_usable(h);
+    c.fold = h->fast && c.reg_cheb && h->lp_mc == 4 && h->kpm.d_fold && 2 * Lo2 + nct <= nrz && dot_all && elph_dft_mfma_fold_usable(h);
     return c;
 }
 
@@ -1239,7 +1238,7 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
     CgBufs B = make_bufs(h, nrhs);
     // kernels that skip finished right-hand sides read the state copy written by the latest k_cg_ap launch
     const CgState *st = cg_mode ? h->d_state + (h->ap_count & 1) : nullptr;
-    if (!h->kpm_active) {
+    if (!h->kpm.any_active()) {
         if (cg_mode) {
             hipLaunchKernelGGL(k_copy_dot, dim3((unsigned)L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, zS, rS, B.rz,
                                B.nrz, N, L, st);
@@ -1258,8 +1257,8 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
     if (!(parts & 1)) {
     } else if (cg_mode == 2) {
         int rcd = elph_dft_mfma_fwd_xr(h, h->d_nu, const_cast<double *>(rS), B.z, B.pap, B.npap, B.rr, B.alpha, N, nrhs, st,
-                                       fold ? h->d_kfold + (h->solo_chain >= 0 && h->kpm_nch > 1 ? 2 * (size_t)h->solo_chain * Lo2 : 0) : nullptr,
-                                       (h->solo_chain >= 0) ? 1 : std::max(1, h->kpm_nch), B.rz, B.nrz, 2 * Lo2);
+                                       fold ? h->kpm.d_fold + (h->solo_chain >= 0 && h->kpm.nch() > 1 ? 2 * (size_t)h->solo_chain * Lo2 : 0) : nullptr,
+                                       (h->solo_chain >= 0) ? 1 : std::max(1, h->kpm.nch()), B.rz, B.nrz, 2 * Lo2);
         if (rcd) return rcd;
     } else {
         int rcd = elph_dft_fwd_twisted(h, h->d_nu, rS, N, nrhs, st);

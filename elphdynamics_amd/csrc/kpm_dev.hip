@@ -306,7 +306,7 @@ __global__ void __launch_bounds__(WAVE) k_kpm_bounds(double *__restrict__ e_out 
 int elph_kpm_bounds_dev(elph_handle_s *h, int nch, const double *d_bstart, double *d_eout) {
     const int N = (int)h->N;
     if (N > 512) return ELPH_E_UNSUPPORTED;
-    int n = h->kpm_n;
+    int n = h->kpm.par.n;
     if (n > N) n = N;
     if (n < 1) n = 1;
     if (n > 64) return ELPH_E_UNSUPPORTED;
@@ -319,14 +319,14 @@ int elph_kpm_bounds_dev(elph_handle_s *h, int nch, const double *d_bstart, doubl
         const size_t extra = (size_t)h->nb * (2 * sizeof(double) + 2 * sizeof(int)) + 16;
         if (h->nb > 0 && shm + extra <= 64 * 1024) { shm += extra; nb_lds = (int)h->nb; }
     }
-    const long long hop_stride = h->kpm_hop_per_chain ? (long long)h->nb : 0;
+    const long long hop_stride = h->kpm.hop_per_chain() ? (long long)h->nb : 0;
     const dim3 grid((unsigned)nch, 2), block(WAVE);
 #define KB_LAUNCH(NPLV)                                                                                                              \
     {                                                                                                                                \
         hipError_t e = hipFuncSetAttribute((const void *)kd::k_kpm_bounds<NPLV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
         if (e != hipSuccess) { elph_set_error("k_kpm_bounds: %s", hipGetErrorString(e)); return ELPH_E_HIP; }                         \
-        hipLaunchKernelGGL((kd::k_kpm_bounds<NPLV>), grid, block, shm, h->stream, d_eout, h->d_Ebar, d_bstart, h->d_bi, h->d_bj,       \
-                           h->d_coloff, h->ncol, h->d_cbar, h->d_sbar, hop_stride, N, n, nch, nb_lds);                                \
+        hipLaunchKernelGGL((kd::k_kpm_bounds<NPLV>), grid, block, shm, h->stream, d_eout, h->kpm.d_Ebar, d_bstart, h->d_bi, h->d_bj,       \
+                           h->d_coloff, h->ncol, h->kpm.d_cbar, h->kpm.d_sbar, hop_stride, N, n, nch, nb_lds);                                \
     }
     switch (npl) {
         case 1: KB_LAUNCH(1); break;

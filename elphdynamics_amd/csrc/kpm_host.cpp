@@ -1,13 +1,15 @@
 // kpm_host.cpp — host-side set-up of the KPM preconditioner (runs once per setup!, not per CG
 // iteration): Arnoldi eigenvalue bounds of A = CBbar diag(Ebar) on N-vectors, the small dense
-// eigen-solve the reference delegates to LAPACK, and the Chebyshev coefficients.
+// eigen-solve the reference delegates to LAPACK, the Chebyshev coefficients, and the plan of every chain's expansion (pure: no handle, no device).
 //
 // Reference: KPMPreconditioners.jl:259-321 (setup!), :387-420 (A, A^-1), :789-839 (coefficients),
 // :845-942 (Arnoldi).  N <= 512 and n <= 20, so this is microseconds of scalar work; the per-iteration
 // apply (ldiv!, :426-481) is on the GPU (kernels.hip).
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <numeric>
 
 #include "elph_internal.h"
 
@@ -196,15 +198,16 @@ int elph_hess_eigvals(std::vector<double> &a, int n, std::vector<double> &wr, st
 }
 
 // KPMPreconditioners.jl:845-942 with the random start vectors supplied by the caller.
-// `chain` selects the configuration's Ē in h->h_Ebar; re-entrant (chains are set up on parallel host threads).
+// `chain` selects the configuration's Ē in h->kpm.h_Ebar; re-entrant (chains are set up on parallel host threads).
 int elph_kpm_arnoldi(const elph_handle_s *h, int chain, const double *b_max, const double *b_min, double *e_min, double *e_max) {
-    const double *Ebar = h->h_Ebar.data() + (size_t)chain * (size_t)h->N;
-    int n = h->kpm_n;
+    const KpmState &K = h->kpm;
+    const double *Ebar = K.h_Ebar.data() + (size_t)chain * (size_t)h->N;
+    int n = K.par.n;
     if (n > h->N) n = (int)h->N;   // :136
     if (n < 1) n = 1;
     // averaged hopping of this chain: one table per chain for SSH chains, one shared table otherwise
-    const size_t hop = (h->h_cbar.size() >= (size_t)(chain + 1) * (size_t)h->nb && h->kpm_hop_per_chain) ? (size_t)chain * (size_t)h->nb : 0;
-    const double *cbar = h->h_cbar.data() + hop, *sbar = h->h_sbar.data() + hop;
+    const size_t hop = K.hop_per_chain() ? (size_t)chain * (size_t)h->nb : 0;
+    const double *cbar = K.h_cbar.data() + hop, *sbar = K.h_sbar.data() + hop;
     const double emax = max_ritz(h, Ebar, n, b_max, false, cbar, sbar);
     const double r = max_ritz(h, Ebar, n, b_min, true, cbar, sbar);
     *e_max = emax;
@@ -238,4 +241,120 @@ void elph_kpm_coefficients(double *c_z, int order, double lam_lo, double lam_hi,
         c_z[2 * m] = f * sr;
         c_z[2 * m + 1] = f * si;
     }
+}
+
+static bool jl_isapprox(double x, double y, double rtol) {
+    return x == y || (std::isfinite(x) && std::isfinite(y) && fabs(x - y) <= rtol * std::max(fabs(x), fabs(y)));
+}
+
+// setup!(P) of one chain for its bounds (KPMPreconditioners.jl:272-318): the acceptance window, and new orders + coefficients when the
+// window moved by more than buf.  An inactive chain keeps its tables (the upload turns them into the identity).
+bool elph_kpm_plan_chain(const KpmParams &p, int L, double e_min, double e_max, KpmChain &C) {
+    const int was = C.active, Lo2 = (L + 1) / 2;
+    const bool fresh = C.fresh;
+    C.fresh = false;
+    C.active = (0.0 < e_min && e_min < 1.0) && (1.0 < e_max) && (e_max - e_min) < 2.0;       // :280 (otherwise inactive, :312-318)
+    const double lo = std::max(0.0, (1 - 2 * p.buf) * e_min), hi = (1 + 2 * p.buf) * e_max;
+    if (!C.active || (jl_isapprox(lo, C.lam_lo, p.buf) && jl_isapprox(hi, C.lam_hi, p.buf))) return fresh || was != C.active;   // :288
+    C.lam_lo = lo; C.lam_hi = hi;
+    int off = 0;
+    std::vector<double> coeff;
+    for (int w = 0; w < Lo2; ++w) {
+        const double phi = 2.0 * M_PI / (double)L * (w + 0.5);                   // ctor :117
+        const int order = std::max(1, (int)floor((hi - lo) * (p.c1 / phi + p.c2)));   // :300
+        C.order[w] = order;
+        coeff.resize(2 * (size_t)(off + order));
+        elph_kpm_coefficients(coeff.data() + 2 * (size_t)off, order, lo, hi, phi);
+        off += order;
+    }
+    C.coeff.swap(coeff);
+    return true;
+}
+
+// The device tables of every chain's expansion.  A chain whose expansion is inactive gets the identity: order 1, c₀ = 1 (ldiv! copies
+// for it, KPMPreconditioners.jl:475-478) and a negative lam_mag (KpmChainView::active).
+KpmTables elph_kpm_tables(int L, const std::vector<KpmChain> &chains) {
+    const int Lo2 = (L + 1) / 2, nch = (int)chains.size();
+    KpmTables T;
+    T.order.assign((size_t)nch * Lo2, 1);
+    T.coff.assign((size_t)nch * (Lo2 + 1), 0);
+    T.wsched.assign((size_t)nch * Lo2, 0);
+    T.desc.assign((size_t)nch * Lo2, KpmDesc());
+    T.fold.assign((size_t)nch * Lo2 * 2, 0.0);
+    T.lam.assign((size_t)nch * 2, 1.0);
+    int off = 0;
+    for (int c = 0; c < nch; ++c) {
+        const KpmChain &C = chains[(size_t)c];
+        int *ord = T.order.data() + (size_t)c * Lo2, *cof = T.coff.data() + (size_t)c * (Lo2 + 1), *ws = T.wsched.data() + (size_t)c * Lo2;
+        int loc = 0, recurse = 0;
+        for (int w = 0; w < Lo2; ++w) {
+            const int o = C.active ? C.order[w] : 1;
+            ord[w] = o;
+            cof[w] = off;
+            if (C.active) T.coeff.insert(T.coeff.end(), C.coeff.begin() + 2 * (size_t)loc, C.coeff.begin() + 2 * (size_t)(loc + o));
+            else { T.coeff.push_back(1.0); T.coeff.push_back(0.0); }
+            loc += C.order[w];
+            off += o;
+            recurse += (o >= 2 || !C.active) ? 1 : 0;
+        }
+        cof[Lo2] = off;
+        T.recurse = std::max(T.recurse, recurse);
+        // schedule: frequency blocks by decreasing order (the low frequencies carry the long recursions)
+        std::iota(ws, ws + Lo2, 0);
+        std::stable_sort(ws, ws + Lo2, [&](int a, int b) { return ord[a] > ord[b]; });
+        for (int y = 0; y < Lo2; ++y) {
+            const int w = ws[y];
+            KpmDesc d;
+            d.w = w; d.order = ord[w]; d.coff = cof[w]; d.pad = 0;
+            d.c0x = T.coeff[2 * (size_t)cof[w]]; d.c0y = T.coeff[2 * (size_t)cof[w] + 1];
+            T.desc[(size_t)c * Lo2 + y] = d;
+            // order-1 fold (active chains only: an identity expansion hands over the r.r partial sums instead, bit for bit)
+            const bool fold = C.active && d.order == 1;
+            const double s1 = fold ? d.c0x * d.c0x + d.c0y * d.c0y : 1.0;
+            const double wgt = ((L & 1) && w == Lo2 - 1) ? 1.0 : 2.0;
+            T.fold[2 * ((size_t)c * Lo2 + w)] = s1;
+            T.fold[2 * ((size_t)c * Lo2 + w) + 1] = fold ? wgt * s1 / (double)L : 0.0;
+        }
+        T.lam[2 * c] = (C.lam_hi + C.lam_lo) / 2;
+        T.lam[2 * c + 1] = C.active ? (C.lam_hi - C.lam_lo) / 2 : -1.0;
+    }
+    return T;
+}
+
+bool elph_kpm_plan(KpmState &K, int L, const double *eb) {
+    bool changed = !K.ready;
+    for (int c = 0; c < K.nch(); ++c) changed |= elph_kpm_plan_chain(K.par, L, eb[2 * (size_t)c], eb[2 * (size_t)c + 1], K.chains[(size_t)c]);
+    if (changed) K.tab = elph_kpm_tables(L, K.chains);
+    return changed;
+}
+
+extern "C" int elph_bench_kpm_plan(int64_t ltau, double buf, double c1, double c2, int nch, int nsteps, const double *e_bounds,
+                                   int *uploaded, int *active, double *lam, int *order, int *coff, int *wsched, double *c0, double *fold,
+                                   double *coeff, int64_t coeff_cap, int64_t *ncoeff) {
+    if (ltau < 1 || nch < 1 || nsteps < 1 || !e_bounds || !(buf >= 0.0)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    const int L = (int)ltau, Lo2 = (L + 1) / 2;
+    KpmState K;      // (host only: the planner touches no device buffer)
+    K.par.buf = buf; K.par.c1 = c1; K.par.c2 = c2;
+    K.chains.assign((size_t)nch, KpmChain(Lo2));
+    for (int s = 0; s < nsteps; ++s) {
+        const bool up = elph_kpm_plan(K, L, e_bounds + (size_t)2 * nch * s);
+        K.ready = true;
+        if (uploaded) uploaded[s] = up;
+    }
+    const KpmTables &T = K.tab;
+    for (int c = 0; c < nch; ++c) {
+        const KpmChain &C = K.chains[(size_t)c];
+        if (active) active[c] = C.active;
+        if (lam) { lam[4 * c] = C.lam_lo; lam[4 * c + 1] = C.lam_hi; lam[4 * c + 2] = T.lam[2 * c]; lam[4 * c + 3] = T.lam[2 * c + 1]; }
+    }
+    if (order) std::copy(T.order.begin(), T.order.end(), order);
+    if (coff) std::copy(T.coff.begin(), T.coff.end(), coff);
+    if (wsched) std::copy(T.wsched.begin(), T.wsched.end(), wsched);
+    if (fold) std::copy(T.fold.begin(), T.fold.end(), fold);
+    if (c0)
+        for (size_t y = 0; y < T.desc.size(); ++y) { c0[2 * y] = T.desc[y].c0x; c0[2 * y + 1] = T.desc[y].c0y; }
+    if (ncoeff) *ncoeff = (int64_t)T.coeff.size();
+    if (coeff && (int64_t)T.coeff.size() > coeff_cap) { elph_set_error("coefficients: %zu doubles, room for %lld", T.coeff.size(), (long long)coeff_cap); return ELPH_E_ARG; }
+    if (coeff) std::copy(T.coeff.begin(), T.coeff.end(), coeff);
+    return ELPH_OK;
 }

@@ -540,13 +540,10 @@ static bool pcg_shape(const elph_handle_s *h, int nrhs, int *Wo, int *Go, int *n
     const char *eo = getenv("ELPH_PCG_WG");
     if (eo && eo[0] == '0') return false;
     if (!(eo && eo[0] == '1') && nrhs < 6) return false;
-    if (!h->fast || h->kind != ELPH_MODEL_HOLSTEIN || h->shape.dpp() != 2 || !h->sq_chain_uniform || h->lp_mc != 4) return false;
-    if (!h->kpm_ready || !h->kpm_active || h->dot_hi != 0 || h->solo_chain >= 0) return false;
-    // (h->kpm_active says that SOME chain's expansion is active; the kernel runs the series of every right-hand side's chain without
-    //  looking at KpmChainView::active, so a chain whose expansion is the identity — lam_mag uploaded as -1, tables unset — keeps the
-    //  whole batch on the streaming form, which hands such a chain z = r)
-    for (int c = 0; c < h->kpm_nch; ++c)
-        if ((size_t)c < h->kpm_chain.size() ? !h->kpm_chain[(size_t)c].active : (h->h_lam.size() > 2 * (size_t)c + 1 && h->h_lam[2 * (size_t)c + 1] <= 0.0)) return false;
+    if (!h->fast || h->kind != ELPH_MODEL_HOLSTEIN || h->shape.dpp() != 2 || !h->kpm.sq_chain_uniform || h->lp_mc != 4) return false;
+    // (the kernel runs the series of every right-hand side's chain without looking at KpmChainView::active, so a chain whose expansion is
+    //  the identity — lam_mag uploaded as -1, tables unset — keeps the whole batch on the streaming form, which hands such a chain z = r)
+    if (!h->kpm.ready || !h->kpm.all_active() || h->dot_hi != 0 || h->solo_chain >= 0) return false;
     if (nrhs < 1 || nrhs > 8) return false;
     const int L = (int)h->L;
     if (L % 2) return false;
@@ -604,7 +601,7 @@ int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_ite
     Pc.rtf = h->mf[0][0].groups * 5; Pc.rti = h->mf[0][1].groups * 5;       // (dft_mfma.hip: MG = 5 row tiles per group)
     Pc.nu = h->d_nu; Pc.zp = h->d_zp;
     Pc.K = elph_kpm_dev(h);
-    Pc.sqc = h->d_sq_cbar; Pc.sqs = h->d_sq_sbar;
+    Pc.sqc = h->kpm.d_sq_cbar; Pc.sqs = h->kpm.d_sq_sbar;
     Pc.Lo2 = (int)((h->L + 1) / 2);
     const size_t HS = 4 * WAVE;
     const size_t shm = std::max((size_t)2 * W * 2 * HS + 48, (size_t)4 * 2 * HS + 16) * sizeof(double);

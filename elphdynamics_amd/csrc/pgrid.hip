@@ -569,7 +569,7 @@ static bool no_pg() {
 
 // Can the per-frequency recursion of this handle run in the patch layout?
 bool elph_pg_cheb_usable(const elph_handle_s *h) {
-    return h->shape.patch() && (h->kpm_hop_uniform || elph_pg_disorder_ok(h)) && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
+    return h->shape.patch() && (h->kpm.hop_uniform || elph_pg_disorder_ok(h)) && h->kind == ELPH_MODEL_HOLSTEIN && !no_pg();
 }
 
 // hopping disorder on this handle's patch shape (square lattices whose (cosh, sinh) table fits the LDS: pgrid::patch_takes_disorder; ELPH_PG_DIS=0:
@@ -592,8 +592,8 @@ int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_p
     int px, py, nw;
     pg_launch_shape(h, nrhs, true, &px, &py, &nw);
     // hopping disorder: the table variants (elph_pg_cheb_usable has checked the shape)
-    if (!h->kpm_hop_uniform && !elph_pg_disorder_ok(h)) { elph_set_error("k_kpm_cheb_pg: hopping disorder on a patch shape without a table variant"); return ELPH_E_UNSUPPORTED; }
-    const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !h->kpm_hop_uniform, [&](auto tag) {
+    if (!h->kpm.hop_uniform && !elph_pg_disorder_ok(h)) { elph_set_error("k_kpm_cheb_pg: hopping disorder on a patch shape without a table variant"); return ELPH_E_UNSUPPORTED; }
+    const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !h->kpm.hop_uniform, [&](auto tag) {
         using LAT = typename decltype(tag)::type;
         hipLaunchKernelGGL((k_kpm_cheb_pg<LAT>), grid, dim3(2 * LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, h->d_nu, K, N, Ls, Lo2, st, rz_part, nrz,
                            (int)h->L, rr_part, h->d_pg_bond);

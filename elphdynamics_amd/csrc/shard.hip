@@ -674,7 +674,7 @@ static int shard_kpm_apply(elph_handle_s *h, elph_handle_s *hf, ShardState *S) {
     if ((rc = launch_ok("k_shard_copy_nu"))) return rc;
     // Chebyshev recursion alone (parts = 2) on the full lattice, in place on hf->d_nu; hf shares this stream.  An inactive expansion
     // (KPMPreconditioners.jl:475-478) is the identity: the spectrum goes back as it came.
-    if (hf->kpm_active && (rc = elph_launch_kpm_apply(hf, hf->d_zp, hf->d_r, 1, 0, 2))) return rc;
+    if (hf->kpm.any_active() && (rc = elph_launch_kpm_apply(hf, hf->d_zp, hf->d_r, 1, 0, 2))) return rc;
     hipLaunchKernelGGL(k_shard_gather_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->d_nu, hf->d_nu, S->d_gsites, Lo2, N, (int)S->n_global);
     if ((rc = launch_ok("k_shard_gather_nu"))) return rc;
     if ((rc = elph_dft_inv_twisted(h, h->d_zp, h->d_nu, N, 1, nullptr, nullptr, nullptr, 0))) return rc;
@@ -690,7 +690,7 @@ static int shard_kpm_core(elph_handle_s *h, elph_handle_s *hfull, ShardState *S,
     if (!S->prepared) { elph_set_error("elph_shard_prepare (and the caller's barrier) must precede every sharded solve"); return ELPH_E_STATE; }
     S->prepared = false;
     if (S->n_global <= 0 || hfull->N != S->n_global || hfull->L != h->L) { elph_set_error("the full-lattice handle does not match the shard's global geometry"); return ELPH_E_ARG; }
-    if (!hfull->kpm_ready) { elph_set_error("elph_kpm_setup has not been called on the full-lattice handle"); return ELPH_E_STATE; }
+    if (!hfull->kpm.ready) { elph_set_error("elph_kpm_setup has not been called on the full-lattice handle"); return ELPH_E_STATE; }
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
     int rc;
     if ((rc = elph_i_ensure_capacity(h, 1)) || (rc = elph_i_ensure_capacity(hfull, 1))) return rc;
