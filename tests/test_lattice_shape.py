@@ -11,12 +11,18 @@ from elphdynamics_amd import _lib, configs, synth
 from elphdynamics_amd import lattice as lat
 
 
+# lattices no recogniser knows: simple cubic, and the three-orbital Lieb lattice (a corner site and the two edge sites of a square cell)
+CUBIC_BONDS = [(1, 1, (1, 0, 0)), (1, 1, (0, 1, 0)), (1, 1, (0, 0, 1))]
+LIEB_BONDS = [(1, 2, (0, 0, 0)), (1, 3, (0, 0, 0)), (2, 1, (1, 0, 0)), (3, 1, (0, 1, 0))]
+
+
 @functools.lru_cache(maxsize=None)
 def tables(kind, norb, Ls, bonds_key, dtau, t_stddev):
     """(nsites, table, cosht, sinht) of a lattice, as HolsteinModel / SSHModel.initialize_model_ build them (configs.make_model's disorder)."""
-    bonds = {"sq": lat.SQUARE_BONDS, "hc": lat.HONEYCOMB_BONDS, "tri": lat.TRIANGULAR_BONDS, "none": []}[bonds_key]
-    L1, L2 = Ls if isinstance(Ls, tuple) else (Ls, Ls if Ls > 1 else 1)
-    la = lat.Lattice(norb, L1, L2, 1)
+    bonds = {"sq": lat.SQUARE_BONDS, "hc": lat.HONEYCOMB_BONDS, "tri": lat.TRIANGULAR_BONDS, "cubic": CUBIC_BONDS, "lieb": LIEB_BONDS,
+             "none": []}[bonds_key]
+    L1, L2, L3 = (Ls + (1,))[:3] if isinstance(Ls, tuple) else (Ls, Ls if Ls > 1 else 1, 1)
+    la = lat.Lattice(norb, L1, L2, L3)
     if not bonds:
         return la.nsites, np.zeros((0, 2), dtype=np.int64), np.zeros(0), np.zeros(0)
     raw = np.concatenate([la.calc_neighbor_table(o1, o2, d) for (o1, o2, d) in bonds], axis=0)
@@ -54,6 +60,13 @@ CASES.update({f"ring_hc{a}x{b}": ("holstein", 2, (a, b), "hc", 0.1, 0.0, False) 
 CASES.update({f"disorder_sq{L}": ("holstein", 1, L, "sq", 0.1, 0.1, False) for L in (8, 16, 20, 28, 30, 32)})
 CASES["disorder_hc12"] = ("holstein", 2, 12, "hc", 0.1, 0.1, False)
 CASES["shuffled_sq16"] = ("holstein", 1, 16, "sq", 0.1, 0.0, True)
+# look-alikes: cubic 4 x 4 x 4 has 3N bonds in 6 colours, the counts of the 8 x 8 triangular lattice (also out of checkerboard order);
+# 4 x 4 x 2 has 5 colours; three orbitals per cell.  None of them is a lattice the register forms know: the generic kernels run.
+CASES["cubic4x4x4"] = ("holstein", 1, (4, 4, 4), "cubic", 0.1, 0.0, False)
+CASES["shuffled_cubic4x4x4"] = ("holstein", 1, (4, 4, 4), "cubic", 0.1, 0.0, True)
+CASES["cubic4x4x2"] = ("holstein", 1, (4, 4, 2), "cubic", 0.1, 0.0, False)
+CASES["lieb4x4"] = ("holstein", 3, (4, 4), "lieb", 0.1, 0.0, False)
+NOT_RECOGNISED = (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0)      # kind NONE: one wavefront, uniform hopping, no bond map
 
 # (slots: _lib.LATTICE_SHAPE_SLOTS)
 EXPECTED = {
@@ -138,6 +151,7 @@ EXPECTED = {
     'y': (0, 0, 0, 6, 6, 0, 0, 0, 0, 0, 1, 0, 0, 2, 1, 0),
     'z': (0, 0, 0, 10, 10, 0, 0, 0, 0, 0, 1, 0, 0, 4, 1, 0),
 }
+EXPECTED.update({case: NOT_RECOGNISED for case in ("cubic4x4x4", "shuffled_cubic4x4x4", "cubic4x4x2", "lieb4x4")})
 EXPECTED_NO_MW = {      # where ELPH_PG_MW=0 changes the result
     'H27': (0, 0, 0, 27, 27, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0),
     'L26': (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0),
@@ -154,6 +168,18 @@ EXPECTED_NO_MW = {      # where ELPH_PG_MW=0 changes the result
     'l48': (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0),
     'l64': (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0),
 }
+
+
+def test_cubic_look_alike_has_the_triangular_counts():
+    """The cubic 4 x 4 x 4 table really reaches match_triangular: 3N bonds, 6 colours, N = 8 x 8 (4 x 4 x 2: 5 colours)."""
+    n, tab, c, s = tables("holstein", 1, (4, 4, 4), "cubic", 0.1, 0.0)
+    assert n == 64 and tab.shape[0] == 3 * n
+    la = lat.Lattice(1, 4, 4, 4)
+    raw = np.concatenate([la.calc_neighbor_table(o1, o2, d) for (o1, o2, d) in CUBIC_BONDS], axis=0)
+    assert lat.initialize_checkerboard(raw)["ncolours"] == 6
+    la = lat.Lattice(1, 4, 4, 2)
+    raw = np.concatenate([la.calc_neighbor_table(o1, o2, d) for (o1, o2, d) in CUBIC_BONDS], axis=0)
+    assert lat.initialize_checkerboard(raw)["ncolours"] == 5
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
