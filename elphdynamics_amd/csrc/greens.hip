@@ -188,6 +188,7 @@ size_t spatial_lds_bytes(const elph_handle_s *h, const GreensState *g) { return 
 }  // namespace
 
 void elph_greens_free(elph_handle_s *h) {
+    elph_meas_free(h);                     // the measurement accumulators are shaped by the estimator
     GreensState *g = gs_of(h);
     if (!g) return;
     void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};
@@ -322,10 +323,9 @@ extern "C" int elph_greens_get_vectors(elph_handle h, double *R, double *MinvR) 
     return ELPH_OK;
 }
 
-// setup!(estimator, n₁, n₂) — n₁, n₂ 1-based.  Each output (NULL = not copied back) is Complex[2L, n_s, n_s, L1, L2, L3],
-// interleaved re/im, first index fastest.  The arrays also stay on the device (elph_greens_dev_arrays).
-extern "C" int elph_greens_setup(elph_handle h, int n1, int n2, double *GD0, double *GD0_GD0, double *GDD_G00, double *GD0_G0D) {
-    CHECK_H(h);
+// The device part of setup!(estimator, n₁, n₂): the four correlations C[c][Δτ < L][s₂ + n_s (s₁ + n_s cell)] (real) and, with `expand`,
+// their doubled complex copies in the reference's shape.  Stream-ordered: no copy to the host, no synchronisation.
+int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand) {
     RC(need_greens(h));
     GreensState *g = gs_of(h);
     if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
@@ -351,10 +351,48 @@ extern "C" int elph_greens_setup(elph_handle h, int n1, int n2, double *GD0, dou
     RC(elph_dft_inv_twisted(h, g->C, g->Y, ncol, 1, nullptr, nullptr, nullptr, 0));
     // the plain inverse walks [rhs][Lh][ncol] spectra and writes [rhs][L][ncol]
     RC(elph_dft_inv_plain(h, g->C + (size_t)L * ncol, g->Y + ystride, ncol, 3));
-    hipLaunchKernelGGL(k_gr_out, dim3((unsigned)((ncol + 31) / 32), (unsigned)((L + 31) / 32), 4), dim3(TPB), 0, h->stream, g->out, g->C, L,
-                       ncol);
-    RC(gr_check("k_gr_out"));
-    const size_t cnt = 2 * (size_t)L * ncol;   // complex numbers per array
+    if (expand) {
+        hipLaunchKernelGGL(k_gr_out, dim3((unsigned)((ncol + 31) / 32), (unsigned)((L + 31) / 32), 4), dim3(TPB), 0, h->stream, g->out, g->C, L,
+                           ncol);
+        RC(gr_check("k_gr_out"));
+    }
+    return ELPH_OK;
+}
+
+// What measure.hip reads of the estimator (device pointers stay owned by it).
+int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
+    RC(need_greens(h));
+    const GreensState *g = gs_of(h);
+    v->ns = g->ns; v->L1 = g->L1; v->L2 = g->L2; v->L3 = g->L3; v->nc = g->nc; v->nv = g->nv;
+    v->have_vectors = g->have_vectors;
+    v->R = g->R; v->X = g->X; v->C = g->C;
+    return ELPH_OK;
+}
+
+// translational_average! (Utilities.jl:49-60) of a real field periodic in τ with itself, every orbital pair at once:
+//   outS[Δτ][a + n_s (b + n_s Δcell)] = 1/(L Nc) Σ_{τ, cell} v[τ + Δτ][a, cell + Δcell] · v[τ][b, cell]      (vS, outS: layout S)
+// — the plain-spectrum branch of setup! with both spectra that of v.  Uses the estimator's ν, Y scratch: call it before, not between,
+// elph_i_greens_setup_dev and what reads its C.
+int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS) {
+    RC(need_greens(h));
+    GreensState *g = gs_of(h);
+    const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N;
+    RC(elph_dft_fwd_plain(h, g->nuP, vS, N, 1));
+    const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
+    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 1), dim3(TPB), spatial_lds_bytes(h, g), h->stream, g->Y, g->nuP, g->nuP, Lh, N, ns,
+                       g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
+    RC(gr_check("k_gr_spatial(autocorrelation)"));
+    RC(elph_dft_inv_plain(h, outS, g->Y, ncol, 1));
+    return ELPH_OK;
+}
+
+// setup!(estimator, n₁, n₂) — n₁, n₂ 1-based.  Each output (NULL = not copied back) is Complex[2L, n_s, n_s, L1, L2, L3],
+// interleaved re/im, first index fastest.  The arrays also stay on the device (elph_greens_dev_arrays).
+extern "C" int elph_greens_setup(elph_handle h, int n1, int n2, double *GD0, double *GD0_GD0, double *GDD_G00, double *GD0_G0D) {
+    CHECK_H(h);
+    RC(elph_i_greens_setup_dev(h, n1, n2, true));
+    GreensState *g = gs_of(h);
+    const size_t cnt = 2 * (size_t)h->L * (size_t)g->ns * (size_t)h->N;   // complex numbers per array
     // order of the device arrays: 0 GΔ0, 1 GΔ0·GΔ0, 2 GΔΔ·G00, 3 GΔ0·G0Δ (fields 0/1, 2/3, 4/5, 6/7)
     double *outs[4] = {GD0, GD0_GD0, GDD_G00, GD0_G0D};
     for (int c = 0; c < 4; ++c)

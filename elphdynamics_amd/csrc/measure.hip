@@ -1,0 +1,448 @@
+// measure.hip — the Holstein measurements of Measurements.jl accumulated on the device (DESIGN.md "Measurements on the device"):
+//   make_measurements!            Measurements.jl:545-566   (without its update!: the estimator's vectors are there already)
+//     make_global_measurements!   :845-861, :1283-1312      density, Nsqr, mu
+//     make_onsite_measurements!   :916-976                  density, double_occ, x, x2, x4, phonon_pe, phonon_ke, elph_energy, mu per orbital
+//     make_intersite_measurements! :1029-1070               el_ke per bond definition
+//     measure_Greens! / _DenDen! / _SpinSpin! / _PairGreens! / _PhononGreens!   :1469-1650
+//   reset_measurements!           :698-758
+// Everything the reference adds up is real, so every accumulator is a double; the complex arrays of the reference appear when
+// elph_meas_fetch copies out.  One allocation holds [scalars | Greens | DenDen | SpinSpin | PairGreens | PhononGreens]: reset is one
+// memset, fetch one copy.
+//
+// Reductions have ONE order, whatever the device does: a thread walks its cells in index order, the 64 lanes of a wave fold by halves
+// (shuffles), the waves of a workgroup are added in index order through LDS, each workgroup (= one time slice) writes one partial, and
+// a single workgroup adds the L partials in slice order and updates the accumulator.  No floating-point atomics anywhere: the same
+// inputs give the same bits.
+//
+// Layouts: vectors in layout S (element (tau, site) at tau * N + site, orbital = site % n_s, cell = site / n_s); the estimator's real
+// correlations C[c][tau < L][s2 + n_s (s1 + n_s cell)], c = 0 G[D,0], 1 G[D,0] G[D,0], 2 G[D,D] G[0,0], 3 G[D,0] G[0,D], so that
+// measure_*(l, o1, o2, tau) (GreensFunctions.jl:293-329) is C[c][tau][(o2 - 1) + n_s ((o1 - 1) + n_s cell(l))]; a correlation accumulator
+// is [L0][L1][L2][L3][n_p], first index fastest, L0 = L + 1 (time-dependent) or 1 (equal-time).
+
+#include <vector>
+
+#include "elph_internal.h"
+
+#define RC(call)                \
+    do {                        \
+        int _rc = (call);       \
+        if (_rc) return _rc;    \
+    } while (0)
+
+#define CHECK_H(h)                                                    \
+    do {                                                              \
+        if (!(h)) { elph_set_error("null handle"); return ELPH_E_ARG; } \
+        HIPCHK(hipSetDevice((h)->device));                            \
+    } while (0)
+
+namespace {
+
+constexpr int TPB = 256;
+constexpr int NWAVE = TPB / ELPH_WAVE;
+constexpr int NCORR = 5;
+const char *const CORR_NAMES[NCORR] = {"Greens", "DenDen", "SpinSpin", "PairGreens", "PhononGreens"};
+enum { GREENS = 0, DENDEN = 1, SPINSPIN = 2, PAIRGREENS = 3, PHONONGREENS = 4 };
+constexpr int NONSITE = 9;      // density, double_occ, x, x2, x4, phonon_pe, phonon_ke, elph_energy, mu
+constexpr int NXONLY = 6;       // x, x2, x4, phonon_pe, phonon_ke, mu: functions of the field alone
+
+struct FoldReq {                // by value into k_ms_fold
+    double *acc[NCORR];
+    const int *pairs[NCORR];    // [np][2] 0-based (o1, o2)
+    int np[NCORR], L0[NCORR];   // np = 0: not measured
+};
+
+struct MeasState {
+    int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, ndef = 0;
+    int64_t nbonds = 0;
+    double dtau = 0.0, mu_mean = 0.0;
+    double *par = nullptr;          // [4][N] omega, omega4, lambda, mu
+    int *bs = nullptr;              // [2][nbonds] 0-based sites of every bond, the reference's bond order
+    double *bt = nullptr;           // [nbonds]
+    int *pairs = nullptr;           // all requests' pairs, concatenated
+    double *acc = nullptr;          // [nsc | the measured correlations]
+    size_t nacc = 0, off[NCORR] = {};
+    int nsc = 0;
+    double *x = nullptr;            // [ndim] the field, layout S
+    double *ph = nullptr;           // [L][ns*N] the field's translation average (PhononGreens requested)
+    double *xs = nullptr;           // [NXONLY][ns] the field-only on-site terms of this accumulate, normalised
+    double *part = nullptr;         // [L][max(nq, NXONLY*ns)] one partial per workgroup
+    FoldReq req{};
+    size_t fold_max = 0;            // threads of the largest fold
+};
+
+MeasState *ms_of(elph_handle_s *h) { return (MeasState *)h->meas; }
+
+int ms_check(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
+    return ELPH_OK;
+}
+
+// Sum over the workgroup in a fixed order; the result is valid on thread 0.  red: NWAVE doubles of LDS.
+__device__ __forceinline__ double block_sum(double v, double *red) {
+    for (int off = ELPH_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, ELPH_WAVE);
+    __syncthreads();                                   // the previous call's readers are done with red
+    if ((threadIdx.x & (ELPH_WAVE - 1)) == 0) red[threadIdx.x / ELPH_WAVE] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < NWAVE; ++w) s += red[w];
+    return s;
+}
+
+// The field-only on-site terms (Measurements.jl:955-970), one workgroup per time slice: part[t][o * NXONLY + k].
+__global__ void __launch_bounds__(TPB) k_ms_x(double *__restrict__ part, const double *__restrict__ x, const double *__restrict__ par, int N,
+                                              int L, int ns, int nc, double dtau) {
+    __shared__ double red[NWAVE];
+    const int t = blockIdx.x, tn = (t + 1 == L) ? 0 : t + 1;
+    const double *xt = x + (size_t)t * N, *xn = x + (size_t)tn * N;
+    const double *om = par, *om4 = par + N, *mu = par + 3 * (size_t)N;
+    for (int o = 0; o < ns; ++o) {
+        double a[NXONLY] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int c = threadIdx.x; c < nc; c += TPB) {
+            const int i = c * ns + o;
+            const double xi = xt[i], dx = xn[i] - xi, x2 = xi * xi, x4 = x2 * x2;
+            a[0] += xi;
+            a[1] += x2;
+            a[2] += x4;
+            a[3] += om[i] * om[i] * x2 / 2 + om4[i] * x4;
+            a[4] += 0.5 / dtau - dx * dx / (dtau * dtau) / 2;
+            a[5] += mu[i];
+        }
+        for (int k = 0; k < NXONLY; ++k) {
+            const double s = block_sum(a[k], red);
+            if (threadIdx.x == 0) part[(size_t)t * NXONLY * ns + o * NXONLY + k] = s;
+        }
+    }
+}
+
+// xs[k][o] = (sum of the slices' partials in slice order) / (Nc L)
+__global__ void __launch_bounds__(TPB) k_ms_x_finish(double *__restrict__ xs, const double *__restrict__ part, int L, int ns, double norm) {
+    const int nq = NXONLY * ns;
+    for (int q = threadIdx.x; q < nq; q += TPB) {
+        double s = 0.0;
+        for (int t = 0; t < L; ++t) s += part[(size_t)t * nq + q];
+        const int o = q / NXONLY, k = q % NXONLY;
+        xs[k * ns + o] = s / norm;
+    }
+}
+
+// The terms of one pair of vectors that need the estimate (Measurements.jl:949-962, :1056-1064, :1287-1288), one workgroup per slice.
+// part[t][q]: q = 3 o + {density, double_occ, elph_energy}; 3 n_s + {dot(M^-1 r1, r1), dot(M^-1 r2, r2)}; 3 n_s + 2 + bond definition.
+__global__ void __launch_bounds__(TPB) k_ms_pair(double *__restrict__ part, const double *__restrict__ X1, const double *__restrict__ X2,
+                                                 const double *__restrict__ R1, const double *__restrict__ R2, const double *__restrict__ x,
+                                                 const double *__restrict__ lam, const int *__restrict__ bs, const double *__restrict__ bt,
+                                                 int N, int ns, int nc, int ndef, long long nbonds) {
+    __shared__ double red[NWAVE];
+    const int t = blockIdx.x, nq = 3 * ns + 2 + ndef;
+    const size_t o0 = (size_t)t * N;
+    const double *a1 = X1 + o0, *a2 = X2 + o0, *b1 = R1 + o0, *b2 = R2 + o0, *xt = x + o0;
+    double *out = part + (size_t)t * nq;
+    double d1 = 0.0, d2 = 0.0;
+    for (int o = 0; o < ns; ++o) {
+        double den = 0.0, docc = 0.0, eph = 0.0, g1s = 0.0, g2s = 0.0;
+        for (int c = threadIdx.x; c < nc; c += TPB) {
+            const int i = c * ns + o;
+            const double G1 = a1[i] * b1[i], G2 = a2[i] * b2[i];
+            den += (1.0 - G1) + (1.0 - G2);
+            docc += (1.0 - G1) * (1.0 - G2);
+            eph += lam[i] * xt[i] * (2.0 - G1 - G2);
+            g1s += G1;
+            g2s += G2;
+        }
+        double s = block_sum(den, red);
+        if (threadIdx.x == 0) out[3 * o] = s;
+        s = block_sum(docc, red);
+        if (threadIdx.x == 0) out[3 * o + 1] = s;
+        s = block_sum(eph, red);
+        if (threadIdx.x == 0) out[3 * o + 2] = s;
+        d1 += block_sum(g1s, red);                     // thread 0: orbitals in index order
+        d2 += block_sum(g2s, red);
+    }
+    if (threadIdx.x == 0) { out[3 * ns] = d1; out[3 * ns + 1] = d2; }
+    for (int d = 0; d < ndef; ++d) {
+        double ke = 0.0;
+        for (int c = threadIdx.x; c < nc; c += TPB) {
+            const long long b = (long long)d * nc + c;
+            const int s1 = bs[b], s2 = bs[nbonds + b];
+            // -t h, h = -(G1 + G2 + G3 + G4)
+            ke += bt[b] * (a1[s1] * b1[s2] + a1[s2] * b1[s1] + a2[s1] * b2[s2] + a2[s2] * b2[s1]);
+        }
+        const double s = block_sum(ke, red);
+        if (threadIdx.x == 0) out[3 * ns + 2 + d] = s;
+    }
+}
+
+// One workgroup: the slices' partials in slice order, the tau = 0 slice of G[D,0] G[0,D] for Nsqr, then every scalar accumulator of
+// this pair.  acc: [density, Nsqr, mu | NONSITE x n_s | ndef].
+__global__ void __launch_bounds__(TPB) k_ms_finish(double *__restrict__ acc, const double *__restrict__ part, const double *__restrict__ xs,
+                                                   const double *__restrict__ C3, int N, int L, int ns, int nc, int ndef, double mu_mean) {
+    extern __shared__ double tot[];                    // [nq] + red[NWAVE]
+    const int nq = 3 * ns + 2 + ndef, ncol = ns * N;
+    double *red = tot + nq;
+    for (int q = threadIdx.x; q < nq; q += TPB) {
+        double s = 0.0;
+        for (int t = 0; t < L; ++t) s += part[(size_t)t * nq + q];
+        tot[q] = s;
+    }
+    double g = 0.0;
+    for (int i = threadIdx.x; i < ncol; i += TPB) g += C3[i];
+    const double sumG = block_sum(g, red);             // (its barriers also publish tot)
+    const double norm = (double)nc * (double)L;
+    if (threadIdx.x == 0) {
+        const double Nd = (double)N;
+        const double Tr1 = tot[3 * ns] / L, Tr2 = tot[3 * ns + 1] / L;
+        const double N1 = 2 * (Nd - Tr1), N2 = 2 * (Nd - Tr2);
+        acc[0] += (N1 + N2) / (2 * Nd);
+        acc[1] += N1 * N2 + Tr1 + Tr2 - 2 * (Nd / ns) * sumG;
+        acc[2] += mu_mean;
+    }
+    double *on = acc + 3;
+    for (int o = threadIdx.x; o < ns; o += TPB) {
+        on[0 * ns + o] += tot[3 * o] / norm;
+        on[1 * ns + o] += tot[3 * o + 1] / norm;
+        on[2 * ns + o] += xs[0 * ns + o];
+        on[3 * ns + o] += xs[1 * ns + o];
+        on[4 * ns + o] += xs[2 * ns + o];
+        on[5 * ns + o] += xs[3 * ns + o];
+        on[6 * ns + o] += xs[4 * ns + o];
+        on[7 * ns + o] += tot[3 * o + 2] / norm;
+        on[8 * ns + o] += xs[5 * ns + o];
+    }
+    for (int d = threadIdx.x; d < ndef; d += TPB) acc[3 + NONSITE * ns + d] += tot[3 * ns + 2 + d] / norm;
+}
+
+// One thread per (tau, cell, listed pair) of correlation blockIdx.y (Measurements.jl:1469-1650).  C: the estimator's four real tables of
+// this pair; ph: the field's translation average.
+__global__ void __launch_bounds__(TPB) k_ms_fold(FoldReq rq, const double *__restrict__ C, const double *__restrict__ ph, int N, int L, int ns,
+                                                 int L1, int L2, int L3) {
+    const int which = blockIdx.y, np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
+    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (idx >= (long long)L0 * nc * np) return;
+    int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc);
+    const int p = (int)(idx / ((long long)L0 * nc));
+    int o1 = rq.pairs[which][2 * p], o2 = rq.pairs[which][2 * p + 1];
+    const size_t ncol = (size_t)ns * N, tab = (size_t)L * ncol;
+    const bool beta = (tau == L);
+    double v;
+    if (which == PHONONGREENS) {
+        // x1x2[D] = 1/(L Nc) sum x_o1[. + D] x_o2[.]; slice L is slice 0
+        v = ph[(size_t)(beta ? 0 : tau) * ncol + o1 + ns * (o2 + ns * cell)];
+    } else if (which == SPINSPIN) {
+        if (beta) {                                    // <s(i+r, beta) s(i, 0)> = <s(i-r, 0) s(i, 0)>, orbitals swapped
+            tau = 0;
+            const int l1 = cell % L1, l2 = (cell / L1) % L2, l3 = cell / (L1 * L2);
+            cell = ((L1 - l1) % L1) + L1 * (((L2 - l2) % L2) + L2 * ((L3 - l3) % L3));
+            const int s = o1; o1 = o2; o2 = s;
+        }
+        const size_t e = (size_t)tau * ncol + o2 + ns * (o1 + ns * cell);
+        v = -2 * C[3 * tab + e];
+        if (cell == 0 && o1 == o2 && tau == 0) v += 2 * C[e];
+    } else {
+        const int tm = beta ? 0 : tau;                 // tau % L
+        const size_t e = (size_t)tm * ncol + o2 + ns * (o1 + ns * cell);
+        const bool diag = (cell == 0 && o1 == o2);
+        if (which == GREENS) {
+            v = C[e];
+            if (beta) v = (diag ? 1.0 : 0.0) - v;      // G_r(beta) = delta_r - G_r(0)
+        } else if (which == DENDEN) {
+            const double G00 = C[o1 + ns * o1], Grr = C[o2 + ns * o2];      // tau = 0, r = 0 diagonal entries
+            double h = -C[3 * tab + e];
+            if (diag && tm == 0) h += C[e];
+            v = 4.0 * (1.0 - Grr - G00 + C[2 * tab + e] + 0.5 * h);
+        } else {                                       // PAIRGREENS
+            v = C[tab + e];
+            if (beta && diag) v = v + 1.0 - 2 * C[o1 + ns * o1];            // P_r(beta) = P_r(0) + delta_r (1 - 2 G_0(0))
+        }
+    }
+    rq.acc[which][idx] += v;
+}
+
+template <class T>
+int ms_alloc(T **p, size_t n) {
+    HIPCHK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
+    return ELPH_OK;
+}
+
+int need_meas(elph_handle_s *h) {
+    if (!h->meas) { elph_set_error("elph_meas_create has not been called"); return ELPH_E_STATE; }
+    return ELPH_OK;
+}
+
+int refuse_chains(elph_handle_s *h) {
+    if (h->nchains > 1) {
+        elph_set_error("measurements: %d chains are resident in this handle; one configuration per handle is measured", h->nchains);
+        return ELPH_E_UNSUPPORTED;
+    }
+    return ELPH_OK;
+}
+
+}  // namespace
+
+void elph_meas_free(elph_handle_s *h) {
+    MeasState *m = ms_of(h);
+    if (!m) return;
+    void *ptrs[] = {m->par, m->bs, m->bt, m->pairs, m->acc, m->x, m->ph, m->xs, m->part};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete m;
+    h->meas = nullptr;
+}
+
+extern "C" int elph_meas_create(elph_handle h, const double *omega, const double *omega4, const double *lambda, const double *mu, double dtau,
+                                int64_t nbonds, int ndef, const int64_t *bond_sites, const double *bond_t, const int *measure,
+                                const int *time_dependent, const int *npairs, const int *pairs) {
+    CHECK_H(h);
+    elph_meas_free(h);
+    if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("measurements: the SSH model is not supported (Holstein only)"); return ELPH_E_UNSUPPORTED; }
+    if (h->shard || h->is_slab) { elph_set_error("measurements: sharded and slab handles are not supported"); return ELPH_E_UNSUPPORTED; }
+    RC(refuse_chains(h));
+    ElphGreensView g;
+    RC(elph_i_greens_view(h, &g));
+    if (!omega || !omega4 || !lambda || !mu || !measure || !time_dependent || !npairs) { elph_set_error("measurements: a null parameter array"); return ELPH_E_ARG; }
+    if (!(dtau > 0.0)) { elph_set_error("measurements: dtau = %g", dtau); return ELPH_E_ARG; }
+    const int N = (int)h->N, L = (int)h->L, ns = g.ns, nc = g.nc;
+    if (ndef < 0 || nbonds != (int64_t)ndef * nc || (nbonds > 0 && (!bond_sites || !bond_t))) {
+        elph_set_error("measurements: %lld bonds are not %d bond definitions x %d cells (bond = (definition - 1) * ncells + cell)", (long long)nbonds,
+                       ndef, nc);
+        return ELPH_E_ARG;
+    }
+    std::vector<int> bs(2 * (size_t)nbonds);
+    for (int64_t b = 0; b < nbonds; ++b)
+        for (int k = 0; k < 2; ++k) {
+            const int64_t s = bond_sites[2 * b + k];
+            if (s < 1 || s > N) { elph_set_error("measurements: bond %lld joins site %lld, outside 1..%d", (long long)b + 1, (long long)s, N); return ELPH_E_ARG; }
+            bs[(size_t)k * nbonds + b] = (int)(s - 1);
+        }
+    std::vector<int> prs;
+    size_t at = 0, total = 0;
+    MeasState tmp;                                     // request bookkeeping before anything is allocated
+    tmp.nsc = 3 + NONSITE * ns + ndef;
+    total = (size_t)tmp.nsc;
+    std::vector<size_t> pair_off(NCORR, 0);
+    for (int c = 0; c < NCORR; ++c) {
+        tmp.req.np[c] = 0; tmp.req.L0[c] = 1;
+        if (!measure[c]) continue;
+        if (npairs[c] < 1 || !pairs) { elph_set_error("measurements: %s is requested with no orbital pair", CORR_NAMES[c]); return ELPH_E_ARG; }
+        for (int p = 0; p < npairs[c]; ++p)
+            for (int k = 0; k < 2; ++k) {
+                const int o = pairs[2 * (at + p) + k];
+                if (o < 1 || o > ns) {
+                    elph_set_error("measurements: %s pair %d names orbital %d, outside 1..%d", CORR_NAMES[c], p + 1, o, ns);
+                    return ELPH_E_ARG;
+                }
+                prs.push_back(o - 1);
+            }
+        pair_off[c] = 2 * at;
+        at += (size_t)npairs[c];
+        tmp.req.np[c] = npairs[c];
+        tmp.req.L0[c] = time_dependent[c] ? L + 1 : 1;
+        tmp.off[c] = total;
+        const size_t cnt = (size_t)tmp.req.L0[c] * nc * npairs[c];
+        total += cnt;
+        tmp.fold_max = std::max(tmp.fold_max, cnt);
+    }
+    MeasState *m = new MeasState(tmp);
+    h->meas = m;
+    m->ns = ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = ndef; m->nbonds = nbonds; m->dtau = dtau;
+    m->nacc = total;
+    double mus = 0.0;
+    for (int i = 0; i < N; ++i) mus += mu[i];
+    m->mu_mean = mus / N;                              // mean(model.mu), :858
+    const int nq = std::max(3 * ns + 2 + ndef, NXONLY * ns);
+    int rc = ELPH_OK;
+    auto ok = [&](int r) { if (rc == ELPH_OK) rc = r; return rc == ELPH_OK; };
+    const bool allocated = ok(ms_alloc(&m->par, 4 * (size_t)N)) && ok(ms_alloc(&m->bs, 2 * (size_t)nbonds)) && ok(ms_alloc(&m->bt, (size_t)nbonds)) &&
+        ok(ms_alloc(&m->pairs, prs.size())) && ok(ms_alloc(&m->acc, total)) && ok(ms_alloc(&m->x, (size_t)h->ndim)) &&
+        ok(ms_alloc(&m->xs, (size_t)NXONLY * ns)) && ok(ms_alloc(&m->part, (size_t)L * nq)) &&
+        (m->req.np[PHONONGREENS] == 0 || ok(ms_alloc(&m->ph, (size_t)L * ns * N)));
+    if (!allocated || rc != ELPH_OK) { elph_meas_free(h); return rc; }
+    auto up = [&](void *dst, const void *src, size_t bytes) -> int {
+        if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return ELPH_OK;
+    };
+    const double *pp[4] = {omega, omega4, lambda, mu};
+    for (int k = 0; k < 4; ++k) ok(up(m->par + (size_t)k * N, pp[k], (size_t)N * sizeof(double)));
+    ok(up(m->bs, bs.data(), bs.size() * sizeof(int)));
+    ok(up(m->bt, bond_t, (size_t)nbonds * sizeof(double)));
+    ok(up(m->pairs, prs.data(), prs.size() * sizeof(int)));
+    if (rc == ELPH_OK && hipMemset(m->acc, 0, total * sizeof(double)) != hipSuccess) { elph_set_error("measurements: hipMemset failed"); rc = ELPH_E_HIP; }
+    if (rc != ELPH_OK) { elph_meas_free(h); return rc; }
+    for (int c = 0; c < NCORR; ++c) {
+        m->req.acc[c] = m->acc + m->off[c];
+        m->req.pairs[c] = m->pairs + pair_off[c];
+    }
+    return ELPH_OK;
+}
+
+extern "C" int elph_meas_accumulate(elph_handle h, const double *x) {
+    CHECK_H(h);
+    RC(need_meas(h));
+    RC(refuse_chains(h));
+    if (!x) { elph_set_error("x is null"); return ELPH_E_ARG; }
+    MeasState *m = ms_of(h);
+    ElphGreensView g;
+    RC(elph_i_greens_view(h, &g));
+    if (!g.have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
+    const int N = (int)h->N, L = (int)h->L, ns = m->ns, nc = m->nc, nv = g.nv;
+    const size_t nd = (size_t)h->ndim;
+    RC(elph_i_ensure_capacity(h, 1));
+    HIPCHK(hipMemcpyAsync(h->d_stage_in, x, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RC(elph_launch_r2s(h, m->x, h->d_stage_in, 1));
+    // what depends on the field alone: once per call, added once per pair below (the reference's loop recomputes it per pair)
+    hipLaunchKernelGGL(k_ms_x, dim3((unsigned)L), dim3(TPB), 0, h->stream, m->part, m->x, m->par, N, L, ns, nc, m->dtau);
+    RC(ms_check("k_ms_x"));
+    hipLaunchKernelGGL(k_ms_x_finish, dim3(1), dim3(TPB), 0, h->stream, m->xs, m->part, L, ns, (double)nc * (double)L);
+    RC(ms_check("k_ms_x_finish"));
+    if (m->req.np[PHONONGREENS]) RC(elph_i_greens_autocorr_dev(h, m->ph, m->x));
+    const int nq = 3 * ns + 2 + m->ndef;
+    const size_t shm = ((size_t)nq + NWAVE) * sizeof(double);
+    const size_t tab = (size_t)L * ns * N;
+    for (int i = 1; i < nv; ++i)
+        for (int j = i + 1; j <= nv; ++j) {
+            // the doubled complex copies of the tables are refreshed for the last pair only (elph_greens_dev_arrays)
+            RC(elph_i_greens_setup_dev(h, i, j, i == nv - 1));
+            const double *X1 = g.X + (size_t)(i - 1) * nd, *X2 = g.X + (size_t)(j - 1) * nd;
+            const double *R1 = g.R + (size_t)(i - 1) * nd, *R2 = g.R + (size_t)(j - 1) * nd;
+            hipLaunchKernelGGL(k_ms_pair, dim3((unsigned)L), dim3(TPB), 0, h->stream, m->part, X1, X2, R1, R2, m->x, m->par + 2 * (size_t)N, m->bs,
+                               m->bt, N, ns, nc, m->ndef, (long long)m->nbonds);
+            RC(ms_check("k_ms_pair"));
+            hipLaunchKernelGGL(k_ms_finish, dim3(1), dim3(TPB), shm, h->stream, m->acc, m->part, m->xs, g.C + 3 * tab, N, L, ns, nc, m->ndef,
+                               m->mu_mean);
+            RC(ms_check("k_ms_finish"));
+            if (m->fold_max) {
+                hipLaunchKernelGGL(k_ms_fold, dim3((unsigned)((m->fold_max + TPB - 1) / TPB), NCORR), dim3(TPB), 0, h->stream, m->req, g.C, m->ph, N,
+                                   L, ns, m->L1, m->L2, m->L3);
+                RC(ms_check("k_ms_fold"));
+            }
+        }
+    HIPCHK(hipStreamSynchronize(h->stream));           // x (a host pointer) is not retained after return
+    return ELPH_OK;
+}
+
+extern "C" int elph_meas_fetch(elph_handle h, double *scalars, double *Greens, double *DenDen, double *SpinSpin, double *PairGreens,
+                               double *PhononGreens) {
+    CHECK_H(h);
+    RC(need_meas(h));
+    MeasState *m = ms_of(h);
+    std::vector<double> host(m->nacc);
+    HIPCHK(hipMemcpyAsync(host.data(), m->acc, m->nacc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (scalars)
+        for (int i = 0; i < m->nsc; ++i) scalars[i] = host[(size_t)i];
+    double *outs[NCORR] = {Greens, DenDen, SpinSpin, PairGreens, PhononGreens};
+    for (int c = 0; c < NCORR; ++c) {
+        if (!outs[c] || !m->req.np[c]) continue;
+        const size_t cnt = (size_t)m->req.L0[c] * m->nc * m->req.np[c];
+        const double *src = host.data() + m->off[c];
+        for (size_t i = 0; i < cnt; ++i) { outs[c][2 * i] = src[i]; outs[c][2 * i + 1] = 0.0; }
+    }
+    return ELPH_OK;
+}
+
+extern "C" int elph_meas_reset(elph_handle h) {
+    CHECK_H(h);
+    RC(need_meas(h));
+    MeasState *m = ms_of(h);
+    HIPCHK(hipMemsetAsync(m->acc, 0, m->nacc * sizeof(double), h->stream));
+    return ELPH_OK;
+}

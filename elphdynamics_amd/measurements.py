@@ -1,0 +1,303 @@
+"""Host-side mirror of Measurements.jl for the Holstein model: the measurement container, its accumulation on the device, and the
+per-bin processing and files.
+
+    c = initialize_measurements_container(model, info, datafolder)     Measurements.jl:27-178
+    initialize_measurement_folders_(c)                                 :343-540
+    make_measurements_(c, model, Gr, nmeas, P=None, R=None, rng=None)  :545-566   update! then every pair of vectors, on the device
+    process_measurements_(c, bin_size, model)                          :574-676   fetch, momentum copy, normalise, susceptibilities
+    write_measurements_(c, model, bin)                                 :681-693
+    reset_measurements_(c, model)                                      :698-758
+
+`info` is the `[measurements]` table of an input deck (process_input keeps it as sim.input["measurements"]).  The constructor reads host
+attributes of the model only and makes no library call; the device side (elph_meas_create, csrc/measure.hip) is made by the first
+make_measurements_ / accumulate_.  Between two process_measurements_ the sums live on the device: the container's arrays are filled by
+process_measurements_ (or fetch_), one small copy per bin.
+
+Arrays keep the reference's shapes in Fortran order (Julia's memory image): a correlation's `position` and `momentum` are complex128
+(L0, L1, L2, L3, n_p) with L0 = Ltau + 1 (time-dependent, tau = beta included) or 1 (equal-time), `pairs` is int (2, n_p), 1-based; a
+susceptibility's are (L1, L2, L3, n_p).
+
+Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
+BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, the SSH model, several chains resident in the handle;
+sharded and slab handles are refused by the library.
+
+One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
+The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,
+double_occ, x, x2, x4, phonon_pe, phonon_ke, elph_energy, mu / el_ke.  Readers key on the name column.
+"""
+import os
+from math import comb
+
+import numpy as np
+
+from . import greens as _greens
+from ._lib import P_int, check, dptr, iptr
+
+GLOBAL_KEYS = ("density", "Nsqr", "mu")
+ONSITE_KEYS = ("density", "double_occ", "x", "x2", "x4", "phonon_pe", "phonon_ke", "elph_energy", "mu")
+INTERSITE_KEYS = ("el_ke",)
+ONSITE_CORR = ("Greens", "DenDen", "SpinSpin", "PairGreens", "PhononGreens")        # the order of elph_meas_create's request arrays
+INTERSITE_CORR = ("BondBond", "CurrentCurrent", "BondPairGreens")
+SUSC_OF = (("PairSusc", "PairGreens"), ("ChargeSusc", "DenDen"), ("SpinSusc", "SpinSpin"))      # :148-155
+
+
+class UnsupportedMeasurement(NotImplementedError):
+    """A request of the [measurements] table, or a model, that this port does not measure."""
+
+
+class Correlation:
+    """(position, momentum, pairs) of one correlation function or susceptibility (:792, :814)."""
+
+    def __init__(self, shape, pairs):
+        self.position = np.zeros(shape, dtype=np.complex128, order="F")
+        self.momentum = np.zeros(shape, dtype=np.complex128, order="F")
+        self.pairs = pairs
+
+
+class MeasurementsContainer:
+    def __init__(self):
+        self.global_meas, self.onsite_meas, self.intersite_meas = {}, {}, {}
+        self.onsite_corr, self.intersite_corr, self.onsite_susc, self.intersite_susc = {}, {}, {}, {}
+        self.snapshots = []
+        self.n_rand_vecs = 1
+        self.datafolder = ""
+        self._device_of = None           # the model whose handle holds the device side
+
+
+def _pairs(entry, n):
+    """:776-782: the listed pairs sorted (lexicographically, as sort! of a Vector{Vector{Int}}), or all n^2 with the first index slowest."""
+    if "pairs" in entry:
+        pairs = sorted([int(p[0]), int(p[1])] for p in entry["pairs"])
+    else:
+        pairs = [[i, j] for i in range(1, n + 1) for j in range(1, n + 1)]
+    return np.array(pairs, dtype=np.int64).reshape(-1, 2).T.copy()
+
+
+def initialize_measurements_container(model, info, datafolder):
+    """initialize_measurements_container(holstein, info, datafolder) (:27-178)."""
+    if getattr(model, "kind", None) != 0:
+        raise UnsupportedMeasurement("measurements of the SSH model are not supported (Holstein only)")
+    if getattr(model, "_nchains", 1) > 1:
+        raise UnsupportedMeasurement("measurements with several chains resident (model._nchains = %d) are not supported" % model._nchains)
+    info = info or {}
+    for name in INTERSITE_CORR:
+        if info.get(name, {}).get("measure", False) is True:
+            what = name + (" (and BondPairSusc)" if name == "BondPairGreens" else "")
+            raise UnsupportedMeasurement("[measurements.%s] measure = true: the inter-site correlation %s is not supported" % (name, what))
+    for key, val in info.get("Snapshots", {}).items():
+        if val is True:
+            raise UnsupportedMeasurement("[measurements.Snapshots] %s = true: snapshots are not supported" % key)
+    lat = model.lattice
+    L, L1, L2, L3, no = model.Ltau, lat.L1, lat.L2, lat.L3, lat.norbits
+    c = MeasurementsContainer()
+    c.n_rand_vecs = int(info.get("num_random_vectors", 1))                  # :36-40
+    c.datafolder = datafolder
+    c.global_meas = {k: 0j for k in GLOBAL_KEYS}
+    c.onsite_meas = {k: np.zeros(no, dtype=np.complex128) for k in ONSITE_KEYS}
+    c.intersite_meas = {k: np.zeros(int(model.nbonds), dtype=np.complex128) for k in INTERSITE_KEYS}
+    for name in ONSITE_CORR:                                                # init_corr_container!, :767-796
+        entry = info.get(name)
+        if entry is None or entry.get("measure", False) is not True:
+            continue
+        pairs = _pairs(entry, no)
+        L0 = L + 1 if entry.get("time_dependent", False) is True else 1
+        c.onsite_corr[name] = Correlation((L0, L1, L2, L3, pairs.shape[1]), pairs)
+    for susc, corr in SUSC_OF:                                              # init_susc_container!, :801-819
+        if corr in c.onsite_corr and c.onsite_corr[corr].position.shape[0] > 1:
+            pairs = c.onsite_corr[corr].pairs
+            c.onsite_susc[susc] = Correlation((L1, L2, L3, pairs.shape[1]), pairs)
+    return c
+
+
+def _key_file(path, header, arr, pairs):
+    """The key of one array (:391-416, :471-496): 1-based index in memory order, the pair's orbitals, 0-based displacements, last
+    axis first."""
+    with open(path, "w") as f:
+        f.write(header + "\n")
+        nd = arr.ndim
+        for i, idx in enumerate(np.ndindex(*arr.shape[::-1])):
+            cidx = idx[::-1]                                                 # first index fastest
+            p = cidx[-1]
+            f.write(" ".join(["%d" % (i + 1), "%d" % pairs[0, p], "%d" % pairs[1, p]] + ["%d" % cidx[k] for k in range(nd - 2, -1, -1)]) + "\n")
+
+
+def initialize_measurement_folders_(container):
+    """initialize_measurement_folders!(container) (:343-540)."""
+    d = container.datafolder
+    for name in ("global_measurements_f", "onsite_measurements_f", "intersite_measurements_f"):
+        os.mkdir(os.path.join(d, name))
+    for group, cols in ((container.onsite_corr, " tau"), (container.onsite_susc, "")):
+        for k, corr in group.items():
+            for space, letter in (("position", "r"), ("momentum", "k")):
+                folder = os.path.join(d, "%s_%s_f" % (k, space))
+                os.mkdir(folder)
+                header = "index orbit1 orbit2 %s3 %s2 %s1%s" % (letter, letter, letter, cols)
+                _key_file(os.path.join(folder, "%s_%s_key.out" % (k, space)), header, getattr(corr, space), corr.pairs)
+
+
+def bond_arrays(model):
+    """(sites (nbonds_total, 2) 1-based, t) in the reference's bond order bond = (definition - 1) * ncells + cell (:1044-1054):
+    neighbor_table[:, checkerboard_perm[bond]] and t[bond].  initialize_model_ sorts model.neighbor_table into checkerboard order and
+    leaves model.t in definition order; checkerboard_perm maps a definition-ordered bond to its row of the sorted table."""
+    nb = int(model.Nbonds)
+    if nb != int(model.nbonds) * model.lattice.ncells:
+        raise ValueError("el_ke: %d bonds are not %d definitions x %d cells (duplicate bonds were removed on a short axis): the "
+                         "reference's bond -> definition map does not hold" % (nb, model.nbonds, model.lattice.ncells))
+    if nb == 0:
+        return np.zeros((0, 2), dtype=np.int64), np.zeros(0)
+    rows = np.asarray(model.checkerboard_perm, dtype=np.int64) - 1
+    return np.ascontiguousarray(model.neighbor_table[rows], dtype=np.int64), np.ascontiguousarray(model.t, dtype=np.float64)
+
+
+def _ensure_device(container, model, Gr):
+    if container._device_of is model:
+        return
+    if getattr(model, "kind", None) != 0:
+        raise UnsupportedMeasurement("measurements of the SSH model are not supported (Holstein only)")
+    assert Gr.model is model
+    if Gr.nv != container.n_rand_vecs:
+        raise ValueError("the estimator holds %d vectors, the container normalises for num_random_vectors = %d" % (Gr.nv, container.n_rand_vecs))
+    sites, t = bond_arrays(model)
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)  # noqa: E731
+    measure = i32([name in container.onsite_corr for name in ONSITE_CORR])
+    timedep = i32([name in container.onsite_corr and container.onsite_corr[name].position.shape[0] > 1 for name in ONSITE_CORR])
+    npairs = i32([container.onsite_corr[name].pairs.shape[1] if name in container.onsite_corr else 0 for name in ONSITE_CORR])
+    plist = [container.onsite_corr[name].pairs.T.reshape(-1) for name in ONSITE_CORR if name in container.onsite_corr]
+    pairs = i32(np.concatenate(plist)) if plist else i32([0, 0])
+    ip = lambda a: a.ctypes.data_as(P_int)  # noqa: E731
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+    check(model._lib.elph_meas_create(model._h, dptr(f64(model.omega)), dptr(f64(model.omega4)), dptr(f64(model.lam)), dptr(f64(model.mu)),
+                                      float(model.dtau), sites.shape[0], int(model.nbonds), iptr(sites) if sites.size else None,
+                                      dptr(t) if t.size else None, ip(measure), ip(timedep), ip(npairs), ip(pairs)))
+    container._device_of = model
+
+
+def accumulate_(container, model, Gr):
+    """make_measurements! without its update! (:550-560): every pair i < j of the estimator's vectors is set up and folded into the device's
+    accumulators; nothing comes back to the host."""
+    if getattr(model, "_nchains", 1) > 1:
+        raise UnsupportedMeasurement("measurements with several chains resident (model._nchains = %d) are not supported" % model._nchains)
+    _ensure_device(container, model, Gr)
+    check(model._lib.elph_meas_accumulate(model._h, dptr(np.ascontiguousarray(model.x, dtype=np.float64))))
+    Gr.n1, Gr.n2 = Gr.nv - 1, Gr.nv                                         # the estimator's device tables are the last pair's now
+
+
+def make_measurements_(container, model, Gr, nmeas, P=None, R=None, rng=None):
+    """make_measurements!(container, model, Gr, nmeas, preconditioner) (:545-566).  R / rng: the noise vectors of update_ (greens.py).
+    Returns update_'s (iters, residual_error, flag).  nmeas numbers the snapshots of the reference; none are taken here."""
+    out = _greens.update_(Gr, model, P, rng=rng, R=R)
+    accumulate_(container, model, Gr)
+    return out
+
+
+def fetch_(container, model):
+    """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
+    if container._device_of is not model:
+        raise RuntimeError("nothing has been measured on this model yet")
+    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
+    scal = np.zeros(3 + len(ONSITE_KEYS) * no + nb)
+    ptrs = []
+    for name in ONSITE_CORR:
+        ptrs.append(container.onsite_corr[name].position.ctypes.data_as(type(dptr(scal))) if name in container.onsite_corr else None)
+    check(model._lib.elph_meas_fetch(model._h, dptr(scal), *ptrs))
+    for i, k in enumerate(GLOBAL_KEYS):
+        container.global_meas[k] = complex(scal[i])
+    for i, k in enumerate(ONSITE_KEYS):
+        container.onsite_meas[k][:] = scal[3 + i * no:3 + (i + 1) * no]
+    container.intersite_meas["el_ke"][:] = scal[3 + len(ONSITE_KEYS) * no:]
+
+
+def simpson(f, dx):
+    """simpson(f, dx) (Utilities.jl:65-76) along the first axis: composite Simpson over pairs of intervals and, for an even number of
+    points, the reference's end correction over the last interval."""
+    f = np.asarray(f)
+    n = f.shape[0]
+    F = np.zeros(f.shape[1:], dtype=f.dtype)
+    for i in range(1, n - 1, 2):                                            # Julia's i = 2, 4, ..., <= n - 1
+        F = F + dx * (1 / 3 * f[i - 1] + 4 / 3 * f[i] + 1 / 3 * f[i + 1])
+    if n % 2 == 0:
+        F = F + dx * (5 / 12 * f[n - 1] + 2 / 3 * f[n - 2] - 1 / 12 * f[n - 3])
+    return F
+
+
+def fourier_transform_correlations_(group):
+    """fourier_transform_correlations! (:1160-1170): momentum = fft of position over the three cell axes."""
+    for corr in group.values():
+        corr.momentum[...] = np.fft.fftn(corr.position, axes=(1, 2, 3))
+
+
+def normalize_(container, bin_size):
+    """:590-629: everything divided by bin_size * binomial(n_rand_vecs, 2)."""
+    V = int(bin_size) * comb(container.n_rand_vecs, 2)
+    if V == 0:
+        raise ValueError("bin_size * binomial(num_random_vectors = %d, 2) is zero" % container.n_rand_vecs)
+    for k in container.global_meas:
+        container.global_meas[k] /= V
+    for group in (container.onsite_meas, container.intersite_meas):
+        for k in group:
+            group[k] /= V
+    for corr in container.onsite_corr.values():
+        corr.position /= V
+        corr.momentum /= V
+
+
+def measure_susceptibilities_(container, dtau):
+    """:636-663 with measure_susceptibility! (:2550-2572): Simpson's rule over tau of the normalised correlations."""
+    for susc, corr in SUSC_OF:
+        if susc in container.onsite_susc:
+            container.onsite_susc[susc].position[...] = simpson(container.onsite_corr[corr].position, dtau)
+            container.onsite_susc[susc].momentum[...] = simpson(container.onsite_corr[corr].momentum, dtau)
+
+
+def process_measurements_(container, bin_size, model):
+    """process_measurements!(container, sim_params, model) (:574-676); bin_size is sim_params.bin_size."""
+    fetch_(container, model)
+    fourier_transform_correlations_(container.onsite_corr)
+    normalize_(container, bin_size)
+    measure_susceptibilities_(container, model.dtau)
+
+
+def _write_correlation(arr, name, space, datafolder, bin):
+    """write_correlation! (:1258-1274)."""
+    meas = "%s_%s" % (name, space)
+    with open(os.path.join(datafolder, meas + "_f", "%s_%.5d.out" % (meas, bin)), "w") as f:
+        f.write("index %s_real %s_imag\n" % (meas, meas))
+        flat = arr.reshape(-1, order="F")
+        f.writelines("%d %.8f %.8f\n" % (i + 1, v.real, v.imag) for i, v in enumerate(flat))
+
+
+def write_measurements_(container, model, bin):
+    """write_measurements!(container, model, bin) (:681-693, :1175-1274)."""
+    d = container.datafolder
+    with open(os.path.join(d, "global_measurements_f", "global_measurements_%.5d.out" % bin), "w") as f:
+        for k in GLOBAL_KEYS:
+            f.write("%s %.8f\n" % (k, container.global_meas[k].real))
+    with open(os.path.join(d, "onsite_measurements_f", "onsite_measurements_%.5d.out" % bin), "w") as f:
+        f.write("measurement orbit value\n")
+        for k in ONSITE_KEYS:
+            for o, v in enumerate(container.onsite_meas[k]):
+                f.write("%s %d %.8f\n" % (k, o + 1, v.real))
+    with open(os.path.join(d, "intersite_measurements_f", "intersite_measurements_%.5d.out" % bin), "w") as f:
+        f.write("measurement bond value\n")
+        for k in INTERSITE_KEYS:
+            for b, v in enumerate(container.intersite_meas[k]):
+                f.write("%s %d %.8f\n" % (k, b + 1, v.real))
+    for group in (container.onsite_corr, container.onsite_susc):
+        for name, corr in group.items():
+            _write_correlation(corr.position, name, "position", d, bin)
+            _write_correlation(corr.momentum, name, "momentum", d, bin)
+
+
+def reset_measurements_(container, model):
+    """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
+    for k in container.global_meas:
+        container.global_meas[k] = 0j
+    for group in (container.onsite_meas, container.intersite_meas):
+        for k in group:
+            group[k][:] = 0
+    for group in (container.onsite_corr, container.onsite_susc):
+        for corr in group.values():
+            corr.position[...] = 0
+            corr.momentum[...] = 0
+    if container._device_of is model and model is not None and getattr(model, "_h", None):
+        check(model._lib.elph_meas_reset(model._h))

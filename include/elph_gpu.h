@@ -390,8 +390,48 @@ int elph_greens_get_vectors(elph_handle h, double *R, double *MinvR);
 int elph_greens_setup(elph_handle h, int n1, int n2, double *GD0, double *GD0_GD0, double *GDD_G00, double *GD0_G0D);
 
 /* Device-resident results of the last elph_greens_setup: arrays[0..3] in the order above, `count` complex numbers each
- * (valid until the next elph_greens_setup / elph_greens_create / elph_destroy). */
+ * (valid until the next elph_greens_setup / elph_greens_create / elph_destroy).  elph_meas_accumulate runs setup! for every pair of
+ * vectors: after it these arrays hold the tables of the LAST pair (n_v - 1, n_v), not those of the caller's last elph_greens_setup. */
 int elph_greens_dev_arrays(elph_handle h, void **arrays, int64_t *count);
+
+/* ---------------------------------------------------------------- measurements (Holstein model; Measurements.jl) */
+
+/* The device side of a measurements container (initialize_measurements_container, Measurements.jl:27-178, for what make_measurements!
+ * adds up): accumulators for the global (density, Nsqr, mu; :845-861, :1283-1312), on-site (:916-976) and inter-site (el_ke, :1029-1070)
+ * measurements and for the requested on-site correlations (:1469-1650), all doubles on the device.  Needs elph_greens_create first (n_s,
+ * L1..L3 and n_v are the estimator's); a new elph_greens_create drops the container.
+ *   omega, omega4, lambda, mu   double[nsites]: model.ω, .ω₄, .λ, .μ;  dtau: model.Δτ
+ *   nbonds, ndef                nbonds = ndef * ncells bonds of ndef bond definitions, in the reference's bond order
+ *                               bond = (definition - 1) * ncells + cell (:1048)
+ *   bond_sites                  int64[2 * nbonds], column-major 2 x nbonds, 1-based: neighbor_table[:, checkerboard_perm[bond]] (:1050-1052)
+ *   bond_t                      double[nbonds]: model.t[bond] (:1054)
+ *   measure, time_dependent, npairs   int[5] for Greens, DenDen, SpinSpin, PairGreens, PhononGreens in this order: measured or not;
+ *                               L_tau + 1 slices (tau = beta included) or the equal-time slice alone; number of orbital pairs
+ *   pairs                       int[2 * sum of npairs over the measured ones]: their (o1, o2) lists one after the other, 1-based, in the
+ *                               order the container keeps them (:776-782)
+ * ELPH_E_ARG (an orbital outside 1..n_s, a bond site outside the lattice, a bond count that is not ndef * ncells) and
+ * ELPH_E_UNSUPPORTED (SSH model, several chains resident, a sharded or slab handle) leave the handle without a container and usable. */
+int elph_meas_create(elph_handle h, const double *omega, const double *omega4, const double *lambda, const double *mu, double dtau,
+                     int64_t nbonds, int ndef, const int64_t *bond_sites, const double *bond_t, const int *measure,
+                     const int *time_dependent, const int *npairs, const int *pairs);
+
+/* make_measurements! (Measurements.jl:545-566) without its update!: the estimator holds vectors already (elph_greens_update or
+ * elph_greens_set_vectors; ELPH_E_STATE otherwise).  x: model.x, double[ndim], reference layout.  For every pair i < j of the n_v vectors
+ * the device part of setup! and the folds into the accumulators run on the handle's stream with no copy to the host and no
+ * synchronisation in between; the call synchronises once before it returns.  Sums are taken in one fixed order without atomics: the
+ * same inputs give the same bits. */
+int elph_meas_accumulate(elph_handle h, const double *x);
+
+/* The un-normalised sums since the last reset; one device-to-host copy, one synchronisation.  Each pointer may be NULL.
+ *   scalars    double[3 + 9 n_s + ndef]: density, Nsqr, mu; then n_s values each of density, double_occ, x, x2, x4, phonon_pe,
+ *              phonon_ke, elph_energy, mu; then el_ke per bond definition
+ *   Greens … PhononGreens   Complex{Float64}[L0, L1, L2, L3, n_p] as interleaved (re, im) doubles, first index fastest, L0 = L_tau + 1 or 1:
+ *              the container's `position` arrays (:786-790); imaginary parts are exact zeros.  Unmeasured ones are left untouched. */
+int elph_meas_fetch(elph_handle h, double *scalars, double *Greens, double *DenDen, double *SpinSpin, double *PairGreens,
+                    double *PhononGreens);
+
+/* reset_measurements! (Measurements.jl:698-758): every accumulator to zero (stream-ordered). */
+int elph_meas_reset(elph_handle h);
 
 /* ---------------------------------------------------------------- KPM preconditioner */
 
