@@ -340,6 +340,7 @@ struct elph_handle_s {
     void *hmc = nullptr;                   // HmcState (hmc.hip), owned
     void *greens = nullptr;                // GreensState (greens.hip), owned
     void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
+    void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
     void *d_res = nullptr;                 // control block of the workgroup-resident CG (cg_wg.hip): meeting records, abort word, boundary slices
     size_t res_cap = 0;
     // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854);
@@ -426,12 +427,14 @@ int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const doub
 int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec, double tol_power, int64_t *iters, int *flag);
 void elph_greens_free(elph_handle_s *h);
 void elph_meas_free(elph_handle_s *h);                                      // measure.hip
-// greens.hip internals used by measure.hip
+void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip
+// greens.hip internals used by measure.hip and bondcorr.hip
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;
     bool have_vectors;
     const double *R, *X;       // [nv][ndim] layout S
     const double *C;           // [4][L][ns*N] the real correlations of the last elph_i_greens_setup_dev
+    const double2 *tw;         // [L1 + L2 + L3] exp(-2πi j/Lx), the twiddles of the cell-axis DFTs
 };
 int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v);
 int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand);      // no copy to the host, no synchronisation

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "cell_dft_dev.h"
 #include "elph_internal.h"
 
 #define RC(call)                \
@@ -38,6 +39,7 @@
 namespace {
 
 constexpr int TPB = 256;
+static_assert(TPB == CELL_DFT_TPB, "dft_cells walks the workgroup of k_gr_spatial");
 
 struct GreensState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, nv = 2;
@@ -83,39 +85,6 @@ __global__ void __launch_bounds__(TPB) k_gr_fields(double *__restrict__ f, const
 }
 
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// dst[e] = Σ_j src[e with axis index j] · w^(a·j), a = axis index of e; w = tw (forward) or conj tw (inverse)
-template <bool INV>
-__device__ void dft_axis(double2 *dst, const double2 *src, int total, int stride, int len, const double2 *__restrict__ tw) {
-    for (int e = threadIdx.x; e < total; e += TPB) {
-        const int a = (e / stride) % len;
-        const int base = e - a * stride;
-        double2 acc = make_double2(0.0, 0.0);
-        int m = 0;                                  // (a*j) mod len, exact
-        for (int j = 0; j < len; ++j) {
-            double2 w = tw[m];
-            if (INV) w.y = -w.y;
-            const double2 v = src[base + j * stride];
-            acc.x += v.x * w.x - v.y * w.y;
-            acc.y += v.x * w.y + v.y * w.x;
-            m += a;
-            if (m >= len) m -= len;
-        }
-        dst[e] = acc;
-    }
-    __syncthreads();
-}
-
-// DFT over the (up to) three cell axes of `total` = unit*L1*L2*L3 complex numbers held in LDS buffer a (scratch b);
-// returns the buffer that holds the result.  unit = n_s when the orbital index is interleaved, 1 for cell arrays.
-template <bool INV>
-__device__ double2 *dft_cells(double2 *a, double2 *b, int unit, int L1, int L2, int L3, const double2 *__restrict__ tw) {
-    const int total = unit * L1 * L2 * L3;
-    if (L1 > 1) { dft_axis<INV>(b, a, total, unit, L1, tw); double2 *t = a; a = b; b = t; }
-    if (L2 > 1) { dft_axis<INV>(b, a, total, unit * L1, L2, tw + L1); double2 *t = a; a = b; b = t; }
-    if (L3 > 1) { dft_axis<INV>(b, a, total, unit * L1 * L2, L3, tw + L1 + L2); double2 *t = a; a = b; b = t; }
-    return a;
-}
 
 // One workgroup per (frequency k, product c): spatial DFT of the two spectra, outer product over orbitals with
 // fft(b)[-ω,-k] = conj fft(b)[ω,k], inverse spatial DFT.  Y[c][k][s2 + ns*(s1 + ns*cell)].
@@ -189,6 +158,7 @@ size_t spatial_lds_bytes(const elph_handle_s *h, const GreensState *g) { return 
 
 void elph_greens_free(elph_handle_s *h) {
     elph_meas_free(h);                     // the measurement accumulators are shaped by the estimator
+    elph_bond_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;
     void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};
@@ -359,13 +329,13 @@ int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand) {
     return ELPH_OK;
 }
 
-// What measure.hip reads of the estimator (device pointers stay owned by it).
+// What measure.hip and bondcorr.hip read of the estimator (device pointers stay owned by it).
 int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
     RC(need_greens(h));
     const GreensState *g = gs_of(h);
     v->ns = g->ns; v->L1 = g->L1; v->L2 = g->L2; v->L3 = g->L3; v->nc = g->nc; v->nv = g->nv;
     v->have_vectors = g->have_vectors;
-    v->R = g->R; v->X = g->X; v->C = g->C;
+    v->R = g->R; v->X = g->X; v->C = g->C; v->tw = g->tw;
     return ELPH_OK;
 }
 

@@ -98,6 +98,7 @@ class HolsteinModel(AbstractModel):
         self.Ndim = self.Ndof
         self.Nbonds = 0
         self.nbonds = 0
+        self.bond_definitions = []                                  # (o1, o2, (v1, v2, v3)) per assign_t_, in call order
         self.x = np.zeros(self.Ndof)
         self.expnDtauV = None                                       # lives on the GPU (layout S)
         self.t = np.zeros(0)
@@ -128,6 +129,7 @@ class HolsteinModel(AbstractModel):
             t_new = t_new + stddev * _rng(rng).standard_normal(n)
         self.t = np.concatenate([self.t, phase * t_new])
         self.nbonds += 1
+        self.bond_definitions.append((int(o1), int(o2), tuple(int(k) for k in v)))
 
     def _assign(self, arr, val, orbit, stddev=0.0, rng=None):
         sel = slice(None) if orbit == 0 else slice(orbit - 1, None, self.lattice.norbits)

@@ -433,6 +433,39 @@ int elph_meas_fetch(elph_handle h, double *scalars, double *Greens, double *DenD
 /* reset_measurements! (Measurements.jl:698-758): every accumulator to zero (stream-ordered). */
 int elph_meas_reset(elph_handle h);
 
+/* ---------------------------------------------------------------- bond correlations (Holstein model; Measurements.jl) */
+
+/* The device side of the inter-site correlation group of a measurements container (init_corr_container!, Measurements.jl:156-175,
+ * :767-796): accumulators for BondBond (measure_BondBond!, :1663-1785) and BondPairGreens (measure_BondPairGreens!, :2390-2483), all
+ * doubles on the device, beside (not inside) the container of elph_meas_create.  Needs elph_greens_create first (n_s, L1..L3 and n_v are
+ * the estimator's); a new elph_greens_create drops it.
+ *   n_def, o1, o2, v            model.bond_definitions: int[n_def] starting orbital Bond.o1, int[n_def] ending orbital Bond.o2 (1-based),
+ *                               int[3 * n_def] displacement Bond.v in unit cells, definition-major
+ *   measure, time_dependent, npairs   int[2] for BondBond, BondPairGreens in this order: measured or not; L_tau + 1 slices (tau = beta
+ *                               included) or the equal-time slice alone; number of pairs of bond definitions
+ *   pairs                       int[2 * sum of npairs over the measured ones]: their (pairs[1,p], pairs[2,p]) lists one after the other,
+ *                               1-based indices of bond definitions, in the order the container keeps them (:776-782)
+ * ELPH_E_ARG (an orbital outside 1..n_s, a bond index outside 1..n_def; the message names the correlation or definition and the
+ * offending index) and ELPH_E_UNSUPPORTED (SSH model, several chains resident, a sharded or slab handle, a lattice whose frequency
+ * slice does not fit the LDS) leave the handle without bond accumulators and usable. */
+int elph_bond_create(elph_handle h, int n_def, const int *o1, const int *o2, const int *v, const int *measure, const int *time_dependent,
+                     const int *npairs, const int *pairs);
+
+/* The calls to measure_BondBond! / measure_BondPairGreens! of make_intersite_measurements! for every pair i < j of the estimator's n_v
+ * vectors (elph_greens_update or elph_greens_set_vectors first; ELPH_E_STATE otherwise): per pair the device part of setup! (for G[D,0]
+ * of the delta terms), the fields of shifted vectors, their transforms, one inverse transform per listed pair and correlation, and the
+ * fold into the accumulators, on the handle's stream with no copy and no synchronisation in between; the call synchronises once before
+ * it returns.  No atomics: the same inputs give the same bits.  Afterwards elph_greens_dev_arrays holds the tables of the LAST pair. */
+int elph_bond_accumulate(elph_handle h);
+
+/* The un-normalised sums since the last reset; one device-to-host copy, one synchronisation.  Each pointer may be NULL.
+ *   BondBond, BondPairGreens   Complex{Float64}[L0, L1, L2, L3, n_p] as interleaved (re, im) doubles, first index fastest, L0 = L_tau + 1
+ *              or 1: the container's `position` arrays (:786-790); imaginary parts are exact zeros.  Unmeasured ones are left untouched. */
+int elph_bond_fetch(elph_handle h, double *BondBond, double *BondPairGreens);
+
+/* reset_measurements! (Measurements.jl:698-758) for the two bond correlations: every accumulator to zero (stream-ordered). */
+int elph_bond_reset(elph_handle h);
+
 /* ---------------------------------------------------------------- KPM preconditioner */
 
 /* SymmetricKPMPreconditioner(model, n, buf, c1, c2) — KPMPreconditioners.jl:219-235, ctor :101-146 */
