@@ -21,57 +21,33 @@
 #include <vector>
 
 #include "cell_dft_dev.h"
+#include "corr_req.h"
 #include "elph_internal.h"
-
-#define RC(call)                \
-    do {                        \
-        int _rc = (call);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
-#define CHECK_H(h)                                                    \
-    do {                                                              \
-        if (!(h)) { elph_set_error("null handle"); return ELPH_E_ARG; } \
-        HIPCHK(hipSetDevice((h)->device));                            \
-    } while (0)
 
 namespace {
 
 constexpr int TPB = CELL_DFT_TPB;
 constexpr int NBOND = 2;
 const char *const BOND_NAMES[NBOND] = {"BondBond", "BondPairGreens"};
+const CorrWords WORDS = {"bond correlations", "bond", "with no pair of bonds"};
 enum { BONDBOND = 0, BONDPAIR = 1 };
 constexpr int NFIELD = 6;       // per definition; 0..3 serve BondBond, 4..5 BondPairGreens
 constexpr int DEFW = 8;         // ints per definition: s, e (0-based orbitals), v mod L (3), v as given (3)
 
-struct BondReq {                // by value into the kernels
-    double *acc[NBOND];
-    const int *pairs[NBOND];    // [np][2] 0-based (n″, n′)
-    int np[NBOND], L0[NBOND];   // np = 0: not measured
-};
+using BondReq = CorrReq<NBOND>;          // pairs (n″, n′)
 
 struct BondState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, ndef = 0;
     int k0 = 0, k1 = 0;             // the fields [k0, k1) are transformed
     int *defs = nullptr;            // [ndef][DEFW]
-    int *pairs = nullptr;           // both requests' pairs, concatenated
-    double *acc = nullptr;          // [BondBond | BondPairGreens]
-    size_t nacc = 0, off[NBOND] = {};
+    CorrPlan<NBOND> cr;             // the requests; cr.acc: [BondBond | BondPairGreens]
     double *f = nullptr;            // [NFIELD][ndef][L][nc] the fields of one pair of vectors
     double2 *nu = nullptr;          // [NFIELD][ndef][Lh][nc] their half spectra, then their cell-axis DFTs in place
     double2 *Y = nullptr;           // [nP][Lh][nc] per-frequency correlations of the listed pairs, BondBond's first
     double *B = nullptr;            // [nP][L][nc]
-    BondReq req{};
-    size_t fold_max = 0;
 };
 
 BondState *bs_of(elph_handle_s *h) { return (BondState *)h->bond; }
-
-int bc_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
 
 size_t bc_lds_bytes(int nc) { return 2 * (size_t)nc * sizeof(double2); }
 
@@ -190,32 +166,14 @@ __global__ void __launch_bounds__(TPB) k_bc_fold(BondReq rq, const double *__res
     rq.acc[which][idx] += v;
 }
 
-template <class T>
-int bc_alloc(T **p, size_t n) {
-    HIPCHK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return ELPH_OK;
-}
-
-int need_bond(elph_handle_s *h) {
-    if (!h->bond) { elph_set_error("elph_bond_create has not been called"); return ELPH_E_STATE; }
-    return ELPH_OK;
-}
-
-int refuse_chains(elph_handle_s *h) {
-    if (h->nchains > 1) {
-        elph_set_error("bond correlations: %d chains are resident in this handle; one configuration per handle is measured", h->nchains);
-        return ELPH_E_UNSUPPORTED;
-    }
-    return ELPH_OK;
-}
+int need_bond(elph_handle_s *h) { return corr_need(h->bond, "elph_bond_create"); }
 
 }  // namespace
 
 void elph_bond_free(elph_handle_s *h) {
     BondState *m = bs_of(h);
     if (!m) return;
-    void *ptrs[] = {m->defs, m->pairs, m->acc, m->f, m->nu, m->Y, m->B};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    corr_free({m->defs, m->cr.pairs, m->cr.acc, m->f, m->nu, m->Y, m->B});
     delete m;
     h->bond = nullptr;
 }
@@ -224,9 +182,7 @@ extern "C" int elph_bond_create(elph_handle h, int n_def, const int *o1, const i
                                 const int *time_dependent, const int *npairs, const int *pairs) {
     CHECK_H(h);
     elph_bond_free(h);
-    if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("bond correlations: the SSH model is not supported (Holstein only)"); return ELPH_E_UNSUPPORTED; }
-    if (h->shard || h->is_slab) { elph_set_error("bond correlations: sharded and slab handles are not supported"); return ELPH_E_UNSUPPORTED; }
-    RC(refuse_chains(h));
+    RC(corr_refuse_handle(h, WORDS.prefix));
     ElphGreensView g;
     RC(elph_i_greens_view(h, &g));
     if (n_def < 1 || !o1 || !o2 || !v || !measure || !time_dependent || !npairs) {
@@ -256,103 +212,62 @@ extern "C" int elph_bond_create(elph_handle h, int n_def, const int *o1, const i
             defs[(size_t)n * DEFW + 5 + k] = r;
         }
     }
-    BondState tmp;                                     // request bookkeeping before anything is allocated
-    std::vector<int> prs;
-    size_t at = 0, total = 0, pair_off[NBOND] = {0, 0};
-    for (int c = 0; c < NBOND; ++c) {
-        tmp.req.np[c] = 0; tmp.req.L0[c] = 1;
-        if (!measure[c]) continue;
-        if (npairs[c] < 1 || !pairs) { elph_set_error("bond correlations: %s is requested with no pair of bonds", BOND_NAMES[c]); return ELPH_E_ARG; }
-        for (int p = 0; p < npairs[c]; ++p)
-            for (int k = 0; k < 2; ++k) {
-                const int n = pairs[2 * (at + p) + k];
-                if (n < 1 || n > n_def) {
-                    elph_set_error("bond correlations: %s pair %d names bond %d, outside 1..%d", BOND_NAMES[c], p + 1, n, n_def);
-                    return ELPH_E_ARG;
-                }
-                prs.push_back(n - 1);
-            }
-        pair_off[c] = 2 * at;
-        at += (size_t)npairs[c];
-        tmp.req.np[c] = npairs[c];
-        tmp.req.L0[c] = time_dependent[c] ? L + 1 : 1;
-        tmp.off[c] = total;
-        const size_t cnt = (size_t)tmp.req.L0[c] * nc * npairs[c];
-        total += cnt;
-        tmp.fold_max = std::max(tmp.fold_max, cnt);
-    }
-    BondState *m = new BondState(tmp);
+    CorrPlan<NBOND> plan;                              // request bookkeeping before anything is allocated
+    RC(corr_plan(plan, WORDS, BOND_NAMES, measure, time_dependent, npairs, pairs, n_def, L, nc, 0));
+    BondState *m = new BondState;
     h->bond = m;
+    m->cr = plan;
     m->ns = ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = n_def;
-    m->nacc = total;
-    m->k0 = m->req.np[BONDBOND] ? 0 : 4;
-    m->k1 = m->req.np[BONDPAIR] ? NFIELD : 4;
-    const size_t nP = at, nf = (size_t)NFIELD * n_def;
-    int rc = ELPH_OK;
-    auto ok = [&](int r) { if (rc == ELPH_OK) rc = r; return rc == ELPH_OK; };
-    const bool allocated = ok(bc_alloc(&m->defs, defs.size())) && ok(bc_alloc(&m->pairs, prs.size())) && ok(bc_alloc(&m->acc, total)) &&
-        ok(bc_alloc(&m->f, nf * L * nc)) && ok(bc_alloc(&m->nu, nf * Lh * nc)) && ok(bc_alloc(&m->Y, nP * Lh * nc)) &&
-        ok(bc_alloc(&m->B, nP * L * nc));
-    if (!allocated || rc != ELPH_OK) { elph_bond_free(h); return rc; }
-    auto up = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-        return ELPH_OK;
-    };
-    ok(up(m->defs, defs.data(), defs.size() * sizeof(int)));
-    ok(up(m->pairs, prs.data(), prs.size() * sizeof(int)));
-    if (rc == ELPH_OK && hipMemset(m->acc, 0, std::max<size_t>(total, 1) * sizeof(double)) != hipSuccess) {
-        elph_set_error("bond correlations: hipMemset failed");
-        rc = ELPH_E_HIP;
-    }
+    m->k0 = plan.req.np[BONDBOND] ? 0 : 4;
+    m->k1 = plan.req.np[BONDPAIR] ? NFIELD : 4;
+    const size_t nP = (size_t)plan.npairs, nf = (size_t)NFIELD * n_def;
+    CorrFirstError ok;
+    const bool allocated = ok(corr_alloc(&m->defs, defs.size())) && ok(corr_alloc(m->cr)) && ok(corr_alloc(&m->f, nf * L * nc)) &&
+        ok(corr_alloc(&m->nu, nf * Lh * nc)) && ok(corr_alloc(&m->Y, nP * Lh * nc)) && ok(corr_alloc(&m->B, nP * L * nc));
+    if (!allocated) { elph_bond_free(h); return ok.rc; }
+    if (ok(corr_up(m->defs, defs.data(), defs.size() * sizeof(int)))) ok(corr_upload(m->cr, WORDS.prefix));
     const int lds = (int)bc_lds_bytes(nc);
-    if (rc == ELPH_OK && (hipFuncSetAttribute((const void *)k_bc_spatial_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+    if (ok.rc == ELPH_OK && (hipFuncSetAttribute((const void *)k_bc_spatial_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
                           hipFuncSetAttribute((const void *)k_bc_correlate, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)) {
         elph_set_error("bond correlations: %d bytes of LDS were refused", lds);
-        rc = ELPH_E_HIP;
+        ok(ELPH_E_HIP);
     }
-    if (rc != ELPH_OK) { elph_bond_free(h); return rc; }
-    for (int c = 0; c < NBOND; ++c) {
-        m->req.acc[c] = m->acc + m->off[c];
-        m->req.pairs[c] = m->pairs + pair_off[c];
-    }
-    return ELPH_OK;
+    if (ok.rc != ELPH_OK) elph_bond_free(h);
+    return ok.rc;
 }
 
 extern "C" int elph_bond_accumulate(elph_handle h) {
     CHECK_H(h);
     RC(need_bond(h));
-    RC(refuse_chains(h));
+    RC(corr_refuse_chains(h, WORDS.prefix));
     BondState *m = bs_of(h);
     ElphGreensView g;
     RC(elph_i_greens_view(h, &g));
     if (!g.have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
     const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = m->ns, nc = m->nc, nv = g.nv, ndef = m->ndef;
-    const size_t nd = (size_t)h->ndim;
-    const int nP = m->req.np[BONDBOND] + m->req.np[BONDPAIR], nk = m->k1 - m->k0;
+    const int nP = m->cr.npairs, nk = m->k1 - m->k0;
     const size_t shm = bc_lds_bytes(nc);
     const long long nfld = (long long)L * nc * ndef;
     const double norm = 1.0 / ((double)L * (double)nc * (double)nc);   // 1/(L Nc)² in all: the other 1/L is in the inverse τ table
     for (int i = 1; i < nv && nP; ++i)
         for (int j = i + 1; j <= nv; ++j) {
-            // G[Δ,0] of this pair of vectors for the δ terms; the doubled complex copies are refreshed for the last pair only
-            RC(elph_i_greens_setup_dev(h, i, j, i == nv - 1));
-            const double *X1 = g.X + (size_t)(i - 1) * nd, *X2 = g.X + (size_t)(j - 1) * nd;
-            const double *R1 = g.R + (size_t)(i - 1) * nd, *R2 = g.R + (size_t)(j - 1) * nd;
-            hipLaunchKernelGGL(k_bc_fields, dim3((unsigned)((nfld + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, m->f, X1, X2, R1, R2, m->defs, N, L, ns,
+            ElphGreensPair v;                          // its setup leaves G[Δ,0] of this pair of vectors for the δ terms
+            RC(elph_i_greens_pair_dev(h, i, j, &v));
+            hipLaunchKernelGGL(k_bc_fields, dim3((unsigned)((nfld + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, m->f, v.X1, v.X2, v.R1, v.R2, m->defs, N, L, ns,
                                m->L1, m->L2, m->L3, ndef);
-            RC(bc_check("k_bc_fields"));
+            RC(elph_launch_check("k_bc_fields"));
             double2 *nu = m->nu + (size_t)m->k0 * ndef * Lh * nc;
             RC(elph_dft_fwd_plain(h, nu, m->f + (size_t)m->k0 * ndef * L * nc, nc, nk * ndef));
             hipLaunchKernelGGL(k_bc_spatial_fwd, dim3((unsigned)Lh, (unsigned)(nk * ndef)), dim3(TPB), shm, h->stream, nu, Lh, m->L1, m->L2, m->L3,
                                g.tw);
-            RC(bc_check("k_bc_spatial_fwd"));
-            hipLaunchKernelGGL(k_bc_correlate, dim3((unsigned)Lh, (unsigned)nP), dim3(TPB), shm, h->stream, m->Y, m->nu, m->req, Lh, ndef, m->L1,
+            RC(elph_launch_check("k_bc_spatial_fwd"));
+            hipLaunchKernelGGL(k_bc_correlate, dim3((unsigned)Lh, (unsigned)nP), dim3(TPB), shm, h->stream, m->Y, m->nu, m->cr.req, Lh, ndef, m->L1,
                                m->L2, m->L3, g.tw, norm);
-            RC(bc_check("k_bc_correlate"));
+            RC(elph_launch_check("k_bc_correlate"));
             RC(elph_dft_inv_plain(h, m->B, m->Y, nc, nP));
-            hipLaunchKernelGGL(k_bc_fold, dim3((unsigned)((m->fold_max + TPB - 1) / TPB), NBOND), dim3(TPB), 0, h->stream, m->req, m->B, g.C,
+            hipLaunchKernelGGL(k_bc_fold, dim3((unsigned)((m->cr.fold_max + TPB - 1) / TPB), NBOND), dim3(TPB), 0, h->stream, m->cr.req, m->B, g.C,
                                m->defs, L, ns, m->L1, m->L2, m->L3);
-            RC(bc_check("k_bc_fold"));
+            RC(elph_launch_check("k_bc_fold"));
         }
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
@@ -361,24 +276,13 @@ extern "C" int elph_bond_accumulate(elph_handle h) {
 extern "C" int elph_bond_fetch(elph_handle h, double *BondBond, double *BondPairGreens) {
     CHECK_H(h);
     RC(need_bond(h));
-    BondState *m = bs_of(h);
-    std::vector<double> host(std::max<size_t>(m->nacc, 1));
-    HIPCHK(hipMemcpyAsync(host.data(), m->acc, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<double> host;
     double *outs[NBOND] = {BondBond, BondPairGreens};
-    for (int c = 0; c < NBOND; ++c) {
-        if (!outs[c] || !m->req.np[c]) continue;
-        const size_t cnt = (size_t)m->req.L0[c] * m->nc * m->req.np[c];
-        const double *src = host.data() + m->off[c];
-        for (size_t i = 0; i < cnt; ++i) { outs[c][2 * i] = src[i]; outs[c][2 * i + 1] = 0.0; }
-    }
-    return ELPH_OK;
+    return corr_fetch(h, bs_of(h)->cr, host, outs);
 }
 
 extern "C" int elph_bond_reset(elph_handle h) {
     CHECK_H(h);
     RC(need_bond(h));
-    BondState *m = bs_of(h);
-    HIPCHK(hipMemsetAsync(m->acc, 0, std::max<size_t>(m->nacc, 1) * sizeof(double), h->stream));
-    return ELPH_OK;
+    return corr_reset(h, bs_of(h)->cr);
 }

@@ -1022,15 +1022,6 @@ __global__ void __launch_bounds__(2 * WAVE) k_kpm_cheb_ri(double2 *__restrict__ 
 #define LP_CAT(a, b) LP_CAT2(a, b)
 #define LPFN(name) LP_CAT(name##_n, ELPH_LP_NPL)
 
-static int check_launch_f(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        elph_set_error("launch %s failed: %s", what, hipGetErrorString(e));
-        return ELPH_E_HIP;
-    }
-    return ELPH_OK;
-}
-
 static unsigned xcd_grid(const elph_handle_s *h, int nvec) { return 8u * (unsigned)((h->L + 7) / 8) * (unsigned)nvec; }
 
 int LPFN(elph_fast_mul)(elph_handle_s *h, int which, double *yS, const double *vS, int nvec) {
@@ -1049,7 +1040,7 @@ int LPFN(elph_fast_mul)(elph_handle_s *h, int which, double *yS, const double *v
             else hipLaunchKernelGGL((k_mul_fast<NPL, 2, false>), grid, dim3(WAVE), shm, h->stream, yS, vS, m);
         }
     });
-    return check_launch_f("k_mul_fast");
+    return elph_launch_check("k_mul_fast");
 }
 
 int LPFN(elph_fast_cg_ap)(elph_handle_s *h, const CgBufs &B, int nrhs, int parity, bool px) {
@@ -1066,7 +1057,7 @@ int LPFN(elph_fast_cg_ap)(elph_handle_s *h, const CgBufs &B, int nrhs, int parit
                 if (ssh) hipLaunchKernelGGL((k_cg_ap_chunk_rt<NPL, true>), grid, dim3(WAVE), shm, h->stream, B, m, parity, T);
                 else hipLaunchKernelGGL((k_cg_ap_chunk_rt<NPL, false>), grid, dim3(WAVE), shm, h->stream, B, m, parity, T);
             });
-            return check_launch_f("k_cg_ap_chunk_rt");
+            return elph_launch_check("k_cg_ap_chunk_rt");
         }
         // (blocks in the XCD-aware order of chunk_block_map; solo_chain: the model shows ONE chain to the kernels)
         const int po = parity | ((h->solo_chain < 0) ? 2 : 0);
@@ -1096,7 +1087,7 @@ int LPFN(elph_fast_cg_ap)(elph_handle_s *h, const CgBufs &B, int nrhs, int parit
 #undef LAUNCH_CHUNK
 #undef CHUNK_PX_BRANCH
 #undef CHUNK_PX_SSH_BRANCH
-        return check_launch_f("k_cg_ap_chunk");
+        return elph_launch_check("k_cg_ap_chunk");
     }
     if (px) { elph_set_error("k_cg_ap_fast: the p/x-fused iteration exists in the chunked kernel only"); return ELPH_E_STATE; }
     const dim3 grid(xcd_grid(h, nrhs));
@@ -1104,7 +1095,7 @@ int LPFN(elph_fast_cg_ap)(elph_handle_s *h, const CgBufs &B, int nrhs, int parit
         if (ssh) hipLaunchKernelGGL((k_cg_ap_fast<NPL, true>), grid, dim3(WAVE), shm, h->stream, B, m, parity);
         else hipLaunchKernelGGL((k_cg_ap_fast<NPL, false>), grid, dim3(WAVE), shm, h->stream, B, m, parity);
     });
-    return check_launch_f("k_cg_ap_fast");
+    return elph_launch_check("k_cg_ap_fast");
 }
 
 int LPFN(elph_fast_cg_xr)(elph_handle_s *h, const CgBufs &B, int nrhs, int parity) {
@@ -1112,7 +1103,7 @@ int LPFN(elph_fast_cg_xr)(elph_handle_s *h, const CgBufs &B, int nrhs, int parit
     DISPATCH_NPL_F(h->npl, {
         hipLaunchKernelGGL((k_cg_xr_fast<NPL>), grid, dim3(WAVE), 0, h->stream, B, (int)h->N, (int)h->L, parity);
     });
-    return check_launch_f("k_cg_xr_fast");
+    return elph_launch_check("k_cg_xr_fast");
 }
 
 
@@ -1127,7 +1118,7 @@ int LPFN(elph_fast_kpm_cheb_lds)(elph_handle_s *h, int nrhs, const CgState *st, 
         hipLaunchKernelGGL((k_kpm_cheb_ri<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3(2 * WAVE), shm, h->stream, h->d_nu, K, m,
                            Lo2, st, rz_part, nrz, rr_part);
     });
-    return check_launch_f("k_kpm_cheb_ri");
+    return elph_launch_check("k_kpm_cheb_ri");
 }
 
 #undef DISPATCH_NPL_F

@@ -192,15 +192,6 @@ __device__ __forceinline__ void kpm_cheb_sq_body(double2 *__restrict__ nu, KpmDe
 
 #endif
 
-static int check_launch_f(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        elph_set_error("launch %s failed: %s", what, hipGetErrorString(e));
-        return ELPH_E_HIP;
-    }
-    return ELPH_OK;
-}
-
 // ---- the per-count launchers (cg_fast_impl.inc, one translation unit each) and the dispatch on h->npl -----------------------------
 #define LP_DECL(K)                                                                                             \
     int elph_fast_mul_n##K(elph_handle_s *h, int which, double *yS, const double *vS, int nvec);               \
@@ -349,24 +340,24 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, 
         } else if (P == 2) { if (h->kpm.sq_chain_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
         else        { if (h->kpm.sq_chain_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
 #undef SQ_LAUNCH
-        return check_launch_f("k_kpm_cheb_sq");
+        return elph_launch_check("k_kpm_cheb_sq");
     }
     if (form == REG_SQ_GRID) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
                            h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
-        return check_launch_f("k_kpm_cheb_sq(grid)");
+        return elph_launch_check("k_kpm_cheb_sq(grid)");
     }
     if (form == REG_HC_GRID) {
 #define HG_LAUNCH(NV) hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, false, NV>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
                                          h->d_nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
         if (hgn == 2) HG_LAUNCH(2); else if (hgn == 4) HG_LAUNCH(4); else HG_LAUNCH(8);
 #undef HG_LAUNCH
-        return check_launch_f("k_kpm_cheb_sq(honeycomb grid)");
+        return elph_launch_check("k_kpm_cheb_sq(honeycomb grid)");
     }
     if (form == REG_HC12) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
                            h->d_nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
-        return check_launch_f("k_kpm_cheb_sq(honeycomb)");
+        return elph_launch_check("k_kpm_cheb_sq(honeycomb)");
     }
 #else
     (void)reg;

@@ -1,0 +1,150 @@
+// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5) and bondcorr.hip (bonds, N = 2):
+// the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group does with its one
+// accumulator allocation [lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's accumulator is
+// [L0][L1][L2][L3][n_p] doubles, first index fastest, L0 = L + 1 (time-dependent, tau = beta included) or 1 (equal-time).
+#pragma once
+
+#include <algorithm>
+#include <vector>
+
+#include "elph_internal.h"
+
+template <int N>
+struct CorrReq {                // by value into the kernels
+    double *acc[N];
+    const int *pairs[N];        // [np][2] 0-based
+    int np[N], L0[N];           // np = 0: not measured
+};
+
+// the words in which the two groups' messages differ
+struct CorrWords {
+    const char *prefix;         // "measurements" / "bond correlations"
+    const char *index;          // what a pair names: "orbital" / "bond"
+    const char *no_pair;        // "with no orbital pair" / "with no pair of bonds"
+};
+
+template <int N>
+struct CorrPlan {
+    CorrReq<N> req{};           // np, L0 from corr_plan; acc, pairs from corr_upload
+    std::vector<int> prs;       // every request's pairs, 0-based, concatenated
+    size_t off[N] = {}, pair_off[N] = {};      // of a correlation in acc / of its pairs in prs
+    size_t total = 0;           // doubles of acc: lead + the measured correlations
+    size_t fold_max = 0;        // elements of the largest correlation
+    int nc = 1, npairs = 0;     // cells; listed pairs of all requests
+    int *pairs = nullptr;       // device: prs
+    double *acc = nullptr;      // device: [max(total, 1)]
+    size_t count(int c) const { return (size_t)req.L0[c] * nc * req.np[c]; }
+};
+
+// measure / time_dependent / npairs / pairs (1-based, the requests' lists one after another) of a create call into P.  A pair's indices
+// run over 1..limit; `lead` doubles precede the first correlation.  Pure: no HIP call, so a bad request fails before anything is allocated.
+template <int N>
+int corr_plan(CorrPlan<N> &P, const CorrWords &w, const char *const *names, const int *measure, const int *time_dependent, const int *npairs,
+              const int *pairs, int limit, int L, int nc, size_t lead) {
+    P = CorrPlan<N>();
+    P.nc = nc;
+    P.total = lead;
+    size_t at = 0;
+    for (int c = 0; c < N; ++c) {
+        P.req.np[c] = 0; P.req.L0[c] = 1;
+        if (!measure[c]) continue;
+        if (npairs[c] < 1 || !pairs) { elph_set_error("%s: %s is requested %s", w.prefix, names[c], w.no_pair); return ELPH_E_ARG; }
+        for (int p = 0; p < npairs[c]; ++p)
+            for (int k = 0; k < 2; ++k) {
+                const int o = pairs[2 * (at + p) + k];
+                if (o < 1 || o > limit) {
+                    elph_set_error("%s: %s pair %d names %s %d, outside 1..%d", w.prefix, names[c], p + 1, w.index, o, limit);
+                    return ELPH_E_ARG;
+                }
+                P.prs.push_back(o - 1);
+            }
+        P.pair_off[c] = 2 * at;
+        at += (size_t)npairs[c];
+        P.req.np[c] = npairs[c];
+        P.req.L0[c] = time_dependent[c] ? L + 1 : 1;
+        P.off[c] = P.total;
+        P.total += P.count(c);
+        P.fold_max = std::max(P.fold_max, P.count(c));
+    }
+    P.npairs = (int)at;
+    return ELPH_OK;
+}
+
+template <class T>
+int corr_alloc(T **p, size_t n) {
+    HIPCHK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
+    return ELPH_OK;
+}
+
+inline int corr_up(void *dst, const void *src, size_t bytes) {
+    if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return ELPH_OK;
+}
+
+// keeps the first error of a chain of calls; true while there is none
+struct CorrFirstError {
+    int rc = ELPH_OK;
+    bool operator()(int r) { if (rc == ELPH_OK) rc = r; return rc == ELPH_OK; }
+};
+
+template <int N>
+int corr_alloc(CorrPlan<N> &P) {
+    RC(corr_alloc(&P.pairs, P.prs.size()));
+    return corr_alloc(&P.acc, P.total);
+}
+
+// the pairs to the device, the accumulator zeroed, req bound to the two allocations
+template <int N>
+int corr_upload(CorrPlan<N> &P, const char *prefix) {
+    RC(corr_up(P.pairs, P.prs.data(), P.prs.size() * sizeof(int)));
+    if (hipMemset(P.acc, 0, std::max<size_t>(P.total, 1) * sizeof(double)) != hipSuccess) { elph_set_error("%s: hipMemset failed", prefix); return ELPH_E_HIP; }
+    for (int c = 0; c < N; ++c) {
+        P.req.acc[c] = P.acc + P.off[c];
+        P.req.pairs[c] = P.pairs + P.pair_off[c];
+    }
+    return ELPH_OK;
+}
+
+// one copy of the accumulator into host; every measured correlation with an output widened to interleaved complex
+template <int N>
+int corr_fetch(elph_handle_s *h, const CorrPlan<N> &P, std::vector<double> &host, double *const *outs) {
+    host.resize(std::max<size_t>(P.total, 1));
+    HIPCHK(hipMemcpyAsync(host.data(), P.acc, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < N; ++c) {
+        if (!outs[c] || !P.req.np[c]) continue;
+        const double *src = host.data() + P.off[c];
+        for (size_t i = 0, cnt = P.count(c); i < cnt; ++i) { outs[c][2 * i] = src[i]; outs[c][2 * i + 1] = 0.0; }
+    }
+    return ELPH_OK;
+}
+
+template <int N>
+int corr_reset(elph_handle_s *h, const CorrPlan<N> &P) {
+    HIPCHK(hipMemsetAsync(P.acc, 0, std::max<size_t>(P.total, 1) * sizeof(double), h->stream));
+    return ELPH_OK;
+}
+
+inline void corr_free(std::initializer_list<void *> ptrs) {
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+}
+
+// ---- the state checks of both groups' entry points
+inline int corr_need(const void *state, const char *create) {
+    if (!state) { elph_set_error("%s has not been called", create); return ELPH_E_STATE; }
+    return ELPH_OK;
+}
+
+inline int corr_refuse_chains(const elph_handle_s *h, const char *prefix) {
+    if (h->nchains > 1) {
+        elph_set_error("%s: %d chains are resident in this handle; one configuration per handle is measured", prefix, h->nchains);
+        return ELPH_E_UNSUPPORTED;
+    }
+    return ELPH_OK;
+}
+
+inline int corr_refuse_handle(const elph_handle_s *h, const char *prefix) {
+    if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("%s: the SSH model is not supported (Holstein only)", prefix); return ELPH_E_UNSUPPORTED; }
+    if (h->shard || h->is_slab) { elph_set_error("%s: sharded and slab handles are not supported", prefix); return ELPH_E_UNSUPPORTED; }
+    return corr_refuse_chains(h, prefix);
+}

@@ -169,15 +169,6 @@ __global__ void __launch_bounds__(WAVE) k_dft_inv_tab(double *__restrict__ out, 
     }
 }
 
-static int dft_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        elph_set_error("launch %s failed: %s", what, hipGetErrorString(e));
-        return ELPH_E_HIP;
-    }
-    return ELPH_OK;
-}
-
 // Single-solve shapes (2 outputs per wave: many waves for the latency-bound case).  These kernels are bound by the
 // scalar twiddle stream (106 SGPRs hold < 30 twiddles); a wider shape (8 outputs per wave) was measured ~15 % SLOWER in
 // a batch, so batches go to the matrix-core GEMM form in dft_mfma.hip instead.
@@ -192,7 +183,7 @@ int elph_dft_fwd_twisted(elph_handle_s *h, double2 *nu, const double *vS, int N,
     hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, false>),
                            dim3((unsigned)nst, (unsigned)((Lo2 + DFT_KPT - 1) / DFT_KPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, nu,
                            vS, h->d_Tk, N, L, Lo2, dft_pad(L, 2 * DFT_TC), st, (const double *)nullptr, 0.0);
-    return dft_check("k_dft_fwd_tab(twisted)");
+    return elph_launch_check("k_dft_fwd_tab(twisted)");
 }
 
 // out = Re( conj(Theta) .* iFFT(nu) ) from the half spectrum; rz_part (optional) receives partial r.out sums
@@ -205,7 +196,7 @@ int elph_dft_inv_twisted(elph_handle_s *h, double *outS, const double2 *nu, int 
     hipLaunchKernelGGL((k_dft_inv_tab<DFT_TPT, DFT_KC>),
                            dim3((unsigned)nst, (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, outS,
                            nu, h->d_Tt, N, L, Lo2, dft_pad(Lo2, 2 * DFT_KC), st, rvec, rz_part, nrz);
-    return dft_check("k_dft_inv_tab(twisted)");
+    return elph_launch_check("k_dft_inv_tab(twisted)");
 }
 
 // u[rhs][k][s] *= (D[k][s]^p + D[L-k][s]^p)/2  — the symmetrised diagonal of fourier_accelerate! between the two GEMM-form
@@ -230,7 +221,7 @@ int elph_dft_accel(elph_handle_s *h, double *outS, const double *inS, const doub
         if (rc) return rc;
         const long long total = (long long)nvec * Lh * N;
         hipLaunchKernelGGL(k_dft_diag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, u, diagS, power, N, L, Lh, total);
-        rc = dft_check("k_dft_diag");
+        rc = elph_launch_check("k_dft_diag");
         if (rc) return rc;
         return elph_dft_big_inv(h, false, outS, u, N, nvec, nullptr, nullptr, 0);
     }
@@ -239,7 +230,7 @@ int elph_dft_accel(elph_handle_s *h, double *outS, const double *inS, const doub
         if (rc) return rc;
         const long long total = (long long)nvec * Lh * N;
         hipLaunchKernelGGL(k_dft_diag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, u, diagS, power, N, L, Lh, total);
-        rc = dft_check("k_dft_diag");
+        rc = elph_launch_check("k_dft_diag");
         if (rc) return rc;
         return elph_dft_mfma_inv(h, 1, outS, u, N, nvec, nullptr, nullptr, nullptr, 0);
     }
@@ -248,7 +239,7 @@ int elph_dft_accel(elph_handle_s *h, double *outS, const double *inS, const doub
     hipLaunchKernelGGL((k_dft_inv_tab<DFT_TPT, DFT_KC>), dim3((unsigned)nst, (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nvec),
                        dim3(WAVE), 0, h->stream, outS, u, h->d_Pt, N, L, Lh, dft_pad(Lh, 2 * DFT_KC), (const CgState *)nullptr,
                        (const double *)nullptr, (double *)nullptr, 0);
-    return dft_check("fourier_accelerate");
+    return elph_launch_check("fourier_accelerate");
 }
 
 // nu[rhs][k][s] (half spectrum, k <= L/2) = FFT_t(v)[k]  — plain (untwisted) transform, no diagonal
@@ -259,7 +250,7 @@ int elph_dft_fwd_plain(elph_handle_s *h, double2 *nu, const double *vS, int N, i
     hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, true>),
                            dim3((unsigned)nst, (unsigned)((Lh + DFT_KPT - 1) / DFT_KPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, nu, vS,
                            h->d_Pk, N, L, Lh, dft_pad(L, 2 * DFT_TC), (const CgState *)nullptr, (const double *)nullptr, 0.0);
-    return dft_check("k_dft_fwd_tab(plain)");
+    return elph_launch_check("k_dft_fwd_tab(plain)");
 }
 
 // out = Re iFFT(nu) from the half spectrum k <= L/2 (Hermitian weights and 1/L in the table)
@@ -271,7 +262,7 @@ int elph_dft_inv_plain(elph_handle_s *h, double *outS, const double2 *nu, int N,
                            dim3((unsigned)nst, (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, outS,
                            nu, h->d_Pt, N, L, Lh, dft_pad(Lh, 2 * DFT_KC), (const CgState *)nullptr, (const double *)nullptr,
                            (double *)nullptr, 0);
-    return dft_check("k_dft_inv_tab(plain)");
+    return elph_launch_check("k_dft_inv_tab(plain)");
 }
 
 // host: build the four twiddle tables with exact index reduction

@@ -22,19 +22,7 @@
 #include "elph_internal.h"
 
 #define WAVE ELPH_WAVE
-#define RC(call)                \
-    do {                        \
-        int _rc = (call);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
 namespace {
-
-int big_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
 
 // u[t][s] = (TWISTED ? Theta_t : 1) * v[t][s]
 template <bool TWISTED>
@@ -300,12 +288,12 @@ int big_fft(elph_handle_s *h, int N, int nvec) {
         hipLaunchKernelGGL((k_big_direct<INV>), grid, dim3(WAVE), 0, h->stream, h->d_big_b, h->d_big_a, h->d_big_TW, N, L, INV ? 1.0 / (double)L : 1.0);
         hipError_t e = hipMemcpyAsync(h->d_big_a, h->d_big_b, (size_t)nvec * L * N * sizeof(double2), hipMemcpyDeviceToDevice, h->stream);
         if (e != hipSuccess) { elph_set_error("dft_big: copy: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-        return big_check(INV ? "k_big_direct(inverse)" : "k_big_direct(forward)");
+        return elph_launch_check(INV ? "k_big_direct(inverse)" : "k_big_direct(forward)");
     }
     hipLaunchKernelGGL((k_big_step1<INV>), grid, dim3(WAVE), 0, h->stream, h->d_big_b, h->d_big_a, h->d_big_W1, h->d_big_TW, N, L, L1, L2);
     hipLaunchKernelGGL((k_big_step2<INV>), grid, dim3(WAVE), 0, h->stream, h->d_big_a, h->d_big_b, h->d_big_W2, N, L, L1, L2,
                        INV ? 1.0 / (double)L : 1.0);
-    return big_check(INV ? "big_fft(inverse)" : "big_fft(forward)");
+    return elph_launch_check(INV ? "big_fft(inverse)" : "big_fft(forward)");
 }
 
 }  // namespace
@@ -372,7 +360,7 @@ int elph_dft_big_fwd(elph_handle_s *h, bool twisted, double2 *nu, const double *
             hipLaunchKernelGGL((k_big_s1<false, false>), g1, dim3(WAVE), 0, h->stream, h->d_big_b, vS, (const double2 *)nullptr, h->d_big_W1, h->d_big_TW, h->d_big_TH, N, L, L1, L2, K);
             hipLaunchKernelGGL((k_big_s2<false, false>), g2, dim3(WAVE), 0, h->stream, nu, (double *)nullptr, h->d_big_b, h->d_big_W2, h->d_big_TH, N, L, L1, L2, K, 1.0, (const double *)nullptr, (double *)nullptr, 0);
         }
-        return big_check("k_big_s1/s2(forward)");
+        return elph_launch_check("k_big_s1/s2(forward)");
     }
     const long long total = (long long)nvec * L * N;
     if (twisted) hipLaunchKernelGGL((k_big_load<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_big_a, vS, h->d_big_TH, N, L, total);
@@ -380,7 +368,7 @@ int elph_dft_big_fwd(elph_handle_s *h, bool twisted, double2 *nu, const double *
     RC(big_fft<false>(h, N, nvec));
     const long long th = (long long)nvec * K * N;
     hipLaunchKernelGGL(k_big_take, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, h->stream, nu, h->d_big_a, N, L, K, th);
-    return big_check("k_big_take");
+    return elph_launch_check("k_big_take");
 }
 
 int elph_dft_big_inv(elph_handle_s *h, bool twisted, double *outS, const double2 *nu, int N, int nvec, const double *rvec,
@@ -401,7 +389,7 @@ int elph_dft_big_inv(elph_handle_s *h, bool twisted, double *outS, const double2
                 hipLaunchKernelGGL((k_big_s1<true, false>), g1, dim3(WAVE), 0, h->stream, h->d_big_b, (const double *)nullptr, nu, h->d_big_W1, h->d_big_TW, h->d_big_TH, N, L, L1, L2, K);
                 hipLaunchKernelGGL((k_big_s2<true, false>), g2, dim3(WAVE), 0, h->stream, (double2 *)nullptr, outS, h->d_big_b, h->d_big_W2, h->d_big_TH, N, L, L1, L2, K, scale, rvec, rz_part, nrz);
             }
-            return big_check("k_big_s1/s2(inverse)");
+            return elph_launch_check("k_big_s1/s2(inverse)");
         }
     }
     const long long total = (long long)nvec * L * N;
@@ -411,5 +399,5 @@ int elph_dft_big_inv(elph_handle_s *h, bool twisted, double *outS, const double2
     const dim3 grid((unsigned)L, (unsigned)nvec);
     if (twisted) hipLaunchKernelGGL((k_big_store<true>), grid, dim3(WAVE), 0, h->stream, outS, h->d_big_a, h->d_big_TH, N, L, rvec, rz_part, nrz);
     else hipLaunchKernelGGL((k_big_store<false>), grid, dim3(WAVE), 0, h->stream, outS, h->d_big_a, h->d_big_TH, N, L, rvec, rz_part, nrz);
-    return big_check("k_big_store");
+    return elph_launch_check("k_big_store");
 }

@@ -683,12 +683,6 @@ int pick_nt(int need) {
     return 0;
 }
 
-int mf_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
-
 template <bool INV>
 int launch(elph_handle_s *h, int nt, double *out, const double *in, const double *W, int N, int K, int groups, int nrhs,
            const CgState *st, const double *rvec, double *rz_part, int nrz) {
@@ -701,7 +695,7 @@ int launch(elph_handle_s *h, int nt, double *out, const double *in, const double
         default: elph_set_error("dft_mfma: no kernel for %d reduction tiles", nt); return ELPH_E_UNSUPPORTED;
     }
 #undef MF_CASE
-    return mf_check(INV ? "k_dft_mfma(inverse)" : "k_dft_mfma(forward)");
+    return elph_launch_check(INV ? "k_dft_mfma(inverse)" : "k_dft_mfma(forward)");
 }
 
 template <bool INV>
@@ -716,7 +710,7 @@ int launch_1(elph_handle_s *h, int nt, double *out, const double *in, const doub
         default: elph_set_error("dft_mfma_1: no kernel for %d reduction tiles", nt); return ELPH_E_UNSUPPORTED;
     }
 #undef MF1_CASE
-    return mf_check(INV ? "k_dft_mfma_1(inverse)" : "k_dft_mfma_1(forward)");
+    return elph_launch_check(INV ? "k_dft_mfma_1(inverse)" : "k_dft_mfma_1(forward)");
 }
 
 template <bool INV, bool XR = false>
@@ -748,7 +742,7 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
 #undef R2S_CASE
 #undef R2S_LAUNCH
         if (attr_rc != hipSuccess) { elph_set_error("hipFuncSetAttribute(dynamic LDS %zu B) failed: %s", panel, hipGetErrorString(attr_rc)); return ELPH_E_HIP; }
-        return mf_check(INV ? "k_dft_mfma_r2s(inverse)" : "k_dft_mfma_r2s(forward)");
+        return elph_launch_check(INV ? "k_dft_mfma_r2s(inverse)" : "k_dft_mfma_r2s(forward)");
     }
     if (PXF.p) { elph_set_error("dft_mfma: the p/x-fused inverse exists in the streaming form only"); return ELPH_E_STATE; }
 #define R2_CASE(NTV) case NTV: hipLaunchKernelGGL((k_dft_mfma_r2<NTV, INV, XR>), grid, block, 0, h->stream, out, in, T.W, tw, N, L, st, rvec, rz_part, nrz, X); break;
@@ -757,7 +751,7 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
         default: elph_set_error("dft_mfma_r2: no register-resident kernel for %d reduction tiles (panels beyond 144 KB need L <= 256)", T.nt); return ELPH_E_UNSUPPORTED;
     }
 #undef R2_CASE
-    return mf_check(INV ? "k_dft_mfma_r2(inverse)" : "k_dft_mfma_r2(forward)");
+    return elph_launch_check(INV ? "k_dft_mfma_r2(inverse)" : "k_dft_mfma_r2(forward)");
 }
 
 }  // namespace

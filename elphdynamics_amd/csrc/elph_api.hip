@@ -28,6 +28,12 @@ void elph_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+int elph_launch_check(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
+    return ELPH_OK;
+}
+
 extern "C" const char *elph_last_error(void) { return g_err; }
 extern "C" int elph_abi_version(void) { return ELPH_ABI_VERSION; }
 // the build record: written by elphdynamics_amd/build.py into a translation unit of its own at every link
@@ -39,21 +45,6 @@ extern "C" int elph_device_count(void) {
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-#define CHECK_H(h)                                    \
-    do {                                              \
-        if (!(h)) {                                   \
-            elph_set_error("null handle");            \
-            return ELPH_E_ARG;                        \
-        }                                             \
-        HIPCHK(hipSetDevice((h)->device));            \
-    } while (0)
-
-#define RC(call)                \
-    do {                        \
-        int _rc = (call);       \
-        if (_rc) return _rc;    \
-    } while (0)
 
 template <class T>
 static int dev_alloc(T **p, size_t n) {

@@ -28,6 +28,7 @@
 #define ELPH_CG_CHUNK 16        // CG iterations between two reads of the CG states by the host (even: ping-pong parity)
 
 void elph_set_error(const char *fmt, ...);
+int elph_launch_check(const char *what);      // elph_api.hip: hipGetLastError after a launch, "launch <what> failed: ..." into the error text
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -36,6 +37,18 @@ void elph_set_error(const char *fmt, ...);
             elph_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
             return ELPH_E_HIP;                                                               \
         }                                                                                    \
+    } while (0)
+
+#define RC(call)                \
+    do {                        \
+        int _rc = (call);       \
+        if (_rc) return _rc;    \
+    } while (0)
+
+#define CHECK_H(h)                                                    \
+    do {                                                              \
+        if (!(h)) { elph_set_error("null handle"); return ELPH_E_ARG; } \
+        HIPCHK(hipSetDevice((h)->device));                            \
     } while (0)
 
 // Model description handed to kernels by value.
@@ -432,12 +445,15 @@ void elph_bond_free(elph_handle_s *h);                                      // b
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;
     bool have_vectors;
-    const double *R, *X;       // [nv][ndim] layout S
     const double *C;           // [4][L][ns*N] the real correlations of the last elph_i_greens_setup_dev
     const double2 *tw;         // [L1 + L2 + L3] exp(-2πi j/Lx), the twiddles of the cell-axis DFTs
 };
 int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v);
 int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand);      // no copy to the host, no synchronisation
+// one step of the loop over pairs i < j of the nv vectors (make_measurements!, Measurements.jl:550-560): setup_dev of the pair, the doubled
+// complex copies refreshed for the last pair only (elph_greens_dev_arrays), and the pair's vectors x = M⁻¹r, r
+struct ElphGreensPair { const double *X1, *X2, *R1, *R2; };
+int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p);
 int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS);
 int elph_launch_r2s(elph_handle_s *h, double *dstS, const double *srcR, int nvec, int ncols = 0);
 int elph_launch_s2r(elph_handle_s *h, double *dstR, const double *srcS, int nvec, int ncols = 0);

@@ -24,18 +24,6 @@
 #include "cell_dft_dev.h"
 #include "elph_internal.h"
 
-#define RC(call)                \
-    do {                        \
-        int _rc = (call);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
-#define CHECK_H(h)                                                    \
-    do {                                                              \
-        if (!(h)) { elph_set_error("null handle"); return ELPH_E_ARG; } \
-        HIPCHK(hipSetDevice((h)->device));                            \
-    } while (0)
-
 namespace {
 
 constexpr int TPB = 256;
@@ -55,12 +43,6 @@ struct GreensState {
 };
 
 GreensState *gs_of(elph_handle_s *h) { return (GreensState *)h->greens; }
-
-int gr_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
 
 // The eight fields of setup! (GreensFunctions.jl:261-284), pointwise, layout S:
 //   0: (M⁻¹r₁ + M⁻¹r₂)/√2   1: (r₁ + r₂)/√2            — antiperiodic pair (G[Δ,0])
@@ -305,7 +287,7 @@ int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand) {
     const long long n = (long long)nd;
     hipLaunchKernelGGL(k_gr_fields, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, g->f, g->X + (size_t)(n1 - 1) * nd,
                        g->X + (size_t)(n2 - 1) * nd, g->R + (size_t)(n1 - 1) * nd, g->R + (size_t)(n2 - 1) * nd, n);
-    RC(gr_check("k_gr_fields"));
+    RC(elph_launch_check("k_gr_fields"));
     RC(elph_dft_fwd_twisted(h, g->nuA, g->f, N, 2, nullptr));
     RC(elph_dft_fwd_plain(h, g->nuP, g->f + 2 * nd, N, 6));
     // total normalisation 1/(L·Nc)² (see header): 1/L comes from the inverse τ tables, the rest here
@@ -314,18 +296,29 @@ int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand) {
     const long long ystride = (long long)Lh * ncol;
     hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lo2, 1), dim3(TPB), shm, h->stream, g->Y, g->nuA, g->nuA + (size_t)Lo2 * N, Lo2, N, ns,
                        g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
-    RC(gr_check("k_gr_spatial(twisted)"));
+    RC(elph_launch_check("k_gr_spatial(twisted)"));
     hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 3), dim3(TPB), shm, h->stream, g->Y + ystride, g->nuP, g->nuP + (size_t)Lh * N, Lh, N,
                        ns, g->L1, g->L2, g->L3, g->tw, norm, 2LL * Lh * N, ystride);
-    RC(gr_check("k_gr_spatial(plain)"));
+    RC(elph_launch_check("k_gr_spatial(plain)"));
     RC(elph_dft_inv_twisted(h, g->C, g->Y, ncol, 1, nullptr, nullptr, nullptr, 0));
     // the plain inverse walks [rhs][Lh][ncol] spectra and writes [rhs][L][ncol]
     RC(elph_dft_inv_plain(h, g->C + (size_t)L * ncol, g->Y + ystride, ncol, 3));
     if (expand) {
         hipLaunchKernelGGL(k_gr_out, dim3((unsigned)((ncol + 31) / 32), (unsigned)((L + 31) / 32), 4), dim3(TPB), 0, h->stream, g->out, g->C, L,
                            ncol);
-        RC(gr_check("k_gr_out"));
+        RC(elph_launch_check("k_gr_out"));
     }
+    return ELPH_OK;
+}
+
+// One step of the loop over pairs i < j of the vectors: the pair's setup (the doubled complex copies for the last pair only) and vectors.
+int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p) {
+    RC(need_greens(h));
+    const GreensState *g = gs_of(h);
+    RC(elph_i_greens_setup_dev(h, i, j, i == g->nv - 1));
+    const size_t nd = (size_t)h->ndim;
+    p->X1 = g->X + (size_t)(i - 1) * nd; p->X2 = g->X + (size_t)(j - 1) * nd;
+    p->R1 = g->R + (size_t)(i - 1) * nd; p->R2 = g->R + (size_t)(j - 1) * nd;
     return ELPH_OK;
 }
 
@@ -335,7 +328,7 @@ int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
     const GreensState *g = gs_of(h);
     v->ns = g->ns; v->L1 = g->L1; v->L2 = g->L2; v->L3 = g->L3; v->nc = g->nc; v->nv = g->nv;
     v->have_vectors = g->have_vectors;
-    v->R = g->R; v->X = g->X; v->C = g->C; v->tw = g->tw;
+    v->C = g->C; v->tw = g->tw;
     return ELPH_OK;
 }
 
@@ -351,7 +344,7 @@ int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS)
     const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
     hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 1), dim3(TPB), spatial_lds_bytes(h, g), h->stream, g->Y, g->nuP, g->nuP, Lh, N, ns,
                        g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
-    RC(gr_check("k_gr_spatial(autocorrelation)"));
+    RC(elph_launch_check("k_gr_spatial(autocorrelation)"));
     RC(elph_dft_inv_plain(h, outS, g->Y, ncol, 1));
     return ELPH_OK;
 }

@@ -15,12 +15,6 @@
 
 #include "elph_internal.h"
 
-#define RC(call)                \
-    do {                        \
-        int _rc = (call);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
 namespace {
 
 constexpr int TPB = 256;
@@ -507,15 +501,6 @@ void elph_hmc_free(elph_handle_s *h) {
     delete st;
     h->hmc = nullptr;
 }
-
-#define CHECK_H(h)                                    \
-    do {                                              \
-        if (!(h)) {                                   \
-            elph_set_error("null handle");            \
-            return ELPH_E_ARG;                        \
-        }                                             \
-        HIPCHK(hipSetDevice((h)->device));            \
-    } while (0)
 
 static int hmc_create_core(elph_handle_s *h, int nchains, int nf, bool ssh, const double *omega, const double *omega4, double dtau,
                            const double *fa_mass) {

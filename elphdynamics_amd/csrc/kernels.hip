@@ -1056,22 +1056,13 @@ static inline int gen_npl(const elph_handle_s *h) { const int bs = gen_bs(h); re
         default: { constexpr int NPL = 8; CALL; } break;          \
     }
 
-static int check_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        elph_set_error("launch %s failed: %s", what, hipGetErrorString(e));
-        return ELPH_E_HIP;
-    }
-    return ELPH_OK;
-}
-
 // ncols: columns of the vectors (0 = the lattice sites; SSH phonon fields have Nph columns)
 int elph_launch_r2s(elph_handle_s *h, double *dstS, const double *srcR, int nvec, int ncols) {
     // in: rows = N sites, cols = L
     const int N = ncols > 0 ? ncols : (int)h->N;
     dim3 grid((unsigned)((h->L + 31) / 32), (unsigned)((N + 31) / 32), (unsigned)nvec);
     hipLaunchKernelGGL(k_transpose, grid, dim3(32, 8), 0, h->stream, dstS, srcR, N, (int)h->L);
-    return check_launch("k_transpose(r2s)");
+    return elph_launch_check("k_transpose(r2s)");
 }
 
 int elph_launch_s2r(elph_handle_s *h, double *dstR, const double *srcS, int nvec, int ncols) {
@@ -1079,19 +1070,19 @@ int elph_launch_s2r(elph_handle_s *h, double *dstR, const double *srcS, int nvec
     const int N = ncols > 0 ? ncols : (int)h->N;
     dim3 grid((unsigned)((N + 31) / 32), (unsigned)((h->L + 31) / 32), (unsigned)nvec);
     hipLaunchKernelGGL(k_transpose, grid, dim3(32, 8), 0, h->stream, dstR, srcS, (int)h->L, N);
-    return check_launch("k_transpose(s2r)");
+    return elph_launch_check("k_transpose(s2r)");
 }
 
 int elph_launch_expV(elph_handle_s *h, const double *xR, double dtau, int chain) {
     dim3 grid((unsigned)((h->L + 31) / 32), (unsigned)((h->N + 31) / 32), 1);
     hipLaunchKernelGGL(k_expV, grid, dim3(32, 8), 0, h->stream, h->d_E + (size_t)chain * (size_t)h->ndim, xR, h->d_lam, (int)h->N, (int)h->L, dtau);
-    return check_launch("k_expV");
+    return elph_launch_check("k_expV");
 }
 
 int elph_launch_zero(elph_handle_s *h, double *p, int64_t n) {
     if (n <= 0) return ELPH_OK;
     hipLaunchKernelGGL(k_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p, (long long)n);
-    return check_launch("k_zero");
+    return elph_launch_check("k_zero");
 }
 
 int elph_launch_mul(elph_handle_s *h, int which, double *yS, const double *vS, int nvec) {
@@ -1105,7 +1096,7 @@ int elph_launch_mul(elph_handle_s *h, int which, double *yS, const double *vS, i
         else if (which == 1) hipLaunchKernelGGL((k_mul<NPL, 1>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, yS, vS, m);
         else hipLaunchKernelGGL((k_mul<NPL, 2>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, yS, vS, m);
     });
-    return check_launch("k_mul");
+    return elph_launch_check("k_mul");
 }
 
 static CgBufs make_bufs(elph_handle_s *h, int nrhs) {
@@ -1143,7 +1134,7 @@ int elph_launch_ssh_update(elph_handle_s *h, const double *x_dev, int nph, const
         hipLaunchKernelGGL(k_ssh_expmu, dim3((unsigned)((h->N + 255) / 256), (unsigned)nch), dim3(256), 0, h->stream, h->d_E,
                            per ? h->d_mu_ch : h->d_lam, (int)h->N, dtau, per ? (int)h->N : 0);
     }
-    return check_launch("ssh update_model");
+    return elph_launch_check("ssh update_model");
 }
 
 int elph_launch_ssh_scatter(elph_handle_s *h, double *F_dev, const double *q_dev, const double *x_dev, const double *par_dev,
@@ -1152,20 +1143,20 @@ int elph_launch_ssh_scatter(elph_handle_s *h, double *F_dev, const double *q_dev
     if (n == 0) return ELPH_OK;
     hipLaunchKernelGGL(k_ssh_scatter, dim3((unsigned)((n + 255) / 256), (unsigned)nch), dim3(256), 0, h->stream, F_dev, q_dev, x_dev, par_dev, cb0_dev,
                        nph, (int)h->nb, (int)h->L, dtau, tau_major, scale);
-    return check_launch("k_ssh_scatter");
+    return elph_launch_check("k_ssh_scatter");
 }
 
 int elph_launch_cs_bar(elph_handle_s *h, double *cbar_dev, double *sbar_dev, int nch) {
     hipLaunchKernelGGL(k_cs_bar, dim3((unsigned)((h->nb + 255) / 256), (unsigned)nch), dim3(256), 0, h->stream, cbar_dev, sbar_dev, h->d_c, h->d_s,
                        (int)h->nb, (int)h->L);
-    return check_launch("k_cs_bar");
+    return elph_launch_check("k_cs_bar");
 }
 
 // Ē of the first `nch` resident chains in one launch
 int elph_launch_ebar(elph_handle_s *h, int nch) {
     hipLaunchKernelGGL(k_ebar, dim3((unsigned)((h->N + 63) / 64), (unsigned)nch), dim3(256), 0, h->stream, h->kpm.d_Ebar, h->d_E,
                        (int)h->N, (int)h->L);
-    return check_launch("k_ebar");
+    return elph_launch_check("k_ebar");
 }
 
 // The kernels of one CG iteration for nrhs right-hand sides on one stream (in_flight: on all streams — the parts of a split batch), decided
@@ -1246,7 +1237,7 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
             const long long n = (long long)nrhs * N * L;
             hipLaunchKernelGGL(k_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, zS, rS, n);
         }
-        return check_launch("kpm identity");
+        return elph_launch_check("kpm identity");
     }
     // inside CG the solve's plan; a standalone apply takes its Chebyshev form from the same rule
     const CgPlan pl = cg_mode ? h->plan : elph_plan_cg(h, nrhs, true, nrhs);
@@ -1301,7 +1292,7 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         int rcd = elph_dft_inv_twisted(h, zS, h->d_nu, N, nrhs, st, fuse ? rS : nullptr, fuse ? B.rz : nullptr, B.nrz);
         if (rcd) return rcd;
     }
-    return check_launch("kpm apply");
+    return elph_launch_check("kpm apply");
 }
 
 int elph_launch_rz_partials(elph_handle_s *h, int nrhs);
@@ -1323,7 +1314,7 @@ int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero) {
     const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
     double *bb = h->d_part + 3 * P;
     hipLaunchKernelGGL(k_cg_init, dim3((unsigned)L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->d_b, h->d_tmp, bb, N, L);
-    rc = check_launch("k_cg_init");
+    rc = elph_launch_check("k_cg_init");
     if (rc) return rc;
     if (use_prec) {
         // z0 = P^-1 r0, p0 = z0, rho0 = r0.z0 (IterativeSolvers.jl:182-189); once per solve
@@ -1332,11 +1323,11 @@ int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero) {
         rc = elph_launch_rz_partials(h, nrhs);
         if (rc) return rc;
         hipLaunchKernelGGL(k_cg_init_prec, dim3((unsigned)L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, N, L);
-        rc = check_launch("k_cg_init_prec");
+        rc = elph_launch_check("k_cg_init_prec");
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_cg_state0, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, B, bb, L);
-    return check_launch("k_cg_state0");
+    return elph_launch_check("k_cg_state0");
 }
 
 // partial r.zp into B.rz (slot t = slice sum, rest zero)
@@ -1359,7 +1350,7 @@ int elph_launch_rz_partials(elph_handle_s *h, int nrhs) {
     CgBufs B = make_bufs(h, nrhs);
     hipLaunchKernelGGL(k_rz_part, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, h->d_r, h->d_zp, B.rz,
                        B.nrz, (int)h->N, (int)h->L);
-    return check_launch("k_rz_part");
+    return elph_launch_check("k_rz_part");
 }
 
 // the generic family's k_cg_ap (which = 0; px: its p/x-fused form, which reads the ready p) or k_cg_xr (which = 1)
@@ -1372,13 +1363,13 @@ static int launch_gen(elph_handle_s *h, const CgBufs &B, int nrhs, int which, bo
         DISPATCH_NPL(gen_npl(h), {
             hipLaunchKernelGGL((k_cg_ap<NPL, true>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, parity);
         });
-        return check_launch("k_cg_ap<PX>");
+        return elph_launch_check("k_cg_ap<PX>");
     }
     DISPATCH_NPL(gen_npl(h), {
         if (which == 0) hipLaunchKernelGGL((k_cg_ap<NPL>), grid, dim3((unsigned)gen_bs(h)), shm, h->stream, B, m, parity);
         else hipLaunchKernelGGL((k_cg_xr<NPL>), grid, dim3((unsigned)gen_bs(h)), 0, h->stream, B, N, L, parity);
     });
-    return check_launch(which == 0 ? "k_cg_ap" : "k_cg_xr");
+    return elph_launch_check(which == 0 ? "k_cg_ap" : "k_cg_xr");
 }
 
 // the planned k_cg_ap (px: its p/x-fused form); advances the ping-pong parity
@@ -1428,7 +1419,7 @@ int elph_launch_residual(elph_handle_s *h, int nrhs) {
     hipLaunchKernelGGL(k_resid_part, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, h->d_tmp, h->d_b, pa,
                        pb, (int)h->N, (int)h->L);
     hipLaunchKernelGGL(k_resid_final, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, pa, pb, h->d_scal, (int)h->L);
-    return check_launch("residual");
+    return elph_launch_check("residual");
 }
 
 int elph_launch_tau_to_omega(elph_handle_s *h, double2 *nuS_full, const double *vS) {
@@ -1441,7 +1432,7 @@ int elph_launch_tau_to_omega(elph_handle_s *h, double2 *nuS_full, const double *
     const long long n = (long long)N * L;
     hipLaunchKernelGGL(k_expand_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nuS_full, h->d_nu, N,
                        L, Lo2);
-    return check_launch("tau_to_omega");
+    return elph_launch_check("tau_to_omega");
 }
 
 int elph_launch_omega_to_tau(elph_handle_s *h, double *vS, const double2 *nuS_full) {
@@ -1449,7 +1440,7 @@ int elph_launch_omega_to_tau(elph_handle_s *h, double *vS, const double2 *nuS_fu
     const int nst = (N + WAVE - 1) / WAVE;
     hipLaunchKernelGGL(k_dft_inv_twisted_full, dim3((unsigned)nst, (unsigned)L, 1), dim3(WAVE), 0, h->stream, vS, nuS_full,
                        h->d_theta, N, L);
-    return check_launch("omega_to_tau");
+    return elph_launch_check("omega_to_tau");
 }
 
 int elph_launch_fft_accel(elph_handle_s *h, double *outS, const double *inS, const double *diagS, double power,
@@ -1461,7 +1452,7 @@ int elph_launch_fft_accel(elph_handle_s *h, double *outS, const double *inS, con
 int elph_launch_lambda_rhs(elph_handle_s *h, double *bS, const double *phiS, const double *xS, double dtau, int nch) {
     hipLaunchKernelGGL(k_lambda_rhs, dim3((unsigned)h->L, 2, (unsigned)nch), dim3(WAVE), 0, h->stream, bS, phiS, xS, h->d_lam,
                        (int)h->N, (int)h->L, dtau);
-    return check_launch("k_lambda_rhs");
+    return elph_launch_check("k_lambda_rhs");
 }
 
 int elph_launch_force_holstein(elph_handle_s *h, double *FS, const double *XS, const double *phiS, const double *xS, double dtau,
@@ -1472,7 +1463,7 @@ int elph_launch_force_holstein(elph_handle_s *h, double *FS, const double *XS, c
         hipLaunchKernelGGL((k_force_holstein<NPL>), dim3((unsigned)h->L, (unsigned)nch), dim3((unsigned)gen_bs(h)), shm, h->stream, FS,
                            XS, phiS, xS, h->d_lam, m, dtau);
     });
-    return check_launch("k_force_holstein");
+    return elph_launch_check("k_force_holstein");
 }
 
 int elph_launch_dmdx_holstein(elph_handle_s *h, double *FS, const double *uS, const double *vS, const double *xS, double dtau,
@@ -1483,7 +1474,7 @@ int elph_launch_dmdx_holstein(elph_handle_s *h, double *FS, const double *uS, co
         hipLaunchKernelGGL((k_dmdx_holstein<NPL>), dim3((unsigned)h->L, (unsigned)nch), dim3((unsigned)gen_bs(h)), shm, h->stream, FS, uS, vS, xS,
                            h->d_lam, m, dtau, scale);
     });
-    return check_launch("k_dmdx_holstein");
+    return elph_launch_check("k_dmdx_holstein");
 }
 
 int elph_launch_force_ssh(elph_handle_s *h, double *q, const double *XS, const double *US, int nch) {
@@ -1492,7 +1483,7 @@ int elph_launch_force_ssh(elph_handle_s *h, double *q, const double *XS, const d
     DISPATCH_NPL(gen_npl(h), {
         hipLaunchKernelGGL((k_force_ssh<NPL>), dim3((unsigned)h->L, (unsigned)nch), dim3((unsigned)gen_bs(h)), shm, h->stream, q, XS, m, US, nch);
     });
-    return check_launch("k_force_ssh");
+    return elph_launch_check("k_force_ssh");
 }
 
 // pieces of elph_launch_cg_init for the step-wise API (A x0 expected in d_tmp)
@@ -1503,18 +1494,18 @@ int elph_launch_cg_init_only(elph_handle_s *h, int nrhs) {
     double *bb = h->d_part + 3 * P;
     hipLaunchKernelGGL(k_cg_init, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->d_b, h->d_tmp, bb,
                        (int)h->N, (int)h->L);
-    return check_launch("k_cg_init");
+    return elph_launch_check("k_cg_init");
 }
 
 int elph_launch_cg_init_prec_only(elph_handle_s *h, int nrhs) {
     CgBufs B = make_bufs(h, nrhs);
     hipLaunchKernelGGL(k_cg_init_prec, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, (int)h->N, (int)h->L);
-    return check_launch("k_cg_init_prec");
+    return elph_launch_check("k_cg_init_prec");
 }
 
 int elph_launch_cg_state0_only(elph_handle_s *h, int nrhs) {
     CgBufs B = make_bufs(h, nrhs);
     const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
     hipLaunchKernelGGL(k_cg_state0, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->d_part + 3 * P, (int)h->L);
-    return check_launch("k_cg_state0");
+    return elph_launch_check("k_cg_state0");
 }

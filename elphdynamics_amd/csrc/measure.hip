@@ -21,19 +21,8 @@
 
 #include <vector>
 
+#include "corr_req.h"
 #include "elph_internal.h"
-
-#define RC(call)                \
-    do {                        \
-        int _rc = (call);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
-#define CHECK_H(h)                                                    \
-    do {                                                              \
-        if (!(h)) { elph_set_error("null handle"); return ELPH_E_ARG; } \
-        HIPCHK(hipSetDevice((h)->device));                            \
-    } while (0)
 
 namespace {
 
@@ -41,15 +30,10 @@ constexpr int TPB = 256;
 constexpr int NWAVE = TPB / ELPH_WAVE;
 constexpr int NCORR = 5;
 const char *const CORR_NAMES[NCORR] = {"Greens", "DenDen", "SpinSpin", "PairGreens", "PhononGreens"};
+const CorrWords WORDS = {"measurements", "orbital", "with no orbital pair"};
 enum { GREENS = 0, DENDEN = 1, SPINSPIN = 2, PAIRGREENS = 3, PHONONGREENS = 4 };
 constexpr int NONSITE = 9;      // density, double_occ, x, x2, x4, phonon_pe, phonon_ke, elph_energy, mu
 constexpr int NXONLY = 6;       // x, x2, x4, phonon_pe, phonon_ke, mu: functions of the field alone
-
-struct FoldReq {                // by value into k_ms_fold
-    double *acc[NCORR];
-    const int *pairs[NCORR];    // [np][2] 0-based (o1, o2)
-    int np[NCORR], L0[NCORR];   // np = 0: not measured
-};
 
 struct MeasState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, ndef = 0;
@@ -58,25 +42,15 @@ struct MeasState {
     double *par = nullptr;          // [4][N] omega, omega4, lambda, mu
     int *bs = nullptr;              // [2][nbonds] 0-based sites of every bond, the reference's bond order
     double *bt = nullptr;           // [nbonds]
-    int *pairs = nullptr;           // all requests' pairs, concatenated
-    double *acc = nullptr;          // [nsc | the measured correlations]
-    size_t nacc = 0, off[NCORR] = {};
+    CorrPlan<NCORR> cr;             // the requests, pairs (o1, o2); cr.acc: [nsc | the measured correlations]
     int nsc = 0;
     double *x = nullptr;            // [ndim] the field, layout S
     double *ph = nullptr;           // [L][ns*N] the field's translation average (PhononGreens requested)
     double *xs = nullptr;           // [NXONLY][ns] the field-only on-site terms of this accumulate, normalised
     double *part = nullptr;         // [L][max(nq, NXONLY*ns)] one partial per workgroup
-    FoldReq req{};
-    size_t fold_max = 0;            // threads of the largest fold
 };
 
 MeasState *ms_of(elph_handle_s *h) { return (MeasState *)h->meas; }
-
-int ms_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
 
 // Sum over the workgroup in a fixed order; the result is valid on thread 0.  red: NWAVE doubles of LDS.
 __device__ __forceinline__ double block_sum(double v, double *red) {
@@ -214,7 +188,7 @@ __global__ void __launch_bounds__(TPB) k_ms_finish(double *__restrict__ acc, con
 
 // One thread per (tau, cell, listed pair) of correlation blockIdx.y (Measurements.jl:1469-1650).  C: the estimator's four real tables of
 // this pair; ph: the field's translation average.
-__global__ void __launch_bounds__(TPB) k_ms_fold(FoldReq rq, const double *__restrict__ C, const double *__restrict__ ph, int N, int L, int ns,
+__global__ void __launch_bounds__(TPB) k_ms_fold(CorrReq<NCORR> rq, const double *__restrict__ C, const double *__restrict__ ph, int N, int L, int ns,
                                                  int L1, int L2, int L3) {
     const int which = blockIdx.y, np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
     const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -258,32 +232,14 @@ __global__ void __launch_bounds__(TPB) k_ms_fold(FoldReq rq, const double *__res
     rq.acc[which][idx] += v;
 }
 
-template <class T>
-int ms_alloc(T **p, size_t n) {
-    HIPCHK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return ELPH_OK;
-}
-
-int need_meas(elph_handle_s *h) {
-    if (!h->meas) { elph_set_error("elph_meas_create has not been called"); return ELPH_E_STATE; }
-    return ELPH_OK;
-}
-
-int refuse_chains(elph_handle_s *h) {
-    if (h->nchains > 1) {
-        elph_set_error("measurements: %d chains are resident in this handle; one configuration per handle is measured", h->nchains);
-        return ELPH_E_UNSUPPORTED;
-    }
-    return ELPH_OK;
-}
+int need_meas(elph_handle_s *h) { return corr_need(h->meas, "elph_meas_create"); }
 
 }  // namespace
 
 void elph_meas_free(elph_handle_s *h) {
     MeasState *m = ms_of(h);
     if (!m) return;
-    void *ptrs[] = {m->par, m->bs, m->bt, m->pairs, m->acc, m->x, m->ph, m->xs, m->part};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    corr_free({m->par, m->bs, m->bt, m->cr.pairs, m->cr.acc, m->x, m->ph, m->xs, m->part});
     delete m;
     h->meas = nullptr;
 }
@@ -293,9 +249,7 @@ extern "C" int elph_meas_create(elph_handle h, const double *omega, const double
                                 const int *time_dependent, const int *npairs, const int *pairs) {
     CHECK_H(h);
     elph_meas_free(h);
-    if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("measurements: the SSH model is not supported (Holstein only)"); return ELPH_E_UNSUPPORTED; }
-    if (h->shard || h->is_slab) { elph_set_error("measurements: sharded and slab handles are not supported"); return ELPH_E_UNSUPPORTED; }
-    RC(refuse_chains(h));
+    RC(corr_refuse_handle(h, WORDS.prefix));
     ElphGreensView g;
     RC(elph_i_greens_view(h, &g));
     if (!omega || !omega4 || !lambda || !mu || !measure || !time_dependent || !npairs) { elph_set_error("measurements: a null parameter array"); return ELPH_E_ARG; }
@@ -313,106 +267,67 @@ extern "C" int elph_meas_create(elph_handle h, const double *omega, const double
             if (s < 1 || s > N) { elph_set_error("measurements: bond %lld joins site %lld, outside 1..%d", (long long)b + 1, (long long)s, N); return ELPH_E_ARG; }
             bs[(size_t)k * nbonds + b] = (int)(s - 1);
         }
-    std::vector<int> prs;
-    size_t at = 0, total = 0;
-    MeasState tmp;                                     // request bookkeeping before anything is allocated
-    tmp.nsc = 3 + NONSITE * ns + ndef;
-    total = (size_t)tmp.nsc;
-    std::vector<size_t> pair_off(NCORR, 0);
-    for (int c = 0; c < NCORR; ++c) {
-        tmp.req.np[c] = 0; tmp.req.L0[c] = 1;
-        if (!measure[c]) continue;
-        if (npairs[c] < 1 || !pairs) { elph_set_error("measurements: %s is requested with no orbital pair", CORR_NAMES[c]); return ELPH_E_ARG; }
-        for (int p = 0; p < npairs[c]; ++p)
-            for (int k = 0; k < 2; ++k) {
-                const int o = pairs[2 * (at + p) + k];
-                if (o < 1 || o > ns) {
-                    elph_set_error("measurements: %s pair %d names orbital %d, outside 1..%d", CORR_NAMES[c], p + 1, o, ns);
-                    return ELPH_E_ARG;
-                }
-                prs.push_back(o - 1);
-            }
-        pair_off[c] = 2 * at;
-        at += (size_t)npairs[c];
-        tmp.req.np[c] = npairs[c];
-        tmp.req.L0[c] = time_dependent[c] ? L + 1 : 1;
-        tmp.off[c] = total;
-        const size_t cnt = (size_t)tmp.req.L0[c] * nc * npairs[c];
-        total += cnt;
-        tmp.fold_max = std::max(tmp.fold_max, cnt);
-    }
-    MeasState *m = new MeasState(tmp);
+    const int nsc = 3 + NONSITE * ns + ndef;
+    CorrPlan<NCORR> plan;                              // request bookkeeping before anything is allocated
+    RC(corr_plan(plan, WORDS, CORR_NAMES, measure, time_dependent, npairs, pairs, ns, L, nc, (size_t)nsc));
+    MeasState *m = new MeasState;
     h->meas = m;
-    m->ns = ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = ndef; m->nbonds = nbonds; m->dtau = dtau;
-    m->nacc = total;
+    m->cr = plan;
+    m->ns = ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = ndef; m->nbonds = nbonds; m->dtau = dtau; m->nsc = nsc;
     double mus = 0.0;
     for (int i = 0; i < N; ++i) mus += mu[i];
     m->mu_mean = mus / N;                              // mean(model.mu), :858
     const int nq = std::max(3 * ns + 2 + ndef, NXONLY * ns);
-    int rc = ELPH_OK;
-    auto ok = [&](int r) { if (rc == ELPH_OK) rc = r; return rc == ELPH_OK; };
-    const bool allocated = ok(ms_alloc(&m->par, 4 * (size_t)N)) && ok(ms_alloc(&m->bs, 2 * (size_t)nbonds)) && ok(ms_alloc(&m->bt, (size_t)nbonds)) &&
-        ok(ms_alloc(&m->pairs, prs.size())) && ok(ms_alloc(&m->acc, total)) && ok(ms_alloc(&m->x, (size_t)h->ndim)) &&
-        ok(ms_alloc(&m->xs, (size_t)NXONLY * ns)) && ok(ms_alloc(&m->part, (size_t)L * nq)) &&
-        (m->req.np[PHONONGREENS] == 0 || ok(ms_alloc(&m->ph, (size_t)L * ns * N)));
-    if (!allocated || rc != ELPH_OK) { elph_meas_free(h); return rc; }
-    auto up = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-        return ELPH_OK;
-    };
+    CorrFirstError ok;
+    const bool allocated = ok(corr_alloc(&m->par, 4 * (size_t)N)) && ok(corr_alloc(&m->bs, 2 * (size_t)nbonds)) && ok(corr_alloc(&m->bt, (size_t)nbonds)) &&
+        ok(corr_alloc(m->cr)) && ok(corr_alloc(&m->x, (size_t)h->ndim)) && ok(corr_alloc(&m->xs, (size_t)NXONLY * ns)) &&
+        ok(corr_alloc(&m->part, (size_t)L * nq)) && (m->cr.req.np[PHONONGREENS] == 0 || ok(corr_alloc(&m->ph, (size_t)L * ns * N)));
+    if (!allocated) { elph_meas_free(h); return ok.rc; }
     const double *pp[4] = {omega, omega4, lambda, mu};
-    for (int k = 0; k < 4; ++k) ok(up(m->par + (size_t)k * N, pp[k], (size_t)N * sizeof(double)));
-    ok(up(m->bs, bs.data(), bs.size() * sizeof(int)));
-    ok(up(m->bt, bond_t, (size_t)nbonds * sizeof(double)));
-    ok(up(m->pairs, prs.data(), prs.size() * sizeof(int)));
-    if (rc == ELPH_OK && hipMemset(m->acc, 0, total * sizeof(double)) != hipSuccess) { elph_set_error("measurements: hipMemset failed"); rc = ELPH_E_HIP; }
-    if (rc != ELPH_OK) { elph_meas_free(h); return rc; }
-    for (int c = 0; c < NCORR; ++c) {
-        m->req.acc[c] = m->acc + m->off[c];
-        m->req.pairs[c] = m->pairs + pair_off[c];
-    }
-    return ELPH_OK;
+    for (int k = 0; k < 4; ++k) ok(corr_up(m->par + (size_t)k * N, pp[k], (size_t)N * sizeof(double)));
+    ok(corr_up(m->bs, bs.data(), bs.size() * sizeof(int)));
+    ok(corr_up(m->bt, bond_t, (size_t)nbonds * sizeof(double)));
+    if (ok.rc == ELPH_OK) ok(corr_upload(m->cr, WORDS.prefix));
+    if (ok.rc != ELPH_OK) elph_meas_free(h);
+    return ok.rc;
 }
 
 extern "C" int elph_meas_accumulate(elph_handle h, const double *x) {
     CHECK_H(h);
     RC(need_meas(h));
-    RC(refuse_chains(h));
+    RC(corr_refuse_chains(h, WORDS.prefix));
     if (!x) { elph_set_error("x is null"); return ELPH_E_ARG; }
     MeasState *m = ms_of(h);
     ElphGreensView g;
     RC(elph_i_greens_view(h, &g));
     if (!g.have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
     const int N = (int)h->N, L = (int)h->L, ns = m->ns, nc = m->nc, nv = g.nv;
-    const size_t nd = (size_t)h->ndim;
     RC(elph_i_ensure_capacity(h, 1));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, x, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_stage_in, x, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
     RC(elph_launch_r2s(h, m->x, h->d_stage_in, 1));
     // what depends on the field alone: once per call, added once per pair below (the reference's loop recomputes it per pair)
     hipLaunchKernelGGL(k_ms_x, dim3((unsigned)L), dim3(TPB), 0, h->stream, m->part, m->x, m->par, N, L, ns, nc, m->dtau);
-    RC(ms_check("k_ms_x"));
+    RC(elph_launch_check("k_ms_x"));
     hipLaunchKernelGGL(k_ms_x_finish, dim3(1), dim3(TPB), 0, h->stream, m->xs, m->part, L, ns, (double)nc * (double)L);
-    RC(ms_check("k_ms_x_finish"));
-    if (m->req.np[PHONONGREENS]) RC(elph_i_greens_autocorr_dev(h, m->ph, m->x));
+    RC(elph_launch_check("k_ms_x_finish"));
+    if (m->cr.req.np[PHONONGREENS]) RC(elph_i_greens_autocorr_dev(h, m->ph, m->x));
     const int nq = 3 * ns + 2 + m->ndef;
     const size_t shm = ((size_t)nq + NWAVE) * sizeof(double);
     const size_t tab = (size_t)L * ns * N;
     for (int i = 1; i < nv; ++i)
         for (int j = i + 1; j <= nv; ++j) {
-            // the doubled complex copies of the tables are refreshed for the last pair only (elph_greens_dev_arrays)
-            RC(elph_i_greens_setup_dev(h, i, j, i == nv - 1));
-            const double *X1 = g.X + (size_t)(i - 1) * nd, *X2 = g.X + (size_t)(j - 1) * nd;
-            const double *R1 = g.R + (size_t)(i - 1) * nd, *R2 = g.R + (size_t)(j - 1) * nd;
-            hipLaunchKernelGGL(k_ms_pair, dim3((unsigned)L), dim3(TPB), 0, h->stream, m->part, X1, X2, R1, R2, m->x, m->par + 2 * (size_t)N, m->bs,
+            ElphGreensPair v;
+            RC(elph_i_greens_pair_dev(h, i, j, &v));
+            hipLaunchKernelGGL(k_ms_pair, dim3((unsigned)L), dim3(TPB), 0, h->stream, m->part, v.X1, v.X2, v.R1, v.R2, m->x, m->par + 2 * (size_t)N, m->bs,
                                m->bt, N, ns, nc, m->ndef, (long long)m->nbonds);
-            RC(ms_check("k_ms_pair"));
-            hipLaunchKernelGGL(k_ms_finish, dim3(1), dim3(TPB), shm, h->stream, m->acc, m->part, m->xs, g.C + 3 * tab, N, L, ns, nc, m->ndef,
+            RC(elph_launch_check("k_ms_pair"));
+            hipLaunchKernelGGL(k_ms_finish, dim3(1), dim3(TPB), shm, h->stream, m->cr.acc, m->part, m->xs, g.C + 3 * tab, N, L, ns, nc, m->ndef,
                                m->mu_mean);
-            RC(ms_check("k_ms_finish"));
-            if (m->fold_max) {
-                hipLaunchKernelGGL(k_ms_fold, dim3((unsigned)((m->fold_max + TPB - 1) / TPB), NCORR), dim3(TPB), 0, h->stream, m->req, g.C, m->ph, N,
+            RC(elph_launch_check("k_ms_finish"));
+            if (m->cr.fold_max) {
+                hipLaunchKernelGGL(k_ms_fold, dim3((unsigned)((m->cr.fold_max + TPB - 1) / TPB), NCORR), dim3(TPB), 0, h->stream, m->cr.req, g.C, m->ph, N,
                                    L, ns, m->L1, m->L2, m->L3);
-                RC(ms_check("k_ms_fold"));
+                RC(elph_launch_check("k_ms_fold"));
             }
         }
     HIPCHK(hipStreamSynchronize(h->stream));           // x (a host pointer) is not retained after return
@@ -424,25 +339,16 @@ extern "C" int elph_meas_fetch(elph_handle h, double *scalars, double *Greens, d
     CHECK_H(h);
     RC(need_meas(h));
     MeasState *m = ms_of(h);
-    std::vector<double> host(m->nacc);
-    HIPCHK(hipMemcpyAsync(host.data(), m->acc, m->nacc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<double> host;
+    double *outs[NCORR] = {Greens, DenDen, SpinSpin, PairGreens, PhononGreens};
+    RC(corr_fetch(h, m->cr, host, outs));
     if (scalars)
         for (int i = 0; i < m->nsc; ++i) scalars[i] = host[(size_t)i];
-    double *outs[NCORR] = {Greens, DenDen, SpinSpin, PairGreens, PhononGreens};
-    for (int c = 0; c < NCORR; ++c) {
-        if (!outs[c] || !m->req.np[c]) continue;
-        const size_t cnt = (size_t)m->req.L0[c] * m->nc * m->req.np[c];
-        const double *src = host.data() + m->off[c];
-        for (size_t i = 0; i < cnt; ++i) { outs[c][2 * i] = src[i]; outs[c][2 * i + 1] = 0.0; }
-    }
     return ELPH_OK;
 }
 
 extern "C" int elph_meas_reset(elph_handle h) {
     CHECK_H(h);
     RC(need_meas(h));
-    MeasState *m = ms_of(h);
-    HIPCHK(hipMemsetAsync(m->acc, 0, m->nacc * sizeof(double), h->stream));
-    return ELPH_OK;
+    return corr_reset(h, ms_of(h)->cr);
 }

@@ -477,12 +477,6 @@ __global__ void __launch_bounds__(LAT::NW * WAVE) k_mul_pg(double *__restrict__ 
     }
 }
 
-int pg_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
-
 }   // namespace
 
 // The patch-kernel instantiation of (kind, px, py, nw): calls launch(Tag<LAT>{}) for the matching alias.  tables: hopping disorder — the table
@@ -599,7 +593,7 @@ int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_p
                            (int)h->L, rr_part, h->d_pg_bond);
     });
     if (rc) return rc;
-    return pg_check("k_kpm_cheb_pg");
+    return elph_launch_check("k_kpm_cheb_pg");
 }
 
 // the mat-vec kernel of the CG iteration in the patch layout (generic family only: the lane-program family has its own chunked kernel)
@@ -630,7 +624,7 @@ int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs
         else hipLaunchKernelGGL((k_cg_ap_pg<LAT, false>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, B, m, parity, Ls, T, h->d_pg_bond);
     });
     if (rc) return rc;
-    return pg_check("k_cg_ap_pg");
+    return elph_launch_check("k_cg_ap_pg");
 }
 
 // mulM!, mulMT!, mulMTM! in the patch layout (generic family only)
@@ -652,5 +646,5 @@ int elph_pg_mul(elph_handle_s *h, const ModelDev &m, int which, double *yS, cons
         else hipLaunchKernelGGL((k_mul_pg<LAT, 2>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);
     });
     if (rc) return rc;
-    return pg_check("k_mul_pg");
+    return elph_launch_check("k_mul_pg");
 }

@@ -535,12 +535,6 @@ __global__ void __launch_bounds__(64) k_shard_rz_own(const double *__restrict__ 
     }
 }
 
-static int launch_ok(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("launch %s failed: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
-
 // Wait bound of the sharded solves (ms): ELPH_SHARD_TIMEOUT_MS, else ELPH_WG_TIMEOUT_MS, else 20 s.  A sharded solve has no fallback
 // behind it (a time-out is ELPH_E_HIP), so it keeps the long bound; the 2 s default of ELPH_WG_TIMEOUT_MS belongs to the un-sharded
 // resident kernels, which fall back to the streaming iteration.
@@ -609,7 +603,7 @@ extern "C" int elph_shard_selftest(elph_handle h, int rounds, double *us_per_rou
     const long long bound_ms = (eb && atoll(eb) > 0) ? atoll(eb) : 10000;
     const unsigned seq = 0x5E1F0000u + (++S->selftest_calls & 0xFFFFu);       // (a collective: every rank's n-th call carries the same number)
     hipLaunchKernelGGL(k_shard_selftest, dim3(1), dim3(64), 0, h->stream, S->ctl, S->ext_off, seq, rounds, bound_ms * 100000LL, d_lat, d_status);
-    int rc = launch_ok("k_shard_selftest");
+    int rc = elph_launch_check("k_shard_selftest");
     long long lat[ELPH_SHARD_MAXRANKS];
     int status[ELPH_SHARD_MAXRANKS];
     if (rc == ELPH_OK) {
@@ -654,7 +648,7 @@ extern "C" int elph_peer_access(int dev_a, int dev_b, int *can) {
 static int allsum(elph_handle_s *h, ShardState *S, double *part, int n, int slot) {
     hipLaunchKernelGGL(k_shard_allsum, dim3(1), dim3(64), 0, h->stream, part, n, S->ctl, S->ext_off, slot, ++S->epoch, S->d_abort,
                        shard_timeout_ticks());
-    return launch_ok("k_shard_allsum");
+    return elph_launch_check("k_shard_allsum");
 }
 
 // z = P^-1 r on the slab (own + ghost sites) through the full-lattice handle hf; r.z partials (own sites) -> B.rz, combined over ranks
@@ -666,20 +660,20 @@ static int shard_kpm_apply(elph_handle_s *h, elph_handle_s *hf, ShardState *S) {
     const unsigned ep = ++S->epoch;
     hipLaunchKernelGGL(k_shard_push_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->d_nu, S->ctl, Lo2, N, S->ctl.own_lo,
                        S->ctl.own_hi - S->ctl.own_lo, (int)S->own_gstart, (int)S->n_global, S->nu_off, S->ext_off, ep, S->d_counter);
-    if ((rc = launch_ok("k_shard_push_nu"))) return rc;
+    if ((rc = elph_launch_check("k_shard_push_nu"))) return rc;
     hipLaunchKernelGGL(k_shard_wait_nu, dim3(1), dim3(64), 0, h->stream, S->ctl, S->ext_off, ep, S->d_abort, shard_timeout_ticks());
-    if ((rc = launch_ok("k_shard_wait_nu"))) return rc;
+    if ((rc = elph_launch_check("k_shard_wait_nu"))) return rc;
     const long long nfull = (long long)Lo2 * S->n_global;
     hipLaunchKernelGGL(k_shard_copy_nu, dim3((unsigned)((nfull + 255) / 256)), dim3(256), 0, h->stream, hf->d_nu, S->mail + S->nu_off, nfull);
-    if ((rc = launch_ok("k_shard_copy_nu"))) return rc;
+    if ((rc = elph_launch_check("k_shard_copy_nu"))) return rc;
     // Chebyshev recursion alone (parts = 2) on the full lattice, in place on hf->d_nu; hf shares this stream.  An inactive expansion
     // (KPMPreconditioners.jl:475-478) is the identity: the spectrum goes back as it came.
     if (hf->kpm.any_active() && (rc = elph_launch_kpm_apply(hf, hf->d_zp, hf->d_r, 1, 0, 2))) return rc;
     hipLaunchKernelGGL(k_shard_gather_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->d_nu, hf->d_nu, S->d_gsites, Lo2, N, (int)S->n_global);
-    if ((rc = launch_ok("k_shard_gather_nu"))) return rc;
+    if ((rc = elph_launch_check("k_shard_gather_nu"))) return rc;
     if ((rc = elph_dft_inv_twisted(h, h->d_zp, h->d_nu, N, 1, nullptr, nullptr, nullptr, 0))) return rc;
     hipLaunchKernelGGL(k_shard_rz_own, dim3((unsigned)L), dim3(64), 0, h->stream, h->d_r, h->d_zp, B.rz, B.nrz, N, L, S->ctl.own_lo, S->ctl.own_hi);
-    if ((rc = launch_ok("k_shard_rz_own"))) return rc;
+    if ((rc = elph_launch_check("k_shard_rz_own"))) return rc;
     return allsum(h, S, B.rz, B.nrz, 2);
 }
 
@@ -880,13 +874,13 @@ static int ghost_sync_dev(elph_handle_s *h, ShardState *S, double *vec, int nvec
     if (S->barrier(S->coll_ctx) != 0) { elph_set_error("the caller's barrier failed"); return ELPH_E_HIP; }
     hipLaunchKernelGGL(k_shard_push_cols, dim3((unsigned)rows), dim3(256), 0, h->stream, (const double *)vec, S->ctl, S->nu_off, ncols, ngcol, d_gcol,
                        d_own, S->ctl.own_lo, S->ctl.own_hi);
-    { const int rcl = launch_ok("k_shard_push_cols"); if (rcl) return rcl; }
+    { const int rcl = elph_launch_check("k_shard_push_cols"); if (rcl) return rcl; }
     // (2) every rank's stores have landed (a kernel's system-scope stores are visible once its stream has drained)
     HIPCHK(hipStreamSynchronize(h->stream));
     if (S->barrier(S->coll_ctx) != 0) { elph_set_error("the caller's barrier failed"); return ELPH_E_HIP; }
     hipLaunchKernelGGL(k_shard_pull_cols, dim3((unsigned)rows), dim3(256), 0, h->stream, vec, (const u64s *)(S->mail + S->nu_off), ncols, ngcol, d_gcol,
                        d_own, S->ctl.own_lo, S->ctl.own_hi);
-    { const int rcl = launch_ok("k_shard_pull_cols"); if (rcl) return rcl; }
+    { const int rcl = elph_launch_check("k_shard_pull_cols"); if (rcl) return rcl; }
     ++S->ghost_dev;
     *done = true;
     return ELPH_OK;
@@ -951,7 +945,7 @@ int elph_i_shard_global_ebar(elph_handle_s *h, std::vector<double> &Eg) {
     if (S->n_global <= 0) { elph_set_error("the shard was created without its global geometry"); return ELPH_E_STATE; }
     const int lo = S->ctl.own_lo, hi = S->ctl.own_hi, n = hi - lo;
     hipLaunchKernelGGL(k_shard_ebar_own, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_tmp, h->d_E, (int)h->N, (int)h->L, lo, hi);
-    int rc = launch_ok("k_shard_ebar_own");
+    int rc = elph_launch_check("k_shard_ebar_own");
     if (rc) return rc;
     std::vector<double> own((size_t)n);
     HIPCHK(hipMemcpyAsync(own.data(), h->d_tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
@@ -1098,7 +1092,7 @@ int elph_i_shard_ldiv_dev(elph_handle_s *h, elph_handle_s *hfull, int use_prec, 
         if (rc) return rc;
         hipLaunchKernelGGL(k_shard_resid_own, dim3((unsigned)h->L), dim3(64), 0, h->stream, h->d_tmp, h->d_b, h->d_part, (int)h->N, (int)h->L,
                            S->ctl.own_lo, S->ctl.own_hi);
-        if ((rc = launch_ok("k_shard_resid_own"))) return rc;
+        if ((rc = elph_launch_check("k_shard_resid_own"))) return rc;
         std::vector<double> p(2 * (size_t)h->L);
         HIPCHK(hipMemcpyAsync(p.data(), h->d_part, p.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));

@@ -74,12 +74,45 @@ def _pairs(entry, n):
     return np.array(pairs, dtype=np.int64).reshape(-1, 2).T.copy()
 
 
+def _refuse_ssh(model, subject):
+    if getattr(model, "kind", None) != 0:
+        raise UnsupportedMeasurement("%s of the SSH model are not supported (Holstein only)" % subject)
+
+
+def _refuse_chains(model, subject):
+    if getattr(model, "_nchains", 1) > 1:
+        raise UnsupportedMeasurement("%s with several chains resident (model._nchains = %d) are not supported" % (subject, model._nchains))
+
+
+def _refuse_model(model, subject):
+    """The models neither container measures; subject: "measurements" / "bond correlations"."""
+    _refuse_ssh(model, subject)
+    _refuse_chains(model, subject)
+
+
+def _requested(info, names):
+    return [name for name in names if (info.get(name) or {}).get("measure", False) is True]
+
+
+def _corr_group(info, names, n, L, dims):
+    """init_corr_container! (:767-796) for every requested name; n: what a pair's indices count (orbitals, bond definitions)."""
+    group = {}
+    for name in _requested(info, names):
+        pairs = _pairs(info[name], n)
+        L0 = L + 1 if info[name].get("time_dependent", False) is True else 1
+        group[name] = Correlation((L0,) + dims + (pairs.shape[1],), pairs)
+    return group
+
+
+def _susc_group(corr_group, table, dims):
+    """init_susc_container! (:801-819): one susceptibility per time-dependent correlation of `table`, on the same pairs."""
+    return {susc: Correlation(dims + (corr_group[corr].pairs.shape[1],), corr_group[corr].pairs)
+            for susc, corr in table if corr in corr_group and corr_group[corr].position.shape[0] > 1}
+
+
 def initialize_measurements_container(model, info, datafolder):
     """initialize_measurements_container(holstein, info, datafolder) (:27-178)."""
-    if getattr(model, "kind", None) != 0:
-        raise UnsupportedMeasurement("measurements of the SSH model are not supported (Holstein only)")
-    if getattr(model, "_nchains", 1) > 1:
-        raise UnsupportedMeasurement("measurements with several chains resident (model._nchains = %d) are not supported" % model._nchains)
+    _refuse_model(model, "measurements")
     info = info or {}
     for name in INTERSITE_CORR:
         if info.get(name, {}).get("measure", False) is True:
@@ -89,24 +122,15 @@ def initialize_measurements_container(model, info, datafolder):
         if val is True:
             raise UnsupportedMeasurement("[measurements.Snapshots] %s = true: snapshots are not supported" % key)
     lat = model.lattice
-    L, L1, L2, L3, no = model.Ltau, lat.L1, lat.L2, lat.L3, lat.norbits
+    dims, no = (lat.L1, lat.L2, lat.L3), lat.norbits
     c = MeasurementsContainer()
     c.n_rand_vecs = int(info.get("num_random_vectors", 1))                  # :36-40
     c.datafolder = datafolder
     c.global_meas = {k: 0j for k in GLOBAL_KEYS}
     c.onsite_meas = {k: np.zeros(no, dtype=np.complex128) for k in ONSITE_KEYS}
     c.intersite_meas = {k: np.zeros(int(model.nbonds), dtype=np.complex128) for k in INTERSITE_KEYS}
-    for name in ONSITE_CORR:                                                # init_corr_container!, :767-796
-        entry = info.get(name)
-        if entry is None or entry.get("measure", False) is not True:
-            continue
-        pairs = _pairs(entry, no)
-        L0 = L + 1 if entry.get("time_dependent", False) is True else 1
-        c.onsite_corr[name] = Correlation((L0, L1, L2, L3, pairs.shape[1]), pairs)
-    for susc, corr in SUSC_OF:                                              # init_susc_container!, :801-819
-        if corr in c.onsite_corr and c.onsite_corr[corr].position.shape[0] > 1:
-            pairs = c.onsite_corr[corr].pairs
-            c.onsite_susc[susc] = Correlation((L1, L2, L3, pairs.shape[1]), pairs)
+    c.onsite_corr = _corr_group(info, ONSITE_CORR, no, model.Ltau, dims)
+    c.onsite_susc = _susc_group(c.onsite_corr, SUSC_OF, dims)
     return c
 
 
@@ -122,18 +146,23 @@ def _key_file(path, header, arr, pairs):
             f.write(" ".join(["%d" % (i + 1), "%d" % pairs[0, p], "%d" % pairs[1, p]] + ["%d" % cidx[k] for k in range(nd - 2, -1, -1)]) + "\n")
 
 
+def _group_folders(datafolder, corr_group, susc_group, col1, col2):
+    """The folders and key files of a group's correlations and susceptibilities (:420-540); col1, col2: what a pair's columns are called."""
+    for group, cols in ((corr_group, " tau"), (susc_group, "")):
+        for k, corr in group.items():
+            for space, letter in (("position", "r"), ("momentum", "k")):
+                folder = os.path.join(datafolder, "%s_%s_f" % (k, space))
+                os.mkdir(folder)
+                header = "index %s %s %s3 %s2 %s1%s" % (col1, col2, letter, letter, letter, cols)
+                _key_file(os.path.join(folder, "%s_%s_key.out" % (k, space)), header, getattr(corr, space), corr.pairs)
+
+
 def initialize_measurement_folders_(container):
     """initialize_measurement_folders!(container) (:343-540)."""
     d = container.datafolder
     for name in ("global_measurements_f", "onsite_measurements_f", "intersite_measurements_f"):
         os.mkdir(os.path.join(d, name))
-    for group, cols in ((container.onsite_corr, " tau"), (container.onsite_susc, "")):
-        for k, corr in group.items():
-            for space, letter in (("position", "r"), ("momentum", "k")):
-                folder = os.path.join(d, "%s_%s_f" % (k, space))
-                os.mkdir(folder)
-                header = "index orbit1 orbit2 %s3 %s2 %s1%s" % (letter, letter, letter, cols)
-                _key_file(os.path.join(folder, "%s_%s_key.out" % (k, space)), header, getattr(corr, space), corr.pairs)
+    _group_folders(d, container.onsite_corr, container.onsite_susc, "orbit1", "orbit2")
 
 
 def bond_arrays(model):
@@ -150,34 +179,45 @@ def bond_arrays(model):
     return np.ascontiguousarray(model.neighbor_table[rows], dtype=np.int64), np.ascontiguousarray(model.t, dtype=np.float64)
 
 
-def _ensure_device(container, model, Gr):
-    if container._device_of is model:
-        return
-    if getattr(model, "kind", None) != 0:
-        raise UnsupportedMeasurement("measurements of the SSH model are not supported (Holstein only)")
+def _i32(v):
+    return np.ascontiguousarray(v, dtype=np.int32)
+
+
+def _ip(a):
+    return a.ctypes.data_as(P_int)
+
+
+def _request_arrays(group, names):
+    """measure / time_dependent / npairs / pairs of a *_create call (int32; the requests' pair lists one after another)."""
+    plist = [group[name].pairs.T.reshape(-1) for name in names if name in group]
+    return (_i32([name in group for name in names]), _i32([name in group and group[name].position.shape[0] > 1 for name in names]),
+            _i32([group[name].pairs.shape[1] if name in group else 0 for name in names]), _i32(np.concatenate(plist)) if plist else _i32([0, 0]))
+
+
+def _check_estimator(container, model, Gr):
     assert Gr.model is model
     if Gr.nv != container.n_rand_vecs:
         raise ValueError("the estimator holds %d vectors, the container normalises for num_random_vectors = %d" % (Gr.nv, container.n_rand_vecs))
+
+
+def _ensure_device(container, model, Gr):
+    if container._device_of is model:
+        return
+    _refuse_ssh(model, "measurements")
+    _check_estimator(container, model, Gr)
     sites, t = bond_arrays(model)
-    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)  # noqa: E731
-    measure = i32([name in container.onsite_corr for name in ONSITE_CORR])
-    timedep = i32([name in container.onsite_corr and container.onsite_corr[name].position.shape[0] > 1 for name in ONSITE_CORR])
-    npairs = i32([container.onsite_corr[name].pairs.shape[1] if name in container.onsite_corr else 0 for name in ONSITE_CORR])
-    plist = [container.onsite_corr[name].pairs.T.reshape(-1) for name in ONSITE_CORR if name in container.onsite_corr]
-    pairs = i32(np.concatenate(plist)) if plist else i32([0, 0])
-    ip = lambda a: a.ctypes.data_as(P_int)  # noqa: E731
+    request = _request_arrays(container.onsite_corr, ONSITE_CORR)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     check(model._lib.elph_meas_create(model._h, dptr(f64(model.omega)), dptr(f64(model.omega4)), dptr(f64(model.lam)), dptr(f64(model.mu)),
                                       float(model.dtau), sites.shape[0], int(model.nbonds), iptr(sites) if sites.size else None,
-                                      dptr(t) if t.size else None, ip(measure), ip(timedep), ip(npairs), ip(pairs)))
+                                      dptr(t) if t.size else None, *map(_ip, request)))
     container._device_of = model
 
 
 def accumulate_(container, model, Gr):
     """make_measurements! without its update! (:550-560): every pair i < j of the estimator's vectors is set up and folded into the device's
     accumulators; nothing comes back to the host."""
-    if getattr(model, "_nchains", 1) > 1:
-        raise UnsupportedMeasurement("measurements with several chains resident (model._nchains = %d) are not supported" % model._nchains)
+    _refuse_chains(model, "measurements")
     _ensure_device(container, model, Gr)
     check(model._lib.elph_meas_accumulate(model._h, dptr(np.ascontiguousarray(model.x, dtype=np.float64))))
     Gr.n1, Gr.n2 = Gr.nv - 1, Gr.nv                                         # the estimator's device tables are the last pair's now
@@ -227,27 +267,49 @@ def fourier_transform_correlations_(group):
         corr.momentum[...] = np.fft.fftn(corr.position, axes=(1, 2, 3))
 
 
-def normalize_(container, bin_size):
-    """:590-629: everything divided by bin_size * binomial(n_rand_vecs, 2)."""
+def _bin_volume(container, bin_size):
+    """bin_size * binomial(n_rand_vecs, 2): the pairs of vectors a bin's sums run over (:590-592)."""
     V = int(bin_size) * comb(container.n_rand_vecs, 2)
     if V == 0:
         raise ValueError("bin_size * binomial(num_random_vectors = %d, 2) is zero" % container.n_rand_vecs)
+    return V
+
+
+def _divide_group(group, V):
+    for corr in group.values():
+        corr.position /= V
+        corr.momentum /= V
+
+
+def _simpson_group(susc_group, corr_group, table, dtau):
+    """measure_susceptibility! (:2550-2572) for the susceptibilities of `table` that are measured."""
+    for susc, corr in table:
+        if susc in susc_group:
+            susc_group[susc].position[...] = simpson(corr_group[corr].position, dtau)
+            susc_group[susc].momentum[...] = simpson(corr_group[corr].momentum, dtau)
+
+
+def _process_group(corr_group, susc_group, table, V, dtau):
+    """A group's part of process_measurements! (:574-676): momentum = fft over the cell axes, both divided by V, Simpson's rule over tau."""
+    fourier_transform_correlations_(corr_group)
+    _divide_group(corr_group, V)
+    _simpson_group(susc_group, corr_group, table, dtau)
+
+
+def normalize_(container, bin_size):
+    """:590-629: everything divided by bin_size * binomial(n_rand_vecs, 2)."""
+    V = _bin_volume(container, bin_size)
     for k in container.global_meas:
         container.global_meas[k] /= V
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k] /= V
-    for corr in container.onsite_corr.values():
-        corr.position /= V
-        corr.momentum /= V
+    _divide_group(container.onsite_corr, V)
 
 
 def measure_susceptibilities_(container, dtau):
     """:636-663 with measure_susceptibility! (:2550-2572): Simpson's rule over tau of the normalised correlations."""
-    for susc, corr in SUSC_OF:
-        if susc in container.onsite_susc:
-            container.onsite_susc[susc].position[...] = simpson(container.onsite_corr[corr].position, dtau)
-            container.onsite_susc[susc].momentum[...] = simpson(container.onsite_corr[corr].momentum, dtau)
+    _simpson_group(container.onsite_susc, container.onsite_corr, SUSC_OF, dtau)
 
 
 def process_measurements_(container, bin_size, model):
@@ -267,6 +329,20 @@ def _write_correlation(arr, name, space, datafolder, bin):
         f.writelines("%d %.8f %.8f\n" % (i + 1, v.real, v.imag) for i, v in enumerate(flat))
 
 
+def _write_groups(datafolder, bin, *groups):
+    for group in groups:
+        for name, corr in group.items():
+            _write_correlation(corr.position, name, "position", datafolder, bin)
+            _write_correlation(corr.momentum, name, "momentum", datafolder, bin)
+
+
+def _zero_groups(*groups):
+    for group in groups:
+        for corr in group.values():
+            corr.position[...] = 0
+            corr.momentum[...] = 0
+
+
 def write_measurements_(container, model, bin):
     """write_measurements!(container, model, bin) (:681-693, :1175-1274)."""
     d = container.datafolder
@@ -283,10 +359,7 @@ def write_measurements_(container, model, bin):
         for k in INTERSITE_KEYS:
             for b, v in enumerate(container.intersite_meas[k]):
                 f.write("%s %d %.8f\n" % (k, b + 1, v.real))
-    for group in (container.onsite_corr, container.onsite_susc):
-        for name, corr in group.items():
-            _write_correlation(corr.position, name, "position", d, bin)
-            _write_correlation(corr.momentum, name, "momentum", d, bin)
+    _write_groups(d, bin, container.onsite_corr, container.onsite_susc)
 
 
 def reset_measurements_(container, model):
@@ -296,9 +369,6 @@ def reset_measurements_(container, model):
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k][:] = 0
-    for group in (container.onsite_corr, container.onsite_susc):
-        for corr in group.values():
-            corr.position[...] = 0
-            corr.momentum[...] = 0
+    _zero_groups(container.onsite_corr, container.onsite_susc)
     if container._device_of is model and model is not None and getattr(model, "_h", None):
         check(model._lib.elph_meas_reset(model._h))
