@@ -1091,6 +1091,14 @@ int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, 
     return ldiv_core(h, nrhs, use_prec, maxiter, iters, resid, flag);
 }
 int elph_i_ensure_capacity(elph_handle_s *h, int nrhs) { return ensure_capacity(h, nrhs); }
+
+// Room for nrhs vectors and for the bond brackets q[chain][tau][bond] of nch chains (SSH force).  The brackets go to d_p (2*cap_rhs*ndim
+// doubles) and their scatter onto the phonon fields to d_tmp (cap_rhs*ndim), so a lattice with more than two bonds per site (triangular,
+// cubic) needs more than the two right-hand sides of the solves: ceil(nb/N) vectors per chain hold both.
+int elph_i_ssh_bracket_capacity(elph_handle_s *h, int nrhs, int nch) {
+    const int per_site = (int)((h->nb + h->N - 1) / h->N);
+    return ensure_capacity(h, std::max(nrhs, nch * per_site));
+}
 // SSH: one set of hopping tables (tau-major cosh/sinh + their lane-program copies) and one field buffer per chain
 static int ssh_reserve_chains(elph_handle_s *h, int nchains) {
     if (nchains <= h->ssh_chain_cap) return ELPH_OK;
@@ -1298,8 +1306,8 @@ extern "C" int elph_fermion_force_holstein(elph_handle h, const double *x, const
 // the two solves of calc_O⁻¹Λϕ! for an SSH handle (Λ = identity) + the bond brackets q[tau][n] left in h->d_p
 static int ssh_force_core(elph_handle_s *h, const double *rhs_plus, const double *rhs_minus, int use_precond, double tol_power,
                           int64_t *iters, int *flag) {
-    RC(ensure_capacity(h, 2));
-    const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double), nq = (size_t)h->L * (size_t)h->nb;
+    RC(elph_i_ssh_bracket_capacity(h, 2, 1));
+    const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
     HIPCHK(hipMemcpyAsync(h->d_stage_in, rhs_plus, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, rhs_minus, bytes, hipMemcpyHostToDevice, h->stream));
     RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, 2));
@@ -1320,7 +1328,6 @@ static int ssh_force_core(elph_handle_s *h, const double *rhs_plus, const double
     if (fl == 0) tot = (tot + 1) / 2;
     *iters = tot;
     *flag = fl;
-    if (nq > 2 * nd) { elph_set_error("more bonds than 2*nsites: scratch too small"); return ELPH_E_UNSUPPORTED; }
     return elph_launch_force_ssh(h, h->d_p, h->d_x);     // d_p: 2*cap*ndim doubles of scratch, free once the solves are done
 }
 
@@ -1424,9 +1431,8 @@ static int ssh_dmdx_core(elph_handle_s *h, const double *u_dev, const double *v_
     RC(need_model(h));
     if (!u_dev || !v_dev) { elph_set_error("null argument"); return ELPH_E_ARG; }
     if (h->nchains != 1) { elph_set_error("muldMdx! acts on one phonon configuration; the handle holds %d chains", h->nchains); return ELPH_E_STATE; }
-    RC(ensure_capacity(h, 2));
-    const size_t nd = (size_t)h->ndim, nq = (size_t)h->L * (size_t)h->nb;
-    if (nq > 2 * nd) { elph_set_error("more bonds than 2*nsites: scratch too small"); return ELPH_E_UNSUPPORTED; }
+    RC(elph_i_ssh_bracket_capacity(h, 2, 1));          // no-op when u_dev, v_dev are the handle's own staging (ssh_dmdx_stage)
+    const size_t nd = (size_t)h->ndim;
     RC(elph_launch_r2s(h, h->d_b, u_dev, 1));
     RC(elph_launch_r2s(h, h->d_b + nd, v_dev, 1));
     return elph_launch_force_ssh(h, h->d_p, h->d_b + nd, h->d_b, 1);      // b0 = e^{Δτμ} v(τ−1), c0 = CBᵀ u
@@ -1434,7 +1440,7 @@ static int ssh_dmdx_core(elph_handle_s *h, const double *u_dev, const double *v_
 
 static int ssh_dmdx_stage(elph_handle_s *h, const double *u, const double *v) {
     if (!u || !v) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    RC(ensure_capacity(h, 2));
+    RC(elph_i_ssh_bracket_capacity(h, 2, 1));
     const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
     HIPCHK(hipMemcpyAsync(h->d_stage_in, u, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, v, bytes, hipMemcpyHostToDevice, h->stream));

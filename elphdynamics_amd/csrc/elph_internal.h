@@ -420,6 +420,7 @@ KpmDev elph_kpm_dev(const elph_handle_s *h);
 // elph_api.hip internals used by hmc.hip
 int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag);
 int elph_i_ensure_capacity(elph_handle_s *h, int nrhs);
+int elph_i_ssh_bracket_capacity(elph_handle_s *h, int nrhs, int nch);     // nrhs vectors + the SSH bond brackets of nch chains
 int elph_i_set_dot_range(elph_handle_s *h, int64_t site_lo, int64_t site_hi);   // inner products over [lo, hi) only (a shard's own sites)
 int elph_i_reserve_chains(elph_handle_s *h, int nchains);   // d_E for nchains configurations, h->nchains = nchains
 void elph_hmc_free(elph_handle_s *h);

@@ -558,7 +558,7 @@ extern "C" int elph_hmc_create_ssh_chains(elph_handle h, int nchains, int64_t np
     CHECK_H(h);
     if (h->kind != ELPH_MODEL_SSH) { elph_set_error("elph_hmc_create_ssh: SSH handles only"); return ELPH_E_UNSUPPORTED; }
     if (nchains < 1 || nph < 1 || !omega || !omega4 || !fa_mass || !(dtau > 0.0)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    if ((size_t)h->L * (size_t)h->nb > 2 * (size_t)h->ndim) { elph_set_error("more bonds than 2*nsites: scratch too small"); return ELPH_E_UNSUPPORTED; }
+    RC(elph_i_ssh_bracket_capacity(h, 2 * nchains, nchains));
     RC(elph_i_reserve_chains(h, nchains));
     RC(elph_i_ssh_upload_params(h, nph, cb_index, t_ph, alpha, alpha2, t_bare_cb, mu));
     return hmc_create_core(h, nchains, (int)nph, true, omega, omega4, dtau, fa_mass);

@@ -1236,9 +1236,8 @@ extern "C" int elph_shard_fermion_force_ssh(elph_handle h, elph_handle hfull, co
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
     if (!rhs_plus || !rhs_minus || !q_out || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
     int rc;
-    if ((rc = elph_i_ensure_capacity(h, 2))) return rc;
+    if ((rc = elph_i_ssh_bracket_capacity(h, 2, 1))) return rc;
     const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double), L = (size_t)h->L, nb = (size_t)h->nb, nq = L * nb;
-    if (nq > 2 * nd) { elph_set_error("more bonds than 2*nsites: scratch too small"); return ELPH_E_UNSUPPORTED; }
     HIPCHK(hipMemcpyAsync(h->d_stage_in, rhs_plus, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, rhs_minus, bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = elph_launch_r2s(h, h->d_b, h->d_stage_in, 2))) return rc;

@@ -1783,17 +1783,10 @@ def _wg_info(m, nrhs=1):
     return us.value, T.value, W.value, G.value
 
 
-@pytest.mark.parametrize("tag", ["b", "d", "e", "B", "C", "D", "E", "s", "q", "Q", "S", "y", "z", "Y", "r", "R", "w", "W", "u", "T", "t6", "t12"])
-def test_wg_resident_cg_equals_the_two_kernel_iteration(tag, monkeypatch):
-    """The whole solve in one launch (Krylov vectors in registers / LDS, teams of workgroups meeting through L2) against the
-    streaming two-kernel iteration: same algorithm, different summation trees for p.z and r.r — same iteration count up to
-    the knife edge, solutions equal to the solver tolerance at 1e-5 and to 1e-11 when both solve to 1e-13; both slices-per-wave
-    shapes and, on the 16 x 16 square lattice, both forms of the checkerboard (DPP exchange / lane program in LDS)."""
-    from elphdynamics_amd import configs, models
-    m = configs.make_model(tag, tol=1e-5)
-    usable, T, W, G = _wg_info(m)
-    assert usable == 1, tag
-    R, B = configs.rhs(m, 3)
+def _wg_resident_vs_streaming(m, B, variants, monkeypatch, tag):
+    """The comparison of test_wg_resident_cg_equals_the_two_kernel_iteration on a model and a batch of right-hand sides: every
+    variant (environment switches of the resident kernel) against the streaming iteration (ELPH_NO_WG=1) at 1e-5 and at 1e-13."""
+    from elphdynamics_amd import models
 
     def solve(env, tol):
         for k in ("ELPH_NO_WG", "ELPH_WG_T", "ELPH_WG_NO_DPP"):
@@ -1807,6 +1800,29 @@ def test_wg_resident_cg_equals_the_two_kernel_iteration(tag, monkeypatch):
         return X, it
 
     Xs, its = solve({"ELPH_NO_WG": "1"}, 1e-5)
+    for env in variants:
+        Xw, itw = solve(env, 1e-5)
+        # (another summation tree: the stop test crosses the tolerance within a step — within a few steps where the residual curve is
+        #  flat at the end of a solve of several hundred iterations)
+        assert np.max(np.abs(itw - its)) <= max(1, int(its.max()) // 150), (tag, env, itw, its)
+        assert rel(Xw, Xs) < 5e-5, (tag, env)
+    Xs13, _ = solve({"ELPH_NO_WG": "1"}, 1e-13)
+    for env in variants:
+        Xw13, _ = solve(env, 1e-13)
+        assert rel(Xw13, Xs13) < 1e-11, (tag, env, rel(Xw13, Xs13))
+
+
+@pytest.mark.parametrize("tag", ["b", "d", "e", "B", "C", "D", "E", "s", "q", "Q", "S", "y", "z", "Y", "r", "R", "w", "W", "u", "T", "t6", "t12"])
+def test_wg_resident_cg_equals_the_two_kernel_iteration(tag, monkeypatch):
+    """The whole solve in one launch (Krylov vectors in registers / LDS, teams of workgroups meeting through L2) against the
+    streaming two-kernel iteration: same algorithm, different summation trees for p.z and r.r — same iteration count up to
+    the knife edge, solutions equal to the solver tolerance at 1e-5 and to 1e-11 when both solve to 1e-13; both slices-per-wave
+    shapes and, on the 16 x 16 square lattice, both forms of the checkerboard (DPP exchange / lane program in LDS)."""
+    from elphdynamics_amd import configs
+    m = configs.make_model(tag, tol=1e-5)
+    usable, T, W, G = _wg_info(m)
+    assert usable == 1, tag
+    R, B = configs.rhs(m, 3)
     variants = [{}, {"ELPH_WG_T": "1"}, {"ELPH_WG_T": "2"}]
     if tag == "C":      # 4 slices per wave is the shape of large batches (DPP form only)
         variants += [{"ELPH_WG_T": "4"}, {"ELPH_WG_NO_DPP": "1"}, {"ELPH_WG_NO_DPP": "1", "ELPH_WG_T": "1"}]
@@ -1821,16 +1837,7 @@ def test_wg_resident_cg_equals_the_two_kernel_iteration(tag, monkeypatch):
             variants += [{"ELPH_WG_T": "4"}]
     if tag == "B":          # the 8 x 8 DPP form (one site per lane; default: one workgroup per right-hand side, 5 slices per wave) and its lane-program A/B
         variants += [{"ELPH_WG_T": "5"}, {"ELPH_WG_T": "8"}, {"ELPH_WG_NO_DPP": "1"}, {"ELPH_WG_NO_DPP": "1", "ELPH_WG_T": "5"}, {"ELPH_WG_NO_DPP": "1", "ELPH_WG_T": "8"}]
-    for env in variants:
-        Xw, itw = solve(env, 1e-5)
-        # (another summation tree: the stop test crosses the tolerance within a step — within a few steps where the residual curve is
-        #  flat at the end of a solve of several hundred iterations)
-        assert np.max(np.abs(itw - its)) <= max(1, int(its.max()) // 150), (tag, env, itw, its)
-        assert rel(Xw, Xs) < 5e-5, (tag, env)
-    Xs13, _ = solve({"ELPH_NO_WG": "1"}, 1e-13)
-    for env in variants:
-        Xw13, _ = solve(env, 1e-13)
-        assert rel(Xw13, Xs13) < 1e-11, (tag, env, rel(Xw13, Xs13))
+    _wg_resident_vs_streaming(m, B, variants, monkeypatch, tag)
     m.close()
 
 
