@@ -26,6 +26,7 @@
 // two-kernel iteration.
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "cg_fast_common.h"
@@ -1138,14 +1139,16 @@ static hipError_t launch_npl(elph_handle_s *h, const Shape &sh, dim3 grid, const
 // registers x 8 waves, or need most of the LDS), a sixteenth of the CUs left to whatever else the device runs: 240 on a whole MI355X
 // (256 CUs), proportionally fewer on a partitioned or CU-masked device (CPX: 32 CUs -> 30).  Queried once per device.
 int elph_i_resident_wg_limit(const elph_handle_s *h) {
-    static int cache[64] = {};
+    static std::atomic<int> cache[64];      // (0: not asked yet; two threads that ask at once store the same answer)
     const int d = (h && h->device >= 0 && h->device < 64) ? h->device : 0;
-    if (cache[d] <= 0) {
+    int lim = cache[d].load(std::memory_order_relaxed);
+    if (lim <= 0) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || cus <= 0) cus = 256;
-        cache[d] = std::max(1, cus - cus / 16);
+        lim = std::max(1, cus - cus / 16);
+        cache[d].store(lim, std::memory_order_relaxed);
     }
-    return cache[d];
+    return lim;
 }
 
 // ELPH_WG_T: force the slices per wave of the resident kernel (0: the rule of pick_shape)
@@ -1191,20 +1194,66 @@ char elph_slabs_test_timeout() {
 // solve that WOULD have taken a resident kernel — called by both of them (elph_wg_cg, elph_pcg_wg), so a handle that only ever runs
 // preconditioned solves recovers too.
 int elph_wg_cooldown_step(elph_handle_s *h) {
-    if (!h->wg_broken) return ELPH_OK;
-    if (--h->wg_cooldown > 0) return ELPH_OK;
-    h->wg_broken = false;
-    if (h->d_res && h->wg_abort_off) HIPCHK(hipMemsetAsync(static_cast<char *>(h->d_res) + h->wg_abort_off, 0, sizeof(int), h->stream));
+    ResidentState &S = h->res;
+    if (!S.cooling() || --S.cooldown > 0) return ELPH_OK;
+    if (S.d_res && S.abort_off) HIPCHK(hipMemsetAsync(static_cast<char *>(S.d_res) + S.abort_off, 0, sizeof(int), h->stream));
+    return ELPH_OK;
+}
+
+// after the stream has drained: did a team give up?  Reads the abort word and nothing else — what a time-out means is the caller's.
+int elph_wg_aborted(const elph_handle_s *h, bool *aborted) {
+    *aborted = false;
+    const ResidentState &S = h->res;
+    if (!S.d_res || S.abort_off == 0) return ELPH_OK;
+    int ab = 0;
+    HIPCHK(hipMemcpy(&ab, static_cast<const char *>(S.d_res) + S.abort_off, sizeof(int), hipMemcpyDeviceToHost));
+    *aborted = ab != 0;
+    return ELPH_OK;
+}
+
+// A resident launch of this handle timed out and its solve goes to the streaming iteration: the ONLY writer of that record.
+void elph_wg_timed_out(elph_handle_s *h) {
+    ResidentState &S = h->res;
+    S.cooldown = elph_wg_cooldown();
+    ++S.fallbacks;
+    elph_set_error("workgroup-resident CG timed out waiting for its team (T=%d W=%d G=%d); falling back to the two-kernel iteration", S.T, S.W, S.G);
+}
+
+// The control block of one resident launch (elph_internal.h: ResidentState).  Tags: a range of (iterations + 2) values per launch; the
+// block is zeroed only when it is (re)allocated or the 32-bit range wraps — or for every launch that numbers from 0 (WG_TAGS_RESTART).
+// The abort word sits at the END of the allocation (its place must not move with the batch size).
+int elph_wg_ctl(elph_handle_s *h, size_t n_rec, size_t n_extra, unsigned long long span, long long timeout_ms, WgTags tags, wg::WgCtl *R) {
+    ResidentState &S = h->res;
+    const size_t need = (n_rec + n_extra) * sizeof(wg::u64) + 64;
+    bool zero = tags == WG_TAGS_RESTART || (unsigned long long)S.next_tag + span >= 0xFFFFFFFFull;
+    if (need > S.cap) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (S.d_res) HIPCHK(hipFree(S.d_res));
+        S.d_res = nullptr;
+        S.cap = 0;
+        HIPCHK(hipMalloc(&S.d_res, need));
+        S.cap = need;
+        zero = true;
+    }
+    if (zero) { HIPCHK(hipMemsetAsync(S.d_res, 0, S.cap, h->stream)); S.next_tag = 0; }
+    S.abort_off = S.cap - 64;
+    *R = wg::WgCtl{};
+    R->slots = static_cast<wg::u64 *>(S.d_res);
+    R->bnd = nullptr;
+    R->abort = reinterpret_cast<int *>(static_cast<char *>(S.d_res) + S.abort_off);
+    R->epoch0 = S.next_tag;
+    if (tags == WG_TAGS_RUNNING) S.next_tag += (unsigned)span;
+    R->timeout_ticks = timeout_ms * 100000LL;      // wall_clock64 runs at 100 MHz
     return ELPH_OK;
 }
 
 // Runs the whole un-preconditioned CG for rhs [0, nrhs) after elph_launch_cg_init (fixed_iters > 0: exactly that many
 // iterations without stop test — measurement).  *ran = false: not applicable, nothing was launched.
-// ELPH_E_HIP with "workgroup-resident" in the message: a team timed out; the caller re-initialises and runs the two-kernel path.
-int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran) {
+// A team that timed out shows in the abort word (elph_wg_aborted): the caller restores x0_save, re-initialises and runs the two-kernel path.
+int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool x0_zero, double *x0_save, bool *ran) {
     *ran = false;
     if (B.params.use_prec) return ELPH_OK;
-    if (h->wg_broken) return ELPH_OK;                   // (cooling down after a time-out: elph_wg_cooldown_step, run_cg)
+    if (h->res.cooling()) return ELPH_OK;               // (after a time-out: elph_wg_cooldown_step, run_cg)
     if (!elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs)) return ELPH_OK;
     wg::Shape sh;
     ModelDev m = elph_model_dev(h);
@@ -1222,37 +1271,17 @@ int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iter
     }
     const size_t HS = (size_t)sh.npl * WAVE;
     const size_t n_slots = 2 * (size_t)nrhs * wg::SLOTS_PER_RHS, n_bnd = (sh.G > 1) ? 2 * (size_t)nrhs * sh.G * 2 * HS * 2 : 0;      // (x 2: by the parity of the iteration)
-    const size_t need = (n_slots + n_bnd) * sizeof(wg::u64) + 64;
-    // tags: a range of (iterations + 2) values per launch; the control block is zeroed only when it is (re)allocated or the
-    // 32-bit range wraps.  The abort word sits at the END of the allocation (its place must not move with the batch size).
-    const unsigned long long span = (unsigned long long)std::min<long long>(fixed_iters > 0 ? fixed_iters : B.params.maxiter, 1LL << 30) + 2;
-    bool zero = false;
-    if (need > h->res_cap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_res) HIPCHK(hipFree(h->d_res));
-        h->d_res = nullptr;
-        HIPCHK(hipMalloc(&h->d_res, need));
-        h->res_cap = need;
-        zero = true;
-    }
-    if ((unsigned long long)h->wg_epoch + span >= 0xFFFFFFFFull) zero = true;
-    if (zero) { HIPCHK(hipMemsetAsync(h->d_res, 0, h->res_cap, h->stream)); h->wg_epoch = 0; }
-    wg::WgCtl R;
-    char *base = static_cast<char *>(h->d_res);
-    R.slots = reinterpret_cast<wg::u64 *>(base);
-    R.bnd = R.slots + n_slots;
-    R.abort = reinterpret_cast<int *>(base + h->res_cap - 64);
-    R.epoch0 = h->wg_epoch;
-    h->wg_epoch += (unsigned)span;
-    R.G = sh.G; R.W = sh.W;
     // (2 s: a team at the dispatch frontier of an oversubscribed grid waits for whole solves of the resident ones — tens of ms for a
     //  batch of hundreds of right-hand sides; a measurement launch of thousands of fixed iterations gets its own duration on top)
-    R.timeout_ticks = (elph_wg_timeout_ms(2000) + (fixed_iters > 0 ? fixed_iters / 10 : 0)) * 100000LL;     // wall_clock64 runs at 100 MHz
+    wg::WgCtl R;
+    RC(elph_wg_ctl(h, n_slots, n_bnd, elph_wg_tag_span(B.params, fixed_iters), elph_wg_timeout_ms(2000) + (fixed_iters > 0 ? fixed_iters / 10 : 0),
+                   WG_TAGS_RUNNING, &R));
+    R.bnd = R.slots + n_slots;
+    R.G = sh.G; R.W = sh.W;
     R.fixed_iters = fixed_iters;
-    R.x0_zero = h->wg_x0_zero ? 1 : 0;     // (x0 = 0 known: the 4-slice DPP shape has an instantiation that does not read it)
-    h->wg_x0_zero = false;
-    if (fixed_iters <= 0)       // the caller's initial guess survives in d_zp (unused by an un-preconditioned solve) for the fallback
-        HIPCHK(hipMemcpyAsync(h->d_zp, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    R.x0_zero = x0_zero ? 1 : 0;           // (x0 = 0 known: the 4-slice DPP shape has an instantiation that does not read it)
+    if (x0_save)                // the caller's initial guess survives for the fallback (run_cg: in d_zp, unused by an un-preconditioned solve)
+        HIPCHK(hipMemcpyAsync(x0_save, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     const dim3 grid((unsigned)(8 * ((nrhs + 7) / 8) * sh.G));      // one solve per workgroup: every right-hand side has its team in the grid
     hipError_t e = hipSuccess;
     if (sh.hg) {
@@ -1278,26 +1307,8 @@ int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iter
         default: e = wg::launch_npl<5>(h, sh, grid, B, m, R); break;
     }
     if (e != hipSuccess) { elph_set_error("launch k_cg_wg failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    h->wg_T = sh.T; h->wg_W = sh.W; h->wg_G = sh.G;
-    h->wg_abort_off = h->res_cap - 64;
+    h->res.launched(sh.T, sh.W, sh.G);
     *ran = true;
-    return ELPH_OK;
-}
-
-// after the stream has drained: did a team give up?  (the abort word follows the records in the control block)
-int elph_wg_aborted(elph_handle_s *h, bool *aborted) {
-    *aborted = false;
-    if (!h->d_res || h->wg_abort_off == 0) return ELPH_OK;
-    int ab = 0;
-    HIPCHK(hipMemcpy(&ab, static_cast<char *>(h->d_res) + h->wg_abort_off, sizeof(int), hipMemcpyDeviceToHost));
-    if (ab) {
-        h->wg_broken = true;
-        h->wg_cooldown = elph_wg_cooldown();
-        ++h->wg_fallbacks;
-        *aborted = true;
-        elph_set_error("workgroup-resident CG timed out waiting for its team (T=%d W=%d G=%d); falling back to the two-kernel iteration",
-                       h->wg_T, h->wg_W, h->wg_G);
-    }
     return ELPH_OK;
 }
 
@@ -1320,7 +1331,7 @@ extern "C" int elph_debug_wg_stamps(unsigned long long *out16) {
 
 // One rank's launch of a solve over several GPUs (shard.hip holds the mailbox and calls this).  x0 = 0, b in B.r and B.p.
 // one rank's launch arguments of a sharded solve: form and team shape of its slab, control block (zeroed), tags
-static int shard_rank_setup(elph_handle_s *h, const CgBufs &B, long long fixed_iters, const ElphShardCtl &Sh, ModelDev &m, wg::Shape &sh,
+static int shard_rank_setup(elph_handle_s *h, long long fixed_iters, const ElphShardCtl &Sh, ModelDev &m, wg::Shape &sh,
                             wg::WgCtl &R) {
     m = elph_model_dev(h);
     // a slab whose rows the caller closed into a ring (a periodic rectangle in the reference's colouring: sharded.py, ring=True) runs a
@@ -1347,35 +1358,14 @@ static int shard_rank_setup(elph_handle_s *h, const CgBufs &B, long long fixed_i
     }
     const size_t HS = (size_t)sh.npl * WAVE;
     const size_t n_slots = 2 * wg::SLOTS_PER_RHS, n_bnd = (sh.G > 1) ? 2 * (size_t)sh.G * 2 * HS * 2 : 0;
-    const size_t need = (n_slots + n_bnd) * sizeof(wg::u64) + 64;
-    // tags: a range of (iterations + 2) values per launch; the control block is zeroed only when it is (re)allocated or the
-    // 32-bit range wraps.  The abort word sits at the END of the allocation (its place must not move with the batch size).
-    const unsigned long long span = (unsigned long long)std::min<long long>(fixed_iters > 0 ? fixed_iters : B.params.maxiter, 1LL << 30) + 2;
-    bool zero = false;
-    if (need > h->res_cap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_res) HIPCHK(hipFree(h->d_res));
-        h->d_res = nullptr;
-        HIPCHK(hipMalloc(&h->d_res, need));
-        h->res_cap = need;
-        zero = true;
-    }
-    if ((unsigned long long)h->wg_epoch + span >= 0xFFFFFFFFull) zero = true;
-    if (zero) { HIPCHK(hipMemsetAsync(h->d_res, 0, h->res_cap, h->stream)); h->wg_epoch = 0; }
-    char *base = static_cast<char *>(h->d_res);
-    R.slots = reinterpret_cast<wg::u64 *>(base);
+    // (the records of a sharded solve live in the ranks' mailboxes, one numbering for all: this rank's block — the boundary granules of
+    //  its workgroups — is zeroed and its tags restart at 2 with every launch.  A sharded solve has NO streaming fallback behind it — a
+    //  time-out is a failed solve — and its ranks start with whatever skew the host's barrier, first-launch code loading and time-slicing
+    //  leave: the long bound, elph_shard_timeout_ms)
+    RC(elph_wg_ctl(h, n_slots, n_bnd, 0, elph_shard_timeout_ms(), WG_TAGS_RESTART, &R));
     R.bnd = R.slots + n_slots;
-    R.abort = reinterpret_cast<int *>(base + h->res_cap - 64);
-    R.epoch0 = 0;                                          // (the records of a sharded solve live in the ranks' mailboxes: one numbering for all)
-    (void)span;
     R.G = sh.G; R.W = sh.W;
-    // (a sharded solve has NO streaming fallback behind it — a time-out is a failed solve — and its ranks start with whatever skew the
-    //  host's barrier, first-launch code loading and time-slicing leave: the long bound, elph_shard_timeout_ms)
-    R.timeout_ticks = elph_shard_timeout_ms() * 100000LL;
     R.fixed_iters = fixed_iters;
-    R.x0_zero = 0;
-    HIPCHK(hipMemsetAsync(base, 0, h->res_cap, h->stream));   // boundary granules of this rank's workgroups: tags restart at 2
-    h->wg_epoch = 0;
     return ELPH_OK;
 }
 
@@ -1383,7 +1373,7 @@ int elph_wg_cg_shard(elph_handle_s *h, const CgBufs &B, long long fixed_iters, c
     ModelDev m;
     wg::Shape sh;
     wg::WgCtl R;
-    const int rcs = shard_rank_setup(h, B, fixed_iters, Sh, m, sh, R);
+    const int rcs = shard_rank_setup(h, fixed_iters, Sh, m, sh, R);
     if (rcs) return rcs;
     const dim3 grid((unsigned)sh.G);                       // one right-hand side: its G workgroups, round-robin over the XCDs
     hipError_t e = hipSuccess;
@@ -1396,8 +1386,7 @@ int elph_wg_cg_shard(elph_handle_s *h, const CgBufs &B, long long fixed_iters, c
         default: e = wg::launch_shard_npl<5>(h, sh, grid, B, m, R, Sh); break;
     }
     if (e != hipSuccess) { elph_set_error("launch k_cg_wg (shard) failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    h->wg_T = sh.T; h->wg_W = sh.W; h->wg_G = sh.G;
-    h->wg_abort_off = h->res_cap - 64;
+    h->res.launched(sh.T, sh.W, sh.G);
     if (G_out) *G_out = sh.G;
     return ELPH_OK;
 }
@@ -1416,7 +1405,7 @@ int elph_wg_cg_ranks(elph_handle_s *const *hs, int P, const CgBufs *Bs, long lon
     for (int q = 0; q < P; ++q) {
         if (hs[q]->stream != stream) { elph_set_error("slab %d runs on another stream", q); return ELPH_E_STATE; }
         wg::Shape sh;
-        const int rc = shard_rank_setup(hs[q], Bs[q], fixed_iters, ctls[q], A[(size_t)q].m, sh, A[(size_t)q].R);
+        const int rc = shard_rank_setup(hs[q], fixed_iters, ctls[q], A[(size_t)q].m, sh, A[(size_t)q].R);
         if (rc) return rc;
         if (sh.hg || hs[q]->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("slabs on one device: lane-program or GRID form, site phonons"); return ELPH_E_UNSUPPORTED; }
         if (q == 0) sh0 = sh;
@@ -1452,7 +1441,7 @@ int elph_wg_cg_ranks(elph_handle_s *const *hs, int P, const CgBufs *Bs, long lon
 #undef RANKS_CASE
 #undef RANKS_LAUNCH
     if (e != hipSuccess) { elph_set_error("launch k_cg_wg (ranks) failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    for (int q = 0; q < P; ++q) { hs[q]->wg_T = 1; hs[q]->wg_W = sh0.W; hs[q]->wg_G = sh0.G; hs[q]->wg_abort_off = hs[q]->res_cap - 64; }
+    for (int q = 0; q < P; ++q) hs[q]->res.launched(1, sh0.W, sh0.G);
     if (G_out) *G_out = sh0.G;
     return ELPH_OK;
 }

@@ -465,7 +465,7 @@ extern "C" int elph_destroy(elph_handle h) {
     void *ptrs[] = {h->d_bi, h->d_bj, h->d_coloff, h->d_c, h->d_s, h->d_E, h->d_lam, h->d_stage_in, h->d_stage_out,
                     h->d_b, h->d_x, h->d_r, h->d_z, h->d_zp, h->d_p, h->d_tmp, h->d_part, h->d_state, h->d_phi, h->d_xfield,
                     h->d_hist, h->d_scal, h->d_alpha, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar, h->d_ssh_cb, h->d_ssh_slot, h->d_nu, h->d_tw, h->d_theta, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s,
-                    h->d_Tk, h->d_Tt, h->d_Pk, h->d_Pt, h->d_sq_bond, h->d_pg_bond, h->d_res, h->d_mu_ch};
+                    h->d_Tk, h->d_Tt, h->d_Pk, h->d_Pt, h->d_sq_bond, h->d_pg_bond, h->res.d_res, h->d_mu_ch};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_scal) (void)hipHostFree(h->h_scal);
@@ -929,6 +929,50 @@ static int read_hist(elph_handle_s *h, int nrhs, int64_t maxiter, double *eps_hi
     return ELPH_OK;
 }
 
+// Which resident form would this solve take, ignoring the cool-down (except that a handle that cools down does not BUILD its slabs just to
+// be counted) — in the order they are tried: the whole un-preconditioned solve in
+// one launch with the Krylov vectors in registers (cg_wg.hip: k_cg_wg); on a lattice beyond one wave's slice the same kernel on slabs of
+// rows of the lattice, all on this device, one launch per right-hand side (slabs.hip; x0 = 0 only — the slab kernel starts from it:
+// ldiv!'s zero-fill); the whole PRECONDITIONED solve in one launch for one to eight right-hand sides on the 16 x 16 square lattice
+// (pcg_wg.hip: k_pcg_wg).  `after`: the forms up to that one have declined.  The shape only — elph_wg_cg's cost rule is its own.
+enum ResidentForm { RES_NONE, RES_CG_WG, RES_SLABS, RES_PCG_WG };
+static ResidentForm resident_form(elph_handle_s *h, int nrhs, int use_prec, bool x0_zero, int64_t maxiter, ResidentForm after = RES_NONE) {
+    if (maxiter < 1) return RES_NONE;
+    if (use_prec) return (after < RES_PCG_WG && elph_pcg_wg_usable(h, nrhs)) ? RES_PCG_WG : RES_NONE;
+    if (after < RES_CG_WG && h->fast && elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs)) return RES_CG_WG;
+    // (cooling down: only slabs that exist already count — it has them, or the form is not its own)
+    if (after < RES_SLABS && x0_zero && (h->slabs || !h->res.cooling()) && elph_i_slabs_usable(h, nrhs)) return RES_SLABS;
+    return RES_NONE;
+}
+
+// One attempt of k_cg_wg / k_pcg_wg (use_prec) at the solve elph_launch_cg_init has set up.  The launcher parks the caller's initial guess
+// in x0_save — scratch its kind of solve does not use — once it has decided to launch.  *solved: the states are terminal, iters filled.
+// Otherwise the streaming iteration can start: nothing was launched (the form declined), or a team gave up (x, r of the right-hand sides
+// that had finished were overwritten) and every right-hand side is back at the caller's initial guess, re-initialised.
+static int resident_attempt(elph_handle_s *h, const SplitRun &S, int nrhs, int use_prec, const CgParams &P, bool x0_zero, double *x0_save,
+                            int64_t *iters, bool *solved) {
+    *solved = false;
+    bool ran = false, all_done = false, aborted = false;
+    CgBufs B = elph_make_bufs(h, nrhs);
+    B.params = P;
+    RC(use_prec ? elph_pcg_wg(h, B, nrhs, 0, x0_save, &ran) : elph_wg_cg(h, B, nrhs, 0, x0_zero, x0_save, &ran));
+    if (!ran) return ELPH_OK;
+    RC(read_states(S, iters, &all_done));
+    RC(elph_wg_aborted(h, &aborted));
+    if (!aborted) {
+        if (!all_done) {
+            elph_set_error(use_prec ? "resident preconditioned CG ended without a terminal state (internal error)"
+                                    : "workgroup-resident CG ended without a terminal state (internal error)");
+            return ELPH_E_STATE;
+        }
+        *solved = true;
+        return ELPH_OK;
+    }
+    elph_wg_timed_out(h);
+    HIPCHK(hipMemcpyAsync(h->d_x, x0_save, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return elph_launch_cg_init(h, nrhs, use_prec);
+}
+
 // Runs CG on d_b / d_x (layout S) for nrhs right-hand sides.  Returns per-rhs iteration counts.
 static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t maxiter, double kmax, int64_t *iters,
                   double *eps_hist /* host, optional, nrhs*(maxiter+1) */) {
@@ -948,75 +992,29 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
         }
     }
     h->cur_params = P;
-    // one solve of the cool-down after a resident kernel timed out — counted only for solves that WOULD have taken a resident kernel (either
-    // kernel, either kind of solve): a stream of large streaming batches in between does not bring the retry forward, and a solve that
+    // one solve of the cool-down after a resident kernel timed out — counted only for solves that WOULD have taken a resident kernel (any
+    // form, either kind of solve): a stream of large streaming batches in between does not bring the retry forward, and a solve that
     // never launches a resident kernel does not clear the abort word
-    if (h->wg_broken) {
-        bool eligible = maxiter >= 1 && (use_prec ? elph_pcg_wg_usable(h, nrhs) : h->fast && elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs));
-        if (!use_prec && !eligible && h->slabs && x0_zero && maxiter >= 1) eligible = elph_i_slabs_usable(h, nrhs);      // (the slab form of a large lattice, slabs.hip)
-        if (eligible) RC(elph_wg_cooldown_step(h));
-    }
+    if (h->res.cooling() && resident_form(h, nrhs, use_prec, x0_zero, maxiter) != RES_NONE) RC(elph_wg_cooldown_step(h));
     RC(elph_launch_cg_init(h, nrhs, use_prec, x0_zero));      // (x0 = 0: A x0 = 0 without the mat-vec)
-    h->wg_x0_zero = h->x_zero_seen;
     SplitRun S(h, nrhs);
-    bool all_done = false;
 
-    // whole solve in one launch with the Krylov vectors in registers (cg_wg.hip: k_cg_wg) when it applies
-    if (h->fast && !use_prec && maxiter >= 1 && elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs)) {
-        bool ran = false;
-        CgBufs B = elph_make_bufs(h, nrhs);
-        B.params = P;
-        // (elph_wg_cg saves the caller's initial guess in d_zp — unused by an un-preconditioned solve — once it has decided to launch)
-        RC(elph_wg_cg(h, B, nrhs, 0, &ran));
-        if (ran) {
-            RC(read_states(S, iters, &all_done));
-            bool aborted = false;
-            RC(elph_wg_aborted(h, &aborted));
-            if (!aborted) {
-                if (!all_done) { elph_set_error("workgroup-resident CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-                return read_hist(h, nrhs, maxiter, eps_hist);
-            }
-            // a team gave up (x, r of the right-hand sides that had finished were overwritten): start every right-hand side again
-            // from the caller's initial guess; the two-kernel iteration below does the work
-            HIPCHK(hipMemcpyAsync(h->d_x, h->d_zp, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            RC(elph_launch_cg_init(h, nrhs, use_prec));
+    // the resident forms, each where it applies; one that declines leaves the solve to the next, a time-out to the streaming iteration
+    for (ResidentForm f = RES_NONE; !h->res.cooling() && (f = resident_form(h, nrhs, use_prec, x0_zero, maxiter, f)) != RES_NONE;) {
+        bool solved = false;
+        if (f == RES_SLABS) {
+            RC(elph_i_slabs_solve(h, nrhs, P, 0, iters, &solved, nullptr));
+            if (!solved) RC(elph_launch_cg_init(h, nrhs, use_prec, true));      // (x is zero again: elph_i_slabs_solve)
+        } else {
+            RC(resident_attempt(h, S, nrhs, use_prec, P, x0_zero, use_prec ? h->d_tmp : h->d_zp, iters, &solved));
         }
-    }
-
-    // a lattice beyond one wave's slice: the resident kernel on slabs of rows of the lattice, all on this device, one launch per right-hand
-    // side (slabs.hip).  x0 = 0 only (the slab kernel starts from it): ldiv!'s zero-fill.
-    if (!use_prec && maxiter >= 1 && x0_zero && !h->wg_broken && elph_i_slabs_usable(h, nrhs)) {
-        bool ran = false;
-        RC(elph_i_slabs_solve(h, nrhs, P, 0, iters, &ran, nullptr));
-        if (ran) return read_hist(h, nrhs, maxiter, eps_hist);
-        RC(elph_launch_cg_init(h, nrhs, use_prec, true));      // (x is zero again: elph_i_slabs_solve)
-    }
-
-    // the whole PRECONDITIONED solve in one launch (pcg_wg.hip: k_pcg_wg) for one to eight right-hand sides on the 16 x 16 square lattice
-    if (use_prec && maxiter >= 1 && !h->wg_broken && elph_pcg_wg_usable(h, nrhs)) {
-        bool ran = false;
-        CgBufs B = elph_make_bufs(h, nrhs);
-        B.params = P;
-        const size_t xbytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);
-        HIPCHK(hipMemcpyAsync(h->d_tmp, h->d_x, xbytes, hipMemcpyDeviceToDevice, h->stream));     // the initial guess, for the fallback (A x0 in d_tmp has been consumed)
-        RC(elph_pcg_wg(h, B, nrhs, 0, &ran));
-        if (ran) {
-            RC(read_states(S, iters, &all_done));
-            bool aborted = false;
-            RC(elph_wg_aborted(h, &aborted));
-            if (!aborted) {
-                if (!all_done) { elph_set_error("resident preconditioned CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-                return read_hist(h, nrhs, maxiter, eps_hist);
-            }
-            HIPCHK(hipMemcpyAsync(h->d_x, h->d_tmp, xbytes, hipMemcpyDeviceToDevice, h->stream));
-            RC(elph_launch_cg_init(h, nrhs, use_prec));
-        }
+        if (solved) return read_hist(h, nrhs, maxiter, eps_hist);
     }
 
     // the streaming iteration, ELPH_CG_CHUNK iterations of every part between two reads of the states
     if (split_wanted(h, nrhs, use_prec, eps_hist != nullptr)) RC(split_begin(h, nrhs, S));
     const int64_t max_chunks = (maxiter + 1 + ELPH_CG_CHUNK - 1) / ELPH_CG_CHUNK + 1;
-    all_done = false;
+    bool all_done = false;
     for (int64_t c = 0; c < max_chunks && !all_done; ++c) {
         for (int it = 0; it < ELPH_CG_CHUNK; ++it) RC(split_iteration(S, use_prec));
         RC(read_states(S, iters, &all_done));
@@ -1871,7 +1869,7 @@ extern "C" int elph_bench_prepare(elph_handle h, int what, int nrhs, const doubl
     h->x_zero = false;
     RC(elph_launch_cg_init(h, nrhs, P.use_prec, true));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->bench_fresh = true;
+    h->x_zero = true;      // (x is zero: the elph_bench_run(9 | 10) that follows consumes the hint as run_cg does)
     return ELPH_OK;
 }
 
@@ -1895,8 +1893,8 @@ extern "C" int elph_bench_info(elph_handle h, int nrhs, int *slices_per_wave) {
 // out (0: the resident kernel is in use), *fallbacks = how many launches were given up and re-solved by the streaming iteration.
 extern "C" int elph_wg_status(elph_handle h, int *cooling_down, int64_t *fallbacks) {
     CHECK_H(h);
-    if (cooling_down) *cooling_down = h->wg_broken ? h->wg_cooldown : 0;
-    if (fallbacks) *fallbacks = h->wg_fallbacks;
+    if (cooling_down) *cooling_down = h->res.cooldown;
+    if (fallbacks) *fallbacks = h->res.fallbacks;
     return ELPH_OK;
 }
 
@@ -1904,7 +1902,7 @@ extern "C" int elph_bench_wg_info(elph_handle h, int nrhs, int *usable, int *T, 
     CHECK_H(h);
     if (!usable || nrhs < 1) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     int t = 0, w = 0, g = 0;
-    *usable = (!h->wg_broken && elph_wg_usable(h, &t, &w, &g, nrhs)) ? 1 : 0;
+    *usable = (!h->res.cooling() && elph_wg_usable(h, &t, &w, &g, nrhs)) ? 1 : 0;
     if (T) *T = t;
     if (W) *W = w;
     if (G) *G = g;
@@ -1965,15 +1963,15 @@ extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int u
     int rc = ELPH_OK;
     if (what == 9 || what == 10) {        // `reps` iterations of the whole batch in one launch of the workgroup-resident kernel (10: the preconditioned one)
         bool ran = false, aborted = false;
+        const bool x0_zero = h->x_zero;      // (x is known to be zero only right after elph_bench_prepare)
+        h->x_zero = false;
         CgBufs B = elph_make_bufs(h, nrhs);
         B.params = h->cur_params;
         hipError_t er = hipStreamSynchronize(h->stream);
         if (er == hipSuccess) er = hipEventRecord(e0, h->stream);
         if (er == hipSuccess) {
             rc = elph_wg_cooldown_step(h);
-            h->wg_x0_zero = h->bench_fresh && h->x_zero_seen;      // (x is known to be zero only right after elph_bench_prepare)
-            h->bench_fresh = false;
-            if (rc == ELPH_OK) rc = (what == 9) ? elph_wg_cg(h, B, nrhs, reps, &ran) : elph_pcg_wg(h, B, nrhs, reps, &ran);
+            if (rc == ELPH_OK) rc = (what == 9) ? elph_wg_cg(h, B, nrhs, reps, x0_zero, nullptr, &ran) : elph_pcg_wg(h, B, nrhs, reps, nullptr, &ran);
             if (rc == ELPH_OK && !ran) { elph_set_error("the workgroup-resident kernel does not apply to this handle"); rc = ELPH_E_UNSUPPORTED; }
         }
         if (er == hipSuccess && rc == ELPH_OK) er = hipEventRecord(e1, h->stream);
@@ -1985,7 +1983,7 @@ extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int u
         if (er != hipSuccess) { elph_set_error("bench (workgroup-resident): %s", hipGetErrorString(er)); return ELPH_E_HIP; }
         if (rc) return rc;
         RC(elph_wg_aborted(h, &aborted));
-        if (aborted) return ELPH_E_HIP;
+        if (aborted) { elph_wg_timed_out(h); return ELPH_E_HIP; }
         *ms_total = (double)ms;
         return ELPH_OK;
     }

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -302,6 +303,24 @@ struct KpmState {
     double lam_mag(int c) const { return tab.lam.empty() ? 1.0 : tab.lam[2 * (size_t)c + 1]; }
 };
 
+// The host state of the resident solvers — k_cg_wg in its plain, sharded and slab launches (cg_wg.hip), k_pcg_wg (pcg_wg.hip).  They share
+// ONE control block per handle, one tag numbering, one abort word and one time-out / cool-down / fallback protocol:
+//   block   [meeting records | extra words: k_cg_wg's boundary granules or k_pcg_wg's flags | ... | abort word in the last 64 bytes]
+//           laid out, grown, zeroed and numbered by elph_wg_ctl alone;
+//   shape   of the last launch, for the time-out message: launched();
+//   health  elph_wg_timed_out is the only writer of a time-out, elph_wg_cooldown_step the only one that counts it down and clears it.
+struct ResidentState {
+    void *d_res = nullptr;                 // the control block (freed by elph_destroy)
+    size_t cap = 0;                        // its bytes
+    unsigned next_tag = 0;                 // next free tag of the meeting records (WgCtl::epoch0 of the next launch)
+    size_t abort_off = 0;                  // byte offset of the abort word in d_res (0: nothing launched yet)
+    int T = 0, W = 0, G = 0;               // shape of the last resident launch (0: none yet)
+    int cooldown = 0;                      // solves left on the streaming iteration after a time-out, then the resident kernels are tried again
+    long long fallbacks = 0;               // how many launches timed out (elph_wg_status)
+    bool cooling() const { return cooldown > 0; }
+    void launched(int t, int w, int g) { T = t; W = w; G = g; }
+};
+
 struct elph_handle_s {
     int kind = 0, device = 0;
     int64_t N = 0, L = 0, nb = 0, ndim = 0;
@@ -354,19 +373,12 @@ struct elph_handle_s {
     void *greens = nullptr;                // GreensState (greens.hip), owned
     void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
     void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
-    void *d_res = nullptr;                 // control block of the workgroup-resident CG (cg_wg.hip): meeting records, abort word, boundary slices
-    size_t res_cap = 0;
-    // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854);
-    // run_cg reads AND clears it first thing (an early error return cannot leave it behind for the next solve) and hands it to
-    // elph_launch_cg_init (A x0 = 0 needs no mat-vec; x_zero_seen tells the resident kernel not to read x0 either)
-    bool x_zero = false, x_zero_seen = false, wg_x0_zero = false;
-    bool bench_fresh = false;              // elph_bench_prepare ran and no elph_bench_run(9 | 10) has consumed its zeroed x yet
-    bool wg_broken = false;                // a workgroup-resident launch timed out: streaming iteration for the next wg_cooldown solves, then retry
-    int wg_cooldown = 0;
-    long long wg_fallbacks = 0;            // how many times that happened (elph_wg_status)
-    unsigned wg_epoch = 0;                 // next free tag of the meeting records (cg_wg.hip: WgCtl::epoch0)
-    size_t wg_abort_off = 0;               // byte offset of the abort word in d_res
-    int wg_T = 0, wg_W = 0, wg_G = 0;      // shape of the last workgroup-resident solve (0: none yet)
+    ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
+    // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
+    // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
+    // behind for the next solve) and hand it on as an argument: to elph_launch_cg_init (A x0 = 0 needs no mat-vec) and to elph_wg_cg
+    // (the resident kernel does not read x0 either)
+    bool x_zero = false;
     long long ap_count = 0;                // k_cg_ap launches since the last cg_init (ping-pong parity)
     int force_T = 0;                       // ELPH_CHUNK_T: 0 auto, 1 never chunk, n > 1 force n slices per wave (template sizes 2/4/5/8/10/16/20 dividing Ltau: the unrolled kernel; any other: k_cg_ap_chunk_rt, ragged last chunk)
 
@@ -523,8 +535,22 @@ void elph_i_slabs_free(elph_handle_s *h);
 
 // ---- workgroup-resident CG (cg_wg.hip): the whole un-preconditioned solve in one launch
 bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs = 1);
-int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran);
-int elph_wg_aborted(elph_handle_s *h, bool *aborted);       // after the stream has drained
+// x0_zero: the library zeroed d_x for this solve; x0_save: where the initial guess goes once the launch is decided, for the caller's
+// fallback after a time-out (nullptr: not kept — a measurement launch)
+int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool x0_zero, double *x0_save, bool *ran);
+// the resident solvers' control block for one launch (ResidentState): room for n_rec record words + n_extra words behind them + the abort
+// word, zeroed when it grows or the 32-bit tags would wrap; *R comes back with slots, abort, epoch0 (a range of `span` tags of its own)
+// and timeout_ticks filled, bnd = nullptr, everything else 0.  WG_TAGS_RESTART (a sharded launch: its records live in the ranks'
+// mailboxes under one numbering for all) zeroes the block every time and numbers from 0 — no span.
+namespace wg { struct WgCtl; }
+enum WgTags { WG_TAGS_RUNNING, WG_TAGS_RESTART };
+int elph_wg_ctl(elph_handle_s *h, size_t n_rec, size_t n_extra, unsigned long long span, long long timeout_ms, WgTags tags, wg::WgCtl *R);
+// tags of one launch: one per iteration + 2
+inline unsigned long long elph_wg_tag_span(const CgParams &P, long long fixed_iters) {
+    return (unsigned long long)std::min<long long>(fixed_iters > 0 ? fixed_iters : P.maxiter, 1LL << 30) + 2;
+}
+int elph_wg_aborted(const elph_handle_s *h, bool *aborted); // after the stream has drained: was the abort word raised?  (reads only)
+void elph_wg_timed_out(elph_handle_s *h);                   // THE record of a time-out: cool-down, fallback count, message
 bool elph_pg_cheb_usable(const elph_handle_s *h);
 bool elph_pg_disorder_ok(const elph_handle_s *h);      // hopping disorder on this handle's patch shape (pgrid.hip)                       // pgrid.hip
 int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part = nullptr, int nrz = 0, const double *rr_part = nullptr);
@@ -540,7 +566,7 @@ int elph_wg_cooldown();                                     // ELPH_WG_COOLDOWN 
 char elph_slabs_test_timeout();                             // first character of ELPH_SLABS_TEST_TIMEOUT, 0 when unset (cg_wg.hip)
 // ---- workgroup-resident KPM-preconditioned CG (pcg_wg.hip): the whole preconditioned solve of 1..8 right-hand sides in one launch
 bool elph_pcg_wg_usable(const elph_handle_s *h, int nrhs);
-int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran);
+int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, double *x0_save, bool *ran);      // x0_save: as elph_wg_cg's
 CgBufs elph_make_bufs(elph_handle_s *h, int nrhs);
 // reg: the plan's reg_cheb (the register-exchange recursion where elph_reg_cheb_form has one); rz_part: the r.z partials in frequency space
 int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, double *rz_part = nullptr, int nrz = 0,

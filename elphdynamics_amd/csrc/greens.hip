@@ -221,6 +221,7 @@ extern "C" int elph_greens_update(elph_handle h, const double *R, int use_precon
     RC(elph_launch_r2s(h, g->R, h->d_stage_in, nv));
     RC(elph_launch_mul(h, 1, h->d_b, g->R, nv));                       // Mᵀr₁ (model.v″, :223-224)
     RC(elph_launch_zero(h, h->d_x, (int64_t)nv * h->ndim));            // fill!(M⁻¹r₁, 0)  :213
+    h->x_zero = false;                                                 // (this path does not use the x = 0 hint, and takes nobody else's)
     std::vector<int64_t> it((size_t)nv);
     std::vector<double> res((size_t)nv);
     std::vector<int> fl((size_t)nv);

@@ -1304,8 +1304,7 @@ int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero) {
     h->ap_count = 0;
     const int N = (int)h->N, L = (int)h->L;
     int rc = ELPH_OK;
-    h->x_zero_seen = x_zero;
-    if (h->x_zero_seen) {       // x0 = 0 (the library zeroed it for this solve): A x0 = 0 without the mat-vec
+    if (x_zero) {       // x0 = 0 (the library zeroed it for this solve): A x0 = 0 without the mat-vec
         if (hipMemsetAsync(h->d_tmp, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream) != hipSuccess) { elph_set_error("memset failed"); return ELPH_E_HIP; }
     } else {
         rc = elph_launch_mul(h, 2, h->d_tmp, h->d_x, nrhs);

@@ -527,7 +527,7 @@ extern "C" int elph_debug_pcg_stamps(unsigned long long *out32) {
 #endif
 
 // Whether the resident preconditioned kernel takes this solve, and its team shape (the shape only: a handle cooling down after a time-out
-// — h->wg_broken — is its callers' test).
+// — h->res.cooling() — is its callers' test).
 static bool pcg_shape(const elph_handle_s *h, int nrhs, int *Wo, int *Go, int *nto) {
     // Measured on MI355X (profiles/r03/pcg_wg_phase_stamps.log) this form takes 38.9 us per iteration for one
     // right-hand side of config C against 35.2 us of the five-kernel streaming form — the two tau-transforms cost 6 us each on the
@@ -564,37 +564,19 @@ bool elph_pcg_wg_usable(const elph_handle_s *h, int nrhs) { return pcg_shape(h, 
 
 // Runs the whole preconditioned CG for rhs [0, nrhs) after elph_launch_cg_init(h, nrhs, 1) (fixed_iters > 0: exactly that many
 // iterations without stop test — measurement).  *ran = false: not applicable, nothing was launched.
-int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool *ran) {
+int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, double *x0_save, bool *ran) {
     *ran = false;
     int W = 0, G = 0, nt = 0;
-    if (!B.params.use_prec || h->wg_broken || !pcg_shape(h, nrhs, &W, &G, &nt)) return ELPH_OK;      // (cooling down: elph_wg_cooldown_step, run_cg)
+    if (!B.params.use_prec || h->res.cooling() || !pcg_shape(h, nrhs, &W, &G, &nt)) return ELPH_OK;      // (cooling down: elph_wg_cooldown_step, run_cg)
     ModelDev m = elph_model_dev(h);
     if (!m.uniform || !m.sq_bond) return ELPH_OK;
     const size_t n_slots = 2 * (size_t)nrhs * wg::SLOTS_PER_RHS, n_flags = (size_t)nrhs * wg::PCG_FLAGS;
-    const size_t need = (n_slots + n_flags) * sizeof(wg::u64) + 64;
-    const unsigned long long span = (unsigned long long)std::min<long long>(fixed_iters > 0 ? fixed_iters : B.params.maxiter, 1LL << 30) + 2;
-    bool zero = false;
-    if (need > h->res_cap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_res) HIPCHK(hipFree(h->d_res));
-        h->d_res = nullptr;
-        HIPCHK(hipMalloc(&h->d_res, need));
-        h->res_cap = need;
-        zero = true;
-    }
-    if ((unsigned long long)h->wg_epoch + span >= 0xFFFFFFFFull) zero = true;
-    if (zero) { HIPCHK(hipMemsetAsync(h->d_res, 0, h->res_cap, h->stream)); h->wg_epoch = 0; }
-    wg::WgCtl R;
-    char *base = static_cast<char *>(h->d_res);
-    R.slots = reinterpret_cast<wg::u64 *>(base);
-    R.bnd = nullptr;
-    R.abort = reinterpret_cast<int *>(base + h->res_cap - 64);
-    R.epoch0 = h->wg_epoch;
-    h->wg_epoch += (unsigned)span;
+    wg::WgCtl R;        // (bnd stays nullptr: the words behind the records are this kernel's flags)
+    RC(elph_wg_ctl(h, n_slots, n_flags, elph_wg_tag_span(B.params, fixed_iters), elph_wg_timeout_ms(2000), WG_TAGS_RUNNING, &R));
     R.G = G; R.W = W;
-    R.timeout_ticks = elph_wg_timeout_ms(2000) * 100000LL;
     R.fixed_iters = fixed_iters;
-    R.x0_zero = 0;
+    if (x0_save)        // the caller's initial guess, for the fallback (run_cg: in d_tmp — A x0 there has been consumed)
+        HIPCHK(hipMemcpyAsync(x0_save, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     wg::PcgCtl Pc;
     Pc.flags = R.slots + n_slots;
     Pc.Wf = h->mf[0][0].W; Pc.Wi = h->mf[0][1].W;
@@ -615,8 +597,7 @@ int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_ite
         if (e == hipSuccess) { hipLaunchKernelGGL((wg::k_pcg_wg<20>), grid, dim3(512), shm, h->stream, B, m, R, Pc); e = hipGetLastError(); }
     }
     if (e != hipSuccess) { elph_set_error("launch k_pcg_wg failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    h->wg_T = 2; h->wg_W = W; h->wg_G = G;
-    h->wg_abort_off = h->res_cap - 64;
+    h->res.launched(2, W, G);
     *ran = true;
     return ELPH_OK;
 }

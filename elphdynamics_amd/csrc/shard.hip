@@ -308,7 +308,7 @@ static int shard_run(elph_handle_s *h, const double *b_slab, double tol, int64_t
     bool aborted = false;
     rc = elph_wg_aborted(h, &aborted);
     if (rc) return rc;
-    if (aborted) return ELPH_E_HIP;
+    if (aborted) { elph_wg_timed_out(h); return ELPH_E_HIP; }
     return ELPH_OK;
 }
 
@@ -369,7 +369,7 @@ int elph_i_shard_run_ranks(elph_handle_s *const *hs, int P, int nsets, void *h_a
         bool aborted = false;
         rc = elph_wg_aborted(hs[q], &aborted);
         if (rc) return rc;
-        if (aborted) { hs[q]->wg_broken = false; hs[q]->wg_cooldown = 0; return ELPH_I_ABORTED; }      // (the caller owns the fallback and its cool-down; every OTHER failure keeps its own code)
+        if (aborted) return ELPH_I_ABORTED;      // (the caller owns the fallback and its cool-down; every OTHER failure keeps its own code)
     }
     if (state_out) for (int k = 0; k < nsets; ++k) state_out[k] = hs[k * P]->h_state[0];
     return ELPH_OK;

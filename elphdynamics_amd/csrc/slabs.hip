@@ -194,7 +194,7 @@ static bool slabs_debug() { return getenv("ELPH_SLABS_DEBUG") != nullptr; }
 // right-hand side, or two where two SETS of slabs fit the chip together (2 P G <= 240 workgroups: both solves in one launch — one launch
 // after the other two right-hand sides cost 22-25 us against 15-18 streaming).
 // ELPH_SLABS=0: never; =1: wherever the decomposition exists (any count, slabs up to 320 sites, up to 8 right-hand sides: the tests);
-// ELPH_SLABS_P forces the slab count.  The shape only: a handle cooling down after a time-out (h->wg_broken) is its callers' test.
+// ELPH_SLABS_P forces the slab count.  The shape only: a handle cooling down after a time-out (h->res.cooling()) is its callers' test.
 bool elph_i_slabs_usable(elph_handle_s *h, int nrhs) {
     const char *e = getenv("ELPH_SLABS");
     const int force = e ? atoi(e) : -1;
@@ -291,9 +291,8 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
         if (rc == ELPH_I_ABORTED) {
             // a time-out inside the launch (the abort word was raised — and nothing else: an event, copy or launch failure comes back as
             // ELPH_E_HIP and is returned below): cool down like the other resident kernels, streaming takes over
-            h->wg_broken = true;
-            h->wg_cooldown = elph_wg_cooldown();
-            ++h->wg_fallbacks;
+            h->res.launched(S->hs[0]->res.T, S->hs[0]->res.W, S->hs[0]->res.G);      // (the slabs' shape, for the message)
+            elph_wg_timed_out(h);
             HIPCHK(hipMemsetAsync(h->d_x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
             return ELPH_OK;
         }
@@ -321,7 +320,7 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
 extern "C" int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int *sites_per_slab, int *own_sites) {
     if (!h || !usable) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     HIPCHK(hipSetDevice(h->device));
-    *usable = (!h->wg_broken && elph_i_slabs_usable(h, nrhs)) ? 1 : 0;      // (0 while the handle cools down after a time-out)
+    *usable = (!h->res.cooling() && elph_i_slabs_usable(h, nrhs)) ? 1 : 0;      // (0 while the handle cools down after a time-out)
     const SlabSet *S = static_cast<const SlabSet *>(h->slabs);
     if (slabs) *slabs = (*usable && S) ? S->P : 0;
     if (sites_per_slab) *sites_per_slab = (*usable && S) ? S->Nloc : 0;

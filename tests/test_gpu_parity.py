@@ -529,6 +529,19 @@ def test_hopping_disorder_in_the_patch_layout_batched(tag, nchains, per, monkeyp
     assert rel(out["1"][0], out["0"][0]) < 1e-9
 
 
+def _holstein_16x16_ltau80():
+    """Config C's lattice with 80 time slices: the smallest model on which both resident kernels exist (k_pcg_wg: 5 CG workgroups)."""
+    from elphdynamics_amd import lattice as lat, models, synth
+    m = models.HolsteinModel(lat.Lattice(1, 16, 16, 1), 8.0, 0.1, tol=1e-5, maxiter=10000)
+    m.assign_t_(1.0, 1, 1, (1, 0, 0)); m.assign_t_(1.0, 1, 1, (0, 1, 0))
+    m.assign_omega_(1.0); m.assign_lambda_(1.0); m.assign_mu_(0.0)
+    m.initialize_model_()
+    m.x[:] = synth.phonon_field(m.Nph, m.Ltau, 8.0, 0.1, omega=1.0, lam=1.0, seed=21)
+    models.update_model_(m)
+    assert m.Ltau == 80
+    return m
+
+
 @pytest.mark.parametrize("ltau", [160, 80])
 def test_resident_preconditioned_cg_vs_streaming_and_oracle(oracle, monkeypatch, ltau):
     """pcg_wg.hip (ELPH_PCG_WG=1: the whole KPM-preconditioned solve of 1..8 right-hand sides in one launch — CG workgroups, helper
@@ -536,18 +549,8 @@ def test_resident_preconditioned_cg_vs_streaming_and_oracle(oracle, monkeypatch,
     five-kernel streaming form and the oracle on config C (160 time slices: 40 reduction tiles per transform tile) and on the same
     lattice with 80 slices (the 20-tile instantiation; 5 CG workgroups, helpers with two frequencies per wave pair idle in part):
     same iteration counts, same residual history, solutions to 1e-10."""
-    from elphdynamics_amd import configs, models, preconditioners as pc, synth
-    from elphdynamics_amd import lattice as lat
-    if ltau == 160:
-        m = configs.make_model("C", tol=1e-5)
-    else:
-        m = models.HolsteinModel(lat.Lattice(1, 16, 16, 1), 8.0, 0.1, tol=1e-5, maxiter=10000)
-        m.assign_t_(1.0, 1, 1, (1, 0, 0)); m.assign_t_(1.0, 1, 1, (0, 1, 0))
-        m.assign_omega_(1.0); m.assign_lambda_(1.0); m.assign_mu_(0.0)
-        m.initialize_model_()
-        m.x[:] = synth.phonon_field(m.Nph, m.Ltau, 8.0, 0.1, omega=1.0, lam=1.0, seed=21)
-        models.update_model_(m)
-        assert m.Ltau == 80
+    from elphdynamics_amd import configs, models, preconditioners as pc
+    m = configs.make_model("C", tol=1e-5) if ltau == 160 else _holstein_16x16_ltau80()
     om = _oracle_model(oracle, m)
     P = pc.SymmetricKPMPreconditioner(m, 20, 0.05, 1.0, 1.0)
     oP = oracle.make_kpm(om, n=20, buf=0.05, c1=1.0, c2=1.0)
@@ -2084,6 +2087,53 @@ def test_wg_resident_cg_shape_pin_makes_bits_independent_of_the_batch(monkeypatc
     # without the pin the two batch sizes take different shapes (documented behaviour, not a defect): same solution to the tolerance
     monkeypatch.delenv("ELPH_WG_T")
     assert _wg_info(m, 1)[1] == 1 and _wg_info(m, 20)[1] == 2 and _wg_info(m, 50)[1] == 4
+    m.close()
+
+
+def test_resident_kernels_alternate_on_one_handle(oracle, monkeypatch):
+    """k_cg_wg and k_pcg_wg share one control block per handle — one tag numbering, one abort word — and lay it out differently (records +
+    boundary granules, records + flags).  One handle runs them alternately (16 x 16 sites, 80 time slices; ELPH_PCG_WG=1 and
+    ELPH_WG_ALWAYS=1 make every solve resident); the batch of 24 grows the block, which is reallocated and zeroed.  Both kernels sum in
+    a fixed order, so every solve must be BIT-identical — iteration counts and solution — to the same solve on a fresh handle that has
+    run nothing else, with no fallback counted anywhere; a preconditioned solve of the streaming form (other summation order) must differ
+    in bits, which shows that k_pcg_wg did run."""
+    from elphdynamics_amd import configs, models, preconditioners as pc
+    monkeypatch.setenv("ELPH_PCG_WG", "1")
+    monkeypatch.setenv("ELPH_WG_ALWAYS", "1")
+    bounds = {}
+
+    def handle():
+        m = _holstein_16x16_ltau80()
+        P = pc.SymmetricKPMPreconditioner(m, 20, 0.05, 1.0, 1.0)
+        if not bounds:
+            oP = oracle.make_kpm(_oracle_model(oracle, m), n=20, buf=0.05, c1=1.0, c2=1.0)
+            rng = np.random.default_rng(11)
+            bounds["e_min"], bounds["e_max"] = oracle.kpm_setup(oP, b_max=rng.standard_normal(m.Nsites), b_min=rng.standard_normal(m.Nsites))
+        pc.setup_(P, **bounds)
+        return m, P
+
+    def solve(m, P, B, prec):
+        if not prec:
+            assert _wg_info(m, len(B))[0] == 1
+        X = np.zeros_like(B)
+        it, _, fl = models.ldiv_batched_(X, m, B, P=P if prec else None)
+        assert not fl.any() and _wg_status(m) == (0, 0), (prec, len(B), _wg_status(m))
+        return X, it
+
+    m, P = handle()
+    _, B = configs.rhs(m, 24)
+    for step, (prec, nr) in enumerate([(True, 8), (False, 1), (False, 24), (True, 3), (False, 2), (True, 8)]):
+        Bs = np.ascontiguousarray(B[:nr])
+        X, it = solve(m, P, Bs, prec)
+        m1, P1 = handle()
+        X1, it1 = solve(m1, P1, Bs, prec)
+        assert np.array_equal(it, it1) and np.array_equal(X, X1), (step, prec, nr)
+        if prec:
+            monkeypatch.setenv("ELPH_PCG_WG", "0")
+            Xs, its = solve(m1, P1, Bs, prec)
+            monkeypatch.setenv("ELPH_PCG_WG", "1")
+            assert np.array_equal(its, it1) and rel(X1, Xs) < 1e-9 and not np.array_equal(X1, Xs), (step, nr)
+        m1.close()
     m.close()
 
 
