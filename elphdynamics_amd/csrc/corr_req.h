@@ -1,4 +1,5 @@
-// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5) and bondcorr.hip (bonds, N = 2):
+// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2) and
+// ssh_measure.hip (on-site and PhononGreens over phonon types, N = 5):
 // the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group does with its one
 // accumulator allocation [lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's accumulator is
 // [L0][L1][L2][L3][n_p] doubles, first index fastest, L0 = L + 1 (time-dependent, tau = beta included) or 1 (equal-time).
@@ -16,11 +17,15 @@ struct CorrReq {                // by value into the kernels
     int np[N], L0[N];           // np = 0: not measured
 };
 
-// the words in which the two groups' messages differ
+// the words in which the groups' messages differ
 struct CorrWords {
-    const char *prefix;         // "measurements" / "bond correlations"
+    const char *prefix;         // "measurements" / "bond correlations" / "SSH measurements"
     const char *index;          // what a pair names: "orbital" / "bond"
     const char *no_pair;        // "with no orbital pair" / "with no pair of bonds"
+    // one correlation of the group may count something else: its index in the request arrays (-1: none), what its pairs name
+    // ("phonon type") and how a request without pairs reads
+    int other = -1;
+    const char *other_index = nullptr, *other_no_pair = nullptr;
 };
 
 template <int N>
@@ -37,10 +42,11 @@ struct CorrPlan {
 };
 
 // measure / time_dependent / npairs / pairs (1-based, the requests' lists one after another) of a create call into P.  A pair's indices
-// run over 1..limit; `lead` doubles precede the first correlation.  Pure: no HIP call, so a bad request fails before anything is allocated.
+// run over 1..limit (1..other_limit for the correlation w.other); `lead` doubles precede the first correlation.  Pure: no HIP call, so a
+// bad request fails before anything is allocated.
 template <int N>
 int corr_plan(CorrPlan<N> &P, const CorrWords &w, const char *const *names, const int *measure, const int *time_dependent, const int *npairs,
-              const int *pairs, int limit, int L, int nc, size_t lead) {
+              const int *pairs, int limit, int L, int nc, size_t lead, int other_limit = 0) {
     P = CorrPlan<N>();
     P.nc = nc;
     P.total = lead;
@@ -48,12 +54,14 @@ int corr_plan(CorrPlan<N> &P, const CorrWords &w, const char *const *names, cons
     for (int c = 0; c < N; ++c) {
         P.req.np[c] = 0; P.req.L0[c] = 1;
         if (!measure[c]) continue;
-        if (npairs[c] < 1 || !pairs) { elph_set_error("%s: %s is requested %s", w.prefix, names[c], w.no_pair); return ELPH_E_ARG; }
+        const bool other = (c == w.other);
+        const int lim = other ? other_limit : limit;
+        if (npairs[c] < 1 || !pairs) { elph_set_error("%s: %s is requested %s", w.prefix, names[c], other ? w.other_no_pair : w.no_pair); return ELPH_E_ARG; }
         for (int p = 0; p < npairs[c]; ++p)
             for (int k = 0; k < 2; ++k) {
                 const int o = pairs[2 * (at + p) + k];
-                if (o < 1 || o > limit) {
-                    elph_set_error("%s: %s pair %d names %s %d, outside 1..%d", w.prefix, names[c], p + 1, w.index, o, limit);
+                if (o < 1 || o > lim) {
+                    elph_set_error("%s: %s pair %d names %s %d, outside 1..%d", w.prefix, names[c], p + 1, other ? w.other_index : w.index, o, lim);
                     return ELPH_E_ARG;
                 }
                 P.prs.push_back(o - 1);
@@ -129,7 +137,7 @@ inline void corr_free(std::initializer_list<void *> ptrs) {
     for (void *p : ptrs) if (p) (void)hipFree(p);
 }
 
-// ---- the state checks of both groups' entry points
+// ---- the state checks of the groups' entry points
 inline int corr_need(const void *state, const char *create) {
     if (!state) { elph_set_error("%s has not been called", create); return ELPH_E_STATE; }
     return ELPH_OK;
@@ -143,8 +151,13 @@ inline int corr_refuse_chains(const elph_handle_s *h, const char *prefix) {
     return ELPH_OK;
 }
 
-inline int corr_refuse_handle(const elph_handle_s *h, const char *prefix) {
-    if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("%s: the SSH model is not supported (Holstein only)", prefix); return ELPH_E_UNSUPPORTED; }
+// kind: the model the group measures
+inline int corr_refuse_handle(const elph_handle_s *h, const char *prefix, int kind = ELPH_MODEL_HOLSTEIN) {
+    if (h->kind != kind) {
+        if (kind == ELPH_MODEL_HOLSTEIN) elph_set_error("%s: the SSH model is not supported (Holstein only)", prefix);
+        else elph_set_error("%s: the Holstein model is not supported (SSH only)", prefix);
+        return ELPH_E_UNSUPPORTED;
+    }
     if (h->shard || h->is_slab) { elph_set_error("%s: sharded and slab handles are not supported", prefix); return ELPH_E_UNSUPPORTED; }
     return corr_refuse_chains(h, prefix);
 }

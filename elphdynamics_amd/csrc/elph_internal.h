@@ -373,6 +373,7 @@ struct elph_handle_s {
     void *greens = nullptr;                // GreensState (greens.hip), owned
     void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
     void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
+    void *ssh_meas = nullptr;              // SshMeasState (ssh_measure.hip), owned; freed with greens
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
     // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
     // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
@@ -454,6 +455,7 @@ int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec
 void elph_greens_free(elph_handle_s *h);
 void elph_meas_free(elph_handle_s *h);                                      // measure.hip
 void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip
+void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip
 // greens.hip internals used by measure.hip and bondcorr.hip
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;

@@ -141,6 +141,7 @@ size_t spatial_lds_bytes(const elph_handle_s *h, const GreensState *g) { return 
 void elph_greens_free(elph_handle_s *h) {
     elph_meas_free(h);                     // the measurement accumulators are shaped by the estimator
     elph_bond_free(h);
+    elph_i_ssh_meas_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;
     void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};

@@ -23,15 +23,16 @@
 
 #include "corr_req.h"
 #include "elph_internal.h"
+#include "meas_dev.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int NWAVE = TPB / ELPH_WAVE;
+constexpr int TPB = MEAS_TPB;
+constexpr int NWAVE = MEAS_NWAVE;
 constexpr int NCORR = 5;
 const char *const CORR_NAMES[NCORR] = {"Greens", "DenDen", "SpinSpin", "PairGreens", "PhononGreens"};
 const CorrWords WORDS = {"measurements", "orbital", "with no orbital pair"};
-enum { GREENS = 0, DENDEN = 1, SPINSPIN = 2, PAIRGREENS = 3, PHONONGREENS = 4 };
+constexpr int PHONONGREENS = 4;       // 0..3: the folds of meas_dev.h
 constexpr int NONSITE = 9;      // density, double_occ, x, x2, x4, phonon_pe, phonon_ke, elph_energy, mu
 constexpr int NXONLY = 6;       // x, x2, x4, phonon_pe, phonon_ke, mu: functions of the field alone
 
@@ -51,18 +52,6 @@ struct MeasState {
 };
 
 MeasState *ms_of(elph_handle_s *h) { return (MeasState *)h->meas; }
-
-// Sum over the workgroup in a fixed order; the result is valid on thread 0.  red: NWAVE doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int off = ELPH_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, ELPH_WAVE);
-    __syncthreads();                                   // the previous call's readers are done with red
-    if ((threadIdx.x & (ELPH_WAVE - 1)) == 0) red[threadIdx.x / ELPH_WAVE] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < NWAVE; ++w) s += red[w];
-    return s;
-}
 
 // The field-only on-site terms (Measurements.jl:955-970), one workgroup per time slice: part[t][o * NXONLY + k].
 __global__ void __launch_bounds__(TPB) k_ms_x(double *__restrict__ part, const double *__restrict__ x, const double *__restrict__ par, int N,
@@ -193,42 +182,14 @@ __global__ void __launch_bounds__(TPB) k_ms_fold(CorrReq<NCORR> rq, const double
     const int which = blockIdx.y, np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
     const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
     if (idx >= (long long)L0 * nc * np) return;
-    int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc);
+    const int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc);
     const int p = (int)(idx / ((long long)L0 * nc));
-    int o1 = rq.pairs[which][2 * p], o2 = rq.pairs[which][2 * p + 1];
-    const size_t ncol = (size_t)ns * N, tab = (size_t)L * ncol;
-    const bool beta = (tau == L);
+    const int o1 = rq.pairs[which][2 * p], o2 = rq.pairs[which][2 * p + 1];
     double v;
-    if (which == PHONONGREENS) {
-        // x1x2[D] = 1/(L Nc) sum x_o1[. + D] x_o2[.]; slice L is slice 0
-        v = ph[(size_t)(beta ? 0 : tau) * ncol + o1 + ns * (o2 + ns * cell)];
-    } else if (which == SPINSPIN) {
-        if (beta) {                                    // <s(i+r, beta) s(i, 0)> = <s(i-r, 0) s(i, 0)>, orbitals swapped
-            tau = 0;
-            const int l1 = cell % L1, l2 = (cell / L1) % L2, l3 = cell / (L1 * L2);
-            cell = ((L1 - l1) % L1) + L1 * (((L2 - l2) % L2) + L2 * ((L3 - l3) % L3));
-            const int s = o1; o1 = o2; o2 = s;
-        }
-        const size_t e = (size_t)tau * ncol + o2 + ns * (o1 + ns * cell);
-        v = -2 * C[3 * tab + e];
-        if (cell == 0 && o1 == o2 && tau == 0) v += 2 * C[e];
-    } else {
-        const int tm = beta ? 0 : tau;                 // tau % L
-        const size_t e = (size_t)tm * ncol + o2 + ns * (o1 + ns * cell);
-        const bool diag = (cell == 0 && o1 == o2);
-        if (which == GREENS) {
-            v = C[e];
-            if (beta) v = (diag ? 1.0 : 0.0) - v;      // G_r(beta) = delta_r - G_r(0)
-        } else if (which == DENDEN) {
-            const double G00 = C[o1 + ns * o1], Grr = C[o2 + ns * o2];      // tau = 0, r = 0 diagonal entries
-            double h = -C[3 * tab + e];
-            if (diag && tm == 0) h += C[e];
-            v = 4.0 * (1.0 - Grr - G00 + C[2 * tab + e] + 0.5 * h);
-        } else {                                       // PAIRGREENS
-            v = C[tab + e];
-            if (beta && diag) v = v + 1.0 - 2 * C[o1 + ns * o1];            // P_r(beta) = P_r(0) + delta_r (1 - 2 G_0(0))
-        }
-    }
+    if (which == PHONONGREENS)                         // x1x2[D] = 1/(L Nc) sum x_o1[. + D] x_o2[.]; slice L is slice 0
+        v = ph[(size_t)(tau == L ? 0 : tau) * ns * N + o1 + ns * (o2 + ns * cell)];
+    else
+        v = meas_fold(which, C, N, L, ns, L1, L2, L3, tau, cell, o1, o2);
     rq.acc[which][idx] += v;
 }
 

@@ -209,6 +209,7 @@ class SSHModel(AbstractModel):
     def initialize_model_(self, rng=None):
         """SSHModels.jl:348-505.  Disorder widths draw from `rng` (numpy Generator) in the reference's order (:381-411)."""
         tabs, t, alpha, alpha2, omega, omega4, ph2b, names = [], [], [], [], [], [], [], []
+        b2d, b2p = [], []                                                  # 1-based; 0 = a bare bond (:386, :427-431)
         nb_so_far = 0
 
         def spread(mean, std, n, signed):
@@ -223,15 +224,22 @@ class SSHModel(AbstractModel):
             n = new.shape[0]
             tabs.append(new)
             t += spread(d["t"], d.get("t_std", 0.0), n, True)
+            b2d += [len(tabs)] * n
             if d["has_phonon"]:
                 names.append(d.get("name", ""))
+                b2p += list(range((len(names) - 1) * n + 1, len(names) * n + 1))
                 omega += spread(d["omega"], d.get("omega_std", 0.0), n, False)
                 omega4 += spread(d.get("omega4", 0.0), d.get("omega4_std", 0.0), n, False)
                 alpha += spread(d["alpha"], d.get("alpha_std", 0.0), n, True)
                 alpha2 += spread(d["alpha2"], d.get("alpha2_std", 0.0), n, True)
                 ph2b += list(range(nb_so_far + 1, nb_so_far + n + 1))      # 1-based bond of each phonon (:413)
+            else:
+                b2p += [0] * n
             nb_so_far += n
         self.nph = len(names)                                              # number of phonon types
+        self.nbonds = len(self.bond_definitions)                           # number of bond definitions (:351)
+        self.bond_to_definition = np.array(b2d, dtype=np.int64)
+        self.bond_to_phonon = np.array(b2p, dtype=np.int64)
         self.phonon_names = names
         raw = np.concatenate(tabs, axis=0) if tabs else np.zeros((0, 2), dtype=np.int64)
         cb = _lat.initialize_checkerboard(raw)

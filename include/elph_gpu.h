@@ -466,6 +466,49 @@ int elph_bond_fetch(elph_handle h, double *BondBond, double *BondPairGreens);
 /* reset_measurements! (Measurements.jl:698-758) for the two bond correlations: every accumulator to zero (stream-ordered). */
 int elph_bond_reset(elph_handle h);
 
+/* ---------------------------------------------------------------- measurements of the bond-phonon (SSH) model (Measurements.jl) */
+
+/* The device side of initialize_measurements_container(ssh, ...) (Measurements.jl:180-338): accumulators, all doubles on the device, for the
+ * global scalars, the on-site scalars density, double_occ, mu per orbital (:978-1024), the inter-site scalars x, x2, x4, phonon_pe,
+ * phonon_ke, elph_energy, el_ke, sign_switch per bond definition (:1072-1155), the on-site correlations Greens, DenDen, SpinSpin,
+ * PairGreens and the inter-site PhononGreens over phonon types (:2488-2541).  It stands beside elph_meas_create (Holstein handles only)
+ * in a slot of its own.  Needs elph_greens_create first; a new elph_greens_create drops it.
+ *   mu                          double[N] model.mu
+ *   nbonds, ndef                model.Nbonds, model.nbonds; the normalisation of the inter-site scalars is (nbonds / ndef) * L_tau
+ *   bond_sites, bond_t          int64[2 * nbonds] 1-based (s1, s2) = neighbor_table[:, checkerboard_perm[bond]] and double[nbonds] model.t,
+ *                               both in the reference's bond order (the order of model.t)
+ *   bond_to_definition          int64[nbonds] 1-based definition of every bond
+ *   bond_to_phonon              int64[nbonds] 1-based phonon of every bond, 0 on a bare bond
+ *   Nph, nph                    phonons, phonon types; omega, alpha, alpha2: double[Nph] (NULL allowed when Nph = 0)
+ *   measure, time_dependent, npairs   int[5] in the order Greens, DenDen, SpinSpin, PairGreens, PhononGreens
+ *   pairs                       as elph_meas_create; a PhononGreens pair names phonon types 1..nph
+ * ELPH_E_ARG (an orbital outside 1..n_s, a phonon type outside 1..nph, a site, definition or phonon outside its range, a bond count
+ * that is not the handle's) and ELPH_E_UNSUPPORTED (Holstein model, several chains resident, a sharded or slab handle, PhononGreens
+ * requested with Nph != nph * ncells, where the reference's reshape of the field fails) leave the handle without a container and usable. */
+int elph_ssh_meas_create(elph_handle h, const double *mu, double dtau, int64_t nbonds, int ndef, const int64_t *bond_sites,
+                         const double *bond_t, const int64_t *bond_to_definition, const int64_t *bond_to_phonon, int64_t Nph, int nph,
+                         const double *omega, const double *alpha, const double *alpha2, const int *measure, const int *time_dependent,
+                         const int *npairs, const int *pairs);
+
+/* make_measurements! without its update! for the SSH model: x is model.x (L_tau * Nph doubles, host, phonon slowest), from which the
+ * modulated hopping t' = t - (alpha x + sign(x) alpha2 x^2) is recomputed.  Stream-ordered like elph_meas_accumulate; one
+ * synchronisation before it returns; one fixed summation order without atomics: the same inputs give the same bits.  Afterwards
+ * elph_greens_dev_arrays holds the tables of the LAST pair. */
+int elph_ssh_meas_accumulate(elph_handle h, const double *x);
+
+/* The un-normalised sums since the last reset; one device-to-host copy, one synchronisation.  Each pointer may be NULL.
+ *   scalars    double[3 + 3 n_s + 8 ndef]: density, Nsqr, mu; then n_s values each of density, double_occ, mu; then ndef values each of
+ *              x, x2, x4, phonon_pe, phonon_ke, elph_energy, el_ke, sign_switch
+ *   Greens … PhononGreens   as elph_meas_fetch */
+int elph_ssh_meas_fetch(elph_handle h, double *scalars, double *Greens, double *DenDen, double *SpinSpin, double *PairGreens,
+                        double *PhononGreens);
+
+/* reset_measurements! (Measurements.jl:698-758): every accumulator to zero (stream-ordered). */
+int elph_ssh_meas_reset(elph_handle h);
+
+/* Drops the container (elph_greens_create and elph_destroy do so as well). */
+int elph_ssh_meas_free(elph_handle h);
+
 /* ---------------------------------------------------------------- KPM preconditioner */
 
 /* SymmetricKPMPreconditioner(model, n, buf, c1, c2) — KPMPreconditioners.jl:219-235, ctor :101-146 */
