@@ -19,7 +19,8 @@ bond-definition indices: pairs[0, p] is the bond at the origin (n'' of the refer
 
 Scope.  CurrentCurrent with measure = true is refused with UnsupportedMeasurement: the reference's Holstein method scales its fields by
 the hopping inside `for tau in L_tau`, which visits the last time slice alone, and whether to mirror that is undecided.  So are a request
-on a model without bond definitions, the SSH model and several chains resident; sharded and slab handles are refused by the library.
+on a model without bond definitions, the SSH model (ssh_bond_measurements.py measures its BondBond, CurrentCurrent and BondPairGreens)
+and several chains resident; sharded and slab handles are refused by the library.
 """
 from ._lib import P_dbl, check
 from .measurements import (UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _i32, _ip, _process_group,

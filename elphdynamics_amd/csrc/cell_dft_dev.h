@@ -1,5 +1,5 @@
 // cell_dft_dev.h — direct DFTs over the (up to) three cell axes of an array held in LDS, shared by the Green's-function estimator
-// (greens.hip) and the bond correlations (bondcorr.hip).  Spatial extents are the lattice's (8…32): host-built twiddles
+// (greens.hip) and the bond correlations (bondcorr_dev.h).  Spatial extents are the lattice's (8…32): host-built twiddles
 // tw[L1 + L2 + L3] = exp(-2πi j/Lx), exact index reduction.  Workgroups of CELL_DFT_TPB threads.
 #pragma once
 

@@ -1,5 +1,5 @@
-// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2) and
-// ssh_measure.hip (on-site and PhononGreens over phonon types, N = 5):
+// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2),
+// ssh_measure.hip (on-site and PhononGreens over phonon types, N = 5) and ssh_bondcorr.hip (bonds, N = 2, and CurrentCurrent, N = 1):
 // the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group does with its one
 // accumulator allocation [lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's accumulator is
 // [L0][L1][L2][L3][n_p] doubles, first index fastest, L0 = L + 1 (time-dependent, tau = beta included) or 1 (equal-time).

@@ -374,6 +374,7 @@ struct elph_handle_s {
     void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
     void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
     void *ssh_meas = nullptr;              // SshMeasState (ssh_measure.hip), owned; freed with greens
+    void *ssh_bond = nullptr;              // SshBondState (ssh_bondcorr.hip), owned; freed with greens
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
     // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
     // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
@@ -456,7 +457,8 @@ void elph_greens_free(elph_handle_s *h);
 void elph_meas_free(elph_handle_s *h);                                      // measure.hip
 void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip
 void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip
-// greens.hip internals used by measure.hip and bondcorr.hip
+void elph_ssh_bond_free(elph_handle_s *h);                                  // ssh_bondcorr.hip
+// greens.hip internals used by the measurement units
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;
     bool have_vectors;

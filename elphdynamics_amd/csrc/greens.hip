@@ -142,6 +142,7 @@ void elph_greens_free(elph_handle_s *h) {
     elph_meas_free(h);                     // the measurement accumulators are shaped by the estimator
     elph_bond_free(h);
     elph_i_ssh_meas_free(h);
+    elph_ssh_bond_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;
     void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};

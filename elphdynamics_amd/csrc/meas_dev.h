@@ -1,5 +1,5 @@
-// meas_dev.h — the device code the two measurement units share (measure.hip: Holstein, ssh_measure.hip: bond phonons): the workgroup
-// sum in its one fixed order, and the folds of the estimator's four real tables into Greens, DenDen, SpinSpin and PairGreens
+// meas_dev.h — the device code the measurement units share (measure.hip: Holstein, ssh_measure.hip and ssh_bondcorr.hip: bond phonons):
+// the workgroup sum in its one fixed order, the modulated hopping of a bond phonon, and the folds of the estimator's four real tables into Greens, DenDen, SpinSpin and PairGreens
 // (Measurements.jl:1469-1596), which do not depend on the model.  Layouts: header of measure.hip.
 #pragma once
 
@@ -21,6 +21,13 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
     if (threadIdx.x == 0)
         for (int w = 0; w < MEAS_NWAVE; ++w) s += red[w];
     return s;
+}
+
+__device__ __forceinline__ int sign_of(double v) { return (v > 0.0) - (v < 0.0); }          // Julia's sign: sign(0) = 0
+
+// the modulated hopping t' = t - (alpha x + sign(x) alpha2 x^2) of a bond phonon (SSHModels.jl:531-533)
+__device__ __forceinline__ double t_modulated(double t, double alpha, double alpha2, double x) {
+    return t - (alpha * x + sign_of(x) * alpha2 * (x * x));
 }
 
 // measure_<which>(l = cell, o1, o2, tau) of one pair of vectors (o1, o2 0-based, tau <= L).  C: the estimator's four real tables

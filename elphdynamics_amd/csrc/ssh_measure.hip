@@ -74,12 +74,6 @@ SshMeasState *sm_of(elph_handle_s *h) { return (SshMeasState *)h->ssh_meas; }
 
 size_t ph_lds_bytes(int nc) { return 4 * (size_t)nc * sizeof(double2); }
 
-__device__ __forceinline__ int sign_of(double v) { return (v > 0.0) - (v < 0.0); }          // Julia's sign: sign(0) = 0
-
-__device__ __forceinline__ double t_modulated(double t, double alpha, double alpha2, double x) {
-    return t - (alpha * x + sign_of(x) * alpha2 * (x * x));
-}
-
 // The field-only terms (Measurements.jl:1127-1147), one workgroup per time slice: part[t][d * NXONLY + k].
 __global__ void __launch_bounds__(TPB) k_sm_x(double *__restrict__ part, const double *__restrict__ x, const double *__restrict__ bpar,
                                               const int *__restrict__ bph, const int *__restrict__ doff, const int *__restrict__ dlist, int Nph,

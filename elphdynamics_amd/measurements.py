@@ -20,7 +20,8 @@ susceptibility's are (L1, L2, L3, n_p).
 Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
 BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, the SSH model, several chains resident in the handle;
 sharded and slab handles are refused by the library.  BondBond, BondPairGreens and BondPairSusc live in a container of their own beside
-this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent is measured nowhere.
+this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent is measured for the SSH model
+alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.
 
 One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
 The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,

@@ -1,0 +1,137 @@
+"""Host-side mirror of the inter-site correlation group of Measurements.jl for the bond-phonon (SSH) model: BondBond, CurrentCurrent,
+BondPairGreens and the susceptibility BondPairSusc (:295-302, :322), accumulated on the device (csrc/ssh_bondcorr.hip) with the
+reference's per-bin processing and files.  It stands beside ssh_measurements.py as bond_measurements.py stands beside measurements.py.
+
+    c = initialize_ssh_bond_container(model, info, datafolder)       init_corr_container! / init_susc_container!, :295-302, :322, :767-819
+    initialize_ssh_bond_folders_(c)                                  the inter-site parts of :420-540
+    accumulate_ssh_bonds_(c, model, Gr)                              measure_BondBond! (:1663-1785), measure_CurrentCurrent!(ssh) (:2100-2384),
+                                                                     measure_BondPairGreens! (:2390-2483)
+    fetch_ssh_bonds_(c, model)
+    process_ssh_bond_measurements_(c, bin_size, model)               the inter-site parts of :574-676, BondPairSusc :666-672
+    write_ssh_bond_measurements_(c, model, bin)                      :681-693
+    reset_ssh_bond_measurements_(c, model)                           :698-758
+
+It is used next to an SSHMeasurementsContainer (whose constructor keeps refusing the three names) on the same model and estimator, in
+either order.  `info` is the same `[measurements]` table; the bond definitions are model.bond_definitions (what assign_hopping_
+recorded), pairs default to all n_def^2.  The constructor makes no library call; the device side (elph_ssh_bond_create) is made by the
+first accumulate_ssh_bonds_.  Arrays as in bond_measurements.py: pairs[0, p] is the bond at the origin (n'' of the reference),
+pairs[1, p] the displaced one (n').  CurrentCurrent has no susceptibility.
+
+measure_CurrentCurrent! is mirrored as it executes, which differs from its comments in three places.  The fourth of its eight terms is
+subtracted (:2231) under a comment that says `J +=`.  The sixth term averages the field of n'' against the field of n', in that order
+(:2256-2260), unlike the other seven.  The b == c delta term reads M^-1 r1[:, b] (:2340) where its comment names a.
+Where the reference throws: the b == c term indexes with r'' unreduced (:2336-2348), a BoundsError for a negative or >= L displacement;
+here r'' is reduced mod L.  The reshape of t' to (Ltau, L1, L2, L3, n_def) (:2145) throws unless Nbonds = n_def * ncells; the library
+refuses a CurrentCurrent request there (ELPH_E_UNSUPPORTED naming both counts), BondBond and BondPairGreens stay available.
+
+Scope.  Refused with UnsupportedMeasurement naming the request: a Holstein model (bond_measurements.py measures it), several chains
+resident, a request on a model without bond definitions; sharded and slab handles are refused by the library.
+"""
+import numpy as np
+
+from ._lib import P_dbl, check, dptr, iptr
+from .measurements import (INTERSITE_CORR, UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _i32, _ip,  # noqa: F401
+                           _process_group, _refuse_chains, _request_arrays, _requested, _susc_group, _write_groups, _zero_groups, simpson)
+
+SSH_BOND_CORR = INTERSITE_CORR                                 # BondBond, CurrentCurrent, BondPairGreens: elph_ssh_bond_create's request order
+SSH_BOND_SUSC_OF = (("BondPairSusc", "BondPairGreens"),)       # :322
+SUBJECT = "SSH bond correlations"
+
+
+class SSHBondContainer:
+    def __init__(self):
+        self.intersite_corr, self.intersite_susc = {}, {}
+        self.bond_definitions = []
+        self.n_rand_vecs = 1
+        self.datafolder = ""
+        self._device_of = None           # the model whose handle holds the device side
+
+
+def _refuse_model(model):
+    if getattr(model, "kind", None) != 1:
+        raise UnsupportedMeasurement("%s of the Holstein model are not supported (SSH only; see bond_measurements.py)" % SUBJECT)
+    _refuse_chains(model, SUBJECT)
+
+
+def initialize_ssh_bond_container(model, info, datafolder):
+    """The BondBond, CurrentCurrent, BondPairGreens and BondPairSusc part of initialize_measurements_container(ssh, info, datafolder)
+    (:295-302, :322)."""
+    _refuse_model(model)
+    info = info or {}
+    defs = [(int(d["o1"]), int(d["o2"]), tuple(int(k) for k in d["v"])) for d in getattr(model, "bond_definitions", [])]
+    dims = (model.lattice.L1, model.lattice.L2, model.lattice.L3)
+    c = SSHBondContainer()
+    c.n_rand_vecs = int(info.get("num_random_vectors", 1))                  # :189-193
+    c.datafolder = datafolder
+    c.bond_definitions = defs
+    if not defs and _requested(info, SSH_BOND_CORR):
+        raise UnsupportedMeasurement("[measurements.%s] measure = true: the model has no bond definitions (none recorded by assign_hopping_)"
+                                     % _requested(info, SSH_BOND_CORR)[0])
+    c.intersite_corr = _corr_group(info, SSH_BOND_CORR, len(defs), model.Ltau, dims)
+    c.intersite_susc = _susc_group(c.intersite_corr, SSH_BOND_SUSC_OF, dims)
+    return c
+
+
+def initialize_ssh_bond_folders_(container):
+    """The inter-site parts of initialize_measurement_folders!(container) (:420-540)."""
+    _group_folders(container.datafolder, container.intersite_corr, container.intersite_susc, "bond1", "bond2")
+
+
+def _ensure_device(container, model, Gr):
+    if container._device_of is model:
+        return
+    _refuse_model(model)
+    _check_estimator(container, model, Gr)
+    defs = container.bond_definitions
+    o1, o2 = _i32([d[0] for d in defs] or [0]), _i32([d[1] for d in defs] or [0])
+    v = _i32([k for d in defs for k in d[2]] or [0, 0, 0])
+    request = _request_arrays(container.intersite_corr, SSH_BOND_CORR)
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+    i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)  # noqa: E731
+    nb, nph_tot = int(model.Nbonds), int(model.Nph)
+    t, b2d, b2p = f64(model.t), i64(model.bond_to_definition), i64(model.bond_to_phonon)
+    al, al2 = f64(model.alpha), f64(model.alpha2)
+    check(model._lib.elph_ssh_bond_create(model._h, len(defs), _ip(o1), _ip(o2), _ip(v), nb, dptr(t) if nb else None, iptr(b2d) if nb else None,
+                                          iptr(b2p) if nb else None, nph_tot, dptr(al) if nph_tot else None, dptr(al2) if nph_tot else None,
+                                          *map(_ip, request)))
+    container._device_of = model
+
+
+def accumulate_ssh_bonds_(container, model, Gr):
+    """measure_BondBond!, measure_CurrentCurrent! and measure_BondPairGreens! for every pair i < j of the estimator's vectors (the loop of
+    make_measurements!, :550-560), folded into the device's accumulators; nothing comes back to the host."""
+    _refuse_model(model)
+    if not container.intersite_corr:                                        # nothing requested: nothing to set up or fold
+        return
+    _ensure_device(container, model, Gr)
+    check(model._lib.elph_ssh_bond_accumulate(model._h, dptr(np.ascontiguousarray(model.x, dtype=np.float64))))
+    Gr.n1, Gr.n2 = Gr.nv - 1, Gr.nv                                         # the estimator's device tables are the last pair's now
+
+
+def fetch_ssh_bonds_(container, model):
+    """The device's un-normalised sums into the container's position arrays; the momentum arrays are not touched."""
+    if container._device_of is not model:
+        raise RuntimeError("no SSH bond correlation has been measured on this model yet")
+    corr = container.intersite_corr
+    ptrs = [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in SSH_BOND_CORR]
+    check(model._lib.elph_ssh_bond_fetch(model._h, *ptrs))
+
+
+def process_ssh_bond_measurements_(container, bin_size, model):
+    """The inter-site parts of process_measurements!(container, sim_params, model) (:574-676): fetch, momentum = fft over the cell axes,
+    division by bin_size * binomial(n_rand_vecs, 2), Simpson's rule over tau for BondPairSusc (:666-672)."""
+    fetch_ssh_bonds_(container, model)
+    _process_group(container.intersite_corr, container.intersite_susc, SSH_BOND_SUSC_OF, _bin_volume(container, bin_size), model.dtau)
+
+
+def write_ssh_bond_measurements_(container, model, bin):
+    """The inter-site correlations and susceptibilities of write_measurements!(container, model, bin) (:681-693, :1258-1274)."""
+    _write_groups(container.datafolder, bin, container.intersite_corr, container.intersite_susc)
+
+
+def reset_ssh_bond_measurements_(container, model):
+    """reset_measurements!(container, model) (:698-758) for the three correlations: the container's arrays and the device's accumulators
+    to zero."""
+    _zero_groups(container.intersite_corr, container.intersite_susc)
+    if container._device_of is model and model is not None and getattr(model, "_h", None):
+        check(model._lib.elph_ssh_bond_reset(model._h))

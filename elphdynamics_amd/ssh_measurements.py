@@ -20,7 +20,8 @@ inter-site PhononGreens over pairs of phonon types 1..nph (:2488-2541; all nph^2
 Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
 BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, a Holstein model, several chains resident in the
 handle; sharded and slab handles, and PhononGreens on a lattice where Nph != nph * ncells (the reference's reshape of the field
-throws), are refused by the library.
+throws), are refused by the library.  BondBond, CurrentCurrent, BondPairGreens and BondPairSusc live in a container of their own beside
+this one (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), used on the same model and estimator.
 
 Line order in the scalar files (the reference's is the unspecified order of a Julia Dict), extending the one of measurements.py:
 density, Nsqr, mu / density, double_occ, mu / x, x2, x4, phonon_pe, phonon_ke, elph_energy, el_ke, sign_switch.
@@ -65,7 +66,8 @@ def initialize_ssh_measurements_container(model, info, datafolder):
     for name in INTERSITE_CORR:
         if info.get(name, {}).get("measure", False) is True:
             what = name + (" (and BondPairSusc)" if name == "BondPairGreens" else "")
-            raise UnsupportedMeasurement("[measurements.%s] measure = true: the inter-site correlation %s of the SSH model is not supported" % (name, what))
+            raise UnsupportedMeasurement("[measurements.%s] measure = true: the inter-site correlation %s of the SSH model is not supported by this container; "
+                                         "ssh_bond_measurements.initialize_ssh_bond_container measures it" % (name, what))
     for key, val in info.get("Snapshots", {}).items():
         if val is True:
             raise UnsupportedMeasurement("[measurements.Snapshots] %s = true: snapshots are not supported" % key)

@@ -509,6 +509,41 @@ int elph_ssh_meas_reset(elph_handle h);
 /* Drops the container (elph_greens_create and elph_destroy do so as well). */
 int elph_ssh_meas_free(elph_handle h);
 
+/* ---------------------------------------------------------------- inter-site correlations of the bond-phonon (SSH) model */
+
+/* The device side of the SSH container's BondBond, CurrentCurrent and BondPairGreens (init_corr_container! over ssh.nbonds bond
+ * definitions, Measurements.jl:295-302): accumulators, all doubles on the device, in a slot of their own beside elph_ssh_meas_create.
+ * BondBond (measure_BondBond!, :1663-1785) and BondPairGreens (measure_BondPairGreens!, :2390-2483) are the AbstractModel methods
+ * elph_bond_create measures on a Holstein handle; CurrentCurrent is measure_CurrentCurrent!(..., model::SSHModel, ...) (:2100-2384).
+ * Needs elph_greens_create first; a new elph_greens_create drops it.
+ *   n_def, o1, o2, v            model.bond_definitions, as elph_bond_create
+ *   Nbonds, t                   model.Nbonds, double[Nbonds] model.t in the reference's bond order (CurrentCurrent only; bond
+ *                               cell + ncells * (definition - 1) is the reference's reshape of t' to (L_tau, L1, L2, L3, n_def))
+ *   bond_to_definition, bond_to_phonon   int64[Nbonds] 1-based, 0 = a bare bond, as elph_ssh_meas_create (CurrentCurrent only)
+ *   Nph, alpha, alpha2          phonons; double[Nph] (CurrentCurrent only; NULL allowed when Nph = 0)
+ *   measure, time_dependent, npairs   int[3] in the order BondBond, CurrentCurrent, BondPairGreens
+ *   pairs                       as elph_bond_create: the measured ones' lists one after the other in that order
+ * ELPH_E_ARG (an orbital outside 1..n_s, a bond index outside 1..n_def, a definition or phonon outside its range, a bond count that is
+ * not the handle's) and ELPH_E_UNSUPPORTED (Holstein model, several chains resident, a sharded or slab handle, a lattice whose frequency
+ * slice does not fit the LDS, CurrentCurrent requested with Nbonds != n_def * ncells, where the reference's reshape of t' fails; BondBond
+ * and BondPairGreens stay available there) leave the handle without these accumulators and usable. */
+int elph_ssh_bond_create(elph_handle h, int n_def, const int *o1, const int *o2, const int *v, int64_t Nbonds, const double *t,
+                         const int64_t *bond_to_definition, const int64_t *bond_to_phonon, int64_t Nph, const double *alpha,
+                         const double *alpha2, const int *measure, const int *time_dependent, const int *npairs, const int *pairs);
+
+/* The calls to measure_BondBond! / measure_CurrentCurrent! / measure_BondPairGreens! of make_intersite_measurements! for every pair
+ * i < j of the estimator's n_v vectors (ELPH_E_STATE without vectors).  x is model.x (L_tau * Nph doubles, host, phonon slowest), from
+ * which CurrentCurrent recomputes t' = t - (alpha x + sign(x) alpha2 x^2); it may be NULL when CurrentCurrent is not requested.
+ * Stream-ordered like elph_bond_accumulate; one synchronisation before it returns; no atomics and one fixed summation order: the same
+ * inputs give the same bits.  Afterwards elph_greens_dev_arrays holds the tables of the LAST pair. */
+int elph_ssh_bond_accumulate(elph_handle h, const double *x);
+
+/* The un-normalised sums since the last reset, as elph_bond_fetch.  Each pointer may be NULL; unmeasured ones are left untouched. */
+int elph_ssh_bond_fetch(elph_handle h, double *BondBond, double *CurrentCurrent, double *BondPairGreens);
+
+/* reset_measurements! (Measurements.jl:698-758) for the three correlations: every accumulator to zero (stream-ordered). */
+int elph_ssh_bond_reset(elph_handle h);
+
 /* ---------------------------------------------------------------- KPM preconditioner */
 
 /* SymmetricKPMPreconditioner(model, n, buf, c1, c2) — KPMPreconditioners.jl:219-235, ctor :101-146 */
