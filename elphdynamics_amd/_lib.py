@@ -149,6 +149,8 @@ BENCH_SIGNATURES = {
     "elph_bench_lattice_shape": (c_int, [c_int, c_i64, c_i64, P_i64, P_dbl, P_dbl, P_int]),
     "elph_bench_kpm_plan": (c_int, [c_i64, c_dbl, c_dbl, c_dbl, c_int, c_int, P_dbl, P_int, P_int, P_dbl, P_int, P_int, P_int, P_dbl,
                                     P_dbl, P_dbl, c_i64, P_i64]),
+    "elph_bench_hess_max_real": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl]),
+    "elph_bench_kpm_bounds": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_int]),
 }
 
 # the slots of elph_bench_lattice_shape's vector, in order (elph_bench.h)
@@ -189,6 +191,31 @@ def kpm_plan(ltau, bounds, buf=0.05, c1=1.0, c2=1.0):
     return dict(uploaded=up.astype(bool).tolist(), active=act.astype(bool).tolist(), lam_lo=lam[:, 0], lam_hi=lam[:, 1], lam_avg=lam[:, 2],
                 lam_mag=lam[:, 3], order=order, wsched=wsched, coff=coff, c0=c0[..., 0] + 1j * c0[..., 1], fold=fold,
                 coeff=coeff[0::2] + 1j * coeff[1::2])
+
+
+def hess_max_real(mats, where=0, handle=None):
+    """The largest real part of the eigenvalues of each upper-Hessenberg matrix of `mats` (all n x n) by the library's QR iteration: the host's
+    (where = 0, needs no device) or the device's (where = 1, needs a handle); +inf where it did not converge."""
+    lib = load()
+    mats = [np.asarray(a, dtype=np.float64) for a in mats]
+    n = mats[0].shape[0]
+    assert all(a.shape == (n, n) for a in mats)
+    A = np.ascontiguousarray(np.stack([a.T for a in mats]))          # column-major
+    out = np.zeros(len(mats))
+    check(lib.elph_bench_hess_max_real(handle, int(where), len(mats), n, dptr(A), dptr(out)))
+    return out
+
+
+def kpm_bounds(handle, nchains, b_max, b_min, where):
+    """The raw Arnoldi bounds of the resident chains (elph_bench_kpm_bounds): ((nchains, 2) array of (e_min, e_max), ran_on_device).
+    where: 0 host, 1 device (host where the kernel refuses), 2 as setup!(P) chooses."""
+    lib = load()
+    b_max, b_min = np.ascontiguousarray(b_max, dtype=np.float64), np.ascontiguousarray(b_min, dtype=np.float64)
+    assert b_max.shape[0] == nchains and b_max.shape == b_min.shape
+    e = np.zeros((nchains, 2))
+    ran = c_int(-1)
+    check(lib.elph_bench_kpm_bounds(handle, int(where), dptr(b_max), dptr(b_min), dptr(e), C.byref(ran)))
+    return e, ran.value
 
 
 class ElphError(RuntimeError):

@@ -1610,45 +1610,72 @@ static int kpm_update_A(elph_handle_s *h, const KpmSource &src) {
     return ELPH_OK;
 }
 
+// The Arnoldi bounds of every chain the caller does not skip, on the device (kpm_dev.hip: all chains in one launch; eb[2c] = e_min and
+// eb[2c+1] = e_max).  ELPH_E_UNSUPPORTED where the kernel refuses the shape: eb is untouched and the caller takes the host path.
+static int kpm_bounds_device(elph_handle_s *h, const double *b_max, const double *b_min, const std::vector<char> &skip, std::vector<double> &eb) {
+    KpmState &K = h->kpm;
+    const int N = (int)h->N, nch = K.nch();
+    const size_t nst = (size_t)2 * nch * N;
+    if (!K.d_start) RC(dev_alloc(&K.d_start, (size_t)K.tab_cap * (2 * N + 2)));
+    HIPCHK(hipMemcpyAsync(K.d_start, b_max, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(K.d_start + (size_t)nch * N, b_min, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
+    RC(elph_kpm_bounds_dev(h, nch, K.d_start, K.d_start + nst));
+    std::vector<double> dev((size_t)2 * nch);
+    HIPCHK(hipMemcpyAsync(dev.data(), K.d_start + nst, sizeof(double) * 2 * (size_t)nch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < nch; ++c)
+        if (!skip[(size_t)c]) { eb[2 * (size_t)c] = dev[2 * (size_t)c]; eb[2 * (size_t)c + 1] = dev[2 * (size_t)c + 1]; }
+    return ELPH_OK;
+}
+
+// The same on the host (kpm_host.cpp), chain by chain: needs Ē (and the averaged hoppings) on the host
+static int kpm_bounds_host(elph_handle_s *h, const double *b_max, const double *b_min, const std::vector<char> &skip, std::vector<double> &eb) {
+    KpmState &K = h->kpm;
+    const int N = (int)h->N, nch = K.nch();
+    HIPCHK(hipMemcpy(K.h_Ebar.data(), K.d_Ebar, sizeof(double) * (size_t)nch * N, hipMemcpyDeviceToHost));
+    for (int c = 0; c < nch; ++c)
+        if (!skip[(size_t)c]) (void)elph_kpm_arnoldi(h, c, b_max + (size_t)c * N, b_min + (size_t)c * N, &eb[2 * (size_t)c], &eb[2 * (size_t)c + 1]);
+    return ELPH_OK;
+}
+
+// Whether setup!(P) asks the device for its bounds: three chains and more on a lattice of one wave, or as ELPH_KPM_HOST / ELPH_KPM_DEVICE pin it
+// (one or two chains: the host's scalar Arnoldi + LAPACK-style QR, 0.1 ms per chain, beats a kernel whose one wave spends
+//  ~0.25 ms on the same sequential work; from three chains on all of them run side by side on the device)
+static bool kpm_bounds_on_device(const elph_handle_s *h) {
+    const char *eh = getenv("ELPH_KPM_HOST"), *ed = getenv("ELPH_KPM_DEVICE");     // read per call: tests pin one path
+    const bool host_only = eh && eh[0] == '1', dev_always = ed && ed[0] == '1';
+    return !host_only && h->N <= 512 && (h->kpm.nch() >= 3 || dev_always);
+}
+
+// The Arnoldi bounds of the chains not skipped, on the device when the caller asks for it and the kernel takes the shape, else on the host;
+// *ran_on_device says which
+static int kpm_bounds_arnoldi(elph_handle_s *h, bool device, const double *b_max, const double *b_min, const std::vector<char> &skip,
+                              std::vector<double> &eb, int *ran_on_device) {
+    if (ran_on_device) *ran_on_device = 0;
+    if (device) {
+        const int rcd = kpm_bounds_device(h, b_max, b_min, skip, eb);
+        if (rcd == ELPH_OK && ran_on_device) *ran_on_device = 1;
+        if (rcd != ELPH_E_UNSUPPORTED) return rcd;
+    }
+    return kpm_bounds_host(h, b_max, b_min, skip, eb);
+}
+
 // The eigenvalue bounds of every chain (:272-273), eb[2c] = e_min and eb[2c+1] = e_max: injected, or the Arnoldi process with the caller's
 // start vectors — on the device for all chains at once (kpm_dev.hip: one wavefront per chain and per operator, Ritz values by a
 // wave-parallel Hessenberg QR), on the host for lattices beyond one wave
 static int kpm_bounds(elph_handle_s *h, const double *b_max, const double *b_min, const double *e_min, const double *e_max,
                       std::vector<double> &eb) {
-    KpmState &K = h->kpm;
-    const int N = (int)h->N, nch = K.nch();
-    auto injected = [&](int c) { return e_min && e_max && std::isfinite(e_min[c]) && std::isfinite(e_max[c]); };
+    const int nch = h->kpm.nch();
+    std::vector<char> injected((size_t)nch, 0);
     eb.assign((size_t)2 * nch, NAN);
     bool need_arnoldi = false;
-    for (int c = 0; c < nch; ++c)
-        if (injected(c)) { eb[2 * (size_t)c] = e_min[c]; eb[2 * (size_t)c + 1] = e_max[c]; } else need_arnoldi = true;
+    for (int c = 0; c < nch; ++c) {
+        injected[(size_t)c] = e_min && e_max && std::isfinite(e_min[c]) && std::isfinite(e_max[c]);
+        if (injected[(size_t)c]) { eb[2 * (size_t)c] = e_min[c]; eb[2 * (size_t)c + 1] = e_max[c]; } else need_arnoldi = true;
+    }
     if (!need_arnoldi) return ELPH_OK;
     if (!(b_max && b_min)) { elph_set_error("Arnoldi start vectors required when bounds are not injected"); return ELPH_E_ARG; }
-    const char *eh = getenv("ELPH_KPM_HOST"), *ed = getenv("ELPH_KPM_DEVICE");     // read per call: tests pin one path
-    const bool host_only = eh && eh[0] == '1', dev_always = ed && ed[0] == '1';
-    // (one or two chains: the host's scalar Arnoldi + LAPACK-style QR, 0.1 ms per chain, beats a kernel whose one wave spends
-    //  ~0.25 ms on the same sequential work; from three chains on all of them run side by side on the device)
-    if (!host_only && N <= 512 && (nch >= 3 || dev_always)) {
-        const size_t nst = (size_t)2 * nch * N;
-        if (!K.d_start) RC(dev_alloc(&K.d_start, (size_t)K.tab_cap * (2 * N + 2)));
-        HIPCHK(hipMemcpyAsync(K.d_start, b_max, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(K.d_start + (size_t)nch * N, b_min, sizeof(double) * (size_t)nch * N, hipMemcpyHostToDevice, h->stream));
-        const int rcd = elph_kpm_bounds_dev(h, nch, K.d_start, K.d_start + nst);
-        if (rcd == ELPH_OK) {
-            std::vector<double> dev((size_t)2 * nch);
-            HIPCHK(hipMemcpyAsync(dev.data(), K.d_start + nst, sizeof(double) * 2 * (size_t)nch, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            for (int c = 0; c < nch; ++c)
-                if (!injected(c)) { eb[2 * (size_t)c] = dev[2 * (size_t)c]; eb[2 * (size_t)c + 1] = dev[2 * (size_t)c + 1]; }
-            return ELPH_OK;
-        }
-        if (rcd != ELPH_E_UNSUPPORTED) return rcd;
-    }
-    // the host path needs Ē (and the averaged hoppings) on the host
-    HIPCHK(hipMemcpy(K.h_Ebar.data(), K.d_Ebar, sizeof(double) * (size_t)nch * N, hipMemcpyDeviceToHost));
-    for (int c = 0; c < nch; ++c)
-        if (!injected(c)) (void)elph_kpm_arnoldi(h, c, b_max + (size_t)c * N, b_min + (size_t)c * N, &eb[2 * (size_t)c], &eb[2 * (size_t)c + 1]);
-    return ELPH_OK;
+    return kpm_bounds_arnoldi(h, kpm_bounds_on_device(h), b_max, b_min, injected, eb, nullptr);
 }
 
 // the device copies of the tables
@@ -1688,6 +1715,23 @@ static int kpm_setup_core(elph_handle_s *h, const KpmSource &src, const double *
         if (lam_lo) lam_lo[c] = K.chains[(size_t)c].lam_lo;
         if (lam_hi) lam_hi[c] = K.chains[(size_t)c].lam_hi;
     }
+    return ELPH_OK;
+}
+
+// elph_bench.h: the bounds as kpm_bounds' two branches compute them, with nothing of setup!(P) after them
+extern "C" int elph_bench_kpm_bounds(elph_handle h, int where, const double *b_max, const double *b_min, double *e_out, int *ran_on_device) {
+    CHECK_H(h);
+    KpmState &K = h->kpm;
+    if (!K.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
+    if (!b_max || !b_min || !e_out || where < 0 || where > 2) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    RC(need_model(h));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    RC(kpm_reserve(h, h->nchains));
+    RC(kpm_update_A(h, KpmSource()));
+    const std::vector<char> none((size_t)K.nch(), 0);
+    std::vector<double> eb((size_t)2 * K.nch(), NAN);
+    RC(kpm_bounds_arnoldi(h, where == 1 || (where == 2 && kpm_bounds_on_device(h)), b_max, b_min, none, eb, ran_on_device));
+    std::copy(eb.begin(), eb.end(), e_out);
     return ELPH_OK;
 }
 

@@ -61,6 +61,18 @@ int elph_bench_kpm_plan(int64_t ltau, double buf, double c1, double c2, int nch,
                         int *active, double *lam, int *order, int *coff, int *wsched, double *c0, double *fold, double *coeff,
                         int64_t coeff_cap, int64_t *ncoeff);
 
+/* The Hessenberg QR iteration of the Arnoldi bounds alone: out[k] = the largest real part of the eigenvalues of the k-th of nmat upper-Hessenberg
+ * matrices A ([nmat][n x n], column-major, host memory), +inf where the iteration did not converge.  where = 0: the host's elph_hess_eigvals
+ * (kpm_host.cpp; h may be NULL, needs no device); where = 1: the device's hess_max_real (kpm_dev.hip) as k_kpm_bounds calls it, one wavefront per
+ * matrix, the matrix in LDS — ELPH_E_UNSUPPORTED beyond n = 64. */
+int elph_bench_hess_max_real(elph_handle h, int where, int nmat, int n, const double *A, double *out);
+/* The raw Arnoldi bounds of every resident chain, e_out[nch][2] = (e_min, e_max), as setup!(P) computes them before it plans (no margin, no
+ * acceptance window, no retention): where = 0 the host branch (kpm_host.cpp), 1 the device kernel (kpm_dev.hip) with the host as its fallback where
+ * the kernel refuses the shape, 2 whichever setup!(P) itself would take (chain count, ELPH_KPM_HOST / ELPH_KPM_DEVICE).  *ran_on_device = 1 when
+ * the device kernel produced them.  b_max, b_min: [nch][N] start vectors.  Needs elph_kpm_create and a model update, like elph_kpm_setup_chains;
+ * leaves the planned expansions alone. */
+int elph_bench_kpm_bounds(elph_handle h, int where, const double *b_max, const double *b_min, double *e_out, int *ran_on_device);
+
 /* Whether an un-preconditioned solve of nrhs right-hand sides FROM x = 0 on this handle runs in the slab form (slabs.hip: lattices beyond
  * 320 sites as slabs of rows on the same device, the resident kernel per slab, one launch) and its shape. */
 int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int *sites_per_slab, int *own_sites);

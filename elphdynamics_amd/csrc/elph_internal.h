@@ -633,3 +633,4 @@ int elph_kpm_arnoldi(const elph_handle_s *h, int chain, const double *b_max, con
                      double *e_max);
 int elph_hess_eigvals(std::vector<double> &a, int n, std::vector<double> &wr, std::vector<double> &wi);
 int elph_kpm_bounds_dev(elph_handle_s *h, int nch, const double *d_bstart, double *d_eout);
+int elph_hess_max_real_dev(elph_handle_s *h, int nmat, int n, const double *A, double *out);      // kpm_dev.hip: the device QR iteration alone

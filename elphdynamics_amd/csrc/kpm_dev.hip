@@ -298,7 +298,38 @@ __global__ void __launch_bounds__(WAVE) k_kpm_bounds(double *__restrict__ e_out 
     }
 }
 
+// hess_max_real alone, for elph_bench_hess_max_real: one wave per matrix (column-major n x n, n <= 64), the matrix copied to the wave's LDS
+// as k_kpm_bounds hands it over
+__global__ void __launch_bounds__(WAVE) k_hess_max_real(double *__restrict__ out /*[nmat]*/, const double *__restrict__ A /*[nmat][n*n]*/, int n) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x;
+    const double *a = A + (size_t)blockIdx.x * n * n;
+    for (int i = lane; i < n * n; i += WAVE) lds[i] = a[i];
+    LDS_ORDER();
+    const double best = hess_max_real(lds, n, lane);
+    if (lane == 0) out[blockIdx.x] = best;
+}
+
 }  // namespace kd
+
+// The largest real part of the eigenvalues of nmat upper-Hessenberg matrices (host memory, column-major n x n each) by the device's QR
+// iteration; out[nmat] on the host, +inf where it did not converge.  ELPH_E_UNSUPPORTED beyond n = 64 (one row / column per lane).
+int elph_hess_max_real_dev(elph_handle_s *h, int nmat, int n, const double *A, double *out) {
+    if (n > 64) { elph_set_error("hess_max_real on the device: n = %d > 64", n); return ELPH_E_UNSUPPORTED; }
+    const size_t na = (size_t)nmat * n * n;
+    double *d = nullptr;
+    HIPCHK(hipMalloc(&d, (na + (size_t)nmat) * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d, A, na * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kd::k_hess_max_real, dim3((unsigned)nmat), dim3(WAVE), (size_t)n * n * sizeof(double), h->stream, d + na, d, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + na, (size_t)nmat * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { elph_set_error("k_hess_max_real: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
+    return ELPH_OK;
+}
 
 // Arnoldi bounds of the first nch resident chains on the device.  d_bstart: [2][nch][N] start vectors (b_max then b_min) on the device;
 // d_eout: [nch][2] (e_min, e_max).  Returns ELPH_E_UNSUPPORTED when the lattice is beyond one wave (N > 512): the caller then

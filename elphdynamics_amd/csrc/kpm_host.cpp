@@ -328,6 +328,22 @@ bool elph_kpm_plan(KpmState &K, int L, const double *eb) {
     return changed;
 }
 
+extern "C" int elph_bench_hess_max_real(elph_handle h, int where, int nmat, int n, const double *A, double *out) {
+    if (nmat < 1 || n < 1 || !A || !out || (where != 0 && where != 1)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    if (where == 1) {
+        CHECK_H(h);
+        return elph_hess_max_real_dev(h, nmat, n, A, out);
+    }
+    // the host's QR iteration as max_ritz uses it (needs neither a handle nor a device)
+    std::vector<double> a((size_t)n * n), wr(n), wi(n);
+    for (int k = 0; k < nmat; ++k) {
+        a.assign(A + (size_t)k * n * n, A + (size_t)(k + 1) * n * n);
+        out[k] = INFINITY;
+        if (elph_hess_eigvals(a, n, wr, wi) == 0) out[k] = *std::max_element(wr.begin(), wr.end());
+    }
+    return ELPH_OK;
+}
+
 extern "C" int elph_bench_kpm_plan(int64_t ltau, double buf, double c1, double c2, int nch, int nsteps, const double *e_bounds,
                                    int *uploaded, int *active, double *lam, int *order, int *coff, int *wsched, double *c0, double *fold,
                                    double *coeff, int64_t coeff_cap, int64_t *ncoeff) {

@@ -395,11 +395,11 @@ def test_kpm_vs_oracle(oracle, tag):
     rng = np.random.default_rng(11)
     bmax, bmin = rng.standard_normal(m.Nsites), rng.standard_normal(m.Nsites)
     e_min, e_max = oracle.kpm_setup(oP, b_max=bmax, b_min=bmin)
-    pc.setup_(P, b_max=bmax, b_min=bmin)                       # own Arnoldi (device kernel, kpm_dev.hip), same start vectors
+    pc.setup_(P, b_max=bmax, b_min=bmin)                       # own Arnoldi, same start vectors (one chain: the HOST path, kpm_host.cpp; the device kernel: test_gpu_kpm_bounds.py)
     assert P.active and oP.active == 1
     # The largest Ritz value of a 20-step Krylov space of a 256 x 256 non-normal matrix moves by 2-3e-6 with the summation order of
-    # the Gram-Schmidt dot products alone (sequential vs tree vs BLAS: checked in numpy on this very matrix); the device sums each
-    # dot product as a DPP tree, the oracle sequentially.  The expansion takes the bounds with a 5 % margin (KPMPreconditioners.jl:282-285).
+    # the Gram-Schmidt dot products alone (sequential vs tree vs BLAS: checked in numpy on this very matrix); the device kernel sums each
+    # dot product as a DPP tree, the host path and the oracle sequentially.  The expansion takes the bounds with a 5 % margin (KPMPreconditioners.jl:282-285).
     assert abs(P.lam_lo - oP.lam_lo) < 2e-5 and abs(P.lam_hi - oP.lam_hi) < 2e-5
     # parity of everything downstream: inject the oracle's bounds (parity runs take explicit inputs)
     P = pc.SymmetricKPMPreconditioner(m, 20, 0.05, 1.0, 1.0)
