@@ -86,6 +86,11 @@ SIGNATURES = {
     "elph_meas_accumulate": (c_int, [Handle, P_dbl]),
     "elph_meas_fetch": (c_int, [Handle, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl]),
     "elph_meas_reset": (c_int, [Handle]),
+    "elph_meas_chains_create": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, c_i64, c_int, P_i64, P_dbl, P_int, P_int, P_int, P_int]),
+    "elph_meas_chains_set_mu": (c_int, [Handle, P_dbl]),
+    "elph_meas_chains_accumulate": (c_int, [Handle, P_dbl]),
+    "elph_meas_chains_fetch": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl]),
+    "elph_meas_chains_reset": (c_int, [Handle]),
     "elph_bond_create": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int, P_int, P_int, P_int]),
     "elph_bond_accumulate": (c_int, [Handle]),
     "elph_bond_fetch": (c_int, [Handle, P_dbl, P_dbl]),

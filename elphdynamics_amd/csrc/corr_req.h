@@ -1,4 +1,4 @@
-// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2),
+// corr_req.h — the request for a group of correlation functions, shared by measure.hip and measure_chains.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2),
 // ssh_measure.hip (on-site and PhononGreens over phonon types, N = 5) and ssh_bondcorr.hip (bonds, N = 2, and CurrentCurrent, N = 1):
 // the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group does with its one
 // accumulator allocation [lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's accumulator is
@@ -137,6 +137,29 @@ inline void corr_free(std::initializer_list<void *> ptrs) {
     for (void *p : ptrs) if (p) (void)hipFree(p);
 }
 
+// What elph_meas_create and elph_meas_chains_create check of their parameter arrays and bonds before anything is planned or allocated
+// (prefix: the unit's word in the message); bs comes back as [2][nbonds] 0-based sites.
+inline int corr_check_onsite_params(const elph_handle_s *h, const char *prefix, int nc, const double *omega, const double *omega4, const double *lambda,
+                           const double *mu, double dtau, int64_t nbonds, int ndef, const int64_t *bond_sites, const double *bond_t,
+                           const int *measure, const int *time_dependent, const int *npairs, std::vector<int> &bs) {
+    if (!omega || !omega4 || !lambda || !mu || !measure || !time_dependent || !npairs) { elph_set_error("%s: a null parameter array", prefix); return ELPH_E_ARG; }
+    if (!(dtau > 0.0)) { elph_set_error("%s: dtau = %g", prefix, dtau); return ELPH_E_ARG; }
+    const int N = (int)h->N;
+    if (ndef < 0 || nbonds != (int64_t)ndef * nc || (nbonds > 0 && (!bond_sites || !bond_t))) {
+        elph_set_error("%s: %lld bonds are not %d bond definitions x %d cells (bond = (definition - 1) * ncells + cell)", prefix, (long long)nbonds,
+                       ndef, nc);
+        return ELPH_E_ARG;
+    }
+    bs.assign(2 * (size_t)nbonds, 0);
+    for (int64_t b = 0; b < nbonds; ++b)
+        for (int k = 0; k < 2; ++k) {
+            const int64_t s = bond_sites[2 * b + k];
+            if (s < 1 || s > N) { elph_set_error("%s: bond %lld joins site %lld, outside 1..%d", prefix, (long long)b + 1, (long long)s, N); return ELPH_E_ARG; }
+            bs[(size_t)k * nbonds + b] = (int)(s - 1);
+        }
+    return ELPH_OK;
+}
+
 // ---- the state checks of the groups' entry points
 inline int corr_need(const void *state, const char *create) {
     if (!state) { elph_set_error("%s has not been called", create); return ELPH_E_STATE; }
@@ -152,12 +175,17 @@ inline int corr_refuse_chains(const elph_handle_s *h, const char *prefix) {
 }
 
 // kind: the model the group measures
-inline int corr_refuse_handle(const elph_handle_s *h, const char *prefix, int kind = ELPH_MODEL_HOLSTEIN) {
+inline int corr_refuse_model(const elph_handle_s *h, const char *prefix, int kind = ELPH_MODEL_HOLSTEIN) {
     if (h->kind != kind) {
         if (kind == ELPH_MODEL_HOLSTEIN) elph_set_error("%s: the SSH model is not supported (Holstein only)", prefix);
         else elph_set_error("%s: the Holstein model is not supported (SSH only)", prefix);
         return ELPH_E_UNSUPPORTED;
     }
     if (h->shard || h->is_slab) { elph_set_error("%s: sharded and slab handles are not supported", prefix); return ELPH_E_UNSUPPORTED; }
+    return ELPH_OK;
+}
+
+inline int corr_refuse_handle(const elph_handle_s *h, const char *prefix, int kind = ELPH_MODEL_HOLSTEIN) {
+    RC(corr_refuse_model(h, prefix, kind));
     return corr_refuse_chains(h, prefix);
 }

@@ -372,6 +372,7 @@ struct elph_handle_s {
     void *hmc = nullptr;                   // HmcState (hmc.hip), owned
     void *greens = nullptr;                // GreensState (greens.hip), owned
     void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
+    void *meas_chains = nullptr;           // MeasChainsState (measure_chains.hip), owned; freed with greens
     void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
     void *ssh_meas = nullptr;              // SshMeasState (ssh_measure.hip), owned; freed with greens
     void *ssh_bond = nullptr;              // SshBondState (ssh_bondcorr.hip), owned; freed with greens
@@ -455,6 +456,7 @@ int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const doub
 int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec, double tol_power, int64_t *iters, int *flag);
 void elph_greens_free(elph_handle_s *h);
 void elph_meas_free(elph_handle_s *h);                                      // measure.hip
+void elph_meas_chains_free(elph_handle_s *h);                               // measure_chains.hip
 void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip
 void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip
 void elph_ssh_bond_free(elph_handle_s *h);                                  // ssh_bondcorr.hip
@@ -472,6 +474,17 @@ int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand);     
 struct ElphGreensPair { const double *X1, *X2, *R1, *R2; };
 int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p);
 int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS);
+// the same pipelines for one pair of vectors of every resident chain at once, in scratch the caller owns (measure_chains.hip); sizes in
+// elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N
+struct ElphGreensChainScratch {
+    int nchains;
+    double *f;                 // [8][nchains][ndim] the input fields
+    double2 *nuA, *nuP;        // [2][nchains][Lo2][N] twisted, [6][nchains][Lh][N] plain half spectra
+    double2 *Y;                // [4][nchains][Lh][ncol] per-frequency spatial correlations
+    double *C;                 // [4][nchains][L][ncol] the real tables: table-major, a chain's tables lie nchains L ncol apart
+};
+int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p);      // p: chain 0's vectors; chain c's lie c ndim further
+int elph_i_greens_autocorr_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, double *outS, const double *vS);
 int elph_launch_r2s(elph_handle_s *h, double *dstS, const double *srcR, int nvec, int ncols = 0);
 int elph_launch_s2r(elph_handle_s *h, double *dstR, const double *srcS, int nvec, int ncols = 0);
 int elph_launch_expV(elph_handle_s *h, const double *xR, double dtau, int chain = 0);

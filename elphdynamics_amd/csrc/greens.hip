@@ -68,18 +68,14 @@ __global__ void __launch_bounds__(TPB) k_gr_fields(double *__restrict__ f, const
 
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
-// One workgroup per (frequency k, product c): spatial DFT of the two spectra, outer product over orbitals with
-// fft(b)[-ω,-k] = conj fft(b)[ω,k], inverse spatial DFT.  Y[c][k][s2 + ns*(s1 + ns*cell)].
+// The work of one workgroup on one frequency slice: spatial DFT of the two spectra a, b (N complex numbers each), outer product over
+// orbitals with fft(b)[-ω,-k] = conj fft(b)[ω,k], inverse spatial DFT into y[s2 + ns*(s1 + ns*cell)].
 // LDS: 3 buffers of N complex + 2 of nc complex.
-__global__ void __launch_bounds__(TPB) k_gr_spatial(double2 *__restrict__ Y, const double2 *__restrict__ nuA,
-                                                    const double2 *__restrict__ nuB, int K, int N, int ns, int L1, int L2,
-                                                    int L3, const double2 *__restrict__ tw, double norm,
-                                                    long long conv_stride_in, long long conv_stride_out) {
-    extern __shared__ double2 lds[];
-    const int k = blockIdx.x, c = blockIdx.y, nc = L1 * L2 * L3;
+__device__ __forceinline__ void gr_spatial_slice(double2 *__restrict__ y, const double2 *__restrict__ a, const double2 *__restrict__ b,
+                                                 double2 *lds, int N, int ns, int L1, int L2, int L3, const double2 *__restrict__ tw,
+                                                 double norm) {
+    const int nc = L1 * L2 * L3;
     double2 *A = lds, *B = lds + N, *T = lds + 2 * N, *P = lds + 3 * N, *Q = P + nc;
-    const double2 *a = nuA + (size_t)c * conv_stride_in + (size_t)k * N;
-    const double2 *b = nuB + (size_t)c * conv_stride_in + (size_t)k * N;
     for (int e = threadIdx.x; e < N; e += TPB) A[e] = a[e];
     __syncthreads();
     double2 *Af = dft_cells<false>(A, T, ns, L1, L2, L3, tw);
@@ -87,7 +83,6 @@ __global__ void __launch_bounds__(TPB) k_gr_spatial(double2 *__restrict__ Y, con
     for (int e = threadIdx.x; e < N; e += TPB) B[e] = b[e];
     __syncthreads();
     double2 *Bf = dft_cells<false>(B, free1, ns, L1, L2, L3, tw);
-    double2 *y = Y + (size_t)c * conv_stride_out + (size_t)k * ns * N;
     for (int s1 = 0; s1 < ns; ++s1) {
         for (int s2 = 0; s2 < ns; ++s2) {
             for (int q = threadIdx.x; q < nc; q += TPB) {
@@ -100,6 +95,29 @@ __global__ void __launch_bounds__(TPB) k_gr_spatial(double2 *__restrict__ Y, con
             __syncthreads();
         }
     }
+}
+
+// One workgroup per (frequency k, product c).  Y[c][k][s2 + ns*(s1 + ns*cell)].
+__global__ void __launch_bounds__(TPB) k_gr_spatial(double2 *__restrict__ Y, const double2 *__restrict__ nuA,
+                                                    const double2 *__restrict__ nuB, int K, int N, int ns, int L1, int L2,
+                                                    int L3, const double2 *__restrict__ tw, double norm,
+                                                    long long conv_stride_in, long long conv_stride_out) {
+    extern __shared__ double2 lds[];
+    const int k = blockIdx.x, c = blockIdx.y;
+    const double2 *a = nuA + (size_t)c * conv_stride_in + (size_t)k * N;
+    const double2 *b = nuB + (size_t)c * conv_stride_in + (size_t)k * N;
+    gr_spatial_slice(Y + (size_t)c * conv_stride_out + (size_t)k * ns * N, a, b, lds, N, ns, L1, L2, L3, tw, norm);
+}
+
+// The same for every resident chain at once: one workgroup per (frequency k, product c, chain).  The spectra of a field are
+// [chain][K][N], the fields of a product lie field_stride apart (= nchains K N) and products conv_stride_in apart; Y[c][chain][k][...].
+__global__ void __launch_bounds__(TPB) k_gr_spatial_chains(double2 *__restrict__ Y, const double2 *__restrict__ nuA, long long field_stride,
+                                                           int K, int N, int ns, int L1, int L2, int L3, const double2 *__restrict__ tw,
+                                                           double norm, long long conv_stride_in, long long conv_stride_out) {
+    extern __shared__ double2 lds[];
+    const int k = blockIdx.x, c = blockIdx.y, chain = blockIdx.z;
+    const double2 *a = nuA + (size_t)c * conv_stride_in + ((size_t)chain * K + k) * N;
+    gr_spatial_slice(Y + (size_t)c * conv_stride_out + ((size_t)chain * K + k) * ns * N, a, a + field_stride, lds, N, ns, L1, L2, L3, tw, norm);
 }
 
 // C[c][t][col] (real, Δτ < L) -> out[c][τ + 2L*col] complex for τ < 2L; the second half is sgn(c) times the first.
@@ -140,6 +158,7 @@ size_t spatial_lds_bytes(const elph_handle_s *h, const GreensState *g) { return 
 
 void elph_greens_free(elph_handle_s *h) {
     elph_meas_free(h);                     // the measurement accumulators are shaped by the estimator
+    elph_meas_chains_free(h);
     elph_bond_free(h);
     elph_i_ssh_meas_free(h);
     elph_ssh_bond_free(h);
@@ -188,6 +207,7 @@ extern "C" int elph_greens_create(elph_handle h, int norbits, int L1, int L2, in
     RC(gr_alloc(&g->tw, tw.size()));
     HIPCHK(hipMemcpy(g->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute((const void *)k_gr_spatial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spatial_lds_bytes(h, g)));
+    HIPCHK(hipFuncSetAttribute((const void *)k_gr_spatial_chains, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spatial_lds_bytes(h, g)));
     return ELPH_OK;
 }
 
@@ -332,6 +352,57 @@ int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
     v->ns = g->ns; v->L1 = g->L1; v->L2 = g->L2; v->L3 = g->L3; v->nc = g->nc; v->nv = g->nv;
     v->have_vectors = g->have_vectors;
     v->C = g->C; v->tw = g->tw;
+    return ELPH_OK;
+}
+
+// setup!(estimator, n₁, n₂) for one pair of vectors of EVERY resident chain in one pass: v1, v2 count a chain's vectors (1-based, up to
+// n_v = nv / nchains), vector v of chain c is row (v - 1) nchains + c of R and M⁻¹R, so the inputs of all chains are one contiguous
+// block and the pipeline of elph_i_greens_setup_dev runs with its batch multiplied by nchains.  The scratch is the caller's (S), the
+// result S.C[table][chain][Δτ < L][s₂ + n_s (s₁ + n_s cell)]; the estimator's own scratch and tables are not touched.
+int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p) {
+    RC(need_greens(h));
+    GreensState *g = gs_of(h);
+    const int nch = S.nchains;
+    if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
+    if (nch < 1 || g->nv % nch) { elph_set_error("the estimator's %d vectors are not a multiple of %d chains", g->nv, nch); return ELPH_E_STATE; }
+    const int nvc = g->nv / nch;
+    if (v1 < 1 || v1 > nvc || v2 < 1 || v2 > nvc) { elph_set_error("v1=%d, v2=%d outside 1..%d", v1, v2, nvc); return ELPH_E_ARG; }
+    const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N;
+    const size_t nd = (size_t)h->ndim, blk = (size_t)nch * nd;
+    const long long n = (long long)blk;
+    p->X1 = g->X + (size_t)(v1 - 1) * blk; p->X2 = g->X + (size_t)(v2 - 1) * blk;
+    p->R1 = g->R + (size_t)(v1 - 1) * blk; p->R2 = g->R + (size_t)(v2 - 1) * blk;
+    hipLaunchKernelGGL(k_gr_fields, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, S.f, p->X1, p->X2, p->R1, p->R2, n);
+    RC(elph_launch_check("k_gr_fields(chains)"));
+    RC(elph_dft_fwd_twisted(h, S.nuA, S.f, N, 2 * nch, nullptr));
+    RC(elph_dft_fwd_plain(h, S.nuP, S.f + 2 * blk, N, 6 * nch));
+    const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
+    const size_t shm = spatial_lds_bytes(h, g);
+    const long long ytab = (long long)nch * Lh * ncol;                 // one table's spectra; the twisted one fills nch Lo2 ncol of it
+    hipLaunchKernelGGL(k_gr_spatial_chains, dim3((unsigned)Lo2, 1, (unsigned)nch), dim3(TPB), shm, h->stream, S.Y, S.nuA, (long long)nch * Lo2 * N,
+                       Lo2, N, ns, g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
+    RC(elph_launch_check("k_gr_spatial_chains(twisted)"));
+    hipLaunchKernelGGL(k_gr_spatial_chains, dim3((unsigned)Lh, 3, (unsigned)nch), dim3(TPB), shm, h->stream, S.Y + ytab, S.nuP,
+                       (long long)nch * Lh * N, Lh, N, ns, g->L1, g->L2, g->L3, g->tw, norm, 2LL * nch * Lh * N, ytab);
+    RC(elph_launch_check("k_gr_spatial_chains(plain)"));
+    const size_t ctab = (size_t)nch * L * ncol;
+    RC(elph_dft_inv_twisted(h, S.C, S.Y, ncol, nch, nullptr, nullptr, nullptr, 0));
+    RC(elph_dft_inv_plain(h, S.C + ctab, S.Y + ytab, ncol, 3 * nch));
+    return ELPH_OK;
+}
+
+// elph_i_greens_autocorr_dev for nchains fields at once: vS[chain][ndim] (layout S) -> outS[chain][Δτ][a + n_s (b + n_s Δcell)].  Uses
+// S.nuP and S.Y: call it before, not between, elph_i_greens_setup_chains_dev and what reads S.C.
+int elph_i_greens_autocorr_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, double *outS, const double *vS) {
+    RC(need_greens(h));
+    GreensState *g = gs_of(h);
+    const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N, nch = S.nchains;
+    RC(elph_dft_fwd_plain(h, S.nuP, vS, N, nch));
+    const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
+    hipLaunchKernelGGL(k_gr_spatial_chains, dim3((unsigned)Lh, 1, (unsigned)nch), dim3(TPB), spatial_lds_bytes(h, g), h->stream, S.Y, S.nuP, 0LL, Lh,
+                       N, ns, g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
+    RC(elph_launch_check("k_gr_spatial_chains(autocorrelation)"));
+    RC(elph_dft_inv_plain(h, outS, S.Y, ncol, nch));
     return ELPH_OK;
 }
 

@@ -23,18 +23,16 @@
 
 #include "corr_req.h"
 #include "elph_internal.h"
-#include "meas_dev.h"
+#include "meas_holstein_dev.h"
 
 namespace {
 
 constexpr int TPB = MEAS_TPB;
 constexpr int NWAVE = MEAS_NWAVE;
-constexpr int NCORR = 5;
+constexpr int NCORR = MS_NCORR;
 const char *const CORR_NAMES[NCORR] = {"Greens", "DenDen", "SpinSpin", "PairGreens", "PhononGreens"};
 const CorrWords WORDS = {"measurements", "orbital", "with no orbital pair"};
-constexpr int PHONONGREENS = 4;       // 0..3: the folds of meas_dev.h
-constexpr int NONSITE = 9;      // density, double_occ, x, x2, x4, phonon_pe, phonon_ke, elph_energy, mu
-constexpr int NXONLY = 6;       // x, x2, x4, phonon_pe, phonon_ke, mu: functions of the field alone
+constexpr int PHONONGREENS = MS_PHONONGREENS, NONSITE = MS_NONSITE, NXONLY = MS_NXONLY;      // the kernels' bodies: meas_holstein_dev.h
 
 struct MeasState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, ndef = 0;
@@ -53,144 +51,37 @@ struct MeasState {
 
 MeasState *ms_of(elph_handle_s *h) { return (MeasState *)h->meas; }
 
-// The field-only on-site terms (Measurements.jl:955-970), one workgroup per time slice: part[t][o * NXONLY + k].
+// The field-only on-site terms, one workgroup per time slice: part[t][o * NXONLY + k].
 __global__ void __launch_bounds__(TPB) k_ms_x(double *__restrict__ part, const double *__restrict__ x, const double *__restrict__ par, int N,
                                               int L, int ns, int nc, double dtau) {
     __shared__ double red[NWAVE];
-    const int t = blockIdx.x, tn = (t + 1 == L) ? 0 : t + 1;
-    const double *xt = x + (size_t)t * N, *xn = x + (size_t)tn * N;
-    const double *om = par, *om4 = par + N, *mu = par + 3 * (size_t)N;
-    for (int o = 0; o < ns; ++o) {
-        double a[NXONLY] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int c = threadIdx.x; c < nc; c += TPB) {
-            const int i = c * ns + o;
-            const double xi = xt[i], dx = xn[i] - xi, x2 = xi * xi, x4 = x2 * x2;
-            a[0] += xi;
-            a[1] += x2;
-            a[2] += x4;
-            a[3] += om[i] * om[i] * x2 / 2 + om4[i] * x4;
-            a[4] += 0.5 / dtau - dx * dx / (dtau * dtau) / 2;
-            a[5] += mu[i];
-        }
-        for (int k = 0; k < NXONLY; ++k) {
-            const double s = block_sum(a[k], red);
-            if (threadIdx.x == 0) part[(size_t)t * NXONLY * ns + o * NXONLY + k] = s;
-        }
-    }
+    ms_x_slice(part, x, par, par + N, par + 3 * (size_t)N, N, L, ns, nc, dtau, blockIdx.x, red);
 }
 
-// xs[k][o] = (sum of the slices' partials in slice order) / (Nc L)
 __global__ void __launch_bounds__(TPB) k_ms_x_finish(double *__restrict__ xs, const double *__restrict__ part, int L, int ns, double norm) {
-    const int nq = NXONLY * ns;
-    for (int q = threadIdx.x; q < nq; q += TPB) {
-        double s = 0.0;
-        for (int t = 0; t < L; ++t) s += part[(size_t)t * nq + q];
-        const int o = q / NXONLY, k = q % NXONLY;
-        xs[k * ns + o] = s / norm;
-    }
+    ms_x_finish(xs, part, L, ns, norm);
 }
 
-// The terms of one pair of vectors that need the estimate (Measurements.jl:949-962, :1056-1064, :1287-1288), one workgroup per slice.
-// part[t][q]: q = 3 o + {density, double_occ, elph_energy}; 3 n_s + {dot(M^-1 r1, r1), dot(M^-1 r2, r2)}; 3 n_s + 2 + bond definition.
+// The terms of one pair of vectors that need the estimate, one workgroup per slice.
 __global__ void __launch_bounds__(TPB) k_ms_pair(double *__restrict__ part, const double *__restrict__ X1, const double *__restrict__ X2,
                                                  const double *__restrict__ R1, const double *__restrict__ R2, const double *__restrict__ x,
                                                  const double *__restrict__ lam, const int *__restrict__ bs, const double *__restrict__ bt,
                                                  int N, int ns, int nc, int ndef, long long nbonds) {
     __shared__ double red[NWAVE];
-    const int t = blockIdx.x, nq = 3 * ns + 2 + ndef;
-    const size_t o0 = (size_t)t * N;
-    const double *a1 = X1 + o0, *a2 = X2 + o0, *b1 = R1 + o0, *b2 = R2 + o0, *xt = x + o0;
-    double *out = part + (size_t)t * nq;
-    double d1 = 0.0, d2 = 0.0;
-    for (int o = 0; o < ns; ++o) {
-        double den = 0.0, docc = 0.0, eph = 0.0, g1s = 0.0, g2s = 0.0;
-        for (int c = threadIdx.x; c < nc; c += TPB) {
-            const int i = c * ns + o;
-            const double G1 = a1[i] * b1[i], G2 = a2[i] * b2[i];
-            den += (1.0 - G1) + (1.0 - G2);
-            docc += (1.0 - G1) * (1.0 - G2);
-            eph += lam[i] * xt[i] * (2.0 - G1 - G2);
-            g1s += G1;
-            g2s += G2;
-        }
-        double s = block_sum(den, red);
-        if (threadIdx.x == 0) out[3 * o] = s;
-        s = block_sum(docc, red);
-        if (threadIdx.x == 0) out[3 * o + 1] = s;
-        s = block_sum(eph, red);
-        if (threadIdx.x == 0) out[3 * o + 2] = s;
-        d1 += block_sum(g1s, red);                     // thread 0: orbitals in index order
-        d2 += block_sum(g2s, red);
-    }
-    if (threadIdx.x == 0) { out[3 * ns] = d1; out[3 * ns + 1] = d2; }
-    for (int d = 0; d < ndef; ++d) {
-        double ke = 0.0;
-        for (int c = threadIdx.x; c < nc; c += TPB) {
-            const long long b = (long long)d * nc + c;
-            const int s1 = bs[b], s2 = bs[nbonds + b];
-            // -t h, h = -(G1 + G2 + G3 + G4)
-            ke += bt[b] * (a1[s1] * b1[s2] + a1[s2] * b1[s1] + a2[s1] * b2[s2] + a2[s2] * b2[s1]);
-        }
-        const double s = block_sum(ke, red);
-        if (threadIdx.x == 0) out[3 * ns + 2 + d] = s;
-    }
+    ms_pair_slice(part, X1, X2, R1, R2, x, lam, bs, bt, N, ns, nc, ndef, nbonds, blockIdx.x, red);
 }
 
-// One workgroup: the slices' partials in slice order, the tau = 0 slice of G[D,0] G[0,D] for Nsqr, then every scalar accumulator of
-// this pair.  acc: [density, Nsqr, mu | NONSITE x n_s | ndef].
+// One workgroup: every scalar accumulator of this pair.
 __global__ void __launch_bounds__(TPB) k_ms_finish(double *__restrict__ acc, const double *__restrict__ part, const double *__restrict__ xs,
                                                    const double *__restrict__ C3, int N, int L, int ns, int nc, int ndef, double mu_mean) {
     extern __shared__ double tot[];                    // [nq] + red[NWAVE]
-    const int nq = 3 * ns + 2 + ndef, ncol = ns * N;
-    double *red = tot + nq;
-    for (int q = threadIdx.x; q < nq; q += TPB) {
-        double s = 0.0;
-        for (int t = 0; t < L; ++t) s += part[(size_t)t * nq + q];
-        tot[q] = s;
-    }
-    double g = 0.0;
-    for (int i = threadIdx.x; i < ncol; i += TPB) g += C3[i];
-    const double sumG = block_sum(g, red);             // (its barriers also publish tot)
-    const double norm = (double)nc * (double)L;
-    if (threadIdx.x == 0) {
-        const double Nd = (double)N;
-        const double Tr1 = tot[3 * ns] / L, Tr2 = tot[3 * ns + 1] / L;
-        const double N1 = 2 * (Nd - Tr1), N2 = 2 * (Nd - Tr2);
-        acc[0] += (N1 + N2) / (2 * Nd);
-        acc[1] += N1 * N2 + Tr1 + Tr2 - 2 * (Nd / ns) * sumG;
-        acc[2] += mu_mean;
-    }
-    double *on = acc + 3;
-    for (int o = threadIdx.x; o < ns; o += TPB) {
-        on[0 * ns + o] += tot[3 * o] / norm;
-        on[1 * ns + o] += tot[3 * o + 1] / norm;
-        on[2 * ns + o] += xs[0 * ns + o];
-        on[3 * ns + o] += xs[1 * ns + o];
-        on[4 * ns + o] += xs[2 * ns + o];
-        on[5 * ns + o] += xs[3 * ns + o];
-        on[6 * ns + o] += xs[4 * ns + o];
-        on[7 * ns + o] += tot[3 * o + 2] / norm;
-        on[8 * ns + o] += xs[5 * ns + o];
-    }
-    for (int d = threadIdx.x; d < ndef; d += TPB) acc[3 + NONSITE * ns + d] += tot[3 * ns + 2 + d] / norm;
+    ms_finish(acc, part, xs, C3, N, L, ns, nc, ndef, mu_mean, tot);
 }
 
-// One thread per (tau, cell, listed pair) of correlation blockIdx.y (Measurements.jl:1469-1650).  C: the estimator's four real tables of
-// this pair; ph: the field's translation average.
+// One thread per (tau, cell, listed pair) of correlation blockIdx.y.
 __global__ void __launch_bounds__(TPB) k_ms_fold(CorrReq<NCORR> rq, const double *__restrict__ C, const double *__restrict__ ph, int N, int L, int ns,
                                                  int L1, int L2, int L3) {
-    const int which = blockIdx.y, np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
-    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
-    if (idx >= (long long)L0 * nc * np) return;
-    const int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc);
-    const int p = (int)(idx / ((long long)L0 * nc));
-    const int o1 = rq.pairs[which][2 * p], o2 = rq.pairs[which][2 * p + 1];
-    double v;
-    if (which == PHONONGREENS)                         // x1x2[D] = 1/(L Nc) sum x_o1[. + D] x_o2[.]; slice L is slice 0
-        v = ph[(size_t)(tau == L ? 0 : tau) * ns * N + o1 + ns * (o2 + ns * cell)];
-    else
-        v = meas_fold(which, C, N, L, ns, L1, L2, L3, tau, cell, o1, o2);
-    rq.acc[which][idx] += v;
+    ms_fold(rq, blockIdx.y, (long long)blockIdx.x * TPB + threadIdx.x, C, ph, N, L, ns, L1, L2, L3);
 }
 
 int need_meas(elph_handle_s *h) { return corr_need(h->meas, "elph_meas_create"); }
@@ -213,21 +104,9 @@ extern "C" int elph_meas_create(elph_handle h, const double *omega, const double
     RC(corr_refuse_handle(h, WORDS.prefix));
     ElphGreensView g;
     RC(elph_i_greens_view(h, &g));
-    if (!omega || !omega4 || !lambda || !mu || !measure || !time_dependent || !npairs) { elph_set_error("measurements: a null parameter array"); return ELPH_E_ARG; }
-    if (!(dtau > 0.0)) { elph_set_error("measurements: dtau = %g", dtau); return ELPH_E_ARG; }
     const int N = (int)h->N, L = (int)h->L, ns = g.ns, nc = g.nc;
-    if (ndef < 0 || nbonds != (int64_t)ndef * nc || (nbonds > 0 && (!bond_sites || !bond_t))) {
-        elph_set_error("measurements: %lld bonds are not %d bond definitions x %d cells (bond = (definition - 1) * ncells + cell)", (long long)nbonds,
-                       ndef, nc);
-        return ELPH_E_ARG;
-    }
-    std::vector<int> bs(2 * (size_t)nbonds);
-    for (int64_t b = 0; b < nbonds; ++b)
-        for (int k = 0; k < 2; ++k) {
-            const int64_t s = bond_sites[2 * b + k];
-            if (s < 1 || s > N) { elph_set_error("measurements: bond %lld joins site %lld, outside 1..%d", (long long)b + 1, (long long)s, N); return ELPH_E_ARG; }
-            bs[(size_t)k * nbonds + b] = (int)(s - 1);
-        }
+    std::vector<int> bs;
+    RC(corr_check_onsite_params(h, WORDS.prefix, nc, omega, omega4, lambda, mu, dtau, nbonds, ndef, bond_sites, bond_t, measure, time_dependent, npairs, bs));
     const int nsc = 3 + NONSITE * ns + ndef;
     CorrPlan<NCORR> plan;                              // request bookkeeping before anything is allocated
     RC(corr_plan(plan, WORDS, CORR_NAMES, measure, time_dependent, npairs, pairs, ns, L, nc, (size_t)nsc));

@@ -21,7 +21,9 @@ Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: B
 BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, the SSH model, several chains resident in the handle;
 sharded and slab handles are refused by the library.  BondBond, BondPairGreens and BondPairSusc live in a container of their own beside
 this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent is measured for the SSH model
-alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.
+alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.  Several chains resident in the handle (a lockstep
+run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure_chains.hip): one container per chain, all
+chains in the same launches; the functions here keep refusing them.  The bond correlations and the SSH model over chains stay refused.
 
 One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
 The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,
@@ -111,9 +113,9 @@ def _susc_group(corr_group, table, dims):
             for susc, corr in table if corr in corr_group and corr_group[corr].position.shape[0] > 1}
 
 
-def initialize_measurements_container(model, info, datafolder):
-    """initialize_measurements_container(holstein, info, datafolder) (:27-178)."""
-    _refuse_model(model, "measurements")
+def _new_container(model, info, datafolder):
+    """The container of one configuration for the request `info`, after the caller has decided that the model is measured: the requests
+    neither path measures are refused here."""
     info = info or {}
     for name in INTERSITE_CORR:
         if info.get(name, {}).get("measure", False) is True:
@@ -133,6 +135,12 @@ def initialize_measurements_container(model, info, datafolder):
     c.onsite_corr = _corr_group(info, ONSITE_CORR, no, model.Ltau, dims)
     c.onsite_susc = _susc_group(c.onsite_corr, SUSC_OF, dims)
     return c
+
+
+def initialize_measurements_container(model, info, datafolder):
+    """initialize_measurements_container(holstein, info, datafolder) (:27-178)."""
+    _refuse_model(model, "measurements")
+    return _new_container(model, info, datafolder)
 
 
 def _key_file(path, header, arr, pairs):
@@ -232,21 +240,30 @@ def make_measurements_(container, model, Gr, nmeas, P=None, R=None, rng=None):
     return out
 
 
-def fetch_(container, model):
-    """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
-    if container._device_of is not model:
-        raise RuntimeError("nothing has been measured on this model yet")
+def _fetch_buffers(container):
+    """(scalars, the position arrays' pointers in ONSITE_CORR order) for a *_fetch call into the container."""
     no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
     scal = np.zeros(3 + len(ONSITE_KEYS) * no + nb)
-    ptrs = []
-    for name in ONSITE_CORR:
-        ptrs.append(container.onsite_corr[name].position.ctypes.data_as(type(dptr(scal))) if name in container.onsite_corr else None)
-    check(model._lib.elph_meas_fetch(model._h, dptr(scal), *ptrs))
+    ptrs = [container.onsite_corr[name].position.ctypes.data_as(type(dptr(scal))) if name in container.onsite_corr else None for name in ONSITE_CORR]
+    return scal, ptrs
+
+
+def _store_scalars(container, scal):
+    no = len(container.onsite_meas["density"])
     for i, k in enumerate(GLOBAL_KEYS):
         container.global_meas[k] = complex(scal[i])
     for i, k in enumerate(ONSITE_KEYS):
         container.onsite_meas[k][:] = scal[3 + i * no:3 + (i + 1) * no]
     container.intersite_meas["el_ke"][:] = scal[3 + len(ONSITE_KEYS) * no:]
+
+
+def fetch_(container, model):
+    """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
+    if container._device_of is not model:
+        raise RuntimeError("nothing has been measured on this model yet")
+    scal, ptrs = _fetch_buffers(container)
+    check(model._lib.elph_meas_fetch(model._h, dptr(scal), *ptrs))
+    _store_scalars(container, scal)
 
 
 def simpson(f, dx):
@@ -313,12 +330,17 @@ def measure_susceptibilities_(container, dtau):
     _simpson_group(container.onsite_susc, container.onsite_corr, SUSC_OF, dtau)
 
 
+def _process_fetched(container, bin_size, dtau):
+    """process_measurements! after the fetch: momentum copy, normalisation, susceptibilities."""
+    fourier_transform_correlations_(container.onsite_corr)
+    normalize_(container, bin_size)
+    measure_susceptibilities_(container, dtau)
+
+
 def process_measurements_(container, bin_size, model):
     """process_measurements!(container, sim_params, model) (:574-676); bin_size is sim_params.bin_size."""
     fetch_(container, model)
-    fourier_transform_correlations_(container.onsite_corr)
-    normalize_(container, bin_size)
-    measure_susceptibilities_(container, model.dtau)
+    _process_fetched(container, bin_size, model.dtau)
 
 
 def _write_correlation(arr, name, space, datafolder, bin):
@@ -363,13 +385,17 @@ def write_measurements_(container, model, bin):
     _write_groups(d, bin, container.onsite_corr, container.onsite_susc)
 
 
-def reset_measurements_(container, model):
-    """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
+def _zero_container(container):
     for k in container.global_meas:
         container.global_meas[k] = 0j
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k][:] = 0
     _zero_groups(container.onsite_corr, container.onsite_susc)
+
+
+def reset_measurements_(container, model):
+    """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
+    _zero_container(container)
     if container._device_of is model and model is not None and getattr(model, "_h", None):
         check(model._lib.elph_meas_reset(model._h))

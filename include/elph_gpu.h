@@ -433,6 +433,44 @@ int elph_meas_fetch(elph_handle h, double *scalars, double *Greens, double *DenD
 /* reset_measurements! (Measurements.jl:698-758): every accumulator to zero (stream-ordered). */
 int elph_meas_reset(elph_handle h);
 
+/* ---------------------------------------------------------------- measurements of resident chains (Holstein model; Measurements.jl) */
+
+/* elph_meas_create for every chain resident in the handle (elph_update_model_holstein_chains, elph_hmc_create_chains): one container per
+ * chain (initialize_measurements_container, Measurements.jl:27-178) in one device allocation [chain][scalars | Greens | DenDen | SpinSpin
+ * | PairGreens | PhononGreens], beside (not inside) the container of elph_meas_create, and the scratch in which the estimator's setup!
+ * (GreensFunctions.jl:239-288) runs for one pair of vectors of all chains at once.  The estimator serves the chains with
+ * n_v * nchains vectors, vector v of chain c at index v * nchains + c (0-based).  Arguments as elph_meas_create, except
+ *   nchains   >= 1 and equal to the number of chains resident in the handle (ELPH_E_ARG otherwise, naming both)
+ *   mu        double[nchains * nsites], a row per chain: a tuner per chain moves it (elph_hmc_set_mu_chains); the global mu (:858) and
+ *             the on-site mu (:970) of chain c come from row c
+ * ELPH_E_ARG and ELPH_E_UNSUPPORTED (SSH model, a sharded or slab handle) as elph_meas_create: a refused request allocates nothing and
+ * leaves the handle without this container and usable. */
+int elph_meas_chains_create(elph_handle h, int nchains, const double *omega, const double *omega4, const double *lambda, const double *mu,
+                            double dtau, int64_t nbonds, int ndef, const int64_t *bond_sites, const double *bond_t, const int *measure,
+                            const int *time_dependent, const int *npairs, const int *pairs);
+
+/* The chemical-potential tuners moved the chains' mu (MuFinder.jl:68-107: model.μ .= μ′ between two updates; elph_hmc_set_mu_chains for
+ * the dynamics): mu, double[nchains * nsites], replaces the rows elph_meas_chains_create took, for the global mu (Measurements.jl:858) and
+ * the on-site mu (:970) of the accumulates that follow.  The sums so far are kept. */
+int elph_meas_chains_set_mu(elph_handle h, const double *mu);
+
+/* make_measurements! (Measurements.jl:545-566) without its update!, for every chain: X is double[nchains * ndim], chain c's model.x in
+ * the reference layout at X + c * ndim.  For every pair v1 < v2 of a chain's n_v vectors the device part of setup! and the folds run
+ * once for all chains (the chain is a grid axis: the number of launches does not depend on nchains), stream-ordered, with one
+ * synchronisation before the call returns.  Sums as elph_meas_accumulate: one fixed order, no atomics; chain c's numbers depend on chain
+ * c's inputs alone.  ELPH_E_STATE: the handle no longer holds the number of chains the container was created for (after
+ * elph_update_model_holstein, say), the estimator's vectors are not a multiple of it (the message names both counts), or it holds no
+ * vectors yet. */
+int elph_meas_chains_accumulate(elph_handle h, const double *X);
+
+/* One chain's un-normalised sums since the last reset (process_measurements!, Measurements.jl:574-676, reads them): the outputs of
+ * elph_meas_fetch for chain `chain` (0-based; ELPH_E_ARG outside 0..nchains-1).  One device-to-host copy, one synchronisation. */
+int elph_meas_chains_fetch(elph_handle h, int chain, double *scalars, double *Greens, double *DenDen, double *SpinSpin, double *PairGreens,
+                           double *PhononGreens);
+
+/* reset_measurements! (Measurements.jl:698-758) of every chain: one memset (stream-ordered). */
+int elph_meas_chains_reset(elph_handle h);
+
 /* ---------------------------------------------------------------- bond correlations (Holstein model; Measurements.jl) */
 
 /* The device side of the inter-site correlation group of a measurements container (init_corr_container!, Measurements.jl:156-175,
