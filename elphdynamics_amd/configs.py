@@ -93,8 +93,9 @@ def make_model(tag, tol=1e-5, maxiter=10000, rough=True, device=0, seed=synth.SE
     lattice = lat.Lattice(norb, L1, L2, 1)
     if kind == "holstein":
         m = models.HolsteinModel(lattice, beta, dtau, tol=tol, maxiter=maxiter, device=device)
+        rng = np.random.default_rng(seed + 991)      # ONE generator for all definitions: the hoppings of a cell differ from direction to direction
         for (o1, o2, d) in bonds:
-            m.assign_t_(1.0, o1, o2, d, stddev=t_stddev, rng=np.random.default_rng(seed + 991))   # (t_stddev: hopping disorder, :427-447)
+            m.assign_t_(1.0, o1, o2, d, stddev=t_stddev, rng=rng)   # (t_stddev: hopping disorder, :427-447; nothing is drawn at 0)
         m.assign_omega_(1.0)
         m.assign_lambda_(1.0)
         m.assign_mu_(0.0)

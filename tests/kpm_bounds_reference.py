@@ -36,8 +36,9 @@ def host_model(tag, t_stddev=0.0, seed=synth.SEED_FIELDS):
     lattice = lat.Lattice(norb, L1, L2, 1)
     if kind == "holstein":
         m = _HostHolstein(lattice, beta, dtau)
+        rng = np.random.default_rng(seed + 991)
         for (o1, o2, d) in bonds:
-            m.assign_t_(1.0, o1, o2, d, stddev=t_stddev, rng=np.random.default_rng(seed + 991))
+            m.assign_t_(1.0, o1, o2, d, stddev=t_stddev, rng=rng)
         m.assign_omega_(1.0)
         m.assign_lambda_(1.0)
         m.assign_mu_(0.0)

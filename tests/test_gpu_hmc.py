@@ -58,9 +58,9 @@ def test_hmc_golden_through_the_raw_abi(nb):
         lib.elph_destroy(h)
 
 
-def _pair(oracle, tag, tol, lam2=0.0, seed=0):
+def _pair(oracle, tag, tol, lam2=0.0, seed=0, t_stddev=0.0):
     from elphdynamics_amd import configs, preconditioners as pc, synth
-    m = configs.make_model(tag, tol=tol, maxiter=20000)
+    m = configs.make_model(tag, tol=tol, maxiter=20000, t_stddev=t_stddev)
     m.omega4[:] = 0.02
     if lam2:
         m.lam2[:] = lam2
@@ -87,8 +87,13 @@ def _oracle_update(oracle, om, m, fa, x, v, dt, nt, nb, alpha, rnd, P=None):
                                        ("q", 1, 2), ("z", 1, 2), ("r", 1, 2),      # the GRID / HGRID forms (L = 10 square, 10 x 10 honeycomb cells, 12 x 6 rectangle)
                                        ("t12", 1, 2), ("h", 1, 2), ("k", 1, 2)])   # the PGRID kernels (12 x 12 triangular, 18 x 18 honeycomb cells, 20 x 20 square)
 def test_hmc_update_vs_oracle(oracle, tag, nb, nt):
+    check_hmc_update_vs_oracle(oracle, tag, nb, nt)
+
+
+def check_hmc_update_vs_oracle(oracle, tag, nb, nt, t_stddev=0.0):
+    """One update of `nt` leapfrog steps on configuration `tag` (hopping disorder `t_stddev`) against the oracle's, same random numbers."""
     from elphdynamics_amd import hmc
-    m, fa, om = _pair(oracle, tag, tol=1e-6, lam2=0.02)
+    m, fa, om = _pair(oracle, tag, tol=1e-6, lam2=0.02, t_stddev=t_stddev)
     dt = 0.05
     H = hmc.HybridMonteCarlo(m, fa, dt, nt * dt, alpha=0.0, Nb=nb)
     assert H.Nt == nt

@@ -117,8 +117,8 @@ def test_short_and_full_recursions(tag, opts, depths):
     m, X, bmax, bmin = make(tag, **opts)
     try:
         if opts:
-            # the hoppings really differ: make_model seeds every bond direction's draws alike, so each direction has Nsites distinct ones
-            assert len(set(np.round(m.cosht, 12))) == m.Nsites and m.Nbonds == 2 * m.Nsites
+            # the hoppings really differ, from bond to bond and from direction to direction: make_model draws all of them from one generator
+            assert len(set(np.round(m.cosht, 12))) == m.Nbonds == 2 * m.Nsites
         for n in depths:
             if n > 5:       # full depth: rougher fields, on which the reference's own summation orders agree to 3e-6 (chain_fields)
                 from elphdynamics_amd import models

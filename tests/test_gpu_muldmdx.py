@@ -96,9 +96,13 @@ def test_muldMdx_ssh_golden(lib):
 
 @pytest.mark.parametrize("tag", ["b", "B", "C", "D", "d", "g"])
 def test_muldMdx_holstein_vs_oracle(oracle, tag):
+    check_muldMdx_holstein_vs_oracle(oracle, tag)
+
+
+def check_muldMdx_holstein_vs_oracle(oracle, tag, t_stddev=0.0):
     from elphdynamics_amd import configs, models, synth
     from oracle.oracle import dp
-    m = configs.make_model(tag, tol=1e-8)
+    m = configs.make_model(tag, tol=1e-8, t_stddev=t_stddev)
     m.lam2[:] = 0.03 * synth.randn(5, m.Nsites)
     models.update_model_(m)
     E = oracle.update_model_holstein(m.Nsites, m.Ltau, m.dtau, m.x, m.lam, m.lam2, m.mu)

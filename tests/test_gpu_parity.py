@@ -280,8 +280,15 @@ def _oracle_model(orc, m):
 
 @pytest.mark.parametrize("tag", ["A", "b", "d", "t", "u", "e", "B", "C", "D", "E", "T", "g", "G", "h", "s", "q", "Q", "S", "y", "z", "Y", "r", "R", "w", "W", "k", "j", "i", "l30", "h20", "h21", "h24", "t6", "t12", "t20", "t24", "t32", "l22", "l26", "l36", "l34", "l40", "l48", "l64", "h30", "h22", "e8", "e12", "e20", "e24"])      # h30, h22: honeycomb cells on two wavefronts; l36: 4 x 6 patches (round 6); l34 … l64: several wavefronts per slice; l22, l26: square 22 x 22 / 26 x 26 — no register form (2 x 11, 2 x 13), the LDS kernels
 def test_matvec_vs_oracle(oracle, tag):
-    from elphdynamics_amd import configs, models, synth
+    from elphdynamics_amd import configs
     m = configs.make_model(tag)
+    check_matvec_vs_oracle(oracle, m)
+    m.close()
+
+
+def check_matvec_vs_oracle(oracle, m):
+    """The mat-vec family of the model's handle against the oracle's on the same tables and field (the model stays open)."""
+    from elphdynamics_amd import models, synth
     om = _oracle_model(oracle, m)
     v = synth.randn(77, m.Ndim)
     u = synth.randn(78, m.Ndim)
@@ -308,13 +315,20 @@ def test_matvec_vs_oracle(oracle, tag):
     Mu = np.empty(m.Ndim)
     models.mulM_(Mu, m, u)
     assert rel(a, 2.0 * Mv - 3.0 * Mu) < 1e-13                                              # linearity
-    m.close()
 
 
 @pytest.mark.parametrize("tag", ["b", "d", "t", "u", "e", "B", "C", "D", "E", "T", "g", "h", "s", "q", "Q", "S", "y", "z", "Y", "r", "R", "w", "W", "G", "k", "j", "i", "l30", "h20", "h21", "h24", "H18", "t6", "t12", "t24", "t32", "l22", "l26", "l36", "l34", "l40", "l48", "l64", "h30", "h22", "e8", "e12", "e20", "e24"])      # h30, h22: honeycomb cells on two wavefronts; l36: 4 x 6 patches (round 6); l34 … l64: several wavefronts per slice; l22, l26: square 22 x 22 / 26 x 26 — no register form (2 x 11, 2 x 13), the LDS kernels
 def test_cg_vs_oracle(oracle, tag):
-    from elphdynamics_amd import configs, models
+    from elphdynamics_amd import configs
     m = configs.make_model(tag, tol=1e-5)
+    check_cg_vs_oracle(oracle, m)
+    m.close()
+
+
+def check_cg_vs_oracle(oracle, m):
+    """Plain CG on a model made with tol = 1e-5 against the oracle's: production tolerance, then the tight solve (the model stays open,
+    its solver tolerance at 1e-13)."""
+    from elphdynamics_amd import configs, models
     om = _oracle_model(oracle, m)
     R, B = configs.rhs(m, 1)
     b = np.ascontiguousarray(B[0])
@@ -344,7 +358,6 @@ def test_cg_vs_oracle(oracle, tag):
     Mx = np.empty(m.Ndim)
     models.mulM_(Mx, m, x3)
     assert rel(Mx, R[0]) < 1e-8                                                             # x = M^-1 R indeed
-    m.close()
 
 
 @pytest.mark.parametrize("tag", ["b", "C", "T"])
@@ -452,8 +465,15 @@ def test_kpm_with_hopping_disorder_vs_oracle(oracle, tag):
             assert _pg_info(m)[1:4] == (2, 2, 4)        # (disordered 32 x 32, 28 x 28, 30 x 30: 2 x 2 patches on four wavefronts instead of the uniform lattice's one-wavefront shape)
     elif tag in ("l36", "h", "i"):
         assert _pg_info(m)[4] == 0, _pg_info(m)
+    check_kpm_with_injected_bounds_vs_oracle(oracle, m)
+    m.close()
+
+
+def check_kpm_with_injected_bounds_vs_oracle(oracle, m):
+    """Mat-vecs, the KPM apply and the preconditioned CG of a model made with tol = 1e-5 against the oracle, the expansion set up on the
+    oracle's eigenvalue bounds (the model stays open)."""
+    from elphdynamics_amd import configs, models, preconditioners as pc, synth
     om = _oracle_model(oracle, m)
-    from elphdynamics_amd import synth
     v, y = synth.randn(177, m.Ndim), np.empty(m.Ndim)
     for fn, ofn in ((models.mulM_, oracle.mulM), (models.mulMt_, oracle.mulMT), (models.mulMtM_, oracle.mulMTM)):
         fn(y, m, v)
@@ -473,7 +493,6 @@ def test_kpm_with_hopping_disorder_vs_oracle(oracle, tag):
     it, hist = models.solve_(x, m, b, P=P, tol=1e-5, history=True)
     xo, ito, histo = oracle.cg_solve(om, b, tol=1e-5, maxiter=10000, P=oP, history=True)
     assert it == ito and rel(x, xo) < 1e-8
-    m.close()
 
 
 @pytest.mark.parametrize("tag", ["G40", "j", "h20", "l30", "l36"])

@@ -29,11 +29,12 @@ def tables(kind, norb, Ls, bonds_key, dtau, t_stddev):
     if kind == "ssh":
         return la.nsites, lat.initialize_checkerboard(raw)["table"], None, None
     t = []
+    rng = np.random.default_rng(synth.SEED_FIELDS + 991)      # one generator for all bond definitions, as in make_model
     for (o1, o2, d) in bonds:
         n = la.calc_neighbor_table(o1, o2, d).shape[0]
         tn = np.full(n, 1.0)
         if t_stddev:
-            tn = tn + t_stddev * np.random.default_rng(synth.SEED_FIELDS + 991).standard_normal(n)
+            tn = tn + t_stddev * rng.standard_normal(n)
         t.append(tn)
     cb = lat.initialize_checkerboard(raw, np.concatenate(t), dtau)
     return la.nsites, cb["table"], cb["cosht"], cb["sinht"]
