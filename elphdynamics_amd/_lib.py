@@ -95,6 +95,10 @@ SIGNATURES = {
     "elph_bond_accumulate": (c_int, [Handle]),
     "elph_bond_fetch": (c_int, [Handle, P_dbl, P_dbl]),
     "elph_bond_reset": (c_int, [Handle]),
+    "elph_bond_chains_create": (c_int, [Handle, c_int, c_int, P_int, P_int, P_int, P_int, P_int, P_int, P_int]),
+    "elph_bond_chains_accumulate": (c_int, [Handle]),
+    "elph_bond_chains_fetch": (c_int, [Handle, c_int, P_dbl, P_dbl]),
+    "elph_bond_chains_reset": (c_int, [Handle]),
     "elph_ssh_meas_create": (c_int, [Handle, P_dbl, c_dbl, c_i64, c_int, P_i64, P_dbl, P_i64, P_i64, c_i64, c_int, P_dbl, P_dbl, P_dbl, P_int, P_int,
                                      P_int, P_int]),
     "elph_ssh_meas_accumulate": (c_int, [Handle, P_dbl]),

@@ -20,7 +20,8 @@ bond-definition indices: pairs[0, p] is the bond at the origin (n'' of the refer
 Scope.  CurrentCurrent with measure = true is refused with UnsupportedMeasurement: the reference's Holstein method scales its fields by
 the hopping inside `for tau in L_tau`, which visits the last time slice alone, and whether to mirror that is undecided.  So are a request
 on a model without bond definitions, the SSH model (ssh_bond_measurements.py measures its BondBond, CurrentCurrent and BondPairGreens)
-and several chains resident; sharded and slab handles are refused by the library.
+and several chains resident (chain_bond_measurements.py measures every resident chain at once); sharded and slab handles are refused by
+the library.
 """
 from ._lib import P_dbl, check
 from .measurements import (UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _i32, _ip, _process_group,
@@ -42,9 +43,9 @@ class BondContainer:
 SUBJECT = "bond correlations"
 
 
-def initialize_bond_container(model, info, datafolder, bond_definitions=None):
-    """The inter-site group of initialize_measurements_container(holstein, info, datafolder) (:156-175)."""
-    _refuse_model(model, SUBJECT)
+def _new_bond_container(model, info, datafolder, bond_definitions=None):
+    """The container of one configuration for the request `info`, after the caller has decided that the model is measured: the requests
+    neither path measures are refused here."""
     info = info or {}
     if info.get("CurrentCurrent", {}).get("measure", False) is True:
         raise UnsupportedMeasurement("[measurements.CurrentCurrent] measure = true: not supported; the reference's Holstein method scales "
@@ -63,6 +64,12 @@ def initialize_bond_container(model, info, datafolder, bond_definitions=None):
     c.intersite_corr = _corr_group(info, BOND_CORR, len(defs), model.Ltau, dims)
     c.intersite_susc = _susc_group(c.intersite_corr, BOND_SUSC_OF, dims)
     return c
+
+
+def initialize_bond_container(model, info, datafolder, bond_definitions=None):
+    """The inter-site group of initialize_measurements_container(holstein, info, datafolder) (:156-175)."""
+    _refuse_model(model, SUBJECT)
+    return _new_bond_container(model, info, datafolder, bond_definitions)
 
 
 def initialize_bond_folders_(container):
@@ -107,7 +114,11 @@ def process_bond_measurements_(container, bin_size, model):
     """The inter-site parts of process_measurements!(container, sim_params, model) (:574-676): fetch, momentum = fft over the cell axes,
     division by bin_size * binomial(n_rand_vecs, 2), Simpson's rule over tau for BondPairSusc (:666-672)."""
     fetch_bonds_(container, model)
-    _process_group(container.intersite_corr, container.intersite_susc, BOND_SUSC_OF, _bin_volume(container, bin_size), model.dtau)
+    _process_fetched(container, bin_size, model.dtau)
+
+
+def _process_fetched(container, bin_size, dtau):
+    _process_group(container.intersite_corr, container.intersite_susc, BOND_SUSC_OF, _bin_volume(container, bin_size), dtau)
 
 
 def write_bond_measurements_(container, model, bin):

@@ -23,8 +23,9 @@ The device side is shaped by the estimator and dropped by the library when a new
 sums it held): the next accumulate_ with the new estimator makes it again, with the mu given then (or model.mu).
 
 Scope: what measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the SSH model,
-BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true — the bond correlations and
-the SSH model over chains are not measured.  measurements.py itself keeps refusing resident chains.
+BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true — the SSH model over chains is
+not measured; BondBond, BondPairGreens and BondPairSusc of the chains are chain_bond_measurements.py's, whose container is used beside
+this one on the same model and estimator, in either order.  measurements.py itself keeps refusing resident chains.
 """
 import numpy as np
 

@@ -19,7 +19,8 @@
 // [L0][L1][L2][L3][n_p] first index fastest, L0 = L + 1 (time-dependent, τ = β included) or 1 (equal-time).
 //
 // The kernels, their state and the launches of one pair of vectors are in bondcorr_dev.h, shared with ssh_bondcorr.hip (the same two
-// correlations of the bond-phonon model); this unit holds the Holstein entry points.
+// correlations of the bond-phonon model) and bondcorr_chains.hip (every resident chain of a lockstep run at once); this unit holds the
+// Holstein entry points of one configuration.
 
 #include "bondcorr_dev.h"
 
@@ -52,7 +53,7 @@ extern "C" int elph_bond_create(elph_handle h, int n_def, const int *o1, const i
     CorrPlan<NBOND> plan;                              // request bookkeeping before anything is allocated
     RC(corr_plan(plan, WORDS, BOND_NAMES, measure, time_dependent, npairs, pairs, n_def, (int)h->L, g.nc, 0));
     BondState *m = nullptr;
-    const int rc = bc_make(&m, h, WORDS, g, plan, defs, n_def);
+    const int rc = bc_make(&m, h, WORDS, g, plan, defs, n_def, 1, k_bc_correlate);
     h->bond = m;
     return rc;
 }

@@ -1,8 +1,10 @@
-// bondcorr_dev.h — what the two bond-correlation units share (bondcorr.hip: Holstein, ssh_bondcorr.hip: bond phonons): the kernels of
+// bondcorr_dev.h — what the bond-correlation units share (bondcorr.hip and bondcorr_chains.hip: Holstein, ssh_bondcorr.hip: bond phonons): the
+// kernels of
 //   measure_BondBond!         Measurements.jl:1663-1785
 //   measure_BondPairGreens!   Measurements.jl:2390-2483
 // which read model.bond_definitions and nothing else of the model, their state, and the host steps around them (the definitions'
-// table, create, the launches of one pair of vectors).  One text of each kernel; the formulas and layouts are in bondcorr.hip's header.
+// table, create, the launches of one pair of vectors).  One text of each kernel body, shared with bondcorr_chains.hip (the Holstein
+// correlations of every resident chain at once); the formulas and layouts are in bondcorr.hip's header.
 #pragma once
 
 #include <vector>
@@ -23,13 +25,14 @@ using BondReq = CorrReq<NBOND>;          // pairs (n″, n′)
 
 struct BondState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, ndef = 0;
+    int nchains = 1;                // configurations the buffers serve: 1, or every resident chain (bondcorr_chains.hip)
     int k0 = 0, k1 = 0;             // the fields [k0, k1) are transformed
     int *defs = nullptr;            // [ndef][DEFW]
-    CorrPlan<NBOND> cr;             // the requests; cr.acc: [BondBond | BondPairGreens]
-    double *f = nullptr;            // [NFIELD][ndef][L][nc] the fields of one pair of vectors
-    double2 *nu = nullptr;          // [NFIELD][ndef][Lh][nc] their half spectra, then their cell-axis DFTs in place
-    double2 *Y = nullptr;           // [nP][Lh][nc] per-frequency correlations of the listed pairs, BondBond's first
-    double *B = nullptr;            // [nP][L][nc]
+    CorrPlan<NBOND> cr;             // ONE configuration's plan; cr.acc: [chain][BondBond | BondPairGreens], cr.req bound to chain 0
+    double *f = nullptr;            // [NFIELD][ndef][chain][L][nc] the fields of one pair of vectors
+    double2 *nu = nullptr;          // [NFIELD][ndef][chain][Lh][nc] their half spectra, then their cell-axis DFTs in place
+    double2 *Y = nullptr;           // [nP][chain][Lh][nc] per-frequency correlations of the listed pairs, BondBond's first
+    double *B = nullptr;            // [nP][chain][L][nc]
 };
 
 size_t bc_lds_bytes(int nc) { return 2 * (size_t)nc * sizeof(double2); }
@@ -44,13 +47,18 @@ __device__ __forceinline__ int shifted_cell(int cell, const int *dv, int L1, int
     return cell_plus(cell, dv[2], dv[3], dv[4], L1, L2, L3);
 }
 
-// The six fields of every definition (header of bondcorr.hip), one thread per (cell, τ, definition): gathers inside one time slice of
-// layout S.
-__global__ void __launch_bounds__(BC_TPB) k_bc_fields(double *__restrict__ f, const double *__restrict__ X1, const double *__restrict__ X2,
-                                                      const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs,
-                                                      int N, int L, int ns, int L1, int L2, int L3, int ndef) {
+// ---- what one thread or workgroup does in each kernel, shared by the single-configuration kernels below and the kernels of
+// bondcorr_chains.hip (every resident chain, the chain a grid axis): the two differ only in where a workgroup finds its chain's block.
+// The buffers carry the chain between the definition (or listed pair) and the time axis — f: [NFIELD][ndef][chain][L][nc], nu the same
+// with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc] — so a body takes its chain's block of definition (pair) 0 and the distance
+// between two definitions (pairs); with one configuration that distance is the block itself.
+
+// The six fields of every definition (header of bondcorr.hip) for idx = (cell, τ, definition), first fastest: gathers inside one time
+// slice of layout S.  f: the chain's block of field 0 of definition 0; dstride: doubles between two definitions.
+__device__ __forceinline__ void bc_fields_at(double *__restrict__ f, const double *__restrict__ X1, const double *__restrict__ X2,
+                                             const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs, int N,
+                                             int L, int ns, int L1, int L2, int L3, int ndef, long long idx, size_t dstride) {
     const int nc = L1 * L2 * L3;
-    const long long idx = (long long)blockIdx.x * BC_TPB + threadIdx.x;
     const long long per = (long long)L * nc;
     if (idx >= per * ndef) return;
     const int cell = (int)(idx % nc), t = (int)((idx / nc) % L), n = (int)(idx / per);
@@ -58,7 +66,7 @@ __global__ void __launch_bounds__(BC_TPB) k_bc_fields(double *__restrict__ f, co
     const size_t is = (size_t)t * N + (size_t)cell * ns + dv[0];
     const size_t ie = (size_t)t * N + (size_t)shifted_cell(cell, dv, L1, L2, L3) * ns + dv[1];
     const double x1s = X1[is], x2s = X2[is], r2s = R2[is], x1e = X1[ie], r1e = R1[ie], r2e = R2[ie];
-    const size_t fs = (size_t)ndef * per, o = (size_t)n * per + (size_t)t * nc + cell;
+    const size_t fs = (size_t)ndef * dstride, o = (size_t)n * dstride + (size_t)t * nc + cell;
     f[o] = x1s * r1e;
     f[fs + o] = x2s * r2e;
     f[2 * fs + o] = x1s * r2e;
@@ -67,30 +75,16 @@ __global__ void __launch_bounds__(BC_TPB) k_bc_fields(double *__restrict__ f, co
     f[5 * fs + o] = r1e * r2s;
 }
 
-// One workgroup per (frequency, field): the cell-axis DFT of one frequency slice, in place.  LDS: 2 buffers of nc complex.
-__global__ void __launch_bounds__(BC_TPB) k_bc_spatial_fwd(double2 *__restrict__ nu, int Lh, int L1, int L2, int L3,
-                                                           const double2 *__restrict__ tw) {
-    extern __shared__ double2 lds[];
+// Frequency k of listed pair p (BondBond's pairs first): the product of the spectra (BondBond's two terms combined), inverse cell-axis
+// DFT, into the slice y.  nu: the chain's spectra of field 0 of definition 0; field `kind` of definition n sits (kind * ndef + n) * dstride
+// further on.  lds: 2 buffers of nc complex.
+__device__ __forceinline__ void bc_correlate_slice(double2 *__restrict__ y, const double2 *__restrict__ nu, const BondReq &rq, int p, int k, int ndef,
+                                                   int L1, int L2, int L3, const double2 *__restrict__ tw, double norm, size_t dstride, double2 *lds) {
     const int nc = L1 * L2 * L3;
-    double2 *s = nu + ((size_t)blockIdx.y * Lh + blockIdx.x) * nc;
-    for (int q = threadIdx.x; q < nc; q += BC_TPB) lds[q] = s[q];
-    __syncthreads();
-    const double2 *F = dft_cells<false>(lds, lds + nc, 1, L1, L2, L3, tw);
-    for (int q = threadIdx.x; q < nc; q += BC_TPB) s[q] = F[q];
-}
-
-// One workgroup per (frequency, listed pair): the product of the spectra (BondBond's two terms combined), inverse cell-axis DFT.
-// nu: the spectra of field 0; field k of definition n sits k * ndef + n slices of Lh * nc further on.  LDS: 2 buffers of nc complex.
-__global__ void __launch_bounds__(BC_TPB) k_bc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, BondReq rq, int Lh, int ndef,
-                                                         int L1, int L2, int L3, const double2 *__restrict__ tw, double norm) {
-    extern __shared__ double2 lds[];
-    const int nc = L1 * L2 * L3, k = blockIdx.x;
-    int p = blockIdx.y;
     const int which = (p < rq.np[BONDBOND]) ? BONDBOND : BONDPAIR;
     if (which == BONDPAIR) p -= rq.np[BONDBOND];
     const int n2 = rq.pairs[which][2 * p], n1 = rq.pairs[which][2 * p + 1];       // n″, n′
-    const size_t slice = (size_t)Lh * nc;
-    auto field = [&](int kind, int n) { return nu + ((size_t)kind * ndef + n) * slice + (size_t)k * nc; };
+    auto field = [&](int kind, int n) { return nu + ((size_t)kind * ndef + n) * dstride + (size_t)k * nc; };
     double2 *P = lds, *Q = lds + nc;
     if (which == BONDBOND) {
         const double2 *f0 = field(0, n1), *f1 = field(1, n2), *f2 = field(2, n1), *f3 = field(3, n2);
@@ -108,24 +102,23 @@ __global__ void __launch_bounds__(BC_TPB) k_bc_correlate(double2 *__restrict__ Y
     }
     __syncthreads();
     const double2 *Pf = dft_cells<true>(P, Q, 1, L1, L2, L3, tw);
-    double2 *y = Y + ((size_t)blockIdx.y * Lh + k) * nc;
     for (int q = threadIdx.x; q < nc; q += BC_TPB) y[q] = Pf[q];
 }
 
-// One thread per (τ, cell, listed pair) of correlation blockIdx.y: the δ terms and the τ = β slice (Measurements.jl:1750-1781,
-// :2457-2479).  G0: the τ = 0 slice of the estimator's G[Δ,0] of this pair of vectors, measure_GΔ0(l, o₁, o₂, 0) =
-// G0[(o₂ - 1) + n_s ((o₁ - 1) + n_s cell(l))] (header of measure.hip).
-__global__ void __launch_bounds__(BC_TPB) k_bc_fold(BondReq rq, const double *__restrict__ B, const double *__restrict__ G0,
-                                                    const int *__restrict__ defs, int L, int ns, int L1, int L2, int L3) {
-    const int which = blockIdx.y, np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
-    const long long idx = (long long)blockIdx.x * BC_TPB + threadIdx.x;
+// Element idx = (τ, cell, listed pair) of correlation `which`: the δ terms and the τ = β slice (Measurements.jl:1750-1781, :2457-2479)
+// added to the accumulator at idx + acc_off.  B: the chain's block of listed pair 0, pstride doubles between two pairs.  G0: the τ = 0
+// slice of the estimator's G[Δ,0] of this pair of vectors, measure_GΔ0(l, o₁, o₂, 0) = G0[(o₂ - 1) + n_s ((o₁ - 1) + n_s cell(l))]
+// (header of measure.hip).
+__device__ __forceinline__ void bc_fold_at(const BondReq &rq, int which, long long idx, const double *__restrict__ B, const double *__restrict__ G0,
+                                           const int *__restrict__ defs, int L, int ns, int L1, int L2, int L3, size_t pstride, size_t acc_off) {
+    const int np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
     if (idx >= (long long)L0 * nc * np) return;
     const int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc), p = (int)(idx / ((long long)L0 * nc));
     const int *d2 = defs + rq.pairs[which][2 * p] * DEFW, *d1 = defs + rq.pairs[which][2 * p + 1] * DEFW;
     const int d = d2[0], c = d2[1], b = d1[0], a = d1[1];
     const int l1 = cell % L1, l2 = (cell / L1) % L2, l3 = cell / (L1 * L2);
     const bool beta = (tau == L);
-    const double *Bp = B + ((size_t)(which == BONDPAIR ? rq.np[BONDBOND] : 0) + p) * L * nc;
+    const double *Bp = B + ((size_t)(which == BONDPAIR ? rq.np[BONDBOND] : 0) + p) * pstride;
     double v;
     if (which == BONDBOND) {
         // B(β, r) = B(0, -r) with its δ term
@@ -152,7 +145,43 @@ __global__ void __launch_bounds__(BC_TPB) k_bc_fold(BondReq rq, const double *__
             if (d_ac && d_rl) v -= G0[b + ns * (d + ns * cell)];                   // measure_GΔ0(l, d, b, 0)
         }
     }
-    rq.acc[which][idx] += v;
+    rq.acc[which][acc_off + idx] += v;
+}
+
+// ---- the kernels of one configuration
+
+// One thread per (cell, τ, definition).
+__global__ void __launch_bounds__(BC_TPB) k_bc_fields(double *__restrict__ f, const double *__restrict__ X1, const double *__restrict__ X2,
+                                                      const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs,
+                                                      int N, int L, int ns, int L1, int L2, int L3, int ndef) {
+    bc_fields_at(f, X1, X2, R1, R2, defs, N, L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * BC_TPB + threadIdx.x, (size_t)L * (L1 * L2 * L3));
+}
+
+// One workgroup per (frequency, slice of Lh frequencies): the cell-axis DFT of one frequency slice, in place; a slice is a field of a
+// definition (of a chain: the chain kernels launch it over their longer list of slices as it is).  LDS: 2 buffers of nc complex.
+__global__ void __launch_bounds__(BC_TPB) k_bc_spatial_fwd(double2 *__restrict__ nu, int Lh, int L1, int L2, int L3,
+                                                           const double2 *__restrict__ tw) {
+    extern __shared__ double2 lds[];
+    const int nc = L1 * L2 * L3;
+    double2 *s = nu + ((size_t)blockIdx.y * Lh + blockIdx.x) * nc;
+    for (int q = threadIdx.x; q < nc; q += BC_TPB) lds[q] = s[q];
+    __syncthreads();
+    const double2 *F = dft_cells<false>(lds, lds + nc, 1, L1, L2, L3, tw);
+    for (int q = threadIdx.x; q < nc; q += BC_TPB) s[q] = F[q];
+}
+
+// One workgroup per (frequency, listed pair).  nu: the spectra of field 0.  LDS: 2 buffers of nc complex.
+__global__ void __launch_bounds__(BC_TPB) k_bc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, BondReq rq, int Lh, int ndef,
+                                                         int L1, int L2, int L3, const double2 *__restrict__ tw, double norm) {
+    extern __shared__ double2 lds[];
+    const int nc = L1 * L2 * L3;
+    bc_correlate_slice(Y + ((size_t)blockIdx.y * Lh + blockIdx.x) * nc, nu, rq, blockIdx.y, blockIdx.x, ndef, L1, L2, L3, tw, norm, (size_t)Lh * nc, lds);
+}
+
+// One thread per (τ, cell, listed pair) of correlation blockIdx.y.
+__global__ void __launch_bounds__(BC_TPB) k_bc_fold(BondReq rq, const double *__restrict__ B, const double *__restrict__ G0,
+                                                    const int *__restrict__ defs, int L, int ns, int L1, int L2, int L3) {
+    bc_fold_at(rq, blockIdx.y, (long long)blockIdx.x * BC_TPB + threadIdx.x, B, G0, defs, L, ns, L1, L2, L3, (size_t)L * (L1 * L2 * L3), 0);
 }
 
 // ---- host
@@ -211,21 +240,28 @@ void bc_free(BondState *m) {
     delete m;
 }
 
-// The state of a planned request: allocations, the definitions and pairs on the device, zeroed accumulators.  *out stays null on failure.
+// The state of a planned request for nchains configurations: allocations, the definitions and pairs on the device, zeroed accumulators,
+// the LDS of this unit's k_bc_spatial_fwd and of `correlate`, the unit's kernel of bc_correlate_slice.  *out stays null on failure.
+template <class K>
 int bc_make(BondState **out, elph_handle_s *h, const CorrWords &w, const ElphGreensView &g, const CorrPlan<NBOND> &plan, const std::vector<int> &defs,
-            int n_def) {
+            int n_def, int nchains, K correlate) {
     const int L = (int)h->L, Lh = L / 2 + 1, nc = g.nc;
     BondState *m = new BondState;
     m->cr = plan;
-    m->ns = g.ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = n_def;
+    m->ns = g.ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = n_def; m->nchains = nchains;
     m->k0 = plan.req.np[BONDBOND] ? 0 : 4;
     m->k1 = plan.req.np[BONDPAIR] ? NFIELD : 4;
-    const size_t nP = (size_t)plan.npairs, nf = (size_t)NFIELD * n_def;
+    const size_t nch = (size_t)nchains, nP = nch * plan.npairs, nf = nch * NFIELD * n_def;
     CorrFirstError ok;
-    const bool allocated = ok(corr_alloc(&m->defs, defs.size())) && ok(corr_alloc(m->cr)) && ok(corr_alloc(&m->f, nf * L * nc)) &&
-        ok(corr_alloc(&m->nu, nf * Lh * nc)) && ok(corr_alloc(&m->Y, nP * Lh * nc)) && ok(corr_alloc(&m->B, nP * L * nc));
-    if (allocated && ok(corr_up(m->defs, defs.data(), defs.size() * sizeof(int)))) ok(corr_upload(m->cr, w.prefix));
-    if (ok.rc == ELPH_OK && ok(bc_allow_lds(k_bc_spatial_fwd, w, nc))) ok(bc_allow_lds(k_bc_correlate, w, nc));
+    const bool allocated = ok(corr_alloc(&m->defs, defs.size())) && ok(corr_alloc(&m->cr.pairs, m->cr.prs.size())) &&
+        ok(corr_alloc(&m->cr.acc, nch * m->cr.total)) && ok(corr_alloc(&m->f, nf * L * nc)) && ok(corr_alloc(&m->nu, nf * Lh * nc)) &&
+        ok(corr_alloc(&m->Y, nP * Lh * nc)) && ok(corr_alloc(&m->B, nP * L * nc));
+    if (allocated && ok(corr_up(m->defs, defs.data(), defs.size() * sizeof(int)))) ok(corr_upload(m->cr, w.prefix));   // zeroes chain 0's block
+    if (ok.rc == ELPH_OK && nchains > 1 && hipMemset(m->cr.acc, 0, nch * m->cr.total * sizeof(double)) != hipSuccess) {
+        elph_set_error("%s: hipMemset failed", w.prefix);
+        ok(ELPH_E_HIP);
+    }
+    if (ok.rc == ELPH_OK && ok(bc_allow_lds(k_bc_spatial_fwd, w, nc))) ok(bc_allow_lds(correlate, w, nc));
     if (ok.rc != ELPH_OK) { bc_free(m); return ok.rc; }
     *out = m;
     return ELPH_OK;

@@ -374,6 +374,7 @@ struct elph_handle_s {
     void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
     void *meas_chains = nullptr;           // MeasChainsState (measure_chains.hip), owned; freed with greens
     void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
+    void *bond_chains = nullptr;           // BondChainsState (bondcorr_chains.hip), owned; freed with greens
     void *ssh_meas = nullptr;              // SshMeasState (ssh_measure.hip), owned; freed with greens
     void *ssh_bond = nullptr;              // SshBondState (ssh_bondcorr.hip), owned; freed with greens
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
@@ -458,6 +459,7 @@ void elph_greens_free(elph_handle_s *h);
 void elph_meas_free(elph_handle_s *h);                                      // measure.hip
 void elph_meas_chains_free(elph_handle_s *h);                               // measure_chains.hip
 void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip
+void elph_bond_chains_free(elph_handle_s *h);                               // bondcorr_chains.hip
 void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip
 void elph_ssh_bond_free(elph_handle_s *h);                                  // ssh_bondcorr.hip
 // greens.hip internals used by the measurement units
@@ -474,8 +476,8 @@ int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand);     
 struct ElphGreensPair { const double *X1, *X2, *R1, *R2; };
 int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p);
 int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS);
-// the same pipelines for one pair of vectors of every resident chain at once, in scratch the caller owns (measure_chains.hip); sizes in
-// elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N
+// the same pipelines for one pair of vectors of every resident chain at once, in scratch the caller owns (measure_chains.hip,
+// bondcorr_chains.hip); sizes in elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N
 struct ElphGreensChainScratch {
     int nchains;
     double *f;                 // [8][nchains][ndim] the input fields
@@ -483,6 +485,9 @@ struct ElphGreensChainScratch {
     double2 *Y;                // [4][nchains][Lh][ncol] per-frequency spatial correlations
     double *C;                 // [4][nchains][L][ncol] the real tables: table-major, a chain's tables lie nchains L ncol apart
 };
+// the five buffers sized by the estimator's shape for nchains chains (S zero-initialised; on failure what was allocated is freed) / freed
+int elph_i_greens_chain_scratch_alloc(elph_handle_s *h, int nchains, ElphGreensChainScratch *S);
+void elph_i_greens_chain_scratch_free(ElphGreensChainScratch *S);
 int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p);      // p: chain 0's vectors; chain c's lie c ndim further
 int elph_i_greens_autocorr_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, double *outS, const double *vS);
 int elph_launch_r2s(elph_handle_s *h, double *dstS, const double *srcR, int nvec, int ncols = 0);

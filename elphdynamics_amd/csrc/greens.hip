@@ -160,6 +160,7 @@ void elph_greens_free(elph_handle_s *h) {
     elph_meas_free(h);                     // the measurement accumulators are shaped by the estimator
     elph_meas_chains_free(h);
     elph_bond_free(h);
+    elph_bond_chains_free(h);
     elph_i_ssh_meas_free(h);
     elph_ssh_bond_free(h);
     GreensState *g = gs_of(h);
@@ -353,6 +354,28 @@ int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
     v->have_vectors = g->have_vectors;
     v->C = g->C; v->tw = g->tw;
     return ELPH_OK;
+}
+
+// The scratch of the two chain pipelines below for nchains chains, sized by the estimator's shape (sizes: elph_internal.h).
+int elph_i_greens_chain_scratch_alloc(elph_handle_s *h, int nchains, ElphGreensChainScratch *S) {
+    RC(need_greens(h));
+    const GreensState *g = gs_of(h);
+    const size_t nch = (size_t)nchains, nd = (size_t)h->ndim, N = (size_t)h->N, L = (size_t)h->L, Lo2 = (L + 1) / 2, Lh = L / 2 + 1, ncol = (size_t)g->ns * N;
+    S->nchains = nchains;
+    int rc = gr_alloc(&S->f, 8 * nch * nd);
+    if (rc == ELPH_OK) rc = gr_alloc(&S->nuA, 2 * nch * Lo2 * N);
+    if (rc == ELPH_OK) rc = gr_alloc(&S->nuP, 6 * nch * Lh * N);
+    if (rc == ELPH_OK) rc = gr_alloc(&S->Y, 4 * nch * Lh * ncol);
+    if (rc == ELPH_OK) rc = gr_alloc(&S->C, 4 * nch * L * ncol);
+    if (rc != ELPH_OK) elph_i_greens_chain_scratch_free(S);
+    return rc;
+}
+
+void elph_i_greens_chain_scratch_free(ElphGreensChainScratch *S) {
+    void *ptrs[] = {S->f, S->nuA, S->nuP, S->Y, S->C};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    S->f = S->C = nullptr;
+    S->nuA = S->nuP = S->Y = nullptr;
 }
 
 // setup!(estimator, n₁, n₂) for one pair of vectors of EVERY resident chain in one pass: v1, v2 count a chain's vectors (1-based, up to

@@ -109,7 +109,8 @@ int need_state(elph_handle_s *h) { return corr_need(h->meas_chains, "elph_meas_c
 void elph_meas_chains_free(elph_handle_s *h) {
     MeasChainsState *m = mc_of(h);
     if (!m) return;
-    corr_free({m->par, m->mu, m->bs, m->bt, m->cr.pairs, m->cr.acc, m->xr, m->x, m->ph, m->xs, m->part, m->gs.f, m->gs.nuA, m->gs.nuP, m->gs.Y, m->gs.C});
+    corr_free({m->par, m->mu, m->bs, m->bt, m->cr.pairs, m->cr.acc, m->xr, m->x, m->ph, m->xs, m->part});
+    elph_i_greens_chain_scratch_free(&m->gs);
     delete m;
     h->meas_chains = nullptr;
 }
@@ -137,15 +138,13 @@ extern "C" int elph_meas_chains_create(elph_handle h, int nchains, const double 
     m->cr = plan;
     m->nchains = nchains; m->ns = ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = ndef; m->nbonds = nbonds; m->dtau = dtau; m->nsc = nsc;
     m->nqmax = std::max(3 * ns + 2 + ndef, MS_NXONLY * ns);
-    const size_t nch = (size_t)nchains, nd = (size_t)h->ndim, Lo2 = ((size_t)L + 1) / 2, Lh = (size_t)L / 2 + 1, ncol = (size_t)ns * N;
+    const size_t nch = (size_t)nchains, nd = (size_t)h->ndim, ncol = (size_t)ns * N;
     const bool phonon = m->cr.req.np[MS_PHONONGREENS] != 0;
-    m->gs.nchains = nchains;
     CorrFirstError ok;
     const bool allocated = ok(corr_alloc(&m->par, 3 * (size_t)N)) && ok(corr_alloc(&m->mu, nch * N + nch)) && ok(corr_alloc(&m->bs, 2 * (size_t)nbonds)) &&
         ok(corr_alloc(&m->bt, (size_t)nbonds)) && ok(corr_alloc(&m->cr.pairs, m->cr.prs.size())) && ok(corr_alloc(&m->cr.acc, nch * m->cr.total)) &&
         ok(corr_alloc(&m->xr, nch * nd)) && ok(corr_alloc(&m->x, nch * nd)) && ok(corr_alloc(&m->xs, nch * MS_NXONLY * ns)) && ok(corr_alloc(&m->part, nch * L * m->nqmax)) &&
-        (!phonon || ok(corr_alloc(&m->ph, nch * L * ncol))) && ok(corr_alloc(&m->gs.f, 8 * nch * nd)) && ok(corr_alloc(&m->gs.nuA, 2 * nch * Lo2 * N)) &&
-        ok(corr_alloc(&m->gs.nuP, 6 * nch * Lh * N)) && ok(corr_alloc(&m->gs.Y, 4 * nch * Lh * ncol)) && ok(corr_alloc(&m->gs.C, 4 * nch * L * ncol));
+        (!phonon || ok(corr_alloc(&m->ph, nch * L * ncol))) && ok(elph_i_greens_chain_scratch_alloc(h, nchains, &m->gs));
     if (!allocated) { elph_meas_chains_free(h); return ok.rc; }
     const double *pp[3] = {omega, omega4, lambda};
     for (int k = 0; k < 3; ++k) ok(corr_up(m->par + (size_t)k * N, pp[k], (size_t)N * sizeof(double)));

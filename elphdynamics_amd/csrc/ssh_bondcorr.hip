@@ -327,7 +327,7 @@ extern "C" int elph_ssh_bond_create(elph_handle h, int n_def, const int *o1, con
     m->ns = g.ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = n_def; m->Nph = Nph;
     m->cr = cplan;
     CorrFirstError ok;
-    if (bplan.npairs) ok(bc_make(&m->bond, h, WORDS, g, bplan, defs, n_def));
+    if (bplan.npairs) ok(bc_make(&m->bond, h, WORDS, g, bplan, defs, n_def, 1, k_bc_correlate));
     if (ok.rc == ELPH_OK && np) {
         const size_t nf = (size_t)NCC * n_def;
         const bool allocated = ok(corr_alloc(m->cr)) && ok(corr_alloc(&m->defs, defs.size())) && ok(corr_alloc(&m->bph, nb)) &&

@@ -504,6 +504,48 @@ int elph_bond_fetch(elph_handle h, double *BondBond, double *BondPairGreens);
 /* reset_measurements! (Measurements.jl:698-758) for the two bond correlations: every accumulator to zero (stream-ordered). */
 int elph_bond_reset(elph_handle h);
 
+/* ---------------------------------------------------------------- bond correlations of resident chains (Holstein model; Measurements.jl) */
+
+/* elph_bond_create for every chain resident in the handle (elph_update_model_holstein_chains, elph_hmc_create_chains): the accumulators of
+ * BondBond (measure_BondBond!, Measurements.jl:1663-1785) and BondPairGreens (measure_BondPairGreens!, :2390-2483) of every chain in one
+ * device allocation [chain][BondBond | BondPairGreens], the buffers of one pair of vectors of all chains, and the scratch in which the
+ * estimator's setup! (GreensFunctions.jl:239-288) runs for one pair of vectors of all chains at once.  It stands beside the containers of
+ * elph_bond_create and elph_meas_chains_create in a slot of its own.  Needs elph_greens_create first; a new elph_greens_create drops it.
+ * The estimator serves the chains with n_v * nchains vectors, vector v of chain c at index v * nchains + c (0-based).  Arguments as
+ * elph_bond_create, and
+ *   nchains   >= 1 and equal to the number of chains resident in the handle
+ * Checked in this order, before anything is allocated; a refused request leaves the handle without this container and usable:
+ *   ELPH_E_UNSUPPORTED   the SSH model; a sharded or slab handle
+ *   ELPH_E_ARG           nchains < 1 or not the resident number (the message names both)
+ *   ELPH_E_STATE         elph_greens_create has not been called
+ *   ELPH_E_ARG           n_def < 1 or a null array; an orbital outside 1..n_s (naming the definition); a measured correlation without
+ *                        pairs, or a bond index outside 1..n_def (naming the correlation, the pair and the index)
+ *   ELPH_E_UNSUPPORTED   a lattice whose frequency slice does not fit the LDS; a request whose grids would exceed 65535 in y or z:
+ *                        (fields transformed: 4 for BondBond + 2 for BondPairGreens) * n_def * nchains slices, or (listed pairs of both
+ *                        correlations) * nchains transforms (the message says which product)
+ *   ELPH_E_HIP           an allocation failed */
+int elph_bond_chains_create(elph_handle h, int nchains, int n_def, const int *o1, const int *o2, const int *v, const int *measure,
+                            const int *time_dependent, const int *npairs, const int *pairs);
+
+/* measure_BondBond! / measure_BondPairGreens! (Measurements.jl:1663-1785, :2390-2483) for every pair v1 < v2 of a chain's n_v vectors, of
+ * every chain: per pair the device part of setup! (for G[D,0] of the delta terms), the fields, their transforms, one inverse transform per
+ * listed pair and the fold run once for all chains (the chain is a grid axis: the number of launches does not depend on nchains),
+ * stream-ordered, with one synchronisation before the call returns.  The correlations read the vectors and neither the field nor mu: no
+ * X.  Sums as elph_bond_accumulate: every element one thread's sum in index order, no atomics; chain c's numbers depend on chain c's
+ * vectors alone.  The estimator's own tables (elph_greens_dev_arrays) are not touched.  With no pair requested nothing is launched.
+ *   ELPH_E_STATE   elph_bond_chains_create has not been called; the handle no longer holds the number of chains the container was created
+ *                  for (after elph_update_model_holstein, say); the estimator's vectors are not a multiple of it (the message names both
+ *                  counts); the estimator holds no vectors yet */
+int elph_bond_chains_accumulate(elph_handle h);
+
+/* One chain's un-normalised sums since the last reset: the outputs of elph_bond_fetch for chain `chain` (0-based).  One device-to-host
+ * copy, one synchronisation.  ELPH_E_STATE: not created; ELPH_E_ARG: a chain outside 0..nchains-1. */
+int elph_bond_chains_fetch(elph_handle h, int chain, double *BondBond, double *BondPairGreens);
+
+/* reset_measurements! (Measurements.jl:698-758) for the bond correlations of every chain: one memset (stream-ordered).  ELPH_E_STATE: not
+ * created. */
+int elph_bond_chains_reset(elph_handle h);
+
 /* ---------------------------------------------------------------- measurements of the bond-phonon (SSH) model (Measurements.jl) */
 
 /* The device side of initialize_measurements_container(ssh, ...) (Measurements.jl:180-338): accumulators, all doubles on the device, for the
