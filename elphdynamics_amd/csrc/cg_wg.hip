@@ -18,6 +18,16 @@
 // bit-identical across the team and from run to run.  (A sharded solve, SHARD, meets on two levels: the workgroups of a rank, then
 // the ranks through their mailboxes.)
 //
+// Behind the meeting (un-sharded solves, FUSED in the kernel): everything that decides — alpha, r'.r', the stop test, beta — follows from
+// the four sums, so it is made FIRST; then ONE pass over the own slices makes r' = r - alpha z (stored to LDS for the neighbouring waves),
+// x += alpha p and p = r' + beta p from the r' it still holds in a register; then the barrier that releases the neighbours' r', and the
+// two halo slices of p.  The square-lattice DPP forms add their four sums per batch of reverse sweeps.  Every fma keeps its operands and
+// every sum its order: the bits of a solve are those of the order this replaces (update, barrier, stop test, p-update from LDS), which
+// the sharded solves and the one-slice shapes keep (one slice per wave: measured 1.3 % slower with the pass than without).
+// (Built, measured and left out: the forward sweeps of the slabs 1 .. T — they read the wave's own slices of p only — BEFORE that barrier,
+// the loop rotated by them.  4-slice shape 1.0 % over the old order against 2.2 % without the rotation, 2 slices 0.3 against 2.4 %, one
+// slice 4 % slower: profiles/wg_fused_tail/.)
+//
 // Placement: team members are blocks with equal blockIdx % 8 (they share an XCD and its L2 under the observed round-robin
 // placement — speed only, never correctness).  The grid may hold more teams than the chip can keep resident: blocks are
 // dispatched in index order, a team's members have neighbouring indices, so at most the eight teams at the dispatch
@@ -351,8 +361,21 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         wg_barrier();                                   // bc[0] is rewritten by the first meeting of the loop
     }
     // screens of the stop test (see there)
-    const double rr_far = (P.tol * normb) * (P.tol * normb) * 1.000001, y_num = 4.0 * (eps0 * normb) * (eps0 * normb);
-    const double it_kappa = 0.17 * sqrt(P.kmax);
+    double rr_far = (P.tol * normb) * (P.tol * normb) * 1.000001, y_num = 4.0 * (eps0 * normb) * (eps0 * normb);
+    double it_kappa = 0.17 * sqrt(P.kmax);
+    // FUSED (un-sharded solves of two and more slices per wave): the tail of an iteration decides first — alpha, r'.r', the stop test and beta follow from the
+    // meeting's four sums alone — and then makes ONE pass over the own slices: r' = r - alpha z (to LDS for the neighbours), x += alpha p and
+    // p = r' + beta p from the r' it holds in a register.  (The order it replaces — update, barrier, stop test, p-update — read every
+    // r' back from LDS behind the barrier.)
+    // One slice per wave keeps the old order (config C, 2 right-hand sides: 3.40 us per iteration against 3.44 with the pass).
+    // BSUM (the square-lattice DPP forms): the four sums are added behind each batch of reverse sweeps.
+    constexpr bool FUSED = !SHARD && T >= 2, BSUM = SQ;
+    // (alpha, beta and the screens of the stop test carry the same bits in every lane: FUSED keeps them in scalar registers — the pass holds
+    //  alpha AND beta, and the 4-slice shape has no vector register to spare)
+    auto uni = [](double v) __attribute__((always_inline)) {
+        return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+    };
+    if constexpr (FUSED) { rr_far = uni(rr_far); y_num = uni(y_num); it_kappa = uni(it_kappa); normb = uni(normb); eps0 = uni(eps0); }
     STAMP_DECL;
     for (long long seq = 0;; ++seq) {
         const unsigned epoch = R.epoch0 + (unsigned)seq + (SHARD ? 2u : 1u);
@@ -367,6 +390,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         //      z(t) = w(t) - sg(t+1) E(t+1) CB_{t+1}^T w(t+1)  for t = t0 .. t0+T-1  (T reverse sweeps at once)
         // (w and z share registers: z(t0+j) overwrites w(t0+j) once the reverse sweep of w(t0+j+1) has been taken)
         double (&w)[T + 1][NPL] = zw;
+        double b_pz = 0.0, b_rz = 0.0, b_zz = 0.0, b_rr = 0.0;   // BSUM: the four sums of the meeting (see there), summed behind the reverse batches
         if constexpr (S8) {
 #pragma unroll
             for (int k = 0; k <= T; ++k) w[k][0] = EXPV(k, 0) * p[k][0];
@@ -497,6 +521,21 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
 #pragma unroll
                     for (int q = 0; q < 4; ++q) w[j0 + i][q] = w[j0 + i][q] - sg * (EXPV(j0 + i + 1, q) * gq[i][q]);    // z(t0+j0+i)
                 }
+                // the four sums over the slices of this batch, in the (j, q) order of the single loop of the other forms: with two batches
+                // the first batch's share overlaps the cross-lane latency of the second batch's sweeps
+                if constexpr (BSUM) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (own[q]) {
+                            const double rv = rl[(j0 + i) * HSL + lr + q * LSL];
+                            b_pz += p[j0 + i + 1][q] * w[j0 + i][q];
+                            b_rz += rv * w[j0 + i][q];
+                            b_zz += w[j0 + i][q] * w[j0 + i][q];
+                            b_rr += rv * rv;
+                        }
+                }
             }
         } else {
 #pragma unroll
@@ -532,6 +571,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         int lane_b = lane;
         if constexpr (HC && T >= 3) asm volatile("" : "+v"(lane_b));
         double rr;                                            // r.r of the NEW residual
+        double alpha_f = 0.0;                                 // FUSED: alpha, for the pass behind the stop test
         {   // ================= the single-meeting iteration ==================================================================
         // The two meetings of the textbook iteration (p.z -> alpha; then r.r of the new residual and its boundary slices -> beta, halo
         // of p) fold into ONE: every workgroup publishes FOUR sums — p.z, r.z, z.z and the r.r of the current residual — and the
@@ -543,7 +583,8 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         // accumulates.  When the step shrinks the residual so much that the identity cancels (r'.r' < r.r / 1000: never in the
         // hundreds of iterations of these matrices, but possible on a nearly diagonal one) the direct sum is taken in a second,
         // single-sum meeting — the same branch in every wave of the team, since all hold the same bits.
-        double s_pz = 0.0, s_rz = 0.0, s_zz = 0.0, s_rr = 0.0;
+        double s_pz = b_pz, s_rz = b_rz, s_zz = b_zz, s_rr = b_rr;
+        if constexpr (!BSUM) {                                // (BSUM: summed behind the reverse batches)
 #pragma unroll
         for (int j = 0; j < T; ++j)
 #pragma unroll
@@ -555,6 +596,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                     s_zz += z[j][q] * z[j][q];
                     s_rr += rv * rv;
                 }
+        }
         {
             const double k4 = wave_sum4(s_pz, s_rz, s_zz, s_rr, lane);
             if (lane < 4) part[lane * 8 + wv] = k4;
@@ -726,9 +768,11 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         }
         STAMP(1);
         rho = rr0;                                            // r.r of the residual this iteration started from, summed from the vector
-        const double alpha = rr0 / pap;                                                            // :278-279 (rho = r.r)
+        const double alpha = FUSED ? uni(rr0 / pap) : rr0 / pap;
+        if constexpr (FUSED) alpha_f = alpha;                 // :278-279 (rho = r.r)
         rr = rr0 + alpha * (alpha * zz - 2.0 * rz);
         // ---- x += alpha p, r -= alpha z (own slices) ----------------------------------------------------------------------------
+        if constexpr (!FUSED) {
 #pragma unroll
         for (int j = 0; j < T; ++j)
 #pragma unroll
@@ -747,13 +791,24 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             for (int q = 0; q < NPL; ++q) if (lwok) rh[lr + q * LSL] = rh[lr + q * LSL] - alpha * zh[lr + q * LSL];
         }
         STAMP(3);
+        }
+        // FUSED: the same update waits for the stop test and beta (below) and takes the p-update along (WITHP: p = r' + beta p from the r'
+        // just made; never in the honeycomb DPP form — a mirror lane's z is not the real lane's, its p is made from the real lane's r' in
+        // LDS).  When the identity cancels — the scalars at hand tell — the direct sum and the second meeting come first, as in the sharded
+        // solves, and the sum takes r' as the pass will make it (below); the pass itself stays ONE piece of straight-line code after the
+        // stop test: with the update on two paths that join again, x sat in two register sets at once and the 4-slice shape spilled
         if (!(rr > 1e-3 * rr0)) {
             // the identity cancels: take r'.r' from the vector itself (second meeting of this iteration; every wave of the team is here)
             double a = 0.0;
 #pragma unroll
             for (int j = 0; j < T; ++j)
 #pragma unroll
-                for (int q = 0; q < NPL; ++q) if (own[q]) { const double rn = rl[j * HSL + lr + q * LSL]; a += rn * rn; }
+                for (int q = 0; q < NPL; ++q)
+                    if (own[q]) {
+                        // (FUSED: r' is not in LDS yet — the same fma makes the same bits here as in the pass that will store them)
+                        const double rn = FUSED ? rl[j * HSL + lr + q * LSL] - alpha * z[j][q] : rl[j * HSL + lr + q * LSL];
+                        a += rn * rn;
+                    }
             a = wave_sum_dpp(a);
             if (lane == 0) partF[wv] = a;
             wg_barrier();
@@ -792,8 +847,10 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                 rr = tot[4];
             }
         }
-        wg_barrier();                                         // the new residual of every wave is in LDS: the neighbours' halo slices
-        STAMP(4);
+        if constexpr (!FUSED) {
+            wg_barrier();                                     // the new residual of every wave is in LDS: the neighbours' halo slices
+            STAMP(4);
+        }
         }
         STAMP(5);
         STAMP(6);
@@ -823,6 +880,38 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             if (g == 0 && wv == 0 && lane == 0 && P.record_hist) B.hist[(size_t)rhs * P.hist_stride + it] = eps;
         }
         STAMP(7);
+        if constexpr (FUSED) {
+            // the fused pass.  beta is made, and p is updated, whether or not this was the last iteration: past `done` nothing reads p
+            // (x takes alpha p of the OLD p inside the pass), and a select per value would cost more than the update.  rho = rr0 here.
+            const double beta = uni(rr / rho);
+#pragma unroll
+            for (int j = 0; j < T; ++j)
+#pragma unroll
+                for (int q = 0; q < NPL; ++q) {
+                    const double rn = rl[j * HSL + lr + q * LSL] - alpha_f * z[j][q];                 // :285
+                    if (lwok) rl[j * HSL + lr + q * LSL] = rn;
+                    if (X_GLB) { if (lwok) xg[(size_t)(t0 + j) * N + sc[q]] = xr[X_REG ? j : 0][q] + alpha_f * p[j + 1][q]; }
+                    else if (X_REG) xr[X_REG ? j : 0][q] += alpha_f * p[j + 1][q];                   // :282
+                    else if (lwok) xl[j * HSL + lr + q * LSL] += alpha_f * p[j + 1][q];
+                    if constexpr (!HC) p[j + 1][q] = rn + beta * p[j + 1][q];
+                }
+            if constexpr (HC) {
+                // from the real lane's r' in LDS: a wave reads what it wrote itself, no barrier — but the COMPILER must not hand a mirror
+                // lane, which stored nothing, the r it read from that slot before the real lane's store
+                WAVE_LDS_ORDER();
+#pragma unroll
+                for (int j = 0; j < T; ++j)
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) p[j + 1][q] = rl[j * HSL + lr + q * LSL] + beta * p[j + 1][q];
+            }
+            if (G > 1 && (wv == 0 || wv == W - 1)) {          // the neighbouring workgroup's boundary slice of the new residual
+                double *rh = rhalo + ((wv == 0) ? 0 : HSL);
+                const double *zh = zhalo + ((wv == 0) ? 0 : HSL);
+#pragma unroll
+                for (int q = 0; q < NPL; ++q) if (lwok) rh[lr + q * LSL] = rh[lr + q * LSL] - alpha_f * zh[lr + q * LSL];
+            }
+            STAMP(3);
+        }
         if (done) {
             STAMP_OUT(it);
             TL(2);
@@ -830,6 +919,9 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             //  value for the whole solve — in a kernel that has none to spare: 10 -> 2 spilled registers at 4 slices per wave)
             int lane2 = lane;
             asm volatile("" : "+v"(lane2));
+            // (FUSED: the first slice likewise, from the wave number read afresh as a scalar — one base address per slice would otherwise sit in
+            //  vector registers for the whole solve; and the state record is read again below rather than kept)
+            const int t0s = FUSED ? (g * W + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * T : t0;
 #pragma unroll
             for (int j = 0; j < T; ++j)
 #pragma unroll
@@ -839,11 +931,11 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                         // (the residual stays on the chip: ldiv! judges a solution by its TRUE residual, Models.jl:150-160; a shard's
                         //  caller may want it)
                         if (SHARD) rg[(size_t)(t0 + j) * N + s2] = rl[j * HSL + lr + q * LSL];
-                        if (!X_GLB) xg[(size_t)(t0 + j) * N + s2] = X_REG ? xr[X_REG ? j : 0][q] : xl[j * HSL + lr + q * LSL];
+                        if (!X_GLB) xg[(size_t)(t0s + j) * N + s2] = X_REG ? xr[X_REG ? j : 0][q] : xl[j * HSL + lr + q * LSL];
                     }
                 }
             if (g == 0 && wv == 0 && lane == 0) {
-                CgState o = S;
+                CgState o = FUSED ? ld_state(st2) : S;
                 o.rho = rho; o.kmin = kmin; o.eps = eps; o.seq = it + 1; o.iters = it; o.done = done;
                 st2[0] = o;
                 st2[1] = o;
@@ -853,7 +945,11 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         }
         const double beta = rr / rho;
         rho = rr;
-        // ---- next direction on the own slices and on the two halo slices (p = r + beta p is pointwise) --------------------
+        if constexpr (FUSED) {
+            wg_barrier();                                     // the new residual of every wave is in LDS: the neighbours' halo slices
+            STAMP(4);
+        }
+        // ---- next direction on the two halo slices, and (sharded solves) on the own slices (p = r + beta p is pointwise) ----
         {
             const bool lx = (G > 1 && wv == 0), rx = (G > 1 && wv == W - 1);
             const double *sl = rall + ((size_t)((wv > 0) ? wv - 1 : W - 1) * T + (T - 1)) * HSL;    // last slice of the wave below
@@ -871,10 +967,12 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                 }
             }
         }
+        if constexpr (!FUSED) {
 #pragma unroll
         for (int j = 0; j < T; ++j)
 #pragma unroll
             for (int q = 0; q < NPL; ++q) p[j + 1][q] = rl[j * HSL + lr + q * LSL] + beta * p[j + 1][q];
+        }
         STAMP(8);
     }
 #undef EXPV
