@@ -105,6 +105,12 @@ SIGNATURES = {
     "elph_ssh_meas_fetch": (c_int, [Handle, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl]),
     "elph_ssh_meas_reset": (c_int, [Handle]),
     "elph_ssh_meas_free": (c_int, [Handle]),
+    "elph_ssh_meas_chains_create": (c_int, [Handle, c_int, P_dbl, c_dbl, c_i64, c_int, P_i64, P_dbl, P_i64, P_i64, c_i64, c_int, P_dbl, P_dbl, P_dbl, P_int,
+                                            P_int, P_int, P_int]),
+    "elph_ssh_meas_chains_set_mu": (c_int, [Handle, P_dbl]),
+    "elph_ssh_meas_chains_accumulate": (c_int, [Handle, P_dbl]),
+    "elph_ssh_meas_chains_fetch": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl]),
+    "elph_ssh_meas_chains_reset": (c_int, [Handle]),
     "elph_ssh_bond_create": (c_int, [Handle, c_int, P_int, P_int, P_int, c_i64, P_dbl, P_i64, P_i64, c_i64, P_dbl, P_dbl, P_int, P_int, P_int, P_int]),
     "elph_ssh_bond_accumulate": (c_int, [Handle, P_dbl]),
     "elph_ssh_bond_fetch": (c_int, [Handle, P_dbl, P_dbl, P_dbl]),

@@ -1,5 +1,5 @@
 // corr_req.h — the request for a group of correlation functions, shared by measure.hip and measure_chains.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2),
-// ssh_measure.hip (on-site and PhononGreens over phonon types, N = 5) and ssh_bondcorr.hip (bonds, N = 2, and CurrentCurrent, N = 1):
+// ssh_measure.hip and ssh_measure_chains.hip (on-site and PhononGreens over phonon types, N = 5) and ssh_bondcorr.hip (bonds, N = 2, and CurrentCurrent, N = 1):
 // the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group does with its one
 // accumulator allocation [lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's accumulator is
 // [L0][L1][L2][L3][n_p] doubles, first index fastest, L0 = L + 1 (time-dependent, tau = beta included) or 1 (equal-time).
@@ -157,6 +157,76 @@ inline int corr_check_onsite_params(const elph_handle_s *h, const char *prefix, 
             if (s < 1 || s > N) { elph_set_error("%s: bond %lld joins site %lld, outside 1..%d", prefix, (long long)b + 1, (long long)s, N); return ELPH_E_ARG; }
             bs[(size_t)k * nbonds + b] = (int)(s - 1);
         }
+    return ELPH_OK;
+}
+
+// What elph_ssh_meas_create and elph_ssh_meas_chains_create check of their parameter arrays, bonds and phonons before anything is planned
+// or allocated, and the bond tables they put on the device: bs [2][nbonds] 0-based sites, bph [nbonds] 0-based phonon (-1 on a bare bond),
+// bpar [4][nbonds] t, omega, alpha, alpha2 (zeros on a bare bond), doff / dlist the bonds of every definition in bond order.  ndef comes
+// back as 0 for a model without bonds.
+struct CorrSshBonds {
+    std::vector<int> bs, bph, doff, dlist;
+    std::vector<double> bpar;
+};
+
+inline int corr_check_ssh_params(const elph_handle_s *h, const char *prefix, const double *mu, double dtau, int64_t nbonds, int &ndef,
+                                 const int64_t *bond_sites, const double *bond_t, const int64_t *bond_to_definition, const int64_t *bond_to_phonon,
+                                 int64_t Nph, int nph, const double *omega, const double *alpha, const double *alpha2, const int *measure,
+                                 const int *time_dependent, const int *npairs, CorrSshBonds &T) {
+    if (!mu || !measure || !time_dependent || !npairs) { elph_set_error("%s: a null parameter array", prefix); return ELPH_E_ARG; }
+    if (!(dtau > 0.0)) { elph_set_error("%s: dtau = %g", prefix, dtau); return ELPH_E_ARG; }
+    const int N = (int)h->N, L = (int)h->L;
+    if (ndef < 0 || nbonds < 0 || nbonds != h->nb || (nbonds > 0 && (ndef < 1 || nbonds < ndef || !bond_sites || !bond_t || !bond_to_definition || !bond_to_phonon))) {
+        elph_set_error("%s: %lld bonds in %d bond definitions (the handle has %lld bonds), or a null bond array", prefix, (long long)nbonds, ndef,
+                       (long long)h->nb);
+        return ELPH_E_ARG;
+    }
+    if (nbonds == 0) ndef = 0;
+    if (Nph < 0 || nph < 0 || Nph > 0x7fffffff / (int64_t)(L + 1) || (Nph > 0 && (!omega || !alpha || !alpha2))) {
+        elph_set_error("%s: %lld phonons of %d types, or a null phonon array", prefix, (long long)Nph, nph);
+        return ELPH_E_ARG;
+    }
+    T.bs.assign(2 * (size_t)nbonds, 0);
+    T.bph.assign((size_t)nbonds, 0);
+    T.doff.assign((size_t)ndef + 1, 0);
+    T.dlist.assign((size_t)nbonds, 0);
+    T.bpar.assign(4 * (size_t)nbonds, 0.0);
+    for (int64_t b = 0; b < nbonds; ++b) {
+        for (int k = 0; k < 2; ++k) {
+            const int64_t s = bond_sites[2 * b + k];
+            if (s < 1 || s > N) { elph_set_error("%s: bond %lld joins site %lld, outside 1..%d", prefix, (long long)b + 1, (long long)s, N); return ELPH_E_ARG; }
+            T.bs[(size_t)k * nbonds + b] = (int)(s - 1);
+        }
+        const int64_t d = bond_to_definition[b], p = bond_to_phonon[b];
+        if (d < 1 || d > ndef) { elph_set_error("%s: bond %lld belongs to definition %lld, outside 1..%d", prefix, (long long)b + 1, (long long)d, ndef); return ELPH_E_ARG; }
+        if (p < 0 || p > Nph) { elph_set_error("%s: bond %lld carries phonon %lld, outside 0..%lld", prefix, (long long)b + 1, (long long)p, (long long)Nph); return ELPH_E_ARG; }
+        ++T.doff[(size_t)d];
+        T.bph[(size_t)b] = (int)p - 1;
+        T.bpar[(size_t)b] = bond_t[b];
+        if (p > 0) {
+            T.bpar[(size_t)nbonds + b] = omega[p - 1];
+            T.bpar[2 * (size_t)nbonds + b] = alpha[p - 1];
+            T.bpar[3 * (size_t)nbonds + b] = alpha2[p - 1];
+        }
+    }
+    for (int d = 0; d < ndef; ++d) T.doff[(size_t)d + 1] += T.doff[(size_t)d];
+    std::vector<int> at(T.doff.begin(), T.doff.end() - 1);
+    for (int64_t b = 0; b < nbonds; ++b) T.dlist[(size_t)at[(size_t)bond_to_definition[b] - 1]++] = (int)b;
+    return ELPH_OK;
+}
+
+// PhononGreens over phonon types needs the field to reshape to (Ltau, L1, L2, L3, nph) and a frequency slice to fit in LDS
+inline int corr_check_phonongreens(const char *prefix, int nph, int64_t Nph, int L1, int L2, int L3, size_t lds_bytes) {
+    const int nc = L1 * L2 * L3;
+    if (nph < 1 || Nph != (int64_t)nph * nc) {
+        elph_set_error("%s: PhononGreens needs Nph = nph x ncells phonons; %lld phonons are not %d types x %d cells (the "
+                       "reference's reshape of the field to (Ltau, L1, L2, L3, nph) fails)", prefix, (long long)Nph, nph, nc);
+        return ELPH_E_UNSUPPORTED;
+    }
+    if (lds_bytes > 160 * 1024) {
+        elph_set_error("%s: PhononGreens: a frequency slice of the %d x %d x %d lattice (%d cells) does not fit in 160 KB of LDS", prefix, L1, L2, L3, nc);
+        return ELPH_E_UNSUPPORTED;
+    }
     return ELPH_OK;
 }
 

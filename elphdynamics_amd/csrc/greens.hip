@@ -162,6 +162,7 @@ void elph_greens_free(elph_handle_s *h) {
     elph_bond_free(h);
     elph_bond_chains_free(h);
     elph_i_ssh_meas_free(h);
+    elph_ssh_meas_chains_free(h);
     elph_ssh_bond_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;

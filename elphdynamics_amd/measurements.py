@@ -23,7 +23,9 @@ sharded and slab handles are refused by the library.  BondBond, BondPairGreens a
 this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent is measured for the SSH model
 alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.  Several chains resident in the handle (a lockstep
 run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure_chains.hip): one container per chain, all
-chains in the same launches; the functions here keep refusing them.  The bond correlations and the SSH model over chains stay refused.
+chains in the same launches; the functions here keep refusing them.  The bond correlations of the chains are
+chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure_chains.hip), except its
+bond correlations BondBond, CurrentCurrent and BondPairGreens, which stay refused over chains.
 
 One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
 The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,

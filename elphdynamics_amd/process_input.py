@@ -196,7 +196,7 @@ def initialize_swap_update(inp, model):
 
 
 def process_input_file(deck, device=0, nchains=1, rng=None):
-    """deck: path of a TOML file or an already parsed dict.  nchains > 1 (Holstein): the dynamics advance that many independent
+    """deck: path of a TOML file or an already parsed dict.  nchains > 1 (Holstein and SSH decks): the dynamics advance that many independent
     runs of the deck in lockstep on this GPU (what the reference does with one process per run ID, ElPhDynamics.jl:90-95)."""
     inp = read_deck(deck) if isinstance(deck, (str, os.PathLike)) else deck
     sim_params = initialize_simulation_params(inp)

@@ -1,64 +1,66 @@
-"""Measurements of every chain resident in a handle (a lockstep run: hmc.update_chains_, langevin.evolve_): the chain-aware twin of
-measurements.py.  One MeasurementsContainer per chain, each with its own data folder; on the device all chains are accumulated by the
-same launches (elph_meas_chains_*, csrc/measure_chains.hip), the chain a grid axis.
+"""Measurements of every chain of the bond-phonon (SSH) model resident in a handle (a lockstep run: langevin.evolve_, hmc.update_chains_):
+the chain-aware twin of ssh_measurements.py, as chain_measurements.py is of measurements.py.  One SSHMeasurementsContainer per chain, each
+with its own data folder; on the device all chains are accumulated by the same launches (elph_ssh_meas_chains_*,
+csrc/ssh_measure_chains.hip), the chain a grid axis.
 
-    cm = initialize_chain_measurements_container(model, info, datafolders)     one container per chain (Measurements.jl:27-178 each)
-    initialize_measurement_folders_(cm)                                        :343-540 per chain
+    cm = initialize_ssh_chain_measurements_container(model, info, datafolders)   one container per chain (Measurements.jl:180-338 each)
+    initialize_measurement_folders_(cm)                                          :343-540 per chain
     make_measurements_(cm, model, Gr, X, nmeas, P=None, R=None, rng=None, mu=None)      :545-566: update! of all chains' vectors as one
-                                                                                batched solve, then accumulate_
-    accumulate_(cm, model, Gr, X, mu=None)                                     every pair of a chain's vectors, all chains at once
-    fetch_(cm, model)                                                          the device's sums into the chains' containers
-    process_measurements_(cm, bin_size, model)                                 :574-676 per chain
-    write_measurements_(cm, model, bin)                                        :681-693 per chain, into the chain's folder
-    reset_measurements_(cm, model)                                             :698-758
+                                                                                  batched solve, then accumulate_
+    accumulate_(cm, model, Gr, X, mu=None)                                       every pair of a chain's vectors, all chains at once
+    fetch_(cm, model)                                                            the device's sums into the chains' containers
+    process_measurements_(cm, bin_size, model)                                   :574-676 per chain
+    write_measurements_(cm, model, bin)                                          :681-693 per chain, into the chain's folder
+    reset_measurements_(cm, model)                                               :698-758
 
-X is (nchains, Ndof): chain c's field (the HybridMonteCarlo's X after pull_()).  mu is (nchains, Nsites), a row per chain, for a run
-whose tuners move the chains' chemical potentials apart (hmc.set_mu_).  Given, it replaces the rows the device side holds, for this and
-every later accumulate; None keeps them (model.mu for every chain when the device side is made, by the first accumulate_).  The
-estimator serves the chains with n_rand_vecs * nchains vectors, vector v of chain c at index v * nchains + c (greens.chain_vector), as
+X is (nchains, Ndof): chain c's field (the dynamics' X after pull_()).  mu is (nchains, Nsites), a row per chain, for a run whose tuners
+move the chains' chemical potentials apart (hmc.set_mu_).  Given, it replaces the rows the device side holds, for this and every later
+accumulate; None keeps them (model.mu for every chain when the device side is made, by the first accumulate_).  The estimator serves the
+chains with n_rand_vecs * nchains vectors, vector v of chain c at index v * nchains + c (greens.chain_vector), as
 process_input_file(deck, nchains=n) builds it; a bin is normalised by bin_size * binomial(n_rand_vecs, 2) with the vectors PER CHAIN.
 A chain's folder holds exactly the files of a single-configuration run.
 
 The device side is shaped by the estimator and dropped by the library when a new EstimateGreensFunction is made on the model (with the
 sums it held): the next accumulate_ with the new estimator makes it again, with the mu given then (or model.mu).
 
-Scope: what measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the SSH model,
-BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true — the SSH model over chains is
-ssh_chain_measurements.py's (its bond correlations over chains stay refused); BondBond, BondPairGreens and BondPairSusc of the chains are chain_bond_measurements.py's, whose container is used beside
-this one on the same model and estimator, in either order.  measurements.py itself keeps refusing resident chains.
+Scope: what ssh_measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the Holstein
+model (chain_measurements.py measures it), BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry
+set to true.  The SSH bond correlations over chains are measured nowhere yet: ssh_bond_measurements.py serves one configuration per
+handle.  ssh_measurements.py itself keeps refusing resident chains.
 """
 import numpy as np
 
 from . import greens as _greens
-from . import measurements as _ms
-from ._lib import check, dptr, iptr
+from . import ssh_measurements as _sm
+from ._lib import check, dptr
 
-UnsupportedMeasurement = _ms.UnsupportedMeasurement
+UnsupportedMeasurement = _sm.UnsupportedMeasurement
+SUBJECT = "SSH chain measurements"
 
 
-class ChainMeasurementsContainer:
+class SSHChainMeasurementsContainer:
     def __init__(self, chains, n_rand_vecs):
-        self.chains = chains                 # one MeasurementsContainer per chain
+        self.chains = chains                 # one SSHMeasurementsContainer per chain
         self.nchains = len(chains)
         self.n_rand_vecs = n_rand_vecs       # per chain
         self._device_of = None               # the model whose handle holds the device side ...
         self._device_est = None              # ... and the estimator it was shaped by: a newer one on the model has dropped it
 
 
-def initialize_chain_measurements_container(model, info, datafolders):
+def initialize_ssh_chain_measurements_container(model, info, datafolders):
     """One container per resident chain of `model` for the request `info`; datafolders: one folder per chain."""
-    _ms._refuse_ssh(model, "chain measurements")
+    _sm._refuse_holstein(model)
     nchains = int(getattr(model, "_nchains", 1))
     datafolders = list(datafolders)
     if len(datafolders) != nchains:
         raise ValueError("%d data folders for the %d chains resident in the model" % (len(datafolders), nchains))
-    chains = [_ms._new_container(model, info, folder) for folder in datafolders]
-    return ChainMeasurementsContainer(chains, chains[0].n_rand_vecs)
+    chains = [_sm._new_container(model, info, folder) for folder in datafolders]
+    return SSHChainMeasurementsContainer(chains, chains[0].n_rand_vecs)
 
 
 def initialize_measurement_folders_(cm):
     for c in cm.chains:
-        _ms.initialize_measurement_folders_(c)
+        _sm.initialize_measurement_folders_(c)
 
 
 def _chain_rows(a, cm, width, what):
@@ -71,6 +73,7 @@ def _chain_rows(a, cm, width, what):
 def _check(cm, model, Gr, X, mu):
     """Everything that can be wrong on the host, before any library call."""
     assert Gr.model is model
+    _sm._refuse_holstein(model)
     if int(getattr(model, "_nchains", 1)) != cm.nchains:
         raise ValueError("the container was made for %d chains, %d are resident in the model" % (cm.nchains, getattr(model, "_nchains", 1)))
     if Gr.nv != cm.n_rand_vecs * cm.nchains:
@@ -85,15 +88,11 @@ def _check(cm, model, Gr, X, mu):
 def _ensure_device(cm, model, Gr, mu):
     if cm._device_of is model and cm._device_est is Gr:
         if mu is not None:              # the tuners moved it since: the device's rows follow (a small copy), the sums so far are kept
-            check(model._lib.elph_meas_chains_set_mu(model._h, dptr(mu)))
+            check(model._lib.elph_ssh_meas_chains_set_mu(model._h, dptr(mu)))
         return
-    sites, t = _ms.bond_arrays(model)
-    request = _ms._request_arrays(cm.chains[0].onsite_corr, _ms.ONSITE_CORR)
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-    mu = f64(np.tile(model.mu, (cm.nchains, 1))) if mu is None else mu
-    check(model._lib.elph_meas_chains_create(model._h, cm.nchains, dptr(f64(model.omega)), dptr(f64(model.omega4)), dptr(f64(model.lam)),
-                                             dptr(mu), float(model.dtau), sites.shape[0], int(model.nbonds), iptr(sites) if sites.size else None,
-                                             dptr(t) if t.size else None, *map(_ms._ip, request)))
+    mu = np.ascontiguousarray(np.tile(model.mu, (cm.nchains, 1)), dtype=np.float64) if mu is None else mu
+    args, keep = _sm._create_args(cm.chains[0], model)
+    check(model._lib.elph_ssh_meas_chains_create(model._h, cm.nchains, dptr(mu), *args))
     cm._device_of, cm._device_est = model, Gr
 
 
@@ -102,7 +101,7 @@ def accumulate_(cm, model, Gr, X, mu=None):
     device's accumulators for all chains at once; nothing comes back to the host."""
     X, mu = _check(cm, model, Gr, X, mu)
     _ensure_device(cm, model, Gr, mu)
-    check(model._lib.elph_meas_chains_accumulate(model._h, dptr(X)))
+    check(model._lib.elph_ssh_meas_chains_accumulate(model._h, dptr(X)))
 
 
 def make_measurements_(cm, model, Gr, X, nmeas, P=None, R=None, rng=None, mu=None):
@@ -120,27 +119,27 @@ def fetch_(cm, model):
     if cm._device_of is not model:
         raise RuntimeError("nothing has been measured on this model yet")
     for chain, c in enumerate(cm.chains):
-        scal, ptrs = _ms._fetch_buffers(c)
-        check(model._lib.elph_meas_chains_fetch(model._h, chain, dptr(scal), *ptrs))
-        _ms._store_scalars(c, scal)
+        scal, ptrs = _sm._fetch_buffers(c)
+        check(model._lib.elph_ssh_meas_chains_fetch(model._h, chain, dptr(scal), *ptrs))
+        _sm._store_scalars(c, scal)
 
 
 def process_measurements_(cm, bin_size, model):
     """process_measurements! (:574-676) per chain; every chain's sums run over binomial(n_rand_vecs, 2) pairs of ITS vectors."""
     fetch_(cm, model)
     for c in cm.chains:
-        _ms._process_fetched(c, bin_size, model.dtau)
+        _sm._process_fetched(c, bin_size, model.dtau)
 
 
 def write_measurements_(cm, model, bin):
     """write_measurements! (:681-693) per chain, into the chain's folder."""
     for c in cm.chains:
-        _ms.write_measurements_(c, model, bin)
+        _sm.write_measurements_(c, model, bin)
 
 
 def reset_measurements_(cm, model):
     """reset_measurements! (:698-758): every chain's arrays and the device's accumulators to zero."""
     for c in cm.chains:
-        _ms._zero_container(c)
+        _sm._zero_container(c)
     if cm._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_meas_chains_reset(model._h))
+        check(model._lib.elph_ssh_meas_chains_reset(model._h))

@@ -21,7 +21,10 @@ Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: B
 BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, a Holstein model, several chains resident in the
 handle; sharded and slab handles, and PhononGreens on a lattice where Nph != nph * ncells (the reference's reshape of the field
 throws), are refused by the library.  BondBond, CurrentCurrent, BondPairGreens and BondPairSusc live in a container of their own beside
-this one (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), used on the same model and estimator.
+this one (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), used on the same model and estimator.  Several chains resident in the handle
+(a lockstep run) are measured by the chain-aware twin of this module, ssh_chain_measurements.py (csrc/ssh_measure_chains.hip): one
+container per chain, all chains in the same launches; the functions here keep refusing them.  BondBond, CurrentCurrent and BondPairGreens
+over chains stay refused.
 
 Line order in the scalar files (the reference's is the unspecified order of a Julia Dict), extending the one of measurements.py:
 density, Nsqr, mu / density, double_occ, mu / x, x2, x4, phonon_pe, phonon_ke, elph_energy, el_ke, sign_switch.
@@ -58,10 +61,9 @@ def _refuse_holstein(model):
         raise UnsupportedMeasurement("%s of the Holstein model are not supported (SSH only; see measurements.py)" % SUBJECT)
 
 
-def initialize_ssh_measurements_container(model, info, datafolder):
-    """initialize_measurements_container(ssh, info, datafolder) (:180-338)."""
-    _refuse_holstein(model)
-    _refuse_chains(model, SUBJECT)
+def _new_container(model, info, datafolder):
+    """The container of one configuration of an SSH model for the request `info`, after the caller has decided that the model is measured
+    (ssh_chain_measurements.py makes one per resident chain): the requests neither path measures are refused here."""
     info = info or {}
     for name in INTERSITE_CORR:
         if info.get(name, {}).get("measure", False) is True:
@@ -86,6 +88,13 @@ def initialize_ssh_measurements_container(model, info, datafolder):
     return c
 
 
+def initialize_ssh_measurements_container(model, info, datafolder):
+    """initialize_measurements_container(ssh, info, datafolder) (:180-338)."""
+    _refuse_holstein(model)
+    _refuse_chains(model, SUBJECT)
+    return _new_container(model, info, datafolder)
+
+
 def initialize_measurement_folders_(container):
     """initialize_measurement_folders!(container) (:343-540): the on-site groups' key files name orbit1, orbit2, the inter-site ones bond1, bond2."""
     d = container.datafolder
@@ -108,11 +117,9 @@ def _all_corr(container):
     return dict(container.onsite_corr, **container.intersite_corr)
 
 
-def _ensure_device(container, model, Gr):
-    if container._device_of is model:
-        return
-    _refuse_holstein(model)
-    _check_estimator(container, model, Gr)
+def _create_args(container, model):
+    """The arguments of elph_ssh_meas_create after mu and of elph_ssh_meas_chains_create after nchains and mu: dtau, the bonds, the phonons
+    and the container's requests.  The second value keeps the arrays alive for the call."""
     sites, t = bond_arrays(model)
     request = _request_arrays(_all_corr(container), CREATE_ORDER)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
@@ -120,9 +127,18 @@ def _ensure_device(container, model, Gr):
     nph_tot, nb = int(model.Nph), int(model.Nbonds)
     b2d, b2p = i64(model.bond_to_definition), i64(model.bond_to_phonon)
     par = [f64(a) for a in (model.omega, model.alpha, model.alpha2)]
-    check(model._lib.elph_ssh_meas_create(model._h, dptr(f64(model.mu)), float(model.dtau), nb, int(model.nbonds), iptr(sites) if nb else None,
-                                          dptr(t) if nb else None, iptr(b2d) if nb else None, iptr(b2p) if nb else None, nph_tot, int(model.nph),
-                                          *[dptr(a) if nph_tot else None for a in par], *map(_ip, request)))
+    args = [float(model.dtau), nb, int(model.nbonds), iptr(sites) if nb else None, dptr(t) if nb else None, iptr(b2d) if nb else None,
+            iptr(b2p) if nb else None, nph_tot, int(model.nph), *[dptr(a) if nph_tot else None for a in par], *map(_ip, request)]
+    return args, (sites, t, b2d, b2p, par, request)
+
+
+def _ensure_device(container, model, Gr):
+    if container._device_of is model:
+        return
+    _refuse_holstein(model)
+    _check_estimator(container, model, Gr)
+    args, keep = _create_args(container, model)
+    check(model._lib.elph_ssh_meas_create(model._h, dptr(np.ascontiguousarray(model.mu, dtype=np.float64)), *args))
     container._device_of = model
 
 
@@ -143,15 +159,16 @@ def make_measurements_(container, model, Gr, nmeas, P=None, R=None, rng=None):
     return out
 
 
-def fetch_(container, model):
-    """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
-    if container._device_of is not model:
-        raise RuntimeError("nothing has been measured on this model yet")
+def _fetch_buffers(container):
+    """(scalars, the position arrays' pointers in CREATE_ORDER) for a *_fetch call into the container."""
     no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
     scal = np.zeros(3 + len(ONSITE_KEYS) * no + len(INTERSITE_KEYS) * nb)
     corr = _all_corr(container)
-    ptrs = [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in CREATE_ORDER]
-    check(model._lib.elph_ssh_meas_fetch(model._h, dptr(scal), *ptrs))
+    return scal, [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in CREATE_ORDER]
+
+
+def _store_scalars(container, scal):
+    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
     for i, k in enumerate(GLOBAL_KEYS):
         container.global_meas[k] = complex(scal[i])
     for i, k in enumerate(ONSITE_KEYS):
@@ -161,17 +178,31 @@ def fetch_(container, model):
         container.intersite_meas[k][:] = scal[at + i * nb:at + (i + 1) * nb]
 
 
-def process_measurements_(container, bin_size, model):
-    """process_measurements!(container, sim_params, model) (:574-676); bin_size is sim_params.bin_size."""
-    fetch_(container, model)
+def fetch_(container, model):
+    """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
+    if container._device_of is not model:
+        raise RuntimeError("nothing has been measured on this model yet")
+    scal, ptrs = _fetch_buffers(container)
+    check(model._lib.elph_ssh_meas_fetch(model._h, dptr(scal), *ptrs))
+    _store_scalars(container, scal)
+
+
+def _process_fetched(container, bin_size, dtau):
+    """process_measurements! after the fetch: momentum copy, normalisation, susceptibilities."""
     V = _bin_volume(container, bin_size)
     for k in container.global_meas:
         container.global_meas[k] /= V
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k] /= V
-    _process_group(container.onsite_corr, container.onsite_susc, SUSC_OF, V, model.dtau)
-    _process_group(container.intersite_corr, container.intersite_susc, (), V, model.dtau)
+    _process_group(container.onsite_corr, container.onsite_susc, SUSC_OF, V, dtau)
+    _process_group(container.intersite_corr, container.intersite_susc, (), V, dtau)
+
+
+def process_measurements_(container, bin_size, model):
+    """process_measurements!(container, sim_params, model) (:574-676); bin_size is sim_params.bin_size."""
+    fetch_(container, model)
+    _process_fetched(container, bin_size, model.dtau)
 
 
 def write_measurements_(container, model, bin):
@@ -193,13 +224,17 @@ def write_measurements_(container, model, bin):
     _write_groups(d, bin, container.onsite_corr, container.intersite_corr, container.onsite_susc, container.intersite_susc)
 
 
-def reset_measurements_(container, model):
-    """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
+def _zero_container(container):
     for k in container.global_meas:
         container.global_meas[k] = 0j
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k][:] = 0
     _zero_groups(container.onsite_corr, container.intersite_corr, container.onsite_susc, container.intersite_susc)
+
+
+def reset_measurements_(container, model):
+    """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
+    _zero_container(container)
     if container._device_of is model and model is not None and getattr(model, "_h", None):
         check(model._lib.elph_ssh_meas_reset(model._h))

@@ -589,6 +589,52 @@ int elph_ssh_meas_reset(elph_handle h);
 /* Drops the container (elph_greens_create and elph_destroy do so as well). */
 int elph_ssh_meas_free(elph_handle h);
 
+/* ---------------------------------------------------------------- measurements of resident chains (bond-phonon (SSH) model) */
+
+/* elph_ssh_meas_create for every chain resident in the handle (elph_update_model_ssh_fields_chains, elph_hmc_create_ssh_chains): one
+ * container per chain in one device allocation [chain][scalars | Greens | DenDen | SpinSpin | PairGreens | PhononGreens], in a slot of
+ * its own beside the container of elph_ssh_meas_create, with the buffers of the fields of all chains and the scratch in which the
+ * estimator's setup! (GreensFunctions.jl:239-288) runs for one pair of vectors of all chains at once.  Needs elph_greens_create first; a
+ * new elph_greens_create drops it.  The estimator serves the chains with n_v * nchains vectors, vector v of chain c at index
+ * v * nchains + c (0-based).  Arguments as elph_ssh_meas_create, except
+ *   nchains   >= 1 and equal to the number of chains resident in the handle
+ *   mu        double[nchains * nsites], a row per chain: a tuner per chain moves it (elph_hmc_set_mu_chains); the global mu (:858) and
+ *             the on-site mu (:1018) of chain c come from row c
+ * The bonds, the phonon parameters and the requests are the model's and serve every chain.  Checked in this order, before anything is
+ * allocated; a refused request leaves the handle without this container and usable:
+ *   ELPH_E_UNSUPPORTED   the Holstein model ("SSH only"); a sharded or slab handle
+ *   ELPH_E_ARG           nchains < 1 or not the resident number (the message names both)
+ *   ELPH_E_STATE         elph_greens_create has not been called
+ *   ELPH_E_ARG           as elph_ssh_meas_create: a null array, a site, definition, phonon, orbital or phonon type outside its range
+ *   ELPH_E_UNSUPPORTED   PhononGreens requested with Nph != nph * ncells, or on a lattice whose frequency slice does not fit the LDS */
+int elph_ssh_meas_chains_create(elph_handle h, int nchains, const double *mu, double dtau, int64_t nbonds, int ndef, const int64_t *bond_sites,
+                                const double *bond_t, const int64_t *bond_to_definition, const int64_t *bond_to_phonon, int64_t Nph, int nph,
+                                const double *omega, const double *alpha, const double *alpha2, const int *measure, const int *time_dependent,
+                                const int *npairs, const int *pairs);
+
+/* The chemical-potential tuners moved the chains' mu: mu, double[nchains * nsites], replaces the rows elph_ssh_meas_chains_create took,
+ * for the global and the on-site mu of the accumulates that follow.  The sums so far are kept.  ELPH_E_STATE: not created. */
+int elph_ssh_meas_chains_set_mu(elph_handle h, const double *mu);
+
+/* make_measurements! (Measurements.jl:545-566) without its update!, for every chain: X is double[nchains * Nph * L_tau], chain c's
+ * model.x (phonon slowest) at X + c * Nph * L_tau.  The field-only terms, PhononGreens and, for every pair v1 < v2 of a chain's n_v
+ * vectors, the device part of setup! and the folds run once for all chains (the chain is a grid axis: the number of launches does not
+ * depend on nchains), stream-ordered, with one synchronisation before the call returns.  Sums as elph_ssh_meas_accumulate: one fixed
+ * order, no atomics; chain c's numbers depend on chain c's inputs alone.  The estimator's own tables (elph_greens_dev_arrays) are not
+ * touched.
+ *   ELPH_E_STATE   elph_ssh_meas_chains_create has not been called; the handle no longer holds the number of chains the container was
+ *                  created for (after elph_update_model_ssh_fields, say; the message names both counts); the estimator's vectors are
+ *                  not a multiple of it; the estimator holds no vectors yet */
+int elph_ssh_meas_chains_accumulate(elph_handle h, const double *X);
+
+/* One chain's un-normalised sums since the last reset: the outputs of elph_ssh_meas_fetch for chain `chain` (0-based).  One
+ * device-to-host copy, one synchronisation.  ELPH_E_STATE: not created; ELPH_E_ARG: a chain outside 0..nchains-1. */
+int elph_ssh_meas_chains_fetch(elph_handle h, int chain, double *scalars, double *Greens, double *DenDen, double *SpinSpin, double *PairGreens,
+                               double *PhononGreens);
+
+/* reset_measurements! (Measurements.jl:698-758) of every chain: one memset (stream-ordered).  ELPH_E_STATE: not created. */
+int elph_ssh_meas_chains_reset(elph_handle h);
+
 /* ---------------------------------------------------------------- inter-site correlations of the bond-phonon (SSH) model */
 
 /* The device side of the SSH container's BondBond, CurrentCurrent and BondPairGreens (init_corr_container! over ssh.nbonds bond
