@@ -115,6 +115,11 @@ SIGNATURES = {
     "elph_ssh_bond_accumulate": (c_int, [Handle, P_dbl]),
     "elph_ssh_bond_fetch": (c_int, [Handle, P_dbl, P_dbl, P_dbl]),
     "elph_ssh_bond_reset": (c_int, [Handle]),
+    "elph_ssh_bond_chains_create": (c_int, [Handle, c_int, c_int, P_int, P_int, P_int, c_i64, P_dbl, P_i64, P_i64, c_i64, P_dbl, P_dbl, P_int, P_int, P_int,
+                                            P_int]),
+    "elph_ssh_bond_chains_accumulate": (c_int, [Handle, P_dbl]),
+    "elph_ssh_bond_chains_fetch": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl]),
+    "elph_ssh_bond_chains_reset": (c_int, [Handle]),
     "elph_hmc_create_ssh": (c_int, [Handle, c_i64, P_dbl, P_dbl, P_i64, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, P_dbl]),
     "elph_hmc_create_ssh_chains": (c_int, [Handle, c_int, c_i64, P_dbl, P_dbl, P_i64, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, P_dbl]),
     "elph_hmc_create_chains": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, P_dbl]),

@@ -24,7 +24,7 @@ sums it held): the next accumulate_ with the new estimator makes it again, with 
 
 Scope: what measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the SSH model,
 BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true — the SSH model over chains is
-ssh_chain_measurements.py's (its bond correlations over chains stay refused); BondBond, BondPairGreens and BondPairSusc of the chains are chain_bond_measurements.py's, whose container is used beside
+ssh_chain_measurements.py's (its bond correlations over chains ssh_chain_bond_measurements.py's); BondBond, BondPairGreens and BondPairSusc of the chains are chain_bond_measurements.py's, whose container is used beside
 this one on the same model and estimator, in either order.  measurements.py itself keeps refusing resident chains.
 """
 import numpy as np

@@ -1,10 +1,11 @@
-// bondcorr_dev.h — what the bond-correlation units share (bondcorr.hip and bondcorr_chains.hip: Holstein, ssh_bondcorr.hip: bond phonons): the
-// kernels of
+// bondcorr_dev.h — what the bond-correlation units share (bondcorr.hip and bondcorr_chains.hip: Holstein, ssh_bondcorr.hip and
+// ssh_bondcorr_chains.hip: bond phonons): the kernels of
 //   measure_BondBond!         Measurements.jl:1663-1785
 //   measure_BondPairGreens!   Measurements.jl:2390-2483
 // which read model.bond_definitions and nothing else of the model, their state, and the host steps around them (the definitions'
-// table, create, the launches of one pair of vectors).  One text of each kernel body, shared with bondcorr_chains.hip (the Holstein
-// correlations of every resident chain at once); the formulas and layouts are in bondcorr.hip's header.
+// table, create, the launches of one pair of vectors).  One text of each kernel body, shared by the single-configuration kernels and the
+// chain kernels k_bcc_* (every resident chain at once: bondcorr_chains.hip, ssh_bondcorr_chains.hip); the formulas and layouts are in
+// bondcorr.hip's header.
 #pragma once
 
 #include <vector>
@@ -47,8 +48,8 @@ __device__ __forceinline__ int shifted_cell(int cell, const int *dv, int L1, int
     return cell_plus(cell, dv[2], dv[3], dv[4], L1, L2, L3);
 }
 
-// ---- what one thread or workgroup does in each kernel, shared by the single-configuration kernels below and the kernels of
-// bondcorr_chains.hip (every resident chain, the chain a grid axis): the two differ only in where a workgroup finds its chain's block.
+// ---- what one thread or workgroup does in each kernel, shared by the single-configuration kernels and the chain kernels below
+// (every resident chain, the chain a grid axis): the two differ only in where a workgroup finds its chain's block.
 // The buffers carry the chain between the definition (or listed pair) and the time axis — f: [NFIELD][ndef][chain][L][nc], nu the same
 // with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc] — so a body takes its chain's block of definition (pair) 0 and the distance
 // between two definitions (pairs); with one configuration that distance is the block itself.
@@ -184,6 +185,37 @@ __global__ void __launch_bounds__(BC_TPB) k_bc_fold(BondReq rq, const double *__
     bc_fold_at(rq, blockIdx.y, (long long)blockIdx.x * BC_TPB + threadIdx.x, B, G0, defs, L, ns, L1, L2, L3, (size_t)L * (L1 * L2 * L3), 0);
 }
 
+// ---- the kernels of every resident chain at once (bondcorr_chains.hip, ssh_bondcorr_chains.hip): the chain is the last grid axis; per: L nc,
+// slice: Lh nc
+
+// One thread per (cell, tau, definition) of chain blockIdx.y.  X1 .. R2: chain 0's vectors, chain c's c L N further on.
+__global__ void __launch_bounds__(BC_TPB) k_bcc_fields(double *__restrict__ f, ElphGreensPair v, const int *__restrict__ defs, int N, int L, int ns,
+                                                       int L1, int L2, int L3, int ndef, int nchains) {
+    const size_t ch = blockIdx.y, o = ch * L * N, per = (size_t)L * (L1 * L2 * L3);
+    bc_fields_at(f + ch * per, v.X1 + o, v.X2 + o, v.R1 + o, v.R2 + o, defs, N, L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * BC_TPB + threadIdx.x,
+                 (size_t)nchains * per);
+}
+
+// One workgroup per (frequency, listed pair, chain).  LDS: 2 buffers of nc complex.
+__global__ void __launch_bounds__(BC_TPB) k_bcc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, BondReq rq, int Lh, int ndef, int L1,
+                                                          int L2, int L3, const double2 *__restrict__ tw, double norm, int nchains) {
+    extern __shared__ double2 lds[];
+    const int nc = L1 * L2 * L3;
+    const size_t ch = blockIdx.z, slice = (size_t)Lh * nc;
+    bc_correlate_slice(Y + (((size_t)blockIdx.y * nchains + ch) * Lh + blockIdx.x) * nc, nu + ch * slice, rq, blockIdx.y, blockIdx.x, ndef, L1, L2, L3, tw,
+                       norm, (size_t)nchains * slice, lds);
+}
+
+// One thread per (tau, cell, listed pair) of correlation blockIdx.y of chain blockIdx.z.  C0: table 0 of chain 0; block: doubles of a
+// chain's accumulators.
+__global__ void __launch_bounds__(BC_TPB) k_bcc_fold(BondReq rq, const double *__restrict__ B, const double *__restrict__ C0,
+                                                     const int *__restrict__ defs, int N, int L, int ns, int L1, int L2, int L3, int nchains,
+                                                     size_t block) {
+    const size_t ch = blockIdx.z, per = (size_t)L * (L1 * L2 * L3);
+    bc_fold_at(rq, blockIdx.y, (long long)blockIdx.x * BC_TPB + threadIdx.x, B + ch * per, C0 + ch * L * ns * N, defs, L, ns, L1, L2, L3,
+               (size_t)nchains * per, ch * block);
+}
+
 // ---- host
 
 // model.bond_definitions (o₁, o₂ 1-based, v in unit cells) into the [n_def][DEFW] table the kernels read; w: the unit's words.
@@ -289,6 +321,30 @@ int bc_accumulate_pair(elph_handle_s *h, BondState *m, const ElphGreensView &g, 
     hipLaunchKernelGGL(k_bc_fold, dim3((unsigned)((m->cr.fold_max + BC_TPB - 1) / BC_TPB), NBOND), dim3(BC_TPB), 0, h->stream, m->cr.req, m->B, g.C,
                        m->defs, L, ns, m->L1, m->L2, m->L3);
     return elph_launch_check("k_bc_fold");
+}
+
+// BondBond and BondPairGreens of one pair of vectors v of every chain (m->nchains), after its elph_i_greens_setup_chains_dev into S, into
+// m's accumulators [chain][BondBond | BondPairGreens].
+int bc_accumulate_pair_chains(elph_handle_s *h, BondState *m, const ElphGreensView &g, const ElphGreensChainScratch &S, const ElphGreensPair &v) {
+    const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = m->ns, nc = m->nc, ndef = m->ndef, nch = m->nchains;
+    const int nP = m->cr.npairs, nk = m->k1 - m->k0;
+    const size_t shm = bc_lds_bytes(nc);
+    const long long nfld = (long long)L * nc * ndef;
+    const double norm = 1.0 / ((double)L * (double)nc * (double)nc);   // 1/(L Nc)² in all: the other 1/L is in the inverse τ table
+    hipLaunchKernelGGL(k_bcc_fields, dim3((unsigned)((nfld + BC_TPB - 1) / BC_TPB), (unsigned)nch), dim3(BC_TPB), 0, h->stream, m->f, v, m->defs, N, L, ns,
+                       m->L1, m->L2, m->L3, ndef, nch);
+    RC(elph_launch_check("k_bcc_fields"));
+    double2 *nu = m->nu + (size_t)m->k0 * ndef * nch * Lh * nc;
+    RC(elph_dft_fwd_plain(h, nu, m->f + (size_t)m->k0 * ndef * nch * L * nc, nc, nk * ndef * nch));
+    hipLaunchKernelGGL(k_bc_spatial_fwd, dim3((unsigned)Lh, (unsigned)(nk * ndef * nch)), dim3(BC_TPB), shm, h->stream, nu, Lh, m->L1, m->L2, m->L3, g.tw);
+    RC(elph_launch_check("k_bc_spatial_fwd(chains)"));
+    hipLaunchKernelGGL(k_bcc_correlate, dim3((unsigned)Lh, (unsigned)nP, (unsigned)nch), dim3(BC_TPB), shm, h->stream, m->Y, m->nu, m->cr.req, Lh, ndef,
+                       m->L1, m->L2, m->L3, g.tw, norm, nch);
+    RC(elph_launch_check("k_bcc_correlate"));
+    RC(elph_dft_inv_plain(h, m->B, m->Y, nc, nP * nch));
+    hipLaunchKernelGGL(k_bcc_fold, dim3((unsigned)((m->cr.fold_max + BC_TPB - 1) / BC_TPB), NBOND, (unsigned)nch), dim3(BC_TPB), 0, h->stream, m->cr.req,
+                       m->B, S.C, m->defs, N, L, ns, m->L1, m->L2, m->L3, nch, m->cr.total);
+    return elph_launch_check("k_bcc_fold");
 }
 
 }  // namespace

@@ -378,6 +378,7 @@ struct elph_handle_s {
     void *ssh_meas = nullptr;              // SshMeasState (ssh_measure.hip), owned; freed with greens
     void *ssh_meas_chains = nullptr;       // SshMeasChainsState (ssh_measure_chains.hip), owned; freed with greens
     void *ssh_bond = nullptr;              // SshBondState (ssh_bondcorr.hip), owned; freed with greens
+    void *ssh_bond_chains = nullptr;       // SshBondChainsState (ssh_bondcorr_chains.hip), owned; freed with greens
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
     // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
     // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
@@ -464,6 +465,7 @@ void elph_bond_chains_free(elph_handle_s *h);                               // b
 void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip
 void elph_ssh_meas_chains_free(elph_handle_s *h);                           // ssh_measure_chains.hip
 void elph_ssh_bond_free(elph_handle_s *h);                                  // ssh_bondcorr.hip
+void elph_ssh_bond_chains_free(elph_handle_s *h);                           // ssh_bondcorr_chains.hip
 // greens.hip internals used by the measurement units
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;
@@ -479,7 +481,7 @@ struct ElphGreensPair { const double *X1, *X2, *R1, *R2; };
 int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p);
 int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS);
 // the same pipelines for one pair of vectors of every resident chain at once, in scratch the caller owns (measure_chains.hip,
-// bondcorr_chains.hip, ssh_measure_chains.hip); sizes in elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N
+// bondcorr_chains.hip, ssh_measure_chains.hip, ssh_bondcorr_chains.hip); sizes in elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N
 struct ElphGreensChainScratch {
     int nchains;
     double *f;                 // [8][nchains][ndim] the input fields

@@ -28,28 +28,18 @@
 // else is one thread's sum in index order.  No floating-point atomics: the same inputs give the same bits.
 //
 // State: the handle's slot ssh_bond.  BondBond and BondPairGreens live in a BondState of bondcorr_dev.h (made when one of them is
-// requested), CurrentCurrent in an accumulator and scratch of this unit's.
+// requested), CurrentCurrent in an accumulator and scratch of this unit's.  The bodies of the CurrentCurrent kernels are in
+// currcorr_dev.h, shared with ssh_bondcorr_chains.hip (every resident chain at once); the kernels here are thin wrappers over them.
 
 #include <vector>
 
-#include "bondcorr_dev.h"
-#include "meas_dev.h"
+#include "currcorr_dev.h"
 
 namespace {
 
 constexpr int TPB = MEAS_TPB;
 constexpr int NWAVE = MEAS_NWAVE;
-static_assert(TPB == BC_TPB, "dft_cells walks the workgroup of k_cc_correlate");
-constexpr int NREQ = 3;               // the entry points' request order
-enum { REQ_BONDBOND = 0, REQ_CURRENT = 1, REQ_BONDPAIR = 2 };
-const char *const BOND_NAMES[NBOND] = {"BondBond", "BondPairGreens"};
-const char *const CC_NAMES[1] = {"CurrentCurrent"};
 const CorrWords WORDS = {"SSH bond correlations", "bond", "with no pair of bonds"};
-constexpr int NCC = 8;                // fields per definition (header)
-constexpr int NDELTA = 4;             // δ terms: a == c, a == d, b == c, b == d
-constexpr int NHPAR = 3;              // per bond: t, alpha, alpha2 (zeros on a bare bond)
-
-using CcReq = CorrReq<1>;
 
 struct SshBondState {
     BondState *bond = nullptr;      // BondBond, BondPairGreens (null: neither requested)
@@ -71,49 +61,16 @@ struct SshBondState {
 
 SshBondState *sb_of(elph_handle_s *h) { return (SshBondState *)h->ssh_bond; }
 
-// t′ of bond `bond` = cell + nc n on slice t
-__device__ __forceinline__ double cc_hopping(const double *__restrict__ bpar, const int *__restrict__ bph, const double *__restrict__ xr,
-                                             int nb, int L, int bond, int t) {
-    const int ph = bph[bond];
-    const double t0 = bpar[bond];
-    return ph < 0 ? t0 : t_modulated(t0, bpar[nb + bond], bpar[2 * nb + bond], xr[(size_t)ph * L + t]);
-}
-
-// The displacements l of the four δ terms (header) from the reduced shifts of n′ (d1) and n″ (d2).
-__device__ __forceinline__ void cc_delta_shifts(int l[NDELTA][3], const int *d1, const int *d2, int L1, int L2, int L3) {
-    const int dims[3] = {L1, L2, L3};
-    for (int k = 0; k < 3; ++k) {
-        l[0][k] = (d2[2 + k] + dims[k] - d1[2 + k]) % dims[k];
-        l[1][k] = (dims[k] - d1[2 + k]) % dims[k];
-        l[2][k] = d2[2 + k];
-        l[3][k] = 0;
-    }
-}
+// ---- the CurrentCurrent kernels of one configuration: the bodies of currcorr_dev.h with the stride between definitions (pairs) equal to
+// the block
 
 // The eight fields of every definition (header), one thread per (cell, τ, definition).
 __global__ void __launch_bounds__(TPB) k_cc_fields(double *__restrict__ f, const double *__restrict__ X1, const double *__restrict__ X2,
                                                    const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs,
                                                    const double *__restrict__ bpar, const int *__restrict__ bph, const double *__restrict__ xr,
                                                    int N, int L, int ns, int L1, int L2, int L3, int ndef) {
-    const int nc = L1 * L2 * L3;
-    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
-    const long long per = (long long)L * nc;
-    if (idx >= per * ndef) return;
-    const int cell = (int)(idx % nc), t = (int)((idx / nc) % L), n = (int)(idx / per);
-    const int *dv = defs + n * DEFW;
-    const size_t is = (size_t)t * N + (size_t)cell * ns + dv[0];
-    const size_t ie = (size_t)t * N + (size_t)shifted_cell(cell, dv, L1, L2, L3) * ns + dv[1];
-    const double x1s = X1[is], x2s = X2[is], r1s = R1[is], r2s = R2[is], x1e = X1[ie], x2e = X2[ie], r1e = R1[ie], r2e = R2[ie];
-    const double tp = cc_hopping(bpar, bph, xr, ndef * nc, L, n * nc + cell, t);
-    const size_t fs = (size_t)ndef * per, o = (size_t)n * per + (size_t)t * nc + cell;
-    f[o] = (x1s * r1e) * tp;
-    f[fs + o] = (x1e * r1s) * tp;
-    f[2 * fs + o] = (x2e * r2s) * tp;
-    f[3 * fs + o] = (x2s * r2e) * tp;
-    f[4 * fs + o] = (x1s * r2e) * tp;
-    f[5 * fs + o] = (x2e * r1s) * tp;
-    f[6 * fs + o] = (r1e * x2s) * tp;
-    f[7 * fs + o] = (x1e * r2s) * tp;
+    cc_fields_at(f, X1, X2, R1, R2, defs, bpar, bph, xr, N, L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * TPB + threadIdx.x,
+                 (size_t)L * (L1 * L2 * L3));
 }
 
 // One workgroup per (frequency, listed pair): the eight products of the spectra in the reference's order (term 6 with its operands
@@ -121,34 +78,8 @@ __global__ void __launch_bounds__(TPB) k_cc_fields(double *__restrict__ f, const
 __global__ void __launch_bounds__(TPB) k_cc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, CcReq rq, int Lh, int ndef, int L1,
                                                       int L2, int L3, const double2 *__restrict__ tw, double norm) {
     extern __shared__ double2 lds[];
-    const int nc = L1 * L2 * L3, k = blockIdx.x, p = blockIdx.y;
-    const int n2 = rq.pairs[0][2 * p], n1 = rq.pairs[0][2 * p + 1];               // n″, n′
-    const size_t slice = (size_t)Lh * nc;
-    auto field = [&](int kind, int n) { return nu + ((size_t)kind * ndef + n) * slice + (size_t)k * nc; };
-    const double2 *A0 = field(0, n1), *A1 = field(1, n1), *A4 = field(4, n1), *A7 = field(7, n1);
-    const double2 *B2 = field(2, n2), *B3 = field(3, n2), *B5 = field(5, n2), *B6 = field(6, n2);
-    double2 *P = lds, *Q = lds + nc;
-    for (int q = threadIdx.x; q < nc; q += TPB) {
-        const double2 a0 = A0[q], a1 = A1[q], a4 = A4[q], a7 = A7[q], b2 = B2[q], b3 = B3[q], b5 = B5[q], b6 = B6[q];
-        double re = 0.0, im = 0.0;
-        auto add = [&](double w, const double2 &u, const double2 &v) {           // w · u·conj(v)
-            re += w * (u.x * v.x + u.y * v.y);
-            im += w * (u.y * v.x - u.x * v.y);
-        };
-        add(4.0, a0, b2);
-        add(-4.0, a0, b3);
-        add(-4.0, a1, b2);
-        add(-4.0, a1, b3);
-        add(-2.0, a4, b5);
-        add(2.0, b6, a4);
-        add(2.0, a7, b5);
-        add(-2.0, a7, b6);
-        P[q] = make_double2(re * norm, im * norm);
-    }
-    __syncthreads();
-    const double2 *Pf = dft_cells<true>(P, Q, 1, L1, L2, L3, tw);
-    double2 *y = Y + ((size_t)p * Lh + k) * nc;
-    for (int q = threadIdx.x; q < nc; q += TPB) y[q] = Pf[q];
+    const int nc = L1 * L2 * L3;
+    cc_correlate_slice(Y + ((size_t)blockIdx.y * Lh + blockIdx.x) * nc, nu, rq, blockIdx.y, blockIdx.x, ndef, L1, L2, L3, tw, norm, (size_t)Lh * nc, lds);
 }
 
 // One workgroup per (time slice, listed pair): this slice's part of the four δ sums (header), zero where the orbitals differ.
@@ -156,71 +87,18 @@ __global__ void __launch_bounds__(TPB) k_cc_delta(double *__restrict__ part, CcR
                                                   const int *__restrict__ defs, const double *__restrict__ bpar, const int *__restrict__ bph,
                                                   const double *__restrict__ xr, int N, int L, int ns, int L1, int L2, int L3, int ndef) {
     __shared__ double red[NWAVE];
-    const int nc = L1 * L2 * L3, nb = ndef * nc, t = blockIdx.x, p = blockIdx.y;
-    const int n2 = rq.pairs[0][2 * p], n1 = rq.pairs[0][2 * p + 1];
-    const int *d2 = defs + n2 * DEFW, *d1 = defs + n1 * DEFW;
-    const int d = d2[0], c = d2[1], b = d1[0], a = d1[1];
-    const bool on[NDELTA] = {a == c, a == d, b == c, b == d};
-    int l[NDELTA][3];
-    cc_delta_shifts(l, d1, d2, L1, L2, L3);
-    const double *x1 = X1 + (size_t)t * N, *r1 = R1 + (size_t)t * N;
-    double s[NDELTA] = {0.0, 0.0, 0.0, 0.0};
-    for (int j = threadIdx.x; j < nc; j += TPB) {
-        const double u = cc_hopping(bpar, bph, xr, nb, L, n1 * nc + j, t);
-        const int jp = shifted_cell(j, d1, L1, L2, L3);                           // j + r′
-        if (on[0]) {
-            const int jl = cell_plus(j, l[0][0], l[0][1], l[0][2], L1, L2, L3);
-            s[0] += (x1[j * ns + b] * u) * (r1[jl * ns + d] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + jl, t));
-        }
-        if (on[1]) {
-            const int jl = cell_plus(j, l[1][0], l[1][1], l[1][2], L1, L2, L3);
-            s[1] += (x1[j * ns + b] * u) * (r1[shifted_cell(jl, d2, L1, L2, L3) * ns + c] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + jl, t));
-        }
-        if (on[2]) {
-            const int jl = cell_plus(j, l[2][0], l[2][1], l[2][2], L1, L2, L3);
-            s[2] += (x1[jp * ns + b] * u) * (r1[jl * ns + d] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + jl, t));
-        }
-        if (on[3])
-            s[3] += (x1[jp * ns + a] * u) * (r1[shifted_cell(j, d2, L1, L2, L3) * ns + c] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + j, t));
-    }
-    for (int k = 0; k < NDELTA; ++k) {
-        const double tot = block_sum(s[k], red);
-        if (threadIdx.x == 0) part[((size_t)p * L + t) * NDELTA + k] = tot;
-    }
+    cc_delta_slice(part + (size_t)blockIdx.y * L * NDELTA, rq, blockIdx.y, blockIdx.x, X1, R1, defs, bpar, bph, xr, N, L, ns, L1, L2, L3, ndef, red);
 }
 
 // dl[p][k] = ± 2 (the slices' partials in slice order) / (L nc), one thread per (listed pair, δ term)
 __global__ void __launch_bounds__(TPB) k_cc_delta_finish(double *__restrict__ dl, const double *__restrict__ part, int np, int L, int nc) {
-    const int q = blockIdx.x * TPB + threadIdx.x;
-    if (q >= np * NDELTA) return;
-    const int p = q / NDELTA, k = q % NDELTA;
-    double s = 0.0;
-    for (int t = 0; t < L; ++t) s += part[((size_t)p * L + t) * NDELTA + k];
-    const double v = 2 * s / ((double)L * (double)nc);
-    dl[q] = (k == 1 || k == 2) ? -v : v;
+    cc_delta_finish_at(dl, part, np, L, nc, blockIdx.x * TPB + threadIdx.x);
 }
 
 // One thread per (τ, cell, listed pair): the δ terms at their τ = 0 cells, the τ = β slice J(β, r) = J(0, -r) (:2363-2380).
 __global__ void __launch_bounds__(TPB) k_cc_fold(CcReq rq, const double *__restrict__ B, const double *__restrict__ dl, const int *__restrict__ defs,
                                                  int L, int L1, int L2, int L3) {
-    const int np = rq.np[0], L0 = rq.L0[0], nc = L1 * L2 * L3;
-    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
-    if (idx >= (long long)L0 * nc * np) return;
-    const int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc), p = (int)(idx / ((long long)L0 * nc));
-    const bool beta = (tau == L);
-    const int l1 = cell % L1, l2 = (cell / L1) % L2, l3 = cell / (L1 * L2);
-    const int rc = beta ? ((L1 - l1) % L1) + L1 * (((L2 - l2) % L2) + L2 * ((L3 - l3) % L3)) : cell;
-    double v = B[((size_t)p * L + (beta ? 0 : tau)) * nc + rc];
-    if (beta || tau == 0) {
-        const int *d2 = defs + rq.pairs[0][2 * p] * DEFW, *d1 = defs + rq.pairs[0][2 * p + 1] * DEFW;
-        const int d = d2[0], c = d2[1], b = d1[0], a = d1[1];
-        const bool on[NDELTA] = {a == c, a == d, b == c, b == d};
-        int l[NDELTA][3];
-        cc_delta_shifts(l, d1, d2, L1, L2, L3);
-        for (int k = 0; k < NDELTA; ++k)                                          // in the reference's order
-            if (on[k] && rc == l[k][0] + L1 * (l[k][1] + L2 * l[k][2])) v += dl[p * NDELTA + k];
-    }
-    rq.acc[0][idx] += v;
+    cc_fold_at(rq, (long long)blockIdx.x * TPB + threadIdx.x, B, dl, defs, L, L1, L2, L3, (size_t)L * (L1 * L2 * L3), NDELTA, 0);
 }
 
 int need_ssh_bond(elph_handle_s *h) { return corr_need(h->ssh_bond, "elph_ssh_bond_create"); }
@@ -276,52 +154,14 @@ extern "C" int elph_ssh_bond_create(elph_handle h, int n_def, const int *o1, con
     std::vector<int> defs;
     RC(bc_defs_table(defs, WORDS, g, n_def, o1, o2, v));
     const int L = (int)h->L, Lh = L / 2 + 1, nc = g.nc;
-    // the request arrays come as [BondBond, CurrentCurrent, BondPairGreens], the pair lists of the measured ones one after another: split
-    // into the two plans (pure: a bad request fails before anything is allocated)
-    size_t at[NREQ + 1] = {0, 0, 0, 0};
-    for (int c = 0; c < NREQ; ++c) at[c + 1] = at[c] + (size_t)((measure[c] && npairs[c] > 0) ? npairs[c] : 0);
-    std::vector<int> bpairs;
-    if (pairs) {
-        bpairs.assign(pairs + 2 * at[REQ_BONDBOND], pairs + 2 * at[REQ_BONDBOND + 1]);
-        bpairs.insert(bpairs.end(), pairs + 2 * at[REQ_BONDPAIR], pairs + 2 * at[REQ_BONDPAIR + 1]);
-    }
-    const int bm[NBOND] = {measure[REQ_BONDBOND], measure[REQ_BONDPAIR]}, bt[NBOND] = {time_dependent[REQ_BONDBOND], time_dependent[REQ_BONDPAIR]};
-    const int bn[NBOND] = {npairs[REQ_BONDBOND], npairs[REQ_BONDPAIR]};
-    CorrPlan<NBOND> bplan;
-    RC(corr_plan(bplan, WORDS, BOND_NAMES, bm, bt, bn, pairs ? bpairs.data() : nullptr, n_def, L, nc, 0));
+    CorrPlan<NBOND> bplan;                             // request bookkeeping before anything is allocated
     CorrPlan<1> cplan;
-    RC(corr_plan(cplan, WORDS, CC_NAMES, measure + REQ_CURRENT, time_dependent + REQ_CURRENT, npairs + REQ_CURRENT,
-                 pairs ? pairs + 2 * at[REQ_CURRENT] : nullptr, n_def, L, nc, 0));
+    RC(cc_split_plans(bplan, cplan, WORDS, measure, time_dependent, npairs, pairs, n_def, L, nc));
     const int np = cplan.req.np[0];
     const size_t nb = (size_t)n_def * nc;
     std::vector<int> bph;
     std::vector<double> bpar;
-    if (np) {
-        if (Nbonds < 0 || Nbonds != h->nb || !t || !bond_to_definition || !bond_to_phonon || Nph < 0 || Nph > 0x7fffffff / (int64_t)(L + 1) ||
-            (Nph > 0 && (!alpha || !alpha2))) {
-            elph_set_error("%s: CurrentCurrent: %lld bonds (the handle has %lld) carrying %lld phonons, or a null bond or phonon array", WORDS.prefix,
-                           (long long)Nbonds, (long long)h->nb, (long long)Nph);
-            return ELPH_E_ARG;
-        }
-        if ((size_t)Nbonds != nb) {
-            elph_set_error("%s: CurrentCurrent needs Nbonds = n_def x ncells bonds; %lld bonds are not %d definitions x %d cells (the reference's "
-                           "reshape of t' to (Ltau, L1, L2, L3, n_def) fails)", WORDS.prefix, (long long)Nbonds, n_def, nc);
-            return ELPH_E_UNSUPPORTED;
-        }
-        bph.assign(nb, -1);
-        bpar.assign((size_t)NHPAR * nb, 0.0);
-        for (size_t b = 0; b < nb; ++b) {
-            const int64_t d = bond_to_definition[b], p = bond_to_phonon[b];
-            if (d < 1 || d > n_def) { elph_set_error("%s: bond %lld belongs to definition %lld, outside 1..%d", WORDS.prefix, (long long)b + 1, (long long)d, n_def); return ELPH_E_ARG; }
-            if (p < 0 || p > Nph) { elph_set_error("%s: bond %lld carries phonon %lld, outside 0..%lld", WORDS.prefix, (long long)b + 1, (long long)p, (long long)Nph); return ELPH_E_ARG; }
-            bpar[b] = t[b];
-            if (p > 0) {
-                bph[b] = (int)p - 1;
-                bpar[nb + b] = alpha[p - 1];
-                bpar[2 * nb + b] = alpha2[p - 1];
-            }
-        }
-    }
+    if (np) RC(cc_check_params(h, WORDS.prefix, n_def, nc, Nbonds, t, bond_to_definition, bond_to_phonon, Nph, alpha, alpha2, bph, bpar));
     SshBondState *m = new SshBondState;
     h->ssh_bond = m;
     m->ns = g.ns; m->L1 = g.L1; m->L2 = g.L2; m->L3 = g.L3; m->nc = nc; m->ndef = n_def; m->Nph = Nph;

@@ -24,8 +24,8 @@ this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and e
 alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.  Several chains resident in the handle (a lockstep
 run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure_chains.hip): one container per chain, all
 chains in the same launches; the functions here keep refusing them.  The bond correlations of the chains are
-chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure_chains.hip), except its
-bond correlations BondBond, CurrentCurrent and BondPairGreens, which stay refused over chains.
+chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure_chains.hip), its bond
+correlations BondBond, CurrentCurrent and BondPairGreens over chains by ssh_chain_bond_measurements.py (csrc/ssh_bondcorr_chains.hip).
 
 One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
 The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,

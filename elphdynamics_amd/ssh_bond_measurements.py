@@ -25,7 +25,8 @@ here r'' is reduced mod L.  The reshape of t' to (Ltau, L1, L2, L3, n_def) (:214
 refuses a CurrentCurrent request there (ELPH_E_UNSUPPORTED naming both counts), BondBond and BondPairGreens stay available.
 
 Scope.  Refused with UnsupportedMeasurement naming the request: a Holstein model (bond_measurements.py measures it), several chains
-resident, a request on a model without bond definitions; sharded and slab handles are refused by the library.
+resident (ssh_chain_bond_measurements.py measures them, all chains in the same launches), a request on a model without bond definitions;
+sharded and slab handles are refused by the library.
 """
 import numpy as np
 
@@ -47,16 +48,18 @@ class SSHBondContainer:
         self._device_of = None           # the model whose handle holds the device side
 
 
-def _refuse_model(model):
+def _refuse_holstein(model):
     if getattr(model, "kind", None) != 1:
         raise UnsupportedMeasurement("%s of the Holstein model are not supported (SSH only; see bond_measurements.py)" % SUBJECT)
+
+
+def _refuse_model(model):
+    _refuse_holstein(model)
     _refuse_chains(model, SUBJECT)
 
 
-def initialize_ssh_bond_container(model, info, datafolder):
-    """The BondBond, CurrentCurrent, BondPairGreens and BondPairSusc part of initialize_measurements_container(ssh, info, datafolder)
-    (:295-302, :322)."""
-    _refuse_model(model)
+def _new_ssh_bond_container(model, info, datafolder):
+    """The container of one configuration for the request `info`, after the caller has decided that the model is measured."""
     info = info or {}
     defs = [(int(d["o1"]), int(d["o2"]), tuple(int(k) for k in d["v"])) for d in getattr(model, "bond_definitions", [])]
     dims = (model.lattice.L1, model.lattice.L2, model.lattice.L3)
@@ -72,16 +75,21 @@ def initialize_ssh_bond_container(model, info, datafolder):
     return c
 
 
+def initialize_ssh_bond_container(model, info, datafolder):
+    """The BondBond, CurrentCurrent, BondPairGreens and BondPairSusc part of initialize_measurements_container(ssh, info, datafolder)
+    (:295-302, :322)."""
+    _refuse_model(model)
+    return _new_ssh_bond_container(model, info, datafolder)
+
+
 def initialize_ssh_bond_folders_(container):
     """The inter-site parts of initialize_measurement_folders!(container) (:420-540)."""
     _group_folders(container.datafolder, container.intersite_corr, container.intersite_susc, "bond1", "bond2")
 
 
-def _ensure_device(container, model, Gr):
-    if container._device_of is model:
-        return
-    _refuse_model(model)
-    _check_estimator(container, model, Gr)
+def _create_args(container, model):
+    """The arguments of elph_ssh_bond_create after the handle and of elph_ssh_bond_chains_create after nchains: the bond definitions, the
+    bonds and phonons of the model, the request.  Second value: the arrays the pointers refer to, to be kept alive across the call."""
     defs = container.bond_definitions
     o1, o2 = _i32([d[0] for d in defs] or [0]), _i32([d[1] for d in defs] or [0])
     v = _i32([k for d in defs for k in d[2]] or [0, 0, 0])
@@ -91,9 +99,18 @@ def _ensure_device(container, model, Gr):
     nb, nph_tot = int(model.Nbonds), int(model.Nph)
     t, b2d, b2p = f64(model.t), i64(model.bond_to_definition), i64(model.bond_to_phonon)
     al, al2 = f64(model.alpha), f64(model.alpha2)
-    check(model._lib.elph_ssh_bond_create(model._h, len(defs), _ip(o1), _ip(o2), _ip(v), nb, dptr(t) if nb else None, iptr(b2d) if nb else None,
-                                          iptr(b2p) if nb else None, nph_tot, dptr(al) if nph_tot else None, dptr(al2) if nph_tot else None,
-                                          *map(_ip, request)))
+    args = [len(defs), _ip(o1), _ip(o2), _ip(v), nb, dptr(t) if nb else None, iptr(b2d) if nb else None, iptr(b2p) if nb else None, nph_tot,
+            dptr(al) if nph_tot else None, dptr(al2) if nph_tot else None] + [_ip(a) for a in request]
+    return args, (o1, o2, v, t, b2d, b2p, al, al2, request)
+
+
+def _ensure_device(container, model, Gr):
+    if container._device_of is model:
+        return
+    _refuse_model(model)
+    _check_estimator(container, model, Gr)
+    args, keep = _create_args(container, model)
+    check(model._lib.elph_ssh_bond_create(model._h, *args))
     container._device_of = model
 
 
@@ -121,7 +138,11 @@ def process_ssh_bond_measurements_(container, bin_size, model):
     """The inter-site parts of process_measurements!(container, sim_params, model) (:574-676): fetch, momentum = fft over the cell axes,
     division by bin_size * binomial(n_rand_vecs, 2), Simpson's rule over tau for BondPairSusc (:666-672)."""
     fetch_ssh_bonds_(container, model)
-    _process_group(container.intersite_corr, container.intersite_susc, SSH_BOND_SUSC_OF, _bin_volume(container, bin_size), model.dtau)
+    _process_fetched(container, bin_size, model.dtau)
+
+
+def _process_fetched(container, bin_size, dtau):
+    _process_group(container.intersite_corr, container.intersite_susc, SSH_BOND_SUSC_OF, _bin_volume(container, bin_size), dtau)
 
 
 def write_ssh_bond_measurements_(container, model, bin):

@@ -650,9 +650,10 @@ int elph_ssh_meas_chains_reset(elph_handle h);
  *   measure, time_dependent, npairs   int[3] in the order BondBond, CurrentCurrent, BondPairGreens
  *   pairs                       as elph_bond_create: the measured ones' lists one after the other in that order
  * ELPH_E_ARG (an orbital outside 1..n_s, a bond index outside 1..n_def, a definition or phonon outside its range, a bond count that is
- * not the handle's) and ELPH_E_UNSUPPORTED (Holstein model, several chains resident, a sharded or slab handle, a lattice whose frequency
- * slice does not fit the LDS, CurrentCurrent requested with Nbonds != n_def * ncells, where the reference's reshape of t' fails; BondBond
- * and BondPairGreens stay available there) leave the handle without these accumulators and usable. */
+ * not the handle's) and ELPH_E_UNSUPPORTED (Holstein model, several chains resident: elph_ssh_bond_chains_create measures those, a sharded
+ * or slab handle, a lattice whose frequency slice does not fit the LDS, CurrentCurrent requested with Nbonds != n_def * ncells, where the
+ * reference's reshape of t' fails; BondBond and BondPairGreens stay available there) leave the handle without these accumulators and
+ * usable. */
 int elph_ssh_bond_create(elph_handle h, int n_def, const int *o1, const int *o2, const int *v, int64_t Nbonds, const double *t,
                          const int64_t *bond_to_definition, const int64_t *bond_to_phonon, int64_t Nph, const double *alpha,
                          const double *alpha2, const int *measure, const int *time_dependent, const int *npairs, const int *pairs);
@@ -669,6 +670,56 @@ int elph_ssh_bond_fetch(elph_handle h, double *BondBond, double *CurrentCurrent,
 
 /* reset_measurements! (Measurements.jl:698-758) for the three correlations: every accumulator to zero (stream-ordered). */
 int elph_ssh_bond_reset(elph_handle h);
+
+/* ---------------------------------------------------------------- inter-site correlations of resident chains (bond-phonon (SSH) model) */
+
+/* elph_ssh_bond_create for every chain resident in the handle (elph_update_model_ssh_fields_chains, elph_hmc_create_ssh_chains): the
+ * accumulators of BondBond, CurrentCurrent and BondPairGreens of every chain, [chain][BondBond | BondPairGreens] in one device allocation
+ * and [chain][CurrentCurrent] in another, the buffers of one pair of vectors of all chains, the fields of all chains, and the scratch in
+ * which the estimator's setup! (GreensFunctions.jl:239-288) runs for one pair of vectors of all chains at once.  It stands beside the
+ * containers of elph_ssh_bond_create and elph_ssh_meas_chains_create in a slot of its own.  Needs elph_greens_create first; a new
+ * elph_greens_create drops it.  The estimator serves the chains with n_v * nchains vectors, vector v of chain c at index v * nchains + c
+ * (0-based).  Arguments as elph_ssh_bond_create (request order BondBond, CurrentCurrent, BondPairGreens), and
+ *   nchains   >= 1 and equal to the number of chains resident in the handle
+ * The bonds, the phonon parameters and the requests are the model's and serve every chain.  Checked in this order, before anything is
+ * allocated; a refused request leaves the handle without this container and usable:
+ *   ELPH_E_UNSUPPORTED   the Holstein model ("SSH only"); a sharded or slab handle
+ *   ELPH_E_ARG           nchains < 1 or not the resident number (the message names both)
+ *   ELPH_E_STATE         elph_greens_create has not been called
+ *   ELPH_E_ARG / ELPH_E_UNSUPPORTED   as elph_ssh_bond_create: n_def < 1 or a null array, an orbital outside 1..n_s, a lattice whose
+ *                        frequency slice does not fit the LDS, a measured correlation without pairs, a bond index outside 1..n_def; for
+ *                        CurrentCurrent a bond count that is not the handle's, Nbonds != n_def * ncells (ELPH_E_UNSUPPORTED; BondBond and
+ *                        BondPairGreens alone stay available there), a definition or phonon outside its range
+ *   ELPH_E_UNSUPPORTED   a request whose grids would exceed 65535 in y or z: (fields transformed: 8 for CurrentCurrent, 4 for BondBond +
+ *                        2 for BondPairGreens, the larger of the two) * n_def * nchains slices, or (listed pairs of CurrentCurrent, or of
+ *                        the other two together, the larger) * nchains transforms (the message says which product)
+ *   ELPH_E_HIP           an allocation failed */
+int elph_ssh_bond_chains_create(elph_handle h, int nchains, int n_def, const int *o1, const int *o2, const int *v, int64_t Nbonds,
+                                const double *t, const int64_t *bond_to_definition, const int64_t *bond_to_phonon, int64_t Nph,
+                                const double *alpha, const double *alpha2, const int *measure, const int *time_dependent, const int *npairs,
+                                const int *pairs);
+
+/* measure_BondBond! / measure_CurrentCurrent! / measure_BondPairGreens! for every pair v1 < v2 of a chain's n_v vectors, of every chain.
+ * X is double[nchains * Nph * L_tau] (host), chain c's model.x (phonon slowest) at X + c * Nph * L_tau, from which CurrentCurrent
+ * recomputes chain c's t'; it may be NULL when CurrentCurrent is not requested or Nph = 0.  One asynchronous copy of X, then per pair of
+ * vectors the device part of setup! and the kernels of the three correlations run once for all chains (the chain is a grid axis: the
+ * number of launches does not depend on nchains), stream-ordered, with one synchronisation before the call returns (X is not retained).
+ * Sums as elph_ssh_bond_accumulate: one fixed order, no atomics, the same inputs give the same bits; chain c's numbers depend on chain
+ * c's vectors and field alone.  The estimator's own tables (elph_greens_dev_arrays) are not touched.
+ *   ELPH_E_STATE   elph_ssh_bond_chains_create has not been called; the handle no longer holds the number of chains the container was
+ *                  created for (the message names both counts); the estimator's vectors are not a multiple of it; the estimator holds
+ *                  no vectors yet
+ *   ELPH_E_ARG     X is NULL although CurrentCurrent is requested and Nph > 0 */
+int elph_ssh_bond_chains_accumulate(elph_handle h, const double *X);
+
+/* One chain's un-normalised sums since the last reset: the outputs of elph_ssh_bond_fetch for chain `chain` (0-based).  One
+ * device-to-host copy and one synchronisation per accumulator allocation.  ELPH_E_STATE: not created; ELPH_E_ARG: a chain outside
+ * 0..nchains-1. */
+int elph_ssh_bond_chains_fetch(elph_handle h, int chain, double *BondBond, double *CurrentCurrent, double *BondPairGreens);
+
+/* reset_measurements! (Measurements.jl:698-758) for the three correlations of every chain: one memset per accumulator allocation
+ * (stream-ordered).  ELPH_E_STATE: not created. */
+int elph_ssh_bond_chains_reset(elph_handle h);
 
 /* ---------------------------------------------------------------- KPM preconditioner */
 
