@@ -165,6 +165,7 @@ void elph_greens_free(elph_handle_s *h) {
     elph_ssh_meas_chains_free(h);
     elph_ssh_bond_free(h);
     elph_ssh_bond_chains_free(h);
+    elph_density_moments_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;
     void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};
@@ -355,6 +356,7 @@ int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
     v->ns = g->ns; v->L1 = g->L1; v->L2 = g->L2; v->L3 = g->L3; v->nc = g->nc; v->nv = g->nv;
     v->have_vectors = g->have_vectors;
     v->C = g->C; v->tw = g->tw;
+    v->R = g->R; v->X = g->X;
     return ELPH_OK;
 }
 

@@ -471,6 +471,25 @@ int elph_meas_chains_fetch(elph_handle h, int chain, double *scalars, double *Gr
 /* reset_measurements! (Measurements.jl:698-758) of every chain: one memset (stream-ordered). */
 int elph_meas_chains_reset(elph_handle h);
 
+/* ---------------------------------------------------------------- density moments for the chemical-potential tuner (MuFinder.jl) */
+
+/* <N> and <N^2> of every resident chain from the estimator's vectors, as update_mu! measures them for its tuner (MuFinder.jl:77-97;
+ * measure_density and measure_N2, Measurements.jl:1283-1312), averaged over the binomial(n_v, 2) pairs of a chain's n_v vectors.  No setup!:
+ * with C_pq(tau) = sum_site (M^-1 r_p)[site, tau] r_q[site, tau] the pair's T_p = (1/L) sum_tau C_pp(tau), N_p = 2 (N - T_p) and
+ * N^2_pq = N_p N_q + T_p + T_q - (2/L) sum_tau C_pq(tau) C_qp(tau), the table's sum over every displacement at equal time, slice by slice.
+ * One pass over R and M^-1 R on the handle's stream (two launches, stream-ordered), one device-to-host copy of 2 nchains doubles, one
+ * synchronisation.  Holstein and SSH handles alike: only the vectors, nsites and L_tau enter.  Vector v of chain c is row v * nchains + c
+ * (0-based) of the estimator.  Fixed summation order, no atomics: the same inputs give the same bits, and chain c's numbers depend on chain
+ * c's rows alone.  The scratch (nchains L_tau n_v^2 doubles) is made on first use, regrown when the shape grows, dropped by
+ * elph_greens_create and freed by elph_destroy.
+ *   nchains   the number of chains resident in the handle (1 for one configuration); ELPH_E_ARG otherwise, naming both counts
+ *   N, Nsqr   double[nchains] each
+ *   ELPH_E_STATE         elph_greens_create has not been called; the estimator holds no vectors yet; its vector count is not a multiple
+ *                        of nchains, or leaves a chain fewer than two vectors
+ *   ELPH_E_UNSUPPORTED   a sharded or slab handle
+ * A refused call leaves the handle usable. */
+int elph_density_moments(elph_handle h, int nchains, double *N, double *Nsqr);
+
 /* ---------------------------------------------------------------- bond correlations (Holstein model; Measurements.jl) */
 
 /* The device side of the inter-site correlation group of a measurements container (init_corr_container!, Measurements.jl:156-175,
