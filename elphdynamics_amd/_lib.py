@@ -92,6 +92,7 @@ SIGNATURES = {
     "elph_meas_chains_fetch": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl]),
     "elph_meas_chains_reset": (c_int, [Handle]),
     "elph_density_moments": (c_int, [Handle, c_int, P_dbl, P_dbl]),
+    "elph_snapshots": (c_int, [Handle, c_int, P_dbl, P_dbl]),
     "elph_bond_create": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int, P_int, P_int, P_int]),
     "elph_bond_accumulate": (c_int, [Handle]),
     "elph_bond_fetch": (c_int, [Handle, P_dbl, P_dbl]),

@@ -23,7 +23,7 @@ The device side is shaped by the estimator and dropped by the library when a new
 sums it held): the next accumulate_ with the new estimator makes it again, with the mu given then (or model.mu).
 
 Scope: what measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the SSH model,
-BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true — the SSH model over chains is
+BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them for every chain, in a container of its own) — the SSH model over chains is
 ssh_chain_measurements.py's (its bond correlations over chains ssh_chain_bond_measurements.py's); BondBond, BondPairGreens and BondPairSusc of the chains are chain_bond_measurements.py's, whose container is used beside
 this one on the same model and estimator, in either order.  measurements.py itself keeps refusing resident chains.
 """

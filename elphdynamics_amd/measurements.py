@@ -18,7 +18,8 @@ Arrays keep the reference's shapes in Fortran order (Julia's memory image): a co
 susceptibility's are (L1, L2, L3, n_p).
 
 Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
-BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, the SSH model, several chains resident in the handle;
+BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them, in a container of its own: snapshots.split_info splits the
+table), the SSH model, several chains resident in the handle;
 sharded and slab handles are refused by the library.  BondBond, BondPairGreens and BondPairSusc live in a container of their own beside
 this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent is measured for the SSH model
 alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.  Several chains resident in the handle (a lockstep

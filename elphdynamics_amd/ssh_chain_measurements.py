@@ -25,7 +25,7 @@ sums it held): the next accumulate_ with the new estimator makes it again, with 
 
 Scope: what ssh_measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the Holstein
 model (chain_measurements.py measures it), BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry
-set to true.  The SSH bond correlations over chains live in a container of their own beside this one (ssh_chain_bond_measurements.py,
+set to true (snapshots.py takes them for every chain, in a container of its own).  The SSH bond correlations over chains live in a container of their own beside this one (ssh_chain_bond_measurements.py,
 csrc/ssh_bondcorr_chains.hip), used on the same model and estimator, in either order.  ssh_measurements.py itself keeps refusing
 resident chains.
 """

@@ -18,7 +18,7 @@ inter-site PhononGreens over pairs of phonon types 1..nph (:2488-2541; all nph^2
 (:291-293).  pairs[0, p] = b1, pairs[1, p] = b2: PhononGreens[D] = 1/(L Nc) sum x_b2[. + D] x_b1[.].
 
 Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
-BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true, a Holstein model, several chains resident in the
+BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them, in a container of its own), a Holstein model, several chains resident in the
 handle; sharded and slab handles, and PhononGreens on a lattice where Nph != nph * ncells (the reference's reshape of the field
 throws), are refused by the library.  BondBond, CurrentCurrent, BondPairGreens and BondPairSusc live in a container of their own beside
 this one (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), used on the same model and estimator.  Several chains resident in the handle

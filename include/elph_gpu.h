@@ -490,6 +490,30 @@ int elph_meas_chains_reset(elph_handle h);
  * A refused call leaves the handle usable. */
 int elph_density_moments(elph_handle h, int nchains, double *N, double *Nsqr);
 
+/* ---------------------------------------------------------------- snapshots (make_snapshot_measurements!, Measurements.jl) */
+
+/* The density and double-occupancy snapshots of every resident chain from the estimator's vectors: the per-site profiles
+ * take_density_snapshot! and take_double_occupancy_snapshot! write to one file per measurement (Measurements.jl:1351-1435).  With R and
+ * M^-1 R viewed as (L_tau, nsites, n_v) and d_n(tau, i) = 1 - M^-1R[tau, i, n] R[tau, i, n]:
+ *   density[i]          = sum_tau sum_{n = 1..n_v} 2 d_n                          / (n_v L_tau)
+ *   double_occupancy[i] = sum_tau sum_{n = 1..n_v - 1} sum_{m = 2..n_v} d_n d_m   / (binomial(n_v, 2) L_tau)
+ * The ranges of n and m are the reference's (:1416-1417): for n_v > 2 they hold n = m terms and both orders of some pairs, and so does
+ * this call, through the double sum's product form (S - d_{n_v}) (S - d_1), S = sum_n d_n, per (tau, i).  One pass over R and M^-1 R on
+ * the handle's stream (two launches, stream-ordered: partial sums over segments of the tau axis, then the segments in order), one
+ * device-to-host copy per requested output, one synchronisation.  Holstein and SSH handles alike: only the vectors, nsites and L_tau
+ * enter.  A chain's n_v is the estimator's vector count / nchains; vector v of chain c is row v * nchains + c (0-based).  Fixed summation
+ * order, no atomics: the same inputs give the same bits; the segments depend on L_tau alone, so chain c's profiles depend on chain c's
+ * rows alone and equal those of a single-configuration handle holding these rows.  The scratch (about nchains nsites L_tau / 2 doubles)
+ * is made on first use, regrown when the shape grows, dropped by elph_greens_create and freed by elph_destroy.
+ *   nchains      the number of chains resident in the handle (1 for one configuration); ELPH_E_ARG otherwise, naming both counts
+ *   density      double[nchains * nsites], chain-major, sites in the handle's order, normalised; NULL: not wanted
+ *   double_occ   the same for the double occupancy; NULL: not wanted.  Both NULL: ELPH_E_ARG
+ *   ELPH_E_STATE         elph_greens_create has not been called; the estimator holds no vectors yet; its vector count is not a multiple
+ *                        of nchains, or leaves a chain fewer than two vectors (binomial(1, 2) = 0: the reference would divide by zero)
+ *   ELPH_E_UNSUPPORTED   a sharded or slab handle
+ * A refused call leaves the handle usable.  (The phonon_position snapshot is the tau-mean of the field the caller holds: host arithmetic.) */
+int elph_snapshots(elph_handle h, int nchains, double *density, double *double_occ);
+
 /* ---------------------------------------------------------------- bond correlations (Holstein model; Measurements.jl) */
 
 /* The device side of the inter-site correlation group of a measurements container (init_corr_container!, Measurements.jl:156-175,
