@@ -122,6 +122,10 @@ SIGNATURES = {
     "elph_ssh_bond_chains_accumulate": (c_int, [Handle, P_dbl]),
     "elph_ssh_bond_chains_fetch": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl]),
     "elph_ssh_bond_chains_reset": (c_int, [Handle]),
+    "elph_current_create": (c_int, [Handle, c_int, c_int, P_int, P_int, P_int, c_i64, P_dbl, c_int, c_int, c_int, P_int]),
+    "elph_current_accumulate": (c_int, [Handle]),
+    "elph_current_fetch": (c_int, [Handle, c_int, P_dbl]),
+    "elph_current_reset": (c_int, [Handle]),
     "elph_hmc_create_ssh": (c_int, [Handle, c_i64, P_dbl, P_dbl, P_i64, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, P_dbl]),
     "elph_hmc_create_ssh_chains": (c_int, [Handle, c_int, c_i64, P_dbl, P_dbl, P_i64, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, P_dbl]),
     "elph_hmc_create_chains": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, c_dbl, P_dbl]),

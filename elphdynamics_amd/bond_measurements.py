@@ -17,9 +17,10 @@ constructor makes no library call; the device side (elph_bond_create) is made by
 Arrays as in measurements.py: `position` and `momentum` complex128 (L0, L1, L2, L3, n_p) in Fortran order, `pairs` int (2, n_p) of 1-based
 bond-definition indices: pairs[0, p] is the bond at the origin (n'' of the reference), pairs[1, p] the displaced one (n').
 
-Scope.  CurrentCurrent with measure = true is refused with UnsupportedMeasurement: the reference's Holstein method scales its fields by
-the hopping inside `for tau in L_tau`, which visits the last time slice alone, and whether to mirror that is undecided.  So are a request
-on a model without bond definitions, the SSH model (ssh_bond_measurements.py measures its BondBond, CurrentCurrent and BondPairGreens)
+Scope.  CurrentCurrent with measure = true is refused here with UnsupportedMeasurement (the message is from before the question it
+names was settled): current_measurements.py measures it, in a container of its own beside this one, mirroring the reference's Holstein
+method as it executes (it scales its fields by the hopping inside `for tau in L_tau`, which visits the last time slice alone);
+current_measurements.split_info hands this constructor the table without that entry.  Refused too are a request on a model without bond definitions, the SSH model (ssh_bond_measurements.py measures its BondBond, CurrentCurrent and BondPairGreens)
 and several chains resident (chain_bond_measurements.py measures every resident chain at once); sharded and slab handles are refused by
 the library.
 """

@@ -25,7 +25,8 @@ The device side is shaped by the estimator and dropped by the library when a new
 sums it held): the next accumulate_bonds_ with the new estimator makes it again.
 
 Scope: what bond_measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request:
-CurrentCurrent with measure = true, the SSH model, a request on a model without bond definitions.  bond_measurements.py itself keeps
+CurrentCurrent with measure = true (current_measurements.py measures it for every resident chain, in a container of its own beside this
+one; its split_info hands this constructor the table without that entry), the SSH model, a request on a model without bond definitions.  bond_measurements.py itself keeps
 refusing resident chains; sharded and slab handles are refused by the library.
 """
 from . import bond_measurements as _bm

@@ -1,11 +1,21 @@
-// currcorr_dev.h — what the two CurrentCurrent units share (ssh_bondcorr.hip: one configuration, ssh_bondcorr_chains.hip: every resident
-// chain at once): the bodies of the kernels of
-//   measure_CurrentCurrent!(ssh)     Measurements.jl:2100-2384
-// and the checks of the bond and phonon parameters both create calls make.  One text of each kernel body; the formulas, the eight fields
-// A0 .. A7 and the four δ terms are in ssh_bondcorr.hip's header.  As in bondcorr_dev.h the buffers carry the chain between the definition
-// (or listed pair) and the time axis — f: [NCC][ndef][chain][L][nc], nu the same with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc],
-// part: [pair][chain][L][NDELTA], dl: [pair][chain][NDELTA] — so a body takes its chain's block of definition (pair) 0 and the distance
-// between two definitions (pairs); with one configuration that distance is the block itself.
+// currcorr_dev.h — what the three CurrentCurrent units share (ssh_bondcorr.hip: the SSH model, one configuration; ssh_bondcorr_chains.hip:
+// the SSH model, every resident chain at once; currcorr.hip: the Holstein model, one configuration or every resident chain): the bodies
+// of the kernels of
+//   measure_CurrentCurrent!(ssh)        Measurements.jl:2100-2384
+//   measure_CurrentCurrent!(holstein)   Measurements.jl:1790-2098
+// and the checks of the bond and phonon parameters the create calls make.  One text of each kernel body; the formulas, the eight fields
+// A0 .. A7 and the four δ terms are in ssh_bondcorr.hip's header.  The two methods differ in the hopping that weights every factor and
+// in nothing else, so the bodies that weight take the weight of (bond, slice) as a policy W, `double W::operator()(int bond, int t)`:
+// CcModulated for the SSH model, CcLastSlice for the Holstein model.
+// One difference between the units is deliberate and lies outside the bodies: cc_fold_at adds into whatever block rq.acc names.  The two
+// SSH units bind it to the accumulator itself; currcorr.hip binds it to a second block that it zeroes per accumulate and adds to the
+// accumulator once (k_cur_add), because its contract promises that the same accumulate twice is EXACTLY twice the first, where the SSH
+// units promise that up to rounding (their tests hold 4 eps).  Do not align one with the other without changing that contract and its
+// tests.
+// As in bondcorr_dev.h the buffers carry the chain between the definition (or listed pair) and the time axis — f: [NCC][ndef][chain][L][nc],
+// nu the same with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc], part: [pair][chain][L][NDELTA], dl: [pair][chain][NDELTA] — so a
+// body takes its chain's block of definition (pair) 0 and the distance between two definitions (pairs); with one configuration that
+// distance is the block itself.
 #pragma once
 
 #include <vector>
@@ -22,13 +32,27 @@ constexpr int NHPAR = 3;              // per bond: t, alpha, alpha2 (zeros on a 
 
 using CcReq = CorrReq<1>;
 
-// t′ of bond `bond` = cell + nc n on slice t
-__device__ __forceinline__ double cc_hopping(const double *__restrict__ bpar, const int *__restrict__ bph, const double *__restrict__ xr,
-                                             int nb, int L, int bond, int t) {
-    const int ph = bph[bond];
-    const double t0 = bpar[bond];
-    return ph < 0 ? t0 : t_modulated(t0, bpar[nb + bond], bpar[2 * nb + bond], xr[(size_t)ph * L + t]);
-}
+// The SSH model's weight: t′ of bond `bond` = cell + nc n on slice t, the modulated hopping recomputed from the field.  bpar [NHPAR][nb],
+// bph [nb], xr [Nph][L]: the tables of cc_check_params and the (chain's) field.
+struct CcModulated {
+    const double *__restrict__ bpar;
+    const int *__restrict__ bph;
+    const double *__restrict__ xr;
+    int nb, L;
+    __device__ __forceinline__ double operator()(int bond, int t) const {
+        const int ph = bph[bond];
+        const double t0 = bpar[bond];
+        return ph < 0 ? t0 : t_modulated(t0, bpar[nb + bond], bpar[2 * nb + bond], xr[(size_t)ph * L + t]);
+    }
+};
+
+// The Holstein model's weight, as the reference executes it: the static model.t of bond `bond` = cell + nc n on the LAST time slice and
+// 1 on every other one (Measurements.jl:1868-1871 and its twins: `for τ in Lₜ` visits Lₜ alone).  t0 [nb].
+struct CcLastSlice {
+    const double *__restrict__ t0;
+    int L;
+    __device__ __forceinline__ double operator()(int bond, int t) const { return t == L - 1 ? t0[bond] : 1.0; }
+};
 
 // The displacements l of the four δ terms (header) from the reduced shifts of n′ (d1) and n″ (d2).
 __device__ __forceinline__ void cc_delta_shifts(int l[NDELTA][3], const int *d1, const int *d2, int L1, int L2, int L3) {
@@ -42,11 +66,12 @@ __device__ __forceinline__ void cc_delta_shifts(int l[NDELTA][3], const int *d1,
 }
 
 // The eight fields of every definition for idx = (cell, τ, definition), first fastest.  f: the chain's block of field 0 of definition 0;
-// dstride: doubles between two definitions; X1 .. R2, xr: the chain's vectors and field.
+// dstride: doubles between two definitions; X1 .. R2: the chain's vectors; w: the (chain's) weight.
+template <class W>
 __device__ __forceinline__ void cc_fields_at(double *__restrict__ f, const double *__restrict__ X1, const double *__restrict__ X2,
                                              const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs,
-                                             const double *__restrict__ bpar, const int *__restrict__ bph, const double *__restrict__ xr, int N,
-                                             int L, int ns, int L1, int L2, int L3, int ndef, long long idx, size_t dstride) {
+                                             const W &w, int N, int L, int ns, int L1, int L2, int L3, int ndef, long long idx,
+                                             size_t dstride) {
     const int nc = L1 * L2 * L3;
     const long long per = (long long)L * nc;
     if (idx >= per * ndef) return;
@@ -55,7 +80,7 @@ __device__ __forceinline__ void cc_fields_at(double *__restrict__ f, const doubl
     const size_t is = (size_t)t * N + (size_t)cell * ns + dv[0];
     const size_t ie = (size_t)t * N + (size_t)shifted_cell(cell, dv, L1, L2, L3) * ns + dv[1];
     const double x1s = X1[is], x2s = X2[is], r1s = R1[is], r2s = R2[is], x1e = X1[ie], x2e = X2[ie], r1e = R1[ie], r2e = R2[ie];
-    const double tp = cc_hopping(bpar, bph, xr, ndef * nc, L, n * nc + cell, t);
+    const double tp = w(n * nc + cell, t);
     const size_t fs = (size_t)ndef * dstride, o = (size_t)n * dstride + (size_t)t * nc + cell;
     f[o] = (x1s * r1e) * tp;
     f[fs + o] = (x1e * r1s) * tp;
@@ -101,12 +126,13 @@ __device__ __forceinline__ void cc_correlate_slice(double2 *__restrict__ y, cons
 }
 
 // Time slice t of listed pair p: this slice's part of the four δ sums (header), zero where the orbitals differ, into part[t][NDELTA].
-// part: the [L][NDELTA] block of this pair (of this chain); X1, R1, xr: the chain's vector 1 and field.  red: MEAS_NWAVE doubles of LDS.
+// part: the [L][NDELTA] block of this pair (of this chain); X1, R1: the chain's vector 1; w: the (chain's) weight.  red: MEAS_NWAVE
+// doubles of LDS.
+template <class W>
 __device__ __forceinline__ void cc_delta_slice(double *__restrict__ part, const CcReq &rq, int p, int t, const double *__restrict__ X1,
-                                               const double *__restrict__ R1, const int *__restrict__ defs, const double *__restrict__ bpar,
-                                               const int *__restrict__ bph, const double *__restrict__ xr, int N, int L, int ns, int L1, int L2,
-                                               int L3, int ndef, double *red) {
-    const int nc = L1 * L2 * L3, nb = ndef * nc;
+                                               const double *__restrict__ R1, const int *__restrict__ defs, const W &w, int N, int ns, int L1,
+                                               int L2, int L3, double *red) {
+    const int nc = L1 * L2 * L3;
     const int n2 = rq.pairs[0][2 * p], n1 = rq.pairs[0][2 * p + 1];
     const int *d2 = defs + n2 * DEFW, *d1 = defs + n1 * DEFW;
     const int d = d2[0], c = d2[1], b = d1[0], a = d1[1];
@@ -116,22 +142,22 @@ __device__ __forceinline__ void cc_delta_slice(double *__restrict__ part, const 
     const double *x1 = X1 + (size_t)t * N, *r1 = R1 + (size_t)t * N;
     double s[NDELTA] = {0.0, 0.0, 0.0, 0.0};
     for (int j = threadIdx.x; j < nc; j += MEAS_TPB) {
-        const double u = cc_hopping(bpar, bph, xr, nb, L, n1 * nc + j, t);
+        const double u = w(n1 * nc + j, t);
         const int jp = shifted_cell(j, d1, L1, L2, L3);                           // j + r′
         if (on[0]) {
             const int jl = cell_plus(j, l[0][0], l[0][1], l[0][2], L1, L2, L3);
-            s[0] += (x1[j * ns + b] * u) * (r1[jl * ns + d] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + jl, t));
+            s[0] += (x1[j * ns + b] * u) * (r1[jl * ns + d] * w(n2 * nc + jl, t));
         }
         if (on[1]) {
             const int jl = cell_plus(j, l[1][0], l[1][1], l[1][2], L1, L2, L3);
-            s[1] += (x1[j * ns + b] * u) * (r1[shifted_cell(jl, d2, L1, L2, L3) * ns + c] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + jl, t));
+            s[1] += (x1[j * ns + b] * u) * (r1[shifted_cell(jl, d2, L1, L2, L3) * ns + c] * w(n2 * nc + jl, t));
         }
         if (on[2]) {
             const int jl = cell_plus(j, l[2][0], l[2][1], l[2][2], L1, L2, L3);
-            s[2] += (x1[jp * ns + b] * u) * (r1[jl * ns + d] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + jl, t));
+            s[2] += (x1[jp * ns + b] * u) * (r1[jl * ns + d] * w(n2 * nc + jl, t));
         }
         if (on[3])
-            s[3] += (x1[jp * ns + a] * u) * (r1[shifted_cell(j, d2, L1, L2, L3) * ns + c] * cc_hopping(bpar, bph, xr, nb, L, n2 * nc + j, t));
+            s[3] += (x1[jp * ns + a] * u) * (r1[shifted_cell(j, d2, L1, L2, L3) * ns + c] * w(n2 * nc + j, t));
     }
     for (int k = 0; k < NDELTA; ++k) {
         const double tot = block_sum(s[k], red);
@@ -176,6 +202,14 @@ __device__ __forceinline__ void cc_fold_at(const CcReq &rq, long long idx, const
 
 // ---- host
 
+// CurrentCurrent needs model.t (t′) to reshape to (.., L1, L2, L3, n_def): what every create call answers where it does not.
+inline int cc_check_bond_count(const char *prefix, int n_def, int nc, int64_t Nbonds) {
+    if (Nbonds == (int64_t)n_def * nc) return ELPH_OK;
+    elph_set_error("%s: CurrentCurrent needs Nbonds = n_def x ncells bonds; %lld bonds are not %d definitions x %d cells (the reference's "
+                   "reshape of t' to (Ltau, L1, L2, L3, n_def) fails)", prefix, (long long)Nbonds, n_def, nc);
+    return ELPH_E_UNSUPPORTED;
+}
+
 // What elph_ssh_bond_create and elph_ssh_bond_chains_create check of the bonds and phonons of a CurrentCurrent request before anything
 // is allocated, and the tables they put on the device: bph [n_def nc] 0-based phonon of bond cell + nc n (-1 on a bare bond), bpar
 // [NHPAR][n_def nc] t, alpha, alpha2 (zeros on a bare bond).
@@ -190,11 +224,7 @@ inline int cc_check_params(const elph_handle_s *h, const char *prefix, int n_def
                        (long long)Nbonds, (long long)h->nb, (long long)Nph);
         return ELPH_E_ARG;
     }
-    if ((size_t)Nbonds != nb) {
-        elph_set_error("%s: CurrentCurrent needs Nbonds = n_def x ncells bonds; %lld bonds are not %d definitions x %d cells (the reference's "
-                       "reshape of t' to (Ltau, L1, L2, L3, n_def) fails)", prefix, (long long)Nbonds, n_def, nc);
-        return ELPH_E_UNSUPPORTED;
-    }
+    RC(cc_check_bond_count(prefix, n_def, nc, Nbonds));
     bph.assign(nb, -1);
     bpar.assign((size_t)NHPAR * nb, 0.0);
     for (size_t b = 0; b < nb; ++b) {

@@ -381,6 +381,7 @@ struct elph_handle_s {
     void *ssh_bond_chains = nullptr;       // SshBondChainsState (ssh_bondcorr_chains.hip), owned; freed with greens
     void *density_moments = nullptr;       // DensityMomentsState (density_moments.hip), owned; freed with greens
     void *snapshots = nullptr;             // SnapshotsState (snapshots.hip), owned; freed with greens
+    void *current = nullptr;               // CurrentState (currcorr.hip), owned; freed with greens
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
     // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
     // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
@@ -470,12 +471,13 @@ void elph_ssh_bond_free(elph_handle_s *h);                                  // s
 void elph_ssh_bond_chains_free(elph_handle_s *h);                           // ssh_bondcorr_chains.hip
 void elph_density_moments_free(elph_handle_s *h);                           // density_moments.hip
 void elph_snapshots_free(elph_handle_s *h);                                 // snapshots.hip
+void elph_current_free(elph_handle_s *h);                                   // currcorr.hip
 // greens.hip internals used by the measurement units
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;
     bool have_vectors;
     const double *C;           // [4][L][ns*N] the real correlations of the last elph_i_greens_setup_dev
-    const double *R, *X;       // [nv][ndim] layout S: the noise vectors and M⁻¹R (density_moments.hip and snapshots.hip read them in place)
+    const double *R, *X;       // [nv][ndim] layout S: the noise vectors and M⁻¹R (density_moments.hip, snapshots.hip and currcorr.hip read them in place)
     const double2 *tw;         // [L1 + L2 + L3] exp(-2πi j/Lx), the twiddles of the cell-axis DFTs
 };
 int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v);

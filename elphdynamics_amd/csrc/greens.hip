@@ -167,6 +167,7 @@ void elph_greens_free(elph_handle_s *h) {
     elph_ssh_bond_chains_free(h);
     elph_density_moments_free(h);
     elph_snapshots_free(h);
+    elph_current_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;
     void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};

@@ -29,7 +29,8 @@
 //
 // State: the handle's slot ssh_bond.  BondBond and BondPairGreens live in a BondState of bondcorr_dev.h (made when one of them is
 // requested), CurrentCurrent in an accumulator and scratch of this unit's.  The bodies of the CurrentCurrent kernels are in
-// currcorr_dev.h, shared with ssh_bondcorr_chains.hip (every resident chain at once); the kernels here are thin wrappers over them.
+// currcorr_dev.h, shared with ssh_bondcorr_chains.hip (every resident chain at once) and, under another hopping weight, with currcorr.hip
+// (the Holstein model's method, :1790-2098); the kernels here are thin wrappers over them with the weight CcModulated.
 
 #include <vector>
 
@@ -69,8 +70,8 @@ __global__ void __launch_bounds__(TPB) k_cc_fields(double *__restrict__ f, const
                                                    const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs,
                                                    const double *__restrict__ bpar, const int *__restrict__ bph, const double *__restrict__ xr,
                                                    int N, int L, int ns, int L1, int L2, int L3, int ndef) {
-    cc_fields_at(f, X1, X2, R1, R2, defs, bpar, bph, xr, N, L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * TPB + threadIdx.x,
-                 (size_t)L * (L1 * L2 * L3));
+    cc_fields_at(f, X1, X2, R1, R2, defs, CcModulated{bpar, bph, xr, ndef * (L1 * L2 * L3), L}, N, L, ns, L1, L2, L3, ndef,
+                 (long long)blockIdx.x * TPB + threadIdx.x, (size_t)L * (L1 * L2 * L3));
 }
 
 // One workgroup per (frequency, listed pair): the eight products of the spectra in the reference's order (term 6 with its operands
@@ -87,7 +88,8 @@ __global__ void __launch_bounds__(TPB) k_cc_delta(double *__restrict__ part, CcR
                                                   const int *__restrict__ defs, const double *__restrict__ bpar, const int *__restrict__ bph,
                                                   const double *__restrict__ xr, int N, int L, int ns, int L1, int L2, int L3, int ndef) {
     __shared__ double red[NWAVE];
-    cc_delta_slice(part + (size_t)blockIdx.y * L * NDELTA, rq, blockIdx.y, blockIdx.x, X1, R1, defs, bpar, bph, xr, N, L, ns, L1, L2, L3, ndef, red);
+    cc_delta_slice(part + (size_t)blockIdx.y * L * NDELTA, rq, blockIdx.y, blockIdx.x, X1, R1, defs,
+                   CcModulated{bpar, bph, xr, ndef * (L1 * L2 * L3), L}, N, ns, L1, L2, L3, red);
 }
 
 // dl[p][k] = ± 2 (the slices' partials in slice order) / (L nc), one thread per (listed pair, δ term)

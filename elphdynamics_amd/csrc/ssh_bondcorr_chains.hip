@@ -3,7 +3,7 @@
 // on the vectors per chain and on the request, not on the number of chains.
 //   measure_BondBond!                Measurements.jl:1663-1785     the chain kernels of bondcorr_dev.h, shared with bondcorr_chains.hip
 //   measure_BondPairGreens!          Measurements.jl:2390-2483
-//   measure_CurrentCurrent!(ssh)     Measurements.jl:2100-2384     the bodies of currcorr_dev.h, shared with ssh_bondcorr.hip
+//   measure_CurrentCurrent!(ssh)     Measurements.jl:2100-2384     the bodies of currcorr_dev.h, shared with ssh_bondcorr.hip and currcorr.hip
 // per chain, for every pair of ITS vectors.  What a thread or workgroup computes is ssh_bondcorr.hip's, and so is the rule of the
 // reductions: a thread walks its cells in index order, the lanes of a wave fold by halves, the waves are added in index order through
 // LDS, one partial per time slice, the slices added in slice order; everything else is one thread's sum in index order.  No
@@ -66,8 +66,8 @@ __global__ void __launch_bounds__(TPB) k_ccc_fields(double *__restrict__ f, Elph
                                                     const double *__restrict__ bpar, const int *__restrict__ bph, const double *__restrict__ xr,
                                                     int N, int Nph, int L, int ns, int L1, int L2, int L3, int ndef, int nchains) {
     const size_t ch = blockIdx.y, o = ch * L * N, per = (size_t)L * (L1 * L2 * L3);
-    cc_fields_at(f + ch * per, v.X1 + o, v.X2 + o, v.R1 + o, v.R2 + o, defs, bpar, bph, xr + ch * Nph * L, N, L, ns, L1, L2, L3, ndef,
-                 (long long)blockIdx.x * TPB + threadIdx.x, (size_t)nchains * per);
+    cc_fields_at(f + ch * per, v.X1 + o, v.X2 + o, v.R1 + o, v.R2 + o, defs, CcModulated{bpar, bph, xr + ch * Nph * L, ndef * (L1 * L2 * L3), L}, N,
+                 L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * TPB + threadIdx.x, (size_t)nchains * per);
 }
 
 // One workgroup per (frequency, listed pair, chain).  LDS: 2 buffers of nc complex.
@@ -87,8 +87,8 @@ __global__ void __launch_bounds__(TPB) k_ccc_delta(double *__restrict__ part, Cc
                                                    int nchains) {
     __shared__ double red[NWAVE];
     const size_t ch = blockIdx.z, o = ch * L * N;
-    cc_delta_slice(part + ((size_t)blockIdx.y * nchains + ch) * L * NDELTA, rq, blockIdx.y, blockIdx.x, X1 + o, R1 + o, defs, bpar, bph,
-                   xr + ch * Nph * L, N, L, ns, L1, L2, L3, ndef, red);
+    cc_delta_slice(part + ((size_t)blockIdx.y * nchains + ch) * L * NDELTA, rq, blockIdx.y, blockIdx.x, X1 + o, R1 + o, defs,
+                   CcModulated{bpar, bph, xr + ch * Nph * L, ndef * (L1 * L2 * L3), L}, N, ns, L1, L2, L3, red);
 }
 
 // One thread per (δ term, chain, listed pair): dl and part are [pair][chain] blocks, np nchains of them.

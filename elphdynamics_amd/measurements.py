@@ -21,8 +21,9 @@ Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: B
 BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them, in a container of its own: snapshots.split_info splits the
 table), the SSH model, several chains resident in the handle;
 sharded and slab handles are refused by the library.  BondBond, BondPairGreens and BondPairSusc live in a container of their own beside
-this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent is measured for the SSH model
-alone (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), nowhere for this one.  Several chains resident in the handle (a lockstep
+this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent of this model lives in another
+(current_measurements.py, csrc/currcorr.hip: one configuration or resident chains), that of the SSH model in ssh_bond_measurements.py
+(csrc/ssh_bondcorr.hip).  Several chains resident in the handle (a lockstep
 run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure_chains.hip): one container per chain, all
 chains in the same launches; the functions here keep refusing them.  The bond correlations of the chains are
 chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure_chains.hip), its bond

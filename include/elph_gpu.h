@@ -589,6 +589,58 @@ int elph_bond_chains_fetch(elph_handle h, int chain, double *BondBond, double *B
  * created. */
 int elph_bond_chains_reset(elph_handle h);
 
+/* ---------------------------------------------------------------- CurrentCurrent of the Holstein model (Measurements.jl) */
+
+/* The device side of a Holstein container's CurrentCurrent (measure_CurrentCurrent!(..., model::HolsteinModel, ...),
+ * Measurements.jl:1790-2098), for one configuration or for every chain resident in the handle: the accumulators of every chain in one
+ * device allocation [chain][CurrentCurrent] and the buffers of one pair of vectors of all chains, in a slot of its own beside the
+ * containers of elph_bond_create, elph_bond_chains_create and elph_meas_create.  The reference is mirrored as it executes: the eight
+ * translation averages, the four delta terms and the tau = beta slice of the SSH method (:2100-2384, elph_ssh_bond_create), every factor
+ * weighted by the static hopping t = reshaped(model.t, (L1, L2, L3, n_def)) (:1835) inside `for tau in L_tau` (:1868-1871), which visits
+ * the last time slice alone: the weight of bond cell + ncells * (definition - 1) is 1 on slices 1 .. L_tau - 1 and t on slice L_tau.
+ * The b == c delta term's displacement r'' is reduced mod L (unreduced the reference's index throws).  Needs elph_greens_create first;
+ * a new elph_greens_create drops it.  The estimator serves the chains with n_v * nchains vectors, vector v of chain c at index
+ * v * nchains + c (0-based).
+ *   nchains          >= 1 and equal to the number of chains resident in the handle (1: one configuration)
+ *   n_def, o1, o2, v model.bond_definitions, as elph_bond_create
+ *   Nbonds, t        model.Nbonds, double[Nbonds] model.t in definition order (assign_t! appends, initialize_model! never permutes it)
+ *   measure, time_dependent, npairs, pairs   the request for CurrentCurrent: measured or not; L_tau + 1 slices or the equal-time slice
+ *                    alone; int[2 * npairs] 1-based (pairs[1,p], pairs[2,p]) indices of bond definitions
+ * Checked before anything is allocated; a refused request leaves the handle without this container and usable:
+ *   ELPH_E_UNSUPPORTED   the SSH model (elph_ssh_bond_create measures its CurrentCurrent); a sharded or slab handle
+ *   ELPH_E_ARG           nchains < 1 or not the resident number (the message names both)
+ *   ELPH_E_STATE         elph_greens_create has not been called
+ *   ELPH_E_ARG           n_def < 1 or a null array; an orbital outside 1..n_s (naming the definition); measured without pairs, or a bond
+ *                        index outside 1..n_def (naming the pair and the index); Nbonds not the handle's, or t null
+ *   ELPH_E_UNSUPPORTED   Nbonds != n_def * ncells, where the reference's reshape of t fails (the message names both counts); a lattice
+ *                        whose frequency slice does not fit the LDS; a request whose grids would exceed 65535 in y or z:
+ *                        8 * n_def * nchains slices, or npairs * nchains transforms (the message says which product)
+ *   ELPH_E_HIP           an allocation failed */
+int elph_current_create(elph_handle h, int nchains, int n_def, const int *o1, const int *o2, const int *v, int64_t Nbonds, const double *t,
+                        int measure, int time_dependent, int npairs, const int *pairs);
+
+/* measure_CurrentCurrent! (Measurements.jl:1790-2098) for every pair v1 < v2 of a chain's n_v vectors, of every chain: the fields, their
+ * transforms, one inverse transform per listed pair, the delta terms and the fold run once for all chains (the chain is a grid axis: the
+ * number of launches does not depend on nchains), stream-ordered, with no copy and no synchronisation in between and one
+ * synchronisation before the call returns.  The method reads R and M^-1 R and nothing setup! makes: the estimator's pipeline does not
+ * run and its tables (elph_greens_dev_arrays) are not touched.  Every element is one thread's sum in index order, the delta means in
+ * the reduction order of elph_meas_accumulate, no atomics: the same inputs give the same bits, and chain c's bits depend on chain c's
+ * vectors alone and equal those of a single-configuration handle holding them.  With no pair requested nothing is launched.
+ *   ELPH_E_STATE   elph_current_create has not been called; the handle no longer holds the number of chains the container was created
+ *                  for (the message names both counts); the estimator's vectors are not a multiple of it; the estimator holds no
+ *                  vectors yet */
+int elph_current_accumulate(elph_handle h);
+
+/* One chain's un-normalised sums since the last reset (chain 0-based; 0 for one configuration): Complex{Float64}[L0, L1, L2, L3, n_p]
+ * as interleaved (re, im) doubles, first index fastest, L0 = L_tau + 1 or 1, laid out as elph_ssh_bond_fetch's CurrentCurrent; imaginary
+ * parts are exact zeros.  NULL or unmeasured: left untouched.  One device-to-host copy, one synchronisation.  ELPH_E_STATE: not
+ * created; ELPH_E_ARG: a chain outside 0..nchains-1. */
+int elph_current_fetch(elph_handle h, int chain, double *CurrentCurrent);
+
+/* reset_measurements! (Measurements.jl:698-758) for CurrentCurrent of every chain: one memset (stream-ordered).  ELPH_E_STATE: not
+ * created. */
+int elph_current_reset(elph_handle h);
+
 /* ---------------------------------------------------------------- measurements of the bond-phonon (SSH) model (Measurements.jl) */
 
 /* The device side of initialize_measurements_container(ssh, ...) (Measurements.jl:180-338): accumulators, all doubles on the device, for the
