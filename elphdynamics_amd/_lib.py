@@ -78,6 +78,9 @@ SIGNATURES = {
     "elph_greens_create": (c_int, [Handle, c_int, c_int, c_int, c_int, c_int]),
     "elph_greens_nv": (c_int, [Handle, P_int]),
     "elph_greens_update": (c_int, [Handle, P_dbl, c_int, P_i64, P_dbl, P_int]),
+    "elph_greens_set_rng": (c_int, [Handle, C.c_uint64]),
+    "elph_greens_rng_batches": (c_int, [Handle, C.POINTER(C.c_uint64)]),
+    "elph_greens_update_rng": (c_int, [Handle, c_int, P_i64, P_dbl, P_int]),
     "elph_greens_set_vectors": (c_int, [Handle, P_dbl, P_dbl]),
     "elph_greens_get_vectors": (c_int, [Handle, P_dbl, P_dbl]),
     "elph_greens_setup": (c_int, [Handle, c_int, c_int, P_dbl, P_dbl, P_dbl, P_dbl]),
@@ -177,6 +180,7 @@ BENCH_SIGNATURES = {
                                     P_dbl, P_dbl, c_i64, P_i64]),
     "elph_bench_hess_max_real": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl]),
     "elph_bench_kpm_bounds": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_int]),
+    "elph_bench_greens_noise": (c_int, [Handle, c_int, c_i64, C.c_uint64, c_int, P_dbl, c_i64, c_i64, P_dbl]),
 }
 
 # the slots of elph_bench_lattice_shape's vector, in order (elph_bench.h)

@@ -77,6 +77,14 @@ int elph_bench_kpm_bounds(elph_handle h, int where, const double *b_max, const d
  * 320 sites as slabs of rows on the same device, the resident kernel per slab, one launch) and its shape. */
 int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int *sites_per_slab, int *own_sites);
 
+/* The estimator's noise generator alone (greens_noise.hip): fills a device buffer of the hook's own with nvec vectors of ndim standard normals of
+ * batch `seed`, `reps` times back to back between two HIP events; *ms_total = the event time.  mapping: 0 = Box-Muller pair k on thread k (the
+ * mapping of the HMC state's generator), 1 = site fastest across the lanes (even Ltau; ELPH_E_UNSUPPORTED otherwise), -1 = what the estimator's
+ * device-drawn update launches.  out (may be NULL): elements [out_first, out_first + out_count) of the buffer as it lies on the device, layout S
+ * [vec][tau][site].  Needs no estimator. */
+int elph_bench_greens_noise(elph_handle h, int mapping, int64_t nvec, uint64_t seed, int reps, double *ms_total, int64_t out_first,
+                            int64_t out_count, double *out);
+
 /* the sharded solve (shard.hip): exactly `iters` iterations (no stop test); *ms = HIP-event time of this rank's launch.  b_slab may
  * be NULL (keeps the right-hand side of the previous call).  Needs elph_shard_prepare + barrier like a solve. */
 int elph_shard_iterate(elph_handle h, const double *b_slab, int64_t iters, double *ms);

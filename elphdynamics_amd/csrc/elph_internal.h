@@ -501,6 +501,9 @@ int elph_i_greens_chain_scratch_alloc(elph_handle_s *h, int nchains, ElphGreensC
 void elph_i_greens_chain_scratch_free(ElphGreensChainScratch *S);
 int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p);      // p: chain 0's vectors; chain c's lie c ndim further
 int elph_i_greens_autocorr_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, double *outS, const double *vS);
+// greens_noise.hip: nvec vectors of ndim standard normals of batch `seed` (rng_dev.h), numbered in the reference layout, into dstS (layout S).
+// mapping of Box-Muller pairs to threads: 0 pair-indexed, 1 site-fastest (even Ltau only), -1 the one the estimator ships.  Stream-ordered.
+int elph_i_greens_randn(elph_handle_s *h, double *dstS, uint64_t seed, int64_t nvec, int mapping = -1);
 int elph_launch_r2s(elph_handle_s *h, double *dstS, const double *srcR, int nvec, int ncols = 0);
 int elph_launch_s2r(elph_handle_s *h, double *dstR, const double *srcS, int nvec, int ncols = 0);
 int elph_launch_expV(elph_handle_s *h, const double *xR, double dtau, int chain = 0);

@@ -23,6 +23,7 @@
 
 #include "cell_dft_dev.h"
 #include "elph_internal.h"
+#include "rng_dev.h"
 
 namespace {
 
@@ -32,6 +33,8 @@ static_assert(TPB == CELL_DFT_TPB, "dft_cells walks the workgroup of k_gr_spatia
 struct GreensState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, nv = 2;
     bool have_vectors = false;
+    bool rng_on = false;                   // the estimator's own generator (elph_greens_set_rng)
+    uint64_t rng_seed = 0, rng_batches = 0;
     double *R = nullptr, *X = nullptr;     // [nv][ndim] layout S: noise vectors and M⁻¹R
     double *f = nullptr;                   // [8][ndim] the eight real input fields of setup!
     double2 *nuA = nullptr;                // [2][Lo2][N] twisted half spectra of fields 0,1
@@ -229,24 +232,20 @@ extern "C" int elph_greens_nv(elph_handle h, int *nv) {
     return ELPH_OK;
 }
 
-// update!(estimator, model, P): the caller supplies the n_v noise vectors (the reference draws them from model.rng, :212)
-extern "C" int elph_greens_update(elph_handle h, const double *R, int use_precond, int64_t *iters, double *residual_error,
-                                  int *flag) {
-    CHECK_H(h);
-    RC(need_greens(h));
-    if (!R) { elph_set_error("R is null"); return ELPH_E_ARG; }
-    GreensState *g = gs_of(h);
-    const int nv = g->nv;
-    // several chains resident: right-hand side r of the batch belongs to chain r % nchains, so vector v of chain c is row
-    // v * nchains + c of R — the estimator must then hold a multiple of nchains vectors
+// several chains resident: right-hand side r of the batch belongs to chain r % nchains, so vector v of chain c is row
+// v * nchains + c of R — the estimator must then hold a multiple of nchains vectors
+static int check_chain_count(const elph_handle_s *h, int nv) {
     if (h->nchains != 1 && nv % h->nchains) {
         elph_set_error("%d chains are resident: the estimator needs a multiple of that many vectors (it has %d)", h->nchains, nv);
         return ELPH_E_ARG;
     }
+    return ELPH_OK;
+}
+
+// update! after its randn!: the noise vectors are in g->R (layout S).  Mᵀr, zero start, the batched solve, M⁻¹R into g->X; one synchronisation.
+static int solve_from_R(elph_handle_s *h, GreensState *g, int use_precond, int64_t *iters, double *residual_error, int *flag) {
+    const int nv = g->nv;
     const size_t nd = (size_t)h->ndim;
-    RC(elph_i_ensure_capacity(h, nv));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, R, (size_t)nv * nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, g->R, h->d_stage_in, nv));
     RC(elph_launch_mul(h, 1, h->d_b, g->R, nv));                       // Mᵀr₁ (model.v″, :223-224)
     RC(elph_launch_zero(h, h->d_x, (int64_t)nv * h->ndim));            // fill!(M⁻¹r₁, 0)  :213
     h->x_zero = false;                                                 // (this path does not use the x = 0 hint, and takes nobody else's)
@@ -263,6 +262,55 @@ extern "C" int elph_greens_update(elph_handle h, const double *R, int use_precon
     }
     g->have_vectors = true;
     return ELPH_OK;
+}
+
+// update!(estimator, model, P): the caller supplies the n_v noise vectors (the reference draws them from model.rng, :212)
+extern "C" int elph_greens_update(elph_handle h, const double *R, int use_precond, int64_t *iters, double *residual_error,
+                                  int *flag) {
+    CHECK_H(h);
+    RC(need_greens(h));
+    if (!R) { elph_set_error("R is null"); return ELPH_E_ARG; }
+    GreensState *g = gs_of(h);
+    const int nv = g->nv;
+    RC(check_chain_count(h, nv));
+    RC(elph_i_ensure_capacity(h, nv));
+    HIPCHK(hipMemcpyAsync(h->d_stage_in, R, (size_t)nv * (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RC(elph_launch_r2s(h, g->R, h->d_stage_in, nv));
+    return solve_from_R(h, g, use_precond, iters, residual_error, flag);
+}
+
+// The estimator's own generator (independent of the HMC state's, elph_hmc_set_rng): batch b, counted since this call, is seeded with output b
+// of SplitMix64(seed).  A new elph_greens_create starts without one.
+extern "C" int elph_greens_set_rng(elph_handle h, uint64_t seed) {
+    CHECK_H(h);
+    RC(need_greens(h));
+    GreensState *g = gs_of(h);
+    g->rng_on = true;
+    g->rng_seed = seed;
+    g->rng_batches = 0;
+    return ELPH_OK;
+}
+
+extern "C" int elph_greens_rng_batches(elph_handle h, uint64_t *batches) {
+    CHECK_H(h);
+    RC(need_greens(h));
+    if (!batches) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    *batches = gs_of(h)->rng_batches;
+    return ELPH_OK;
+}
+
+// update!(estimator, model, P) with its randn!(R) on the device: one batch of n_v * ndim normals straight into g->R (greens_noise.hip), no
+// vector crosses the bus in either direction
+extern "C" int elph_greens_update_rng(elph_handle h, int use_precond, int64_t *iters, double *residual_error, int *flag) {
+    CHECK_H(h);
+    RC(need_greens(h));
+    GreensState *g = gs_of(h);
+    if (!g->rng_on) { elph_set_error("the estimator has no generator: call elph_greens_set_rng first"); return ELPH_E_STATE; }
+    const int nv = g->nv;
+    RC(check_chain_count(h, nv));
+    RC(elph_i_ensure_capacity(h, nv));
+    RC(elph_i_greens_randn(h, g->R, sm64(g->rng_seed, ++g->rng_batches), nv));
+    return solve_from_R(h, g, use_precond, iters, residual_error, flag);
 }
 
 // estimator.R / estimator.M⁻¹R as host arrays (n_v vectors of length ndim, reference layout); either may be NULL

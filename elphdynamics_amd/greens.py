@@ -34,6 +34,19 @@ class EstimateGreensFunction:
         self.GD0_GD0 = np.zeros(shp, dtype=np.complex128, order="F")
         self.GD0_G0D = np.zeros(shp, dtype=np.complex128, order="F")
         check(model._lib.elph_greens_create(model._h, self.ns, self.L1, self.L2, self.L3, self.nv))
+        self.device_rng = False
+
+    def device_rng_(self, seed):
+        """Give the estimator the library's own generator (elph_greens_set_rng): update_ without an explicit R then draws the noise
+        vectors on the device, batch b equal to synth.randn(synth.batch_seed(seed, b), nv * Ndim).reshape(nv, Ndim), and copies no
+        vector in either direction — self.R and self.MinvR are STALE until pull_().  The seed must differ from the one given to
+        HybridMonteCarlo.device_rng_: the same seed would produce the same batches."""
+        check(self.model._lib.elph_greens_set_rng(self.model._h, C.c_uint64(int(seed) & ((1 << 64) - 1))))
+        self.device_rng = True
+
+    def pull_(self):
+        """Fetch the device's R and M⁻¹R into self.R, self.MinvR (after a device-drawn update_ they are stale until this is called)."""
+        check(self.model._lib.elph_greens_get_vectors(self.model._h, dptr(self.R), dptr(self.MinvR)))
 
     # views of the pair selected by setup_ (estimator.r₁ … M⁻¹r₂)
     @property
@@ -56,6 +69,9 @@ class EstimateGreensFunction:
 def update_(est, model, P=None, rng=None, R=None, setup_kwargs=None):
     """update!(estimator, model, preconditioner).  The noise vectors come from `R` ((n_v, Ndim)) or from `rng`
     (numpy Generator) — Julia's Xoshiro stream is not reproducible here, so parity runs pass R explicitly.
+    Precedence: an explicit R wins; otherwise, after est.device_rng_(seed), the library draws R on the device
+    (elph_greens_update_rng) — est.R is not filled and M⁻¹R is not copied back (est.pull_() fetches both), and `rng`
+    feeds only the preconditioner's set-up; otherwise R comes from `rng`.
     Returns (iters, residual_error, flag) per vector (the reference discards them)."""
     m = est.model
     assert model is m
@@ -68,14 +84,17 @@ def update_(est, model, P=None, rng=None, R=None, setup_kwargs=None):
             pc.setup_chains_(P, rng=rng, **(setup_kwargs or {}))
     else:
         pc.setup_(P, rng=rng, **(setup_kwargs or {}))                      # :206
-    if R is None:
-        rng = rng or np.random.default_rng()
-        R = rng.standard_normal((est.nv, m.Ndim))
-    est.R[:] = R
     it = np.zeros(est.nv, dtype=np.int64)
     res = np.zeros(est.nv)
     fl = np.zeros(est.nv, dtype=np.int32)
     use_prec = 0 if P is None else 1
+    if R is None and est.device_rng:
+        check(m._lib.elph_greens_update_rng(m._h, use_prec, it.ctypes.data_as(P_i64), dptr(res), fl.ctypes.data_as(P_int)))
+        return it, res, fl
+    if R is None:
+        rng = rng or np.random.default_rng()
+        R = rng.standard_normal((est.nv, m.Ndim))
+    est.R[:] = R
     check(m._lib.elph_greens_update(m._h, dptr(est.R), use_prec, it.ctypes.data_as(P_i64), dptr(res), fl.ctypes.data_as(P_int)))
     check(m._lib.elph_greens_get_vectors(m._h, None, dptr(est.MinvR)))
     return it, res, fl

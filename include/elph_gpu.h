@@ -374,6 +374,21 @@ int elph_greens_nv(elph_handle h, int *nv);
  * vector v of chain c at row v * nchains + c (elph_greens_setup then takes those 1-based indices). */
 int elph_greens_update(elph_handle h, const double *R, int use_precond, int64_t *iters, double *residual_error, int *flag);
 
+/* The estimator's own on-device generator, so that update! draws its randn!(R) (:212) where the solve runs: with 64 chains and n_v = 10
+ * the host route draws 26 million normals and moves 210 MB in each direction per update.  elph_greens_set_rng gives the estimator a
+ * generator of its own (ELPH_E_STATE before elph_greens_create; a new elph_greens_create returns it to having none): batch b (1-based,
+ * counted since this call, independently of the HMC state's generator and its batch count) is seeded with output b of SplitMix64(seed),
+ * as for elph_hmc_set_rng.  The HMC generator and the estimator's MUST get different seeds: with the same seed they produce the same
+ * batches.  elph_greens_rng_batches: the batches drawn so far.
+ * elph_greens_update_rng is elph_greens_update with R drawn on the device: ONE batch of n_v * ndim normals, numbered in the layout the
+ * host array would have had ([n_v][ndim], tau fastest) — R equals synth.randn(batch seed, n_v * ndim).reshape(n_v, ndim) handed to
+ * elph_greens_update — written straight into the estimator's R; no vector is copied to or from the host, and the call synchronises once.
+ * Same chain-count rule (ELPH_E_ARG) and same outputs as elph_greens_update; ELPH_E_STATE without elph_greens_set_rng.  A refused call
+ * draws no batch.  The KPM set-up stays the caller's call before it, with the caller's Arnoldi start vectors. */
+int elph_greens_set_rng(elph_handle h, uint64_t seed);
+int elph_greens_rng_batches(elph_handle h, uint64_t *batches);
+int elph_greens_update_rng(elph_handle h, int use_precond, int64_t *iters, double *residual_error, int *flag);
+
 /* estimator.R / estimator.M⁻¹R (double[n_v * ndim], vector-major, tau fastest); NULL = skip.  set: replay of vectors
  * produced elsewhere (both must have been given before elph_greens_setup). */
 int elph_greens_set_vectors(elph_handle h, const double *R, const double *MinvR);
