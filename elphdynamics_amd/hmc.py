@@ -386,16 +386,54 @@ def special_move_chains_(model, hmc, kind, cols_i, cols_j=None, P=None, rng=None
     return acc.astype(bool), s0, s1, it, fl
 
 
+def special_update_(model, hmc, kind, nmoves, P=None):
+    """nmoves moves of special_update! (SpecialUpdates.jl:97-366) for every chain of `hmc` in ONE library call
+    (elph_hmc_special_update_chains): the sites / bonds / phonon pairs are drawn on the device by the handle's generator
+    (hmc.device_rng_ first), the Metropolis test is decided there, and only the per-move results come back.
+    -> namespace(accepted bool (nmoves, nch), col_i, col_j (0-based columns drawn), S0, S1, iters, flags), all (nmoves, nch)."""
+    from types import SimpleNamespace
+    from ._lib import P_i64, P_int, check, dptr
+    nm, nch = int(nmoves), hmc.nchains
+    shape = (max(nm, 0), nch)
+    acc, fl = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32)
+    ci, cj, it = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+    s0, s1 = np.zeros(shape), np.zeros(shape)
+    model._push_solver()
+    check(model._lib.elph_hmc_special_update_chains(
+        model._h, int(kind), nm, 0 if P is None else 1, acc.ctypes.data_as(P_int), ci.ctypes.data_as(P_i64), cj.ctypes.data_as(P_i64),
+        dptr(s0), dptr(s1), it.ctypes.data_as(P_i64), fl.ctypes.data_as(P_int)))
+    if model.kind == models.SSH:
+        model._cs_stale = True
+    return SimpleNamespace(accepted=acc.astype(bool), col_i=ci, col_j=cj, S0=s0, S1=s1, iters=it, flags=fl)
+
+
+def _device_draw(hmc, draw, rng):
+    """draw = "host" / "device" of the frequency-driven helpers -> True for the device route, after its preconditions."""
+    if draw not in ("host", "device"):
+        raise ValueError(f'draw = {draw!r}: "host" or "device"')
+    if draw == "host":
+        return False
+    if not hmc.device_rng:
+        raise ValueError('draw="device" takes its moves from the handle\'s generator: call hmc.device_rng_(seed) first')
+    if rng is not None:
+        raise ValueError('draw="device" does not use a host generator: leave rng out')
+    return True
+
+
 def _isapprox(a, b):
     """Julia's a ≈ b for vectors: ‖a − b‖ ≤ √eps · max(‖a‖, ‖b‖)."""
     return np.linalg.norm(a - b) <= 1.4901161193847656e-08 * max(np.linalg.norm(a), np.linalg.norm(b))
 
 
-def reflection_update_(model, hmc, nsites, P=None, rng=None):
+def reflection_update_(model, hmc, nsites, P=None, rng=None, draw="host"):
     """special_update!(model, hmc, ru::ReflectionUpdate, P) (SpecialUpdates.jl:103-136): nsites sites drawn with replacement,
-    one move each; returns the accepted fraction.  Holstein only (null operation otherwise, :138-141)."""
+    one move each; returns the accepted fraction.  Holstein only (null operation otherwise, :138-141).
+    draw="device": the sites come from the handle's generator and all moves are one library call (special_update_)."""
+    device = _device_draw(hmc, draw, rng)
     if model.kind != models.HOLSTEIN or nsites < 1:
         return 0.0
+    if device:
+        return float(special_update_(model, hmc, REFLECT, min(model.Nph, nsites), P=P).accepted.mean())
     rng = rng or np.random.default_rng()
     if hmc.nchains > 1:      # every chain draws its own sites; move k of all chains is one batched action evaluation
         nmv = min(model.Nph, nsites)
@@ -405,11 +443,18 @@ def reflection_update_(model, hmc, nsites, P=None, rng=None):
     return sum(special_move_(model, hmc, REFLECT, int(i), P=P, rng=rng)[0] for i in sites) / len(sites)
 
 
-def swap_update_(model, hmc, nbonds, P=None, rng=None):
+def swap_update_(model, hmc, nbonds, P=None, rng=None, draw="host"):
     """special_update!(model, hmc, su::SwapUpdate, P): Holstein (:205-236) — the two sites of nbonds randomly drawn bonds swap
-    their phonon world lines; SSH (:302-362) — two randomly drawn bond phonons with different world lines swap them."""
+    their phonon world lines; SSH (:302-362) — two randomly drawn bond phonons with different world lines swap them.
+    draw="device": bonds / phonon pairs come from the handle's generator, the world lines are compared on the device and all moves
+    are one library call (special_update_); a chain whose world lines are all equal proposes the identity."""
+    device = _device_draw(hmc, draw, rng)
     if nbonds < 1:
         return 0.0
+    if device:
+        if model.Nbonds == 0 or (model.kind == models.SSH and model.Nph < 2):
+            return 0.0
+        return float(special_update_(model, hmc, SWAP, min(model.Nbonds, nbonds), P=P).accepted.mean())
     rng = rng or np.random.default_rng()
     if model.kind == models.SSH and hmc.nchains > 1:      # every chain draws its own pair of different world lines
         if model.Nph < 2:

@@ -312,8 +312,8 @@ int elph_hmc_set_shared_fields(elph_handle h, const int64_t *primary_column);
  * elph_hmc_set_rng) seeded with output b of SplitMix64(seed), numbered in the layout the host array would have had — so a run
  * is reproducible from (seed, batch count) and equals the run that is handed synth.randn(batch seed, n) explicitly.  Field and
  * site vectors are generated on the device; Arnoldi start vectors and Metropolis uniforms (small) on the host.  Order of the
- * batches within a call: HMC update R, Rp, Rm, kpm_randn, u_accept; special move Rp, Rm, kpm_randn, u_accept; Langevin step eta,
- * kpm_randn, g1, g2. */
+ * batches within a call: HMC update R, Rp, Rm, kpm_randn, u_accept; special move Rp, Rm, kpm_randn, u_accept; every move of
+ * elph_hmc_special_update_chains draw, Rp, Rm, kpm_randn, u_accept; Langevin step eta, kpm_randn, g1, g2. */
 int elph_hmc_set_rng(elph_handle h, uint64_t seed);
 int elph_hmc_rng_batches(elph_handle h, uint64_t *batches);
 
@@ -331,6 +331,22 @@ int elph_hmc_special_move(elph_handle h, int kind, int64_t col_i, int64_t col_j,
 int elph_hmc_special_move_chains(elph_handle h, int kind, const int64_t *col_i, const int64_t *col_j, const double *Rp,
                                  const double *Rm, int use_precond, const double *kpm_randn, const double *u_accept,
                                  int *accepted, double *S0, double *S1, int64_t *iters, int *flag);
+/* special_update! itself for every chain of the HMC state (SpecialUpdates.jl:97-366; the draws it replaces: :113 the site of a
+ * reflection, :248-258 the bond of a Holstein swap, :324-328 the phonon pair of an SSH swap): nmoves moves in one call, the columns
+ * drawn on the device by the generator of elph_hmc_set_rng (required: ELPH_E_STATE without it), the Metropolis test decided there.
+ * kind 0 reflection, 1 swap.  Batches per move: draw, Rp, Rm, [kpm_randn], u_accept; the last four as the move entry above lays
+ * them out.  The draw batch: chain c takes u0 = uniform 2c and u1 = uniform 2c + 1; with pick(u, n) = min(floor(u n), n - 1):
+ *   reflection      column pick(u0, Nph);
+ *   Holstein swap   the two sites of bond pick(u0, nbonds) of the handle's neighbor table;
+ *   SSH swap        i = pick(u0, Nph); D = the columns, in increasing order, whose world line is not isapprox that of i
+ *                   (|x_i - x_q| <= sqrt(eps) max(|x_i|, |x_q|) in the 2-norm); j = D[pick(u1, |D|)], and j = i when D is empty:
+ *                   the move is then the identity and is evaluated like any other (the reference's while loop would not end).
+ * Outputs are [nmoves][nchains]: accepted; col_i, col_j the 0-based columns drawn (col_j = col_i for a reflection); S0, S1; iters,
+ * flag of the move's two solves — all but accepted may be NULL.  Per move the number of launches and of copies does not depend on
+ * the number of chains and no field vector leaves the device.  Shared fields, sharded lattices and slab handles:
+ * ELPH_E_UNSUPPORTED. */
+int elph_hmc_special_update_chains(elph_handle h, int kind, int64_t nmoves, int use_precond, int *accepted, int64_t *col_i,
+                                   int64_t *col_j, double *S0, double *S1, int64_t *iters, int *flag);
 
 /* ---------------------------------------------------------------- Langevin dynamics (caller of the path) */
 
