@@ -28,10 +28,14 @@ def run_rank(comm, what, tag, out):
     # ---- sharded handles exist (rank threads of one process share the process's hardware queues: a kernel that waits for a peer must not
     # ---- sit behind an idle handle's stream on the same queue)
     m = configs.make_model(tag, tol=1e-12, maxiter=20000)
+    if kind == "holstein" and os.environ.get("ELPH_TEST_SITE_DISORDER") == "1":      # site-dependent ω, ω₄, λ, λ₂, μ: every slab takes its own slice
+        import site_disorder_cases
+        site_disorder_cases.prepare(tag)(m)
     res = dict(world=comm.world)
     ref0 = comm.rank == 0
     if kind == "holstein":
-        m.lam2[:] = 0.03 * synth.randn(5, m.Nsites)
+        if os.environ.get("ELPH_TEST_SITE_DISORDER") != "1":
+            m.lam2[:] = 0.03 * synth.randn(5, m.Nsites)
     else:
         m.alpha2[:] = 0.02
     models.update_model_(m)
@@ -55,7 +59,8 @@ def run_rank(comm, what, tag, out):
         m.solver.tol = 1e-10
         if kind != "holstein" and getattr(m, "omega4", None) is None:
             m.omega4 = np.zeros(m.Nph)
-        m.omega4[:] = 0.02
+        if not (kind == "holstein" and os.environ.get("ELPH_TEST_SITE_DISORDER") == "1"):
+            m.omega4[:] = 0.02
         fa = pc.FourierAccelerator(m)
         pc.update_M_(fa, m, 0.0, np.inf, 1.0, 0.3)
         omega, omega4, faM = m.omega.copy(), m.omega4.copy(), np.array(fa.M)
@@ -105,6 +110,7 @@ def run_rank(comm, what, tag, out):
         res.update(it6=it6, flag6=fl6, nz6=float(np.abs(x6).sum()))
     elif what == "force" and kind == "holstein":
         F, Xp, Xm, it, fl = S.fermion_force_holstein(x0, lam, lam2, mu, dtau, pp, pm)
+        res.update(force_with=np.stack([lam, lam2, mu]))
         res.update(F=F, Xp=Xp, Xm=Xm, it=it, flag=fl)
     elif what == "force":
         q, it, fl = S.fermion_force_ssh(bp, bm, Nb)
@@ -116,6 +122,7 @@ def run_rank(comm, what, tag, out):
         S.install_collectives()
         # the sharded update: the slab's part of every global array
         _lib.check(lib.elph_hmc_create(S.h, d(site(omega)), d(site(omega4)), d(site(lam)), d(site(lam2)), d(site(mu)), dtau, d(S._local(faM))))
+        res.update(created_with=np.stack([site(a) for a in (omega, omega4, lam, lam2, mu)]), created_sites=np.asarray(S.gsites))
         _lib.check(lib.elph_hmc_set_state(S.h, d(S._local(x0)), d(np.zeros(S.Nloc * Ltau))))
         if with_kpm:      # the expansion lives on a handle of the whole lattice (created by setup_kpm; its Ē is injected at every setup!(P))
             S.setup_kpm(E, n=20, buf=0.05, c1=1.0, c2=1.0, seed=1)

@@ -44,9 +44,20 @@ def test_langevin_step_matches_dense_golden(cls, key):
 def test_langevin_step_vs_oracle(oracle, tag, scheme, with_kpm):
     """Two consecutive steps (the field stays on the device between them) vs the oracle, with the KPM preconditioner set up
     from the same Arnoldi start vectors; also the reference's iteration-count conventions."""
+    check_langevin_step_vs_oracle(oracle, tag, scheme, with_kpm)
+
+
+# the relative bound of check_langevin_step_vs_oracle on the displacement of one step, by name (tests/test_site_disorder_host.py)
+STEP_BOUND = 1e-6
+
+
+def check_langevin_step_vs_oracle(oracle, tag, scheme, with_kpm, prepare=None):
+    """prepare(m): called on the model before anything reads its parameter arrays (the accelerator, the oracle's model, the dynamics)."""
     from elphdynamics_amd import configs, langevin, preconditioners as pc, synth
     m = configs.make_model(tag, tol=1e-8, maxiter=20000)
     m.omega4[:] = 0.02
+    if prepare is not None:
+        prepare(m)
     fa = pc.FourierAccelerator(m)
     pc.update_Q_(fa, m, 0.0, np.inf, 0.7)
     E = oracle.update_model_holstein(m.Nsites, m.Ltau, m.dtau, m.x, m.lam, m.lam2, m.mu)
@@ -64,7 +75,7 @@ def test_langevin_step_vs_oracle(oracle, tag, scheme, with_kpm):
                                            m.lam2, m.mu, m.dtau, P=Po, kpm_randn=rnd["kpm_randn"], tol=1e-8, maxiter=20000)
         it = langevin.evolve_(m, dyn, fa, P, randoms=rnd)
         assert dyn.flag == 0 and abs(it - it_o) <= 1
-        assert rel(m.x - x_prev, x_o - x_prev) < 1e-6
+        assert rel(m.x - x_prev, x_o - x_prev) < STEP_BOUND
     m.close()
 
 
@@ -135,6 +146,11 @@ def test_langevin_error_paths():
 def test_langevin_chains_match_single_trajectories(tag, scheme, with_kpm):
     """nchains trajectories in lockstep (one batched solve per force, one KPM expansion per chain) == each trajectory run alone
     with its own random numbers; two steps so that the fields differ between chains at the second."""
+    check_langevin_chains_match_single_trajectories(tag, scheme, with_kpm)
+
+
+def check_langevin_chains_match_single_trajectories(tag, scheme, with_kpm, prepare=None):
+    """prepare(m): called on every model before anything reads its parameter arrays."""
     from elphdynamics_amd import configs, langevin, preconditioners as pc, synth
     nch = 3
     cls = [langevin.EulerDynamics, langevin.RungeKuttaDynamics, langevin.HeunsDynamics][scheme]
@@ -142,6 +158,8 @@ def test_langevin_chains_match_single_trajectories(tag, scheme, with_kpm):
     def make():
         m = configs.make_model(tag, tol=1e-9, maxiter=20000)
         m.omega4[:] = 0.02
+        if prepare is not None:
+            prepare(m)
         fa = pc.FourierAccelerator(m)
         pc.update_Q_(fa, m, 0.0, np.inf, 0.7)
         P = pc.SymmetricKPMPreconditioner(m, n=min(20, m.Nsites), buf=0.05, c1=1.0, c2=1.0) if with_kpm else None

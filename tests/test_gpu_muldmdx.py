@@ -99,11 +99,14 @@ def test_muldMdx_holstein_vs_oracle(oracle, tag):
     check_muldMdx_holstein_vs_oracle(oracle, tag)
 
 
-def check_muldMdx_holstein_vs_oracle(oracle, tag, t_stddev=0.0):
+def check_muldMdx_holstein_vs_oracle(oracle, tag, t_stddev=0.0, prepare=None):
+    """prepare(m): called on the model before update_model! reads its parameter arrays."""
     from elphdynamics_amd import configs, models, synth
     from oracle.oracle import dp
     m = configs.make_model(tag, tol=1e-8, t_stddev=t_stddev)
     m.lam2[:] = 0.03 * synth.randn(5, m.Nsites)
+    if prepare is not None:
+        prepare(m)
     models.update_model_(m)
     E = oracle.update_model_holstein(m.Nsites, m.Ltau, m.dtau, m.x, m.lam, m.lam2, m.mu)
     om = oracle.make_model(0, m.Nsites, m.Ltau, m.neighbor_table, m.cosht, m.sinht, E)
@@ -224,7 +227,27 @@ class _DevBuf:
 def test_muldMdx_device_pointer_twins(lib):
     """_dev entry points on device buffers (reference layout) give the bits of the host entry points."""
     from elphdynamics_amd import _lib, configs, models, synth
-    m = configs.make_model("B", tol=1e-8)
+    check_muldMdx_holstein_device_pointer_twin(lib, "B")
+    ms = configs.make_model("e", tol=1e-8)
+    models.update_model_(ms)
+    refs = np.zeros(ms.Ndof)
+    us, vs = synth.randn(923, ms.Ndim), synth.randn(924, ms.Ndim)
+    models.muldMdx_(refs, us, ms, vs)
+    du, dv, dout = _DevBuf(us), _DevBuf(vs), _DevBuf(n=ms.Ndof)
+    _lib.check(lib.elph_muldMdx_ssh_fields_dev(ms._h, dout.p, du.p, dv.p))
+    _lib.check(lib.elph_synchronize(ms._h))
+    assert np.array_equal(dout.get(), refs)
+    for b in (du, dv, dout):
+        b.free()
+    ms.close()
+
+
+def check_muldMdx_holstein_device_pointer_twin(lib, tag, prepare=None):
+    """The Holstein half of test_muldMdx_device_pointer_twins on configuration `tag`; prepare(m): called before update_model!."""
+    from elphdynamics_amd import _lib, configs, models, synth
+    m = configs.make_model(tag, tol=1e-8)
+    if prepare is not None:
+        prepare(m)
     models.update_model_(m)
     u, v = synth.randn(921, m.Ndim), synth.randn(922, m.Ndim)
     ref = np.zeros(m.Ndim)
@@ -242,15 +265,3 @@ def test_muldMdx_device_pointer_twins(lib):
     for b in (du, dv, dx, dout):
         b.free()
     m.close()
-    ms = configs.make_model("e", tol=1e-8)
-    models.update_model_(ms)
-    refs = np.zeros(ms.Ndof)
-    us, vs = synth.randn(923, ms.Ndim), synth.randn(924, ms.Ndim)
-    models.muldMdx_(refs, us, ms, vs)
-    du, dv, dout = _DevBuf(us), _DevBuf(vs), _DevBuf(n=ms.Ndof)
-    _lib.check(lib.elph_muldMdx_ssh_fields_dev(ms._h, dout.p, du.p, dv.p))
-    _lib.check(lib.elph_synchronize(ms._h))
-    assert np.array_equal(dout.get(), refs)
-    for b in (du, dv, dout):
-        b.free()
-    ms.close()

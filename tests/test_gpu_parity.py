@@ -769,9 +769,16 @@ def test_error_paths(lib):
 
 def test_calc_OinvLambda_phi_vs_oracle(oracle):
     """HMC.calc_O⁻¹Λϕ! (HMC.jl:820-915): Λ construction, the two solves as one batch, tol^power, cld(iters,2)."""
+    check_calc_OinvLambda_phi_vs_oracle(oracle, "B")
+
+
+def check_calc_OinvLambda_phi_vs_oracle(oracle, tag, prepare=None):
+    """prepare(m): called on the model before anything reads its parameter arrays."""
     from elphdynamics_amd import configs, hmc, synth
     from oracle.oracle import dp
-    m = configs.make_model("B", tol=1e-4)
+    m = configs.make_model(tag, tol=1e-4)
+    if prepare is not None:
+        prepare(m)
     om = _oracle_model(oracle, m)
     N, L, n = m.Nsites, m.Ltau, m.Ndim
     phi_p, phi_m = synth.randn(301, n), synth.randn(302, n)
@@ -927,9 +934,20 @@ def _oracle_force(oracle, om, m, phi_p, phi_m, tol):
 @pytest.mark.parametrize("tag", ["b", "B", "d", "g", "C", "D"])
 def test_fermion_force_vs_oracle(oracle, tag):
     """update_model! + calc_O⁻¹Λϕ! + calc_dSfdx! on the device vs the oracle's composition."""
+    check_fermion_force_vs_oracle(oracle, tag)
+
+
+# the relative bound of check_fermion_force_vs_oracle on the solutions and on F, by name (tests/test_site_disorder_host.py)
+FORCE_BOUND = 1e-8
+
+
+def check_fermion_force_vs_oracle(oracle, tag, prepare=None):
+    """prepare(m): called on the model before anything reads its parameter arrays."""
     from elphdynamics_amd import configs, hmc, synth
     m = configs.make_model(tag, tol=1e-11)
     m.lam2[:] = 0.03 * synth.randn(5, m.Nsites)                 # exercise the lambda2 terms too
+    if prepare is not None:
+        prepare(m)
     om_E = oracle.update_model_holstein(m.Nsites, m.Ltau, m.dtau, m.x, m.lam, m.lam2, m.mu)
     om = oracle.make_model(0, m.Nsites, m.Ltau, m.neighbor_table, m.cosht, m.sinht, om_E)
     phi_p, phi_m = synth.randn(41, m.Ndim), synth.randn(42, m.Ndim)
@@ -937,24 +955,32 @@ def test_fermion_force_vs_oracle(oracle, tag):
     F = np.ones(m.Ndim)                                           # accumulation: starts from a non-zero array
     it, fl, Xp, Xm = hmc.calc_dSfdx_(F, m, phi_p, phi_m, None, power=1.0, return_solutions=True)
     assert fl == 0 and it > 0
-    assert rel(Xp, Xo[0]) < 1e-8 and rel(Xm, Xo[1]) < 1e-8
-    assert rel(F - 1.0, Fo) < 1e-8
+    assert rel(Xp, Xo[0]) < FORCE_BOUND and rel(Xm, Xo[1]) < FORCE_BOUND
+    assert rel(F - 1.0, Fo) < FORCE_BOUND
     m.close()
 
 
 def test_fermion_force_is_the_gradient_of_the_action(oracle):
     """dS_f/dx_k from the device force equals a central finite difference of
     S_f(x) = 1/2 sum_± (Λϕ±)ᵀ (MᵀM)⁻¹ (Λϕ±)  (HMC.jl:757-783) evaluated with the oracle."""
+    check_fermion_force_is_the_gradient_of_the_action(oracle, "b", lambda m: (0, 7, m.Ltau, 5 * m.Ltau + 3, m.Ndim - 1))
+
+
+def check_fermion_force_is_the_gradient_of_the_action(oracle, tag, probes, prepare=None):
+    """probes(m): the elements of the field the difference quotient is taken at; prepare(m): called on the model before anything
+    reads its parameter arrays."""
     from elphdynamics_amd import configs, hmc, synth
-    m = configs.make_model("b", tol=1e-12)
+    m = configs.make_model(tag, tol=1e-12)
     m.lam2[:] = 0.02
+    if prepare is not None:
+        prepare(m)
     phi_p, phi_m = synth.randn(51, m.Ndim), synth.randn(52, m.Ndim)
     F = np.zeros(m.Ndim)
     it, fl = hmc.calc_dSfdx_(F, m, phi_p, phi_m, None, power=1.0)
     assert fl == 0
     x0 = m.x.copy()
     h = 1e-5
-    for k in (0, 7, m.Ltau, 5 * m.Ltau + 3, m.Ndim - 1):
+    for k in probes(m):
         S = []
         for sgn in (+1, -1):
             m.x[:] = x0

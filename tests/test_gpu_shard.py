@@ -292,14 +292,17 @@ def test_sharded_fermion_force_vs_one_handle(tmp_path, tag, world, per_proc):
     """BASELINE configs 4 and 5: the fermion force of the Holstein honeycomb lattice (D) and the bond brackets of the optical SSH model (E)
     sharded over 2 / 4 / 8 ranks reproduce elph_fermion_force_* of ONE handle to 1e-10 (solves to 1e-12 on both sides); iters and flag
     identical on every rank."""
-    res = _run_callers("force", tag, tmp_path, world, per_proc=per_proc)
+    _assert_sharded_force_equals_one_handle(_run_callers("force", tag, tmp_path, world, per_proc=per_proc), tag == "D")
+
+
+def _assert_sharded_force_equals_one_handle(res, holstein):
     a = res[0]
-    key = "F" if tag == "D" else "q"
+    key = "F" if holstein else "q"
     for b in res[1:]:
         assert int(b["it"]) == int(a["it"]) and int(b["flag"]) == 0 and np.array_equal(a[key], b[key])
     assert int(a["flag"]) == 0 and int(a["flag_ref"]) == 0 and abs(int(a["it"]) - int(a["it_ref"])) <= 2
     assert _rel(a[key], a[key + "_ref"]) < 1e-10, _rel(a[key], a[key + "_ref"])
-    if tag == "D":
+    if holstein:
         assert _rel(a["Xp"], a["Xp_ref"]) < 1e-10 and _rel(a["Xm"], a["Xm_ref"]) < 1e-10
 
 
@@ -372,7 +375,10 @@ def test_sharded_hmc_update_vs_one_handle(tmp_path, world, nb):
     """One HMC update of BASELINE config 4 (Holstein honeycomb L = 12, Ntau = 120) on a lattice sharded over 2 / 4 ranks —
     elph_hmc_update on the slab handle: sharded solves, own-row energies summed over the ranks, ghost rows of ϕ± and of the fermion force
     from their owners — against the update of ONE handle with the same random numbers: same decision, H, S, K and the field to 1e-9."""
-    res = _run_callers("hmc", "D", tmp_path, world, per_proc=2 if world == 8 else 1, extra_env={"ELPH_TEST_NB": str(nb)})
+    _assert_sharded_update_equals_one_handle(_run_callers("hmc", "D", tmp_path, world, per_proc=2 if world == 8 else 1, extra_env={"ELPH_TEST_NB": str(nb)}))
+
+
+def _assert_sharded_update_equals_one_handle(res):
     a = res[0]
     for b in res[1:]:
         assert int(b["accepted"]) == int(a["accepted"]) and np.array_equal(a["energies"], b["energies"]) and np.array_equal(a["x"], b["x"])
@@ -382,3 +388,38 @@ def test_sharded_hmc_update_vs_one_handle(tmp_path, world, nb):
     assert abs(e[2] - er[2]) < 1e-8 * abs(er[2]) and abs(e[3] - er[3]) < 1e-8 * abs(er[3])
     assert _rel(a["x"], a["x_ref"]) < 1e-9 and _rel(a["v"], a["v_ref"]) < 1e-8
     assert abs(float(a["iters"]) - float(a["iters_ref"])) <= 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Site-dependent ω, ω₄, λ, λ₂ and μ (tests/site_disorder_cases.py) on a sharded lattice: the slab's slice of every parameter array
+# (elph_shard_fermion_force_holstein; elph_hmc_create on a slab handle), 2 ranks, one process per rank, the assertions of the
+# uniform tests on config D.  The lattice is config y — honeycomb, 6 x 6 cells, 20 time slices: the smallest two-orbital configuration
+# with square cell counts whose slabs pass the ghost-row check at 2 ranks (3 own rows + 1 + 1 ghost rows of the 6; d, 3 x 3 cells, does not).
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+SITE_DISORDER_TAG = "y"
+
+
+def _assert_the_worker_ran_disordered(res, what):
+    """The arrays the worker handed to the library: no two sites of an array alike — λ, λ₂, μ of the whole lattice for the force
+    (the library takes the slab's part), the slab's ω, ω₄, λ, λ₂, μ for elph_hmc_create — and the slabs together hold every site."""
+    if what == "force":
+        for a in res:
+            assert a["force_with"].shape == (3, 72) and all(len(np.unique(row)) == 72 for row in a["force_with"])
+        return
+    for a in res:
+        n = len(a["created_sites"])
+        assert 36 < n < 72 and a["created_with"].shape == (5, n) and all(len(np.unique(row)) == n for row in a["created_with"])
+    assert set(np.concatenate([a["created_sites"] for a in res]).tolist()) == set(range(72))
+
+
+def test_sharded_fermion_force_with_site_disorder(tmp_path):
+    res = _run_callers("force", SITE_DISORDER_TAG, tmp_path, 2, extra_env={"ELPH_TEST_SITE_DISORDER": "1"})
+    _assert_the_worker_ran_disordered(res, "force")
+    _assert_sharded_force_equals_one_handle(res, True)
+
+
+def test_sharded_hmc_update_with_site_disorder(tmp_path):
+    res = _run_callers("hmc", SITE_DISORDER_TAG, tmp_path, 2, extra_env={"ELPH_TEST_SITE_DISORDER": "1", "ELPH_TEST_NB": "1"})
+    _assert_the_worker_ran_disordered(res, "hmc")
+    _assert_sharded_update_equals_one_handle(res)

@@ -28,9 +28,12 @@ def _dynamics(m, nch, with_kpm):
     return H, P
 
 
-def _make(tag, nch, with_kpm=False):
+def _make(tag, nch, with_kpm=False, prepare=None):
+    """prepare(m): called on the model before anything reads its parameter arrays."""
     from elphdynamics_amd import configs
     m = configs.make_model(tag, tol=1e-9, maxiter=20000)
+    if prepare is not None:
+        prepare(m)
     H, P = _dynamics(m, nch, with_kpm)
     return m, H, P
 
@@ -81,9 +84,13 @@ PARITY = [("b", k, nch, kpm) for k in (sur.REFLECT, sur.SWAP) for nch in (1, 3) 
 def test_device_drawn_moves_equal_their_explicit_replay(tag, kind, nch, with_kpm):
     """Three moves drawn and decided on the device against the same three moves handed to special_move_chains_ one by one, with the
     columns of the restated draw and Rp, Rm, kpm_randn, u of the batch numbers the order draw, Rp, Rm, [kpm_randn], u gives."""
+    check_device_drawn_moves_equal_their_explicit_replay(tag, kind, nch, with_kpm)
+
+
+def check_device_drawn_moves_equal_their_explicit_replay(tag, kind, nch, with_kpm, prepare=None):
     from elphdynamics_amd import hmc
     nmoves = 3
-    m, H, P = _make(tag, nch, with_kpm)
+    m, H, P = _make(tag, nch, with_kpm, prepare)
     X0 = _fields(m, nch)
     _push(m, H, X0)
     H.device_rng_(SEED)
@@ -91,7 +98,7 @@ def test_device_drawn_moves_equal_their_explicit_replay(tag, kind, nch, with_kpm
     assert a.accepted.shape == (nmoves, nch) and a.accepted.dtype == bool
     Xa, nb = _pull(m, H), _batches(m)
     m.close()
-    m, H, P = _make(tag, nch, with_kpm)
+    m, H, P = _make(tag, nch, with_kpm, prepare)
     _push(m, H, X0)
     b = sur.replay(m, H, kind, nmoves, SEED, with_kpm, P, X0)
     Xb = _pull(m, H)
