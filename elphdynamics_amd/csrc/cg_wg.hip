@@ -492,6 +492,95 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                     for (int q = 0; q < 4; ++q) w[j0 + i][q] = w[j0 + i][q] - sg * (EXPV(j0 + i + 1, q) * gq[i][q]);      // z(t0+j0+i)
                 }
             }
+        } else if constexpr (SQ && !SSH && UNI && T == 4) {
+            // 4 slices per wave: the arithmetic of the branch below in another interleaving.  The y-odd colour's crossing (ds_bpermute; the
+            // eight waves of the workgroup queue at the CU's one LDS crossbar) is ISSUED for a pair of slabs and APPLIED only after work that
+            // does not need it (cg_wg_dev.h: sq_cross_issue / sq_cross_apply), and the slices of exp(-dtau V) and of r that a reverse
+            // batch reads from LDS are all requested at once, one colour before they are used — LDS operations return in order, so a
+            // read behind a crossing waits for the crossing and a read that is waited for at once exposes its whole latency.  Every fma
+            // keeps its operands and every sum its (slice, register) order: the same bits.  The colours stay colour-major over the slabs:
+            // a slab-PAIR-major forward sweep (colours 0 .. 2 of the next pair under a pair's crossing, 52 vector instructions of cover
+            // instead of 12 .. 26) measured 3 % SLOWER than the parent — consecutive colours of one pair depend on each other, colours of
+            // different pairs do not (profiles/wg_sweep_order).
+#pragma unroll
+            for (int k = 0; k <= T; ++k)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[k][q] = EXPV(k, q) * p[k][q];
+            auto fwd_tail = [&](auto kc) __attribute__((always_inline)) {              // w(t0+k) from the swept slab k
+                constexpr int k = decltype(kc)::value;
+                const double sg = sgn(wrap(t0 + k)) * X.k4;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[k][q] = p[k + 1][q] - sg * w[k][q];
+            };
+            using std::integral_constant;
+            using SX = SqCtx<UNI>;
+            double c0[2], c1[2], d0[2], d1[2], e0[1], e1[1];
+            // forward sweeps (y-odd is the last colour): the crossing of slabs 0, 1 under the y-even colour of slabs 2 .. 4, that of slabs
+            // 2, 3 under the epilogue of slabs 0, 1, that of slab 4 under the epilogue of slabs 2, 3 — and between those two the crossing
+            // of the FIRST reverse batch (y-odd is its first colour; w(t0+1), w(t0+2) are final by then)
+            sq_pairs<T + 1, 0, 0, SX>(w, X); sq_pairs<T + 1, 0, 1, SX>(w, X);
+            sq_colour<2, 2, 0, SX>(&w[0], X);
+            sq_cross_issue<2, SX>(&w[0], X, c0, c1);
+            sq_colour<2, 2, 2, SX>(&w[2], X); sq_colour<1, 2, 4, SX>(&w[4], X);
+            sq_cross_apply<2, 0, SX>(&w[0], X, c0, c1);
+            sq_cross_issue<2, SX>(&w[2], X, c0, c1);
+            fwd_tail(integral_constant<int, 0>()); fwd_tail(integral_constant<int, 1>());
+            __builtin_amdgcn_sched_barrier(0);
+            sq_cross_apply<2, 2, SX>(&w[2], X, c0, c1);
+            sq_cross_issue<1, SX>(&w[4], X, e0, e1);
+            fwd_tail(integral_constant<int, 2>());
+            __builtin_amdgcn_sched_barrier(0);
+            sq_cross_issue<2, SX>(&w[1], X, d0, d1);
+            fwd_tail(integral_constant<int, 3>());
+            __builtin_amdgcn_sched_barrier(0);
+            sq_cross_apply<1, 4, SX>(&w[4], X, e0, e1);
+            fwd_tail(integral_constant<int, 4>());
+            __builtin_amdgcn_sched_barrier(0);
+            // a reverse batch of two slabs whose crossing (x0, x1) is in flight: z(t0+j0+i) and the batch's share of the four sums, in the
+            // order of the branch below.  exp(-dtau V) is requested before the x-odd colour; r before the NEXT batch's crossing is issued,
+            // into the registers the swept slabs leave free — that crossing then has the 32 fma of the sums to itself.
+            auto rev_batch = [&](auto j0c, const double (&x0)[2], const double (&x1)[2], auto next_crossing) __attribute__((always_inline)) {
+                constexpr int j0 = decltype(j0c)::value;
+                double gq[2][4], ev[2][4], rv[2][4];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) gq[i][q] = w[j0 + i + 1][q];
+                sq_cross_apply<2, 0, SX>(gq, X, x0, x1);
+                sq_colour<2, 2, 0, SX>(gq, X);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) ev[i][q] = EXPV(j0 + i + 1, q);
+                __builtin_amdgcn_sched_barrier(0);
+                sq_colour<2, 1, 0, SX>(gq, X);
+                sq_colour<2, 0, 0, SX>(gq, X);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const double sg = sgn(wrap(t0 + j0 + i + 1)) * X.k4;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) w[j0 + i][q] = w[j0 + i][q] - sg * (ev[i][q] * gq[i][q]);    // z(t0+j0+i)
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) rv[i][q] = rl[(j0 + i) * HSL + lr + q * LSL];
+                __builtin_amdgcn_sched_barrier(0);
+                next_crossing();
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        b_pz += p[j0 + i + 1][q] * w[j0 + i][q];
+                        b_rz += rv[i][q] * w[j0 + i][q];
+                        b_zz += w[j0 + i][q] * w[j0 + i][q];
+                        b_rr += rv[i][q] * rv[i][q];
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            rev_batch(integral_constant<int, 0>(), d0, d1, [&]() __attribute__((always_inline)) { sq_cross_issue<2, SX>(&w[3], X, c0, c1); });
+            rev_batch(integral_constant<int, 2>(), c0, c1, []() {});
         } else if constexpr (SQ) {
 #pragma unroll
             for (int k = 0; k <= T; ++k)

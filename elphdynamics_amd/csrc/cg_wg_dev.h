@@ -102,7 +102,9 @@ __device__ __forceinline__ void sweepN(double *buf, const unsigned (&ij)[MC * ((
 // the sweep applies the bracket (ONE fma per site and colour instead of mul + fma) and hands the factor k4 = c^4 to the caller,
 // who folds it into the constant of the fma that consumes the swept vector.  Same operator in real arithmetic; against the
 // reference's  c y_i + s y_j  it differs by rounding only (a few ulp per sweep; parity tolerances in tests/ unchanged).
-// f64 instructions are what the two waves of a SIMD compete for in this kernel (profiles/r02/wg_phase_stamps.log).
+// The two waves of a SIMD do NOT compete for f64 issue in this kernel: at 4 slices per wave a wave's vector ALU is active in 22 % of its
+// cycles and the wave is parked at an s_waitcnt or a barrier in half of them (SQ counters, profiles/wg_sweep_order) — what an fma
+// saved buys is small next to a latency taken off the chain (LDS reads, crossings, the meeting).
 // (SSH — one table set per time slice: SqSsh below.  Round 2 built it with a (cosh, sinh) per site and colour, one slice per wave,
 // under the two-meeting iteration whose team of 20 workgroups set the time — no gain then.)
 template <bool UNI>
@@ -225,6 +227,28 @@ __device__ __forceinline__ void sq_sweepC(double (&v)[NS][4], const CTX &X) {
 template <int NS, bool REVERSE, bool UNI>
 __device__ __forceinline__ void sq_sweepN(double (&v)[NS][4], const SqCtx<UNI> &X) { sq_sweepC<NS, REVERSE, SqCtx<UNI>>(v, X); }
 
+// The y-odd colour in two halves, for a caller that puts work of its own between them (4 slices per wave, k_cg_wg).  All eight waves
+// of a workgroup reach this colour together and the CU's one LDS crossbar serves their ds_bpermute one after the other: inside one
+// sq_colour region a wave has only the quad swap of registers 2, 3 to do meanwhile.  Split, the crossing of CNT slabs is issued
+// (sq_cross_issue, a scheduling region of its own), the caller runs whatever does not need v[..][0..1] of those slabs, and
+// sq_cross_apply takes the colour's arithmetic — the same fma on the same operands as sq_colour<CNT, 3>, so the same bits.
+template <int CNT, class CTX>
+__device__ __forceinline__ void sq_cross_issue(const double (*v)[4], const CTX &X, double (&c0)[CNT], double (&c1)[CNT]) {
+#pragma unroll
+    for (int n = 0; n < CNT; ++n) { c0[n] = __shfl(v[n][0], X.yx, WAVE); c1[n] = __shfl(v[n][1], X.yx, WAVE); }
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int CNT, int N0, class CTX>
+__device__ __forceinline__ void sq_cross_apply(double (*v)[4], const CTX &X, const double (&c0)[CNT], const double (&c1)[CNT]) {
+#pragma unroll
+    for (int n = 0; n < CNT; ++n) {
+        const double t2 = dpp_f64<0xB1>(v[n][2]), t3 = dpp_f64<0xB1>(v[n][3]);           // quad_perm [1,0,3,2]
+        v[n][2] = X.up(N0 + n, 3, 2, v[n][2], t2); v[n][3] = X.up(N0 + n, 3, 3, v[n][3], t3);
+    }
+#pragma unroll
+    for (int n = 0; n < CNT; ++n) { v[n][0] = X.up(N0 + n, 3, 0, v[n][0], c0[n]); v[n][1] = X.up(N0 + n, 3, 1, v[n][1], c1[n]); }
+    __builtin_amdgcn_sched_barrier(0);
+}
 // SSH: slab n with table set SOFF + n
 template <int NS, bool REVERSE, int SOFF, int NREG, bool LDS0>
 __device__ __forceinline__ void sq_sweepS(double (&v)[NS][4], const SqSsh<NREG, LDS0> &X) {
