@@ -1,7 +1,7 @@
 """Bond correlations of every chain resident in a handle (a lockstep run: hmc.update_chains_, langevin.evolve_): the chain-aware twin
 of bond_measurements.py, beside chain_measurements.py the way bond_measurements.py stands beside measurements.py.  One BondContainer per
 chain, each with its own data folder; on the device all chains are accumulated by the same launches (elph_bond_chains_*,
-csrc/bondcorr_chains.hip), the chain a grid axis.
+csrc/bondcorr.hip), the chain a grid axis.
 
     cb = initialize_chain_bond_container(model, info, datafolders, bond_definitions=None)   one container per chain (:156-175, :767-819 each)
     initialize_bond_folders_(cb)                                                            the inter-site parts of :420-540 per chain

@@ -1,6 +1,6 @@
 """Measurements of every chain resident in a handle (a lockstep run: hmc.update_chains_, langevin.evolve_): the chain-aware twin of
 measurements.py.  One MeasurementsContainer per chain, each with its own data folder; on the device all chains are accumulated by the
-same launches (elph_meas_chains_*, csrc/measure_chains.hip), the chain a grid axis.
+same launches (elph_meas_chains_*, csrc/measure.hip), the chain a grid axis.
 
     cm = initialize_chain_measurements_container(model, info, datafolders)     one container per chain (Measurements.jl:27-178 each)
     initialize_measurement_folders_(cm)                                        :343-540 per chain

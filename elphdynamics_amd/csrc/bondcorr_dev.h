@@ -1,11 +1,10 @@
-// bondcorr_dev.h — what the bond-correlation units share (bondcorr.hip and bondcorr_chains.hip: Holstein, ssh_bondcorr.hip and
-// ssh_bondcorr_chains.hip: bond phonons): the kernels of
+// bondcorr_dev.h — what the bond-correlation units share (bondcorr.hip: Holstein, ssh_bondcorr.hip: bond phonons, currcorr.hip): the
+// kernels of
 //   measure_BondBond!         Measurements.jl:1663-1785
 //   measure_BondPairGreens!   Measurements.jl:2390-2483
 // which read model.bond_definitions and nothing else of the model, their state, and the host steps around them (the definitions'
-// table, create, the launches of one pair of vectors).  One text of each kernel body, shared by the single-configuration kernels and the
-// chain kernels k_bcc_* (every resident chain at once: bondcorr_chains.hip, ssh_bondcorr_chains.hip); the formulas and layouts are in
-// bondcorr.hip's header.
+// table, create, the launches of one pair of vectors).  The chain is the last grid axis of every kernel and nchains = 1 is the single
+// configuration; the formulas and layouts are in bondcorr.hip's header.
 #pragma once
 
 #include <vector>
@@ -26,7 +25,7 @@ using BondReq = CorrReq<NBOND>;          // pairs (n″, n′)
 
 struct BondState {
     int ns = 1, L1 = 1, L2 = 1, L3 = 1, nc = 1, ndef = 0;
-    int nchains = 1;                // configurations the buffers serve: 1, or every resident chain (bondcorr_chains.hip)
+    int nchains = 1;                // configurations the buffers serve: 1, or every resident chain
     int k0 = 0, k1 = 0;             // the fields [k0, k1) are transformed
     int *defs = nullptr;            // [ndef][DEFW]
     CorrPlan<NBOND> cr;             // ONE configuration's plan; cr.acc: [chain][BondBond | BondPairGreens], cr.req bound to chain 0
@@ -48,11 +47,10 @@ __device__ __forceinline__ int shifted_cell(int cell, const int *dv, int L1, int
     return cell_plus(cell, dv[2], dv[3], dv[4], L1, L2, L3);
 }
 
-// ---- what one thread or workgroup does in each kernel, shared by the single-configuration kernels and the chain kernels below
-// (every resident chain, the chain a grid axis): the two differ only in where a workgroup finds its chain's block.
-// The buffers carry the chain between the definition (or listed pair) and the time axis — f: [NFIELD][ndef][chain][L][nc], nu the same
-// with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc] — so a body takes its chain's block of definition (pair) 0 and the distance
-// between two definitions (pairs); with one configuration that distance is the block itself.
+// ---- what one thread or workgroup does in each kernel.  The buffers carry the chain between the definition (or listed pair) and the
+// time axis — f: [NFIELD][ndef][chain][L][nc], nu the same with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc] — so a body takes
+// its chain's block of definition (pair) 0 and the distance between two definitions (pairs); with one configuration that distance is
+// the block itself.
 
 // The six fields of every definition (header of bondcorr.hip) for idx = (cell, τ, definition), first fastest: gathers inside one time
 // slice of layout S.  f: the chain's block of field 0 of definition 0; dstride: doubles between two definitions.
@@ -149,17 +147,10 @@ __device__ __forceinline__ void bc_fold_at(const BondReq &rq, int which, long lo
     rq.acc[which][acc_off + idx] += v;
 }
 
-// ---- the kernels of one configuration
-
-// One thread per (cell, τ, definition).
-__global__ void __launch_bounds__(BC_TPB) k_bc_fields(double *__restrict__ f, const double *__restrict__ X1, const double *__restrict__ X2,
-                                                      const double *__restrict__ R1, const double *__restrict__ R2, const int *__restrict__ defs,
-                                                      int N, int L, int ns, int L1, int L2, int L3, int ndef) {
-    bc_fields_at(f, X1, X2, R1, R2, defs, N, L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * BC_TPB + threadIdx.x, (size_t)L * (L1 * L2 * L3));
-}
+// ---- the kernels: the chain is the last grid axis; per: L nc, slice: Lh nc
 
 // One workgroup per (frequency, slice of Lh frequencies): the cell-axis DFT of one frequency slice, in place; a slice is a field of a
-// definition (of a chain: the chain kernels launch it over their longer list of slices as it is).  LDS: 2 buffers of nc complex.
+// definition of a chain.  LDS: 2 buffers of nc complex.
 __global__ void __launch_bounds__(BC_TPB) k_bc_spatial_fwd(double2 *__restrict__ nu, int Lh, int L1, int L2, int L3,
                                                            const double2 *__restrict__ tw) {
     extern __shared__ double2 lds[];
@@ -171,34 +162,17 @@ __global__ void __launch_bounds__(BC_TPB) k_bc_spatial_fwd(double2 *__restrict__
     for (int q = threadIdx.x; q < nc; q += BC_TPB) s[q] = F[q];
 }
 
-// One workgroup per (frequency, listed pair).  nu: the spectra of field 0.  LDS: 2 buffers of nc complex.
-__global__ void __launch_bounds__(BC_TPB) k_bc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, BondReq rq, int Lh, int ndef,
-                                                         int L1, int L2, int L3, const double2 *__restrict__ tw, double norm) {
-    extern __shared__ double2 lds[];
-    const int nc = L1 * L2 * L3;
-    bc_correlate_slice(Y + ((size_t)blockIdx.y * Lh + blockIdx.x) * nc, nu, rq, blockIdx.y, blockIdx.x, ndef, L1, L2, L3, tw, norm, (size_t)Lh * nc, lds);
-}
-
-// One thread per (τ, cell, listed pair) of correlation blockIdx.y.
-__global__ void __launch_bounds__(BC_TPB) k_bc_fold(BondReq rq, const double *__restrict__ B, const double *__restrict__ G0,
-                                                    const int *__restrict__ defs, int L, int ns, int L1, int L2, int L3) {
-    bc_fold_at(rq, blockIdx.y, (long long)blockIdx.x * BC_TPB + threadIdx.x, B, G0, defs, L, ns, L1, L2, L3, (size_t)L * (L1 * L2 * L3), 0);
-}
-
-// ---- the kernels of every resident chain at once (bondcorr_chains.hip, ssh_bondcorr_chains.hip): the chain is the last grid axis; per: L nc,
-// slice: Lh nc
-
 // One thread per (cell, tau, definition) of chain blockIdx.y.  X1 .. R2: chain 0's vectors, chain c's c L N further on.
-__global__ void __launch_bounds__(BC_TPB) k_bcc_fields(double *__restrict__ f, ElphGreensPair v, const int *__restrict__ defs, int N, int L, int ns,
-                                                       int L1, int L2, int L3, int ndef, int nchains) {
+__global__ void __launch_bounds__(BC_TPB) k_bc_fields(double *__restrict__ f, ElphGreensPair v, const int *__restrict__ defs, int N, int L, int ns,
+                                                      int L1, int L2, int L3, int ndef, int nchains) {
     const size_t ch = blockIdx.y, o = ch * L * N, per = (size_t)L * (L1 * L2 * L3);
     bc_fields_at(f + ch * per, v.X1 + o, v.X2 + o, v.R1 + o, v.R2 + o, defs, N, L, ns, L1, L2, L3, ndef, (long long)blockIdx.x * BC_TPB + threadIdx.x,
                  (size_t)nchains * per);
 }
 
 // One workgroup per (frequency, listed pair, chain).  LDS: 2 buffers of nc complex.
-__global__ void __launch_bounds__(BC_TPB) k_bcc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, BondReq rq, int Lh, int ndef, int L1,
-                                                          int L2, int L3, const double2 *__restrict__ tw, double norm, int nchains) {
+__global__ void __launch_bounds__(BC_TPB) k_bc_correlate(double2 *__restrict__ Y, const double2 *__restrict__ nu, BondReq rq, int Lh, int ndef, int L1,
+                                                         int L2, int L3, const double2 *__restrict__ tw, double norm, int nchains) {
     extern __shared__ double2 lds[];
     const int nc = L1 * L2 * L3;
     const size_t ch = blockIdx.z, slice = (size_t)Lh * nc;
@@ -208,9 +182,9 @@ __global__ void __launch_bounds__(BC_TPB) k_bcc_correlate(double2 *__restrict__ 
 
 // One thread per (tau, cell, listed pair) of correlation blockIdx.y of chain blockIdx.z.  C0: table 0 of chain 0; block: doubles of a
 // chain's accumulators.
-__global__ void __launch_bounds__(BC_TPB) k_bcc_fold(BondReq rq, const double *__restrict__ B, const double *__restrict__ C0,
-                                                     const int *__restrict__ defs, int N, int L, int ns, int L1, int L2, int L3, int nchains,
-                                                     size_t block) {
+__global__ void __launch_bounds__(BC_TPB) k_bc_fold(BondReq rq, const double *__restrict__ B, const double *__restrict__ C0,
+                                                    const int *__restrict__ defs, int N, int L, int ns, int L1, int L2, int L3, int nchains,
+                                                    size_t block) {
     const size_t ch = blockIdx.z, per = (size_t)L * (L1 * L2 * L3);
     bc_fold_at(rq, blockIdx.y, (long long)blockIdx.x * BC_TPB + threadIdx.x, B + ch * per, C0 + ch * L * ns * N, defs, L, ns, L1, L2, L3,
                (size_t)nchains * per, ch * block);
@@ -272,11 +246,30 @@ void bc_free(BondState *m) {
     delete m;
 }
 
+// The chain multiplies the slices of the cell-axis DFT (grid y) and the right-hand sides of the tau-DFTs (grid z): nk fields per
+// definition and nlist listed pairs must fit the grid.  Refuses only what would fail at launch.
+int bc_check_grid(const CorrWords &w, long long nk, int n_def, long long nlist, int nchains) {
+    constexpr long long GRID_YZ_MAX = 65535;
+    if (nk * n_def * nchains > GRID_YZ_MAX) {
+        elph_set_error("%s: %lld fields x %d bond definitions x %d chains = %lld slices exceed the grid's %lld", w.prefix, nk, n_def, nchains,
+                       nk * n_def * nchains, GRID_YZ_MAX);
+        return ELPH_E_UNSUPPORTED;
+    }
+    if (nlist * nchains > GRID_YZ_MAX) {
+        elph_set_error("%s: %lld listed pairs x %d chains = %lld transforms exceed the grid's %lld", w.prefix, nlist, nchains, nlist * nchains,
+                       GRID_YZ_MAX);
+        return ELPH_E_UNSUPPORTED;
+    }
+    return ELPH_OK;
+}
+
+// the fields per definition a BondBond / BondPairGreens plan transforms
+long long bc_fields_of(const CorrPlan<NBOND> &plan) { return (plan.req.np[BONDBOND] ? 4 : 0) + (plan.req.np[BONDPAIR] ? NFIELD - 4 : 0); }
+
 // The state of a planned request for nchains configurations: allocations, the definitions and pairs on the device, zeroed accumulators,
-// the LDS of this unit's k_bc_spatial_fwd and of `correlate`, the unit's kernel of bc_correlate_slice.  *out stays null on failure.
-template <class K>
+// the LDS of this unit's k_bc_spatial_fwd and k_bc_correlate.  *out stays null on failure.
 int bc_make(BondState **out, elph_handle_s *h, const CorrWords &w, const ElphGreensView &g, const CorrPlan<NBOND> &plan, const std::vector<int> &defs,
-            int n_def, int nchains, K correlate) {
+            int n_def, int nchains) {
     const int L = (int)h->L, Lh = L / 2 + 1, nc = g.nc;
     BondState *m = new BondState;
     m->cr = plan;
@@ -285,66 +278,46 @@ int bc_make(BondState **out, elph_handle_s *h, const CorrWords &w, const ElphGre
     m->k1 = plan.req.np[BONDPAIR] ? NFIELD : 4;
     const size_t nch = (size_t)nchains, nP = nch * plan.npairs, nf = nch * NFIELD * n_def;
     CorrFirstError ok;
-    const bool allocated = ok(corr_alloc(&m->defs, defs.size())) && ok(corr_alloc(&m->cr.pairs, m->cr.prs.size())) &&
-        ok(corr_alloc(&m->cr.acc, nch * m->cr.total)) && ok(corr_alloc(&m->f, nf * L * nc)) && ok(corr_alloc(&m->nu, nf * Lh * nc)) &&
-        ok(corr_alloc(&m->Y, nP * Lh * nc)) && ok(corr_alloc(&m->B, nP * L * nc));
-    if (allocated && ok(corr_up(m->defs, defs.data(), defs.size() * sizeof(int)))) ok(corr_upload(m->cr, w.prefix));   // zeroes chain 0's block
-    if (ok.rc == ELPH_OK && nchains > 1 && hipMemset(m->cr.acc, 0, nch * m->cr.total * sizeof(double)) != hipSuccess) {
-        elph_set_error("%s: hipMemset failed", w.prefix);
-        ok(ELPH_E_HIP);
-    }
-    if (ok.rc == ELPH_OK && ok(bc_allow_lds(k_bc_spatial_fwd, w, nc))) ok(bc_allow_lds(correlate, w, nc));
+    const bool allocated = ok(corr_alloc(&m->defs, defs.size())) && ok(corr_alloc(m->cr, nch)) && ok(corr_alloc(&m->f, nf * L * nc)) &&
+        ok(corr_alloc(&m->nu, nf * Lh * nc)) && ok(corr_alloc(&m->Y, nP * Lh * nc)) && ok(corr_alloc(&m->B, nP * L * nc));
+    if (allocated && ok(corr_up(m->defs, defs.data(), defs.size() * sizeof(int)))) ok(corr_upload(m->cr, w.prefix, nch));
+    if (ok.rc == ELPH_OK && ok(bc_allow_lds(k_bc_spatial_fwd, w, nc))) ok(bc_allow_lds(k_bc_correlate, w, nc));
     if (ok.rc != ELPH_OK) { bc_free(m); return ok.rc; }
     *out = m;
     return ELPH_OK;
 }
 
-// BondBond and BondPairGreens of one pair of vectors v, after its elph_i_greens_pair_dev (whose G[Δ,0] the δ terms read), into m's
-// accumulators.
-int bc_accumulate_pair(elph_handle_s *h, BondState *m, const ElphGreensView &g, const ElphGreensPair &v) {
-    const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = m->ns, nc = m->nc, ndef = m->ndef;
-    const int nP = m->cr.npairs, nk = m->k1 - m->k0;
-    const size_t shm = bc_lds_bytes(nc);
-    const long long nfld = (long long)L * nc * ndef;
-    const double norm = 1.0 / ((double)L * (double)nc * (double)nc);   // 1/(L Nc)² in all: the other 1/L is in the inverse τ table
-    hipLaunchKernelGGL(k_bc_fields, dim3((unsigned)((nfld + BC_TPB - 1) / BC_TPB)), dim3(BC_TPB), 0, h->stream, m->f, v.X1, v.X2, v.R1, v.R2, m->defs, N, L,
-                       ns, m->L1, m->L2, m->L3, ndef);
-    RC(elph_launch_check("k_bc_fields"));
-    double2 *nu = m->nu + (size_t)m->k0 * ndef * Lh * nc;
-    RC(elph_dft_fwd_plain(h, nu, m->f + (size_t)m->k0 * ndef * L * nc, nc, nk * ndef));
-    hipLaunchKernelGGL(k_bc_spatial_fwd, dim3((unsigned)Lh, (unsigned)(nk * ndef)), dim3(BC_TPB), shm, h->stream, nu, Lh, m->L1, m->L2, m->L3, g.tw);
-    RC(elph_launch_check("k_bc_spatial_fwd"));
-    hipLaunchKernelGGL(k_bc_correlate, dim3((unsigned)Lh, (unsigned)nP), dim3(BC_TPB), shm, h->stream, m->Y, m->nu, m->cr.req, Lh, ndef, m->L1, m->L2,
-                       m->L3, g.tw, norm);
-    RC(elph_launch_check("k_bc_correlate"));
-    RC(elph_dft_inv_plain(h, m->B, m->Y, nc, nP));
-    hipLaunchKernelGGL(k_bc_fold, dim3((unsigned)((m->cr.fold_max + BC_TPB - 1) / BC_TPB), NBOND), dim3(BC_TPB), 0, h->stream, m->cr.req, m->B, g.C,
-                       m->defs, L, ns, m->L1, m->L2, m->L3);
-    return elph_launch_check("k_bc_fold");
-}
-
 // BondBond and BondPairGreens of one pair of vectors v of every chain (m->nchains), after its elph_i_greens_setup_chains_dev into S, into
 // m's accumulators [chain][BondBond | BondPairGreens].
-int bc_accumulate_pair_chains(elph_handle_s *h, BondState *m, const ElphGreensView &g, const ElphGreensChainScratch &S, const ElphGreensPair &v) {
+int bc_accumulate_pair(elph_handle_s *h, BondState *m, const ElphGreensView &g, const ElphGreensChainScratch &S, const ElphGreensPair &v) {
     const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = m->ns, nc = m->nc, ndef = m->ndef, nch = m->nchains;
     const int nP = m->cr.npairs, nk = m->k1 - m->k0;
     const size_t shm = bc_lds_bytes(nc);
     const long long nfld = (long long)L * nc * ndef;
     const double norm = 1.0 / ((double)L * (double)nc * (double)nc);   // 1/(L Nc)² in all: the other 1/L is in the inverse τ table
-    hipLaunchKernelGGL(k_bcc_fields, dim3((unsigned)((nfld + BC_TPB - 1) / BC_TPB), (unsigned)nch), dim3(BC_TPB), 0, h->stream, m->f, v, m->defs, N, L, ns,
+    hipLaunchKernelGGL(k_bc_fields, dim3((unsigned)((nfld + BC_TPB - 1) / BC_TPB), (unsigned)nch), dim3(BC_TPB), 0, h->stream, m->f, v, m->defs, N, L, ns,
                        m->L1, m->L2, m->L3, ndef, nch);
-    RC(elph_launch_check("k_bcc_fields"));
+    RC(elph_launch_check("k_bc_fields"));
     double2 *nu = m->nu + (size_t)m->k0 * ndef * nch * Lh * nc;
     RC(elph_dft_fwd_plain(h, nu, m->f + (size_t)m->k0 * ndef * nch * L * nc, nc, nk * ndef * nch));
     hipLaunchKernelGGL(k_bc_spatial_fwd, dim3((unsigned)Lh, (unsigned)(nk * ndef * nch)), dim3(BC_TPB), shm, h->stream, nu, Lh, m->L1, m->L2, m->L3, g.tw);
-    RC(elph_launch_check("k_bc_spatial_fwd(chains)"));
-    hipLaunchKernelGGL(k_bcc_correlate, dim3((unsigned)Lh, (unsigned)nP, (unsigned)nch), dim3(BC_TPB), shm, h->stream, m->Y, m->nu, m->cr.req, Lh, ndef,
+    RC(elph_launch_check("k_bc_spatial_fwd"));
+    hipLaunchKernelGGL(k_bc_correlate, dim3((unsigned)Lh, (unsigned)nP, (unsigned)nch), dim3(BC_TPB), shm, h->stream, m->Y, m->nu, m->cr.req, Lh, ndef,
                        m->L1, m->L2, m->L3, g.tw, norm, nch);
-    RC(elph_launch_check("k_bcc_correlate"));
+    RC(elph_launch_check("k_bc_correlate"));
     RC(elph_dft_inv_plain(h, m->B, m->Y, nc, nP * nch));
-    hipLaunchKernelGGL(k_bcc_fold, dim3((unsigned)((m->cr.fold_max + BC_TPB - 1) / BC_TPB), NBOND, (unsigned)nch), dim3(BC_TPB), 0, h->stream, m->cr.req,
+    hipLaunchKernelGGL(k_bc_fold, dim3((unsigned)((m->cr.fold_max + BC_TPB - 1) / BC_TPB), NBOND, (unsigned)nch), dim3(BC_TPB), 0, h->stream, m->cr.req,
                        m->B, S.C, m->defs, N, L, ns, m->L1, m->L2, m->L3, nch, m->cr.total);
-    return elph_launch_check("k_bcc_fold");
+    return elph_launch_check("k_bc_fold");
 }
+
+// a chain's [BondBond | BondPairGreens] to the host / the accumulators of all chains zeroed
+int bc_fetch(elph_handle_s *h, const BondState *m, int chain, double *BondBond, double *BondPairGreens) {
+    std::vector<double> host;
+    double *outs[NBOND] = {BondBond, BondPairGreens};
+    return corr_fetch(h, m->cr, host, outs, chain);
+}
+
+int bc_reset(elph_handle_s *h, const BondState *m) { return corr_reset(h, m->cr, (size_t)m->nchains); }
 
 }  // namespace

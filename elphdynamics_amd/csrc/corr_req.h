@@ -1,8 +1,10 @@
-// corr_req.h — the request for a group of correlation functions, shared by measure.hip and measure_chains.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2),
-// ssh_measure.hip and ssh_measure_chains.hip (on-site and PhononGreens over phonon types, N = 5) and ssh_bondcorr.hip (bonds, N = 2, and CurrentCurrent, N = 1):
-// the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group does with its one
-// accumulator allocation [lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's accumulator is
-// [L0][L1][L2][L3][n_p] doubles, first index fastest, L0 = L + 1 (time-dependent, tau = beta included) or 1 (equal-time).
+// corr_req.h — the request for a group of correlation functions, shared by measure.hip (on-site, N = 5), bondcorr.hip (bonds, N = 2),
+// ssh_measure.hip (on-site and PhononGreens over phonon types, N = 5), ssh_bondcorr.hip (bonds, N = 2, and CurrentCurrent, N = 1) and
+// currcorr.hip (N = 1): the record the kernels receive by value, the host's bookkeeping with its pure planner, and what every such group
+// does with its one accumulator allocation [chain][lead doubles | the measured correlations]: bind, fetch, reset, free.  A correlation's
+// accumulator is [L0][L1][L2][L3][n_p] doubles, first index fastest, L0 = L + 1 (time-dependent, tau = beta included) or 1 (equal-time).
+// The plan is ONE chain's; a state for nchains chains holds nchains such blocks behind one another, and the kernels find a chain's block
+// from the chain's grid index.  The state checks of the groups' two entry-point families are at the end.
 #pragma once
 
 #include <algorithm>
@@ -37,7 +39,7 @@ struct CorrPlan {
     size_t fold_max = 0;        // elements of the largest correlation
     int nc = 1, npairs = 0;     // cells; listed pairs of all requests
     int *pairs = nullptr;       // device: prs
-    double *acc = nullptr;      // device: [max(total, 1)]
+    double *acc = nullptr;      // device: [chains][total] (at least one double)
     size_t count(int c) const { return (size_t)req.L0[c] * nc * req.np[c]; }
 };
 
@@ -96,16 +98,16 @@ struct CorrFirstError {
 };
 
 template <int N>
-int corr_alloc(CorrPlan<N> &P) {
+int corr_alloc(CorrPlan<N> &P, size_t chains = 1) {
     RC(corr_alloc(&P.pairs, P.prs.size()));
-    return corr_alloc(&P.acc, P.total);
+    return corr_alloc(&P.acc, chains * P.total);
 }
 
-// the pairs to the device, the accumulator zeroed, req bound to the two allocations
+// the pairs to the device, the accumulator of every chain zeroed, req bound to the pairs and to chain 0's block
 template <int N>
-int corr_upload(CorrPlan<N> &P, const char *prefix) {
+int corr_upload(CorrPlan<N> &P, const char *prefix, size_t chains = 1) {
     RC(corr_up(P.pairs, P.prs.data(), P.prs.size() * sizeof(int)));
-    if (hipMemset(P.acc, 0, std::max<size_t>(P.total, 1) * sizeof(double)) != hipSuccess) { elph_set_error("%s: hipMemset failed", prefix); return ELPH_E_HIP; }
+    if (hipMemset(P.acc, 0, std::max<size_t>(chains * P.total, 1) * sizeof(double)) != hipSuccess) { elph_set_error("%s: hipMemset failed", prefix); return ELPH_E_HIP; }
     for (int c = 0; c < N; ++c) {
         P.req.acc[c] = P.acc + P.off[c];
         P.req.pairs[c] = P.pairs + P.pair_off[c];
@@ -113,11 +115,11 @@ int corr_upload(CorrPlan<N> &P, const char *prefix) {
     return ELPH_OK;
 }
 
-// one copy of the accumulator into host; every measured correlation with an output widened to interleaved complex
+// one copy of a chain's block of the accumulator into host; every measured correlation with an output widened to interleaved complex
 template <int N>
-int corr_fetch(elph_handle_s *h, const CorrPlan<N> &P, std::vector<double> &host, double *const *outs) {
+int corr_fetch(elph_handle_s *h, const CorrPlan<N> &P, std::vector<double> &host, double *const *outs, int chain = 0) {
     host.resize(std::max<size_t>(P.total, 1));
-    HIPCHK(hipMemcpyAsync(host.data(), P.acc, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(host.data(), P.acc + (size_t)chain * P.total, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int c = 0; c < N; ++c) {
         if (!outs[c] || !P.req.np[c]) continue;
@@ -128,8 +130,8 @@ int corr_fetch(elph_handle_s *h, const CorrPlan<N> &P, std::vector<double> &host
 }
 
 template <int N>
-int corr_reset(elph_handle_s *h, const CorrPlan<N> &P) {
-    HIPCHK(hipMemsetAsync(P.acc, 0, std::max<size_t>(P.total, 1) * sizeof(double), h->stream));
+int corr_reset(elph_handle_s *h, const CorrPlan<N> &P, size_t chains = 1) {
+    HIPCHK(hipMemsetAsync(P.acc, 0, std::max<size_t>(chains * P.total, 1) * sizeof(double), h->stream));
     return ELPH_OK;
 }
 
@@ -137,7 +139,7 @@ inline void corr_free(std::initializer_list<void *> ptrs) {
     for (void *p : ptrs) if (p) (void)hipFree(p);
 }
 
-// What elph_meas_create and elph_meas_chains_create check of their parameter arrays and bonds before anything is planned or allocated
+// What the creates of measure.hip check of their parameter arrays and bonds before anything is planned or allocated
 // (prefix: the unit's word in the message); bs comes back as [2][nbonds] 0-based sites.
 inline int corr_check_onsite_params(const elph_handle_s *h, const char *prefix, int nc, const double *omega, const double *omega4, const double *lambda,
                            const double *mu, double dtau, int64_t nbonds, int ndef, const int64_t *bond_sites, const double *bond_t,
@@ -160,7 +162,7 @@ inline int corr_check_onsite_params(const elph_handle_s *h, const char *prefix, 
     return ELPH_OK;
 }
 
-// What elph_ssh_meas_create and elph_ssh_meas_chains_create check of their parameter arrays, bonds and phonons before anything is planned
+// What the creates of ssh_measure.hip check of their parameter arrays, bonds and phonons before anything is planned
 // or allocated, and the bond tables they put on the device: bs [2][nbonds] 0-based sites, bph [nbonds] 0-based phonon (-1 on a bare bond),
 // bpar [4][nbonds] t, omega, alpha, alpha2 (zeros on a bare bond), doff / dlist the bonds of every definition in bond order.  ndef comes
 // back as 0 for a model without bonds.
@@ -258,4 +260,45 @@ inline int corr_refuse_model(const elph_handle_s *h, const char *prefix, int kin
 inline int corr_refuse_handle(const elph_handle_s *h, const char *prefix, int kind = ELPH_MODEL_HOLSTEIN) {
     RC(corr_refuse_model(h, prefix, kind));
     return corr_refuse_chains(h, prefix);
+}
+
+// ---- what the _chains entry points ask where the single-configuration ones refuse resident chains
+inline int corr_check_chain_count(const elph_handle_s *h, const char *prefix, int nchains) {
+    if (nchains < 1 || nchains != h->nchains) {
+        elph_set_error("%s: created for %d chains, %d are resident in this handle", prefix, nchains, h->nchains);
+        return ELPH_E_ARG;
+    }
+    return ELPH_OK;
+}
+
+inline int corr_same_chains(const elph_handle_s *h, const char *prefix, int nchains) {
+    if (h->nchains != nchains) {
+        elph_set_error("%s: created for %d chains, %d are resident in this handle now", prefix, nchains, h->nchains);
+        return ELPH_E_STATE;
+    }
+    return ELPH_OK;
+}
+
+inline int corr_check_chain(const char *prefix, int chain, int nchains) {
+    if (chain < 0 || chain >= nchains) { elph_set_error("%s: chain %d outside 0..%d", prefix, chain, nchains - 1); return ELPH_E_ARG; }
+    return ELPH_OK;
+}
+
+// ---- the two ends of every accumulate
+// the estimator as the accumulate of a state for nchains chains needs it: nv / nchains vectors per chain, set
+inline int corr_vectors(elph_handle_s *h, const char *prefix, int nchains, ElphGreensView *g) {
+    RC(elph_i_greens_view(h, g));
+    if (g->nv % nchains) {
+        elph_set_error("%s: the estimator's %d vectors are not a multiple of the %d resident chains", prefix, g->nv, nchains);
+        return ELPH_E_STATE;
+    }
+    if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
+    return ELPH_OK;
+}
+
+// rc of the launches, after a synchronisation on every path: a host pointer the launches copy from is not retained after return
+inline int corr_synchronised(elph_handle_s *h, const char *prefix, int rc) {
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (rc == ELPH_OK && e != hipSuccess) { elph_set_error("%s: hipStreamSynchronize -> %s", prefix, hipGetErrorString(e)); return ELPH_E_HIP; }
+    return rc;
 }

@@ -1,6 +1,6 @@
 // currcorr.hip — CurrentCurrent of the Holstein model accumulated on the device, for one configuration or for EVERY chain resident in
 // the handle at once (DESIGN.md "CurrentCurrent of the Holstein model"):
-//   measure_CurrentCurrent!(holstein)   Measurements.jl:1790-2098     the bodies of currcorr_dev.h, shared with the two SSH units
+//   measure_CurrentCurrent!(holstein)   Measurements.jl:1790-2098     the bodies of currcorr_dev.h, shared with the SSH unit
 //   translational_average!              Utilities.jl:49-60
 // The reference is mirrored as it executes.  Read term by term the method builds the eight fields A0 .. A7 per bond definition of the
 // SSH method (:2100-2384; formulas, notation and the four δ terms in ssh_bondcorr.hip's header), the same eight translation averages
@@ -17,7 +17,7 @@
 // density_moments.hip and snapshots.hip do) and never runs the estimator's pipeline: the estimator's own tables are not touched.  The
 // weights depend on neither the field nor the chain: one table [n_def N_cells], uploaded at create.
 //
-// Layouts are ssh_bondcorr_chains.hip's.  Vector v (0-based) of chain c is row v nchains + c of the estimator, so the v-th vectors of all
+// Layouts are ssh_bondcorr.hip's.  Vector v (0-based) of chain c is row v nchains + c of the estimator, so the v-th vectors of all
 // chains are one block [chain][ndim]; nchains = 1 is the single configuration.  Every buffer carries the chain between the definition
 // (or listed pair) and the time axis:
 //   f  [NCC][ndef][chain][L][nc]     nu [NCC][ndef][chain][Lh][nc]     Y [pair][chain][Lh][nc]     B [pair][chain][L][nc]

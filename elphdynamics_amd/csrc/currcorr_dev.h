@@ -1,16 +1,15 @@
-// currcorr_dev.h — what the three CurrentCurrent units share (ssh_bondcorr.hip: the SSH model, one configuration; ssh_bondcorr_chains.hip:
-// the SSH model, every resident chain at once; currcorr.hip: the Holstein model, one configuration or every resident chain): the bodies
-// of the kernels of
+// currcorr_dev.h — what the two CurrentCurrent units share (ssh_bondcorr.hip: the SSH model; currcorr.hip: the Holstein model; each for
+// one configuration or every resident chain): the bodies of the kernels of
 //   measure_CurrentCurrent!(ssh)        Measurements.jl:2100-2384
 //   measure_CurrentCurrent!(holstein)   Measurements.jl:1790-2098
 // and the checks of the bond and phonon parameters the create calls make.  One text of each kernel body; the formulas, the eight fields
 // A0 .. A7 and the four δ terms are in ssh_bondcorr.hip's header.  The two methods differ in the hopping that weights every factor and
 // in nothing else, so the bodies that weight take the weight of (bond, slice) as a policy W, `double W::operator()(int bond, int t)`:
 // CcModulated for the SSH model, CcLastSlice for the Holstein model.
-// One difference between the units is deliberate and lies outside the bodies: cc_fold_at adds into whatever block rq.acc names.  The two
-// SSH units bind it to the accumulator itself; currcorr.hip binds it to a second block that it zeroes per accumulate and adds to the
+// One difference between the units is deliberate and lies outside the bodies: cc_fold_at adds into whatever block rq.acc names.  The SSH
+// unit binds it to the accumulator itself; currcorr.hip binds it to a second block that it zeroes per accumulate and adds to the
 // accumulator once (k_cur_add), because its contract promises that the same accumulate twice is EXACTLY twice the first, where the SSH
-// units promise that up to rounding (their tests hold 4 eps).  Do not align one with the other without changing that contract and its
+// unit promises that up to rounding (its tests hold 4 eps).  Do not align one with the other without changing that contract and its
 // tests.
 // As in bondcorr_dev.h the buffers carry the chain between the definition (or listed pair) and the time axis — f: [NCC][ndef][chain][L][nc],
 // nu the same with Lh, Y: [pair][chain][Lh][nc], B: [pair][chain][L][nc], part: [pair][chain][L][NDELTA], dl: [pair][chain][NDELTA] — so a

@@ -371,14 +371,12 @@ struct elph_handle_s {
     bool is_slab = false;                  // this handle IS a slab of another handle (never decomposed again)
     void *hmc = nullptr;                   // HmcState (hmc.hip), owned
     void *greens = nullptr;                // GreensState (greens.hip), owned
-    void *meas = nullptr;                  // MeasState (measure.hip), owned; freed with greens
-    void *meas_chains = nullptr;           // MeasChainsState (measure_chains.hip), owned; freed with greens
-    void *bond = nullptr;                  // BondState (bondcorr.hip), owned; freed with greens
-    void *bond_chains = nullptr;           // BondChainsState (bondcorr_chains.hip), owned; freed with greens
-    void *ssh_meas = nullptr;              // SshMeasState (ssh_measure.hip), owned; freed with greens
-    void *ssh_meas_chains = nullptr;       // SshMeasChainsState (ssh_measure_chains.hip), owned; freed with greens
-    void *ssh_bond = nullptr;              // SshBondState (ssh_bondcorr.hip), owned; freed with greens
-    void *ssh_bond_chains = nullptr;       // SshBondChainsState (ssh_bondcorr_chains.hip), owned; freed with greens
+    // the measurement families, two slots each, owned and freed with greens: the single-configuration entry points' state (nchains = 1,
+    // the estimator's own scratch) and the _chains entry points' (every resident chain, scratch of its own) — the same type, side by side
+    void *meas = nullptr, *meas_chains = nullptr;                  // MeasState (measure.hip)
+    void *bond = nullptr, *bond_chains = nullptr;                  // HolsteinBondState (bondcorr.hip)
+    void *ssh_meas = nullptr, *ssh_meas_chains = nullptr;          // SshMeasState (ssh_measure.hip)
+    void *ssh_bond = nullptr, *ssh_bond_chains = nullptr;          // SshBondState (ssh_bondcorr.hip)
     void *density_moments = nullptr;       // DensityMomentsState (density_moments.hip), owned; freed with greens
     void *snapshots = nullptr;             // SnapshotsState (snapshots.hip), owned; freed with greens
     void *current = nullptr;               // CurrentState (currcorr.hip), owned; freed with greens
@@ -461,14 +459,14 @@ int elph_i_shard_global_csbar(elph_handle_s *h, std::vector<double> &cs, int64_t
 int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const double *sbar_host, const double *b_max, const double *b_min);      // elph_api.hip
 int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec, double tol_power, int64_t *iters, int *flag);
 void elph_greens_free(elph_handle_s *h);
-void elph_meas_free(elph_handle_s *h);                                      // measure.hip
-void elph_meas_chains_free(elph_handle_s *h);                               // measure_chains.hip
-void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip
-void elph_bond_chains_free(elph_handle_s *h);                               // bondcorr_chains.hip
-void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip
-void elph_ssh_meas_chains_free(elph_handle_s *h);                           // ssh_measure_chains.hip
-void elph_ssh_bond_free(elph_handle_s *h);                                  // ssh_bondcorr.hip
-void elph_ssh_bond_chains_free(elph_handle_s *h);                           // ssh_bondcorr_chains.hip
+void elph_meas_free(elph_handle_s *h);                                      // measure.hip: the slot meas
+void elph_meas_chains_free(elph_handle_s *h);                               //              the slot meas_chains
+void elph_bond_free(elph_handle_s *h);                                      // bondcorr.hip: bond
+void elph_bond_chains_free(elph_handle_s *h);                               //               bond_chains
+void elph_i_ssh_meas_free(elph_handle_s *h);                                // ssh_measure.hip: ssh_meas (elph_ssh_meas_free is its public form)
+void elph_ssh_meas_chains_free(elph_handle_s *h);                           //                  ssh_meas_chains
+void elph_ssh_bond_free(elph_handle_s *h);                                  // ssh_bondcorr.hip: ssh_bond
+void elph_ssh_bond_chains_free(elph_handle_s *h);                           //                   ssh_bond_chains
 void elph_density_moments_free(elph_handle_s *h);                           // density_moments.hip
 void elph_snapshots_free(elph_handle_s *h);                                 // snapshots.hip
 void elph_current_free(elph_handle_s *h);                                   // currcorr.hip
@@ -476,30 +474,31 @@ void elph_current_free(elph_handle_s *h);                                   // c
 struct ElphGreensView {
     int ns, L1, L2, L3, nc, nv;
     bool have_vectors;
-    const double *C;           // [4][L][ns*N] the real correlations of the last elph_i_greens_setup_dev
+    const double *C;           // [4][L][ns*N] the real correlations of the last pair set up in the estimator's own scratch
     const double *R, *X;       // [nv][ndim] layout S: the noise vectors and M⁻¹R (density_moments.hip, snapshots.hip and currcorr.hip read them in place)
     const double2 *tw;         // [L1 + L2 + L3] exp(-2πi j/Lx), the twiddles of the cell-axis DFTs
 };
 int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v);
-int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand);      // no copy to the host, no synchronisation
-// one step of the loop over pairs i < j of the nv vectors (make_measurements!, Measurements.jl:550-560): setup_dev of the pair, the doubled
-// complex copies refreshed for the last pair only (elph_greens_dev_arrays), and the pair's vectors x = M⁻¹r, r
-struct ElphGreensPair { const double *X1, *X2, *R1, *R2; };
-int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p);
-int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS);
-// the same pipelines for one pair of vectors of every resident chain at once, in scratch the caller owns (measure_chains.hip,
-// bondcorr_chains.hip, ssh_measure_chains.hip, ssh_bondcorr_chains.hip); sizes in elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N
+struct ElphGreensPair { const double *X1, *X2, *R1, *R2; };                // a pair's vectors x = M⁻¹r, r
+// The buffers of the estimator's pipeline (setup!, and the autocorrelation of a field) for one pair of vectors of nchains chains at once;
+// sizes in elements, with Lo2 = ceil(L/2), Lh = L/2 + 1, ncol = n_s N.  The estimator owns one for nchains = 1 — what elph_greens_setup
+// and the single-configuration measurement entry points run in; the _chains entry points allocate their own, so that they leave the
+// estimator's tables alone.
 struct ElphGreensChainScratch {
     int nchains;
     double *f;                 // [8][nchains][ndim] the input fields
     double2 *nuA, *nuP;        // [2][nchains][Lo2][N] twisted, [6][nchains][Lh][N] plain half spectra
     double2 *Y;                // [4][nchains][Lh][ncol] per-frequency spatial correlations
     double *C;                 // [4][nchains][L][ncol] the real tables: table-major, a chain's tables lie nchains L ncol apart
+    double2 *out;              // the estimator's own scratch: [4][2L ncol] the doubled complex copies (elph_greens_dev_arrays); null otherwise
 };
 // the five buffers sized by the estimator's shape for nchains chains (S zero-initialised; on failure what was allocated is freed) / freed
 int elph_i_greens_chain_scratch_alloc(elph_handle_s *h, int nchains, ElphGreensChainScratch *S);
 void elph_i_greens_chain_scratch_free(ElphGreensChainScratch *S);
-int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p);      // p: chain 0's vectors; chain c's lie c ndim further
+const ElphGreensChainScratch *elph_i_greens_own_scratch(elph_handle_s *h);      // the estimator's (null before elph_greens_create)
+// one step of the loop over pairs v1 < v2 of a chain's vectors: the four tables of the pair into S.C; in the estimator's own scratch the
+// doubled complex copies are refreshed for the last pair.  p: chain 0's vectors; chain c's lie c ndim further.  No synchronisation.
+int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p);
 int elph_i_greens_autocorr_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, double *outS, const double *vS);
 // greens_noise.hip: nvec vectors of ndim standard normals of batch `seed` (rng_dev.h), numbered in the reference layout, into dstS (layout S).
 // mapping of Box-Muller pairs to threads: 0 pair-indexed, 1 site-fastest (even Ltau only), -1 the one the estimator ships.  Stream-ordered.

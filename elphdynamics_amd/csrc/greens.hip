@@ -13,10 +13,14 @@
 //   * R and M⁻¹R sit in layout S (slice-major) after the solve, which is the layout the τ-DFT kernels of dft.hip read
 //     with coalesced rows; the spatial transform of one frequency slice (N complex numbers) fits in LDS, so
 //     forward spatial DFT of a and b, the orbital outer product, and the inverse spatial DFT are ONE kernel
-//     (k_gr_spatial, one workgroup per (product, frequency));
+//     (k_gr_spatial, one workgroup per (product, frequency, chain));
 //   * the result is real; the second half of the 2L axis is ∓ the first.  Output arrays keep the reference's shape
 //     Complex[2L, n_s, n_s, L1, L2, L3] (imaginary parts are exact zeros) so measure_GΔ0 & co. index them unchanged.
 // Spatial extents are the lattice's (8…32): direct DFTs with host-built twiddles, exact index reduction.
+//
+// There is ONE pipeline, over an ElphGreensChainScratch: one pair of vectors of every chain the scratch serves, the chain a grid axis.
+// The estimator's own scratch serves one chain (nchains = 1: row n of R is vector n) and alone carries the doubled complex copies; a
+// measurement unit of resident chains brings scratch of its own, so that the estimator's tables are not touched.
 
 #include <cmath>
 #include <vector>
@@ -36,12 +40,7 @@ struct GreensState {
     bool rng_on = false;                   // the estimator's own generator (elph_greens_set_rng)
     uint64_t rng_seed = 0, rng_batches = 0;
     double *R = nullptr, *X = nullptr;     // [nv][ndim] layout S: noise vectors and M⁻¹R
-    double *f = nullptr;                   // [8][ndim] the eight real input fields of setup!
-    double2 *nuA = nullptr;                // [2][Lo2][N] twisted half spectra of fields 0,1
-    double2 *nuP = nullptr;                // [6][Lh][N]  plain half spectra of fields 2..7
-    double2 *Y = nullptr;                  // [4][Kmax][ns*N] per-frequency spatial correlations
-    double *C = nullptr;                   // [4][L][ns*N]    correlations, Δτ < L
-    double2 *out = nullptr;                // [4][2L*ns*N]    reference layout
+    ElphGreensChainScratch own{};          // the pipeline's buffers for one chain (layouts: elph_internal.h), with own.out [4][2L*ns*N]
     double2 *tw = nullptr;                 // [L1 + L2 + L3] exp(-2πi j/Lx)
 };
 
@@ -100,23 +99,12 @@ __device__ __forceinline__ void gr_spatial_slice(double2 *__restrict__ y, const 
     }
 }
 
-// One workgroup per (frequency k, product c).  Y[c][k][s2 + ns*(s1 + ns*cell)].
-__global__ void __launch_bounds__(TPB) k_gr_spatial(double2 *__restrict__ Y, const double2 *__restrict__ nuA,
-                                                    const double2 *__restrict__ nuB, int K, int N, int ns, int L1, int L2,
-                                                    int L3, const double2 *__restrict__ tw, double norm,
+// One workgroup per (frequency k, product c, chain).  The spectra of a field are [chain][K][N], the two fields of a product lie
+// field_stride apart (nchains K N for a pair of spectra, 0 for an autocorrelation) and products conv_stride_in apart;
+// Y[c][chain][k][s2 + ns*(s1 + ns*cell)].
+__global__ void __launch_bounds__(TPB) k_gr_spatial(double2 *__restrict__ Y, const double2 *__restrict__ nuA, long long field_stride, int K, int N,
+                                                    int ns, int L1, int L2, int L3, const double2 *__restrict__ tw, double norm,
                                                     long long conv_stride_in, long long conv_stride_out) {
-    extern __shared__ double2 lds[];
-    const int k = blockIdx.x, c = blockIdx.y;
-    const double2 *a = nuA + (size_t)c * conv_stride_in + (size_t)k * N;
-    const double2 *b = nuB + (size_t)c * conv_stride_in + (size_t)k * N;
-    gr_spatial_slice(Y + (size_t)c * conv_stride_out + (size_t)k * ns * N, a, b, lds, N, ns, L1, L2, L3, tw, norm);
-}
-
-// The same for every resident chain at once: one workgroup per (frequency k, product c, chain).  The spectra of a field are
-// [chain][K][N], the fields of a product lie field_stride apart (= nchains K N) and products conv_stride_in apart; Y[c][chain][k][...].
-__global__ void __launch_bounds__(TPB) k_gr_spatial_chains(double2 *__restrict__ Y, const double2 *__restrict__ nuA, long long field_stride,
-                                                           int K, int N, int ns, int L1, int L2, int L3, const double2 *__restrict__ tw,
-                                                           double norm, long long conv_stride_in, long long conv_stride_out) {
     extern __shared__ double2 lds[];
     const int k = blockIdx.x, c = blockIdx.y, chain = blockIdx.z;
     const double2 *a = nuA + (size_t)c * conv_stride_in + ((size_t)chain * K + k) * N;
@@ -173,8 +161,9 @@ void elph_greens_free(elph_handle_s *h) {
     elph_current_free(h);
     GreensState *g = gs_of(h);
     if (!g) return;
-    void *ptrs[] = {g->R, g->X, g->f, g->nuA, g->nuP, g->Y, g->C, g->out, g->tw};
+    void *ptrs[] = {g->R, g->X, g->tw};
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    elph_i_greens_chain_scratch_free(&g->own);
     delete g;
     h->greens = nullptr;
 }
@@ -195,15 +184,11 @@ extern "C" int elph_greens_create(elph_handle h, int norbits, int L1, int L2, in
         elph_greens_free(h);
         return ELPH_E_UNSUPPORTED;
     }
-    const size_t nd = (size_t)h->ndim, N = (size_t)h->N, L = (size_t)h->L, Lo2 = (L + 1) / 2, Lh = L / 2 + 1;
+    const size_t nd = (size_t)h->ndim, N = (size_t)h->N, L = (size_t)h->L;
     RC(gr_alloc(&g->R, (size_t)g->nv * nd));
     RC(gr_alloc(&g->X, (size_t)g->nv * nd));
-    RC(gr_alloc(&g->f, 8 * nd));
-    RC(gr_alloc(&g->nuA, 2 * Lo2 * N));
-    RC(gr_alloc(&g->nuP, 6 * Lh * N));
-    RC(gr_alloc(&g->Y, 4 * Lh * (size_t)g->ns * N));
-    RC(gr_alloc(&g->C, 4 * L * (size_t)g->ns * N));
-    RC(gr_alloc(&g->out, 4 * 2 * L * (size_t)g->ns * N));
+    RC(elph_i_greens_chain_scratch_alloc(h, 1, &g->own));
+    RC(gr_alloc(&g->own.out, 4 * 2 * L * (size_t)g->ns * N));
     std::vector<double2> tw((size_t)L1 + L2 + L3);
     size_t o = 0;
     for (int len : {L1, L2, L3}) {
@@ -216,7 +201,6 @@ extern "C" int elph_greens_create(elph_handle h, int norbits, int L1, int L2, in
     RC(gr_alloc(&g->tw, tw.size()));
     HIPCHK(hipMemcpy(g->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute((const void *)k_gr_spatial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spatial_lds_bytes(h, g)));
-    HIPCHK(hipFuncSetAttribute((const void *)k_gr_spatial_chains, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spatial_lds_bytes(h, g)));
     return ELPH_OK;
 }
 
@@ -352,65 +336,20 @@ extern "C" int elph_greens_get_vectors(elph_handle h, double *R, double *MinvR) 
     return ELPH_OK;
 }
 
-// The device part of setup!(estimator, n₁, n₂): the four correlations C[c][Δτ < L][s₂ + n_s (s₁ + n_s cell)] (real) and, with `expand`,
-// their doubled complex copies in the reference's shape.  Stream-ordered: no copy to the host, no synchronisation.
-int elph_i_greens_setup_dev(elph_handle_s *h, int n1, int n2, bool expand) {
-    RC(need_greens(h));
-    GreensState *g = gs_of(h);
-    if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
-    if (n1 < 1 || n1 > g->nv || n2 < 1 || n2 > g->nv) { elph_set_error("n1=%d, n2=%d outside 1..%d", n1, n2, g->nv); return ELPH_E_ARG; }
-    const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N;
-    const size_t nd = (size_t)h->ndim;
-    const long long n = (long long)nd;
-    hipLaunchKernelGGL(k_gr_fields, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, g->f, g->X + (size_t)(n1 - 1) * nd,
-                       g->X + (size_t)(n2 - 1) * nd, g->R + (size_t)(n1 - 1) * nd, g->R + (size_t)(n2 - 1) * nd, n);
-    RC(elph_launch_check("k_gr_fields"));
-    RC(elph_dft_fwd_twisted(h, g->nuA, g->f, N, 2, nullptr));
-    RC(elph_dft_fwd_plain(h, g->nuP, g->f + 2 * nd, N, 6));
-    // total normalisation 1/(L·Nc)² (see header): 1/L comes from the inverse τ tables, the rest here
-    const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
-    const size_t shm = spatial_lds_bytes(h, g);
-    const long long ystride = (long long)Lh * ncol;
-    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lo2, 1), dim3(TPB), shm, h->stream, g->Y, g->nuA, g->nuA + (size_t)Lo2 * N, Lo2, N, ns,
-                       g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
-    RC(elph_launch_check("k_gr_spatial(twisted)"));
-    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 3), dim3(TPB), shm, h->stream, g->Y + ystride, g->nuP, g->nuP + (size_t)Lh * N, Lh, N,
-                       ns, g->L1, g->L2, g->L3, g->tw, norm, 2LL * Lh * N, ystride);
-    RC(elph_launch_check("k_gr_spatial(plain)"));
-    RC(elph_dft_inv_twisted(h, g->C, g->Y, ncol, 1, nullptr, nullptr, nullptr, 0));
-    // the plain inverse walks [rhs][Lh][ncol] spectra and writes [rhs][L][ncol]
-    RC(elph_dft_inv_plain(h, g->C + (size_t)L * ncol, g->Y + ystride, ncol, 3));
-    if (expand) {
-        hipLaunchKernelGGL(k_gr_out, dim3((unsigned)((ncol + 31) / 32), (unsigned)((L + 31) / 32), 4), dim3(TPB), 0, h->stream, g->out, g->C, L,
-                           ncol);
-        RC(elph_launch_check("k_gr_out"));
-    }
-    return ELPH_OK;
-}
-
-// One step of the loop over pairs i < j of the vectors: the pair's setup (the doubled complex copies for the last pair only) and vectors.
-int elph_i_greens_pair_dev(elph_handle_s *h, int i, int j, ElphGreensPair *p) {
-    RC(need_greens(h));
-    const GreensState *g = gs_of(h);
-    RC(elph_i_greens_setup_dev(h, i, j, i == g->nv - 1));
-    const size_t nd = (size_t)h->ndim;
-    p->X1 = g->X + (size_t)(i - 1) * nd; p->X2 = g->X + (size_t)(j - 1) * nd;
-    p->R1 = g->R + (size_t)(i - 1) * nd; p->R2 = g->R + (size_t)(j - 1) * nd;
-    return ELPH_OK;
-}
-
 // What measure.hip and bondcorr.hip read of the estimator (device pointers stay owned by it).
 int elph_i_greens_view(elph_handle_s *h, ElphGreensView *v) {
     RC(need_greens(h));
     const GreensState *g = gs_of(h);
     v->ns = g->ns; v->L1 = g->L1; v->L2 = g->L2; v->L3 = g->L3; v->nc = g->nc; v->nv = g->nv;
     v->have_vectors = g->have_vectors;
-    v->C = g->C; v->tw = g->tw;
+    v->C = g->own.C; v->tw = g->tw;
     v->R = g->R; v->X = g->X;
     return ELPH_OK;
 }
 
-// The scratch of the two chain pipelines below for nchains chains, sized by the estimator's shape (sizes: elph_internal.h).
+const ElphGreensChainScratch *elph_i_greens_own_scratch(elph_handle_s *h) { return h->greens ? &gs_of(h)->own : nullptr; }
+
+// The scratch of the two pipelines below for nchains chains, sized by the estimator's shape (sizes: elph_internal.h); out stays null.
 int elph_i_greens_chain_scratch_alloc(elph_handle_s *h, int nchains, ElphGreensChainScratch *S) {
     RC(need_greens(h));
     const GreensState *g = gs_of(h);
@@ -426,77 +365,78 @@ int elph_i_greens_chain_scratch_alloc(elph_handle_s *h, int nchains, ElphGreensC
 }
 
 void elph_i_greens_chain_scratch_free(ElphGreensChainScratch *S) {
-    void *ptrs[] = {S->f, S->nuA, S->nuP, S->Y, S->C};
+    void *ptrs[] = {S->f, S->nuA, S->nuP, S->Y, S->C, S->out};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     S->f = S->C = nullptr;
-    S->nuA = S->nuP = S->Y = nullptr;
+    S->nuA = S->nuP = S->Y = S->out = nullptr;
 }
 
-// setup!(estimator, n₁, n₂) for one pair of vectors of EVERY resident chain in one pass: v1, v2 count a chain's vectors (1-based, up to
-// n_v = nv / nchains), vector v of chain c is row (v - 1) nchains + c of R and M⁻¹R, so the inputs of all chains are one contiguous
-// block and the pipeline of elph_i_greens_setup_dev runs with its batch multiplied by nchains.  The scratch is the caller's (S), the
-// result S.C[table][chain][Δτ < L][s₂ + n_s (s₁ + n_s cell)]; the estimator's own scratch and tables are not touched.
-int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p) {
-    RC(need_greens(h));
+// The device part of setup!(estimator, n₁, n₂) for one pair of vectors of EVERY chain of S in one pass: v1, v2 count a chain's vectors
+// (1-based, up to n_v = nv / nchains), vector v of chain c is row (v - 1) nchains + c of R and M⁻¹R, so the inputs of all chains are one
+// contiguous block and every transform runs with its batch multiplied by nchains.  The result is the four real correlations
+// S.C[table][chain][Δτ < L][s₂ + n_s (s₁ + n_s cell)] and, with `expand` (S.out: the estimator's own scratch), their doubled complex copies
+// in the reference's shape; p: chain 0's vectors.  Stream-ordered: no copy to the host, no synchronisation.
+static int setup_pair(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p, bool expand) {
     GreensState *g = gs_of(h);
     const int nch = S.nchains;
-    if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
-    if (nch < 1 || g->nv % nch) { elph_set_error("the estimator's %d vectors are not a multiple of %d chains", g->nv, nch); return ELPH_E_STATE; }
-    const int nvc = g->nv / nch;
-    if (v1 < 1 || v1 > nvc || v2 < 1 || v2 > nvc) { elph_set_error("v1=%d, v2=%d outside 1..%d", v1, v2, nvc); return ELPH_E_ARG; }
     const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N;
     const size_t nd = (size_t)h->ndim, blk = (size_t)nch * nd;
     const long long n = (long long)blk;
     p->X1 = g->X + (size_t)(v1 - 1) * blk; p->X2 = g->X + (size_t)(v2 - 1) * blk;
     p->R1 = g->R + (size_t)(v1 - 1) * blk; p->R2 = g->R + (size_t)(v2 - 1) * blk;
     hipLaunchKernelGGL(k_gr_fields, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, S.f, p->X1, p->X2, p->R1, p->R2, n);
-    RC(elph_launch_check("k_gr_fields(chains)"));
+    RC(elph_launch_check("k_gr_fields"));
     RC(elph_dft_fwd_twisted(h, S.nuA, S.f, N, 2 * nch, nullptr));
     RC(elph_dft_fwd_plain(h, S.nuP, S.f + 2 * blk, N, 6 * nch));
+    // total normalisation 1/(L·Nc)² (see header): 1/L comes from the inverse τ tables, the rest here
     const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
     const size_t shm = spatial_lds_bytes(h, g);
     const long long ytab = (long long)nch * Lh * ncol;                 // one table's spectra; the twisted one fills nch Lo2 ncol of it
-    hipLaunchKernelGGL(k_gr_spatial_chains, dim3((unsigned)Lo2, 1, (unsigned)nch), dim3(TPB), shm, h->stream, S.Y, S.nuA, (long long)nch * Lo2 * N,
-                       Lo2, N, ns, g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
-    RC(elph_launch_check("k_gr_spatial_chains(twisted)"));
-    hipLaunchKernelGGL(k_gr_spatial_chains, dim3((unsigned)Lh, 3, (unsigned)nch), dim3(TPB), shm, h->stream, S.Y + ytab, S.nuP,
-                       (long long)nch * Lh * N, Lh, N, ns, g->L1, g->L2, g->L3, g->tw, norm, 2LL * nch * Lh * N, ytab);
-    RC(elph_launch_check("k_gr_spatial_chains(plain)"));
+    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lo2, 1, (unsigned)nch), dim3(TPB), shm, h->stream, S.Y, S.nuA, (long long)nch * Lo2 * N, Lo2, N, ns,
+                       g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
+    RC(elph_launch_check("k_gr_spatial(twisted)"));
+    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 3, (unsigned)nch), dim3(TPB), shm, h->stream, S.Y + ytab, S.nuP, (long long)nch * Lh * N, Lh,
+                       N, ns, g->L1, g->L2, g->L3, g->tw, norm, 2LL * nch * Lh * N, ytab);
+    RC(elph_launch_check("k_gr_spatial(plain)"));
     const size_t ctab = (size_t)nch * L * ncol;
     RC(elph_dft_inv_twisted(h, S.C, S.Y, ncol, nch, nullptr, nullptr, nullptr, 0));
+    // the plain inverse walks [rhs][Lh][ncol] spectra and writes [rhs][L][ncol]
     RC(elph_dft_inv_plain(h, S.C + ctab, S.Y + ytab, ncol, 3 * nch));
+    if (expand) {
+        hipLaunchKernelGGL(k_gr_out, dim3((unsigned)((ncol + 31) / 32), (unsigned)((L + 31) / 32), 4), dim3(TPB), 0, h->stream, S.out, S.C, L, ncol);
+        RC(elph_launch_check("k_gr_out"));
+    }
     return ELPH_OK;
 }
 
-// elph_i_greens_autocorr_dev for nchains fields at once: vS[chain][ndim] (layout S) -> outS[chain][Δτ][a + n_s (b + n_s Δcell)].  Uses
-// S.nuP and S.Y: call it before, not between, elph_i_greens_setup_chains_dev and what reads S.C.
+// One step of a measurement's loop over the pairs v1 < v2 of a chain's vectors (make_measurements!, Measurements.jl:550-560) in the scratch
+// S.  In the estimator's own scratch the doubled complex copies are refreshed for the last pair (elph_greens_dev_arrays); in scratch a
+// measurement unit owns, the estimator's scratch and tables are not touched.
+int elph_i_greens_setup_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, int v1, int v2, ElphGreensPair *p) {
+    RC(need_greens(h));
+    const GreensState *g = gs_of(h);
+    const int nch = S.nchains;
+    if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
+    if (nch < 1 || g->nv % nch) { elph_set_error("the estimator's %d vectors are not a multiple of %d chains", g->nv, nch); return ELPH_E_STATE; }
+    const int nvc = g->nv / nch;
+    if (v1 < 1 || v1 > nvc || v2 < 1 || v2 > nvc) { elph_set_error("v1=%d, v2=%d outside 1..%d", v1, v2, nvc); return ELPH_E_ARG; }
+    return setup_pair(h, S, v1, v2, p, S.out && v1 == nvc - 1);
+}
+
+// translational_average! (Utilities.jl:49-60) of a real field periodic in τ with itself, every orbital pair at once, for the nchains fields
+// vS[chain][ndim] (layout S) — the plain-spectrum branch of setup! with both spectra that of v:
+//   outS[chain][Δτ][a + n_s (b + n_s Δcell)] = 1/(L Nc) Σ_{τ, cell} v[τ + Δτ][a, cell + Δcell] · v[τ][b, cell]
+// Uses S.nuP and S.Y: call it before, not between, elph_i_greens_setup_chains_dev and what reads S.C.
 int elph_i_greens_autocorr_chains_dev(elph_handle_s *h, const ElphGreensChainScratch &S, double *outS, const double *vS) {
     RC(need_greens(h));
     GreensState *g = gs_of(h);
     const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N, nch = S.nchains;
     RC(elph_dft_fwd_plain(h, S.nuP, vS, N, nch));
     const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
-    hipLaunchKernelGGL(k_gr_spatial_chains, dim3((unsigned)Lh, 1, (unsigned)nch), dim3(TPB), spatial_lds_bytes(h, g), h->stream, S.Y, S.nuP, 0LL, Lh,
-                       N, ns, g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
-    RC(elph_launch_check("k_gr_spatial_chains(autocorrelation)"));
-    RC(elph_dft_inv_plain(h, outS, S.Y, ncol, nch));
-    return ELPH_OK;
-}
-
-// translational_average! (Utilities.jl:49-60) of a real field periodic in τ with itself, every orbital pair at once:
-//   outS[Δτ][a + n_s (b + n_s Δcell)] = 1/(L Nc) Σ_{τ, cell} v[τ + Δτ][a, cell + Δcell] · v[τ][b, cell]      (vS, outS: layout S)
-// — the plain-spectrum branch of setup! with both spectra that of v.  Uses the estimator's ν, Y scratch: call it before, not between,
-// elph_i_greens_setup_dev and what reads its C.
-int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS) {
-    RC(need_greens(h));
-    GreensState *g = gs_of(h);
-    const int N = (int)h->N, L = (int)h->L, Lh = L / 2 + 1, ns = g->ns, ncol = ns * N;
-    RC(elph_dft_fwd_plain(h, g->nuP, vS, N, 1));
-    const double norm = 1.0 / ((double)L * (double)g->nc * (double)g->nc);
-    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 1), dim3(TPB), spatial_lds_bytes(h, g), h->stream, g->Y, g->nuP, g->nuP, Lh, N, ns,
+    hipLaunchKernelGGL(k_gr_spatial, dim3((unsigned)Lh, 1, (unsigned)nch), dim3(TPB), spatial_lds_bytes(h, g), h->stream, S.Y, S.nuP, 0LL, Lh, N, ns,
                        g->L1, g->L2, g->L3, g->tw, norm, 0LL, 0LL);
     RC(elph_launch_check("k_gr_spatial(autocorrelation)"));
-    RC(elph_dft_inv_plain(h, outS, g->Y, ncol, 1));
+    RC(elph_dft_inv_plain(h, outS, S.Y, ncol, nch));
     return ELPH_OK;
 }
 
@@ -504,13 +444,17 @@ int elph_i_greens_autocorr_dev(elph_handle_s *h, double *outS, const double *vS)
 // interleaved re/im, first index fastest.  The arrays also stay on the device (elph_greens_dev_arrays).
 extern "C" int elph_greens_setup(elph_handle h, int n1, int n2, double *GD0, double *GD0_GD0, double *GDD_G00, double *GD0_G0D) {
     CHECK_H(h);
-    RC(elph_i_greens_setup_dev(h, n1, n2, true));
+    RC(need_greens(h));
     GreensState *g = gs_of(h);
+    if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
+    if (n1 < 1 || n1 > g->nv || n2 < 1 || n2 > g->nv) { elph_set_error("n1=%d, n2=%d outside 1..%d", n1, n2, g->nv); return ELPH_E_ARG; }
+    ElphGreensPair p;
+    RC(setup_pair(h, g->own, n1, n2, &p, true));
     const size_t cnt = 2 * (size_t)h->L * (size_t)g->ns * (size_t)h->N;   // complex numbers per array
     // order of the device arrays: 0 GΔ0, 1 GΔ0·GΔ0, 2 GΔΔ·G00, 3 GΔ0·G0Δ (fields 0/1, 2/3, 4/5, 6/7)
     double *outs[4] = {GD0, GD0_GD0, GDD_G00, GD0_G0D};
     for (int c = 0; c < 4; ++c)
-        if (outs[c]) HIPCHK(hipMemcpyAsync(outs[c], g->out + (size_t)c * cnt, cnt * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+        if (outs[c]) HIPCHK(hipMemcpyAsync(outs[c], g->own.out + (size_t)c * cnt, cnt * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -521,7 +465,7 @@ extern "C" int elph_greens_dev_arrays(elph_handle h, void **arrays, int64_t *cou
     RC(need_greens(h));
     GreensState *g = gs_of(h);
     const size_t cnt = 2 * (size_t)h->L * (size_t)g->ns * (size_t)h->N;
-    if (arrays) for (int c = 0; c < 4; ++c) arrays[c] = (void *)(g->out + (size_t)c * cnt);
+    if (arrays) for (int c = 0; c < 4; ++c) arrays[c] = (void *)(g->own.out + (size_t)c * cnt);
     if (count) *count = (int64_t)cnt;
     return ELPH_OK;
 }

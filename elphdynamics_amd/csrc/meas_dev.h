@@ -31,11 +31,11 @@ __device__ __forceinline__ double t_modulated(double t, double alpha, double alp
 }
 
 // measure_<which>(l = cell, o1, o2, tau) of one pair of vectors (o1, o2 0-based, tau <= L).  C: the estimator's four real tables
-// C[c][tau < L][s2 + n_s (s1 + n_s cell)] of this pair.  tstride: doubles between two of the four tables; 0 = they are contiguous (L n_s N),
-// as the estimator's own are; the tables of resident chains lie nchains times as far apart (measure_chains.hip).
+// C[c][tau < L][s2 + n_s (s1 + n_s cell)] of this pair.  tstride: doubles between two of the four tables, nchains L n_s N in the
+// pipeline's [table][chain][L][n_s N] (measure.hip, ssh_measure.hip).
 __device__ __forceinline__ double meas_fold(int which, const double *__restrict__ C, int N, int L, int ns, int L1, int L2, int L3, int tau,
-                                            int cell, int o1, int o2, size_t tstride = 0) {
-    const size_t ncol = (size_t)ns * N, tab = tstride ? tstride : (size_t)L * ncol;
+                                            int cell, int o1, int o2, size_t tstride) {
+    const size_t ncol = (size_t)ns * N, tab = tstride;
     const bool beta = (tau == L);
     double v;
     if (which == MEAS_SPINSPIN) {

@@ -1,6 +1,6 @@
-// meas_holstein_dev.h — what one workgroup does in each kernel of the Holstein measurements, shared by measure.hip (one configuration
-// per handle) and measure_chains.hip (every resident chain, the chain a grid axis): the kernels of the two units differ only in where a
-// workgroup finds its configuration.  Layouts and the rule of the reductions: header of measure.hip.
+// meas_holstein_dev.h — what one workgroup does in each kernel of the Holstein measurements (measure.hip: the chain is a grid axis, and a
+// kernel there only says where a workgroup finds its chain's block).  Every function takes ONE configuration's pointers.  Layouts and the
+// rule of the reductions: header of measure.hip.
 #pragma once
 
 #include "corr_req.h"
@@ -131,11 +131,11 @@ __device__ __forceinline__ void ms_finish(double *__restrict__ acc, const double
 }
 
 // Element idx = (tau, cell, listed pair) of correlation `which` (Measurements.jl:1469-1650).  C: the estimator's four real tables of this
-// pair, tstride apart (0: contiguous); ph: the field's translation average, this configuration's at ph_off (ph may be null when
+// pair, tstride apart; ph: the field's translation average, this configuration's at ph_off (ph may be null when
 // PhononGreens is not measured: it is only indexed then); acc_off: where this configuration's accumulators start.
 __device__ __forceinline__ void ms_fold(const CorrReq<MS_NCORR> &rq, int which, long long idx, const double *__restrict__ C,
-                                        const double *__restrict__ ph, int N, int L, int ns, int L1, int L2, int L3, size_t tstride = 0,
-                                        size_t acc_off = 0, size_t ph_off = 0) {
+                                        const double *__restrict__ ph, int N, int L, int ns, int L1, int L2, int L3, size_t tstride,
+                                        size_t acc_off, size_t ph_off) {
     const int np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
     if (idx >= (long long)L0 * nc * np) return;
     const int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc);

@@ -1,7 +1,6 @@
-// meas_ssh_dev.h — what one workgroup does in each kernel of the bond-phonon (SSH) measurements, shared by ssh_measure.hip (one
-// configuration per handle) and ssh_measure_chains.hip (every resident chain, the chain a grid axis): the kernels of the two units differ
-// only in where a workgroup finds its configuration.  Every function takes ONE configuration's pointers.  Layouts and the rule of the
-// reductions: header of ssh_measure.hip.
+// meas_ssh_dev.h — what one workgroup does in each kernel of the bond-phonon (SSH) measurements (ssh_measure.hip: the chain is a grid
+// axis, and a kernel there only says where a workgroup finds its chain's block).  Every function takes ONE configuration's pointers.
+// Layouts and the rule of the reductions: header of ssh_measure.hip.
 #pragma once
 
 #include "cell_dft_dev.h"
@@ -172,11 +171,11 @@ __device__ __forceinline__ void sm_ph(double2 *__restrict__ y, const double2 *__
 }
 
 // Element idx = (tau, cell, listed pair) of correlation `which`.  C: the estimator's four real tables of this pair of vectors, tstride
-// apart (0: contiguous); B: this configuration's translation averages of the listed phonon-type pairs, [nP][L][nc] (only indexed when
+// apart; B: this configuration's translation averages of the listed phonon-type pairs, [nP][L][nc] (only indexed when
 // PhononGreens is measured); slice L is slice 0; acc_off: where this configuration's accumulators start.
 __device__ __forceinline__ void sm_fold(const CorrReq<SM_NCORR> &rq, int which, long long idx, const double *__restrict__ C,
-                                        const double *__restrict__ B, int N, int L, int ns, int L1, int L2, int L3, size_t tstride = 0,
-                                        size_t acc_off = 0) {
+                                        const double *__restrict__ B, int N, int L, int ns, int L1, int L2, int L3, size_t tstride,
+                                        size_t acc_off) {
     const int np = rq.np[which], L0 = rq.L0[which], nc = L1 * L2 * L3;
     if (idx >= (long long)L0 * nc * np) return;
     const int tau = (int)(idx % L0), cell = (int)((idx / L0) % nc);

@@ -24,10 +24,10 @@ sharded and slab handles are refused by the library.  BondBond, BondPairGreens a
 this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent of this model lives in another
 (current_measurements.py, csrc/currcorr.hip: one configuration or resident chains), that of the SSH model in ssh_bond_measurements.py
 (csrc/ssh_bondcorr.hip).  Several chains resident in the handle (a lockstep
-run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure_chains.hip): one container per chain, all
+run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure.hip): one container per chain, all
 chains in the same launches; the functions here keep refusing them.  The bond correlations of the chains are
-chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure_chains.hip), its bond
-correlations BondBond, CurrentCurrent and BondPairGreens over chains by ssh_chain_bond_measurements.py (csrc/ssh_bondcorr_chains.hip).
+chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure.hip), its bond
+correlations BondBond, CurrentCurrent and BondPairGreens over chains by ssh_chain_bond_measurements.py (csrc/ssh_bondcorr.hip).
 
 One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
 The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,

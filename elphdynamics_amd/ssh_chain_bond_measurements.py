@@ -1,7 +1,7 @@
 """Inter-site correlations of every chain of the bond-phonon (SSH) model resident in a handle (a lockstep run: langevin.evolve_,
 hmc.update_chains_): the chain-aware twin of ssh_bond_measurements.py, beside ssh_chain_measurements.py the way ssh_bond_measurements.py
 stands beside ssh_measurements.py.  One SSHBondContainer per chain, each with its own data folder; on the device all chains are
-accumulated by the same launches (elph_ssh_bond_chains_*, csrc/ssh_bondcorr_chains.hip), the chain a grid axis.
+accumulated by the same launches (elph_ssh_bond_chains_*, csrc/ssh_bondcorr.hip), the chain a grid axis.
 
     cb = initialize_ssh_chain_bond_container(model, info, datafolders)   one container per chain (:295-302, :322, :767-819 each)
     initialize_ssh_bond_folders_(cb)                                     the inter-site parts of :420-540 per chain

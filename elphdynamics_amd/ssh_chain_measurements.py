@@ -1,7 +1,7 @@
 """Measurements of every chain of the bond-phonon (SSH) model resident in a handle (a lockstep run: langevin.evolve_, hmc.update_chains_):
 the chain-aware twin of ssh_measurements.py, as chain_measurements.py is of measurements.py.  One SSHMeasurementsContainer per chain, each
 with its own data folder; on the device all chains are accumulated by the same launches (elph_ssh_meas_chains_*,
-csrc/ssh_measure_chains.hip), the chain a grid axis.
+csrc/ssh_measure.hip), the chain a grid axis.
 
     cm = initialize_ssh_chain_measurements_container(model, info, datafolders)   one container per chain (Measurements.jl:180-338 each)
     initialize_measurement_folders_(cm)                                          :343-540 per chain
@@ -26,7 +26,7 @@ sums it held): the next accumulate_ with the new estimator makes it again, with 
 Scope: what ssh_measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the Holstein
 model (chain_measurements.py measures it), BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry
 set to true (snapshots.py takes them for every chain, in a container of its own).  The SSH bond correlations over chains live in a container of their own beside this one (ssh_chain_bond_measurements.py,
-csrc/ssh_bondcorr_chains.hip), used on the same model and estimator, in either order.  ssh_measurements.py itself keeps refusing
+csrc/ssh_bondcorr.hip), used on the same model and estimator, in either order.  ssh_measurements.py itself keeps refusing
 resident chains.
 """
 import numpy as np

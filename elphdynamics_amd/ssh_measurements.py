@@ -22,9 +22,9 @@ BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true 
 handle; sharded and slab handles, and PhononGreens on a lattice where Nph != nph * ncells (the reference's reshape of the field
 throws), are refused by the library.  BondBond, CurrentCurrent, BondPairGreens and BondPairSusc live in a container of their own beside
 this one (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), used on the same model and estimator.  Several chains resident in the handle
-(a lockstep run) are measured by the chain-aware twin of this module, ssh_chain_measurements.py (csrc/ssh_measure_chains.hip): one
+(a lockstep run) are measured by the chain-aware twin of this module, ssh_chain_measurements.py (csrc/ssh_measure.hip): one
 container per chain, all chains in the same launches; the functions here keep refusing them.  BondBond, CurrentCurrent and BondPairGreens
-over chains are ssh_chain_bond_measurements.py's (csrc/ssh_bondcorr_chains.hip).
+over chains are ssh_chain_bond_measurements.py's (csrc/ssh_bondcorr.hip).
 
 Line order in the scalar files (the reference's is the unspecified order of a Julia Dict), extending the one of measurements.py:
 density, Nsqr, mu / density, double_occ, mu / x, x2, x4, phonon_pe, phonon_ke, elph_energy, el_ke, sign_switch.

@@ -1,4 +1,4 @@
-"""GPU parity of the bond correlations of resident chains (csrc/bondcorr_chains.hip through elphdynamics_amd/chain_bond_measurements.py):
+"""GPU parity of the bond correlations of resident chains (csrc/bondcorr.hip through elphdynamics_amd/chain_bond_measurements.py):
 every chain's container against the direct-sum restatement tests/bond_reference.py evaluated on that chain's vectors [v * nchains + c],
 with the bound of tests/test_gpu_bond_measurements.py (its `compare`: max|got - ref| < 1e-12 * max(1, max|ref|)).
 
@@ -14,7 +14,7 @@ import bond_reference as bref
 import measurements_reference as mref
 from test_bond_measurements_host import SMALL, SQUARE, TD
 from test_gpu_bond_measurements import compare, request_of, snapshot
-from test_gpu_measurements import build_model, mulM_still_right, parse
+from test_gpu_measurements import assert_same_bits_as_single, build_model, mulM_still_right, parse
 
 pytestmark = pytest.mark.gpu
 
@@ -212,6 +212,29 @@ def test_production_shape_against_the_single_configuration_path():
     finally:
         m.close()
         m2.close()
+
+
+def test_one_chain_resident_agrees_with_the_single_configuration_path():
+    from elphdynamics_amd import bond_measurements as bm, chain_bond_measurements as cbm, greens
+    ns, dims, L, defs, table = SMALL["sq4x4"]
+    m = build_model(ns, dims, L, defs, seed=3)
+    try:
+        info = dict(table, num_random_vectors=3)
+        cb = cbm.initialize_chain_bond_container(m, info, [""])
+        c1 = bm.initialize_bond_container(m, info, "")
+        est = greens.EstimateGreensFunction(m, nv=3)
+        greens.set_vectors_(est, *vectors(m, 1, 3, seed=1))
+        cbm.accumulate_bonds_(cb, m, est)
+        bm.accumulate_bonds_(c1, m, est)                                    # both containers live on the handle side by side
+        cbm.fetch_bonds_(cb, m)
+        bm.fetch_bonds_(c1, m)
+        want = want_of(m, cb, est.R, est.MinvR, 0)
+        compare(cb.chains[0], want, label="one chain resident, chain container")
+        compare(c1, want, label="one chain resident, single-configuration container")
+        assert set(snapshot(c1)) == set(bref.CORRS) and all(np.abs(v).max() > 0 for v in snapshot(c1).values())
+        assert_same_bits_as_single(snapshot(cb.chains[0]), snapshot(c1), "one chain resident")
+    finally:
+        m.close()
 
 
 def test_deck_in_lockstep_measured_end_to_end(tmp_path):

@@ -1,4 +1,4 @@
-"""GPU parity of the measurements of resident chains (csrc/measure_chains.hip through elphdynamics_amd/chain_measurements.py): every
+"""GPU parity of the measurements of resident chains (csrc/measure.hip through elphdynamics_amd/chain_measurements.py): every
 chain's container against the direct-sum restatement tests/measurements_reference.py evaluated on that chain's field, mu row and vectors
 [v * nchains + c], with the bounds of tests/test_gpu_measurements.py (its `compare`: 1e-12 on the correlations, 1e-12 of the yardstick on
 the reduced scalars).
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import measurements_reference as ref
-from test_gpu_measurements import ALL_TD, SHAPES, build_model, compare, parse, ref_par, request_of, snapshot
+from test_gpu_measurements import ALL_TD, SHAPES, assert_same_bits_as_single, build_model, compare, parse, ref_par, request_of, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -197,7 +197,7 @@ def test_one_chain_resident_agrees_with_the_single_configuration_path():
         ms.accumulate_(c1, m, est)                                          # both containers live on the handle side by side
         cms.fetch_(cm, m)
         ms.fetch_(c1, m)
-        assert_close_to_single(cm.chains[0], c1, "one chain resident")
+        assert_same_bits_as_single(snapshot(cm.chains[0]), snapshot(c1), "one chain resident")
         compare(cm.chains[0], ref.measure(est.R, est.MinvR, m.x, ref_par(m, defs), request_of(c1)), label="one chain resident")
     finally:
         m.close()

@@ -81,6 +81,15 @@ def snapshot(c):
     return out
 
 
+def assert_same_bits_as_single(chain, single, label):
+    """chain, single: the snapshots of a chain container's chain 0 and of a single-configuration container measured on one handle with one
+    chain resident.  The single-configuration entry points are the one-chain case of the chain entry points (same state, kernels and
+    launches), so every fetched array of the two is equal bit for bit."""
+    assert set(chain) == set(single)
+    for k in single:
+        assert np.array_equal(chain[k], single[k]), (label, k, np.abs(chain[k] - single[k]).max())
+
+
 def in_units(err, yard):
     """err / yard elementwise; a yardstick of zero (every term is zero, e.g. mu = 0 everywhere) admits no error at all."""
     err, yard = np.atleast_1d(np.asarray(err, dtype=np.float64)), np.atleast_1d(np.asarray(yard, dtype=np.float64))
@@ -156,6 +165,39 @@ def test_accumulators_match_direct_sums(case):
         # the estimator is left usable
         greens.setup_(est, 1, 2)
         for a, b in zip(before, (est.GD0, est.GD0_GD0, est.GDD_G00, est.GD0_G0D)):
+            assert np.array_equal(a, b)
+    finally:
+        m.close()
+
+
+def test_what_an_accumulate_leaves_in_the_estimators_tables():
+    """include/elph_gpu.h: elph_meas_accumulate leaves the estimator's tables and their doubled complex copies (elph_greens_dev_arrays)
+    holding the last pair of vectors, (n_v - 1, n_v); elph_meas_chains_accumulate does not touch them, even with one chain resident."""
+    from elphdynamics_amd import chain_measurements as cms, greens, measurements as ms
+    from test_gpu_current_measurements import device_tables
+    ns, dims, L, defs, table = SHAPES["sq4x4"]
+    m = build_model(ns, dims, L, defs, seed=sum(dims) + L)
+    try:
+        info = dict(table, num_random_vectors=3)
+        c = ms.initialize_measurements_container(m, info, "")
+        cm = cms.initialize_chain_measurements_container(m, info, [""])
+        est = greens.EstimateGreensFunction(m, nv=3)
+        rng = np.random.default_rng(L)
+        greens.set_vectors_(est, rng.standard_normal((3, m.Ndim)), rng.standard_normal((3, m.Ndim)))
+        greens.setup_(est, 2, 3)
+        _, last_pair = device_tables(m)
+        assert all(t.any() for t in last_pair)
+        greens.setup_(est, 1, 2)
+        _, first_pair = device_tables(m)
+        assert not any(np.array_equal(a, b) for a, b in zip(first_pair, last_pair))
+        cms.accumulate_(cm, m, est, m.x[None, :])                           # scratch of its own: the tables stay those of (1, 2)
+        for a, b in zip(first_pair, device_tables(m)[1]):
+            assert np.array_equal(a, b)
+        ms.accumulate_(c, m, est)                                           # the estimator's scratch: the tables are those of (2, 3)
+        for a, b in zip(last_pair, device_tables(m)[1]):
+            assert np.array_equal(a, b)
+        cms.accumulate_(cm, m, est, m.x[None, :])
+        for a, b in zip(last_pair, device_tables(m)[1]):
             assert np.array_equal(a, b)
     finally:
         m.close()

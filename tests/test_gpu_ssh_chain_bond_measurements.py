@@ -1,4 +1,4 @@
-"""GPU parity of the SSH bond correlations of resident chains (csrc/ssh_bondcorr_chains.hip through
+"""GPU parity of the SSH bond correlations of resident chains (csrc/ssh_bondcorr.hip through
 elphdynamics_amd/ssh_chain_bond_measurements.py): every chain's container against the direct sums of tests/ssh_bond_reference.py
 evaluated on that chain's field and vectors [v * nchains + c], with the bound of tests/test_gpu_ssh_bond_measurements.py (its `compare`,
 imported: max|got - ref| < 1e-12 * max(1, max|ref|) per key, imaginary parts exactly zero).  A chain's sums have exactly the terms of
@@ -29,6 +29,7 @@ import ssh_measurement_cases as smc
 from test_gpu_ssh_bond_measurements import compare, raw_create as raw_single_create, snapshot
 from test_gpu_ssh_chain_measurements import chain_field
 from test_gpu_ssh_chain_measurements import snapshot as onsite_snapshot
+from test_gpu_measurements import assert_same_bits_as_single
 from test_gpu_ssh_measurements import mulM_still_right
 from test_ssh_bond_measurements_host import ALL3, CASES, TD, build, check_files, request_of, yardstick
 
@@ -281,7 +282,7 @@ def test_one_chain_resident_agrees_with_the_single_configuration_path():
         sb.fetch_ssh_bonds_(c1, m)
         compare(cb.chains[0], want, label="one chain resident, chain container")
         compare(c1, want, label="one chain resident, single-configuration container")
-        assert_close_to_single(cb.chains[0], c1, "one chain resident")
+        assert_same_bits_as_single(snapshot(cb.chains[0]), snapshot(c1), "one chain resident")
     finally:
         m.close()
 

@@ -1,4 +1,4 @@
-"""GPU parity of the SSH measurements of resident chains (csrc/ssh_measure_chains.hip through elphdynamics_amd/ssh_chain_measurements.py):
+"""GPU parity of the SSH measurements of resident chains (csrc/ssh_measure.hip through elphdynamics_amd/ssh_chain_measurements.py):
 every chain's container against the direct-sum restatement tests/ssh_measurements_reference.py evaluated on that chain's field, mu row and
 vectors [v * nchains + c], with the bounds of tests/test_gpu_ssh_measurements.py (its `compare`, imported: 1e-12 on the correlations, 1e-12
 of the yardstick on the reduced scalars, imaginary parts exactly zero).  A chain's sums have exactly the terms of the single-configuration
@@ -23,7 +23,7 @@ import pytest
 import ssh_cases as sc
 import ssh_measurement_cases as smc
 import ssh_measurements_reference as ref
-from test_gpu_measurements import parse
+from test_gpu_measurements import assert_same_bits_as_single, parse
 from test_gpu_ssh_measurements import compare, raw_create as raw_single_create, snapshot
 
 pytestmark = pytest.mark.gpu
@@ -218,7 +218,7 @@ def test_one_chain_resident_agrees_with_the_single_configuration_path():
         want = ref.measure(est.R, est.MinvR, m.x, smc.ref_par(m), smc.request_of(c1))
         compare(cm.chains[0], want, label="one chain resident, chain container")
         compare(c1, want, label="one chain resident, single-configuration container")
-        assert_close_to_single(cm.chains[0], c1, "one chain resident")
+        assert_same_bits_as_single(snapshot(cm.chains[0]), snapshot(c1), "one chain resident")
     finally:
         m.close()
 
