@@ -177,6 +177,7 @@ BENCH_SIGNATURES = {
     "elph_bench_pg_info": (c_int, [Handle, P_int, P_int, P_int, P_int, P_int]),
     "elph_bench_slabs_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_lattice_shape": (c_int, [c_int, c_i64, c_i64, P_i64, P_dbl, P_dbl, P_int]),
+    "elph_bench_wg_plan": (c_int, [c_int, c_i64, c_i64, c_i64, P_i64, P_dbl, P_dbl, c_int, c_int, P_int]),
     "elph_bench_kpm_plan": (c_int, [c_i64, c_dbl, c_dbl, c_dbl, c_int, c_int, P_dbl, P_int, P_int, P_dbl, P_int, P_int, P_int, P_dbl,
                                     P_dbl, P_dbl, c_i64, P_i64]),
     "elph_bench_hess_max_real": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl]),
@@ -199,6 +200,24 @@ def lattice_shape(kind, nsites, table, cosht=None, sinht=None):
     check(lib.elph_bench_lattice_shape(int(kind), int(nsites), table.shape[0], iptr(table) if table.size else None,
                                        None if c is None else dptr(c), None if s is None else dptr(s), out))
     return dict(zip(LATTICE_SHAPE_SLOTS, list(out)))
+
+
+# the slots of elph_bench_wg_plan's vector, in order (elph_bench.h); WG_FORMS: the numbers of its "form" slot (cg_wg.hip: wg::Form)
+WG_PLAN_SLOTS = ("usable", "form", "npl", "T", "W", "G", "shm", "resident", "has_kernel")
+WG_FORMS = {"LANE": 0, "SQ16": 1, "HC12": 2, "S8": 4, "GRID": 5, "HGRID": 6, "TGRID": 7}
+
+
+def wg_plan(kind, nsites, ltau, table, cosht=None, sinht=None, nrhs=1, world=0):
+    """The resident CG launch a handle made from this bond table plans for nrhs right-hand sides (world > 0: as one rank of a sharded solve
+    over that many), as {slot: value}.  Reads the ELPH_*WG* switches of the environment as a solve does.  Needs no device."""
+    lib = load()
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 2)
+    c = None if cosht is None else np.ascontiguousarray(cosht, dtype=np.float64)
+    s = None if sinht is None else np.ascontiguousarray(sinht, dtype=np.float64)
+    out = (c_int * len(WG_PLAN_SLOTS))()
+    check(lib.elph_bench_wg_plan(int(kind), int(nsites), int(ltau), table.shape[0], iptr(table) if table.size else None,
+                                 None if c is None else dptr(c), None if s is None else dptr(s), int(nrhs), int(world), out))
+    return dict(zip(WG_PLAN_SLOTS, list(out)))
 
 
 def kpm_plan(ltau, bounds, buf=0.05, c1=1.0, c2=1.0):

@@ -69,6 +69,59 @@ __device__ unsigned long long g_wg_timeline[4096 * 4];
 // control block, mailboxes — come from memory (R.ranks).  The ranks wait for each other, so they must all be resident: one grid
 // guarantees what P streams do not (streams share the process's few hardware queues, and a queue runs its launches one after the other).
 struct WgRankArgs { CgBufs B; ModelDev m; WgCtl R; ShardCtl Sh; };
+
+// The forms of the kernel (its template parameter FORM stays an int: the numbers are part of the kernels' names).
+enum Form { LANE = 0, SQ16 = 1, HC12 = 2, S8 = 4, GRID = 5, HGRID = 6, TGRID = 7 };
+
+// Where the loop-invariant and the update-only vectors of a (form, sites per lane, slices per wave) live, and the dynamic LDS that follows
+// from it — ONE statement for the kernel (which carves its pointers from it) and for the host (which sizes every launch from `total`).
+struct WgPlace {
+    int SL, LSL, HSL, NSLAB;      // doubles per lane-program slab | lanes per register and doubles per slice in LDS | LDS slabs per wave
+    bool S_LDS, E_LDS, X_REG, E_SHARED, X_GLB, PH_LDS;
+};
+__host__ __device__ __forceinline__ constexpr WgPlace wg_place(int FORM, int NPL, int T, bool SSH) {
+    const bool SQ = FORM == SQ16, HC = FORM == HC12, GR = FORM == GRID || FORM == TGRID;
+    WgPlace P{};
+    // slices in LDS: LSL lanes per register, HSL doubles per slice.  Honeycomb form: the 48 REAL lanes only — a mirror lane READS the
+    // slot of the lane it mirrors (lr) and writes nothing (lwok): its r, exp(-dtau V) and halo values are the real lane's by
+    // construction, and a quarter of the LDS is not spent on copies (what lets 3 slices per wave fit)
+    P.SL = NPL * WAVE + 2 * WAVE; P.LSL = HC ? 48 : WAVE; P.HSL = NPL * P.LSL;
+    P.NSLAB = FORM != LANE ? 0 : T + 1;            // (the other forms exchange registers)
+    // 4 slices per wave (DPP form, throughput shape): exp(-dtau V) moves to LDS (read twice per iteration; 40 registers) and x stays in
+    // registers instead (LDS is full); otherwise E in registers (0.35 us per iteration faster at 2 slices per wave), x and r in LDS
+    // bond phonons, DPP form, 2 slices per wave: the table set of slice t0 in LDS (24 doubles per lane), x in registers
+    P.S_LDS = SQ && SSH && T == 2;
+    // honeycomb DPP form, 2 slices per wave: exp(-dtau V) in LDS too (six sites per lane: 36 registers)
+    P.E_LDS = ((SQ || GR) && T >= 4) || (HC && T >= 2);
+    P.X_REG = ((SQ || GR) && T >= 4) || P.S_LDS || (HC && T >= 3);
+    // (honeycomb: neighbouring waves SHARE the slice of exp(-dtau V) between them — [W T + 1] slices per workgroup instead of W (T + 1);
+    //  both write the same values to it)
+    P.E_SHARED = HC;
+    // honeycomb, 3 slices per wave: x lives in MEMORY (it is touched once per iteration, x += alpha p): its slices are loaded behind the
+    // sums — the meeting that follows hides the round trip — and stored back by the update; between two updates no register holds it
+    P.X_GLB = HC && T >= 3;
+    // honeycomb, 3 slices per wave: the two HALO slices of p wait in LDS between the p-update that makes them and the mat-vec that
+    // consumes them (24 registers that would otherwise sit through both sweeps)
+    P.PH_LDS = HC && T >= 3;
+    return P;
+}
+// The regions of the dynamic LDS, in doubles, each as the step from the region the kernel reaches it from:
+//   [W][NSLAB][SL] slabs | r [W][T][HSL] | x [W][T][HSL] (unless X_REG) | exp(-dtau V) (E_LDS) or the SSH table set (S_LDS) |
+//   partials and totals [48] | rhalo [2][HSL] | zhalo [2][HSL] | the halo slices of p [W][2][HSL] (PH_LDS)
+struct WgLayout { size_t r, x_r, e_r, part_e, rhalo_part, zhalo_rhalo, ph_zhalo, total; };
+__host__ __device__ __forceinline__ constexpr WgLayout wg_layout(int FORM, int NPL, int T, bool SSH, int W) {
+    const WgPlace P = wg_place(FORM, NPL, T, SSH);
+    WgLayout Y{};
+    Y.r = (size_t)W * P.NSLAB * P.SL;
+    Y.x_r = (size_t)W * T * P.HSL;
+    Y.e_r = (size_t)(P.X_REG ? 1 : 2) * W * T * P.HSL;
+    Y.part_e = P.E_LDS ? (P.E_SHARED ? ((size_t)W * T + 1) * P.HSL : (size_t)W * (T + 1) * P.HSL) : (P.S_LDS ? (size_t)W * SQ_TABS * WAVE : 0);
+    Y.rhalo_part = 48;
+    Y.zhalo_rhalo = 2 * P.HSL;
+    Y.ph_zhalo = 2 * P.HSL;
+    Y.total = Y.r + Y.e_r + Y.part_e + Y.rhalo_part + Y.zhalo_rhalo + Y.ph_zhalo + (P.PH_LDS ? (size_t)W * 2 * P.HSL : 0);
+    return Y;
+}
 template <int NPL, int T, bool SSH, bool UNI, int FORM, bool SHARD, bool X0Z = false, bool RANKS = false>
 __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, ShardCtl Sh) {
     static_assert(!RANKS || SHARD, "several ranks per launch: sharded solves only");
@@ -79,44 +132,27 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         bid = blockIdx.x - rk * (unsigned)R.G;
         B = A[rk].B; m = A[rk].m; Sh = A[rk].Sh; R = A[rk].R;
     }
-    constexpr bool SQ = FORM == 1, HC = FORM == 2, S8 = FORM == 4, TG = FORM == 7, GR = FORM == 5 || TG, HG = FORM == 6, REGX = FORM != 0;      // REGX: the checkerboard exchanges registers, no LDS slabs
+    constexpr bool SQ = FORM == Form::SQ16, HC = FORM == Form::HC12, S8 = FORM == Form::S8, TG = FORM == Form::TGRID, GR = FORM == Form::GRID || TG, HG = FORM == Form::HGRID, REGX = FORM != Form::LANE;      // REGX: the checkerboard exchanges registers, no LDS slabs
     // (FORM 7, TG: an even-L TRIANGULAR lattice up to 16 x 16 in the GRID layout — the same 2 x 2 patches, the two diagonal colours of
     //  pgrid::Tri<2, 2> added to the sweep, c^6 where the square lattice takes c^4)
     static_assert(!TG || !SHARD, "triangular grid form: no shards");
     static_assert(!HG || ((NPL == 2 || NPL == 4 || NPL == 8) && UNI && !SSH && T <= 2), "honeycomb grid form: 1, 2 or 4 cells per lane, uniform hopping, at most two slices per wave");
     static_assert(!GR || (NPL == 4 && UNI && !SSH && T <= 4), "grid form (even-L square lattices, 2 x 2 patches on a G x G lane grid): uniform hopping, at most four slices per wave");
     static_assert(!S8 || (NPL == 1 && UNI && !SSH && !SHARD), "8 x 8 DPP form: one site per lane, uniform hopping");
-    static_assert(!SHARD || (T == 1 && (FORM == 0 || FORM == 5 || FORM == 6)), "sharded solves: one slice per wave; lane-program, GRID or HGRID form (the slab closed into a ring)");
+    static_assert(!SHARD || (T == 1 && (FORM == Form::LANE || FORM == Form::GRID || FORM == Form::HGRID)), "sharded solves: one slice per wave; lane-program, GRID or HGRID form (the slab closed into a ring)");
     static_assert(!HC || (NPL == HC_NPL && UNI && !SSH && T <= 3), "honeycomb DPP form: six sites per lane, uniform hopping");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     static_assert(!SQ || NPL == 4, "DPP form: the 16 x 16 square lattice, four sites per lane");
     static_assert(!(SQ && SSH) || (!UNI && T <= 2), "DPP form with bond phonons: a table set per slice, at most two slices per wave");
     static_assert(!SQ || UNI || T <= 2, "DPP form with per-site hopping: 32 registers of (cosh, sinh) leave room for two slices");
     constexpr int NE = MC * ((NPL + 1) / 2);
-    constexpr int HS = NPL * WAVE, SL = slab_len<NPL>();
-    // slices in LDS: LSL lanes per register, HSL doubles per slice.  Honeycomb form: the 48 REAL lanes only — a mirror lane READS the
-    // slot of the lane it mirrors (lr) and writes nothing (lwok): its r, exp(-dtau V) and halo values are the real lane's by
-    // construction, and a quarter of the LDS is not spent on copies (what lets 3 slices per wave fit)
-    constexpr int LSL = HC ? 48 : WAVE, HSL = NPL * LSL;
-    constexpr int NSLAB = REGX ? 0 : T + 1;            // LDS slabs per wave (lane-program form)
+    // where the vectors live and how the LDS is cut: wg_place / wg_layout above, the host's statement too
+    constexpr WgPlace PL = wg_place(FORM, NPL, T, SSH);
+    constexpr int HS = NPL * WAVE, SL = PL.SL, LSL = PL.LSL, HSL = PL.HSL, NSLAB = PL.NSLAB;
+    static_assert(SL == slab_len<NPL>(), "the slab of the lane-program sweeps");
+    constexpr bool S_LDS = PL.S_LDS, E_LDS = PL.E_LDS, X_REG = PL.X_REG, E_SHARED = PL.E_SHARED, X_GLB = PL.X_GLB, PH_LDS = PL.PH_LDS;
     constexpr int NT = SSH ? T + 1 : 1;                // hopping-table sets (SSH: one per slice t0 .. t0+T)
     constexpr int NEJ = SSH ? 1 : T + 1;               // exp(-dtau V) slices (SSH: exp(dtau mu), per site only)
-    // where the loop-invariant and the update-only vectors live.  4 slices per wave (DPP form, throughput shape): exp(-dtau V) moves
-    // to LDS (read twice per iteration; 40 registers) and x stays in registers instead (LDS is full); otherwise E in registers
-    // (0.35 us per iteration faster at 2 slices per wave), x and r in LDS
-    // bond phonons, DPP form, 2 slices per wave: the table set of slice t0 in LDS (24 doubles per lane), x in registers
-    constexpr bool S_LDS = SQ && SSH && T == 2;
-    // honeycomb DPP form, 2 slices per wave: exp(-dtau V) in LDS too (six sites per lane: 36 registers)
-    constexpr bool E_LDS = ((SQ || GR) && T >= 4) || (HC && T >= 2), X_REG = ((SQ || GR) && T >= 4) || S_LDS || (HC && T >= 3);
-    // (honeycomb: neighbouring waves SHARE the slice of exp(-dtau V) between them — [W T + 1] slices per workgroup instead of W (T + 1);
-    //  both write the same values to it)
-    constexpr bool E_SHARED = HC;
-    // honeycomb, 3 slices per wave: x lives in MEMORY (it is touched once per iteration, x += alpha p): its slices are loaded behind the
-    // sums — the meeting that follows hides the round trip — and stored back by the update; between two updates no register holds it
-    constexpr bool X_GLB = HC && T >= 3;
-    // honeycomb, 3 slices per wave: the two HALO slices of p wait in LDS between the p-update that makes them and the mat-vec that
-    // consumes them (24 registers that would otherwise sit through both sweeps)
-    constexpr bool PH_LDS = HC && T >= 3;
     constexpr int NSREG = (SQ && SSH) ? (S_LDS ? T : T + 1) : 1;
     const int W = R.W, G = R.G;
     // (a shard: ONE right-hand side, its G workgroups are the whole grid, spread over the XCDs — several ranks on one GPU, the test
@@ -147,18 +183,19 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
     const int HLX = HG ? m.hc_LX : 0, HLY = HG ? m.hc_LY : 0;         // honeycomb grid form: (LX / PX) x (LY / PY) lanes
     const bool lwok = HC ? hc_real(lane) : (GR ? lane < GGX * GGY : (HG ? lane < (HLX / HgDim<NPL>::PX) * (HLY / HgDim<NPL>::PY) : true));
     const size_t ndim = (size_t)N * L;
+    const WgLayout LY = wg_layout(FORM, NPL, T, SSH, W);
     double *slab = lds + (size_t)wv * NSLAB * SL;
-    double *rall = lds + (size_t)W * NSLAB * SL;       // [W][T][HS]: r of every wave's slices — neighbours read their halo slices here
+    double *rall = lds + LY.r;                         // [W][T][HS]: r of every wave's slices — neighbours read their halo slices here
     double *rl = rall + (size_t)wv * T * HSL;
-    double *xl = rall + (size_t)W * T * HSL + (size_t)wv * T * HSL;    // [W][T][HSL]: this wave's slices of x (unless X_REG)
-    double *eall = rall + (size_t)(X_REG ? 1 : 2) * W * T * HSL;       // [W][T+1][HSL]: exp(-dtau V) of slices t0 .. t0+T (E_LDS)
+    double *xl = rall + LY.x_r + (size_t)wv * T * HSL; // [W][T][HSL]: this wave's slices of x (unless X_REG)
+    double *eall = rall + LY.e_r;                      // [W][T+1][HSL]: exp(-dtau V) of slices t0 .. t0+T (E_LDS)
     double *el = eall + (size_t)wv * (E_SHARED ? T : T + 1) * HSL;
-    double *partA = eall + (E_LDS ? (E_SHARED ? ((size_t)W * T + 1) * HSL : (size_t)W * (T + 1) * HSL) : (S_LDS ? (size_t)W * SQ_TABS * WAVE : 0)), *partB = partA + 8, *bc = partA + 16;   // bc: p.z total, r.r total, 0.0 = a poller gave up
+    double *partA = eall + LY.part_e, *partB = partA + 8, *bc = partA + 16;   // bc: p.z total, r.r total, 0.0 = a poller gave up
     // single-meeting form: part[4][8] wave partials of p.z, r.z, z.z, r.r | tot[8]: the four totals, [4] the direct r.r of the fallback
     // meeting, [5] 0.0 = a poller gave up | partF[8] | rhalo[2][HS]: the boundary slices of r of the two neighbouring workgroups (kept in
     // LDS rather than in registers: the 4-slice shape has none to spare)
-    double *part = partA, *tot = partA + 32, *partF = partA + 40, *rhalo = partA + 48, *zhalo = rhalo + 2 * HSL;
-    double *phl = zhalo + 2 * HSL + (size_t)wv * 2 * HSL;             // [W][2][HSL]: the halo slices of p (PH_LDS)
+    double *part = partA, *tot = partA + 32, *partF = partA + 40, *rhalo = partA + LY.rhalo_part, *zhalo = rhalo + LY.zhalo_rhalo;
+    double *phl = zhalo + LY.ph_zhalo + (size_t)wv * 2 * HSL;         // [W][2][HSL]: the halo slices of p (PH_LDS)
 #define PHALO(k, q) phl[((k) ? 1 : 0) * HSL + lr + (q) * LSL]   // zhalo[2][HS]: their boundary slices of z
     auto wrap = [L](int t) { return (t < 0) ? t + L : ((t >= L) ? t - L : t); };
     auto sgn = [](int t) { return (t == 0) ? -1.0 : 1.0; };
@@ -1072,68 +1109,115 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
 // host side
 // ------------------------------------------------------------------------------------------
 
-struct Shape { int T, W, G; size_t shm; bool sq, hc, s8, gr, hg; int npl; bool tg = false; };   // npl: sites per lane of the kernel (honeycomb DPP form: 6; grid form: 4)
-
-// ELPH_WG_NO_DPP=1: none of the register-exchange forms below, the lane-program form instead (read per call: the tests switch it)
-static bool wg_no_dpp() {
-    const char *e = getenv("ELPH_WG_NO_DPP");
-    return e && e[0] == '1';
+// ONE RECORD PER LAUNCH: which form, which team shape, how much LDS, resident or streaming — made once, by a pure function (plan_wg; a
+// shard's: plan_shard) of what the handle knows (WgFacts) and what the caller and the environment ask (WgKnobs).  elph_wg_cg,
+// elph_wg_usable, the sharded launches and the device-free probe elph_i_wg_plan_probe all read the same record; launch() maps it to
+// the one instantiation of k_cg_wg that runs it.
+struct WgFacts {
+    int kind = 0, L = 0, npl = 0, lp_mc = 0;     // npl: ceil(N / 64), the lane program's sites per lane
+    long long ndim = 0;
+    bool fast = false, fast_capable = false, uniform = false;      // uniform: Holstein, one (cosh, sinh) on every bond (LatticeShape::hop_uniform)
+    const LatticeShape *shape = nullptr;
+    int dot_hi = 0, solo_chain = -1;
+};
+static WgFacts wg_facts(const elph_handle_s *h) {
+    WgFacts F;
+    F.kind = h->kind; F.L = (int)h->L; F.npl = h->npl; F.lp_mc = h->lp_mc; F.ndim = (long long)h->ndim;
+    F.fast = h->fast; F.fast_capable = h->fast_capable; F.uniform = h->shape.hop_uniform; F.shape = &h->shape;
+    F.dot_hi = h->dot_hi; F.solo_chain = h->solo_chain;
+    return F;
 }
 
-// DPP form: Holstein on the 16 x 16 square lattice in the reference's colouring (elph_recognise_lattice)
-static bool sq_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->shape.dpp() == 2 && m.sq_bond && !wg_no_dpp();
+// the batch, the measurement mode and the switches of DESIGN.md §9 — read once per plan, and per call: the tests switch them
+struct WgKnobs {
+    int nrhs = 1;
+    long long fixed_iters = 0;     // > 0: a measurement of this kernel — no cost rule
+    bool no_wg = false;            // ELPH_NO_WG=1: the streaming iteration
+    bool no_dpp = false;           // ELPH_WG_NO_DPP=1: none of the register-exchange forms, the lane-program form instead
+    bool always = false;           // ELPH_WG_ALWAYS=1: no cost rule
+    int force_T = 0;               // ELPH_WG_T: the slices per wave (0: the rule of pick_shape)
+    int wmax = 8;                  // ELPH_WG_W (experiments): cap on the waves per workgroup
+};
+static WgKnobs wg_knobs(int nrhs, long long fixed_iters) {
+    auto on = [](const char *e) { return e && e[0] == '1'; };
+    WgKnobs K;
+    K.nrhs = nrhs; K.fixed_iters = fixed_iters;
+    K.no_wg = on(getenv("ELPH_NO_WG")); K.no_dpp = on(getenv("ELPH_WG_NO_DPP")); K.always = on(getenv("ELPH_WG_ALWAYS"));
+    const char *et = getenv("ELPH_WG_T"), *ew = getenv("ELPH_WG_W");
+    K.force_T = et ? atoi(et) : 0;
+    K.wmax = ew ? std::max(1, atoi(ew)) : 8;
+    return K;
 }
+
+struct WgPlan {
+    bool usable = false;           // a resident form and shape exist for this handle and batch
+    Form form = LANE;
+    int npl = 0, T = 0, W = 0, G = 0;      // npl: sites per lane of the KERNEL (honeycomb DPP form: 6; grid form: 4; honeycomb grid form: 2, 4, 8)
+    bool ssh = false, uniform = false;
+    size_t shm = 0;                // bytes of dynamic LDS: wg_layout's total
+    int per_round = 0;             // right-hand sides one round of the grid holds: one team per G CUs of an XCD
+    double resident_us = 0.0, streaming_us = 0.0;      // per iteration: one round of this plan | the two-kernel iteration of the whole batch
+    bool resident = false;         // usable, and the cost rule (or a measurement, or ELPH_WG_ALWAYS) takes it
+};
+
+// Which form a lattice takes.  for_shard: the slab of a sharded solve, its rows closed into a ring by the caller — a periodic rectangle.
+//  SQ16   the 16 x 16 square lattice in the reference's colouring (elph_recognise_lattice), Holstein or SSH
+//  HC12   Holstein with uniform hopping on 12 x 12 honeycomb cells
+//  S8     Holstein with uniform hopping on the 8 x 8 square lattice
+//  TGRID  Holstein with uniform hopping on an even-L triangular lattice of at most 16 x 16 sites (the recognised shape has a grid of
+//         lanes): the GRID layout with the two diagonal colours (pgrid::Tri<2, 2>)
+//  GRID   Holstein with uniform hopping on a periodic LX x LY square lattice whose 2 x 2 patches fit the lanes of a wave
+//         (LatticeShape::small_square).  An ordinary solve takes it for the sizes WITHOUT a DPP form of their own (not 16 x 16, not 8 x 8);
+//         a sharded solve for every size — the DPP forms know no shards
+//  HGRID  Holstein with uniform hopping on a periodic honeycomb lattice whose cells fit a grid of lanes (LatticeShape::hgrid_regs: 2, 4 or
+//         8 registers per lane = 1, 2 x 1 or 2 x 2 cells; 12 x 12 has a DPP form of its own — which knows no shards)
+//  LANE   everything else with a 4-colour lane program
+// *npl: the kernel's sites per lane.
+static Form pick_form(const WgFacts &F, const WgKnobs &K, bool for_shard, int *npl) {
+    const LatticeShape &S = *F.shape;
+    const bool hol_uni = F.kind == ELPH_MODEL_HOLSTEIN && F.uniform && !K.no_dpp;
+    const bool grid = hol_uni && S.small_square() && S.GX * S.GY >= 1 && S.GX * S.GY <= 64;
+    Form f = LANE;
+    if (for_shard) {
+        // (measured, profiles/r04/shard_ring_grid_forms_ab.log: the GRID form pays from three sites per lane of the lane program — a
+        //  slab of up to 128 sites is two LDS values per lane and colour, cheaper than four registers on half the lanes: config C over 4 / 8
+        //  ranks 5.3 / 6.0 us in the lane program against 6.5 / 7.2; the HGRID form with 8 registers per lane spills in the shard's
+        //  kernel: config D on one rank 16.6 against 9.6 us)
+        if (grid && F.npl >= 3) f = GRID;
+        else if (hol_uni && S.hgrid_regs() > 0 && S.hgrid_regs() != 8) f = HGRID;
+    } else {
+        if (S.dpp() == 2 && !K.no_dpp) f = SQ16;
+        else if (hol_uni && S.hc12()) f = HC12;
+        else if (hol_uni && S.dpp() == 1) f = S8;
+        else if (hol_uni && S.kind == LatticeShape::TRIANGULAR && S.GX > 0) f = TGRID;
+        else if (grid && S.dpp() == 0) f = GRID;
+        else if (hol_uni && S.hgrid_regs() > 0) f = HGRID;
+    }
+    *npl = f == HC12 ? HC_NPL : ((f == GRID || f == TGRID) ? 4 : (f == HGRID ? S.hgrid_regs() : F.npl));
+    return f;
+}
+
+static int largest_divisor_le8(int n, int cap = 8) { for (int w = std::min(cap, n); w >= 1; --w) if (n % w == 0) return w; return 1; }
 
 // T slices per wave: what the register file takes at two waves per SIMD — lane-program form 2 for site phonons with <= 4 sites
 // per lane, else 1; DPP form 2 (config C: 5.8 us per iteration, 24 right-hand sides fill the chip), or 4 for batches that the
 // 2-slice shape cannot hold in one round (6.8 us per iteration, but 48 right-hand sides per round: 14 vs 7.3 M mat-vecs/s);
 // W = the largest divisor of Ltau / T that is <= 8 waves; G = workgroups per right-hand side (<= 32: the 2G record granules of
-// a meeting are polled by one wave instruction)
-// honeycomb DPP form: Holstein with uniform hopping on 12 x 12 cells in the reference's colouring
-static bool hc_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->shape.hc12() && m.uniform && !wg_no_dpp();
-}
-
-// 8 x 8 DPP form: Holstein with uniform hopping on the 8 x 8 square lattice in the reference's colouring
-static bool s8_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->shape.dpp() == 1 && m.uniform && !wg_no_dpp();
-}
-
-// grid form: Holstein with uniform hopping on a periodic LX x LY square lattice in the reference's colouring whose 2 x 2 patches fit the
-// lanes of a wave (LatticeShape::small_square).  An ordinary solve takes it for the sizes WITHOUT a DPP form of their own (not 16 x 16,
-// not 8 x 8); a sharded solve (for_shard) for every size — the slab closed into a ring is such a lattice, and the DPP forms know no shards.
-static bool gr_form(const elph_handle_s *h, const ModelDev &m, bool for_shard = false) {
-    if (h->kind != ELPH_MODEL_HOLSTEIN || !h->shape.small_square() || !m.uniform || m.grid_GX * m.grid_GY < 1 || m.grid_GX * m.grid_GY > 64 || wg_no_dpp()) return false;
-    return for_shard || h->shape.dpp() == 0;
-}
-
-// triangular grid form: Holstein with uniform hopping on an even-L triangular lattice of at most 16 x 16 sites in the reference's colouring
-// (the recognised shape has a grid of lanes): the GRID layout with the two diagonal colours (pgrid::Tri<2, 2>)
-static bool tg_form(const elph_handle_s *h, const ModelDev &m) {
-    return h->kind == ELPH_MODEL_HOLSTEIN && h->shape.kind == LatticeShape::TRIANGULAR && h->shape.GX > 0 && m.uniform && !wg_no_dpp();
-}
-
-// honeycomb grid form: Holstein with uniform hopping on a periodic honeycomb lattice of LX x LY cells in the reference's colouring whose cells
-// fit a grid of lanes (LatticeShape::hgrid_regs; 12 x 12 has a DPP form of its own — which knows no shards).  Returns the registers per
-// lane (2, 4 or 8: 1, 2 x 1 or 2 x 2 cells), 0: no.
-static int hg_form(const elph_handle_s *h, const ModelDev &m, bool for_shard = false) {
-    if (h->kind != ELPH_MODEL_HOLSTEIN || (h->shape.hc12() && !for_shard) || !m.uniform || wg_no_dpp()) return 0;
-    return h->shape.hgrid_regs();
-}
-
-static int largest_divisor_le8(int n, int cap = 8) { for (int w = std::min(cap, n); w >= 1; --w) if (n % w == 0) return w; return 1; }
-
-static bool pick_shape(const elph_handle_s *h, const ModelDev &m, int forceT, int nrhs, Shape *out) {
-    const int L = (int)h->L;
-    const bool ssh = (h->kind == ELPH_MODEL_SSH), sq = sq_form(h, m), hc = !sq && hc_form(h, m), s8 = !sq && !hc && s8_form(h, m);
-    const bool tg = !sq && !hc && !s8 && tg_form(h, m);
-    const bool gr = !sq && !hc && !s8 && (tg || gr_form(h, m));
-    const int hgn = (!sq && !hc && !s8 && !gr) ? hg_form(h, m) : 0;
-    const bool hg = hgn > 0;
-    const int npl = hc ? HC_NPL : (gr ? 4 : (hg ? hgn : h->npl));
-    if (h->lp_mc != 4 && !tg) return false;               // (a six-colour lattice has no lane-program form here: only the triangular grid form)
-    if (!hc && !gr && !hg && h->npl > 5) return false;     // (the lane-program form carries at most 320 sites; elph_wg_usable lets larger honeycomb lattices through for the grid form only)
+// a meeting are polled by one wave instruction).  Fills form, npl, T, W, G, shm of *out.
+static bool pick_shape(const WgFacts &F, const WgKnobs &K, WgPlan *out) {
+    const int L = F.L, forceT = K.force_T, nrhs = K.nrhs;
+    int npl = 0;
+    const Form form = pick_form(F, K, false, &npl);
+    const bool ssh = F.kind == ELPH_MODEL_SSH, sq = form == SQ16, hc = form == HC12, s8 = form == S8, gr = form == GRID || form == TGRID, hg = form == HGRID;
+    const bool lane = !sq && !hc && !gr && !hg;            // (the lane-program form and, where the rules below do not name it, the 8 x 8 DPP form)
+    if (F.lp_mc != 4 && form != TGRID) return false;       // (a six-colour lattice has no lane-program form here: only the triangular grid form)
+    if (lane && F.npl > 5) return false;                   // (the lane-program form carries at most 320 sites; plan_wg lets larger honeycomb lattices through for the grid form only)
+    auto take = [&](int T, int W, int G) {
+        const size_t shm = wg_layout(form, npl, T, ssh, W).total * sizeof(double);
+        if (shm > 160 * 1024) return false;
+        out->form = form; out->npl = npl; out->T = T; out->W = W; out->G = G; out->shm = shm;
+        return true;
+    };
     // one site per lane (the 8 x 8 lattice: config B): the whole time axis fits ONE workgroup — up to 8 waves of 4, 5 or 8 slices — and
     // a team of one needs no records, no boundary granules, no polls: its meeting is an LDS reduction and a barrier, and a round holds
     // 256 right-hand sides.  Its iteration is longer (config B: 6.3 us at 5 slices per wave against 3.5 at 2 with teams of four), so it
@@ -1145,16 +1229,11 @@ static bool pick_shape(const elph_handle_s *h, const ModelDev &m, int forceT, in
     }
     // (the 8 x 8 DPP form: the team of one is the fastest shape at every batch size — 2.04 us per iteration for one right-hand side, 2.3 us
     //  for 256 = 222 M mat-vecs/s — its sweeps are a few dozen register moves)
-    if (!ssh && !sq && !hc && !gr && !hg && h->npl == 1 && (big_batch || s8)) {
+    if (!ssh && lane && F.npl == 1 && (big_batch || s8)) {
         const int one[3] = {4, 5, 8};
         for (int T : one) {
             if ((forceT && T != forceT) || L % T || L / T > 8 || L / T < 2) continue;
-            const int W = L / T;
-            const size_t SL = (size_t)npl * WAVE + 2 * WAVE, HS = (size_t)npl * WAVE;
-            const size_t shm = ((size_t)W * (s8 ? 0 : T + 1) * SL + 2 * (size_t)W * T * HS + 48 + 4 * HS) * sizeof(double);
-            if (shm > 160 * 1024) continue;
-            out->T = T; out->W = W; out->G = 1; out->shm = shm; out->sq = false; out->hc = false; out->s8 = s8; out->gr = false; out->hg = false; out->npl = npl;
-            return true;
+            if (take(T, L / T, 1)) return true;
         }
     }
     const int cand[4] = {4, 3, 2, 1};
@@ -1174,7 +1253,7 @@ static bool pick_shape(const elph_handle_s *h, const ModelDev &m, int forceT, in
             }
         }
         if (T == 4) {
-            if (!(sq || gr) || !m.uniform || ssh) continue;
+            if (!(sq || gr) || !F.uniform || ssh) continue;
             if (forceT != 4) {                           // only when 2 slices per wave would need a second round: 8 XCDs x (32 CUs / G2) teams
                 if (L % 2) continue;
                 const int G2 = (L / 2) / largest_divisor_le8(L / 2);
@@ -1183,15 +1262,15 @@ static bool pick_shape(const elph_handle_s *h, const ModelDev &m, int forceT, in
         }
         if (gr && T == 3) continue;
         if (hg && T > 2) continue;
-        if (T == 2 && (sq || hc || gr || hg) && forceT != 2) {
+        if (T == 2 && !lane && forceT != 2) {
             // DPP form: a batch that one round of 1 slice per wave holds (config C: up to 8 right-hand sides, one team of 20 workgroups per
             // XCD) runs that shape — with ONE meeting per iteration the shorter mat-vec wins over the larger team: 3.47 against 4.00 us
             // per iteration for one right-hand side (round 2, two meetings: the other way round)
             const int G1 = L / largest_divisor_le8(L);
             if (G1 <= 32 && L / G1 >= 2 && nrhs <= 8 * (32 / G1)) continue;
         }
-        if (T == 2 && !sq && !hc && !gr && !hg && ((ssh && h->npl > 4) || h->npl > 5 || (!ssh && h->npl >= 4 && !m.uniform))) continue;
-        if (T == 2 && !sq && !hc && !gr && !hg && (h->npl == 5 || ssh) && forceT != 2) {
+        if (T == 2 && lane && ((ssh && F.npl > 4) || F.npl > 5 || (!ssh && F.npl >= 4 && !F.uniform))) continue;
+        if (T == 2 && lane && (F.npl == 5 || ssh) && forceT != 2) {
             // 5 sites per lane (honeycomb L = 12) and bond phonons (three table sets per wave: 41 registers spill): 2 slices per wave are
             // slower per iteration (D: 10.0 vs 9.3 us; E: 12.9 vs 9.5 us) but hold more right-hand sides per round (D: 24 instead
             // of 16; E: 24 instead of 8) — taken once a batch exceeds the round of 1 slice per wave
@@ -1199,23 +1278,10 @@ static bool pick_shape(const elph_handle_s *h, const ModelDev &m, int forceT, in
             if (G1 <= 32 && nrhs <= 8 * (32 / G1)) continue;
         }
         if (L % T) continue;
-        const int Wt = L / T;
-        int W = 0;
-        const char *ew = getenv("ELPH_WG_W");              // (experiments: cap on the waves per workgroup)
-        const int wmax = ew ? std::max(1, atoi(ew)) : 8;
-        for (int w = std::min(wmax, Wt); w >= 1; --w) if (Wt % w == 0) { W = w; break; }
-        const int G = Wt / W;
+        const int Wt = L / T, W = largest_divisor_le8(Wt, K.wmax), G = Wt / W;
         if (G > 32) continue;
         if (G > 1 && W < 2) continue;                    // (a wave polls at most ONE neighbouring workgroup's boundary slice)
-        const size_t SL = (size_t)npl * WAVE + 2 * WAVE, HS = (size_t)npl * (hc ? 48 : WAVE);     // (the kernel's HSL: a slice in LDS)
-        const bool s_lds = sq && ssh && T == 2;            // (the kernel's S_LDS: table set of slice t0 in LDS, x in registers)
-        const bool e_lds = ((sq || gr) && T >= 4) || (hc && T >= 2), x_reg = ((sq || gr) && T >= 4) || s_lds || (hc && T >= 3);
-        const size_t shm = ((size_t)W * ((sq || hc || s8 || gr || hg) ? 0 : T + 1) * SL + (size_t)(x_reg ? 1 : 2) * W * T * HS +
-                            (e_lds ? (hc ? ((size_t)W * T + 1) * HS : (size_t)W * (T + 1) * HS) : 0) + (s_lds ? (size_t)W * wg::SQ_TABS * WAVE : 0) +
-                            48 + 4 * HS + ((hc && T >= 3) ? (size_t)W * 2 * HS : 0)) * sizeof(double);   // + partials, totals, rhalo[2][HS], zhalo[2][HS] (+ the halo slices of p)
-        if (shm > 160 * 1024) continue;
-        out->T = T; out->W = W; out->G = G; out->shm = shm; out->sq = sq; out->hc = hc; out->s8 = s8; out->gr = gr; out->hg = hg; out->npl = npl; out->tg = tg;
-        return true;
+        if (take(T, W, G)) return true;
     }
     return false;
 }
@@ -1223,99 +1289,148 @@ static bool pick_shape(const elph_handle_s *h, const ModelDev &m, int forceT, in
 // ---- the cost model behind the choice of form: ONE table, every entry with the measurement it was fitted to -----------------------
 // us per iteration of ONE round of the resident kernel (a round holds 8 x floor(32 / G) right-hand sides: one team per G CUs of an XCD)
 //     t = a + g * G + s * T * (sites per lane / 4 where the form scales with them)
-// and of the two-kernel streaming iteration (HBM-bound, linear in the batch).  Fitted on MI355X; a form that is not in the table is
-// priced as the lane program.  The rule only has to order the two forms: a 20 % error in an entry moves a crossover by a few
-// right-hand sides.
-struct WgCost { const char *form; double a, g, s; const char *measured; };
+// and of the two-kernel streaming iteration (HBM-bound, linear in the batch).  Fitted on MI355X.  The rule only has to order the two
+// forms: a 20 % error in an entry moves a crossover by a few right-hand sides.
+struct WgCost { Form form; bool ssh; double a, g, s; const char *measured; };
 static const WgCost wg_cost_table[] = {
-    {"lane program (FORM 0)",            2.00, 0.12, 0.50, "profiles/r02/time_forms.log: configs B, C, D, E at 1-2 slices per wave; x sites per lane; + 3.9 for SSH at 2 slices, 0.85 T per slice from 4"},
-    {"16x16 DPP (FORM 1, Holstein)",     2.66, 0.01, 0.62, "profiles/r03/time_forms.log: 3.5 / 4.0 / 5.2 us at 1 / 2 / 4 slices per wave"},
-    {"16x16 DPP, bond phonons",          2.50, 0.00, 1.30, "profiles/r03/time_forms_E_ssh_dpp.log: 3.8 / 5.1 us at 1 / 2 slices"},
-    {"honeycomb 12x12 DPP (FORM 2)",     2.10, 0.00, 1.70, "profiles/r03/time_forms_D_honeycomb_dpp.log: 3.8 / 5.5 us at 1 / 2 slices; 8.6 us at 3 (time_forms_D_three_slices_per_wave.log)"},
-    {"8x8 DPP (FORM 4), team of one",    2.30, 0.00, 0.00, "profiles/r03/time_wg_B_8x8_dpp_form.log: 2.04-2.3 us whatever the batch"},
-    {"GRID (FORM 5)",                    2.90, 0.01, 1.35, "profiles/r04/grid_form_even_L_square_lattices.log: L = 12: 4.3 / 5.6 / 10.0 us at 1 / 2 / 4 slices; L = 14, 10: 3.6-4.0 at 1"},
-    {"TGRID (FORM 7, triangular)",       3.20, 0.00, 2.20, "profiles/r04/tgrid_triangular_resident.log: L = 16: 4.9 / 6.7 / 12.4 us at 1 / 2 / 4 slices per wave (4: 69 doubles spilled)"},
-    {"HGRID (FORM 6)",                   2.30, 0.01, 1.10, "profiles/r04/hgrid_form_honeycomb_lattices.log: L = 6: 2.5 us (2 registers per lane), L = 10: 3.3-3.8 (4), L = 16: 4.5-5.8 (8); x sites per lane / 4"},
+    {LANE,  false, 2.00, 0.12, 0.50, "profiles/r02/time_forms.log: configs B, C, D, E at 1-2 slices per wave; x sites per lane; + 3.9 for SSH at 2 slices, 0.85 T per slice from 4"},
+    {SQ16,  false, 2.66, 0.01, 0.62, "profiles/r03/time_forms.log: 3.5 / 4.0 / 5.2 us at 1 / 2 / 4 slices per wave"},
+    {SQ16,  true,  2.50, 0.00, 1.30, "profiles/r03/time_forms_E_ssh_dpp.log: 3.8 / 5.1 us at 1 / 2 slices"},
+    {HC12,  false, 2.10, 0.00, 1.70, "profiles/r03/time_forms_D_honeycomb_dpp.log: 3.8 / 5.5 us at 1 / 2 slices; 8.6 us at 3 (time_forms_D_three_slices_per_wave.log)"},
+    {S8,    false, 2.30, 0.00, 0.00, "profiles/r03/time_wg_B_8x8_dpp_form.log: team of one, 2.04-2.3 us whatever the batch"},
+    {GRID,  false, 2.90, 0.01, 1.35, "profiles/r04/grid_form_even_L_square_lattices.log: L = 12: 4.3 / 5.6 / 10.0 us at 1 / 2 / 4 slices; L = 14, 10: 3.6-4.0 at 1"},
+    {TGRID, false, 3.20, 0.00, 2.20, "profiles/r04/tgrid_triangular_resident.log: L = 16: 4.9 / 6.7 / 12.4 us at 1 / 2 / 4 slices per wave (4: 69 doubles spilled)"},
+    {HGRID, false, 2.30, 0.01, 1.10, "profiles/r04/hgrid_form_honeycomb_lattices.log: L = 6: 2.5 us (2 registers per lane), L = 10: 3.3-3.8 (4), L = 16: 4.5-5.8 (8); x sites per lane / 4"},
 };
 static const double wg_streaming_cost[3] = {10.0, 0.56, 0.02};   // us: launch floor + nrhs x (0.56 x Ndim / 40960 [x 1.1 for SSH] + 0.02) — profiles/r03/time_forms.log (C: 37 us at 64, 128 at 256)
 
-static double resident_iteration_us(const elph_handle_s *h, const Shape &sh) {
-    const bool ssh = h->kind == ELPH_MODEL_SSH;
-    if (sh.s8) return wg_cost_table[4].a;
-    if (sh.sq && ssh) return wg_cost_table[2].a + wg_cost_table[2].s * sh.T;
-    if (sh.hc) return (sh.T == 3) ? 8.6 : wg_cost_table[3].a + wg_cost_table[3].s * sh.T;
-    if (sh.sq) return wg_cost_table[1].a + wg_cost_table[1].g * sh.G + wg_cost_table[1].s * sh.T;
-    if (sh.gr && sh.tg) return wg_cost_table[6].a + wg_cost_table[6].g * sh.G + wg_cost_table[6].s * sh.T;
-    if (sh.gr) return wg_cost_table[5].a + wg_cost_table[5].g * sh.G + wg_cost_table[5].s * sh.T;
-    if (sh.hg) return wg_cost_table[7].a + wg_cost_table[7].g * sh.G + wg_cost_table[7].s * sh.T * (sh.npl / 4.0);
-    return wg_cost_table[0].a + wg_cost_table[0].g * sh.G + (sh.T >= 4 ? 0.85 : wg_cost_table[0].s) * sh.T * h->npl + ((ssh && sh.T == 2) ? 3.9 : 0.0);
-}
-static double streaming_iteration_us(const elph_handle_s *h, int nrhs) {
-    return wg_streaming_cost[0] + nrhs * (wg_streaming_cost[1] * (double)h->ndim / 40960.0 * (h->kind == ELPH_MODEL_SSH ? 1.1 : 1.0) + wg_streaming_cost[2]);
-}
-
-template <int NPL, int T, bool SSH, bool UNI, int FORM, bool SHARD = false, bool X0Z = false>
-static hipError_t launch_k(elph_handle_s *h, const Shape &sh, dim3 grid, const CgBufs &B, const ModelDev &m, const WgCtl &R,
-                           const ShardCtl &Sh = ShardCtl()) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_cg_wg<NPL, T, SSH, UNI, FORM, SHARD, X0Z>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_cg_wg<NPL, T, SSH, UNI, FORM, SHARD, X0Z>), grid, dim3(sh.W * WAVE), sh.shm, h->stream, B, m, R, Sh);
-    return hipGetLastError();
-}
-
-template <int NPL>
-static hipError_t launch_shard_npl(elph_handle_s *h, const Shape &sh, dim3 grid, const CgBufs &B, const ModelDev &m, const WgCtl &R,
-                                   const ShardCtl &Sh) {
-    if (h->kind == ELPH_MODEL_SSH) return launch_k<NPL, 1, true, false, 0, true>(h, sh, grid, B, m, R, Sh);
-    return m.uniform ? launch_k<NPL, 1, false, true, 0, true>(h, sh, grid, B, m, R, Sh)
-                     : launch_k<NPL, 1, false, false, 0, true>(h, sh, grid, B, m, R, Sh);
-}
-// a shard in a register-exchange form: the slab is a periodic rectangle (its rows closed into a ring by the caller's bond table)
-static hipError_t launch_shard_grid(elph_handle_s *h, const Shape &sh, dim3 grid, const CgBufs &B, const ModelDev &m, const WgCtl &R,
-                                    const ShardCtl &Sh) {
-    if (sh.gr) return launch_k<4, 1, false, true, 5, true>(h, sh, grid, B, m, R, Sh);
-    switch (sh.npl) {
-        case 2: return launch_k<2, 1, false, true, 6, true>(h, sh, grid, B, m, R, Sh);
-        case 4: return launch_k<4, 1, false, true, 6, true>(h, sh, grid, B, m, R, Sh);
-        default: return launch_k<8, 1, false, true, 6, true>(h, sh, grid, B, m, R, Sh);
+// the entry of a form; bond phonons take the form's SSH entry where it has one (the lane program prices them by a term of its own)
+static const WgCost &wg_cost(Form form, bool ssh) {
+    const WgCost *hol = nullptr;
+    for (const WgCost &c : wg_cost_table) {
+        if (c.form == form && c.ssh == ssh) return c;
+        if (c.form == form && !c.ssh) hol = &c;
     }
+    return hol ? *hol : wg_cost_table[0];
+}
+static double resident_iteration_us(const WgFacts &F, const WgPlan &P) {
+    const WgCost &c = wg_cost(P.form, P.ssh);
+    switch (P.form) {
+        case S8: return c.a;
+        case HC12: return (P.T == 3) ? 8.6 : c.a + c.s * P.T;
+        case SQ16: return P.ssh ? c.a + c.s * P.T : c.a + c.g * P.G + c.s * P.T;
+        case HGRID: return c.a + c.g * P.G + c.s * P.T * (P.npl / 4.0);
+        case GRID: case TGRID: return c.a + c.g * P.G + c.s * P.T;
+        case LANE: break;
+    }
+    return c.a + c.g * P.G + (P.T >= 4 ? 0.85 : c.s) * P.T * F.npl + ((P.ssh && P.T == 2) ? 3.9 : 0.0);
+}
+static double streaming_iteration_us(const WgFacts &F, int nrhs) {
+    return wg_streaming_cost[0] + nrhs * (wg_streaming_cost[1] * (double)F.ndim / 40960.0 * (F.kind == ELPH_MODEL_SSH ? 1.1 : 1.0) + wg_streaming_cost[2]);
 }
 
-template <int NPL>
-static hipError_t launch_npl(elph_handle_s *h, const Shape &sh, dim3 grid, const CgBufs &B, const ModelDev &m, const WgCtl &R) {
-    if constexpr (NPL == 4) {
-        if (sh.sq) {
-            if (h->kind == ELPH_MODEL_SSH) return (sh.T == 2) ? launch_k<4, 2, true, false, 1>(h, sh, grid, B, m, R) : launch_k<4, 1, true, false, 1>(h, sh, grid, B, m, R);
-            if (!m.uniform) return (sh.T == 2) ? launch_k<4, 2, false, false, 1>(h, sh, grid, B, m, R) : launch_k<4, 1, false, false, 1>(h, sh, grid, B, m, R);
-            if (sh.T == 4) return R.x0_zero ? launch_k<4, 4, false, true, 1, false, true>(h, sh, grid, B, m, R) : launch_k<4, 4, false, true, 1>(h, sh, grid, B, m, R);
-            if (sh.T == 2) return launch_k<4, 2, false, true, 1>(h, sh, grid, B, m, R);
-            return launch_k<4, 1, false, true, 1>(h, sh, grid, B, m, R);
-        }
+// The plan of an un-sharded solve.  Which form is faster for THIS batch is a deterministic rule (never a timing at run time — which form
+// runs decides the last bits of a solution) from ONE table of measured constants, wg_cost_table above.
+static WgPlan plan_wg(const WgFacts &F, const WgKnobs &K) {
+    WgPlan P;
+    P.ssh = F.kind == ELPH_MODEL_SSH; P.uniform = F.uniform;
+    const LatticeShape &S = *F.shape;
+    const bool hol = F.kind == ELPH_MODEL_HOLSTEIN;
+    const bool tri_grid = hol && S.kind == LatticeShape::TRIANGULAR && S.GX > 0;      // (a six-colour lattice, but its resident form needs no lane program)
+    // (npl > 5: the lane-program form's limit — 320 sites; the honeycomb grid form carries up to 512 in one wave)
+    if (K.no_wg || !F.fast || (F.lp_mc != 4 && !tri_grid) || (F.npl > 5 && !(S.honeycomb() && !S.hc12() && hol)) || F.dot_hi != 0 || F.solo_chain >= 0) return P;
+    if (!pick_shape(F, K, &P)) return P;
+    P.usable = true;
+    P.per_round = 8 * std::max(1, 32 / P.G);
+    P.resident_us = resident_iteration_us(F, P);
+    P.streaming_us = streaming_iteration_us(F, K.nrhs);
+    const double rounds = (double)((K.nrhs + P.per_round - 1) / P.per_round);
+    P.resident = K.fixed_iters > 0 || K.always || !(rounds * P.resident_us > P.streaming_us);
+    return P;
+}
+
+// One rank's plan of a solve over `world` ranks: one slice per wave on every rank (slab sizes differ between ranks; the team shape must
+// not: elph_shard_shape).  A slab whose rows the caller closed into a ring (a periodic rectangle in the reference's colouring: sharded.py,
+// ring=True) runs a register-exchange form — the own rows of z = M^T M p do not see the ring bond (it lies beyond the ghost rows'
+// dependency closure).  A sharded solve has no streaming iteration to compare with: its plan is resident.
+static int plan_shard(const WgFacts &F, const WgKnobs &K, int world, WgPlan *out) {
+    WgPlan P;
+    P.ssh = F.kind == ELPH_MODEL_SSH; P.uniform = F.uniform;
+    P.form = pick_form(F, K, true, &P.npl);
+    if (P.form == LANE && (!F.fast_capable || F.lp_mc != 4 || F.npl > 5)) {
+        elph_set_error("sharded solve: the slab needs a 4-colour lane program and <= 320 sites (N = %lld)", F.ndim / std::max(F.L, 1));
+        return ELPH_E_UNSUPPORTED;
     }
-    if (h->kind == ELPH_MODEL_SSH) {
-        if constexpr (NPL <= 4) { if (sh.T == 2) return launch_k<NPL, 2, true, false, 0>(h, sh, grid, B, m, R); }
-        return launch_k<NPL, 1, true, false, 0>(h, sh, grid, B, m, R);
+    RC(elph_shard_shape(F.L, world, &P.W, &P.G, nullptr, nullptr));
+    P.T = 1;
+    P.shm = wg_layout(P.form, P.npl, P.T, P.ssh, P.W).total * sizeof(double);
+    P.per_round = 1;
+    P.usable = P.resident = true;
+    *out = P;
+    return ELPH_OK;
+}
+
+// ---- the launch table: every instantiation of k_cg_wg, named once ------------------------------------------------------------------
+// PLAIN: an un-sharded solve; SHARD: one rank of a solve over several GPUs; RANKS: several ranks of a sharded solve in one launch
+enum Variant { PLAIN, SHARD, RANKS };
+typedef void (*WgKernel)(CgBufs, ModelDev, WgCtl, ShardCtl);
+struct WgEntry { Variant v; int form, npl, T; bool ssh, uni, x0z; WgKernel fn; };
+#define K(V, FORM, NPL, T, SSH, UNI, X0Z) {V, FORM, NPL, T, SSH, UNI, X0Z, k_cg_wg<NPL, T, SSH, UNI, FORM, (V) != PLAIN, X0Z, (V) == RANKS>}
+#define K_UNI(V, FORM, NPL, T) K(V, FORM, NPL, T, false, true, false), K(V, FORM, NPL, T, false, false, false)      // Holstein: uniform | per-bond hopping
+#define K_SSH(V, FORM, NPL, T) K(V, FORM, NPL, T, true, false, false)
+#define K_HOL(V, FORM, NPL, T) K(V, FORM, NPL, T, false, true, false)                                                // the forms of uniform hopping
+static const WgEntry wg_kernels[] = {
+    // lane program: 1 or 2 slices per wave up to five sites per lane (bond phonons: 2 slices up to four) ...
+    K_UNI(PLAIN, LANE, 1, 1), K_UNI(PLAIN, LANE, 2, 1), K_UNI(PLAIN, LANE, 3, 1), K_UNI(PLAIN, LANE, 4, 1), K_UNI(PLAIN, LANE, 5, 1),
+    K_UNI(PLAIN, LANE, 1, 2), K_UNI(PLAIN, LANE, 2, 2), K_UNI(PLAIN, LANE, 3, 2), K_UNI(PLAIN, LANE, 4, 2), K_UNI(PLAIN, LANE, 5, 2),
+    K_SSH(PLAIN, LANE, 1, 1), K_SSH(PLAIN, LANE, 2, 1), K_SSH(PLAIN, LANE, 3, 1), K_SSH(PLAIN, LANE, 4, 1), K_SSH(PLAIN, LANE, 5, 1),
+    K_SSH(PLAIN, LANE, 1, 2), K_SSH(PLAIN, LANE, 2, 2), K_SSH(PLAIN, LANE, 3, 2), K_SSH(PLAIN, LANE, 4, 2),
+    // ... and one site per lane in a team of one: 4, 5 or 8 slices per wave
+    K_UNI(PLAIN, LANE, 1, 4), K_UNI(PLAIN, LANE, 1, 5), K_UNI(PLAIN, LANE, 1, 8),
+    // 16 x 16 DPP form: uniform hopping up to 4 slices per wave (with the variant that does not read x0 = 0), per-site hopping and bond phonons up to 2
+    K_UNI(PLAIN, SQ16, 4, 1), K_UNI(PLAIN, SQ16, 4, 2), K_HOL(PLAIN, SQ16, 4, 4), K(PLAIN, SQ16, 4, 4, false, true, true),
+    K_SSH(PLAIN, SQ16, 4, 1), K_SSH(PLAIN, SQ16, 4, 2),
+    K_HOL(PLAIN, HC12, HC_NPL, 1), K_HOL(PLAIN, HC12, HC_NPL, 2), K_HOL(PLAIN, HC12, HC_NPL, 3),
+    K_HOL(PLAIN, S8, 1, 1), K_HOL(PLAIN, S8, 1, 2), K_HOL(PLAIN, S8, 1, 4), K_HOL(PLAIN, S8, 1, 5), K_HOL(PLAIN, S8, 1, 8),
+    K_HOL(PLAIN, GRID, 4, 1), K_HOL(PLAIN, GRID, 4, 2), K_HOL(PLAIN, GRID, 4, 4),
+    K_HOL(PLAIN, TGRID, 4, 1), K_HOL(PLAIN, TGRID, 4, 2), K_HOL(PLAIN, TGRID, 4, 4),
+    K_HOL(PLAIN, HGRID, 2, 1), K_HOL(PLAIN, HGRID, 4, 1), K_HOL(PLAIN, HGRID, 8, 1), K_HOL(PLAIN, HGRID, 2, 2), K_HOL(PLAIN, HGRID, 4, 2), K_HOL(PLAIN, HGRID, 8, 2),
+    // one rank of a sharded solve: one slice per wave; the slab in the lane program, or — closed into a ring — in the GRID or HGRID form
+    K_UNI(SHARD, LANE, 1, 1), K_UNI(SHARD, LANE, 2, 1), K_UNI(SHARD, LANE, 3, 1), K_UNI(SHARD, LANE, 4, 1), K_UNI(SHARD, LANE, 5, 1),
+    K_SSH(SHARD, LANE, 1, 1), K_SSH(SHARD, LANE, 2, 1), K_SSH(SHARD, LANE, 3, 1), K_SSH(SHARD, LANE, 4, 1), K_SSH(SHARD, LANE, 5, 1),
+    K_HOL(SHARD, GRID, 4, 1), K_HOL(SHARD, HGRID, 2, 1), K_HOL(SHARD, HGRID, 4, 1), K_HOL(SHARD, HGRID, 8, 1),
+    // the ranks of one device in one launch: site phonons, lane program or GRID form
+    K_UNI(RANKS, LANE, 1, 1), K_UNI(RANKS, LANE, 2, 1), K_UNI(RANKS, LANE, 3, 1), K_UNI(RANKS, LANE, 4, 1), K_UNI(RANKS, LANE, 5, 1),
+    K_HOL(RANKS, GRID, 4, 1),
+};
+#undef K_HOL
+#undef K_SSH
+#undef K_UNI
+#undef K
+
+// (x0_zero is a licence, not a demand: a plan without a kernel that skips reading x0 runs the one that reads it)
+static const WgEntry *find_kernel(const WgPlan &P, Variant v, bool x0_zero) {
+    const WgEntry *reads_x0 = nullptr;
+    for (const WgEntry &k : wg_kernels) {
+        if (k.v != v || k.form != P.form || k.npl != P.npl || k.T != P.T || k.ssh != P.ssh || k.uni != P.uniform) continue;
+        if (k.x0z == x0_zero) return &k;
+        if (!k.x0z) reads_x0 = &k;
     }
-    if constexpr (NPL == 1) {
-        if (sh.s8) {                // (the 8 x 8 DPP form)
-            switch (sh.T) {
-                case 8: return launch_k<1, 8, false, true, 4>(h, sh, grid, B, m, R);
-                case 5: return launch_k<1, 5, false, true, 4>(h, sh, grid, B, m, R);
-                case 4: return launch_k<1, 4, false, true, 4>(h, sh, grid, B, m, R);
-                case 2: return launch_k<1, 2, false, true, 4>(h, sh, grid, B, m, R);
-                default: return launch_k<1, 1, false, true, 4>(h, sh, grid, B, m, R);
-            }
-        }
+    return reads_x0;
+}
+
+static int launch(const WgPlan &P, Variant v, bool x0_zero, dim3 grid, hipStream_t stream, const CgBufs &B, const ModelDev &m, const WgCtl &R,
+                  const ShardCtl &Sh = ShardCtl()) {
+    static const char *const vname[] = {"", " (shard)", " (ranks)"};
+    const WgEntry *k = find_kernel(P, v, x0_zero);
+    if (!k) {
+        elph_set_error("k_cg_wg%s: no kernel for form %d with %d sites per lane, %d slices per wave, ssh %d, uniform %d", vname[v], (int)P.form, P.npl, P.T, (int)P.ssh, (int)P.uniform);
+        return ELPH_E_STATE;
     }
-    if constexpr (NPL == 1) {       // (one workgroup per right-hand side: pick_shape)
-        if (sh.T == 4) return m.uniform ? launch_k<1, 4, false, true, 0>(h, sh, grid, B, m, R) : launch_k<1, 4, false, false, 0>(h, sh, grid, B, m, R);
-        if (sh.T == 5) return m.uniform ? launch_k<1, 5, false, true, 0>(h, sh, grid, B, m, R) : launch_k<1, 5, false, false, 0>(h, sh, grid, B, m, R);
-        if (sh.T == 8) return m.uniform ? launch_k<1, 8, false, true, 0>(h, sh, grid, B, m, R) : launch_k<1, 8, false, false, 0>(h, sh, grid, B, m, R);
-    }
-    if constexpr (NPL <= 5) {
-        if (sh.T == 2) return m.uniform ? launch_k<NPL, 2, false, true, 0>(h, sh, grid, B, m, R) : launch_k<NPL, 2, false, false, 0>(h, sh, grid, B, m, R);
-    }
-    return m.uniform ? launch_k<NPL, 1, false, true, 0>(h, sh, grid, B, m, R) : launch_k<NPL, 1, false, false, 0>(h, sh, grid, B, m, R);
+    hipError_t e = hipFuncSetAttribute((const void *)k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.shm);
+    if (e == hipSuccess) { hipLaunchKernelGGL(k->fn, grid, dim3(P.W * WAVE), P.shm, stream, B, m, R, Sh); e = hipGetLastError(); }
+    if (e != hipSuccess) { elph_set_error("launch k_cg_wg%s failed: %s", vname[v], hipGetErrorString(e)); return ELPH_E_HIP; }
+    return ELPH_OK;
 }
 
 }  // namespace wg
@@ -1338,25 +1453,28 @@ int elph_i_resident_wg_limit(const elph_handle_s *h) {
     return lim;
 }
 
-// ELPH_WG_T: force the slices per wave of the resident kernel (0: the rule of pick_shape)
-static int wg_t() {
-    const char *et = getenv("ELPH_WG_T");
-    return et ? atoi(et) : 0;
+// a view of the plan: does a resident form exist for this handle and batch, and with which team shape (not: does the cost rule take it)
+bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs) {
+    const wg::WgPlan P = wg::plan_wg(wg::wg_facts(h), wg::wg_knobs(nrhs, 0));
+    if (!P.usable) return false;
+    if (T) *T = P.T;
+    if (W) *W = P.W;
+    if (G) *G = P.G;
+    return true;
 }
 
-bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs) {
-    const char *eo = getenv("ELPH_NO_WG");                 // read per call: the tests switch between the two forms
-    const bool off = eo && eo[0] == '1';
-    // (h->npl > 5: the lane-program form's limit — 320 sites; the honeycomb grid form carries up to 512 in one wave)
-    const bool hol = h->kind == ELPH_MODEL_HOLSTEIN;
-    const bool tri_grid = hol && h->shape.kind == LatticeShape::TRIANGULAR && h->shape.GX > 0;      // (a six-colour lattice, but its resident form needs no lane program)
-    if (off || !h->fast || (h->lp_mc != 4 && !tri_grid) || (h->npl > 5 && !(h->shape.honeycomb() && !h->shape.hc12() && hol)) || h->dot_hi != 0 || h->solo_chain >= 0) return false;
-    wg::Shape sh;
-    if (!wg::pick_shape(h, elph_model_dev(h), wg_t(), nrhs, &sh)) return false;
-    if (T) *T = sh.T;
-    if (W) *W = sh.W;
-    if (G) *G = sh.G;
-    return true;
+// The plan of a handle that need not own a device (elph_bench_wg_plan): world = 0 the un-sharded solve of nrhs right-hand sides, world > 0
+// one rank of a solve over that many.  out[9]: usable, form, sites per lane, T, W, G, bytes of LDS, resident, whether the launch table
+// holds the plan's kernel.
+void elph_i_wg_plan_probe(const elph_handle_s *h, int nrhs, int world, int *out) {
+    const wg::WgFacts F = wg::wg_facts(h);
+    const wg::WgKnobs K = wg::wg_knobs(nrhs, 0);
+    wg::WgPlan P;
+    if (world > 0) { if (wg::plan_shard(F, K, world, &P) != ELPH_OK) P = wg::WgPlan(); }
+    else P = wg::plan_wg(F, K);
+    const bool has = P.usable && wg::find_kernel(P, world > 0 ? wg::SHARD : wg::PLAIN, false) != nullptr;
+    const int v[9] = {P.usable, (int)P.form, P.npl, P.T, P.W, P.G, (int)P.shm, P.resident, has};
+    std::copy(v, v + 9, out);
 }
 
 // The operational knobs of every resident kernel (cg_wg.hip, pcg_wg.hip, slabs.hip, shard.hip), read per call:
@@ -1441,60 +1559,25 @@ int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iter
     *ran = false;
     if (B.params.use_prec) return ELPH_OK;
     if (h->res.cooling()) return ELPH_OK;               // (after a time-out: elph_wg_cooldown_step, run_cg)
-    if (!elph_wg_usable(h, nullptr, nullptr, nullptr, nrhs)) return ELPH_OK;
-    wg::Shape sh;
-    ModelDev m = elph_model_dev(h);
-    if (!wg::pick_shape(h, m, wg_t(), nrhs, &sh)) return ELPH_OK;
-    // Which form is faster for THIS batch: a deterministic rule (never a timing at run time — which form runs decides the last bits of a
-    // solution) from ONE table of measured constants, wg_cost_table above.  fixed_iters > 0 (measurement of this kernel) and
-    // ELPH_WG_ALWAYS=1 skip it.
-    {
-        const char *ea = getenv("ELPH_WG_ALWAYS");
-        if (fixed_iters <= 0 && !(ea && ea[0] == '1')) {
-            const int per_round = 8 * std::max(1, 32 / sh.G);
-            const double rounds = (double)((nrhs + per_round - 1) / per_round);
-            if (rounds * wg::resident_iteration_us(h, sh) > wg::streaming_iteration_us(h, nrhs)) return ELPH_OK;
-        }
-    }
-    const size_t HS = (size_t)sh.npl * WAVE;
-    const size_t n_slots = 2 * (size_t)nrhs * wg::SLOTS_PER_RHS, n_bnd = (sh.G > 1) ? 2 * (size_t)nrhs * sh.G * 2 * HS * 2 : 0;      // (x 2: by the parity of the iteration)
+    const wg::WgPlan P = wg::plan_wg(wg::wg_facts(h), wg::wg_knobs(nrhs, fixed_iters));
+    if (!P.resident) return ELPH_OK;
+    const ModelDev m = elph_model_dev(h);
+    const size_t HS = (size_t)P.npl * WAVE;
+    const size_t n_slots = 2 * (size_t)nrhs * wg::SLOTS_PER_RHS, n_bnd = (P.G > 1) ? 2 * (size_t)nrhs * P.G * 2 * HS * 2 : 0;      // (x 2: by the parity of the iteration)
     // (2 s: a team at the dispatch frontier of an oversubscribed grid waits for whole solves of the resident ones — tens of ms for a
     //  batch of hundreds of right-hand sides; a measurement launch of thousands of fixed iterations gets its own duration on top)
     wg::WgCtl R;
     RC(elph_wg_ctl(h, n_slots, n_bnd, elph_wg_tag_span(B.params, fixed_iters), elph_wg_timeout_ms(2000) + (fixed_iters > 0 ? fixed_iters / 10 : 0),
                    WG_TAGS_RUNNING, &R));
     R.bnd = R.slots + n_slots;
-    R.G = sh.G; R.W = sh.W;
+    R.G = P.G; R.W = P.W;
     R.fixed_iters = fixed_iters;
     R.x0_zero = x0_zero ? 1 : 0;           // (x0 = 0 known: the 4-slice DPP shape has an instantiation that does not read it)
     if (x0_save)                // the caller's initial guess survives for the fallback (run_cg: in d_zp, unused by an un-preconditioned solve)
         HIPCHK(hipMemcpyAsync(x0_save, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    const dim3 grid((unsigned)(8 * ((nrhs + 7) / 8) * sh.G));      // one solve per workgroup: every right-hand side has its team in the grid
-    hipError_t e = hipSuccess;
-    if (sh.hg) {
-        switch (sh.npl) {
-            case 2: e = (sh.T == 2) ? wg::launch_k<2, 2, false, true, 6>(h, sh, grid, B, m, R) : wg::launch_k<2, 1, false, true, 6>(h, sh, grid, B, m, R); break;
-            case 4: e = (sh.T == 2) ? wg::launch_k<4, 2, false, true, 6>(h, sh, grid, B, m, R) : wg::launch_k<4, 1, false, true, 6>(h, sh, grid, B, m, R); break;
-            default: e = (sh.T == 2) ? wg::launch_k<8, 2, false, true, 6>(h, sh, grid, B, m, R) : wg::launch_k<8, 1, false, true, 6>(h, sh, grid, B, m, R); break;
-        }
-    } else if (sh.gr && sh.tg) {
-        e = (sh.T == 4) ? wg::launch_k<4, 4, false, true, 7>(h, sh, grid, B, m, R)
-          : (sh.T == 2) ? wg::launch_k<4, 2, false, true, 7>(h, sh, grid, B, m, R) : wg::launch_k<4, 1, false, true, 7>(h, sh, grid, B, m, R);
-    } else if (sh.gr) {
-        e = (sh.T == 4) ? wg::launch_k<4, 4, false, true, 5>(h, sh, grid, B, m, R)
-          : (sh.T == 2) ? wg::launch_k<4, 2, false, true, 5>(h, sh, grid, B, m, R) : wg::launch_k<4, 1, false, true, 5>(h, sh, grid, B, m, R);
-    } else if (sh.hc) {
-        e = (sh.T == 3) ? wg::launch_k<wg::HC_NPL, 3, false, true, 2>(h, sh, grid, B, m, R)
-          : (sh.T == 2) ? wg::launch_k<wg::HC_NPL, 2, false, true, 2>(h, sh, grid, B, m, R) : wg::launch_k<wg::HC_NPL, 1, false, true, 2>(h, sh, grid, B, m, R);
-    } else switch (h->npl) {
-        case 1: e = wg::launch_npl<1>(h, sh, grid, B, m, R); break;
-        case 2: e = wg::launch_npl<2>(h, sh, grid, B, m, R); break;
-        case 3: e = wg::launch_npl<3>(h, sh, grid, B, m, R); break;
-        case 4: e = wg::launch_npl<4>(h, sh, grid, B, m, R); break;
-        default: e = wg::launch_npl<5>(h, sh, grid, B, m, R); break;
-    }
-    if (e != hipSuccess) { elph_set_error("launch k_cg_wg failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    h->res.launched(sh.T, sh.W, sh.G);
+    const dim3 grid((unsigned)(8 * ((nrhs + 7) / 8) * P.G));       // one solve per workgroup: every right-hand side has its team in the grid
+    RC(wg::launch(P, wg::PLAIN, x0_zero, grid, h->stream, B, m, R));
+    h->res.launched(P.T, P.W, P.G);
     *ran = true;
     return ELPH_OK;
 }
@@ -1517,118 +1600,66 @@ extern "C" int elph_debug_wg_stamps(unsigned long long *out16) {
 #endif
 
 // One rank's launch of a solve over several GPUs (shard.hip holds the mailbox and calls this).  x0 = 0, b in B.r and B.p.
-// one rank's launch arguments of a sharded solve: form and team shape of its slab, control block (zeroed), tags
-static int shard_rank_setup(elph_handle_s *h, long long fixed_iters, const ElphShardCtl &Sh, ModelDev &m, wg::Shape &sh,
-                            wg::WgCtl &R) {
+// one rank's launch arguments of a sharded solve: the plan of its slab (wg::plan_shard), control block (zeroed), tags
+static int shard_rank_setup(elph_handle_s *h, long long fixed_iters, const ElphShardCtl &Sh, ModelDev &m, wg::WgPlan &P, wg::WgCtl &R) {
     m = elph_model_dev(h);
-    // a slab whose rows the caller closed into a ring (a periodic rectangle in the reference's colouring: sharded.py, ring=True) runs a
-    // register-exchange form — the own rows of z = M^T M p do not see the ring bond (it lies beyond the ghost rows' dependency closure)
-    // (measured, profiles/r04/shard_ring_grid_forms_ab.log: the GRID form pays from three sites per lane of the lane program — a
-    //  slab of up to 128 sites is two LDS values per lane and colour, cheaper than four registers on half the lanes: config C over 4 / 8
-    //  ranks 5.3 / 6.0 us in the lane program against 6.5 / 7.2; the HGRID form with 8 registers per lane spills in the shard's
-    //  kernel: config D on one rank 16.6 against 9.6 us)
-    const bool gr = wg::gr_form(h, m, true) && h->npl >= 3;
-    int hgn = gr ? 0 : wg::hg_form(h, m, true);
-    if (hgn == 8) hgn = 0;
-    if (!gr && !hgn && (!h->fast_capable || h->lp_mc != 4 || h->npl > 5)) {
-        elph_set_error("sharded solve: the slab needs a 4-colour lane program and <= 320 sites (N = %lld)", (long long)h->N);
-        return ELPH_E_UNSUPPORTED;
-    }
-    {   // one slice per wave on every rank (slab sizes differ between ranks; the team shape must not): elph_shard_shape
-        int W = 0, G = 0;
-        const int rc = elph_shard_shape(h->L, Sh.P, &W, &G, nullptr, nullptr);
-        if (rc) return rc;
-        sh.npl = gr ? 4 : (hgn ? hgn : h->npl);
-        const size_t SL = (size_t)sh.npl * WAVE + 2 * WAVE, HS = (size_t)sh.npl * WAVE;
-        sh.T = 1; sh.W = W; sh.G = G; sh.sq = false; sh.hc = false; sh.s8 = false; sh.gr = gr; sh.hg = hgn > 0;
-        sh.shm = ((size_t)W * ((gr || hgn) ? 0 : 2) * SL + 2 * (size_t)W * HS + 48 + 4 * HS) * sizeof(double);     // + partials, totals, rhalo[2][HS], zhalo[2][HS]
-    }
-    const size_t HS = (size_t)sh.npl * WAVE;
-    const size_t n_slots = 2 * wg::SLOTS_PER_RHS, n_bnd = (sh.G > 1) ? 2 * (size_t)sh.G * 2 * HS * 2 : 0;
+    RC(wg::plan_shard(wg::wg_facts(h), wg::wg_knobs(1, fixed_iters), Sh.P, &P));
+    const size_t HS = (size_t)P.npl * WAVE;
+    const size_t n_slots = 2 * wg::SLOTS_PER_RHS, n_bnd = (P.G > 1) ? 2 * (size_t)P.G * 2 * HS * 2 : 0;
     // (the records of a sharded solve live in the ranks' mailboxes, one numbering for all: this rank's block — the boundary granules of
     //  its workgroups — is zeroed and its tags restart at 2 with every launch.  A sharded solve has NO streaming fallback behind it — a
     //  time-out is a failed solve — and its ranks start with whatever skew the host's barrier, first-launch code loading and time-slicing
     //  leave: the long bound, elph_shard_timeout_ms)
     RC(elph_wg_ctl(h, n_slots, n_bnd, 0, elph_shard_timeout_ms(), WG_TAGS_RESTART, &R));
     R.bnd = R.slots + n_slots;
-    R.G = sh.G; R.W = sh.W;
+    R.G = P.G; R.W = P.W;
     R.fixed_iters = fixed_iters;
     return ELPH_OK;
 }
 
 int elph_wg_cg_shard(elph_handle_s *h, const CgBufs &B, long long fixed_iters, const ElphShardCtl &Sh, int *G_out) {
     ModelDev m;
-    wg::Shape sh;
+    wg::WgPlan P;
     wg::WgCtl R;
-    const int rcs = shard_rank_setup(h, fixed_iters, Sh, m, sh, R);
-    if (rcs) return rcs;
-    const dim3 grid((unsigned)sh.G);                       // one right-hand side: its G workgroups, round-robin over the XCDs
-    hipError_t e = hipSuccess;
-    if (sh.gr || sh.hg) e = wg::launch_shard_grid(h, sh, grid, B, m, R, Sh);
-    else switch (h->npl) {
-        case 1: e = wg::launch_shard_npl<1>(h, sh, grid, B, m, R, Sh); break;
-        case 2: e = wg::launch_shard_npl<2>(h, sh, grid, B, m, R, Sh); break;
-        case 3: e = wg::launch_shard_npl<3>(h, sh, grid, B, m, R, Sh); break;
-        case 4: e = wg::launch_shard_npl<4>(h, sh, grid, B, m, R, Sh); break;
-        default: e = wg::launch_shard_npl<5>(h, sh, grid, B, m, R, Sh); break;
-    }
-    if (e != hipSuccess) { elph_set_error("launch k_cg_wg (shard) failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    h->res.launched(sh.T, sh.W, sh.G);
-    if (G_out) *G_out = sh.G;
+    RC(shard_rank_setup(h, fixed_iters, Sh, m, P, R));
+    const dim3 grid((unsigned)P.G);                        // one right-hand side: its G workgroups, round-robin over the XCDs
+    RC(wg::launch(P, wg::SHARD, false, grid, h->stream, B, m, R, Sh));
+    h->res.launched(P.T, P.W, P.G);
+    if (G_out) *G_out = P.G;
     return ELPH_OK;
 }
 
 // ALL RANKS OF A SHARDED SOLVE WHOSE SLABS LIVE ON ONE DEVICE, IN ONE LAUNCH (slabs.hip): the same kernel, rank q's workgroups = blocks
 // q G .. q G + G - 1, launch arguments from d_args (device memory, P x elph_wg_rank_args_bytes()).  Every slab must take the lane-program
-// form with the same sites per lane and the same team shape; all P G workgroups must be resident at once (they wait for each other).
+// or the GRID form with the same sites per lane and the same team shape; all P G workgroups must be resident at once (they wait for each other).
 size_t elph_wg_rank_args_bytes() { return sizeof(wg::WgRankArgs); }
 
 int elph_wg_cg_ranks(elph_handle_s *const *hs, int P, const CgBufs *Bs, long long fixed_iters, const ElphShardCtl *ctls, void *h_args,
                      void *d_args, hipStream_t stream, long long timeout_ms, int *G_out) {
     if (P < 1 || P > 2 * ELPH_SHARD_MAXRANKS) { elph_set_error("bad rank count %d", P); return ELPH_E_ARG; }      // (up to two sets of slabs)
     wg::WgRankArgs *A = static_cast<wg::WgRankArgs *>(h_args);          // (pinned, owned by the caller: the copy below is asynchronous)
-    wg::Shape sh0;
-    bool uni = true;
+    wg::WgPlan P0;
     for (int q = 0; q < P; ++q) {
         if (hs[q]->stream != stream) { elph_set_error("slab %d runs on another stream", q); return ELPH_E_STATE; }
-        wg::Shape sh;
-        const int rc = shard_rank_setup(hs[q], fixed_iters, ctls[q], A[(size_t)q].m, sh, A[(size_t)q].R);
-        if (rc) return rc;
-        if (sh.hg || hs[q]->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("slabs on one device: lane-program or GRID form, site phonons"); return ELPH_E_UNSUPPORTED; }
-        if (q == 0) sh0 = sh;
-        else if (sh.npl != sh0.npl || sh.W != sh0.W || sh.G != sh0.G || sh.shm != sh0.shm || sh.gr != sh0.gr) { elph_set_error("slabs on one device: slab %d has another shape", q); return ELPH_E_UNSUPPORTED; }
-        uni = uni && A[(size_t)q].m.uniform;
+        wg::WgPlan Pq;
+        RC(shard_rank_setup(hs[q], fixed_iters, ctls[q], A[(size_t)q].m, Pq, A[(size_t)q].R));
+        if (Pq.form == wg::HGRID || hs[q]->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("slabs on one device: lane-program or GRID form, site phonons"); return ELPH_E_UNSUPPORTED; }
+        if (q == 0) P0 = Pq;
+        else if (Pq.npl != P0.npl || Pq.W != P0.W || Pq.G != P0.G || Pq.shm != P0.shm || Pq.form != P0.form) { elph_set_error("slabs on one device: slab %d has another shape", q); return ELPH_E_UNSUPPORTED; }
+        P0.uniform = P0.uniform && Pq.uniform;      // (one kernel for all slabs: uniform hopping only if every slab has it)
         if (timeout_ms > 0) A[(size_t)q].R.timeout_ticks = timeout_ms * 100000LL;      // (slabs of one device: a streaming fallback exists, the short bound)
         A[(size_t)q].B = Bs[q];
         A[(size_t)q].Sh = ctls[q];
     }
-    if ((long long)P * sh0.G > elph_i_resident_wg_limit(hs[0])) { elph_set_error("slabs on one device: %d x %d workgroups cannot all be resident", P, sh0.G); return ELPH_E_UNSUPPORTED; }
+    if ((long long)P * P0.G > elph_i_resident_wg_limit(hs[0])) { elph_set_error("slabs on one device: %d x %d workgroups cannot all be resident", P, P0.G); return ELPH_E_UNSUPPORTED; }
     HIPCHK(hipMemcpyAsync(d_args, A, (size_t)P * sizeof(wg::WgRankArgs), hipMemcpyHostToDevice, stream));
     wg::WgCtl R0 = A[0].R;
     R0.ranks = d_args;
     // (tests, ELPH_SLABS_TEST_TIMEOUT=2: the last rank's workgroups are NOT launched — the others wait for them until their bound and give up)
     const int drop = (elph_slabs_test_timeout() == '2') ? 1 : 0;
-    const dim3 grid((unsigned)((P - drop) * sh0.G)), block((unsigned)(sh0.W * WAVE));
-    hipError_t e = hipSuccess;
-#define RANKS_LAUNCH(NPLV, UNIV) do {                                                                                                  \
-        auto kfn = wg::k_cg_wg<NPLV, 1, false, UNIV, 0, true, false, true>;                                                            \
-        e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh0.shm);                          \
-        if (e == hipSuccess) { hipLaunchKernelGGL(kfn, grid, block, sh0.shm, stream, Bs[0], A[0].m, R0, ctls[0]); e = hipGetLastError(); } \
-    } while (0)
-#define RANKS_CASE(NPLV) case NPLV: if (uni) RANKS_LAUNCH(NPLV, true); else RANKS_LAUNCH(NPLV, false); break;
-    if (sh0.gr) {      // slabs closed into rings: periodic rectangles in the reference's colouring, the GRID form (2 x 2 patches per lane)
-        auto kfn = wg::k_cg_wg<4, 1, false, true, 5, true, false, true>;
-        e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh0.shm);
-        if (e == hipSuccess) { hipLaunchKernelGGL(kfn, grid, block, sh0.shm, stream, Bs[0], A[0].m, R0, ctls[0]); e = hipGetLastError(); }
-    } else
-    switch (sh0.npl) {
-        RANKS_CASE(1) RANKS_CASE(2) RANKS_CASE(3) RANKS_CASE(4)
-        default: if (uni) RANKS_LAUNCH(5, true); else RANKS_LAUNCH(5, false); break;
-    }
-#undef RANKS_CASE
-#undef RANKS_LAUNCH
-    if (e != hipSuccess) { elph_set_error("launch k_cg_wg (ranks) failed: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-    for (int q = 0; q < P; ++q) hs[q]->res.launched(1, sh0.W, sh0.G);
-    if (G_out) *G_out = sh0.G;
+    const dim3 grid((unsigned)((P - drop) * P0.G));
+    RC(wg::launch(P0, wg::RANKS, false, grid, stream, Bs[0], A[0].m, R0, ctls[0]));
+    for (int q = 0; q < P; ++q) hs[q]->res.launched(1, P0.W, P0.G);
+    if (G_out) *G_out = P0.G;
     return ELPH_OK;
 }

@@ -77,7 +77,8 @@ void elph_lp_pack(const elph_handle_s *h, const double *per_bond, double *out, d
 
 static LatticeShape elph_recognise_lattice(const elph_handle_s *h);
 
-static int build_lane_program(elph_handle_s *h) {
+// the host half: colours per program, the (i, j) words of every lane, whether the lane-program kernels apply, the recognised lattice
+static void plan_lane_program(elph_handle_s *h) {
     h->lp_mc = (h->ncol <= 4) ? 4 : 6;      // kernels exist for 4-colour (square, honeycomb, chain) and 6-colour (triangular) programs
     const int PP = (h->npl + 1) / 2, NE = h->lp_mc * PP;
     h->lp_ne = NE;
@@ -105,12 +106,17 @@ static int build_lane_program(elph_handle_s *h) {
         }
     }
     h->fast_capable = h->fast;
+    h->shape = elph_recognise_lattice(h);
+}
+
+static int build_lane_program(elph_handle_s *h) {
+    plan_lane_program(h);
+    const int NE = h->lp_ne;
     RC(dev_alloc(&h->d_lp_ij, (size_t)NE * ELPH_WAVE));
     HIPCHK(hipMemcpy(h->d_lp_ij, h->h_lp_ij.data(), sizeof(unsigned) * NE * ELPH_WAVE, hipMemcpyHostToDevice));
     const size_t ntau = (h->kind == ELPH_MODEL_SSH) ? (size_t)h->L : 1;
     RC(dev_alloc(&h->d_lp_c, ntau * NE * ELPH_WAVE));
     RC(dev_alloc(&h->d_lp_s, ntau * NE * ELPH_WAVE));
-    h->shape = elph_recognise_lattice(h);
     if (h->shape.sq_L() > 0) {
         RC(dev_alloc(&h->d_sq_bond, (size_t)4 * h->N));
         HIPCHK(hipMemcpy(h->d_sq_bond, h->shape.bond.data(), sizeof(int) * 4 * h->N, hipMemcpyHostToDevice));
@@ -1986,6 +1992,24 @@ extern "C" int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds
     const int v[] = {sq ? sh.LX : 0, sq ? sh.LY : 0, sh.dpp(), hc ? sh.LX : 0, hc ? sh.LY : 0, sh.hc12(), sh.patch_kind(), sh.patch() ? sh.LX : 0, sh.PX, sh.PY,
                      std::max(sh.NW, 1), sh.GX, sh.GY, sh.hgrid_regs(), sh.hop_uniform, sh.sq_L() > 0 ? 1 : sh.patch_kind() == LatticeShape::SQUARE ? 2 : 0};
     std::copy(std::begin(v), std::end(v), out);
+    return ELPH_OK;
+}
+
+// the plan of the resident CG launch that elph_create's handle would make for this bond table and time axis, on a host-only handle (no
+// device): the slots of _lib.WG_PLAN_SLOTS
+extern "C" int elph_bench_wg_plan(int kind, int64_t nsites, int64_t ltau, int64_t nbonds, const int64_t *neighbor_table, const double *cosht,
+                                  const double *sinht, int nrhs, int world, int *out) {
+    if (!out || (kind != ELPH_MODEL_HOLSTEIN && kind != ELPH_MODEL_SSH) || nsites < 1 || nsites > ELPH_MAX_SITES || ltau < 1 || nbonds < 0 || nrhs < 1 || world < 0) {
+        elph_set_error("bad argument"); return ELPH_E_ARG;
+    }
+    RC(check_bond_table(kind, nsites, nbonds, neighbor_table, cosht, sinht));
+    elph_handle_s h;
+    h.kind = kind; h.N = nsites; h.L = ltau; h.nb = nbonds; h.ndim = nsites * ltau;
+    h.npl = (int)((nsites + ELPH_WAVE - 1) / ELPH_WAVE);
+    colour_bonds(&h, neighbor_table);
+    if (kind == ELPH_MODEL_HOLSTEIN) { h.h_c.assign(cosht, cosht + nbonds); h.h_s.assign(sinht, sinht + nbonds); }
+    plan_lane_program(&h);
+    elph_i_wg_plan_probe(&h, nrhs, world, out);
     return ELPH_OK;
 }
 

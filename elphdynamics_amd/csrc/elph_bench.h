@@ -52,6 +52,14 @@ int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, int *nw, int 
 int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht, const double *sinht,
                              int *out);
 
+/* The plan of the workgroup-resident CG launch (cg_wg.hip: WgPlan) that a handle created from this bond table at Ltau = ltau makes for nrhs
+ * right-hand sides (needs no device; reads the ELPH_*WG* switches as a solve does).  world = 0: the un-sharded solve; world > 0: one rank of a
+ * sharded solve over that many ranks (the table is the rank's slab).  out[9] = usable; the form (0 lane program, 1 16 x 16 DPP, 2 12 x 12
+ * honeycomb DPP, 4 8 x 8 DPP, 5 GRID, 6 HGRID, 7 triangular GRID); the kernel's sites per lane; T, W, G; bytes of dynamic LDS; whether the cost
+ * rule takes the resident kernel; whether the launch table holds the plan's kernel. */
+int elph_bench_wg_plan(int kind, int64_t nsites, int64_t ltau, int64_t nbonds, const int64_t *neighbor_table, const double *cosht,
+                       const double *sinht, int nrhs, int world, int *out);
+
 /* What setup!(P) plans for nch chains at Ltau = ltau over nsteps successive steps of bounds (kpm_host.cpp: elph_kpm_plan; needs no device).
  * e_bounds: [nsteps][nch][2] (e_min, e_max); uploaded[s] = 1 when step s uploads the tables.  After the last step: active[nch]; lam[nch][4] =
  * lam_lo, lam_hi and the uploaded (lam_avg, lam_mag); the tables order, wsched [nch][Lo2] and coff [nch][Lo2+1]; c0 [nch][Lo2][2] the leading

@@ -570,6 +570,8 @@ void elph_i_slabs_free(elph_handle_s *h);
 
 // ---- workgroup-resident CG (cg_wg.hip): the whole un-preconditioned solve in one launch
 bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs = 1);
+// the launch plan of a handle that need not own a device, as elph_bench_wg_plan reports it (world > 0: one rank of a sharded solve)
+void elph_i_wg_plan_probe(const elph_handle_s *h, int nrhs, int world, int *out);
 // x0_zero: the library zeroed d_x for this solve; x0_save: where the initial guess goes once the launch is decided, for the caller's
 // fallback after a time-out (nullptr: not kept — a measurement launch)
 int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool x0_zero, double *x0_save, bool *ran);
