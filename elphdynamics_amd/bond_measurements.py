@@ -17,14 +17,12 @@ constructor makes no library call; the device side (elph_bond_create) is made by
 Arrays as in measurements.py: `position` and `momentum` complex128 (L0, L1, L2, L3, n_p) in Fortran order, `pairs` int (2, n_p) of 1-based
 bond-definition indices: pairs[0, p] is the bond at the origin (n'' of the reference), pairs[1, p] the displaced one (n').
 
-Scope.  CurrentCurrent with measure = true is refused here with UnsupportedMeasurement (the message is from before the question it
-names was settled): current_measurements.py measures it, in a container of its own beside this one, mirroring the reference's Holstein
-method as it executes (it scales its fields by the hopping inside `for tau in L_tau`, which visits the last time slice alone);
-current_measurements.split_info hands this constructor the table without that entry.  Refused too are a request on a model without bond definitions, the SSH model (ssh_bond_measurements.py measures its BondBond, CurrentCurrent and BondPairGreens)
-and several chains resident (chain_bond_measurements.py measures every resident chain at once); sharded and slab handles are refused by
-the library.
+Scope: the table in measurements.py's docstring has what each of the nine modules measures and refuses, this one included.  The message
+that refuses CurrentCurrent here is from before the question it names was settled: current_measurements.py measures it, mirroring the
+reference's Holstein method as it executes.
 """
-from ._lib import P_dbl, check
+from ._chain_unit import pack_bond_definitions, position_pointers, require_device, reset_device
+from ._lib import check
 from .measurements import (UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _i32, _ip, _process_group,
                            _refuse_model, _request_arrays, _requested, _susc_group, _write_groups, _zero_groups, simpson)  # noqa: F401
 
@@ -78,16 +76,20 @@ def initialize_bond_folders_(container):
     _group_folders(container.datafolder, container.intersite_corr, container.intersite_susc, "bond1", "bond2")
 
 
+def _create_args(container, model):
+    """The arguments of elph_bond_create after the handle and of elph_bond_chains_create after nchains: the bond definitions and the
+    request (nothing of the model).  Second value: the arrays the pointers refer to, to be kept alive across the call."""
+    arrays = pack_bond_definitions(container.bond_definitions) + _request_arrays(container.intersite_corr, BOND_CORR)
+    return [len(container.bond_definitions), *map(_ip, arrays)], arrays
+
+
 def _ensure_device(container, model, Gr):
     if container._device_of is model:
         return
     _refuse_model(model, SUBJECT)
     _check_estimator(container, model, Gr)
-    defs = container.bond_definitions
-    o1, o2 = _i32([d[0] for d in defs] or [0]), _i32([d[1] for d in defs] or [0])
-    v = _i32([k for d in defs for k in d[2]] or [0, 0, 0])
-    request = _request_arrays(container.intersite_corr, BOND_CORR)
-    check(model._lib.elph_bond_create(model._h, len(defs), _ip(o1), _ip(o2), _ip(v), *map(_ip, request)))
+    args, keep = _create_args(container, model)
+    check(model._lib.elph_bond_create(model._h, *args))
     container._device_of = model
 
 
@@ -104,11 +106,8 @@ def accumulate_bonds_(container, model, Gr):
 
 def fetch_bonds_(container, model):
     """The device's un-normalised sums into the container's position arrays; the momentum arrays are not touched."""
-    if container._device_of is not model:
-        raise RuntimeError("no bond correlation has been measured on this model yet")
-    corr = container.intersite_corr
-    ptrs = [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in BOND_CORR]
-    check(model._lib.elph_bond_fetch(model._h, *ptrs))
+    require_device(container, model, "no bond correlation")
+    check(model._lib.elph_bond_fetch(model._h, *position_pointers(container.intersite_corr, BOND_CORR)))
 
 
 def process_bond_measurements_(container, bin_size, model):
@@ -131,5 +130,4 @@ def reset_bond_measurements_(container, model):
     """reset_measurements!(container, model) (:698-758) for the inter-site correlations: the container's arrays and the device's
     accumulators to zero."""
     _zero_groups(container.intersite_corr, container.intersite_susc)
-    if container._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_bond_reset(model._h))
+    reset_device(container, model, "elph_bond_reset")

@@ -22,37 +22,25 @@ A chain's folder holds exactly the files of a single-configuration run.
 The device side is shaped by the estimator and dropped by the library when a new EstimateGreensFunction is made on the model (with the
 sums it held): the next accumulate_ with the new estimator makes it again, with the mu given then (or model.mu).
 
-Scope: what measurements.py measures for one configuration.  Refused with UnsupportedMeasurement naming the request: the SSH model,
-BondBond, CurrentCurrent, BondPairGreens with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them for every chain, in a container of its own) — the SSH model over chains is
-ssh_chain_measurements.py's (its bond correlations over chains ssh_chain_bond_measurements.py's); BondBond, BondPairGreens and BondPairSusc of the chains are chain_bond_measurements.py's, whose container is used beside
-this one on the same model and estimator, in either order.  measurements.py itself keeps refusing resident chains.
+Scope: what measurements.py measures for one configuration, and its refusals but the resident chains; the table in measurements.py's
+docstring has the module for everything else.  The functions below are the on-site family of _chain_unit.py with this module's record.
 """
-import numpy as np
-
-from . import greens as _greens
+from . import _chain_unit as _cu
 from . import measurements as _ms
-from ._lib import check, dptr, iptr
 
 UnsupportedMeasurement = _ms.UnsupportedMeasurement
+FAMILY = _cu.OnsiteFamily(single=_ms, refuse=lambda model: _ms._refuse_ssh(model, "chain measurements"), check_refuses=False,
+                          prefix="elph_meas_chains_")
 
 
-class ChainMeasurementsContainer:
-    def __init__(self, chains, n_rand_vecs):
-        self.chains = chains                 # one MeasurementsContainer per chain
-        self.nchains = len(chains)
-        self.n_rand_vecs = n_rand_vecs       # per chain
-        self._device_of = None               # the model whose handle holds the device side ...
-        self._device_est = None              # ... and the estimator it was shaped by: a newer one on the model has dropped it
+class ChainMeasurementsContainer(_cu.ChainContainer):
+    """chains: one MeasurementsContainer per chain."""
 
 
 def initialize_chain_measurements_container(model, info, datafolders):
     """One container per resident chain of `model` for the request `info`; datafolders: one folder per chain."""
-    _ms._refuse_ssh(model, "chain measurements")
-    nchains = int(getattr(model, "_nchains", 1))
-    datafolders = list(datafolders)
-    if len(datafolders) != nchains:
-        raise ValueError("%d data folders for the %d chains resident in the model" % (len(datafolders), nchains))
-    chains = [_ms._new_container(model, info, folder) for folder in datafolders]
+    FAMILY.refuse(model)
+    chains = [_ms._new_container(model, info, folder) for folder in _cu.chain_folders(model, datafolders)]
     return ChainMeasurementsContainer(chains, chains[0].n_rand_vecs)
 
 
@@ -61,68 +49,22 @@ def initialize_measurement_folders_(cm):
         _ms.initialize_measurement_folders_(c)
 
 
-def _chain_rows(a, cm, width, what):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.shape != (cm.nchains, width):
-        raise ValueError("%s has shape %s, not (nchains, %s) = (%d, %d)" % (what, a.shape, "Ndof" if what == "X" else "Nsites", cm.nchains, width))
-    return a
-
-
-def _check(cm, model, Gr, X, mu):
-    """Everything that can be wrong on the host, before any library call."""
-    assert Gr.model is model
-    if int(getattr(model, "_nchains", 1)) != cm.nchains:
-        raise ValueError("the container was made for %d chains, %d are resident in the model" % (cm.nchains, getattr(model, "_nchains", 1)))
-    if Gr.nv != cm.n_rand_vecs * cm.nchains:
-        raise ValueError("the estimator holds %d vectors, the container normalises for num_random_vectors = %d for each of %d chains"
-                         % (Gr.nv, cm.n_rand_vecs, cm.nchains))
-    X = _chain_rows(X, cm, model.Ndof, "X")
-    if mu is not None:
-        mu = _chain_rows(mu, cm, model.Nsites, "mu")
-    return X, mu
-
-
-def _ensure_device(cm, model, Gr, mu):
-    if cm._device_of is model and cm._device_est is Gr:
-        if mu is not None:              # the tuners moved it since: the device's rows follow (a small copy), the sums so far are kept
-            check(model._lib.elph_meas_chains_set_mu(model._h, dptr(mu)))
-        return
-    sites, t = _ms.bond_arrays(model)
-    request = _ms._request_arrays(cm.chains[0].onsite_corr, _ms.ONSITE_CORR)
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-    mu = f64(np.tile(model.mu, (cm.nchains, 1))) if mu is None else mu
-    check(model._lib.elph_meas_chains_create(model._h, cm.nchains, dptr(f64(model.omega)), dptr(f64(model.omega4)), dptr(f64(model.lam)),
-                                             dptr(mu), float(model.dtau), sites.shape[0], int(model.nbonds), iptr(sites) if sites.size else None,
-                                             dptr(t) if t.size else None, *map(_ms._ip, request)))
-    cm._device_of, cm._device_est = model, Gr
-
-
 def accumulate_(cm, model, Gr, X, mu=None):
     """make_measurements! without its update! for every chain: each pair v1 < v2 of a chain's vectors is set up and folded into the
     device's accumulators for all chains at once; nothing comes back to the host."""
-    X, mu = _check(cm, model, Gr, X, mu)
-    _ensure_device(cm, model, Gr, mu)
-    check(model._lib.elph_meas_chains_accumulate(model._h, dptr(X)))
+    _cu.onsite_accumulate(FAMILY, cm, model, Gr, X, mu)
 
 
 def make_measurements_(cm, model, Gr, X, nmeas, P=None, R=None, rng=None, mu=None):
     """make_measurements!(container, model, Gr, nmeas, preconditioner) (:545-566) for every chain: one batched solve for all chains'
     vectors (greens.update_, which sets the preconditioner up per chain), then accumulate_.  Returns update_'s (iters, residual_error,
     flag), entry v * nchains + c for vector v of chain c."""
-    X, mu = _check(cm, model, Gr, X, mu)
-    out = _greens.update_(Gr, model, P, rng=rng, R=R)
-    accumulate_(cm, model, Gr, X, mu)
-    return out
+    return _cu.onsite_make(FAMILY, cm, model, Gr, X, P, R, rng, mu)
 
 
 def fetch_(cm, model):
     """The device's un-normalised sums into every chain's container (position arrays and scalars)."""
-    if cm._device_of is not model:
-        raise RuntimeError("nothing has been measured on this model yet")
-    for chain, c in enumerate(cm.chains):
-        scal, ptrs = _ms._fetch_buffers(c)
-        check(model._lib.elph_meas_chains_fetch(model._h, chain, dptr(scal), *ptrs))
-        _ms._store_scalars(c, scal)
+    _cu.onsite_fetch(FAMILY, cm, model)
 
 
 def process_measurements_(cm, bin_size, model):
@@ -140,7 +82,4 @@ def write_measurements_(cm, model, bin):
 
 def reset_measurements_(cm, model):
     """reset_measurements! (:698-758): every chain's arrays and the device's accumulators to zero."""
-    for c in cm.chains:
-        _ms._zero_container(c)
-    if cm._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_meas_chains_reset(model._h))
+    _cu.onsite_reset(FAMILY, cm, model)

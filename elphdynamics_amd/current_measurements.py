@@ -28,16 +28,17 @@ and nothing setup_ makes: Gr.n1 and Gr.n2 are left alone.  The estimator serves 
 of chain c at index v * nchains + c; a bin is normalised by bin_size * binomial(n_rand_vecs, 2) with the vectors PER CHAIN.
 CurrentCurrent has no susceptibility (:157-162).
 
-Refused with UnsupportedMeasurement: the SSH model (ssh_bond_measurements.py and ssh_chain_bond_measurements.py measure its
-CurrentCurrent), a request on a model without bond definitions.  Sharded and slab handles, and a model whose Nbonds is not
-n_def * ncells (the reference's reshape of t fails), are refused by the library.
+Scope: the table in measurements.py's docstring has what each of the nine modules measures and refuses, this one included; the container,
+its host checks and its device-side guards are _chain_unit.py's.  Refused by the library besides sharded and slab handles: a model whose
+Nbonds is not n_def * ncells (the reference's reshape of t fails).
 """
 import os
 
 import numpy as np
 
-from ._lib import P_dbl, check, dptr
-from .measurements import (UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _i32, _ip, _process_group,
+from . import _chain_unit as _cu
+from ._lib import check, dptr
+from .measurements import (UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _ip, _process_group,
                            _refuse_ssh, _request_arrays, _write_groups, _zero_groups)
 
 CURRENT_CORR = ("CurrentCurrent",)
@@ -53,14 +54,12 @@ class CurrentChain:
         self.n_rand_vecs = n_rand_vecs
 
 
-class CurrentContainer:
+class CurrentContainer(_cu.ChainContainer):
+    """chains: one CurrentChain per chain."""
+
     def __init__(self, chains, bond_definitions, n_rand_vecs):
-        self.chains = chains                 # one CurrentChain per chain
-        self.nchains = len(chains)
+        super().__init__(chains, n_rand_vecs)
         self.bond_definitions = bond_definitions
-        self.n_rand_vecs = n_rand_vecs       # per chain
-        self._device_of = None               # the model whose handle holds the device side ...
-        self._device_est = None              # ... and the estimator it was shaped by: a newer one on the model has dropped it
 
 
 def split_info(info):
@@ -79,10 +78,7 @@ def initialize_current_container(model, info, datafolders, bond_definitions=None
     """CurrentCurrent's part of initialize_measurements_container(holstein, info, datafolder) (:157-162) for every resident chain."""
     _refuse_ssh(model, SUBJECT)
     info = info or {}
-    nchains = int(getattr(model, "_nchains", 1))
-    datafolders = [datafolders] if isinstance(datafolders, (str, os.PathLike)) else list(datafolders)
-    if len(datafolders) != nchains:
-        raise ValueError("%d data folders for the %d chains resident in the model" % (len(datafolders), nchains))
+    datafolders = _cu.chain_folders(model, datafolders)
     defs = bond_definitions if bond_definitions is not None else getattr(model, "bond_definitions", [])
     defs = [(int(o1), int(o2), tuple(int(k) for k in v)) for o1, o2, v in defs]
     requested = (info.get("CurrentCurrent") or {}).get("measure", False) is True
@@ -104,23 +100,19 @@ def initialize_current_folders_(c):
 def _check(c, model, Gr):
     """Everything that can be wrong on the host, before any library call."""
     _refuse_ssh(model, SUBJECT)
-    if int(getattr(model, "_nchains", 1)) != c.nchains:
-        raise ValueError("the container was made for %d chains, %d are resident in the model" % (c.nchains, getattr(model, "_nchains", 1)))
+    _cu.check_chains(c, model)
     if c.nchains == 1:
         _check_estimator(c, model, Gr)
     else:
         assert Gr.model is model
-        if Gr.nv != c.n_rand_vecs * c.nchains:
-            raise ValueError("the estimator holds %d vectors, the container normalises for num_random_vectors = %d for each of %d chains"
-                             % (Gr.nv, c.n_rand_vecs, c.nchains))
+        _cu.check_vectors(c, Gr)
 
 
 def _ensure_device(c, model, Gr):
-    if c._device_of is model and c._device_est is Gr:
+    if _cu.device_current(c, model, Gr):
         return
     defs = c.bond_definitions
-    o1, o2 = _i32([d[0] for d in defs] or [0]), _i32([d[1] for d in defs] or [0])
-    v = _i32([k for d in defs for k in d[2]] or [0, 0, 0])
+    o1, o2, v = _cu.pack_bond_definitions(defs)
     measure, td, npairs, pairs = _request_arrays(c.chains[0].intersite_corr, CURRENT_CORR)
     t = np.ascontiguousarray(model.t, dtype=np.float64)
     check(model._lib.elph_current_create(model._h, c.nchains, len(defs), _ip(o1), _ip(o2), _ip(v), int(model.Nbonds), dptr(t) if t.size else None,
@@ -141,11 +133,9 @@ def accumulate_current_(c, model, Gr):
 
 def fetch_current_(c, model):
     """The device's un-normalised sums into every chain's position array; the momentum arrays are not touched."""
-    if c._device_of is not model:
-        raise RuntimeError("no CurrentCurrent has been measured on this model yet")
+    _cu.require_device(c, model, "no CurrentCurrent")
     for chain, ch in enumerate(c.chains):
-        corr = ch.intersite_corr.get("CurrentCurrent")
-        check(model._lib.elph_current_fetch(model._h, chain, corr.position.ctypes.data_as(P_dbl) if corr is not None else None))
+        check(model._lib.elph_current_fetch(model._h, chain, *_cu.position_pointers(ch.intersite_corr, CURRENT_CORR)))
 
 
 def _process_fetched(c, bin_size, dtau):
@@ -171,5 +161,4 @@ def reset_current_measurements_(c, model):
     """reset_measurements!(container, model) (:698-758) for CurrentCurrent: every chain's arrays and the device's accumulators to zero."""
     for ch in c.chains:
         _zero_groups(ch.intersite_corr)
-    if c._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_current_reset(model._h))
+    _cu.reset_device(c, model, "elph_current_reset")

@@ -17,17 +17,32 @@ Arrays keep the reference's shapes in Fortran order (Julia's memory image): a co
 (L0, L1, L2, L3, n_p) with L0 = Ltau + 1 (time-dependent, tau = beta included) or 1 (equal-time), `pairs` is int (2, n_p), 1-based; a
 susceptibility's are (L1, L2, L3, n_p).
 
-Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
-BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them, in a container of its own: snapshots.split_info splits the
-table), the SSH model, several chains resident in the handle;
-sharded and slab handles are refused by the library.  BondBond, BondPairGreens and BondPairSusc live in a container of their own beside
-this one (bond_measurements.py, csrc/bondcorr.hip), used on the same model and estimator; CurrentCurrent of this model lives in another
-(current_measurements.py, csrc/currcorr.hip: one configuration or resident chains), that of the SSH model in ssh_bond_measurements.py
-(csrc/ssh_bondcorr.hip).  Several chains resident in the handle (a lockstep
-run) are measured by the chain-aware twin of this module, chain_measurements.py (csrc/measure.hip): one container per chain, all
-chains in the same launches; the functions here keep refusing them.  The bond correlations of the chains are
-chain_bond_measurements.py's; the SSH model over chains is measured by ssh_chain_measurements.py (csrc/ssh_measure.hip), its bond
-correlations BondBond, CurrentCurrent and BondPairGreens over chains by ssh_chain_bond_measurements.py (csrc/ssh_bondcorr.hip).
+Who measures what.  Nine modules, one container each, used beside one another on the same model and estimator, in any order.  What a
+module does not measure it refuses with UnsupportedMeasurement naming the request, never skips; sharded and slab handles are refused by
+the library.  "scalars": the global, on-site and inter-site numbers of the three scalar files.  The chain modules measure every chain
+resident in a handle (a lockstep run) in the same launches, one single-configuration container per chain; what they share is written
+once in _chain_unit.py.
+
+    module                          model     configurations  correlations (their susceptibilities)             device unit
+    measurements.py                 Holstein  one             scalars; Greens, DenDen, SpinSpin, PairGreens,    csrc/measure.hip
+                                                              PhononGreens (PairSusc, ChargeSusc, SpinSusc)
+    chain_measurements.py           Holstein  chains          as measurements.py                                csrc/measure.hip
+    bond_measurements.py            Holstein  one             BondBond, BondPairGreens (BondPairSusc)           csrc/bondcorr.hip
+    chain_bond_measurements.py      Holstein  chains          as bond_measurements.py                           csrc/bondcorr.hip
+    current_measurements.py         Holstein  one or chains   CurrentCurrent                                    csrc/currcorr.hip
+    ssh_measurements.py             SSH       one             scalars; Greens, DenDen, SpinSpin, PairGreens     csrc/ssh_measure.hip
+                                                              (PairSusc, ChargeSusc, SpinSusc), PhononGreens
+    ssh_chain_measurements.py       SSH       chains          as ssh_measurements.py                            csrc/ssh_measure.hip
+    ssh_bond_measurements.py        SSH       one             BondBond, CurrentCurrent, BondPairGreens          csrc/ssh_bondcorr.hip
+                                                              (BondPairSusc)
+    ssh_chain_bond_measurements.py  SSH       chains          as ssh_bond_measurements.py                       csrc/ssh_bondcorr.hip
+
+Refused by every module: the other model.  By the one-configuration modules: several chains resident in the handle (model._nchains
+> 1); current_measurements.py takes either.  By the four on-site modules: BondBond, CurrentCurrent, BondPairGreens (and with it
+BondPairSusc) with measure = true, and a [measurements.Snapshots] entry set to true (snapshots.py takes them for one configuration or
+every chain, in a container of its own: snapshots.split_info splits the table).  By bond_measurements.py and
+chain_bond_measurements.py: CurrentCurrent with measure = true (current_measurements.split_info hands them the table without it).  By the
+five bond and current modules: a request on a model without bond definitions.
 
 One thing is not the reference's: the line order inside the global_measurements, onsite_measurements and intersite_measurements files.
 The reference writes them in the iteration order of a Julia Dict, which is unspecified; here it is density, Nsqr, mu / density,
@@ -39,11 +54,13 @@ from math import comb
 import numpy as np
 
 from . import greens as _greens
+from ._chain_unit import position_pointers, require_device, reset_device
 from ._lib import P_int, check, dptr, iptr
 
 GLOBAL_KEYS = ("density", "Nsqr", "mu")
 ONSITE_KEYS = ("density", "double_occ", "x", "x2", "x4", "phonon_pe", "phonon_ke", "elph_energy", "mu")
 INTERSITE_KEYS = ("el_ke",)
+KEYS = (GLOBAL_KEYS, ONSITE_KEYS, INTERSITE_KEYS)           # a model's scalars in the order of its device unit's buffer and of its files
 ONSITE_CORR = ("Greens", "DenDen", "SpinSpin", "PairGreens", "PhononGreens")        # the order of elph_meas_create's request arrays
 INTERSITE_CORR = ("BondBond", "CurrentCurrent", "BondPairGreens")
 SUSC_OF = (("PairSusc", "PairGreens"), ("ChargeSusc", "DenDen"), ("SpinSusc", "SpinSpin"))      # :148-155
@@ -84,6 +101,13 @@ def _pairs(entry, n):
 def _refuse_ssh(model, subject):
     if getattr(model, "kind", None) != 0:
         raise UnsupportedMeasurement("%s of the SSH model are not supported (Holstein only)" % subject)
+
+
+def _refuse_holstein(model, subject):
+    """subject: "SSH measurements" / "SSH bond correlations"; the module named is the Holstein one for the same correlations."""
+    if getattr(model, "kind", None) != 1:
+        raise UnsupportedMeasurement("%s of the Holstein model are not supported (SSH only; see %smeasurements.py)"
+                                     % (subject, "bond_" if "bond" in subject else ""))
 
 
 def _refuse_chains(model, subject):
@@ -213,17 +237,24 @@ def _check_estimator(container, model, Gr):
         raise ValueError("the estimator holds %d vectors, the container normalises for num_random_vectors = %d" % (Gr.nv, container.n_rand_vecs))
 
 
+def _create_args(container, model, mu):
+    """The arguments of elph_meas_create after the handle and of elph_meas_chains_create after nchains: the model's parameters with `mu`
+    (float64: Nsites, or a row per chain), the bonds and the container's requests.  The second value keeps the arrays alive for the call."""
+    sites, t = bond_arrays(model)
+    request = _request_arrays(container.onsite_corr, ONSITE_CORR)
+    par = [np.ascontiguousarray(a, dtype=np.float64) for a in (model.omega, model.omega4, model.lam)]
+    args = [*map(dptr, par), dptr(mu), float(model.dtau), sites.shape[0], int(model.nbonds), iptr(sites) if sites.size else None,
+            dptr(t) if t.size else None, *map(_ip, request)]
+    return args, (sites, t, request, par, mu)
+
+
 def _ensure_device(container, model, Gr):
     if container._device_of is model:
         return
     _refuse_ssh(model, "measurements")
     _check_estimator(container, model, Gr)
-    sites, t = bond_arrays(model)
-    request = _request_arrays(container.onsite_corr, ONSITE_CORR)
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-    check(model._lib.elph_meas_create(model._h, dptr(f64(model.omega)), dptr(f64(model.omega4)), dptr(f64(model.lam)), dptr(f64(model.mu)),
-                                      float(model.dtau), sites.shape[0], int(model.nbonds), iptr(sites) if sites.size else None,
-                                      dptr(t) if t.size else None, *map(_ip, request)))
+    args, keep = _create_args(container, model, np.ascontiguousarray(model.mu, dtype=np.float64))
+    check(model._lib.elph_meas_create(model._h, *args))
     container._device_of = model
 
 
@@ -244,27 +275,32 @@ def make_measurements_(container, model, Gr, nmeas, P=None, R=None, rng=None):
     return out
 
 
+def _scalar_buffer(container, keys=KEYS):
+    """The buffer a *_fetch call fills: the global scalars, every on-site key per orbital, every inter-site key per bond definition."""
+    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
+    return np.zeros(len(keys[0]) + len(keys[1]) * no + len(keys[2]) * nb)
+
+
+def _store_scalars(container, scal, keys=KEYS):
+    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
+    for i, k in enumerate(keys[0]):
+        container.global_meas[k] = complex(scal[i])
+    at = len(keys[0])
+    for i, k in enumerate(keys[1]):
+        container.onsite_meas[k][:] = scal[at + i * no:at + (i + 1) * no]
+    at += len(keys[1]) * no
+    for i, k in enumerate(keys[2]):
+        container.intersite_meas[k][:] = scal[at + i * nb:at + (i + 1) * nb]
+
+
 def _fetch_buffers(container):
     """(scalars, the position arrays' pointers in ONSITE_CORR order) for a *_fetch call into the container."""
-    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
-    scal = np.zeros(3 + len(ONSITE_KEYS) * no + nb)
-    ptrs = [container.onsite_corr[name].position.ctypes.data_as(type(dptr(scal))) if name in container.onsite_corr else None for name in ONSITE_CORR]
-    return scal, ptrs
-
-
-def _store_scalars(container, scal):
-    no = len(container.onsite_meas["density"])
-    for i, k in enumerate(GLOBAL_KEYS):
-        container.global_meas[k] = complex(scal[i])
-    for i, k in enumerate(ONSITE_KEYS):
-        container.onsite_meas[k][:] = scal[3 + i * no:3 + (i + 1) * no]
-    container.intersite_meas["el_ke"][:] = scal[3 + len(ONSITE_KEYS) * no:]
+    return _scalar_buffer(container), position_pointers(container.onsite_corr, ONSITE_CORR)
 
 
 def fetch_(container, model):
     """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
-    if container._device_of is not model:
-        raise RuntimeError("nothing has been measured on this model yet")
+    require_device(container, model)
     scal, ptrs = _fetch_buffers(container)
     check(model._lib.elph_meas_fetch(model._h, dptr(scal), *ptrs))
     _store_scalars(container, scal)
@@ -318,14 +354,18 @@ def _process_group(corr_group, susc_group, table, V, dtau):
     _simpson_group(susc_group, corr_group, table, dtau)
 
 
-def normalize_(container, bin_size):
-    """:590-629: everything divided by bin_size * binomial(n_rand_vecs, 2)."""
-    V = _bin_volume(container, bin_size)
+def _divide_scalars(container, V):
     for k in container.global_meas:
         container.global_meas[k] /= V
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k] /= V
+
+
+def normalize_(container, bin_size):
+    """:590-629: everything divided by bin_size * binomial(n_rand_vecs, 2)."""
+    V = _bin_volume(container, bin_size)
+    _divide_scalars(container, V)
     _divide_group(container.onsite_corr, V)
 
 
@@ -370,23 +410,23 @@ def _zero_groups(*groups):
             corr.momentum[...] = 0
 
 
-def write_measurements_(container, model, bin):
-    """write_measurements!(container, model, bin) (:681-693, :1175-1274)."""
+def write_measurements_(container, model, bin, keys=KEYS):
+    """write_measurements!(container, model, bin) (:681-693, :1175-1274); keys: the scalars' line order (the model's KEYS)."""
     d = container.datafolder
     with open(os.path.join(d, "global_measurements_f", "global_measurements_%.5d.out" % bin), "w") as f:
-        for k in GLOBAL_KEYS:
+        for k in keys[0]:
             f.write("%s %.8f\n" % (k, container.global_meas[k].real))
     with open(os.path.join(d, "onsite_measurements_f", "onsite_measurements_%.5d.out" % bin), "w") as f:
         f.write("measurement orbit value\n")
-        for k in ONSITE_KEYS:
+        for k in keys[1]:
             for o, v in enumerate(container.onsite_meas[k]):
                 f.write("%s %d %.8f\n" % (k, o + 1, v.real))
     with open(os.path.join(d, "intersite_measurements_f", "intersite_measurements_%.5d.out" % bin), "w") as f:
         f.write("measurement bond value\n")
-        for k in INTERSITE_KEYS:
+        for k in keys[2]:
             for b, v in enumerate(container.intersite_meas[k]):
                 f.write("%s %d %.8f\n" % (k, b + 1, v.real))
-    _write_groups(d, bin, container.onsite_corr, container.onsite_susc)
+    _write_groups(d, bin, container.onsite_corr, container.intersite_corr, container.onsite_susc, container.intersite_susc)
 
 
 def _zero_container(container):
@@ -395,11 +435,10 @@ def _zero_container(container):
     for group in (container.onsite_meas, container.intersite_meas):
         for k in group:
             group[k][:] = 0
-    _zero_groups(container.onsite_corr, container.onsite_susc)
+    _zero_groups(container.onsite_corr, container.intersite_corr, container.onsite_susc, container.intersite_susc)
 
 
 def reset_measurements_(container, model):
     """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
     _zero_container(container)
-    if container._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_meas_reset(model._h))
+    reset_device(container, model, "elph_meas_reset")

@@ -25,6 +25,7 @@ import os
 import numpy as np
 
 from . import hmc as _hmc
+from ._chain_unit import chain_rows
 from ._lib import check, dptr
 
 LOG_HEADER = "mu_bar kappa_bar n_bar Nsqr_bar mu n Nsqr\n"
@@ -188,9 +189,7 @@ def tune_mu_chains_(model, tuners, Gr, mu, hmc=None):
     Returns mu (float64, C-contiguous: the caller's array when it is that already) for chain_measurements.accumulate_(..., mu=mu) or
     its SSH twin.  An inactive tuner records its row's mean and leaves the row."""
     nch = len(tuners)
-    out = np.ascontiguousarray(mu, dtype=np.float64)
-    if out.shape != (nch, model.Nsites):
-        raise ValueError("mu has shape %s, not (nchains, Nsites) = (%d, %d)" % (out.shape, nch, model.Nsites))
+    out = chain_rows(mu, nch, model.Nsites, "mu")
     if not any(t.active for t in tuners):
         for c, t in enumerate(tuners):
             t.mu = float(np.mean(out[c]))

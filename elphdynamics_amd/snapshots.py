@@ -25,6 +25,7 @@ import os
 
 import numpy as np
 
+from ._chain_unit import chain_folders, chain_rows, check_chains
 from ._lib import check, dptr
 from .measurements import UnsupportedMeasurement
 
@@ -48,15 +49,12 @@ def split_info(info):
 def initialize_snapshots_container(model, info, datafolders):
     """The snapshot part of initialize_measurements_container (:57-82) for the [measurements] table `info`; datafolders: one string for
     one configuration, or one folder per resident chain."""
-    nchains = int(getattr(model, "_nchains", 1))
-    datafolders = [datafolders] if isinstance(datafolders, (str, os.PathLike)) else list(datafolders)
-    if len(datafolders) != nchains:
-        raise ValueError("%d data folders for the %d chains resident in the model" % (len(datafolders), nchains))
+    datafolders = chain_folders(model, datafolders)
     _, snap = split_info(info)
     for key, val in snap.items():
         if val is True and key not in SNAPSHOTS:
             raise UnsupportedMeasurement("[measurements.Snapshots] %s = true: there is no such snapshot (%s)" % (key, ", ".join(SNAPSHOTS)))
-    return SnapshotsContainer([name for name in SNAPSHOTS if snap.get(name, False) is True], [os.fspath(f) for f in datafolders], nchains)
+    return SnapshotsContainer([name for name in SNAPSHOTS if snap.get(name, False) is True], [os.fspath(f) for f in datafolders], len(datafolders))
 
 
 def initialize_snapshot_folders_(sc):
@@ -71,9 +69,8 @@ def snapshot_arrays_(sc, model, Gr, X=None):
     asks for what is requested only, phonon_position (nchains, Nph) from X or, for one configuration, model.x."""
     if Gr.model is not model:
         raise ValueError("the estimator was made for another model")
-    nch = int(getattr(model, "_nchains", 1))
-    if nch != sc.nchains:
-        raise ValueError("the container was made for %d chains, %d are resident in the model" % (sc.nchains, nch))
+    check_chains(sc, model)
+    nch = sc.nchains
     out = {}
     if "phonon_position" in sc.snapshots:
         if X is None:
@@ -83,8 +80,7 @@ def snapshot_arrays_(sc, model, Gr, X=None):
         X = np.ascontiguousarray(X, dtype=np.float64)
         if X.ndim == 1 and nch == 1:
             X = X[None]
-        if X.shape != (nch, model.Ndof):
-            raise ValueError("X has shape %s, not (nchains, Ndof) = (%d, %d)" % (X.shape, nch, model.Ndof))
+        X = chain_rows(X, nch, model.Ndof, "X")
     device = [name for name in sc.snapshots if name != "phonon_position"]
     if device:
         for name in device:

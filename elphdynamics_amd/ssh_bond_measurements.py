@@ -24,37 +24,27 @@ Where the reference throws: the b == c term indexes with r'' unreduced (:2336-23
 here r'' is reduced mod L.  The reshape of t' to (Ltau, L1, L2, L3, n_def) (:2145) throws unless Nbonds = n_def * ncells; the library
 refuses a CurrentCurrent request there (ELPH_E_UNSUPPORTED naming both counts), BondBond and BondPairGreens stay available.
 
-Scope.  Refused with UnsupportedMeasurement naming the request: a Holstein model (bond_measurements.py measures it), several chains
-resident (ssh_chain_bond_measurements.py measures them, all chains in the same launches), a request on a model without bond definitions;
-sharded and slab handles are refused by the library.
+Scope: the table in measurements.py's docstring has what each of the nine modules measures and refuses, this one included.
 """
 import numpy as np
 
-from ._lib import P_dbl, check, dptr, iptr
+from ._chain_unit import pack_bond_definitions, position_pointers, require_device, reset_device
+from ._lib import check, dptr, iptr
+from .bond_measurements import BondContainer
 from .measurements import (INTERSITE_CORR, UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group, _group_folders, _i32, _ip,  # noqa: F401
-                           _process_group, _refuse_chains, _request_arrays, _requested, _susc_group, _write_groups, _zero_groups, simpson)
+                           _process_group, _refuse_chains, _refuse_holstein, _request_arrays, _requested, _susc_group, _write_groups, _zero_groups, simpson)
 
 SSH_BOND_CORR = INTERSITE_CORR                                 # BondBond, CurrentCurrent, BondPairGreens: elph_ssh_bond_create's request order
 SSH_BOND_SUSC_OF = (("BondPairSusc", "BondPairGreens"),)       # :322
 SUBJECT = "SSH bond correlations"
 
 
-class SSHBondContainer:
-    def __init__(self):
-        self.intersite_corr, self.intersite_susc = {}, {}
-        self.bond_definitions = []
-        self.n_rand_vecs = 1
-        self.datafolder = ""
-        self._device_of = None           # the model whose handle holds the device side
-
-
-def _refuse_holstein(model):
-    if getattr(model, "kind", None) != 1:
-        raise UnsupportedMeasurement("%s of the Holstein model are not supported (SSH only; see bond_measurements.py)" % SUBJECT)
+class SSHBondContainer(BondContainer):
+    """The same fields."""
 
 
 def _refuse_model(model):
-    _refuse_holstein(model)
+    _refuse_holstein(model, SUBJECT)
     _refuse_chains(model, SUBJECT)
 
 
@@ -91,8 +81,7 @@ def _create_args(container, model):
     """The arguments of elph_ssh_bond_create after the handle and of elph_ssh_bond_chains_create after nchains: the bond definitions, the
     bonds and phonons of the model, the request.  Second value: the arrays the pointers refer to, to be kept alive across the call."""
     defs = container.bond_definitions
-    o1, o2 = _i32([d[0] for d in defs] or [0]), _i32([d[1] for d in defs] or [0])
-    v = _i32([k for d in defs for k in d[2]] or [0, 0, 0])
+    o1, o2, v = pack_bond_definitions(defs)
     request = _request_arrays(container.intersite_corr, SSH_BOND_CORR)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)  # noqa: E731
@@ -127,11 +116,8 @@ def accumulate_ssh_bonds_(container, model, Gr):
 
 def fetch_ssh_bonds_(container, model):
     """The device's un-normalised sums into the container's position arrays; the momentum arrays are not touched."""
-    if container._device_of is not model:
-        raise RuntimeError("no SSH bond correlation has been measured on this model yet")
-    corr = container.intersite_corr
-    ptrs = [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in SSH_BOND_CORR]
-    check(model._lib.elph_ssh_bond_fetch(model._h, *ptrs))
+    require_device(container, model, "no SSH bond correlation")
+    check(model._lib.elph_ssh_bond_fetch(model._h, *position_pointers(container.intersite_corr, SSH_BOND_CORR)))
 
 
 def process_ssh_bond_measurements_(container, bin_size, model):
@@ -154,5 +140,4 @@ def reset_ssh_bond_measurements_(container, model):
     """reset_measurements!(container, model) (:698-758) for the three correlations: the container's arrays and the device's accumulators
     to zero."""
     _zero_groups(container.intersite_corr, container.intersite_susc)
-    if container._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_ssh_bond_reset(model._h))
+    reset_device(container, model, "elph_ssh_bond_reset")

@@ -14,48 +14,32 @@ accumulated by the same launches (elph_ssh_bond_chains_*, csrc/ssh_bondcorr.hip)
     reset_ssh_bond_measurements_(cb, model)                              :698-758
 
 X is (nchains, Ndof): chain c's field (the dynamics' X after pull_()), from which CurrentCurrent recomputes chain c's modulated hopping.
-The estimator serves the chains with n_rand_vecs * nchains vectors, vector v of chain c at index v * nchains + c (greens.chain_vector),
-as process_input_file(deck, nchains=n) builds it; a bin is normalised by bin_size * binomial(n_rand_vecs, 2) with the vectors PER CHAIN.
-A chain's folder holds exactly the files ssh_bond_measurements.py writes for one configuration, BondPairSusc included.
+The estimator's vectors per chain, the normalisation of a bin, the life of the device side and the use beside the on-site chain
+container (here an ssh_chain_measurements.SSHChainMeasurementsContainer) are chain_bond_measurements.py's.  A chain's folder holds
+exactly the files ssh_bond_measurements.py writes for one configuration, BondPairSusc included.
 
-It is used next to an ssh_chain_measurements.SSHChainMeasurementsContainer (whose constructor keeps refusing the three names) on the
-same model and estimator, in either order: the two device sides are separate, and neither touches the estimator's own tables, so Gr.n1
-and Gr.n2 are left alone.
-
-The device side is shaped by the estimator and dropped by the library when a new EstimateGreensFunction is made on the model (with the
-sums it held): the next accumulate_ssh_bonds_ with the new estimator makes it again.
-
-Scope: what ssh_bond_measurements.py measures for one configuration, with its departures from the reference's comments.  Refused with
-UnsupportedMeasurement naming the request: the Holstein model (chain_bond_measurements.py measures it), a request on a model without
-bond definitions.  ssh_bond_measurements.py itself keeps refusing resident chains; sharded and slab handles, and CurrentCurrent where
-Nbonds != n_def * ncells, are refused by the library.
+Scope: what ssh_bond_measurements.py measures for one configuration, with its departures from the reference's comments, and its
+refusals but the resident chains (the library's of CurrentCurrent where Nbonds != n_def * ncells included); the table in
+measurements.py's docstring has the module for everything else.  The functions below are the bond family of _chain_unit.py with this
+module's record.
 """
-import numpy as np
-
+from . import _chain_unit as _cu
 from . import ssh_bond_measurements as _sb
-from ._lib import P_dbl, check, dptr
 
 UnsupportedMeasurement = _sb.UnsupportedMeasurement
 SUBJECT = "SSH chain bond correlations"
+FAMILY = _cu.BondFamily(single=_sb, refuse=lambda model: _sb._refuse_holstein(model, _sb.SUBJECT), prefix="elph_ssh_bond_chains_",
+                        corr=_sb.SSH_BOND_CORR, takes_X=True, noun="SSH bond correlation")
 
 
-class SSHChainBondContainer:
-    def __init__(self, chains, n_rand_vecs):
-        self.chains = chains                 # one SSHBondContainer per chain
-        self.nchains = len(chains)
-        self.n_rand_vecs = n_rand_vecs       # per chain
-        self._device_of = None               # the model whose handle holds the device side ...
-        self._device_est = None              # ... and the estimator it was shaped by: a newer one on the model has dropped it
+class SSHChainBondContainer(_cu.ChainContainer):
+    """chains: one SSHBondContainer per chain."""
 
 
 def initialize_ssh_chain_bond_container(model, info, datafolders):
     """One SSHBondContainer per resident chain of `model` for the request `info`; datafolders: one folder per chain."""
-    _sb._refuse_holstein(model)
-    nchains = int(getattr(model, "_nchains", 1))
-    datafolders = list(datafolders)
-    if len(datafolders) != nchains:
-        raise ValueError("%d data folders for the %d chains resident in the model" % (len(datafolders), nchains))
-    chains = [_sb._new_ssh_bond_container(model, info, folder) for folder in datafolders]
+    FAMILY.refuse(model)
+    chains = [_sb._new_ssh_bond_container(model, info, folder) for folder in _cu.chain_folders(model, datafolders)]
     return SSHChainBondContainer(chains, chains[0].n_rand_vecs)
 
 
@@ -64,48 +48,16 @@ def initialize_ssh_bond_folders_(cb):
         _sb.initialize_ssh_bond_folders_(c)
 
 
-def _check(cb, model, Gr, X):
-    """Everything that can be wrong on the host, before any library call."""
-    assert Gr.model is model
-    _sb._refuse_holstein(model)
-    if int(getattr(model, "_nchains", 1)) != cb.nchains:
-        raise ValueError("the container was made for %d chains, %d are resident in the model" % (cb.nchains, getattr(model, "_nchains", 1)))
-    if Gr.nv != cb.n_rand_vecs * cb.nchains:
-        raise ValueError("the estimator holds %d vectors, the container normalises for num_random_vectors = %d for each of %d chains"
-                         % (Gr.nv, cb.n_rand_vecs, cb.nchains))
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    if X.shape != (cb.nchains, model.Ndof):
-        raise ValueError("X has shape %s, not (nchains, Ndof) = (%d, %d)" % (X.shape, cb.nchains, model.Ndof))
-    return X
-
-
-def _ensure_device(cb, model, Gr):
-    if cb._device_of is model and cb._device_est is Gr:
-        return
-    args, keep = _sb._create_args(cb.chains[0], model)
-    check(model._lib.elph_ssh_bond_chains_create(model._h, cb.nchains, *args))
-    cb._device_of, cb._device_est = model, Gr
-
-
 def accumulate_ssh_bonds_(cb, model, Gr, X):
     """measure_BondBond!, measure_CurrentCurrent! and measure_BondPairGreens! for every pair v1 < v2 of a chain's vectors, folded into the
     device's accumulators for all chains at once; nothing comes back to the host, and the estimator's own tables (Gr.n1, Gr.n2) are not
     touched."""
-    X = _check(cb, model, Gr, X)
-    if not cb.chains[0].intersite_corr:                                     # nothing requested: nothing to set up or fold
-        return
-    _ensure_device(cb, model, Gr)
-    check(model._lib.elph_ssh_bond_chains_accumulate(model._h, dptr(X)))
+    _cu.bond_accumulate(FAMILY, cb, model, Gr, X)
 
 
 def fetch_ssh_bonds_(cb, model):
     """The device's un-normalised sums into every chain's position arrays; the momentum arrays are not touched."""
-    if cb._device_of is not model:
-        raise RuntimeError("no SSH bond correlation has been measured on this model yet")
-    for chain, c in enumerate(cb.chains):
-        corr = c.intersite_corr
-        ptrs = [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in _sb.SSH_BOND_CORR]
-        check(model._lib.elph_ssh_bond_chains_fetch(model._h, chain, *ptrs))
+    _cu.bond_fetch(FAMILY, cb, model)
 
 
 def process_ssh_bond_measurements_(cb, bin_size, model):
@@ -124,7 +76,4 @@ def write_ssh_bond_measurements_(cb, model, bin):
 
 def reset_ssh_bond_measurements_(cb, model):
     """reset_measurements! (:698-758): every chain's arrays and the device's accumulators to zero."""
-    for c in cb.chains:
-        _sb._zero_groups(c.intersite_corr, c.intersite_susc)
-    if cb._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_ssh_bond_chains_reset(model._h))
+    _cu.bond_reset(FAMILY, cb, model)

@@ -17,14 +17,9 @@ correlations Greens, DenDen, SpinSpin, PairGreens over orbital pairs with the su
 inter-site PhononGreens over pairs of phonon types 1..nph (:2488-2541; all nph^2 by default), present only when the model has phonons
 (:291-293).  pairs[0, p] = b1, pairs[1, p] = b2: PhononGreens[D] = 1/(L Nc) sum x_b2[. + D] x_b1[.].
 
-Scope.  Refused with UnsupportedMeasurement naming the request, never skipped: BondBond, CurrentCurrent, BondPairGreens (and with it
-BondPairSusc) with measure = true, a [measurements.Snapshots] entry set to true (snapshots.py takes them, in a container of its own), a Holstein model, several chains resident in the
-handle; sharded and slab handles, and PhononGreens on a lattice where Nph != nph * ncells (the reference's reshape of the field
-throws), are refused by the library.  BondBond, CurrentCurrent, BondPairGreens and BondPairSusc live in a container of their own beside
-this one (ssh_bond_measurements.py, csrc/ssh_bondcorr.hip), used on the same model and estimator.  Several chains resident in the handle
-(a lockstep run) are measured by the chain-aware twin of this module, ssh_chain_measurements.py (csrc/ssh_measure.hip): one
-container per chain, all chains in the same launches; the functions here keep refusing them.  BondBond, CurrentCurrent and BondPairGreens
-over chains are ssh_chain_bond_measurements.py's (csrc/ssh_bondcorr.hip).
+Scope: the table in measurements.py's docstring has what each of the nine modules measures and refuses, this one included.  Refused by
+the library besides sharded and slab handles: PhononGreens on a lattice where Nph != nph * ncells (the reference's reshape of the field
+throws).
 
 Line order in the scalar files (the reference's is the unspecified order of a Julia Dict), extending the one of measurements.py:
 density, Nsqr, mu / density, double_occ, mu / x, x2, x4, phonon_pe, phonon_ke, elph_energy, el_ke, sign_switch.
@@ -34,31 +29,23 @@ import os
 import numpy as np
 
 from . import greens as _greens
-from ._lib import P_dbl, check, dptr, iptr
-from .measurements import (GLOBAL_KEYS, INTERSITE_CORR, SUSC_OF, UnsupportedMeasurement, _bin_volume, _check_estimator, _corr_group,  # noqa: F401
-                           _group_folders, _ip, _process_group, _refuse_chains, _request_arrays, _susc_group, _write_groups, _zero_groups,
-                           simpson)
+from . import measurements as _ms
+from ._chain_unit import position_pointers, require_device, reset_device
+from ._lib import check, dptr, iptr
+from .measurements import (GLOBAL_KEYS, INTERSITE_CORR, SUSC_OF, MeasurementsContainer, UnsupportedMeasurement, _bin_volume,  # noqa: F401
+                           _check_estimator, _corr_group, _divide_scalars, _group_folders, _ip, _process_group, _refuse_chains,
+                           _refuse_holstein, _request_arrays, _susc_group, _write_groups, _zero_container, _zero_groups, simpson)
 
 ONSITE_KEYS = ("density", "double_occ", "mu")
 INTERSITE_KEYS = ("x", "x2", "x4", "phonon_pe", "phonon_ke", "elph_energy", "el_ke", "sign_switch")
+KEYS = (GLOBAL_KEYS, ONSITE_KEYS, INTERSITE_KEYS)
 ONSITE_CORR = ("Greens", "DenDen", "SpinSpin", "PairGreens")
 CREATE_ORDER = ONSITE_CORR + ("PhononGreens",)              # the order of elph_ssh_meas_create's request arrays
 SUBJECT = "SSH measurements"
 
 
-class SSHMeasurementsContainer:
-    def __init__(self):
-        self.global_meas, self.onsite_meas, self.intersite_meas = {}, {}, {}
-        self.onsite_corr, self.intersite_corr, self.onsite_susc, self.intersite_susc = {}, {}, {}, {}
-        self.snapshots = []
-        self.n_rand_vecs = 1
-        self.datafolder = ""
-        self._device_of = None           # the model whose handle holds the device side
-
-
-def _refuse_holstein(model):
-    if getattr(model, "kind", None) != 1:
-        raise UnsupportedMeasurement("%s of the Holstein model are not supported (SSH only; see measurements.py)" % SUBJECT)
+class SSHMeasurementsContainer(MeasurementsContainer):
+    """The same fields; the inter-site scalars and PhononGreens (intersite_corr) are filled here."""
 
 
 def _new_container(model, info, datafolder):
@@ -90,7 +77,7 @@ def _new_container(model, info, datafolder):
 
 def initialize_ssh_measurements_container(model, info, datafolder):
     """initialize_measurements_container(ssh, info, datafolder) (:180-338)."""
-    _refuse_holstein(model)
+    _refuse_holstein(model, SUBJECT)
     _refuse_chains(model, SUBJECT)
     return _new_container(model, info, datafolder)
 
@@ -117,9 +104,9 @@ def _all_corr(container):
     return dict(container.onsite_corr, **container.intersite_corr)
 
 
-def _create_args(container, model):
-    """The arguments of elph_ssh_meas_create after mu and of elph_ssh_meas_chains_create after nchains and mu: dtau, the bonds, the phonons
-    and the container's requests.  The second value keeps the arrays alive for the call."""
+def _create_args(container, model, mu):
+    """The arguments of elph_ssh_meas_create after the handle and of elph_ssh_meas_chains_create after nchains: `mu` (float64: Nsites, or a
+    row per chain), dtau, the bonds, the phonons and the container's requests.  The second value keeps the arrays alive for the call."""
     sites, t = bond_arrays(model)
     request = _request_arrays(_all_corr(container), CREATE_ORDER)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
@@ -127,18 +114,18 @@ def _create_args(container, model):
     nph_tot, nb = int(model.Nph), int(model.Nbonds)
     b2d, b2p = i64(model.bond_to_definition), i64(model.bond_to_phonon)
     par = [f64(a) for a in (model.omega, model.alpha, model.alpha2)]
-    args = [float(model.dtau), nb, int(model.nbonds), iptr(sites) if nb else None, dptr(t) if nb else None, iptr(b2d) if nb else None,
+    args = [dptr(mu), float(model.dtau), nb, int(model.nbonds), iptr(sites) if nb else None, dptr(t) if nb else None, iptr(b2d) if nb else None,
             iptr(b2p) if nb else None, nph_tot, int(model.nph), *[dptr(a) if nph_tot else None for a in par], *map(_ip, request)]
-    return args, (sites, t, b2d, b2p, par, request)
+    return args, (mu, sites, t, b2d, b2p, par, request)
 
 
 def _ensure_device(container, model, Gr):
     if container._device_of is model:
         return
-    _refuse_holstein(model)
+    _refuse_holstein(model, SUBJECT)
     _check_estimator(container, model, Gr)
-    args, keep = _create_args(container, model)
-    check(model._lib.elph_ssh_meas_create(model._h, dptr(np.ascontiguousarray(model.mu, dtype=np.float64)), *args))
+    args, keep = _create_args(container, model, np.ascontiguousarray(model.mu, dtype=np.float64))
+    check(model._lib.elph_ssh_meas_create(model._h, *args))
     container._device_of = model
 
 
@@ -161,27 +148,16 @@ def make_measurements_(container, model, Gr, nmeas, P=None, R=None, rng=None):
 
 def _fetch_buffers(container):
     """(scalars, the position arrays' pointers in CREATE_ORDER) for a *_fetch call into the container."""
-    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
-    scal = np.zeros(3 + len(ONSITE_KEYS) * no + len(INTERSITE_KEYS) * nb)
-    corr = _all_corr(container)
-    return scal, [corr[name].position.ctypes.data_as(P_dbl) if name in corr else None for name in CREATE_ORDER]
+    return _ms._scalar_buffer(container, KEYS), position_pointers(_all_corr(container), CREATE_ORDER)
 
 
 def _store_scalars(container, scal):
-    no, nb = len(container.onsite_meas["density"]), len(container.intersite_meas["el_ke"])
-    for i, k in enumerate(GLOBAL_KEYS):
-        container.global_meas[k] = complex(scal[i])
-    for i, k in enumerate(ONSITE_KEYS):
-        container.onsite_meas[k][:] = scal[3 + i * no:3 + (i + 1) * no]
-    at = 3 + len(ONSITE_KEYS) * no
-    for i, k in enumerate(INTERSITE_KEYS):
-        container.intersite_meas[k][:] = scal[at + i * nb:at + (i + 1) * nb]
+    _ms._store_scalars(container, scal, KEYS)
 
 
 def fetch_(container, model):
     """The device's un-normalised sums into the container (position arrays and scalars); the momentum arrays are not touched."""
-    if container._device_of is not model:
-        raise RuntimeError("nothing has been measured on this model yet")
+    require_device(container, model)
     scal, ptrs = _fetch_buffers(container)
     check(model._lib.elph_ssh_meas_fetch(model._h, dptr(scal), *ptrs))
     _store_scalars(container, scal)
@@ -190,11 +166,7 @@ def fetch_(container, model):
 def _process_fetched(container, bin_size, dtau):
     """process_measurements! after the fetch: momentum copy, normalisation, susceptibilities."""
     V = _bin_volume(container, bin_size)
-    for k in container.global_meas:
-        container.global_meas[k] /= V
-    for group in (container.onsite_meas, container.intersite_meas):
-        for k in group:
-            group[k] /= V
+    _divide_scalars(container, V)
     _process_group(container.onsite_corr, container.onsite_susc, SUSC_OF, V, dtau)
     _process_group(container.intersite_corr, container.intersite_susc, (), V, dtau)
 
@@ -207,34 +179,10 @@ def process_measurements_(container, bin_size, model):
 
 def write_measurements_(container, model, bin):
     """write_measurements!(container, model, bin) (:681-693, :1175-1274)."""
-    d = container.datafolder
-    with open(os.path.join(d, "global_measurements_f", "global_measurements_%.5d.out" % bin), "w") as f:
-        for k in GLOBAL_KEYS:
-            f.write("%s %.8f\n" % (k, container.global_meas[k].real))
-    with open(os.path.join(d, "onsite_measurements_f", "onsite_measurements_%.5d.out" % bin), "w") as f:
-        f.write("measurement orbit value\n")
-        for k in ONSITE_KEYS:
-            for o, v in enumerate(container.onsite_meas[k]):
-                f.write("%s %d %.8f\n" % (k, o + 1, v.real))
-    with open(os.path.join(d, "intersite_measurements_f", "intersite_measurements_%.5d.out" % bin), "w") as f:
-        f.write("measurement bond value\n")
-        for k in INTERSITE_KEYS:
-            for b, v in enumerate(container.intersite_meas[k]):
-                f.write("%s %d %.8f\n" % (k, b + 1, v.real))
-    _write_groups(d, bin, container.onsite_corr, container.intersite_corr, container.onsite_susc, container.intersite_susc)
-
-
-def _zero_container(container):
-    for k in container.global_meas:
-        container.global_meas[k] = 0j
-    for group in (container.onsite_meas, container.intersite_meas):
-        for k in group:
-            group[k][:] = 0
-    _zero_groups(container.onsite_corr, container.intersite_corr, container.onsite_susc, container.intersite_susc)
+    _ms.write_measurements_(container, model, bin, KEYS)
 
 
 def reset_measurements_(container, model):
     """reset_measurements!(container, model) (:698-758): the container's arrays and the device's accumulators to zero."""
     _zero_container(container)
-    if container._device_of is model and model is not None and getattr(model, "_h", None):
-        check(model._lib.elph_ssh_meas_reset(model._h))
+    reset_device(container, model, "elph_ssh_meas_reset")
