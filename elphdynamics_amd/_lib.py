@@ -178,6 +178,8 @@ BENCH_SIGNATURES = {
     "elph_bench_slabs_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_lattice_shape": (c_int, [c_int, c_i64, c_i64, P_i64, P_dbl, P_dbl, P_int]),
     "elph_bench_wg_plan": (c_int, [c_int, c_i64, c_i64, c_i64, P_i64, P_dbl, P_dbl, c_int, c_int, P_int]),
+    "elph_bench_dft_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_int, P_int]),
+    "elph_bench_dft_info": (c_int, [Handle, c_int, c_int, c_int, c_int, c_int, P_int]),
     "elph_bench_kpm_plan": (c_int, [c_i64, c_dbl, c_dbl, c_dbl, c_int, c_int, P_dbl, P_int, P_int, P_dbl, P_int, P_int, P_int, P_dbl,
                                     P_dbl, P_dbl, c_i64, P_i64]),
     "elph_bench_hess_max_real": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl]),
@@ -218,6 +220,21 @@ def wg_plan(kind, nsites, ltau, table, cosht=None, sinht=None, nrhs=1, world=0):
     check(lib.elph_bench_wg_plan(int(kind), int(nsites), int(ltau), table.shape[0], iptr(table) if table.size else None,
                                  None if c is None else dptr(c), None if s is None else dptr(s), int(nrhs), int(world), out))
     return dict(zip(WG_PLAN_SLOTS, list(out)))
+
+
+# the slots of elph_bench_dft_plan's vector, in order (elph_bench.h); DFT_FORMS: the numbers of its "form" slots (elph_internal.h: DftForm)
+DFT_PLAN_SLOTS = ("form", "nt", "groups", "lds", "slots", "xr", "px", "fold", "short_slots", "pair_form")
+DFT_FORMS = {"SCALAR": 0, "ONE_TILE": 1, "DIRECT": 2, "SPLIT_REG": 3, "SPLIT_LDS": 4, "BIG_ROW": 5, "BIG_BLOCKED": 6, "BIG_DIRECT": 7}
+
+
+def dft_plan(ltau, which, inverse, N, nvec, nrz_slots=0, handle=None):
+    """The plan of one tau-axis transform (which: 0 twisted, 1 plain) of nvec vectors of N columns under the ELPH_DFT_* / ELPH_FUSE_* switches of
+    the environment, as {slot: value}: on a time axis of ltau slices without a device, or (handle given) from that handle's own record."""
+    lib = load()
+    out = (c_int * len(DFT_PLAN_SLOTS))()
+    args = (int(which), int(bool(inverse)), int(N), int(nvec), int(nrz_slots), out)
+    check(lib.elph_bench_dft_plan(int(ltau), *args) if handle is None else lib.elph_bench_dft_info(handle, *args))
+    return dict(zip(DFT_PLAN_SLOTS, list(out)))
 
 
 def kpm_plan(ltau, bounds, buf=0.05, c1=1.0, c2=1.0):

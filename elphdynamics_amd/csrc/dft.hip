@@ -169,36 +169,6 @@ __global__ void __launch_bounds__(WAVE) k_dft_inv_tab(double *__restrict__ out, 
     }
 }
 
-// Single-solve shapes (2 outputs per wave: many waves for the latency-bound case).  These kernels are bound by the
-// scalar twiddle stream (106 SGPRs hold < 30 twiddles); a wider shape (8 outputs per wave) was measured ~15 % SLOWER in
-// a batch, so batches go to the matrix-core GEMM form in dft_mfma.hip instead.
-constexpr int DFT_KPT = 2, DFT_TC = 40, DFT_TPT = 2, DFT_KC = 20;
-static int dft_pad(int n, int m) { return ((n + m - 1) / m) * m; }
-// nu[rhs][k][s] (half spectrum, k < ceil(L/2)) = FFT_t(Theta .* v)[k]
-int elph_dft_fwd_twisted(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs, const CgState *st) {
-    const int L = (int)h->L, Lo2 = (L + 1) / 2, nst = (N + WAVE - 1) / WAVE;
-    if (elph_dft_big(h)) return elph_dft_big_fwd(h, true, nu, vS, N, nrhs);       // (finished right-hand sides are transformed too)
-    if (elph_dft_mfma_usable(h, 0, false, N, nrhs)) return elph_dft_mfma_fwd(h, 0, nu, vS, N, nrhs, st);
-    if (elph_dft_mfma1_usable(h, false, N, 0)) return elph_dft_mfma1_fwd(h, nu, vS, N, nrhs, st);
-    hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, false>),
-                           dim3((unsigned)nst, (unsigned)((Lo2 + DFT_KPT - 1) / DFT_KPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, nu,
-                           vS, h->d_Tk, N, L, Lo2, dft_pad(L, 2 * DFT_TC), st, (const double *)nullptr, 0.0);
-    return elph_launch_check("k_dft_fwd_tab(twisted)");
-}
-
-// out = Re( conj(Theta) .* iFFT(nu) ) from the half spectrum; rz_part (optional) receives partial r.out sums
-int elph_dft_inv_twisted(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs, const CgState *st,
-                         const double *rvec, double *rz_part, int nrz) {
-    const int L = (int)h->L, Lo2 = (L + 1) / 2, nst = (N + WAVE - 1) / WAVE;
-    if (elph_dft_big(h)) return elph_dft_big_inv(h, true, outS, nu, N, nrhs, rvec, rz_part, nrz);
-    if (elph_dft_mfma_usable(h, 0, true, N, nrhs)) return elph_dft_mfma_inv(h, 0, outS, nu, N, nrhs, st, rvec, rz_part, nrz);
-    if (elph_dft_mfma1_usable(h, true, N, rz_part ? nrz : 0)) return elph_dft_mfma1_inv(h, outS, nu, N, nrhs, st, rvec, rz_part, nrz);
-    hipLaunchKernelGGL((k_dft_inv_tab<DFT_TPT, DFT_KC>),
-                           dim3((unsigned)nst, (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, outS,
-                           nu, h->d_Tt, N, L, Lo2, dft_pad(Lo2, 2 * DFT_KC), st, rvec, rz_part, nrz);
-    return elph_launch_check("k_dft_inv_tab(twisted)");
-}
-
 // u[rhs][k][s] *= (D[k][s]^p + D[L-k][s]^p)/2  — the symmetrised diagonal of fourier_accelerate! between the two GEMM-form
 // transforms of a batch (the scalar forward kernel applies it in its epilogue)
 __global__ void __launch_bounds__(256) k_dft_diag(double2 *__restrict__ u, const double *__restrict__ diag, double power, int N,
@@ -213,72 +183,120 @@ __global__ void __launch_bounds__(256) k_dft_diag(double2 *__restrict__ u, const
     u[i] = v;
 }
 
+// Single-solve shapes (2 outputs per wave: many waves for the latency-bound case).  These kernels are bound by the
+// scalar twiddle stream (106 SGPRs hold < 30 twiddles); a wider shape (8 outputs per wave) was measured ~15 % SLOWER in
+// a batch, so batches go to the matrix-core GEMM form in dft_mfma.hip instead.
+constexpr int DFT_KPT = 2, DFT_TC = 40, DFT_TPT = ELPH_DFT_TPT, DFT_KC = 20;
+static int dft_pad(int n, int m) { return ((n + m - 1) / m) * m; }
+
+static DftPlan plan(const elph_handle_s *h, int which, bool inverse, int N, int nvec, int nrz_slots) {
+    return elph_plan_dft(h->dft.shape, dft_switches(), which, inverse, N, nvec, nrz_slots);
+}
+static int half(int which, int L) { return which == DFT_TWISTED ? (L + 1) / 2 : L / 2 + 1; }      // frequencies of the half spectrum
+
+// nu[rhs][k][s] = FFT_t((twisted ? Theta : 1) .* v)[k], k < half; diag (plain, scalar form only): fourier_accelerate!'s diagonal in the epilogue
+static int dft_fwd(elph_handle_s *h, const DftPlan &p, int which, double2 *nu, const double *vS, int N, int nrhs, const CgState *st,
+                   const double *diag = nullptr, double power = 0.0) {
+    const int L = (int)h->L, K = half(which, L);
+    const dim3 grid((unsigned)((N + WAVE - 1) / WAVE), (unsigned)((K + DFT_KPT - 1) / DFT_KPT), (unsigned)nrhs);
+    switch (p.form) {
+    case DFT_SCALAR:
+        if (which == DFT_TWISTED)
+            hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, false>), grid, dim3(WAVE), 0, h->stream, nu, vS, h->dft.Tk, N, L, K,
+                               dft_pad(L, 2 * DFT_TC), st, (const double *)nullptr, 0.0);
+        else
+            hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, true>), grid, dim3(WAVE), 0, h->stream, nu, vS, h->dft.Pk, N, L, K,
+                               dft_pad(L, 2 * DFT_TC), st, diag, power);
+        return elph_launch_check(which == DFT_TWISTED ? "k_dft_fwd_tab(twisted)" : "k_dft_fwd_tab(plain)");
+    case DFT_BIG_ROW: case DFT_BIG_BLOCKED: case DFT_BIG_DIRECT:      // (finished right-hand sides are transformed too)
+        return elph_dft_big_fwd(h, p.form, which == DFT_TWISTED, nu, vS, N, nrhs);
+    default:
+        return elph_dft_mfma_run(h, p, which, false, reinterpret_cast<double *>(nu), vS, N, nrhs, st, nullptr, nullptr, 0);
+    }
+}
+
+// out = Re((twisted ? conj(Theta) : 1) .* iFFT(nu)) from the half spectrum (Hermitian weights and 1/L in the tables); rz_part (optional)
+// receives partial r.out sums
+static int dft_inv(elph_handle_s *h, const DftPlan &p, int which, double *outS, const double2 *nu, int N, int nrhs, const CgState *st,
+                   const double *rvec, double *rz_part, int nrz) {
+    const int L = (int)h->L, K = half(which, L);
+    if (p.short_slots) {
+        const bool big = p.form >= DFT_BIG_ROW, r2 = p.form == DFT_SPLIT_REG || p.form == DFT_SPLIT_LDS;
+        elph_set_error("%s: %d partial slots needed, %d available", big ? "dft_big" : r2 ? "dft_mfma_r2" : "dft_mfma", p.slots, nrz);
+        return ELPH_E_STATE;
+    }
+    switch (p.form) {
+    case DFT_SCALAR:
+        // r.z partial slots: (blockIdx.y * gridDim.x + blockIdx.x) < ceil(L/TPT)*nst <= L*npl = nrz; the kernel clears the rest
+        hipLaunchKernelGGL((k_dft_inv_tab<DFT_TPT, DFT_KC>), dim3((unsigned)((N + WAVE - 1) / WAVE), (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nrhs),
+                           dim3(WAVE), 0, h->stream, outS, nu, which == DFT_TWISTED ? h->dft.Tt : h->dft.Pt, N, L, K, dft_pad(K, 2 * DFT_KC), st, rvec,
+                           rz_part, nrz);
+        return elph_launch_check(which == DFT_TWISTED ? "k_dft_inv_tab(twisted)" : "k_dft_inv_tab(plain)");
+    case DFT_BIG_ROW: case DFT_BIG_BLOCKED: case DFT_BIG_DIRECT:
+        return elph_dft_big_inv(h, p.form, which == DFT_TWISTED, outS, nu, N, nrhs, rvec, rz_part, nrz);
+    default:
+        return elph_dft_mfma_run(h, p, which, true, outS, reinterpret_cast<const double *>(nu), N, nrhs, st, rvec, rz_part, nrz);
+    }
+}
+
+// the twisted pair (TimeFreqFFTs.jl: tau_to_omega!, omega_to_tau!): half spectrum k < ceil(L/2)
+int elph_dft_fwd_twisted(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs, const CgState *st) {
+    return dft_fwd(h, plan(h, DFT_TWISTED, false, N, nrhs, 0), DFT_TWISTED, nu, vS, N, nrhs, st);
+}
+int elph_dft_inv_twisted(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs, const CgState *st,
+                         const double *rvec, double *rz_part, int nrz) {
+    return dft_inv(h, plan(h, DFT_TWISTED, true, N, nrhs, rz_part ? nrz : 0), DFT_TWISTED, outS, nu, N, nrhs, st, rvec, rz_part, nrz);
+}
+// the plain (untwisted) pair: half spectrum k <= L/2
+int elph_dft_fwd_plain(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs) {
+    return dft_fwd(h, plan(h, DFT_PLAIN, false, N, nrhs, 0), DFT_PLAIN, nu, vS, N, nrhs, nullptr);
+}
+int elph_dft_inv_plain(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs) {
+    return dft_inv(h, plan(h, DFT_PLAIN, true, N, nrhs, 0), DFT_PLAIN, outS, nu, N, nrhs, nullptr, nullptr, nullptr, 0);
+}
+
 // out = Re iFFT( diag^power .* FFT(in) ), N columns, nvec vectors sharing one diagonal
 int elph_dft_accel(elph_handle_s *h, double *outS, const double *inS, const double *diagS, double power, int N, double2 *u, int nvec) {
-    const int L = (int)h->L, Lh = L / 2 + 1, nst = (N + WAVE - 1) / WAVE;
-    if (elph_dft_big(h)) {
-        int rc = elph_dft_big_fwd(h, false, u, inS, N, nvec);
-        if (rc) return rc;
+    DftPlan pf = plan(h, DFT_PLAIN, false, N, nvec, 0), pi = plan(h, DFT_PLAIN, true, N, nvec, 0);
+    elph_dft_pair(pf, pi);
+    const bool in_epilogue = pf.form == DFT_SCALAR;      // the scalar forward kernel applies the diagonal itself
+    RC(dft_fwd(h, pf, DFT_PLAIN, u, inS, N, nvec, nullptr, in_epilogue ? diagS : nullptr, power));
+    if (!in_epilogue) {
+        const int L = (int)h->L, Lh = L / 2 + 1;
         const long long total = (long long)nvec * Lh * N;
         hipLaunchKernelGGL(k_dft_diag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, u, diagS, power, N, L, Lh, total);
-        rc = elph_launch_check("k_dft_diag");
-        if (rc) return rc;
-        return elph_dft_big_inv(h, false, outS, u, N, nvec, nullptr, nullptr, 0);
+        RC(elph_launch_check("k_dft_diag"));
     }
-    if (elph_dft_mfma_usable(h, 1, false, N, nvec) && elph_dft_mfma_usable(h, 1, true, N, nvec)) {
-        int rc = elph_dft_mfma_fwd(h, 1, u, inS, N, nvec, nullptr);
-        if (rc) return rc;
-        const long long total = (long long)nvec * Lh * N;
-        hipLaunchKernelGGL(k_dft_diag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, u, diagS, power, N, L, Lh, total);
-        rc = elph_launch_check("k_dft_diag");
-        if (rc) return rc;
-        return elph_dft_mfma_inv(h, 1, outS, u, N, nvec, nullptr, nullptr, nullptr, 0);
-    }
-    hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, true>), dim3((unsigned)nst, (unsigned)((Lh + DFT_KPT - 1) / DFT_KPT), (unsigned)nvec),
-                       dim3(WAVE), 0, h->stream, u, inS, h->d_Pk, N, L, Lh, dft_pad(L, 2 * DFT_TC), (const CgState *)nullptr, diagS, power);
-    hipLaunchKernelGGL((k_dft_inv_tab<DFT_TPT, DFT_KC>), dim3((unsigned)nst, (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nvec),
-                       dim3(WAVE), 0, h->stream, outS, u, h->d_Pt, N, L, Lh, dft_pad(Lh, 2 * DFT_KC), (const CgState *)nullptr,
-                       (const double *)nullptr, (double *)nullptr, 0);
-    return elph_launch_check("fourier_accelerate");
+    return dft_inv(h, pi, DFT_PLAIN, outS, u, N, nvec, nullptr, nullptr, nullptr, 0);
 }
 
-// nu[rhs][k][s] (half spectrum, k <= L/2) = FFT_t(v)[k]  — plain (untwisted) transform, no diagonal
-int elph_dft_fwd_plain(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs) {
-    const int L = (int)h->L, Lh = L / 2 + 1, nst = (N + WAVE - 1) / WAVE;
-    if (elph_dft_big(h)) return elph_dft_big_fwd(h, false, nu, vS, N, nrhs);
-    if (elph_dft_mfma_usable(h, 1, false, N, nrhs)) return elph_dft_mfma_fwd(h, 1, nu, vS, N, nrhs, nullptr);
-    hipLaunchKernelGGL((k_dft_fwd_tab<DFT_KPT, DFT_TC, true>),
-                           dim3((unsigned)nst, (unsigned)((Lh + DFT_KPT - 1) / DFT_KPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, nu, vS,
-                           h->d_Pk, N, L, Lh, dft_pad(L, 2 * DFT_TC), (const CgState *)nullptr, (const double *)nullptr, 0.0);
-    return elph_launch_check("k_dft_fwd_tab(plain)");
+int elph_dft_upload(void **dev, const void *src, size_t bytes) {
+    HIPCHK(hipMalloc(dev, bytes));
+    HIPCHK(hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice));
+    return ELPH_OK;
 }
 
-// out = Re iFFT(nu) from the half spectrum k <= L/2 (Hermitian weights and 1/L in the table)
-int elph_dft_inv_plain(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs) {
-    const int L = (int)h->L, Lh = L / 2 + 1, nst = (N + WAVE - 1) / WAVE;
-    if (elph_dft_big(h)) return elph_dft_big_inv(h, false, outS, nu, N, nrhs, nullptr, nullptr, 0);
-    if (elph_dft_mfma_usable(h, 1, true, N, nrhs)) return elph_dft_mfma_inv(h, 1, outS, nu, N, nrhs, nullptr, nullptr, nullptr, 0);
-    hipLaunchKernelGGL((k_dft_inv_tab<DFT_TPT, DFT_KC>),
-                           dim3((unsigned)nst, (unsigned)((L + DFT_TPT - 1) / DFT_TPT), (unsigned)nrhs), dim3(WAVE), 0, h->stream, outS,
-                           nu, h->d_Pt, N, L, Lh, dft_pad(Lh, 2 * DFT_KC), (const CgState *)nullptr, (const double *)nullptr,
-                           (double *)nullptr, 0);
-    return elph_launch_check("k_dft_inv_tab(plain)");
+void elph_dft_free(elph_handle_s *h) {
+    DftState &D = h->dft;
+    void *ptrs[] = {D.theta, D.Tk, D.Tt, D.Pk, D.Pt, D.W[0][0], D.W[0][1], D.W[1][0], D.W[1][1], D.W_r2[0], D.W_r2[1], D.r2_tw,
+                    D.big_W1, D.big_W2, D.big_TW, D.big_a, D.big_b};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    D = DftState{};
 }
 
-// host: build the four twiddle tables with exact index reduction
+// host: h->dft — the shape of the time axis and the tables of the forms it offers, with exact index reduction
 int elph_dft_build_tables(elph_handle_s *h) {
-    {   // long axes: one Cooley-Tukey split instead of O(L^2) tables (dft_big.hip) — always beyond 1024 slices; from 401 (where the matrix-core
-        // forms end) to 1024 when the length has a divisor >= 4 below its square root: measured (round 6, profiles/r06/long_time_axes_split_from_401.log,
-        // 16 x 16 sites, KPM apply of 16 right-hand sides): 480 slices 298 -> 219 us, 512: 350 -> 238, 800: 815 -> 394, 1000: 1328 -> 512 against the
-        // scalar-twiddle kernels
-        bool big = h->L > 1024;
-        if (h->L > 400 && !big) {
-            long long best = 0;
-            for (long long f = 2; f * f <= h->L; ++f) if (h->L % f == 0) best = f;
-            big = best >= 4;
+    DftState &D = h->dft;
+    D.shape = dft_shape(h->L);
+    {
+        std::vector<double2> theta((size_t)2 * h->L);
+        for (size_t m = 0; m < theta.size(); ++m) {
+            const double a = M_PI * (double)m / (double)h->L;
+            theta[m] = make_double2(cos(a), -sin(a));
         }
-        if (big) return elph_dft_big_build_tables(h);
+        RC(elph_dft_upload((void **)&D.theta, theta.data(), theta.size() * sizeof(double2)));
     }
+    if (D.shape.big()) return elph_dft_big_build_tables(h);
     const int L = (int)h->L, Lo2 = (L + 1) / 2, Lh = L / 2 + 1;
     const int Lp = dft_pad(L, 2 * DFT_TC), Kp2 = dft_pad(Lo2, 2 * DFT_KC), Kph = dft_pad(Lh, 2 * DFT_KC);
     const double2 zero = make_double2(0.0, 0.0);
@@ -303,11 +321,7 @@ int elph_dft_build_tables(elph_handle_s *h) {
             Pt[(size_t)t * Kph + k] = make_double2(wgt * invL * cos(a), wgt * invL * sin(a));
         }
     }
-    struct { double2 **d; std::vector<double2> *v; } tabs[] = {{&h->d_Tk, &Tk}, {&h->d_Tt, &Tt}, {&h->d_Pk, &Pk}, {&h->d_Pt, &Pt}};
-    for (auto &tb : tabs) {
-        if (*tb.d) { HIPCHK(hipFree(*tb.d)); *tb.d = nullptr; }
-        HIPCHK(hipMalloc((void **)tb.d, tb.v->size() * sizeof(double2)));
-        HIPCHK(hipMemcpy(*tb.d, tb.v->data(), tb.v->size() * sizeof(double2), hipMemcpyHostToDevice));
-    }
+    struct { double2 **d; std::vector<double2> *v; } tabs[] = {{&D.Tk, &Tk}, {&D.Tt, &Tt}, {&D.Pk, &Pk}, {&D.Pt, &Pt}};
+    for (auto &tb : tabs) RC(elph_dft_upload((void **)tb.d, tb.v->data(), tb.v->size() * sizeof(double2)));
     return elph_dft_mfma_build_tables(h);
 }

@@ -269,135 +269,104 @@ __global__ void __launch_bounds__(WAVE) k_big_s2(double2 *__restrict__ nu, doubl
 
 int ensure_work(elph_handle_s *h, int N, int nvec) {
     const size_t need = (size_t)nvec * (size_t)h->L * (size_t)N;
-    if (need <= h->big_cap) return ELPH_OK;
+    if (need <= h->dft.big_cap) return ELPH_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_big_a) { HIPCHK(hipFree(h->d_big_a)); h->d_big_a = nullptr; }
-    if (h->d_big_b) { HIPCHK(hipFree(h->d_big_b)); h->d_big_b = nullptr; }
-    HIPCHK(hipMalloc((void **)&h->d_big_a, need * sizeof(double2)));
-    HIPCHK(hipMalloc((void **)&h->d_big_b, need * sizeof(double2)));
-    h->big_cap = need;
+    if (h->dft.big_a) { HIPCHK(hipFree(h->dft.big_a)); h->dft.big_a = nullptr; }
+    if (h->dft.big_b) { HIPCHK(hipFree(h->dft.big_b)); h->dft.big_b = nullptr; }
+    HIPCHK(hipMalloc((void **)&h->dft.big_a, need * sizeof(double2)));
+    HIPCHK(hipMalloc((void **)&h->dft.big_b, need * sizeof(double2)));
+    h->dft.big_cap = need;
     return ELPH_OK;
 }
 
-// full complex transform of nvec vectors of N columns: result in h->d_big_a (input in h->d_big_a, scratch h->d_big_b)
+// full complex transform of nvec vectors of N columns: result in h->dft.big_a (input in h->dft.big_a, scratch h->dft.big_b)
 template <bool INV>
 int big_fft(elph_handle_s *h, int N, int nvec) {
-    const int L = (int)h->L, L1 = h->big_L1, L2 = h->big_L2, nst = (N + WAVE - 1) / WAVE;
+    const int L = (int)h->L, L1 = h->dft.shape.L1, L2 = h->dft.shape.L2, nst = (N + WAVE - 1) / WAVE;
     const dim3 grid((unsigned)nst, (unsigned)L, (unsigned)nvec);
     if (L2 == 1) {                                        // no split: direct transform, result back into d_big_a
-        hipLaunchKernelGGL((k_big_direct<INV>), grid, dim3(WAVE), 0, h->stream, h->d_big_b, h->d_big_a, h->d_big_TW, N, L, INV ? 1.0 / (double)L : 1.0);
-        hipError_t e = hipMemcpyAsync(h->d_big_a, h->d_big_b, (size_t)nvec * L * N * sizeof(double2), hipMemcpyDeviceToDevice, h->stream);
+        hipLaunchKernelGGL((k_big_direct<INV>), grid, dim3(WAVE), 0, h->stream, h->dft.big_b, h->dft.big_a, h->dft.big_TW, N, L, INV ? 1.0 / (double)L : 1.0);
+        hipError_t e = hipMemcpyAsync(h->dft.big_a, h->dft.big_b, (size_t)nvec * L * N * sizeof(double2), hipMemcpyDeviceToDevice, h->stream);
         if (e != hipSuccess) { elph_set_error("dft_big: copy: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
         return elph_launch_check(INV ? "k_big_direct(inverse)" : "k_big_direct(forward)");
     }
-    hipLaunchKernelGGL((k_big_step1<INV>), grid, dim3(WAVE), 0, h->stream, h->d_big_b, h->d_big_a, h->d_big_W1, h->d_big_TW, N, L, L1, L2);
-    hipLaunchKernelGGL((k_big_step2<INV>), grid, dim3(WAVE), 0, h->stream, h->d_big_a, h->d_big_b, h->d_big_W2, N, L, L1, L2,
+    hipLaunchKernelGGL((k_big_step1<INV>), grid, dim3(WAVE), 0, h->stream, h->dft.big_b, h->dft.big_a, h->dft.big_W1, h->dft.big_TW, N, L, L1, L2);
+    hipLaunchKernelGGL((k_big_step2<INV>), grid, dim3(WAVE), 0, h->stream, h->dft.big_a, h->dft.big_b, h->dft.big_W2, N, L, L1, L2,
                        INV ? 1.0 / (double)L : 1.0);
     return elph_launch_check(INV ? "big_fft(inverse)" : "big_fft(forward)");
 }
 
 }  // namespace
 
-bool elph_dft_big(const elph_handle_s *h) { return h->big_L1 > 0; }
-
-// host: factor L and build W1, W2, TW, Theta (exact index reduction, as in dft.hip)
+// host: W1, W2, TW of the split h->dft.shape chose (exact index reduction, as in dft.hip); Theta_t = exp(-i pi t / L) is h->dft.theta
 int elph_dft_big_build_tables(elph_handle_s *h) {
-    const int L = (int)h->L;
-    h->big_L1 = h->big_L2 = 0;
-    int best = 0;
-    for (int f = 2; (long long)f * f <= L; ++f)
-        if (L % f == 0 && L / f <= 1024) best = f;            // the largest divisor <= sqrt(L) whose cofactor fits
-    // no such split (a prime, or a prime factor beyond 1024): L1 = L, L2 = 1 selects the direct transform (k_big_direct)
-    const bool split = best >= 2;
-    const int L1 = split ? best : L, L2 = split ? L / best : 1;
-    std::vector<double2> W1(split ? (size_t)L1 * L1 : 1), W2((size_t)L2 * L2), TW((size_t)L), TH((size_t)L);
+    const int L = (int)h->L, L1 = h->dft.shape.L1, L2 = h->dft.shape.L2;
+    const bool split = L2 > 1;
+    std::vector<double2> W1(split ? (size_t)L1 * L1 : 1), W2((size_t)L2 * L2), TW((size_t)L);
     for (int c = 0; split && c < L1; ++c)
         for (int a = 0; a < L1; ++a) { const double x = 2.0 * M_PI * (double)(((long long)c * a) % L1) / (double)L1; W1[(size_t)c * L1 + a] = make_double2(cos(x), -sin(x)); }
     for (int d = 0; d < L2; ++d)
         for (int b = 0; b < L2; ++b) { const double x = 2.0 * M_PI * (double)(((long long)d * b) % L2) / (double)L2; W2[(size_t)d * L2 + b] = make_double2(cos(x), -sin(x)); }
     for (int n = 0; n < L; ++n) {
-        const double x = 2.0 * M_PI * (double)n / (double)L, y = M_PI * (double)n / (double)L;
+        const double x = 2.0 * M_PI * (double)n / (double)L;
         TW[(size_t)n] = make_double2(cos(x), -sin(x));
-        TH[(size_t)n] = make_double2(cos(y), -sin(y));        // Theta_t = exp(-i pi t / L)
     }
-    struct { double2 **d; std::vector<double2> *v; } tabs[] = {{&h->d_big_W1, &W1}, {&h->d_big_W2, &W2}, {&h->d_big_TW, &TW}, {&h->d_big_TH, &TH}};
-    for (auto &tb : tabs) {
-        if (*tb.d) { HIPCHK(hipFree(*tb.d)); *tb.d = nullptr; }
-        HIPCHK(hipMalloc((void **)tb.d, tb.v->size() * sizeof(double2)));
-        HIPCHK(hipMemcpy(*tb.d, tb.v->data(), tb.v->size() * sizeof(double2), hipMemcpyHostToDevice));
-    }
-    h->big_L1 = L1; h->big_L2 = L2;
+    struct { double2 **d; std::vector<double2> *v; } tabs[] = {{&h->dft.big_W1, &W1}, {&h->dft.big_W2, &W2}, {&h->dft.big_TW, &TW}};
+    for (auto &tb : tabs) RC(elph_dft_upload((void **)tb.d, tb.v->data(), tb.v->size() * sizeof(double2)));
     return ELPH_OK;
 }
 
-void elph_dft_big_free(elph_handle_s *h) {
-    double2 **p[] = {&h->d_big_W1, &h->d_big_W2, &h->d_big_TW, &h->d_big_TH, &h->d_big_a, &h->d_big_b};
-    for (auto q : p) if (*q) { (void)hipFree(*q); *q = nullptr; }
-    h->big_cap = 0; h->big_L1 = h->big_L2 = 0;
-}
-
-// nu[vec][k][s], k < K: K = ceil(L/2) (twisted) or L/2 + 1 (plain)
-// Which form: the blocked pair has BT times fewer waves — a batch of one or two right-hand sides does not fill the chip with them and is latency-bound
-// (measured, profiles/r06/long_time_axes_blocked_transforms.log: 16 x 16 sites, 1000 slices, ONE right-hand side 29 -> 40 us per transform; 16: 224 -> 113;
-// 64: 1152 -> 358), so it runs from 16384 one-row waves on.  ELPH_DFT_BIG_BLOCKED=0 / 1: never / always (A/B, tests; read per call)
-static bool blocked_form(const elph_handle_s *h, int N, int nvec) {
-    if (h->big_L2 <= 1) return false;
-    const char *e = getenv("ELPH_DFT_BIG_BLOCKED");
-    if (e) return e[0] != '0';
-    return (long long)nvec * ((N + WAVE - 1) / WAVE) * h->L >= 16384;
-}
-
-int elph_dft_big_fwd(elph_handle_s *h, bool twisted, double2 *nu, const double *vS, int N, int nvec) {
+// nu[vec][k][s], k < K: K = ceil(L/2) (twisted) or L/2 + 1 (plain); form: DFT_BIG_BLOCKED the register-blocked pair, else one output row per wave
+int elph_dft_big_fwd(elph_handle_s *h, DftForm form, bool twisted, double2 *nu, const double *vS, int N, int nvec) {
     const int L = (int)h->L, K = twisted ? (L + 1) / 2 : L / 2 + 1;
     RC(ensure_work(h, N, nvec));
-    if (blocked_form(h, N, nvec)) {
-        const int L1 = h->big_L1, L2 = h->big_L2, nst = (N + WAVE - 1) / WAVE;
+    if (form == DFT_BIG_BLOCKED) {
+        const int L1 = h->dft.shape.L1, L2 = h->dft.shape.L2, nst = (N + WAVE - 1) / WAVE;
         const dim3 g1((unsigned)nst, (unsigned)(((L1 + BT - 1) / BT) * L2), (unsigned)nvec), g2((unsigned)nst, (unsigned)(((L2 + BT - 1) / BT) * L1), (unsigned)nvec);
         if (twisted) {
-            hipLaunchKernelGGL((k_big_s1<false, true>), g1, dim3(WAVE), 0, h->stream, h->d_big_b, vS, (const double2 *)nullptr, h->d_big_W1, h->d_big_TW, h->d_big_TH, N, L, L1, L2, K);
-            hipLaunchKernelGGL((k_big_s2<false, true>), g2, dim3(WAVE), 0, h->stream, nu, (double *)nullptr, h->d_big_b, h->d_big_W2, h->d_big_TH, N, L, L1, L2, K, 1.0, (const double *)nullptr, (double *)nullptr, 0);
+            hipLaunchKernelGGL((k_big_s1<false, true>), g1, dim3(WAVE), 0, h->stream, h->dft.big_b, vS, (const double2 *)nullptr, h->dft.big_W1, h->dft.big_TW, h->dft.theta, N, L, L1, L2, K);
+            hipLaunchKernelGGL((k_big_s2<false, true>), g2, dim3(WAVE), 0, h->stream, nu, (double *)nullptr, h->dft.big_b, h->dft.big_W2, h->dft.theta, N, L, L1, L2, K, 1.0, (const double *)nullptr, (double *)nullptr, 0);
         } else {
-            hipLaunchKernelGGL((k_big_s1<false, false>), g1, dim3(WAVE), 0, h->stream, h->d_big_b, vS, (const double2 *)nullptr, h->d_big_W1, h->d_big_TW, h->d_big_TH, N, L, L1, L2, K);
-            hipLaunchKernelGGL((k_big_s2<false, false>), g2, dim3(WAVE), 0, h->stream, nu, (double *)nullptr, h->d_big_b, h->d_big_W2, h->d_big_TH, N, L, L1, L2, K, 1.0, (const double *)nullptr, (double *)nullptr, 0);
+            hipLaunchKernelGGL((k_big_s1<false, false>), g1, dim3(WAVE), 0, h->stream, h->dft.big_b, vS, (const double2 *)nullptr, h->dft.big_W1, h->dft.big_TW, h->dft.theta, N, L, L1, L2, K);
+            hipLaunchKernelGGL((k_big_s2<false, false>), g2, dim3(WAVE), 0, h->stream, nu, (double *)nullptr, h->dft.big_b, h->dft.big_W2, h->dft.theta, N, L, L1, L2, K, 1.0, (const double *)nullptr, (double *)nullptr, 0);
         }
         return elph_launch_check("k_big_s1/s2(forward)");
     }
     const long long total = (long long)nvec * L * N;
-    if (twisted) hipLaunchKernelGGL((k_big_load<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_big_a, vS, h->d_big_TH, N, L, total);
-    else hipLaunchKernelGGL((k_big_load<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_big_a, vS, h->d_big_TH, N, L, total);
+    if (twisted) hipLaunchKernelGGL((k_big_load<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->dft.big_a, vS, h->dft.theta, N, L, total);
+    else hipLaunchKernelGGL((k_big_load<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->dft.big_a, vS, h->dft.theta, N, L, total);
     RC(big_fft<false>(h, N, nvec));
     const long long th = (long long)nvec * K * N;
-    hipLaunchKernelGGL(k_big_take, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, h->stream, nu, h->d_big_a, N, L, K, th);
+    hipLaunchKernelGGL(k_big_take, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, h->stream, nu, h->dft.big_a, N, L, K, th);
     return elph_launch_check("k_big_take");
 }
 
-int elph_dft_big_inv(elph_handle_s *h, bool twisted, double *outS, const double2 *nu, int N, int nvec, const double *rvec,
+int elph_dft_big_inv(elph_handle_s *h, DftForm form, bool twisted, double *outS, const double2 *nu, int N, int nvec, const double *rvec,
                      double *rz_part, int nrz) {
     const int L = (int)h->L, K = twisted ? (L + 1) / 2 : L / 2 + 1;
-    if (rz_part && nrz < L) { elph_set_error("dft_big: %d partial slots needed, %d available", L, nrz); return ELPH_E_STATE; }
     RC(ensure_work(h, N, nvec));
     {
         const int nst = (N + WAVE - 1) / WAVE;
-        if (blocked_form(h, N, nvec) && (!rz_part || nrz >= L * nst)) {
-            const int L1 = h->big_L1, L2 = h->big_L2;
+        if (form == DFT_BIG_BLOCKED) {
+            const int L1 = h->dft.shape.L1, L2 = h->dft.shape.L2;
             const dim3 g1((unsigned)nst, (unsigned)(((L1 + BT - 1) / BT) * L2), (unsigned)nvec), g2((unsigned)nst, (unsigned)(((L2 + BT - 1) / BT) * L1), (unsigned)nvec);
             const double scale = 1.0 / (double)L;
             if (twisted) {
-                hipLaunchKernelGGL((k_big_s1<true, true>), g1, dim3(WAVE), 0, h->stream, h->d_big_b, (const double *)nullptr, nu, h->d_big_W1, h->d_big_TW, h->d_big_TH, N, L, L1, L2, K);
-                hipLaunchKernelGGL((k_big_s2<true, true>), g2, dim3(WAVE), 0, h->stream, (double2 *)nullptr, outS, h->d_big_b, h->d_big_W2, h->d_big_TH, N, L, L1, L2, K, scale, rvec, rz_part, nrz);
+                hipLaunchKernelGGL((k_big_s1<true, true>), g1, dim3(WAVE), 0, h->stream, h->dft.big_b, (const double *)nullptr, nu, h->dft.big_W1, h->dft.big_TW, h->dft.theta, N, L, L1, L2, K);
+                hipLaunchKernelGGL((k_big_s2<true, true>), g2, dim3(WAVE), 0, h->stream, (double2 *)nullptr, outS, h->dft.big_b, h->dft.big_W2, h->dft.theta, N, L, L1, L2, K, scale, rvec, rz_part, nrz);
             } else {
-                hipLaunchKernelGGL((k_big_s1<true, false>), g1, dim3(WAVE), 0, h->stream, h->d_big_b, (const double *)nullptr, nu, h->d_big_W1, h->d_big_TW, h->d_big_TH, N, L, L1, L2, K);
-                hipLaunchKernelGGL((k_big_s2<true, false>), g2, dim3(WAVE), 0, h->stream, (double2 *)nullptr, outS, h->d_big_b, h->d_big_W2, h->d_big_TH, N, L, L1, L2, K, scale, rvec, rz_part, nrz);
+                hipLaunchKernelGGL((k_big_s1<true, false>), g1, dim3(WAVE), 0, h->stream, h->dft.big_b, (const double *)nullptr, nu, h->dft.big_W1, h->dft.big_TW, h->dft.theta, N, L, L1, L2, K);
+                hipLaunchKernelGGL((k_big_s2<true, false>), g2, dim3(WAVE), 0, h->stream, (double2 *)nullptr, outS, h->dft.big_b, h->dft.big_W2, h->dft.theta, N, L, L1, L2, K, scale, rvec, rz_part, nrz);
             }
             return elph_launch_check("k_big_s1/s2(inverse)");
         }
     }
     const long long total = (long long)nvec * L * N;
-    if (twisted) hipLaunchKernelGGL((k_big_expand<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_big_a, nu, N, L, K, total);
-    else hipLaunchKernelGGL((k_big_expand<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_big_a, nu, N, L, K, total);
+    if (twisted) hipLaunchKernelGGL((k_big_expand<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->dft.big_a, nu, N, L, K, total);
+    else hipLaunchKernelGGL((k_big_expand<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->dft.big_a, nu, N, L, K, total);
     RC(big_fft<true>(h, N, nvec));
     const dim3 grid((unsigned)L, (unsigned)nvec);
-    if (twisted) hipLaunchKernelGGL((k_big_store<true>), grid, dim3(WAVE), 0, h->stream, outS, h->d_big_a, h->d_big_TH, N, L, rvec, rz_part, nrz);
-    else hipLaunchKernelGGL((k_big_store<false>), grid, dim3(WAVE), 0, h->stream, outS, h->d_big_a, h->d_big_TH, N, L, rvec, rz_part, nrz);
+    if (twisted) hipLaunchKernelGGL((k_big_store<true>), grid, dim3(WAVE), 0, h->stream, outS, h->dft.big_a, h->dft.theta, N, L, rvec, rz_part, nrz);
+    else hipLaunchKernelGGL((k_big_store<false>), grid, dim3(WAVE), 0, h->stream, outS, h->dft.big_a, h->dft.theta, N, L, rvec, rz_part, nrz);
     return elph_launch_check("k_big_store");
 }

@@ -673,58 +673,40 @@ int pick_nt_r2(int need) {
     return 0;
 }
 
-bool r2_enabled() {
-    const char *e = getenv("ELPH_DFT_R2");         // read per call (tests compare both forms)
-    return !(e && atoi(e) == 0);
-}
-
 int pick_nt(int need) {
     for (int c : NT_CAND) if (need <= c) return c;
     return 0;
 }
 
-template <bool INV>
-int launch(elph_handle_s *h, int nt, double *out, const double *in, const double *W, int N, int K, int groups, int nrhs,
+// ONE: k_dft_mfma_1, grid y = row tiles; else k_dft_mfma, grid y = row groups
+template <bool INV, bool ONE>
+int launch(elph_handle_s *h, int nt, double *out, const double *in, const double *W, int N, int K, int rows, int nrhs,
            const CgState *st, const double *rvec, double *rz_part, int nrz) {
-    const int nct = (N + 15) / 16;
-    const dim3 grid((unsigned)((nct + CW - 1) / CW), (unsigned)groups, (unsigned)nrhs), block(CW * WAVE);
-    const int L = (int)h->L;
-#define MF_CASE(NTV) case NTV: hipLaunchKernelGGL((k_dft_mfma<NTV, INV>), grid, block, 0, h->stream, out, in, W, N, L, K, st, rvec, rz_part, nrz); break;
+    constexpr int cw = ONE ? CW1 : CW;
+    const int nct = (N + 15) / 16, L = (int)h->L;
+    const dim3 grid((unsigned)((nct + cw - 1) / cw), (unsigned)rows, (unsigned)nrhs), block(cw * WAVE);
+#define MF_CASE(NTV) case NTV: hipLaunchKernelGGL((ONE ? k_dft_mfma_1<NTV, INV> : k_dft_mfma<NTV, INV>), grid, block, 0, h->stream, out, in, W, N, L, K, st, rvec, rz_part, nrz); break;
     switch (nt) {
         MF_CASE(12) MF_CASE(20) MF_CASE(32) MF_CASE(40) MF_CASE(44) MF_CASE(64)
         default: elph_set_error("dft_mfma: no kernel for %d reduction tiles", nt); return ELPH_E_UNSUPPORTED;
     }
 #undef MF_CASE
-    return elph_launch_check(INV ? "k_dft_mfma(inverse)" : "k_dft_mfma(forward)");
-}
-
-template <bool INV>
-int launch_1(elph_handle_s *h, int nt, double *out, const double *in, const double *W, int N, int K, int row_tiles, int nrhs,
-             const CgState *st, const double *rvec, double *rz_part, int nrz) {
-    const int nct = (N + 15) / 16;
-    const dim3 grid((unsigned)((nct + CW1 - 1) / CW1), (unsigned)row_tiles, (unsigned)nrhs), block(CW1 * WAVE);
-    const int L = (int)h->L;
-#define MF1_CASE(NTV) case NTV: hipLaunchKernelGGL((k_dft_mfma_1<NTV, INV>), grid, block, 0, h->stream, out, in, W, N, L, K, st, rvec, rz_part, nrz); break;
-    switch (nt) {
-        MF1_CASE(12) MF1_CASE(20) MF1_CASE(32) MF1_CASE(40) MF1_CASE(44) MF1_CASE(64)
-        default: elph_set_error("dft_mfma_1: no kernel for %d reduction tiles", nt); return ELPH_E_UNSUPPORTED;
-    }
-#undef MF1_CASE
-    return elph_launch_check(INV ? "k_dft_mfma_1(inverse)" : "k_dft_mfma_1(forward)");
+    return elph_launch_check(ONE ? (INV ? "k_dft_mfma_1(inverse)" : "k_dft_mfma_1(forward)") : (INV ? "k_dft_mfma(inverse)" : "k_dft_mfma(forward)"));
 }
 
 template <bool INV, bool XR = false>
-int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, const double *in, int N, int nrhs, const CgState *st,
+int launch_r2(elph_handle_s *h, const DftPlan &T, double *out, const double *in, int N, int nrhs, const CgState *st,
               const double *rvec, double *rz_part, int nrz, XrFuse X = XrFuse{}, PxFuse PXF = PxFuse{}) {
     const int nct = (N + 15) / 16;
     const dim3 grid((unsigned)((nct + CW - 1) / CW), (unsigned)T.groups, (unsigned)nrhs), block(CW * WAVE);
     const int L = (int)h->L;
-    const double2 *tw = reinterpret_cast<const double2 *>(h->d_r2_tw);
+    const double *W = h->dft.W_r2[INV ? 1 : 0];
+    const double2 *tw = reinterpret_cast<const double2 *>(h->dft.r2_tw);
     // streaming form: W panel of a row group in LDS.  Up to 64 KB is the default dynamic-LDS limit; the long time axes
     // (L = 256 ... 400: 80 ... 128 KB of the CU's 160 KB) ask for it explicitly, once per kernel instantiation
-    const size_t panel = (size_t)MG * T.nt * WAVE * sizeof(double);
+    const size_t panel = (size_t)T.lds;
     const size_t shm_s = panel + (X.fold ? (size_t)(L / 2) * 2 * sizeof(double) : 0);      // + the fold table of the chain (forward, XrFuse)
-    if (panel <= 144 * 1024) {
+    if (T.form == DFT_SPLIT_LDS) {
         hipError_t attr_rc = hipSuccess;
 #define R2S_LAUNCH(NTV, RZV, PXV) do {                                                                                         \
             auto kfn = k_dft_mfma_r2s<NTV, INV, XR, RZV, PXV>;                                                                  \
@@ -732,7 +714,7 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
                 static bool raised = false;                                                                                     \
                 if (!raised) { attr_rc = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(panel + 8192)); raised = (attr_rc == hipSuccess); } \
             }                                                                                                                   \
-            if (attr_rc == hipSuccess) hipLaunchKernelGGL(kfn, grid, block, shm_s, h->stream, out, in, T.W, tw, N, L, st, rvec, rz_part, nrz, X, PXF); \
+            if (attr_rc == hipSuccess) hipLaunchKernelGGL(kfn, grid, block, shm_s, h->stream, out, in, W, tw, N, L, st, rvec, rz_part, nrz, X, PXF); \
         } while (0)
 #define R2S_CASE(NTV) case NTV: if (INV && !XR && PXF.p) R2S_LAUNCH(NTV, false, (INV && !XR)); else if (INV && rz_part) R2S_LAUNCH(NTV, INV, false); else R2S_LAUNCH(NTV, false, false); break;
         switch (T.nt) {
@@ -745,7 +727,7 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
         return elph_launch_check(INV ? "k_dft_mfma_r2s(inverse)" : "k_dft_mfma_r2s(forward)");
     }
     if (PXF.p) { elph_set_error("dft_mfma: the p/x-fused inverse exists in the streaming form only"); return ELPH_E_STATE; }
-#define R2_CASE(NTV) case NTV: hipLaunchKernelGGL((k_dft_mfma_r2<NTV, INV, XR>), grid, block, 0, h->stream, out, in, T.W, tw, N, L, st, rvec, rz_part, nrz, X); break;
+#define R2_CASE(NTV) case NTV: hipLaunchKernelGGL((k_dft_mfma_r2<NTV, INV, XR>), grid, block, 0, h->stream, out, in, W, tw, N, L, st, rvec, rz_part, nrz, X); break;
     switch (T.nt) {
         R2_CASE(5) R2_CASE(10) R2_CASE(15) R2_CASE(20) R2_CASE(25) R2_CASE(32)
         default: elph_set_error("dft_mfma_r2: no register-resident kernel for %d reduction tiles (panels beyond 144 KB need L <= 256)", T.nt); return ELPH_E_UNSUPPORTED;
@@ -756,104 +738,166 @@ int launch_r2(elph_handle_s *h, const elph_handle_s::MfmaTab &T, double *out, co
 
 }  // namespace
 
-// which: 0 twisted, 1 plain
-bool elph_dft_mfma_usable(const elph_handle_s *h, int which, bool inverse, int N, int nrhs) {
-    const char *e = getenv("ELPH_DFT_MFMA");       // read per call: tests switch both ways inside one process
-    const int force = e ? atoi(e) : -1;
-    if (force == 0) return false;
-    const elph_handle_s::MfmaTab &T = h->mf[which][inverse ? 1 : 0];
-    const bool split = which == 0 && h->mf_r2[inverse ? 1 : 0].W && r2_enabled();      // exists up to L = 400, the direct form to 256
-    if (!T.W && !split) return false;
-    if (force == 1) return true;
-    // measured crossover against the scalar-twiddle kernels (tools/time_dft_crossover.py, configs C and D): the split form wins
-    // from ~100 column-tile waves (8 right-hand sides at N = 256), the direct form from ~512 waves; against the
-    // one-tile-per-wave form (k_dft_mfma_1; config C, preconditioned iteration: 54.8 vs 69.9 us at 10 right-hand sides, 71.8 vs
-    // 74.2 at 24, 80.7 vs 76.9 at 32, 100.7 vs 83.5 at 48) from ~450
-    if (split) return (long long)((N + 15) / 16) * nrhs >= (which == 0 && elph_dft_mfma1_usable(h, inverse, N, 0) ? 448 : 100);
-    return (long long)((N + 15) / 16) * T.groups * nrhs >= 512;
+// What the time axis offers: the long-axis split or the tables of the matrix-core forms (host arithmetic only)
+DftShape dft_shape(int64_t L64) {
+    const int L = (int)L64;
+    DftShape S;
+    S.L = L;
+    // long axes: one Cooley-Tukey split instead of O(L^2) tables (dft_big.hip) — always beyond 1024 slices; from 401 (where the matrix-core
+    // forms end) to 1024 when the length has a divisor >= 4 below its square root: measured (round 6, profiles/r06/long_time_axes_split_from_401.log,
+    // 16 x 16 sites, KPM apply of 16 right-hand sides): 480 slices 298 -> 219 us, 512: 350 -> 238, 800: 815 -> 394, 1000: 1328 -> 512 against the
+    // scalar-twiddle kernels
+    int best = 0;
+    for (int f = 2; (long long)f * f <= L; ++f)
+        if (L % f == 0 && L / f <= 1024) best = f;            // the largest divisor <= sqrt(L) whose cofactor fits
+    if (L > 1024 || (L > 400 && best >= 4)) {
+        // no such split (a prime, or a prime factor beyond 1024): L1 = L, L2 = 1 selects the direct transform (k_big_direct)
+        S.L1 = best >= 2 ? best : L;
+        S.L2 = best >= 2 ? L / best : 1;
+        return S;
+    }
+    for (int which = 0; which < 2; ++which) {
+        const int K = which == DFT_TWISTED ? (L + 1) / 2 : L / 2 + 1;
+        for (int inv = 0; inv < 2; ++inv) {
+            const int rows = inv ? L : 2 * K, red = inv ? 2 * K : L;
+            DftTab &T = S.mf[which][inv];
+            T.nt = pick_nt((red + 3) / 4);                    // 0 beyond L = 256: scalar kernels only
+            if (T.nt) T.groups = ((rows + 15) / 16 + MG - 1) / MG;
+        }
+    }
+    if (L % 2 == 0 && L >= 8) {
+        // forward: rows (k < Q, re/im), 8 frequencies per row tile, reduction j < H; inverse: rows j < H, reduction (k < Q, re/im)
+        const int H = L / 2, Q = (H + 1) / 2;
+        for (int inv = 0; inv < 2; ++inv) {
+            DftTab &T = S.r2[inv];
+            T.nt = pick_nt_r2(inv ? (Q + 1) / 2 : (H + 3) / 4);
+            if (T.nt) T.groups = ((inv ? (H + 15) / 16 : (Q + 7) / 8) + MG - 1) / MG;
+        }
+    }
+    return S;
 }
 
-// one output tile per wave: the twisted pair for batches below the crossover of the forms above
-bool elph_dft_mfma1_usable(const elph_handle_s *h, bool inverse, int N, int nrz_slots) {
-    const elph_handle_s::MfmaTab &T = h->mf[0][inverse ? 1 : 0];
-    if (!T.W) return false;
-    return !inverse || nrz_slots <= 0 || ((N + 15) / 16) * T.groups * MG <= nrz_slots;
-}
-int elph_dft_mfma1_fwd(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs, const CgState *st) {
-    const elph_handle_s::MfmaTab &T = h->mf[0][0];
-    return launch_1<false>(h, T.nt, reinterpret_cast<double *>(nu), vS, T.W, N, (int)(h->L + 1) / 2, T.groups * MG, nrhs, st, nullptr, nullptr, 0);
-}
-int elph_dft_mfma1_inv(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs, const CgState *st, const double *rvec,
-                       double *rz_part, int nrz) {
-    const elph_handle_s::MfmaTab &T = h->mf[0][1];
-    return launch_1<true>(h, T.nt, outS, reinterpret_cast<const double *>(nu), T.W, N, (int)(h->L + 1) / 2, T.groups * MG, nrhs, st, rvec, rz_part, nrz);
+// read per plan: tests switch both ways inside one process
+DftSwitches dft_switches() {
+    auto num = [](const char *e) { return e ? atoi(e) : -1; };
+    DftSwitches sw;
+    sw.mfma = num(getenv("ELPH_DFT_MFMA"));
+    sw.r2 = num(getenv("ELPH_DFT_R2")) != 0;
+    sw.fuse_xr = num(getenv("ELPH_FUSE_XR")) != 0;
+    sw.fuse_px = num(getenv("ELPH_FUSE_PX")) != 0;
+    const char *b = getenv("ELPH_DFT_BIG_BLOCKED");
+    sw.big_blocked = b ? (b[0] != '0') : -1;
+    return sw;
 }
 
-int elph_dft_mfma_fwd(elph_handle_s *h, int which, double2 *nu, const double *vS, int N, int nrhs, const CgState *st) {
-    if (which == 0 && h->mf_r2[0].W && r2_enabled())
-        return launch_r2<false>(h, h->mf_r2[0], reinterpret_cast<double *>(nu), vS, N, nrhs, st, nullptr, nullptr, 0);
-    const elph_handle_s::MfmaTab &T = h->mf[which][0];
-    const int K = which == 0 ? (int)(h->L + 1) / 2 : (int)h->L / 2 + 1;
-    return launch<false>(h, T.nt, reinterpret_cast<double *>(nu), vS, T.W, N, K, T.groups, nrhs, st, nullptr, nullptr, 0);
-}
+// the W panel of a row group that the streaming split form stages in LDS (of the CU's 160 KB); beyond it the data stay in registers
+constexpr size_t DFT_PANEL_MAX = 144 * 1024;
 
-// whether launch_r2<false> takes the streaming form (the one that knows the order-1 fold)
-bool elph_dft_mfma_fold_usable(const elph_handle_s *h) {
-    const elph_handle_s::MfmaTab &T = h->mf_r2[0];
-    if (!T.W || !r2_enabled() || T.groups != 1 || (h->L & 1)) return false;
+DftPlan elph_dft_split_plan(const DftShape &S, bool inverse) {
+    const DftTab &T = S.r2[inverse ? 1 : 0];
     const size_t panel = (size_t)MG * T.nt * WAVE * sizeof(double);
-    return panel <= 144 * 1024;
+    DftPlan p;
+    p.form = panel <= DFT_PANEL_MAX ? DFT_SPLIT_LDS : DFT_SPLIT_REG;
+    p.nt = T.nt;
+    p.groups = T.groups;
+    p.lds = p.form == DFT_SPLIT_LDS ? (int)panel : 0;
+    return p;
 }
 
-// forward twisted transform of r - alpha z with the residual update of k_cg_xr folded in (see XrFuse); usable: see below
-bool elph_dft_mfma_xr_usable(const elph_handle_s *h, int N, int nrhs) {
-    const char *e = getenv("ELPH_FUSE_XR");
-    if (e && atoi(e) == 0) return false;
-    // r.r partial slots: one per column tile where the time axis has that many (L slots per right-hand side), else — streaming form only —
-    // one per workgroup of CW tiles (round 6: large lattices on short time axes)
-    const int nct = (N + 15) / 16;
-    const size_t panel = (size_t)MG * h->mf_r2[0].nt * WAVE * sizeof(double);
-    const bool streaming = panel <= 144 * 1024;
-    const bool slots_ok = nct <= (int)h->L || (streaming && (nct + CW - 1) / CW <= (int)h->L);
-    return h->mf_r2[0].W && r2_enabled() && elph_dft_mfma_usable(h, 0, false, N, nrhs) && slots_ok &&
-           h->mf_r2[0].groups == 1;           // one row group: every element of r belongs to exactly one wave
+// The form of one transform of nvec vectors of N columns.  ELPH_DFT_MFMA=1 overrides the crossovers, not the existence of tables; =0 still
+// leaves the one-tile form for the twisted pair.  ELPH_DFT_BIG_BLOCKED=0 / 1: never / always the blocked long-axis pair (A/B, tests).
+DftPlan elph_plan_dft(const DftShape &S, const DftSwitches &sw, int which, bool inverse, int N, int nvec, int nrz_slots) {
+    const int L = S.L, d = inverse ? 1 : 0, nct = (N + 15) / 16, nst = (N + WAVE - 1) / WAVE;
+    const bool rz = inverse && which == DFT_TWISTED && nrz_slots > 0;      // the plain transforms deliver no r.z
+    DftPlan p;
+    if (S.big()) {
+        // the blocked pair has 8 times fewer waves — a batch of one or two right-hand sides does not fill the chip with them and is latency-bound
+        // (measured, profiles/r06/long_time_axes_blocked_transforms.log: 16 x 16 sites, 1000 slices, ONE right-hand side 29 -> 40 us per transform;
+        // 16: 224 -> 113; 64: 1152 -> 358), so it runs from 16384 one-row waves on; its r.z takes a slot per (time slice, site tile)
+        const bool blocked = S.L2 > 1 && (sw.big_blocked >= 0 ? sw.big_blocked != 0 : (long long)nvec * nst * L >= 16384);
+        p.form = (blocked && (!rz || nrz_slots >= L * nst)) ? DFT_BIG_BLOCKED : S.L2 == 1 ? DFT_BIG_DIRECT : DFT_BIG_ROW;
+        p.slots = !rz ? 0 : p.form == DFT_BIG_BLOCKED ? L * nst : L;
+    } else {
+        const DftTab &T = S.mf[which][d];
+        const bool split = which == DFT_TWISTED && S.r2[d].nt && sw.r2;      // exists up to L = 400, the direct form to 256
+        const bool one_tile = which == DFT_TWISTED && T.nt;
+        // measured crossover against the scalar-twiddle kernels (tools/time_dft_crossover.py, configs C and D): the split form wins
+        // from ~100 column-tile waves (8 right-hand sides at N = 256), the direct form from ~512 waves; against the
+        // one-tile-per-wave form (k_dft_mfma_1; config C, preconditioned iteration: 54.8 vs 69.9 us at 10 right-hand sides, 71.8 vs
+        // 74.2 at 24, 80.7 vs 76.9 at 32, 100.7 vs 83.5 at 48) from ~450
+        bool mc = sw.mfma != 0 && (T.nt || split);
+        if (mc && sw.mfma != 1) mc = split ? (long long)nct * nvec >= (one_tile ? 448 : 100) : (long long)nct * T.groups * nvec >= 512;
+        if (mc) {
+            if (split) p = elph_dft_split_plan(S, inverse);
+            else { p.form = DFT_DIRECT; p.nt = T.nt; p.groups = T.groups; }
+            p.slots = rz ? nct * p.groups : 0;
+        } else if (one_tile && (!rz || nct * T.groups * MG <= nrz_slots)) {
+            p.form = DFT_ONE_TILE; p.nt = T.nt; p.groups = T.groups;
+            p.slots = rz ? nct * T.groups * MG : 0;
+        } else {
+            p.slots = rz ? nst * ((L + ELPH_DFT_TPT - 1) / ELPH_DFT_TPT) : 0;
+        }
+        if (split && S.r2[d].groups == 1 && !(L & 1)) {      // one row group: every element of r (p, x) belongs to exactly one lane
+            const bool lds = elph_dft_split_plan(S, inverse).form == DFT_SPLIT_LDS;
+            // XR's r.r partial slots: one per column tile where the time axis has that many (L slots per right-hand side), else — streaming form
+            // only — one per workgroup of CW tiles (round 6: large lattices on short time axes)
+            p.xr = !inverse && mc && sw.fuse_xr && (nct <= L || (lds && (nct + CW - 1) / CW <= L));
+            p.px = inverse && mc && sw.fuse_px && lds;      // the p/x-fused inverse exists in the streaming form only
+            p.fold = !inverse && lds;                       // ... as does the order-1 fold; it reads no batch size
+        }
+    }
+    p.short_slots = rz && p.form != DFT_SCALAR && p.slots > nrz_slots;
+    return p;
 }
 
+void elph_dft_pair(DftPlan &fwd, DftPlan &inv) {
+    if ((fwd.form == DFT_DIRECT) != (inv.form == DFT_DIRECT)) fwd = inv = DftPlan{};
+}
+
+void elph_i_dft_plan_probe(const DftShape &S, int which, bool inverse, int N, int nvec, int nrz_slots, int *out) {
+    const DftSwitches sw = dft_switches();
+    const DftPlan p = elph_plan_dft(S, sw, which, inverse, N, nvec, nrz_slots);
+    DftPlan pair[2] = {p, p};
+    if (which == DFT_PLAIN) {
+        pair[0] = elph_plan_dft(S, sw, which, false, N, nvec, 0);
+        pair[1] = elph_plan_dft(S, sw, which, true, N, nvec, 0);
+        elph_dft_pair(pair[0], pair[1]);
+    }
+    const int v[] = {p.form, p.nt, p.groups, p.lds, p.slots, p.xr, p.px, p.fold, p.short_slots, pair[inverse ? 1 : 0].form};
+    std::copy(std::begin(v), std::end(v), out);
+}
+
+int elph_dft_mfma_run(elph_handle_s *h, const DftPlan &p, int which, bool inverse, double *out, const double *in, int N, int nrhs,
+                      const CgState *st, const double *rvec, double *rz_part, int nrz) {
+    const int L = (int)h->L, K = which == DFT_TWISTED ? (L + 1) / 2 : L / 2 + 1;
+    const double *W = h->dft.W[which][inverse ? 1 : 0];
+    switch (p.form) {
+    case DFT_ONE_TILE:
+        return (inverse ? launch<true, true> : launch<false, true>)(h, p.nt, out, in, W, N, K, p.groups * MG, nrhs, st, rvec, rz_part, nrz);
+    case DFT_DIRECT:
+        return (inverse ? launch<true, false> : launch<false, false>)(h, p.nt, out, in, W, N, K, p.groups, nrhs, st, rvec, rz_part, nrz);
+    case DFT_SPLIT_REG: case DFT_SPLIT_LDS:
+        return inverse ? launch_r2<true>(h, p, out, in, N, nrhs, st, rvec, rz_part, nrz) : launch_r2<false>(h, p, out, in, N, nrhs, st, rvec, rz_part, nrz);
+    default:
+        elph_set_error("dft_mfma: not a matrix-core form (%d)", (int)p.form);
+        return ELPH_E_STATE;
+    }
+}
+
+// forward twisted transform of r - alpha z with the residual update of k_cg_xr folded in (see XrFuse); planned: DftPlan::xr
 int elph_dft_mfma_fwd_xr(elph_handle_s *h, double2 *nu, double *rS, const double *zS, const double *pap, int npap, double *rr,
                          double *alpha, int N, int nrhs, const CgState *st, const double *fold, int fold_nch, double *frz, int fnrz,
                          int fslot0) {
     XrFuse X{zS, rS, pap, rr, alpha, npap, (int)h->L, fold, frz, fold_nch, fnrz, fslot0};
-    return launch_r2<false, true>(h, h->mf_r2[0], reinterpret_cast<double *>(nu), rS, N, nrhs, st, nullptr, nullptr, 0, X);
+    return launch_r2<false, true>(h, elph_dft_split_plan(h->dft.shape, false), reinterpret_cast<double *>(nu), rS, N, nrhs, st, nullptr, nullptr, 0, X);
 }
 
-int elph_dft_mfma_inv(elph_handle_s *h, int which, double *outS, const double2 *nu, int N, int nrhs, const CgState *st,
-                      const double *rvec, double *rz_part, int nrz) {
-    if (which == 0 && h->mf_r2[1].W && r2_enabled()) {
-        const elph_handle_s::MfmaTab &T2 = h->mf_r2[1];
-        if (rz_part && (int)((N + 15) / 16) * T2.groups > nrz) { elph_set_error("dft_mfma_r2: %d partial slots needed, %d available", ((N + 15) / 16) * T2.groups, nrz); return ELPH_E_STATE; }
-        return launch_r2<true>(h, T2, outS, reinterpret_cast<const double *>(nu), N, nrhs, st, rvec, rz_part, nrz);
-    }
-    const elph_handle_s::MfmaTab &T = h->mf[which][1];
-    const int K = which == 0 ? (int)(h->L + 1) / 2 : (int)h->L / 2 + 1;
-    if (rz_part && (int)((N + 15) / 16) * T.groups > nrz) { elph_set_error("dft_mfma: %d partial slots needed, %d available", ((N + 15) / 16) * T.groups, nrz); return ELPH_E_STATE; }
-    return launch<true>(h, T.nt, outS, reinterpret_cast<const double *>(nu), T.W, N, K, T.groups, nrhs, st, rvec, rz_part, nrz);
-}
-
-// inverse twisted transform with the p- and x-update of the preconditioned CG iteration in its epilogue (PxFuse)
-bool elph_dft_mfma_px_usable(const elph_handle_s *h, int N, int nrhs) {
-    const char *e = getenv("ELPH_FUSE_PX");
-    if (e && atoi(e) == 0) return false;
-    const elph_handle_s::MfmaTab &T = h->mf_r2[1];
-    if (!T.W || !r2_enabled() || T.groups != 1 || (h->L & 1)) return false;       // one row group: every element of p, x belongs to one lane
-    const size_t panel = (size_t)MG * T.nt * WAVE * sizeof(double);
-    return panel <= 144 * 1024 && elph_dft_mfma_usable(h, 0, true, N, nrhs);
-}
-
+// inverse twisted transform with the p- and x-update of the preconditioned CG iteration in its epilogue (PxFuse); planned: DftPlan::px
 int elph_dft_mfma_inv_px(elph_handle_s *h, const double2 *nu, int N, int nrhs, const CgState *st, double *pS, double *xS,
                          const double *alpha, const double *rz, int nrz) {
     if (!st) { elph_set_error("dft_mfma: the p/x-fused inverse needs the CG state"); return ELPH_E_STATE; }
     PxFuse PXF{pS, xS, alpha, rz, nrz};
-    return launch_r2<true>(h, h->mf_r2[1], nullptr, reinterpret_cast<const double *>(nu), N, nrhs, st, nullptr, nullptr, 0, XrFuse{}, PXF);
+    return launch_r2<true>(h, elph_dft_split_plan(h->dft.shape, true), nullptr, reinterpret_cast<const double *>(nu), N, nrhs, st, nullptr, nullptr, 0, XrFuse{}, PXF);
 }
 
 // host: the four W matrices in A-tile order (zero-padded to groups*MG row tiles x nt reduction tiles)
@@ -871,13 +915,10 @@ int elph_dft_mfma_build_tables(elph_handle_s *h) {
             return (k == 0 || 2 * k == L) ? 1.0 : 2.0;
         };
         for (int inv = 0; inv < 2; ++inv) {
-            elph_handle_s::MfmaTab &T = h->mf[which][inv];
-            if (T.W) { HIPCHK(hipFree(T.W)); T.W = nullptr; }
+            const DftTab &T = h->dft.shape.mf[which][inv];
+            if (T.nt == 0) continue;
             const int rows = inv ? L : 2 * K, red = inv ? 2 * K : L;
             const int nmt = (rows + 15) / 16, ntt = (red + 3) / 4;
-            T.nt = pick_nt(ntt);
-            if (T.nt == 0) continue;                       // L > 256: scalar kernels only
-            T.groups = (nmt + MG - 1) / MG;
             const int nmt_pad = T.groups * MG;
             std::vector<double> W((size_t)nmt_pad * T.nt * WAVE, 0.0);
             for (int mt = 0; mt < nmt; ++mt)
@@ -898,23 +939,17 @@ int elph_dft_mfma_build_tables(elph_handle_s *h) {
                         }
                         W[((size_t)mt * T.nt + tt) * WAVE + lane] = val;
                     }
-            HIPCHK(hipMalloc((void **)&T.W, W.size() * sizeof(double)));
-            HIPCHK(hipMemcpy(T.W, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice));
+            RC(elph_dft_upload((void **)&h->dft.W[which][inv], W.data(), W.size() * sizeof(double)));
         }
     }
     // ---- the even/odd split of the twisted transform (L even): half-length tables and the twiddles
-    for (auto &T : h->mf_r2) if (T.W) { HIPCHK(hipFree(T.W)); T.W = nullptr; }
-    if (h->d_r2_tw) { HIPCHK(hipFree(h->d_r2_tw)); h->d_r2_tw = nullptr; }
-    if (L % 2 == 0 && L >= 8) {
+    if (h->dft.shape.r2[0].nt || h->dft.shape.r2[1].nt) {
         const int H = L / 2, Q = (H + 1) / 2;
         auto angle = [&](int k, int j) { const long long m = ((long long)(2 * k + 1) * j) % (2LL * H); return M_PI * (double)m / (double)H; };
         for (int inv = 0; inv < 2; ++inv) {
-            elph_handle_s::MfmaTab &T = h->mf_r2[inv];
-            // forward: rows (k < Q, re/im), 8 frequencies per row tile, reduction j < H; inverse: rows j < H, reduction (k < Q, re/im)
-            const int nmt = inv ? (H + 15) / 16 : (Q + 7) / 8, ntt = inv ? (Q + 1) / 2 : (H + 3) / 4;
-            T.nt = pick_nt_r2(ntt);
+            const DftTab &T = h->dft.shape.r2[inv];
             if (T.nt == 0) continue;
-            T.groups = (nmt + MG - 1) / MG;
+            const int nmt = inv ? (H + 15) / 16 : (Q + 7) / 8, ntt = inv ? (Q + 1) / 2 : (H + 3) / 4;
             const int nmt_pad = T.groups * MG;
             std::vector<double> W((size_t)nmt_pad * T.nt * WAVE, 0.0);
             for (int mt = 0; mt < nmt; ++mt)
@@ -936,8 +971,7 @@ int elph_dft_mfma_build_tables(elph_handle_s *h) {
                         }
                         W[((size_t)mt * T.nt + tt) * WAVE + lane] = val;
                     }
-            HIPCHK(hipMalloc((void **)&T.W, W.size() * sizeof(double)));
-            HIPCHK(hipMemcpy(T.W, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice));
+            RC(elph_dft_upload((void **)&h->dft.W_r2[inv], W.data(), W.size() * sizeof(double)));
         }
         std::vector<double> tw((size_t)2 * H);
         for (int k = 0; k < H; ++k) {
@@ -945,14 +979,7 @@ int elph_dft_mfma_build_tables(elph_handle_s *h) {
             tw[2 * (size_t)k] = cos(a);
             tw[2 * (size_t)k + 1] = -sin(a);
         }
-        HIPCHK(hipMalloc((void **)&h->d_r2_tw, tw.size() * sizeof(double)));
-        HIPCHK(hipMemcpy(h->d_r2_tw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
+        RC(elph_dft_upload((void **)&h->dft.r2_tw, tw.data(), tw.size() * sizeof(double)));
     }
     return ELPH_OK;
-}
-
-void elph_dft_mfma_free(elph_handle_s *h) {
-    for (auto &a : h->mf) for (auto &T : a) if (T.W) { (void)hipFree(T.W); T.W = nullptr; }
-    for (auto &T : h->mf_r2) if (T.W) { (void)hipFree(T.W); T.W = nullptr; }
-    if (h->d_r2_tw) { (void)hipFree(h->d_r2_tw); h->d_r2_tw = nullptr; }
 }

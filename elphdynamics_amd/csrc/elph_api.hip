@@ -429,25 +429,6 @@ extern "C" int elph_create(elph_handle *out, int kind, int64_t nsites, int64_t l
             return fail(ELPH_E_HIP);
         }
     }
-    // twiddles: tw1[m] = exp(-2 pi i m/L), m<L ; tw2[m] = exp(-i pi m/L), m<2L (exact index reduction on host)
-    {
-        std::vector<double2> tw1((size_t)ltau), tw2((size_t)2 * ltau);
-        for (int64_t m = 0; m < ltau; ++m) {
-            const double a = 2.0 * M_PI * (double)m / (double)ltau;
-            tw1[m] = make_double2(cos(a), -sin(a));
-        }
-        for (int64_t m = 0; m < 2 * ltau; ++m) {
-            const double a = M_PI * (double)m / (double)ltau;
-            tw2[m] = make_double2(cos(a), -sin(a));
-        }
-        if ((rc = dev_alloc(&h->d_tw, (size_t)ltau))) return fail(rc);
-        if ((rc = dev_alloc(&h->d_theta, (size_t)2 * ltau))) return fail(rc);
-        if (hipMemcpy(h->d_tw, tw1.data(), sizeof(double2) * tw1.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->d_theta, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            elph_set_error("twiddle upload failed");
-            return fail(ELPH_E_HIP);
-        }
-    }
     if ((rc = elph_dft_build_tables(h))) return fail(rc);
     if ((rc = build_lane_program(h))) return fail(rc);
     if ((rc = upload_lp_cs(h))) return fail(rc);
@@ -465,13 +446,12 @@ extern "C" int elph_destroy(elph_handle h) {
     elph_shard_free(h);
     elph_hmc_free(h);
     elph_greens_free(h);
-    elph_dft_mfma_free(h);
-    elph_dft_big_free(h);
+    elph_dft_free(h);
     elph_kpm_free(h);
     void *ptrs[] = {h->d_bi, h->d_bj, h->d_coloff, h->d_c, h->d_s, h->d_E, h->d_lam, h->d_stage_in, h->d_stage_out,
                     h->d_b, h->d_x, h->d_r, h->d_z, h->d_zp, h->d_p, h->d_tmp, h->d_part, h->d_state, h->d_phi, h->d_xfield,
-                    h->d_hist, h->d_scal, h->d_alpha, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar, h->d_ssh_cb, h->d_ssh_slot, h->d_nu, h->d_tw, h->d_theta, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s,
-                    h->d_Tk, h->d_Tt, h->d_Pk, h->d_Pt, h->d_sq_bond, h->d_pg_bond, h->res.d_res, h->d_mu_ch};
+                    h->d_hist, h->d_scal, h->d_alpha, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar, h->d_ssh_cb, h->d_ssh_slot, h->d_nu, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s,
+                    h->d_sq_bond, h->d_pg_bond, h->res.d_res, h->d_mu_ch};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_scal) (void)hipHostFree(h->h_scal);
@@ -2010,6 +1990,20 @@ extern "C" int elph_bench_wg_plan(int kind, int64_t nsites, int64_t ltau, int64_
     if (kind == ELPH_MODEL_HOLSTEIN) { h.h_c.assign(cosht, cosht + nbonds); h.h_s.assign(sinht, sinht + nbonds); }
     plan_lane_program(&h);
     elph_i_wg_plan_probe(&h, nrhs, world, out);
+    return ELPH_OK;
+}
+
+// the plan of one tau-axis transform (dft_mfma.hip: elph_plan_dft) at Ltau = ltau without a device, and on a handle's own h->dft.shape: the
+// slots of _lib.DFT_PLAN_SLOTS
+extern "C" int elph_bench_dft_plan(int64_t ltau, int which, int inverse, int N, int nvec, int nrz_slots, int *out) {
+    if (!out || ltau < 1 || (which != DFT_TWISTED && which != DFT_PLAIN) || N < 1 || nvec < 1 || nrz_slots < 0) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    elph_i_dft_plan_probe(dft_shape(ltau), which, inverse != 0, N, nvec, nrz_slots, out);
+    return ELPH_OK;
+}
+extern "C" int elph_bench_dft_info(elph_handle h, int which, int inverse, int N, int nvec, int nrz_slots, int *out) {
+    CHECK_H(h);
+    if (!out || (which != DFT_TWISTED && which != DFT_PLAIN) || N < 1 || nvec < 1 || nrz_slots < 0) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    elph_i_dft_plan_probe(h->dft.shape, which, inverse != 0, N, nvec, nrz_slots, out);
     return ELPH_OK;
 }
 

@@ -60,6 +60,17 @@ int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int
 int elph_bench_wg_plan(int kind, int64_t nsites, int64_t ltau, int64_t nbonds, const int64_t *neighbor_table, const double *cosht,
                        const double *sinht, int nrhs, int world, int *out);
 
+/* The plan of one tau-axis transform (dft_mfma.hip: elph_plan_dft) of nvec vectors of N columns on a time axis of ltau slices (needs no device;
+ * reads ELPH_DFT_MFMA, ELPH_DFT_R2, ELPH_FUSE_XR, ELPH_FUSE_PX and ELPH_DFT_BIG_BLOCKED as a transform does).  which: 0 twisted, 1 plain;
+ * nrz_slots: the r.z partial slots offered by an inverse that has to deliver them, else 0.  out[10] = the form (0 scalar tables, 1 one tile per
+ * wave, 2 direct matrix-core, 3 / 4 even/odd split in registers / with its W panel in LDS, 5 / 6 / 7 long axis: one row per wave / blocked /
+ * direct); the reduction tiles and row groups of its table; bytes of dynamic LDS; the r.z slots it fills; whether the residual update, the
+ * p/x-update and the order-1 fold may ride on it; whether nrz_slots is too few (the transform returns ELPH_E_STATE); the form
+ * fourier_accelerate runs this direction in (plain: the matrix cores only when both directions take them; twisted: the form itself).
+ * elph_bench_dft_info: the same from the record a handle made at elph_create. */
+int elph_bench_dft_plan(int64_t ltau, int which, int inverse, int N, int nvec, int nrz_slots, int *out);
+int elph_bench_dft_info(elph_handle h, int which, int inverse, int N, int nvec, int nrz_slots, int *out);
+
 /* What setup!(P) plans for nch chains at Ltau = ltau over nsteps successive steps of bounds (kpm_host.cpp: elph_kpm_plan; needs no device).
  * e_bounds: [nsteps][nch][2] (e_min, e_max); uploaded[s] = 1 when step s uploads the tables.  After the last step: active[nch]; lam[nch][4] =
  * lam_lo, lam_hi and the uploaded (lam_avg, lam_mag); the tables order, wsched [nch][Lo2] and coff [nch][Lo2+1]; c0 [nch][Lo2][2] the leading

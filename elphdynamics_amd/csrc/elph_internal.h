@@ -321,6 +321,46 @@ struct ResidentState {
     void launched(int t, int w, int g) { T = t; W = w; G = g; }
 };
 
+// The tau-axis transforms (dft.hip, dft_mfma.hip, dft_big.hip).  What a time axis offers is derived once (dft_shape), the switches are read
+// once per plan (dft_switches), one pure planner chooses the form of a transform (elph_plan_dft); the launchers read the plan and decide
+// nothing.  The device-free probe elph_bench_dft_plan holds the planner to tests/golden/dft_plan.json.
+enum DftKind { DFT_TWISTED = 0, DFT_PLAIN = 1 };
+// SCALAR: scalar-twiddle tables (dft.hip); matrix cores (dft_mfma.hip): ONE_TILE one 16 x 16 output tile per wave (k_dft_mfma_1), DIRECT the
+// (2K x L) GEMM (k_dft_mfma), SPLIT_REG / SPLIT_LDS the even/odd split of the twisted transform with its data in registers (k_dft_mfma_r2) / its
+// W panel in LDS (k_dft_mfma_r2s); long axes (dft_big.hip): BIG_ROW one output row per wave, BIG_BLOCKED k_big_s1 / k_big_s2, BIG_DIRECT a prime
+enum DftForm { DFT_SCALAR, DFT_ONE_TILE, DFT_DIRECT, DFT_SPLIT_REG, DFT_SPLIT_LDS, DFT_BIG_ROW, DFT_BIG_BLOCKED, DFT_BIG_DIRECT };
+struct DftTab { int nt = 0, groups = 0; };     // reduction tiles (a template size; 0: no such table), row groups of 5 row tiles
+struct DftShape {
+    int L = 0;
+    int L1 = 0, L2 = 0;        // the long-axis split L = L1 * L2 (0: not a long axis; L2 == 1: the direct long transform)
+    DftTab mf[2][2];           // the direct matrix-core tables [twisted / plain][forward / inverse]
+    DftTab r2[2];              // the even/odd split of the twisted transform [forward / inverse]: even L >= 8
+    bool big() const { return L1 > 0; }
+};
+// ELPH_DFT_MFMA (-1 unset), ELPH_DFT_R2, ELPH_FUSE_XR, ELPH_FUSE_PX, ELPH_DFT_BIG_BLOCKED (-1 unset)
+struct DftSwitches { int mfma = -1; bool r2 = true, fuse_xr = true, fuse_px = true; int big_blocked = -1; };
+struct DftPlan {
+    DftForm form = DFT_SCALAR;
+    int nt = 0, groups = 0;    // of the table the form reads (matrix-core forms)
+    int lds = 0;               // dynamic LDS bytes: the W panel of DFT_SPLIT_LDS
+    int slots = 0;             // r.z partial slots the form fills (0: no r.z asked for)
+    bool short_slots = false;  // the inverse has to deliver r.z and the caller offers fewer slots than the form fills: ELPH_E_STATE
+    // what the preconditioned CG iteration may fuse into this transform (elph_plan_cg): the residual update and the order-1 fold into the
+    // forward twisted transform, the p/x-update into the inverse one
+    bool xr = false, px = false, fold = false;
+};
+struct DftState {
+    DftShape shape;
+    double2 *theta = nullptr;                    // [2L] exp(-i pi t / L)
+    double2 *Tk = nullptr, *Tt = nullptr;        // scalar twisted tables [Lo2][L] / [L][Lo2]
+    double2 *Pk = nullptr, *Pt = nullptr;        // scalar plain tables   [Lh][L]  / [L][Lh]
+    double *W[2][2] = {}, *W_r2[2] = {};         // matrix-core tables in A-tile order, as shape.mf / shape.r2
+    double *r2_tw = nullptr;                     // [L/2] (cos, -sin) of pi (2k+1) / L
+    double2 *big_W1 = nullptr, *big_W2 = nullptr, *big_TW = nullptr;      // long axis: the two sub-transforms and the L roots of unity
+    double2 *big_a = nullptr, *big_b = nullptr;  // ... two complex work vectors of big_cap elements, grown with the batch (dft_big.hip)
+    size_t big_cap = 0;
+};
+
 struct elph_handle_s {
     int kind = 0, device = 0;
     int64_t N = 0, L = 0, nb = 0, ndim = 0;
@@ -413,23 +453,9 @@ struct elph_handle_s {
     KpmState kpm;                          // the KPM preconditioner (elph_kpm_create, kpm_setup_core)
     double2 *d_nu = nullptr;               // cap_rhs * Lo2 * N complex (half spectrum, omega-major)
 
-    // FFT twiddles
-    double2 *d_tw = nullptr;               // [L] exp(-2 pi i k / L)
-    double2 *d_theta = nullptr;            // [L] exp(-i pi t / L)
-    double2 *d_Tk = nullptr, *d_Tt = nullptr;   // twisted DFT tables [Lo2][L] / [L][Lo2] (dft.hip)
-    double2 *d_Pk = nullptr, *d_Pt = nullptr;   // plain DFT tables   [Lh][L]  / [L][Lh]
-    // batched tau-DFT on the matrix cores (dft_mfma.hip): W in A-tile order, [which: twisted/plain][fwd/inv]
-    struct MfmaTab { double *W = nullptr; int nt = 0, groups = 0; };
-    MfmaTab mf[2][2];
-    // twisted transform split once over even/odd tau (L % 4 == 0): half-length tables [fwd/inv] + the L/2 twiddles
-    MfmaTab mf_r2[2];
-    double *d_r2_tw = nullptr;             // [L/2] (cos, -sin) of pi (2k+1) / L
+    DftState dft;                          // the tau-axis transforms: shape, tables, work buffers (elph_dft_build_tables)
     double *d_diag = nullptr;              // fourier-acceleration diagonal staging
     int64_t diag_cap = 0;
-    // long time axes (L > 1024, dft_big.hip): one Cooley-Tukey split L = big_L1 * big_L2, tables and two complex work vectors
-    int big_L1 = 0, big_L2 = 0;
-    double2 *d_big_W1 = nullptr, *d_big_W2 = nullptr, *d_big_TW = nullptr, *d_big_TH = nullptr, *d_big_a = nullptr, *d_big_b = nullptr;
-    size_t big_cap = 0;
 };
 
 // ---- launchers implemented in kernels.hip -------------------------------------------------
@@ -616,8 +642,18 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight);
 // packs per-bond values (order of h_bi/h_bj) into the lane-program layout [NE][64] (idle slots = fill)
 void elph_lp_pack(const elph_handle_s *h, const double *per_bond, double *out, double fill);
 
-// ---- tau-axis transforms (dft.hip) -------------------------------------------------------------
-int elph_dft_build_tables(elph_handle_s *h);
+// ---- tau-axis transforms (dft.hip; the planner and the matrix-core forms in dft_mfma.hip, long axes in dft_big.hip) ------------------------
+constexpr int ELPH_DFT_TPT = 2;                             // time slices per wave of the scalar inverse (its r.z slots: ceil(L / TPT) per site tile)
+DftShape dft_shape(int64_t L);                              // pure: no HIP calls
+DftSwitches dft_switches();                                 // the one reader of the five switches; called per plan
+// which: DftKind; nrz_slots: the r.z partial slots offered by an inverse that has to deliver them, else 0
+DftPlan elph_plan_dft(const DftShape &S, const DftSwitches &sw, int which, bool inverse, int N, int nvec, int nrz_slots);
+DftPlan elph_dft_split_plan(const DftShape &S, bool inverse);      // the even/odd split's form and table alone (the fused launches below)
+void elph_dft_pair(DftPlan &fwd, DftPlan &inv);             // fourier_accelerate's plain pair: the matrix cores only when both directions take them
+void elph_i_dft_plan_probe(const DftShape &S, int which, bool inverse, int N, int nvec, int nrz_slots, int *out);      // _lib.DFT_PLAN_SLOTS
+int elph_dft_build_tables(elph_handle_s *h);                // h->dft: with elph_dft_free the only allocator / freer of its tables
+void elph_dft_free(elph_handle_s *h);
+int elph_dft_upload(void **dev, const void *src, size_t bytes);
 int elph_dft_fwd_twisted(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs, const CgState *st);
 int elph_dft_inv_twisted(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs, const CgState *st,
                          const double *rvec, double *rz_part, int nrz);
@@ -625,32 +661,19 @@ int elph_dft_fwd_plain(elph_handle_s *h, double2 *nu, const double *vS, int N, i
 int elph_dft_inv_plain(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs);
 int elph_dft_accel(elph_handle_s *h, double *outS, const double *inS, const double *diagS, double power, int N, double2 *u,
                    int nvec = 1);
-
-// ---- batched tau-axis transforms on the matrix cores (dft_mfma.hip); which: 0 twisted, 1 plain
+// the launches of a plan's form: DFT_ONE_TILE, DFT_DIRECT, DFT_SPLIT_* (dft_mfma.hip) and DFT_BIG_* (dft_big.hip)
+int elph_dft_mfma_run(elph_handle_s *h, const DftPlan &p, int which, bool inverse, double *out, const double *in, int N, int nrhs,
+                      const CgState *st, const double *rvec, double *rz_part, int nrz);
 int elph_dft_mfma_build_tables(elph_handle_s *h);
-bool elph_dft_mfma_xr_usable(const elph_handle_s *h, int N, int nrhs);
-bool elph_dft_mfma_px_usable(const elph_handle_s *h, int N, int nrhs);
-int elph_dft_mfma_inv_px(elph_handle_s *h, const double2 *nu, int N, int nrhs, const CgState *st, double *pS, double *xS,
-                         const double *alpha, const double *rz, int nrz);
-bool elph_dft_mfma_fold_usable(const elph_handle_s *h);
-bool elph_dft_big(const elph_handle_s *h);
-int elph_dft_big_build_tables(elph_handle_s *h);
-void elph_dft_big_free(elph_handle_s *h);
-int elph_dft_big_fwd(elph_handle_s *h, bool twisted, double2 *nu, const double *vS, int N, int nvec);
-int elph_dft_big_inv(elph_handle_s *h, bool twisted, double *outS, const double2 *nu, int N, int nvec, const double *rvec,
-                     double *rz_part, int nrz);
-bool elph_dft_mfma1_usable(const elph_handle_s *h, bool inverse, int N, int nrz_slots);
-int elph_dft_mfma1_fwd(elph_handle_s *h, double2 *nu, const double *vS, int N, int nrhs, const CgState *st);
-int elph_dft_mfma1_inv(elph_handle_s *h, double *outS, const double2 *nu, int N, int nrhs, const CgState *st, const double *rvec,
-                       double *rz_part, int nrz);
 int elph_dft_mfma_fwd_xr(elph_handle_s *h, double2 *nu, double *rS, const double *zS, const double *pap, int npap, double *rr,
                          double *alpha, int N, int nrhs, const CgState *st, const double *fold = nullptr, int fold_nch = 1,
                          double *frz = nullptr, int fnrz = 0, int fslot0 = 0);
-void elph_dft_mfma_free(elph_handle_s *h);
-bool elph_dft_mfma_usable(const elph_handle_s *h, int which, bool inverse, int N, int nrhs);
-int elph_dft_mfma_fwd(elph_handle_s *h, int which, double2 *nu, const double *vS, int N, int nrhs, const CgState *st);
-int elph_dft_mfma_inv(elph_handle_s *h, int which, double *outS, const double2 *nu, int N, int nrhs, const CgState *st,
-                      const double *rvec, double *rz_part, int nrz);
+int elph_dft_mfma_inv_px(elph_handle_s *h, const double2 *nu, int N, int nrhs, const CgState *st, double *pS, double *xS,
+                         const double *alpha, const double *rz, int nrz);
+int elph_dft_big_build_tables(elph_handle_s *h);
+int elph_dft_big_fwd(elph_handle_s *h, DftForm form, bool twisted, double2 *nu, const double *vS, int N, int nvec);
+int elph_dft_big_inv(elph_handle_s *h, DftForm form, bool twisted, double *outS, const double2 *nu, int N, int nvec, const double *rvec,
+                     double *rz_part, int nrz);
 
 // ---- host-side KPM setup (kpm_host.cpp) ---------------------------------------------------
 void elph_kpm_coefficients(double *c_z, int order, double lam_lo, double lam_hi, double phi);

@@ -1164,8 +1164,8 @@ int elph_launch_ebar(elph_handle_s *h, int nch) {
 // This is the only reader, on the iteration path, of the switches that choose the iteration's form (A/B; read when a solve is planned):
 // ELPH_NO_SQ=1 (the LDS Chebyshev recursion where a register-exchange form exists), ELPH_PG_PX=0 / ELPH_GEN_PX=0 / ELPH_LDS_CHEB_PX=0 (the
 // unfused iteration of the patch-form lattices / the rest of the generic family / the lane programs whose recursion runs through the LDS
-// slab), ELPH_SQ16_AP=0 (the lane-program k_cg_ap instead of the register form of cg_sq16.hip).  ELPH_FUSE_XR, ELPH_FUSE_PX and
-// ELPH_DFT_MFMA are read by the elph_dft_mfma_*_usable predicates it calls.
+// slab), ELPH_SQ16_AP=0 (the lane-program k_cg_ap instead of the register form of cg_sq16.hip).  The switches of the tau-axis transforms
+// (dft_switches) enter through the two plans of the twisted pair, whose xr, px and fold say what the iteration may fuse into them.
 CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) {
     const char *e_nosq = getenv("ELPH_NO_SQ"), *e_pg = getenv("ELPH_PG_PX"), *e_gen = getenv("ELPH_GEN_PX");
     const char *e_lds = getenv("ELPH_LDS_CHEB_PX"), *e_sq16 = getenv("ELPH_SQ16_AP");
@@ -1173,6 +1173,8 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
     const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2, nrz = (int)(h->L * h->npl), nct = (N + 15) / 16;
     const bool dot_all = h->dot_hi <= 0 || (h->dot_lo == 0 && h->dot_hi == N);      // every site enters the inner products (make_bufs)
     const bool hol = h->kind == ELPH_MODEL_HOLSTEIN, pg_cheb = elph_pg_cheb_usable(h), rz2 = 2 * Lo2 <= nrz;
+    const DftSwitches sw = dft_switches();
+    const DftPlan fwd = elph_plan_dft(h->dft.shape, sw, DFT_TWISTED, false, N, nrhs, 0), inv = elph_plan_dft(h->dft.shape, sw, DFT_TWISTED, true, N, nrhs, 0);
     CgPlan c;
     c.nrhs = nrhs;
     c.in_flight = in_flight;
@@ -1180,7 +1182,7 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
     c.reg_cheb = !no_sq && elph_reg_cheb_form(h) != REG_NONE;
     // p/x-fused (PxFuse, dft_mfma.hip): residual update folded into the forward transform, r.z from the Chebyshev kernel in frequency space
     // (so that beta is known BEFORE the inverse transform), streaming MFMA inverse with the p/x-update in its epilogue
-    if (prec && h->kpm.ready && h->kpm.any_active() && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs) && elph_dft_mfma_px_usable(h, N, nrhs)) {
+    if (prec && h->kpm.ready && h->kpm.any_active() && dot_all && fwd.xr && inv.px) {
         if (!h->fast && hol && (h->kpm.hop_uniform || elph_pg_disorder_ok(h)) && elph_pg_ap_usable(h) && pg_cheb) {
             // (round 6) the patch-form lattices of the generic family: k_cg_ap_pg + k_kpm_cheb_pg (pgrid.hip)
             c.px = pg_px_ok && rz2;
@@ -1212,12 +1214,12 @@ CgPlan elph_plan_cg(const elph_handle_s *h, int nrhs, bool prec, int in_flight) 
         // a large even-L square lattice: the patch-layout kernel (pgrid.hip)
         c.ap = (elph_pg_ap_usable(h) && (h->shape.hop_uniform || elph_pg_disorder_ok(h))) ? CgPlan::AP_PG : CgPlan::AP_GEN;
     }
-    c.xr_in_fwd = c.px || (h->fast && h->kpm.any_active() && dot_all && elph_dft_mfma_xr_usable(h, N, nrhs));
+    c.xr_in_fwd = c.px || (h->fast && h->kpm.any_active() && dot_all && fwd.xr);
     c.rz_freq = dot_all && (c.cheb == CgPlan::CH_LANE ? rz2 : c.cheb == CgPlan::CH_PG ? c.px && rz2 : c.px && Lo2 <= nrz);
     // FOLD (dft_mfma.hip: XrFuse): with the residual update in the forward transform and a register-exchange Chebyshev kernel (the one that
     // knows the fold) the frequencies of order 1 — z_w = |c0|^2 r_w — are finished by the forward transform; the Chebyshev kernel keeps
     // their slot bookkeeping only
-    c.fold = h->fast && c.reg_cheb && h->lp_mc == 4 && h->kpm.d_fold && 2 * Lo2 + nct <= nrz && dot_all && elph_dft_mfma_fold_usable(h);
+    c.fold = h->fast && c.reg_cheb && h->lp_mc == 4 && h->kpm.d_fold && 2 * Lo2 + nct <= nrz && dot_all && fwd.fold;
     return c;
 }
 
@@ -1438,7 +1440,7 @@ int elph_launch_omega_to_tau(elph_handle_s *h, double *vS, const double2 *nuS_fu
     const int N = (int)h->N, L = (int)h->L;
     const int nst = (N + WAVE - 1) / WAVE;
     hipLaunchKernelGGL(k_dft_inv_twisted_full, dim3((unsigned)nst, (unsigned)L, 1), dim3(WAVE), 0, h->stream, vS, nuS_full,
-                       h->d_theta, N, L);
+                       h->dft.theta, N, L);
     return elph_launch_check("omega_to_tau");
 }
 

@@ -552,8 +552,8 @@ static bool pcg_shape(const elph_handle_s *h, int nrhs, int *Wo, int *Go, int *n
     for (int w = std::min(8, Wt); w >= 1; --w) if (Wt % w == 0) { W = w; break; }
     const int G = Wt / W;
     if (G + wg::PCG_H > 32 || (G > 1 && W < 2)) return false;
-    const elph_handle_s::MfmaTab &Tf = h->mf[0][0], &Ti = h->mf[0][1];
-    if (!Tf.W || !Ti.W || Tf.nt != Ti.nt || (Tf.nt != 20 && Tf.nt != 40)) return false;
+    const DftTab &Tf = h->dft.shape.mf[0][0], &Ti = h->dft.shape.mf[0][1];
+    if (Tf.nt != Ti.nt || (Tf.nt != 20 && Tf.nt != 40)) return false;
     if (Wo) *Wo = W;
     if (Go) *Go = G;
     if (nto) *nto = Tf.nt;
@@ -579,8 +579,8 @@ int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_ite
         HIPCHK(hipMemcpyAsync(x0_save, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     wg::PcgCtl Pc;
     Pc.flags = R.slots + n_slots;
-    Pc.Wf = h->mf[0][0].W; Pc.Wi = h->mf[0][1].W;
-    Pc.rtf = h->mf[0][0].groups * 5; Pc.rti = h->mf[0][1].groups * 5;       // (dft_mfma.hip: MG = 5 row tiles per group)
+    Pc.Wf = h->dft.W[0][0]; Pc.Wi = h->dft.W[0][1];
+    Pc.rtf = h->dft.shape.mf[0][0].groups * 5; Pc.rti = h->dft.shape.mf[0][1].groups * 5;       // (dft_mfma.hip: MG = 5 row tiles per group)
     Pc.nu = h->d_nu; Pc.zp = h->d_zp;
     Pc.K = elph_kpm_dev(h);
     Pc.sqc = h->kpm.d_sq_cbar; Pc.sqs = h->kpm.d_sq_sbar;

@@ -9,21 +9,13 @@ device arrays (elph_greens_dev_arrays) the host copies bit for bit.  The estimat
 
 setup! runs four time-axis transforms: forward twisted of 2 vectors and forward plain of 6 vectors over N columns, inverse twisted of
 1 vector and inverse plain of 3 vectors over ns*N columns.  On the 3 x 2 honeycomb cells of the time-axis cases (N = 12, ns*N = 24)
-the switches select these forms (dft.hip, dft_mfma.hip, dft_big.hip):
-  L = 7, 45    ELPH_DFT_MFMA=0    twisted: one-tile matrix-core form (k_dft_mfma_1); plain: scalar tables
-               ELPH_DFT_MFMA=1    twisted and plain: direct matrix-core form (k_dft_mfma; an odd L has no even/odd split)
-  L = 160      ELPH_DFT_MFMA=0    twisted: one-tile; plain: scalar tables
-               ELPH_DFT_MFMA=1    twisted: even/odd split (k_dft_mfma_r2s, W panel in LDS); plain: direct matrix-core
-               + ELPH_DFT_R2=0    twisted and plain: direct matrix-core
-  L = 320      ELPH_DFT_R2=0      all four: scalar tables (no direct matrix-core tables beyond 256 slices)
-               ELPH_DFT_R2=1 and ELPH_DFT_MFMA=1   twisted: split with a 100 KB W panel; plain: scalar tables
-  L = 480, 1000, 1280   ELPH_DFT_BIG_BLOCKED=0 / 1   Cooley-Tukey split (20 x 24, 25 x 40, 32 x 40): one output row per wave / the
-               register-blocked pair k_big_s1 / k_big_s2
-  L = 409, 422 scalar tables beyond 400 slices (a prime; 2 x 211 has no divisor >= 4)
-  L = 1031     direct long transform (k_big_direct: a prime beyond 1024)
-No switch reaches the scalar kernels with the twisted pair at L <= 256: ELPH_DFT_MFMA=0 leaves the one-tile form, which
-elph_dft_mfma1_usable chooses without reading a switch.  ELPH_DFT_R2=1 alone at L = 320 keeps the scalar kernels on a lattice this small
-(the split starts at 100 column-tile waves), hence ELPH_DFT_MFMA=1 with it.
+the switches select the forms of TIME_AXES below (elph_plan_dft, dft_mfma.hip), which the test asserts of the handle's own plan and of the
+device-free probe before it compares numbers: an odd L has no even/odd split; there are no direct matrix-core tables beyond 256 slices; the
+split at L = 320 stages a 100 KB W panel; 480, 1000 and 1280 slices split as 20 x 24, 25 x 40 and 32 x 40; 409 is a prime and 422 = 2 x 211
+has no divisor >= 4 (scalar tables beyond 400 slices); 1031 is a prime beyond 1024.
+No switch reaches the scalar kernels with the twisted pair at L <= 256: ELPH_DFT_MFMA=0 leaves the one-tile form, which the planner
+chooses without reading a switch.  ELPH_DFT_R2=1 alone at L = 320 keeps the scalar kernels on a lattice this small (the split starts at
+100 column-tile waves), hence ELPH_DFT_MFMA=1 with it.
 
 End to end (update_ on the device's own solve to 1e-13, with and without the KPM preconditioner): rectangular honeycomb, a chain and two
 cubic lattices, M^-1 R against the oracle's solve within the README's 1e-10, the tables within 1e-12 on the device's vectors; the cubic
@@ -82,11 +74,17 @@ def check_tables(est, orc, n1, n2):
         assert np.array_equal(out, getattr(est, nm).reshape(-1, order="F").view(np.float64)), nm
 
 
-def parity_on_fixed_vectors(ns, L1, L2, L3, L, seed):
-    from elphdynamics_amd import greens
+def parity_on_fixed_vectors(ns, L1, L2, L3, L, seed, forms=None):
+    from elphdynamics_amd import _lib, greens
     from oracle.greens import EstimateGreensFunction as OracleEst
     m = bondfree_model(ns, L1, L2, L3, L)
     try:
+        if forms:      # setup!'s four transforms: (kind, direction, columns, vectors) and the form each is planned in
+            N = m.Nsites
+            for (which, inv, ncol, nvec), form in zip(((0, 0, N, 2), (1, 0, N, 6), (0, 1, ns * N, 1), (1, 1, ns * N, 3)), forms):
+                plan = _lib.dft_plan(L, which, inv, ncol, nvec, handle=m._h)
+                assert plan == _lib.dft_plan(L, which, inv, ncol, nvec), (which, inv)
+                assert plan["form"] == _lib.DFT_FORMS[form] and not plan["short_slots"], (which, inv, plan)
         est = greens.EstimateGreensFunction(m, nv=3)
         assert est.GD0.shape == (2 * L, ns, ns, L1, L2, L3)
         rng = np.random.default_rng(seed)
@@ -125,32 +123,41 @@ def test_setup_matches_oracle_across_cell_shapes(case):
     parity_on_fixed_vectors(ns, L1, L2, L3, L, seed=sum(CELL_SHAPES[case]))
 
 
+# (L, switches, (form of the twisted pair, form of the plain pair)): _lib.DFT_FORMS
 TIME_AXES = [
-    (7, {"ELPH_DFT_MFMA": "0"}), (7, {"ELPH_DFT_MFMA": "1"}),
-    (45, {"ELPH_DFT_MFMA": "0"}), (45, {"ELPH_DFT_MFMA": "1"}),
-    (160, {"ELPH_DFT_MFMA": "0"}), (160, {"ELPH_DFT_MFMA": "1"}), (160, {"ELPH_DFT_MFMA": "1", "ELPH_DFT_R2": "0"}),
-    (320, {"ELPH_DFT_R2": "0"}), (320, {"ELPH_DFT_R2": "1", "ELPH_DFT_MFMA": "1"}),
-    (480, {"ELPH_DFT_BIG_BLOCKED": "0"}), (480, {"ELPH_DFT_BIG_BLOCKED": "1"}),
-    (1000, {"ELPH_DFT_BIG_BLOCKED": "0"}), (1000, {"ELPH_DFT_BIG_BLOCKED": "1"}),
-    (409, {}), (422, {}), (1031, {}),
-    (1280, {"ELPH_DFT_BIG_BLOCKED": "0"}), (1280, {"ELPH_DFT_BIG_BLOCKED": "1"}),
+    (7, {"ELPH_DFT_MFMA": "0"}, ("ONE_TILE", "SCALAR")), (7, {"ELPH_DFT_MFMA": "1"}, ("DIRECT", "DIRECT")),
+    (45, {"ELPH_DFT_MFMA": "0"}, ("ONE_TILE", "SCALAR")), (45, {"ELPH_DFT_MFMA": "1"}, ("DIRECT", "DIRECT")),
+    (160, {"ELPH_DFT_MFMA": "0"}, ("ONE_TILE", "SCALAR")), (160, {"ELPH_DFT_MFMA": "1"}, ("SPLIT_LDS", "DIRECT")),
+    (160, {"ELPH_DFT_MFMA": "1", "ELPH_DFT_R2": "0"}, ("DIRECT", "DIRECT")),
+    (320, {"ELPH_DFT_R2": "0"}, ("SCALAR", "SCALAR")), (320, {"ELPH_DFT_R2": "1", "ELPH_DFT_MFMA": "1"}, ("SPLIT_LDS", "SCALAR")),
+    (480, {"ELPH_DFT_BIG_BLOCKED": "0"}, ("BIG_ROW", "BIG_ROW")), (480, {"ELPH_DFT_BIG_BLOCKED": "1"}, ("BIG_BLOCKED", "BIG_BLOCKED")),
+    (1000, {"ELPH_DFT_BIG_BLOCKED": "0"}, ("BIG_ROW", "BIG_ROW")), (1000, {"ELPH_DFT_BIG_BLOCKED": "1"}, ("BIG_BLOCKED", "BIG_BLOCKED")),
+    (409, {}, ("SCALAR", "SCALAR")), (422, {}, ("SCALAR", "SCALAR")), (1031, {}, ("BIG_DIRECT", "BIG_DIRECT")),
+    (1280, {"ELPH_DFT_BIG_BLOCKED": "0"}, ("BIG_ROW", "BIG_ROW")), (1280, {"ELPH_DFT_BIG_BLOCKED": "1"}, ("BIG_BLOCKED", "BIG_BLOCKED")),
 ]
 
 
+# every form but the register-resident split, which no time axis reaches (tests/test_dft_plan.py)
+_FORMS_REACHABLE = ("SCALAR", "ONE_TILE", "DIRECT", "SPLIT_LDS", "BIG_ROW", "BIG_BLOCKED", "BIG_DIRECT")
+
+
 def _time_id(case):
-    L, env = case
+    L, env, _ = case
     return "L%d" % L + "".join("-%s%s" % (k[len("ELPH_DFT_"):], v) for k, v in sorted(env.items()))
 
 
-@pytest.mark.parametrize("L,env", TIME_AXES, ids=[_time_id(c) for c in TIME_AXES])
-def test_setup_matches_oracle_across_time_axes(L, env, monkeypatch):
-    """Odd and even time axes through every transform form the dispatch can choose for setup!'s four calls (module docstring),
-    on 3 x 2 honeycomb cells (rectangular, two orbitals: 24 columns for the inverse transforms)."""
+@pytest.mark.parametrize("L,env,forms", TIME_AXES, ids=[_time_id(c) for c in TIME_AXES])
+def test_setup_matches_oracle_across_time_axes(L, env, forms, monkeypatch):
+    """Odd and even time axes through every transform form the planner can choose for setup!'s four calls (module docstring), on 3 x 2
+    honeycomb cells (rectangular, two orbitals: 24 columns for the inverse transforms): the handle plans the listed form, as the
+    device-free probe does, and the tables match the oracle."""
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    parity_on_fixed_vectors(2, 3, 2, 1, L, seed=L)
+    twisted, plain = forms
+    assert {f for _, _, fs in TIME_AXES for f in fs} == set(_FORMS_REACHABLE)
+    parity_on_fixed_vectors(2, 3, 2, 1, L, seed=L, forms=(twisted, plain, twisted, plain))
 
 
 @pytest.mark.parametrize("ns,L1,L2,nbytes", [(1, 46, 46, 169280), (2, 36, 36, 165888)])

@@ -99,7 +99,7 @@ def test_px_fused_batch_with_hopping_disorder(oracle, tag, monkeypatch):
     Re / Im recursion through the LDS slab (k_kpm_cheb_ri) against the unfused form (ELPH_LDS_CHEB_PX=0) with the bounds of
     test_px_fused_iteration_generic_family — iteration counts within one, two tol = 1e-8 solves to 1e-9, the fused form asserted taken —
     and two right-hand sides (chains 0 and 3) against the oracle's tight solve to 1e-6.  The library's own rules keep so small a batch
-    on the unfused iteration (elph_choose_T_px: fewer than 1024 waves; elph_dft_mfma_usable: fewer than 448 column tiles): the chunk
+    on the unfused iteration (elph_choose_T_px: fewer than 1024 waves; elph_plan_dft: fewer than 448 column-tile waves): the chunk
     length and the matrix-core transforms are pinned, as test_px_fused_preconditioned_iteration_equals_the_unfused_one pins its small batches."""
     from elphdynamics_amd import models
     nchains, per = 8, 2
