@@ -141,6 +141,9 @@ SIGNATURES = {
     "elph_kpm_orders": (c_int, [Handle, P_i64, P_i64]),
     "elph_kpm_apply": (c_int, [Handle, P_dbl, P_dbl]),
     "elph_kpm_apply_dev": (c_int, [Handle, C.c_void_p, C.c_void_p]),
+    "elph_kpm_apply_side": (c_int, [Handle, c_int, P_dbl, P_dbl, c_int]),
+    "elph_msolve": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl, c_int, c_dbl, c_i64, c_i64, c_int, P_i64]),
+    "elph_mldiv": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl, c_int, c_i64, c_int, P_i64, P_dbl, P_int]),
     "elph_fourier_accelerate": (c_int, [Handle, P_dbl, P_dbl, P_dbl, c_dbl, c_i64]),
     "elph_tau_to_omega": (c_int, [Handle, P_dbl, P_dbl]),
     "elph_omega_to_tau": (c_int, [Handle, P_dbl, P_dbl]),

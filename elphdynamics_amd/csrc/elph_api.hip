@@ -446,6 +446,7 @@ extern "C" int elph_destroy(elph_handle h) {
     elph_shard_free(h);
     elph_hmc_free(h);
     elph_greens_free(h);
+    elph_msolve_free(h);
     elph_dft_free(h);
     elph_kpm_free(h);
     void *ptrs[] = {h->d_bi, h->d_bj, h->d_coloff, h->d_c, h->d_s, h->d_E, h->d_lam, h->d_stage_in, h->d_stage_out,

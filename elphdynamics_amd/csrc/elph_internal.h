@@ -420,6 +420,7 @@ struct elph_handle_s {
     void *density_moments = nullptr;       // DensityMomentsState (density_moments.hip), owned; freed with greens
     void *snapshots = nullptr;             // SnapshotsState (snapshots.hip), owned; freed with greens
     void *current = nullptr;               // CurrentState (currcorr.hip), owned; freed with greens
+    void *msolve = nullptr;                // MsolveState (msolve.hip), owned: the work vectors of BiCGStab and GMRES, GMRES's Krylov basis
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
     // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
     // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
@@ -548,6 +549,9 @@ int elph_launch_cg_init_only(elph_handle_s *h, int nrhs);
 int elph_launch_cg_state0_only(elph_handle_s *h, int nrhs);
 int elph_launch_cg_init_prec_only(elph_handle_s *h, int nrhs);
 int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nrhs, int cg_mode, int parts = 7);
+// one side of the expansion (kernels.hip: k_kpm_cheb_side): transposed 0 Left ~ M⁻¹, 1 Right ~ M⁻ᵀ; done: [nrhs] skip flags or nullptr
+int elph_launch_kpm_apply_side(elph_handle_s *h, double *zS, const double *rS, int nrhs, int transposed, const int *done);
+void elph_msolve_free(elph_handle_s *h);                                    // msolve.hip
 int elph_launch_ebar(elph_handle_s *h, int nch = 1);
 int elph_launch_fft_accel(elph_handle_s *h, double *outS, const double *inS, const double *diagS, double power, int64_t ncol,
                           int nvec = 1);

@@ -667,6 +667,57 @@ __global__ void __launch_bounds__(1024) k_kpm_cheb(double2 *__restrict__ nu, Kpm
     }
 }
 
+// One side of the expansion alone, for the solvers that work on M or Mᵀ directly (msolve.hip): ONE kpm_series call per frequency block,
+//   TRANSPOSED = false: M⁻¹[ω,ω] with the coefficients c        (LeftKPMPreconditioner,  KPMPreconditioners.jl:514-554)
+//   TRANSPOSED = true:  M⁻ᵀ[ω,ω] with the coefficients conj(c)  (RightKPMPreconditioner, :560-600)
+// in the LDS-slab form and the longest-first schedule of k_kpm_cheb, whatever the bond table.  done: [nrhs] flags of the solve in progress (a
+// finished right-hand side is skipped), or nullptr.  Up to 6 sites per thread (6144 sites): the four vectors of kpm_series fit the 128
+// registers of a 1024-thread workgroup without scratch; with 7 or 8 they do not, and the launcher refuses such a lattice.
+template <int NPL, bool TRANSPOSED>
+__global__ void __launch_bounds__(1024) k_kpm_cheb_side(double2 *__restrict__ nu, KpmDev K, ModelDev m, int Lo2, const int *__restrict__ done,
+                                                        int lds_tables) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double2 *buf = reinterpret_cast<double2 *>(lds);
+    const int rhs = blockIdx.x;
+    if (done && done[rhs]) return;
+    const unsigned *lij = nullptr;
+    const double *lc = nullptr, *ls = nullptr;
+    const KpmChainView V = kpm_chain_view(K, rhs, m.N);
+    K.cbar = V.cbar; K.sbar = V.sbar;
+    if (lds_tables) {
+        double *tc = lds + 2 * (size_t)m.N, *ts = tc + m.nb;
+        unsigned *tij = reinterpret_cast<unsigned *>(ts + m.nb);
+        for (int n = threadIdx.x; n < m.nb; n += blockDim.x) {
+            tc[n] = K.cbar[n]; ts[n] = K.sbar[n];
+            tij[n] = (unsigned)m.bi[n] | ((unsigned)m.bj[n] << 16);
+        }
+        lij = tij; lc = tc; ls = ts;                               // the first barrier inside kpm_mulAprime publishes them
+    }
+    const int w = V.wsched[blockIdx.y];
+    const int N = m.N;
+    const int order = V.order[w];
+    const double2 *c = K.coeff + V.coff[w];
+    double2 *u = nu + ((size_t)rhs * Lo2 + w) * N;
+    double eb[NPL];
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int s = threadIdx.x + q * blockDim.x;
+        eb[q] = (s < N) ? V.Ebar[s] : 0.0;
+    }
+    double2 vin[NPL], res[NPL];
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int s = threadIdx.x + q * blockDim.x;
+        vin[q] = (s < N) ? u[s] : make_double2(0.0, 0.0);
+    }
+    kpm_series<NPL, TRANSPOSED, TRANSPOSED>(res, vin, buf, eb, c, order, K, m, V.a, V.b, lij, lc, ls);
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int s = threadIdx.x + q * blockDim.x;
+        if (s < N) u[s] = res[q];
+    }
+}
+
 // Ebar[i] = mean_tau E[tau][i]  (update_A!, KPMPreconditioners.jl:332-349)
 // update_model! of the SSH model on the device (SSHModels.jl:510-562).
 //   pass 1 (fill):   every (tau, bond) gets cosh/sinh of its bare hopping  (bonds without a phonon keep that)
@@ -1295,6 +1346,44 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         if (rcd) return rcd;
     }
     return elph_launch_check("kpm apply");
+}
+
+// z = (one side of the expansion) r on layout-S vectors (z may be r): transposed 0: the Left preconditioner ~ M⁻¹, 1: the Right one ~ M⁻ᵀ.
+// The forward and inverse twisted transforms are those of elph_launch_kpm_apply; between them k_kpm_cheb_side.  An expansion that is
+// inactive on every chain is the identity copy (KPMPreconditioners.jl:475-478).
+int elph_launch_kpm_apply_side(elph_handle_s *h, double *zS, const double *rS, int nrhs, int transposed, const int *done) {
+    const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
+    if (!h->kpm.any_active()) {
+        if (zS == rS) return ELPH_OK;
+        const long long n = (long long)nrhs * N * L;
+        hipLaunchKernelGGL(k_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, zS, rS, n);
+        return elph_launch_check("kpm identity");
+    }
+    KpmDev K = elph_kpm_dev(h);
+    ModelDev m = elph_model_dev(h);
+    const size_t shm = (size_t)N * sizeof(double2);
+    int maxcol = 1;
+    for (int cidx = 0; cidx < h->ncol; ++cidx) maxcol = std::max(maxcol, h->h_coloff[(size_t)cidx + 1] - h->h_coloff[(size_t)cidx]);
+    const int cbs = std::min(1024, std::max(gen_bs(h), ELPH_WAVE * ((maxcol + ELPH_WAVE - 1) / ELPH_WAVE)));
+    const int cnpl = (N + cbs - 1) / cbs;
+    const size_t tab = (size_t)h->nb * (2 * sizeof(double) + sizeof(unsigned));
+    const int lds_tables = (N <= 65535 && shm + tab <= 64 * 1024) ? 1 : 0;
+    if (cnpl > 6) {
+        elph_set_error("the one-sided KPM preconditioners serve lattices of up to %d sites (this one: %d)", 6 * cbs, N);
+        return ELPH_E_UNSUPPORTED;
+    }
+    RC(elph_dft_fwd_twisted(h, h->d_nu, rS, N, nrhs, nullptr));
+#define SIDE_NPL(n)                                                                                                                            \
+    case n:                                                                                                                                    \
+        if (transposed) hipLaunchKernelGGL((k_kpm_cheb_side<n, true>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs),               \
+                                           shm + (lds_tables ? tab : 0), h->stream, h->d_nu, K, m, Lo2, done, lds_tables);                     \
+        else hipLaunchKernelGGL((k_kpm_cheb_side<n, false>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs),                         \
+                                shm + (lds_tables ? tab : 0), h->stream, h->d_nu, K, m, Lo2, done, lds_tables);                                \
+        break;
+    switch (cnpl) { SIDE_NPL(1) SIDE_NPL(2) SIDE_NPL(3) SIDE_NPL(4) SIDE_NPL(5) SIDE_NPL(6) }
+#undef SIDE_NPL
+    RC(elph_launch_check("k_kpm_cheb_side"));
+    return elph_dft_inv_twisted(h, zS, h->d_nu, N, nrhs, nullptr, nullptr, nullptr, (int)(h->L * h->npl));
 }
 
 int elph_launch_rz_partials(elph_handle_s *h, int nrhs);

@@ -10,7 +10,7 @@ operation to libelphgpu.so through its C ABI (include/elph_gpu.h).  Julia's `f!`
     mulM_(y, model, v), mulMt_(y, model, v)      HolsteinModels.jl:569,631 / SSHModels.jl:581,646
     mulMtM_(y, model, v)                         Models.jl:215
     ldiv_(x, model, b, P=None, maxiter=0)        Models.jl:74,139  -> (iters, residual_error, flag)
-    solve_(x, model, b, cg, P=None, ...)         IterativeSolvers.jl:153,239 -> iters
+    solve_(x, model, b, solver, P=None, ...)     IterativeSolvers.jl:153,239 (CG), :354 (BiCGStab), :464 (GMRES) -> iters
     transpose_(model)                            Models.jl:244
 
 All vectors are numpy float64, flat, reference layout (tau fastest, Utilities.jl:12-15).
@@ -42,6 +42,40 @@ class ConjugateGradient:
         self.N = int(ndim)
 
 
+class BiCGStab:
+    """IterativeSolvers.jl:323-349 (tol, maxiter); the work vectors live on the GPU."""
+
+    def __init__(self, ndim, tol=1e-4, maxiter=0):
+        self.tol = float(tol)
+        self.maxiter = int(maxiter) if maxiter >= 1 else int(ndim)      # (the handle reads 0 as ndim, as for ConjugateGradient)
+        self.N = int(ndim)
+
+
+class GMRES:
+    """IterativeSolvers.jl:427-461 (tol, maxiter, restart): maxiter < 0 -> ndim, restart < 0 -> min(20, ndim); H and V live on the GPU."""
+
+    def __init__(self, ndim, tol=1e-4, maxiter=-1, restart=-1):
+        self.ndim = self.N = int(ndim)
+        self.tol = float(tol)
+        self.maxiter = int(maxiter) if maxiter >= 1 else self.ndim      # (0 too: the handle reads 0 as ndim)
+        self.restart = int(restart) if restart >= 0 else min(20, self.ndim)
+
+
+SOLVER_CODES = {BiCGStab: 1, GMRES: 2}               # include/elph_gpu.h: ELPH_SOLVER_BICGSTAB, ELPH_SOLVER_GMRES
+
+
+def make_solver(name, ndim, tol, maxiter, restart=-1):
+    """The solver of a model and its mul_by_M, as HolsteinModels.jl:286-298 / SSHModels.jl choose them from solver.type."""
+    key = str(name).lower()                          # lowercase(iterativesolver), :289
+    if key == "cg":
+        return ConjugateGradient(ndim, tol=tol, maxiter=maxiter), False
+    if key == "bicgstab":
+        return BiCGStab(ndim, tol=tol, maxiter=maxiter), True
+    if key == "gmres":
+        return GMRES(ndim, tol=tol, maxiter=maxiter, restart=restart), True
+    raise ValueError(f"solver {name!r}: one of 'CG', 'BiCGStab', 'GMRES'")
+
+
 class AbstractModel:
     """Common part of HolsteinModel / SSHModel (Models.jl:65): owns the GPU handle."""
 
@@ -60,7 +94,7 @@ class AbstractModel:
         self._push_solver()
 
     def _push_solver(self):
-        check(self._lib.elph_solver_set(self._h, self.solver.tol, self.solver.maxiter, self.solver.kmax))
+        check(self._lib.elph_solver_set(self._h, self.solver.tol, self.solver.maxiter, getattr(self.solver, "kmax", 1e12)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -88,7 +122,7 @@ class HolsteinModel(AbstractModel):
 
     kind = HOLSTEIN
 
-    def __init__(self, lattice, beta, dtau, tol=1e-4, maxiter=10000, device=0):
+    def __init__(self, lattice, beta, dtau, tol=1e-4, maxiter=10000, device=0, solver="CG", restart=-1):
         self.lattice = lattice
         self.beta, self.dtau = float(beta), float(dtau)
         self.Ltau = _lat.ltau_from_beta(beta, dtau)                 # HolsteinModels.jl:205
@@ -111,9 +145,9 @@ class HolsteinModel(AbstractModel):
         self.lam = np.zeros(self.Nph)
         self.lam2 = np.zeros(self.Nph)
         self.mu = np.zeros(self.Nsites)
-        self.mul_by_M = False                                       # CG works on MtM (HolsteinModels.jl:268-276)
+        # CG works on MtM, GMRES and BiCGStab on M or Mt directly (HolsteinModels.jl:286-298)
+        self.solver, self.mul_by_M = make_solver(solver, self.Ndim, tol, maxiter, restart)
         self.transposed = False
-        self.solver = ConjugateGradient(self.Ndim, tol=tol, maxiter=maxiter)
         self._device = device
         self._h = None
 
@@ -180,7 +214,7 @@ class SSHModel(AbstractModel):
     cosht = property(lambda self: self._cs("_cosht"), lambda self, v: setattr(self, "_cosht", v))
     sinht = property(lambda self: self._cs("_sinht"), lambda self, v: setattr(self, "_sinht", v))
 
-    def __init__(self, lattice, beta, dtau, tol=1e-4, maxiter=10000, device=0):
+    def __init__(self, lattice, beta, dtau, tol=1e-4, maxiter=10000, device=0, solver="CG", restart=-1):
         self.lattice = lattice
         self.beta, self.dtau = float(beta), float(dtau)
         self.Ltau = _lat.ltau_from_beta(beta, dtau)
@@ -188,9 +222,8 @@ class SSHModel(AbstractModel):
         self.Ndim = self.Nsites * self.Ltau
         self.bond_definitions = []
         self.mu = np.zeros(self.Nsites)
-        self.mul_by_M = False
+        self.solver, self.mul_by_M = make_solver(solver, self.Ndim, tol, maxiter, restart)
         self.transposed = False
-        self.solver = ConjugateGradient(self.Ndim, tol=tol, maxiter=maxiter)
         self._device = device
         self._h = None
 
@@ -387,45 +420,81 @@ def muldMdx_(dMdx, u, model, v):
 # solvers
 # ----------------------------------------------------------------------------------------------
 
-def _use_prec(P):
-    return 0 if P is None else 1
+def _use_prec(P, model=None, by_M=None):
+    """0 / 1 for the library; a preconditioner of the wrong family for the solver is a ValueError: the symmetric expansion belongs to CG on
+    MtM, the one-sided ones to GMRES / BiCGStab on M or Mt (ProcessInputFile.jl:502-506).  by_M: the solver works on M or Mt (None: as
+    model.mul_by_M says)."""
+    if P is None:
+        return 0
+    if model is not None:
+        by_M = model.mul_by_M if by_M is None else by_M
+        sided = hasattr(P, "side_for")
+        if by_M and not sided:
+            raise ValueError("GMRES and BiCGStab (a mul_by_M model) take a Left / Right / LeftRight KPM preconditioner, not the symmetric one")
+        if not by_M and sided:
+            raise ValueError("CG solves MtM x = b and takes SymmetricKPMPreconditioner, not a one-sided one")
+        if sided and P.side_for(model) != bool(model.transposed):
+            raise ValueError("the device solvers pair M with the Left and Mt with the Right preconditioner, as LeftRightKPMPreconditioner does")
+    return 1
+
+
+def _restart(solver):
+    return int(getattr(solver, "restart", -1))
 
 
 def solve_(x, model, b, cg=None, P=None, maxiter=0, tol=0.0, kmax=0.0, history=False):
-    """solve!(x, A, b, cg[, P]; maxiter, tol, kmax) -> iters (IterativeSolvers.jl:153-234, 239-314).
-    With history=True also returns eps_0..eps_iters."""
+    """solve!(x, A, b, solver[, P]; maxiter, tol, kmax) -> iters (IterativeSolvers.jl:153-234, 239-314 CG; :354-417 BiCGStab; :464-570
+    GMRES), dispatched on the solver's type.  A = MtM for CG, M or Mt (model.transposed) for the other two.  With history=True (CG only)
+    also returns eps_0..eps_iters."""
     cg = cg or model.solver
-    model._push_solver()
     if P is not None:
         assert P.model is model
+    use = _use_prec(P, model, by_M=type(cg) in SOLVER_CODES)
+    model._push_solver()
+    if type(cg) in SOLVER_CODES:
+        assert not history and not kmax, "history and kmax belong to ConjugateGradient"
+        it = np.zeros(1, dtype=np.int64)
+        check(model._lib.elph_msolve(model._h, SOLVER_CODES[type(cg)], int(bool(model.transposed)), 1, dptr(_vec(x, model.Ndim)),
+                                     dptr(_vec(b, model.Ndim)), use, tol or cg.tol, int(maxiter), cg.maxiter, _restart(cg), iptr(it)))
+        return int(it[0])
     mi = maxiter if maxiter else cg.maxiter
     it = C.c_int64()
     hist = np.full(mi + 1, np.nan) if history else None
     check(model._lib.elph_cg_solve(model._h, dptr(_vec(x, model.Ndim)), dptr(_vec(b, model.Ndim)), tol or cg.tol, mi,
-                                   kmax or cg.kmax, _use_prec(P), C.byref(it), dptr(hist) if history else None))
+                                   kmax or cg.kmax, use, C.byref(it), dptr(hist) if history else None))
     if history:
         return int(it.value), hist[:it.value + 1]
     return int(it.value)
 
 
 def ldiv_(x, model, b, P=None, maxiter=0):
-    """ldiv!(x, model, b[, P]; maxiter) -> (iters, residual_error, flag)  (Models.jl:74-186)."""
-    assert not model.mul_by_M and not model.transposed, "the GPU path solves MtM x = b (CG), as the reference does"
+    """ldiv!(x, model, b[, P]; maxiter) -> (iters, residual_error, flag)  (Models.jl:74-186): MtM x = b by CG, or — a mul_by_M model —
+    M x = b / Mt x = b (model.transposed) by the model's BiCGStab or GMRES."""
+    if model.mul_by_M:
+        it, res, fl = ldiv_batched_(_vec(x, model.Ndim).reshape(1, -1), model, _vec(b, model.Ndim).reshape(1, -1), P, maxiter)
+        return int(it[0]), float(res[0]), int(fl[0])
+    assert not model.transposed, "the CG path solves MtM x = b, as the reference does"
+    use = _use_prec(P, model)
     model._push_solver()
     it, fl, res = C.c_int64(), C.c_int(), C.c_double()
-    check(model._lib.elph_ldiv(model._h, dptr(_vec(x, model.Ndim)), dptr(_vec(b, model.Ndim)), _use_prec(P), maxiter,
+    check(model._lib.elph_ldiv(model._h, dptr(_vec(x, model.Ndim)), dptr(_vec(b, model.Ndim)), use, maxiter,
                                C.byref(it), C.byref(res), C.byref(fl)))
     return int(it.value), float(res.value), int(fl.value)
 
 
 def ldiv_batched_(X, model, B, P=None, maxiter=0):
     """nrhs independent solves of the same matrix advanced together; X, B: (nrhs, Ndim) arrays."""
+    use = _use_prec(P, model)
     model._push_solver()
     nrhs = B.shape[0]
     assert X.shape == B.shape == (nrhs, model.Ndim)
     it = np.zeros(nrhs, dtype=np.int64)
     res = np.zeros(nrhs)
     fl = np.zeros(nrhs, dtype=np.int32)
-    check(model._lib.elph_ldiv_batched(model._h, nrhs, dptr(X), dptr(B), _use_prec(P), maxiter, iptr(it), dptr(res),
+    if model.mul_by_M:
+        check(model._lib.elph_mldiv(model._h, SOLVER_CODES[type(model.solver)], int(bool(model.transposed)), nrhs, dptr(X), dptr(B),
+                                    use, maxiter, _restart(model.solver), iptr(it), dptr(res), fl.ctypes.data_as(_lib.P_int)))
+        return it, res, fl
+    check(model._lib.elph_ldiv_batched(model._h, nrhs, dptr(X), dptr(B), use, maxiter, iptr(it), dptr(res),
                                        fl.ctypes.data_as(_lib.P_int)))
     return it, res, fl

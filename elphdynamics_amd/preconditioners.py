@@ -1,12 +1,14 @@
-"""Mirror of KPMPreconditioners.jl (symmetric / CG variant) and FourierAcceleration.jl on the GPU path.
+"""Mirror of KPMPreconditioners.jl and FourierAcceleration.jl on the GPU path.
 
-    P = SymmetricKPMPreconditioner(model, n, buf, c1, c2)     KPMPreconditioners.jl:219-235
-    setup_(P[, rng | e_min=, e_max=])                         :259-321
-    ldiv_(z, P, r)                                            :426-481
+    P = SymmetricKPMPreconditioner(model, n, buf, c1, c2)     KPMPreconditioners.jl:219-235   (CG on MtM)
+    P = LeftKPMPreconditioner(...) / RightKPMPreconditioner(...) / LeftRightKPMPreconditioner(...)      (GMRES, BiCGStab on M or Mt)
+    setup_(P[, rng | e_min=, e_max=])                         :259-321   (every variant: setup! of the one expansion they share)
+    kpm_ldiv_(z, P, r)                                        :426-481; one side: :494-600
     fa = FourierAccelerator(model); update_M_/update_Q_;      FourierAcceleration.jl:11-82,149-167
     fourier_accelerate_(v_out, fa, v, power, use_mass=False)  :91-143
 
-The Left/Right/LeftRight KPM variants belong to GMRES/BiCGStab and are out of scope.
+The Left preconditioner approximates M^-1, the Right one M^-T, and LeftRight is the one of the two that model.transposed selects
+(:494-508); all sit on the expansion the handle holds, so Left after Right is the symmetric apply.
 """
 import ctypes as C
 import math
@@ -17,8 +19,16 @@ from ._lib import check, dptr
 
 
 class SymmetricKPMPreconditioner:
-    def __init__(self, model, n=20, buf=0.05, c1=1.0, c2=1.0):
+    def __init__(self, model, n=20, buf=0.05, c1=1.0, c2=1.0, expansion=None):
+        """expansion: another preconditioner of the same model whose expansion this one shares (the `expansion` field the reference's
+        variants have in common, KPMPreconditioners.jl:101-146); without it the handle's expansion is made anew — a handle holds ONE, so
+        preconditioners made earlier on it then need setup_ again."""
         self.model = model
+        if expansion is not None:
+            assert expansion.model is model
+            self.n, self.buf, self.c1, self.c2 = expansion.n, expansion.buf, expansion.c1, expansion.c2
+            self.active, self.lam_lo, self.lam_hi = expansion.active, expansion.lam_lo, expansion.lam_hi
+            return
         self.n, self.buf, self.c1, self.c2 = int(n), float(buf), float(c1), float(c2)
         check(model._lib.elph_kpm_create(model._h, self.n, self.buf, self.c1, self.c2))
         self.active = True
@@ -31,6 +41,28 @@ class SymmetricKPMPreconditioner:
         tot = C.c_int64()
         check(self.model._lib.elph_kpm_orders(self.model._h, o.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(tot)))
         return o
+
+
+class LeftKPMPreconditioner(SymmetricKPMPreconditioner):
+    """M^-1 by the expansion, frequency block by frequency block (KPMPreconditioners.jl:514-554): for M x = b."""
+
+    def side_for(self, model):
+        """The side applied for this model: False the Left (M^-1), True the Right (M^-T) one."""
+        return False
+
+
+class RightKPMPreconditioner(SymmetricKPMPreconditioner):
+    """M^-T by the expansion with the conjugated coefficients (KPMPreconditioners.jl:560-600): for Mt x = b."""
+
+    def side_for(self, model):
+        return True
+
+
+class LeftRightKPMPreconditioner(SymmetricKPMPreconditioner):
+    """The Left preconditioner while model.transposed is false, the Right one while it is true (KPMPreconditioners.jl:494-508)."""
+
+    def side_for(self, model):
+        return bool(model.transposed)
 
 
 def setup_(P, rng=None, e_min=None, e_max=None, b_max=None, b_min=None):
@@ -81,11 +113,16 @@ def setup_chains_(P, rng=None, e_min=None, e_max=None, b_max=None, b_min=None):
 
 
 def kpm_ldiv_(z, P, r):
-    """ldiv!(z, P, r): z = P^-1 r; plain copy for the identity (IterativeSolvers.jl:14-17)."""
+    """ldiv!(z, P, r): z = P^-1 r; plain copy for the identity (IterativeSolvers.jl:14-17).  A one-sided preconditioner also takes
+    (nvec, Ndim) arrays: vector k goes through the expansion of chain k % nchains."""
     if P is None:
         z[:] = r
         return
     m = P.model
+    if hasattr(P, "side_for"):                       # one side of the expansion; LeftRight: the one model.transposed selects
+        assert z.shape == r.shape and r.size % m.Ndim == 0
+        check(m._lib.elph_kpm_apply_side(m._h, r.size // m.Ndim, dptr(z), dptr(r), int(P.side_for(m))))
+        return
     check(m._lib.elph_kpm_apply(m._h, dptr(z), dptr(r)))
 
 

@@ -878,6 +878,41 @@ int elph_kpm_orders(elph_handle h, int64_t *orders, int64_t *total);
 int elph_kpm_apply(elph_handle h, double *z, const double *r);
 int elph_kpm_apply_dev(elph_handle h, double *z_dev, const double *r_dev);
 
+/* ---- BiCGStab and GMRES on M x = b or Mᵀ x = b (csrc/msolve.hip): the solvers of `mul_by_M = true` models, HolsteinModels.jl:286-298 ----
+ *
+ * One side of the expansion of the last setup!, on nvec vectors in the reference layout (vector r: the expansion of chain r % nchains) —
+ * mul!(v′, P, v) per frequency block between the twisted transforms: transposed = 0 the LeftKPMPreconditioner ~ M⁻¹ (KPMPreconditioners.jl:514-554), transposed = 1 the
+ * RightKPMPreconditioner ~ M⁻ᵀ with the conjugated coefficients (:560-600); Left after Right is the symmetric apply above.  An inactive
+ * expansion copies (:475-478). */
+int elph_kpm_apply_side(elph_handle h, int nvec, double *vout, const double *vin, int transposed);
+
+#define ELPH_SOLVER_BICGSTAB 1
+#define ELPH_SOLVER_GMRES 2
+
+/* solve!(x, A, b, solver[, P]; maxiter, tol) -> iters for nrhs right-hand sides at once (IterativeSolvers.jl:354-417 BiCGStab, :464-570
+ * GMRES with update! :552-570 and the rotations :572-584), A = M (transposed = 0) or Mᵀ (1).  X: initial guesses in, solutions out; X, B:
+ * double[nrhs*ndim], RHS-major; right-hand side r uses chain r % nchains; each follows exactly the single-vector recurrences and stop rule,
+ * every inner product is summed in a fixed order.  use_precond: the side of the expansion that LeftRightKPMPreconditioner takes for
+ * model.transposed (:494-508) — Left for transposed = 0, Right for 1.  tol = 0: the handle's; solver_maxiter is the solver's own maxiter field
+ * (0: the handle's), maxiter the call's keyword (0: solver_maxiter); restart < 0: min(20, ndim) (:448-450; ignored by BiCGStab).
+ * As the reference executes: BiCGStab returns maxiter on breakdown (ρ = 0, ω = 0); GMRES runs whole cycles — iter < maxiter is tested between
+ * cycles only, inside a cycle only the tolerance and iter == solver_maxiter end it, so iters may exceed a maxiter below solver_maxiter.
+ * ONE deliberate difference: a cycle cut at iter == solver_maxiter after i < restart steps updates x with the i columns it built; the
+ * reference back-substitutes over all `restart` columns there (:538), through columns this cycle never wrote (0/0 in the first cycle).
+ * Whenever solver_maxiter is a multiple of restart the two coincide.
+ * GMRES keeps its Krylov basis on the device from the first GMRES solve until the handle is destroyed: (restart + 1) ndim doubles per
+ * right-hand side (6.9 MB at 16 x 16 sites, 160 slices, restart 20).
+ * ELPH_E_STATE on a sharded handle or one with a restricted inner-product range. */
+int elph_msolve(elph_handle h, int solver, int transposed, int nrhs, double *X, const double *B, int use_precond, double tol,
+                int64_t maxiter, int64_t solver_maxiter, int restart, int64_t *iters);
+
+/* ldiv!(x, model, b[, P]; maxiter) of a mul_by_M model for nrhs right-hand sides (Models.jl:74-186) with the handle's tol and maxiter
+ * (the solver-set entry point above): the solve, the true residual |A x - b| / |b|, flag 0 / 1 (out of iterations: iters == maxiter with a
+ * preconditioner, :103; == solver.maxiter without, :160) / 2, x zeroed where the flag is positive; a flagged preconditioned right-hand side
+ * is solved again without the expansion from x = 0 with 10 maxiter (:129-133) and reports that solve. */
+int elph_mldiv(elph_handle h, int solver, int transposed, int nrhs, double *X, const double *B, int use_precond, int64_t maxiter,
+               int restart, int64_t *iters, double *residual_error, int *flag);
+
 /* ---------------------------------------------------------------- Fourier acceleration */
 
 /* fourier_accelerate!(v', fa, v, power; use_mass) — FourierAcceleration.jl:91-143, real in/out.
