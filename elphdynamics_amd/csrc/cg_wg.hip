@@ -539,10 +539,20 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             // a slab-PAIR-major forward sweep (colours 0 .. 2 of the next pair under a pair's crossing, 52 vector instructions of cover
             // instead of 12 .. 26) measured 3 % SLOWER than the parent — consecutive colours of one pair depend on each other, colours of
             // different pairs do not (profiles/wg_sweep_order).
+            // The forward prologue's ten reads of exp(-dtau V) go out together, into the registers of w (z was consumed by the fused pass:
+            // they are free), in a scheduling region of their own, and the products retire them with counted waits — the compiler, no
+            // register to spare, had serialised them (read, wait, two products, read, ...: eight waits with 0 .. 4 vector instructions of
+            // cover at the very top of every wave's chain).  The same v_mul_f64 on the same operands.
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k <= T; ++k)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) w[k][q] = EXPV(k, q) * p[k][q];
+                for (int q = 0; q < 4; ++q) w[k][q] = EXPV(k, q);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k <= T; ++k)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[k][q] = w[k][q] * p[k][q];
             auto fwd_tail = [&](auto kc) __attribute__((always_inline)) {              // w(t0+k) from the swept slab k
                 constexpr int k = decltype(kc)::value;
                 const double sg = sgn(wrap(t0 + k)) * X.k4;
@@ -1033,8 +1043,20 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             if (G > 1 && (wv == 0 || wv == W - 1)) {          // the neighbouring workgroup's boundary slice of the new residual
                 double *rh = rhalo + ((wv == 0) ? 0 : HSL);
                 const double *zh = zhalo + ((wv == 0) ? 0 : HSL);
+                if constexpr (SQ && !SSH && UNI && T == 4) {
+                    // (4 slices per wave: the four reads at once and the results written in one group — left alone it is two serialised
+                    //  read-wait-fma-write groups, the stores to rh are in the way of the reads behind them, while the other six waves
+                    //  already wait at the barrier below.  No `lwok`: every lane of this form holds sites.)
+                    double rhv[NPL], zhv[NPL];
 #pragma unroll
-                for (int q = 0; q < NPL; ++q) if (lwok) rh[lr + q * LSL] = rh[lr + q * LSL] - alpha_f * zh[lr + q * LSL];
+                    for (int q = 0; q < NPL; ++q) { rhv[q] = rh[lr + q * LSL]; zhv[q] = zh[lr + q * LSL]; }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) rh[lr + q * LSL] = rhv[q] - alpha_f * zhv[q];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) if (lwok) rh[lr + q * LSL] = rh[lr + q * LSL] - alpha_f * zh[lr + q * LSL];
+                }
             }
             STAMP(3);
         }
