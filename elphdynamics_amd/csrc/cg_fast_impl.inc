@@ -1115,7 +1115,7 @@ int LPFN(elph_fast_kpm_cheb_lds)(elph_handle_s *h, int nrhs, const CgState *st, 
     const int Lo2 = (int)((h->L + 1) / 2);
     const size_t shm = (size_t)(2 * (h->npl * WAVE + 2 * WAVE) + 2 * h->npl * WAVE) * sizeof(double);
     DISPATCH_NPL_F(h->npl, {
-        hipLaunchKernelGGL((k_kpm_cheb_ri<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3(2 * WAVE), shm, h->stream, h->d_nu, K, m,
+        hipLaunchKernelGGL((k_kpm_cheb_ri<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3(2 * WAVE), shm, h->stream, h->work.nu, K, m,
                            Lo2, st, rz_part, nrz, rr_part);
     });
     return elph_launch_check("k_kpm_cheb_ri");

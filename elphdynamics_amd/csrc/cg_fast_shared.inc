@@ -332,11 +332,11 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, 
         // one frequency per block (the kernel loops over y, y + gridDim.y, ...: 2, 4 or 8 frequencies per block were measured — no
         // faster at 1 right-hand side or at 128: block dispatch is not what the kernel waits for)
 #define SQ_LAUNCH(PV, UV, ...) hipLaunchKernelGGL((k_kpm_cheb_sq<PV, UV, ##__VA_ARGS__>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
-                                             h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
+                                             h->work.nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
         const int P = h->shape.dpp();
         if (P == 2 && h->kpm.sq_chain_uniform && nrhs >= 16) {
             hipLaunchKernelGGL((k_kpm_cheb_sq_w4<2, true, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                               h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+                               h->work.nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         } else if (P == 2) { if (h->kpm.sq_chain_uniform) SQ_LAUNCH(2, true, true); else SQ_LAUNCH(2, false, true); }
         else        { if (h->kpm.sq_chain_uniform) SQ_LAUNCH(1, true); else SQ_LAUNCH(1, false); }
 #undef SQ_LAUNCH
@@ -344,19 +344,19 @@ int elph_fast_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, bool reg, 
     }
     if (form == REG_SQ_GRID) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                           h->d_nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+                           h->work.nu, K, h->kpm.d_sq_cbar, h->kpm.d_sq_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         return elph_launch_check("k_kpm_cheb_sq(grid)");
     }
     if (form == REG_HC_GRID) {
 #define HG_LAUNCH(NV) hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, false, false, NV>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream, \
-                                         h->d_nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
+                                         h->work.nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct)
         if (hgn == 2) HG_LAUNCH(2); else if (hgn == 4) HG_LAUNCH(4); else HG_LAUNCH(8);
 #undef HG_LAUNCH
         return elph_launch_check("k_kpm_cheb_sq(honeycomb grid)");
     }
     if (form == REG_HC12) {
         hipLaunchKernelGGL((k_kpm_cheb_sq<2, true, false, true>), dim3((unsigned)nrhs, gy), dim3(2 * WAVE), 0, h->stream,
-                           h->d_nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
+                           h->work.nu, K, h->kpm.d_cbar, h->kpm.d_sbar, (int)h->N, Lo2, st, rz_part, nrz, (int)h->L, rr_part, fold_nct);
         return elph_launch_check("k_kpm_cheb_sq(honeycomb)");
     }
 #else

@@ -1595,8 +1595,8 @@ int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iter
     R.G = P.G; R.W = P.W;
     R.fixed_iters = fixed_iters;
     R.x0_zero = x0_zero ? 1 : 0;           // (x0 = 0 known: the 4-slice DPP shape has an instantiation that does not read it)
-    if (x0_save)                // the caller's initial guess survives for the fallback (run_cg: in d_zp, unused by an un-preconditioned solve)
-        HIPCHK(hipMemcpyAsync(x0_save, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (x0_save)                // the caller's initial guess survives for the fallback (run_cg: in work.zp, unused by an un-preconditioned solve)
+        HIPCHK(hipMemcpyAsync(x0_save, h->work.x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     const dim3 grid((unsigned)(8 * ((nrhs + 7) / 8) * P.G));       // one solve per workgroup: every right-hand side has its team in the grid
     RC(wg::launch(P, wg::PLAIN, x0_zero, grid, h->stream, B, m, R));
     h->res.launched(P.T, P.W, P.G);

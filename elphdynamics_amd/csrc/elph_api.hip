@@ -298,34 +298,92 @@ static int upload_lp_cs(elph_handle_s *h) {
 // life cycle
 // ------------------------------------------------------------------------------------------
 
-static int ensure_capacity(elph_handle_s *h, int nrhs) {
-    if (nrhs <= h->cap_rhs) return ELPH_OK;
+int elph_work_reserve(elph_handle_s *h, int nrhs) {
+    SolveWork &W = h->work;
+    if (nrhs <= W.cap_rhs) return ELPH_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t nd = (size_t)h->ndim, c = (size_t)nrhs;
-    RC(dev_alloc(&h->d_stage_in, c * nd));
-    RC(dev_alloc(&h->d_stage_out, c * nd));
-    RC(dev_alloc(&h->d_b, c * nd));
-    RC(dev_alloc(&h->d_x, c * nd));
-    RC(dev_alloc(&h->d_r, c * nd));
-    RC(dev_alloc(&h->d_z, c * nd));
-    RC(dev_alloc(&h->d_zp, c * nd));
-    RC(dev_alloc(&h->d_tmp, c * nd));
-    RC(dev_alloc(&h->d_p, 2 * c * nd));
-    RC(dev_alloc(&h->d_phi, 2 * nd));
-    RC(dev_alloc(&h->d_xfield, nd));
-    RC(dev_alloc(&h->d_part, 4 * c * (size_t)h->L * (size_t)h->npl));
-    RC(dev_alloc(&h->d_state, 2 * c));
-    RC(dev_alloc(&h->d_scal, 4 * c));
-    RC(dev_alloc(&h->d_alpha, c));
-    const size_t Lo2 = (size_t)(h->L + 1) / 2, Lh = (size_t)h->L / 2 + 1;
-    RC(dev_alloc(&h->d_nu, c * std::max(std::max(Lo2, Lh) * (size_t)h->N, nd)));
-    if (h->h_state) HIPCHK(hipHostFree(h->h_state));
-    if (h->h_scal) HIPCHK(hipHostFree(h->h_scal));
-    HIPCHK(hipHostMalloc((void **)&h->h_state, 2 * c * sizeof(CgState), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&h->h_scal, 4 * c * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipMemsetAsync(h->d_part, 0, 4 * c * (size_t)h->L * (size_t)h->npl * sizeof(double), h->stream));
-    h->cap_rhs = nrhs;
+    const size_t Lo2 = (size_t)(h->L + 1) / 2, Lh = (size_t)h->L / 2 + 1, c = (size_t)nrhs;
+    W.ndim = (size_t)h->ndim; W.nnu = Lo2 * (size_t)h->N; W.nrz = (size_t)h->L * (size_t)h->npl;
+    for (double **v : {&W.stage_in, &W.stage_out, &W.b, &W.x, &W.r, &W.z, &W.zp, &W.tmp}) RC(dev_alloc(v, c * W.ndim));
+    RC(dev_alloc(&W.p, 2 * c * W.ndim));
+    RC(dev_alloc(&W.phi, 2 * W.ndim));
+    RC(dev_alloc(&W.xfield, W.ndim));
+    RC(dev_alloc(&W.sums, 4 * c * W.nrz));
+    RC(dev_alloc(&W.state, 2 * c));
+    RC(dev_alloc(&W.scal, 4 * c));
+    RC(dev_alloc(&W.alpha, c));
+    RC(dev_alloc(&W.nu, c * std::max(std::max(Lo2, Lh) * (size_t)h->N, W.ndim)));      // (the plain transforms' Lh frequencies fit too)
+    if (W.h_state) HIPCHK(hipHostFree(W.h_state));
+    if (W.h_scal) HIPCHK(hipHostFree(W.h_scal));
+    HIPCHK(hipHostMalloc((void **)&W.h_state, 2 * c * sizeof(CgState), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&W.h_scal, 4 * c * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(W.sums, 0, 4 * c * W.nrz * sizeof(double), h->stream));
+    W.cap_rhs = nrhs;
     return ELPH_OK;
+}
+
+void elph_work_release(elph_handle_s *h) {
+    SolveWork &W = h->work;
+    void *ptrs[] = {W.stage_in, W.stage_out, W.b, W.x, W.r, W.z, W.zp, W.tmp, W.p, W.nu, W.sums, W.state, W.alpha, W.scal, W.hist, W.phi, W.xfield};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (W.h_state) (void)hipHostFree(W.h_state);
+    if (W.h_scal) (void)hipHostFree(W.h_scal);
+    W = SolveWork();
+}
+
+// elements of a staged transfer; refuses one the staging buffers do not hold
+static int staged_size(elph_handle_s *h, int nvec, int ncols, size_t *n) {
+    *n = (size_t)nvec * (size_t)(ncols ? ncols : h->N) * (size_t)h->L;
+    const size_t held = (size_t)h->work.cap_rhs * h->work.ndim;
+    if (*n > held) { elph_set_error("staging %zu doubles, the staging buffers hold %zu", *n, held); return ELPH_E_STATE; }
+    return ELPH_OK;
+}
+
+int elph_stage_in(elph_handle_s *h, double *dstS, const double *hostR, int nvec, int ncols) {
+    size_t n = 0;
+    RC(staged_size(h, nvec, ncols, &n));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, hostR, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return elph_launch_r2s(h, dstS, h->work.stage_in, nvec, ncols);
+}
+
+int elph_stage_out(elph_handle_s *h, double *hostR, const double *srcS, int nvec, int ncols) {
+    size_t n = 0;
+    RC(staged_size(h, nvec, ncols, &n));
+    RC(elph_launch_s2r(h, h->work.stage_out, srcS, nvec, ncols));
+    HIPCHK(hipMemcpyAsync(hostR, h->work.stage_out, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return ELPH_OK;
+}
+
+int elph_retry_in_slot0(elph_handle_s *h, int r, const std::function<int()> &solve_and_flag) {
+    SolveWork &W = h->work;
+    const size_t bytes = W.ndim * sizeof(double);
+    if (r != 0) {
+        HIPCHK(hipMemcpyAsync(W.stage_out, W.x, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(W.stage_in, W.b, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(W.x, W.x + r * W.ndim, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(W.b, W.b + r * W.ndim, bytes, hipMemcpyDeviceToDevice, h->stream));
+    }
+    if (h->nchains > 1) h->solo_chain = r % h->nchains;   // slot 0 must keep rhs r's fermion matrix
+    const int rc = solve_and_flag();
+    h->solo_chain = -1;
+    RC(rc);
+    if (r != 0) {
+        HIPCHK(hipMemcpyAsync(W.x + r * W.ndim, W.x, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(W.x, W.stage_out, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(W.b, W.stage_in, bytes, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return ELPH_OK;
+}
+
+void elph_fold_pair(int nch, const int64_t *it2, const int *fl2, int64_t *iters, int *flag) {
+    for (int c = 0; c < nch; ++c) {
+        int64_t tot = it2[c];
+        int fl = fl2[c];
+        if (fl == 0) { tot += it2[nch + c]; fl = fl2[nch + c]; }      // a failed first solve suppresses the second (:880)
+        if (fl == 0) tot = (tot + 1) / 2;                             // cld(iters, 2)  (:907-909)
+        iters[c] = tot;
+        flag[c] = fl;
+    }
 }
 
 // the bond-table arguments of elph_create (and of the recognition probe)
@@ -432,7 +490,7 @@ extern "C" int elph_create(elph_handle *out, int kind, int64_t nsites, int64_t l
     if ((rc = elph_dft_build_tables(h))) return fail(rc);
     if ((rc = build_lane_program(h))) return fail(rc);
     if ((rc = upload_lp_cs(h))) return fail(rc);
-    if ((rc = ensure_capacity(h, 1))) return fail(rc);
+    if ((rc = elph_work_reserve(h, 1))) return fail(rc);
     if (hipStreamSynchronize(h->stream) != hipSuccess) { elph_set_error("sync failed"); return fail(ELPH_E_HIP); }
     *out = h;
     return ELPH_OK;
@@ -449,13 +507,10 @@ extern "C" int elph_destroy(elph_handle h) {
     elph_msolve_free(h);
     elph_dft_free(h);
     elph_kpm_free(h);
-    void *ptrs[] = {h->d_bi, h->d_bj, h->d_coloff, h->d_c, h->d_s, h->d_E, h->d_lam, h->d_stage_in, h->d_stage_out,
-                    h->d_b, h->d_x, h->d_r, h->d_z, h->d_zp, h->d_p, h->d_tmp, h->d_part, h->d_state, h->d_phi, h->d_xfield,
-                    h->d_hist, h->d_scal, h->d_alpha, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar, h->d_ssh_cb, h->d_ssh_slot, h->d_nu, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s,
-                    h->d_sq_bond, h->d_pg_bond, h->res.d_res, h->d_mu_ch};
+    elph_work_release(h);
+    void *ptrs[] = {h->d_bi, h->d_bj, h->d_coloff, h->d_c, h->d_s, h->d_E, h->d_lam, h->d_ssh_x, h->d_ssh_par, h->d_ssh_tbare, h->d_ssh_bar,
+                    h->d_ssh_cb, h->d_ssh_slot, h->d_diag, h->d_lp_ij, h->d_lp_c, h->d_lp_s, h->d_sq_bond, h->d_pg_bond, h->res.d_res, h->d_mu_ch};
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (h->h_state) (void)hipHostFree(h->h_state);
-    if (h->h_scal) (void)hipHostFree(h->h_scal);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     for (int k = 1; k < ELPH_SPLIT_PARTS; ++k)
         if (h->split_stream[k]) (void)hipStreamDestroy(h->split_stream[k]);
@@ -496,9 +551,9 @@ extern "C" int elph_update_model_holstein(elph_handle h, const double *x, const 
     HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, x, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, x, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
     set_nchains(h, 1);   // expansions were per chain
-    RC(elph_launch_expV(h, h->d_stage_in, dtau));
+    RC(elph_launch_expV(h, h->work.stage_in, dtau));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
     return ELPH_OK;
@@ -522,9 +577,9 @@ extern "C" int elph_update_model_holstein_chains(elph_handle h, int nchains, con
     HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     // all configurations in one transfer (the staging buffer holds cap_rhs vectors), one exp kernel per chain, one sync
-    RC(ensure_capacity(h, nchains));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, X, (size_t)nchains * nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    for (int c = 0; c < nchains; ++c) RC(elph_launch_expV(h, h->d_stage_in + (size_t)c * nd, dtau, c));
+    RC(elph_work_reserve(h, nchains));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, X, (size_t)nchains * nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    for (int c = 0; c < nchains; ++c) RC(elph_launch_expV(h, h->work.stage_in + (size_t)c * nd, dtau, c));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
     h->kpm.ready = false;   // the preconditioner belongs to ONE configuration
@@ -535,9 +590,9 @@ extern "C" int elph_set_expV(elph_handle h, const double *expnDtauV) {
     CHECK_H(h);
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!expnDtauV) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, expnDtauV, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, expnDtauV, (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
     set_nchains(h, 1);   // expansions were per chain
-    RC(elph_launch_r2s(h, h->d_E, h->d_stage_in, 1));
+    RC(elph_launch_r2s(h, h->d_E, h->work.stage_in, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_E = true;
     return ELPH_OK;
@@ -697,23 +752,23 @@ static int need_model(elph_handle_s *h) {
 static int mul_dev(elph_handle_s *h, int which, double *y_dev, const double *v_dev) {
     RC(need_model(h));
     if (!y_dev || !v_dev) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    RC(elph_launch_r2s(h, h->d_b, v_dev, 1));
+    RC(elph_launch_r2s(h, h->work.b, v_dev, 1));
     if (which == 3) {                                    // M Mᵀ v (Models.jl:229-238): two launches, not on the CG path
-        RC(elph_launch_mul(h, 1, h->d_tmp, h->d_b, 1));
-        RC(elph_launch_mul(h, 0, h->d_x, h->d_tmp, 1));
+        RC(elph_launch_mul(h, 1, h->work.tmp, h->work.b, 1));
+        RC(elph_launch_mul(h, 0, h->work.x, h->work.tmp, 1));
     } else {
-        RC(elph_launch_mul(h, which, h->d_x, h->d_b, 1));
+        RC(elph_launch_mul(h, which, h->work.x, h->work.b, 1));
     }
-    RC(elph_launch_s2r(h, y_dev, h->d_x, 1));
+    RC(elph_launch_s2r(h, y_dev, h->work.x, 1));
     return ELPH_OK;
 }
 
 static int mul_host(elph_handle_s *h, int which, double *y, const double *v) {
     if (!y || !v) { elph_set_error("null argument"); return ELPH_E_ARG; }
     const size_t bytes = (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, v, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(mul_dev(h, which, h->d_stage_out, h->d_stage_in));
-    HIPCHK(hipMemcpyAsync(y, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, v, bytes, hipMemcpyHostToDevice, h->stream));
+    RC(mul_dev(h, which, h->work.stage_out, h->work.stage_in));
+    HIPCHK(hipMemcpyAsync(y, h->work.stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -811,8 +866,8 @@ struct SplitRun {
     elph_handle_s *main = nullptr, *view[ELPH_SPLIT_PARTS] = {};
     CgPlan before;                                        // the whole batch's plan (split_begin replaces it with the parts')
     SplitRun(elph_handle_s *h, int nrhs) : n1(nrhs), main(h) { view[0] = h; }
-    // A solve that leaves through an error return must not leave kernels of the other streams in flight behind it (they write d_x, d_p, d_r,
-    // d_state of their parts while the caller's next step — ldiv's zero-fill, a retry, a new solve — runs on the main stream), nor the handle
+    // A solve that leaves through an error return must not leave kernels of the other streams in flight behind it (they write work.x, work.p, work.r,
+    // work.state of their parts while the caller's next step — ldiv's zero-fill, a retry, a new solve — runs on the main stream), nor the handle
     // believing in a plan that never ran to its end.
     ~SplitRun() {
         for (int k = 1; k < ways; ++k)
@@ -861,14 +916,9 @@ static int split_begin(elph_handle_s *h, int nrhs, SplitRun &S) {
     if (!h->split_ev) HIPCHK(hipEventCreateWithFlags(&h->split_ev, hipEventDisableTiming));
     h->plan = elph_plan_cg(h, S.n1, true, nrhs);          // (split_legal: the parts run p/x-fused whatever the whole batch would have run)
     HIPCHK(hipEventRecord(h->split_ev, h->stream));       // the start state (x0, r0, p0, rho0 of every right-hand side) is on the main stream
-    const size_t nd = (size_t)h->ndim, Lo2 = (size_t)(h->L + 1) / 2, nrz = (size_t)h->L * (size_t)h->npl;
     for (int k = 1; k < S.ways; ++k) {
         elph_handle_s *v = S.view[k] = new elph_handle_s(*h);
-        const size_t r0 = (size_t)k * (size_t)S.n1;
-        v->d_x += r0 * nd; v->d_r += r0 * nd; v->d_z += r0 * nd; v->d_zp += r0 * nd; v->d_b += r0 * nd; v->d_tmp += r0 * nd; v->d_p += r0 * nd;
-        v->d_nu += r0 * Lo2 * (size_t)h->N;
-        v->d_state += 2 * r0; v->h_state += 2 * r0; v->d_alpha += r0;
-        v->d_part += r0 * nrz;    // the three partial-sum arrays lie cap_rhs * nrz apart and are indexed [rhs][<= nrz]: one offset serves all
+        v->work = h->work.part((size_t)k * (size_t)S.n1);
         v->stream = h->split_stream[k];
         HIPCHK(hipStreamWaitEvent(v->stream, h->split_ev, 0));
     }
@@ -896,11 +946,11 @@ static int split_join(SplitRun &S) {
 // right-hand side whose newer state copy is terminal; *all_done: every one is
 static int read_states(const SplitRun &S, int64_t *iters, bool *all_done) {
     for (int k = 0; k < S.ways; ++k)
-        HIPCHK(hipMemcpyAsync(S.view[k]->h_state, S.view[k]->d_state, sizeof(CgState) * 2 * (size_t)S.n1, hipMemcpyDeviceToHost, S.view[k]->stream));
+        HIPCHK(hipMemcpyAsync(S.view[k]->work.h_state, S.view[k]->work.state, sizeof(CgState) * 2 * (size_t)S.n1, hipMemcpyDeviceToHost, S.view[k]->stream));
     for (int k = 0; k < S.ways; ++k) HIPCHK(hipStreamSynchronize(S.view[k]->stream));
     *all_done = true;
     for (int r = 0; r < S.ways * S.n1; ++r) {
-        const CgState &a = S.main->h_state[2 * r], &b = S.main->h_state[2 * r + 1];
+        const CgState &a = S.main->work.h_state[2 * r], &b = S.main->work.h_state[2 * r + 1];
         const CgState &s = (b.seq > a.seq) ? b : a;
         if (!s.done) *all_done = false;
         else iters[r] = s.iters;
@@ -911,7 +961,7 @@ static int read_states(const SplitRun &S, int64_t *iters, bool *all_done) {
 // the eps histories of a finished solve (host, nrhs x (maxiter + 1); nullptr: none recorded)
 static int read_hist(elph_handle_s *h, int nrhs, int64_t maxiter, double *eps_hist) {
     if (!eps_hist) return ELPH_OK;
-    HIPCHK(hipMemcpyAsync(eps_hist, h->d_hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(eps_hist, h->work.hist, sizeof(double) * (size_t)nrhs * (size_t)(maxiter + 1), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -956,11 +1006,11 @@ static int resident_attempt(elph_handle_s *h, const SplitRun &S, int nrhs, int u
         return ELPH_OK;
     }
     elph_wg_timed_out(h);
-    HIPCHK(hipMemcpyAsync(h->d_x, x0_save, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.x, x0_save, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return elph_launch_cg_init(h, nrhs, use_prec);
 }
 
-// Runs CG on d_b / d_x (layout S) for nrhs right-hand sides.  Returns per-rhs iteration counts.
+// Runs CG on work.b / work.x (layout S) for nrhs right-hand sides.  Returns per-rhs iteration counts.
 static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t maxiter, double kmax, int64_t *iters,
                   double *eps_hist /* host, optional, nrhs*(maxiter+1) */) {
     const bool x0_zero = h->x_zero;        // the hint belongs to THIS solve: consumed before anything can return
@@ -972,10 +1022,10 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
     P.hist_stride = maxiter + 1;
     if (eps_hist) {
         const int64_t need = (int64_t)nrhs * (maxiter + 1);
-        if (need > h->hist_cap) {
+        if (need > h->work.hist_cap) {
             HIPCHK(hipStreamSynchronize(h->stream));
-            RC(dev_alloc(&h->d_hist, (size_t)need));
-            h->hist_cap = need;
+            RC(dev_alloc(&h->work.hist, (size_t)need));
+            h->work.hist_cap = need;
         }
     }
     h->cur_params = P;
@@ -993,7 +1043,7 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
             RC(elph_i_slabs_solve(h, nrhs, P, 0, iters, &solved, nullptr));
             if (!solved) RC(elph_launch_cg_init(h, nrhs, use_prec, true));      // (x is zero again: elph_i_slabs_solve)
         } else {
-            RC(resident_attempt(h, S, nrhs, use_prec, P, x0_zero, use_prec ? h->d_tmp : h->d_zp, iters, &solved));
+            RC(resident_attempt(h, S, nrhs, use_prec, P, x0_zero, use_prec ? h->work.tmp : h->work.zp, iters, &solved));
         }
         if (solved) return read_hist(h, nrhs, maxiter, eps_hist);
     }
@@ -1015,16 +1065,16 @@ static int run_cg(elph_handle_s *h, int nrhs, int use_prec, double tol, int64_t 
     return read_hist(h, nrhs, maxiter, eps_hist);
 }
 
-// residual + flag logic of ldiv! for rhs already solved into d_x; zeroes x where flag > 0
+// residual + flag logic of ldiv! for rhs already solved into work.x; zeroes x where flag > 0
 static int residual_and_flags(elph_handle_s *h, int nrhs, const int64_t *iters, int64_t cmp_maxiter, double *resid, int *flag) {
     RC(elph_launch_residual(h, nrhs));
-    HIPCHK(hipMemcpyAsync(h->h_scal, h->d_scal, sizeof(double) * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.h_scal, h->work.scal, sizeof(double) * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int r = 0; r < nrhs; ++r) {
-        resid[r] = h->h_scal[r];
+        resid[r] = h->work.h_scal[r];
         if (resid[r] > sqrt(h->tol)) {           // Models.jl:100,157 (NaN compares false, as in the reference)
             flag[r] = (iters[r] == cmp_maxiter) ? 1 : 2;
-            RC(elph_launch_zero(h, h->d_x + (size_t)r * (size_t)h->ndim, h->ndim));   // fill!(x,0)
+            RC(elph_launch_zero(h, h->work.x + (size_t)r * (size_t)h->ndim, h->ndim));   // fill!(x,0)
         } else {
             flag[r] = 0;
         }
@@ -1032,7 +1082,7 @@ static int residual_and_flags(elph_handle_s *h, int nrhs, const int64_t *iters, 
     return ELPH_OK;
 }
 
-// ldiv! on device-resident layout-S d_b/d_x
+// ldiv! on device-resident layout-S work.b/work.x
 static int ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag) {
     RC(need_model(h));
     if (maxiter == 0) maxiter = h->maxiter;                                  // Models.jl:78-80,143-145
@@ -1046,28 +1096,12 @@ static int ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, 
     // failed right-hand sides: retry without preconditioner, 10x maxiter, from x = 0 (Models.jl:129-133)
     for (int r = 0; r < nrhs; ++r) {
         if (flag[r] == 0) continue;
-        const size_t nd = (size_t)h->ndim;
-        if (r != 0) {
-            // park rhs 0, move rhs r into slot 0, solve single, move back
-            HIPCHK(hipMemcpyAsync(h->d_tmp, h->d_x, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_z, h->d_b, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_x, h->d_x + r * nd, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_b, h->d_b + r * nd, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_stage_out, h->d_tmp, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_stage_in, h->d_z, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
         int64_t it1 = 0; double rs1 = 0; int fl1 = 0;
-        if (h->nchains > 1) h->solo_chain = r % h->nchains;   // slot 0 must keep rhs r's fermion matrix
-        int rc1 = run_cg(h, 1, 0, h->tol, 10 * maxiter, h->kmax, &it1, nullptr);
-        if (rc1 == ELPH_OK) rc1 = residual_and_flags(h, 1, &it1, h->maxiter, &rs1, &fl1);
-        if (h->solo_chain >= 0) h->solo_chain = -1;
-        RC(rc1);
+        RC(elph_retry_in_slot0(h, r, [&]() -> int {
+            RC(run_cg(h, 1, 0, h->tol, 10 * maxiter, h->kmax, &it1, nullptr));
+            return residual_and_flags(h, 1, &it1, h->maxiter, &rs1, &fl1);
+        }));
         iters[r] = it1; resid[r] = rs1; flag[r] = fl1;
-        if (r != 0) {
-            HIPCHK(hipMemcpyAsync(h->d_x + r * nd, h->d_x, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_x, h->d_stage_out, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_b, h->d_stage_in, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
     }
     return ELPH_OK;
 }
@@ -1075,14 +1109,13 @@ static int ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, 
 int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag) {
     return ldiv_core(h, nrhs, use_prec, maxiter, iters, resid, flag);
 }
-int elph_i_ensure_capacity(elph_handle_s *h, int nrhs) { return ensure_capacity(h, nrhs); }
 
-// Room for nrhs vectors and for the bond brackets q[chain][tau][bond] of nch chains (SSH force).  The brackets go to d_p (2*cap_rhs*ndim
-// doubles) and their scatter onto the phonon fields to d_tmp (cap_rhs*ndim), so a lattice with more than two bonds per site (triangular,
+// Room for nrhs vectors and for the bond brackets q[chain][tau][bond] of nch chains (SSH force).  The brackets go to work.p (two vectors per
+// right-hand side) and their scatter onto the phonon fields to work.tmp (one), so a lattice with more than two bonds per site (triangular,
 // cubic) needs more than the two right-hand sides of the solves: ceil(nb/N) vectors per chain hold both.
 int elph_i_ssh_bracket_capacity(elph_handle_s *h, int nrhs, int nch) {
     const int per_site = (int)((h->nb + h->N - 1) / h->N);
-    return ensure_capacity(h, std::max(nrhs, nch * per_site));
+    return elph_work_reserve(h, std::max(nrhs, nch * per_site));
 }
 // SSH: one set of hopping tables (tau-major cosh/sinh + their lane-program copies) and one field buffer per chain
 static int ssh_reserve_chains(elph_handle_s *h, int nchains) {
@@ -1127,9 +1160,9 @@ int elph_i_reserve_chains(elph_handle_s *h, int nchains) {
 }
 
 static int stage_in_dev(elph_handle_s *h, int nrhs, const double *X_dev, const double *B_dev) {
-    RC(ensure_capacity(h, nrhs));
-    RC(elph_launch_r2s(h, h->d_b, B_dev, nrhs));
-    RC(elph_launch_r2s(h, h->d_x, X_dev, nrhs));
+    RC(elph_work_reserve(h, nrhs));
+    RC(elph_launch_r2s(h, h->work.b, B_dev, nrhs));
+    RC(elph_launch_r2s(h, h->work.x, X_dev, nrhs));
     h->x_zero = false;                              // (a caller's initial guess)
     return ELPH_OK;
 }
@@ -1151,7 +1184,7 @@ extern "C" int elph_ldiv_batched_dev(elph_handle h, int nrhs, double *X_dev, con
     if (nrhs < 1 || !X_dev || !B_dev || !iters || !residual_error || !flag || maxiter < 0) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     RC(stage_in_dev(h, nrhs, X_dev, B_dev));
     RC(ldiv_core(h, nrhs, use_prec, maxiter, iters, residual_error, flag));
-    RC(elph_launch_s2r(h, X_dev, h->d_x, nrhs));
+    RC(elph_launch_s2r(h, X_dev, h->work.x, nrhs));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -1165,21 +1198,18 @@ extern "C" int elph_ldiv_batched(elph_handle h, int nrhs, double *X, const doubl
                                  int64_t *iters, double *residual_error, int *flag) {
     CHECK_H(h);
     if (nrhs < 1 || !X || !B || !iters || !residual_error || !flag || maxiter < 0) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    RC(ensure_capacity(h, nrhs));
+    RC(elph_work_reserve(h, nrhs));
     const size_t bytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, B, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, nrhs));
+    RC(elph_stage_in(h, h->work.b, B, nrhs));
     if (x0_is_zero(h, nrhs, use_prec, X)) {          // fill!(x, 0) of the callers (HMC.jl:854, GreensFunctions.jl:334): seen on the host, the slab form may take the solve
-        HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, h->stream));
+        HIPCHK(hipMemsetAsync(h->work.x, 0, bytes, h->stream));
         h->x_zero = true;
     } else {
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, X, bytes, hipMemcpyHostToDevice, h->stream));
-        RC(elph_launch_r2s(h, h->d_x, h->d_stage_in, nrhs));
+        RC(elph_stage_in(h, h->work.x, X, nrhs));
         h->x_zero = false;                          // (a caller's initial guess)
     }
     RC(ldiv_core(h, nrhs, use_prec, maxiter, iters, residual_error, flag));
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_x, nrhs));
-    HIPCHK(hipMemcpyAsync(X, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    RC(elph_stage_out(h, X, h->work.x, nrhs));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -1198,19 +1228,16 @@ extern "C" int elph_cg_solve(elph_handle h, double *x, const double *b, double t
     if (tol == 0.0) tol = h->tol;
     if (kappa_max == 0.0) kappa_max = h->kmax;
     const size_t bytes = (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, b, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, 1));
+    RC(elph_stage_in(h, h->work.b, b, 1));
     if (x0_is_zero(h, 1, use_precond, x)) {
-        HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, h->stream));
+        HIPCHK(hipMemsetAsync(h->work.x, 0, bytes, h->stream));
         h->x_zero = true;
     } else {
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, x, bytes, hipMemcpyHostToDevice, h->stream));
-        RC(elph_launch_r2s(h, h->d_x, h->d_stage_in, 1));
+        RC(elph_stage_in(h, h->work.x, x, 1));
         h->x_zero = false;                          // (a caller's initial guess)
     }
     RC(run_cg(h, 1, use_precond ? 1 : 0, tol, maxiter, kappa_max, iters, eps_hist));
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_x, 1));
-    HIPCHK(hipMemcpyAsync(x, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    RC(elph_stage_out(h, x, h->work.x, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -1232,6 +1259,55 @@ int elph_i_set_dot_range(elph_handle_s *h, int64_t site_lo, int64_t site_hi) {
 // fermion force: update_model! + calc_O⁻¹Λϕ! + calc_dSfdx! with x, phi± , X± resident
 // ------------------------------------------------------------------------------------------
 
+int elph_i_force_holstein(elph_handle_s *h, const double *x, const double *lambda, const double *lambda2, const double *mu, double dtau,
+                          const double *phi_plus, const double *phi_minus, double *dSfdx, double *Xp_out, double *Xm_out, int64_t *iters,
+                          int *flag, int own_lo, int own_hi, const ElphPairSolve &solve_pair) {
+    RC(elph_work_reserve(h, 2));
+    const SolveWork &W = h->work;
+    const size_t nd = (size_t)h->ndim, N = (size_t)h->N, L = (size_t)h->L;
+    // update_model! (HolsteinModels.jl:526-549) and x in layout S
+    HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(W.stage_in, x, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RC(elph_launch_expV(h, W.stage_in, dtau));
+    RC(elph_launch_r2s(h, W.xfield, W.stage_in, 1));
+    h->have_E = true;
+    // phi± -> layout S; b± = Λ phi± (HMC.jl:840-842)
+    RC(elph_stage_in(h, W.phi, phi_plus, 1));
+    RC(elph_stage_in(h, W.phi + nd, phi_minus, 1));
+    RC(elph_launch_lambda_rhs(h, W.b, W.phi, W.xfield, dtau));
+    RC(solve_pair(iters, flag));
+    // dSf/dx (HMC.jl:790-814)
+    RC(elph_launch_force_holstein(h, W.tmp, W.x, W.phi, W.xfield, dtau));
+    std::vector<double> F(nd);
+    RC(elph_stage_out(h, F.data(), W.tmp, 1));
+    if (Xp_out) RC(elph_stage_out(h, Xp_out, W.x, 1));
+    if (Xm_out) RC(elph_stage_out(h, Xm_out, W.x + nd, 1));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = (size_t)own_lo * L; i < (size_t)own_hi * L; ++i) dSfdx[i] += F[i];      // "@. dSfdx += ..." accumulates (:803-811)
+    return ELPH_OK;
+}
+
+// the two solves of calc_O⁻¹Λϕ! as one batch from x = 0 (fill!(O⁻¹Λϕ, 0), HMC.jl:854,883) at tol^power
+static ElphPairSolve batch_pair(elph_handle_s *h, int use_precond, double tol_power) {
+    return [=](int64_t *iters, int *flag) -> int {
+        const size_t nd = (size_t)h->ndim;
+        HIPCHK(hipMemsetAsync(h->work.x, 0, 2 * nd * sizeof(double), h->stream));
+        h->x_zero = true;
+        int64_t it2[2] = {0, 0};
+        double res2[2];
+        int fl2[2] = {0, 0};
+        {
+            TolPower scope(h, tol_power);
+            RC(ldiv_core(h, 2, use_precond, 0, it2, res2, fl2));
+        }
+        elph_fold_pair(1, it2, fl2, iters, flag);
+        if (fl2[0]) RC(elph_launch_zero(h, h->work.x + nd, (int64_t)nd));
+        return ELPH_OK;
+    };
+}
+
 extern "C" int elph_fermion_force_holstein(elph_handle h, const double *x, const double *lambda, const double *lambda2,
                                            const double *mu, double dtau, const double *phi_plus, const double *phi_minus,
                                            int use_precond, double tol_power, double *dSfdx, double *Xp_out, double *Xm_out,
@@ -1239,90 +1315,38 @@ extern "C" int elph_fermion_force_holstein(elph_handle h, const double *x, const
     CHECK_H(h);
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!x || !lambda || !lambda2 || !mu || !phi_plus || !phi_minus || !dSfdx || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    RC(ensure_capacity(h, 2));
     set_nchains(h, 1);   // expansions were per chain
-    const size_t nd = (size_t)h->ndim, N = (size_t)h->N, bytes = nd * sizeof(double);
-    // update_model! (HolsteinModels.jl:526-549) and x in layout S
-    HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, x, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_expV(h, h->d_stage_in, dtau));
-    RC(elph_launch_r2s(h, h->d_xfield, h->d_stage_in, 1));
-    h->have_E = true;
-    // phi± -> layout S; b± = Λ phi± (HMC.jl:840-842)
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, phi_plus, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, phi_minus, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_phi, h->d_stage_in, 2));
-    RC(elph_launch_lambda_rhs(h, h->d_b, h->d_phi, h->d_xfield, dtau));
-    HIPCHK(hipMemsetAsync(h->d_x, 0, 2 * bytes, h->stream));                      // fill!(O⁻¹Λϕ, 0)  (HMC.jl:854,883)
-    h->x_zero = true;
-    // the two solves as one batch at tol^power (HMC.jl:827-828, restored below as at :912)
-    const double tol0 = h->tol;
-    h->tol = pow(tol0, tol_power);
-    int64_t it2[2] = {0, 0};
-    double res2[2];
-    int fl2[2] = {0, 0};
-    int rc = ldiv_core(h, 2, use_precond, 0, it2, res2, fl2);
-    h->tol = tol0;
-    if (rc) return rc;
-    int64_t tot = it2[0];
-    int fl = fl2[0];
-    if (fl == 0) { tot += it2[1]; fl = fl2[1]; }                                  // a failed first solve suppresses the second (:880)
-    else RC(elph_launch_zero(h, h->d_x + nd, (int64_t)nd));
-    if (fl == 0) tot = (tot + 1) / 2;                                             // cld(iters, 2)  (:907-909)
-    *iters = tot;
-    *flag = fl;
-    // dSf/dx (HMC.jl:790-814)
-    RC(elph_launch_force_holstein(h, h->d_tmp, h->d_x, h->d_phi, h->d_xfield, dtau));
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_tmp, 1));
-    std::vector<double> F(nd);
-    HIPCHK(hipMemcpyAsync(F.data(), h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (Xp_out || Xm_out) {
-        RC(elph_launch_s2r(h, h->d_stage_in, h->d_x, 2));
-        if (Xp_out) HIPCHK(hipMemcpyAsync(Xp_out, h->d_stage_in, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (Xm_out) HIPCHK(hipMemcpyAsync(Xm_out, h->d_stage_in + nd, bytes, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i < nd; ++i) dSfdx[i] += F[i];                             // "@. dSfdx += ..." accumulates (:803-811)
-    return ELPH_OK;
+    return elph_i_force_holstein(h, x, lambda, lambda2, mu, dtau, phi_plus, phi_minus, dSfdx, Xp_out, Xm_out, iters, flag, 0, (int)h->N,
+                                 batch_pair(h, use_precond, tol_power));
 }
 
-// the two solves of calc_O⁻¹Λϕ! for an SSH handle (Λ = identity) + the bond brackets q[tau][n] left in h->d_p
-static int ssh_force_core(elph_handle_s *h, const double *rhs_plus, const double *rhs_minus, int use_precond, double tol_power,
-                          int64_t *iters, int *flag) {
+// the two solves of calc_O⁻¹Λϕ! for an SSH handle (Λ = identity) + the bond brackets q[tau][n] left in h->work.p
+static int ssh_force_core(elph_handle_s *h, const double *rhs_plus, const double *rhs_minus, int64_t *iters, int *flag,
+                          const ElphPairSolve &solve_pair) {
     RC(elph_i_ssh_bracket_capacity(h, 2, 1));
-    const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, rhs_plus, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, rhs_minus, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, 2));
-    HIPCHK(hipMemsetAsync(h->d_x, 0, 2 * bytes, h->stream));
-    h->x_zero = true;
-    const double tol0 = h->tol;
-    h->tol = pow(tol0, tol_power);
-    int64_t it2[2] = {0, 0};
-    double res2[2];
-    int fl2[2] = {0, 0};
-    int rc = ldiv_core(h, 2, use_precond, 0, it2, res2, fl2);
-    h->tol = tol0;
-    if (rc) return rc;
-    int64_t tot = it2[0];
-    int fl = fl2[0];
-    if (fl == 0) { tot += it2[1]; fl = fl2[1]; }
-    else RC(elph_launch_zero(h, h->d_x + nd, (int64_t)nd));
-    if (fl == 0) tot = (tot + 1) / 2;
-    *iters = tot;
-    *flag = fl;
-    return elph_launch_force_ssh(h, h->d_p, h->d_x);     // d_p: 2*cap*ndim doubles of scratch, free once the solves are done
+    RC(elph_stage_in(h, h->work.b, rhs_plus, 1));
+    RC(elph_stage_in(h, h->work.b + h->ndim, rhs_minus, 1));
+    RC(solve_pair(iters, flag));
+    return elph_launch_force_ssh(h, h->work.p, h->work.x);     // work.p: scratch, free once the solves are done
 }
 
 static int ssh_solutions_out(elph_handle_s *h, double *Xp_out, double *Xm_out) {
-    const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
-    if (Xp_out || Xm_out) {
-        RC(elph_launch_s2r(h, h->d_stage_in, h->d_x, 2));
-        if (Xp_out) HIPCHK(hipMemcpyAsync(Xp_out, h->d_stage_in, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (Xm_out) HIPCHK(hipMemcpyAsync(Xm_out, h->d_stage_in + nd, bytes, hipMemcpyDeviceToHost, h->stream));
-    }
+    if (Xp_out) RC(elph_stage_out(h, Xp_out, h->work.x, 1));
+    if (Xm_out) RC(elph_stage_out(h, Xm_out, h->work.x + h->ndim, 1));
+    return ELPH_OK;
+}
+
+int elph_i_force_ssh(elph_handle_s *h, const double *rhs_plus, const double *rhs_minus, double *q_out, double *Xp_out, double *Xm_out,
+                     int64_t *iters, int *flag, const ElphPairSolve &solve_pair) {
+    RC(ssh_force_core(h, rhs_plus, rhs_minus, iters, flag, solve_pair));
+    // q[tau][n] on the device (tau-major) -> q_out[n*L + tau] (tau fastest, like the reference's (Ltau x Nbonds) arrays)
+    const size_t L = (size_t)h->L, nb = (size_t)h->nb, nq = L * nb;
+    std::vector<double> qt(nq);
+    if (nq) HIPCHK(hipMemcpyAsync(qt.data(), h->work.p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RC(ssh_solutions_out(h, Xp_out, Xm_out));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t t = 0; t < L; ++t)
+        for (size_t n = 0; n < nb; ++n) q_out[n * L + t] = qt[t * nb + n];
     return ELPH_OK;
 }
 
@@ -1333,16 +1357,7 @@ extern "C" int elph_fermion_force_ssh(elph_handle h, const double *rhs_plus, con
     if (h->kind != ELPH_MODEL_SSH) { elph_set_error("not an SSH handle"); return ELPH_E_ARG; }
     RC(need_model(h));
     if (!rhs_plus || !rhs_minus || !q_out || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    RC(ssh_force_core(h, rhs_plus, rhs_minus, use_precond, tol_power, iters, flag));
-    // q[tau][n] on the device (tau-major) -> q_out[n*L + tau] (tau fastest, like the reference's (Ltau x Nbonds) arrays)
-    const size_t L = (size_t)h->L, nb = (size_t)h->nb, nq = L * nb;
-    std::vector<double> qt(nq);
-    HIPCHK(hipMemcpyAsync(qt.data(), h->d_p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RC(ssh_solutions_out(h, Xp_out, Xm_out));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (size_t t = 0; t < L; ++t)
-        for (size_t n = 0; n < nb; ++n) q_out[n * L + t] = qt[t * nb + n];
-    return ELPH_OK;
+    return elph_i_force_ssh(h, rhs_plus, rhs_minus, q_out, Xp_out, Xm_out, iters, flag, batch_pair(h, use_precond, tol_power));
 }
 
 // The same with the scatter onto the phonon fields done on the device (SSHModels.jl:797-823 with one field per bond):
@@ -1356,11 +1371,11 @@ extern "C" int elph_fermion_force_ssh_fields(elph_handle h, const double *rhs_pl
     RC(need_model(h));
     if (!rhs_plus || !rhs_minus || !dSdx || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
     if (!h->cs_host_stale || h->ssh_nph < 0) { elph_set_error("elph_update_model_ssh_fields has not been called for the current field"); return ELPH_E_STATE; }
-    RC(ssh_force_core(h, rhs_plus, rhs_minus, use_precond, tol_power, iters, flag));
+    RC(ssh_force_core(h, rhs_plus, rhs_minus, iters, flag, batch_pair(h, use_precond, tol_power)));
     const size_t nf = (size_t)h->ssh_nph * (size_t)h->L;
-    double *dF = h->d_tmp;                                   // cap*ndim doubles
-    if (nf > (size_t)h->cap_rhs * (size_t)h->ndim) { elph_set_error("more phonon fields than scratch"); return ELPH_E_UNSUPPORTED; }
-    RC(elph_launch_ssh_scatter(h, dF, h->d_p, h->d_ssh_x, h->d_ssh_par, h->d_ssh_cb, h->ssh_nph, h->ssh_dtau));
+    double *dF = h->work.tmp;                                   // cap*ndim doubles
+    if (nf > (size_t)h->work.cap_rhs * (size_t)h->ndim) { elph_set_error("more phonon fields than scratch"); return ELPH_E_UNSUPPORTED; }
+    RC(elph_launch_ssh_scatter(h, dF, h->work.p, h->d_ssh_x, h->d_ssh_par, h->d_ssh_cb, h->ssh_nph, h->ssh_dtau));
     std::vector<double> F(nf);
     if (nf) HIPCHK(hipMemcpyAsync(F.data(), dF, nf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     RC(ssh_solutions_out(h, Xp_out, Xm_out));
@@ -1382,15 +1397,15 @@ extern "C" int elph_muldMdx_holstein_dev(elph_handle h, double *dMdx_dev, const 
     RC(need_model(h));
     if (!dMdx_dev || !u_dev || !v_dev || !x_dev || !lambda || !lambda2) { elph_set_error("null argument"); return ELPH_E_ARG; }
     if (h->nchains != 1) { elph_set_error("muldMdx! acts on one phonon configuration; the handle holds %d chains", h->nchains); return ELPH_E_STATE; }
-    RC(ensure_capacity(h, 2));
+    RC(elph_work_reserve(h, 2));
     const size_t nd = (size_t)h->ndim, N = (size_t)h->N;
     HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_xfield, x_dev, 1));
-    RC(elph_launch_r2s(h, h->d_b, u_dev, 1));
-    RC(elph_launch_r2s(h, h->d_b + nd, v_dev, 1));
-    RC(elph_launch_dmdx_holstein(h, h->d_tmp, h->d_b, h->d_b + nd, h->d_xfield, dtau, 1.0));
-    RC(elph_launch_s2r(h, dMdx_dev, h->d_tmp, 1));
+    RC(elph_launch_r2s(h, h->work.xfield, x_dev, 1));
+    RC(elph_launch_r2s(h, h->work.b, u_dev, 1));
+    RC(elph_launch_r2s(h, h->work.b + nd, v_dev, 1));
+    RC(elph_launch_dmdx_holstein(h, h->work.tmp, h->work.b, h->work.b + nd, h->work.xfield, dtau, 1.0));
+    RC(elph_launch_s2r(h, dMdx_dev, h->work.tmp, 1));
     HIPCHK(hipStreamSynchronize(h->stream));           // lambda / lambda2 are the caller's host arrays
     return ELPH_OK;
 }
@@ -1399,18 +1414,18 @@ extern "C" int elph_muldMdx_holstein(elph_handle h, double *dMdx, const double *
                                      const double *lambda, const double *lambda2, double dtau) {
     CHECK_H(h);
     if (!dMdx || !u || !v || !x) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    RC(ensure_capacity(h, 3));                         // stage_in: u, v, x
+    RC(elph_work_reserve(h, 3));                         // stage_in: u, v, x
     const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, u, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, v, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + 2 * nd, x, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_muldMdx_holstein_dev(h, h->d_stage_out, h->d_stage_in, h->d_stage_in + nd, h->d_stage_in + 2 * nd, lambda, lambda2, dtau));
-    HIPCHK(hipMemcpyAsync(dMdx, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, u, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in + nd, v, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in + 2 * nd, x, bytes, hipMemcpyHostToDevice, h->stream));
+    RC(elph_muldMdx_holstein_dev(h, h->work.stage_out, h->work.stage_in, h->work.stage_in + nd, h->work.stage_in + 2 * nd, lambda, lambda2, dtau));
+    HIPCHK(hipMemcpyAsync(dMdx, h->work.stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
 
-// the bond brackets q[tau][n] of muldMdx!(·, u, ssh, v) left in h->d_p (u, v: device, reference layout)
+// the bond brackets q[tau][n] of muldMdx!(·, u, ssh, v) left in h->work.p (u, v: device, reference layout)
 static int ssh_dmdx_core(elph_handle_s *h, const double *u_dev, const double *v_dev) {
     if (h->kind != ELPH_MODEL_SSH) { elph_set_error("not an SSH handle"); return ELPH_E_ARG; }
     RC(need_model(h));
@@ -1418,18 +1433,18 @@ static int ssh_dmdx_core(elph_handle_s *h, const double *u_dev, const double *v_
     if (h->nchains != 1) { elph_set_error("muldMdx! acts on one phonon configuration; the handle holds %d chains", h->nchains); return ELPH_E_STATE; }
     RC(elph_i_ssh_bracket_capacity(h, 2, 1));          // no-op when u_dev, v_dev are the handle's own staging (ssh_dmdx_stage)
     const size_t nd = (size_t)h->ndim;
-    RC(elph_launch_r2s(h, h->d_b, u_dev, 1));
-    RC(elph_launch_r2s(h, h->d_b + nd, v_dev, 1));
-    return elph_launch_force_ssh(h, h->d_p, h->d_b + nd, h->d_b, 1);      // b0 = e^{Δτμ} v(τ−1), c0 = CBᵀ u
+    RC(elph_launch_r2s(h, h->work.b, u_dev, 1));
+    RC(elph_launch_r2s(h, h->work.b + nd, v_dev, 1));
+    return elph_launch_force_ssh(h, h->work.p, h->work.b + nd, h->work.b, 1);      // b0 = e^{Δτμ} v(τ−1), c0 = CBᵀ u
 }
 
 static int ssh_dmdx_stage(elph_handle_s *h, const double *u, const double *v) {
     if (!u || !v) { elph_set_error("null argument"); return ELPH_E_ARG; }
     RC(elph_i_ssh_bracket_capacity(h, 2, 1));
     const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, u, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, v, bytes, hipMemcpyHostToDevice, h->stream));
-    return ssh_dmdx_core(h, h->d_stage_in, h->d_stage_in + nd);
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, u, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in + nd, v, bytes, hipMemcpyHostToDevice, h->stream));
+    return ssh_dmdx_core(h, h->work.stage_in, h->work.stage_in + nd);
 }
 
 extern "C" int elph_muldMdx_ssh(elph_handle h, double *q_out, const double *u, const double *v) {
@@ -1438,7 +1453,7 @@ extern "C" int elph_muldMdx_ssh(elph_handle h, double *q_out, const double *u, c
     RC(ssh_dmdx_stage(h, u, v));
     const size_t L = (size_t)h->L, nb = (size_t)h->nb, nq = L * nb;
     std::vector<double> qt(nq);
-    if (nq) HIPCHK(hipMemcpyAsync(qt.data(), h->d_p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (nq) HIPCHK(hipMemcpyAsync(qt.data(), h->work.p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (size_t t = 0; t < L; ++t)
         for (size_t n = 0; n < nb; ++n) q_out[n * L + t] = qt[t * nb + n];
@@ -1448,9 +1463,9 @@ extern "C" int elph_muldMdx_ssh(elph_handle h, double *q_out, const double *u, c
 static int ssh_dmdx_fields(elph_handle_s *h, double **dF, size_t *nf) {
     if (!h->cs_host_stale || h->ssh_nph < 0) { elph_set_error("elph_update_model_ssh_fields has not been called for the current field"); return ELPH_E_STATE; }
     *nf = (size_t)h->ssh_nph * (size_t)h->L;
-    *dF = h->d_tmp;
-    if (*nf > (size_t)h->cap_rhs * (size_t)h->ndim) { elph_set_error("more phonon fields than scratch"); return ELPH_E_UNSUPPORTED; }
-    return elph_launch_ssh_scatter(h, *dF, h->d_p, h->d_ssh_x, h->d_ssh_par, h->d_ssh_cb, h->ssh_nph, h->ssh_dtau);
+    *dF = h->work.tmp;
+    if (*nf > (size_t)h->work.cap_rhs * (size_t)h->ndim) { elph_set_error("more phonon fields than scratch"); return ELPH_E_UNSUPPORTED; }
+    return elph_launch_ssh_scatter(h, *dF, h->work.p, h->d_ssh_x, h->d_ssh_par, h->d_ssh_cb, h->ssh_nph, h->ssh_dtau);
 }
 
 extern "C" int elph_muldMdx_ssh_fields(elph_handle h, double *dMdx, const double *u, const double *v) {
@@ -1771,9 +1786,9 @@ extern "C" int elph_kpm_apply_dev(elph_handle h, double *z_dev, const double *r_
     CHECK_H(h);
     if (!h->kpm.ready) { elph_set_error("elph_kpm_setup has not been called"); return ELPH_E_STATE; }
     if (!z_dev || !r_dev) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    RC(elph_launch_r2s(h, h->d_r, r_dev, 1));
-    RC(elph_launch_kpm_apply(h, h->d_zp, h->d_r, 1, 0));
-    RC(elph_launch_s2r(h, z_dev, h->d_zp, 1));
+    RC(elph_launch_r2s(h, h->work.r, r_dev, 1));
+    RC(elph_launch_kpm_apply(h, h->work.zp, h->work.r, 1, 0));
+    RC(elph_launch_s2r(h, z_dev, h->work.zp, 1));
     return ELPH_OK;
 }
 
@@ -1781,9 +1796,9 @@ extern "C" int elph_kpm_apply(elph_handle h, double *z, const double *r) {
     CHECK_H(h);
     if (!z || !r) { elph_set_error("null argument"); return ELPH_E_ARG; }
     const size_t bytes = (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, r, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_kpm_apply_dev(h, h->d_stage_out, h->d_stage_in));
-    HIPCHK(hipMemcpyAsync(z, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.stage_in, r, bytes, hipMemcpyHostToDevice, h->stream));
+    RC(elph_kpm_apply_dev(h, h->work.stage_out, h->work.stage_in));
+    HIPCHK(hipMemcpyAsync(z, h->work.stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -1822,11 +1837,10 @@ extern "C" int elph_tau_to_omega(elph_handle h, double *nu_complex, const double
     CHECK_H(h);
     if (!nu_complex || !v) { elph_set_error("null argument"); return ELPH_E_ARG; }
     const size_t nd = (size_t)h->ndim;
-    RC(ensure_capacity(h, 2));   // complex scratch = 2 real vectors
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, v, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, 1));
-    double2 *fullS = reinterpret_cast<double2 *>(h->d_p);           // [L][N] complex
-    RC(elph_launch_tau_to_omega(h, fullS, h->d_b));
+    RC(elph_work_reserve(h, 2));   // complex scratch = 2 real vectors
+    RC(elph_stage_in(h, h->work.b, v, 1));
+    double2 *fullS = reinterpret_cast<double2 *>(h->work.p);           // [L][N] complex
+    RC(elph_launch_tau_to_omega(h, fullS, h->work.b));
     // complex layout S -> complex layout R: transpose re and im planes separately via a strided copy
     // (API convenience path; the solver itself never leaves layout S)
     std::vector<double> tmp(2 * nd);
@@ -1845,18 +1859,17 @@ extern "C" int elph_omega_to_tau(elph_handle h, double *v, const double *nu_comp
     CHECK_H(h);
     if (!nu_complex || !v) { elph_set_error("null argument"); return ELPH_E_ARG; }
     const size_t nd = (size_t)h->ndim, N = (size_t)h->N, L = (size_t)h->L;
-    RC(ensure_capacity(h, 2));
+    RC(elph_work_reserve(h, 2));
     std::vector<double> tmp(2 * nd);
     for (size_t k = 0; k < L; ++k)
         for (size_t s = 0; s < N; ++s) {
             tmp[2 * (k * N + s)] = nu_complex[2 * (s * L + k)];
             tmp[2 * (k * N + s) + 1] = nu_complex[2 * (s * L + k) + 1];
         }
-    double2 *fullS = reinterpret_cast<double2 *>(h->d_p);
+    double2 *fullS = reinterpret_cast<double2 *>(h->work.p);
     HIPCHK(hipMemcpy(fullS, tmp.data(), 2 * nd * sizeof(double), hipMemcpyHostToDevice));
-    RC(elph_launch_omega_to_tau(h, h->d_x, fullS));
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_x, 1));
-    HIPCHK(hipMemcpyAsync(v, h->d_stage_out, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RC(elph_launch_omega_to_tau(h, h->work.x, fullS));
+    RC(elph_stage_out(h, v, h->work.x, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -1867,16 +1880,16 @@ extern "C" int elph_omega_to_tau(elph_handle h, double *v, const double *nu_comp
 
 static int bench_launch_unit(elph_handle_s *h, int what, int nrhs) {
     switch (what) {
-        case 0: return elph_launch_mul(h, 2, h->d_z, h->d_b, nrhs);
+        case 0: return elph_launch_mul(h, 2, h->work.z, h->work.b, nrhs);
         case 1: return elph_launch_cg_iteration(h, nrhs, 0);
-        case 2: return elph_launch_kpm_apply(h, h->d_zp, h->d_b, nrhs, 0);
+        case 2: return elph_launch_kpm_apply(h, h->work.zp, h->work.b, nrhs, 0);
         case 3: return elph_launch_cg_iteration(h, nrhs, 1);
         case 11: return ELPH_E_ARG;      // (two half-batches on two streams: elph_bench_run drives both handles itself)
         case 4: return elph_launch_cg_kernel(h, nrhs, 0);
         case 5: return elph_launch_cg_kernel(h, nrhs, 1);
         default: {
             // 6, 7, 8: the three kernels of the KPM apply as the preconditioned iteration (case 3) launches them, one at a time
-            return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, h->plan.xr_in_fwd ? 2 : 1, 1 << (what - 6));
+            return elph_launch_kpm_apply(h, h->work.zp, h->work.r, nrhs, h->plan.xr_in_fwd ? 2 : 1, 1 << (what - 6));
         }
     }
 }
@@ -1886,17 +1899,15 @@ extern "C" int elph_bench_prepare(elph_handle h, int what, int nrhs, const doubl
     RC(need_model(h));
     if (nrhs < 1 || what < 0 || what > 12) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     if ((what == 2 || what == 3 || what == 10 || what == 11 || (what >= 6 && what <= 8)) && !h->kpm.ready) { elph_set_error("KPM not set up"); return ELPH_E_STATE; }
-    RC(ensure_capacity(h, nrhs));
+    RC(elph_work_reserve(h, nrhs));
     if (B) {
-        const size_t bytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, B, bytes, hipMemcpyHostToDevice, h->stream));
-        RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, nrhs));
+        RC(elph_stage_in(h, h->work.b, B, nrhs));
     }
     // fixed-count CG: tol = 0 never converges, kmax = inf, x0 = 0
     CgParams P;
     P.tol = 0.0; P.kmax = INFINITY; P.maxiter = (long long)1 << 40; P.use_prec = (what == 3 || what == 10 || what == 11 || (what >= 6 && what <= 8)); P.record_hist = 0; P.hist_stride = 0;
     h->cur_params = P;
-    HIPCHK(hipMemsetAsync(h->d_x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(h->work.x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
     h->x_zero = false;
     RC(elph_launch_cg_init(h, nrhs, P.use_prec, true));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1906,9 +1917,8 @@ extern "C" int elph_bench_prepare(elph_handle h, int what, int nrhs, const doubl
 
 extern "C" int elph_bench_get_x(elph_handle h, int nrhs, double *X) {
     CHECK_H(h);
-    if (nrhs < 1 || nrhs > h->cap_rhs || !X) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_x, nrhs));
-    HIPCHK(hipMemcpyAsync(X, h->d_stage_out, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (nrhs < 1 || nrhs > h->work.cap_rhs || !X) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    RC(elph_stage_out(h, X, h->work.x, nrhs));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -2010,7 +2020,7 @@ extern "C" int elph_bench_dft_info(elph_handle h, int which, int inverse, int N,
 
 extern "C" int elph_bench_run(elph_handle h, int what, int nrhs, int reps, int use_graph, double *ms_total) {
     CHECK_H(h);
-    if (nrhs < 1 || nrhs > h->cap_rhs || reps < 1 || !ms_total || what < 0 || what > 12) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    if (nrhs < 1 || nrhs > h->work.cap_rhs || reps < 1 || !ms_total || what < 0 || what > 12) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     if (use_graph) { elph_set_error("elph_bench_run: captured-graph replay is not supported (use_graph must be 0)"); return ELPH_E_UNSUPPORTED; }
     if (what == 12) {        // `reps` un-preconditioned iterations of every right-hand side in the slab form of a large lattice (slabs.hip): sum of the launches' event times
         if (!elph_i_slabs_usable(h, nrhs)) { elph_set_error("the slab form does not apply to this handle / batch"); return ELPH_E_UNSUPPORTED; }

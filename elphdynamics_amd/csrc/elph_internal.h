@@ -16,7 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <math.h>
+
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -361,6 +364,44 @@ struct DftState {
     size_t big_cap = 0;
 };
 
+// The workspace of a solve (host only; all device vectors in layout S): everything sized by the number of right-hand sides the handle has
+// room for.  elph_work_reserve (elph_api.hip) is its only allocator, elph_work_release its only freer, part() the only code that knows which
+// arrays are per right-hand side and how far each advances.
+struct SolveWork {
+    int cap_rhs = 0;                       // right-hand sides there is room for
+    size_t ndim = 0, nnu = 0, nrz = 0;     // elements per right-hand side: of a vector, of nu (ceil(L/2) N), of one partial-sum array (L npl)
+    double *stage_in = nullptr, *stage_out = nullptr;      // layout R staging [cap_rhs][ndim] (elph_stage_in, elph_stage_out)
+    double *b = nullptr, *x = nullptr, *r = nullptr, *z = nullptr, *zp = nullptr;      // [cap_rhs][ndim]
+    double *tmp = nullptr;                 // [cap_rhs][ndim] scratch (v''')
+    double *p = nullptr;                   // [2][cap_rhs][ndim] ping-pong by parity
+    double2 *nu = nullptr;                 // [cap_rhs][>= nnu] complex (half spectrum, omega-major)
+    double *sums = nullptr;                // partial sums: the four arrays pap, rr, rz, bb of [cap_rhs][nrz]
+    CgState *state = nullptr, *h_state = nullptr;          // [cap_rhs][2], device and pinned
+    double *alpha = nullptr;               // [cap_rhs] CG step length handed from k_cg_xr to the next k_cg_ap
+    double *scal = nullptr, *h_scal = nullptr;             // [4 cap_rhs] small scalar scratch (residual norms), device and pinned
+    double *hist = nullptr;                // hist_cap doubles: the eps histories of a solve that records them (run_cg grows it)
+    int64_t hist_cap = 0;
+    double *phi = nullptr, *xfield = nullptr;              // force assembly: phi+- [2][ndim], x in layout S [ndim]
+
+    size_t part_stride() const { return (size_t)cap_rhs * nrz; }      // between two of the partial-sum arrays
+    double *pap() const { return sums; }
+    double *rr() const { return sums + part_stride(); }
+    double *rz() const { return sums + 2 * part_stride(); }
+    double *bb() const { return sums + 3 * part_stride(); }
+    // The view of the right-hand sides from r0 on (the second stream's part of a split batch).  cap_rhs stays the whole record's: it is the
+    // distance of the partial-sum arrays, which are indexed [rhs][<= nrz], so one offset serves all four.  p is [2][cap_rhs][ndim]: slot 1 of
+    // one part would overlap slot 0 of the next, so a view is only good for an iteration that reads and writes slot 0 alone, the p/x-fused
+    // one (elph_api.hip: split_legal demands it).  What is not per right-hand side (staging, scal, hist, phi, xfield) is shared.
+    SolveWork part(size_t r0) const {
+        SolveWork v = *this;
+        v.b += r0 * ndim; v.x += r0 * ndim; v.r += r0 * ndim; v.z += r0 * ndim; v.zp += r0 * ndim; v.tmp += r0 * ndim; v.p += r0 * ndim;
+        v.nu += r0 * nnu;
+        v.state += 2 * r0; v.h_state += 2 * r0; v.alpha += r0;
+        v.sums += r0 * nrz;
+        return v;
+    }
+};
+
 struct elph_handle_s {
     int kind = 0, device = 0;
     int64_t N = 0, L = 0, nb = 0, ndim = 0;
@@ -422,7 +463,7 @@ struct elph_handle_s {
     void *current = nullptr;               // CurrentState (currcorr.hip), owned; freed with greens
     void *msolve = nullptr;                // MsolveState (msolve.hip), owned: the work vectors of BiCGStab and GMRES, GMRES's Krylov basis
     ResidentState res;                     // the resident solvers' control block, last launch shape and health (cg_wg.hip)
-    // x = 0 hint: set by the library right after it zeroes d_x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
+    // x = 0 hint: set by the library right after it zeroes work.x for a solve it is about to start (fill!(x, 0) of the callers, HMC.jl:854;
     // elph_bench_prepare).  run_cg — and elph_bench_run(9 | 10) — read AND clear it first thing (an early error return cannot leave it
     // behind for the next solve) and hand it on as an argument: to elph_launch_cg_init (A x0 = 0 needs no mat-vec) and to elph_wg_cg
     // (the resident kernel does not read x0 either)
@@ -434,25 +475,10 @@ struct elph_handle_s {
     double tol = 1e-4, kmax = 1e12;
     int64_t maxiter = 0;
 
-    // workspace
-    int cap_rhs = 0;
-    double *d_stage_in = nullptr, *d_stage_out = nullptr;  // layout R staging, cap_rhs*ndim
-    double *d_b = nullptr, *d_x = nullptr, *d_r = nullptr, *d_z = nullptr, *d_zp = nullptr;
-    double *d_p = nullptr;                 // 2 * cap_rhs * ndim (ping-pong)
-    double *d_tmp = nullptr;               // cap_rhs*ndim scratch (v''')
-    double *d_phi = nullptr, *d_xfield = nullptr;   // force assembly: phi+- (2*ndim), x in layout S (ndim)
-    double *d_part = nullptr;              // partial sums: 4 arrays of cap_rhs * L
-    CgState *d_state = nullptr;            // cap_rhs * 2
-    CgState *h_state = nullptr;            // pinned, cap_rhs * 2
+    SolveWork work;                        // the workspace of every solve (elph_work_reserve)
     CgParams cur_params;                   // parameters of the solve in progress (copied into every launch)
-    double *d_hist = nullptr;
-    int64_t hist_cap = 0;
-    double *d_scal = nullptr;              // small scalar scratch (residual norms), 4*cap_rhs
-    double *d_alpha = nullptr;             // cap_rhs: CG step length handed from k_cg_xr to the next k_cg_ap
-    double *h_scal = nullptr;              // pinned
 
     KpmState kpm;                          // the KPM preconditioner (elph_kpm_create, kpm_setup_core)
-    double2 *d_nu = nullptr;               // cap_rhs * Lo2 * N complex (half spectrum, omega-major)
 
     DftState dft;                          // the tau-axis transforms: shape, tables, work buffers (elph_dft_build_tables)
     double *d_diag = nullptr;              // fourier-acceleration diagonal staging
@@ -465,7 +491,39 @@ KpmDev elph_kpm_dev(const elph_handle_s *h);
 
 // elph_api.hip internals used by hmc.hip
 int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag);
-int elph_i_ensure_capacity(elph_handle_s *h, int nrhs);
+// the solve workspace and the idioms built on it (elph_api.hip)
+int elph_work_reserve(elph_handle_s *h, int nrhs);      // room for nrhs right-hand sides in h->work (grows only; drains the stream when it does)
+void elph_work_release(elph_handle_s *h);
+// nvec host vectors in the reference layout <-> device vectors in layout S through the staging buffers, stream-ordered, no synchronisation;
+// ncols = 0: site vectors (ndim), otherwise field vectors of that many columns.  ELPH_E_STATE when the staging buffer is too small.
+int elph_stage_in(elph_handle_s *h, double *dstS, const double *hostR, int nvec, int ncols = 0);
+int elph_stage_out(elph_handle_s *h, double *hostR, const double *srcS, int nvec, int ncols = 0);
+// Right-hand side r of a batch once more, alone, in slot 0 (the retry of a flagged right-hand side, Models.jl:129-133): slot 0 of x and b
+// is parked in the staging buffers, r moves in, the kernels see r's chain only (solo_chain, when the handle holds several), solve_and_flag
+// runs, the result moves back to r and slot 0 is restored.
+int elph_retry_in_slot0(elph_handle_s *h, int r, const std::function<int()> &solve_and_flag);
+// the solver tolerance at tol^power for the length of a scope: the two solves of calc_O⁻¹Λϕ! (HMC.jl:827-828, restored as at :912)
+struct TolPower {
+    elph_handle_s *h;
+    double tol0;
+    TolPower(elph_handle_s *hh, double power) : h(hh), tol0(hh->tol) { h->tol = pow(tol0, power); }
+    ~TolPower() { h->tol = tol0; }
+    TolPower(const TolPower &) = delete;
+    TolPower &operator=(const TolPower &) = delete;
+};
+// what calc_O⁻¹Λϕ! returns for each of nch chains from the (iters, flag) of its + and − solve, it2 / fl2: [2][nch]: a failed first solve
+// suppresses the second (HMC.jl:880), two good ones report cld(total, 2) (:907-909)
+void elph_fold_pair(int nch, const int64_t *it2, const int *fl2, int64_t *iters, int *flag);
+// The fermion force of one configuration (update_model! + calc_O⁻¹Λϕ! + calc_dSfdx!); the entry points of elph_api.hip and shard.hip check
+// their arguments and supply the pair solve: right-hand sides in work.b[0..1], solutions into work.x[0..1], (iters, flag) as above.
+typedef std::function<int(int64_t *iters, int *flag)> ElphPairSolve;
+// Holstein: the force is accumulated into the rows [own_lo, own_hi) of dSfdx (the whole lattice: 0, N)
+int elph_i_force_holstein(elph_handle_s *h, const double *x, const double *lambda, const double *lambda2, const double *mu, double dtau,
+                          const double *phi_plus, const double *phi_minus, double *dSfdx, double *Xp_out, double *Xm_out, int64_t *iters,
+                          int *flag, int own_lo, int own_hi, const ElphPairSolve &solve_pair);
+// SSH: the bond brackets q_out[n Ltau + tau]
+int elph_i_force_ssh(elph_handle_s *h, const double *rhs_plus, const double *rhs_minus, double *q_out, double *Xp_out, double *Xm_out,
+                     int64_t *iters, int *flag, const ElphPairSolve &solve_pair);
 int elph_i_ssh_bracket_capacity(elph_handle_s *h, int nrhs, int nch);     // nrhs vectors + the SSH bond brackets of nch chains
 int elph_i_set_dot_range(elph_handle_s *h, int64_t site_lo, int64_t site_hi);   // inner products over [lo, hi) only (a shard's own sites)
 int elph_i_reserve_chains(elph_handle_s *h, int nchains);   // d_E for nchains configurations, h->nchains = nchains
@@ -541,7 +599,7 @@ int elph_launch_ssh_scatter(elph_handle_s *h, double *F_dev, const double *q_dev
 int elph_i_ssh_upload_params(elph_handle_s *h, int64_t nph, const int64_t *cb_index, const double *t_ph, const double *alpha,
                              const double *alpha2, const double *t_bare_cb, const double *mu);
 int elph_launch_mul(elph_handle_s *h, int which /*0 M, 1 MT, 2 MTM*/, double *yS, const double *vS, int nvec);
-int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero = false);   // x_zero: d_x was zeroed by the library for THIS solve
+int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero = false);   // x_zero: work.x was zeroed by the library for THIS solve
 int elph_launch_cg_iteration(elph_handle_s *h, int nrhs, int use_prec);
 int elph_launch_cg_kernel(elph_handle_s *h, int nrhs, int which /*0 = k_cg_ap, 1 = k_cg_xr*/);
 int elph_launch_residual(elph_handle_s *h, int nrhs);
@@ -595,14 +653,14 @@ int elph_i_shard_create_local(elph_handle_s *h, int rank, int world, int64_t own
                               int64_t cap_ghost, void *key_out);      // shard.hip: elph_shard_create for slabs that all live on one device (mailbox = ordinary device memory, not exported)
 // ---- slabs.hip: the resident un-preconditioned solve of a lattice BEYOND one wave's slice (N > 320) as slabs of rows on the same device
 bool elph_i_slabs_usable(elph_handle_s *h, int nrhs);      // builds the slabs on first use
-int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long fixed_iters, int64_t *iters, bool *ran, double *ms_out);      // (P.record_hist: the eps histories go to h->d_hist)
+int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long fixed_iters, int64_t *iters, bool *ran, double *ms_out);      // (P.record_hist: the eps histories go to h->work.hist)
 void elph_i_slabs_free(elph_handle_s *h);
 
 // ---- workgroup-resident CG (cg_wg.hip): the whole un-preconditioned solve in one launch
 bool elph_wg_usable(const elph_handle_s *h, int *T, int *W, int *G, int nrhs = 1);
 // the launch plan of a handle that need not own a device, as elph_bench_wg_plan reports it (world > 0: one rank of a sharded solve)
 void elph_i_wg_plan_probe(const elph_handle_s *h, int nrhs, int world, int *out);
-// x0_zero: the library zeroed d_x for this solve; x0_save: where the initial guess goes once the launch is decided, for the caller's
+// x0_zero: the library zeroed work.x for this solve; x0_save: where the initial guess goes once the launch is decided, for the caller's
 // fallback after a time-out (nullptr: not kept — a measurement launch)
 int elph_wg_cg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_iters, bool x0_zero, double *x0_save, bool *ran);
 // the resident solvers' control block for one launch (ResidentState): room for n_rec record words + n_extra words behind them + the abort

@@ -230,14 +230,14 @@ static int check_chain_count(const elph_handle_s *h, int nv) {
 static int solve_from_R(elph_handle_s *h, GreensState *g, int use_precond, int64_t *iters, double *residual_error, int *flag) {
     const int nv = g->nv;
     const size_t nd = (size_t)h->ndim;
-    RC(elph_launch_mul(h, 1, h->d_b, g->R, nv));                       // Mᵀr₁ (model.v″, :223-224)
-    RC(elph_launch_zero(h, h->d_x, (int64_t)nv * h->ndim));            // fill!(M⁻¹r₁, 0)  :213
+    RC(elph_launch_mul(h, 1, h->work.b, g->R, nv));                       // Mᵀr₁ (model.v″, :223-224)
+    RC(elph_launch_zero(h, h->work.x, (int64_t)nv * h->ndim));            // fill!(M⁻¹r₁, 0)  :213
     h->x_zero = false;                                                 // (this path does not use the x = 0 hint, and takes nobody else's)
     std::vector<int64_t> it((size_t)nv);
     std::vector<double> res((size_t)nv);
     std::vector<int> fl((size_t)nv);
     RC(elph_i_ldiv_core(h, nv, use_precond ? 1 : 0, 0, it.data(), res.data(), fl.data()));
-    HIPCHK(hipMemcpyAsync(g->X, h->d_x, (size_t)nv * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(g->X, h->work.x, (size_t)nv * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < nv; ++i) {
         if (iters) iters[i] = it[i];
@@ -257,9 +257,8 @@ extern "C" int elph_greens_update(elph_handle h, const double *R, int use_precon
     GreensState *g = gs_of(h);
     const int nv = g->nv;
     RC(check_chain_count(h, nv));
-    RC(elph_i_ensure_capacity(h, nv));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, R, (size_t)nv * (size_t)h->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, g->R, h->d_stage_in, nv));
+    RC(elph_work_reserve(h, nv));
+    RC(elph_stage_in(h, g->R, R, nv));
     return solve_from_R(h, g, use_precond, iters, residual_error, flag);
 }
 
@@ -292,7 +291,7 @@ extern "C" int elph_greens_update_rng(elph_handle h, int use_precond, int64_t *i
     if (!g->rng_on) { elph_set_error("the estimator has no generator: call elph_greens_set_rng first"); return ELPH_E_STATE; }
     const int nv = g->nv;
     RC(check_chain_count(h, nv));
-    RC(elph_i_ensure_capacity(h, nv));
+    RC(elph_work_reserve(h, nv));
     RC(elph_i_greens_randn(h, g->R, sm64(g->rng_seed, ++g->rng_batches), nv));
     return solve_from_R(h, g, use_precond, iters, residual_error, flag);
 }
@@ -302,15 +301,12 @@ extern "C" int elph_greens_set_vectors(elph_handle h, const double *R, const dou
     CHECK_H(h);
     RC(need_greens(h));
     GreensState *g = gs_of(h);
-    const size_t bytes = (size_t)g->nv * (size_t)h->ndim * sizeof(double);
-    RC(elph_i_ensure_capacity(h, g->nv));
+    RC(elph_work_reserve(h, g->nv));
     if (R) {
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, R, bytes, hipMemcpyHostToDevice, h->stream));
-        RC(elph_launch_r2s(h, g->R, h->d_stage_in, g->nv));
+        RC(elph_stage_in(h, g->R, R, g->nv));
     }
     if (MinvR) {
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, MinvR, bytes, hipMemcpyHostToDevice, h->stream));
-        RC(elph_launch_r2s(h, g->X, h->d_stage_in, g->nv));
+        RC(elph_stage_in(h, g->X, MinvR, g->nv));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     if (R && MinvR) g->have_vectors = true;
@@ -322,15 +318,12 @@ extern "C" int elph_greens_get_vectors(elph_handle h, double *R, double *MinvR) 
     RC(need_greens(h));
     GreensState *g = gs_of(h);
     if (!g->have_vectors) { elph_set_error("no vectors yet: call elph_greens_update or elph_greens_set_vectors"); return ELPH_E_STATE; }
-    const size_t bytes = (size_t)g->nv * (size_t)h->ndim * sizeof(double);
     if (R) {
-        RC(elph_launch_s2r(h, h->d_stage_out, g->R, g->nv));
-        HIPCHK(hipMemcpyAsync(R, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+        RC(elph_stage_out(h, R, g->R, g->nv));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     if (MinvR) {
-        RC(elph_launch_s2r(h, h->d_stage_out, g->X, g->nv));
-        HIPCHK(hipMemcpyAsync(MinvR, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+        RC(elph_stage_out(h, MinvR, g->X, g->nv));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return ELPH_OK;

@@ -314,14 +314,14 @@ int calc_OinvLphi(elph_handle_s *h, HmcState *st, int use_precond, double power,
             RC(elph_i_shard_global_csbar(h, cs, &nbg));
             if (nbg != hf->nb) { elph_set_error("the full-lattice handle has %lld bonds, elph_shard_set_bonds named %lld", (long long)hf->nb, (long long)nbg); return ELPH_E_ARG; }
             RC(elph_i_kpm_setup_csbar(hf, cs.data(), cs.data() + nbg, bmax, bmin));
-            HIPCHK(hipMemcpyAsync(h->d_b, st->phi, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->work.b, st->phi, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         } else {
             std::vector<double> Eg;
             RC(elph_i_shard_global_ebar(h, Eg));
             RC(elph_i_kpm_setup_ebar(hf, Eg.data(), bmax, bmin));
-            RC(elph_launch_lambda_rhs(h, h->d_b, st->phi, st->x, st->dtau, nch));
+            RC(elph_launch_lambda_rhs(h, h->work.b, st->phi, st->x, st->dtau, nch));
         }
-        HIPCHK(hipMemsetAsync(h->d_x, 0, 2 * (size_t)nch * nd * sizeof(double), h->stream));
+        HIPCHK(hipMemsetAsync(h->work.x, 0, 2 * (size_t)nch * nd * sizeof(double), h->stream));
         h->x_zero = false;
         return elph_i_shard_solve_pair(h, hf, 1, power, iters, flag);
     }
@@ -333,31 +333,23 @@ int calc_OinvLphi(elph_handle_s *h, HmcState *st, int use_precond, double power,
         use = 1;                      // an inactive preconditioner is the identity inside the preconditioned recurrence
     }
     if (st->ssh)        // Λ ≡ 1 (HMC.jl:943-946,970-973): the right-hand sides are ϕ± themselves
-        HIPCHK(hipMemcpyAsync(h->d_b, st->phi, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->work.b, st->phi, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     else
-        RC(elph_launch_lambda_rhs(h, h->d_b, st->phi, st->x, st->dtau, nch));
-    HIPCHK(hipMemsetAsync(h->d_x, 0, 2 * (size_t)nch * nd * sizeof(double), h->stream));
+        RC(elph_launch_lambda_rhs(h, h->work.b, st->phi, st->x, st->dtau, nch));
+    HIPCHK(hipMemsetAsync(h->work.x, 0, 2 * (size_t)nch * nd * sizeof(double), h->stream));
     h->x_zero = true;
     if (sharded(h)) {      // one lattice over several ranks: the two solves one after the other through the sharded kernel (shard.hip)
         h->x_zero = false;
         return elph_i_shard_solve_pair(h, nullptr, 0, power, iters, flag);
     }
-    const double tol0 = h->tol;
-    h->tol = pow(tol0, power);
     std::vector<int64_t> it2((size_t)2 * nch, 0);
     std::vector<double> res2((size_t)2 * nch);
     std::vector<int> fl2((size_t)2 * nch, 0);
-    const int rc = elph_i_ldiv_core(h, 2 * nch, use, 0, it2.data(), res2.data(), fl2.data());
-    h->tol = tol0;
-    if (rc) return rc;
-    for (int c = 0; c < nch; ++c) {
-        int64_t tot = it2[(size_t)c];
-        int fl = fl2[(size_t)c];
-        if (fl == 0) { tot += it2[(size_t)nch + c]; fl = fl2[(size_t)nch + c]; }
-        if (fl == 0) tot = (tot + 1) / 2;
-        iters[c] = tot;
-        flag[c] = fl;
+    {
+        TolPower scope(h, power);
+        RC(elph_i_ldiv_core(h, 2 * nch, use, 0, it2.data(), res2.data(), fl2.data()));
     }
+    elph_fold_pair(nch, it2.data(), fl2.data(), iters, flag);
     return ELPH_OK;
 }
 
@@ -369,7 +361,7 @@ int fa(elph_handle_s *h, HmcState *st, double *out, const double *in, double pow
 int calc_H(elph_handle_s *h, HmcState *st, double *H, double *S, double *K) {
     const int nch = st->nch;
     std::vector<double> sf((size_t)2 * nch), sb((size_t)nch), k((size_t)nch);
-    RC(dots_host(h, st, h->d_b, h->d_x, (long long)h->ndim, 2 * nch, sf.data()));
+    RC(dots_host(h, st, h->work.b, h->work.x, (long long)h->ndim, 2 * nch, sf.data()));
     RC(calc_Sb(h, st, sb.data()));
     RC(fa(h, st, st->y, st->v, 1.0));
     if (st->shared || st->wown) {       // calc_K of the SSH model counts primary fields only (HMC.jl:720-738); on a shard: the owned columns
@@ -390,11 +382,11 @@ int calc_H(elph_handle_s *h, HmcState *st, double *H, double *S, double *K) {
 int force(elph_handle_s *h, HmcState *st, bool with_Sb) {
     const long long n = (long long)st->nf * h->L * st->nch;
     if (st->ssh) {      // dSf/dx = -dMdx(M X₊, X₊) - dMdx(M X₋, X₋)  (HMC.jl:797-808; muldΛdx! is a no-op)
-        RC(elph_launch_force_ssh(h, h->d_p, h->d_x, nullptr, st->nch));        // bond brackets q[chain][tau][bond] (d_p is free here)
-        RC(elph_launch_ssh_scatter(h, st->dS, h->d_p, st->x, h->d_ssh_par, h->d_ssh_cb, st->nf, st->dtau, 1, -1.0, st->nch));
+        RC(elph_launch_force_ssh(h, h->work.p, h->work.x, nullptr, st->nch));        // bond brackets q[chain][tau][bond] (work.p is free here)
+        RC(elph_launch_ssh_scatter(h, st->dS, h->work.p, st->x, h->d_ssh_par, h->d_ssh_cb, st->nf, st->dtau, 1, -1.0, st->nch));
         RC(alias_sum(h, st, st->dS));
     } else {
-        RC(elph_launch_force_holstein(h, st->dS, h->d_x, st->phi, st->x, st->dtau, st->nch));
+        RC(elph_launch_force_holstein(h, st->dS, h->work.x, st->phi, st->x, st->dtau, st->nch));
     }
     // a sharded lattice: the fermion force is exact on the own rows (the MᵀM closure); the ghost rows — which the leapfrog moves along with
     // the own ones, so that the next update_model! sees the whole slab — take it from their owners.  The boson force and the Fourier
@@ -423,14 +415,6 @@ int leap(elph_handle_s *h, HmcState *st, double cv, double cx) {
     return chk("k_hmc_leap");
 }
 
-// host [nvec][ndim] (reference layout) -> device layout S, staged through the handle's staging buffer (cap = 2 nch vectors)
-// ncols = 0: site vectors (ndim); otherwise field vectors with that many columns
-int upload_vectors(elph_handle_s *h, double *dstS, const double *host, int nvec, int ncols = 0) {
-    const size_t per = (size_t)(ncols > 0 ? ncols : h->N) * (size_t)h->L;
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, host, (size_t)nvec * per * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    return elph_launch_r2s(h, dstS, h->d_stage_in, nvec, ncols);
-}
-
 HmcState *state_of(elph_handle_s *h) { return static_cast<HmcState *>(h->hmc); }
 
 // seed of the next batch: output number (batches drawn so far + 1) of SplitMix64 started at the handle's seed
@@ -438,7 +422,7 @@ uint64_t next_batch_seed(HmcState *st) { return sm64(st->rng_seed, ++st->rng_bat
 
 // a random input vector set: uploaded when the caller gives it, otherwise drawn on the device (no PCIe, no host generator)
 int randn_vectors(elph_handle_s *h, HmcState *st, double *dstS, const double *host, int nvec, int ncols = 0) {
-    if (host) return upload_vectors(h, dstS, host, nvec, ncols);
+    if (host) return elph_stage_in(h, dstS, host, nvec, ncols);
     if (!st->rng_on) { elph_set_error("a random input is NULL and elph_hmc_set_rng has not been called"); return ELPH_E_ARG; }
     const int nc = ncols > 0 ? ncols : (int)h->N;
     const long long n = (long long)nvec * nc * h->L;
@@ -500,7 +484,7 @@ static int hmc_create_core(elph_handle_s *h, int nchains, int nf, bool ssh, cons
                            const double *fa_mass) {
     // staging / scratch must hold the field vectors too (SSH: Nph columns may exceed the number of sites)
     const int per_field = (int)(((int64_t)nf + h->N - 1) / h->N);
-    RC(elph_i_ensure_capacity(h, std::max(2 * nchains, 2 * per_field + 1)));
+    RC(elph_work_reserve(h, std::max(2 * nchains, 2 * per_field + 1)));
     elph_hmc_free(h);
     HmcState *st = new HmcState();
     h->hmc = st;
@@ -517,7 +501,7 @@ static int hmc_create_core(elph_handle_s *h, int nchains, int nf, bool ssh, cons
     st->dtau = dtau;
     HIPCHK(hipMemcpyAsync(st->par, omega, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(st->par + nf, omega4, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RC(upload_vectors(h, st->faM, fa_mass, 1, nf));
+    RC(elph_stage_in(h, st->faM, fa_mass, 1, nf));
     HIPCHK(hipMemsetAsync(st->v, 0, nc * nfd * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(st->x, 0, nc * nfd * sizeof(double), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -529,7 +513,7 @@ extern "C" int elph_hmc_create_chains(elph_handle h, int nchains, const double *
     CHECK_H(h);
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("elph_hmc_create[_chains]: Holstein handles (SSH: elph_hmc_create_ssh)"); return ELPH_E_UNSUPPORTED; }
     if (nchains < 1 || !omega || !omega4 || !lambda || !lambda2 || !mu || !fa_mass || !(dtau > 0.0)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    RC(elph_i_ensure_capacity(h, 2 * nchains));
+    RC(elph_work_reserve(h, 2 * nchains));
     RC(elph_i_reserve_chains(h, nchains));
     const size_t N = (size_t)h->N;
     HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -587,12 +571,12 @@ extern "C" int elph_hmc_set_state(elph_handle h, const double *x, const double *
         }
     }
     if (x) {
-        RC(upload_vectors(h, st->x, x, st->nch, st->nf));
+        RC(elph_stage_in(h, st->x, x, st->nch, st->nf));
         HIPCHK(hipStreamSynchronize(h->stream));
         st->have_state = true;
     }
     if (v) {
-        RC(upload_vectors(h, st->v, v, st->nch, st->nf));
+        RC(elph_stage_in(h, st->v, v, st->nch, st->nf));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return ELPH_OK;
@@ -602,15 +586,12 @@ extern "C" int elph_hmc_get_state(elph_handle h, double *x, double *v) {
     CHECK_H(h);
     HmcState *st = state_of(h);
     if (!st) { elph_set_error("elph_hmc_create has not been called"); return ELPH_E_STATE; }
-    const size_t bytes = (size_t)st->nch * (size_t)st->nf * (size_t)h->L * sizeof(double);
     if (x) {
-        RC(elph_launch_s2r(h, h->d_stage_out, st->x, st->nch, st->nf));
-        HIPCHK(hipMemcpyAsync(x, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+        RC(elph_stage_out(h, x, st->x, st->nch, st->nf));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     if (v) {
-        RC(elph_launch_s2r(h, h->d_stage_out, st->v, st->nch, st->nf));
-        HIPCHK(hipMemcpyAsync(v, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+        RC(elph_stage_out(h, v, st->v, st->nch, st->nf));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return ELPH_OK;
@@ -766,7 +747,7 @@ extern "C" int elph_hmc_update_chains(elph_handle h, double dt, int64_t nt, int 
             return ELPH_E_UNSUPPORTED;
         }
     }
-    RC(elph_i_ensure_capacity(h, 2 * nch));
+    RC(elph_work_reserve(h, 2 * nch));
     RC(elph_i_reserve_chains(h, nch));
     // nd: site vectors (ϕ±, R±, solutions); nfd: field vectors (x, v, dS/dx) of one chain
     const size_t nd = (size_t)h->ndim, nfd = (size_t)st->nf * (size_t)h->L, cbytes = nfd * sizeof(double), bytes = (size_t)nch * cbytes;
@@ -806,11 +787,11 @@ extern "C" int elph_hmc_update_chains(elph_handle h, double dt, int64_t nt, int 
         RC(uniform_host(st, u_own, (size_t)nch));
         u_accept = u_own.data();
     }
-    RC(elph_launch_mul(h, 1, h->d_b, st->R2, 2 * nch));
+    RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
     if (st->ssh) {      // Λ⁻¹ ≡ 1: ϕ± = MᵀR±
-        HIPCHK(hipMemcpyAsync(st->phi, h->d_b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     } else {
-        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->d_b, st->x, h->d_lam,
+        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->work.b, st->x, h->d_lam,
                            (int)h->N, (int)h->L, st->dtau, nch);
         RC(chk("k_hmc_phi"));
     }
@@ -925,20 +906,20 @@ int langevin_force(elph_handle_s *h, HmcState *st, double *dS, const double *g_h
     const int nch = st->nch;
     RC(randn_vectors(h, st, st->R2, g_host, nch));                              // g in layout S
     if (use_precond) RC(elph_kpm_setup_chains(h, bmax, bmin, nullptr, nullptr, nullptr, nullptr, nullptr));   // setup!(P), :366
-    RC(elph_launch_mul(h, 1, h->d_b, st->R2, nch));                             // Mᵀg (model.v″, :378)
-    HIPCHK(hipMemsetAsync(h->d_x, 0, (size_t)nch * nd * sizeof(double), h->stream));   // fill!(M⁻¹g, 0), :367
+    RC(elph_launch_mul(h, 1, h->work.b, st->R2, nch));                             // Mᵀg (model.v″, :378)
+    HIPCHK(hipMemsetAsync(h->work.x, 0, (size_t)nch * nd * sizeof(double), h->stream));   // fill!(M⁻¹g, 0), :367
     h->x_zero = true;
     std::vector<double> res((size_t)nch);
     RC(elph_i_ldiv_core(h, nch, use_precond ? 1 : 0, 0, iters, res.data(), flag));
     const long long n = (long long)st->nf * h->L * nch;
     if (st->ssh) {      // muldMdx!(dSfdx, g, ssh, M⁻¹g) (SSHModels.jl:707-829) with u = g given; no shifted term for bond phonons
-        RC(elph_launch_force_ssh(h, h->d_p, h->d_x, st->R2, nch));
-        RC(elph_launch_ssh_scatter(h, dS, h->d_p, st->x, h->d_ssh_par, h->d_ssh_cb, st->nf, st->dtau, 1, -2.0, nch));
+        RC(elph_launch_force_ssh(h, h->work.p, h->work.x, st->R2, nch));
+        RC(elph_launch_ssh_scatter(h, dS, h->work.p, st->x, h->d_ssh_par, h->d_ssh_cb, st->nf, st->dtau, 1, -2.0, nch));
         RC(alias_sum(h, st, dS));
         hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, dS, st->x, st->par, st->nf, (int)h->L, st->dtau, 1, nch,
                            (const double *)nullptr);
     } else {
-        RC(elph_launch_dmdx_holstein(h, dS, st->R2, h->d_x, st->x, st->dtau, -2.0, nch));   // -2 gᵀ(∂M/∂x)M⁻¹g, :381-384
+        RC(elph_launch_dmdx_holstein(h, dS, st->R2, h->work.x, st->x, st->dtau, -2.0, nch));   // -2 gᵀ(∂M/∂x)M⁻¹g, :381-384
         hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, dS, st->x, st->par, (int)h->N, (int)h->L, st->dtau, 1, nch,
                            (const double *)h->d_lam);                           // calc_dSbdx!(dSdx, model, true), :341
     }
@@ -988,7 +969,7 @@ extern "C" int elph_langevin_evolve(elph_handle h, int scheme, double dt, int us
     }
     if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
     const int nch = st->nch;
-    RC(elph_i_ensure_capacity(h, std::max(2, 2 * nch)));
+    RC(elph_work_reserve(h, std::max(2, 2 * nch)));
     RC(elph_i_reserve_chains(h, nch));
     const size_t N = (size_t)h->N;
     const long long n = (long long)st->nf * h->L * nch;      // field vectors of all chains (Holstein: nch * ndim)
@@ -1095,7 +1076,7 @@ extern "C" int elph_hmc_special_move_chains(elph_handle h, int kind, const int64
         return ELPH_E_ARG;
     }
     if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
-    RC(elph_i_ensure_capacity(h, 2 * nch));
+    RC(elph_work_reserve(h, 2 * nch));
     RC(elph_i_reserve_chains(h, nch));
     const size_t nd = (size_t)h->ndim, nfd = (size_t)st->nf * (size_t)h->L;
     const int L = (int)h->L;
@@ -1112,11 +1093,11 @@ extern "C" int elph_hmc_special_move_chains(elph_handle h, int kind, const int64
         RC(uniform_host(st, u_own, (size_t)nch));
         u_accept = u_own.data();
     }
-    RC(elph_launch_mul(h, 1, h->d_b, st->R2, 2 * nch));
+    RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
     if (st->ssh) {
-        HIPCHK(hipMemcpyAsync(st->phi, h->d_b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     } else {
-        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->d_b, st->x, h->d_lam, (int)h->N, L,
+        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->work.b, st->x, h->d_lam, (int)h->N, L,
                            st->dtau, nch);
         RC(chk("k_hmc_phi"));
     }
@@ -1137,7 +1118,7 @@ extern "C" int elph_hmc_special_move_chains(elph_handle h, int kind, const int64
     std::vector<int64_t> iters((size_t)nch, 0);
     std::vector<int> flag((size_t)nch, 0), undo((size_t)nch, 0);
     RC(calc_OinvLphi(h, st, use_precond, 2.0, kpm_randn, &kpm_calls, iters.data(), flag.data()));
-    RC(dots_host(h, st, h->d_b, h->d_x, (long long)nd, 2 * nch, sf.data()));
+    RC(dots_host(h, st, h->work.b, h->work.x, (long long)nd, 2 * nch, sf.data()));
     RC(calc_Sb(h, st, sb1.data()));
     bool any_undo = false;
     for (int c = 0; c < nch; ++c) {
@@ -1362,7 +1343,7 @@ extern "C" int elph_hmc_special_update_chains(elph_handle h, int kind, int64_t n
     const bool ssh_swap = st->ssh && kind == 1;
     if (kind == 1 && !st->ssh && h->nb < 1) { elph_set_error("a Holstein swap needs a bond"); return ELPH_E_ARG; }
     if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
-    RC(elph_i_ensure_capacity(h, 2 * nch));
+    RC(elph_work_reserve(h, 2 * nch));
     RC(elph_i_reserve_chains(h, nch));
     SpScratch S;
     RC(special_scratch(st, L, (size_t)nmoves, ssh_swap, &S));
@@ -1392,11 +1373,11 @@ extern "C" int elph_hmc_special_update_chains(elph_handle h, int kind, int64_t n
         RC(randn_vectors(h, st, st->R2 + (size_t)nch * nd, nullptr, nch));
         if (use_precond) RC(randn_host(st, kpm_own, 2 * (size_t)nch * (size_t)h->N));
         const uint64_t seed_u = next_batch_seed(st);
-        RC(elph_launch_mul(h, 1, h->d_b, st->R2, 2 * nch));
+        RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
         if (st->ssh) {
-            HIPCHK(hipMemcpyAsync(st->phi, h->d_b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         } else {
-            hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->d_b, st->x, h->d_lam, (int)h->N, L,
+            hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->work.b, st->x, h->d_lam, (int)h->N, L,
                                st->dtau, nch);
             RC(chk("k_hmc_phi"));
         }
@@ -1409,7 +1390,7 @@ extern "C" int elph_hmc_special_update_chains(elph_handle h, int kind, int64_t n
         int64_t kpm_calls = 0;
         RC(calc_OinvLphi(h, st, use_precond, 2.0, use_precond ? kpm_own.data() : nullptr, &kpm_calls, iters.data() + row, flag.data() + row));
         HIPCHK(hipMemcpyAsync(S.flag, flag.data() + row, (size_t)nch * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        RC(dots_dev(h, p_sf, h->d_b, h->d_x, (long long)nd, 2 * nch));
+        RC(dots_dev(h, p_sf, h->work.b, h->work.x, (long long)nd, 2 * nch));
         RC(sb_dev(h, st, p_sb1));
         // the Metropolis test and the undo of the rejected chains
         hipLaunchKernelGGL(k_sp_accept, dim3((unsigned)((nch + ELPH_WAVE - 1) / ELPH_WAVE)), dim3(ELPH_WAVE), 0, h->stream, (const double *)S.part, nch, L,

@@ -1152,11 +1152,10 @@ int elph_launch_mul(elph_handle_s *h, int which, double *yS, const double *vS, i
 
 static CgBufs make_bufs(elph_handle_s *h, int nrhs) {
     CgBufs B;
-    const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)(h->npl);  // partial stride per array
-    B.x = h->d_x; B.r = h->d_r; B.z = h->d_z; B.zp = h->d_zp; B.p = h->d_p;
-    B.pap = h->d_part; B.rr = h->d_part + P; B.rz = h->d_part + 2 * P;
-    B.state = h->d_state; B.params = h->cur_params; B.hist = h->d_hist;
-    B.alpha = h->d_alpha;
+    B.x = h->work.x; B.r = h->work.r; B.z = h->work.z; B.zp = h->work.zp; B.p = h->work.p;
+    B.pap = h->work.pap(); B.rr = h->work.rr(); B.rz = h->work.rz();
+    B.state = h->work.state; B.params = h->cur_params; B.hist = h->work.hist;
+    B.alpha = h->work.alpha;
     B.dot_lo = h->dot_hi > 0 ? h->dot_lo : 0;
     B.dot_hi = h->dot_hi > 0 ? h->dot_hi : (int)h->N;
     B.nrz = (int)(h->L * h->npl);
@@ -1281,7 +1280,7 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
     const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
     CgBufs B = make_bufs(h, nrhs);
     // kernels that skip finished right-hand sides read the state copy written by the latest k_cg_ap launch
-    const CgState *st = cg_mode ? h->d_state + (h->ap_count & 1) : nullptr;
+    const CgState *st = cg_mode ? h->work.state + (h->ap_count & 1) : nullptr;
     if (!h->kpm.any_active()) {
         if (cg_mode) {
             hipLaunchKernelGGL(k_copy_dot, dim3((unsigned)L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, zS, rS, B.rz,
@@ -1300,12 +1299,12 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
     const bool fold = cg_mode == 2 && pl.fold;
     if (!(parts & 1)) {
     } else if (cg_mode == 2) {
-        int rcd = elph_dft_mfma_fwd_xr(h, h->d_nu, const_cast<double *>(rS), B.z, B.pap, B.npap, B.rr, B.alpha, N, nrhs, st,
+        int rcd = elph_dft_mfma_fwd_xr(h, h->work.nu, const_cast<double *>(rS), B.z, B.pap, B.npap, B.rr, B.alpha, N, nrhs, st,
                                        fold ? h->kpm.d_fold + (h->solo_chain >= 0 && h->kpm.nch() > 1 ? 2 * (size_t)h->solo_chain * Lo2 : 0) : nullptr,
                                        (h->solo_chain >= 0) ? 1 : std::max(1, h->kpm.nch()), B.rz, B.nrz, 2 * Lo2);
         if (rcd) return rcd;
     } else {
-        int rcd = elph_dft_fwd_twisted(h, h->d_nu, rS, N, nrhs, st);
+        int rcd = elph_dft_fwd_twisted(h, h->work.nu, rS, N, nrhs, st);
         if (rcd) return rcd;
     }
     const size_t shm = (size_t)N * sizeof(double2);
@@ -1331,18 +1330,18 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         const int lds_tables = (N <= 65535 && shm + tab <= 64 * 1024) ? 1 : 0;
         DISPATCH_NPL(cnpl, {
             hipLaunchKernelGGL((k_kpm_cheb<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs), shm + (lds_tables ? tab : 0),
-                               h->stream, h->d_nu, K, m, Lo2, st, lds_tables, rz_done ? B.rz : nullptr, B.nrz, B.rr);
+                               h->stream, h->work.nu, K, m, Lo2, st, lds_tables, rz_done ? B.rz : nullptr, B.nrz, B.rr);
         });
     }
     // r.z partial slots: (blockIdx.y * gridDim.x + blockIdx.x) < ceil(L/TPT)*nst <= L*npl = nrz; the kernel clears the rest
     if ((parts & 4) && cg_mode == 2 && pl.px) {
         // p/x-fused tail: x += alpha p, p = P^-1 r + beta p in the epilogue of the inverse transform; P^-1 r itself is not written
         if (!rz_done) { elph_set_error("p/x-fused iteration planned, but the Chebyshev kernel did not deliver r.z (internal error)"); return ELPH_E_STATE; }
-        int rcd = elph_dft_mfma_inv_px(h, h->d_nu, N, nrhs, st, h->d_p, h->d_x, B.alpha, B.rz, B.nrz);
+        int rcd = elph_dft_mfma_inv_px(h, h->work.nu, N, nrhs, st, h->work.p, h->work.x, B.alpha, B.rz, B.nrz);
         if (rcd) return rcd;
     } else if (parts & 4) {
         const bool fuse = cg_mode && !rz_done;
-        int rcd = elph_dft_inv_twisted(h, zS, h->d_nu, N, nrhs, st, fuse ? rS : nullptr, fuse ? B.rz : nullptr, B.nrz);
+        int rcd = elph_dft_inv_twisted(h, zS, h->work.nu, N, nrhs, st, fuse ? rS : nullptr, fuse ? B.rz : nullptr, B.nrz);
         if (rcd) return rcd;
     }
     return elph_launch_check("kpm apply");
@@ -1372,52 +1371,38 @@ int elph_launch_kpm_apply_side(elph_handle_s *h, double *zS, const double *rS, i
         elph_set_error("the one-sided KPM preconditioners serve lattices of up to %d sites (this one: %d)", 6 * cbs, N);
         return ELPH_E_UNSUPPORTED;
     }
-    RC(elph_dft_fwd_twisted(h, h->d_nu, rS, N, nrhs, nullptr));
+    RC(elph_dft_fwd_twisted(h, h->work.nu, rS, N, nrhs, nullptr));
 #define SIDE_NPL(n)                                                                                                                            \
     case n:                                                                                                                                    \
         if (transposed) hipLaunchKernelGGL((k_kpm_cheb_side<n, true>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs),               \
-                                           shm + (lds_tables ? tab : 0), h->stream, h->d_nu, K, m, Lo2, done, lds_tables);                     \
+                                           shm + (lds_tables ? tab : 0), h->stream, h->work.nu, K, m, Lo2, done, lds_tables);                     \
         else hipLaunchKernelGGL((k_kpm_cheb_side<n, false>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs),                         \
-                                shm + (lds_tables ? tab : 0), h->stream, h->d_nu, K, m, Lo2, done, lds_tables);                                \
+                                shm + (lds_tables ? tab : 0), h->stream, h->work.nu, K, m, Lo2, done, lds_tables);                                \
         break;
     switch (cnpl) { SIDE_NPL(1) SIDE_NPL(2) SIDE_NPL(3) SIDE_NPL(4) SIDE_NPL(5) SIDE_NPL(6) }
 #undef SIDE_NPL
     RC(elph_launch_check("k_kpm_cheb_side"));
-    return elph_dft_inv_twisted(h, zS, h->d_nu, N, nrhs, nullptr, nullptr, nullptr, (int)(h->L * h->npl));
+    return elph_dft_inv_twisted(h, zS, h->work.nu, N, nrhs, nullptr, nullptr, nullptr, (int)(h->L * h->npl));
 }
 
 int elph_launch_rz_partials(elph_handle_s *h, int nrhs);
 
 int elph_launch_cg_init(elph_handle_s *h, int nrhs, int use_prec, bool x_zero) {
-    // expects d_b (layout S), d_x = initial guess; computes r0, p0 and seeds the state
+    // expects work.b (layout S), work.x = initial guess; computes r0, p0 and seeds the state
     h->plan = elph_plan_cg(h, nrhs, use_prec, nrhs);      // the kernels of this solve's iteration
-    CgBufs B = make_bufs(h, nrhs);
-    h->ap_count = 0;
-    const int N = (int)h->N, L = (int)h->L;
-    int rc = ELPH_OK;
     if (x_zero) {       // x0 = 0 (the library zeroed it for this solve): A x0 = 0 without the mat-vec
-        if (hipMemsetAsync(h->d_tmp, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream) != hipSuccess) { elph_set_error("memset failed"); return ELPH_E_HIP; }
+        if (hipMemsetAsync(h->work.tmp, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream) != hipSuccess) { elph_set_error("memset failed"); return ELPH_E_HIP; }
     } else {
-        rc = elph_launch_mul(h, 2, h->d_tmp, h->d_x, nrhs);
-        if (rc) return rc;
+        RC(elph_launch_mul(h, 2, h->work.tmp, h->work.x, nrhs));
     }
-    const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
-    double *bb = h->d_part + 3 * P;
-    hipLaunchKernelGGL(k_cg_init, dim3((unsigned)L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->d_b, h->d_tmp, bb, N, L);
-    rc = elph_launch_check("k_cg_init");
-    if (rc) return rc;
+    RC(elph_launch_cg_init_only(h, nrhs));
     if (use_prec) {
         // z0 = P^-1 r0, p0 = z0, rho0 = r0.z0 (IterativeSolvers.jl:182-189); once per solve
-        rc = elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 0);
-        if (rc) return rc;
-        rc = elph_launch_rz_partials(h, nrhs);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_cg_init_prec, dim3((unsigned)L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, N, L);
-        rc = elph_launch_check("k_cg_init_prec");
-        if (rc) return rc;
+        RC(elph_launch_kpm_apply(h, h->work.zp, h->work.r, nrhs, 0));
+        RC(elph_launch_rz_partials(h, nrhs));
+        RC(elph_launch_cg_init_prec_only(h, nrhs));
     }
-    hipLaunchKernelGGL(k_cg_state0, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, B, bb, L);
-    return elph_launch_check("k_cg_state0");
+    return elph_launch_cg_state0_only(h, nrhs);
 }
 
 // partial r.zp into B.rz (slot t = slice sum, rest zero)
@@ -1438,7 +1423,7 @@ __global__ void __launch_bounds__(WAVE) k_rz_part(const double *__restrict__ r, 
 
 int elph_launch_rz_partials(elph_handle_s *h, int nrhs) {
     CgBufs B = make_bufs(h, nrhs);
-    hipLaunchKernelGGL(k_rz_part, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, h->d_r, h->d_zp, B.rz,
+    hipLaunchKernelGGL(k_rz_part, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, h->work.r, h->work.zp, B.rz,
                        B.nrz, (int)h->N, (int)h->L);
     return elph_launch_check("k_rz_part");
 }
@@ -1486,10 +1471,10 @@ int elph_launch_cg_iteration(elph_handle_s *h, int nrhs, int use_prec) {
     CgBufs B = make_bufs(h, nrhs);
     int rc = launch_cg_ap(h, B, nrhs, use_prec && h->plan.px);
     if (rc) return rc;
-    if (use_prec && h->plan.xr_in_fwd) return elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 2);      // k_cg_xr rides on the forward transform
+    if (use_prec && h->plan.xr_in_fwd) return elph_launch_kpm_apply(h, h->work.zp, h->work.r, nrhs, 2);      // k_cg_xr rides on the forward transform
     rc = launch_cg_xr(h, B, nrhs);
     if (rc) return rc;
-    return use_prec ? elph_launch_kpm_apply(h, h->d_zp, h->d_r, nrhs, 1) : ELPH_OK;
+    return use_prec ? elph_launch_kpm_apply(h, h->work.zp, h->work.r, nrhs, 1) : ELPH_OK;
 }
 
 // one kernel of the iteration alone (measurement; the sharded iteration): 0 = k_cg_ap, 1 = k_cg_xr
@@ -1500,15 +1485,14 @@ int elph_launch_cg_kernel(elph_handle_s *h, int nrhs, int which) {
 
 CgBufs elph_make_bufs(elph_handle_s *h, int nrhs) { return make_bufs(h, nrhs); }
 
-// true residual of d_x against d_b -> d_scal[rhs]
+// true residual of work.x against work.b -> work.scal[rhs]
 int elph_launch_residual(elph_handle_s *h, int nrhs) {
-    int rc = elph_launch_mul(h, 2, h->d_tmp, h->d_x, nrhs);
+    int rc = elph_launch_mul(h, 2, h->work.tmp, h->work.x, nrhs);
     if (rc) return rc;
-    const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
-    double *pa = h->d_part, *pb = h->d_part + P;
-    hipLaunchKernelGGL(k_resid_part, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, h->d_tmp, h->d_b, pa,
+    double *pa = h->work.pap(), *pb = h->work.rr();
+    hipLaunchKernelGGL(k_resid_part, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, h->work.tmp, h->work.b, pa,
                        pb, (int)h->N, (int)h->L);
-    hipLaunchKernelGGL(k_resid_final, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, pa, pb, h->d_scal, (int)h->L);
+    hipLaunchKernelGGL(k_resid_final, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, pa, pb, h->work.scal, (int)h->L);
     return elph_launch_check("residual");
 }
 
@@ -1516,11 +1500,11 @@ int elph_launch_tau_to_omega(elph_handle_s *h, double2 *nuS_full, const double *
     const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
 
     {
-        int rcd = elph_dft_fwd_twisted(h, h->d_nu, vS, N, 1, nullptr);
+        int rcd = elph_dft_fwd_twisted(h, h->work.nu, vS, N, 1, nullptr);
         if (rcd) return rcd;
     }
     const long long n = (long long)N * L;
-    hipLaunchKernelGGL(k_expand_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nuS_full, h->d_nu, N,
+    hipLaunchKernelGGL(k_expand_spectrum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nuS_full, h->work.nu, N,
                        L, Lo2);
     return elph_launch_check("tau_to_omega");
 }
@@ -1535,7 +1519,7 @@ int elph_launch_omega_to_tau(elph_handle_s *h, double *vS, const double2 *nuS_fu
 
 int elph_launch_fft_accel(elph_handle_s *h, double *outS, const double *inS, const double *diagS, double power,
                           int64_t ncol, int nvec) {
-    return elph_dft_accel(h, outS, inS, diagS, power, (int)ncol, h->d_nu, nvec);
+    return elph_dft_accel(h, outS, inS, diagS, power, (int)ncol, h->work.nu, nvec);
 }
 
 // nch chains: b, phi laid out [sign][chain][ndim], x [chain][ndim]
@@ -1576,13 +1560,11 @@ int elph_launch_force_ssh(elph_handle_s *h, double *q, const double *XS, const d
     return elph_launch_check("k_force_ssh");
 }
 
-// pieces of elph_launch_cg_init for the step-wise API (A x0 expected in d_tmp)
+// the pieces of elph_launch_cg_init, also for the step-wise callers (A x0 expected in work.tmp)
 int elph_launch_cg_init_only(elph_handle_s *h, int nrhs) {
     CgBufs B = make_bufs(h, nrhs);
     h->ap_count = 0;
-    const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
-    double *bb = h->d_part + 3 * P;
-    hipLaunchKernelGGL(k_cg_init, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->d_b, h->d_tmp, bb,
+    hipLaunchKernelGGL(k_cg_init, dim3((unsigned)h->L, (unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->work.b, h->work.tmp, h->work.bb(),
                        (int)h->N, (int)h->L);
     return elph_launch_check("k_cg_init");
 }
@@ -1595,7 +1577,6 @@ int elph_launch_cg_init_prec_only(elph_handle_s *h, int nrhs) {
 
 int elph_launch_cg_state0_only(elph_handle_s *h, int nrhs) {
     CgBufs B = make_bufs(h, nrhs);
-    const size_t P = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
-    hipLaunchKernelGGL(k_cg_state0, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->d_part + 3 * P, (int)h->L);
+    hipLaunchKernelGGL(k_cg_state0, dim3((unsigned)nrhs), dim3(WAVE), 0, h->stream, B, h->work.bb(), (int)h->L);
     return elph_launch_check("k_cg_state0");
 }

@@ -347,7 +347,7 @@ int ms_alloc(T **p, size_t n) {
 int ms_reserve(elph_handle_s *h, int nrhs, int restart /* 0: BiCGStab */) {
     if (!h->msolve) h->msolve = new MsolveState();
     MsolveState *S = ms_state(h);
-    RC(elph_i_ensure_capacity(h, nrhs));
+    RC(elph_work_reserve(h, nrhs));
     const size_t nd = (size_t)h->ndim;
     if (nrhs > S->cap) {
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -396,12 +396,12 @@ int ms_apply(elph_handle_s *h, double *z, const double *r, int nrhs, int transpo
     return elph_launch_kpm_apply_side(h, z, r, nrhs, transposed, ms_state(h)->done);
 }
 
-// solve!(x, A, b, bicgstab[, P]) on d_b / d_x
+// solve!(x, A, b, bicgstab[, P]) on work.b / work.x
 int run_bicgstab(elph_handle_s *h, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t *iters) {
     RC(ms_reserve(h, nrhs, 0));
     MsolveState *S = ms_state(h);
     BiBufs B;
-    B.x = h->d_x; B.b = h->d_b; B.rec = S->rec; B.done = S->done; B.nd = h->ndim;
+    B.x = h->work.x; B.b = h->work.b; B.rec = S->rec; B.done = S->done; B.nd = h->ndim;
     B.r = ms_vec(h, 0); B.rt = ms_vec(h, 1); B.p = ms_vec(h, 2); B.s = ms_vec(h, 3); B.v = ms_vec(h, 4); B.t = ms_vec(h, 5);
     B.ph = use_prec ? ms_vec(h, 6) : B.p;
     B.sh = use_prec ? ms_vec(h, 7) : B.s;
@@ -424,23 +424,23 @@ int run_bicgstab(elph_handle_s *h, int transposed, int nrhs, int use_prec, doubl
     return ELPH_OK;
 }
 
-// solve!(x, A, b, gmres[, M]) on d_b / d_x
+// solve!(x, A, b, gmres[, M]) on work.b / work.x
 int run_gmres(elph_handle_s *h, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t solver_maxiter, int restart,
               int64_t *iters) {
     RC(ms_reserve(h, nrhs, restart));
     MsolveState *S = ms_state(h);
     GmBufs G;
-    G.x = h->d_x; G.b = h->d_b; G.V = S->V; G.gm = S->gm; G.rec = S->rec; G.done = S->done;
+    G.x = h->work.x; G.b = h->work.b; G.V = S->V; G.gm = S->gm; G.rec = S->rec; G.done = S->done;
     G.nd = h->ndim; G.vstride = (long long)S->cap * h->ndim; G.R = restart;
     double *w_raw = ms_vec(h, 8), *r_raw = ms_vec(h, 9);
     G.w = use_prec ? ms_vec(h, 10) : w_raw;
     G.r = r_raw;
-    G.pb = use_prec ? ms_vec(h, 11) : h->d_b;
+    G.pb = use_prec ? ms_vec(h, 11) : h->work.b;
     const int which = transposed ? 1 : 0, bs = ms_block(h);
     const size_t shm = (size_t)(restart + 1) * sizeof(double);
     const dim3 grid((unsigned)nrhs), block((unsigned)bs);
     HIPCHK(hipMemsetAsync(S->done, 0, (size_t)nrhs * sizeof(int), h->stream));
-    if (use_prec) RC(ms_apply(h, ms_vec(h, 11), h->d_b, nrhs, transposed));
+    if (use_prec) RC(ms_apply(h, ms_vec(h, 11), h->work.b, nrhs, transposed));
 
     // r = P⁻¹ (b - A x), then the tests between two cycles and the start of the next one
     auto residual_and_start = [&](int first, int64_t iter) -> int {
@@ -496,12 +496,12 @@ int ms_solve(elph_handle_s *h, int solver, int transposed, int nrhs, int use_pre
     return run_gmres(h, transposed, nrhs, use_prec, tol, maxiter, solver_maxiter, restart, iters);
 }
 
-// residual_error and flag of ldiv! for d_x against d_b; x zeroed where the flag is positive (Models.jl:93-126, :150-183)
+// residual_error and flag of ldiv! for work.x against work.b; x zeroed where the flag is positive (Models.jl:93-126, :150-183)
 int ms_residual_and_flags(elph_handle_s *h, int transposed, int nrhs, const int64_t *iters, int64_t cmp_maxiter, double *resid, int *flag) {
     MsolveState *S = ms_state(h);
     double *ax = ms_vec(h, 8);
-    RC(elph_launch_mul(h, transposed ? 1 : 0, ax, h->d_x, nrhs));
-    hipLaunchKernelGGL(k_ms_resid, dim3((unsigned)nrhs), dim3((unsigned)ms_block(h)), 0, h->stream, S->scal, ax, h->d_b, (long long)h->ndim);
+    RC(elph_launch_mul(h, transposed ? 1 : 0, ax, h->work.x, nrhs));
+    hipLaunchKernelGGL(k_ms_resid, dim3((unsigned)nrhs), dim3((unsigned)ms_block(h)), 0, h->stream, S->scal, ax, h->work.b, (long long)h->ndim);
     RC(elph_launch_check("k_ms_resid"));
     HIPCHK(hipMemcpyAsync(S->h_scal, S->scal, sizeof(double) * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -509,7 +509,7 @@ int ms_residual_and_flags(elph_handle_s *h, int transposed, int nrhs, const int6
         resid[r] = S->h_scal[r];
         if (resid[r] > sqrt(h->tol)) {           // (NaN compares false, as in the reference)
             flag[r] = (iters[r] == cmp_maxiter) ? 1 : 2;
-            HIPCHK(hipMemsetAsync(h->d_x + (size_t)r * (size_t)h->ndim, 0, (size_t)h->ndim * sizeof(double), h->stream));
+            HIPCHK(hipMemsetAsync(h->work.x + (size_t)r * (size_t)h->ndim, 0, (size_t)h->ndim * sizeof(double), h->stream));
         } else {
             flag[r] = 0;
         }
@@ -517,7 +517,7 @@ int ms_residual_and_flags(elph_handle_s *h, int transposed, int nrhs, const int6
     return ELPH_OK;
 }
 
-// ldiv! on d_b / d_x
+// ldiv! on work.b / work.x
 int ms_ldiv(elph_handle_s *h, int solver, int transposed, int nrhs, int use_prec, int64_t maxiter, int restart, int64_t *iters, double *resid,
             int *flag) {
     if (maxiter == 0) maxiter = h->maxiter;                                                       // Models.jl:78-80, :143-145
@@ -525,47 +525,15 @@ int ms_ldiv(elph_handle_s *h, int solver, int transposed, int nrhs, int use_prec
     RC(ms_residual_and_flags(h, transposed, nrhs, iters, use_prec ? maxiter : h->maxiter, resid, flag));      // :103 maxiter, :160 solver.maxiter
     if (!use_prec) return ELPH_OK;
     // flagged right-hand sides: again without the preconditioner, from x = 0 (zeroed above), 10 x maxiter (:129-133), one at a time in slot 0
-    const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
     for (int r = 0; r < nrhs; ++r) {
         if (flag[r] == 0) continue;
-        double *park_x = h->d_stage_out, *park_b = h->d_stage_in;
-        if (r != 0) {
-            HIPCHK(hipMemcpyAsync(park_x, h->d_x, bytes, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(park_b, h->d_b, bytes, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_x, h->d_x + r * nd, bytes, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_b, h->d_b + r * nd, bytes, hipMemcpyDeviceToDevice, h->stream));
-        }
         int64_t it1 = 0; double rs1 = 0; int fl1 = 0;
-        if (h->nchains > 1) h->solo_chain = r % h->nchains;      // slot 0 must keep rhs r's fermion matrix
-        int rc1 = ms_solve(h, solver, transposed, 1, 0, h->tol, 10 * maxiter, h->maxiter, restart, &it1);
-        if (rc1 == ELPH_OK) rc1 = ms_residual_and_flags(h, transposed, 1, &it1, h->maxiter, &rs1, &fl1);
-        h->solo_chain = -1;
-        RC(rc1);
+        RC(elph_retry_in_slot0(h, r, [&]() -> int {
+            RC(ms_solve(h, solver, transposed, 1, 0, h->tol, 10 * maxiter, h->maxiter, restart, &it1));
+            return ms_residual_and_flags(h, transposed, 1, &it1, h->maxiter, &rs1, &fl1);
+        }));
         iters[r] = it1; resid[r] = rs1; flag[r] = fl1;
-        if (r != 0) {
-            HIPCHK(hipMemcpyAsync(h->d_x + r * nd, h->d_x, bytes, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_x, park_x, bytes, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_b, park_b, bytes, hipMemcpyDeviceToDevice, h->stream));
-        }
     }
-    return ELPH_OK;
-}
-
-// X, B (host, reference layout) into d_x, d_b
-int ms_stage_in(elph_handle_s *h, int nrhs, const double *X, const double *B) {
-    const size_t bytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, B, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_b, h->d_stage_in, nrhs));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, X, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_x, h->d_stage_in, nrhs));
-    return ELPH_OK;
-}
-
-int ms_stage_out(elph_handle_s *h, int nrhs, double *X) {
-    const size_t bytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_x, nrhs));
-    HIPCHK(hipMemcpyAsync(X, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
 
@@ -588,13 +556,10 @@ extern "C" int elph_kpm_apply_side(elph_handle h, int nvec, double *vout, const 
     CHECK_H(h);
     if (!vout || !vin || nvec < 1) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     if (!h->kpm.ready) { elph_set_error("elph_kpm_setup has not been called"); return ELPH_E_STATE; }
-    RC(elph_i_ensure_capacity(h, nvec));
-    const size_t bytes = (size_t)nvec * (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, vin, bytes, hipMemcpyHostToDevice, h->stream));
-    RC(elph_launch_r2s(h, h->d_r, h->d_stage_in, nvec));
-    RC(elph_launch_kpm_apply_side(h, h->d_zp, h->d_r, nvec, transposed ? 1 : 0, nullptr));
-    RC(elph_launch_s2r(h, h->d_stage_out, h->d_zp, nvec));
-    HIPCHK(hipMemcpyAsync(vout, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    RC(elph_work_reserve(h, nvec));
+    RC(elph_stage_in(h, h->work.r, vin, nvec));
+    RC(elph_launch_kpm_apply_side(h, h->work.zp, h->work.r, nvec, transposed ? 1 : 0, nullptr));
+    RC(elph_stage_out(h, vout, h->work.zp, nvec));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -609,9 +574,12 @@ extern "C" int elph_msolve(elph_handle h, int solver, int transposed, int nrhs, 
     if (solver_maxiter == 0) solver_maxiter = h->maxiter;
     if (maxiter == 0) maxiter = solver_maxiter;
     RC(ms_reserve(h, nrhs, solver == ELPH_SOLVER_GMRES ? restart : 0));
-    RC(ms_stage_in(h, nrhs, X, B));
+    RC(elph_stage_in(h, h->work.b, B, nrhs));
+    RC(elph_stage_in(h, h->work.x, X, nrhs));
     RC(ms_solve(h, solver, transposed ? 1 : 0, nrhs, use_precond ? 1 : 0, tol, maxiter, solver_maxiter, restart, iters));
-    return ms_stage_out(h, nrhs, X);
+    RC(elph_stage_out(h, X, h->work.x, nrhs));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ELPH_OK;
 }
 
 extern "C" int elph_mldiv(elph_handle h, int solver, int transposed, int nrhs, double *X, const double *B, int use_precond, int64_t maxiter,
@@ -621,7 +589,10 @@ extern "C" int elph_mldiv(elph_handle h, int solver, int transposed, int nrhs, d
     restart = default_restart(h, restart);
     RC(need_ready(h, solver, transposed, nrhs, use_precond, restart));
     RC(ms_reserve(h, nrhs, solver == ELPH_SOLVER_GMRES ? restart : 0));
-    RC(ms_stage_in(h, nrhs, X, B));
+    RC(elph_stage_in(h, h->work.b, B, nrhs));
+    RC(elph_stage_in(h, h->work.x, X, nrhs));
     RC(ms_ldiv(h, solver, transposed ? 1 : 0, nrhs, use_precond ? 1 : 0, maxiter, restart, iters, residual_error, flag));
-    return ms_stage_out(h, nrhs, X);
+    RC(elph_stage_out(h, X, h->work.x, nrhs));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ELPH_OK;
 }

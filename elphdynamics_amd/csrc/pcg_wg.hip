@@ -575,13 +575,13 @@ int elph_pcg_wg(elph_handle_s *h, const CgBufs &B, int nrhs, long long fixed_ite
     RC(elph_wg_ctl(h, n_slots, n_flags, elph_wg_tag_span(B.params, fixed_iters), elph_wg_timeout_ms(2000), WG_TAGS_RUNNING, &R));
     R.G = G; R.W = W;
     R.fixed_iters = fixed_iters;
-    if (x0_save)        // the caller's initial guess, for the fallback (run_cg: in d_tmp — A x0 there has been consumed)
-        HIPCHK(hipMemcpyAsync(x0_save, h->d_x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (x0_save)        // the caller's initial guess, for the fallback (run_cg: in work.tmp — A x0 there has been consumed)
+        HIPCHK(hipMemcpyAsync(x0_save, h->work.x, (size_t)nrhs * (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     wg::PcgCtl Pc;
     Pc.flags = R.slots + n_slots;
     Pc.Wf = h->dft.W[0][0]; Pc.Wi = h->dft.W[0][1];
     Pc.rtf = h->dft.shape.mf[0][0].groups * 5; Pc.rti = h->dft.shape.mf[0][1].groups * 5;       // (dft_mfma.hip: MG = 5 row tiles per group)
-    Pc.nu = h->d_nu; Pc.zp = h->d_zp;
+    Pc.nu = h->work.nu; Pc.zp = h->work.zp;
     Pc.K = elph_kpm_dev(h);
     Pc.sqc = h->kpm.d_sq_cbar; Pc.sqs = h->kpm.d_sq_sbar;
     Pc.Lo2 = (int)((h->L + 1) / 2);

@@ -577,7 +577,7 @@ bool elph_pg_disorder_ok(const elph_handle_s *h) {
     return s.patch_kind() == LatticeShape::SQUARE && h->d_pg_bond && pgrid::patch_takes_disorder(s.PX, s.PY, s.NW) && !(e && e[0] == '0');
 }
 
-// nu (d_nu: [nrhs][Lo2][N] complex) <- P^-1 in frequency space, every (right-hand side, frequency) a block of two wavefronts
+// nu (work.nu: [nrhs][Lo2][N] complex) <- P^-1 in frequency space, every (right-hand side, frequency) a block of two wavefronts
 int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_part, int nrz, const double *rr_part) {
     KpmDev K = elph_kpm_dev(h);
     const int Lo2 = (int)((h->L + 1) / 2), N = (int)h->N, Ls = h->shape.LX;
@@ -589,7 +589,7 @@ int elph_pg_kpm_cheb(elph_handle_s *h, int nrhs, const CgState *st, double *rz_p
     if (!h->kpm.hop_uniform && !elph_pg_disorder_ok(h)) { elph_set_error("k_kpm_cheb_pg: hopping disorder on a patch shape without a table variant"); return ELPH_E_UNSUPPORTED; }
     const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !h->kpm.hop_uniform, [&](auto tag) {
         using LAT = typename decltype(tag)::type;
-        hipLaunchKernelGGL((k_kpm_cheb_pg<LAT>), grid, dim3(2 * LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, h->d_nu, K, N, Ls, Lo2, st, rz_part, nrz,
+        hipLaunchKernelGGL((k_kpm_cheb_pg<LAT>), grid, dim3(2 * LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, h->work.nu, K, N, Ls, Lo2, st, rz_part, nrz,
                            (int)h->L, rr_part, h->d_pg_bond);
     });
     if (rc) return rc;

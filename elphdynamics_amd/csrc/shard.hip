@@ -270,23 +270,19 @@ static int shard_run(elph_handle_s *h, const double *b_slab, double tol, int64_t
     if (!S || !S->prepared) { elph_set_error("elph_shard_prepare (and the caller's barrier) must precede every sharded solve"); return ELPH_E_STATE; }
     S->prepared = false;
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
-    int rc = elph_i_ensure_capacity(h, 1);
+    int rc = elph_work_reserve(h, 1);
     if (rc) return rc;
     CgParams P;
     P.tol = tol; P.kmax = (kappa_max > 0.0) ? kappa_max : h->kmax; P.maxiter = maxiter; P.use_prec = 0; P.record_hist = 0; P.hist_stride = 0;
     h->cur_params = P;
     h->plan = elph_plan_cg(h, 1, false, 1);
     const size_t bytes = (size_t)h->ndim * sizeof(double);
-    if (b_slab) {
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, b_slab, bytes, hipMemcpyHostToDevice, h->stream));
-        rc = elph_launch_r2s(h, h->d_b, h->d_stage_in, 1);
-        if (rc) return rc;
-    }
+    if (b_slab && (rc = elph_stage_in(h, h->work.b, b_slab, 1))) return rc;
     // x0 = 0, r0 = p0 = b (IterativeSolvers.jl:259-274 with a zero initial guess, as every caller passes: HMC.jl:854)
-    HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_r, h->d_b, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_p, h->d_b, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_state, 0, 2 * sizeof(CgState), h->stream));
+    HIPCHK(hipMemsetAsync(h->work.x, 0, bytes, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.r, h->work.b, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.p, h->work.b, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->work.state, 0, 2 * sizeof(CgState), h->stream));
     CgBufs B = elph_make_bufs(h, 1);
     B.params = P;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -303,7 +299,7 @@ static int shard_run(elph_handle_s *h, const double *b_slab, double tol, int64_t
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.h_state, h->work.state, sizeof(CgState) * 2, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     bool aborted = false;
     rc = elph_wg_aborted(h, &aborted);
@@ -312,8 +308,8 @@ static int shard_run(elph_handle_s *h, const double *b_slab, double tol, int64_t
     return ELPH_OK;
 }
 
-// ALL RANKS OF A SOLVE WHOSE SLABS LIVE ON ONE DEVICE (slabs.hip), one launch: every slab's right-hand side is in its d_b already (layout S);
-// the solutions stay in the slabs' d_x.  Everything is queued on the ONE stream the slab handles share — the mailboxes are zeroed, the
+// ALL RANKS OF A SOLVE WHOSE SLABS LIVE ON ONE DEVICE (slabs.hip), one launch: every slab's right-hand side is in its work.b already (layout S);
+// the solutions stay in the slabs' work.x.  Everything is queued on the ONE stream the slab handles share — the mailboxes are zeroed, the
 // Krylov vectors seeded and the kernel launched in stream order, so no barrier is needed between "prepare" and "solve".
 int elph_i_shard_run_ranks(elph_handle_s *const *hs, int P, int nsets, void *h_args, void *d_args, double tol, int64_t maxiter, double kmax,
                            long long fixed_iters, long long timeout_ms, CgState *state_out, double *ms_out, double *const *hist_dev,
@@ -332,16 +328,16 @@ int elph_i_shard_run_ranks(elph_handle_s *const *hs, int P, int nsets, void *h_a
         ShardState *S = static_cast<ShardState *>(h->shard);
         if (!S || !S->connected || h->stream != st) { elph_set_error("slab %d is not connected / runs on another stream", q); return ELPH_E_STATE; }
         if (!h->have_E) { elph_set_error("slab %d has no exp(-dtau V)", q); return ELPH_E_STATE; }
-        int rc = elph_i_ensure_capacity(h, 1);
+        int rc = elph_work_reserve(h, 1);
         if (rc) return rc;
         h->cur_params = Pm;
         h->plan = elph_plan_cg(h, 1, false, 1);
         const size_t bytes = (size_t)h->ndim * sizeof(double);
         HIPCHK(hipMemsetAsync(S->mail, 0, S->mail_bytes, st));
-        HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, st));
-        HIPCHK(hipMemcpyAsync(h->d_r, h->d_b, bytes, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(h->d_p, h->d_b, bytes, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemsetAsync(h->d_state, 0, 2 * sizeof(CgState), st));
+        HIPCHK(hipMemsetAsync(h->work.x, 0, bytes, st));
+        HIPCHK(hipMemcpyAsync(h->work.r, h->work.b, bytes, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(h->work.p, h->work.b, bytes, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(h->work.state, 0, 2 * sizeof(CgState), st));
         Bs[(size_t)q] = elph_make_bufs(h, 1);
         Bs[(size_t)q].params = Pm;
         if (hist_dev) Bs[(size_t)q].hist = hist_dev[q / P];      // (workgroup 0 of rank 0 writes; every rank runs the exact stop arithmetic)
@@ -363,7 +359,7 @@ int elph_i_shard_run_ranks(elph_handle_s *const *hs, int P, int nsets, void *h_a
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (rc) return rc;
-    for (int k = 0; k < nsets; ++k) HIPCHK(hipMemcpyAsync(hs[k * P]->h_state, hs[k * P]->d_state, sizeof(CgState) * 2, hipMemcpyDeviceToHost, st));
+    for (int k = 0; k < nsets; ++k) HIPCHK(hipMemcpyAsync(hs[k * P]->work.h_state, hs[k * P]->work.state, sizeof(CgState) * 2, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int q = 0; q < PT; ++q) {
         bool aborted = false;
@@ -371,7 +367,7 @@ int elph_i_shard_run_ranks(elph_handle_s *const *hs, int P, int nsets, void *h_a
         if (rc) return rc;
         if (aborted) return ELPH_I_ABORTED;      // (the caller owns the fallback and its cool-down; every OTHER failure keeps its own code)
     }
-    if (state_out) for (int k = 0; k < nsets; ++k) state_out[k] = hs[k * P]->h_state[0];
+    if (state_out) for (int k = 0; k < nsets; ++k) state_out[k] = hs[k * P]->work.h_state[0];
     return ELPH_OK;
 }
 
@@ -382,14 +378,12 @@ extern "C" int elph_shard_solve(elph_handle h, double *x_slab, const double *b_s
     if (!x_slab || !b_slab || !(tol >= 0.0) || maxiter < 1) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     int rc = shard_run(h, b_slab, tol, maxiter, kappa_max, 0, nullptr);
     if (rc) return rc;
-    const CgState &s = h->h_state[0];
+    const CgState &s = h->work.h_state[0];
     if (!s.done) { elph_set_error("sharded CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
     if (iters) *iters = s.iters;
     if (done) *done = s.done;
     if (eps) *eps = s.eps;
-    rc = elph_launch_s2r(h, h->d_stage_out, h->d_x, 1);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(x_slab, h->d_stage_out, (size_t)h->ndim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = elph_stage_out(h, x_slab, h->work.x, 1))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -655,30 +649,30 @@ static int allsum(elph_handle_s *h, ShardState *S, double *part, int n, int slot
 static int shard_kpm_apply(elph_handle_s *h, elph_handle_s *hf, ShardState *S) {
     const int N = (int)h->N, L = (int)h->L, Lo2 = (L + 1) / 2;
     CgBufs B = elph_make_bufs(h, 1);
-    int rc = elph_dft_fwd_twisted(h, h->d_nu, h->d_r, N, 1, nullptr);
+    int rc = elph_dft_fwd_twisted(h, h->work.nu, h->work.r, N, 1, nullptr);
     if (rc) return rc;
     const unsigned ep = ++S->epoch;
-    hipLaunchKernelGGL(k_shard_push_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->d_nu, S->ctl, Lo2, N, S->ctl.own_lo,
+    hipLaunchKernelGGL(k_shard_push_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->work.nu, S->ctl, Lo2, N, S->ctl.own_lo,
                        S->ctl.own_hi - S->ctl.own_lo, (int)S->own_gstart, (int)S->n_global, S->nu_off, S->ext_off, ep, S->d_counter);
     if ((rc = elph_launch_check("k_shard_push_nu"))) return rc;
     hipLaunchKernelGGL(k_shard_wait_nu, dim3(1), dim3(64), 0, h->stream, S->ctl, S->ext_off, ep, S->d_abort, shard_timeout_ticks());
     if ((rc = elph_launch_check("k_shard_wait_nu"))) return rc;
     const long long nfull = (long long)Lo2 * S->n_global;
-    hipLaunchKernelGGL(k_shard_copy_nu, dim3((unsigned)((nfull + 255) / 256)), dim3(256), 0, h->stream, hf->d_nu, S->mail + S->nu_off, nfull);
+    hipLaunchKernelGGL(k_shard_copy_nu, dim3((unsigned)((nfull + 255) / 256)), dim3(256), 0, h->stream, hf->work.nu, S->mail + S->nu_off, nfull);
     if ((rc = elph_launch_check("k_shard_copy_nu"))) return rc;
-    // Chebyshev recursion alone (parts = 2) on the full lattice, in place on hf->d_nu; hf shares this stream.  An inactive expansion
+    // Chebyshev recursion alone (parts = 2) on the full lattice, in place on hf->work.nu; hf shares this stream.  An inactive expansion
     // (KPMPreconditioners.jl:475-478) is the identity: the spectrum goes back as it came.
-    if (hf->kpm.any_active() && (rc = elph_launch_kpm_apply(hf, hf->d_zp, hf->d_r, 1, 0, 2))) return rc;
-    hipLaunchKernelGGL(k_shard_gather_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->d_nu, hf->d_nu, S->d_gsites, Lo2, N, (int)S->n_global);
+    if (hf->kpm.any_active() && (rc = elph_launch_kpm_apply(hf, hf->work.zp, hf->work.r, 1, 0, 2))) return rc;
+    hipLaunchKernelGGL(k_shard_gather_nu, dim3((unsigned)Lo2), dim3(256), 0, h->stream, h->work.nu, hf->work.nu, S->d_gsites, Lo2, N, (int)S->n_global);
     if ((rc = elph_launch_check("k_shard_gather_nu"))) return rc;
-    if ((rc = elph_dft_inv_twisted(h, h->d_zp, h->d_nu, N, 1, nullptr, nullptr, nullptr, 0))) return rc;
-    hipLaunchKernelGGL(k_shard_rz_own, dim3((unsigned)L), dim3(64), 0, h->stream, h->d_r, h->d_zp, B.rz, B.nrz, N, L, S->ctl.own_lo, S->ctl.own_hi);
+    if ((rc = elph_dft_inv_twisted(h, h->work.zp, h->work.nu, N, 1, nullptr, nullptr, nullptr, 0))) return rc;
+    hipLaunchKernelGGL(k_shard_rz_own, dim3((unsigned)L), dim3(64), 0, h->stream, h->work.r, h->work.zp, B.rz, B.nrz, N, L, S->ctl.own_lo, S->ctl.own_hi);
     if ((rc = elph_launch_check("k_shard_rz_own"))) return rc;
     return allsum(h, S, B.rz, B.nrz, 2);
 }
 
-// the preconditioned sharded solve on DEVICE-resident vectors: right-hand side in h->d_b (layout S, slab with its ghost entries), solution
-// left in h->d_x; needs S->prepared (elph_shard_prepare + the ranks' barrier)
+// the preconditioned sharded solve on DEVICE-resident vectors: right-hand side in h->work.b (layout S, slab with its ghost entries), solution
+// left in h->work.x; needs S->prepared (elph_shard_prepare + the ranks' barrier)
 static int shard_kpm_core(elph_handle_s *h, elph_handle_s *hfull, ShardState *S, double tol, int64_t maxiter, double kappa_max,
                           int64_t *iters, int *done, double *eps) {
     if (!S->prepared) { elph_set_error("elph_shard_prepare (and the caller's barrier) must precede every sharded solve"); return ELPH_E_STATE; }
@@ -687,7 +681,7 @@ static int shard_kpm_core(elph_handle_s *h, elph_handle_s *hfull, ShardState *S,
     if (!hfull->kpm.ready) { elph_set_error("elph_kpm_setup has not been called on the full-lattice handle"); return ELPH_E_STATE; }
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
     int rc;
-    if ((rc = elph_i_ensure_capacity(h, 1)) || (rc = elph_i_ensure_capacity(hfull, 1))) return rc;
+    if ((rc = elph_work_reserve(h, 1)) || (rc = elph_work_reserve(hfull, 1))) return rc;
     // inner products over the own rows: the generic kernel family (elph_set_dot_range)
     if ((rc = elph_i_set_dot_range(h, S->ctl.own_lo, S->ctl.own_hi))) return rc;
     hipStream_t saved = hfull->stream;
@@ -702,13 +696,12 @@ static int shard_kpm_core(elph_handle_s *h, elph_handle_s *hfull, ShardState *S,
     const size_t bytes = (size_t)h->ndim * sizeof(double);
     auto body = [&]() -> int {
         int r;
-        HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, h->stream));
-        HIPCHK(hipMemsetAsync(h->d_tmp, 0, bytes, h->stream));                      // A x0 = 0
+        HIPCHK(hipMemsetAsync(h->work.x, 0, bytes, h->stream));
+        HIPCHK(hipMemsetAsync(h->work.tmp, 0, bytes, h->stream));                      // A x0 = 0
         if ((r = elph_launch_cg_init_only(h, 1))) return r;                         // r0 = p0 = b, partial r.r and b.b over the own rows
         CgBufs B = elph_make_bufs(h, 1);
-        const size_t Pst = (size_t)h->cap_rhs * (size_t)h->L * (size_t)h->npl;
         if ((r = allsum(h, S, B.rr, (int)h->L, 1))) return r;
-        if ((r = allsum(h, S, h->d_part + 3 * Pst, (int)h->L, 3))) return r;         // b.b
+        if ((r = allsum(h, S, h->work.bb(), (int)h->L, 3))) return r;         // b.b
         if ((r = shard_kpm_apply(h, hfull, S))) return r;                           // z0 = P^-1 r0, rho0 = r0.z0 (IterativeSolvers.jl:182-189)
         if ((r = elph_launch_cg_init_prec_only(h, 1))) return r;                    // p0 = z0
         if ((r = elph_launch_cg_state0_only(h, 1))) return r;
@@ -721,12 +714,12 @@ static int shard_kpm_core(elph_handle_s *h, elph_handle_s *hfull, ShardState *S,
                 if ((r = allsum(h, S, B.rr, (int)h->L, 1))) return r;
                 if ((r = shard_kpm_apply(h, hfull, S))) return r;                   // z = P^-1 r, partial r.z
             }
-            HIPCHK(hipMemcpyAsync(h->h_state, h->d_state, sizeof(CgState) * 2, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(h->work.h_state, h->work.state, sizeof(CgState) * 2, hipMemcpyDeviceToHost, h->stream));
             int ab = 0;
             HIPCHK(hipMemcpyAsync(&ab, S->d_abort, sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             if (ab) { elph_set_error("sharded preconditioned CG: a rank timed out waiting for its peers"); return ELPH_E_HIP; }
-            const CgState &s = h->h_state[h->ap_count & 1];
+            const CgState &s = h->work.h_state[h->ap_count & 1];
             if (s.done) {
                 if (iters) *iters = s.iters;
                 if (done) *done = s.done;
@@ -754,13 +747,10 @@ extern "C" int elph_shard_solve_kpm(elph_handle h, elph_handle hfull, double *x_
     if (!S) { elph_set_error("elph_shard_create has not been called"); return ELPH_E_STATE; }
     if (!x_slab || !b_slab || !(tol >= 0.0) || maxiter < 1) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     int rc;
-    if ((rc = elph_i_ensure_capacity(h, 1))) return rc;
-    const size_t bytes = (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, b_slab, bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = elph_launch_r2s(h, h->d_b, h->d_stage_in, 1))) return rc;
+    if ((rc = elph_work_reserve(h, 1))) return rc;
+    if ((rc = elph_stage_in(h, h->work.b, b_slab, 1))) return rc;
     if ((rc = shard_kpm_core(h, hfull, S, tol, maxiter, kappa_max, iters, done, eps))) return rc;
-    if ((rc = elph_launch_s2r(h, h->d_stage_out, h->d_x, 1))) return rc;
-    HIPCHK(hipMemcpyAsync(x_slab, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = elph_stage_out(h, x_slab, h->work.x, 1))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
@@ -944,11 +934,11 @@ int elph_i_shard_global_ebar(elph_handle_s *h, std::vector<double> &Eg) {
     if (!S) return ELPH_E_STATE;
     if (S->n_global <= 0) { elph_set_error("the shard was created without its global geometry"); return ELPH_E_STATE; }
     const int lo = S->ctl.own_lo, hi = S->ctl.own_hi, n = hi - lo;
-    hipLaunchKernelGGL(k_shard_ebar_own, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_tmp, h->d_E, (int)h->N, (int)h->L, lo, hi);
+    hipLaunchKernelGGL(k_shard_ebar_own, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->work.tmp, h->d_E, (int)h->N, (int)h->L, lo, hi);
     int rc = elph_launch_check("k_shard_ebar_own");
     if (rc) return rc;
     std::vector<double> own((size_t)n);
-    HIPCHK(hipMemcpyAsync(own.data(), h->d_tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(own.data(), h->work.tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     Eg.assign((size_t)S->n_global, 0.0);
     for (int i = 0; i < n; ++i) Eg[(size_t)S->gsites_host[(size_t)(lo + i)]] = own[(size_t)i];
@@ -1062,8 +1052,8 @@ __global__ void __launch_bounds__(64) k_shard_resid_own(const double *__restrict
     if (threadIdx.x == 0) { part[t] = num; part[L + t] = den; }
 }
 
-// ldiv!(x, model, b[, P]) on the slab, device-resident: right-hand side in h->d_b (slot 0, layout S, ghost entries filled), solution in
-// h->d_x (slot 0; exact on own AND ghost rows: the solve keeps r, p, x of the ghost rows current through the boundary exchange).
+// ldiv!(x, model, b[, P]) on the slab, device-resident: right-hand side in h->work.b (slot 0, layout S, ghost entries filled), solution in
+// h->work.x (slot 0; exact on own AND ghost rows: the solve keeps r, p, x of the ghost rows current through the boundary exchange).
 // Models.jl:74-137,139-186 line for line: solve, true residual |MᵀM x − b| / |b| (own rows of every rank, summed), flag 1 (hit maxiter) / 2
 // (false convergence), zero-fill, and with a preconditioner the un-preconditioned retry with 10 maxiter.  iters / resid / flag come out
 // identical on every rank (the sums are).
@@ -1082,19 +1072,19 @@ int elph_i_shard_ldiv_dev(elph_handle_s *h, elph_handle_s *hfull, int use_prec, 
         }
         rc = shard_run(h, nullptr, h->tol, mi, h->kmax, 0, nullptr);
         if (rc) return rc;
-        const CgState &st = h->h_state[0];
+        const CgState &st = h->work.h_state[0];
         if (!st.done) { elph_set_error("sharded CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
         *it = st.iters;
         return ELPH_OK;
     };
     auto residual_flag = [&](int64_t it, int64_t cmp_maxiter, double *res, int *fl) -> int {
-        int rc = elph_launch_mul(h, 2, h->d_tmp, h->d_x, 1);                 // mul!(v, model, x) on the slab: exact on the own rows
+        int rc = elph_launch_mul(h, 2, h->work.tmp, h->work.x, 1);                 // mul!(v, model, x) on the slab: exact on the own rows
         if (rc) return rc;
-        hipLaunchKernelGGL(k_shard_resid_own, dim3((unsigned)h->L), dim3(64), 0, h->stream, h->d_tmp, h->d_b, h->d_part, (int)h->N, (int)h->L,
+        hipLaunchKernelGGL(k_shard_resid_own, dim3((unsigned)h->L), dim3(64), 0, h->stream, h->work.tmp, h->work.b, h->work.pap(), (int)h->N, (int)h->L,
                            S->ctl.own_lo, S->ctl.own_hi);
         if ((rc = elph_launch_check("k_shard_resid_own"))) return rc;
         std::vector<double> p(2 * (size_t)h->L);
-        HIPCHK(hipMemcpyAsync(p.data(), h->d_part, p.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(p.data(), h->work.pap(), p.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         double nd[2] = {0.0, 0.0};
         for (int64_t t = 0; t < h->L; ++t) { nd[0] += p[(size_t)t]; nd[1] += p[(size_t)(h->L + t)]; }
@@ -1102,7 +1092,7 @@ int elph_i_shard_ldiv_dev(elph_handle_s *h, elph_handle_s *hfull, int use_prec, 
         *res = sqrt(nd[0]) / sqrt(nd[1]);
         if (*res > sqrt(h->tol)) {                                           // Models.jl:100,157 (NaN compares false, as in the reference)
             *fl = (it == cmp_maxiter) ? 1 : 2;
-            HIPCHK(hipMemsetAsync(h->d_x, 0, bytes, h->stream));             // fill!(x, 0)
+            HIPCHK(hipMemsetAsync(h->work.x, 0, bytes, h->stream));             // fill!(x, 0)
         } else {
             *fl = 0;
         }
@@ -1125,63 +1115,57 @@ extern "C" int elph_shard_ldiv(elph_handle h, elph_handle hfull, double *x_slab,
     if (!x_slab || !b_slab || !iters || !residual_error || !flag || maxiter < 0) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
     int rc;
-    if ((rc = elph_i_ensure_capacity(h, 1))) return rc;
-    const size_t bytes = (size_t)h->ndim * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, b_slab, bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = elph_launch_r2s(h, h->d_b, h->d_stage_in, 1))) return rc;
+    if ((rc = elph_work_reserve(h, 1))) return rc;
+    if ((rc = elph_stage_in(h, h->work.b, b_slab, 1))) return rc;
     if ((rc = elph_i_shard_ldiv_dev(h, hfull, use_precond, maxiter, iters, residual_error, flag))) return rc;
-    if ((rc = elph_launch_s2r(h, h->d_stage_out, h->d_x, 1))) return rc;
-    HIPCHK(hipMemcpyAsync(x_slab, h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = elph_stage_out(h, x_slab, h->work.x, 1))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
 }
 
-// The two pseudofermion solves of calc_O⁻¹Λϕ! (HMC.jl:851-886) on the slab: right-hand sides in h->d_b[0], h->d_b[1], solutions into
-// h->d_x[0], h->d_x[1] (capacity >= 2), at tol^power; iters = cld(total, 2) and the flag as the reference returns them (:907-909); a
+// The two pseudofermion solves of calc_O⁻¹Λϕ! (HMC.jl:851-886) on the slab: right-hand sides in h->work.b[0], h->work.b[1], solutions into
+// h->work.x[0], h->work.x[1] (capacity >= 2), at tol^power; iters = cld(total, 2) and the flag as the reference returns them (:907-909); a
 // failed first solve suppresses the second (:880).  One sharded solve at a time (the SHARD kernel carries one right-hand side).
 int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec, double tol_power, int64_t *iters, int *flag) {
     const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double);
-    const double tol0 = h->tol;
-    h->tol = pow(tol0, tol_power);
-    int64_t it1 = 0, it2 = 0;
+    TolPower scope(h, tol_power);
+    int64_t it2[2] = {0, 0};
     double res = 0.0;
-    int fl = 0;
+    int fl2[2] = {0, 0};
+    auto copied = [](hipError_t e) -> int {
+        if (e == hipSuccess) return ELPH_OK;
+        elph_set_error("sharded pair: %s", hipGetErrorString(e));
+        return ELPH_E_HIP;
+    };
     // (+): slot 0 as it lies; keep b(−) aside, it moves into slot 0 for its own solve
-    int rc = elph_i_shard_ldiv_dev(h, hfull, use_prec, 0, &it1, &res, &fl);
-    int64_t tot = it1;
-    if (rc == ELPH_OK && fl == 0) {
-        // X₊ waits in slot 1 of d_x for the length of the second solve (a sharded solve carries ONE right-hand side: slot 0 of every per-right-hand-side
+    RC(elph_i_shard_ldiv_dev(h, hfull, use_prec, 0, &it2[0], &res, &fl2[0]));
+    if (fl2[0] == 0) {
+        // X₊ waits in slot 1 of work.x for the length of the second solve (a sharded solve carries ONE right-hand side: slot 0 of every per-right-hand-side
         // array; the handle's capacity is two) — on the device, no host round trip; b₊ aside in the staging buffer, b₋ into slot 0
-        hipError_t e = hipMemcpyAsync(h->d_x + nd, h->d_x, bytes, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h->d_stage_out, h->d_b, bytes, hipMemcpyDeviceToDevice, h->stream);   // b₊ aside
-        if (e == hipSuccess) e = hipMemcpyAsync(h->d_b, h->d_b + nd, bytes, hipMemcpyDeviceToDevice, h->stream);
-        if (e != hipSuccess) { h->tol = tol0; elph_set_error("sharded pair: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-        rc = elph_i_shard_ldiv_dev(h, hfull, use_prec, 0, &it2, &res, &fl);
-        if (rc == ELPH_OK) {
-            tot += it2;
-            // slot 0 holds X₋, slot 1 X₊: swap through slot 1 of d_z (free: the solves are over)
-            e = hipMemcpyAsync(h->d_z + nd, h->d_x, bytes, hipMemcpyDeviceToDevice, h->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(h->d_x, h->d_x + nd, bytes, hipMemcpyDeviceToDevice, h->stream);           // X₊ -> slot 0
-            if (e == hipSuccess) e = hipMemcpyAsync(h->d_x + nd, h->d_z + nd, bytes, hipMemcpyDeviceToDevice, h->stream);      // X₋ -> slot 1
-            if (e == hipSuccess) e = hipMemcpyAsync(h->d_b + nd, h->d_b, bytes, hipMemcpyDeviceToDevice, h->stream);   // b₋ back to slot 1
-            if (e == hipSuccess) e = hipMemcpyAsync(h->d_b, h->d_stage_out, bytes, hipMemcpyDeviceToDevice, h->stream); // b₊ back to slot 0
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) { h->tol = tol0; elph_set_error("sharded pair: %s", hipGetErrorString(e)); return ELPH_E_HIP; }
-        }
-    } else if (rc == ELPH_OK) {
-        rc = elph_launch_zero(h, h->d_x + nd, (int64_t)nd);
+        hipError_t e = hipMemcpyAsync(h->work.x + nd, h->work.x, bytes, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->work.stage_out, h->work.b, bytes, hipMemcpyDeviceToDevice, h->stream);   // b₊ aside
+        if (e == hipSuccess) e = hipMemcpyAsync(h->work.b, h->work.b + nd, bytes, hipMemcpyDeviceToDevice, h->stream);
+        RC(copied(e));
+        RC(elph_i_shard_ldiv_dev(h, hfull, use_prec, 0, &it2[1], &res, &fl2[1]));
+        // slot 0 holds X₋, slot 1 X₊: swap through slot 1 of work.z (free: the solves are over)
+        e = hipMemcpyAsync(h->work.z + nd, h->work.x, bytes, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->work.x, h->work.x + nd, bytes, hipMemcpyDeviceToDevice, h->stream);           // X₊ -> slot 0
+        if (e == hipSuccess) e = hipMemcpyAsync(h->work.x + nd, h->work.z + nd, bytes, hipMemcpyDeviceToDevice, h->stream);      // X₋ -> slot 1
+        if (e == hipSuccess) e = hipMemcpyAsync(h->work.b + nd, h->work.b, bytes, hipMemcpyDeviceToDevice, h->stream);   // b₋ back to slot 1
+        if (e == hipSuccess) e = hipMemcpyAsync(h->work.b, h->work.stage_out, bytes, hipMemcpyDeviceToDevice, h->stream); // b₊ back to slot 0
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        RC(copied(e));
+    } else {
+        RC(elph_launch_zero(h, h->work.x + nd, (int64_t)nd));
     }
-    h->tol = tol0;
-    if (rc) return rc;
-    if (fl == 0) tot = (tot + 1) / 2;                                         // cld(iters, 2)
-    *iters = tot;
-    *flag = fl;
+    elph_fold_pair(1, it2, fl2, iters, flag);
     return ELPH_OK;
 }
 
-// One fermion-force evaluation of the Holstein model on a sharded lattice: elph_fermion_force_holstein's steps (update_model!,
-// calc_O⁻¹Λϕ!, calc_dSfdx!) on the slab.  All vectors are slab vectors (own + ghost rows, ghost entries filled from the global arrays);
-// the force is exact on the OWN rows (the same closure argument as for z = Mᵀ(M p): CB, then CBᵀ) and only those are accumulated into.
+// The fermion force of either model on a sharded lattice: the whole-lattice entry points' steps (elph_api.hip: elph_i_force_holstein,
+// elph_i_force_ssh) on the slab, the two solves one after the other through the sharded kernel.  All vectors are slab vectors (own + ghost
+// rows, ghost entries filled from the global arrays).  Holstein: the force is exact on the OWN rows (the same closure argument as for
+// z = Mᵀ(M p): CB, then CBᵀ) and only those are accumulated into.
 extern "C" int elph_shard_fermion_force_holstein(elph_handle h, elph_handle hfull, const double *x, const double *lambda, const double *lambda2,
                                                  const double *mu, double dtau, const double *phi_plus, const double *phi_minus, int use_precond,
                                                  double tol_power, double *dSfdx, double *Xp_out, double *Xm_out, int64_t *iters, int *flag) {
@@ -1191,41 +1175,13 @@ extern "C" int elph_shard_fermion_force_holstein(elph_handle h, elph_handle hful
     if (!S) return ELPH_E_STATE;
     if (h->kind != ELPH_MODEL_HOLSTEIN) { elph_set_error("not a Holstein handle"); return ELPH_E_ARG; }
     if (!x || !lambda || !lambda2 || !mu || !phi_plus || !phi_minus || !dSfdx || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    int rc;
-    if ((rc = elph_i_ensure_capacity(h, 2))) return rc;
-    const size_t nd = (size_t)h->ndim, N = (size_t)h->N, bytes = nd * sizeof(double);
-    HIPCHK(hipMemcpyAsync(h->d_lam, lambda, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_lam + N, lambda2, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_lam + 2 * N, mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, x, bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = elph_launch_expV(h, h->d_stage_in, dtau))) return rc;
-    if ((rc = elph_launch_r2s(h, h->d_xfield, h->d_stage_in, 1))) return rc;
-    h->have_E = true;
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, phi_plus, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, phi_minus, bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = elph_launch_r2s(h, h->d_phi, h->d_stage_in, 2))) return rc;
-    if ((rc = elph_launch_lambda_rhs(h, h->d_b, h->d_phi, h->d_xfield, dtau))) return rc;
-    if ((rc = elph_i_shard_solve_pair(h, hfull, use_precond, tol_power, iters, flag))) return rc;
-    if ((rc = elph_launch_force_holstein(h, h->d_tmp, h->d_x, h->d_phi, h->d_xfield, dtau))) return rc;
-    if ((rc = elph_launch_s2r(h, h->d_stage_out, h->d_tmp, 1))) return rc;
-    std::vector<double> F(nd);
-    HIPCHK(hipMemcpyAsync(F.data(), h->d_stage_out, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (Xp_out || Xm_out) {
-        if ((rc = elph_launch_s2r(h, h->d_stage_in, h->d_x, 2))) return rc;
-        if (Xp_out) HIPCHK(hipMemcpyAsync(Xp_out, h->d_stage_in, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (Xm_out) HIPCHK(hipMemcpyAsync(Xm_out, h->d_stage_in + nd, bytes, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t L = (size_t)h->L;
-    for (size_t s2 = (size_t)S->ctl.own_lo; s2 < (size_t)S->ctl.own_hi; ++s2)
-        for (size_t t = 0; t < L; ++t) dSfdx[s2 * L + t] += F[s2 * L + t];      // own rows only ("@. dSfdx += ...", HMC.jl:803-811)
-    return ELPH_OK;
+    return elph_i_force_holstein(h, x, lambda, lambda2, mu, dtau, phi_plus, phi_minus, dSfdx, Xp_out, Xm_out, iters, flag, S->ctl.own_lo,
+                                 S->ctl.own_hi, [=](int64_t *it, int *fl) { return elph_i_shard_solve_pair(h, hfull, use_precond, tol_power, it, fl); });
 }
 
-// The same for the bond-phonon model (elph_fermion_force_ssh): the two solves on the given right-hand sides and the bond brackets
-// q_out[n Ltau + tau] of the slab's bonds (local checkerboard order).  A bracket is exact on the rank that owns its bond (both ends in
-// the own rows, or one end in the first ghost row across the slab's edge: the crossing colour is the last factor of the sweep); the
-// caller keeps the brackets of its own bonds and scatters them onto the phonon fields (sharded.py: ShardedSolver.force_ssh).
+// The bond brackets q_out[n Ltau + tau] are those of the slab's bonds (local checkerboard order).  A bracket is exact on the rank that owns
+// its bond (both ends in the own rows, or one end in the first ghost row across the slab's edge: the crossing colour is the last factor of
+// the sweep); the caller keeps the brackets of its own bonds and scatters them onto the phonon fields (sharded.py: ShardedSolver.force_ssh).
 extern "C" int elph_shard_fermion_force_ssh(elph_handle h, elph_handle hfull, const double *rhs_plus, const double *rhs_minus, int use_precond,
                                             double tol_power, double *q_out, double *Xp_out, double *Xm_out, int64_t *iters, int *flag) {
     if (!h) { elph_set_error("null handle"); return ELPH_E_ARG; }
@@ -1235,23 +1191,6 @@ extern "C" int elph_shard_fermion_force_ssh(elph_handle h, elph_handle hfull, co
     if (h->kind != ELPH_MODEL_SSH) { elph_set_error("not an SSH handle"); return ELPH_E_ARG; }
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
     if (!rhs_plus || !rhs_minus || !q_out || !iters || !flag) { elph_set_error("null argument"); return ELPH_E_ARG; }
-    int rc;
-    if ((rc = elph_i_ssh_bracket_capacity(h, 2, 1))) return rc;
-    const size_t nd = (size_t)h->ndim, bytes = nd * sizeof(double), L = (size_t)h->L, nb = (size_t)h->nb, nq = L * nb;
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, rhs_plus, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_stage_in + nd, rhs_minus, bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = elph_launch_r2s(h, h->d_b, h->d_stage_in, 2))) return rc;
-    if ((rc = elph_i_shard_solve_pair(h, hfull, use_precond, tol_power, iters, flag))) return rc;
-    if ((rc = elph_launch_force_ssh(h, h->d_p, h->d_x))) return rc;
-    std::vector<double> qt(nq);
-    if (nq) HIPCHK(hipMemcpyAsync(qt.data(), h->d_p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (Xp_out || Xm_out) {
-        if ((rc = elph_launch_s2r(h, h->d_stage_in, h->d_x, 2))) return rc;
-        if (Xp_out) HIPCHK(hipMemcpyAsync(Xp_out, h->d_stage_in, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (Xm_out) HIPCHK(hipMemcpyAsync(Xm_out, h->d_stage_in + nd, bytes, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (size_t t = 0; t < L; ++t)
-        for (size_t n = 0; n < nb; ++n) q_out[n * L + t] = qt[t * nb + n];
-    return ELPH_OK;
+    return elph_i_force_ssh(h, rhs_plus, rhs_minus, q_out, Xp_out, Xm_out, iters, flag,
+                            [=](int64_t *it, int *fl) { return elph_i_shard_solve_pair(h, hfull, use_precond, tol_power, it, fl); });
 }

@@ -163,13 +163,13 @@ int build(elph_handle_s *h, int P, int lo, int hi, int G, SlabSet **out) {
     return ELPH_OK;
 }
 
-SlabPtrs ptrs_of(const SlabSet *S, int set, int which /* 0 d_b, 1 d_E, 2 d_x */) {
+SlabPtrs ptrs_of(const SlabSet *S, int set, int which /* 0 work.b, 1 d_E, 2 work.x */) {
     SlabPtrs T;
     for (int q = 0; q < ELPH_SHARD_MAXRANKS; ++q) {
         T.p[q] = nullptr; T.g[q] = nullptr;
         if (q < S->P) {
             elph_handle_s *s = S->hs[(size_t)set * (size_t)S->P + (size_t)q];
-            T.p[q] = which == 0 ? s->d_b : (which == 1 ? s->d_E : s->d_x);
+            T.p[q] = which == 0 ? s->work.b : (which == 1 ? s->d_E : s->work.x);
             T.g[q] = S->d_g[(size_t)q];
         }
     }
@@ -243,9 +243,9 @@ bool elph_i_slabs_usable(elph_handle_s *h, int nrhs) {
     return false;
 }
 
-// x = (M^T M)^-1 b for the nrhs right-hand sides in h->d_b (layout S), x0 = 0, into h->d_x; CG states into h->h_state / d_state.
+// x = (M^T M)^-1 b for the nrhs right-hand sides in h->work.b (layout S), x0 = 0, into h->work.x; CG states into h->work.h_state / work.state.
 // *ran = false (and ELPH_OK): the slab form gave up (a time-out: the handle cools down as after any resident kernel's) or does not apply
-// after all — h->d_x is zero again and the caller runs the streaming iteration.
+// after all — h->work.x is zero again and the caller runs the streaming iteration.
 int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long fixed_iters, int64_t *iters, bool *ran, double *ms_out) {
     *ran = false;
     SlabSet *S = static_cast<SlabSet *>(h->slabs);
@@ -262,7 +262,7 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
         const int rc = add_set(h, S);
         if (rc) return rc;
     }
-    for (elph_handle_s *s : S->hs) { const int rc = elph_i_ensure_capacity(s, 1); if (rc) return rc; }
+    for (elph_handle_s *s : S->hs) { const int rc = elph_work_reserve(s, 1); if (rc) return rc; }
     const dim3 gg((unsigned)((Nloc + 255) / 256), (unsigned)L, (unsigned)Pq), gs((unsigned)((S->own_n + 255) / 256), (unsigned)L, (unsigned)Pq);
     for (int k = 0; k < (pairs ? 2 : 1); ++k) {
         hipLaunchKernelGGL(k_slab_gather, gg, dim3(256), 0, h->stream, ptrs_of(S, k, 1), (const double *)h->d_E, N, Nloc);
@@ -274,18 +274,18 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
     for (int r = 0; r < nrhs;) {
         const int ns = (pairs && r + 1 < nrhs) ? 2 : 1;        // right-hand sides of this launch
         for (int k = 0; k < ns; ++k)
-            hipLaunchKernelGGL(k_slab_gather, gg, dim3(256), 0, h->stream, ptrs_of(S, k, 0), (const double *)(h->d_b + (size_t)(r + k) * h->ndim), N, Nloc);
+            hipLaunchKernelGGL(k_slab_gather, gg, dim3(256), 0, h->stream, ptrs_of(S, k, 0), (const double *)(h->work.b + (size_t)(r + k) * h->ndim), N, Nloc);
         HIPCHK(hipGetLastError());
         CgState st[2];
         double ms = 0.0;
         double *hist[2] = {nullptr, nullptr};
-        if (P.record_hist) for (int k = 0; k < ns; ++k) hist[k] = h->d_hist + (size_t)(r + k) * (size_t)P.hist_stride;
+        if (P.record_hist) for (int k = 0; k < ns; ++k) hist[k] = h->work.hist + (size_t)(r + k) * (size_t)P.hist_stride;
         int rc = elph_i_shard_run_ranks(S->hs.data(), Pq, ns, S->h_args, S->d_args, P.tol, P.maxiter, P.kmax, fixed_iters, timeout_ms, st,
                                         ms_out ? &ms : nullptr, P.record_hist ? hist : nullptr, P.hist_stride);
         if (test_give_up && rc == ELPH_OK) rc = ELPH_I_ABORTED;
         if (rc == ELPH_E_UNSUPPORTED) {                  // the slabs do not take the sharded kernel's lane-program form: never again
             elph_i_slabs_free(h);
-            HIPCHK(hipMemsetAsync(h->d_x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
+            HIPCHK(hipMemsetAsync(h->work.x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
             return ELPH_OK;
         }
         if (rc == ELPH_I_ABORTED) {
@@ -293,23 +293,23 @@ int elph_i_slabs_solve(elph_handle_s *h, int nrhs, const CgParams &P, long long 
             // ELPH_E_HIP and is returned below): cool down like the other resident kernels, streaming takes over
             h->res.launched(S->hs[0]->res.T, S->hs[0]->res.W, S->hs[0]->res.G);      // (the slabs' shape, for the message)
             elph_wg_timed_out(h);
-            HIPCHK(hipMemsetAsync(h->d_x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
+            HIPCHK(hipMemsetAsync(h->work.x, 0, (size_t)nrhs * (size_t)h->ndim * sizeof(double), h->stream));
             return ELPH_OK;
         }
         if (rc) return rc;
         ms_sum += ms;
         for (int k = 0; k < ns; ++k) {
             if (!st[k].done && fixed_iters <= 0) { elph_set_error("slab CG ended without a terminal state (internal error)"); return ELPH_E_STATE; }
-            hipLaunchKernelGGL(k_slab_scatter, gs, dim3(256), 0, h->stream, ptrs_of(S, k, 2), h->d_x + (size_t)(r + k) * h->ndim, N, Nloc, S->own_lo, S->own_n);
+            hipLaunchKernelGGL(k_slab_scatter, gs, dim3(256), 0, h->stream, ptrs_of(S, k, 2), h->work.x + (size_t)(r + k) * h->ndim, N, Nloc, S->own_lo, S->own_n);
             st[k].seq = st[k].iters + 1;
-            h->h_state[2 * (r + k)] = st[k];
-            h->h_state[2 * (r + k) + 1] = st[k];
+            h->work.h_state[2 * (r + k)] = st[k];
+            h->work.h_state[2 * (r + k) + 1] = st[k];
             if (iters) iters[r + k] = st[k].iters;
         }
         HIPCHK(hipGetLastError());
         r += ns;
     }
-    HIPCHK(hipMemcpyAsync(h->d_state, h->h_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->work.state, h->work.h_state, sizeof(CgState) * 2 * (size_t)nrhs, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (ms_out) *ms_out = ms_sum;
     *ran = true;
