@@ -45,6 +45,7 @@ SIGNATURES = {
     "elph_mulMT_dev": (c_int, [Handle, C.c_void_p, C.c_void_p]),
     "elph_mulMTM_dev": (c_int, [Handle, C.c_void_p, C.c_void_p]),
     "elph_solver_set": (c_int, [Handle, c_dbl, c_i64, c_dbl]),
+    "elph_solver_set_kind": (c_int, [Handle, c_int, c_int]),
     "elph_cg_solve": (c_int, [Handle, P_dbl, P_dbl, c_dbl, c_i64, c_dbl, c_int, P_i64, P_dbl]),
     "elph_ldiv": (c_int, [Handle, P_dbl, P_dbl, c_int, c_i64, P_i64, P_dbl, P_int]),
     "elph_ldiv_batched": (c_int, [Handle, c_int, P_dbl, P_dbl, c_int, c_i64, P_i64, P_dbl, P_int]),
@@ -174,6 +175,7 @@ BENCH_SIGNATURES = {
     "elph_bench_prepare": (c_int, [Handle, c_int, c_int, P_dbl]),
     "elph_bench_run": (c_int, [Handle, c_int, c_int, c_int, c_int, P_dbl]),
     "elph_bench_get_x": (c_int, [Handle, c_int, P_dbl]),
+    "elph_bench_msolve_pair": (c_int, [Handle, c_int, c_int, c_int, c_int, P_dbl, P_i64]),
     "elph_bench_info": (c_int, [Handle, c_int, P_int]),
     "elph_bench_wg_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_px_info": (c_int, [Handle, P_int]),

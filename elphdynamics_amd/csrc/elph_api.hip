@@ -354,8 +354,10 @@ int elph_stage_out(elph_handle_s *h, double *hostR, const double *srcS, int nvec
     return ELPH_OK;
 }
 
-int elph_retry_in_slot0(elph_handle_s *h, int r, const std::function<int()> &solve_and_flag) {
-    SolveWork &W = h->work;
+int elph_retry_in_slot0(elph_handle_s *h, int r, const std::function<int()> &solve_and_flag, double *x, double *b) {
+    SolveWork W = h->work;
+    if (x) W.x = x;
+    if (b) W.b = b;
     const size_t bytes = W.ndim * sizeof(double);
     if (r != 0) {
         HIPCHK(hipMemcpyAsync(W.stage_out, W.x, bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -384,6 +386,18 @@ void elph_fold_pair(int nch, const int64_t *it2, const int *fl2, int64_t *iters,
         iters[c] = tot;
         flag[c] = fl;
     }
+}
+
+void elph_fold_pair_stages(int nch, const int64_t *it4, const int *fl4, int64_t *iters, int *flag, int *zero_minus) {
+    const size_t n2 = 2 * (size_t)nch;                                   // it4, fl4: [stage][sign][chain]
+    std::vector<int64_t> it2(n2);
+    std::vector<int> fl2(n2);
+    for (size_t r = 0; r < n2; ++r) {
+        it2[r] = it4[r] + it4[n2 + r];                                   // iters += iters′ of the second stage (:863, :871)
+        fl2[r] = std::max(fl4[r], fl4[n2 + r]);                          // flag = max(flag, flag′) (:864, :872)
+    }
+    elph_fold_pair(nch, it2.data(), fl2.data(), iters, flag);
+    if (zero_minus) for (int c = 0; c < nch; ++c) zero_minus[c] = fl2[c] != 0;
 }
 
 // the bond-table arguments of elph_create (and of the recognition probe)
@@ -1293,6 +1307,17 @@ int elph_i_force_holstein(elph_handle_s *h, const double *x, const double *lambd
 static ElphPairSolve batch_pair(elph_handle_s *h, int use_precond, double tol_power) {
     return [=](int64_t *iters, int *flag) -> int {
         const size_t nd = (size_t)h->ndim;
+        if (h->solver_kind != ELPH_SOLVER_CG) {      // the mul_by_M branch (HMC.jl:859-873, :888-902): Mᵀ y = Λϕ±, then M x = y, y in work.z
+            int64_t it4[4] = {0, 0, 0, 0};
+            int fl4[4] = {0, 0, 0, 0}, zero_minus = 0;
+            {
+                TolPower scope(h, tol_power);
+                RC(elph_i_msolve_pair(h, 2, use_precond ? 1 : 0, h->work.x, h->work.z, h->work.b, it4, fl4));
+            }
+            elph_fold_pair_stages(1, it4, fl4, iters, flag, &zero_minus);
+            if (zero_minus) RC(elph_launch_zero(h, h->work.x + nd, (int64_t)nd));
+            return ELPH_OK;
+        }
         HIPCHK(hipMemsetAsync(h->work.x, 0, 2 * nd * sizeof(double), h->stream));
         h->x_zero = true;
         int64_t it2[2] = {0, 0};

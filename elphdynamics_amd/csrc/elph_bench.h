@@ -104,6 +104,13 @@ int elph_bench_slabs_info(elph_handle h, int nrhs, int *usable, int *slabs, int 
 int elph_bench_greens_noise(elph_handle h, int mapping, int64_t nvec, uint64_t seed, int reps, double *ms_total, int64_t out_first,
                             int64_t out_count, double *out);
 
+/* The two-stage pair solve of a BiCGStab / GMRES handle alone (msolve.hip: elph_i_msolve_pair) on the nrhs right-hand sides the last force or
+ * action evaluation left on the device (work.b: Λϕ± of every chain; nrhs at most what that evaluation solved), with the handle's tolerance:
+ * zero_start = 1 as the callers run it (the first mat-vec of every stage skipped on the promise of a zero guess), 0 with that mat-vec on the
+ * zeroed guess — the same bits.  *ms_total = the host's time over `reps` pair solves, synchronised before and after; iters: [2 stages][nrhs]
+ * of the last one (may be NULL). */
+int elph_bench_msolve_pair(elph_handle h, int nrhs, int use_precond, int zero_start, int reps, double *ms_total, int64_t *iters);
+
 /* the sharded solve (shard.hip): exactly `iters` iterations (no stop test); *ms = HIP-event time of this rank's launch.  b_slab may
  * be NULL (keeps the right-hand side of the previous call).  Needs elph_shard_prepare + barrier like a solve. */
 int elph_shard_iterate(elph_handle h, const double *b_slab, int64_t iters, double *ms);

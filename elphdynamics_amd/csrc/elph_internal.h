@@ -474,6 +474,8 @@ struct elph_handle_s {
     // solver defaults (model.solver)
     double tol = 1e-4, kmax = 1e12;
     int64_t maxiter = 0;
+    int solver_kind = ELPH_SOLVER_CG;      // what the callers of the solve run (elph_solver_set_kind); restart: GMRES only
+    int solver_restart = 20;
 
     SolveWork work;                        // the workspace of every solve (elph_work_reserve)
     CgParams cur_params;                   // parameters of the solve in progress (copied into every launch)
@@ -501,7 +503,8 @@ int elph_stage_out(elph_handle_s *h, double *hostR, const double *srcS, int nvec
 // Right-hand side r of a batch once more, alone, in slot 0 (the retry of a flagged right-hand side, Models.jl:129-133): slot 0 of x and b
 // is parked in the staging buffers, r moves in, the kernels see r's chain only (solo_chain, when the handle holds several), solve_and_flag
 // runs, the result moves back to r and slot 0 is restored.
-int elph_retry_in_slot0(elph_handle_s *h, int r, const std::function<int()> &solve_and_flag);
+// x, b: the batch's vectors when they are not work.x / work.b (msolve.hip's callers; solve_and_flag then works on slot 0 of these).
+int elph_retry_in_slot0(elph_handle_s *h, int r, const std::function<int()> &solve_and_flag, double *x = nullptr, double *b = nullptr);
 // the solver tolerance at tol^power for the length of a scope: the two solves of calc_O⁻¹Λϕ! (HMC.jl:827-828, restored as at :912)
 struct TolPower {
     elph_handle_s *h;
@@ -610,6 +613,19 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
 // one side of the expansion (kernels.hip: k_kpm_cheb_side): transposed 0 Left ~ M⁻¹, 1 Right ~ M⁻ᵀ; done: [nrhs] skip flags or nullptr
 int elph_launch_kpm_apply_side(elph_handle_s *h, double *zS, const double *rS, int nrhs, int transposed, const int *done);
 void elph_msolve_free(elph_handle_s *h);                                    // msolve.hip
+// msolve.hip internals used by hmc.hip, greens.hip and elph_api.hip: the handle's solver kind (BiCGStab or GMRES, never CG) on
+// device-resident layout-S vectors.  Both consume the h->x_zero promise of their caller (x was zeroed by the library for THIS solve).
+// ldiv!(x, model, b[, P]; maxiter) for A = M (transposed 0) or Mᵀ (1), use_prec: the Left / the Right side of the expansion
+int elph_i_mldiv_core(elph_handle_s *h, int transposed, int nrhs, int use_prec, int64_t maxiter, double *x, const double *b, int64_t *iters,
+                      double *resid, int *flag);
+int elph_i_msolve_ready(elph_handle_s *h);      // ELPH_E_STATE, naming the solver, where the handle's BiCGStab / GMRES cannot run (sharded, slab, restricted range)
+// O⁻¹ b as the reference's mul_by_M branch of calc_O⁻¹Λϕ! runs it (HMC.jl:851-903): Mᵀ y = b from y = 0 with the Right side, then M x = y
+// from x = 0 with the Left side, y read where the first stage left it; b is not written.  iters2, flag2: [2 stages][nrhs]
+int elph_i_msolve_pair(elph_handle_s *h, int nrhs, int use_prec, double *x, double *y, const double *b, int64_t *iters2, int *flag2);
+// what calc_O⁻¹Λϕ! returns for each of nch chains from the stages of such a pair solve of the 2 nch right-hand sides, it4 / fl4:
+// [2 stages][2 signs][nch]: iters± = it₁± + it₂±, flag± = max(flag₁±, flag₂±) (:863-876), then as elph_fold_pair; zero_minus[c] (may be
+// null): ϕ₋ of chain c was suppressed and its output has to be zero
+void elph_fold_pair_stages(int nch, const int64_t *it4, const int *fl4, int64_t *iters, int *flag, int *zero_minus);
 int elph_launch_ebar(elph_handle_s *h, int nch = 1);
 int elph_launch_fft_accel(elph_handle_s *h, double *outS, const double *inS, const double *diagS, double power, int64_t ncol,
                           int nvec = 1);

@@ -227,9 +227,27 @@ static int check_chain_count(const elph_handle_s *h, int nv) {
 }
 
 // update! after its randn!: the noise vectors are in g->R (layout S).  Mᵀr, zero start, the batched solve, M⁻¹R into g->X; one synchronisation.
+// A BiCGStab / GMRES handle solves M x = r₁ itself (the mul_by_M branch, :216-221): no Mᵀr, R is the right-hand side where it lies and the
+// solution is written where it stays.
 static int solve_from_R(elph_handle_s *h, GreensState *g, int use_precond, int64_t *iters, double *residual_error, int *flag) {
     const int nv = g->nv;
     const size_t nd = (size_t)h->ndim;
+    if (h->solver_kind != ELPH_SOLVER_CG) {
+        std::vector<int64_t> it((size_t)nv);
+        std::vector<double> res((size_t)nv);
+        std::vector<int> fl((size_t)nv);
+        RC(elph_launch_zero(h, g->X, (int64_t)nv * h->ndim));              // fill!(M⁻¹r₁, 0)  :213
+        h->x_zero = true;
+        RC(elph_i_mldiv_core(h, 0, nv, use_precond ? 1 : 0, 0, g->X, g->R, it.data(), res.data(), fl.data()));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int i = 0; i < nv; ++i) {
+            if (iters) iters[i] = it[i];
+            if (residual_error) residual_error[i] = res[i];
+            if (flag) flag[i] = fl[i];
+        }
+        g->have_vectors = true;
+        return ELPH_OK;
+    }
     RC(elph_launch_mul(h, 1, h->work.b, g->R, nv));                       // Mᵀr₁ (model.v″, :223-224)
     RC(elph_launch_zero(h, h->work.x, (int64_t)nv * h->ndim));            // fill!(M⁻¹r₁, 0)  :213
     h->x_zero = false;                                                 // (this path does not use the x = 0 hint, and takes nobody else's)

@@ -293,12 +293,14 @@ int update_model(elph_handle_s *h, HmcState *st) {
 }
 
 // calc_O⁻¹Λϕ!(hmc, model, P, power)  (HMC.jl:820-915) for every chain: setup!(P) per chain, Λϕ±, all 2·nch solves as one
-// batch (right-hand side v·nch + c belongs to chain c), per chain iters = cld(total, 2) and flag
+// batch (right-hand side v·nch + c belongs to chain c), per chain iters = cld(total, 2) and flag.  CG on MᵀM, or — the handle's solver
+// kind — the two-stage pair solve of BiCGStab / GMRES on Mᵀ and M (msolve.hip)
 int calc_OinvLphi(elph_handle_s *h, HmcState *st, int use_precond, double power, const double *kpm_randn, int64_t *kpm_calls,
                   int64_t *iters, int *flag) {
     const size_t nd = (size_t)h->ndim;
     const int nch = st->nch;
     int use = 0;
+    if (h->solver_kind != ELPH_SOLVER_CG) RC(elph_i_msolve_ready(h));      // (before the sharded routes below, which are CG's)
     if (use_precond && sharded(h)) {
         // a sharded lattice: the expansion lives on the full-lattice handle (elph_shard_set_full_lattice), set up identically on every rank from
         // the SAME start vectors (kpm_randn holds vectors of the whole lattice) and the Ē summed over the ranks' own rows
@@ -341,6 +343,19 @@ int calc_OinvLphi(elph_handle_s *h, HmcState *st, int use_precond, double power,
     if (sharded(h)) {      // one lattice over several ranks: the two solves one after the other through the sharded kernel (shard.hip)
         h->x_zero = false;
         return elph_i_shard_solve_pair(h, nullptr, 0, power, iters, flag);
+    }
+    if (h->solver_kind != ELPH_SOLVER_CG) {      // the mul_by_M branch (:859-873, :888-902): Mᵀ y = Λϕ±, then M x = y, y in work.z
+        h->x_zero = false;
+        std::vector<int64_t> it4((size_t)4 * nch, 0);
+        std::vector<int> fl4((size_t)4 * nch, 0), zm((size_t)nch, 0);
+        {
+            TolPower scope(h, power);
+            RC(elph_i_msolve_pair(h, 2 * nch, use, h->work.x, h->work.z, h->work.b, it4.data(), fl4.data()));
+        }
+        elph_fold_pair_stages(nch, it4.data(), fl4.data(), iters, flag, zm.data());
+        for (int c = 0; c < nch; ++c)
+            if (zm[c]) RC(elph_launch_zero(h, h->work.x + (size_t)(nch + c) * nd, (int64_t)nd));
+        return ELPH_OK;
     }
     std::vector<int64_t> it2((size_t)2 * nch, 0);
     std::vector<double> res2((size_t)2 * nch);
@@ -881,7 +896,7 @@ extern "C" int elph_hmc_update(elph_handle h, double dt, int64_t nt, int nb, dou
 // ==========================================================================================
 // Langevin dynamics (LangevinDynamics.jl) on the device — Holstein.  Shares the HMC state (x, scratch vectors, ω, ω₄,
 // the accelerator table, here FourierAccelerator.Q) and its helpers.
-//   calc_dSdx! = calc_dSfdx! (:350-384: one solve MᵀM x = Mᵀg, dSf/dx = -2 gᵀ(∂M/∂x)M⁻¹g, the flag is ignored) + shifted
+//   calc_dSdx! = calc_dSfdx! (:350-384: one solve MᵀM x = Mᵀg — M x = g on a BiCGStab / GMRES handle —, dSf/dx = -2 gᵀ(∂M/∂x)M⁻¹g, the flag is ignored) + shifted
 //                calc_dSbdx! (:334-344)
 //   evolve!    = EulerDynamics (:81-130), RungeKuttaDynamics (:162-232), HeunsDynamics (:272-328)
 // ==========================================================================================
@@ -906,11 +921,15 @@ int langevin_force(elph_handle_s *h, HmcState *st, double *dS, const double *g_h
     const int nch = st->nch;
     RC(randn_vectors(h, st, st->R2, g_host, nch));                              // g in layout S
     if (use_precond) RC(elph_kpm_setup_chains(h, bmax, bmin, nullptr, nullptr, nullptr, nullptr, nullptr));   // setup!(P), :366
-    RC(elph_launch_mul(h, 1, h->work.b, st->R2, nch));                             // Mᵀg (model.v″, :378)
     HIPCHK(hipMemsetAsync(h->work.x, 0, (size_t)nch * nd * sizeof(double), h->stream));   // fill!(M⁻¹g, 0), :367
     h->x_zero = true;
     std::vector<double> res((size_t)nch);
-    RC(elph_i_ldiv_core(h, nch, use_precond ? 1 : 0, 0, iters, res.data(), flag));
+    if (h->solver_kind != ELPH_SOLVER_CG) {      // the mul_by_M branch: M x = g itself, with the Left side (:369-372)
+        RC(elph_i_mldiv_core(h, 0, nch, use_precond ? 1 : 0, 0, h->work.x, st->R2, iters, res.data(), flag));
+    } else {
+        RC(elph_launch_mul(h, 1, h->work.b, st->R2, nch));                         // Mᵀg (model.v″, :378)
+        RC(elph_i_ldiv_core(h, nch, use_precond ? 1 : 0, 0, iters, res.data(), flag));
+    }
     const long long n = (long long)st->nf * h->L * nch;
     if (st->ssh) {      // muldMdx!(dSfdx, g, ssh, M⁻¹g) (SSHModels.jl:707-829) with u = g given; no shifted term for bond phonons
         RC(elph_launch_force_ssh(h, h->work.p, h->work.x, st->R2, nch));

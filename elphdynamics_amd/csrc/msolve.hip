@@ -30,7 +30,14 @@
 // tolerance and iter == solver.maxiter end it.  ONE deliberate difference: a cycle cut at iter == solver.maxiter after i < restart steps
 // updates x with the i columns it built; the reference back-substitutes over all `restart` columns there (:538), reading columns this
 // cycle never wrote (zero in the first cycle: 0/0).  Whenever solver.maxiter is a multiple of restart the two coincide.
+//
+// The callers of the solve (estimator, HMC force and action, Langevin force, special updates) reach these solvers through the handle's
+// solver kind (elph_solver_set_kind) and two internals on device-resident vectors, wherever the caller has them (MsVecs): elph_i_mldiv_core,
+// ldiv! of that kind, and elph_i_msolve_pair, the two-stage O⁻¹ b = M⁻¹ M⁻ᵀ b of calc_O⁻¹Λϕ! (HMC.jl:851-903).  ldiv!'s verdict on a batch is one
+// kernel (k_ms_verdict: residual, flag, x zeroed), and a caller's promise that x = 0 (h->x_zero) starts either solver from r = b without the
+// mat-vec on the zero batch (k_bi_init<true>, k_gm_resid<true>) — the same bits.
 
+#include <chrono>
 #include <cmath>
 
 #include "elph_internal.h"
@@ -48,12 +55,14 @@ struct MsRec {              // one right-hand side
     int pad;
 };
 
+struct MsVerdict { double resid; int flag, pad; };      // ldiv!'s residual_error and flag of one right-hand side
+
 struct MsolveState {
     int cap = 0;                   // right-hand sides the buffers hold
     double *vec = nullptr;         // [MS_NVEC][cap][ndim]
     MsRec *rec = nullptr, *h_rec = nullptr;      // [cap]; pinned
     int *done = nullptr;           // [cap] mirror of rec.done for the preconditioner's kernel
-    double *scal = nullptr, *h_scal = nullptr;   // [cap] residual errors; pinned
+    MsVerdict *verd = nullptr, *h_verd = nullptr;      // [cap] k_ms_verdict's output; pinned
     double *V = nullptr;           // GMRES: [restart + 1][cap][ndim]
     double *gm = nullptr;          // GMRES: per right-hand side H [(R+1) R] column-major | s | cs | sn | y, each R + 1
     int V_restart = 0, V_cap = 0;
@@ -81,14 +90,16 @@ __device__ __forceinline__ double ms_block_sum(double v, double *sc) {
 
 struct BiBufs { double *x, *r, *rt, *p, *ph, *s, *sh, *v, *t; const double *b; MsRec *rec; int *done; long long nd; };
 
-// r = b - A x0 (A x0 in B.t), r̃ = r, and the head of iteration 1: ρ = r̃·r, β = 0, p = r
+// r = b - A x0 (A x0 in B.t), r̃ = r, and the head of iteration 1: ρ = r̃·r, β = 0, p = r.  ZERO: x0 = 0 by the caller's promise — r = b
+// without the mat-vec (A 0 is exactly 0 and b - 0 = b: the same bits), B.t is not read
+template <bool ZERO>
 __global__ void __launch_bounds__(1024) k_bi_init(BiBufs B, long long maxiter) {
     __shared__ double sc[32];
     const int rhs = blockIdx.x;
     const size_t o = (size_t)rhs * (size_t)B.nd;
     double bb = 0.0, rr = 0.0;
     for (long long i = threadIdx.x; i < B.nd; i += blockDim.x) {
-        const double bv = B.b[o + i], rv = bv - B.t[o + i];
+        const double bv = B.b[o + i], rv = ZERO ? bv : bv - B.t[o + i];
         B.r[o + i] = rv; B.rt[o + i] = rv; B.p[o + i] = rv; B.v[o + i] = 0.0;
         bb += bv * bv; rr += rv * rv;
     }
@@ -207,12 +218,14 @@ __device__ __forceinline__ void gm_update(const GmBufs &G, int rhs, int k, doubl
     }
 }
 
-// r = b - A x (A x in G.w) for the running right-hand sides (:493-494, :539-540)
+// r = b - A x (A x in G.w) for the running right-hand sides (:493-494, :539-540).  ZERO (the first residual only): x = 0 by the caller's
+// promise — r = b without the mat-vec, G.w is not read
+template <bool ZERO>
 __global__ void __launch_bounds__(1024) k_gm_resid(GmBufs G, int first) {
     const int rhs = blockIdx.x;
     if (!first && G.rec[rhs].done) return;
     const size_t o = (size_t)rhs * (size_t)G.nd;
-    for (long long i = threadIdx.x; i < G.nd; i += blockDim.x) G.r[o + i] = G.b[o + i] - G.w[o + i];
+    for (long long i = threadIdx.x; i < G.nd; i += blockDim.x) G.r[o + i] = ZERO ? G.b[o + i] : G.b[o + i] - G.w[o + i];
 }
 
 // r = P⁻¹ (b - A x) is in (first: and pb = P⁻¹ b: normb, :485-490):  β = |r|, ϵ = β / normb < tol: return iter; iter >= maxiter: return iter
@@ -318,8 +331,12 @@ __global__ void __launch_bounds__(1024) k_gm_update(GmBufs G, int k) {
 
 // ------------------------------------------------------------------------------------------ the true residual of ldiv! (Models.jl:93-97)
 
-// out[rhs] = |A x - b| / |b| (A x in ax)
-__global__ void __launch_bounds__(1024) k_ms_resid(double *__restrict__ out, const double *__restrict__ ax, const double *__restrict__ b, long long nd) {
+// The verdict of ldiv! on the whole batch (Models.jl:93-126, :150-183): residual_error = |A x - b| / |b| (A x in ax); above sqrt(tol)
+// (NaN compares false, as in the reference) the flag is 1 — out of iterations: the record's iters == cmp_maxiter — or 2, and x is zeroed
+// (fill!(x, 0)); else 0.  out[rhs] = {residual_error, flag}
+__global__ void __launch_bounds__(1024) k_ms_verdict(MsVerdict *__restrict__ out, double *__restrict__ x, const double *__restrict__ ax,
+                                                     const double *__restrict__ b, const MsRec *__restrict__ rec, long long nd,
+                                                     double sqrt_tol, long long cmp_maxiter) {
     __shared__ double sc[32];
     const int rhs = blockIdx.x;
     const size_t o = (size_t)rhs * (size_t)nd;
@@ -330,7 +347,15 @@ __global__ void __launch_bounds__(1024) k_ms_resid(double *__restrict__ out, con
     }
     a = ms_block_sum(a, sc);
     c = ms_block_sum(c, sc + 16);
-    if (threadIdx.x == 0) out[rhs] = sqrt(a) / sqrt(c);
+    const double resid = sqrt(a) / sqrt(c);
+    const bool flagged = resid > sqrt_tol;
+    if (flagged)
+        for (long long i = threadIdx.x; i < nd; i += blockDim.x) x[o + i] = 0.0;
+    if (threadIdx.x == 0) {
+        MsVerdict v;
+        v.resid = resid; v.flag = flagged ? ((rec[rhs].iters == cmp_maxiter) ? 1 : 2) : 0; v.pad = 0;
+        out[rhs] = v;
+    }
 }
 
 // ------------------------------------------------------------------------------------------ host
@@ -354,12 +379,12 @@ int ms_reserve(elph_handle_s *h, int nrhs, int restart /* 0: BiCGStab */) {
         RC(ms_alloc(&S->vec, (size_t)MS_NVEC * nrhs * nd));
         RC(ms_alloc(&S->rec, (size_t)nrhs));
         RC(ms_alloc(&S->done, (size_t)nrhs));
-        RC(ms_alloc(&S->scal, (size_t)nrhs));
+        RC(ms_alloc(&S->verd, (size_t)nrhs));
         if (S->h_rec) HIPCHK(hipHostFree(S->h_rec));
-        if (S->h_scal) HIPCHK(hipHostFree(S->h_scal));
-        S->h_rec = nullptr; S->h_scal = nullptr;
+        if (S->h_verd) HIPCHK(hipHostFree(S->h_verd));
+        S->h_rec = nullptr; S->h_verd = nullptr;
         HIPCHK(hipHostMalloc((void **)&S->h_rec, (size_t)nrhs * sizeof(MsRec), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void **)&S->h_scal, (size_t)nrhs * sizeof(double), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&S->h_verd, (size_t)nrhs * sizeof(MsVerdict), hipHostMallocDefault));
         S->cap = nrhs;
     }
     if (restart > 0 && (restart > S->V_restart || S->cap > S->V_cap)) {
@@ -396,18 +421,22 @@ int ms_apply(elph_handle_s *h, double *z, const double *r, int nrhs, int transpo
     return elph_launch_kpm_apply_side(h, z, r, nrhs, transposed, ms_state(h)->done);
 }
 
-// solve!(x, A, b, bicgstab[, P]) on work.b / work.x
-int run_bicgstab(elph_handle_s *h, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t *iters) {
+// where a solve has its right-hand sides and its solutions ([nrhs][ndim], layout S), and whether x is zero by the caller's promise
+struct MsVecs { double *x; const double *b; bool x_zero; };
+
+// solve!(x, A, b, bicgstab[, P])
+int run_bicgstab(elph_handle_s *h, MsVecs U, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t *iters) {
     RC(ms_reserve(h, nrhs, 0));
     MsolveState *S = ms_state(h);
     BiBufs B;
-    B.x = h->work.x; B.b = h->work.b; B.rec = S->rec; B.done = S->done; B.nd = h->ndim;
+    B.x = U.x; B.b = U.b; B.rec = S->rec; B.done = S->done; B.nd = h->ndim;
     B.r = ms_vec(h, 0); B.rt = ms_vec(h, 1); B.p = ms_vec(h, 2); B.s = ms_vec(h, 3); B.v = ms_vec(h, 4); B.t = ms_vec(h, 5);
     B.ph = use_prec ? ms_vec(h, 6) : B.p;
     B.sh = use_prec ? ms_vec(h, 7) : B.s;
     const int which = transposed ? 1 : 0, bs = ms_block(h);
-    RC(elph_launch_mul(h, which, B.t, B.x, nrhs));
-    hipLaunchKernelGGL(k_bi_init, dim3((unsigned)nrhs), dim3((unsigned)bs), 0, h->stream, B, (long long)maxiter);
+    if (!U.x_zero) RC(elph_launch_mul(h, which, B.t, B.x, nrhs));
+    hipLaunchKernelGGL(U.x_zero ? k_bi_init<true> : k_bi_init<false>, dim3((unsigned)nrhs), dim3((unsigned)bs), 0, h->stream, B,
+                       (long long)maxiter);
     RC(elph_launch_check("k_bi_init"));
     bool all_done = false;
     for (int64_t i = 0; i < maxiter && !all_done; ++i) {
@@ -424,30 +453,31 @@ int run_bicgstab(elph_handle_s *h, int transposed, int nrhs, int use_prec, doubl
     return ELPH_OK;
 }
 
-// solve!(x, A, b, gmres[, M]) on work.b / work.x
-int run_gmres(elph_handle_s *h, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t solver_maxiter, int restart,
+// solve!(x, A, b, gmres[, M])
+int run_gmres(elph_handle_s *h, MsVecs U, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t solver_maxiter, int restart,
               int64_t *iters) {
     RC(ms_reserve(h, nrhs, restart));
     MsolveState *S = ms_state(h);
     GmBufs G;
-    G.x = h->work.x; G.b = h->work.b; G.V = S->V; G.gm = S->gm; G.rec = S->rec; G.done = S->done;
+    G.x = U.x; G.b = U.b; G.V = S->V; G.gm = S->gm; G.rec = S->rec; G.done = S->done;
     G.nd = h->ndim; G.vstride = (long long)S->cap * h->ndim; G.R = restart;
     double *w_raw = ms_vec(h, 8), *r_raw = ms_vec(h, 9);
     G.w = use_prec ? ms_vec(h, 10) : w_raw;
     G.r = r_raw;
-    G.pb = use_prec ? ms_vec(h, 11) : h->work.b;
+    G.pb = use_prec ? ms_vec(h, 11) : U.b;
     const int which = transposed ? 1 : 0, bs = ms_block(h);
     const size_t shm = (size_t)(restart + 1) * sizeof(double);
     const dim3 grid((unsigned)nrhs), block((unsigned)bs);
     HIPCHK(hipMemsetAsync(S->done, 0, (size_t)nrhs * sizeof(int), h->stream));
-    if (use_prec) RC(ms_apply(h, ms_vec(h, 11), h->work.b, nrhs, transposed));
+    if (use_prec) RC(ms_apply(h, ms_vec(h, 11), U.b, nrhs, transposed));
 
     // r = P⁻¹ (b - A x), then the tests between two cycles and the start of the next one
     auto residual_and_start = [&](int first, int64_t iter) -> int {
         double *ax = use_prec ? ms_vec(h, 10) : w_raw;
         GmBufs Gr = G; Gr.w = ax;
-        RC(elph_launch_mul(h, which, ax, G.x, nrhs));
-        hipLaunchKernelGGL(k_gm_resid, grid, block, 0, h->stream, Gr, first);
+        const bool zero = first && U.x_zero;
+        if (!zero) RC(elph_launch_mul(h, which, ax, G.x, nrhs));
+        hipLaunchKernelGGL(zero ? k_gm_resid<true> : k_gm_resid<false>, grid, block, 0, h->stream, Gr, first);
         if (use_prec) RC(ms_apply(h, r_raw, r_raw, nrhs, transposed));
         hipLaunchKernelGGL(k_gm_start, grid, block, 0, h->stream, G, first, (long long)iter, (long long)maxiter, tol);
         return elph_launch_check("k_gm_start");
@@ -480,8 +510,9 @@ int run_gmres(elph_handle_s *h, int transposed, int nrhs, int use_prec, double t
 int need_ready(elph_handle_s *h, int solver, int transposed, int nrhs, int use_prec, int restart) {
     (void)transposed;
     if (!h->have_E) { elph_set_error("update_model has not been called on this handle"); return ELPH_E_STATE; }
-    if (h->shard || h->is_slab) { elph_set_error("BiCGStab / GMRES do not run on a sharded handle"); return ELPH_E_STATE; }
-    if (h->dot_hi > 0) { elph_set_error("BiCGStab / GMRES do not run with a restricted inner-product range"); return ELPH_E_STATE; }
+    const char *name = solver == ELPH_SOLVER_GMRES ? "GMRES" : "BiCGStab";
+    if (h->shard || h->is_slab) { elph_set_error("%s does not run on a sharded or slab handle", name); return ELPH_E_STATE; }
+    if (h->dot_hi > 0) { elph_set_error("%s does not run with a restricted inner-product range", name); return ELPH_E_STATE; }
     if (solver != ELPH_SOLVER_BICGSTAB && solver != ELPH_SOLVER_GMRES) { elph_set_error("solver: 1 BiCGStab, 2 GMRES"); return ELPH_E_ARG; }
     if (nrhs < 1) { elph_set_error("nrhs < 1"); return ELPH_E_ARG; }
     if (solver == ELPH_SOLVER_GMRES && (restart < 1 || restart > 1024)) { elph_set_error("GMRES restart outside 1 ... 1024"); return ELPH_E_ARG; }
@@ -489,49 +520,43 @@ int need_ready(elph_handle_s *h, int solver, int transposed, int nrhs, int use_p
     return ELPH_OK;
 }
 
-int ms_solve(elph_handle_s *h, int solver, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter, int64_t solver_maxiter,
-             int restart, int64_t *iters) {
-    h->x_zero = false;
-    if (solver == ELPH_SOLVER_BICGSTAB) return run_bicgstab(h, transposed, nrhs, use_prec, tol, maxiter, iters);
-    return run_gmres(h, transposed, nrhs, use_prec, tol, maxiter, solver_maxiter, restart, iters);
+int ms_solve(elph_handle_s *h, MsVecs U, int solver, int transposed, int nrhs, int use_prec, double tol, int64_t maxiter,
+             int64_t solver_maxiter, int restart, int64_t *iters) {
+    h->x_zero = false;                       // (a promise belongs to one solve: the callers hand it on in U)
+    if (solver == ELPH_SOLVER_BICGSTAB) return run_bicgstab(h, U, transposed, nrhs, use_prec, tol, maxiter, iters);
+    return run_gmres(h, U, transposed, nrhs, use_prec, tol, maxiter, solver_maxiter, restart, iters);
 }
 
-// residual_error and flag of ldiv! for work.x against work.b; x zeroed where the flag is positive (Models.jl:93-126, :150-183)
-int ms_residual_and_flags(elph_handle_s *h, int transposed, int nrhs, const int64_t *iters, int64_t cmp_maxiter, double *resid, int *flag) {
+// residual_error and flag of ldiv! for the solve the records belong to; x zeroed where the flag is positive: one launch, one read
+int ms_residual_and_flags(elph_handle_s *h, MsVecs U, int transposed, int nrhs, int64_t cmp_maxiter, double *resid, int *flag) {
     MsolveState *S = ms_state(h);
     double *ax = ms_vec(h, 8);
-    RC(elph_launch_mul(h, transposed ? 1 : 0, ax, h->work.x, nrhs));
-    hipLaunchKernelGGL(k_ms_resid, dim3((unsigned)nrhs), dim3((unsigned)ms_block(h)), 0, h->stream, S->scal, ax, h->work.b, (long long)h->ndim);
-    RC(elph_launch_check("k_ms_resid"));
-    HIPCHK(hipMemcpyAsync(S->h_scal, S->scal, sizeof(double) * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
+    RC(elph_launch_mul(h, transposed ? 1 : 0, ax, U.x, nrhs));
+    hipLaunchKernelGGL(k_ms_verdict, dim3((unsigned)nrhs), dim3((unsigned)ms_block(h)), 0, h->stream, S->verd, U.x, (const double *)ax, U.b,
+                       (const MsRec *)S->rec, (long long)h->ndim, sqrt(h->tol), (long long)cmp_maxiter);
+    RC(elph_launch_check("k_ms_verdict"));
+    HIPCHK(hipMemcpyAsync(S->h_verd, S->verd, sizeof(MsVerdict) * (size_t)nrhs, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (int r = 0; r < nrhs; ++r) {
-        resid[r] = S->h_scal[r];
-        if (resid[r] > sqrt(h->tol)) {           // (NaN compares false, as in the reference)
-            flag[r] = (iters[r] == cmp_maxiter) ? 1 : 2;
-            HIPCHK(hipMemsetAsync(h->work.x + (size_t)r * (size_t)h->ndim, 0, (size_t)h->ndim * sizeof(double), h->stream));
-        } else {
-            flag[r] = 0;
-        }
-    }
+    for (int r = 0; r < nrhs; ++r) { resid[r] = S->h_verd[r].resid; flag[r] = S->h_verd[r].flag; }
     return ELPH_OK;
 }
 
-// ldiv! on work.b / work.x
-int ms_ldiv(elph_handle_s *h, int solver, int transposed, int nrhs, int use_prec, int64_t maxiter, int restart, int64_t *iters, double *resid,
-            int *flag) {
+// ldiv! of U.b into U.x
+int ms_ldiv(elph_handle_s *h, MsVecs U, int solver, int transposed, int nrhs, int use_prec, int64_t maxiter, int restart, int64_t *iters,
+            double *resid, int *flag) {
     if (maxiter == 0) maxiter = h->maxiter;                                                       // Models.jl:78-80, :143-145
-    RC(ms_solve(h, solver, transposed, nrhs, use_prec, h->tol, maxiter, h->maxiter, restart, iters));
-    RC(ms_residual_and_flags(h, transposed, nrhs, iters, use_prec ? maxiter : h->maxiter, resid, flag));      // :103 maxiter, :160 solver.maxiter
+    RC(ms_solve(h, U, solver, transposed, nrhs, use_prec, h->tol, maxiter, h->maxiter, restart, iters));
+    RC(ms_residual_and_flags(h, U, transposed, nrhs, use_prec ? maxiter : h->maxiter, resid, flag));      // :103 maxiter, :160 solver.maxiter
     if (!use_prec) return ELPH_OK;
     // flagged right-hand sides: again without the preconditioner, from x = 0 (zeroed above), 10 x maxiter (:129-133), one at a time in slot 0
+    const MsVecs U0 = {U.x, U.b, true};
     for (int r = 0; r < nrhs; ++r) {
         if (flag[r] == 0) continue;
         int64_t it1 = 0; double rs1 = 0; int fl1 = 0;
         RC(elph_retry_in_slot0(h, r, [&]() -> int {
-            RC(ms_solve(h, solver, transposed, 1, 0, h->tol, 10 * maxiter, h->maxiter, restart, &it1));
-            return ms_residual_and_flags(h, transposed, 1, &it1, h->maxiter, &rs1, &fl1);
-        }));
+            RC(ms_solve(h, U0, solver, transposed, 1, 0, h->tol, 10 * maxiter, h->maxiter, restart, &it1));
+            return ms_residual_and_flags(h, U0, transposed, 1, h->maxiter, &rs1, &fl1);
+        }, U.x, const_cast<double *>(U.b)));
         iters[r] = it1; resid[r] = rs1; flag[r] = fl1;
     }
     return ELPH_OK;
@@ -544,12 +569,74 @@ int default_restart(const elph_handle_s *h, int restart) { return restart < 0 ? 
 void elph_msolve_free(elph_handle_s *h) {
     MsolveState *S = ms_state(h);
     if (!S) return;
-    void *ptrs[] = {S->vec, S->rec, S->done, S->scal, S->V, S->gm};
+    void *ptrs[] = {S->vec, S->rec, S->done, S->verd, S->V, S->gm};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (S->h_rec) (void)hipHostFree(S->h_rec);
-    if (S->h_scal) (void)hipHostFree(S->h_scal);
+    if (S->h_verd) (void)hipHostFree(S->h_verd);
     delete S;
     h->msolve = nullptr;
+}
+
+int elph_i_mldiv_core(elph_handle_s *h, int transposed, int nrhs, int use_prec, int64_t maxiter, double *x, const double *b, int64_t *iters,
+                      double *resid, int *flag) {
+    const bool x_zero = h->x_zero;           // the promise belongs to THIS solve: consumed before anything can return
+    h->x_zero = false;
+    const int solver = h->solver_kind, restart = solver == ELPH_SOLVER_GMRES ? h->solver_restart : 0;
+    RC(need_ready(h, solver, transposed, nrhs, use_prec, restart));
+    RC(ms_reserve(h, nrhs, restart));
+    const MsVecs U = {x, b, x_zero};
+    return ms_ldiv(h, U, solver, transposed ? 1 : 0, nrhs, use_prec ? 1 : 0, maxiter, restart, iters, resid, flag);
+}
+
+int elph_i_msolve_ready(elph_handle_s *h) { return need_ready(h, h->solver_kind, 0, 1, 0, h->solver_restart); }
+
+// promise: hand the stages the zero-guess promise (the callers); false: they compute A·0 (elph_bench_msolve_pair's comparison)
+static int msolve_pair(elph_handle_s *h, int nrhs, int use_prec, double *x, double *y, const double *b, int64_t *iters2, int *flag2,
+                       bool promise) {
+    const size_t bytes = (size_t)nrhs * (size_t)h->ndim * sizeof(double);
+    std::vector<double> res((size_t)nrhs);
+    HIPCHK(hipMemsetAsync(y, 0, bytes, h->stream));                // fill!(M⁻ᵀΛϕ, 0)  (HMC.jl:862)
+    h->x_zero = promise;
+    RC(elph_i_mldiv_core(h, 1, nrhs, use_prec, 0, y, b, iters2, res.data(), flag2));
+    HIPCHK(hipMemsetAsync(x, 0, bytes, h->stream));                // fill!(O⁻¹Λϕ, 0)  (:869)
+    h->x_zero = promise;
+    return elph_i_mldiv_core(h, 0, nrhs, use_prec, 0, x, y, iters2 + nrhs, res.data(), flag2 + nrhs);
+}
+
+int elph_i_msolve_pair(elph_handle_s *h, int nrhs, int use_prec, double *x, double *y, const double *b, int64_t *iters2, int *flag2) {
+    return msolve_pair(h, nrhs, use_prec, x, y, b, iters2, flag2, true);
+}
+
+extern "C" int elph_bench_msolve_pair(elph_handle h, int nrhs, int use_precond, int zero_start, int reps, double *ms_total, int64_t *iters) {
+    CHECK_H(h);
+    if (nrhs < 1 || reps < 1 || !ms_total) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    if (h->solver_kind == ELPH_SOLVER_CG) { elph_set_error("the handle's solver is CG: elph_solver_set_kind first"); return ELPH_E_STATE; }
+    if (nrhs > h->work.cap_rhs) { elph_set_error("%d right-hand sides asked for, the last evaluation left %d", nrhs, h->work.cap_rhs); return ELPH_E_ARG; }
+    std::vector<int64_t> it2((size_t)2 * nrhs, 0);
+    std::vector<int> fl2((size_t)2 * nrhs, 0);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int r = 0; r < reps; ++r)
+        RC(msolve_pair(h, nrhs, use_precond ? 1 : 0, h->work.x, h->work.z, h->work.b, it2.data(), fl2.data(), zero_start != 0));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (iters) std::copy(it2.begin(), it2.end(), iters);
+    return ELPH_OK;
+}
+
+extern "C" int elph_solver_set_kind(elph_handle h, int solver, int restart) {
+    CHECK_H(h);
+    if (solver != ELPH_SOLVER_CG && solver != ELPH_SOLVER_BICGSTAB && solver != ELPH_SOLVER_GMRES) {
+        elph_set_error("solver: 0 CG, 1 BiCGStab, 2 GMRES");
+        return ELPH_E_ARG;
+    }
+    if (solver == ELPH_SOLVER_GMRES) {
+        restart = default_restart(h, restart);
+        if (restart < 1 || restart > 1024) { elph_set_error("GMRES restart outside 1 ... 1024"); return ELPH_E_ARG; }
+        h->solver_restart = restart;
+    }
+    h->solver_kind = solver;
+    return ELPH_OK;
 }
 
 extern "C" int elph_kpm_apply_side(elph_handle h, int nvec, double *vout, const double *vin, int transposed) {
@@ -576,7 +663,8 @@ extern "C" int elph_msolve(elph_handle h, int solver, int transposed, int nrhs, 
     RC(ms_reserve(h, nrhs, solver == ELPH_SOLVER_GMRES ? restart : 0));
     RC(elph_stage_in(h, h->work.b, B, nrhs));
     RC(elph_stage_in(h, h->work.x, X, nrhs));
-    RC(ms_solve(h, solver, transposed ? 1 : 0, nrhs, use_precond ? 1 : 0, tol, maxiter, solver_maxiter, restart, iters));
+    const MsVecs U = {h->work.x, h->work.b, false};                // (the caller's guess is taken as given)
+    RC(ms_solve(h, U, solver, transposed ? 1 : 0, nrhs, use_precond ? 1 : 0, tol, maxiter, solver_maxiter, restart, iters));
     RC(elph_stage_out(h, X, h->work.x, nrhs));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;
@@ -591,7 +679,8 @@ extern "C" int elph_mldiv(elph_handle h, int solver, int transposed, int nrhs, d
     RC(ms_reserve(h, nrhs, solver == ELPH_SOLVER_GMRES ? restart : 0));
     RC(elph_stage_in(h, h->work.b, B, nrhs));
     RC(elph_stage_in(h, h->work.x, X, nrhs));
-    RC(ms_ldiv(h, solver, transposed ? 1 : 0, nrhs, use_precond ? 1 : 0, maxiter, restart, iters, residual_error, flag));
+    const MsVecs U = {h->work.x, h->work.b, false};                // (the caller's guess is taken as given)
+    RC(ms_ldiv(h, U, solver, transposed ? 1 : 0, nrhs, use_precond ? 1 : 0, maxiter, restart, iters, residual_error, flag));
     RC(elph_stage_out(h, X, h->work.x, nrhs));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ELPH_OK;

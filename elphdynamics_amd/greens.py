@@ -14,6 +14,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import models
 from . import preconditioners as pc
 from ._lib import P_dbl, P_i64, P_int, check, dptr
 
@@ -75,6 +76,7 @@ def update_(est, model, P=None, rng=None, R=None, setup_kwargs=None):
     Returns (iters, residual_error, flag) per vector (the reference discards them)."""
     m = est.model
     assert model is m
+    use_prec = models._caller_prec(P, m)
     if getattr(m, "_nchains", 1) > 1:
         # chains in lockstep: right-hand side r of the batch belongs to chain r % nchains, so an estimator made with
         # nv = n_v * nchains vectors holds vector v of chain c at index v * nchains + c (chain_vector below)
@@ -87,7 +89,6 @@ def update_(est, model, P=None, rng=None, R=None, setup_kwargs=None):
     it = np.zeros(est.nv, dtype=np.int64)
     res = np.zeros(est.nv)
     fl = np.zeros(est.nv, dtype=np.int32)
-    use_prec = 0 if P is None else 1
     if R is None and est.device_rng:
         check(m._lib.elph_greens_update_rng(m._h, use_prec, it.ctypes.data_as(P_i64), dptr(res), fl.ctypes.data_as(P_int)))
         return it, res, fl

@@ -66,6 +66,19 @@ def calc_OinvLambda_phi(model, phi_p, phi_m, P=None, power=1.0, rng=None, setup_
         pc.setup_(P, rng=rng, **(setup_kwargs or {}))
         it, fl, Xp, Xm = calc_dSfdx_(np.zeros(model.Ndof), model, phi_p, phi_m, P=P, power=power, return_solutions=True)
         return Xp, Xm, it, fl
+    if model.mul_by_M:
+        # BiCGStab / GMRES: the two-stage solves Mᵀ y = ϕ±, M x = y (:859-873, :888-902) and their bookkeeping run inside the library's
+        # pair solve, under tol^power; the bond brackets it also assembles are discarded here
+        import ctypes as C
+        from ._lib import check, dptr
+        pc.setup_(P, rng=rng, **(setup_kwargs or {}))
+        model._push_solver()
+        it, fl = C.c_int64(), C.c_int()
+        Xp, Xm, q = np.empty(model.Ndim), np.empty(model.Ndim), np.zeros(max(1, model.Nbonds * model.Ltau))
+        check(model._lib.elph_fermion_force_ssh(model._h, dptr(np.ascontiguousarray(phi_p)), dptr(np.ascontiguousarray(phi_m)),
+                                                models._caller_prec(P, model), float(power), dptr(q), dptr(Xp), dptr(Xm), C.byref(it),
+                                                C.byref(fl)))
+        return Xp, Xm, int(it.value), int(fl.value)
     tol = model.solver.tol
     model.solver.tol = tol ** power
     try:
@@ -97,7 +110,8 @@ class GreensEstimator:
         self.MinvR = np.zeros((self.nv, model.Ndim))
 
     def update_(self, P=None, rng=None, R=None, setup_kwargs=None):
-        """n_v random vectors r, solve MtM x = Mt r  =>  x = M^-1 r, as one batch (GreensFunctions.jl:208-231)."""
+        """n_v random vectors r, solve MtM x = Mt r  =>  x = M^-1 r, as one batch (GreensFunctions.jl:208-231); a mul_by_M model solves
+        M x = r itself (:216-221)."""
         m = self.model
         pc.setup_(P, rng=rng, **(setup_kwargs or {}))
         if R is None:
@@ -105,8 +119,12 @@ class GreensEstimator:
             R = rng.standard_normal((self.nv, m.Ndim))
         self.R[:] = R
         B = np.empty_like(self.R)
-        for i in range(self.nv):
-            models.mulMt_(B[i], m, np.ascontiguousarray(self.R[i]))      # Mᵀr₁ (model.v″, :223-224)
+        if m.mul_by_M:
+            assert not m.transposed
+            B[:] = self.R                                                # M x = r₁ itself (:216-221)
+        else:
+            for i in range(self.nv):
+                models.mulMt_(B[i], m, np.ascontiguousarray(self.R[i]))  # Mᵀr₁ (model.v″, :223-224)
         self.MinvR[:] = 0.0
         return models.ldiv_batched_(self.MinvR, m, B, P=P)
 
@@ -132,7 +150,7 @@ def calc_dSfdx_(dSdx, model, phi_p, phi_m, P=None, power=1.0, return_solutions=F
     if model.kind == models.HOLSTEIN:
         check(model._lib.elph_fermion_force_holstein(
             model._h, dptr(np.ascontiguousarray(model.x)), dptr(model.lam), dptr(model.lam2), dptr(model.mu), model.dtau,
-            dptr(np.ascontiguousarray(phi_p)), dptr(np.ascontiguousarray(phi_m)), 0 if P is None else 1, float(power),
+            dptr(np.ascontiguousarray(phi_p)), dptr(np.ascontiguousarray(phi_m)), models._caller_prec(P, model), float(power),
             dptr(dSdx), dptr(Xp) if return_solutions else None, dptr(Xm) if return_solutions else None,
             C.byref(it), C.byref(fl)))
     else:
@@ -141,7 +159,7 @@ def calc_dSfdx_(dSdx, model, phi_p, phi_m, P=None, power=1.0, return_solutions=F
         # (SSHModels.jl:797-823; equivalent fields / primary_field are not modelled here).
         models.update_model_(model)
         check(model._lib.elph_fermion_force_ssh_fields(
-            model._h, dptr(np.ascontiguousarray(phi_p)), dptr(np.ascontiguousarray(phi_m)), 0 if P is None else 1,
+            model._h, dptr(np.ascontiguousarray(phi_p)), dptr(np.ascontiguousarray(phi_m)), models._caller_prec(P, model),
             float(power), dptr(dSdx), dptr(Xp) if return_solutions else None, dptr(Xm) if return_solutions else None,
             C.byref(it), C.byref(fl)))
     if return_solutions:
@@ -283,7 +301,7 @@ def update_(model, hmc, fa=None, P=None, rng=None, randoms=None, pull=True):
     c = lambda a: dptr(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)) if a is not None else None
     u = randoms.get("u")
     check(model._lib.elph_hmc_update(
-        model._h, hmc.dt, hmc.Nt, hmc.Nb, hmc.alpha, 0 if P is None else 1, c(randoms.get("R")), c(randoms.get("Rp")),
+        model._h, hmc.dt, hmc.Nt, hmc.Nb, hmc.alpha, models._caller_prec(P, model), c(randoms.get("R")), c(randoms.get("Rp")),
         c(randoms.get("Rm")), c(randoms.get("kpm_randn")), float(u) if u is not None else -1.0, C.byref(acc), C.byref(its), dptr(en),
         C.byref(fl)))
     hmc.accepted, hmc.iters, hmc.flag = bool(acc.value), its.value, int(fl.value)
@@ -317,7 +335,7 @@ def update_chains_(model, hmc, fa=None, P=None, rng=None, randoms=None, pull=Fal
     its, en = np.zeros(nch), np.zeros((nch, 5))
     c = lambda a: dptr(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)) if a is not None else None
     check(model._lib.elph_hmc_update_chains(
-        model._h, hmc.dt, hmc.Nt, hmc.Nb, hmc.alpha, 0 if P is None else 1, c(randoms.get("R")), c(randoms.get("Rp")),
+        model._h, hmc.dt, hmc.Nt, hmc.Nb, hmc.alpha, models._caller_prec(P, model), c(randoms.get("R")), c(randoms.get("Rp")),
         c(randoms.get("Rm")), c(randoms.get("kpm_randn")), c(randoms.get("u")), acc.ctypes.data_as(P_int), dptr(its), dptr(en),
         fl.ctypes.data_as(P_int)))
     hmc.accepted, hmc.iters, hmc.flags, hmc.energies = acc.astype(bool), its, fl, en
@@ -350,7 +368,7 @@ def special_move_(model, hmc, kind, col_i, col_j=0, P=None, rng=None, randoms=No
     c = lambda a: dptr(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)) if a is not None else None
     u = randoms.get("u")
     check(model._lib.elph_hmc_special_move(model._h, int(kind), int(col_i), int(col_j), c(randoms.get("Rp")), c(randoms.get("Rm")),
-                                           0 if P is None else 1, c(randoms.get("kpm_randn")), float(u) if u is not None else -1.0,
+                                           models._caller_prec(P, model), c(randoms.get("kpm_randn")), float(u) if u is not None else -1.0,
                                            C.byref(acc), C.byref(s0), C.byref(s1), C.byref(it), C.byref(fl)))
     if model.kind == models.SSH:
         model._cs_stale = True
@@ -379,7 +397,7 @@ def special_move_chains_(model, hmc, kind, cols_i, cols_j=None, P=None, rng=None
     c = lambda a: dptr(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)) if a is not None else None
     check(model._lib.elph_hmc_special_move_chains(
         model._h, int(kind), ci.ctypes.data_as(P_i64), cj.ctypes.data_as(P_i64), c(randoms.get("Rp")), c(randoms.get("Rm")),
-        0 if P is None else 1, c(randoms.get("kpm_randn")), c(randoms.get("u")), acc.ctypes.data_as(P_int), dptr(s0), dptr(s1),
+        models._caller_prec(P, model), c(randoms.get("kpm_randn")), c(randoms.get("u")), acc.ctypes.data_as(P_int), dptr(s0), dptr(s1),
         it.ctypes.data_as(P_i64), fl.ctypes.data_as(P_int)))
     if model.kind == models.SSH:
         model._cs_stale = True
@@ -400,7 +418,7 @@ def special_update_(model, hmc, kind, nmoves, P=None):
     s0, s1 = np.zeros(shape), np.zeros(shape)
     model._push_solver()
     check(model._lib.elph_hmc_special_update_chains(
-        model._h, int(kind), nm, 0 if P is None else 1, acc.ctypes.data_as(P_int), ci.ctypes.data_as(P_i64), cj.ctypes.data_as(P_i64),
+        model._h, int(kind), nm, models._caller_prec(P, model), acc.ctypes.data_as(P_int), ci.ctypes.data_as(P_i64), cj.ctypes.data_as(P_i64),
         dptr(s0), dptr(s1), it.ctypes.data_as(P_i64), fl.ctypes.data_as(P_int)))
     if model.kind == models.SSH:
         model._cs_stale = True

@@ -96,13 +96,14 @@ def evolve_(model, dyn, fa=None, P=None, rng=None, randoms=None, pull=True):
     """evolve!(model, dyn, fa, preconditioner) -> iters: one Langevin step, entirely on the device.  With dyn.nchains > 1 the
     random vectors are chain-major (see draw_randoms) and the return value is iters[nchains]; dyn.flags holds the solver flag
     of every chain."""
+    use_prec = models._caller_prec(P, model)
     if randoms is None:
         randoms = {} if dyn.device_rng else draw_randoms(dyn, rng or np.random.default_rng(), P is not None)
     model._push_solver()
     nch = dyn.nchains
     it, fl = (C.c_int64 * nch)(), (C.c_int * nch)()
     c = lambda a: dptr(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)) if a is not None else None
-    check(model._lib.elph_langevin_evolve(model._h, dyn.scheme, dyn.dt, 0 if P is None else 1, c(randoms.get("eta")), c(randoms.get("g1")),
+    check(model._lib.elph_langevin_evolve(model._h, dyn.scheme, dyn.dt, use_prec, c(randoms.get("eta")), c(randoms.get("g1")),
                                           c(randoms.get("g2")), c(randoms.get("kpm_randn")), it, fl))
     dyn.flags = np.array(fl[:], dtype=np.int32)
     dyn.flag = int(dyn.flags.max())

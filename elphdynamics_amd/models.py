@@ -61,7 +61,7 @@ class GMRES:
         self.restart = int(restart) if restart >= 0 else min(20, self.ndim)
 
 
-SOLVER_CODES = {BiCGStab: 1, GMRES: 2}               # include/elph_gpu.h: ELPH_SOLVER_BICGSTAB, ELPH_SOLVER_GMRES
+SOLVER_CODES = {BiCGStab: 1, GMRES: 2}               # include/elph_gpu.h: ELPH_SOLVER_BICGSTAB, ELPH_SOLVER_GMRES (ELPH_SOLVER_CG: 0)
 
 
 def make_solver(name, ndim, tol, maxiter, restart=-1):
@@ -95,6 +95,8 @@ class AbstractModel:
 
     def _push_solver(self):
         check(self._lib.elph_solver_set(self._h, self.solver.tol, self.solver.maxiter, getattr(self.solver, "kmax", 1e12)))
+        # the solver's type and restart: what the callers of the solve (estimator, HMC, Langevin, special updates) run inside the library
+        check(self._lib.elph_solver_set_kind(self._h, SOLVER_CODES.get(type(self.solver), 0), _restart(self.solver)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -440,6 +442,18 @@ def _use_prec(P, model=None, by_M=None):
 
 def _restart(solver):
     return int(getattr(solver, "restart", -1))
+
+
+def _caller_prec(P, model):
+    """use_precond of a caller of the solve inside the library (estimator, HMC force and action, Langevin force, special updates): _use_prec's
+    family rule — and a mul_by_M model's callers solve with Mt and with M in turn (HMC.jl:851-903), so of the one-sided preconditioners only
+    LeftRightKPMPreconditioner serves them (ProcessInputFile.jl:502-506)."""
+    use = _use_prec(P, model)
+    if use and model.mul_by_M:
+        from .preconditioners import LeftRightKPMPreconditioner
+        if not isinstance(P, LeftRightKPMPreconditioner):
+            raise ValueError("the callers of a mul_by_M model solve with Mt and then with M: they take LeftRightKPMPreconditioner")
+    return use
 
 
 def solve_(x, model, b, cg=None, P=None, maxiter=0, tol=0.0, kmax=0.0, history=False):

@@ -12,7 +12,8 @@ What is read: [lattice], [holstein] / [ssh] (all tables, disorder widths include
 [tune_density] (its parameters; mu_tuner.from_params makes the tuner of them).  What is not: the measurement container and its folders, logging, checkpoints — the reference's
 control plane (SURVEY §8 "out of scope"); sim.input keeps the whole parsed deck for a driver that wants them.
 
-Only solver.type = "CG" exists on the GPU (the path of BASELINE.json); GMRES / BiCGStab decks raise.
+solver.type = "CG" (CG on MᵀM, the path of BASELINE.json), "BiCGStab" and "GMRES" (on M and Mᵀ, with solver.restart) all run on the GPU: the
+model carries the solver, and the estimator, the dynamics and the special updates dispatch on it inside the library.
 """
 import os
 from types import SimpleNamespace
@@ -54,13 +55,21 @@ def _check_solver(inp):
     if str(s["type"]).lower() != "cg":
         raise NotImplementedError(f"solver.type = {s['type']!r}: the GPU path is the CG solve of MᵀM (solver.type = \"CG\")")
     return float(s["tol"]), int(s["maxiter"])
+# (_check_solver is kept as it was for the callers that want a CG-only deck refused; the model builders below no longer call it: they
+#  read solver_settings and hand the solver's type to the model, which runs every type on the device)
+
+
+def solver_settings(inp):
+    """(type, tol, maxiter, restart) of the [solver] table; restart (GMRES) defaults to 20 (ProcessInputFile.jl:227-243, :342-358)."""
+    s = inp["solver"]
+    return str(s["type"]), float(s["tol"]), int(s["maxiter"]), int(s.get("restart", 20))
 
 
 def initialize_holstein_model(inp, rng, device=0):
     """ProcessInputFile.jl:216-326."""
-    tol, maxiter = _check_solver(inp)
+    kind, tol, maxiter, restart = solver_settings(inp)
     d = inp["holstein"]
-    m = models.HolsteinModel(_lattice(inp), d["beta"], d["dtau"], tol=tol, maxiter=maxiter, device=device)
+    m = models.HolsteinModel(_lattice(inp), d["beta"], d["dtau"], tol=tol, maxiter=maxiter, device=device, solver=kind, restart=restart)
     for key, assign in (("omega", m.assign_omega_), ("mu", m.assign_mu_), ("omega4", m.assign_omega4_)):
         for e in d.get(key, []):
             for orbit in e["orbit"]:
@@ -78,9 +87,9 @@ def initialize_holstein_model(inp, rng, device=0):
 
 def initialize_ssh_model(inp, rng, device=0):
     """ProcessInputFile.jl:331-441."""
-    tol, maxiter = _check_solver(inp)
+    kind, tol, maxiter, restart = solver_settings(inp)
     d = inp["ssh"]
-    m = models.SSHModel(_lattice(inp), d["beta"], d["dtau"], tol=tol, maxiter=maxiter, device=device)
+    m = models.SSHModel(_lattice(inp), d["beta"], d["dtau"], tol=tol, maxiter=maxiter, device=device, solver=kind, restart=restart)
     for e in d["mu"]:
         for orbit in e["orbit"]:
             sel = slice(orbit - 1, None, m.lattice.norbits) if orbit else slice(None)
@@ -116,12 +125,13 @@ def initialize_phonon_fields_(inp, model):
 
 
 def initialize_preconditioner(inp, model):
-    """ProcessInputFile.jl:473-514 (None plays the role of `I`)."""
+    """ProcessInputFile.jl:473-514 (None plays the role of `I`): the symmetric expansion for CG, LeftRightKPMPreconditioner for any other
+    solver (:502-506)."""
     p = inp["solver"].get("preconditioner")
     if p is None:
         return None
-    return pc.SymmetricKPMPreconditioner(model, n=int(p.get("n", 20)), buf=float(p.get("buf", 0.05)), c1=float(p.get("c1", 1.0)),
-                                         c2=float(p.get("c2", 1.0)))
+    cls = pc.SymmetricKPMPreconditioner if str(inp["solver"]["type"]).lower() == "cg" else pc.LeftRightKPMPreconditioner
+    return cls(model, n=int(p.get("n", 20)), buf=float(p.get("buf", 0.05)), c1=float(p.get("c1", 1.0)), c2=float(p.get("c2", 1.0)))
 
 
 def initialize_fourieraccelerator(inp, model):

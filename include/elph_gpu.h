@@ -886,8 +886,19 @@ int elph_kpm_apply_dev(elph_handle h, double *z_dev, const double *r_dev);
  * expansion copies (:475-478). */
 int elph_kpm_apply_side(elph_handle h, int nvec, double *vout, const double *vin, int transposed);
 
+#define ELPH_SOLVER_CG 0
 #define ELPH_SOLVER_BICGSTAB 1
 #define ELPH_SOLVER_GMRES 2
+
+/* The solver of the handle's model (model.solver's type; the default is CG on MᵀM): what the callers of the solve run — the Green's-function
+ * estimator (elph_greens_update[_rng]), the HMC force and action (elph_hmc_update[_chains], elph_fermion_force_*), the Langevin force and
+ * the special updates.  solver: ELPH_SOLVER_CG / _BICGSTAB / _GMRES; restart: GMRES only, < 0: min(20, ndim).
+ * With BiCGStab or GMRES these callers follow the reference's mul_by_M branches: calc_O⁻¹Λϕ! is two solves per pseudofermion field, Mᵀ y = Λϕ
+ * then M x = y (HMC.jl:851-903); the estimator and the Langevin force solve M x = r directly (GreensFunctions.jl:216-226,
+ * LangevinDynamics.jl:366-375).  use_precond = 1 then means LeftRightKPMPreconditioner: the Right side of the handle's expansion for an Mᵀ
+ * solve, the Left side for an M solve.  Such a caller returns ELPH_E_STATE on a sharded or slab handle and with a restricted inner-product
+ * range.  A handle whose kind is CG behaves exactly as before this entry point existed. */
+int elph_solver_set_kind(elph_handle h, int solver, int restart);
 
 /* solve!(x, A, b, solver[, P]; maxiter, tol) -> iters for nrhs right-hand sides at once (IterativeSolvers.jl:354-417 BiCGStab, :464-570
  * GMRES with update! :552-570 and the rotations :572-584), A = M (transposed = 0) or Mᵀ (1).  X: initial guesses in, solutions out; X, B:
