@@ -190,6 +190,7 @@ BENCH_SIGNATURES = {
     "elph_bench_hess_max_real": (c_int, [Handle, c_int, c_int, c_int, P_dbl, P_dbl]),
     "elph_bench_kpm_bounds": (c_int, [Handle, c_int, P_dbl, P_dbl, P_dbl, P_int]),
     "elph_bench_greens_noise": (c_int, [Handle, c_int, c_i64, C.c_uint64, c_int, P_dbl, c_i64, c_i64, P_dbl]),
+    "elph_bench_kpm_side_info": (c_int, [Handle, P_int]),
 }
 
 # the slots of elph_bench_lattice_shape's vector, in order (elph_bench.h)
@@ -240,6 +241,17 @@ def dft_plan(ltau, which, inverse, N, nvec, nrz_slots=0, handle=None):
     args = (int(which), int(bool(inverse)), int(N), int(nvec), int(nrz_slots), out)
     check(lib.elph_bench_dft_plan(int(ltau), *args) if handle is None else lib.elph_bench_dft_info(handle, *args))
     return dict(zip(DFT_PLAN_SLOTS, list(out)))
+
+
+KPM_SIDE_SLOTS = ("cbs", "npl", "lds_tables", "refused", "ms_block")
+
+
+def kpm_side_info(handle):
+    """The launch shape of the one-sided KPM apply and of the BiCGStab / GMRES vector kernels on a handle (elph_bench_kpm_side_info), as
+    {slot: value}."""
+    out = (c_int * len(KPM_SIDE_SLOTS))()
+    check(load().elph_bench_kpm_side_info(handle, out))
+    return dict(zip(KPM_SIDE_SLOTS, list(out)))
 
 
 def kpm_plan(ltau, bounds, buf=0.05, c1=1.0, c2=1.0):

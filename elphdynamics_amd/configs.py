@@ -88,7 +88,8 @@ CONFIGS = {
 
 
 def make_model(tag, tol=1e-5, maxiter=10000, rough=True, device=0, seed=synth.SEED_FIELDS, t_stddev=0.0):
-    kind, norb, Ls, bonds, beta, dtau = CONFIGS[tag]
+    """The model of a tag of CONFIGS, or of a row written like one: (kind, norbits, Lspatial, bonds, beta, dtau)."""
+    kind, norb, Ls, bonds, beta, dtau = CONFIGS[tag] if isinstance(tag, str) else tag
     L1, L2 = Ls if isinstance(Ls, tuple) else (Ls, Ls if Ls > 1 else 1)
     lattice = lat.Lattice(norb, L1, L2, 1)
     if kind == "holstein":

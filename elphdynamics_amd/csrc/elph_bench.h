@@ -111,6 +111,12 @@ int elph_bench_greens_noise(elph_handle h, int mapping, int64_t nvec, uint64_t s
  * of the last one (may be NULL). */
 int elph_bench_msolve_pair(elph_handle h, int nrhs, int use_precond, int zero_start, int reps, double *ms_total, int64_t *iters);
 
+/* The launch shape of the one-sided KPM apply and of the BiCGStab / GMRES vector kernels on this handle (needs no set-up): out[5] = the threads per
+ * workgroup of k_kpm_cheb_side, its sites per thread NPL (the template argument), whether the bond program rides in LDS (lds_tables), whether
+ * elph_kpm_apply_side and a preconditioned elph_msolve refuse the lattice (NPL beyond 6), and the threads per workgroup of the solver kernels
+ * (msolve.hip: ms_block, 64 per wave). */
+int elph_bench_kpm_side_info(elph_handle h, int *out);
+
 /* the sharded solve (shard.hip): exactly `iters` iterations (no stop test); *ms = HIP-event time of this rank's launch.  b_slab may
  * be NULL (keeps the right-hand side of the previous call).  Needs elph_shard_prepare + barrier like a solve. */
 int elph_shard_iterate(elph_handle h, const double *b_slab, int64_t iters, double *ms);

@@ -612,6 +612,12 @@ int elph_launch_cg_init_prec_only(elph_handle_s *h, int nrhs);
 int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nrhs, int cg_mode, int parts = 7);
 // one side of the expansion (kernels.hip: k_kpm_cheb_side): transposed 0 Left ~ M⁻¹, 1 Right ~ M⁻ᵀ; done: [nrhs] skip flags or nullptr
 int elph_launch_kpm_apply_side(elph_handle_s *h, double *zS, const double *rS, int nrhs, int transposed, const int *done);
+// The launch shape of the LDS-slab Chebyshev kernels (k_kpm_cheb, k_kpm_cheb_side), a pure function of the handle: cbs threads per workgroup,
+// npl = ceil(N / cbs) sites per thread, shm bytes of slab, tab bytes of bond program, which rides in LDS next to the slab when lds_tables = 1.
+// The one-sided kernel is instantiated for npl <= ELPH_SIDE_NPL_MAX.
+struct KpmSlabShape { int cbs, npl, lds_tables; size_t shm, tab; };
+constexpr int ELPH_SIDE_NPL_MAX = 6;
+KpmSlabShape elph_kpm_slab_shape(const elph_handle_s *h);
 void elph_msolve_free(elph_handle_s *h);                                    // msolve.hip
 // msolve.hip internals used by hmc.hip, greens.hip and elph_api.hip: the handle's solver kind (BiCGStab or GMRES, never CG) on
 // device-resident layout-S vectors.  Both consume the h->x_zero promise of their caller (x was zeroed by the library for THIS solve).

@@ -1095,6 +1095,21 @@ static inline int gen_bs(const elph_handle_s *h) {
 }
 static inline int gen_npl(const elph_handle_s *h) { const int bs = gen_bs(h); return (int)((h->N + bs - 1) / bs); }
 
+// The LDS-slab Chebyshev launch: one thread per bond of the largest colour (up to 1024), so that a colour is one LDS round trip per thread; the
+// bond program rides in LDS when it fits next to the slab.
+KpmSlabShape elph_kpm_slab_shape(const elph_handle_s *h) {
+    const int N = (int)h->N;
+    KpmSlabShape sh;
+    int maxcol = 1;
+    for (int cidx = 0; cidx < h->ncol; ++cidx) maxcol = std::max(maxcol, h->h_coloff[(size_t)cidx + 1] - h->h_coloff[(size_t)cidx]);
+    sh.cbs = std::min(1024, std::max(gen_bs(h), ELPH_WAVE * ((maxcol + ELPH_WAVE - 1) / ELPH_WAVE)));
+    sh.npl = (N + sh.cbs - 1) / sh.cbs;
+    sh.shm = (size_t)N * sizeof(double2);
+    sh.tab = (size_t)h->nb * (2 * sizeof(double) + sizeof(unsigned));
+    sh.lds_tables = (N <= 65535 && sh.shm + sh.tab <= 64 * 1024) ? 1 : 0;
+    return sh;
+}
+
 #define DISPATCH_NPL(npl, CALL)                                   \
     switch (npl) {                                                \
         case 1: { constexpr int NPL = 1; CALL; } break;           \
@@ -1307,8 +1322,7 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         int rcd = elph_dft_fwd_twisted(h, h->work.nu, rS, N, nrhs, st);
         if (rcd) return rcd;
     }
-    const size_t shm = (size_t)N * sizeof(double2);
-    bool rz_done = cg_mode && pl.rz_freq;     // r.z partials produced in frequency space by the Chebyshev kernel
+    bool rz_done = cg_mode && pl.rz_freq;    // r.z partials produced in frequency space by the Chebyshev kernel
     if (!(parts & 2)) {
         rz_done = h->fast && pl.reg_cheb && cg_mode;      // (timing the inverse transform alone: the form that follows the register-exchange kernel)
     } else if (pl.cheb == CgPlan::CH_PG) {
@@ -1320,17 +1334,10 @@ int elph_launch_kpm_apply(elph_handle_s *h, double *zS, const double *rS, int nr
         int rcf = elph_fast_kpm_cheb(h, nrhs, st, pl.reg_cheb, rz_done ? B.rz : nullptr, B.nrz, B.rr, (fold && rz_done) ? nct : 0);
         if (rcf) return rcf;
     } else {
-        // one thread per bond of the largest colour (up to 1024): a colour is then one LDS round trip per thread; the bond
-        // program rides in LDS when it fits next to the slab
-        int maxcol = 1;
-        for (int cidx = 0; cidx < h->ncol; ++cidx) maxcol = std::max(maxcol, h->h_coloff[(size_t)cidx + 1] - h->h_coloff[(size_t)cidx]);
-        const int cbs = std::min(1024, std::max(gen_bs(h), ELPH_WAVE * ((maxcol + ELPH_WAVE - 1) / ELPH_WAVE)));
-        const int cnpl = (N + cbs - 1) / cbs;
-        const size_t tab = (size_t)h->nb * (2 * sizeof(double) + sizeof(unsigned));
-        const int lds_tables = (N <= 65535 && shm + tab <= 64 * 1024) ? 1 : 0;
-        DISPATCH_NPL(cnpl, {
-            hipLaunchKernelGGL((k_kpm_cheb<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)cbs), shm + (lds_tables ? tab : 0),
-                               h->stream, h->work.nu, K, m, Lo2, st, lds_tables, rz_done ? B.rz : nullptr, B.nrz, B.rr);
+        const KpmSlabShape sh = elph_kpm_slab_shape(h);
+        DISPATCH_NPL(sh.npl, {
+            hipLaunchKernelGGL((k_kpm_cheb<NPL>), dim3((unsigned)nrhs, (unsigned)Lo2), dim3((unsigned)sh.cbs), sh.shm + (sh.lds_tables ? sh.tab : 0),
+                               h->stream, h->work.nu, K, m, Lo2, st, sh.lds_tables, rz_done ? B.rz : nullptr, B.nrz, B.rr);
         });
     }
     // r.z partial slots: (blockIdx.y * gridDim.x + blockIdx.x) < ceil(L/TPT)*nst <= L*npl = nrz; the kernel clears the rest
@@ -1360,15 +1367,11 @@ int elph_launch_kpm_apply_side(elph_handle_s *h, double *zS, const double *rS, i
     }
     KpmDev K = elph_kpm_dev(h);
     ModelDev m = elph_model_dev(h);
-    const size_t shm = (size_t)N * sizeof(double2);
-    int maxcol = 1;
-    for (int cidx = 0; cidx < h->ncol; ++cidx) maxcol = std::max(maxcol, h->h_coloff[(size_t)cidx + 1] - h->h_coloff[(size_t)cidx]);
-    const int cbs = std::min(1024, std::max(gen_bs(h), ELPH_WAVE * ((maxcol + ELPH_WAVE - 1) / ELPH_WAVE)));
-    const int cnpl = (N + cbs - 1) / cbs;
-    const size_t tab = (size_t)h->nb * (2 * sizeof(double) + sizeof(unsigned));
-    const int lds_tables = (N <= 65535 && shm + tab <= 64 * 1024) ? 1 : 0;
-    if (cnpl > 6) {
-        elph_set_error("the one-sided KPM preconditioners serve lattices of up to %d sites (this one: %d)", 6 * cbs, N);
+    const KpmSlabShape sh = elph_kpm_slab_shape(h);
+    const int cbs = sh.cbs, cnpl = sh.npl, lds_tables = sh.lds_tables;
+    const size_t shm = sh.shm, tab = sh.tab;
+    if (cnpl > ELPH_SIDE_NPL_MAX) {
+        elph_set_error("the one-sided KPM preconditioners serve lattices of up to %d sites (this one: %d)", ELPH_SIDE_NPL_MAX * cbs, N);
         return ELPH_E_UNSUPPORTED;
     }
     RC(elph_dft_fwd_twisted(h, h->work.nu, rS, N, nrhs, nullptr));

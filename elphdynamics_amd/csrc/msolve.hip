@@ -624,6 +624,16 @@ extern "C" int elph_bench_msolve_pair(elph_handle h, int nrhs, int use_precond, 
     return ELPH_OK;
 }
 
+extern "C" int elph_bench_kpm_side_info(elph_handle h, int *out) {
+    CHECK_H(h);
+    if (!out) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    const KpmSlabShape sh = elph_kpm_slab_shape(h);
+    out[0] = sh.cbs; out[1] = sh.npl; out[2] = sh.lds_tables;
+    out[3] = sh.npl > ELPH_SIDE_NPL_MAX ? 1 : 0;
+    out[4] = ms_block(h);
+    return ELPH_OK;
+}
+
 extern "C" int elph_solver_set_kind(elph_handle h, int solver, int restart) {
     CHECK_H(h);
     if (solver != ELPH_SOLVER_CG && solver != ELPH_SOLVER_BICGSTAB && solver != ELPH_SOLVER_GMRES) {

@@ -38,17 +38,14 @@ class Lattice:
         pairs = []
         for isite in range(orbit1, self.nsites + 1, self.norbits):
             pairs.append((isite, self.site_to_site(isite, displacement, orbit2)))
-        if remove_duplicates:
-            keep = [True] * len(pairs)
-            for i in range(len(pairs) - 1):
-                if not keep[i]:
-                    continue
-                a, b = pairs[i]
-                for j in range(i + 1, len(pairs)):
-                    a2, b2 = pairs[j]
-                    if (a == a2 and b == b2) or (a == b2 and b == a2):
-                        keep[j] = False
-            pairs = [p for p, k in zip(pairs, keep) if k]
+        if remove_duplicates:       # the first of every unordered pair stays, in its place
+            seen, kept = set(), []
+            for a, b in pairs:
+                key = (a, b) if a <= b else (b, a)
+                if key not in seen:
+                    seen.add(key)
+                    kept.append((a, b))
+            pairs = kept
         return np.array(pairs, dtype=np.int64).reshape(-1, 2)
 
 
@@ -68,15 +65,15 @@ def checkerboard_groups(table):
     nassigned = 0
     while nassigned < nb:
         group += 1
-        members = []            # bonds already in this colour (all earlier-indexed than the candidate)
+        used = set()            # sites of the bonds already in this colour (all earlier-indexed than the candidate)
         for n in range(nb):
             if groups[n] != 0:
                 continue
-            i, j = table[n]
-            if any(i == table[p, 0] or j == table[p, 1] or i == table[p, 1] or j == table[p, 0] for p in members):
+            i, j = int(table[n, 0]), int(table[n, 1])
+            if i in used or j in used:
                 continue
             groups[n] = group
-            members.append(n)
+            used.update((i, j))
             nassigned += 1
     return groups
 

@@ -29,9 +29,18 @@ class _HostSSH(models.SSHModel):
         pass
 
 
+# configurations of single test files, written like the rows of configs.CONFIGS and registered here by their case modules
+# (tests/msolver_size_cases.py): host_model() knows them by tag; on the device configs.make_model() takes the row itself
+LOCAL_CONFIGS = {}
+
+
+def config_row(tag):
+    return configs.CONFIGS[tag] if tag in configs.CONFIGS else LOCAL_CONFIGS[tag]
+
+
 def host_model(tag, t_stddev=0.0, seed=synth.SEED_FIELDS):
     """configs.make_model(tag) up to, and without, the device handle: the same lattice, bond table, hoppings and field."""
-    kind, norb, Ls, bonds, beta, dtau = configs.CONFIGS[tag]
+    kind, norb, Ls, bonds, beta, dtau = config_row(tag)
     L1, L2 = Ls if isinstance(Ls, tuple) else (Ls, Ls if Ls > 1 else 1)
     lattice = lat.Lattice(norb, L1, L2, 1)
     if kind == "holstein":
@@ -98,7 +107,7 @@ def colour_runs(table):
 
 
 class Operator:
-    """v -> A v and v -> A^-1 v in the dtype of v."""
+    """v -> A v, v -> A^T v and v -> A^-1 v in the dtype of v: an N-vector, or an (N, ncols) block of them."""
 
     def __init__(self, table, Ebar, cbar, sbar):
         self.table = np.asarray(table, dtype=np.int64).reshape(-1, 2) - 1
@@ -106,11 +115,15 @@ class Operator:
         self.runs = colour_runs(self.table + 1)
         self.N = len(Ebar)
 
-    def _cb(self, y, inverse):
+    def _cb(self, y, inverse, backwards=None):
+        """The checkerboard product on y in place, run after run (backwards: from the last run to the first; the default: as the inverse
+        needs it); inverse: every bond factor inverted."""
         dt = y.dtype.type
-        for (lo, hi) in (reversed(self.runs) if inverse else self.runs):
+        col = (-1,) + (1,) * (y.ndim - 1)
+        backwards = inverse if backwards is None else backwards
+        for (lo, hi) in (reversed(self.runs) if backwards else self.runs):
             i, j = self.table[lo:hi, 0], self.table[lo:hi, 1]
-            c, s = self.cbar[lo:hi].astype(dt), self.sbar[lo:hi].astype(dt)
+            c, s = self.cbar[lo:hi].astype(dt).reshape(col), self.sbar[lo:hi].astype(dt).reshape(col)
             if inverse:
                 s = -s
             t1, t2 = y[i], y[j]
@@ -118,11 +131,18 @@ class Operator:
             y[j] = c * t2 + s * t1
         return y
 
+    def _E(self, v):
+        return self.Ebar.astype(v.dtype).reshape((-1,) + (1,) * (v.ndim - 1))
+
     def mul(self, v):
-        return self._cb(self.Ebar.astype(v.dtype) * v, False)
+        return self._cb(self._E(v) * v, False)
+
+    def mulT(self, v):
+        """A^T v = diag(Ebar) CBbar^T v: every bond factor is symmetric, so CBbar^T is the product in the opposite order."""
+        return self._E(v) * self._cb(v.copy(), False, backwards=True)
 
     def div(self, v):
-        return self._cb(v.copy(), True) / self.Ebar.astype(v.dtype)
+        return self._cb(v.copy(), True) / self._E(v)
 
     def dense(self, inverse=False):
         eye = np.eye(self.N)

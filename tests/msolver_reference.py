@@ -2,10 +2,12 @@
 preconditioners (KPMPreconditioners.jl:494-600) and of ldiv! for mul_by_M models (Models.jl:74-186) — the reference of
 tests/test_msolvers_host.py (CPU: this file checks itself against the oracle) and tests/test_gpu_msolvers.py (GPU).
 
-Everything is dense: M from oracle.mulM on unit vectors of a host model, the Left / Right preconditioners as matrices built from the
-oracle's expansion tables.  Each solver takes its inner product from kpm_bounds_reference.DOTS (three float64 summation orders and a
-sequential long double); bicgstab() and gmres() also return the LOG-MARGIN of the solve, the smallest |ln(eps / tol)| over every
-comparison with the tolerance it made.  Two correct implementations agree on eps far better than a margin of 1e-2, so a case with that
+Setup is dense: M from oracle.mulM on unit vectors of a host model, the Left / Right preconditioners as matrices built from the
+oracle's expansion tables.  MatrixFreeSetup (tests/test_msolver_sizes_host.py, tests/test_gpu_msolver_sizes.py: lattices of thousands of
+sites) builds no matrix: bicgstab(), gmres() and mldiv() use A and P only through A @ v and P @ v, and take operator objects there — M and
+M^T the oracle's mulM / mulMT on a vector, P side_apply(matrix_free=True).  Each solver takes its inner product from
+kpm_bounds_reference.DOTS (three float64 summation orders and a sequential long double, the latter with dense operators only); bicgstab()
+and gmres() also return the LOG-MARGIN of the solve, the smallest |ln(eps / tol)| over every comparison with the tolerance it made.  Two correct implementations agree on eps far better than a margin of 1e-2, so a case with that
 margin stops at the same iteration on both — which is what lets the GPU tests ask for EQUAL iteration counts.
 
 gmres(as_executed=False) is the library's rule; as_executed=True restates solve! literally: the inner loop breaks at
@@ -42,11 +44,11 @@ def kpm_tables(oP):
                 lam_mag=float(oP.lam_mag))
 
 
-def side_apply(K, table, v, transposed):
+def side_apply(K, table, v, transposed, matrix_free=False):
     """One side of the expansion on v (reference layout, (N L) or (N L, ncols)): the twisted transform (TimeFreqFFTs.jl:37-73), per
     frequency block the Chebyshev series of A' = (A - lam_avg) / lam_mag, A = CBbar diag(Ebar) — Left (transposed False): sum c_n T_n(A'),
     KPMPreconditioners.jl:514-554; Right: sum conj(c_n) T_n(A'^T), :560-600 — the mirror frequencies by conjugation, the inverse transform
-    (:112-130)."""
+    (:112-130).  matrix_free: A' u through Operator.mul / mulT on the (N, ncols) block, bond colour after bond colour, and no N x N matrix."""
     v = np.asarray(v, dtype=np.float64)
     if not K["active"]:
         return v.copy()
@@ -55,10 +57,15 @@ def side_apply(K, table, v, transposed):
     t = np.arange(L)
     F = np.exp(-2j * np.pi * np.outer(np.arange(L), t) / L) * np.exp(-1j * np.pi * t / L)[None, :]      # [w, t]
     nu = np.einsum("wt,itc->iwc", F, V)
-    A = Operator(table, K["Ebar"], K["cbar"], K["sbar"]).dense()
-    if transposed:
-        A = A.T
-    Ap = (A - K["lam_avg"] * np.eye(N)) / K["lam_mag"]
+    op = Operator(table, K["Ebar"], K["cbar"], K["sbar"])
+    if matrix_free:
+        mul = op.mulT if transposed else op.mul
+        Ap = _MatFree(lambda u: (mul(np.ascontiguousarray(u, dtype=np.complex128)) - K["lam_avg"] * u) / K["lam_mag"])
+    else:
+        A = op.dense()
+        if transposed:
+            A = A.T
+        Ap = (A - K["lam_avg"] * np.eye(N)) / K["lam_mag"]
     out = np.zeros_like(nu)
     for w in range(Lo2):
         order = int(K["order"][w])
@@ -82,6 +89,28 @@ def side_apply(K, table, v, transposed):
     return res.reshape(v.shape)
 
 
+class _MatFree:
+    """u -> f(u) behind the @ of a matrix; .T: the operator of ft."""
+
+    matrix_free = True
+
+    def __init__(self, f, ft=None):
+        self.f, self.ft = f, ft
+
+    def __matmul__(self, u):
+        return self.f(u)
+
+    @property
+    def T(self):
+        return _MatFree(self.ft, self.f)
+
+
+def real_operator(f, ft=None):
+    """The float64 operator of v -> f(v) (ft: of its transpose) on contiguous vectors, for bicgstab(), gmres() and mldiv()."""
+    wrap = lambda g: None if g is None else (lambda u: g(np.ascontiguousarray(u, dtype=np.float64)))      # noqa: E731
+    return _MatFree(wrap(f), wrap(ft))
+
+
 def side_matrix(K, table, transposed):
     n = K["N"] * K["L"]
     return side_apply(K, table, np.eye(n), transposed)
@@ -95,7 +124,9 @@ def _lm(eps, tol):
 
 
 def _cast(dt, *arrs):
-    return [None if a is None else np.asarray(a, dtype=dt) for a in arrs]
+    """The arrays in dt; a matrix-free operator passes as it is — it computes in float64 (the oracle's mat-vec), so only with a float64 dt."""
+    assert dt is np.float64 or not any(getattr(a, "matrix_free", False) for a in arrs), "the long-double variant is dense-only"
+    return [a if a is None or getattr(a, "matrix_free", False) else np.asarray(a, dtype=dt) for a in arrs]
 
 
 def bicgstab(A, b, x0, tol, maxiter, P=None, dot="blas"):
@@ -226,7 +257,7 @@ def solve(solver, A, b, x0, tol, maxiter, solver_maxiter, restart, P=None, dot="
 def mldiv(solver, A, b, x0, tol, solver_maxiter, restart, P=None, maxiter=0, dot="blas"):
     """ldiv!(x, model, b[, P]; maxiter) (Models.jl:74-186) -> (x, iters, residual_error, flag)."""
     maxiter = maxiter or solver_maxiter
-    A64, b64 = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    A64, b64 = _cast(np.float64, A, b)
 
     def attempt(x0, P, mi, cmp_maxiter):
         x, it, _ = solve(solver, A, b, x0, tol, mi, solver_maxiter, restart, P, dot)
@@ -258,7 +289,7 @@ class Setup:
         self.m = host_model(name)
         self.om = src.oracle_model(orc, self.m, field)
         self.n = self.m.Ndim
-        self.M = dense_M(orc, self.om, self.n)
+        self.M = self._operator()
         self.b = np.ascontiguousarray(synth.rhs(self.n))
         self.oP = orc.make_kpm(self.om, n=20, buf=0.05, c1=1.0, c2=1.0)
         if bounds:
@@ -269,6 +300,9 @@ class Setup:
             self.bounds = orc.kpm_setup(self.oP, b_max=rng.standard_normal(self.m.Nsites), b_min=rng.standard_normal(self.m.Nsites))
         self.K = kpm_tables(self.oP)
         self._side, self._cache = {}, {}
+
+    def _operator(self):
+        return dense_M(self.orc, self.om, self.n)
 
     def A(self, op):
         return self.M.T if op == "MT" else self.M
@@ -305,15 +339,37 @@ class Setup:
         return self._cache[key]
 
 
+class MatrixFreeSetup(Setup):
+    """The same configuration with no matrix of the size of the problem: M and M^T are the oracle's mulM / mulMT on a vector, the Left / Right
+    preconditioners side_apply(matrix_free=True) on a vector or a block of them.  The float64 summation orders only."""
+
+    def _operator(self):
+        return real_operator(lambda v: self.orc.mulM(self.om, v), lambda v: self.orc.mulMT(self.om, v))
+
+    def side(self, transposed):
+        if transposed not in self._side:
+            self._side[transposed] = real_operator(lambda v, t=transposed: side_apply(self.K, self.m.neighbor_table, v, t, matrix_free=True))
+        return self._side[transposed]
+
+    def xs(self, op):
+        """The solution to a preconditioned residual of 1e-13 (GMRES(20), at most 200 iterations: asserted)."""
+        key = ("xs", op)
+        if key not in self._cache:
+            x, it, _, _ = gmres(self.A(op), self.b, np.zeros(self.n), 1e-13, 200, 200, 20, self.P(op))
+            assert it < 200, (self.name, op, it)
+            self._cache[key] = x
+        return self._cache[key]
+
+
 _setups = {}
 
 
-def setup(orc, name, chain=0, nchains=1, bounds=None):
+def setup(orc, name, chain=0, nchains=1, bounds=None, matrix_free=False):
     """The Setup of chain `chain` of a model run with nchains chains (fields: stop_rule_cases.chain_fields)."""
-    key = (name, chain, nchains, bounds)
+    key = (name, chain, nchains, bounds, matrix_free)
     if key not in _setups:
         field = None if nchains == 1 else src.chain_fields(host_model(name), nchains)[chain]
-        _setups[key] = Setup(orc, name, field, chain, bounds)
+        _setups[key] = (MatrixFreeSetup if matrix_free else Setup)(orc, name, field, chain, bounds)
     return _setups[key]
 
 
