@@ -209,6 +209,29 @@ static bool match_triangular(const elph_handle_s *h, int L) {
     return true;
 }
 
+// simple cubic L x L x L (site = x + L (y + L z); bonds (1,0,0), (0,1,0), (0,0,1)), colours [x-even | x-odd | y-even | y-odd | z-even | z-odd]: what
+// the greedy colouring gives even extents of at least 4 (an odd extent mixes the directions inside the colours and fails here)
+static bool match_cubic(const elph_handle_s *h, int L) {
+    auto partner = [L](int col, int i) {
+        int r[3] = {i % L, (i / L) % L, i / (L * L)};
+        int &a = r[col >> 1];
+        a = (col & 1) ? ((a & 1) ? (a + 1) % L : (a + L - 1) % L) : (a ^ 1);
+        return r[0] + L * (r[1] + L * r[2]);
+    };
+    std::vector<char> seen((size_t)6 * h->N, 0);
+    for (int col = 0; col < 6; ++col) {
+        const int b0 = h->h_coloff[col], b1 = h->h_coloff[col + 1];
+        if (b1 - b0 != h->N / 2) return false;
+        for (int n = b0; n < b1; ++n) {
+            const int i = h->h_bi[n], j = h->h_bj[n];
+            if (partner(col, i) != j || partner(col, j) != i) return false;
+            if (seen[(size_t)col * h->N + i] || seen[(size_t)col * h->N + j]) return false;
+            seen[(size_t)col * h->N + i] = seen[(size_t)col * h->N + j] = 1;
+        }
+    }
+    return true;
+}
+
 // The shape of a handle's lattice from its coloured bond table, its model kind and its hopping table (h_bi, h_bj, h_coloff, kind, h_c, h_s);
 // reads nothing else of the handle and changes nothing.  ELPH_PG_MW=0 (pgrid.hip: elph_pg_mw) keeps the patch shapes to one wavefront per slice.
 static LatticeShape elph_recognise_lattice(const elph_handle_s *h) {
@@ -273,6 +296,14 @@ static LatticeShape elph_recognise_lattice(const elph_handle_s *h) {
         if (L && pgrid::pick_tpatch(L, &px, &py) && match_triangular(h, L)) {
             s.kind = LatticeShape::TRIANGULAR; s.LX = s.LY = L; s.PX = px; s.PY = py; s.NW = 1;
             if (L <= 16) s.GX = s.GY = L / 2;
+            return s;
+        }
+        // simple cubic, Holstein with one (cosh, sinh) for every bond: 2 x 2 x 2 sites per thread (pgrid::Cu); hopping disorder, bond phonons and
+        // every other box keep the kernels of an unrecognised lattice
+        int Lc = 0, nw = 1;
+        for (int l = 6; l <= 12; l += 2) if ((int64_t)l * l * l == N) Lc = l;
+        if (Lc && hol && s.hop_uniform && pgrid::pick_cpatch(Lc, &nw) && (nw == 1 || elph_pg_mw()) && match_cubic(h, Lc)) {
+            s.kind = LatticeShape::CUBIC; s.LX = s.LY = s.LZ = Lc; s.PX = s.PY = 2; s.NW = nw;
         }
     }
     return s;

@@ -40,13 +40,13 @@ int elph_bench_wg_info(elph_handle h, int nrhs, int *usable, int *T, int *W, int
  * in the epilogue of the inverse tau-transform, k_cg_ap_chunk<PX> reading the ready p; kernels.hip: px_plan). */
 int elph_bench_px_info(elph_handle h, int *fused);
 
-/* The patch layout of this handle (pgrid.hip), if any: *kind 0 none, 1 square, 2 honeycomb, 3 triangular; the patch shape and the wavefronts per time
- * slice; *tables = 1 when the hopping is disordered and the mat-vec / Chebyshev kernels take the patch layout with a (cosh, sinh) table in LDS. */
+/* The patch layout of this handle (pgrid.hip), if any: *kind 0 none, 1 square, 2 honeycomb, 3 triangular, 4 simple cubic (2 x 2 x 2 sites per thread, reported as
+ * PX = PY = 2); the patch shape and the wavefronts per time slice; *tables = 1 when the hopping is disordered and the mat-vec / Chebyshev kernels take the patch layout with a (cosh, sinh) table in LDS. */
 int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, int *nw, int *tables);
 
 /* What elph_create would recognise in this bond table (same table arguments; needs no device): out[16] = the small square lattice's LX, LY and its
  * DPP size (1: 8 x 8, 2: 16 x 16, else 0); the honeycomb lattice's LX, LY (cells) and whether it is 12 x 12; the patch layout's kind (0 none,
- * 1 square, 2 honeycomb, 3 triangular), side, PX, PY and wavefronts per slice (1 without one); the GRID layout's lanes GX, GY; the honeycomb grid
+ * 1 square, 2 honeycomb, 3 triangular, 4 simple cubic: side L of the L x L x L box, PX = PY = 2 for its 2 x 2 x 2 patches), side, PX, PY and wavefronts per slice (1 without one); the GRID layout's lanes GX, GY; the honeycomb grid
  * form's registers per lane (2, 4, 8; 0); whether the model's hopping is one (cosh, sinh); the site -> bond map uploaded (0 none, 1 small square,
  * 2 patch).  Reads ELPH_PG_MW as elph_create does. */
 int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht, const double *sinht,

@@ -223,10 +223,11 @@ __device__ __forceinline__ KpmChainView kpm_chain_view(const KpmDev &K, int rhs,
 // The lattice a handle's bond table holds, recognised once at elph_create by elph_recognise_lattice (elph_api.hip) in the reference's colouring
 // (host only).  Derived facts are accessors, not fields.
 struct LatticeShape {
-    enum Kind { NONE, SQUARE, HONEYCOMB, TRIANGULAR };     // (the values are the patch kinds of pgrid.hip)
+    enum Kind { NONE, SQUARE, HONEYCOMB, TRIANGULAR, CUBIC };     // (the values are the patch kinds of pgrid.hip)
     Kind kind = NONE;
-    int LX = 0, LY = 0;            // periodic LX x LY sites (square, triangular) or two-site cells (honeycomb)
-    int PX = 0, PY = 0, NW = 0;    // patch layout (pgrid_dev.h): PX x PY sites / cells per lane on NW wavefronts per slice; 0: none
+    int LX = 0, LY = 0;            // periodic LX x LY sites (square, triangular) or two-site cells (honeycomb); cubic: LX x LY x LZ sites
+    int LZ = 0;                    // simple cubic only (0: a two-dimensional lattice)
+    int PX = 0, PY = 0, NW = 0;    // patch layout (pgrid_dev.h): PX x PY sites / cells per lane (cubic: 2 x 2 x 2 sites) on NW wavefronts per slice; 0: none
     int GX = 0, GY = 0;            // GRID layout (cg_fast_common.h): a GX x GY grid of lanes holding 2 x 2 patches; 0: none
     std::vector<int> bond;         // square lattices: [4][N] the bond that covers site i in colour col
     bool hop_uniform = false;      // Holstein, and every bond of the model's table carries (hop_c, hop_s)
@@ -239,6 +240,7 @@ struct LatticeShape {
     int sq_L() const { return small_square() && LX == LY ? LX : 0; }                        // ... when it is square
     int dpp() const { return sq_L() == 8 ? 1 : sq_L() == 16 ? 2 : 0; }                      // 1: the 8 x 8, 2: the 16 x 16 DPP forms
     bool honeycomb() const { return kind == HONEYCOMB; }
+    int cubic_L() const { return kind == CUBIC && LX == LY && LY == LZ ? LZ : 0; }            // the side of a simple-cubic lattice in the patch layout
     int hc_L() const { return honeycomb() && LX == LY ? LX : 0; }
     bool hc12() const { return hc_L() == 12; }                                                // the honeycomb DPP / quad forms
     // the honeycomb grid form: registers per lane (2, 4 or 8: 1, 2 x 1 or 2 x 2 cells) when the cells fit 64 lanes, else 0

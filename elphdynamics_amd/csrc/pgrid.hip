@@ -1,5 +1,7 @@
 // pgrid.hip — register-exchange kernels for even-L square lattices beyond 16 x 16 (L = 18, 20, 24, 28, 32; pgrid_dev.h: a PX x PY
 // patch of sites per lane, the whole time slice in ONE wavefront), uniform hopping, site phonons (Holstein).
+// The same kernels serve every lattice type of pgrid_dev.h (Sq, Hc, Tri; Cu: simple-cubic L x L x L, 2 x 2 x 2 sites per thread) — they reach the
+// lattice only through LAT::lanes, site_of, make_ctx and apply.
 //
 // k_kpm_cheb_pg: the per-frequency Chebyshev recursion of the KPM preconditioner (KPMPreconditioners.jl:426-481 ldiv!, :606-693 the
 // series) — what the generic kernel (kernels.hip: k_kpm_cheb, a workgroup of up to 1024 threads per (right-hand side, frequency), one
@@ -28,6 +30,7 @@ using H33_2 = pgrid::Hc<3, 3, 2>; using H33_3 = pgrid::Hc<3, 3, 3>; using H33_4 
 using H22_2 = pgrid::Hc<2, 2, 2>; using H22_3 = pgrid::Hc<2, 2, 3>; using H22_4 = pgrid::Hc<2, 2, 4>;
 using TR22 = pgrid::Tri<2, 2>; using TR24 = pgrid::Tri<2, 4>; using TR26 = pgrid::Tri<2, 6>; using TR44 = pgrid::Tri<4, 4>;
 using HC32 = pgrid::Hc<3, 2>; using HC42 = pgrid::Hc<4, 2>; using HC33 = pgrid::Hc<3, 3>;
+using CU_1 = pgrid::Cu<1>; using CU_2 = pgrid::Cu<2>; using CU_4 = pgrid::Cu<4>;      // simple cubic: 2 x 2 x 2 sites per thread, L = 6, 8 / 10 / 12
 
 __device__ __forceinline__ double pg_wave_sum(double v) {
 #pragma unroll
@@ -507,6 +510,9 @@ static int pg_dispatch(int kind, int px, int py, int nw, bool tables, F &&launch
     else if (kind == 2 && px == 2 && nw == 2) launch(Tag<H22_2>{});
     else if (kind == 2 && px == 2 && nw == 3) launch(Tag<H22_3>{});
     else if (kind == 2 && px == 2 && nw == 4) launch(Tag<H22_4>{});
+    else if (kind == 4 && nw == 1) launch(Tag<CU_1>{});
+    else if (kind == 4 && nw == 2) launch(Tag<CU_2>{});
+    else if (kind == 4 && nw == 4) launch(Tag<CU_4>{});
     else if (kind != 3 && nw > 1) { elph_set_error("patch kernels: no instantiation for kind %d, %d x %d patches on %d wavefronts", kind, px, py, nw); return ELPH_E_UNSUPPORTED; }
     else if (kind == 1 && px == 4 && py == 4) launch(Tag<SQ44>{});
     else if (kind == 1 && px == 2 && py == 6) launch(Tag<SQ26>{});
@@ -611,6 +617,7 @@ int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs
     const int L = (int)h->L;
     int px, py, nw;
     pg_launch_shape(h, nrhs, fused, &px, &py, &nw);
+    // (cubic: px = py = 2 stands for 2 x 2 x 2 = 8 registers per vector — two waves per SIMD, as the 2 x 4 square patch)
     const long long slots = 1024LL * ((!h->shape.honeycomb() && px * py <= 8) ? 2 : 1) / nw;      // (a slice of several wavefronts holds as many slots)
     int T = 20;
     for (int c : {1, 2, 4, 5, 8, 10, 16, 20, 32, 40}) { if ((long long)nrhs * ((L + c - 1) / c) <= slots) { T = c; break; } }

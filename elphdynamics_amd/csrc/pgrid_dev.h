@@ -24,6 +24,7 @@ struct Ctx {
     double th, ks;           // tanh of the bond angle; the factor taken out of the colours: c^4 (square), c^3 (honeycomb)
     int xu, xd, yu, yd;      // lanes of the patches X + 1, X - 1, Y + 1, Y - 1 (cyclic); idle lanes: themselves
     int du, dd;              // lanes of the patches (X - 1, Y + 1) and (X + 1, Y - 1): the diagonal bonds of the triangular lattice
+    int zu, zd;              // lanes of the patches Z + 1, Z - 1 (cyclic) of a simple-cubic lattice (Cu); the other kinds leave them unset
     // MULTI-WAVE slices (round 6: square lattices whose patches need more than 64 lanes — L = 22, 26, 34, 38 as 2 x 2 patches on 2 ... 6 wavefronts,
     // L = 40 ... 64 as 4 x 4 patches on 2 ... 4): the "lanes" above are thread indices of the slice's NT = 64 NW threads, and the patch edges
     // cross through LDS instead of ds_bpermute — xb: four exchange buffers of 2 PBMAX x NT doubles (x-odd / y-odd colour x forward / reverse sweep:
@@ -345,6 +346,106 @@ template <int PX_, int PY_> struct Tri {
         }
     }
 };
+// ---- simple cubic: L x L x L sites (site = x + L (y + L z)) in the reference's colouring [x-even | x-odd | y-even | y-odd | z-even | z-odd]
+// (what Checkerboard.jl's greedy colouring gives the three bond definitions (1,0,0), (0,1,0), (0,0,1) for even extents of at least 4; recognised
+// by elph_recognise_lattice, elph_api.hip: match_cubic).  A lane holds a 2 x 2 x 2 patch: lane l = the patch (X, Y, Z) = (l % G, (l / G) % G,
+// l / G^2), G = L / 2; register q = cx + 2 cy + 4 cz is the site (2 X + cx) + L ((2 Y + cy) + L (2 Z + cz)).  An even colour of direction D pairs
+// the registers (q, q ^ (1 << D)) of the lane; an odd colour has no pair inside an extent of 2: the high face (bit D of q set) pairs with the low
+// face of the patch above, the low face with the high face of the patch below — four values each way, all issued before the first is used.
+//   L = 6, 8: 27 / 64 lanes of one wavefront (faces by ds_bpermute, no barrier)      L = 10, 12: 125 / 216 threads on 2 / 4 wavefronts (faces through LDS)
+// EXCHANGE BUFFERS of the multi-wave form: one barrier per crossing colour orders a buffer's writes against the reads of its LAST use only if the
+// crossing in between used ANOTHER buffer (whoever writes has passed that crossing's barrier, which everybody reaches after reading).  The square
+// lattice gives every (colour, sweep direction) a buffer of its own; six of those would be 98 KB at four wavefronts.  Here a buffer belongs to the
+// POSITION of the crossing in its sweep (first, second, third — whichever colour that is in the direction swept): any sequence of forward and
+// reverse sweeps then walks 0 1 2 0 1 2 ..., no two consecutive crossings share a buffer, and THREE buffers (49 KB at four wavefronts) serve
+// every kernel — the alternating sweeps of the mat-vecs and the one-directional series of the Chebyshev recursion alike, with no barrier added.
+template <int D, bool ODD, int POS>      // D: 0 x, 1 y, 2 z; POS: the crossing's position in its sweep (odd colours)
+__device__ __forceinline__ void ccolour(double (&v)[8], const Ctx &X) {
+    constexpr int S = 1 << D;                                     // register stride along the colour's direction
+    // the four registers of the low face (bit D clear), b = 0 ... 3
+    auto lo = [](int b) { return D == 0 ? 2 * b : D == 1 ? (b & 1) + 4 * (b >> 1) : b; };
+    if constexpr (!ODD) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int i = lo(b), j = i + S;
+            const double ni = v[i] + X.th * v[j], nj = v[j] + X.th * v[i];
+            v[i] = ni; v[j] = nj;
+        }
+    } else {
+        const int up = D == 0 ? X.xu : D == 1 ? X.yu : X.zu, dn = D == 0 ? X.xd : D == 1 ? X.yd : X.zd;
+        double fu[4], fd[4];
+        if (X.xb) {
+            double *xb = X.xb + (size_t)POS * 8 * X.nt;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                xb[(2 * b) * X.nt + X.me] = v[lo(b)];
+                xb[(2 * b + 1) * X.nt + X.me] = v[lo(b) + S];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                fu[b] = xb[(2 * b) * X.nt + up];
+                fd[b] = xb[(2 * b + 1) * X.nt + dn];
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                fu[b] = __shfl(v[lo(b)], up, WAVE_);              // the low face of the patch above
+                fd[b] = __shfl(v[lo(b) + S], dn, WAVE_);          // the high face of the patch below
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            v[lo(b) + S] += X.th * fu[b];
+            v[lo(b)] += X.th * fd[b];
+        }
+    }
+}
+template <int NW_ = 1> struct Cu {
+    static constexpr int PX = 2, PY = 2, NS = 8, NW = NW_;
+    static constexpr bool DIS = false;
+    static constexpr int NCOL = 6;
+    static constexpr size_t TAB_BYTES = 0;
+    static constexpr int XB_DOUBLES = (NW_ > 1) ? 3 * 2 * 4 * NW_ * WAVE_ : 1, XB2_DOUBLES = XB_DOUBLES;      // three buffers of 2 faces x 4 values (above)
+    __host__ __device__ static int lanes(int L) { return (L / 2) * (L / 2) * (L / 2); }
+    __host__ __device__ static int site_of(int lane, int q, int L) {
+        const int G = L / 2;
+        const int l = (lane < G * G * G) ? lane : 0, X = l % G, Y = (l / G) % G, Z = l / (G * G);
+        return (2 * X + (q & 1)) + L * ((2 * Y + ((q >> 1) & 1)) + L * (2 * Z + (q >> 2)));
+    }
+    __device__ static Ctx make_ctx(int lane, int L, double c, double s, double *xb = nullptr, int = 3) {
+        const int G = L / 2;
+        Ctx X;
+        X.xb = (NW > 1) ? xb : nullptr; X.nt = NW * WAVE_; X.me = lane; X.bmask = 3; X.tab = nullptr;
+        X.th = s / c; X.ks = (c * c * c) * (c * c * c);      // six colours
+        X.xu = X.xd = X.yu = X.yd = X.du = X.dd = X.zu = X.zd = lane;
+        if (lane < G * G * G) {
+            const int x = lane % G, y = (lane / G) % G, z = lane / (G * G);
+            auto at = [G](int a, int b, int cc) { return a + G * (b + G * cc); };
+            X.xu = at((x + 1) % G, y, z); X.xd = at((x + G - 1) % G, y, z);
+            X.yu = at(x, (y + 1) % G, z); X.yd = at(x, (y + G - 1) % G, z);
+            X.zu = at(x, y, (z + 1) % G); X.zd = at(x, y, (z + G - 1) % G);
+        }
+        return X;
+    }
+    template <bool REVERSE> __device__ static void apply(double (&v)[NS], const Ctx &X) {
+        if constexpr (!REVERSE) {
+            ccolour<0, false, 0>(v, X); ccolour<0, true, 0>(v, X); ccolour<1, false, 0>(v, X); ccolour<1, true, 1>(v, X); ccolour<2, false, 0>(v, X); ccolour<2, true, 2>(v, X);
+        } else {
+            ccolour<2, true, 0>(v, X); ccolour<2, false, 0>(v, X); ccolour<1, true, 1>(v, X); ccolour<1, false, 0>(v, X); ccolour<0, true, 2>(v, X); ccolour<0, false, 0>(v, X);
+        }
+    }
+};
+// The cubic patch form: L x L x L with L = 6, 8, 10, 12 — (L / 2)^3 = 27, 64, 125, 216 patches on *NW = 1, 1, 2, 4 wavefronts per slice.  (L = 4 keeps the
+// six-colour lane program: 8 lanes of 64 would work; L >= 14 needs more than four wavefronts, and the Chebyshev kernel's LDS — two parts, each
+// with its exchange buffers — does not fit a CU.)  The caller admits *NW > 1 only with elph_pg_mw().
+inline bool pick_cpatch(int L, int *NW) {
+    if (L != 6 && L != 8 && L != 10 && L != 12) return false;
+    const int G = L / 2;
+    *NW = (G * G * G + 63) / 64;
+    return true;
+}
+
 // The patch for an even-L triangular lattice (any even L from 4: no other register form exists for it).
 inline bool pick_tpatch(int L, int *PX, int *PY) {
     if (L < 4 || (L & 1)) return false;
