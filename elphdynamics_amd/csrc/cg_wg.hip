@@ -407,6 +407,12 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
     // One slice per wave keeps the old order (config C, 2 right-hand sides: 3.40 us per iteration against 3.44 with the pass).
     // BSUM (the square-lattice DPP forms): the four sums are added behind each batch of reverse sweeps.
     constexpr bool FUSED = !SHARD && T >= 2, BSUM = SQ;
+    // RPOLL (the 16 x 16 uniform form at 4 slices per wave): the pass's sixteen reads of the own slices of r go out in the meeting's poll
+    // window, into registers the reverse batches have left free — nothing writes a wave's own r between the first barrier of the
+    // iteration and the pass (the neighbours only read it, the wave itself writes it in the pass), the `lgkmcnt(0)` of the barrier
+    // behind the poll retires them while every wave waits for L2 anyway, and the pass starts its fma the moment beta exists and issues
+    // only its sixteen stores.  Left alone the eight waves queued 16 reads + 16 writes each at the CU's LDS with the vector ALU idle.
+    constexpr bool RPOLL = SQ && !SSH && UNI && T == 4 && !SHARD;
     // (alpha, beta and the screens of the stop test carry the same bits in every lane: FUSED keeps them in scalar registers — the pass holds
     //  alpha AND beta, and the 4-slice shape has no vector register to spare)
     auto uni = [](double v) __attribute__((always_inline)) {
@@ -708,6 +714,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         if constexpr (HC && T >= 3) asm volatile("" : "+v"(lane_b));
         double rr;                                            // r.r of the NEW residual
         double alpha_f = 0.0;                                 // FUSED: alpha, for the pass behind the stop test
+        double rt[RPOLL ? T : 1][NPL];                        // RPOLL: the own slices of r, read in the poll window for the pass
         {   // ================= the single-meeting iteration ==================================================================
         // The two meetings of the textbook iteration (p.z -> alpha; then r.r of the new residual and its boundary slices -> beta, halo
         // of p) fold into ONE: every workgroup publishes FOUR sums — p.z, r.z, z.z and the r.r of the current residual — and the
@@ -864,6 +871,14 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             pap = tot[0]; rz = tot[1]; zz = tot[2]; rr0 = tot[3];
         } else if (G == 1) {
             const double t4 = sum_part4(part, W, lane);
+            if constexpr (RPOLL) {                            // (a team of one has no poll window: behind the read of the partials, never in front)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < T; ++j)
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) rt[RPOLL ? j : 0][q] = rl[j * HSL + lr + q * LSL];
+                __builtin_amdgcn_sched_barrier(0);
+            }
             pap = readlane_f64(t4, 0); rz = readlane_f64(t4, 8); zz = readlane_f64(t4, 16); rr0 = readlane_f64(t4, 24);
         } else {
             // Every wave fetches its share of the two boundary slices of z (2 NPL segments of 64 values, segment s -> wave s % W, two
@@ -873,6 +888,12 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             bool ok = true;
             double t4 = 0.0;
             if (wv == rw) publish_rec4(slotsA, g, sum_part4(part, W, lane), epoch, lane);
+            if constexpr (RPOLL) {                            // (behind the record's publication, in front of the polls)
+#pragma unroll
+                for (int j = 0; j < T; ++j)
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) rt[RPOLL ? j : 0][q] = rl[j * HSL + lr + q * LSL];
+            }
             for (int s0 = wv; s0 < NSEG || (s0 == wv && wv == rw); s0 += 2 * W) {
                 const int s1 = s0 + W;
                 const u64 *b0 = nullptr, *b1 = nullptr;
@@ -942,11 +963,13 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                 for (int q = 0; q < NPL; ++q)
                     if (own[q]) {
                         // (FUSED: r' is not in LDS yet — the same fma makes the same bits here as in the pass that will store them)
-                        const double rn = FUSED ? rl[j * HSL + lr + q * LSL] - alpha * z[j][q] : rl[j * HSL + lr + q * LSL];
+                        const double rn = RPOLL ? rt[RPOLL ? j : 0][q] - alpha * z[j][q] : (FUSED ? rl[j * HSL + lr + q * LSL] - alpha * z[j][q] : rl[j * HSL + lr + q * LSL]);
                         a += rn * rn;
                     }
             a = wave_sum_dpp(a);
-            if (lane == 0) partF[wv] = a;
+            // (RPOLL holds r in registers from the poll window on: this rare branch makes its slot's address afresh, from the wave number read
+            //  as a scalar — kept in a vector register across the loop it was the one register too many, 8 bytes of scratch)
+            if (lane == 0) partF[RPOLL ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : wv] = a;
             wg_barrier();
             if constexpr (SHARD) {
                 if (wv == 0) {
@@ -1024,7 +1047,7 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
             for (int j = 0; j < T; ++j)
 #pragma unroll
                 for (int q = 0; q < NPL; ++q) {
-                    const double rn = rl[j * HSL + lr + q * LSL] - alpha_f * z[j][q];                 // :285
+                    const double rn = (RPOLL ? rt[RPOLL ? j : 0][q] : rl[j * HSL + lr + q * LSL]) - alpha_f * z[j][q];     // :285
                     if (lwok) rl[j * HSL + lr + q * LSL] = rn;
                     if (X_GLB) { if (lwok) xg[(size_t)(t0 + j) * N + sc[q]] = xr[X_REG ? j : 0][q] + alpha_f * p[j + 1][q]; }
                     else if (X_REG) xr[X_REG ? j : 0][q] += alpha_f * p[j + 1][q];                   // :282
