@@ -180,6 +180,8 @@ BENCH_SIGNATURES = {
     "elph_bench_wg_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_px_info": (c_int, [Handle, P_int]),
     "elph_bench_pg_info": (c_int, [Handle, P_int, P_int, P_int, P_int, P_int]),
+    "elph_bench_pg_chunks": (c_int, [c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, P_int]),
+    "elph_bench_pg_chunk_info": (c_int, [Handle, c_int, c_int, P_int]),
     "elph_bench_slabs_info": (c_int, [Handle, c_int, P_int, P_int, P_int, P_int]),
     "elph_bench_lattice_shape": (c_int, [c_int, c_i64, c_i64, P_i64, P_dbl, P_dbl, P_int]),
     "elph_bench_wg_plan": (c_int, [c_int, c_i64, c_i64, c_i64, P_i64, P_dbl, P_dbl, c_int, c_int, P_int]),
@@ -208,6 +210,26 @@ def lattice_shape(kind, nsites, table, cosht=None, sinht=None):
     check(lib.elph_bench_lattice_shape(int(kind), int(nsites), table.shape[0], iptr(table) if table.size else None,
                                        None if c is None else dptr(c), None if s is None else dptr(s), out))
     return dict(zip(LATTICE_SHAPE_SLOTS, list(out)))
+
+
+# the kernels of elph_bench_pg_chunks / elph_bench_pg_chunk_info (elph_bench.h)
+PG_KERNELS = {"mul": 0, "cg_ap": 1, "cg_ap_px": 2}
+
+
+def pg_chunks(kernel, px, py, nw, honeycomb, nvec, ltau):
+    """(T, chunks per vector, slices of the last chunk) of one launch of a patch mat-vec kernel ("mul", "cg_ap", "cg_ap_px") of nvec vectors in the
+    launch shape (px, py, nw, honeycomb or not) on ltau time slices, under ELPH_PG_T of the environment.  Needs no device."""
+    out = (c_int * 3)()
+    check(load().elph_bench_pg_chunks(PG_KERNELS[kernel], int(px), int(py), int(nw), int(bool(honeycomb)), int(nvec), int(ltau), out))
+    return tuple(out)
+
+
+def pg_chunk_info(handle, kernel, nvec):
+    """{px, py, nw, T, chunks, last, taken}: the launch shape and the chunking this handle would take now for nvec vectors through `kernel`, and
+    whether its mat-vecs and streaming CG iteration run the patch kernels at all."""
+    out = (c_int * 7)()
+    check(load().elph_bench_pg_chunk_info(handle, PG_KERNELS[kernel], int(nvec), out))
+    return dict(zip(("px", "py", "nw", "T", "chunks", "last", "taken"), list(out)))
 
 
 # the slots of elph_bench_wg_plan's vector, in order (elph_bench.h); WG_FORMS: the numbers of its "form" slot (cg_wg.hip: wg::Form)

@@ -2023,6 +2023,24 @@ extern "C" int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, in
     return ELPH_OK;
 }
 
+// the time-axis chunking of the patch mat-vec kernels (pgrid.hip: elph_pg_chunks): from the rule's own inputs without a device, and as this handle
+// would launch nvec vectors now (pg_launch_shape's re-shaping and the pin ELPH_PG_T included)
+extern "C" int elph_bench_pg_chunks(int kernel, int px, int py, int nw, int honeycomb, int64_t nvec, int64_t ltau, int *out) {
+    if (!out || kernel < PG_K_MUL || kernel > PG_K_CG_AP_PX || px < 1 || py < 1 || nw < 1 || nvec < 1 || ltau < 1 || ltau > INT32_MAX) {
+        elph_set_error("bad argument"); return ELPH_E_ARG;
+    }
+    const PgChunks ck = elph_pg_chunks(kernel, px, py, nw, honeycomb != 0, (long long)nvec, (int)ltau);
+    out[0] = ck.T; out[1] = ck.nch; out[2] = ck.last;
+    return ELPH_OK;
+}
+extern "C" int elph_bench_pg_chunk_info(elph_handle h, int kernel, int nvec, int *out) {
+    CHECK_H(h);
+    if (!out || kernel < PG_K_MUL || kernel > PG_K_CG_AP_PX || nvec < 1) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    if (!h->shape.patch()) { elph_set_error("this handle has no patch layout"); return ELPH_E_UNSUPPORTED; }
+    elph_pg_chunk_probe(h, kernel, nvec, out);
+    return ELPH_OK;
+}
+
 // what elph_create recognises in a bond table, on a host-only handle (no device): the slots of _lib.LATTICE_SHAPE_SLOTS
 extern "C" int elph_bench_lattice_shape(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht,
                                         const double *sinht, int *out) {

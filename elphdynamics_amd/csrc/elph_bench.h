@@ -44,6 +44,16 @@ int elph_bench_px_info(elph_handle h, int *fused);
  * PX = PY = 2); the patch shape and the wavefronts per time slice; *tables = 1 when the hopping is disordered and the mat-vec / Chebyshev kernels take the patch layout with a (cosh, sinh) table in LDS. */
 int elph_bench_pg_info(elph_handle h, int *kind, int *px, int *py, int *nw, int *tables);
 
+/* The time-axis chunking of one launch of the patch mat-vec kernels (pgrid.hip: elph_pg_chunks, the one rule both launchers call).  kernel: 0 k_mul_pg,
+ * 1 k_cg_ap_pg, 2 k_cg_ap_pg<PX> (the p/x-fused iteration).  A workgroup walks T consecutive time slices of one vector; out = T, the chunks per vector,
+ * the slices of the last chunk.  ELPH_PG_T=n pins T for both kernels (read per call, clamped to [1, ltau]; unset or not a whole number: the rule).
+ * elph_bench_pg_chunks: from the rule's own inputs — the launch shape (px, py, nw, honeycomb or not), the vectors of the launch, ltau; out[3]; needs no
+ * device.  elph_bench_pg_chunk_info: what this handle would launch for nvec vectors now, out[7] = the launch shape px, py, nw (which a large fused batch
+ * re-shapes, ELPH_PG_2X2_FROM), T, chunks, last, and whether the handle's mat-vecs and streaming CG iteration take these kernels at all (0: a lane
+ * program, ELPH_NO_PG=1 or hopping disorder without a table variant keep them out); ELPH_E_UNSUPPORTED on a handle without a patch layout. */
+int elph_bench_pg_chunks(int kernel, int px, int py, int nw, int honeycomb, int64_t nvec, int64_t ltau, int *out);
+int elph_bench_pg_chunk_info(elph_handle h, int kernel, int nvec, int *out);
+
 /* What elph_create would recognise in this bond table (same table arguments; needs no device): out[16] = the small square lattice's LX, LY and its
  * DPP size (1: 8 x 8, 2: 16 x 16, else 0); the honeycomb lattice's LX, LY (cells) and whether it is 12 x 12; the patch layout's kind (0 none,
  * 1 square, 2 honeycomb, 3 triangular, 4 simple cubic: side L of the L x L x L box, PX = PY = 2 for its 2 x 2 x 2 patches), side, PX, PY and wavefronts per slice (1 without one); the GRID layout's lanes GX, GY; the honeycomb grid

@@ -707,6 +707,11 @@ bool elph_pg_ap_usable(const elph_handle_s *h);
 bool elph_pg_mw();                                          // ELPH_PG_MW: patch shapes of several wavefronts per slice allowed (pgrid.hip)
 bool elph_pg_mul_usable(const elph_handle_s *h);
 int elph_pg_mul(elph_handle_s *h, const ModelDev &m, int which, double *yS, const double *vS, int nvec);
+// the time-axis chunking of one k_mul_pg / k_cg_ap_pg launch (pgrid.hip): T slices per workgroup, nch chunks per vector, the last of `last` slices
+struct PgChunks { int T, nch, last; };
+enum { PG_K_MUL = 0, PG_K_CG_AP = 1, PG_K_CG_AP_PX = 2 };
+PgChunks elph_pg_chunks(int kernel, int px, int py, int nw, bool honeycomb, long long nvec, int L);      // pure but for the pin ELPH_PG_T
+void elph_pg_chunk_probe(const elph_handle_s *h, int kernel, int nvec, int *out);                         // out[7] = px, py, nw, T, nch, last, taken
 int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs, int parity, bool fused = false);      // fused: the p/x-fused iteration (reads the ready p)
 int elph_wg_cooldown_step(elph_handle_s *h);                // one solve of the cool-down after a time-out (both resident kernels call it)
 long long elph_shard_timeout_ms();                          // wait bound of the sharded solves (shard.hip)

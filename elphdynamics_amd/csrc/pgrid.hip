@@ -561,6 +561,47 @@ static void pg_launch_shape(const elph_handle_s *h, int nrhs, bool big, int *px,
     }
 }
 
+// The time-axis chunking of ONE launch of k_mul_pg / k_cg_ap_pg: a workgroup takes T consecutive slices of one vector; nch chunks per vector, the last
+// of `last` slices.  A pure function of its arguments and of the pin; both launchers call it after pg_launch_shape.
+//   k_cg_ap_pg (PG_K_CG_AP, PG_K_CG_AP_PX): the SHORTEST chunk whose waves still fit the chip in one round — 1024 SIMDs x the waves a SIMD holds of this
+//     instantiation (one for 12 or 16 sites per lane: 256 + ~100 registers with the prefetched slice; two for 8; cubic: px = py = 2 stands for
+//     2 x 2 x 2 = 8 registers per vector — two waves per SIMD, as the 2 x 4 square patch), a slice of several wavefronts holding as many slots — a
+//     second, partly filled round costs more than the two halo slices per chunk (measured at L = 32, 72 right-hand sides: 16 slices per wave = 720
+//     waves 98 us, 10 = 1152 waves 140 us; profiles/r04/pgrid_large_lattices.log); beyond one round of 40-slice chunks: 20
+//   k_mul_pg (PG_K_MUL): the shortest chunk with at most 2048 workgroups; beyond one round of 20-slice chunks: 20
+// ELPH_PG_T=n: the chunk length of both kernels, whatever the batch (the pin of the tests: any T at a short time axis) — read per call, here only;
+// clamped to [1, L] like the rule's own choice, so no value makes an empty or an oversized launch; unset, empty or not a whole number: the rule.
+PgChunks elph_pg_chunks(int kernel, int px, int py, int nw, bool honeycomb, long long nvec, int L) {
+    L = std::max(L, 1);
+    nw = std::max(nw, 1);
+    int T = 20;
+    if (kernel == PG_K_MUL) {
+        for (int c : {1, 2, 4, 5, 8, 10, 16, 20}) { if (nvec * ((L + c - 1) / c) <= 2048) { T = c; break; } }
+    } else {
+        const long long slots = 1024LL * ((!honeycomb && px * py <= 8) ? 2 : 1) / nw;
+        for (int c : {1, 2, 4, 5, 8, 10, 16, 20, 32, 40}) { if (nvec * ((L + c - 1) / c) <= slots) { T = c; break; } }
+    }
+    if (const char *e = getenv("ELPH_PG_T")) {
+        char *end = nullptr;
+        const long n = strtol(e, &end, 10);
+        if (end != e && *end == 0) T = (int)std::max(1L, std::min(n, (long)L));
+    }
+    T = std::max(1, std::min(T, L));
+    PgChunks ck;
+    ck.T = T; ck.nch = (L + T - 1) / T; ck.last = L - (ck.nch - 1) * T;
+    return ck;
+}
+// the launch shape and the chunking a handle would take NOW for nvec vectors through `kernel` (elph_bench_pg_chunk_info)
+void elph_pg_chunk_probe(const elph_handle_s *h, int kernel, int nvec, int *out) {
+    int px, py, nw;
+    pg_launch_shape(h, nvec, kernel == PG_K_CG_AP_PX, &px, &py, &nw);
+    const PgChunks ck = elph_pg_chunks(kernel, px, py, nw, h->shape.honeycomb(), nvec, (int)h->L);
+    // (taken: the handle's mat-vecs and streaming CG iteration run these kernels at all — elph_pg_mul_usable / elph_pg_ap_usable and, with hopping disorder, a table variant)
+    const int taken = (elph_pg_ap_usable(h) && (h->shape.hop_uniform || elph_pg_disorder_ok(h))) ? 1 : 0;
+    const int v[] = {px, py, nw, ck.T, ck.nch, ck.last, taken};
+    std::copy(std::begin(v), std::end(v), out);
+}
+
 // ELPH_NO_PG=1: the generic kernels instead of the patch layout, the A/B — read per call
 static bool no_pg() {
     const char *e = getenv("ELPH_NO_PG");
@@ -610,20 +651,12 @@ bool elph_pg_ap_usable(const elph_handle_s *h) {
 int elph_pg_cg_ap(elph_handle_s *h, const CgBufs &B, const ModelDev &m, int nrhs, int parity, bool fused) {
     if (!m.uniform && !elph_pg_disorder_ok(h)) return ELPH_E_UNSUPPORTED;
     if (B.npap != (int)h->L) { elph_set_error("k_cg_ap_pg: one p.z slot per time slice expected"); return ELPH_E_UNSUPPORTED; }
-    // slices per wave: the SHORTEST chunk whose waves still fit the chip in one round — 1024 SIMDs x the waves a SIMD holds of this
-    // instantiation (one for 12 or 16 sites per lane: 256 + ~100 registers with the prefetched slice; two for 8) — a second, partly
-    // filled round costs more than the two halo slices per chunk (measured at L = 32, 72 right-hand sides: 16 slices per wave = 720
-    // waves 98 us, 10 = 1152 waves 140 us; profiles/r04/pgrid_large_lattices.log); beyond one round of 40-slice chunks: 20
     const int L = (int)h->L;
     int px, py, nw;
     pg_launch_shape(h, nrhs, fused, &px, &py, &nw);
-    // (cubic: px = py = 2 stands for 2 x 2 x 2 = 8 registers per vector — two waves per SIMD, as the 2 x 4 square patch)
-    const long long slots = 1024LL * ((!h->shape.honeycomb() && px * py <= 8) ? 2 : 1) / nw;      // (a slice of several wavefronts holds as many slots)
-    int T = 20;
-    for (int c : {1, 2, 4, 5, 8, 10, 16, 20, 32, 40}) { if ((long long)nrhs * ((L + c - 1) / c) <= slots) { T = c; break; } }
-    T = std::max(1, std::min(T, L));
-    const int nch = (L + T - 1) / T;
-    const dim3 grid((unsigned)(nrhs * nch));
+    const PgChunks ck = elph_pg_chunks(fused ? PG_K_CG_AP_PX : PG_K_CG_AP, px, py, nw, h->shape.honeycomb(), nrhs, L);
+    const int T = ck.T;
+    const dim3 grid((unsigned)(nrhs * ck.nch));
     const int Ls = h->shape.LX;
     const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !m.uniform, [&](auto tag) {
         using LAT = typename decltype(tag)::type;
@@ -640,12 +673,11 @@ bool elph_pg_mul_usable(const elph_handle_s *h) { return elph_pg_ap_usable(h); }
 int elph_pg_mul(elph_handle_s *h, const ModelDev &m, int which, double *yS, const double *vS, int nvec) {
     if (!m.uniform && !elph_pg_disorder_ok(h)) return ELPH_E_UNSUPPORTED;
     const int L = (int)h->L, Ls = h->shape.LX;
-    int T = 20;
-    for (int c : {1, 2, 4, 5, 8, 10, 16, 20}) { if ((long long)nvec * ((L + c - 1) / c) <= 2048) { T = c; break; } }
-    T = std::max(1, std::min(T, L));
-    const dim3 grid((unsigned)(nvec * ((L + T - 1) / T)));
     int px, py, nw;
     pg_launch_shape(h, nvec, false, &px, &py, &nw);
+    const PgChunks ck = elph_pg_chunks(PG_K_MUL, px, py, nw, h->shape.honeycomb(), nvec, L);
+    const int T = ck.T;
+    const dim3 grid((unsigned)(nvec * ck.nch));
     const int rc = pg_dispatch(h->shape.patch_kind(), px, py, nw, !m.uniform, [&](auto tag) {
         using LAT = typename decltype(tag)::type;
         if (which == 0) hipLaunchKernelGGL((k_mul_pg<LAT, 0>), grid, dim3(LAT::NW * WAVE), LAT::TAB_BYTES, h->stream, yS, vS, m, Ls, T, h->d_pg_bond);
