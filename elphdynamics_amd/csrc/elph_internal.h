@@ -452,7 +452,7 @@ struct elph_handle_s {
     void *slabs = nullptr;                 // SlabSet (slabs.hip), owned: slab handles of this lattice on the same device
     bool slabs_tried = false;              // the slab decomposition was attempted (slabs == nullptr: it does not apply)
     bool is_slab = false;                  // this handle IS a slab of another handle (never decomposed again)
-    void *hmc = nullptr;                   // HmcState (hmc.hip), owned
+    void *hmc = nullptr;                   // HmcState (hmc_dev.h; hmc.hip, langevin.hip, special_updates.hip), owned by hmc.hip
     void *greens = nullptr;                // GreensState (greens.hip), owned
     // the measurement families, two slots each, owned and freed with greens: the single-configuration entry points' state (nchains = 1,
     // the estimator's own scratch) and the _chains entry points' (every resident chain, scratch of its own) — the same type, side by side
@@ -493,7 +493,7 @@ struct elph_handle_s {
 ModelDev elph_model_dev(const elph_handle_s *h);
 KpmDev elph_kpm_dev(const elph_handle_s *h);
 
-// elph_api.hip internals used by hmc.hip
+// elph_api.hip internals used by hmc.hip, langevin.hip and special_updates.hip
 int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag);
 // the solve workspace and the idioms built on it (elph_api.hip)
 int elph_work_reserve(elph_handle_s *h, int nrhs);      // room for nrhs right-hand sides in h->work (grows only; drains the stream when it does)
@@ -621,7 +621,7 @@ struct KpmSlabShape { int cbs, npl, lds_tables; size_t shm, tab; };
 constexpr int ELPH_SIDE_NPL_MAX = 6;
 KpmSlabShape elph_kpm_slab_shape(const elph_handle_s *h);
 void elph_msolve_free(elph_handle_s *h);                                    // msolve.hip
-// msolve.hip internals used by hmc.hip, greens.hip and elph_api.hip: the handle's solver kind (BiCGStab or GMRES, never CG) on
+// msolve.hip internals used by hmc.hip, langevin.hip, greens.hip and elph_api.hip: the handle's solver kind (BiCGStab or GMRES, never CG) on
 // device-resident layout-S vectors.  Both consume the h->x_zero promise of their caller (x was zeroed by the library for THIS solve).
 // ldiv!(x, model, b[, P]; maxiter) for A = M (transposed 0) or Mᵀ (1), use_prec: the Left / the Right side of the expansion
 int elph_i_mldiv_core(elph_handle_s *h, int transposed, int nrhs, int use_prec, int64_t maxiter, double *x, const double *b, int64_t *iters,

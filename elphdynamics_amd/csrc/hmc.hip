@@ -7,51 +7,13 @@
 // drives the leapfrog loop (every step ends in the CG stop test anyway), and only scalars (partial sums of S, K, the
 // solver status) come back.  The random numbers the reference draws from model.rng are inputs of the call.
 // No CPU fallback: every arithmetic step on lattice vectors is a kernel below or one of the solver's kernels.
+// Here: the state and its setters, the trajectory, and the steps it shares with langevin.hip and special_updates.hip (hmc_dev.h).
 
-#include <cmath>
-#include <cstring>
-#include <thread>
-#include <vector>
+#include "hmc_dev.h"
 
-#include "elph_internal.h"
-#include "rng_dev.h"
+using namespace hmc;
 
 namespace {
-
-constexpr int TPB = 256;
-
-struct HmcState {
-    int nch = 1;                 // chains advanced in lockstep (one phonon configuration, one trajectory each)
-    bool ssh = false;            // SSH: the fields are bond phonons (nf = Nph columns), Λ ≡ 1
-    int nf = 0;                  // phonon columns: nsites (Holstein) or Nph (SSH); field vectors are [tau][column]
-    // per chain: [nch][nf*L], layout S (tau-major) inside a chain
-    double *x = nullptr, *v = nullptr, *x0 = nullptr, *v0 = nullptr, *dS = nullptr, *y = nullptr;
-    double *R2 = nullptr;        // [2][nch][ndim] R±
-    double *phi = nullptr;       // [2][nch][ndim] ϕ±
-    double *faM = nullptr;       // FourierAccelerator.M in layout S ([k][site]), shared by the chains
-    double *par = nullptr;       // [2N] ω, ω₄   (λ, λ₂, μ are h->d_lam)
-    double *part = nullptr;      // [2 nch][L] partial sums
-    double dtau = 0.0;
-    bool have_state = false;
-    // SSH phonon types of the same name share their fields (SSHModels.jl:480-502): primary column of each column, the next
-    // member of its class (-1 ends the list) and the weight 1 (primary) / 0 of each column in Sb and K
-    bool shared = false;
-    int *prim = nullptr, *next = nullptr;
-    double *wcol = nullptr;
-    std::vector<int> prim_host;
-    // a sharded lattice with bond phonons (elph_shard_hmc_set_columns): the slab's phonon columns in the numbering of the whole lattice, which of
-    // them this rank owns (weight 1 / 0, device copy in wown) — sums over fields count owned columns, the force of the others comes from their owners
-    double *wown = nullptr;
-    std::vector<int> gcol;
-    std::vector<double> wown_host;
-    int ngcol = 0;
-    // optional generator for the random inputs the caller leaves NULL (elph_hmc_set_rng)
-    bool rng_on = false;
-    uint64_t rng_seed = 0, rng_batches = 0;
-    // scratch of elph_hmc_special_update_chains, made on first use: one allocation, carved by special_scratch
-    void *sp_buf = nullptr;
-    size_t sp_cap = 0;
-};
 
 // The build's counter-based generator (sm64, u01: rng_dev.h).
 // nvec vectors of ncols*L standard normals, written in layout S ([vec][tau][col]); the batch is numbered in the reference
@@ -193,15 +155,6 @@ __global__ void __launch_bounds__(TPB) k_hmc_dot_part(double *__restrict__ part,
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
-inline unsigned nblk(long long n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-int chk(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { elph_set_error("%s: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
-    return ELPH_OK;
-}
-
-// out[k] = a_k · b_k for `count` consecutive vectors of n elements (count <= 2 nch)
 // Shared fields (layout S: index = tau*nf + column).  k_alias_sum: every member of a class gets the class sum (muldMdx!,
 // SSHModels.jl:820-826); k_alias_copy: every column takes its primary's value (randn!, :568-575); k_mask_cols: v *= wcol.
 __global__ void __launch_bounds__(TPB) k_alias_sum(double *__restrict__ F, const int *__restrict__ prim, const int *__restrict__ next,
@@ -230,24 +183,61 @@ __global__ void __launch_bounds__(TPB) k_mask_cols(double *__restrict__ F, const
 // a sharded lattice (shard.hip: elph_shard_set_collectives): sums count this rank's own columns and are added over the ranks
 bool sharded(const elph_handle_s *h) { return h->shard != nullptr && elph_i_shard_active(h); }
 
-int dots_host(elph_handle_s *h, HmcState *st, const double *a, const double *b, long long n, int count, double *out, bool site_vectors = true) {
+// rows x per_row partials back from the device, each row added in slice order
+int read_sums(elph_handle_s *h, const double *part, int rows, int per_row, double *out) {
+    std::vector<double> p((size_t)rows * per_row);
+    HIPCHK(hipMemcpyAsync(p.data(), part, sizeof(double) * p.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sum_rows(p.data(), rows, per_row, out);
+    return ELPH_OK;
+}
+
+}  // namespace
+
+namespace hmc {
+
+int chk(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { elph_set_error("%s: %s", what, hipGetErrorString(e)); return ELPH_E_HIP; }
+    return ELPH_OK;
+}
+
+int state_ready(elph_handle_s *h, HmcState **st, bool with_field) {
+    *st = state_of(h);
+    if (!*st) { elph_set_error("elph_hmc_create / elph_langevin_create[_ssh][_chains] has not been called"); return ELPH_E_STATE; }
+    if (with_field && !(*st)->have_state) { elph_set_error("elph_hmc_set_state(x) has not been called"); return ELPH_E_STATE; }
+    return ELPH_OK;
+}
+
+int dot_parts(elph_handle_s *h, HmcState *st, double *part, const double *a, const double *b, long long n, int count, bool site_vectors) {
     const int nb = (int)h->L;
-    const long long per = (n + nb - 1) / nb;
     int ncols = 0, clo = 0, chi = 0;
     // a shard: site vectors count the own rows; field vectors of the Holstein model are site vectors; bond-phonon fields were masked by the caller
     if (sharded(h) && (site_vectors || !st->wown)) { ncols = (int)(n / h->L); elph_i_shard_own_range(h, &clo, &chi); }
-    hipLaunchKernelGGL(k_hmc_dot_part, dim3((unsigned)nb, (unsigned)count), dim3(TPB), 0, h->stream, st->part, a, b, n, per, ncols, clo, chi);
-    RC(chk("k_hmc_dot_part"));
-    std::vector<double> p((size_t)nb * count);
-    HIPCHK(hipMemcpyAsync(p.data(), st->part, sizeof(double) * p.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < count; ++k) {
-        double s = 0.0;
-        for (int q = 0; q < nb; ++q) s += p[(size_t)k * nb + q];
-        out[k] = s;
-    }
-    if (sharded(h)) RC(elph_i_shard_allreduce(h, out, count));
-    return ELPH_OK;
+    hipLaunchKernelGGL(k_hmc_dot_part, dim3((unsigned)nb, (unsigned)count), dim3(TPB), 0, h->stream, part, a, b, n, (n + nb - 1) / nb, ncols, clo, chi);
+    return chk("k_hmc_dot_part");
+}
+
+int sb_parts(elph_handle_s *h, HmcState *st, double *part) {
+    int clo = 0, chi = 1 << 30;
+    if (sharded(h) && !st->wown) elph_i_shard_own_range(h, &clo, &chi);
+    const double *w = st->wown ? st->wown : (st->shared ? st->wcol : nullptr);      // (bond phonons on a shard: the owned columns)
+    hipLaunchKernelGGL(k_hmc_sb_part, dim3((unsigned)h->L, (unsigned)st->nch), dim3(TPB), 0, h->stream, part, st->x, st->par, st->nf, (int)h->L,
+                       st->dtau, w, clo, chi);
+    return chk("k_hmc_sb_part");
+}
+
+int dots_host(elph_handle_s *h, HmcState *st, const double *a, const double *b, long long n, int count, double *out, bool site_vectors) {
+    RC(dot_parts(h, st, st->part, a, b, n, count, site_vectors));
+    RC(read_sums(h, st->part, count, (int)h->L, out));
+    return sharded(h) ? elph_i_shard_allreduce(h, out, count) : ELPH_OK;
+}
+
+int calc_Sb(elph_handle_s *h, HmcState *st, double *out) {
+    RC(sb_parts(h, st, st->part));
+    RC(read_sums(h, st->part, st->nch, (int)h->L, out));
+    for (int c = 0; c < st->nch; ++c) out[c] = st->dtau * out[c];
+    return sharded(h) ? elph_i_shard_allreduce(h, out, st->nch) : ELPH_OK;
 }
 
 int alias_sum(elph_handle_s *h, HmcState *st, double *F) {
@@ -257,24 +247,11 @@ int alias_sum(elph_handle_s *h, HmcState *st, double *F) {
     return chk("k_alias_sum");
 }
 
-int calc_Sb(elph_handle_s *h, HmcState *st, double *out) {
-    const int L = (int)h->L, nch = st->nch;
-    int clo = 0, chi = 1 << 30;
-    if (sharded(h) && !st->wown) elph_i_shard_own_range(h, &clo, &chi);
-    const double *w = st->wown ? st->wown : (st->shared ? st->wcol : nullptr);      // (bond phonons on a shard: the owned columns)
-    hipLaunchKernelGGL(k_hmc_sb_part, dim3((unsigned)L, (unsigned)nch), dim3(TPB), 0, h->stream, st->part, st->x, st->par, st->nf, L,
-                       st->dtau, w, clo, chi);
-    RC(chk("k_hmc_sb_part"));
-    std::vector<double> p((size_t)L * nch);
-    HIPCHK(hipMemcpyAsync(p.data(), st->part, sizeof(double) * p.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int c = 0; c < nch; ++c) {
-        double s = 0.0;
-        for (int q = 0; q < L; ++q) s += p[(size_t)c * L + q];
-        out[c] = st->dtau * s;
-    }
-    if (sharded(h)) RC(elph_i_shard_allreduce(h, out, nch));
-    return ELPH_OK;
+int add_dsb(elph_handle_s *h, HmcState *st, double *dS, int accumulate, const double *lam_shift) {
+    const long long n = (long long)st->nf * h->L * st->nch;
+    hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, dS, (const double *)st->x, (const double *)st->par, st->nf, (int)h->L,
+                       st->dtau, accumulate, st->nch, lam_shift);
+    return chk("k_hmc_dsb");
 }
 
 int update_model(elph_handle_s *h, HmcState *st) {
@@ -372,6 +349,40 @@ int fa(elph_handle_s *h, HmcState *st, double *out, const double *in, double pow
     return elph_launch_fft_accel(h, out, in, st->faM, power, st->nf, st->nch);
 }
 
+int randn_vectors(elph_handle_s *h, HmcState *st, double *dstS, const double *host, int nvec, int ncols) {
+    if (host) return elph_stage_in(h, dstS, host, nvec, ncols);
+    RC(need_randoms(st, false, "random inputs"));
+    const int nc = ncols > 0 ? ncols : (int)h->N;
+    const long long n = (long long)nvec * nc * h->L;
+    hipLaunchKernelGGL(k_randn_S, dim3(nblk((n + 1) / 2)), dim3(TPB), 0, h->stream, dstS, next_batch_seed(st), n, nc, (int)h->L);
+    RC(chk("k_randn_S"));
+    if (ncols > 0 && st->shared) {      // randn!(v, ssh): v = v[primary_field]  (SSHModels.jl:568-575)
+        hipLaunchKernelGGL(k_alias_copy, dim3(nblk(n)), dim3(TPB), 0, h->stream, dstS, (const int *)st->prim, nc, n);
+        RC(chk("k_alias_copy"));
+    }
+    return ELPH_OK;
+}
+
+int refresh_phi(elph_handle_s *h, HmcState *st, const double *Rp, const double *Rm) {
+    const size_t nd = (size_t)h->ndim;
+    const int nch = st->nch;                 // R2, ϕ: [sign][chain][ndim]
+    RC(randn_vectors(h, st, st->R2, Rp, nch));
+    RC(randn_vectors(h, st, st->R2 + (size_t)nch * nd, Rm, nch));
+    RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
+    if (st->ssh)        // Λ⁻¹ ≡ 1: ϕ± = MᵀR±
+        HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    else {
+        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, (const double *)h->work.b,
+                           (const double *)st->x, (const double *)h->d_lam, (int)h->N, (int)h->L, st->dtau, nch);
+        RC(chk("k_hmc_phi"));
+    }
+    return ELPH_OK;
+}
+
+}  // namespace hmc
+
+namespace {
+
 // calc_H (HMC.jl:697-705) per chain: S = Sf + Sb (:745-756,768-784), K = v·(M v)/2 (:711-719)
 int calc_H(elph_handle_s *h, HmcState *st, double *H, double *S, double *K) {
     const int nch = st->nch;
@@ -395,7 +406,6 @@ int calc_H(elph_handle_s *h, HmcState *st, double *H, double *S, double *K) {
 
 // dS/dx = dSf/dx [+ dSb/dx]; Q = M^-1 dS/dx in place  (HMC.jl:379-384)
 int force(elph_handle_s *h, HmcState *st, bool with_Sb) {
-    const long long n = (long long)st->nf * h->L * st->nch;
     if (st->ssh) {      // dSf/dx = -dMdx(M X₊, X₊) - dMdx(M X₋, X₋)  (HMC.jl:797-808; muldΛdx! is a no-op)
         RC(elph_launch_force_ssh(h, h->work.p, h->work.x, nullptr, st->nch));        // bond brackets q[chain][tau][bond] (work.p is free here)
         RC(elph_launch_ssh_scatter(h, st->dS, h->work.p, st->x, h->d_ssh_par, h->d_ssh_cb, st->nf, st->dtau, 1, -1.0, st->nch));
@@ -408,19 +418,13 @@ int force(elph_handle_s *h, HmcState *st, bool with_Sb) {
     // acceleration below are pointwise in the site index.
     if (sharded(h) && st->ssh) RC(elph_i_shard_ghost_sync_cols(h, st->dS, 1, st->nf, st->gcol.data(), st->ngcol, st->wown_host.data()));
     else if (sharded(h)) RC(elph_i_shard_ghost_sync(h, st->dS, 1));
-    if (with_Sb) {
-        hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, st->dS, st->x, st->par, st->nf, (int)h->L, st->dtau, 1,
-                           st->nch);
-        RC(chk("k_hmc_dsb"));
-    }
+    if (with_Sb) RC(add_dsb(h, st, st->dS, 1));
     return fa(h, st, st->dS, st->dS, -1.0);
 }
 
+// Q = M^-1 dSb/dx, the inner force of multitimestep_update!  (HMC.jl:528-532)
 int boson_force(elph_handle_s *h, HmcState *st) {
-    const long long n = (long long)st->nf * h->L * st->nch;
-    hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, st->dS, st->x, st->par, st->nf, (int)h->L, st->dtau, 0,
-                       st->nch);
-    RC(chk("k_hmc_dsb"));
+    RC(add_dsb(h, st, st->dS, 0));
     return fa(h, st, st->dS, st->dS, -1.0);
 }
 
@@ -430,53 +434,15 @@ int leap(elph_handle_s *h, HmcState *st, double cv, double cx) {
     return chk("k_hmc_leap");
 }
 
-HmcState *state_of(elph_handle_s *h) { return static_cast<HmcState *>(h->hmc); }
-
-// seed of the next batch: output number (batches drawn so far + 1) of SplitMix64 started at the handle's seed
-uint64_t next_batch_seed(HmcState *st) { return sm64(st->rng_seed, ++st->rng_batches); }
-
-// a random input vector set: uploaded when the caller gives it, otherwise drawn on the device (no PCIe, no host generator)
-int randn_vectors(elph_handle_s *h, HmcState *st, double *dstS, const double *host, int nvec, int ncols = 0) {
-    if (host) return elph_stage_in(h, dstS, host, nvec, ncols);
-    if (!st->rng_on) { elph_set_error("a random input is NULL and elph_hmc_set_rng has not been called"); return ELPH_E_ARG; }
-    const int nc = ncols > 0 ? ncols : (int)h->N;
-    const long long n = (long long)nvec * nc * h->L;
-    hipLaunchKernelGGL(k_randn_S, dim3(nblk((n + 1) / 2)), dim3(TPB), 0, h->stream, dstS, next_batch_seed(st), n, nc, (int)h->L);
-    RC(chk("k_randn_S"));
-    if (ncols > 0 && st->shared) {      // randn!(v, ssh): v = v[primary_field]  (SSHModels.jl:568-575)
-        hipLaunchKernelGGL(k_alias_copy, dim3(nblk(n)), dim3(TPB), 0, h->stream, dstS, (const int *)st->prim, nc, n);
-        RC(chk("k_alias_copy"));
-    }
-    return ELPH_OK;
-}
-
-// host-side batches of the same generator: Arnoldi start vectors and Metropolis uniforms the caller leaves NULL
-int randn_host(HmcState *st, std::vector<double> &out, size_t n) {
-    if (!st->rng_on) { elph_set_error("a random input is NULL and elph_hmc_set_rng has not been called"); return ELPH_E_ARG; }
-    const uint64_t seed = next_batch_seed(st);
-    const size_t m = (n + 1) / 2;
-    out.resize(n);
-    auto fill = [&](size_t k0, size_t k1) {
-        for (size_t k = k0; k < k1; ++k) {
-            const double r = sqrt(-2.0 * log(u01(seed, k))), th = 6.283185307179586476925 * u01(seed, m + k);
-            out[2 * k] = r * cos(th);
-            if (2 * k + 1 < n) out[2 * k + 1] = r * sin(th);
-        }
-    };
-    // counter-based: any split gives the same numbers.  ~20 ns per normal on one core; 64 chains x (Nt + 2) set-ups need 10^6
-    const size_t nthr = std::min<size_t>({(size_t)16, m / 16384 + 1, (size_t)std::max(1u, std::thread::hardware_concurrency())});
-    if (nthr <= 1) { fill(0, m); return ELPH_OK; }
-    std::vector<std::thread> pool;
-    for (size_t t = 0; t < nthr; ++t) pool.emplace_back(fill, m * t / nthr, m * (t + 1) / nthr);
-    for (auto &th : pool) th.join();
-    return ELPH_OK;
-}
-int uniform_host(HmcState *st, std::vector<double> &out, size_t n) {
-    if (!st->rng_on) { elph_set_error("a random input is NULL and elph_hmc_set_rng has not been called"); return ELPH_E_ARG; }
-    const uint64_t seed = next_batch_seed(st);
-    out.resize(n);
-    for (size_t k = 0; k < n; ++k) out[k] = u01(seed, k);
-    return ELPH_OK;
+// Every device allocation of the state, in one list: hmc_create_core makes those with a size, the others are made on first use (0);
+// elph_hmc_free frees them all
+struct DevAlloc { void **p; size_t bytes; };
+std::vector<DevAlloc> device_allocations(const elph_handle_s *h, HmcState *st) {
+    const size_t nd = (size_t)h->ndim * sizeof(double), nfd = (size_t)st->nf * (size_t)h->L * sizeof(double), nc = (size_t)st->nch;
+    return {{(void **)&st->x, nc * nfd}, {(void **)&st->v, nc * nfd}, {(void **)&st->x0, nc * nfd}, {(void **)&st->v0, nc * nfd},
+            {(void **)&st->dS, nc * nfd}, {(void **)&st->y, nc * nfd}, {(void **)&st->faM, nfd}, {(void **)&st->R2, 2 * nc * nd},
+            {(void **)&st->phi, 2 * nc * nd}, {(void **)&st->par, 2 * (size_t)st->nf * sizeof(double)}, {(void **)&st->part, 2 * nc * (size_t)h->L * sizeof(double)},
+            {(void **)&st->prim, 0}, {(void **)&st->next, 0}, {(void **)&st->wcol, 0}, {(void **)&st->wown, 0}, {&st->sp_buf, 0}};
 }
 
 }  // namespace
@@ -484,13 +450,7 @@ int uniform_host(HmcState *st, std::vector<double> &out, size_t n) {
 void elph_hmc_free(elph_handle_s *h) {
     HmcState *st = state_of(h);
     if (!st) return;
-    double *ptrs[] = {st->x, st->v, st->x0, st->v0, st->dS, st->y, st->R2, st->phi, st->faM, st->par, st->part};
-    for (double *p : ptrs) if (p) (void)hipFree(p);
-    if (st->prim) (void)hipFree(st->prim);
-    if (st->next) (void)hipFree(st->next);
-    if (st->wcol) (void)hipFree(st->wcol);
-    if (st->wown) (void)hipFree(st->wown);
-    if (st->sp_buf) (void)hipFree(st->sp_buf);
+    for (const DevAlloc &a : device_allocations(h, st)) if (*a.p) (void)hipFree(*a.p);
     delete st;
     h->hmc = nullptr;
 }
@@ -505,14 +465,8 @@ static int hmc_create_core(elph_handle_s *h, int nchains, int nf, bool ssh, cons
     h->hmc = st;
     st->nch = nchains; st->nf = nf; st->ssh = ssh;
     h->mu_per_chain = false;                 // a new dynamics state starts from the deck's one chemical potential
-    const size_t nd = (size_t)h->ndim, nfd = (size_t)nf * (size_t)h->L, nc = (size_t)nchains;
-    double **vecs[] = {&st->x, &st->v, &st->x0, &st->v0, &st->dS, &st->y};
-    for (double **p : vecs) HIPCHK(hipMalloc((void **)p, nc * nfd * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&st->faM, nfd * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&st->R2, 2 * nc * nd * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&st->phi, 2 * nc * nd * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&st->par, 2 * (size_t)nf * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&st->part, 2 * nc * (size_t)h->L * sizeof(double)));
+    const size_t nfd = (size_t)nf * (size_t)h->L, nc = (size_t)nchains;
+    for (const DevAlloc &a : device_allocations(h, st)) if (a.bytes) HIPCHK(hipMalloc(a.p, a.bytes));
     st->dtau = dtau;
     HIPCHK(hipMemcpyAsync(st->par, omega, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(st->par + nf, omega4, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -566,8 +520,8 @@ extern "C" int elph_hmc_create_ssh(elph_handle h, int64_t nph, const double *ome
 // x, v: double[nchains * ndim] (chain-major, reference layout inside a chain); NULL = leave
 extern "C" int elph_hmc_set_state(elph_handle h, const double *x, const double *v) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_hmc_create has not been called"); return ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
     if (x && st->shared) {      // update_model! refuses fields that differ from their primary (SSHModels.jl:549-559; isapprox)
         const size_t L = (size_t)h->L;
         for (int ch = 0; ch < st->nch; ++ch)
@@ -599,8 +553,8 @@ extern "C" int elph_hmc_set_state(elph_handle h, const double *x, const double *
 
 extern "C" int elph_hmc_get_state(elph_handle h, double *x, double *v) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_hmc_create has not been called"); return ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
     if (x) {
         RC(elph_stage_out(h, x, st->x, st->nch, st->nf));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -612,15 +566,12 @@ extern "C" int elph_hmc_get_state(elph_handle h, double *x, double *v) {
     return ELPH_OK;
 }
 
-// One HMC update of every chain, in lockstep: the leapfrog schedule is common, each chain has its own field, momenta,
-// pseudofermions, energies, Metropolis test and failure flag.  A chain whose solve fails (flag > 0, HMC.jl:405-408) is
-// dead for this update: its field is put back to x0 at once (so that its remaining — ignored — solves stay cheap) and
-// it is rejected at the end.
 // model.μ changed (the chemical-potential tuner, MuFinder.jl:68-107: μ += Δμ on every site): refresh the device copy and the model
 extern "C" int elph_hmc_set_mu(elph_handle h, const double *mu) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st || !mu) { elph_set_error(st ? "null argument" : "elph_hmc_create / elph_langevin_create has not been called"); return st ? ELPH_E_ARG : ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
+    if (!mu) { elph_set_error("null argument"); return ELPH_E_ARG; }
     const size_t N = (size_t)h->N;
     h->mu_per_chain = false;
     HIPCHK(hipMemcpyAsync(h->d_lam + (st->ssh ? 0 : 2 * N), mu, N * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -635,8 +586,9 @@ extern "C" int elph_hmc_set_mu(elph_handle h, const double *mu) {
 // the tuner with chains in lockstep: every chain its own chemical potential, mu[nchains][nsites]
 extern "C" int elph_hmc_set_mu_chains(elph_handle h, const double *mu) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st || !mu) { elph_set_error(st ? "null argument" : "elph_hmc_create / elph_langevin_create has not been called"); return st ? ELPH_E_ARG : ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
+    if (!mu) { elph_set_error("null argument"); return ELPH_E_ARG; }
     const size_t N = (size_t)h->N, nch = (size_t)st->nch;
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((int)nch > h->mu_ch_cap) {
@@ -655,8 +607,9 @@ extern "C" int elph_hmc_set_mu_chains(elph_handle h, const double *mu) {
 
 extern "C" int elph_hmc_set_shared_fields(elph_handle h, const int64_t *primary_column) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st || !st->ssh) { elph_set_error("elph_hmc_create_ssh / elph_langevin_create_ssh has not been called"); return ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
+    if (!st->ssh) { elph_set_error("elph_hmc_create_ssh / elph_langevin_create_ssh has not been called"); return ELPH_E_STATE; }
     if (!primary_column) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     const int nf = st->nf;
     std::vector<int> prim((size_t)nf), next((size_t)nf, -1), last((size_t)nf);
@@ -696,8 +649,9 @@ extern "C" int elph_hmc_set_shared_fields(elph_handle h, const int64_t *primary_
 // force — exact on the owner, where the bond bracket is — reaches the other holders of a column through the host all-reduce.
 extern "C" int elph_shard_hmc_set_columns(elph_handle h, const int64_t *global_column, int64_t n_global_columns, const double *own_weight) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st || !st->ssh) { elph_set_error("elph_hmc_create_ssh has not been called"); return ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
+    if (!st->ssh) { elph_set_error("elph_hmc_create_ssh has not been called"); return ELPH_E_STATE; }
     if (!h->shard) { elph_set_error("elph_shard_create has not been called"); return ELPH_E_STATE; }
     if (!global_column || !own_weight || n_global_columns < st->nf) { elph_set_error("bad argument"); return ELPH_E_ARG; }
     st->gcol.assign((size_t)st->nf, 0);
@@ -718,8 +672,8 @@ extern "C" int elph_shard_hmc_set_columns(elph_handle h, const int64_t *global_c
 
 extern "C" int elph_hmc_set_rng(elph_handle h, uint64_t seed) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_hmc_create / elph_langevin_create has not been called"); return ELPH_E_STATE; }
+    HmcState *st;
+    RC(state_ready(h, &st));
     st->rng_on = true;
     st->rng_seed = seed;
     st->rng_batches = 0;
@@ -734,21 +688,18 @@ extern "C" int elph_hmc_rng_batches(elph_handle h, uint64_t *batches) {
     return ELPH_OK;
 }
 
+// One HMC update of every chain, in lockstep: the leapfrog schedule is common, each chain has its own field, momenta,
+// pseudofermions, energies, Metropolis test and failure flag.  A chain whose solve fails (flag > 0, HMC.jl:405-408) is
+// dead for this update: its field is put back to x0 at once (so that its remaining — ignored — solves stay cheap) and
+// it is rejected at the end.
 extern "C" int elph_hmc_update_chains(elph_handle h, double dt, int64_t nt, int nb, double alpha, int use_precond, const double *R,
                                       const double *Rp, const double *Rm, const double *kpm_randn, const double *u_accept,
                                       int *accepted, double *iters_per_solve, double *energies, int *flag_out) {
     CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_hmc_create has not been called"); return ELPH_E_STATE; }
-    if (!st->have_state) { elph_set_error("elph_hmc_set_state(x) has not been called"); return ELPH_E_STATE; }
-    if (!accepted || nt < 0 || nb < 1 || !(alpha >= 0.0 && alpha < 1.0) || !(dt > 0.0)) {
-        elph_set_error("bad argument");
-        return ELPH_E_ARG;
-    }
-    if ((!R || !Rp || !Rm || !u_accept || (use_precond && !kpm_randn)) && !st->rng_on) {
-        elph_set_error("R, Rp, Rm, u_accept (and kpm_randn with a preconditioner) are required unless elph_hmc_set_rng was called");
-        return ELPH_E_ARG;
-    }
+    HmcState *st;
+    RC(state_ready(h, &st, true));
+    if (!accepted || nt < 0 || nb < 1 || !(alpha >= 0.0 && alpha < 1.0) || !(dt > 0.0)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
+    RC(need_randoms(st, R && Rp && Rm && u_accept && (!use_precond || kpm_randn), "R, Rp, Rm, u_accept (and kpm_randn with a preconditioner)"));
     if (use_precond && !h->kpm.created && !sharded(h)) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
     const int nch = st->nch;
     if (sharded(h)) {
@@ -764,8 +715,7 @@ extern "C" int elph_hmc_update_chains(elph_handle h, double dt, int64_t nt, int 
     }
     RC(elph_work_reserve(h, 2 * nch));
     RC(elph_i_reserve_chains(h, nch));
-    // nd: site vectors (ϕ±, R±, solutions); nfd: field vectors (x, v, dS/dx) of one chain
-    const size_t nd = (size_t)h->ndim, nfd = (size_t)st->nf * (size_t)h->L, cbytes = nfd * sizeof(double), bytes = (size_t)nch * cbytes;
+    const size_t nfd = (size_t)st->nf * (size_t)h->L, cbytes = nfd * sizeof(double), bytes = (size_t)nch * cbytes;
     const long long n = (long long)nfd * nch;
     const double dtp = dt / (double)nb;
     int64_t kpm_calls = 0;
@@ -790,26 +740,10 @@ extern "C" int elph_hmc_update_chains(elph_handle h, double dt, int64_t nt, int 
     RC(chk("k_hmc_refresh_v"));
     HIPCHK(hipMemcpyAsync(st->x0, st->x, bytes, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(st->v0, st->v, bytes, hipMemcpyDeviceToDevice, h->stream));
-    // refresh_ϕ!  (HMC.jl:665-692): ϕ± = Λ⁻¹ Mᵀ R±      (R2, ϕ: [sign][chain][ndim])
-    RC(randn_vectors(h, st, st->R2, Rp, nch));
-    RC(randn_vectors(h, st, st->R2 + (size_t)nch * nd, Rm, nch));
-    std::vector<double> kpm_own, u_own;      // generated in this order after R, R₊, R₋ when the caller left them NULL
-    if (use_precond && !kpm_randn) {
-        RC(randn_host(st, kpm_own, (size_t)(nt + 2) * 2 * (size_t)nch * (size_t)h->N));
-        kpm_randn = kpm_own.data();
-    }
-    if (!u_accept) {
-        RC(uniform_host(st, u_own, (size_t)nch));
-        u_accept = u_own.data();
-    }
-    RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
-    if (st->ssh) {      // Λ⁻¹ ≡ 1: ϕ± = MᵀR±
-        HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    } else {
-        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->work.b, st->x, h->d_lam,
-                           (int)h->N, (int)h->L, st->dtau, nch);
-        RC(chk("k_hmc_phi"));
-    }
+    RC(refresh_phi(h, st, Rp, Rm));
+    std::vector<double> kpm_own, u_own;
+    if (use_precond) RC(given_or_drawn(st, &kpm_randn, kpm_own, (size_t)(nt + 2) * 2 * (size_t)nch * (size_t)h->N, true));
+    RC(given_or_drawn(st, &u_accept, u_own, (size_t)nch, false));
     // a sharded lattice: MᵀR± is exact on the own rows only (its ghost rows would need R beyond the slab); ϕ± of the ghost rows from their owners
     if (sharded(h)) RC(elph_i_shard_ghost_sync(h, st->phi, 2));
 
@@ -890,543 +824,4 @@ extern "C" int elph_hmc_update(elph_handle h, double dt, int64_t nt, int nb, dou
     if (st && st->nch != 1) { elph_set_error("%d chains: use elph_hmc_update_chains", st->nch); return ELPH_E_STATE; }
     return elph_hmc_update_chains(h, dt, nt, nb, alpha, use_precond, R, Rp, Rm, kpm_randn, u_accept >= 0.0 ? &u_accept : nullptr, accepted, iters_per_solve,
                                   energies, flag_out);
-}
-
-
-// ==========================================================================================
-// Langevin dynamics (LangevinDynamics.jl) on the device — Holstein.  Shares the HMC state (x, scratch vectors, ω, ω₄,
-// the accelerator table, here FourierAccelerator.Q) and its helpers.
-//   calc_dSdx! = calc_dSfdx! (:350-384: one solve MᵀM x = Mᵀg — M x = g on a BiCGStab / GMRES handle —, dSf/dx = -2 gᵀ(∂M/∂x)M⁻¹g, the flag is ignored) + shifted
-//                calc_dSbdx! (:334-344)
-//   evolve!    = EulerDynamics (:81-130), RungeKuttaDynamics (:162-232), HeunsDynamics (:272-328)
-// ==========================================================================================
-
-namespace {
-
-__global__ void __launch_bounds__(TPB) k_lv_axpby(double *__restrict__ out, double a, const double *__restrict__ x, double b,
-                                                  const double *__restrict__ y, double c, const double *__restrict__ z, long long n) {
-    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-    if (i < n) out[i] = a * x[i] + b * y[i] + (z ? c * z[i] : 0.0);
-}
-
-int axpby(elph_handle_s *h, double *out, double a, const double *x, double b, const double *y, double c, const double *z, long long n) {
-    hipLaunchKernelGGL(k_lv_axpby, dim3(nblk(n)), dim3(TPB), 0, h->stream, out, a, x, b, y, c, z, n);
-    return chk("k_lv_axpby");
-}
-
-// dS (layout S) = calc_dSdx!(x; g) for every chain (g: [nch][Ndim] on the host); per-chain iteration counts and flags
-int langevin_force(elph_handle_s *h, HmcState *st, double *dS, const double *g_host, int use_precond, const double *bmax,
-                   const double *bmin, int64_t *iters, int *flag) {
-    const size_t nd = (size_t)h->ndim;
-    const int nch = st->nch;
-    RC(randn_vectors(h, st, st->R2, g_host, nch));                              // g in layout S
-    if (use_precond) RC(elph_kpm_setup_chains(h, bmax, bmin, nullptr, nullptr, nullptr, nullptr, nullptr));   // setup!(P), :366
-    HIPCHK(hipMemsetAsync(h->work.x, 0, (size_t)nch * nd * sizeof(double), h->stream));   // fill!(M⁻¹g, 0), :367
-    h->x_zero = true;
-    std::vector<double> res((size_t)nch);
-    if (h->solver_kind != ELPH_SOLVER_CG) {      // the mul_by_M branch: M x = g itself, with the Left side (:369-372)
-        RC(elph_i_mldiv_core(h, 0, nch, use_precond ? 1 : 0, 0, h->work.x, st->R2, iters, res.data(), flag));
-    } else {
-        RC(elph_launch_mul(h, 1, h->work.b, st->R2, nch));                         // Mᵀg (model.v″, :378)
-        RC(elph_i_ldiv_core(h, nch, use_precond ? 1 : 0, 0, iters, res.data(), flag));
-    }
-    const long long n = (long long)st->nf * h->L * nch;
-    if (st->ssh) {      // muldMdx!(dSfdx, g, ssh, M⁻¹g) (SSHModels.jl:707-829) with u = g given; no shifted term for bond phonons
-        RC(elph_launch_force_ssh(h, h->work.p, h->work.x, st->R2, nch));
-        RC(elph_launch_ssh_scatter(h, dS, h->work.p, st->x, h->d_ssh_par, h->d_ssh_cb, st->nf, st->dtau, 1, -2.0, nch));
-        RC(alias_sum(h, st, dS));
-        hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, dS, st->x, st->par, st->nf, (int)h->L, st->dtau, 1, nch,
-                           (const double *)nullptr);
-    } else {
-        RC(elph_launch_dmdx_holstein(h, dS, st->R2, h->work.x, st->x, st->dtau, -2.0, nch));   // -2 gᵀ(∂M/∂x)M⁻¹g, :381-384
-        hipLaunchKernelGGL(k_hmc_dsb, dim3(nblk(n)), dim3(TPB), 0, h->stream, dS, st->x, st->par, (int)h->N, (int)h->L, st->dtau, 1, nch,
-                           (const double *)h->d_lam);                           // calc_dSbdx!(dSdx, model, true), :341
-    }
-    RC(chk("k_hmc_dsb(langevin)"));
-    return ELPH_OK;
-}
-
-}  // namespace
-
-// LangevinDynamics on a Holstein handle: same arguments as elph_hmc_create, with fa_Q = FourierAccelerator.Q (evolve! calls
-// fourier_accelerate! without use_mass).  elph_hmc_set_state / elph_hmc_get_state move the field x.
-extern "C" int elph_langevin_create(elph_handle h, const double *omega, const double *omega4, const double *lambda,
-                                    const double *lambda2, const double *mu, double dtau, const double *fa_Q) {
-    return elph_hmc_create_chains(h, 1, omega, omega4, lambda, lambda2, mu, dtau, fa_Q);
-}
-
-// nchains independent Langevin trajectories of one deck in lockstep (every step one batched solve of nchains right-hand sides,
-// one KPM expansion per chain); state and random vectors are chain-major: x, eta [nchains*Ndof], g1, g2 [nchains*Ndim],
-// kpm_randn [2 set-ups][b_max|b_min][nchains][nsites]; iters, flag [nchains].
-extern "C" int elph_langevin_create_chains(elph_handle h, int nchains, const double *omega, const double *omega4, const double *lambda,
-                                           const double *lambda2, const double *mu, double dtau, const double *fa_Q) {
-    return elph_hmc_create_chains(h, nchains, omega, omega4, lambda, lambda2, mu, dtau, fa_Q);
-}
-
-// The same for an SSH handle: the arguments of elph_hmc_create_ssh with fa_Q (per phonon) in place of the mass table.
-extern "C" int elph_langevin_create_ssh(elph_handle h, int64_t nph, const double *omega, const double *omega4, const int64_t *cb_index,
-                                        const double *t_ph, const double *alpha, const double *alpha2, const double *t_bare_cb,
-                                        const double *mu, double dtau, const double *fa_Q) {
-    return elph_hmc_create_ssh(h, nph, omega, omega4, cb_index, t_ph, alpha, alpha2, t_bare_cb, mu, dtau, fa_Q);
-}
-
-// evolve!(model, dyn, fa, P): scheme 0 Euler, 1 Runge-Kutta, 2 Heun.  The random numbers the reference draws are inputs:
-// eta [Ndof] (randn!(η, model)), g1, g2 [Ndim] (the noise vectors of the first / second force estimate; g2 unused by Euler),
-// kpm_randn [2][2][nsites] (b_max, b_min of the first and second setup!(P); NULL without preconditioner).
-// iters: the count evolve! returns (Euler: the solve; RK: the second solve; Heun: div(it1 + it2, 2)); flag: last ldiv! flag
-// (the reference ignores it: a failed solve contributes M⁻¹g = 0).
-extern "C" int elph_langevin_evolve(elph_handle h, int scheme, double dt, int use_precond, const double *eta, const double *g1,
-                                    const double *g2, const double *kpm_randn, int64_t *iters, int *flag) {
-    CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_langevin_create[_ssh|_chains] has not been called on this handle"); return ELPH_E_STATE; }
-    if (!st->have_state) { elph_set_error("elph_hmc_set_state(x) has not been called"); return ELPH_E_STATE; }
-    if (scheme < 0 || scheme > 2 || !(dt > 0.0)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    if ((!eta || !g1 || (scheme > 0 && !g2) || (use_precond && !kpm_randn)) && !st->rng_on) {
-        elph_set_error("eta, g1 (g2 beyond Euler, kpm_randn with a preconditioner) are required unless elph_hmc_set_rng was called");
-        return ELPH_E_ARG;
-    }
-    if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
-    const int nch = st->nch;
-    RC(elph_work_reserve(h, std::max(2, 2 * nch)));
-    RC(elph_i_reserve_chains(h, nch));
-    const size_t N = (size_t)h->N;
-    const long long n = (long long)st->nf * h->L * nch;      // field vectors of all chains (Holstein: nch * ndim)
-    const double s2 = sqrt(2.0 * dt);
-    std::vector<double> kpm_own;             // batches are drawn in the order eta, kpm_randn, g1, g2
-    RC(update_model(h, st));
-    RC(randn_vectors(h, st, st->v, eta, nch, st->nf));
-    if (use_precond && !kpm_randn) {
-        RC(randn_host(st, kpm_own, 4 * (size_t)nch * N));
-        kpm_randn = kpm_own.data();
-    }
-    // start vectors of the two set-ups: [set-up][b_max | b_min][chain][N]
-    const double *bm1 = kpm_randn, *bn1 = kpm_randn ? kpm_randn + (size_t)nch * N : nullptr;
-    const double *bm2 = kpm_randn ? kpm_randn + 2 * (size_t)nch * N : nullptr, *bn2 = kpm_randn ? kpm_randn + 3 * (size_t)nch * N : nullptr;
-    double *F1 = st->dS, *F2 = st->y, *xi = st->v, *dx = st->v0;      // the momentum buffers are free: Langevin has none
-    std::vector<int64_t> it1((size_t)nch, 0), it2((size_t)nch, 0);
-    std::vector<int> fl((size_t)nch, 0);
-    if (scheme == 0) {
-        RC(langevin_force(h, st, F1, g1, use_precond, bm1, bn1, it1.data(), fl.data()));
-        RC(fa(h, st, F1, F1, 1.0));
-        RC(fa(h, st, xi, xi, 0.5));
-        RC(axpby(h, st->x, 1.0, st->x, s2, xi, -dt, F1, n));                       // x += √(2Δt) Q^½η − Δt Q dS/dx
-    } else if (scheme == 1) {
-        RC(langevin_force(h, st, F1, g1, use_precond, bm1, bn1, it1.data(), fl.data()));
-        RC(axpby(h, dx, s2, xi, -dt, F1, 0.0, nullptr, n));                        // Δx = √(2Δt) η − Δt dS/dx   (no acceleration)
-        RC(axpby(h, st->x, 1.0, st->x, 1.0, dx, 0.0, nullptr, n));
-        RC(update_model(h, st));
-        RC(langevin_force(h, st, F2, g2, use_precond, bm2, bn2, it2.data(), fl.data()));
-        RC(axpby(h, st->x, 1.0, st->x, -1.0, dx, 0.0, nullptr, n));                // x = x′ − Δx
-        RC(axpby(h, F1, 0.5, F2, 0.5, F1, 0.0, nullptr, n));                       // (dSdx′ + dSdx)/2
-        RC(fa(h, st, F1, F1, 1.0));
-        RC(fa(h, st, xi, xi, 0.5));
-        RC(axpby(h, st->x, 1.0, st->x, s2, xi, -dt, F1, n));
-        it1 = it2;
-    } else {
-        RC(fa(h, st, xi, xi, 0.5));                                                // ξ = Q^½η
-        RC(langevin_force(h, st, F1, g1, use_precond, bm1, bn1, it1.data(), fl.data()));
-        RC(fa(h, st, F1, F1, 1.0));                                                // dΓ/dx
-        RC(axpby(h, dx, s2, xi, -dt, F1, 0.0, nullptr, n));
-        RC(axpby(h, st->x, 1.0, st->x, 1.0, dx, 0.0, nullptr, n));
-        RC(update_model(h, st));
-        RC(langevin_force(h, st, F2, g2, use_precond, bm2, bn2, it2.data(), fl.data()));
-        RC(fa(h, st, F2, F2, 1.0));
-        RC(axpby(h, st->x, 1.0, st->x, -1.0, dx, 0.0, nullptr, n));                // x = x′ − Δx
-        RC(axpby(h, F1, 0.5, F1, 0.5, F2, 0.0, nullptr, n));                       // (dΓ + dΓ′)/2
-        RC(axpby(h, st->x, 1.0, st->x, s2, xi, -dt, F1, n));
-        for (int c = 0; c < nch; ++c) it1[(size_t)c] = (it1[(size_t)c] + it2[(size_t)c]) / 2;
-    }
-    RC(update_model(h, st));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int c = 0; c < nch; ++c) {
-        if (iters) iters[c] = it1[(size_t)c];
-        if (flag) flag[c] = fl[(size_t)c];
-    }
-    return ELPH_OK;
-}
-
-
-// ==========================================================================================
-// Special updates (SpecialUpdates.jl): one proposed move on the device-resident field of the HMC state
-// ==========================================================================================
-
-namespace {
-
-// reflect column ci (kind 0) or swap columns ci, cj (kind 1) of a tau-major field vector x[t * nf + column]
-__global__ void __launch_bounds__(TPB) k_hmc_colop(double *__restrict__ x, int nf, int L, int kind, int ci, int cj) {
-    const int t = blockIdx.x * TPB + threadIdx.x;
-    if (t >= L) return;
-    double *row = x + (size_t)t * nf;
-    if (kind == 0) row[ci] = -row[ci];
-    else { const double a = row[ci]; row[ci] = row[cj]; row[cj] = a; }
-}
-
-}  // namespace
-
-// The body of the loops of special_update! (SpecialUpdates.jl:103-136 reflection, :205-275 swap) for the single chain of an
-// HMC state created with elph_hmc_create / elph_hmc_create_ssh:
-//   S₀ = refresh_ϕ!(hmc, model, sample_R = true) — Rp, Rm are the fresh R± (HMC.jl:665-692), S₀ = (R₊² + R₋²)/2 + S_b;
-//   the move (kind 0: x_col(τ) → −x_col(τ) on column col_i; kind 1: columns col_i, col_j exchange their world lines; 0-based
-//   phonon columns = sites for Holstein), update_model!, calc_O⁻¹Λϕ!(…, 2.0), S₁ = calc_S;
-//   accepted iff u < min(1, e^{−(S₁−S₀)}) and flag == 0, otherwise the move is undone and update_model! runs again.
-// kpm_randn: b_max, b_min [2][nsites] of the one setup!(P) (NULL without preconditioner).  The choice of sites / bonds
-// (sample!(model.rng, …)) stays with the caller.  out: accepted, S₀, S₁, iterations, flag.
-extern "C" int elph_hmc_special_move_chains(elph_handle h, int kind, const int64_t *col_i, const int64_t *col_j, const double *Rp,
-                                            const double *Rm, int use_precond, const double *kpm_randn, const double *u_accept,
-                                            int *accepted, double *S0_out, double *S1_out, int64_t *iters_out, int *flag_out) {
-    CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_hmc_create[_ssh][_chains] has not been called"); return ELPH_E_STATE; }
-    if (!st->have_state) { elph_set_error("elph_hmc_set_state(x) has not been called"); return ELPH_E_STATE; }
-    const int nch = st->nch;
-    if (!accepted || !col_i || kind < 0 || kind > 1 || (kind == 1 && !col_j)) { elph_set_error("bad argument"); return ELPH_E_ARG; }
-    for (int c = 0; c < nch; ++c)
-        if (col_i[c] < 0 || col_i[c] >= st->nf || (kind == 1 && (col_j[c] < 0 || col_j[c] >= st->nf))) {
-            elph_set_error("chain %d: column outside 0..%d", c, st->nf - 1);
-            return ELPH_E_ARG;
-        }
-    if (st->shared) {
-        elph_set_error("special moves on shared fields: the reference's swap leaves the fields unequal and then stops in update_model!");
-        return ELPH_E_UNSUPPORTED;
-    }
-    if ((!Rp || !Rm || !u_accept || (use_precond && !kpm_randn)) && !st->rng_on) {
-        elph_set_error("Rp, Rm, u_accept (kpm_randn with a preconditioner) are required unless elph_hmc_set_rng was called");
-        return ELPH_E_ARG;
-    }
-    if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
-    RC(elph_work_reserve(h, 2 * nch));
-    RC(elph_i_reserve_chains(h, nch));
-    const size_t nd = (size_t)h->ndim, nfd = (size_t)st->nf * (size_t)h->L;
-    const int L = (int)h->L;
-    RC(update_model(h, st));
-    // refresh_ϕ!(…, sample_R = true) for every chain   (R2, ϕ: [sign][chain][ndim])
-    RC(randn_vectors(h, st, st->R2, Rp, nch));
-    RC(randn_vectors(h, st, st->R2 + (size_t)nch * nd, Rm, nch));
-    std::vector<double> kpm_own, u_own;      // batches in the order Rp, Rm, kpm_randn, u_accept
-    if (use_precond && !kpm_randn) {
-        RC(randn_host(st, kpm_own, 2 * (size_t)nch * (size_t)h->N));
-        kpm_randn = kpm_own.data();
-    }
-    if (!u_accept) {
-        RC(uniform_host(st, u_own, (size_t)nch));
-        u_accept = u_own.data();
-    }
-    RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
-    if (st->ssh) {
-        HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    } else {
-        hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->work.b, st->x, h->d_lam, (int)h->N, L,
-                           st->dtau, nch);
-        RC(chk("k_hmc_phi"));
-    }
-    std::vector<double> rr((size_t)2 * nch), sf((size_t)2 * nch), sb0((size_t)nch), sb1((size_t)nch);
-    RC(dots_host(h, st, st->R2, st->R2, (long long)nd, 2 * nch, rr.data()));
-    RC(calc_Sb(h, st, sb0.data()));
-    auto move = [&](const std::vector<int> &which) -> int {       // both moves are involutions: the same call undoes them
-        for (int c = 0; c < nch; ++c) {
-            if (!which[(size_t)c]) continue;
-            hipLaunchKernelGGL(k_hmc_colop, dim3((unsigned)((L + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, st->x + (size_t)c * nfd, st->nf, L,
-                               kind, (int)col_i[c], (int)(col_j ? col_j[c] : 0));
-            RC(chk("k_hmc_colop"));
-        }
-        return update_model(h, st);
-    };
-    RC(move(std::vector<int>((size_t)nch, 1)));
-    int64_t kpm_calls = 0;
-    std::vector<int64_t> iters((size_t)nch, 0);
-    std::vector<int> flag((size_t)nch, 0), undo((size_t)nch, 0);
-    RC(calc_OinvLphi(h, st, use_precond, 2.0, kpm_randn, &kpm_calls, iters.data(), flag.data()));
-    RC(dots_host(h, st, h->work.b, h->work.x, (long long)nd, 2 * nch, sf.data()));
-    RC(calc_Sb(h, st, sb1.data()));
-    bool any_undo = false;
-    for (int c = 0; c < nch; ++c) {
-        const double S0 = rr[(size_t)c] / 2 + rr[(size_t)nch + c] / 2 + sb0[(size_t)c];
-        const double S1 = sf[(size_t)c] / 2 + sf[(size_t)nch + c] / 2 + sb1[(size_t)c];
-        const double e = exp(-(S1 - S0)), P = (1.0 < e) ? 1.0 : e;
-        const int acc = (u_accept[c] < P && flag[(size_t)c] == 0) ? 1 : 0;
-        accepted[c] = acc;
-        undo[(size_t)c] = !acc;
-        any_undo = any_undo || !acc;
-        if (S0_out) S0_out[c] = S0;
-        if (S1_out) S1_out[c] = S1;
-        if (iters_out) iters_out[c] = iters[(size_t)c];
-        if (flag_out) flag_out[c] = flag[(size_t)c];
-    }
-    if (any_undo) RC(move(undo));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return ELPH_OK;
-}
-
-extern "C" int elph_hmc_special_move(elph_handle h, int kind, int64_t col_i, int64_t col_j, const double *Rp, const double *Rm,
-                                     int use_precond, const double *kpm_randn, double u_accept, int *accepted, double *S0_out,
-                                     double *S1_out, int64_t *iters_out, int *flag_out) {
-    CHECK_H(h);
-    HmcState *st = state_of(h);
-    if (!st || st->nch != 1) { elph_set_error("elph_hmc_create / elph_hmc_create_ssh (single chain) has not been called"); return ELPH_E_STATE; }
-    return elph_hmc_special_move_chains(h, kind, &col_i, &col_j, Rp, Rm, use_precond, kpm_randn, u_accept >= 0.0 ? &u_accept : nullptr,
-                                        accepted, S0_out, S1_out, iters_out, flag_out);
-}
-
-
-// ==========================================================================================
-// special_update! itself (SpecialUpdates.jl:97-366): nmoves moves of every chain in one call — the sites / bonds / phonon pairs are drawn
-// on the device from the handle's generator, the Metropolis test is decided there, nothing but the small per-move results comes back
-// ==========================================================================================
-
-namespace {
-
-// pick(u, n) = min(floor(u n), n − 1): u01 can round to 1.0
-__device__ __forceinline__ int sp_pick(double u, int n) {
-    const int k = (int)floor(u * (double)n);
-    return k < n - 1 ? k : n - 1;
-}
-
-// the draw of a reflection (:113: one phonon column) or of a Holstein swap (:248-258: the two sites of one bond): chain c uses uniform 2c
-__global__ void __launch_bounds__(TPB) k_sp_draw(int *__restrict__ ci, int *__restrict__ cj, uint64_t seed, int nch, int kind, int nf,
-                                                 int nb, const int *__restrict__ bi, const int *__restrict__ bj) {
-    const int c = blockIdx.x * TPB + threadIdx.x;
-    if (c >= nch) return;
-    const double u0 = u01(seed, 2 * (uint64_t)c);
-    if (kind == 0) {
-        const int i = sp_pick(u0, nf);
-        ci[c] = i; cj[c] = i;
-    } else {
-        const int b = sp_pick(u0, nb);
-        ci[c] = bi[b]; cj[c] = bj[b];
-    }
-}
-
-// the draw of an SSH swap (:324-328), first half: i = pick(u0, Nph) of chain blockIdx.y, and for every column q whether its world line is
-// NOT ≈ that of i (Julia's isapprox: ‖xᵢ − x_q‖ ≤ √eps max(‖xᵢ‖, ‖x_q‖)).  A lane owns a column and walks τ: the loads of a slice are
-// contiguous over the lanes, xᵢ(τ) is one address for the whole workgroup, every sum runs in the order of τ
-__global__ void __launch_bounds__(TPB) k_sp_differs(int *__restrict__ differs, const double *__restrict__ x, uint64_t seed, int nf, int L) {
-    const int c = blockIdx.y, q = blockIdx.x * TPB + threadIdx.x;
-    if (q >= nf) return;
-    const int i = sp_pick(u01(seed, 2 * (uint64_t)c), nf);
-    const double *xc = x + (size_t)c * (size_t)nf * (size_t)L;
-    double ni = 0.0, nq = 0.0, d = 0.0;
-    for (int t = 0; t < L; ++t) {
-        const double a = xc[(size_t)t * nf + i], b = xc[(size_t)t * nf + q];
-        ni += a * a;
-        nq += b * b;
-        d += (a - b) * (a - b);
-    }
-    differs[(size_t)c * nf + q] = !(sqrt(d) <= 1.4901161193847656e-08 * fmax(sqrt(ni), sqrt(nq)));
-}
-
-// second half, one workgroup per chain: D = the flagged columns in increasing order, j = D[pick(u1, |D|)], j = i when D is empty (every
-// world line ≈ xᵢ: the move is the identity).  A thread counts a contiguous segment of columns; the prefix over the threads is exact
-__global__ void __launch_bounds__(TPB) k_sp_select(int *__restrict__ ci, int *__restrict__ cj, const int *__restrict__ differs, uint64_t seed,
-                                                   int nf) {
-    __shared__ int cnt[TPB];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const int *f = differs + (size_t)c * nf;
-    const int seg = (nf + TPB - 1) / TPB;
-    const int lo = min(tid * seg, nf), hi = min(lo + seg, nf);
-    int own = 0;
-    for (int q = lo; q < hi; ++q) own += f[q];
-    cnt[tid] = own;
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < TPB; ++k) {
-        const int v = cnt[k];
-        total += v;
-        if (k < tid) before += v;
-    }
-    const int i = sp_pick(u01(seed, 2 * (uint64_t)c), nf);
-    if (tid == 0) {
-        ci[c] = i;
-        if (total == 0) cj[c] = i;
-    }
-    if (total == 0) return;
-    const int r = sp_pick(u01(seed, 2 * (uint64_t)c + 1), total);
-    if (r < before || r >= before + own) return;
-    int k = before;
-    for (int q = lo; q < hi; ++q) {
-        if (!f[q]) continue;
-        if (k == r) { cj[c] = q; return; }
-        ++k;
-    }
-}
-
-// k_hmc_colop for every chain in one launch (blockIdx.y = chain), on the columns the draw left on the device; mask: only the chains whose
-// entry is non-zero (the undo of the rejected ones), NULL: all.  Both moves are involutions
-__global__ void __launch_bounds__(TPB) k_sp_colop(double *__restrict__ x, int nf, int L, int kind, const int *__restrict__ ci,
-                                                  const int *__restrict__ cj, const int *__restrict__ mask) {
-    const int c = blockIdx.y, t = blockIdx.x * TPB + threadIdx.x;
-    if (t >= L || (mask && !mask[c])) return;
-    double *row = x + ((size_t)c * (size_t)L + (size_t)t) * (size_t)nf;
-    const int i = ci[c], j = cj[c];
-    if (kind == 0) row[i] = -row[i];
-    else if (i != j) { const double a = row[i]; row[i] = row[j]; row[j] = a; }
-}
-
-// The Metropolis test of one move, a thread per chain.  part: [6][nch][L] per-slice partials of R₊², R₋², Λϕ₊·O⁻¹Λϕ₊, Λϕ₋·O⁻¹Λϕ₋,
-// S_b/Δτ before and S_b/Δτ after, each summed here in the order of the slices (the order dots_host and calc_Sb sum them in on the host);
-// u = uniform c of batch seed_u.  Writes the undo mask and the move's row of the outputs
-__global__ void __launch_bounds__(ELPH_WAVE) k_sp_accept(const double *__restrict__ part, int nch, int L, double dtau, uint64_t seed_u,
-                                                         const int *__restrict__ flag, const int *__restrict__ ci, const int *__restrict__ cj,
-                                                         int *__restrict__ undo, int *__restrict__ acc, long long *__restrict__ out_i,
-                                                         long long *__restrict__ out_j, double *__restrict__ out_S0, double *__restrict__ out_S1) {
-#pragma clang fp contract(off)
-    const int c = blockIdx.x * ELPH_WAVE + threadIdx.x;
-    if (c >= nch) return;
-    double s[6];
-    for (int k = 0; k < 6; ++k) {
-        const double *p = part + ((size_t)k * nch + c) * (size_t)L;
-        double a = 0.0;
-        for (int q = 0; q < L; ++q) a += p[q];
-        s[k] = a;
-    }
-    const double sb0 = dtau * s[4], sb1 = dtau * s[5];
-    const double S0 = s[0] / 2 + s[1] / 2 + sb0, S1 = s[2] / 2 + s[3] / 2 + sb1;
-    const double e = exp(-(S1 - S0)), P = (1.0 < e) ? 1.0 : e;
-    const int a = (u01(seed_u, (uint64_t)c) < P && flag[c] == 0) ? 1 : 0;
-    acc[c] = a;
-    undo[c] = !a;
-    out_i[c] = ci[c];
-    out_j[c] = cj[c];
-    out_S0[c] = S0;
-    out_S1[c] = S1;
-}
-
-// the device scratch of elph_hmc_special_update_chains, carved from one allocation that only grows
-struct SpScratch {
-    double *part;                          // [6][nch][L]
-    int *differs;                          // [nch][nf] (SSH swap)
-    int *ci, *cj, *undo, *flag;            // [nch]
-    int *acc;                              // [nmoves][nch]
-    long long *out_i, *out_j;              // [nmoves][nch]
-    double *S0, *S1;                       // [nmoves][nch]
-};
-
-int special_scratch(HmcState *st, int L, size_t nmoves, bool ssh_swap, SpScratch *S) {
-    const size_t nch = (size_t)st->nch, rows = nmoves * nch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_part = take(6 * nch * (size_t)L * sizeof(double)), o_dif = take(ssh_swap ? nch * (size_t)st->nf * sizeof(int) : 0);
-    const size_t o_ci = take(nch * sizeof(int)), o_cj = take(nch * sizeof(int)), o_undo = take(nch * sizeof(int)), o_flag = take(nch * sizeof(int));
-    const size_t o_acc = take(rows * sizeof(int)), o_i = take(rows * sizeof(long long)), o_j = take(rows * sizeof(long long));
-    const size_t o_S0 = take(rows * sizeof(double)), o_S1 = take(rows * sizeof(double));
-    if (off > st->sp_cap) {
-        if (st->sp_buf) { HIPCHK(hipFree(st->sp_buf)); st->sp_buf = nullptr; st->sp_cap = 0; }
-        HIPCHK(hipMalloc(&st->sp_buf, off));
-        st->sp_cap = off;
-    }
-    char *b = static_cast<char *>(st->sp_buf);
-    S->part = reinterpret_cast<double *>(b + o_part);
-    S->differs = reinterpret_cast<int *>(b + o_dif);
-    S->ci = reinterpret_cast<int *>(b + o_ci); S->cj = reinterpret_cast<int *>(b + o_cj);
-    S->undo = reinterpret_cast<int *>(b + o_undo); S->flag = reinterpret_cast<int *>(b + o_flag);
-    S->acc = reinterpret_cast<int *>(b + o_acc);
-    S->out_i = reinterpret_cast<long long *>(b + o_i); S->out_j = reinterpret_cast<long long *>(b + o_j);
-    S->S0 = reinterpret_cast<double *>(b + o_S0); S->S1 = reinterpret_cast<double *>(b + o_S1);
-    return ELPH_OK;
-}
-
-// the per-slice partials of `count` dot products / of S_b/Δτ of every chain, left on the device ([count][L] / [nch][L])
-int dots_dev(elph_handle_s *h, double *part, const double *a, const double *b, long long n, int count) {
-    const int nb = (int)h->L;
-    hipLaunchKernelGGL(k_hmc_dot_part, dim3((unsigned)nb, (unsigned)count), dim3(TPB), 0, h->stream, part, a, b, n, (n + nb - 1) / nb, 0, 0, 0);
-    return chk("k_hmc_dot_part");
-}
-int sb_dev(elph_handle_s *h, HmcState *st, double *part) {
-    hipLaunchKernelGGL(k_hmc_sb_part, dim3((unsigned)h->L, (unsigned)st->nch), dim3(TPB), 0, h->stream, part, st->x, st->par, st->nf, (int)h->L,
-                       st->dtau, (const double *)nullptr, 0, 1 << 30);
-    return chk("k_hmc_sb_part");
-}
-
-}  // namespace
-
-// special_update!(model, hmc, ru / su, P) (SpecialUpdates.jl:97-366) for every chain of the HMC state: nmoves times the body of
-// elph_hmc_special_move_chains with the columns drawn here.  Batches of the generator per move: draw, Rp, Rm, [kpm_randn], u.
-// Draw (chain c: u0, u1 = uniforms 2c, 2c + 1 of the batch): reflection — column pick(u0, nf) (:113); Holstein swap — the two sites of
-// bond pick(u0, nbonds) of the handle's table (:248-258); SSH swap — i = pick(u0, Nph), j = D[pick(u1, |D|)] with D the columns whose
-// world line is not ≈ xᵢ, j = i when there is none (:324-328, the reference's while loop without the loop).
-// Launches and copies per move do not depend on the chain count; the outputs ([nmoves][nch]) are copied back once at the end.
-extern "C" int elph_hmc_special_update_chains(elph_handle h, int kind, int64_t nmoves, int use_precond, int *accepted, int64_t *col_i,
-                                              int64_t *col_j, double *S0_out, double *S1_out, int64_t *iters_out, int *flag_out) {
-    CHECK_H(h);
-    if (h->shard || h->is_slab) { elph_set_error("elph_hmc_special_update_chains: special moves on a sharded lattice are not supported"); return ELPH_E_UNSUPPORTED; }
-    HmcState *st = state_of(h);
-    if (!st) { elph_set_error("elph_hmc_create[_ssh][_chains] has not been called"); return ELPH_E_STATE; }
-    const int nch = st->nch, L = (int)h->L;
-    if (!accepted || kind < 0 || kind > 1 || nmoves < 1 || nmoves > (int64_t)(1 << 28) / nch) { elph_set_error("bad argument (kind 0 / 1, nmoves >= 1)"); return ELPH_E_ARG; }
-    if (st->shared) {
-        elph_set_error("special moves on shared fields: the reference's swap leaves the fields unequal and then stops in update_model!");
-        return ELPH_E_UNSUPPORTED;
-    }
-    if (!st->rng_on) { elph_set_error("elph_hmc_special_update_chains draws its moves on the device: elph_hmc_set_rng has not been called"); return ELPH_E_STATE; }
-    if (!st->have_state) { elph_set_error("elph_hmc_set_state(x) has not been called"); return ELPH_E_STATE; }
-    const bool ssh_swap = st->ssh && kind == 1;
-    if (kind == 1 && !st->ssh && h->nb < 1) { elph_set_error("a Holstein swap needs a bond"); return ELPH_E_ARG; }
-    if (use_precond && !h->kpm.created) { elph_set_error("elph_kpm_create has not been called"); return ELPH_E_STATE; }
-    RC(elph_work_reserve(h, 2 * nch));
-    RC(elph_i_reserve_chains(h, nch));
-    SpScratch S;
-    RC(special_scratch(st, L, (size_t)nmoves, ssh_swap, &S));
-    const size_t nd = (size_t)h->ndim, rows = (size_t)nmoves * (size_t)nch;
-    const dim3 col_grid((unsigned)((L + TPB - 1) / TPB), (unsigned)nch);
-    double *const p_rr = S.part, *const p_sf = S.part + 2 * (size_t)nch * L, *const p_sb0 = S.part + 4 * (size_t)nch * L, *const p_sb1 = S.part + 5 * (size_t)nch * L;
-    std::vector<int64_t> iters(rows, 0);
-    std::vector<int> flag(rows, 0);          // lives until the stream has drained: every move uploads its row
-    std::vector<double> kpm_own;
-    RC(update_model(h, st));
-    for (int64_t mv = 0; mv < nmoves; ++mv) {
-        const size_t row = (size_t)mv * (size_t)nch;
-        // the draw
-        const uint64_t seed_d = next_batch_seed(st);
-        if (ssh_swap) {
-            hipLaunchKernelGGL(k_sp_differs, dim3(nblk(st->nf), (unsigned)nch), dim3(TPB), 0, h->stream, S.differs, (const double *)st->x, seed_d, st->nf, L);
-            RC(chk("k_sp_differs"));
-            hipLaunchKernelGGL(k_sp_select, dim3((unsigned)nch), dim3(TPB), 0, h->stream, S.ci, S.cj, (const int *)S.differs, seed_d, st->nf);
-            RC(chk("k_sp_select"));
-        } else {
-            hipLaunchKernelGGL(k_sp_draw, dim3(nblk(nch)), dim3(TPB), 0, h->stream, S.ci, S.cj, seed_d, nch, kind, st->nf, (int)h->nb,
-                               (const int *)h->d_bi, (const int *)h->d_bj);
-            RC(chk("k_sp_draw"));
-        }
-        // refresh_ϕ!(…, sample_R = true) for every chain, as elph_hmc_special_move_chains: batches Rp, Rm, [kpm_randn], u
-        RC(randn_vectors(h, st, st->R2, nullptr, nch));
-        RC(randn_vectors(h, st, st->R2 + (size_t)nch * nd, nullptr, nch));
-        if (use_precond) RC(randn_host(st, kpm_own, 2 * (size_t)nch * (size_t)h->N));
-        const uint64_t seed_u = next_batch_seed(st);
-        RC(elph_launch_mul(h, 1, h->work.b, st->R2, 2 * nch));
-        if (st->ssh) {
-            HIPCHK(hipMemcpyAsync(st->phi, h->work.b, 2 * (size_t)nch * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        } else {
-            hipLaunchKernelGGL(k_hmc_phi, dim3(nblk((long long)nd * nch), 2), dim3(TPB), 0, h->stream, st->phi, h->work.b, st->x, h->d_lam, (int)h->N, L,
-                               st->dtau, nch);
-            RC(chk("k_hmc_phi"));
-        }
-        RC(dots_dev(h, p_rr, st->R2, st->R2, (long long)nd, 2 * nch));
-        RC(sb_dev(h, st, p_sb0));
-        // the move, the action after it
-        hipLaunchKernelGGL(k_sp_colop, col_grid, dim3(TPB), 0, h->stream, st->x, st->nf, L, kind, (const int *)S.ci, (const int *)S.cj, (const int *)nullptr);
-        RC(chk("k_sp_colop"));
-        RC(update_model(h, st));
-        int64_t kpm_calls = 0;
-        RC(calc_OinvLphi(h, st, use_precond, 2.0, use_precond ? kpm_own.data() : nullptr, &kpm_calls, iters.data() + row, flag.data() + row));
-        HIPCHK(hipMemcpyAsync(S.flag, flag.data() + row, (size_t)nch * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        RC(dots_dev(h, p_sf, h->work.b, h->work.x, (long long)nd, 2 * nch));
-        RC(sb_dev(h, st, p_sb1));
-        // the Metropolis test and the undo of the rejected chains
-        hipLaunchKernelGGL(k_sp_accept, dim3((unsigned)((nch + ELPH_WAVE - 1) / ELPH_WAVE)), dim3(ELPH_WAVE), 0, h->stream, (const double *)S.part, nch, L,
-                           st->dtau, seed_u, (const int *)S.flag, (const int *)S.ci, (const int *)S.cj, S.undo, S.acc + row, S.out_i + row, S.out_j + row,
-                           S.S0 + row, S.S1 + row);
-        RC(chk("k_sp_accept"));
-        hipLaunchKernelGGL(k_sp_colop, col_grid, dim3(TPB), 0, h->stream, st->x, st->nf, L, kind, (const int *)S.ci, (const int *)S.cj, (const int *)S.undo);
-        RC(chk("k_sp_colop"));
-        RC(update_model(h, st));
-    }
-    HIPCHK(hipMemcpyAsync(accepted, S.acc, rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (col_i) HIPCHK(hipMemcpyAsync(col_i, S.out_i, rows * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (col_j) HIPCHK(hipMemcpyAsync(col_j, S.out_j, rows * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (S0_out) HIPCHK(hipMemcpyAsync(S0_out, S.S0, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (S1_out) HIPCHK(hipMemcpyAsync(S1_out, S.S1, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (iters_out) memcpy(iters_out, iters.data(), rows * sizeof(int64_t));
-    if (flag_out) memcpy(flag_out, flag.data(), rows * sizeof(int));
-    return ELPH_OK;
 }

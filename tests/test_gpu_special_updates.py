@@ -228,6 +228,36 @@ def test_a_chain_of_three_decides_as_the_single_chain(kind):
         m1.close()
 
 
+@pytest.mark.parametrize("kind", [sur.SWAP, sur.REFLECT])
+def test_explicit_moves_of_three_chains_move_and_undo_per_chain(kind):
+    """special_move_chains_ on a three-chain handle without a generator and without a preconditioner: the columns are uploaded, all chains
+    move in one masked launch and the rejected ones are undone by the mask.  u = 0 accepts whenever the flag is 0 (chain 0), u = 1 can
+    never lie below min(1, ·) (chain 2 is rejected and must come back bit for bit); chain 1 of the swap gets i == j, the identity:
+    its field stays whatever its decision and S0 = S1, solved twice, to the 1e-8 this file holds an identity move to."""
+    from elphdynamics_amd import hmc, synth
+    nch = 3
+    m, H, P = _make("b", nch)
+    nf, ndim = m.Nph, m.Ndim
+    assert (m.Nsites, m.Ltau) == (16, 20)
+    X0 = _fields(m, nch)
+    _push(m, H, X0)
+    ci, cj = np.array([2, 5, 11]), np.array([9, 5, 4])
+    r = dict(Rp=synth.randn(31, nch * ndim).reshape(nch, ndim), Rm=synth.randn(32, nch * ndim).reshape(nch, ndim), kpm_randn=None,
+             u=np.array([0.0, 0.5, 1.0]))
+    acc, s0, s1, it, fl = hmc.special_move_chains_(m, H, kind, ci, cj, randoms=r)
+    X = _pull(m, H)
+    m.close()
+    print("accepted:", acc.astype(int).tolist(), " S0:", s0.tolist(), " S1:", s1.tolist(), " flags:", fl.tolist())
+    assert not fl.any()
+    assert acc[0] and np.array_equal(X[0], sur.apply_move(X0[0], kind, ci[0], cj[0], nf)) and not np.array_equal(X[0], X0[0])
+    assert not acc[2] and np.array_equal(X[2], X0[2])
+    if kind == sur.SWAP:
+        assert np.array_equal(X[1], X0[1])
+        assert abs(s0[1] - s1[1]) <= 1e-8 * abs(s0[1])
+    else:                       # a reflection has no identity: chain 1's field follows its own decision
+        assert np.array_equal(X[1], sur.apply_move(X0[1], kind, ci[1], cj[1], nf) if acc[1] else X0[1])
+
+
 @pytest.mark.parametrize("tag,kind,with_kpm", [("e", sur.SWAP, False), ("b", sur.REFLECT, True)])
 def test_the_same_seed_gives_the_same_run(tag, kind, with_kpm):
     """Deterministic reductions, no floating-point atomics: fields and every output repeat bit for bit."""
