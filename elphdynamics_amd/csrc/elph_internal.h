@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -104,7 +105,7 @@ __device__ __forceinline__ void ssh_chain_select(ModelDev &m, int rhs) {
 int elph_i_resident_wg_limit(const elph_handle_s *h);      // cg_wg.hip: workgroups of a resident kernel that can be co-resident on the handle's device
 
 // Solver parameters travel BY VALUE in the kernel arguments (never through a small H2D copy + scalar load).
-#define ELPH_SPLIT_PARTS 2    // parts of a preconditioned batch on streams of their own (elph_api.hip: SplitRun)
+#define ELPH_SPLIT_PARTS 2    // parts of a preconditioned batch on streams of their own (cg_solve.hip: SplitRun)
 
 struct CgParams {
     double tol, kmax;
@@ -220,7 +221,7 @@ __device__ __forceinline__ KpmChainView kpm_chain_view(const KpmDev &K, int rhs,
 }
 #endif
 
-// The lattice a handle's bond table holds, recognised once at elph_create by elph_recognise_lattice (elph_api.hip) in the reference's colouring
+// The lattice a handle's bond table holds, recognised once at elph_create by elph_recognise_lattice (lattice_shape.cpp) in the reference's colouring
 // (host only).  Derived facts are accessors, not fields.
 struct LatticeShape {
     enum Kind { NONE, SQUARE, HONEYCOMB, TRIANGULAR, CUBIC };     // (the values are the patch kinds of pgrid.hip)
@@ -254,7 +255,7 @@ struct LatticeShape {
 };
 
 // The KPM preconditioner of a handle (host only): elph_kpm_create's parameters, one expansion per chain, the averaged inputs and the
-// flattened tables, each with its device images.  kpm_setup_core (elph_api.hip) fills it; the planning is pure (kpm_host.cpp).
+// flattened tables, each with its device images.  kpm_setup_core (kpm_setup.hip) fills it; the planning is pure (kpm_host.cpp).
 struct KpmParams { int n = 20; double buf = 0.05, c1 = 1.0, c2 = 1.0; };
 
 // one chain's expansion (KPMExpansion, KPMPreconditioners.jl:101-146); the constructor state is order 1 and c₀ = 1 everywhere
@@ -393,7 +394,7 @@ struct SolveWork {
     // The view of the right-hand sides from r0 on (the second stream's part of a split batch).  cap_rhs stays the whole record's: it is the
     // distance of the partial-sum arrays, which are indexed [rhs][<= nrz], so one offset serves all four.  p is [2][cap_rhs][ndim]: slot 1 of
     // one part would overlap slot 0 of the next, so a view is only good for an iteration that reads and writes slot 0 alone, the p/x-fused
-    // one (elph_api.hip: split_legal demands it).  What is not per right-hand side (staging, scal, hist, phi, xfield) is shared.
+    // one (cg_solve.hip: split_legal demands it).  What is not per right-hand side (staging, scal, hist, phi, xfield) is shared.
     SolveWork part(size_t r0) const {
         SolveWork v = *this;
         v.b += r0 * ndim; v.x += r0 * ndim; v.r += r0 * ndim; v.z += r0 * ndim; v.zp += r0 * ndim; v.tmp += r0 * ndim; v.p += r0 * ndim;
@@ -424,7 +425,7 @@ struct elph_handle_s {
     bool fast_capable = false;             // lane-program kernels possible for this bond table (fast may be switched off)
     int solo_chain = -1;                   // >= 0: kernels see only this chain (single re-solve of one RHS of a chains batch)
     double *d_lam = nullptr;               // [3N] lambda, lambda2, mu staging
-    hipStream_t split_stream[ELPH_SPLIT_PARTS] = {};      // streams 1 … ways-1 + event of the split form of a preconditioned batch (elph_api.hip: SplitRun; [0] unused: the handle's own stream)
+    hipStream_t split_stream[ELPH_SPLIT_PARTS] = {};      // streams 1 … ways-1 + event of the split form of a preconditioned batch (cg_solve.hip: SplitRun; [0] unused: the handle's own stream)
     hipEvent_t split_ev = nullptr;
     CgPlan plan;                           // the kernels of the current solve's CG iteration (kernels.hip: elph_plan_cg)
     // SSH update_model! on the device (elph_update_model_ssh_fields): staging of x, per-phonon tables, slot map
@@ -493,8 +494,35 @@ struct elph_handle_s {
 ModelDev elph_model_dev(const elph_handle_s *h);
 KpmDev elph_kpm_dev(const elph_handle_s *h);
 
-// elph_api.hip internals used by hmc.hip, langevin.hip and special_updates.hip
+// ---- lattice_shape.cpp: the host half of elph_create (no device) ---------------------------------------------------------------------------
+int check_bond_table(int kind, int64_t nsites, int64_t nbonds, const int64_t *neighbor_table, const double *cosht, const double *sinht);
+// sizes, coloured bond table, Holstein hopping table, the lane program's plan and the recognised lattice, from elph_create's (checked) arguments
+void elph_i_host_handle(elph_handle_s *h, int kind, int64_t nsites, int64_t ltau, int64_t nbonds, const int64_t *neighbor_table,
+                        const double *cosht, const double *sinht);
+
+// ---- cg_solve.hip: the CG driver ------------------------------------------------------------------------------------------------------------
+// ldiv! on device-resident layout-S work.b / work.x (also hmc.hip, langevin.hip, special_updates.hip, force.hip)
 int elph_i_ldiv_core(elph_handle_s *h, int nrhs, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag);
+bool split_legal(elph_handle_s *h, int nrhs, int use_prec, bool hist);      // may this batch run as parts on streams of their own?
+// `reps` preconditioned iterations of such a batch as parts, joined on the main stream; *run keeps the parts alive (bench_hooks.hip)
+int elph_i_split_iterations(elph_handle_s *h, int nrhs, int reps, std::shared_ptr<void> *run);
+
+// ---- elph_api.hip: helpers of every host unit ------------------------------------------------------------------------------------------------
+// (re)allocates n elements (at least one) of device memory at *p
+template <class T>
+int dev_alloc(T **p, size_t n) {
+    if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+    if (n == 0) n = 1;
+    HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
+    return ELPH_OK;
+}
+int need_model(elph_handle_s *h);                  // ELPH_E_STATE before the first update_model!
+void set_nchains(elph_handle_s *h, int n);         // the resident configurations; a change invalidates the KPM expansion
+// lambda, lambda2 and (unless null) mu of a Holstein model into d_lam, stream-ordered
+int elph_i_holstein_upload_params(elph_handle_s *h, const double *lambda, const double *lambda2, const double *mu);
+// the reference's (Ltau x Nbonds) column-major tables, bt[bond][tau], <-> the device's tau-major tb[tau][bond]
+void elph_bt_to_tb(double *tb, const double *bt, size_t L, size_t nb);
+void elph_tb_to_bt(double *bt, const double *tb, size_t L, size_t nb);
 // the solve workspace and the idioms built on it (elph_api.hip)
 int elph_work_reserve(elph_handle_s *h, int nrhs);      // room for nrhs right-hand sides in h->work (grows only; drains the stream when it does)
 void elph_work_release(elph_handle_s *h);
@@ -519,7 +547,7 @@ struct TolPower {
 // what calc_O⁻¹Λϕ! returns for each of nch chains from the (iters, flag) of its + and − solve, it2 / fl2: [2][nch]: a failed first solve
 // suppresses the second (HMC.jl:880), two good ones report cld(total, 2) (:907-909)
 void elph_fold_pair(int nch, const int64_t *it2, const int *fl2, int64_t *iters, int *flag);
-// The fermion force of one configuration (update_model! + calc_O⁻¹Λϕ! + calc_dSfdx!); the entry points of elph_api.hip and shard.hip check
+// The fermion force of one configuration (update_model! + calc_O⁻¹Λϕ! + calc_dSfdx!); the entry points of force.hip and shard.hip check
 // their arguments and supply the pair solve: right-hand sides in work.b[0..1], solutions into work.x[0..1], (iters, flag) as above.
 typedef std::function<int(int64_t *iters, int *flag)> ElphPairSolve;
 // Holstein: the force is accumulated into the rows [own_lo, own_hi) of dSfdx (the whole lattice: 0, N)
@@ -541,12 +569,12 @@ int elph_i_shard_allreduce(elph_handle_s *h, double *buf, int n);
 int elph_i_shard_ghost_sync(elph_handle_s *h, double *vecS, int nvec);
 int elph_i_shard_ghost_sync_cols(elph_handle_s *h, double *vecS, int nvec, int ncols, const int *gcol, int ngcol, const double *own);
 int elph_i_shard_ldiv_dev(elph_handle_s *h, elph_handle_s *hfull, int use_prec, int64_t maxiter, int64_t *iters, double *resid, int *flag);
-int elph_i_kpm_setup_ebar(elph_handle_s *h, const double *Ebar_host, const double *b_max, const double *b_min);      // elph_api.hip
+int elph_i_kpm_setup_ebar(elph_handle_s *h, const double *Ebar_host, const double *b_max, const double *b_min);      // kpm_setup.hip
 elph_handle_s *elph_i_shard_full(const elph_handle_s *h);                  // the full-lattice handle registered with elph_shard_set_full_lattice (or nullptr)
 int elph_i_shard_global_ebar(elph_handle_s *h, std::vector<double> &Ebar_global);      // Ē of the whole lattice from every rank's own rows
 bool elph_i_shard_has_bonds(const elph_handle_s *h);                                    // elph_shard_set_bonds has been called for this slab's bonds
 int elph_i_shard_global_csbar(elph_handle_s *h, std::vector<double> &cs, int64_t *n_bonds);   // [c̄ | s̄] of every bond of the lattice from the owners' tables
-int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const double *sbar_host, const double *b_max, const double *b_min);      // elph_api.hip
+int elph_i_kpm_setup_csbar(elph_handle_s *h, const double *cbar_host, const double *sbar_host, const double *b_max, const double *b_min);      // kpm_setup.hip
 int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec, double tol_power, int64_t *iters, int *flag);
 void elph_greens_free(elph_handle_s *h);
 void elph_meas_free(elph_handle_s *h);                                      // measure.hip: the slot meas
@@ -621,7 +649,7 @@ struct KpmSlabShape { int cbs, npl, lds_tables; size_t shm, tab; };
 constexpr int ELPH_SIDE_NPL_MAX = 6;
 KpmSlabShape elph_kpm_slab_shape(const elph_handle_s *h);
 void elph_msolve_free(elph_handle_s *h);                                    // msolve.hip
-// msolve.hip internals used by hmc.hip, langevin.hip, greens.hip and elph_api.hip: the handle's solver kind (BiCGStab or GMRES, never CG) on
+// msolve.hip internals used by hmc.hip, langevin.hip, greens.hip and force.hip: the handle's solver kind (BiCGStab or GMRES, never CG) on
 // device-resident layout-S vectors.  Both consume the h->x_zero promise of their caller (x was zeroed by the library for THIS solve).
 // ldiv!(x, model, b[, P]; maxiter) for A = M (transposed 0) or Mᵀ (1), use_prec: the Left / the Right side of the expansion
 int elph_i_mldiv_core(elph_handle_s *h, int transposed, int nrhs, int use_prec, int64_t maxiter, double *x, const double *b, int64_t *iters,
@@ -775,7 +803,7 @@ KpmTables elph_kpm_tables(int L, const std::vector<KpmChain> &chains);
 // every chain of K for its bounds eb[nch][2] (e_min, e_max); rebuilds K.tab when a chain changed or K is not ready, and says so (the
 // caller then uploads the tables)
 bool elph_kpm_plan(KpmState &K, int L, const double *eb);
-void elph_kpm_free(elph_handle_s *h);      // elph_api.hip: the device buffers of h->kpm; h->kpm back to its initial state
+void elph_kpm_free(elph_handle_s *h);      // kpm_setup.hip: the device buffers of h->kpm; h->kpm back to its initial state
 int elph_kpm_arnoldi(const elph_handle_s *h, int chain, const double *b_max, const double *b_min, double *e_min,
                      double *e_max);
 int elph_hess_eigvals(std::vector<double> &a, int n, std::vector<double> &wr, std::vector<double> &wi);

@@ -538,7 +538,7 @@ static int pg_dispatch(int kind, int px, int py, int nw, bool tables, F &&launch
 // p/x-fused k_cg_ap_pg 70 -> 61, 100 -> 92, 157 -> 139; the iteration 250 -> 233, 318 -> 291, 477 -> 443, 589 -> 546; 28 x 28 at 64: 281 -> 261.  The
 // UNFUSED k_cg_ap_pg and k_mul_pg keep the handle's shape (72 right-hand sides: 184 -> 203 us the wrong way, 96: 273 -> 252).
 // `big`: a launch that may switch (the recursion, the fused k_cg_ap).  ELPH_PG_2X2_FROM=n: from n right-hand sides [48] (A/B; 0: never).
-// ELPH_PG_MW=0: one wavefront per slice, here and in the patch shape a handle chooses (elph_api.hip) — read per call
+// ELPH_PG_MW=0: one wavefront per slice, here and in the patch shape a handle chooses (lattice_shape.cpp) — read per call
 bool elph_pg_mw() {
     const char *e = getenv("ELPH_PG_MW");
     return !(e && e[0] == '0');

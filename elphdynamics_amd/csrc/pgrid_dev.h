@@ -5,7 +5,7 @@
 // workgroup of up to 1024 threads per slice, every checkerboard colour an LDS round trip and a barrier.  Here a lane holds a PX x PY
 // patch (PX, PY even): lane (X, Y) = (l % GX, l / GX), GX = L / PX, GY = L / PY, register q = cx + PX cy is the site
 // (PX X + cx) + L (PY Y + cy).  The reference's colouring of the square lattice (Checkerboard.jl:57-141 through lattice.py; recognised
-// by elph_recognise_lattice, elph_api.hip) is [x-even | x-odd | y-even | y-odd] bonds: the even colours and the inner pairs of the odd colours
+// by elph_recognise_lattice, lattice_shape.cpp) is [x-even | x-odd | y-even | y-odd] bonds: the even colours and the inner pairs of the odd colours
 // pair registers of one lane; only the patch EDGES cross — PY values per direction for x-odd, PX for y-odd, by ds_bpermute, all issued
 // before the first is used.  A 4 x 4 patch does 16 fma per colour and moves 4 + 4 values in two of the four colours: a quarter of the
 // exchange per fma of the 2 x 2 patch, and no barrier anywhere.
@@ -170,7 +170,7 @@ __device__ __forceinline__ void sweep(double (&v)[PX * PY], const Ctx &X) {
 }
 
 // ---- honeycomb: L x L two-site cells (site = 2 (x + L y) + orbital) in the reference's colouring [A-B of a cell | B(x,y)-A(x+1,y) |
-// B(x,y)-A(x,y+1)] (elph_recognise_lattice, elph_api.hip), PX x PY CELLS per lane: register q = 2 (cx + PX cy) + orbital.  A-B pairs registers
+// B(x,y)-A(x,y+1)] (elph_recognise_lattice, lattice_shape.cpp), PX x PY CELLS per lane: register q = 2 (cx + PX cy) + orbital.  A-B pairs registers
 // of the lane; the other two colours pair registers of the lane inside the patch and cross at its edge — PY resp. PX values each way.
 // No even/odd structure: any patch shape that divides L.  (Lattices of up to 16 x 16 cells have the HGRID form, cg_fast_common.h.)
 template <int PX, int PY>
@@ -233,7 +233,7 @@ __device__ __forceinline__ void hcolour(double (&v)[2 * PX * PY], const Ctx &X) 
 
 // ---- triangular: the square lattice's sites with a third bond direction (1, -1) — (x, y) - (x - 1, y + 1) — in the reference's colouring
 // [x-even | x-odd | y-even | diagonal from even y | y-odd | diagonal from odd y] (the order Checkerboard.jl's colouring gives the bond
-// definitions of examples/holstein_hmc_triangular.toml; recognised by elph_recognise_lattice, elph_api.hip).  PX x PY patches as for the
+// definitions of examples/holstein_hmc_triangular.toml; recognised by elph_recognise_lattice, lattice_shape.cpp).  PX x PY patches as for the
 // square lattice; a diagonal from an even row stays inside the patch rows (cy, cy + 1) and crosses only in x (the column cx = 0 to the
 // patch X - 1); a diagonal from the patch's LAST row goes to the patch row above: PX - 1 values from (X, Y + 1), one — the corner — from
 // (X - 1, Y + 1).
@@ -348,7 +348,7 @@ template <int PX_, int PY_> struct Tri {
 };
 // ---- simple cubic: L x L x L sites (site = x + L (y + L z)) in the reference's colouring [x-even | x-odd | y-even | y-odd | z-even | z-odd]
 // (what Checkerboard.jl's greedy colouring gives the three bond definitions (1,0,0), (0,1,0), (0,0,1) for even extents of at least 4; recognised
-// by elph_recognise_lattice, elph_api.hip: match_cubic).  A lane holds a 2 x 2 x 2 patch: lane l = the patch (X, Y, Z) = (l % G, (l / G) % G,
+// by elph_recognise_lattice, lattice_shape.cpp: match_cubic).  A lane holds a 2 x 2 x 2 patch: lane l = the patch (X, Y, Z) = (l % G, (l / G) % G,
 // l / G^2), G = L / 2; register q = cx + 2 cy + 4 cz is the site (2 X + cx) + L ((2 Y + cy) + L (2 Z + cz)).  An even colour of direction D pairs
 // the registers (q, q ^ (1 << D)) of the lane; an odd colour has no pair inside an extent of 2: the high face (bit D of q set) pairs with the low
 // face of the patch above, the low face with the high face of the patch below — four values each way, all issued before the first is used.
@@ -496,7 +496,7 @@ inline bool pick_patch_mw(int L, int *PX, int *PY, int *NW) {
 // hopping is disordered.
 inline bool patch_takes_disorder(int px, int py, int nw) {
     if (nw <= 1) return (px == 4 && py == 4) || (px == 2 && (py == 6 || py == 4));
-    return px == 2 && py == 2 && nw >= 2 && nw <= 5;      // (12 entries per thread: 24 / 36 / 48 / 60 KB; four wavefronts: disordered 28 x 28, 30 x 30 and 32 x 32, elph_api.hip: elph_recognise_lattice; five: 34 x 34)
+    return px == 2 && py == 2 && nw >= 2 && nw <= 5;      // (12 entries per thread: 24 / 36 / 48 / 60 KB; four wavefronts: disordered 28 x 28, 30 x 30 and 32 x 32, lattice_shape.cpp: elph_recognise_lattice; five: 34 x 34)
 }
 
 // The patch shape for an L x L lattice (0: none — the lattice keeps the generic kernels).

@@ -1162,7 +1162,7 @@ int elph_i_shard_solve_pair(elph_handle_s *h, elph_handle_s *hfull, int use_prec
     return ELPH_OK;
 }
 
-// The fermion force of either model on a sharded lattice: the whole-lattice entry points' steps (elph_api.hip: elph_i_force_holstein,
+// The fermion force of either model on a sharded lattice: the whole-lattice entry points' steps (force.hip: elph_i_force_holstein,
 // elph_i_force_ssh) on the slab, the two solves one after the other through the sharded kernel.  All vectors are slab vectors (own + ghost
 // rows, ghost entries filled from the global arrays).  Holstein: the force is exact on the OWN rows (the same closure argument as for
 // z = Mᵀ(M p): CB, then CBᵀ) and only those are accumulated into.

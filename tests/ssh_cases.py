@@ -6,7 +6,7 @@ SHAPES: name -> (orbitals, (L1, L2, L3), bond definitions [(o1, o2, displacement
 Size rule, written once: a case is DENSE when N * Ltau <= DENSE_LIMIT.  Dense cases are compared with the numpy.linalg
 restatement as well (on the CPU: all of them, and only them); the others are compared with the oracle alone.
 
-Which kernel family a case reaches (csrc/elph_api.hip: build_lane_program; csrc/cg_wg.hip: elph_wg_usable) — family() below:
+Which kernel family a case reaches (csrc/lattice_shape.cpp: plan_lane_program; csrc/cg_wg.hip: elph_wg_usable) — family() below:
 the lane-program kernels (k_mul_fast<NPL,WHICH,SSH>, k_force_ssh<NPL>, k_cg_*<NPL,...>) take a lattice of at most 6 colours and
 NPL = ceil(N / 64) <= 8 sites per lane; anything else the generic LDS kernels.  The matrix reaches every instantiated NPL:
   NPL 1: the small cases        NPL 2: sq12x6, sq8x16      NPL 3: sq12, tri12       NPL 4: hc10

@@ -1,4 +1,4 @@
-"""CPU test of the simple-cubic lattice recognition (elph_api.hip: match_cubic in elph_recognise_lattice) through the device-free probe
+"""CPU test of the simple-cubic lattice recognition (lattice_shape.cpp: match_cubic in elph_recognise_lattice) through the device-free probe
 elph_bench_lattice_shape, and of the 2 x 2 x 2 patch layout (pgrid_dev.h: pgrid::Cu) restated in numpy against the bond table.
 
 Recognised: the Holstein model with one (cosh, sinh) for every bond on L x L x L, L = 6, 8, 10, 12 — patch kind 4, reported as side L, PX = PY = 2

@@ -1673,7 +1673,7 @@ def test_register_exchange_k_cg_ap_of_the_fused_iteration(nchains, per, chunk_T,
 
 @pytest.mark.parametrize("tag,nchains,per,chunk_T", [("C", 32, 2, "4"), ("C", 64, 2, None), ("C", 144, 2, None), ("C", 1, 64, "4"), ("D", 64, 2, "4")])
 def test_preconditioned_batch_as_two_half_batches_on_two_streams(tag, nchains, per, chunk_T, monkeypatch):
-    """elph_ldiv_batched of a large KPM-preconditioned batch runs as two half-batches on two streams (elph_api.hip: SplitRun; default
+    """elph_ldiv_batched of a large KPM-preconditioned batch runs as two half-batches on two streams (cg_solve.hip: SplitRun; default
     from 192 right-hand sides, forced here): every right-hand side goes through the same kernels with the same partial-sum layout as in
     one stream.  With the chunk length pinned (ELPH_CHUNK_T) the two forms give the SAME BITS; with the library's own choice the
     halves may take another chunk length than the whole batch (another grouping of the p.z partial sums): iteration counts within

@@ -1,4 +1,4 @@
-"""CPU test of lattice recognition: what elph_create recognises in a bond table (elph_api.hip: elph_recognise_lattice), through the
+"""CPU test of lattice recognition: what elph_create recognises in a bond table (lattice_shape.cpp: elph_recognise_lattice), through the
 device-free probe elph_bench_lattice_shape.  The tables are built as models.py builds them; the expected vectors were recorded on the
 recogniser this probe was introduced against."""
 import functools

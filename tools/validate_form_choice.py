@@ -1,7 +1,7 @@
 """Re-times, on the box it runs on, the neighbours of every decision the library takes from fitted constants, and prints the
 disagreements: (1) un-preconditioned solves — the resident kernel's slices per wave and resident-vs-streaming (cg_wg.hip: pick_shape,
 wg_cost_table), per BASELINE config and batch size around the crossovers; (2) the KPM-preconditioned batch — slices per wave of the
-p/x-fused k_cg_ap (cg_fast_impl.inc: elph_choose_T_px) and one stream vs two half-batches (elph_api.hip: split_wanted).
+p/x-fused k_cg_ap (cg_fast_impl.inc: elph_choose_T_px) and one stream vs two half-batches (cg_solve.hip: split_wanted).
 A decision is flagged when an alternative is more than 8 % faster than what the library picks by itself.
 
     python tools/validate_form_choice.py [--quick] > profiles/rNN/validate_form_choice.log        (GPU box)
@@ -96,7 +96,7 @@ def main():
         for n in (sizes[::2] if quick else sizes):
             auto1 = child(tag, n, "prec", {"ELPH_SPLIT_STREAMS": "0"})
             auto2 = child(tag, n, "prec2", {})
-            lib_pick = auto2 if (n >= (64 if tag == "D" else 192) and auto2.get("us")) else auto1      # (elph_api.hip: split_wanted)
+            lib_pick = auto2 if (n >= (64 if tag == "D" else 192) and auto2.get("us")) else auto1      # (cg_solve.hip: split_wanted)
             alts = {}
             for T in (8, 16, 20):
                 for w in ("prec", "prec2"):
