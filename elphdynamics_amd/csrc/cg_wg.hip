@@ -419,6 +419,16 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
     };
     if constexpr (FUSED) { rr_far = uni(rr_far); y_num = uni(y_num); it_kappa = uni(it_kappa); normb = uni(normb); eps0 = uni(eps0); }
+    // RPOLL, teams of two and more: the boundary wave W-1 issues in front of its SIMD's other wave for the whole solve.  The parent's
+    // phase stamps show wave W-1 reaching the barrier in front of the meeting last; the supposed reason is that it is the younger wave
+    // of its SIMD (the arbitration's loser) AND issues the sixteen granule stores of z with their addresses and selects, while wave 0
+    // does the same stores as the older wave.  What was measured is in DESIGN.md section 3 and profiles/wg_boundary_waves.  ONE
+    // s_setprio, under a condition read as a scalar: the instruction ignores EXEC, under a lane predicate every wave would raise
+    // itself.  (Raised at the top of the mat-vec and dropped behind the first barrier instead, so that a polling wave never outranks
+    // its partner: 0.7 % SLOWER than no priority at all.)
+    if constexpr (RPOLL) {
+        if (G > 1 && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == W - 1) __builtin_amdgcn_s_setprio(1);
+    }
     STAMP_DECL;
     for (long long seq = 0;; ++seq) {
         const unsigned epoch = R.epoch0 + (unsigned)seq + (SHARD ? 2u : 1u);
@@ -715,6 +725,10 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         double rr;                                            // r.r of the NEW residual
         double alpha_f = 0.0;                                 // FUSED: alpha, for the pass behind the stop test
         double rt[RPOLL ? T : 1][NPL];                        // RPOLL: the own slices of r, read in the poll window for the pass
+        // (RPOLL INVARIANT: the pass stores the interior slices 1 .. T-2 of rl late — behind the barrier that follows it and the halo
+        //  reads, and not at all on the `done` exit.  No other wave, and no exit path, reads the interior slices of rl under RPOLL: their
+        //  only readers are this wave's own reads in the next mat-vec and poll window, in order behind its own stores.  A new reader
+        //  of rl on an exit path — as SHARD has for rg — would get stale interior slices.)
         {   // ================= the single-meeting iteration ==================================================================
         // The two meetings of the textbook iteration (p.z -> alpha; then r.r of the new residual and its boundary slices -> beta, halo
         // of p) fold into ONE: every workgroup publishes FOUR sums — p.z, r.z, z.z and the r.r of the current residual — and the
@@ -1042,13 +1056,17 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
         if constexpr (FUSED) {
             // the fused pass.  beta is made, and p is updated, whether or not this was the last iteration: past `done` nothing reads p
             // (x takes alpha p of the OLD p inside the pass), and a select per value would cost more than the update.  rho = rr0 here.
+            // (RPOLL: only the two boundary slices of r' are stored here, in front of the barrier — they are all the neighbouring waves read;
+            //  slices 1 .. T-2 are read by the wave itself, in the next mat-vec, and are stored behind the barrier and the halo reads, from
+            //  the registers of rt.  No `lwok`: every lane of this form holds sites.)
             const double beta = uni(rr / rho);
 #pragma unroll
             for (int j = 0; j < T; ++j)
 #pragma unroll
                 for (int q = 0; q < NPL; ++q) {
                     const double rn = (RPOLL ? rt[RPOLL ? j : 0][q] : rl[j * HSL + lr + q * LSL]) - alpha_f * z[j][q];     // :285
-                    if (lwok) rl[j * HSL + lr + q * LSL] = rn;
+                    if constexpr (RPOLL) { rt[RPOLL ? j : 0][q] = rn; if (j == 0 || j == T - 1) rl[j * HSL + lr + q * LSL] = rn; }
+                    else if (lwok) rl[j * HSL + lr + q * LSL] = rn;
                     if (X_GLB) { if (lwok) xg[(size_t)(t0 + j) * N + sc[q]] = xr[X_REG ? j : 0][q] + alpha_f * p[j + 1][q]; }
                     else if (X_REG) xr[X_REG ? j : 0][q] += alpha_f * p[j + 1][q];                   // :282
                     else if (lwok) xl[j * HSL + lr + q * LSL] += alpha_f * p[j + 1][q];
@@ -1136,6 +1154,13 @@ __global__ void __launch_bounds__(512) k_cg_wg(CgBufs B, ModelDev m, WgCtl R, Sh
                     p[0][q] = hl + beta * p[0][q];
                     p[T + 1][q] = hr + beta * p[T + 1][q];
                 }
+            }
+            if constexpr (RPOLL) {                            // the interior slices of r' (see the pass): behind the halo reads
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 1; j < T - 1; ++j)
+#pragma unroll
+                    for (int q = 0; q < NPL; ++q) rl[j * HSL + lr + q * LSL] = rt[RPOLL ? j : 0][q];
             }
         }
         if constexpr (!FUSED) {
